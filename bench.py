@@ -17,6 +17,9 @@ if any child did (the other ranks are then ended by their exact PIDs).  Under to
 exist and the file runs as one of them.
 
 Only the cpu_baseline leg touches oracle/ (the reference's own code compiled into oracle/_ref, timed on the host).
+
+`--dump-outputs DIR` writes what the timed path computed as DIR/<name>.npy (float64, exact; a few MB): the inputs are fixed seeds, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -162,6 +165,31 @@ def lib_sha16():
         return hashlib.sha256(open(library_path(), "rb").read()).hexdigest()[:16]
     except OSError:
         return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+NTT_DUMP_SAMPLE = 1 << 16  # elements of each transform written by --dump-outputs (a fixed, seeded sample)
+
+
+def u64_as_f64(a):
+    """uint64 limbs -> float64 pairs (low 32 bits, high 32 bits), shape a.shape + (2,): exact, so two dumps compare bit for bit"""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    return np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).astype(np.float64)
+
+
+def ntt_dump_index(n):
+    """the elements of an n-point transform that --dump-outputs keeps: the same sorted sample for every run with the same --log2n"""
+    return np.sort(np.argsort(splitmix64(0xD0D0CAFE, n), kind="stable")[:min(n, NTT_DUMP_SAMPLE)])
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy (float64), at most DUMP_LIMIT_BYTES in all"""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "dump of %d bytes exceeds the %d-byte limit" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype == np.float64, name
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def median_ms(fn, reps=10, warm=3):
@@ -386,7 +414,13 @@ def main():
                          "the reference's own per-thread slicing, and the one split where the digit kernel's work divides by N too; "
                          "rows: 1/N of the (window, point) table rows, all scalars on every rank; buckets: every rank reduces 1/N of the bucket range over all windows; "
                          "windows: whole digit windows)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes DIR/<name>.npy after the run, float64 pairs (low, high 32 bits) of the uint64 limbs: msm_result = the MSM of the last timed "
+                         "step; ntt_fft / ntt_coset_fft = the NTT leg's transform applied once to its seeded input (the leg transforms in place over and over), "
+                         "sampled at the elements ntt_sample_index names")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -687,7 +721,8 @@ def main():
     d_co = torch.from_numpy(ntt_in.view(np.int64)).to(dev)
     ntt = device_ntt_leg(G, dev, d_co, n, ("fft", "coset_fft"), args.steps, args.warmup, barrier)
     ntt_out = None
-    if cpu_leg:
+    dumping = rank == 0 and args.dump_outputs is not None
+    if cpu_leg or dumping:
         ntt_out = {}
         for kind in ("fft", "coset_fft"):
             d_chk = torch.from_numpy(ntt_in.view(np.int64)).to(dev)
@@ -914,6 +949,10 @@ def main():
             line["speedup_vs_cpu_all_cores_resident_pipelined"] = line["value"] / cb["value"]
             if "single_thread_value" in cb:
                 line["speedup_vs_cpu_1_thread_resident_pipelined"] = line["value"] / cb["single_thread_value"]
+        if dumping:
+            idx = ntt_dump_index(n)
+            dump_outputs(args.dump_outputs, {"msm_result": u64_as_f64(res), "ntt_sample_index": idx.astype(np.float64),
+                                             "ntt_fft": u64_as_f64(ntt_out["fft"][idx]), "ntt_coset_fft": u64_as_f64(ntt_out["coset_fft"][idx])})
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -85,9 +85,9 @@ def _neg(oracle, p):
     return q
 
 
-def test_host_field_code_matches_oracle():
+def test_host_field_code_matches_oracle(tmp_path):
     """fe.hpp / g1.hpp (the code the kernels run) compiled for the host and checked against the oracle"""
-    exe = "/tmp/bbgpu_test_fe_host"
+    exe = str(tmp_path / "bbgpu_test_fe_host")
     src = os.path.join(ROOT, "tests", "cpp", "test_fe_host.cpp")
     ob = os.path.join(ROOT, "oracle", "_build")
     subprocess.run(["g++", "-std=c++17", "-O1", "-o", exe, src, "-L" + ob, "-loracle", "-Wl,-rpath," + ob], check=True)
@@ -155,11 +155,11 @@ def test_transcript_reader_matches_reference_format(tmp_path):
         G.read_transcript(path, n + 5)  # more points than the file holds
 
 
-def test_shim_host_members_match_oracle(oracle):
+def test_shim_host_members_match_oracle(oracle, tmp_path):
     """the shim's host-only TU-mates (no caller on the prover path; the reference's benches and tests link them) on seeded inputs"""
     from oracle.pyoracle import FR
     subprocess.run(["make", "-C", os.path.join(ROOT, "barretenberg_amd", "shim")], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    exe = "/tmp/bbgpu_test_shim_host"
+    exe = str(tmp_path / "bbgpu_test_shim_host")
     pkg = os.path.join(ROOT, "barretenberg_amd")
     # the shim's own translation unit is compiled INTO the test with AddressSanitizer + UBSan (CPU build); plain link against libbbshim.so if the image has no sanitizer runtime
     san = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-o", exe,
@@ -240,46 +240,52 @@ def test_shim_host_members_match_oracle(oracle):
         assert np.array_equal(oracle.g1_normalize(p)[:8], np.array([int(x, 16) for x in r[2:10]], dtype=np.uint64)), (i, j)
 
 
-def test_shim_covers_the_replaced_translation_units():
+def test_shim_covers_the_replaced_translation_units(golden):
     """INTEGRATION recipe A replaces two whole translation units: every extern of polynomial_arithmetic.o is defined by the shim, and
-    and every extern of scalar_multiplication.o (the CPU algorithm's own machinery and the precomputed family as host code).  Compared against the reference objects compiled in place (oracle/_ref/obj; skipped where absent)."""
+    and every extern of scalar_multiplication.o (the CPU algorithm's own machinery and the precomputed family as host code).  The externs are those of
+    tests/golden/reference_build.json (tools/gen_ref_build_golden.py), which must equal the reference objects compiled in place (oracle/_ref/obj) where they are built."""
+    want = {k: set(v) for k, v in golden("reference_build.json")["externs"].items()}
     obj = os.path.join(ROOT, "oracle", "_ref", "obj")
     pa, sm = os.path.join(obj, "polynomials", "polynomial_arithmetic.o"), os.path.join(obj, "curves", "bn254", "scalar_multiplication.o")
-    if not (os.path.exists(pa) and os.path.exists(sm)):
-        pytest.skip("reference objects not built here")
 
     def externs(path, dynamic=False):
         out = subprocess.run(["nm"] + (["-D"] if dynamic else []) + ["--defined-only", path], capture_output=True, text=True, check=True).stdout
         return {l.split()[2] for l in out.splitlines() if len(l.split()) == 3 and l.split()[1] == "T" and "barretenberg" in l.split()[2]}
 
+    if os.path.exists(pa) and os.path.exists(sm):
+        assert externs(pa) == want["polynomial_arithmetic"] and externs(sm) == want["scalar_multiplication"], "stale fixture: rerun tools/gen_ref_build_golden.py"
     shim = externs(os.path.join(ROOT, "barretenberg_amd", "libbbshim.so"), dynamic=True)
-    assert externs(pa) <= shim, sorted(externs(pa) - shim)
-    assert externs(sm) <= shim, sorted(externs(sm) - shim)  # since round 2 incl. the CPU algorithm's own machinery and the precomputed family
+    assert want["polynomial_arithmetic"] <= shim, sorted(want["polynomial_arithmetic"] - shim)
+    assert want["scalar_multiplication"] <= shim, sorted(want["scalar_multiplication"] - shim)  # since round 2 incl. the CPU algorithm's own machinery and the precomputed family
 
 
-def test_transcript_writer_matches_the_reference_writer(lib, oracle, tmp_path):
+def test_transcript_writer_matches_the_reference_writer(lib, oracle, golden, tmp_path):
     """bbgpu_transcript_write (io.hpp:36-182 restated for writing, G2 half computed by csrc/host_g2.hpp) against the file the
     REFERENCE's own code wrote for the same secret (oracle/_ref/transcript.dat <- g1/g2::group_exponentiation in plonk_cpu): the G1
     bytes of the shared prefix and both G2 points -- x * G2 is the verifier's pairing input -- must be identical; and our reader
-    reads our file back."""
+    reads our file back.  The reference file's bytes are those of tests/golden/reference_build.json (tools/gen_ref_build_golden.py), which must
+    describe oracle/_ref/transcript.dat where that is built."""
+    import hashlib
     from oracle.pyoracle import FR
+    ref = golden("reference_build.json")["transcript"]
     ref_file = os.path.join(ROOT, "oracle", "_ref", "transcript.dat")
-    if not os.path.exists(ref_file):
-        pytest.skip("reference-written transcript not built here")
+    if os.path.exists(ref_file):
+        data = open(ref_file, "rb").read()
+        num = int.from_bytes(data[16:20], "big")
+        assert (data[0:28].hex(), hashlib.sha256(data[28:28 + 64 * ref["g1_prefix_points"]]).hexdigest(), data[28 + 64 * num:][:256].hex()) == \
+            (ref["manifest_hex"], ref["g1_prefix_sha256"], ref["g2_hex"]), "stale fixture: rerun tools/gen_ref_build_golden.py"
     secret_raw = np.array([0x0123456789abcdef, 0xfedcba9876543210, 0x0f1e2d3c4b5a6978, 0x0123456789abcdef], dtype=np.uint64)  # oracle/plonk_driver.cpp secret()
     x = oracle.to_mont(FR, secret_raw)
     degree = 1025
     table = oracle.point_table(oracle.make_srs(x, degree))
     path = str(tmp_path / "transcript.dat")
     lib.write_transcript(path, table, degree, x)
-    ours, ref = open(path, "rb").read(), open(ref_file, "rb").read()
-    assert len(ours) == 28 + 64 * (degree - 1) + 256 + 64
-    num_ref = int.from_bytes(ref[16:20], "big")
+    ours, manifest = open(path, "rb").read(), bytes.fromhex(ref["manifest_hex"])
+    assert len(ours) == 28 + 64 * (degree - 1) + 256 + 64 and ref["g1_prefix_points"] == degree - 1
     assert int.from_bytes(ours[16:20], "big") == degree - 1 and int.from_bytes(ours[8:12], "big") == degree - 1
-    assert ours[0:8] == ref[0:8] and ours[12:16] == ref[12:16] and ours[20:28] == ref[20:28]  # numbers / G2 counts / start_from
-    assert ours[28:28 + 64 * (degree - 1)] == ref[28:28 + 64 * (degree - 1)]                   # x G .. x^1024 G
-    g2_ours, g2_ref = ours[28 + 64 * (degree - 1):][:256], ref[28 + 64 * num_ref:][:256]
-    assert g2_ours == g2_ref                                                                   # G2, x G2
+    assert ours[0:8] == manifest[0:8] and ours[12:16] == manifest[12:16] and ours[20:28] == manifest[20:28]  # numbers / G2 counts / start_from
+    assert hashlib.sha256(ours[28:28 + 64 * (degree - 1)]).hexdigest() == ref["g1_prefix_sha256"]            # x G .. x^1024 G
+    assert ours[28 + 64 * (degree - 1):][:256].hex() == ref["g2_hex"]                                        # G2, x G2
     assert np.array_equal(lib.read_transcript(path, degree), table)
 
 
@@ -305,6 +311,28 @@ def test_bench_input_generator_is_splitmix64():
         assert [int(v) for v in sc[i]] == want[4 * i:4 * i + 3] + [want[4 * i + 3] & 0x0FFFFFFFFFFFFFFF]
     assert all(sum(int(v) << (64 * k) for k, v in enumerate(s)) < (1 << 252) for s in sc)
     assert [int(v) for v in bench.limbs_of(pow(2, 512, bench.FR_MODULUS))] == [0x1BB8E645AE216DA7, 0x53FE3AB1E35C59E3, 0x8C49833D53BB8085, 0x0216D0B17F4E44A5]  # fr.hpp:49-52 r_squared
+
+
+def test_bench_dump_outputs_are_exact_and_bounded(tmp_path):
+    """bench.py --dump-outputs: uint64 limbs survive the float64 encoding exactly, the NTT sample is the same fixed set of distinct elements every
+    time, and the files of a 2^20 run stay under the 64 MB limit"""
+    import bench
+    a = np.array([0, 1, 0xFFFFFFFF, 1 << 32, 0xFFFFFFFFFFFFFFFF, 0x30644E72E131A029], dtype=np.uint64)
+    f = bench.u64_as_f64(a)
+    assert f.dtype == np.float64 and f.shape == (6, 2)
+    assert [int(lo) | (int(hi) << 32) for lo, hi in f] == [int(v) for v in a]
+    n = 1 << 20
+    idx = bench.ntt_dump_index(n)
+    assert np.array_equal(idx, bench.ntt_dump_index(n)) and idx.shape == (bench.NTT_DUMP_SAMPLE,)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(bench.ntt_dump_index(64), np.arange(64))
+    limbs = bench.raw_scalars(n, 0xF00D)[idx]
+    arrays = {"msm_result": bench.u64_as_f64(np.arange(12, dtype=np.uint64)), "ntt_sample_index": idx.astype(np.float64),
+              "ntt_fft": bench.u64_as_f64(limbs), "ntt_coset_fft": bench.u64_as_f64(limbs)}
+    bench.dump_outputs(str(tmp_path / "out"), arrays)
+    assert sum(os.path.getsize(tmp_path / "out" / (k + ".npy")) for k in arrays) <= bench.DUMP_LIMIT_BYTES
+    for k, v in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "out" / (k + ".npy")), v)
 
 
 def test_shipped_kernels_read_no_result_changing_variable():
