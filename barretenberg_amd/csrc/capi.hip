@@ -294,7 +294,7 @@ void read_host_env()
     if (staging_read) return;
     staging_read = true;
     if (const char* e = getenv("BBGPU_STAGE_MAX_BYTES")) g_ctx.host_stage_max = (size_t)strtoull(e, nullptr, 0);
-    if (const char* e = getenv("BBGPU_STAGE_CHUNK_BYTES")) g_ctx.host_chunk = std::min(Context::HOST_CHUNK, std::max((size_t)64 << 10, (size_t)strtoull(e, nullptr, 0))); // tuning knob
+    if (const char* e = getenv("BBGPU_STAGE_CHUNK_BYTES")) g_ctx.host_chunk = std::min(Context::HOST_CHUNK, std::max((size_t)64 << 10, (size_t)strtoull(e, nullptr, 0))); // testing hook: the chunk size of the staging copies
 }
 
 int ensure_init()
@@ -541,7 +541,7 @@ int add_srs(const uint64_t* host_ptr, size_t n, uint32_t* d_srs, bool auto_regis
     // ... but a slice of fewer than 2^18 points pays the row / column sums over 2^16 buckets for ~30 entries per bucket: 16-bit windows (2^15 buckets, one window
     // more) measured 0.179 against 0.182 ms per step at 2^17 points, four in flight, three alternating runs (15-bit windows: 0.189)
     if (g_ctx.point_world > 1 && c == 17 && n < ((size_t)1 << 18)) c = 16;
-    if (const char* ev = getenv("BBGPU_TABLE_C")) c = std::min(17, std::max(4, atoi(ev))); // tuning knob: window size of the tables
+    if (const char* ev = getenv("BBGPU_TABLE_C")) c = std::min(17, std::max(4, atoi(ev))); // window size of the tables
     const int W = msm_num_windows(c);
     // segments: as few as the 24-bit row index allows, equal lengths (multiples of 8: the sort reads eight digits per load).  One up to 2^20 points;
     // beyond that the tables are kept up to BBGPU_TABLE_MAX_BYTES (default 64 GiB = 2^26 points) -- larger tables fall back to per-window bucket sets
@@ -1040,8 +1040,8 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
             // own sort and bucket-reduction tail (~0.3 ms of launches that only partly hide), so two it is, the first one the smaller: its
             // upload is the part nothing hides, and the second range's upload (0.6 ms x its share) still fits under the first one's kernels.
             const size_t parts = ns < 2 ? 1 : (split_env ? split_env : (n >= ((size_t)1 << 19) ? 2 : 1));
-            static const size_t first_pct = [] { const char* v = getenv("BBGPU_HOST_MSM_FIRST_PCT"); return v ? (size_t)std::min(50, std::max(5, atoi(v))) : (size_t)0; }(); // tuning knob; measured 25 / 30 / 34 / 37 / 42 %: 1.84 / 1.80 / 1.83 / 1.775 / 1.79 ms
-            const size_t base = parts == 2 ? (((first_pct ? n * first_pct / 100 : n * 3 / 8)) & ~(size_t)7) : n / parts;
+            // first range 3/8 of the points; measured 25 / 30 / 34 / 37 / 42 %: 1.84 / 1.80 / 1.83 / 1.775 / 1.79 ms
+            const size_t base = parts == 2 ? ((n * 3 / 8) & ~(size_t)7) : n / parts;
             for (size_t k = 0; k < parts; k++) {
                 const size_t o = k * base, len = (k + 1 == parts) ? n - o : base;
                 if (len) ranges.push_back(Range{ o, len });

@@ -43,13 +43,8 @@ using Fr = FrP;
 // 0.23 ms to ~1.07 ms, and end a few tens of microseconds after it -- the next accumulation waits for them.  Priority 2 (above the
 // accumulation's 0, below the tail kernels' 3) lets them finish in time: measured 1.400 -> 1.382 ms/step at 2^20 and 0.318 -> 0.305 ms
 // for the 2-window share of an 8-way split (tools/msm_ab.py, A/B in one box; priority 3 is no better).
-#ifndef BBGPU_FRONT_PRIO
-#define BBGPU_FRONT_PRIO 2
-#endif
-#define FRONT_PRIO() __builtin_amdgcn_s_setprio(BBGPU_FRONT_PRIO)
-#ifndef BBGPU_TAIL_PRIO
-#define BBGPU_TAIL_PRIO 3 // the tail kernels' wave priority (short dependent chains); A/B builds: -DBBGPU_TAIL_PRIO=0 .. 3
-#endif
+#define FRONT_PRIO() __builtin_amdgcn_s_setprio(2)
+constexpr int TAIL_PRIO = 3; // the tail kernels' wave priority (short dependent chains)
 constexpr int SCALAR_BITS = 254; // r < 2^254 (fr.hpp:12-15)
 constexpr int MSM_MAX_C = 16;    // largest window without tables (one bucket set per window); digits stored as int16
 // (with tables, one shared bucket set: up to 17-bit windows -> 15 of them at 2^20, digits stored as uint16 magnitude + sign bit; capi.hip picks the width)
@@ -672,67 +667,8 @@ template <class DT> __global__ void __launch_bounds__(SORT_THREADS) __attribute_
     }
 }
 
-// pass B: one workgroup per (bin, window): counting sort by `lo`, emits the final entries and the global bucket starts
-__global__ void __launch_bounds__(SORT_THREADS) sortB_kernel(const uint32_t* __restrict__ tmp, const uint32_t* __restrict__ binstart,
-                                                   const uint32_t* __restrict__ bases, uint32_t* __restrict__ sorted, uint32_t* __restrict__ gstart,
-                                                   uint32_t bins, uint32_t lb, uint32_t nb)
-{
-    FRONT_PRIO();
-    __shared__ uint32_t cnt[128];
-    __shared__ uint32_t cur[128];
-    const uint32_t bin = blockIdx.x, wl = blockIdx.y, t = threadIdx.x;
-    const uint32_t nlo = 1u << lb;
-    const uint32_t start = bases[wl] + binstart[(size_t)wl * bins + bin];
-    const uint32_t end = (bin + 1 < bins) ? bases[wl] + binstart[(size_t)wl * bins + bin + 1] : bases[wl + 1];
-    if (t < 128) cnt[t] = 0;
-    __syncthreads();
-    // eight independent loads per lane and trip (a lane's entries are blockDim apart: every load of the wave is one coalesced run)
-    constexpr int UB = 8;
-    for (uint32_t e0 = start + t; e0 < end; e0 += UB * blockDim.x) {
-        uint32_t v[UB];
-#pragma unroll
-        for (int k = 0; k < UB; k++) {
-            const uint32_t e = e0 + k * blockDim.x;
-            v[k] = e < end ? tmp[e] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < UB; k++)
-            if (e0 + k * blockDim.x < end) atomicAdd(&cnt[(v[k] >> 24) & 0x7f], 1u);
-    }
-    __syncthreads();
-    if (t < 64) { // exclusive scan of the <= 128 counters by one wave, two counters per lane
-        const uint32_t a = cnt[2 * t], b2 = cnt[2 * t + 1], sum = a + b2;
-        uint32_t incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off);
-            if ((int)t >= off) incl += o;
-        }
-        cur[2 * t] = start + incl - sum;
-        cur[2 * t + 1] = start + incl - sum + a;
-    }
-    __syncthreads();
-    if (t < nlo) gstart[(size_t)wl * nb + (size_t)bin * nlo + t] = cur[t];
-    __syncthreads();
-    for (uint32_t e0 = start + t; e0 < end; e0 += UB * blockDim.x) {
-        uint32_t v[UB];
-#pragma unroll
-        for (int k = 0; k < UB; k++) {
-            const uint32_t e = e0 + k * blockDim.x;
-            v[k] = e < end ? tmp[e] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < UB; k++) {
-            if (e0 + k * blockDim.x < end) {
-                const uint32_t pos = atomicAdd(&cur[(v[k] >> 24) & 0x7f], 1u);
-                sorted[pos] = v[k] & 0x80ffffffu;
-            }
-        }
-    }
-}
-
-// Pass B with the scatter staged through LDS.  A lane's `sorted[pos] = v` of sortB_kernel is a 4-byte write to one of 128 runs: 64 requests
-// per wave store, and the L2 takes ~128 requests per clock chip-wide -- 15.7M entries = 58 us of request issue alone (measured 74 us).
+// Pass B (one workgroup per (bin, window): counting sort by `lo`, emits the final entries and the global bucket starts) with the scatter
+// staged through LDS.  A lane's plain `sorted[pos] = v` is a 4-byte write to one of 128 runs: 64 requests per wave store, and the L2 takes ~128 requests per clock chip-wide -- 15.7M entries = 58 us of request issue alone (measured 74 us).
 // Here a tile of 8 entries per lane is ranked by sub-bucket in LDS (LDS atomics), laid out sub-bucket by sub-bucket in a 32 KiB
 // buffer, and written out with consecutive lanes on consecutive addresses: runs of ~64 entries = two full 128-byte lines per sub-bucket and tile.
 // Large MSMs (round 3): a bin is cut into `parts` contiguous pieces, one workgroup each (blockIdx.z) -- under skewed digit distributions a
@@ -896,7 +832,7 @@ template <int THREADS> __global__ void __launch_bounds__(THREADS) sortB_staged_k
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void store_raw(uint32_t* dst, const Xyzz& p)
 {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BBGPU_STORE_RAW_X4)
+#if defined(__HIP_DEVICE_COMPILE__)
     // 8-byte stores off one base address.  The compiler's own choice -- nine 16-byte stores -- wants quadruples of adjacent registers,
     // and the accumulator's limbs sit wherever the in-place products of the hot loop leave them: it then shuffles 8 limbs out and
     // back on EVERY trip (22 v_mov + 11 v_mov_b64 in the hot path); pairs it manages to keep adjacent (6 copies left, in the latch).
@@ -927,13 +863,8 @@ __device__ __forceinline__ void load_raw(Xyzz& p, const uint32_t* src)
     }
 }
 // Register budget of the accumulation: with the asm products the allocator settles at 132 VGPRs (three waves per SIMD, which is what the
-// LDS reservation admits anyway).  Holding it to 128 like the tail kernels (-DBBGPU_ACC_CAP128: 4 spills, one scratch access in the hot
-// loop) was measured in one box at 1.272 vs 1.259 ms per pipelined 2^20 step: no gain, the default stays uncapped.
-#ifdef BBGPU_ACC_CAP128
-#define ACC_VGPR_CAP __attribute__((amdgpu_waves_per_eu(4, 4)))
-#else
-#define ACC_VGPR_CAP
-#endif
+// LDS reservation admits anyway).  Holding it to 128 like the tail kernels (4 spills, one scratch access in the hot loop) was measured
+// in one box at 1.272 vs 1.259 ms per pipelined 2^20 step: no gain, the accumulation stays uncapped.
 constexpr int RAW_WORDS = 4 * NL; // 36 words per partial: lazy limbs, no canonicalisation on the hot path
 // The heavy-bucket queue of the merge: heavy[0] = number of queued buckets, heavy[1 .. HEAVY_WGS] = per-bucket arrival counters of the
 // workgroups that share a bucket (K4h), heavy[HEAVY_IDS ..] = bucket ids; HEAVY_WGS raw partial sums follow the id list (MsmCarve).
@@ -943,7 +874,7 @@ constexpr uint32_t HEAVY_IDS = 1 + HEAVY_WGS; // first bucket id
 // slice sums one per lane: both need a workgroup as wide as the queue
 static_assert(MSM_THREADS == (int)HEAVY_WGS, "heavy-bucket queue header is cleared / combined by one lane per K4h workgroup");
 
-__global__ void __launch_bounds__(MSM_THREADS) ACC_VGPR_CAP msm_accumulate_kernel(const uint32_t* __restrict__ srs, const uint32_t* __restrict__ sorted,
+__global__ void __launch_bounds__(MSM_THREADS) msm_accumulate_kernel(const uint32_t* __restrict__ srs, const uint32_t* __restrict__ sorted,
                                                                    const uint32_t* __restrict__ gstart, uint32_t* __restrict__ partials,
                                                                    uint32_t total_buckets, uint32_t ch, uint32_t prio, uint32_t* __restrict__ heavy_counter)
 {
@@ -1034,20 +965,6 @@ __global__ void __launch_bounds__(MSM_THREADS) ACC_VGPR_CAP msm_accumulate_kerne
         }
         asm volatile("" ::: "memory");
         if (!start) madd_ip(acc, acc_inf, px, py);
-#ifdef BBGPU_ACC_JUNK // issue-model experiment (DESIGN_HISTORY 5): extra cheap VALU instructions per trip, results unused
-        {
-            uint32_t j0 = e, j1 = vn;
-#pragma unroll
-            for (int q = 0; q < BBGPU_ACC_JUNK / 2; q++) asm volatile("v_and_b32 %0, 0x1fffffff, %1\n\tv_add_u32 %1, %0, %1" : "+v"(j0), "+v"(j1));
-        }
-#endif
-#ifdef BBGPU_ACC_JUNKMAD // the same with dependent v_mad_u64_u32
-        {
-            unsigned long long ja = e;
-#pragma unroll
-            for (int q = 0; q < BBGPU_ACC_JUNKMAD; q++) asm volatile("v_mad_u64_u32 %0, vcc, %1, %1, %0" : "+v"(ja) : "v"(vn) : "vcc");
-        }
-#endif
         load_affine_m261_signed(px, py, w, (vn >> 31) != 0);
         ld16(srs + (size_t)(vnn & 0x7fffffffu) * 16, w);
         vn = vnn;
@@ -1081,11 +998,7 @@ __device__ __forceinline__ Xyzz shfl_down_xyzz(const Xyzz& p, uint32_t off)
 // The tail kernels are held to 128 VGPRs (amdgpu_waves_per_eu(4, 4), ~32 registers spilled): at the 143 they would otherwise
 // take, their waves do not fit beside the three 128-VGPR accumulation waves per SIMD of the next MSM and the whole tail queued
 // behind it (rocprof timeline: merge 0.5 ms and heavy-merge 0.58 ms in the two-deep pipeline against 0.05 ms alone).
-// TAIL_OCC: the register cap of the tail kernels (see above).  -DBBGPU_TAIL_WAVES=k sets another occupancy target for A/B builds (2: up to 256 VGPRs, no spills).
-#ifndef BBGPU_TAIL_WAVES
-#define BBGPU_TAIL_WAVES 4
-#endif
-#define TAIL_OCC __attribute__((amdgpu_waves_per_eu(BBGPU_TAIL_WAVES, BBGPU_TAIL_WAVES)))
+#define TAIL_OCC __attribute__((amdgpu_waves_per_eu(4, 4))) // the register cap of the tail kernels (see above)
 constexpr int FOLD_T = 256;
 constexpr int FOLD_LDS_WORDS = (FOLD_T / 2) * RAW_WORDS;
 __device__ __forceinline__ void wg_tree_sum(Xyzz& acc, uint32_t* sh, uint32_t T, uint32_t t)
@@ -1122,7 +1035,7 @@ __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_merge_kernel(const u
                                                               uint32_t ch, uint32_t MERGE_LIGHT, uint32_t logG)
 {
     // buckets [bucket_begin, total_buckets): a bucket-range share merges (and later folds) its own buckets only
-    __builtin_amdgcn_s_setprio(BBGPU_TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t G = 1u << logG, b = bucket_begin + (t >> logG), j = t & (G - 1);
     if (b >= total_buckets) return; // whole groups leave together (groups are aligned inside a wave)
@@ -1163,7 +1076,7 @@ __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_merge_kernel(const u
 __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_merge_heavy_kernel(const uint32_t* __restrict__ gstart, const uint32_t* __restrict__ partials,
                                                                     uint32_t* __restrict__ buckets, uint32_t* __restrict__ heavy, uint32_t ch, uint32_t* __restrict__ hpart)
 {
-    __builtin_amdgcn_s_setprio(BBGPU_TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
     __shared__ uint32_t sh[FOLD_LDS_WORDS];
     __shared__ uint32_t last_flag;
     const uint32_t count = heavy[0];
@@ -1233,73 +1146,14 @@ __device__ __forceinline__ uint32_t insert_one_bit(uint32_t m, uint32_t k)
 {
     return ((m >> k) << (k + 1)) | (1u << k) | (m & ((1u << k) - 1));
 }
-
-// Row sums R[hi] = sum_lo B[hi][lo] (blockIdx.x < H) and column sums C[lo] = sum_hi B[hi][lo] (blockIdx.x >= H) of the
-// H x L bucket matrix of group blockIdx.y; blockDim.x = max(H, L).
-__global__ void __launch_bounds__(FOLD_T) TAIL_OCC msm_rowcol_kernel(const uint32_t* __restrict__ buckets, uint32_t* __restrict__ R, uint32_t* __restrict__ Cc,
-                                                          uint32_t H, uint32_t L, uint32_t* __restrict__ zero_out, uint32_t zero_words)
-{
-    __builtin_amdgcn_s_setprio(BBGPU_TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
-    __shared__ uint32_t sh[FOLD_LDS_WORDS];
-    const uint32_t g = blockIdx.y, t = threadIdx.x, nb = H * L;
-    if (zero_out) { // small MSMs: the export slots (infinity = all zero) are cleared here instead of by a fill launch
-        const uint32_t gid = (g * gridDim.x + blockIdx.x) * blockDim.x + t, all = gridDim.y * gridDim.x * blockDim.x;
-        for (uint32_t i = gid; i < zero_words; i += all) zero_out[i] = 0;
-    }
-    const bool row = blockIdx.x < H;
-    const uint32_t idx = row ? blockIdx.x : blockIdx.x - H, count = row ? L : H;
-    Xyzz acc;
-    set_infinity(acc);
-    if (t < count) {
-        const size_t b = row ? (size_t)idx * L + t : (size_t)t * L + idx;
-        uint32_t w[32];
-        ld32(buckets + ((size_t)g * nb + b) * 32, w);
-        load_xyzz(acc, w);
-    }
-    wg_tree_sum(acc, sh, blockDim.x, t);
-    if (t == 0) {
-        uint32_t w[32];
-        store_xyzz(w, acc);
-        st32((row ? R + ((size_t)g * H + idx) * 32 : Cc + ((size_t)g * L + idx) * 32), w);
-    }
-}
-// Job 0: Z = sum R; job 1 + k: TR_k = sum of the R_hi whose bit k is set; job 1 + hbits + k: TC_k likewise over C.  Each job is
-// one workgroup; results go straight into the 64-slot export array in the reference's Montgomery form (slot 0 = Z,
-// 1 + k = TR_k, 32 + k = TC_k; the array is zeroed = infinity beforehand).
-__global__ void __launch_bounds__(FOLD_T) TAIL_OCC msm_final_kernel(const uint32_t* __restrict__ R, const uint32_t* __restrict__ Cc, uint32_t* __restrict__ out,
-                                                         uint32_t hbits, uint32_t lbits)
-{
-    __builtin_amdgcn_s_setprio(BBGPU_TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
-    __shared__ uint32_t sh[FOLD_LDS_WORDS];
-    const uint32_t g = blockIdx.y, t = threadIdx.x, job = blockIdx.x;
-    const uint32_t H = 1u << hbits, L = 1u << lbits;
-    const uint32_t* src;
-    uint32_t count, slot, k = 0;
-    bool sliced = true;
-    if (job == 0) { src = R + (size_t)g * H * 32; count = H; slot = 0; sliced = false; }
-    else if (job < 1 + hbits) { k = job - 1; src = R + (size_t)g * H * 32; count = H >> 1; slot = 1 + k; }
-    else { k = job - 1 - hbits; src = Cc + (size_t)g * L * 32; count = L >> 1; slot = 32 + k; }
-    Xyzz acc;
-    set_infinity(acc);
-    if (t < count) {
-        uint32_t w[32];
-        ld32(src + (size_t)(sliced ? insert_one_bit(t, k) : t) * 32, w);
-        load_xyzz(acc, w);
-    }
-    wg_tree_sum(acc, sh, blockDim.x, t);
-    if (t == 0) {
-        uint32_t o[32];
-        store_xyzz_m256(o, acc);
-        st32(out + ((size_t)g * 64 + slot) * 32, o);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// K5 with quad additions (g1_quad.hpp): the same two kernels, every point spread over the four lanes of a quad.  A workgroup of 256
+// Row sums R[hi] = sum_lo B[hi][lo] and column sums C[lo] = sum_hi B[hi][lo] of the H x L bucket matrix of every group, then one
+// workgroup per job: job 0: Z = sum R; job 1 + k: TR_k = sum of the R_hi whose bit k is set; job 1 + hbits + k: TC_k likewise over C.
+// Results go straight into the 64-slot export array in the reference's Montgomery form (slot 0 = Z, 1 + k = TR_k, 32 + k = TC_k).
+// Both kernels use quad additions (g1_quad.hpp), every point spread over the four lanes of a quad.  A workgroup of 256
 // threads = 64 quads sums up to 256 points: each quad first adds its points e, e + 64, ... (<= 3 dependent additions), then a
 // 4-level tree inside the wave (partners move by ds_bpermute: 9 words per lane and level, not 36), then the four wave sums through
-// 576 bytes of LDS and two more levels: <= 9 dependent quad additions of ~1,250 instructions instead of 8 of ~3,700 plus a 36-word
-// LDS round trip and two barriers per level.
+// 576 bytes of LDS and two more levels: <= 9 dependent quad additions of ~1,250 instructions instead of the 8 of ~3,700 plus a 36-word
+// LDS round trip and two barriers per level of the round-1 form (one point per lane, wg_tree_sum).
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int QFOLD_T = 256;
 __device__ __forceinline__ FqN quad_load(const uint32_t* point32, uint32_t l) // coordinate l of a stored XYZZ point (4 x 8 words, canonical Montgomery-261)
@@ -1367,7 +1221,7 @@ __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_merge_quad_kernel(co
                                                                    uint32_t* __restrict__ buckets, uint32_t* __restrict__ heavy, uint32_t bucket_begin, uint32_t total_buckets,
                                                                    uint32_t ch, uint32_t MERGE_LIGHT, uint32_t logQ)
 {
-    __builtin_amdgcn_s_setprio(BBGPU_TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, l = t & 3, quad = t >> 2;
     const uint32_t Q = 1u << logQ, b = bucket_begin + (quad >> logQ), j = quad & (Q - 1);
     if (b >= total_buckets) return; // whole bucket groups leave together (4 Q lanes, aligned inside a wave)
@@ -1424,7 +1278,7 @@ __global__ void __launch_bounds__(QFOLD_T) TAIL_OCC msm_rowcol_quad_kernel(const
 {
     // rows [r0, r0 + rows) of the H x L bucket matrix (all of them, or a bucket-range share's): blockIdx.x < rows sums row r0 + blockIdx.x,
     // the L blocks after them sum the columns over those rows.  R of the other rows is not written: the caller zeroed it (infinity).
-    __builtin_amdgcn_s_setprio(BBGPU_TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
     __shared__ uint32_t sh[(QFOLD_T / 64) * 4 * NL];
     const uint32_t g = blockIdx.y, t = threadIdx.x, nb = H * L, l = t & 3, quad = t >> 2;
     if (zero_out) { // small MSMs: the export slots (infinity = all zero) are cleared here instead of by a fill launch
@@ -1458,7 +1312,7 @@ constexpr uint32_t ROWCOL_SEG = 4;
 __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_rowcol_seg_kernel(const uint32_t* __restrict__ buckets, uint32_t* __restrict__ segs, uint32_t H, uint32_t L,
                                                                                                                 uint32_t* __restrict__ zero_out, uint32_t zero_words)
 {
-    __builtin_amdgcn_s_setprio(BBGPU_TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
     const uint32_t g = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x, nb = H * L;
     if (zero_out) { // the export slots (infinity = all zero) are cleared here instead of by a fill launch
         const uint32_t gid = g * gridDim.x * blockDim.x + t, all = gridDim.y * gridDim.x * blockDim.x;
@@ -1501,7 +1355,7 @@ __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_rowcol_seg_kernel(co
 }
 __global__ void __launch_bounds__(64) TAIL_OCC msm_segsum_quad_kernel(const uint32_t* __restrict__ segs, uint32_t* __restrict__ R, uint32_t* __restrict__ Cc, uint32_t H, uint32_t L)
 {
-    __builtin_amdgcn_s_setprio(BBGPU_TAIL_PRIO);
+    __builtin_amdgcn_s_setprio(TAIL_PRIO);
     const uint32_t g = blockIdx.y, t = threadIdx.x, l = t & 3, quad = t >> 2;
     const uint32_t row_lanes = H * (L / ROWCOL_SEG), col_lanes = L * (H / ROWCOL_SEG);
     const bool row = blockIdx.x < H;
@@ -1524,7 +1378,7 @@ __global__ void __launch_bounds__(64) TAIL_OCC msm_segsum_quad_kernel(const uint
 __global__ void __launch_bounds__(QFOLD_T) TAIL_OCC msm_final_quad_kernel(const uint32_t* __restrict__ R, const uint32_t* __restrict__ Cc, uint32_t* __restrict__ out,
                                                                  uint32_t hbits, uint32_t lbits)
 {
-    __builtin_amdgcn_s_setprio(BBGPU_TAIL_PRIO);
+    __builtin_amdgcn_s_setprio(TAIL_PRIO);
     __shared__ uint32_t sh[(QFOLD_T / 64) * 4 * NL];
     const uint32_t g = blockIdx.y, t = threadIdx.x, job = blockIdx.x, l = t & 3, quad = t >> 2;
     const uint32_t H = 1u << hbits, L = 1u << lbits;
@@ -1582,34 +1436,8 @@ struct MsmPlan {
 // K4 residency: 3 workgroups of 256 lanes per CU (3 waves per SIMD; v_mad_u64_u32 issue saturates at 2).  The 4th slot is
 // deliberately left free -- enforced by a dynamic-LDS reservation -- so that the short latency-bound kernels of the
 // previous MSM's tail (merge, folds) can run beside the accumulation of the next one (two-slot pipeline).
+constexpr uint32_t ACC_WG_PER_CU = 3;
 constexpr uint32_t ACC_LDS_RESERVE = 41 * 1024; // 3 x 41 KiB fit in 160 KiB, 4 do not
-static uint32_t acc_wg_per_cu()
-{
-    static int v = 0;
-    if (!v) {
-        v = 3;
-        if (const char* e = getenv("BBGPU_ACC_WGS")) v = std::min(4, std::max(1, atoi(e))); // tuning knob (4 = no reservation)
-    }
-    return (uint32_t)v;
-}
-static uint32_t acc_lds_reserve()
-{
-    static int v = -1;
-    if (v < 0) {
-        v = acc_wg_per_cu() == 3 ? (int)ACC_LDS_RESERVE : (acc_wg_per_cu() == 2 ? 60 * 1024 : 0);
-        if (const char* e = getenv("BBGPU_ACC_LDS")) v = std::min(64 * 1024, std::max(0, atoi(e))); // tuning knob
-    }
-    return (uint32_t)v;
-}
-static uint32_t acc_prio()
-{
-    static int v = -1;
-    if (v < 0) {
-        v = 0;
-        if (const char* e = getenv("BBGPU_ACC_PRIO")) v = std::min(2, std::max(0, atoi(e))); // tuning knob
-    }
-    return (uint32_t)v;
-}
 static uint32_t acc_capacity_lanes()
 {
     static uint32_t lanes = 0;
@@ -1617,7 +1445,7 @@ static uint32_t acc_capacity_lanes()
         int dev = 0, cus = 256;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        lanes = (uint32_t)cus * acc_wg_per_cu() * MSM_THREADS;
+        lanes = (uint32_t)cus * ACC_WG_PER_CU * MSM_THREADS;
     }
     return lanes;
 }
@@ -1629,45 +1457,28 @@ constexpr uint32_t MIN_CHUNK = 8;
 constexpr uint64_t TINY_ENTRIES = (uint64_t)1 << 16;
 constexpr uint32_t TINY_MIN_CHUNK = 4;
 static uint32_t min_chunk(uint64_t m) { return m <= TINY_ENTRIES ? TINY_MIN_CHUNK : MIN_CHUNK; }
-static uint32_t chunk_len_m(uint64_t m);
-static bool chunk_forced()
-{
-    static const bool f = getenv("BBGPU_CHUNK") != nullptr || getenv("BBGPU_ACC_WAVES") != nullptr;
-    return f;
-}
-static uint32_t chunk_len(size_t n, uint32_t nw)
-{
-    return chunk_len_m((uint64_t)n * nw);
-}
 // m: expected number of entries of the sorted list
 static uint32_t chunk_len_m(const uint64_t m)
 {
-    static int waves = 0; // BBGPU_ACC_WAVES: k > 1 cuts the list into k times as many (shorter) chunks -> k waves of workgroups (tuning experiments)
-    if (!waves) {
-        waves = 1;
-        if (const char* e = getenv("BBGPU_ACC_WAVES")) waves = std::min(16, std::max(1, atoi(e)));
-    }
-    static const int forced = [] { const char* e = getenv("BBGPU_CHUNK"); return e ? std::max((int)MIN_CHUNK, atoi(e)) : 0; }(); // tuning knob (small MSMs)
-    if (forced) return (uint32_t)std::max<uint64_t>(forced, (m + ((uint64_t)1 << 24) - 1) >> 24);
-    if (waves > 1) {
-        const uint64_t cap = (uint64_t)acc_capacity_lanes() * (uint64_t)waves;
-        return std::max<uint32_t>(MIN_CHUNK, (uint32_t)((m + cap - 1) / cap));
-    }
     // k = 1 .. 3 workgroups per CU, every lane `ch` entries: the kernel lasts ~ch * step(k), step(k) = time of one mixed addition of a wave
     // with k waves on its SIMD: ~6.4 us alone (dependent multiplications), k * 4.46 us once two waves saturate the multiplier
     // (14.7e9 mixed additions per second chip-wide).  A grid that is NOT a whole number of workgroups per CU runs at the pace of the
     // fullest CU: 2^16 points x 17 windows at ch = 8 is 543 workgroups = 2.1 per CU, paced by the CUs holding 3 (107 us);
     // ch = 9 gives 484 = at most 2 per CU (80 us).
     static const double step[3] = { 6.4, 9.2, 13.4 }; // two waves reach ~97 % of the multiplier rate, three all of it
-    const uint64_t per_k = (uint64_t)acc_capacity_lanes() / acc_wg_per_cu(); // lanes of one workgroup per CU
+    const uint64_t per_k = (uint64_t)acc_capacity_lanes() / ACC_WG_PER_CU; // lanes of one workgroup per CU
     uint32_t best = 0;
     double best_cost = 0.0;
-    for (uint32_t k = 1; k <= acc_wg_per_cu() && k <= 3; k++) {
+    for (uint32_t k = 1; k <= ACC_WG_PER_CU; k++) {
         const uint32_t ch = std::max<uint32_t>(min_chunk(m), (uint32_t)((m + per_k * k - 1) / (per_k * k)));
         const double cost = ch * step[k - 1];
         if (!best || cost < best_cost) { best = ch; best_cost = cost; }
     }
     return best;
+}
+static uint32_t chunk_len(size_t n, uint32_t nw)
+{
+    return chunk_len_m((uint64_t)n * nw);
 }
 static size_t arena_points(const MsmPlan& P, uint32_t nw)
 {
@@ -1707,7 +1518,7 @@ static MsmPlan make_plan(size_t n, int c)
 // came from exactly such a pair of hand-kept formulas: the fold arena was sized by a guess, (2 nw nb + 4096) points, while
 // the then per-level fold / slice chain bumped rows + columns + slices per window past it into the next page.)
 struct MsmCarve {
-    size_t digits, signs, histA, histB, binstart, bintot, tmp_entries, gstart, totals, heavy, sorted, partials, buckets, arena, segs, texp, end;
+    size_t digits, signs, histA, histB, binstart, bintot, tmp_entries, gstart, totals, heavy, sorted, partials, buckets, arena, segs, end;
     size_t chunks_cap, histB_bytes;
 };
 // nw: (job, window) pairs = what the entry lists scale with; ng: BUCKET SETS = what the bucket-side arrays scale with -- nw without window tables (one set per
@@ -1737,7 +1548,6 @@ static MsmCarve carve(const MsmPlan& P, size_t n, size_t nw, size_t ng)
     L.buckets = p;     p += al(ng * P.nb * 128);
     L.arena = p;       p += al(arena_points(P, (uint32_t)ng) * 128); // row sums + column sums
     L.segs = p;        p += al(seg_points(P, (uint32_t)ng) * 128);   // segment sums of the two-step row / column sums (large bucket sets)
-    L.texp = p;        p += al(ng * 64 * 128);                   // exported T points
     L.end = p;
     return L;
 }
@@ -1881,7 +1691,6 @@ int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, si
     uint32_t sort_lb = P.sort_lb, sort_bins = P.sort_bins;
     if (table) {
         uint32_t want_bins = 512; // measured: 512 bins 0.196 ms, 1024 bins 0.229 ms, 256 bins 0.215 ms (2^20, 256 slices)
-        if (const char* e = getenv("BBGPU_SORT_BINS")) want_bins = std::min(1024, std::max(64, atoi(e))); // tuning knob
         while (sort_bins < want_bins && sort_lb > 3) { sort_lb--; sort_bins <<= 1; }
     }
     uint32_t slices = table ? std::max<uint32_t>(1, P.slices * nw1 / 2) : P.slices;
@@ -1893,7 +1702,6 @@ int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, si
         const uint32_t want = std::min<uint32_t>(std::min<uint32_t>(208, (uint32_t)(n / 2048)), by_cap);
         slices = std::max(slices, want);
     }
-    if (const char* e = getenv("BBGPU_SLICES")) slices = std::min<uint32_t>(std::max(1, atoi(e)), P.slices * nw1); // tuning knob
     const uint32_t slice_len = (uint32_t)((n + slices - 1) / slices);
     const uint32_t idx_stride = table ? (uint32_t)tab_stride : 0u;
     const uint32_t* points = table ? d_tab : d_srs;
@@ -1930,7 +1738,6 @@ int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, si
     uint32_t* partials = (uint32_t*)(p + LY.partials);
     uint32_t* buckets = (uint32_t*)(p + LY.buckets);
     uint32_t* scratch = (uint32_t*)(p + LY.arena);
-    uint32_t* texp = (uint32_t*)(p + LY.texp);
     // launch-shape checks against the carve (the kernels index these arrays from these quantities)
     if ((uint64_t)G * slices * sort_bins > (uint64_t)nw * P.slices * 1024 || sort_bins > 1024 ||
         (size_t)G * ((size_t)(1u << P.hbits) + (size_t)(1u << P.lbits)) + 64 > arena_points(P, G)) {
@@ -1952,11 +1759,6 @@ int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, si
     }
 
     if (bshare) {
-        static const bool quad_ok = [] { const char* e = getenv("BBGPU_QUAD_TAIL"); return !e || atoi(e) != 0; }();
-        if (!quad_ok) {
-            set_error("bucket-range shares need the quad tail kernels (BBGPU_QUAD_TAIL=0 is set)");
-            return BBGPU_ERR_STATE;
-        }
         // row sums outside the share stay infinity (all zero): the bit-slice kernel reads every row.  First in the stream, far off the tail's critical path
         HIPCHK(hipMemsetAsync(scratch, 0, (size_t)G * BH * 128, st));
     }
@@ -1973,22 +1775,18 @@ int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, si
     sortA_colscan_kernel<<<dim3((sort_bins + SORT_THREADS / 64 - 1) / (SORT_THREADS / 64), G), SORT_THREADS, 0, st>>>(histA, bintot, sort_bins, slices);
     sortA_scan_kernel<<<G, SORT_THREADS, 0, st>>>(bintot, binstart, totals, sort_bins, G == 1 ? bases : nullptr, gstart + (size_t)G * P.nb);
     if (G > 1) sort_bases_kernel<<<1, 64, 0, st>>>(totals, bases, gstart + (size_t)G * P.nb, G);
-    static const int staged = [] { const char* e = getenv("BBGPU_SORT_STAGED"); return e ? atoi(e) : 3; }(); // tuning knob: bit 0 pass B, bit 1 pass A
-    if ((staged & 2) && (P.n & 7u) == 0) {
+    if ((P.n & 7u) == 0) {
         if (wide) sortA_scatter_staged_kernel<uint16_t><<<dim3(slices, G), SORT_THREADS, 0, st>>>((const uint16_t*)digits, signs, histA, binstart, bases, tmp_entries, P.n, sort_bins, sort_lb, slices,
                                                                                   slice_len, (uint32_t)wb, wpg, idx_stride, P.W, row_i0, row_i1, blo, bcnt);
         else sortA_scatter_staged_kernel<int16_t><<<dim3(slices, G), SORT_THREADS, 0, st>>>((const int16_t*)digits, signs, histA, binstart, bases, tmp_entries, P.n, sort_bins, sort_lb, slices,
                                                                             slice_len, (uint32_t)wb, wpg, idx_stride, P.W, row_i0, row_i1, blo, bcnt);
-    } else
-    if (wide) sortA_scatter_kernel<uint16_t><<<dim3(slices, G), SORT_THREADS, 0, st>>>((const uint16_t*)digits, signs, histA, binstart, bases, tmp_entries, P.n, sort_bins, sort_lb, slices,
+    } else if (wide) sortA_scatter_kernel<uint16_t><<<dim3(slices, G), SORT_THREADS, 0, st>>>((const uint16_t*)digits, signs, histA, binstart, bases, tmp_entries, P.n, sort_bins, sort_lb, slices,
                                                                    slice_len, (uint32_t)wb, wpg, idx_stride, P.W, row_i0, row_i1, blo, bcnt);
     else sortA_scatter_kernel<int16_t><<<dim3(slices, G), SORT_THREADS, 0, st>>>((const int16_t*)digits, signs, histA, binstart, bases, tmp_entries, P.n, sort_bins, sort_lb, slices,
                                                                    slice_len, (uint32_t)wb, wpg, idx_stride, P.W, row_i0, row_i1, blo, bcnt);
-    if (!(staged & 1)) sortB_kernel<<<dim3(sort_bins, G), table ? SORT_THREADS : 256, 0, st>>>(tmp_entries, binstart, bases, sorted, gstart, sort_bins, sort_lb, P.nb);
-    else if (table) {
+    if (table) {
         // large MSMs: eight pieces per bin (one more launch, ~8 us on the front; small MSMs are chains of dependent launches and keep one)
-        static const int parts_env = [] { const char* e = getenv("BBGPU_SORTB_PARTS"); return e ? std::min((int)SORTB_MAX_PARTS, std::max(1, atoi(e))) : 0; }(); // tuning knob
-        uint32_t parts = parts_env ? (uint32_t)parts_env : (((uint64_t)n * nw1 >= ((uint64_t)1 << 21) && G <= MSM_MAX_JOBS) ? SORTB_MAX_PARTS : 1u);
+        uint32_t parts = ((uint64_t)n * nw1 >= ((uint64_t)1 << 21) && G <= MSM_MAX_JOBS) ? SORTB_MAX_PARTS : 1u;
         if ((size_t)G * sort_bins * parts * 128 * 4 > LY.histB_bytes) parts = 1; // the workspace keeps the piece counts only for large MSMs (carve)
         if (parts > 1) sortB_count_kernel<SORT_THREADS><<<dim3(sort_bins, G, parts), SORT_THREADS, 0, st>>>(tmp_entries, binstart, bases, histB, sort_bins, parts);
         sortB_staged_kernel<SORT_THREADS><<<dim3(sort_bins, G, parts), SORT_THREADS, 0, st>>>(tmp_entries, binstart, bases, sorted, gstart, sort_bins, sort_lb, P.nb, histB, parts);
@@ -2002,53 +1800,44 @@ int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, si
     // Other MSMs in flight (S.throughput): the chip is shared and what counts is the instructions this one issues.  Lanes with fewer than ~20 entries
     // pay their prologue (start-bucket search, first row) and their partial sums (one per lane and bucket touched: the merge's work) for little;
     // measured on 1/8 shares of a 2^20 MSM, four in flight: chunks of 10 (the latency choice) 0.202 ms per step, 15: 0.191, 20: 0.181, 25: 0.190, 30: 0.183;
-    // 2^16 points, three in flight: 0.126 -> 0.118 ms (tools/point_share_ab.py, tools/msm_ab.py with BBGPU_CHUNK).
-    static const int tp_env = [] { const char* e = getenv("BBGPU_THROUGHPUT"); return e ? atoi(e) : -1; }(); // tuning knob: 0 / 1 force the latency / throughput choices
-    const bool tp = (tp_env < 0 ? hint : tp_env != 0) && jobs == 1;
+    // 2^16 points, three in flight: 0.126 -> 0.118 ms (tools/point_share_ab.py, tools/msm_ab.py).
+    const bool tp = hint && jobs == 1;
     constexpr uint32_t TP_MIN_CHUNK = 20;
     uint32_t ch = bshare ? chunk_len_m(m_expected) : chunk_len(n, nw);
     ch = std::max(ch, min_chunk((uint64_t)n * nw)); // the workspace's partial slots are laid out for chunks no shorter than the WHOLE list's minimum (carve: chunks_cap)
-    if (tp && ch < TP_MIN_CHUNK && !chunk_forced()) // ... as long as one workgroup per CU is left (a 2-of-17-window share of 2^16 points, 131 k entries: chunks of 20 0.091 ms per step, of 8 0.072)
-        ch = std::max(ch, std::min<uint32_t>(TP_MIN_CHUNK, (uint32_t)(m_expected / (acc_capacity_lanes() / acc_wg_per_cu()))));
+    if (tp && ch < TP_MIN_CHUNK) // ... as long as one workgroup per CU is left (a 2-of-17-window share of 2^16 points, 131 k entries: chunks of 20 0.091 ms per step, of 8 0.072)
+        ch = std::max(ch, std::min<uint32_t>(TP_MIN_CHUNK, (uint32_t)(m_expected / (acc_capacity_lanes() / ACC_WG_PER_CU))));
     // merge: 2^logG lanes per bucket, sized for the expected number of partials per bucket (~ entries / (buckets * ch) + 1);
     // a bucket cut into more than 8 partials per lane of its group is queued for the workgroup-per-bucket kernel
     // -- but no wider than what fills the chip once (~2^16 lanes): beyond that the extra lanes only add issue work
     const uint32_t avg_partials = (uint32_t)(m_expected / ((uint64_t)merge_buckets * ch)) + 1;
     uint32_t logG = 0;
-    static const uint32_t lanes_log = [] { const char* e = getenv("BBGPU_MERGE_LANES_LOG"); return e ? (uint32_t)std::min(20, std::max(14, atoi(e))) : 16u; }(); // tuning knob
-    while ((1u << logG) < avg_partials && logG < 6 && ((uint64_t)merge_buckets << (logG + 1)) <= ((uint64_t)1 << lanes_log)) logG++;
+    while ((1u << logG) < avg_partials && logG < 6 && ((uint64_t)merge_buckets << (logG + 1)) <= ((uint64_t)1 << 16)) logG++;
     const uint32_t merge_light = std::max(6u, 8u << logG);
     const uint32_t max_chunks = (uint32_t)(((uint64_t)n * nw + ch - 1) / ch);
     // An MSM is a chain of dependent launches: its three helper launches -- two fills and the device-to-host copy, ~5 us each -- are folded
     // into the kernels around them, the last kernel writing the 8 KiB of results straight into the pinned host buffer.  (Round 1 measured the
     // folded tail 1..3 % SLOWER per pipelined 2^20 step and kept it for small MSMs only; with the round-2 tail it is level or ahead at every
     // size -- 1.371 vs 1.385 ms latency, 1.174 vs 1.176 ms per step, tools/msm_ab.py, two alternating runs in one box -- and is the one path.)
-    static const int fold_env = [] { const char* e = getenv("BBGPU_FOLD_TAIL"); return e ? atoi(e) : 1; }(); // tuning knob: 0 = separate fills and copy
-    const bool fold = fold_env != 0;
-    msm_accumulate_kernel<<<(max_chunks + MSM_THREADS - 1) / MSM_THREADS, MSM_THREADS, acc_lds_reserve(), st>>>(points, sorted, gstart, partials, total_buckets, ch, acc_prio(), fold ? heavy : nullptr);
+    msm_accumulate_kernel<<<(max_chunks + MSM_THREADS - 1) / MSM_THREADS, MSM_THREADS, ACC_LDS_RESERVE, st>>>(points, sorted, gstart, partials, total_buckets, ch, 0, heavy);
     if (tm_acc) {
         HIPCHK(hipEventRecord(ev[3], st));
         if (int rc = acc_ring_record(S, st)) return rc;
     } else {
         S.acc_seq = 0;
     }
-    if (!fold) HIPCHK(hipMemsetAsync(heavy, 0, HEAVY_IDS * 4, st));
-    static const bool quad_tail = [] { const char* e = getenv("BBGPU_QUAD_TAIL"); return !e || atoi(e) != 0; }(); // 0: one point per lane (round 1)
-    static const uint64_t quad_merge_max_entries = [] { const char* e = getenv("BBGPU_QUAD_MERGE_MAX_LOG"); return (uint64_t)1 << (e ? std::min(30, std::max(10, atoi(e))) : 21); }(); // tuning knob
-    static const int quad_merge = [] { const char* e = getenv("BBGPU_QUAD_MERGE"); return e ? atoi(e) : 1; }(); // tuning knob: 0 off, 1 on, 2.. = 1 + forced logQ
     // A quad addition is 4 x 1,350 lane-instructions against 3,700 for one point per lane: quads shorten the chain where the lanes do not
     // fill the chip, and cost issue slots where they do.  2^20 points: 196,608 additions, ~42 us either way (one wave per SIMD and three
     // dependent 9-us additions, or four waves per SIMD sharing the multiplier) -- the plain kernel stays.  2^16 points x 17 windows
     // (8 partials per bucket): 2 quads per bucket 0.261 -> 0.253 ms latency; a 2-of-17-window share 0.200 -> 0.187 ms (tools/msm_ab.py).
-    if (quad_tail && (quad_merge > 1 || (quad_merge == 1 && (uint64_t)n * nw <= quad_merge_max_entries))) {
+    // Quads up to 2^21 entries.
+    if ((uint64_t)n * nw <= ((uint64_t)1 << 21)) {
         // quads per bucket: about half the expected number of partials, within one resident wave of tail workgroups (~2^18 lanes)
         uint32_t logQ = 0;
         while ((2u << logQ) < avg_partials && logQ < 4 && ((uint64_t)merge_buckets << (logQ + 3)) <= ((uint64_t)1 << 17)) logQ++;
-        if (quad_merge > 1) logQ = std::min(4, quad_merge - 2);
         msm_merge_quad_kernel<<<(uint32_t)((((uint64_t)merge_buckets << (logQ + 2)) + MSM_THREADS - 1) / MSM_THREADS), MSM_THREADS, 0, st>>>(gstart, partials, buckets, heavy, blo, blo + merge_buckets, ch,
                                                                                                                                   std::max(32u, 8u << logQ), logQ);
-    } else
-    msm_merge_kernel<<<(uint32_t)((((uint64_t)merge_buckets << logG) + MSM_THREADS - 1) / MSM_THREADS), MSM_THREADS, 0, st>>>(gstart, partials, buckets, heavy,
+    } else msm_merge_kernel<<<(uint32_t)((((uint64_t)merge_buckets << logG) + MSM_THREADS - 1) / MSM_THREADS), MSM_THREADS, 0, st>>>(gstart, partials, buckets, heavy,
                                                                                                                      blo, blo + merge_buckets, ch, merge_light, logG);
     msm_merge_heavy_kernel<<<HEAVY_WGS, MSM_THREADS, 0, st>>>(gstart, partials, buckets, heavy, ch, heavy + (((size_t)G * P.nb + HEAVY_IDS + 63) & ~(size_t)63));
     if (tm) HIPCHK(hipEventRecord(ev[4], st));
@@ -2061,26 +1850,20 @@ int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, si
         // row + column sums in one launch (one workgroup tree per row / column), then Z and the bit-sliced sums in a second
         uint32_t* Rr = scratch;
         uint32_t* Cc = scratch + (size_t)G * H * 32;
-        uint32_t* const hout = (uint32_t*)ws.h_out + (size_t)PC.hout_group * 64 * 32; // this piece's groups of the pinned result array
-        uint32_t* dest = fold ? hout : texp; // pinned host memory is device-accessible under the same pointer
+        // this piece's groups of the pinned result array: pinned host memory is device-accessible under the same pointer
+        uint32_t* const dest = (uint32_t*)ws.h_out + (size_t)PC.hout_group * 64 * 32;
         const uint32_t zero_words = G * 64 * 32;
-        static const bool two_step_env = [] { const char* e = getenv("BBGPU_ROWCOL_TWO_STEP"); return !e || atoi(e) != 0; }(); // 0: the one-launch quad form for every size
-        if (quad_tail && two_step_env && !bshare && rowcol_two_step(P) && (tp || jobs > 1)) { // alone, the one-launch form is ~20 us shorter
+        if (!bshare && rowcol_two_step(P) && (tp || jobs > 1)) { // alone, the one-launch form is ~20 us shorter
             uint32_t* segs = (uint32_t*)(p + LY.segs);
             const uint32_t seg_lanes = 2 * (H * L / ROWCOL_SEG);
-            msm_rowcol_seg_kernel<<<dim3((seg_lanes + MSM_THREADS - 1) / MSM_THREADS, G), MSM_THREADS, 0, st>>>(buckets, segs, H, L, fold ? dest : nullptr, zero_words);
+            msm_rowcol_seg_kernel<<<dim3((seg_lanes + MSM_THREADS - 1) / MSM_THREADS, G), MSM_THREADS, 0, st>>>(buckets, segs, H, L, dest, zero_words);
             msm_segsum_quad_kernel<<<dim3(H + L, G), 64, 0, st>>>(segs, Rr, Cc, H, L);
-        } else
-        if (quad_tail) msm_rowcol_quad_kernel<<<dim3((bshare ? brow1 - brow0 : H) + L, G), QFOLD_T, 0, st>>>(buckets, Rr, Cc, H, L, fold ? dest : nullptr, zero_words, bshare ? brow0 : 0u,
-                                                                                                   bshare ? brow1 - brow0 : H);
-        else msm_rowcol_kernel<<<dim3(H + L, G), std::max(H, L), 0, st>>>(buckets, Rr, Cc, H, L, fold ? dest : nullptr, zero_words);
+        } else msm_rowcol_quad_kernel<<<dim3((bshare ? brow1 - brow0 : H) + L, G), QFOLD_T, 0, st>>>(buckets, Rr, Cc, H, L, dest, zero_words, bshare ? brow0 : 0u,
+                                                                                                  bshare ? brow1 - brow0 : H);
         if (tm) HIPCHK(hipEventRecord(ev[5], st));
-        if (!fold) HIPCHK(hipMemsetAsync(texp, 0, (size_t)G * 64 * 128, st)); // unused slots = infinity (zz = 0)
-        if (quad_tail) msm_final_quad_kernel<<<dim3(1 + P.hbits + P.lbits, G), QFOLD_T, 0, st>>>(Rr, Cc, dest, P.hbits, P.lbits);
-        else msm_final_kernel<<<dim3(1 + P.hbits + P.lbits, G), std::max(H, L), 0, st>>>(Rr, Cc, dest, P.hbits, P.lbits);
+        msm_final_quad_kernel<<<dim3(1 + P.hbits + P.lbits, G), QFOLD_T, 0, st>>>(Rr, Cc, dest, P.hbits, P.lbits);
         if (tm) HIPCHK(hipEventRecord(ev[6], st));
     }
-    if (!fold) HIPCHK(hipMemcpyAsync((uint32_t*)ws.h_out + (size_t)PC.hout_group * 64 * 32, texp, (size_t)G * 64 * 128, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(S.done, st)); // re-recorded by every piece: the event of the last one covers them all (one stream)
     HIPCHK(launch_check());
     S.npieces++;

@@ -31,13 +31,6 @@
 namespace bbgpu {
 
 using Fr = FrP;
-// Phase ablation for timing experiments (DESIGN_HISTORY 4): a BUILD variant like the JUNK knobs (make variant NAME=nttskip1 EXTRA=-DBBGPU_NTT_DEBUG_SKIP=1),
-// never an environment variable -- the shipped kernels have no switch that changes results.  Bit 0: skip the stages, bit 1: skip the twist / scaling products.
-#ifdef BBGPU_NTT_DEBUG_SKIP
-constexpr uint32_t NTT_DEBUG_SKIP = BBGPU_NTT_DEBUG_SKIP;
-#else
-constexpr uint32_t NTT_DEBUG_SKIP = 0;
-#endif
 constexpr int NTT_VMAX = 48;                 // lazy value bound inside one pass: 6 + 3 * 12 stages + slack
 using FrL = Fe<Fr, 1, NTT_VMAX>;             // LDS-resident element
 // The fused pass keeps LAZIER limbs in LDS (round 3): up to 4 U.  A radix-2^2 group then needs two renormalisations instead of four -- the
@@ -80,9 +73,6 @@ __device__ __forceinline__ void store8(uint32_t* p, const uint32_t (&w)[8])
 constexpr int TW_WORDS = 12;
 __device__ __forceinline__ FeT<Fr> load_tw(const uint32_t* table, uint32_t idx)
 {
-#ifdef BBGPU_NTT_ABL_TW // timing ablation (WRONG results; a build variant like BBGPU_NTT_DEBUG_SKIP): every lane reads entry (idx & mask) -- 0: one line per load
-    idx &= BBGPU_NTT_ABL_TW;
-#endif
     const uint4* q = reinterpret_cast<const uint4*>(table + TW_WORDS * (size_t)idx);
     const uint4 a = q[0], b = q[1], c = q[2];
     FeT<Fr> r;
@@ -190,7 +180,7 @@ template <int FLAGS> __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_ker
     // Intermediate sums stay lazy (no renormalisation between the two stages); same multiplies as radix-2, half the LDS
     // traffic and half the barriers.
     const uint32_t half = S >> 1;
-    uint32_t s = (NTT_DEBUG_SKIP & 1) ? A.log_s : 0;
+    uint32_t s = 0;
     for (; s + 1 < A.log_s; s += 2) {
         const uint32_t m = 1u << s, quarter = S >> 2, ngr = cols * quarter;
         for (uint32_t gq = tid; gq < ngr; gq += NTT_THREADS) {
@@ -290,9 +280,7 @@ template <int FLAGS> __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_ker
         for (int l = 0; l < NL; l++) x.d[l] = lds[l * E + c * S + lds_pos(k)];
         const size_t gidx = (size_t)k * A.out_sa + (size_t)b * A.out_sb;
         uint32_t w[8];
-        if ((NTT_DEBUG_SKIP & 2) != 0) {
-            pack(assume_bound<1, 2>(x), w);
-        } else if constexpr (FLAGS & 2) {
+        if constexpr (FLAGS & 2) {
             const uint32_t ex = b * k; // < n
             auto tw = mul(load_tw(A.twist_lo, ex & ((1u << A.lo_bits) - 1)), load_tw(A.twist_hi, ex >> A.lo_bits));
             auto r = mul(x, tw); // 48 * 2 / 169 + 2 = 2  -> fits 256 bits
@@ -333,9 +321,7 @@ template <int FLAGS, int L> __device__ __forceinline__ void ntt_finish_store(con
     static_assert(L <= 6, "the twist / scaling product takes limbs up to 6 U");
     const size_t gidx = (size_t)k * A.out_sa + (size_t)b * A.out_sb;
     uint32_t w[8];
-    if ((NTT_DEBUG_SKIP & 2) != 0) {
-        pack(assume_bound<L, 2>(x), w);
-    } else if constexpr ((FLAGS & 2) && (FLAGS & 32)) {
+    if constexpr ((FLAGS & 2) && (FLAGS & 32)) {
         // one multiplication per element: the twist factor comes from a table as large as the vector, read exactly like the output is written
         uint32_t tw8[8];
         load8(A.twist_full + 8 * gidx, tw8);
@@ -382,13 +368,6 @@ __device__ __forceinline__ Radix4Out radix4_lazy(const FrS& x0, const FrS& x1, c
     const auto a2 = add(x2, t3);                                                // 5 U
     const auto a3 = sub(x2, t3);                                                // 6 U: the multiplier's limit
     const auto u2 = exact_limbs(mul(w2a, a2)), u3 = exact_limbs(mul(w2b, a3));
-#ifdef BBGPU_NTT_JUNK // issue-model experiment (DESIGN_HISTORY 4): k extra cheap VALU instructions per multiplication of a stage pair, results unused
-    {
-        uint32_t j0 = x0.d[0], j1 = x1.d[0];
-#pragma unroll
-        for (int q = 0; q < 2 * BBGPU_NTT_JUNK; q++) asm volatile("v_and_b32 %0, 0x1fffffff, %1\n\tv_add_u32 %1, %0, %1" : "+v"(j0), "+v"(j1));
-    }
-#endif
     Radix4Out o;
     o.y0 = assume_bound<3, NTT_VMAX>(add(a0, u2));
     o.y2 = assume_bound<4, NTT_VMAX>(sub(a0, u2));
@@ -405,27 +384,19 @@ __device__ __forceinline__ void ntt_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-#ifndef NTT_OCC_ATTR
-#define NTT_OCC_ATTR // A/B knob: e.g. -DNTT_OCC_ATTR='__attribute__((amdgpu_waves_per_eu(5,5)))'
-#endif
-template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) NTT_OCC_ATTR ntt_pass_fused_kernel(NttPassArgs A)
+template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) ntt_pass_fused_kernel(NttPassArgs A)
 {
     extern __shared__ uint32_t lds[]; // [9][E]
     // The plane stride is the TILE size of this instantiation (four elements per thread), a compile-time constant: the nine plane offsets of every LDS
     // access then sit in the instruction's offset field instead of costing a v_add each (round 4: ~30 of a stage pair's 1,049 VALU instructions);
     // a launch whose sub-transforms fill less than a tile (n below the tile size) uses the front of every plane.
-#ifdef BBGPU_NTT_RUNTIME_STRIDE
-    const uint32_t E = A.cols << A.log_s;
-#else
     constexpr uint32_t E = (uint32_t)THREADS * 4u;
-#endif
     const uint32_t S = 1u << A.log_s, cols = A.cols, quarter = S >> 2, ngr = cols * quarter;
     uint32_t bid = blockIdx.x;
     if (A.xcd_remap && (gridDim.x & 7u) == 0) bid = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     const uint32_t b0 = bid * cols;
     const uint32_t tid = threadIdx.x;
     using In = Fe<Fr, 1, 6>; // what unpack() / the pre-scale product really hold
-#ifndef BBGPU_NTT_TW_GLOBAL // (-DBBGPU_NTT_TW_GLOBAL: every twiddle from the L1 / L2-resident table, the round-2 .. 4 form: A/B)
     // LDS-staged twiddles of the middle stage pairs (A.tw_lds: the host asks for it where the launch reserved the room): entry e = table entry e << (log_s - 8),
     // copied by the first 384 threads while everybody's first loads are in flight; the barrier behind phase A publishes it
     uint32_t* const lds_tw = lds + NL * E;
@@ -434,7 +405,6 @@ template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) NTT
         const uint32_t e = tid / 3, part = tid - 3 * e;
         reinterpret_cast<uint4*>(lds_tw + TW_WORDS * e)[part] = reinterpret_cast<const uint4*>(A.tw_sub + TW_WORDS * ((size_t)e << tw_shift))[part];
     }
-#endif
 
     // ---- A: load (+ coset pre-scale) + stage pair (0, 1) ------------------------------------------------------------------
     for (uint32_t gq = tid; gq < ngr; gq += THREADS) {
@@ -458,21 +428,16 @@ template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) NTT
         // row t + j S/4 sits at bit-reversed index 4 bitrev(t) + bitrev2(j): the group of LDS indices 4q .. 4q + 3 is rows (0, 2, 1, 3)
         const uint32_t q = bitrev(t, A.log_s - 2), cb = c * S;
         const auto z0 = exact_limbs(x[0]), z1 = exact_limbs(x[2]), z2 = exact_limbs(x[1]), z3 = exact_limbs(x[3]); // unpack() / products: exact limbs
-        FrS y0, y1, y2, y3;
-        if (NTT_DEBUG_SKIP & 1) {
-            y0 = z0; y1 = z1; y2 = z2; y3 = z3;
-        } else {
-            const auto a0 = add(z0, z1);                                   // 2 U
-            const auto a1 = sub(z0, z1);                                   // 3 U
-            const auto a2 = add(z2, z3);                                   // 2 U
-            const auto a3 = sub(z2, z3);                                   // 3 U
-            const FeT<Fr> w4 = load_tw(A.tw_sub, 1u << (A.log_s - 2));     // w_S^(S/4)
-            const auto u3 = exact_limbs(mul(w4, a3));                      // < 3p
-            y0 = assume_bound<4, NTT_VMAX>(add(a0, a2));                   // 4 U: stays lazy
-            y2 = assume_bound<1, NTT_VMAX>(weak(sub(a0, a2)));             // 6 U -> renormalised
-            y1 = assume_bound<4, NTT_VMAX>(add(a1, u3));                   // 4 U
-            y3 = assume_bound<1, NTT_VMAX>(weak(sub(a1, u3)));             // 5 U -> renormalised
-        }
+        const auto a0 = add(z0, z1);                                   // 2 U
+        const auto a1 = sub(z0, z1);                                   // 3 U
+        const auto a2 = add(z2, z3);                                   // 2 U
+        const auto a3 = sub(z2, z3);                                   // 3 U
+        const FeT<Fr> w4 = load_tw(A.tw_sub, 1u << (A.log_s - 2));     // w_S^(S/4)
+        const auto u3 = exact_limbs(mul(w4, a3));                      // < 3p
+        const FrS y0 = assume_bound<4, NTT_VMAX>(add(a0, a2));         // 4 U: stays lazy
+        const FrS y2 = assume_bound<1, NTT_VMAX>(weak(sub(a0, a2)));   // 6 U -> renormalised
+        const FrS y1 = assume_bound<4, NTT_VMAX>(add(a1, u3));         // 4 U
+        const FrS y3 = assume_bound<1, NTT_VMAX>(weak(sub(a1, u3)));   // 5 U -> renormalised
         const uint32_t e0 = cb + lds_pos(4 * q), e1 = cb + lds_pos(4 * q + 1), e2 = cb + lds_pos(4 * q + 2), e3 = cb + lds_pos(4 * q + 3);
 #pragma unroll
         for (int l = 0; l < NL; l++) {
@@ -487,8 +452,7 @@ template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) NTT
     // ---- B: middle stage pairs in LDS ----------------------------------------------------------------------------------------
     const bool odd = (A.log_s & 1) != 0;
     const uint32_t last_s = odd ? A.log_s - 1 : A.log_s - 2; // first stage of the part fused with the store
-    uint32_t s = (NTT_DEBUG_SKIP & 1) ? last_s : 2;
-    for (; s < last_s; s += 2) {
+    for (uint32_t s = 2; s < last_s; s += 2) {
         const uint32_t m = 1u << s;
         for (uint32_t gq = tid; gq < ngr; gq += THREADS) {
             const uint32_t c = gq >> (A.log_s - 2), q = gq & (quarter - 1);
@@ -503,7 +467,6 @@ template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) NTT
                 x2.d[l] = lds[l * E + e2];
                 x3.d[l] = lds[l * E + e3];
             }
-#ifndef BBGPU_NTT_TW_GLOBAL
             FeT<Fr> w1, w2a, w2b;
             if (A.tw_lds && s <= 6) { // (j << (log_s - 1 - s)) >> (log_s - 8) = j << (7 - s), ...
                 w1 = load_tw_lds(lds_tw, j << (7 - s));
@@ -514,11 +477,6 @@ template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) NTT
                 w2a = load_tw(A.tw_sub, j << (A.log_s - 2 - s));
                 w2b = load_tw(A.tw_sub, (j + m) << (A.log_s - 2 - s));
             }
-#else
-            const FeT<Fr> w1 = load_tw(A.tw_sub, j << (A.log_s - 1 - s));
-            const FeT<Fr> w2a = load_tw(A.tw_sub, j << (A.log_s - 2 - s));
-            const FeT<Fr> w2b = load_tw(A.tw_sub, (j + m) << (A.log_s - 2 - s));
-#endif
             const Radix4Out o = radix4_lazy(x0, x1, x2, x3, w1, w2a, w2b);
             const FrL y3 = weak(o.y3); // 5 U would reach 7 U in the x2 role of the next pair
 #pragma unroll
@@ -531,12 +489,9 @@ template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) NTT
         }
         // The 64 groups of a wave in stage pair (s, s + 1) are an aligned block of 2^(s + 2) * (64 >> s) = 256 elements as long as s <= 6 (lds_pos keeps
         // such blocks), the SAME block in every such pair: between two of them only the wave's own LDS writes have to be visible to it -- the LDS
-        // executes a wave's instructions in order -- and the workgroup's other waves may run ahead or behind (round 5; -DBBGPU_NTT_WG_BARRIERS: A/B).
-#ifndef BBGPU_NTT_WG_BARRIERS
+        // executes a wave's instructions in order -- and the workgroup's other waves may run ahead or behind (round 5).
         if (s + 2 < last_s && s + 2 <= 6) ntt_wave_sync();
-        else
-#endif
-        __syncthreads();
+        else __syncthreads();
     }
 
     // ---- C: last stage pair (even log_s) or last stage (odd) + twist / scaling / canonicalisation + store -----------------------
@@ -555,19 +510,12 @@ template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) NTT
                 x3.d[l] = lds[l * E + cb + lds_pos(j + 3 * m)];
             }
             const uint32_t b = b0 + c;
-            if (NTT_DEBUG_SKIP & 1) {
-                ntt_finish_store<FLAGS>(A, x0, j, b);
-                ntt_finish_store<FLAGS>(A, x1, j + m, b);
-                ntt_finish_store<FLAGS>(A, x2, j + 2 * m, b);
-                ntt_finish_store<FLAGS>(A, x3, j + 3 * m, b);
-            } else {
-                // the outputs go straight into the twist / scaling product or into reduce_value(): no renormalisation at all
-                const Radix4Out o = radix4_lazy(x0, x1, x2, x3, load_tw(A.tw_sub, j << 1), load_tw(A.tw_sub, j), load_tw(A.tw_sub, j + m));
-                ntt_finish_store<FLAGS>(A, o.y0, j, b);
-                ntt_finish_store<FLAGS>(A, o.y1, j + m, b);
-                ntt_finish_store<FLAGS>(A, o.y2, j + 2 * m, b);
-                ntt_finish_store<FLAGS>(A, o.y3, j + 3 * m, b);
-            }
+            // the outputs go straight into the twist / scaling product or into reduce_value(): no renormalisation at all
+            const Radix4Out o = radix4_lazy(x0, x1, x2, x3, load_tw(A.tw_sub, j << 1), load_tw(A.tw_sub, j), load_tw(A.tw_sub, j + m));
+            ntt_finish_store<FLAGS>(A, o.y0, j, b);
+            ntt_finish_store<FLAGS>(A, o.y1, j + m, b);
+            ntt_finish_store<FLAGS>(A, o.y2, j + 2 * m, b);
+            ntt_finish_store<FLAGS>(A, o.y3, j + 3 * m, b);
         }
     } else {
         const uint32_t half = S >> 1, nbf = cols * half; // s = log_s - 1
@@ -582,14 +530,9 @@ template <int FLAGS, int THREADS> __global__ void __launch_bounds__(THREADS) NTT
                 y.d[l] = lds[l * E + cb + lds_pos(j + half)];
             }
             const uint32_t b = b0 + c;
-            if (NTT_DEBUG_SKIP & 1) {
-                ntt_finish_store<FLAGS>(A, x, j, b);
-                ntt_finish_store<FLAGS>(A, y, j + half, b);
-            } else {
-                const auto t = exact_limbs(mul(load_tw(A.tw_sub, j), y));
-                ntt_finish_store<FLAGS>(A, assume_bound<5, NTT_VMAX>(add(x, t)), j, b);      // 5 U
-                ntt_finish_store<FLAGS>(A, assume_bound<6, NTT_VMAX>(sub(x, t)), j + half, b); // 6 U: still a legal factor
-            }
+            const auto t = exact_limbs(mul(load_tw(A.tw_sub, j), y));
+            ntt_finish_store<FLAGS>(A, assume_bound<5, NTT_VMAX>(add(x, t)), j, b);      // 5 U
+            ntt_finish_store<FLAGS>(A, assume_bound<6, NTT_VMAX>(sub(x, t)), j + half, b); // 6 U: still a legal factor
         }
     }
 }
@@ -700,13 +643,6 @@ hipError_t pow_table(uint32_t** out, uint32_t count, const H& base, const H& fac
     return launch_check();
 }
 
-// one multiplication per element for the inter-pass twist (a table as large as the vector) instead of two (two sqrt(n)-sized tables); BBGPU_NTT_FULL_TWIST=0: A/B
-bool full_twist_enabled()
-{
-    static const bool on = [] { const char* e = getenv("BBGPU_NTT_FULL_TWIST"); return !e || atoi(e) != 0; }();
-    return on;
-}
-
 hipError_t build_domain(DomainTables* D, int log2n, hipStream_t st)
 {
     D->log2n = log2n;
@@ -748,7 +684,8 @@ hipError_t build_domain(DomainTables* D, int log2n, hipStream_t st)
         }
         if ((e = pow_table(&D->twist_lo[inv], 1u << D->lo_bits, w, one, st)) != hipSuccess) return e;
         if ((e = pow_table(&D->twist_hi[inv], 1u << (log2n - D->lo_bits), h_pow2k(w, D->lo_bits), one, st)) != hipSuccess) return e;
-        if (full_twist_enabled() && !three && D->log_s2 > 0 && log2n <= NTT_FULL_TWIST_MAX_LOG2N) {
+        // one multiplication per element for the inter-pass twist (a table as large as the vector) instead of two (two sqrt(n)-sized tables)
+        if (!three && D->log_s2 > 0 && log2n <= NTT_FULL_TWIST_MAX_LOG2N) {
             const uint32_t n = 1u << log2n;
             if ((e = table_malloc((void**)&D->twist_full[inv], (size_t)n * 32)) != hipSuccess) return e;
             ntt_twist_full_kernel<<<(n + 255) / 256, 256, 0, st>>>(D->twist_full[inv], D->twist_lo[inv], D->twist_hi[inv], (uint32_t)D->lo_bits, (uint32_t)D->log_s2, n, nullptr, 0u);
@@ -853,23 +790,14 @@ hipError_t get_domain(int log2n, hipStream_t st, DomainTables** out, const Domai
 }
 
 
-bool fused_enabled()
-{
-    static const bool on = [] { const char* e = getenv("BBGPU_NTT_FUSED"); return !e || atoi(e) != 0; }();
-    return on;
-}
-
 // elements per workgroup tile (the fused kernel): 1024 (36 KiB, four workgroups of 256 threads per CU), 2048 (72 KiB, two of 512) or 4096
 // (144 KiB, one of 1024: the strided side of a pass then moves rows twice as wide).  Measured (tools/ntt_sizes.py, one box, fft):
 //   tile   2^12    2^14    2^16    2^18    2^20    2^22    2^24
 //   1024  0.031   0.033   0.035   0.050   0.133   0.531   2.17  ms   <- below 2^20 transforms are latency-bound: twice the workgroups, half the barrier width
 //   2048  0.055   0.052   0.053   0.064   0.130   0.527   2.16
 //   4096  0.089   0.100   0.092   0.102   0.131   0.543   2.38       <- wider rows buy nothing: the passes are not bound by coalescing
-// BBGPU_NTT_TILE overrides.
 uint32_t ntt_tile_elems(int log2n)
 {
-    static const int forced = [] { const char* e = getenv("BBGPU_NTT_TILE"); return e ? atoi(e) : 0; }();
-    if (forced == 1024 || forced == 2048 || forced == 4096) return (uint32_t)forced;
     return log2n > 0 && log2n < 20 ? NTT_LDS_ELEMS / 2 : NTT_LDS_ELEMS;
 }
 
@@ -885,26 +813,19 @@ template <int FLAGS> hipError_t launch_pass(const NttPassArgs& A, hipStream_t st
         (void)hipFuncSetAttribute((const void*)ntt_pass_fused_kernel<FLAGS, NTT_THREADS / 2>, hipFuncAttributeMaxDynamicSharedMemorySize, NTT_LDS_ELEMS * NL * 4);
         attr_set = true;
     }
-    // sub-transforms of 16 points and more take the kernel with load / store fused into the first / last stage pair (BBGPU_NTT_FUSED=0: A/B)
-    if (fused_enabled() && A.log_s >= 4) {
+    // sub-transforms of 16 points and more take the kernel with load / store fused into the first / last stage pair
+    if (A.log_s >= 4) {
         NttPassArgs B = A;
         B.store_b_fast = (A.out_sb == 1 && A.cols > 1) ? 1u : 0u;
         if ((size_t)A.cols * S > (size_t)NTT_LDS_ELEMS) // double tile: one workgroup of 1024 threads per CU (144 KiB of LDS), rows twice as wide
             ntt_pass_fused_kernel<FLAGS, 2 * NTT_THREADS><<<dim3(blocks, A.batch ? A.batch : 1), 2 * NTT_THREADS, (size_t)8 * NTT_THREADS * NL * 4, st>>>(B);
-        else if (A.half_tile && (size_t)A.cols * S <= (size_t)NTT_LDS_ELEMS / 2) { // half tile: four workgroups of 256 threads per CU
-            // BBGPU_NTT_LDS_PAD (tuning experiment): bytes of LDS requested on top of the tile, e.g. 36864 keeps TWO half-tile workgroups per CU (two waves per SIMD)
-            static const size_t pad = [] { const char* e = getenv("BBGPU_NTT_LDS_PAD"); return e ? std::min<size_t>((size_t)2 * NTT_THREADS * NL * 4, (size_t)strtoull(e, nullptr, 0)) : (size_t)0; }(); // tuning experiment: extra LDS bytes per half-tile workgroup (36864 = two workgroups per CU)
-            ntt_pass_fused_kernel<FLAGS, NTT_THREADS / 2><<<dim3(blocks, A.batch ? A.batch : 1), NTT_THREADS / 2, (size_t)2 * NTT_THREADS * NL * 4 + pad, st>>>(B);
-        }
+        else if (A.half_tile && (size_t)A.cols * S <= (size_t)NTT_LDS_ELEMS / 2) // half tile: four workgroups of 256 threads per CU
+            ntt_pass_fused_kernel<FLAGS, NTT_THREADS / 2><<<dim3(blocks, A.batch ? A.batch : 1), NTT_THREADS / 2, (size_t)2 * NTT_THREADS * NL * 4, st>>>(B);
         else {
-#ifndef BBGPU_NTT_TW_GLOBAL
             // Round 5, one box, steady state (profiles/r05_ntt_twlds_ab.txt): 2^22 fft 0.416 -> 0.396 ms (-3.5 ... 5.7 % by kind: its 1024-entry tables, 48 KiB, do not fit the 32 KiB L1),
             // 2^20 level (512 entries do); the 256-thread instance (sizes below 2^20) has no room for the table beside four 36 KiB tiles per CU and keeps the global loads
             B.tw_lds = A.log_s >= 8 ? 1u : 0u; // 128 staged entries cover the pairs up to s = 6 of sub-transforms of 256 points and more
             ntt_pass_fused_kernel<FLAGS, NTT_THREADS><<<dim3(blocks, A.batch ? A.batch : 1), NTT_THREADS, (size_t)4 * NTT_THREADS * NL * 4 + (B.tw_lds ? NTT_TW_LDS_ENTRIES * TW_WORDS * 4 : 0), st>>>(B);
-#else
-            ntt_pass_fused_kernel<FLAGS, NTT_THREADS><<<dim3(blocks, A.batch ? A.batch : 1), NTT_THREADS, (size_t)4 * NTT_THREADS * NL * 4, st>>>(B);
-#endif
         }
     } else {
         if ((size_t)A.cols * S > (size_t)NTT_LDS_ELEMS) return hipErrorInvalidValue; // the double tile exists in the fused kernel only
@@ -1054,11 +975,8 @@ int ntt_device_batch(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_
     NttPassArgs A{};
     A.half_tile = ntt_tile_elems(log2n) == NTT_LDS_ELEMS / 2 ? 1u : 0u;
     A.batch = (uint32_t)batch;
-    {
-        // measured (tools/ntt_sizes.py, fft): 2^22 0.617 -> 0.584 ms, 2^21 0.320 -> 0.302, 2^20 0.153 -> 0.149, 2^18 0.0695 -> 0.0707 (slightly worse)
-        static const int remap = [] { const char* e = getenv("BBGPU_NTT_XCD"); return e ? atoi(e) : -1; }(); // tuning knob: 0 / 1 force
-        A.xcd_remap = remap >= 0 ? (uint32_t)remap : (log2n >= 20 ? 1u : 0u);
-    }
+    // measured (tools/ntt_sizes.py, fft): 2^22 0.617 -> 0.584 ms, 2^21 0.320 -> 0.302, 2^20 0.153 -> 0.149, 2^18 0.0695 -> 0.0707 (slightly worse)
+    A.xcd_remap = log2n >= 20 ? 1u : 0u;
     A.lo_bits = D->lo_bits;
     A.twist_lo = D->twist_lo[inverse];
     A.twist_hi = D->twist_hi[inverse];
@@ -1075,7 +993,7 @@ int ntt_device_batch(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_
         A.log_s = D->log_s1; A.log_b = 0; A.cols = 1; A.log_cols = 0;
         A.in_sa = 1; A.in_sb = 0; A.out_sa = 1; A.out_sb = 0; A.b_fast = 0;
         int flags = last_flags | (pre ? 1 : 0);
-        if (fused_enabled() && D->coset_row[0] && (pre || post_table)) { // coset scalings from a per-index table: one multiplication
+        if (D->coset_row[0] && (pre || post_table)) { // coset scalings from a per-index table: one multiplication
             A.row_scale = D->coset_row[post_table ? 1 : 0];
             flags = pre ? ((last_flags & ~4) | 64) : (16 | 128);
         }
@@ -1095,7 +1013,7 @@ int ntt_device_batch(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_
     A.in_sa = n2; A.in_sb = 1; A.out_sa = n2; A.out_sb = 1; A.b_fast = 1;
     A.twist_full = D->twist_full[inverse];
     int flags1 = 2 | (pre ? 1 : 0) | (A.twist_full ? 32 : 0), flags2 = last_flags;
-    if (fused_enabled() && D->coset_twist[0] && (pre || post_table)) {
+    if (D->coset_twist[0] && (pre || post_table)) {
         // coset variants at one extra multiplication per element: the column-constant half of the scaling rides in the coset twist table,
         // the other half is a row table of pass 1 (coset_fft) or of pass 2's outputs (coset_ifft)
         A.twist_full = D->coset_twist[post_table ? 1 : 0];

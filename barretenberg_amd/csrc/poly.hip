@@ -872,9 +872,7 @@ static int scan_pair_at(int mode, const ScanJob* jobs, int count, uint8_t* base,
     for (int j = 0; j < count; j++)
         if (!jobs[j].out) A3[j].n = 0;
     const dim3 g1((uint32_t)nbmax, count), gb(1, count);
-    static const bool fuse_env = [] { const char* e = getenv("BBGPU_SCAN_FUSED"); return !e || atoi(e) != 0; }(); // tuning knob
-    const bool fused = fuse_env && nbmax <= (size_t)SCAN_T;
-    if (fused) {
+    if (nbmax <= (size_t)SCAN_T) {
         for (int j = 0; j < count; j++) {
             A3[j].fused_nb = (uint32_t)((jobs[j].n + SCAN_BLOCK - 1) / SCAN_BLOCK);
             A3[j].total_out = B[j].bpart;
@@ -887,8 +885,7 @@ static int scan_pair_at(int mode, const ScanJob* jobs, int count, uint8_t* base,
             k_scan_phase1<1><<<g1, SCAN_T, 0, st>>>(A[0], A[1]);
             k_scan_phase3<1><<<g1, SCAN_T, 0, st>>>(A3[0], A3[1]);
         }
-    } else
-    if (nbmax > (size_t)SCAN_BLOCK) {
+    } else if (nbmax > (size_t)SCAN_BLOCK) {
         // more block totals than one workgroup scans: the scan over them (exclusive, same direction; Horner: multiplier z^SCAN_BLOCK) is a scan of this
         // kind itself, run on the scratch behind this level's; its grand total lands where the one-workgroup form leaves it (B.bpart)
         if (mode == 0) k_scan_phase1<0><<<g1, SCAN_T, 0, st>>>(A[0], A[1]);

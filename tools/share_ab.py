@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""one-box comparison of the two N-way splits of a 2^20 MSM at N = 8 (and N = 4): a middle share, 1 .. 4 in flight; env knobs apply (BBGPU_ACC_WGS ...)"""
+"""one-box comparison of the two N-way splits of a 2^20 MSM at N = 8 (and N = 4): a middle share, 1 .. 4 in flight"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
