@@ -346,3 +346,23 @@ def test_oracle_on_skewed_scalars_and_plain_tables(oracle, golden):
     case = g["low_memory_1000"]
     got = oracle.msm_affine(oracle.random_scalars(SCALAR_SEED, case["n"]), table, case["n"])
     assert np.array_equal(got[0:4], limbs(case["x"])) and np.array_equal(got[4:8], limbs(case["y"]))
+
+
+# ---- test infrastructure: the max-lift inputs of tests/test_gpu_ntt_sizes.py --------------------------------------------------
+def test_lift_max_is_the_largest_representative(oracle):
+    """tests.util.lift_max against Python ints: result < 2^256, congruent to the input mod r, and result + r would not fit"""
+    from tests.util import extreme_positions, lift_extremes, lift_max
+    r = FR_MODULUS
+    a = oracle.random_scalars(0x11F7, 3000)
+    a[1::2] = oracle.random_scalars(0x11F8, 1500)  # canonical, and below (raw 256-bit words, any value) at odd rows
+    a[1::2, 3] |= np.uint64(0xC000000000000000)
+    ext = lift_extremes(r) + [(1 << 256) - r, (1 << 256) - r - 1, 6 * r - (1 << 256)]
+    for i, v in zip(extreme_positions(a.shape[0], len(ext)), ext):
+        a[i] = from_int(v)
+    before = [to_int(row) for row in a]
+    got = lift_max(a.copy(), r, chunk=256)  # several chunks, the last one partial
+    for x, row in zip(before, got):
+        y = to_int(row)
+        assert y < 1 << 256 and y >= x and (y - x) % r == 0, hex(x)
+        assert y + r >= 1 << 256, hex(x)
+    assert to_int(got[0]) == 5 * r and to_int(got[extreme_positions(3000, len(ext))[5]]) == (1 << 256) - 1
