@@ -52,6 +52,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_plonk_last_timing", "bbgpu_plonk_prover_destroy", "bbgpu_plonk_challenges_from_proof",
     "bbgpu_host_msm_g1", "bbgpu_host_ntt", "bbgpu_host_fr_evaluate", "bbgpu_host_kate_opening", "bbgpu_host_lagrange_l1_fft",
     "bbgpu_host_divide_by_pseudo_vanishing", "bbgpu_memory_stats", "bbgpu_fault_inject", "bbgpu_fault_stats", "bbgpu_srs_set_validate",
+    "bbgpu_init_devices", "bbgpu_num_contexts", "bbgpu_memory_stats_context",
 ]
 
 
@@ -97,7 +98,9 @@ def _ptr(a):
 
 
 class BbGpu:
-    def __init__(self, device=0, init=True):
+    def __init__(self, device=0, init=True, devices=None):
+        """devices: bind one device context per entry (bbgpu_init_devices; entries may repeat) -- the host-pointer MSMs of at least
+        2^17 points are then split over them.  Otherwise one context on `device` (bbgpu_init)."""
         path = library_path()
         if not os.path.exists(path):
             raise BbGpuError("libbbgpu.so is not built (run __graft_entry__.build()); there is no CPU fallback")
@@ -136,8 +139,14 @@ class BbGpu:
         L.bbgpu_lagrange_l1_fft_device.argtypes = [vp, sz, sz, vp]
         L.bbgpu_divide_by_pseudo_vanishing_device.argtypes = [vp, sz, sz, vp]
         L.bbgpu_permutation_lagrange_base_device.argtypes = [vp, vp, sz, vp]
+        if devices is not None:
+            devices = [int(d) for d in devices]
+            device = devices[0] if devices else device
         self.device = device
-        if init:
+        if init and devices is not None:
+            arr = (C.c_int * max(1, len(devices)))(*devices)
+            self._chk(L.bbgpu_init_devices(arr, len(devices)))
+        elif init:
             self._chk(L.bbgpu_init(device))
 
     def _chk(self, rc):
@@ -248,10 +257,23 @@ class BbGpu:
         self._chk(self.lib.bbgpu_srs_cache_stats(C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
-    def memory_stats(self):
-        """device / pinned bytes the library holds for the life of the process, as a dict (bbgpu_memory_stats)"""
+    def init_devices(self, devices):
+        """bind one device context per entry of `devices` (bbgpu_init_devices)"""
+        devices = [int(d) for d in devices]
+        arr = (C.c_int * max(1, len(devices)))(*devices)
+        self._chk(self.lib.bbgpu_init_devices(arr, len(devices)))
+
+    def num_contexts(self):
+        return int(self.lib.bbgpu_num_contexts())
+
+    def memory_stats(self, context=None):
+        """device / pinned bytes the library holds for the life of the process, as a dict (bbgpu_memory_stats: the sum over the device
+        contexts; context=k: context k's share, bbgpu_memory_stats_context)"""
         info = MemoryInfo()
-        self._chk(self.lib.bbgpu_memory_stats(C.byref(info)))
+        if context is None:
+            self._chk(self.lib.bbgpu_memory_stats(C.byref(info)))
+        else:
+            self._chk(self.lib.bbgpu_memory_stats_context(int(context), C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in MemoryInfo._fields_}
 
     def fault_inject(self, spec):

@@ -63,6 +63,14 @@ struct MsmPiece {
     uint32_t hout_group = 0; // first 64-slot group of this piece in ws.h_out
     bool trivial = false;
 };
+// "accumulation ended" events of the last SIZE timed MSMs of one device context, in issue order (msm.hip acc_ring_record / finish_timing).  One ring
+// per context, shared by its slots: the contexts of bbgpu_init_devices issue concurrently, and may sit on different devices.
+struct AccRing {
+    static constexpr int SIZE = 8;
+    hipEvent_t end[SIZE] = {};
+    uint64_t seq = 0; // number of timed accumulations issued so far
+    void release();
+};
 constexpr int MSM_MAX_JOBS = 4;        // MSMs over the same points issued as one batch (one bucket set each)
 constexpr int MSM_MAX_PIECES = 64;      // per slot: an MSM without a free helper slot keeps all its pieces on one
 constexpr uint32_t MSM_HOUT_GROUPS = 256; // 64-slot groups of the pinned result array (pieces x jobs, or the windows of one table-less piece): 2 MiB per slot
@@ -80,7 +88,8 @@ struct MsmSlot {
     bool pending = false, trivial = false, timed = false, timed_light = false;
     size_t n = 0;
     uint32_t jobs = 1;
-    uint64_t acc_seq = 0; // position of this MSM's accumulation in the process-wide sequence of timed accumulations (0 = none)
+    uint64_t acc_seq = 0; // position of this MSM's accumulation in its context's sequence of timed accumulations (0 = none)
+    AccRing* acc_ring = nullptr; // capi.hip: the ring of the slot's context (null: no timed accumulation is recorded)
     // set by the caller before an issue: other MSMs are in flight, so this one is paced by the instructions it issues, not by its dependent chain
     // (msm_issue_batch then takes longer chunks and the two-step row / column sums)
     bool throughput = false;

@@ -1,6 +1,7 @@
 // capi.hip -- the C-ABI of libbbgpu.so (include/bbgpu.h): context, SRS registry, host<->device staging.
-// One process drives one GPU (bbgpu_init(device)); all entry points are serialised by one mutex, which also makes the
-// reference's concurrent pippenger() calls from an OpenMP region (scalar_multiplication.cpp:731-738) safe.
+// One process drives one GPU (bbgpu_init(device)), or several device contexts (bbgpu_init_devices) over which the host-pointer MSMs are split; all
+// entry points are serialised by one mutex, which also makes the reference's concurrent pippenger() calls from an OpenMP region
+// (scalar_multiplication.cpp:731-738) safe.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +12,10 @@
 #include <string.h>
 #include <time.h>
 #include <atomic>
+#include <condition_variable>
+#include <exception>
+#include <functional>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -20,6 +25,7 @@
 #include "host_small.hpp"
 #include "host_fallback.hpp"
 #include "host_copy_pool.hpp"
+#include "multi_plan.hpp"
 #include "poly.h"
 
 namespace bbgpu {
@@ -172,8 +178,6 @@ hipError_t launch_check()
 }
 void fault_absorbed() { fault().absorbed.fetch_add(1); }
 
-static host::CopyPool g_copy_pool; // CPU copies into / out of the pinned staging buffers (host_copy_pool.hpp); also hashes point tables (exact cache mode)
-
 namespace {
 
 struct SrsEntry {
@@ -266,10 +270,26 @@ struct Context {
     hipEvent_t h_stage_free[HOST_RING] = {};
     unsigned h_stage_next = 0;
     size_t host_stage_max = (size_t)8 << 20; // BBGPU_STAGE_MAX_BYTES: larger buffers are handed to hipMemcpyAsync as they are
+    bool stage_env_read = false;             // the two staging variables above have been read (once per context)
+    host::CopyPool copy_pool; // CPU copies into / out of the pinned staging buffers (host_copy_pool.hpp); also hashes point tables (exact cache mode)
+    AccRing acc_ring;         // "accumulation ended" events of this context's timed MSMs (msm.hip)
+    // Set while this context runs its slice of a split host-pointer MSM: the number of points of the WHOLE call, whose window size the slice's tables
+    // take (as bbgpu_set_point_share does, without touching the caller's share settings).  0 otherwise.
+    size_t slice_of_n = 0;
+    std::recursive_mutex own_mu; // the lock of contexts 1 .. (context 0's is g_mu): its staging buffers, copy pool, initialisation
 };
 
+// Device contexts (bbgpu_init_devices).  Context 0 is what every entry point works on; the others exist only for the split host-pointer MSMs, each
+// driven by a persistent worker thread of its own (MultiWorker below).  A thread's CURRENT context is context 0 unless it is such a worker.
+// g_mu is the entry lock of the public API and the lock of context 0.  A split call holds it while the workers run: so the helpers a worker calls
+// (ensure_init, host_to_device, device_to_host_sync, host_stage_release) take the lock of the CURRENT context, never g_mu itself.  While g_mu is free
+// every worker is idle, so an entry point that holds it may read any context.
 std::recursive_mutex g_mu;
-Context g_ctx;
+Context g_ctxs[BBGPU_MAX_CONTEXTS];
+int g_num_ctx = 1; // contexts bound by bbgpu_init_devices (1: bbgpu_init, or nothing bound yet)
+thread_local int t_ctx = 0;
+inline Context& ctx() { return g_ctxs[t_ctx]; }
+inline std::recursive_mutex& ctx_lock() { return t_ctx == 0 ? g_mu : ctx().own_mu; }
 
 #define CHK(x)                                                                                                         \
     do {                                                                                                               \
@@ -282,30 +302,37 @@ Context g_ctx;
 
 void read_host_env()
 {
-    // the staging knobs are read once per process whatever else happened; the two thresholds only while bbgpu_set_host_thresholds() has not set them
-    // (round 5: that call used to switch off the reading of ALL four variables)
-    static bool staging_read = false;
-    const bool thresholds = !g_ctx.host_env_read;
-    g_ctx.host_env_read = true;
-    if (thresholds) {
-        if (const char* e = getenv("BBGPU_HOST_MSM_MAX")) g_ctx.host_msm_max = atoi(e);
-        if (const char* e = getenv("BBGPU_HOST_NTT_MAX")) g_ctx.host_ntt_max = std::min(64, atoi(e));
+    // the staging knobs are read once per context whatever else happened; the two thresholds only while bbgpu_set_host_thresholds() has not set them
+    // (round 5: that call used to switch off the reading of ALL four variables).  Every context reads the same variables, so all agree.
+    if (!ctx().host_env_read) {
+        ctx().host_env_read = true;
+        if (const char* e = getenv("BBGPU_HOST_MSM_MAX")) ctx().host_msm_max = atoi(e);
+        if (const char* e = getenv("BBGPU_HOST_NTT_MAX")) ctx().host_ntt_max = std::min(64, atoi(e));
     }
-    if (staging_read) return;
-    staging_read = true;
-    if (const char* e = getenv("BBGPU_STAGE_MAX_BYTES")) g_ctx.host_stage_max = (size_t)strtoull(e, nullptr, 0);
-    if (const char* e = getenv("BBGPU_STAGE_CHUNK_BYTES")) g_ctx.host_chunk = std::min(Context::HOST_CHUNK, std::max((size_t)64 << 10, (size_t)strtoull(e, nullptr, 0))); // testing hook: the chunk size of the staging copies
+    if (ctx().stage_env_read) return;
+    ctx().stage_env_read = true;
+    if (const char* e = getenv("BBGPU_STAGE_MAX_BYTES")) ctx().host_stage_max = (size_t)strtoull(e, nullptr, 0);
+    if (const char* e = getenv("BBGPU_STAGE_CHUNK_BYTES")) ctx().host_chunk = std::min(Context::HOST_CHUNK, std::max((size_t)64 << 10, (size_t)strtoull(e, nullptr, 0))); // testing hook: the chunk size of the staging copies
+}
+
+int hip_device_count()
+{
+    // asked once per process: without a device every call would repeat the runtime's probe of the machine (~10 ms each; the shim's host
+    // answers would be paced by it)
+    static const int cnt = [] { int c = 0; return hipGetDeviceCount(&c) == hipSuccess ? c : 0; }();
+    return cnt;
 }
 
 int ensure_init()
 {
-    if (g_ctx.ready) {
+    std::lock_guard<std::recursive_mutex> lk(ctx_lock());
+    if (ctx().ready) {
         // HIP's current device is PER THREAD (device 0 in a fresh one): a caller's worker thread -- the reference's OpenMP threads around pippenger(),
         // bench.py's issuing thread on rank r > 0 -- must allocate and launch on the device this process is bound to, not on device 0
         static thread_local int bound_device = -1;
-        if (bound_device != g_ctx.device) {
-            CHK(hipSetDevice(g_ctx.device));
-            bound_device = g_ctx.device;
+        if (bound_device != ctx().device) {
+            CHK(hipSetDevice(ctx().device));
+            bound_device = ctx().device;
         }
         return BBGPU_OK;
     }
@@ -315,24 +342,24 @@ int ensure_init()
     // MSM with 8 queues, a 1/8 share four in flight 0.232 -> 0.205).  16: the eight slot streams, the library's own and the caller's.  Only effective when this is the process's first HIP call; a host
     // program that initialises HIP earlier sets the variable itself (bench.py and the Python binding do).
     (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    // asked once per process: without a device every call would repeat the runtime's probe of the machine (~10 ms each; the shim's host
-    // answers would be paced by it)
-    static const int cnt = [] { int c = 0; return hipGetDeviceCount(&c) == hipSuccess ? c : 0; }();
-    if (cnt == 0) {
+    if (hip_device_count() == 0) {
         set_error("no HIP device available: the GPU entry points of libbbgpu have no CPU fallback");
         return BBGPU_ERR_HIP;
     }
-    CHK(hipSetDevice(g_ctx.device));
-    CHK(hipStreamCreateWithFlags(&g_ctx.stream, hipStreamNonBlocking));
+    CHK(hipSetDevice(ctx().device));
+    CHK(hipStreamCreateWithFlags(&ctx().stream, hipStreamNonBlocking));
     // the slot streams are made HERE, one after the other: the runtime deals streams to hardware queues in creation order, and a slot
     // stream created later (first use of a third slot, in a process that has made other streams meanwhile) can land on the queue of another slot
-    for (auto& sl : g_ctx.slot)
+    for (auto& sl : ctx().slot) {
         if (!sl.stream) CHK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-    CHK(hipEventCreateWithFlags(&g_ctx.shared_done, hipEventDisableTiming));
-    g_ctx.shared_used = false;
-    if (const char* e = getenv("BBGPU_SRS_CACHE_BYTES")) g_ctx.srs_cache_cap = (size_t)strtoull(e, nullptr, 0);
-    if (const char* e = getenv("BBGPU_SRS_VALIDATE")) g_ctx.srs_validate_full = !strcmp(e, "full"); // full: host-pointer MSMs re-hash every row they use on every call (exact, ~+0.1 ms per 2^16 points hidden behind the kernels); default: 16 sampled rows
-    g_ctx.ready = true;
+        sl.acc_ring = &ctx().acc_ring;
+    }
+    CHK(hipEventCreateWithFlags(&ctx().shared_done, hipEventDisableTiming));
+    ctx().shared_used = false;
+    // the cap holds for each device context on its own (bbgpu_init_devices)
+    if (const char* e = getenv("BBGPU_SRS_CACHE_BYTES")) ctx().srs_cache_cap = (size_t)strtoull(e, nullptr, 0);
+    if (const char* e = getenv("BBGPU_SRS_VALIDATE")) ctx().srs_validate_full = !strcmp(e, "full"); // full: host-pointer MSMs re-hash every row they use on every call (exact, ~+0.1 ms per 2^16 points hidden behind the kernels); default: 16 sampled rows
+    ctx().ready = true;
     return BBGPU_OK;
 }
 
@@ -341,14 +368,14 @@ int ensure_init()
 // back on two streams then run one after the other instead of overwriting each other's intermediate data.
 int shared_begin(hipStream_t st)
 {
-    if (g_ctx.shared_used && g_ctx.shared_last != st) CHK(hipStreamWaitEvent(st, g_ctx.shared_done, 0));
+    if (ctx().shared_used && ctx().shared_last != st) CHK(hipStreamWaitEvent(st, ctx().shared_done, 0));
     return BBGPU_OK;
 }
 int shared_end(hipStream_t st)
 {
-    CHK(hipEventRecord(g_ctx.shared_done, st));
-    g_ctx.shared_last = st;
-    g_ctx.shared_used = true;
+    CHK(hipEventRecord(ctx().shared_done, st));
+    ctx().shared_last = st;
+    ctx().shared_used = true;
     return BBGPU_OK;
 }
 
@@ -378,39 +405,39 @@ int grow(uint64_t** buf, size_t* cap, size_t bytes)
 
 int bind_calling_thread()
 {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    return ensure_init();
+    return ensure_init(); // takes the current context's lock
 }
 static int host_stage_ensure()
 {
     for (int k = 0; k < Context::HOST_RING; k++)
-        if (!g_ctx.h_stage[k]) {
-            CHK(hipHostMalloc(&g_ctx.h_stage[k], Context::HOST_CHUNK, hipHostMallocDefault));
-            CHK(hipEventCreateWithFlags(&g_ctx.h_stage_free[k], hipEventDisableTiming));
+        if (!ctx().h_stage[k]) {
+            CHK(hipHostMalloc(&ctx().h_stage[k], Context::HOST_CHUNK, hipHostMallocDefault));
+            CHK(hipEventCreateWithFlags(&ctx().h_stage_free[k], hipEventDisableTiming));
         }
     return BBGPU_OK;
 }
-// Both directions take the library mutex themselves (recursive: the capi entry points already hold it): the resident prover's uploads
-// (plonk.hip, which holds only its own mutex) would otherwise race with a transform or an MSM of another thread on the staging buffers,
-// their events and the single-producer copy pool.  Lock order everywhere: the prover's mutex first, then this one.
+// Both directions take the current context's lock themselves -- context 0's is the library mutex (recursive: the capi entry points already hold it):
+// the resident prover's uploads (plonk.hip, which holds only its own mutex) would otherwise race with a transform or an MSM of another thread on the
+// staging buffers, their events and the single-producer copy pool.  A worker of a split MSM takes its own context's lock (the caller holds g_mu).
+// Lock order everywhere: the prover's mutex first, then g_mu, then a worker context's lock.
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st)
 {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::lock_guard<std::recursive_mutex> lk(ctx_lock());
     read_host_env();
     if (bytes == 0) return BBGPU_OK;
-    if (bytes > g_ctx.host_stage_max) {
+    if (bytes > ctx().host_stage_max) {
         CHK(h2d_async(d_dst, h_src, bytes, st));
         return BBGPU_OK;
     }
     if (int rc = host_stage_ensure()) return rc;
-    const size_t CH = g_ctx.host_chunk;
+    const size_t CH = ctx().host_chunk;
     for (size_t off = 0; off < bytes; off += CH) {
         const size_t len = std::min(CH, bytes - off);
-        const int k = (int)(g_ctx.h_stage_next++ % Context::HOST_RING);
-        CHK(hipEventSynchronize(g_ctx.h_stage_free[k])); // the DMA that last read this buffer has finished (no-op before its first use)
-        g_copy_pool.copy(g_ctx.h_stage[k], (const char*)h_src + off, len);
-        CHK(h2d_async((char*)d_dst + off, g_ctx.h_stage[k], len, st));
-        CHK(hipEventRecord(g_ctx.h_stage_free[k], st));
+        const int k = (int)(ctx().h_stage_next++ % Context::HOST_RING);
+        CHK(hipEventSynchronize(ctx().h_stage_free[k])); // the DMA that last read this buffer has finished (no-op before its first use)
+        ctx().copy_pool.copy(ctx().h_stage[k], (const char*)h_src + off, len);
+        CHK(h2d_async((char*)d_dst + off, ctx().h_stage[k], len, st));
+        CHK(hipEventRecord(ctx().h_stage_free[k], st));
     }
     return BBGPU_OK;
 }
@@ -419,10 +446,10 @@ int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st)
 // whole (nothing touched: an ordinary error the shim answers on the host) or gone (BBGPU_ERR_LOST).
 int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_t st, bool* touched)
 {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::lock_guard<std::recursive_mutex> lk(ctx_lock());
     read_host_env();
     if (touched) *touched = false;
-    if (bytes > g_ctx.host_stage_max) {
+    if (bytes > ctx().host_stage_max) {
         CHK(d2h_async(h_dst, d_src, bytes, st));
         if (touched) *touched = true; // the DMA engine owns the destination from here on
         CHK(hipStreamSynchronize(st));
@@ -430,16 +457,16 @@ int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_
     }
     if (int rc = host_stage_ensure()) return rc;
     // up to HOST_RING - 1 chunks are on the link (or queued for it) while one is copied out of its pinned buffer
-    const size_t CH = g_ctx.host_chunk;
+    const size_t CH = ctx().host_chunk;
     const size_t chunks = (bytes + CH - 1) / CH;
     constexpr size_t AHEAD = Context::HOST_RING - 1;
     int kbuf[Context::HOST_RING] = {};
     auto enqueue = [&](size_t c) -> int {
-        const int k = (int)(g_ctx.h_stage_next++ % Context::HOST_RING);
+        const int k = (int)(ctx().h_stage_next++ % Context::HOST_RING);
         kbuf[c % Context::HOST_RING] = k;
-        CHK(hipEventSynchronize(g_ctx.h_stage_free[k]));
-        CHK(d2h_async(g_ctx.h_stage[k], (const char*)d_src + c * CH, std::min(CH, bytes - c * CH), st));
-        CHK(hipEventRecord(g_ctx.h_stage_free[k], st));
+        CHK(hipEventSynchronize(ctx().h_stage_free[k]));
+        CHK(d2h_async(ctx().h_stage[k], (const char*)d_src + c * CH, std::min(CH, bytes - c * CH), st));
+        CHK(hipEventRecord(ctx().h_stage_free[k], st));
         return BBGPU_OK;
     };
     if (chunks == 0) {
@@ -455,21 +482,21 @@ int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_
             queued++;
         }
         const int k = kbuf[c % Context::HOST_RING];
-        CHK(hipEventSynchronize(g_ctx.h_stage_free[k]));
+        CHK(hipEventSynchronize(ctx().h_stage_free[k]));
         if (touched) *touched = true;
-        g_copy_pool.copy((char*)h_dst + c * CH, g_ctx.h_stage[k], std::min(CH, bytes - c * CH));
+        ctx().copy_pool.copy((char*)h_dst + c * CH, ctx().h_stage[k], std::min(CH, bytes - c * CH));
     }
     return BBGPU_OK;
 }
 void host_stage_release()
 {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    g_copy_pool.shutdown();
+    std::lock_guard<std::recursive_mutex> lk(ctx_lock());
+    ctx().copy_pool.shutdown();
     for (int k = 0; k < Context::HOST_RING; k++) {
-        if (g_ctx.h_stage[k]) (void)hipHostFree(g_ctx.h_stage[k]);
-        if (g_ctx.h_stage_free[k]) (void)hipEventDestroy(g_ctx.h_stage_free[k]);
-        g_ctx.h_stage[k] = nullptr;
-        g_ctx.h_stage_free[k] = nullptr;
+        if (ctx().h_stage[k]) (void)hipHostFree(ctx().h_stage[k]);
+        if (ctx().h_stage_free[k]) (void)hipEventDestroy(ctx().h_stage_free[k]);
+        ctx().h_stage[k] = nullptr;
+        ctx().h_stage_free[k] = nullptr;
     }
 }
 
@@ -515,19 +542,21 @@ int add_srs(const uint64_t* host_ptr, size_t n, uint32_t* d_srs, bool auto_regis
     e.d_srs = d_srs;
     e.live = true;
     e.auto_registered = auto_registered;
-    e.validate_full = g_ctx.srs_validate_full;
-    e.last_use = ++g_ctx.use_clock;
+    e.validate_full = ctx().srs_validate_full;
+    e.last_use = ++ctx().use_clock;
     if (host_ptr) {
         e.row_hash.resize(n);
         struct Job { const uint64_t* p; uint64_t* h; } job{ host_ptr, e.row_hash.data() };
-        g_copy_pool.for_range(n, (size_t)1 << 14, [](void* c, size_t lo, size_t hi) {
+        ctx().copy_pool.for_range(n, (size_t)1 << 14, [](void* c, size_t lo, size_t hi) {
             const Job* j = static_cast<const Job*>(c);
             for (size_t i = lo; i < hi; i++) j->h[i] = hash_row(j->p + i * 16);
         }, &job);
     }
     // a rank's slice of a point-range split takes the window size of the whole MSM: measured on 1/4 and 1/8 slices of 2^20 points, four in flight,
     // 15-bit windows 0.356 / 0.189 ms per step, 17-bit 0.334 / 0.188 (16-bit at 1/8: 0.182) -- tools/slice_ab.py
-    const size_t n_for_c = n * (size_t)g_ctx.point_world;
+    // (the slice a context holds of a split host-pointer MSM, bbgpu_init_devices, takes the window size of the whole call in the same way)
+    const bool slice = ctx().slice_of_n > n || ctx().point_world > 1;
+    const size_t n_for_c = ctx().slice_of_n > n ? ctx().slice_of_n : n * (size_t)ctx().point_world;
     int c = msm_choose_c(n_for_c);
     // with tables every window feeds one shared bucket set, so wider windows only cost bucket-reduction depth while each one
     // saved is n fewer mixed additions: measured on the resident prover (tools/plonk_bench.py), 2^16 gates 3.58 ms at c = 12,
@@ -540,7 +569,7 @@ int add_srs(const uint64_t* host_ptr, size_t n, uint32_t* d_srs, bool auto_regis
     if (n_for_c >= ((size_t)1 << 19)) c = 17;
     // ... but a slice of fewer than 2^18 points pays the row / column sums over 2^16 buckets for ~30 entries per bucket: 16-bit windows (2^15 buckets, one window
     // more) measured 0.179 against 0.182 ms per step at 2^17 points, four in flight, three alternating runs (15-bit windows: 0.189)
-    if (g_ctx.point_world > 1 && c == 17 && n < ((size_t)1 << 18)) c = 16;
+    if (slice && c == 17 && n < ((size_t)1 << 18)) c = 16;
     if (const char* ev = getenv("BBGPU_TABLE_C")) c = std::min(17, std::max(4, atoi(ev))); // window size of the tables
     const int W = msm_num_windows(c);
     // segments: as few as the 24-bit row index allows, equal lengths (multiples of 8: the sort reads eight digits per load).  One up to 2^20 points;
@@ -552,23 +581,23 @@ int add_srs(const uint64_t* host_ptr, size_t n, uint32_t* d_srs, bool auto_regis
     if (const char* v = getenv("BBGPU_TABLE_SEG_POINTS")) seg_cap = std::min(seg_cap, std::max<size_t>(64, (size_t)strtoull(v, nullptr, 0) & ~(size_t)7));
     const size_t nseg = (n + seg_cap - 1) / seg_cap;
     const size_t seg_n = nseg <= 1 ? n : ((((n + nseg - 1) / nseg) + 7) & ~(size_t)7);
-    const bool want_tab = g_ctx.precompute && n >= 1024 && (nseg == 1 || ((uint64_t)n * W * 64 <= tab_max_bytes && nseg <= (size_t)MSM_MAX_PIECES));
+    const bool want_tab = ctx().precompute && n >= 1024 && (nseg == 1 || ((uint64_t)n * W * 64 <= tab_max_bytes && nseg <= (size_t)MSM_MAX_PIECES));
     // a rank of an N-way row split touches windows [floor(W r / N), ceil(W (r + 1) / N)) only (bbgpu_set_table_share)
-    const int twb = (int)((int64_t)W * g_ctx.share_rank / g_ctx.share_world);
-    const int twe = (int)(((int64_t)W * (g_ctx.share_rank + 1) + g_ctx.share_world - 1) / g_ctx.share_world);
+    const int twb = (int)((int64_t)W * ctx().share_rank / ctx().share_world);
+    const int twe = (int)(((int64_t)W * (ctx().share_rank + 1) + ctx().share_world - 1) / ctx().share_world);
     e.bytes = n * 64 + (want_tab ? (size_t)(twe - twb) * n * 64 : 0);
     if (auto_registered) {
-        for (auto& o : g_ctx.srs)
+        for (auto& o : ctx().srs)
             if (o.live && o.auto_registered && o.host_ptr && host_ptr && ranges_overlap(o, host_ptr, n)) free_entry(o);
         for (;;) {
             size_t held = 0;
             SrsEntry* lru = nullptr;
-            for (auto& o : g_ctx.srs)
+            for (auto& o : ctx().srs)
                 if (o.live && o.auto_registered) {
                     held += o.bytes;
                     if (!lru || o.last_use < lru->last_use) lru = &o;
                 }
-            if (!lru || held + e.bytes <= g_ctx.srs_cache_cap) break;
+            if (!lru || held + e.bytes <= ctx().srs_cache_cap) break;
             free_entry(*lru);
         }
     }
@@ -577,7 +606,7 @@ int add_srs(const uint64_t* host_ptr, size_t n, uint32_t* d_srs, bool auto_regis
             SrsEntry::TabSeg sg;
             sg.first = first;
             sg.n = std::min(seg_n, n - first);
-            int rc = srs_build_table(d_srs + first * 16, sg.n, c, W, twb, twe, &sg.d_tab_alloc, &sg.d_tab, g_ctx.stream);
+            int rc = srs_build_table(d_srs + first * 16, sg.n, c, W, twb, twe, &sg.d_tab_alloc, &sg.d_tab, ctx().stream);
             if (rc) {
                 // no room for the window tables (a shared GPU): the points stay resident and the MSMs over them take one bucket set per window --
                 // slower (1.8 ms instead of 1.14 at 2^20) but on the GPU, instead of failing the registration and sending the caller to the host
@@ -605,13 +634,13 @@ int add_srs(const uint64_t* host_ptr, size_t n, uint32_t* d_srs, bool auto_regis
     // a long-lived process that keeps re-registering tables on first sight must not grow the registry by one entry per eviction: dead slots
     // whose index no caller ever held are taken again
     if (auto_registered)
-        for (size_t k = 0; k < g_ctx.srs.size(); k++)
-            if (!g_ctx.srs[k].live && !g_ctx.srs[k].handle_exposed) {
-                g_ctx.srs[k] = std::move(e);
+        for (size_t k = 0; k < ctx().srs.size(); k++)
+            if (!ctx().srs[k].live && !ctx().srs[k].handle_exposed) {
+                ctx().srs[k] = std::move(e);
                 return (int)k;
             }
-    g_ctx.srs.push_back(std::move(e));
-    return (int)g_ctx.srs.size() - 1;
+    ctx().srs.push_back(std::move(e));
+    return (int)ctx().srs.size() - 1;
 }
 int entry_windows(const SrsEntry& e, size_t n)
 {
@@ -627,10 +656,10 @@ bool windows_resident(const SrsEntry& e, int wb, int we)
 // full-size pipeline), the others take whatever else is in flight (shares of a split MSM, small MSMs: up to eight).  -1: all busy.
 int pick_slot()
 {
-    int order[Context::NSLOT] = { g_ctx.next_slot, g_ctx.next_slot ^ 1 };
+    int order[Context::NSLOT] = { ctx().next_slot, ctx().next_slot ^ 1 };
     for (int k = 2; k < Context::NSLOT; k++) order[k] = k;
     for (int k = 0; k < Context::NSLOT; k++)
-        if (!g_ctx.slot[order[k]].pending) return order[k];
+        if (!ctx().slot[order[k]].pending) return order[k];
     set_error("all %d MSM slots are in flight: call bbgpu_msm_g1_wait first", Context::NSLOT);
     return -1;
 }
@@ -641,7 +670,7 @@ int free_slots(int* out, int want)
 {
     int got = 0;
     for (int k = 0; k < Context::NSLOT && got < want; k++)
-        if (!g_ctx.slot[k].pending) out[got++] = k;
+        if (!ctx().slot[k].pending) out[got++] = k;
     return got;
 }
 // the slots a synchronous entry point cycles its jobs / ranges through: marked for the duration of the call, so that a multi-piece job on one of
@@ -650,13 +679,13 @@ struct SlotReservation {
     int a, b;
     SlotReservation(const int* sl, int n) : a(n > 0 ? sl[0] : -1), b(n > 1 ? sl[1] : -1)
     {
-        if (a >= 0) g_ctx.slot[a].reserved = true;
-        if (b >= 0) g_ctx.slot[b].reserved = true;
+        if (a >= 0) ctx().slot[a].reserved = true;
+        if (b >= 0) ctx().slot[b].reserved = true;
     }
     ~SlotReservation()
     {
-        if (a >= 0) g_ctx.slot[a].reserved = false;
-        if (b >= 0) g_ctx.slot[b].reserved = false;
+        if (a >= 0) ctx().slot[a].reserved = false;
+        if (b >= 0) ctx().slot[b].reserved = false;
     }
 };
 int ensure_slot_stream(MsmSlot& S)
@@ -694,16 +723,16 @@ constexpr int MAX_POINT_PIECES = MSM_MAX_PIECES;
 bool others_pending(const MsmSlot* a, const MsmSlot* b = nullptr)
 {
     for (int k = 0; k < Context::NSLOT; k++)
-        if (&g_ctx.slot[k] != a && &g_ctx.slot[k] != b && g_ctx.slot[k].pending) return true;
+        if (&ctx().slot[k] != a && &ctx().slot[k] != b && ctx().slot[k].pending) return true;
     return false;
 }
 // collects whatever slot t (and its helper) still has in flight and forgets it: error paths
 void drain_ticket(int t)
 {
-    MsmSlot& S = g_ctx.slot[t];
+    MsmSlot& S = ctx().slot[t];
     host::Xyzz dump[MSM_MAX_JOBS];
     if (S.helper >= 0) {
-        MsmSlot& H = g_ctx.slot[S.helper];
+        MsmSlot& H = ctx().slot[S.helper];
         if (H.pending) (void)msm_finish_batch(H, dump, nullptr);
         H.is_helper = false;
         S.helper = -1;
@@ -718,7 +747,7 @@ void drain_ticket(int t)
 // both slots' pieces.
 int issue_ticket(int t, const SrsEntry& e, size_t off, const uint64_t* const* d_scalars_v, int jobs, size_t n, int wb, int we, hipStream_t st)
 {
-    MsmSlot& S = g_ctx.slot[t];
+    MsmSlot& S = ctx().slot[t];
     S.helper = -1;
     S.append = false;
     if (!windows_resident(e, wb, we)) return BBGPU_ERR_STATE;
@@ -731,7 +760,7 @@ int issue_ticket(int t, const SrsEntry& e, size_t off, const uint64_t* const* d_
     if (np == 1) {
         S.throughput = others_pending(&S);
         const uint32_t* tab = pc[0].seg ? pc[0].seg->d_tab + pc[0].off_in_seg * 16 : nullptr;
-        return msm_issue_batch(S, e.d_srs + off * 16, tab, pc[0].seg ? pc[0].seg->n : e.n, e.tab_c, d_scalars_v, jobs, n, wb, we, st, g_ctx.timing);
+        return msm_issue_batch(S, e.d_srs + off * 16, tab, pc[0].seg ? pc[0].seg->n : e.n, e.tab_c, d_scalars_v, jobs, n, wb, we, st, ctx().timing);
     }
     // several pieces: a helper slot for every other one, if any slot is free
     int h = -1;
@@ -740,16 +769,16 @@ int issue_ticket(int t, const SrsEntry& e, size_t off, const uint64_t* const* d_
         if (t < 2) order[cnt++] = t ^ 1; // the pair the two-deep pipeline of large MSMs uses
         for (int k = Context::NSLOT - 1; k >= 2; --k) order[cnt++] = k; // from the top: the low ones are what the next tickets take
         for (int k = 0; k < cnt && h < 0; k++)
-            if (order[k] != t && !g_ctx.slot[order[k]].pending && !g_ctx.slot[order[k]].reserved) h = order[k];
+            if (order[k] != t && !ctx().slot[order[k]].pending && !ctx().slot[order[k]].reserved) h = order[k];
     }
-    MsmSlot* H = h >= 0 ? &g_ctx.slot[h] : nullptr;
+    MsmSlot* H = h >= 0 ? &ctx().slot[h] : nullptr;
     if (H) {
         if (int rc = ensure_slot_stream(*H)) return rc;
         // `st` carries the producer of the scalars -- a caller's kernel, or the asynchronous upload host_to_device() queued on the slot's OWN stream
         // (bbgpu_msm_g1 / _batch): the helper's stream starts behind what is enqueued there now, whichever stream that is
-        if (!g_ctx.helper_dep[h]) CHK(hipEventCreateWithFlags(&g_ctx.helper_dep[h], hipEventDisableTiming));
-        CHK(hipEventRecord(g_ctx.helper_dep[h], st));
-        CHK(hipStreamWaitEvent(H->stream, g_ctx.helper_dep[h], 0));
+        if (!ctx().helper_dep[h]) CHK(hipEventCreateWithFlags(&ctx().helper_dep[h], hipEventDisableTiming));
+        CHK(hipEventRecord(ctx().helper_dep[h], st));
+        CHK(hipStreamWaitEvent(H->stream, ctx().helper_dep[h], 0));
         H->helper = -1;
     }
     int issued[2] = { 0, 0 };
@@ -771,7 +800,7 @@ int issue_ticket(int t, const SrsEntry& e, size_t off, const uint64_t* const* d_
         T.append = issued[side] > 0;
         T.throughput = true; // pieces share the chip with each other
         rc = msm_issue_batch(T, e.d_srs + (off + pc[k].first) * 16, pc[k].seg->d_tab + pc[k].off_in_seg * 16, pc[k].seg->n, e.tab_c, sv, jobs, pc[k].len, wb, we,
-                             side ? H->stream : st, g_ctx.timing);
+                             side ? H->stream : st, ctx().timing);
         if (rc == BBGPU_OK) issued[side]++;
     }
     if (H && issued[1] > 0) {
@@ -793,13 +822,13 @@ int issue_on_entry(int t, const SrsEntry& e, size_t off, const uint64_t* d_scala
 // waits for ticket t and adds up its pieces: one point per job
 int finish_ticket(int t, host::Xyzz* results, MsmTiming* timing)
 {
-    MsmSlot& S = g_ctx.slot[t];
+    MsmSlot& S = ctx().slot[t];
     const uint32_t jobs = S.jobs;
     const int h = S.helper;
     S.helper = -1;
     int rc = msm_finish_batch(S, results, timing);
     if (h >= 0) {
-        MsmSlot& H = g_ctx.slot[h];
+        MsmSlot& H = ctx().slot[h];
         host::Xyzz more[MSM_MAX_JOBS];
         const int rc2 = msm_finish_batch(H, more, nullptr);
         H.is_helper = false;
@@ -836,7 +865,7 @@ bool contents_match_full(const SrsEntry& e, size_t off, const uint64_t* points, 
 {
     if (e.row_hash.size() != e.n) return false;
     struct Job { const uint64_t* p; const uint64_t* h; std::atomic<int> bad; } job{ points, e.row_hash.data() + off, { 0 } };
-    g_copy_pool.for_range(n, (size_t)1 << 14, [](void* c, size_t lo, size_t hi) {
+    ctx().copy_pool.for_range(n, (size_t)1 << 14, [](void* c, size_t lo, size_t hi) {
         Job* j = static_cast<Job*>(c);
         uint64_t diff = 0;
         for (size_t i = lo; i < hi; i++) diff |= hash_row(j->p + i * 16) ^ j->h[i];
@@ -861,7 +890,7 @@ void full_check_post(FullCheckJob& job, const SrsEntry& e, size_t off, const uin
     job.bad.store(e.row_hash.size() != e.n ? 1 : 0);
     job.posted = true;
     if (job.bad.load()) return;
-    g_copy_pool.post_range(n, [](void* c, size_t lo, size_t hi) {
+    ctx().copy_pool.post_range(n, [](void* c, size_t lo, size_t hi) {
         FullCheckJob* j = static_cast<FullCheckJob*>(c);
         uint64_t diff = 0;
         for (size_t i = lo; i < hi; i++) diff |= hash_row(j->p + i * 16) ^ j->h[i];
@@ -870,7 +899,7 @@ void full_check_post(FullCheckJob& job, const SrsEntry& e, size_t off, const uin
 }
 bool full_check_join(FullCheckJob& job) // true: contents match
 {
-    g_copy_pool.join();
+    ctx().copy_pool.join();
     job.posted = false;
     return job.bad.load() == 0;
 }
@@ -884,8 +913,8 @@ bool full_check_join(FullCheckJob& job) // true: contents match
 int find_srs(const uint64_t* points, size_t n, size_t* offset, bool* deferred_full = nullptr)
 {
     if (deferred_full) *deferred_full = false;
-    for (size_t k = g_ctx.srs.size(); k-- > 0;) {
-        SrsEntry& e = g_ctx.srs[k];
+    for (size_t k = ctx().srs.size(); k-- > 0;) {
+        SrsEntry& e = ctx().srs[k];
         if (!e.live || !e.host_ptr || e.stale_for_host) continue;
         const uint8_t* b = (const uint8_t*)e.host_ptr;
         const uint8_t* p = (const uint8_t*)points;
@@ -900,7 +929,7 @@ int find_srs(const uint64_t* points, size_t n, size_t* offset, bool* deferred_fu
             continue;
         }
         if (deferred_full) *deferred_full = e.validate_full;
-        e.last_use = ++g_ctx.use_clock;
+        e.last_use = ++ctx().use_clock;
         *offset = d / 128;
         return (int)k;
     }
@@ -910,7 +939,7 @@ int find_srs(const uint64_t* points, size_t n, size_t* offset, bool* deferred_fu
 // the deferred full check of an exact-mode entry failed: never serve this copy to a host-pointer call again
 void srs_mark_stale(int idx)
 {
-    SrsEntry& e = g_ctx.srs[idx];
+    SrsEntry& e = ctx().srs[idx];
     if (trace_srs()) fprintf(stderr, "bbgpu srs: full check: contents of %p differ from the resident copy\n", (const void*)e.host_ptr);
     if (e.auto_registered) free_entry(e);
     else e.stale_for_host = true;
@@ -927,8 +956,9 @@ int log2_exact(size_t n)
 // plain: `points` is an n-entry table of plain affine points (64 bytes apart) instead of the 2n-entry endomorphism table -- the argument of
 // the reference's pippenger_low_memory / pippenger_precomputed (scalar_multiplication.cpp:142-262, :478-574).  Such a table is used once and
 // forgotten (no address-keyed cache: these are test / bench entries of the reference, not the prover's).
-int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n, uint64_t out[12], bool plain, bool* stale);
-int msm_host_ptrs(const uint64_t* scalars, const uint64_t* points, size_t n, uint64_t out[12], bool plain = false)
+int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n, host::Xyzz* out, bool plain, bool* stale);
+// the sum before normalisation: a context's partial sum of a split call (bbgpu_msm_g1) is added to the others' first
+int msm_host_ptrs_sum(const uint64_t* scalars, const uint64_t* points, size_t n, host::Xyzz* out, bool plain = false)
 {
     // EXACT cache mode: the call runs against the resident copy while the host re-hashes every row of the caller's table; if they differ the
     // copy is dropped and the call runs once more, now uploading the table as it is (the reference reads the caller's points on every call,
@@ -938,11 +968,18 @@ int msm_host_ptrs(const uint64_t* scalars, const uint64_t* points, size_t n, uin
     if (stale) rc = msm_host_ptrs_once(scalars, points, n, out, plain, &stale);
     return rc;
 }
-int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n, uint64_t out[12], bool plain, bool* stale)
+int msm_host_ptrs(const uint64_t* scalars, const uint64_t* points, size_t n, uint64_t out[12], bool plain = false)
+{
+    host::Xyzz res;
+    const int rc = msm_host_ptrs_sum(scalars, points, n, &res, plain);
+    if (rc == BBGPU_OK) host::g1_to_normalised(res, out);
+    return rc;
+}
+int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n, host::Xyzz* out, bool plain, bool* stale)
 {
     *stale = false;
     if (n == 0) {
-        host::g1_to_normalised(host::g1_infinity(), out);
+        *out = host::g1_infinity();
         return BBGPU_OK;
     }
     if (!scalars || !points) {
@@ -953,8 +990,8 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
     bool full_check = false;
     int idx = plain ? -1 : find_srs(points, n, &off, &full_check);
     read_host_env();
-    if (idx < 0 && n <= (size_t)g_ctx.host_msm_max) { // the verifier's ~20 freshly built points: no allocation, no launch
-        host::g1_to_normalised(host::msm_small(scalars, points, n, plain ? 8 : 16), out);
+    if (idx < 0 && n <= (size_t)ctx().host_msm_max) { // the verifier's ~20 freshly built points: no allocation, no launch
+        *out = host::msm_small(scalars, points, n, plain ? 8 : 16);
         return BBGPU_OK;
     }
     {
@@ -969,7 +1006,7 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
         return BBGPU_ERR_STATE;
     }
     for (int k = 0; k < ns; k++)
-        if (int rc = ensure_slot_stream(g_ctx.slot[sl[k]])) return rc;
+        if (int rc = ensure_slot_stream(ctx().slot[sl[k]])) return rc;
     SlotReservation reserve(sl, ns);
     // A table that was never registered and is too small to be an SRS (the verifier's ~20 freshly built points,
     // verifier.cpp:359-363) is used once and forgotten: caching it by address would both leak device memory per call and
@@ -979,7 +1016,7 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
     // once the kernels are issued (every way out of this function joins it first: the job reads the caller's table and the entry's fingerprints)
     FullCheckJob bg;
     struct BgGuard { FullCheckJob& j; ~BgGuard() { if (j.posted) (void)full_check_join(j); } } bg_guard{ bg };
-    if (full_check && n * 32 > g_ctx.host_stage_max) full_check_post(bg, g_ctx.srs[idx], off, points, n);
+    if (full_check && n * 32 > ctx().host_stage_max) full_check_post(bg, ctx().srs[idx], off, points, n);
     SrsEntry transient{};
     const bool is_transient = idx < 0 && (plain || n < AUTO_REGISTER_MIN_POINTS);
     const bool tr = trace_srs();
@@ -990,11 +1027,11 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
     const bool small_once = is_transient && n < AUTO_REGISTER_MIN_POINTS;
     if (small_once) {
         const size_t stride = plain ? 64 : 128;
-        int rc = grow(&g_ctx.d_small_tab, &g_ctx.small_tab_cap, AUTO_REGISTER_MIN_POINTS * (128 + 64));
+        int rc = grow(&ctx().d_small_tab, &ctx().small_tab_cap, AUTO_REGISTER_MIN_POINTS * (128 + 64));
         if (rc) return rc;
-        uint32_t* d_raw = (uint32_t*)g_ctx.d_small_tab;
+        uint32_t* d_raw = (uint32_t*)ctx().d_small_tab;
         uint32_t* d = d_raw + AUTO_REGISTER_MIN_POINTS * 32;
-        if ((rc = srs_upload_into(points, n, d_raw, d, g_ctx.slot[sl[0]].stream, stride)) != BBGPU_OK) return rc;
+        if ((rc = srs_upload_into(points, n, d_raw, d, ctx().slot[sl[0]].stream, stride)) != BBGPU_OK) return rc;
         transient.host_ptr = points;
         transient.n = n;
         transient.d_srs = d;
@@ -1003,7 +1040,7 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
     } else
     if (idx < 0) {
         uint32_t* d = nullptr;
-        int rc = srs_upload(points, n, &d, g_ctx.stream, plain ? 64 : 128);
+        int rc = srs_upload(points, n, &d, ctx().stream, plain ? 64 : 128);
         if (rc) return rc;
         if (is_transient) {
             transient.host_ptr = points;
@@ -1016,7 +1053,7 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
         }
         off = 0;
     }
-    const SrsEntry& e = is_transient ? transient : g_ctx.srs[idx];
+    const SrsEntry& e = is_transient ? transient : ctx().srs[idx];
     // The call is cut into point RANGES that go through the free slots like the jobs of a batch: the scalars of range k+1 cross the link while
     // the kernels of range k run, and the partial sums (group elements: the sum over a range of points is a plain term of the whole sum) are
     // added on the host.  Above 2^20 points the ranges are the table segments the call touches (each at most 2^20 points with its own window
@@ -1051,14 +1088,14 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
     size_t max_len = 0;
     for (const auto& r : ranges) max_len = std::max(max_len, r.len);
     const double q1 = tr ? now_ms() : 0;
-    uint64_t** stage[2] = { &g_ctx.d_stage, &g_ctx.d_stage2 };
-    size_t* cap[2] = { &g_ctx.stage_cap, &g_ctx.stage2_cap };
+    uint64_t** stage[2] = { &ctx().d_stage, &ctx().d_stage2 };
+    size_t* cap[2] = { &ctx().stage_cap, &ctx().stage2_cap };
     host::Xyzz res = host::g1_infinity();
     int rc = BBGPU_OK;
     size_t issued = 0, finished = 0;
     auto finish = [&](size_t k) -> int {
         host::Xyzz part;
-        int r = finish_ticket(sl[k % (size_t)ns], &part, k + 1 == ranges.size() ? &g_ctx.last : nullptr);
+        int r = finish_ticket(sl[k % (size_t)ns], &part, k + 1 == ranges.size() ? &ctx().last : nullptr);
         finished = k + 1;
         if (r == BBGPU_OK) res = host::g1_add(res, part);
         return r;
@@ -1066,7 +1103,7 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
     for (size_t k = 0; k < ranges.size() && rc == BBGPU_OK; k++) {
         const size_t w = k % (size_t)ns;
         if (k >= (size_t)ns) rc = finish(k - (size_t)ns); // frees this range's slot and staging buffer
-        MsmSlot& S = g_ctx.slot[sl[w]];
+        MsmSlot& S = ctx().slot[sl[w]];
         if (rc == BBGPU_OK) rc = grow(stage[w], cap[w], max_len * 32);
         if (rc == BBGPU_OK) rc = host_to_device(*stage[w], scalars + ranges[k].o * 4, ranges[k].len * 32, S.stream);
         if (rc == BBGPU_OK) rc = issue_on_entry(sl[w], e, off + ranges[k].o, *stage[w], ranges[k].len, 0, entry_windows(e, ranges[k].len), S.stream);
@@ -1074,7 +1111,7 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
     }
     const double q2 = tr ? now_ms() : 0;
     // exact mode: every row of the caller's table against the fingerprints of the resident copy, on the host while the kernels issued above run
-    if (rc == BBGPU_OK && full_check && !(bg.posted ? full_check_join(bg) : contents_match_full(g_ctx.srs[idx], off, points, n))) {
+    if (rc == BBGPU_OK && full_check && !(bg.posted ? full_check_join(bg) : contents_match_full(ctx().srs[idx], off, points, n))) {
         for (int k = 0; k < ns; k++) drain_ticket(sl[k]);
         srs_mark_stale(idx);
         *stale = true;
@@ -1090,9 +1127,209 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
     const double q3 = tr ? now_ms() : 0;
     if (is_transient && !small_once) (void)dev_free(transient.d_srs); // the finishes have waited for the kernels
     if (rc) return rc;
-    host::g1_to_normalised(res, out);
-    if (tr) fprintf(stderr, "bbgpu msm n=%zu: table %.3f, upload + issue %.3f, wait + host sums %.3f, free + normalise %.3f ms\n", n, q1 - q0, q2 - q1, q3 - q2, now_ms() - q3);
+    *out = res;
+    if (tr) fprintf(stderr, "bbgpu msm n=%zu: table %.3f, upload + issue %.3f, wait + host sums %.3f, free %.3f ms\n", n, q1 - q0, q2 - q1, q3 - q2, now_ms() - q3);
     return BBGPU_OK;
+}
+
+// ---- device contexts of bbgpu_init_devices ----------------------------------------------------------------------------------------------
+// The persistent thread of context k >= 1: created by bbgpu_init_devices, joined by bbgpu_shutdown, one job at a time with context k current.  Its
+// first job binds it (ensure_init: hipSetDevice once, then streams and slots on that device).  Allocated and never destroyed at process exit: a
+// process that ends without bbgpu_shutdown() leaves the thread waiting instead of destroying a joinable std::thread.
+struct MultiWorker {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::function<int()> job;
+    bool busy = false, stop = false;
+    int rc = BBGPU_OK;
+    std::exception_ptr ex; // what the job threw, handed to the caller (who rethrows it once every context has returned)
+    char err[sizeof(g_err)] = "";
+    std::thread th; // started in the constructor's body: every member above exists before the thread can touch it
+    explicit MultiWorker(int k) { th = std::thread([this, k] { loop(k); }); }
+    void loop(int k)
+    {
+        t_ctx = k;
+        std::unique_lock<std::mutex> lk(mu);
+        for (;;) {
+            cv.wait(lk, [&] { return stop || job; });
+            if (!job) return; // stop, nothing posted
+            std::function<int()> fn = std::move(job);
+            job = nullptr;
+            lk.unlock();
+            g_err[0] = 0;
+            int r = BBGPU_ERR_STATE;
+            std::exception_ptr e;
+            try {
+                r = fn();
+            } catch (...) {
+                e = std::current_exception();
+            }
+            lk.lock();
+            rc = r;
+            ex = e;
+            memcpy(err, g_err, sizeof(err));
+            busy = false;
+            cv.notify_all();
+        }
+    }
+    void post(std::function<int()> fn)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        job = std::move(fn);
+        busy = true;
+        cv.notify_all();
+    }
+    int wait(char* err_out, std::exception_ptr* ex_out = nullptr) // the job's return code; its error text to err_out, what it threw to *ex_out
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !busy; });
+        memcpy(err_out, err, sizeof(err));
+        if (ex_out) *ex_out = ex;
+        ex = nullptr;
+        return rc;
+    }
+    void join()
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            stop = true;
+            cv.notify_all();
+        }
+        th.join();
+    }
+};
+MultiWorker* g_workers[BBGPU_MAX_CONTEXTS] = {}; // [0] stays null: context 0 runs on the calling thread
+
+// Runs fn(k) for every k < m at once: k = 0 on the calling thread (which holds g_mu, context 0's lock), k >= 1 on context k's worker.  Returns when
+// all have returned -- each context drains its own slots on a failure, so nothing of the call is still in flight -- with the first failure in context
+// order as the caller's error, named by context and device.
+// An exception (a host allocation, say) is not caught for the caller: the first one in context order is rethrown, but only after every worker has
+// returned, since the workers use `fn` and what it refers to on the caller's stack.
+int run_on_contexts(int m, const std::function<int(int)>& fn)
+{
+    for (int k = 1; k < m; k++) g_workers[k]->post([&fn, k] { return fn(k); });
+    std::exception_ptr thrown;
+    int rc = BBGPU_ERR_STATE;
+    try {
+        rc = fn(0);
+    } catch (...) {
+        thrown = std::current_exception();
+    }
+    int bad = rc ? 0 : -1;
+    char text[sizeof(g_err)];
+    memcpy(text, g_err, sizeof(text));
+    for (int k = 1; k < m; k++) {
+        char e[sizeof(g_err)];
+        std::exception_ptr ex;
+        const int r = g_workers[k]->wait(e, &ex);
+        if (ex && !thrown) thrown = ex;
+        if (r != BBGPU_OK && bad < 0) {
+            rc = r;
+            bad = k;
+            memcpy(text, e, sizeof(text));
+        }
+    }
+    if (thrown) std::rethrow_exception(thrown);
+    if (bad >= 0) {
+        text[sizeof(text) - 1] = 0;
+        set_error("context %d (device %d): %s", bad, g_ctxs[bad].device, text);
+    }
+    return rc;
+}
+
+// Everything the current context holds, on the thread that drives it (its device is that thread's current one).  Context 0 (primary) also owns the
+// resident prover and the transforms' tables.
+void release_context(bool primary)
+{
+    Context& C = ctx();
+    if (!C.ready) return;
+    if (primary) plonk_release_all_locked();
+    // nothing may still be reading the pinned staging buffers or a slot's workspace when they are freed: collect what is in flight
+    // (an MSM a caller never waited for, a copy queued before an error return) and drain every stream first
+    for (int k = 0; k < Context::NSLOT; k++)
+        if (C.slot[k].pending && !C.slot[k].is_helper) drain_ticket(k);
+    for (auto& ev : C.helper_dep) {
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
+    (void)hipStreamSynchronize(C.stream);
+    for (auto& sl : C.slot)
+        if (sl.stream) (void)hipStreamSynchronize(sl.stream);
+    (void)hipDeviceSynchronize();
+    host_stage_release();
+    C.poly_scratch.release();
+    if (C.d_poly_tmp) (void)dev_free(C.d_poly_tmp);
+    C.d_poly_tmp = nullptr;
+    C.poly_tmp_cap = 0;
+    for (auto& e : C.srs) {
+        if (e.live && e.d_srs) (void)dev_free(e.d_srs);
+        if (e.live)
+            for (auto& sg : e.segs)
+                if (sg.d_tab_alloc) (void)dev_free(sg.d_tab_alloc);
+    }
+    C.srs.clear();
+    for (auto& sl : C.slot) sl.release();
+    C.acc_ring.release();
+    if (C.d_stage) (void)dev_free(C.d_stage);
+    if (C.d_stage2) (void)dev_free(C.d_stage2);
+    C.d_stage2 = nullptr;
+    C.stage2_cap = 0;
+    if (C.d_scratch) (void)dev_free(C.d_scratch);
+    C.d_stage = C.d_scratch = nullptr;
+    C.stage_cap = C.scratch_cap = 0;
+    if (C.d_small_tab) (void)dev_free(C.d_small_tab);
+    C.d_small_tab = nullptr;
+    C.small_tab_cap = 0;
+    if (primary) ntt_release_tables();
+    if (C.shared_done) (void)hipEventDestroy(C.shared_done);
+    C.shared_done = nullptr;
+    C.shared_used = false;
+    (void)hipStreamDestroy(C.stream);
+    C.stream = nullptr;
+    C.ready = false;
+}
+
+// caller holds the prover's mutex and g_mu
+void shutdown_locked()
+{
+    for (int k = g_num_ctx - 1; k >= 1; k--) {
+        if (!g_workers[k]) continue;
+        char e[sizeof(g_err)];
+        g_workers[k]->post([] { release_context(false); return BBGPU_OK; });
+        (void)g_workers[k]->wait(e);
+        g_workers[k]->join();
+        delete g_workers[k];
+        g_workers[k] = nullptr;
+    }
+    g_num_ctx = 1;
+    release_context(true);
+}
+
+// one context's share of bbgpu_memory_stats, added to *out
+void add_context_memory(const Context& C, bool primary, bbgpu_memory_info* out)
+{
+    for (const auto& e : C.srs) {
+        if (!e.live) continue;
+        const uint64_t pts = (uint64_t)e.n * 64, tab = e.bytes > pts ? e.bytes - pts : 0;
+        out->srs_points_bytes += pts;
+        out->srs_table_bytes += tab;
+        if (e.auto_registered) out->srs_auto_bytes += e.bytes;
+    }
+    out->srs_cache_cap_bytes += C.srs_cache_cap;
+    if (primary) {
+        size_t cap = 0;
+        int sets = 0;
+        out->ntt_table_bytes += ntt_table_bytes(&cap, &sets);
+        out->ntt_table_cap_bytes += cap;
+        out->ntt_table_sets += (uint64_t)sets;
+    }
+    for (const auto& sl : C.slot) {
+        out->msm_workspace_bytes += sl.ws.cap;
+        if (sl.ws.h_out) out->pinned_host_bytes += (uint64_t)MSM_HOUT_GROUPS * 64 * 128;
+    }
+    out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap;
+    for (int k = 0; k < Context::HOST_RING; k++)
+        if (C.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
 }
 
 } // namespace
@@ -1116,13 +1353,69 @@ int bbgpu_device_count(void)
 int bbgpu_init(int device)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (g_ctx.ready && g_ctx.device == device) return BBGPU_OK;
-    if (g_ctx.ready) {
-        set_error("already bound to device %d (one process per GPU)", g_ctx.device);
+    if (ctx().ready && ctx().device == device) return BBGPU_OK;
+    if (ctx().ready) {
+        set_error("already bound to %d context(s), the first on device %d: bbgpu_shutdown() first", g_num_ctx, ctx().device);
         return BBGPU_ERR_STATE;
     }
-    g_ctx.device = device;
+    ctx().device = device;
     return ensure_init();
+}
+
+int bbgpu_init_devices(const int* devices, int count)
+{
+    // argument checks before any HIP call: they hold on a machine without a GPU as well
+    if (!devices || count < 1 || count > BBGPU_MAX_CONTEXTS) {
+        set_error("bbgpu_init_devices: %s (1 to %d contexts)", devices ? "bad context count" : "null device list", BBGPU_MAX_CONTEXTS);
+        return BBGPU_ERR_ARG;
+    }
+    for (int k = 0; k < count; k++)
+        if (devices[k] < 0) {
+            set_error("bbgpu_init_devices: negative device %d for context %d", devices[k], k);
+            return BBGPU_ERR_ARG;
+        }
+    // lock order of bbgpu_shutdown, which a failed binding ends in: the prover's mutex, then the library's
+    std::lock_guard<std::mutex> lkp(plonk_mutex());
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (g_ctxs[0].ready) {
+        bool same = g_num_ctx == count;
+        for (int k = 0; same && k < count; k++) same = g_ctxs[k].device == devices[k];
+        if (same) return BBGPU_OK;
+        set_error("already bound to %d context(s), the first on device %d: bbgpu_shutdown() first", g_num_ctx, g_ctxs[0].device);
+        return BBGPU_ERR_STATE;
+    }
+    const int cnt = hip_device_count();
+    if (cnt == 0) {
+        set_error("no HIP device available: the GPU entry points of libbbgpu have no CPU fallback");
+        return BBGPU_ERR_HIP;
+    }
+    for (int k = 0; k < count; k++)
+        if (devices[k] >= cnt) {
+            set_error("bbgpu_init_devices: device %d of context %d, the machine has %d", devices[k], k, cnt);
+            return BBGPU_ERR_ARG;
+        }
+    g_ctxs[0].device = devices[0];
+    if (int rc = ensure_init()) return rc;
+    for (int k = 1; k < count; k++) { // one after the other: each context's streams are made in one piece (ensure_init)
+        g_ctxs[k].device = devices[k];
+        g_workers[k] = new MultiWorker(k);
+        g_num_ctx = k + 1;
+        g_workers[k]->post([] { return ensure_init(); });
+        char e[sizeof(g_err)];
+        if (int rc = g_workers[k]->wait(e)) {
+            shutdown_locked();
+            e[sizeof(e) - 1] = 0;
+            set_error("context %d (device %d): %s", k, devices[k], e);
+            return rc;
+        }
+    }
+    return BBGPU_OK;
+}
+
+int bbgpu_num_contexts(void)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return g_num_ctx;
 }
 
 void bbgpu_shutdown(void)
@@ -1130,50 +1423,7 @@ void bbgpu_shutdown(void)
     // lock order: the prover's mutex, then the library's (the prover calls the entry points above while it holds its own)
     std::lock_guard<std::mutex> lkp(plonk_mutex());
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!g_ctx.ready) return;
-    plonk_release_all_locked();
-    // nothing may still be reading the pinned staging buffers or a slot's workspace when they are freed: collect what is in flight
-    // (an MSM a caller never waited for, a copy queued before an error return) and drain every stream first
-    for (int k = 0; k < Context::NSLOT; k++)
-        if (g_ctx.slot[k].pending && !g_ctx.slot[k].is_helper) drain_ticket(k);
-    for (auto& ev : g_ctx.helper_dep) {
-        if (ev) (void)hipEventDestroy(ev);
-        ev = nullptr;
-    }
-    (void)hipStreamSynchronize(g_ctx.stream);
-    for (auto& sl : g_ctx.slot)
-        if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-    (void)hipDeviceSynchronize();
-    host_stage_release();
-    g_ctx.poly_scratch.release();
-    if (g_ctx.d_poly_tmp) (void)dev_free(g_ctx.d_poly_tmp);
-    g_ctx.d_poly_tmp = nullptr;
-    g_ctx.poly_tmp_cap = 0;
-    for (auto& e : g_ctx.srs) {
-        if (e.live && e.d_srs) (void)dev_free(e.d_srs);
-        if (e.live)
-            for (auto& sg : e.segs)
-                if (sg.d_tab_alloc) (void)dev_free(sg.d_tab_alloc);
-    }
-    g_ctx.srs.clear();
-    for (auto& sl : g_ctx.slot) sl.release();
-    if (g_ctx.d_stage) (void)dev_free(g_ctx.d_stage);
-    if (g_ctx.d_stage2) (void)dev_free(g_ctx.d_stage2);
-    g_ctx.d_stage2 = nullptr;
-    g_ctx.stage2_cap = 0;
-    if (g_ctx.d_scratch) (void)dev_free(g_ctx.d_scratch);
-    g_ctx.d_stage = g_ctx.d_scratch = nullptr;
-    g_ctx.stage_cap = g_ctx.scratch_cap = 0;
-    if (g_ctx.d_small_tab) (void)dev_free(g_ctx.d_small_tab);
-    g_ctx.d_small_tab = nullptr;
-    g_ctx.small_tab_cap = 0;
-    ntt_release_tables();
-    if (g_ctx.shared_done) (void)hipEventDestroy(g_ctx.shared_done);
-    g_ctx.shared_done = nullptr;
-    g_ctx.shared_used = false;
-    (void)hipStreamDestroy(g_ctx.stream);
-    g_ctx.stream = nullptr;
-    g_ctx.ready = false;
+    shutdown_locked();
 }
 
 int bbgpu_memory_stats(bbgpu_memory_info* out)
@@ -1181,26 +1431,23 @@ int bbgpu_memory_stats(bbgpu_memory_info* out)
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (!out) return BBGPU_ERR_ARG;
     memset(out, 0, sizeof(*out));
-    for (const auto& e : g_ctx.srs) {
-        if (!e.live) continue;
-        const uint64_t pts = (uint64_t)e.n * 64, tab = e.bytes > pts ? e.bytes - pts : 0;
-        out->srs_points_bytes += pts;
-        out->srs_table_bytes += tab;
-        if (e.auto_registered) out->srs_auto_bytes += e.bytes;
+    for (int k = 0; k < g_num_ctx; k++) add_context_memory(g_ctxs[k], k == 0, out);
+    return BBGPU_OK;
+}
+
+int bbgpu_memory_stats_context(int context, bbgpu_memory_info* out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!out) {
+        set_error("null output");
+        return BBGPU_ERR_ARG;
     }
-    out->srs_cache_cap_bytes = g_ctx.srs_cache_cap;
-    size_t cap = 0;
-    int sets = 0;
-    out->ntt_table_bytes = ntt_table_bytes(&cap, &sets);
-    out->ntt_table_cap_bytes = cap;
-    out->ntt_table_sets = (uint64_t)sets;
-    for (const auto& sl : g_ctx.slot) {
-        out->msm_workspace_bytes += sl.ws.cap;
-        if (sl.ws.h_out) out->pinned_host_bytes += (uint64_t)MSM_HOUT_GROUPS * 64 * 128;
+    if (context < 0 || context >= g_num_ctx) {
+        set_error("no context %d (%d bound)", context, g_num_ctx);
+        return BBGPU_ERR_ARG;
     }
-    out->staging_bytes = g_ctx.stage_cap + g_ctx.stage2_cap + g_ctx.scratch_cap + g_ctx.poly_tmp_cap + g_ctx.poly_scratch.cap + g_ctx.small_tab_cap;
-    for (int k = 0; k < Context::HOST_RING; k++)
-        if (g_ctx.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
+    memset(out, 0, sizeof(*out));
+    add_context_memory(g_ctxs[context], context == 0, out);
     return BBGPU_OK;
 }
 
@@ -1230,21 +1477,22 @@ int bbgpu_fault_stats(bbgpu_fault_info* out)
         out->live_allocations = F.live.size();
         out->live_bytes = F.live_bytes;
     }
-    for (const auto& sl : g_ctx.slot)
-        if (sl.pending) out->slots_pending++;
+    for (int k = 0; k < g_num_ctx; k++)
+        for (const auto& sl : g_ctxs[k].slot)
+            if (sl.pending) out->slots_pending++;
     return BBGPU_OK;
 }
 
 void bbgpu_set_timing(int enabled)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    g_ctx.timing = enabled < 0 || enabled > 2 ? 1 : enabled;
+    for (auto& C : g_ctxs) C.timing = enabled < 0 || enabled > 2 ? 1 : enabled; // settings apply to every context, bound or not
 }
 int bbgpu_last_timing(float* ms_out, int max_entries)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int k = g_ctx.last.count < max_entries ? g_ctx.last.count : max_entries;
-    for (int i = 0; i < k; i++) ms_out[i] = g_ctx.last.ms[i];
+    int k = ctx().last.count < max_entries ? ctx().last.count : max_entries;
+    for (int i = 0; i < k; i++) ms_out[i] = ctx().last.ms[i];
     return k;
 }
 
@@ -1263,11 +1511,11 @@ int bbgpu_ntt_device(uint64_t* d_coeffs, size_t n, int kind, const uint64_t* con
         set_error("bad NTT kind / null buffer");
         return BBGPU_ERR_ARG;
     }
-    rc = grow(&g_ctx.d_scratch, &g_ctx.scratch_cap, n * 32);
+    rc = grow(&ctx().d_scratch, &ctx().scratch_cap, n * 32);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)hip_stream; /* NULL = the legacy default stream, as bbgpu.h says */
     if ((rc = shared_begin(st)) != BBGPU_OK) return rc;
-    rc = ntt_device(d_coeffs, g_ctx.d_scratch, lg, kind, constant, st);
+    rc = ntt_device(d_coeffs, ctx().d_scratch, lg, kind, constant, st);
     if (rc == BBGPU_OK) rc = shared_end(st);
     if (rc == BBGPU_ERR_SIZE) set_error("NTT size 2^%d unsupported (max 2^28)", lg);
     if (rc == BBGPU_ERR_HIP) {
@@ -1291,11 +1539,11 @@ int bbgpu_ntt_device_batch(uint64_t* d_coeffs, size_t n, size_t stride_elems, in
         set_error("bad NTT kind / null buffer / batch / stride");
         return BBGPU_ERR_ARG;
     }
-    rc = grow(&g_ctx.d_scratch, &g_ctx.scratch_cap, (size_t)batch * n * 32);
+    rc = grow(&ctx().d_scratch, &ctx().scratch_cap, (size_t)batch * n * 32);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)hip_stream; /* NULL = the legacy default stream, as bbgpu.h says */
     if ((rc = shared_begin(st)) != BBGPU_OK) return rc;
-    rc = ntt_device_batch(d_coeffs, stride_elems, batch, g_ctx.d_scratch, lg, kind, constant, st);
+    rc = ntt_device_batch(d_coeffs, stride_elems, batch, ctx().d_scratch, lg, kind, constant, st);
     if (rc == BBGPU_OK) rc = shared_end(st);
     if (rc == BBGPU_ERR_SIZE) set_error("NTT size 2^%d unsupported (max 2^28)", lg);
     if (rc == BBGPU_ERR_HIP) {
@@ -1310,7 +1558,7 @@ int bbgpu_ntt(uint64_t* coeffs, size_t n, int kind, const uint64_t* constant)
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (!coeffs) return BBGPU_ERR_ARG;
     read_host_env();
-    if (n <= (size_t)g_ctx.host_ntt_max && log2_exact(n) >= 1 && kind >= 0 && kind <= BBGPU_COSET_FFT_WITH_CONSTANT) {
+    if (n <= (size_t)ctx().host_ntt_max && log2_exact(n) >= 1 && kind >= 0 && kind <= BBGPU_COSET_FFT_WITH_CONSTANT) {
         const bool has_const = (kind == BBGPU_FFT_WITH_CONSTANT || kind == BBGPU_IFFT_WITH_CONSTANT || kind == BBGPU_COSET_FFT_WITH_CONSTANT);
         if (has_const && !constant) return BBGPU_ERR_ARG;
         host::ntt_small(coeffs, log2_exact(n), kind, constant); // SURVEY 8b small sizes: no copy, no launch
@@ -1318,14 +1566,14 @@ int bbgpu_ntt(uint64_t* coeffs, size_t n, int kind, const uint64_t* constant)
     }
     int rc = ensure_init();
     if (rc) return rc;
-    rc = grow(&g_ctx.d_stage, &g_ctx.stage_cap, n * 32);
+    rc = grow(&ctx().d_stage, &ctx().stage_cap, n * 32);
     if (rc) return rc;
-    if ((rc = host_to_device(g_ctx.d_stage, coeffs, n * 32, g_ctx.stream)) != BBGPU_OK) return rc;
-    rc = bbgpu_ntt_device(g_ctx.d_stage, n, kind, constant, g_ctx.stream);
+    if ((rc = host_to_device(ctx().d_stage, coeffs, n * 32, ctx().stream)) != BBGPU_OK) return rc;
+    rc = bbgpu_ntt_device(ctx().d_stage, n, kind, constant, ctx().stream);
     if (rc) return rc;
     // up to here `coeffs` is untouched; a failure while the result is copied back may leave it half overwritten -- LOST only if a byte of it was written
     bool touched = false;
-    rc = device_to_host_sync(coeffs, g_ctx.d_stage, n * 32, g_ctx.stream, &touched);
+    rc = device_to_host_sync(coeffs, ctx().d_stage, n * 32, ctx().stream, &touched);
     return rc == BBGPU_OK ? BBGPU_OK : (touched ? BBGPU_ERR_LOST : rc);
 }
 
@@ -1359,7 +1607,7 @@ int bbgpu_fr_evaluate_device(const uint64_t* d_coeffs, size_t n, const uint64_t 
 {
     POLY_ENTER((d_coeffs || n == 0) && z && out);
     host::Fr r;
-    int rc = poly::evaluate(d_coeffs, n, load_fr(z), &r, g_ctx.poly_scratch, st);
+    int rc = poly::evaluate(d_coeffs, n, load_fr(z), &r, ctx().poly_scratch, st);
     if (rc) return rc;
     memcpy(out, r.d, 32);
     return BBGPU_OK;
@@ -1368,15 +1616,15 @@ int bbgpu_fr_evaluate_device(const uint64_t* d_coeffs, size_t n, const uint64_t 
 int bbgpu_fr_batch_invert_device(uint64_t* d_values, size_t n, void* hip_stream)
 {
     POLY_ENTER(d_values || n == 0);
-    int rc = grow(&g_ctx.d_poly_tmp, &g_ctx.poly_tmp_cap, n * 32);
+    int rc = grow(&ctx().d_poly_tmp, &ctx().poly_tmp_cap, n * 32);
     if (rc) return rc;
-    return poly::batch_invert(d_values, g_ctx.d_poly_tmp, n, g_ctx.poly_scratch, st);
+    return poly::batch_invert(d_values, ctx().d_poly_tmp, n, ctx().poly_scratch, st);
 }
 
 int bbgpu_fr_product_scan_device(const uint64_t* d_in, uint64_t* d_out, size_t n, int reverse, int inclusive, void* hip_stream)
 {
     POLY_ENTER((d_in && d_out) || n == 0);
-    return poly::product_scan(d_in, d_out, n, reverse != 0, inclusive != 0, g_ctx.poly_scratch, st, nullptr);
+    return poly::product_scan(d_in, d_out, n, reverse != 0, inclusive != 0, ctx().poly_scratch, st, nullptr);
 }
 
 int bbgpu_fr_mul_device(uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, size_t n, void* hip_stream)
@@ -1391,18 +1639,18 @@ int bbgpu_kate_opening_device(const uint64_t* d_src, uint64_t* d_dest, size_t n,
     const host::Fr zz = load_fr(z);
     if (f_of_z) {
         host::Fr f;
-        int rc = poly::evaluate(d_src, n, zz, &f, g_ctx.poly_scratch, st);
+        int rc = poly::evaluate(d_src, n, zz, &f, ctx().poly_scratch, st);
         if (rc) return rc;
         memcpy(f_of_z, f.d, 32);
     }
     const uint64_t* src = d_src;
     if (d_dest == d_src) { // the scan's last phase reads its input while writing: work from a copy
-        int rc = grow(&g_ctx.d_poly_tmp, &g_ctx.poly_tmp_cap, n * 32);
+        int rc = grow(&ctx().d_poly_tmp, &ctx().poly_tmp_cap, n * 32);
         if (rc) return rc;
-        CHK(hipMemcpyAsync(g_ctx.d_poly_tmp, d_src, n * 32, hipMemcpyDeviceToDevice, st));
-        src = g_ctx.d_poly_tmp;
+        CHK(hipMemcpyAsync(ctx().d_poly_tmp, d_src, n * 32, hipMemcpyDeviceToDevice, st));
+        src = ctx().d_poly_tmp;
     }
-    return poly::horner_suffix(src, d_dest, n, zz, false, g_ctx.poly_scratch, st, nullptr);
+    return poly::horner_suffix(src, d_dest, n, zz, false, ctx().poly_scratch, st, nullptr);
 }
 
 int bbgpu_lagrange_l1_fft_device(uint64_t* d_l_1, size_t n_src, size_t n_target, void* hip_stream)
@@ -1413,9 +1661,9 @@ int bbgpu_lagrange_l1_fft_device(uint64_t* d_l_1, size_t n_src, size_t n_target,
         set_error("lagrange_l1_fft: domains must be powers of two, target >= source");
         return BBGPU_ERR_SIZE;
     }
-    int rc = grow(&g_ctx.d_poly_tmp, &g_ctx.poly_tmp_cap, n_target * 32);
+    int rc = grow(&ctx().d_poly_tmp, &ctx().poly_tmp_cap, n_target * 32);
     if (rc) return rc;
-    return poly::lagrange_l1_fft(d_l_1, g_ctx.d_poly_tmp, ls, lt, g_ctx.poly_scratch, st);
+    return poly::lagrange_l1_fft(d_l_1, ctx().d_poly_tmp, ls, lt, ctx().poly_scratch, st);
 }
 
 int bbgpu_divide_by_pseudo_vanishing_device(uint64_t* d_coeffs, size_t n_src, size_t n_target, void* hip_stream)
@@ -1434,25 +1682,25 @@ int bbgpu_permutation_lagrange_base_device(uint64_t* d_out, const uint32_t* d_ma
     POLY_ENTER(d_out && d_mapping);
     const int lg = log2_exact(n);
     if (lg < 1 || lg > 28) return BBGPU_ERR_SIZE;
-    int rc = grow(&g_ctx.d_poly_tmp, &g_ctx.poly_tmp_cap, n * 32);
+    int rc = grow(&ctx().d_poly_tmp, &ctx().poly_tmp_cap, n * 32);
     if (rc) return rc;
-    rc = poly::powers(g_ctx.d_poly_tmp, n, host::fr_root_of_unity(lg), host::fr_one(), st);
+    rc = poly::powers(ctx().d_poly_tmp, n, host::fr_root_of_unity(lg), host::fr_one(), st);
     if (rc) return rc;
-    return poly::sigma_from_mapping(d_out, d_mapping, g_ctx.d_poly_tmp, n, st);
+    return poly::sigma_from_mapping(d_out, d_mapping, ctx().d_poly_tmp, n, st);
 }
 
 /* ---- the same helpers on host buffers (what the C++ shim forwards the reference's co-resident TU functions to) ---- */
 static int stage_in(const uint64_t* host, size_t n)
 {
-    int rc = grow(&g_ctx.d_stage, &g_ctx.stage_cap, n * 32);
+    int rc = grow(&ctx().d_stage, &ctx().stage_cap, n * 32);
     if (rc) return rc;
-    return host_to_device(g_ctx.d_stage, host, n * 32, g_ctx.stream);
+    return host_to_device(ctx().d_stage, host, n * 32, ctx().stream);
 }
 // in_place: the destination is also the call's input -- a failure after any byte of it was written is BBGPU_ERR_LOST (nothing left to fall back on)
 static int stage_out(uint64_t* host, const uint64_t* dev, size_t n, bool in_place = false)
 {
     bool touched = false;
-    const int rc = device_to_host_sync(host, dev, n * 32, g_ctx.stream, &touched);
+    const int rc = device_to_host_sync(host, dev, n * 32, ctx().stream, &touched);
     return (rc != BBGPU_OK && in_place && touched) ? BBGPU_ERR_LOST : rc;
 }
 
@@ -1463,7 +1711,7 @@ int bbgpu_fr_evaluate(const uint64_t* coeffs, size_t n, const uint64_t z[4], uin
     if (rc) return rc;
     if ((!coeffs && n) || !z || !out) return BBGPU_ERR_ARG;
     if ((rc = stage_in(coeffs, n)) != BBGPU_OK) return rc;
-    return bbgpu_fr_evaluate_device(g_ctx.d_stage, n, z, out, g_ctx.stream);
+    return bbgpu_fr_evaluate_device(ctx().d_stage, n, z, out, ctx().stream);
 }
 
 int bbgpu_kate_opening(const uint64_t* src, uint64_t* dest, size_t n, const uint64_t z[4], uint64_t f_of_z[4])
@@ -1473,10 +1721,10 @@ int bbgpu_kate_opening(const uint64_t* src, uint64_t* dest, size_t n, const uint
     if (rc) return rc;
     if (((!src || !dest) && n) || !z) return BBGPU_ERR_ARG;
     if ((rc = stage_in(src, n)) != BBGPU_OK) return rc;
-    if ((rc = grow(&g_ctx.d_stage2, &g_ctx.stage2_cap, n * 32)) != BBGPU_OK) return rc;
-    if ((rc = bbgpu_kate_opening_device(g_ctx.d_stage, g_ctx.d_stage2, n, z, f_of_z, g_ctx.stream)) != BBGPU_OK) return rc;
+    if ((rc = grow(&ctx().d_stage2, &ctx().stage2_cap, n * 32)) != BBGPU_OK) return rc;
+    if ((rc = bbgpu_kate_opening_device(ctx().d_stage, ctx().d_stage2, n, z, f_of_z, ctx().stream)) != BBGPU_OK) return rc;
     // the reference calls it in place (polynomial.cpp:327 passes coefficients, coefficients): then a half-written dest is a half-destroyed src
-    return stage_out(dest, g_ctx.d_stage2, n, dest == src);
+    return stage_out(dest, ctx().d_stage2, n, dest == src);
 }
 
 int bbgpu_lagrange_l1_fft(uint64_t* l_1, size_t n_src, size_t n_target)
@@ -1485,9 +1733,9 @@ int bbgpu_lagrange_l1_fft(uint64_t* l_1, size_t n_src, size_t n_target)
     int rc = ensure_init();
     if (rc) return rc;
     if (!l_1) return BBGPU_ERR_ARG;
-    if ((rc = grow(&g_ctx.d_stage, &g_ctx.stage_cap, n_target * 32)) != BBGPU_OK) return rc;
-    if ((rc = bbgpu_lagrange_l1_fft_device(g_ctx.d_stage, n_src, n_target, g_ctx.stream)) != BBGPU_OK) return rc;
-    return stage_out(l_1, g_ctx.d_stage, n_target);
+    if ((rc = grow(&ctx().d_stage, &ctx().stage_cap, n_target * 32)) != BBGPU_OK) return rc;
+    if ((rc = bbgpu_lagrange_l1_fft_device(ctx().d_stage, n_src, n_target, ctx().stream)) != BBGPU_OK) return rc;
+    return stage_out(l_1, ctx().d_stage, n_target);
 }
 
 int bbgpu_divide_by_pseudo_vanishing(uint64_t* coeffs, size_t n_src, size_t n_target)
@@ -1497,8 +1745,8 @@ int bbgpu_divide_by_pseudo_vanishing(uint64_t* coeffs, size_t n_src, size_t n_ta
     if (rc) return rc;
     if (!coeffs) return BBGPU_ERR_ARG;
     if ((rc = stage_in(coeffs, n_target)) != BBGPU_OK) return rc;
-    if ((rc = bbgpu_divide_by_pseudo_vanishing_device(g_ctx.d_stage, n_src, n_target, g_ctx.stream)) != BBGPU_OK) return rc;
-    return stage_out(coeffs, g_ctx.d_stage, n_target, true); // in place, as in bbgpu_ntt
+    if ((rc = bbgpu_divide_by_pseudo_vanishing_device(ctx().d_stage, n_src, n_target, ctx().stream)) != BBGPU_OK) return rc;
+    return stage_out(coeffs, ctx().d_stage, n_target, true); // in place, as in bbgpu_ntt
 }
 
 // polynomial_arithmetic::get_lagrange_evaluations (polynomial_arithmetic.cpp:594-626): {Z_H*(z), L_1(z), L_{n-1}(z)}; host arithmetic
@@ -1608,12 +1856,12 @@ int bbgpu_srs_register(const uint64_t* points_endo_table, size_t n)
     size_t off;
     int idx = find_srs(points_endo_table, n, &off);
     if (idx >= 0 && off == 0) {
-        g_ctx.srs[idx].auto_registered = false; // the caller now holds the handle: never evicted behind its back
-        g_ctx.srs[idx].handle_exposed = true;
+        ctx().srs[idx].auto_registered = false; // the caller now holds the handle: never evicted behind its back
+        ctx().srs[idx].handle_exposed = true;
         return idx;
     }
     uint32_t* d = nullptr;
-    rc = srs_upload(points_endo_table, n, &d, g_ctx.stream);
+    rc = srs_upload(points_endo_table, n, &d, ctx().stream);
     if (rc) return rc;
     return add_srs(points_endo_table, n, d, false);
 }
@@ -1625,7 +1873,7 @@ int bbgpu_srs_generate_range(const uint64_t* x_mont, size_t first, size_t n, uin
     if (rc) return rc;
     if (!x_mont || n == 0 || first > ((size_t)1 << 31) || n > ((size_t)1 << 31)) return BBGPU_ERR_ARG;
     uint32_t* d = nullptr;
-    rc = srs_generate(x_mont, first, n, &d, host_endo_table_out, g_ctx.stream);
+    rc = srs_generate(x_mont, first, n, &d, host_endo_table_out, ctx().stream);
     if (rc) return rc;
     return add_srs(host_endo_table_out, n, d, false);
 }
@@ -1761,19 +2009,19 @@ int bbgpu_srs_set_validate(int srs_handle, int full)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (srs_handle == -1) {
-        g_ctx.srs_validate_full = full != 0;
+        for (auto& C : g_ctxs) C.srs_validate_full = full != 0;
         return BBGPU_OK;
     }
-    if (srs_handle < 0 || srs_handle >= (int)g_ctx.srs.size() || !g_ctx.srs[srs_handle].live) return BBGPU_ERR_ARG;
-    g_ctx.srs[srs_handle].validate_full = full != 0;
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) return BBGPU_ERR_ARG;
+    ctx().srs[srs_handle].validate_full = full != 0;
     return BBGPU_OK;
 }
 
 int bbgpu_srs_release(int handle)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (handle < 0 || handle >= (int)g_ctx.srs.size() || !g_ctx.srs[handle].live) return BBGPU_ERR_ARG;
-    free_entry(g_ctx.srs[handle]);
+    if (handle < 0 || handle >= (int)ctx().srs.size() || !ctx().srs[handle].live) return BBGPU_ERR_ARG;
+    free_entry(ctx().srs[handle]);
     return BBGPU_OK;
 }
 
@@ -1783,7 +2031,7 @@ int bbgpu_srs_cache_stats(int* live_entries, int* auto_entries, uint64_t* auto_b
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     int live = 0, au = 0;
     uint64_t bytes = 0;
-    for (const auto& e : g_ctx.srs)
+    for (const auto& e : ctx().srs)
         if (e.live) {
             live++;
             if (e.auto_registered) {
@@ -1805,8 +2053,8 @@ int bbgpu_msm_num_windows(size_t n)
 int bbgpu_srs_num_windows(int srs_handle, size_t n)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (srs_handle < 0 || srs_handle >= (int)g_ctx.srs.size() || !g_ctx.srs[srs_handle].live) return BBGPU_ERR_ARG;
-    return entry_windows(g_ctx.srs[srs_handle], n);
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) return BBGPU_ERR_ARG;
+    return entry_windows(ctx().srs[srs_handle], n);
 }
 // Multi-GPU: rank `rank` of `world` will only ever be asked for its 1/world share of the (window, point) rows of tables registered
 // from now on, so only the digit windows that share touches are built and kept: 15 x 64 MiB at n = 2^20 become ceil(15 / world) + 1 windows.
@@ -1814,8 +2062,8 @@ void bbgpu_set_table_share(int rank, int world)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (world < 1 || rank < 0 || rank >= world) { rank = 0; world = 1; }
-    g_ctx.share_rank = rank;
-    g_ctx.share_world = world;
+    ctx().share_rank = rank;
+    ctx().share_world = world;
 }
 
 // Multi-GPU, the other split: a rank holds n / world POINTS of a larger MSM as its own SRS (all digit windows of them) and its MSM over the matching
@@ -1823,19 +2071,38 @@ void bbgpu_set_table_share(int rank, int world)
 void bbgpu_set_point_share(int world)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    g_ctx.point_world = world >= 1 && world <= 1024 ? world : 1;
+    ctx().point_world = world >= 1 && world <= 1024 ? world : 1;
 }
 
 void bbgpu_set_precompute(int enabled)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    g_ctx.precompute = enabled != 0;
+    for (auto& C : g_ctxs) C.precompute = enabled != 0;
 }
 
 int bbgpu_msm_g1(const uint64_t* scalars, const uint64_t* points_endo_table, size_t n, uint64_t out[12])
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    return msm_host_ptrs(scalars, points_endo_table, n, out); // binds the device itself unless the host answers (n = 0, tiny unknown tables)
+    multi::Slice sl[BBGPU_MAX_CONTEXTS];
+    const int m = multi::plan_slices(n, g_num_ctx, sl);
+    if (m == 1) return msm_host_ptrs(scalars, points_endo_table, n, out); // binds the device itself unless the host answers (n = 0, tiny unknown tables)
+    if (!scalars || !points_endo_table) {
+        set_error("null scalars/points");
+        return BBGPU_ERR_ARG;
+    }
+    // context k: points [first, first + len) with their own cache lookup / registration on first sight, exact-mode rerun and two-range pipeline
+    host::Xyzz part[BBGPU_MAX_CONTEXTS];
+    const int rc = run_on_contexts(m, [&](int k) {
+        ctx().slice_of_n = n;
+        const int r = msm_host_ptrs_sum(scalars + 4 * sl[k].first, points_endo_table + 16 * sl[k].first, sl[k].len, &part[k]);
+        ctx().slice_of_n = 0;
+        return r;
+    });
+    if (rc) return rc;
+    host::Xyzz acc = part[0];
+    for (int k = 1; k < m; k++) acc = host::g1_add(acc, part[k]); // equal partial sums double, opposite ones cancel (host_g1.hpp)
+    host::g1_to_normalised(acc, out);
+    return BBGPU_OK;
 }
 
 int bbgpu_msm_g1_plain(const uint64_t* scalars, const uint64_t* points, size_t n, uint64_t out[12])
@@ -1847,21 +2114,88 @@ int bbgpu_msm_g1_plain(const uint64_t* scalars, const uint64_t* points, size_t n
 void bbgpu_set_host_thresholds(int msm_max_points, int ntt_max_elements)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    g_ctx.host_env_read = true;
-    g_ctx.host_msm_max = msm_max_points < 0 ? 0 : msm_max_points;
-    g_ctx.host_ntt_max = ntt_max_elements < 0 ? 0 : std::min(64, ntt_max_elements);
+    for (auto& C : g_ctxs) {
+        C.host_env_read = true;
+        C.host_msm_max = msm_max_points < 0 ? 0 : msm_max_points;
+        C.host_ntt_max = ntt_max_elements < 0 ? 0 : std::min(64, ntt_max_elements);
+    }
 }
 
-static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale);
+static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale, host::Xyzz* sums);
+// sums: null -- each job's normalised result goes to its output; else job i's sum goes to sums[i], not normalised (a context's partial sums of a split batch)
+static int msm_g1_batch_run(bbgpu_msm_job* jobs, size_t num_jobs, host::Xyzz* sums)
+{
+    bool stale = false; // exact cache mode: a resident table turned out to differ from the caller's memory -- dropped; the batch runs once more on a fresh upload
+    int rc = msm_g1_batch_once(jobs, num_jobs, &stale, sums);
+    if (stale) rc = msm_g1_batch_once(jobs, num_jobs, &stale, sums);
+    return rc;
+}
+// one at a time: tiny jobs (answered on the host), fewer than two free slots, or jobs above one table segment (each is a pipeline of its own).
+// Else the two-slot pipeline, whose free slots go to sl[0..1].  Caller holds the current context's lock and has called read_host_env().
+static bool batch_one_by_one(size_t n, int* sl)
+{
+    return n == 0 || n <= (size_t)ctx().host_msm_max || n > ((size_t)1 << 20) || free_slots(sl, 2) < 2;
+}
+// the first num_jobs jobs of a batch of equal sizes, non-null pointers, split over m contexts (slices sl): context k takes its slice of EVERY job
+// through its own two-slot pipeline (as the reference's threads each take a range of every job, :703-738); each job's output is the fold of its
+// m partial sums
+static int msm_g1_batch_split(bbgpu_msm_job* jobs, size_t num_jobs, const multi::Slice* sl, int m)
+{
+    if (num_jobs == 0) return BBGPU_OK;
+    const size_t n = jobs[0].num_elements;
+    std::vector<bbgpu_msm_job> local((size_t)m * num_jobs);
+    std::vector<host::Xyzz> part((size_t)m * num_jobs);
+    for (int k = 0; k < m; k++)
+        for (size_t i = 0; i < num_jobs; i++) {
+            bbgpu_msm_job& J = local[(size_t)k * num_jobs + i];
+            J = jobs[i];
+            J.points = jobs[i].points + 16 * sl[k].first;
+            J.scalars = jobs[i].scalars + 4 * sl[k].first;
+            J.num_elements = sl[k].len;
+        }
+    const int rc = run_on_contexts(m, [&](int k) {
+        ctx().slice_of_n = n;
+        const int r = msm_g1_batch_run(&local[(size_t)k * num_jobs], num_jobs, &part[(size_t)k * num_jobs]);
+        ctx().slice_of_n = 0;
+        return r;
+    });
+    if (rc) return rc;
+    for (size_t i = 0; i < num_jobs; i++) {
+        host::Xyzz acc = part[i];
+        for (int k = 1; k < m; k++) acc = host::g1_add(acc, part[(size_t)k * num_jobs + i]);
+        host::g1_to_normalised(acc, jobs[i].output);
+    }
+    return BBGPU_OK;
+}
 int bbgpu_msm_g1_batch(bbgpu_msm_job* jobs, size_t num_jobs)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    bool stale = false; // exact cache mode: a resident table turned out to differ from the caller's memory -- dropped; the batch runs once more on a fresh upload
-    int rc = msm_g1_batch_once(jobs, num_jobs, &stale);
-    if (stale) rc = msm_g1_batch_once(jobs, num_jobs, &stale);
-    return rc;
+    multi::Slice sl[BBGPU_MAX_CONTEXTS];
+    const int m = (num_jobs && jobs) ? multi::plan_slices(jobs[0].num_elements, g_num_ctx, sl) : 1;
+    if (m == 1) return msm_g1_batch_run(jobs, num_jobs, nullptr);
+    // split over the contexts.  The checks of msm_g1_batch_once come first, on the caller's thread, with what one context does on them: unequal sizes
+    // leave every output untouched; a null job i ends the batch with the outputs of the jobs one context would have finished by then written
+    const size_t n = jobs[0].num_elements;
+    for (size_t i = 1; i < num_jobs; i++)
+        if (jobs[i].num_elements != n) {
+            set_error("batched_scalar_multiplications err: each scalar mul must be same size."); // scalar_multiplication.cpp:678-685
+            return BBGPU_ERR_ARG;
+        }
+    for (size_t i = 0; i < num_jobs; i++)
+        if (!jobs[i].scalars || !jobs[i].points) {
+            read_host_env();
+            int fs[2];
+            const bool one_by_one = batch_one_by_one(n, fs);
+            // one by one: jobs 0 .. i-1 are done (msm_host_ptrs reports the null job); the pipeline: job i-1 is issued but not yet collected
+            const size_t done = one_by_one ? i : (i ? i - 1 : 0);
+            if (int rc = msm_g1_batch_split(jobs, done, sl, m)) return rc;
+            if (one_by_one) set_error("null scalars/points");
+            else set_error("null scalars/points in job %zu", i);
+            return BBGPU_ERR_ARG;
+        }
+    return msm_g1_batch_split(jobs, num_jobs, sl, m);
 }
-static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale)
+static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale, host::Xyzz* sums)
 {
     *stale = false;
     int rc = BBGPU_OK;
@@ -1877,23 +2211,23 @@ static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale)
     const size_t n = jobs[0].num_elements;
     read_host_env();
     int sl[2];
-    // one at a time: tiny jobs (answered on the host), fewer than two free slots, or jobs above one table segment (each is a pipeline of its own)
-    bool one_by_one = n == 0 || n <= (size_t)g_ctx.host_msm_max || n > ((size_t)1 << 20) || free_slots(sl, 2) < 2;
+    const bool one_by_one = batch_one_by_one(n, sl);
     if (one_by_one) {
         for (size_t i = 0; i < num_jobs; i++) {
-            rc = msm_host_ptrs(jobs[i].scalars, jobs[i].points, jobs[i].num_elements, jobs[i].output);
+            rc = sums ? msm_host_ptrs_sum(jobs[i].scalars, jobs[i].points, jobs[i].num_elements, &sums[i])
+                      : msm_host_ptrs(jobs[i].scalars, jobs[i].points, jobs[i].num_elements, jobs[i].output);
             if (rc) return rc;
         }
         return BBGPU_OK;
     }
     if ((rc = ensure_init()) != BBGPU_OK) return rc;
     for (int k = 0; k < 2; k++)
-        if ((rc = ensure_slot_stream(g_ctx.slot[sl[k]])) != BBGPU_OK) return rc;
+        if ((rc = ensure_slot_stream(ctx().slot[sl[k]])) != BBGPU_OK) return rc;
     SlotReservation reserve(sl, 2); // a job that straddles two table segments takes its helper elsewhere (or none)
     // Two-slot pipeline over the jobs of a prover round (3/1/3/2 MSMs, prover.cpp:65-122,650-658): job i+1's scalars
     // cross PCIe and its kernels are enqueued while job i's bucket-reduction tail and host finish run.
-    uint64_t** stage[2] = { &g_ctx.d_stage, &g_ctx.d_stage2 };
-    size_t* cap[2] = { &g_ctx.stage_cap, &g_ctx.stage2_cap };
+    uint64_t** stage[2] = { &ctx().d_stage, &ctx().d_stage2 };
+    size_t* cap[2] = { &ctx().stage_cap, &ctx().stage2_cap };
     auto now_ms = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const bool tr = trace_srs();
     struct FullCheck { int idx; size_t off; const uint64_t* points; };
@@ -1901,7 +2235,7 @@ static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale)
     auto issue = [&](size_t i) -> int {
         const double q0 = tr ? now_ms() : 0;
         const int t = (int)(i & 1);
-        MsmSlot& S = g_ctx.slot[sl[t]];
+        MsmSlot& S = ctx().slot[sl[t]];
         if (!jobs[i].scalars || !jobs[i].points) {
             set_error("null scalars/points in job %zu", i);
             return BBGPU_ERR_ARG;
@@ -1911,7 +2245,7 @@ static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale)
         int idx = find_srs(jobs[i].points, n, &off, &full_check);
         if (idx < 0) {
             uint32_t* d = nullptr;
-            int r = srs_upload(jobs[i].points, n, &d, g_ctx.stream);
+            int r = srs_upload(jobs[i].points, n, &d, ctx().stream);
             if (r) return r;
             idx = add_srs(jobs[i].points, n, d, true);
             if (idx < 0) return idx;
@@ -1926,7 +2260,7 @@ static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale)
         if (r) return r;
         if ((r = host_to_device(*stage[t], jobs[i].scalars, n * 32, S.stream)) != BBGPU_OK) return r;
         const double q2 = tr ? now_ms() : 0;
-        r = issue_on_entry(sl[t], g_ctx.srs[idx], off, *stage[t], n, 0, entry_windows(g_ctx.srs[idx], n), S.stream);
+        r = issue_on_entry(sl[t], ctx().srs[idx], off, *stage[t], n, 0, entry_windows(ctx().srs[idx], n), S.stream);
         if (tr) fprintf(stderr, "bbgpu batch: job %zu srs %.3f, copy call %.3f, kernel launches %.3f ms\n", i, q1 - q0, q2 - q1, now_ms() - q2);
         return r;
     };
@@ -1934,7 +2268,8 @@ static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale)
         host::Xyzz res;
         int r = finish_ticket(sl[i & 1], &res, nullptr);
         if (r) return r;
-        host::g1_to_normalised(res, jobs[i].output);
+        if (sums) sums[i] = res;
+        else host::g1_to_normalised(res, jobs[i].output);
         return BBGPU_OK;
     };
     for (size_t i = 0; i < num_jobs && rc == BBGPU_OK; i++) {
@@ -1948,7 +2283,7 @@ static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale)
     if (rc == BBGPU_OK) {
         bool bad = false;
         for (const auto& c : to_check)
-            if (g_ctx.srs[c.idx].live && !contents_match_full(g_ctx.srs[c.idx], c.off, c.points, n)) {
+            if (ctx().srs[c.idx].live && !contents_match_full(ctx().srs[c.idx], c.off, c.points, n)) {
                 srs_mark_stale(c.idx);
                 bad = true;
             }
@@ -1983,11 +2318,11 @@ int bbgpu_msm_g1_device_async(int srs_handle, size_t offset, const uint64_t* d_s
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     int rc = ensure_init();
     if (rc) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)g_ctx.srs.size() || !g_ctx.srs[srs_handle].live) {
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
         set_error("unknown SRS handle %d", srs_handle);
         return BBGPU_ERR_ARG;
     }
-    const SrsEntry& e = g_ctx.srs[srs_handle];
+    const SrsEntry& e = ctx().srs[srs_handle];
     if (offset + n > e.n || (!d_scalars && n)) {
         set_error("MSM range [%zu, %zu) outside the registered table of %zu points", offset, offset + n, e.n);
         return BBGPU_ERR_ARG;
@@ -1997,21 +2332,21 @@ int bbgpu_msm_g1_device_async(int srs_handle, size_t offset, const uint64_t* d_s
     // slots 2 and 3 only take the overflow when both are busy (a prover round's three side-by-side commitments)
     const int t = pick_slot();
     if (t < 0) return BBGPU_ERR_STATE;
-    MsmSlot& S = g_ctx.slot[t];
+    MsmSlot& S = ctx().slot[t];
     if (!S.stream) CHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : S.stream;
     rc = issue_on_entry(t, e, offset, d_scalars, n, window_begin, window_end, st);
     if (rc == BBGPU_ERR_ARG) set_error("bad window range [%d, %d)", window_begin, window_end);
     if (rc) return rc;
-    if (t < 2) g_ctx.next_slot = t ^ 1;
+    if (t < 2) ctx().next_slot = t ^ 1;
     return t;
 }
 
 int bbgpu_srs_has_window_tables(int srs_handle)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (srs_handle < 0 || srs_handle >= (int)g_ctx.srs.size() || !g_ctx.srs[srs_handle].live) return BBGPU_ERR_ARG;
-    return g_ctx.srs[srs_handle].has_tab() ? 1 : 0;
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) return BBGPU_ERR_ARG;
+    return ctx().srs[srs_handle].has_tab() ? 1 : 0;
 }
 
 int bbgpu_msm_g1_device_rows_async(int srs_handle, size_t offset, const uint64_t* d_scalars, size_t n, uint64_t row_begin, uint64_t row_end,
@@ -2020,11 +2355,11 @@ int bbgpu_msm_g1_device_rows_async(int srs_handle, size_t offset, const uint64_t
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     int rc = ensure_init();
     if (rc) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)g_ctx.srs.size() || !g_ctx.srs[srs_handle].live) {
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
         set_error("unknown SRS handle %d", srs_handle);
         return BBGPU_ERR_ARG;
     }
-    const SrsEntry& e = g_ctx.srs[srs_handle];
+    const SrsEntry& e = ctx().srs[srs_handle];
     if (offset + n > e.n || !d_scalars || n == 0) {
         set_error("MSM range [%zu, %zu) outside the registered table of %zu points", offset, offset + n, e.n);
         return BBGPU_ERR_ARG;
@@ -2036,17 +2371,17 @@ int bbgpu_msm_g1_device_rows_async(int srs_handle, size_t offset, const uint64_t
     }
     const int t = pick_slot();
     if (t < 0) return BBGPU_ERR_STATE;
-    MsmSlot& S = g_ctx.slot[t];
+    MsmSlot& S = ctx().slot[t];
     if (!S.stream) CHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : S.stream;
     if (n && row_end > row_begin && !windows_resident(e, (int)(row_begin / n), (int)((row_end + n - 1) / n))) return BBGPU_ERR_STATE;
     S.helper = -1;
     S.append = false;
     S.throughput = others_pending(&S);
-    rc = msm_issue_rows(S, e.d_srs + offset * 16, e.segs[0].d_tab + offset * 16, e.n, e.tab_c, d_scalars, n, row_begin, row_end, st, g_ctx.timing);
+    rc = msm_issue_rows(S, e.d_srs + offset * 16, e.segs[0].d_tab + offset * 16, e.n, e.tab_c, d_scalars, n, row_begin, row_end, st, ctx().timing);
     if (rc == BBGPU_ERR_ARG) set_error("bad row range [%llu, %llu) of %d x %zu", (unsigned long long)row_begin, (unsigned long long)row_end, e.tab_W, n);
     if (rc) return rc;
-    if (t < 2) g_ctx.next_slot = t ^ 1;
+    if (t < 2) ctx().next_slot = t ^ 1;
     return t;
 }
 
@@ -2055,11 +2390,11 @@ int bbgpu_msm_g1_device_buckets_async(int srs_handle, size_t offset, const uint6
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     int rc = ensure_init();
     if (rc) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)g_ctx.srs.size() || !g_ctx.srs[srs_handle].live) {
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
         set_error("unknown SRS handle %d", srs_handle);
         return BBGPU_ERR_ARG;
     }
-    const SrsEntry& e = g_ctx.srs[srs_handle];
+    const SrsEntry& e = ctx().srs[srs_handle];
     if (offset + n > e.n || !d_scalars || n == 0) {
         set_error("MSM range [%zu, %zu) outside the registered table of %zu points", offset, offset + n, e.n);
         return BBGPU_ERR_ARG;
@@ -2071,7 +2406,7 @@ int bbgpu_msm_g1_device_buckets_async(int srs_handle, size_t offset, const uint6
     }
     const int t = pick_slot();
     if (t < 0) return BBGPU_ERR_STATE;
-    MsmSlot& S = g_ctx.slot[t];
+    MsmSlot& S = ctx().slot[t];
     if (!S.stream) CHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : S.stream;
     if (!windows_resident(e, 0, e.tab_W)) return BBGPU_ERR_STATE; // every share reads every window's table
@@ -2082,10 +2417,10 @@ int bbgpu_msm_g1_device_buckets_async(int srs_handle, size_t offset, const uint6
     S.helper = -1;
     S.append = false;
     S.throughput = others_pending(&S);
-    rc = msm_issue_buckets(S, e.d_srs + offset * 16, e.segs[0].d_tab + offset * 16, e.n, e.tab_c, d_scalars, n, (uint32_t)share, (uint32_t)share_count, st, g_ctx.timing);
+    rc = msm_issue_buckets(S, e.d_srs + offset * 16, e.segs[0].d_tab + offset * 16, e.n, e.tab_c, d_scalars, n, (uint32_t)share, (uint32_t)share_count, st, ctx().timing);
     if (rc == BBGPU_ERR_ARG) set_error("bad bucket share %d of %d (at most one share per row of the bucket matrix)", share, share_count);
     if (rc) return rc;
-    if (t < 2) g_ctx.next_slot = t ^ 1;
+    if (t < 2) ctx().next_slot = t ^ 1;
     return t;
 }
 
@@ -2094,11 +2429,11 @@ int bbgpu_msm_g1_device_batch_async(int srs_handle, size_t offset, const uint64_
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     int rc = ensure_init();
     if (rc) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)g_ctx.srs.size() || !g_ctx.srs[srs_handle].live) {
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
         set_error("unknown SRS handle %d", srs_handle);
         return BBGPU_ERR_ARG;
     }
-    const SrsEntry& e = g_ctx.srs[srs_handle];
+    const SrsEntry& e = ctx().srs[srs_handle];
     if (!d_scalars || jobs < 1 || offset + n > e.n) {
         set_error("bad batch: jobs %d, range [%zu, %zu) of %zu points", jobs, offset, offset + n, e.n);
         return BBGPU_ERR_ARG;
@@ -2109,12 +2444,12 @@ int bbgpu_msm_g1_device_batch_async(int srs_handle, size_t offset, const uint64_
     }
     const int t = pick_slot();
     if (t < 0) return BBGPU_ERR_STATE;
-    MsmSlot& S = g_ctx.slot[t];
+    MsmSlot& S = ctx().slot[t];
     if (!S.stream) CHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : S.stream;
     rc = issue_ticket(t, e, offset, d_scalars, jobs, n, 0, entry_windows(e, n), st);
     if (rc) return rc;
-    if (t < 2) g_ctx.next_slot = t ^ 1;
+    if (t < 2) ctx().next_slot = t ^ 1;
     return t;
 }
 
@@ -2128,10 +2463,10 @@ static void wait_ticket_events_unlocked(int ticket)
     hipEvent_t ev[2] = { nullptr, nullptr };
     {
         std::lock_guard<std::recursive_mutex> lk(g_mu);
-        if (ticket < 0 || ticket >= Context::NSLOT || !g_ctx.slot[ticket].pending || g_ctx.slot[ticket].is_helper) return; // the locked part reports it
-        const MsmSlot& S = g_ctx.slot[ticket];
+        if (ticket < 0 || ticket >= Context::NSLOT || !ctx().slot[ticket].pending || ctx().slot[ticket].is_helper) return; // the locked part reports it
+        const MsmSlot& S = ctx().slot[ticket];
         ev[0] = S.done;
-        if (S.helper >= 0) ev[1] = g_ctx.slot[S.helper].done;
+        if (S.helper >= 0) ev[1] = ctx().slot[S.helper].done;
     }
     for (hipEvent_t e : ev)
         if (e) (void)hipEventSynchronize(e); // errors surface in the locked finish, which synchronises again
@@ -2141,13 +2476,13 @@ int bbgpu_msm_g1_batch_wait(int ticket, uint64_t* out)
 {
     wait_ticket_events_unlocked(ticket);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (ticket < 0 || ticket >= Context::NSLOT || !g_ctx.slot[ticket].pending || g_ctx.slot[ticket].is_helper || !out) {
+    if (ticket < 0 || ticket >= Context::NSLOT || !ctx().slot[ticket].pending || ctx().slot[ticket].is_helper || !out) {
         set_error("no MSM batch in flight for ticket %d", ticket);
         return BBGPU_ERR_ARG;
     }
     host::Xyzz res[MSM_MAX_JOBS];
-    const uint32_t jobs = g_ctx.slot[ticket].jobs;
-    int rc = finish_ticket(ticket, res, &g_ctx.last);
+    const uint32_t jobs = ctx().slot[ticket].jobs;
+    int rc = finish_ticket(ticket, res, &ctx().last);
     if (rc) return rc;
     host::g1_batch_to_normalised(res, jobs, out); // one inversion for the whole batch
     return BBGPU_OK;
@@ -2157,12 +2492,12 @@ int bbgpu_msm_g1_wait(int ticket, uint64_t out[12])
 {
     wait_ticket_events_unlocked(ticket);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (ticket < 0 || ticket >= Context::NSLOT || !g_ctx.slot[ticket].pending || g_ctx.slot[ticket].is_helper || g_ctx.slot[ticket].jobs != 1) {
+    if (ticket < 0 || ticket >= Context::NSLOT || !ctx().slot[ticket].pending || ctx().slot[ticket].is_helper || ctx().slot[ticket].jobs != 1) {
         set_error("no MSM in flight for ticket %d", ticket);
         return BBGPU_ERR_ARG;
     }
     host::Xyzz res;
-    int rc = finish_ticket(ticket, &res, &g_ctx.last);
+    int rc = finish_ticket(ticket, &res, &ctx().last);
     if (rc) return rc;
     host::g1_to_normalised(res, out);
     return BBGPU_OK;

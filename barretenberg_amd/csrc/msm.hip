@@ -1440,13 +1440,13 @@ constexpr uint32_t ACC_WG_PER_CU = 3;
 constexpr uint32_t ACC_LDS_RESERVE = 41 * 1024; // 3 x 41 KiB fit in 160 KiB, 4 do not
 static uint32_t acc_capacity_lanes()
 {
-    static uint32_t lanes = 0;
-    if (!lanes) {
+    // initialised once, thread-safely: the worker threads of a split MSM (capi.hip) may ask at the same time
+    static const uint32_t lanes = [] {
         int dev = 0, cus = 256;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        lanes = (uint32_t)cus * ACC_WG_PER_CU * MSM_THREADS;
-    }
+        return (uint32_t)cus * ACC_WG_PER_CU * MSM_THREADS;
+    }();
     return lanes;
 }
 // chunk length of K4: one resident wave of workgroups covers the whole entry list (no tail wave), >= MIN_CHUNK entries per lane
@@ -1624,16 +1624,29 @@ int msm_issue_buckets(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, 
 // enqueued while the previous one still runs (its sort is done early), so the event pair around the kernel also measures the time it sat
 // in the queue; the kernel cannot execute before the previous accumulation has drained (one resident wave of workgroups fills the chip),
 // so its execution time is at most the spacing of consecutive "ended" events.
-constexpr int ACC_RING = 8;
-static hipEvent_t g_acc_end[ACC_RING];
-static uint64_t g_acc_seq = 0; // number of timed accumulations issued so far
+// One ring per device context (AccRing, bbgpu_internal.h): the contexts of a split MSM issue concurrently.
+constexpr int ACC_RING = AccRing::SIZE;
 static int acc_ring_record(MsmSlot& S, hipStream_t st)
 {
-    if (g_acc_seq == 0)
-        for (int i = 0; i < ACC_RING; i++) HIPCHK(hipEventCreate(&g_acc_end[i]));
-    S.acc_seq = ++g_acc_seq;
-    HIPCHK(hipEventRecord(g_acc_end[S.acc_seq % ACC_RING], st));
+    AccRing* R = S.acc_ring;
+    if (!R) {
+        S.acc_seq = 0;
+        return BBGPU_OK;
+    }
+    if (R->seq == 0)
+        for (int i = 0; i < ACC_RING; i++) HIPCHK(hipEventCreate(&R->end[i]));
+    S.acc_seq = ++R->seq;
+    HIPCHK(hipEventRecord(R->end[S.acc_seq % ACC_RING], st));
     return BBGPU_OK;
+}
+void AccRing::release()
+{
+    if (seq)
+        for (auto& e : end) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    seq = 0;
 }
 int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, size_t tab_stride, int tab_c, const uint64_t* const* d_scalars_v, int jobs,
                     size_t n, int wb, int we, hipStream_t st, int want_timing, uint32_t row_i0, uint32_t row_i1, uint32_t brow0, uint32_t brow1)
@@ -1906,8 +1919,9 @@ static int finish_timing(MsmSlot& S, MsmTiming* timing)
         }
         float exec = timing->ms[3];
         // previous timed accumulation still in the ring (not overwritten by a later issue) and already finished (it precedes this one)
-        if (S.acc_seq > 1 && g_acc_seq - (S.acc_seq - 1) < (uint64_t)ACC_RING &&
-            hipEventElapsedTime(&ms, g_acc_end[(S.acc_seq - 1) % ACC_RING], g_acc_end[S.acc_seq % ACC_RING]) == hipSuccess && ms > 0.0f && ms < exec)
+        const AccRing* R = S.acc_ring;
+        if (R && S.acc_seq > 1 && R->seq - (S.acc_seq - 1) < (uint64_t)ACC_RING &&
+            hipEventElapsedTime(&ms, R->end[(S.acc_seq - 1) % ACC_RING], R->end[S.acc_seq % ACC_RING]) == hipSuccess && ms > 0.0f && ms < exec)
             exec = ms;
         (void)hipGetLastError();
         timing->ms[timing->count++] = exec;

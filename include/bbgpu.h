@@ -48,8 +48,30 @@ typedef enum {
 
 /* ---- lifetime ---------------------------------------------------------------------------------------------------- */
 int bbgpu_init(int device);       /* binds the calling process to one GPU (one process per GPU), allocates workspaces */
-void bbgpu_shutdown(void);
+void bbgpu_shutdown(void);        /* tears down every device context; the process may bind again afterwards */
 int bbgpu_device_count(void);
+
+/* ---- several GPUs from one process ---------------------------------------------------------------------------------
+ * bbgpu_init_devices binds the process to `count` device contexts, context k on HIP device devices[k].  Entries may repeat: two contexts on one
+ * device share nothing but the GPU (own streams, MSM slots, staging buffers, SRS cache).  Call it before any other GPU entry, or after
+ * bbgpu_shutdown().  BBGPU_ERR_ARG: null `devices`, count < 1 or > BBGPU_MAX_CONTEXTS, a negative device, a device >= bbgpu_device_count();
+ * BBGPU_ERR_HIP without any device; BBGPU_ERR_STATE when the process is already bound to another set of contexts.  bbgpu_init(d) afterwards
+ * returns BBGPU_OK when d == devices[0].
+ * What is split: ONLY the two host-pointer MSM entries, bbgpu_msm_g1 and bbgpu_msm_g1_batch.  A call of n points uses m = min(count, n / 2^16)
+ * contexts (at least 1); context k takes points [n k / m, n (k + 1) / m) of every job, on a worker thread of its own that the library keeps for
+ * the life of the binding, and the m partial sums are added on the host -- the point-range split of batched_scalar_multiplications
+ * (scalar_multiplication.cpp:703-738), over GPUs instead of threads.  The result is the one-context result, bit for bit.  With m == 1 the call runs
+ * on context 0 as it does without this binding.  Everything else -- transforms, polynomial helpers, bbgpu_msm_g1_plain, the device-pointer MSMs
+ * and their tickets, SRS handles, the resident prover -- runs on context 0.
+ * Memory: each context caches the slices it was given of a table registered on first sight (1 / m of its points and window tables each);
+ * BBGPU_SRS_CACHE_BYTES caps every context's cache on its own.  A table registered EXPLICITLY stays whole on context 0 (its handle serves the
+ * device entries); a split call over it uses it there for context 0's slice and the other contexts register their slices on first sight.
+ * Settings (bbgpu_set_precompute, bbgpu_set_host_thresholds, bbgpu_set_timing, the exact-mode default of bbgpu_srs_set_validate) apply to every
+ * context; the share settings (bbgpu_set_table_share / _point_share) to context 0 only.  A failure in one context is reported as
+ * "context k (device d): ..." after every context has drained its work; the next call starts clean. */
+#define BBGPU_MAX_CONTEXTS 8
+int bbgpu_init_devices(const int* devices, int count);
+int bbgpu_num_contexts(void); /* 1 unless bbgpu_init_devices bound more */
 const char* bbgpu_last_error(void);
 const char* bbgpu_version(void);
 
@@ -70,7 +92,8 @@ typedef struct {
     uint64_t staging_bytes;       /* scalar / coefficient staging, transform scratch, polynomial temporaries */
     uint64_t pinned_host_bytes;   /* pinned host memory: staging buffers and the slots' result arrays */
 } bbgpu_memory_info;
-int bbgpu_memory_stats(bbgpu_memory_info* out);
+int bbgpu_memory_stats(bbgpu_memory_info* out);                     /* the sum over every bound context */
+int bbgpu_memory_stats_context(int context, bbgpu_memory_info* out); /* one context's share (the transforms' tables are context 0's); BBGPU_ERR_ARG for an unbound context */
 
 /* ---- the error contract on a machine that HAS a GPU: fault injection (testing) ---------------------------------------
  * The reference API has no error channel (assert.hpp:19-23 compiles to nothing, scalar_multiplication.cpp:680-684 prints and returns), so a GPU call
