@@ -50,6 +50,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_generate_point_table",
     "bbgpu_plonk_prover_create", "bbgpu_plonk_prover_set_witness", "bbgpu_plonk_construct_proof", "bbgpu_plonk_preprocess", "bbgpu_plonk_last_challenges",
     "bbgpu_plonk_last_timing", "bbgpu_plonk_prover_destroy", "bbgpu_plonk_challenges_from_proof",
+    "bbgpu_plonk_construct_proof_batch", "bbgpu_plonk_batch_challenges", "bbgpu_plonk_last_batch_timing",
     "bbgpu_host_msm_g1", "bbgpu_host_ntt", "bbgpu_host_fr_evaluate", "bbgpu_host_kate_opening", "bbgpu_host_lagrange_l1_fft",
     "bbgpu_host_divide_by_pseudo_vanishing", "bbgpu_memory_stats", "bbgpu_fault_inject", "bbgpu_fault_stats", "bbgpu_srs_set_validate",
     "bbgpu_init_devices", "bbgpu_num_contexts", "bbgpu_memory_stats_context",

@@ -122,5 +122,6 @@ int bind_calling_thread(); // initialises the library if need be and makes the b
 // plonk.hip
 std::mutex& plonk_mutex();        // taken BEFORE capi.hip's mutex wherever both are held
 void plonk_release_all_locked();  // caller holds plonk_mutex()
+uint64_t plonk_lane_bytes();      // device bytes the batch lanes of all provers hold (lock-free: read by bbgpu_memory_stats under capi.hip's mutex)
 
 } // namespace bbgpu

@@ -13,6 +13,8 @@
 // 2n coset) is computed on first use and kept, where the reference recomputes it inside every construct_proof().
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <mutex>
 #include <stdint.h>
@@ -66,6 +68,8 @@ static_assert(sizeof(Proof) == BBGPU_PLONK_PROOF_WORDS * 8, "proof layout");
 struct Challenges {
     Fr beta, gamma, alpha, z, nu;
 };
+
+std::atomic<uint64_t> g_lane_bytes{ 0 }; // device bytes held by the lanes of every prover's batches (bbgpu_memory_stats: staging_bytes)
 
 class PlonkProver {
   public:
@@ -124,6 +128,17 @@ class PlonkProver {
     void release()
     {
         if (st) (void)hipStreamSynchronize(st);
+        release_lanes();
+        if (sigma_coeff) (void)dev_free(sigma_coeff);
+        sigma_coeff = nullptr;
+        lane_tab.release();
+        lane_scratch.release();
+        if (h_lane_slots) (void)hipHostFree(h_lane_slots);
+        h_lane_slots = nullptr;
+        for (hipStream_t& q : st_ticket) {
+            if (q) (void)hipStreamDestroy(q);
+            q = nullptr;
+        }
         for (void* p : allocs) (void)dev_free(p);
         allocs.clear();
         if (h_slots) (void)hipHostFree(h_slots);
@@ -347,7 +362,8 @@ class PlonkProver {
         host::hash_field_elements(buf.data(), buf.size() / 4, h.d);
         return host::fr_to_mont(h); // challenge.hpp:70-71: the raw 256-bit digest, reduced by the Montgomery conversion
     }
-    std::vector<uint64_t> transcript_upto(int stage) const
+    std::vector<uint64_t> transcript_upto(int stage) const { return transcript_of(proof, stage); }
+    static std::vector<uint64_t> transcript_of(const Proof& proof, int stage)
     {
         std::vector<uint64_t> b;
         put_point(b, proof.W_L); put_point(b, proof.W_R); put_point(b, proof.W_O);                  // add_wire_commitments_to_buffer
@@ -568,6 +584,22 @@ class PlonkProver {
         HIPCHK(hipStreamSynchronize(st));
         Fr ev[9];
         memcpy(ev, h_slots, (size_t)nev * 32);
+        take_evaluations(proof, beta_inv, ev, t_eval);
+        const uint64_t* pl[12];
+        Fr cl[12];
+        const int terms = linearisation_terms(proof, challenges, beta_inv, z, sigma[2], pl, cl);
+        poly::LinCombArgs A{};
+        for (int j = 0; j < terms; j++) A.p[j] = (const uint32_t*)pl[j];
+        A.count = terms;
+        A.out = (uint32_t*)r;
+        A.n = (uint32_t)n;
+        RC(poly::lincomb(A, cl, st));
+        RC(poly::evaluate(r, n, zc, &proof.linear_eval, scratch, st)); // :536
+        return BBGPU_OK;
+    }
+    // the evaluations of one proof, in the order of the jobs above (:478-515)
+    void take_evaluations(Proof& proof, const Fr& beta_inv, const Fr ev[9], Fr* t_eval) const
+    {
         if (has_mimc || has_seq) proof.w_o_shifted_eval = ev[7];
         if (has_mimc) proof.q_mimc_coefficient_eval = ev[8];
         proof.w_l_eval = ev[0];
@@ -577,7 +609,13 @@ class PlonkProver {
         proof.sigma_2_eval = host::fr_mul(ev[4], beta_inv);
         proof.z_1_shifted_eval = ev[5];
         *t_eval = ev[6];
-
+    }
+    // r as a linear combination of resident vectors: Z and beta S_3 (`z_poly`, `sigma3_poly`: the proof's own) and the circuit's selectors; returns the
+    // number of terms, pointers in pl, coefficients in cl
+    int linearisation_terms(const Proof& proof, const Challenges& challenges, const Fr& beta_inv, const uint64_t* z_poly, const uint64_t* sigma3_poly,
+                            const uint64_t* pl[12], Fr cl[12]) const
+    {
+        const Fr& zc = challenges.z;
         // linearizer.hpp:29-83
         const Fr k1 = host::fr_from_limbs(FrHostP::GEN5), k2 = host::fr_from_limbs(FrHostP::GEN7);
         const Fr &alpha = challenges.alpha, &beta = challenges.beta, &gamma = challenges.gamma;
@@ -595,16 +633,13 @@ class PlonkProver {
         // :520-528 and arithmetic_widget.cpp:106-126 in one pass: r = z_1 Z + (sigma_3 / beta)(beta S_3) + alpha^4 (...selectors...)
         const Fr alpha4 = host::fr_sqr(host::fr_sqr(alpha));
         const Fr w_lr = host::fr_mul(proof.w_l_eval, proof.w_r_eval);
-        poly::LinCombArgs A{};
-        const uint64_t* ps[10] = { z, sigma[2], q_coeff[0], q_coeff[1], q_coeff[2], q_coeff[3], q_coeff[4], qb_coeff[0], qb_coeff[1], qb_coeff[2] };
+        const uint64_t* ps[10] = { z_poly, sigma3_poly, q_coeff[0], q_coeff[1], q_coeff[2], q_coeff[3], q_coeff[4], qb_coeff[0], qb_coeff[1], qb_coeff[2] };
         // bool_widget.cpp:106-124: (w^2 - w) alpha^5, alpha^6, alpha^7 on q_bl, q_br, q_bo
         const Fr alpha5 = host::fr_mul(alpha4, alpha), alpha6 = host::fr_mul(alpha5, alpha), alpha7 = host::fr_mul(alpha6, alpha);
         auto boolmul = [](const Fr& e, const Fr& a) { return host::fr_mul(host::fr_sub(host::fr_sqr(e), e), a); };
         const Fr cs[10] = { lt_z1, host::fr_mul(lt_sigma3, beta_inv), host::fr_mul(w_lr, alpha4), host::fr_mul(proof.w_l_eval, alpha4),
                             host::fr_mul(proof.w_r_eval, alpha4), host::fr_mul(proof.w_o_eval, alpha4), alpha4,
                             boolmul(proof.w_l_eval, alpha5), boolmul(proof.w_r_eval, alpha6), boolmul(proof.w_o_eval, alpha7) };
-        const uint64_t* pl[12];
-        Fr cl[12];
         int terms = 7;
         for (int j = 0; j < 7; j++) { pl[j] = ps[j]; cl[j] = cs[j]; }
         if (has_seq) { // sequential_widget.cpp:64-74: w_o(z omega) * alpha^4 on q_o_next
@@ -620,26 +655,22 @@ class PlonkProver {
             pl[terms] = qm_coeff[0];
             cl[terms++] = host::fr_mul(host::fr_add(b, a), alpha5);
         }
-        for (int j = 0; j < terms; j++) A.p[j] = (const uint32_t*)pl[j];
-        A.count = terms;
-        A.out = (uint32_t*)r;
-        A.n = (uint32_t)n;
-        RC(poly::lincomb(A, cl, st));
-        RC(poly::evaluate(r, n, zc, &proof.linear_eval, scratch, st)); // :536
-        return BBGPU_OK;
+        return terms;
+    }
+    static Fr nu_challenge(const Proof& proof, const Fr& t_eval)
+    {
+        std::vector<uint64_t> b = transcript_of(proof, 2); // compute_linearisation_challenge, challenge.hpp:114-125
+        put_fr(b, proof.w_l_eval); put_fr(b, proof.w_r_eval); put_fr(b, proof.w_o_eval);
+        put_fr(b, proof.sigma_1_eval); put_fr(b, proof.sigma_2_eval); put_fr(b, proof.z_1_shifted_eval);
+        put_fr(b, proof.linear_eval); put_fr(b, t_eval);
+        return challenge(b);
     }
     // prover.cpp:540-659
     int compute_opening_elements()
     {
         Fr t_eval;
         RC(compute_linearisation_coefficients(&t_eval));
-        {
-            std::vector<uint64_t> b = transcript_upto(2); // compute_linearisation_challenge, challenge.hpp:114-125
-            put_fr(b, proof.w_l_eval); put_fr(b, proof.w_r_eval); put_fr(b, proof.w_o_eval);
-            put_fr(b, proof.sigma_1_eval); put_fr(b, proof.sigma_2_eval); put_fr(b, proof.z_1_shifted_eval);
-            put_fr(b, proof.linear_eval); put_fr(b, t_eval);
-            challenges.nu = challenge(b);
-        }
+        challenges.nu = nu_challenge(proof, t_eval);
         Fr nu[8];
         nu[0] = challenges.nu;
         for (int i = 1; i < 8; i++) nu[i] = host::fr_mul(nu[i - 1], nu[0]);
@@ -725,10 +756,516 @@ class PlonkProver {
         timing[2] = timing[0] - timing[1];
         return BBGPU_OK;
     }
+
+    // ==== a batch of proofs of this circuit, advanced in lockstep (bbgpu_plonk_construct_proof_batch) =================================================
+    // The circuit-only state above is shared; every LANE has the per-proof vectors of init() once more, lane-major inside one allocation per group, so
+    // that the same polynomial of all lanes is one strided batch for the transforms and one launch (grid.y = lane) for the kernels of poly.hip.
+    // Each host synchronisation point of construct_proof() is reached once per batch: the device work of all lanes is enqueued, then the host finishes
+    // every lane's commitments, hashes every lane's transcript and enqueues the next round.
+    struct Lane {
+        Challenges ch;
+        Proof proof;
+        Fr t_eval, beta_inv;
+    };
+    enum { G_WLAG, G_W, G_SIGMA, G_WFFT, G_SFFT, G_Z, G_ZFFT, G_QL, G_QM, G_R, G_TMP, G_COUNT };
+    static constexpr int lane_group_vectors[G_COUNT] = { 3, 3, 3, 12, 12, 1, 4, 4, 2, 1, 3 }; // n-sized vectors per lane: 48 in all
+    int lanes_cap = 0;
+    uint64_t* lane_group[G_COUNT] = {};
+    uint64_t* lane_slots = nullptr;   // 16 x 32 bytes of device results per lane
+    void* h_lane_slots = nullptr;     // pinned mirror, BBGPU_PLONK_MAX_BATCH lanes
+    uint64_t* sigma_coeff = nullptr;  // the three sigma polynomials in coefficient form, UNSCALED: once per circuit (the lanes scale them by their beta)
+    poly::LaneTable lane_tab;
+    poly::Scratch lane_scratch;
+    hipStream_t st_ticket[8] = {};    // one queue per MSM slot: tickets that share a stream serialise
+    std::vector<Lane> lanes;
+    Challenges batch_challenges[BBGPU_PLONK_MAX_BATCH] = {};
+    int batch_count = 0;
+    double batch_timing[4] = {};
+
+    size_t lane_bytes() const { return (size_t)lanes_cap * (48 * n * 32 + 16 * 32); }
+    void release_lanes()
+    {
+        for (uint64_t*& g : lane_group) {
+            if (g) (void)dev_free(g);
+            g = nullptr;
+        }
+        if (lane_slots) (void)dev_free(lane_slots);
+        lane_slots = nullptr;
+        g_lane_bytes -= lane_bytes();
+        lanes_cap = 0;
+    }
+    // vector k of group g of lane l
+    uint64_t* lv(int g, int l, int k = 0) const { return lane_group[g] + ((size_t)l * lane_group_vectors[g] + k) * n * 4; }
+    uint64_t* lslot(int l, int k) const { return lane_slots + ((size_t)l * 16 + k) * 4; }
+    int ensure_lanes(int count)
+    {
+        if (!st_ticket[0])
+            for (hipStream_t& q : st_ticket) HIPCHK(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+        if (!h_lane_slots) HIPCHK(hipHostMalloc(&h_lane_slots, (size_t)BBGPU_PLONK_MAX_BATCH * 16 * 32));
+        RC(lane_tab.init((size_t)2 << 20));
+        if (!sigma_coeff) { // prover.cpp:245-247 without the beta
+            uint64_t* sc = nullptr;
+            HIPCHK(dev_malloc((void**)&sc, 3 * n * 32));
+            int rc = copy(sc, sigma_lagrange[0], 3 * n);
+            if (!rc) rc = ntt_batch(sc, n, 3, BBGPU_IFFT);
+            if (rc) {
+                (void)hipStreamSynchronize(st);
+                (void)dev_free(sc);
+                return rc;
+            }
+            sigma_coeff = sc;
+        }
+        if (count <= lanes_cap) return BBGPU_OK;
+        HIPCHK(hipStreamSynchronize(st));
+        release_lanes(); // nothing of a lane outlives its batch: a larger count starts over
+        lanes_cap = count;
+        g_lane_bytes += lane_bytes();
+        int rc = BBGPU_OK;
+        for (int g = 0; g < G_COUNT && !rc; g++)
+            if (dev_malloc((void**)&lane_group[g], (size_t)count * lane_group_vectors[g] * n * 32) != hipSuccess) rc = BBGPU_ERR_HIP;
+        if (!rc && dev_malloc((void**)&lane_slots, (size_t)count * 16 * 32) != hipSuccess) rc = BBGPU_ERR_HIP;
+        if (rc) release_lanes(); // a refused allocation gives back the groups it had got
+        return rc;
+    }
+
+    // `total` commitments over n scalars each, as batch tickets of up to MSM_MAX_JOBS jobs on queues of their own behind `scalars_ready`; over an SRS
+    // without window tables, single tickets.  As many tickets as there are free slots go out at once; the rest follows when those are collected.
+    // Whatever happens in between, the destructor collects what is still outstanding (see PendingCommit).
+    struct PendingMany {
+        struct Tk { int ticket, first, jobs; bool batched; };
+        std::vector<Tk> held;
+        std::vector<const uint64_t*> scalars;
+        int next = 0, streams = 0;
+        bool batched = true;
+        double t0 = 0.0;
+        PendingMany() = default;
+        PendingMany(const PendingMany&) = delete;
+        PendingMany& operator=(const PendingMany&) = delete;
+        ~PendingMany() { drain(); }
+        void drain()
+        {
+            uint64_t sink[4 * 12];
+            for (const Tk& t : held) (void)(t.batched ? bbgpu_msm_g1_batch_wait(t.ticket, sink) : bbgpu_msm_g1_wait(t.ticket, sink));
+            held.clear();
+        }
+    };
+    // issues tickets until everything is out or no slot is free
+    int commit_many_issue(PendingMany& P)
+    {
+        const int total = (int)P.scalars.size();
+        while (P.next < total) {
+            hipStream_t q = st_ticket[P.streams % 8];
+            int t, jobs;
+            if (P.batched) {
+                jobs = std::min(total - P.next, (int)MSM_MAX_JOBS);
+                HIPCHK(hipStreamWaitEvent(q, scalars_ready, 0));
+                t = bbgpu_msm_g1_device_batch_async(srs, 0, P.scalars.data() + P.next, jobs, n, q);
+                if (t == BBGPU_ERR_ARG && P.held.empty() && P.next == 0) { // no window tables on this SRS: side-by-side single MSMs
+                    P.batched = false;
+                    continue;
+                }
+            } else {
+                jobs = 1;
+                const int W = bbgpu_srs_num_windows(srs, n);
+                if (W < 0) return W;
+                HIPCHK(hipStreamWaitEvent(q, scalars_ready, 0));
+                t = bbgpu_msm_g1_device_async(srs, 0, P.scalars[P.next], n, 0, W, q);
+            }
+            if (t == BBGPU_ERR_STATE && !P.held.empty()) return BBGPU_OK; // every free slot is taken: collect first
+            if (t < 0) return t;
+            P.held.push_back({ t, P.next, jobs, P.batched });
+            P.next += jobs;
+            P.streams++;
+        }
+        return BBGPU_OK;
+    }
+    int commit_many_begin(PendingMany& P)
+    {
+        P.t0 = now_ms();
+        HIPCHK(hipEventRecord(scalars_ready, st)); // the scalars are produced on `st`
+        return commit_many_issue(P);
+    }
+    int commit_many_end(PendingMany& P, uint64_t (*out)[8])
+    {
+        uint64_t res[4 * 12];
+        for (;;) {
+            while (!P.held.empty()) {
+                const PendingMany::Tk t = P.held.front();
+                P.held.erase(P.held.begin()); // a wait consumes the ticket whatever it returns
+                RC(t.batched ? bbgpu_msm_g1_batch_wait(t.ticket, res) : bbgpu_msm_g1_wait(t.ticket, res));
+                for (int i = 0; i < t.jobs; i++) memcpy(out[t.first + i], res + 12 * i, 64); // normalised: x, y canonical
+            }
+            if (P.next >= (int)P.scalars.size()) break;
+            RC(commit_many_issue(P));
+        }
+        batch_timing[1] += now_ms() - P.t0;
+        return BBGPU_OK;
+    }
+    int read_lane_slots(int count)
+    {
+        HIPCHK(d2h_async(h_lane_slots, lane_slots, (size_t)count * 16 * 32, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return BBGPU_OK;
+    }
+    Fr host_slot(int l, int k) const
+    {
+        Fr v;
+        memcpy(v.d, (const uint8_t*)h_lane_slots + ((size_t)l * 16 + k) * 32, 32);
+        return v;
+    }
+
+    int construct_proof_batch(int count, const uint64_t* const* hwl, const uint64_t* const* hwr, const uint64_t* const* hwo, uint64_t* proofs_out)
+    {
+        batch_timing[0] = batch_timing[1] = batch_timing[2] = 0;
+        RC(prepare_circuit());
+        RC(ensure_lanes(count));
+        const double t0 = now_ms();
+        lanes.assign((size_t)count, Lane{});
+        lane_tab.reset();
+        const size_t n4 = 4 * n, n2 = 2 * n;
+        const int L = count;
+        std::vector<Fr> fa((size_t)3 * L), fb((size_t)3 * L), fc((size_t)L);
+        std::vector<uint64_t> pts((size_t)3 * L * 8);
+        uint64_t(*out)[8] = reinterpret_cast<uint64_t(*)[8]>(pts.data());
+
+        // ---- round 1: wires (prover.cpp:124-133, :65-86)
+        for (int l = 0; l < L; l++) {
+            const uint64_t* hw[3] = { hwl[l], hwr[l], hwo[l] };
+            for (int k = 0; k < 3; k++) RC(host_to_device(lv(G_WLAG, l, k), hw[k], n * 32, st));
+        }
+        RC(copy(lv(G_W, 0), lv(G_WLAG, 0), (size_t)3 * L * n));
+        RC(bbgpu_ntt_device_batch(lv(G_W, 0), n, n, 3 * L, BBGPU_IFFT, nullptr, st));
+        {
+            PendingMany P;
+            for (int l = 0; l < L; l++)
+                for (int k = 0; k < 3; k++) P.scalars.push_back(lv(G_W, l, k));
+            RC(commit_many_begin(P));
+            // beside the commitments: the wires on the 4n coset (prover.cpp:418-425) need no challenge
+            std::vector<poly::CopyPadArgs> cp((size_t)3 * L);
+            for (int l = 0; l < L; l++)
+                for (int k = 0; k < 3; k++) {
+                    poly::CopyPadArgs& C = cp[(size_t)l * 3 + k];
+                    C = poly::CopyPadArgs{};
+                    C.dst = (uint32_t*)(lv(G_WFFT, l) + (size_t)k * n4 * 4);
+                    C.src = (const uint32_t*)lv(G_W, l, k);
+                    C.n_src = (uint32_t)n;
+                    C.n_dst = (uint32_t)n4;
+                }
+            RC(poly::copy_pad_lanes(lane_tab, cp.data(), 3 * L, nullptr, st));
+            RC(bbgpu_ntt_device_batch(lv(G_WFFT, 0), n4, n4, 3 * L, BBGPU_COSET_FFT, nullptr, st));
+            RC(commit_many_end(P, out));
+        }
+        for (int l = 0; l < L; l++) {
+            Lane& X = lanes[l];
+            memcpy(X.proof.W_L, out[3 * l], 64);
+            memcpy(X.proof.W_R, out[3 * l + 1], 64);
+            memcpy(X.proof.W_O, out[3 * l + 2], 64);
+            std::vector<uint64_t> b = transcript_of(X.proof, 0);
+            X.ch.gamma = challenge(b); // compute_gamma, challenge.hpp:64-73
+            put_fr(b, X.ch.gamma);
+            X.ch.beta = challenge(b);  // compute_beta, :75-85
+            fa[l] = X.ch.beta;
+            fb[l] = X.ch.gamma;
+        }
+
+        // ---- round 2: the grand product (prover.cpp:135-222, :88-105); see compute_z_coefficients for the scans
+        {
+            std::vector<poly::ZTermsArgs> za((size_t)L);
+            std::vector<poly::ScanJob> sj((size_t)2 * L);
+            for (int l = 0; l < L; l++) {
+                poly::ZTermsArgs& A = za[l];
+                A = poly::ZTermsArgs{};
+                A.w_l = (const uint32_t*)lv(G_WLAG, l, 0); A.w_r = (const uint32_t*)lv(G_WLAG, l, 1); A.w_o = (const uint32_t*)lv(G_WLAG, l, 2);
+                A.s1 = (const uint32_t*)sigma_lagrange[0]; A.s2 = (const uint32_t*)sigma_lagrange[1]; A.s3 = (const uint32_t*)sigma_lagrange[2];
+                A.num = (uint32_t*)lv(G_TMP, l, 0); A.den = (uint32_t*)lv(G_TMP, l, 1);
+                A.n = (uint32_t)n;
+                poly::ScanJob &pn = sj[(size_t)2 * l], &sd = sj[(size_t)2 * l + 1];
+                pn = poly::ScanJob{};
+                sd = poly::ScanJob{};
+                pn.in = lv(G_TMP, l, 0); pn.out = lv(G_TMP, l, 2); pn.n = n; pn.reverse = false; pn.inclusive = false;
+                sd.in = lv(G_TMP, l, 1); sd.out = lv(G_R, l); sd.n = n; sd.reverse = true; sd.inclusive = true; sd.d_total = lslot(l, 0);
+            }
+            RC(poly::z_terms_lanes(lane_tab, za.data(), L, host::fr_root_of_unity(log2n), fa.data(), fb.data(), st));
+            RC(poly::scan_lanes(0, sj.data(), 2 * L, lane_tab, lane_scratch, st));
+            RC(read_lane_slots(L));
+            std::vector<poly::Mul2cArgs> ma((size_t)L);
+            for (int l = 0; l < L; l++) {
+                ma[l] = poly::Mul2cArgs{};
+                ma[l].out = (uint32_t*)lv(G_Z, l);
+                ma[l].a = (const uint32_t*)lv(G_TMP, l, 2);
+                ma[l].b = (const uint32_t*)lv(G_R, l);
+                ma[l].n = (uint32_t)n;
+                fc[l] = host::fr_inv(host_slot(l, 0));
+            }
+            RC(poly::mul2c_lanes(lane_tab, ma.data(), L, fc.data(), st));
+            RC(bbgpu_ntt_device_batch(lv(G_Z, 0), n, n, L, BBGPU_IFFT, nullptr, st));
+        }
+        {
+            PendingMany P;
+            for (int l = 0; l < L; l++) P.scalars.push_back(lv(G_Z, l));
+            RC(commit_many_begin(P));
+            // beside the commitment: the permutation polynomials need beta and gamma only (prover.cpp:245-247, :253-276).  beta sigma_i comes from the
+            // circuit's unscaled coefficient form, scaled per lane; the 4n transform is the plain kind, shared by all lanes
+            std::vector<poly::CopyPadArgs> cp((size_t)3 * L);
+            std::vector<poly::SigmaPrepArgs> sp((size_t)3 * L);
+            for (int l = 0; l < L; l++)
+                for (int k = 0; k < 3; k++) {
+                    const size_t i = (size_t)l * 3 + k;
+                    cp[i] = poly::CopyPadArgs{};
+                    cp[i].dst = (uint32_t*)lv(G_SIGMA, l, k);
+                    cp[i].src = (const uint32_t*)(sigma_coeff + (size_t)k * n * 4);
+                    cp[i].n_src = cp[i].n_dst = (uint32_t)n;
+                    sp[i] = poly::SigmaPrepArgs{};
+                    sp[i].dst = (uint32_t*)(lv(G_SFFT, l) + (size_t)k * n4 * 4);
+                    sp[i].sigma = (const uint32_t*)lv(G_SIGMA, l, k);
+                    sp[i].w = (const uint32_t*)lv(G_W, l, k);
+                    sp[i].n = (uint32_t)n;
+                    sp[i].n_dst = (uint32_t)n4;
+                    fa[i] = lanes[l].ch.beta;
+                    fb[i] = lanes[l].ch.gamma;
+                }
+            RC(poly::copy_pad_lanes(lane_tab, cp.data(), 3 * L, fa.data(), st));
+            RC(poly::sigma_prepare_lanes(lane_tab, sp.data(), 3 * L, fb.data(), st));
+            RC(bbgpu_ntt_device_batch(lv(G_SFFT, 0), n4, n4, 3 * L, BBGPU_COSET_FFT, nullptr, st));
+            RC(commit_many_end(P, out));
+        }
+        for (int l = 0; l < L; l++) {
+            memcpy(lanes[l].proof.Z_1, out[l], 64);
+            lanes[l].ch.alpha = challenge(transcript_of(lanes[l].proof, 1)); // compute_alpha, challenge.hpp:87-98
+        }
+
+        // ---- round 3: the quotient (compute_quotient_numerators, compute_quotient_polynomial, compute_quotient_commitment)
+        {
+            std::vector<poly::CopyPadArgs> cp((size_t)L);
+            std::vector<poly::QuotLargeArgs> la((size_t)L);
+            std::vector<poly::QuotMidArgs> mi((size_t)L);
+            std::vector<Fr> alpha((size_t)L), abase((size_t)L), a5((size_t)L), a6((size_t)L), a7((size_t)L), beta((size_t)L), gamma((size_t)L);
+            for (int l = 0; l < L; l++) {
+                const uint64_t* wf = lv(G_WFFT, l);
+                const uint64_t* sf = lv(G_SFFT, l);
+                alpha[l] = lanes[l].ch.alpha;
+                beta[l] = lanes[l].ch.beta;
+                gamma[l] = lanes[l].ch.gamma;
+                abase[l] = host::fr_sqr(host::fr_sqr(alpha[l])); // :446-451
+                a5[l] = host::fr_mul(abase[l], alpha[l]);
+                a6[l] = host::fr_mul(a5[l], alpha[l]);
+                a7[l] = host::fr_mul(a6[l], alpha[l]);
+                cp[l] = poly::CopyPadArgs{}; // alpha Z, padded (:440, :278: the scaling moved in front of the shared plain transform)
+                cp[l].dst = (uint32_t*)lv(G_ZFFT, l);
+                cp[l].src = (const uint32_t*)lv(G_Z, l);
+                cp[l].n_src = (uint32_t)n;
+                cp[l].n_dst = (uint32_t)n4;
+                poly::QuotLargeArgs& A = la[l];
+                A = poly::QuotLargeArgs{};
+                A.wl_f = (const uint32_t*)wf; A.wr_f = (const uint32_t*)(wf + n4 * 4); A.wo_f = (const uint32_t*)(wf + 2 * n4 * 4);
+                A.s1_f = (const uint32_t*)sf; A.s2_f = (const uint32_t*)(sf + n4 * 4); A.s3_f = (const uint32_t*)(sf + 2 * n4 * 4);
+                A.z_f = (const uint32_t*)lv(G_ZFFT, l);
+                A.q = (uint32_t*)lv(G_QL, l);
+                A.n4 = (uint32_t)n4;
+                poly::QuotMidArgs& M = mi[l];
+                M = poly::QuotMidArgs{};
+                M.z_f = A.z_f;
+                M.wl_f = A.wl_f; M.wr_f = A.wr_f; M.wo_f = A.wo_f;
+                M.l1 = (const uint32_t*)l_1;
+                M.qm_f = (const uint32_t*)q_fft2n[0]; M.ql_f = (const uint32_t*)q_fft2n[1]; M.qr_f = (const uint32_t*)q_fft2n[2];
+                M.qo_f = (const uint32_t*)q_fft2n[3]; M.qc_f = (const uint32_t*)q_fft2n[4];
+                M.q = (uint32_t*)lv(G_QM, l);
+                M.n2 = (uint32_t)n2;
+            }
+            RC(poly::copy_pad_lanes(lane_tab, cp.data(), L, alpha.data(), st));
+            RC(bbgpu_ntt_device_batch(lv(G_ZFFT, 0), n4, n4, L, BBGPU_COSET_FFT, nullptr, st));
+            RC(poly::quotient_large_lanes(lane_tab, la.data(), L, host::fr_root_of_unity(log2n + 2), beta.data(), gamma.data(), st));
+            RC(poly::quotient_mid_lanes(lane_tab, mi.data(), L, alpha.data(), abase.data(), st));
+            if (has_seq) { // sequential_widget.cpp:47-62
+                std::vector<poly::QuotSeqArgs> sq((size_t)L);
+                for (int l = 0; l < L; l++) {
+                    sq[l] = poly::QuotSeqArgs{};
+                    sq[l].wo_f = mi[l].wo_f;
+                    sq[l].qon_f = (const uint32_t*)qs_fft2n;
+                    sq[l].q = mi[l].q;
+                    sq[l].n2 = (uint32_t)n2;
+                }
+                RC(poly::quotient_seq_lanes(lane_tab, sq.data(), L, abase.data(), st));
+            }
+            if (has_bool) {
+                std::vector<poly::QuotBoolArgs> bq((size_t)L);
+                for (int l = 0; l < L; l++) {
+                    bq[l] = poly::QuotBoolArgs{};
+                    bq[l].wl_f = mi[l].wl_f; bq[l].wr_f = mi[l].wr_f; bq[l].wo_f = mi[l].wo_f;
+                    bq[l].qbl_f = (const uint32_t*)qb_fft2n[0]; bq[l].qbr_f = (const uint32_t*)qb_fft2n[1]; bq[l].qbo_f = (const uint32_t*)qb_fft2n[2];
+                    bq[l].q = mi[l].q;
+                    bq[l].n2 = (uint32_t)n2;
+                }
+                RC(poly::quotient_bool_lanes(lane_tab, bq.data(), L, a5.data(), a6.data(), a7.data(), st));
+            }
+            if (has_mimc) {
+                std::vector<poly::QuotMimcArgs> mq((size_t)L);
+                for (int l = 0; l < L; l++) {
+                    mq[l] = poly::QuotMimcArgs{};
+                    mq[l].wl_f = la[l].wl_f; mq[l].wr_f = la[l].wr_f; mq[l].wo_f = la[l].wo_f;
+                    mq[l].qsel_f = (const uint32_t*)qm_fft4n[0]; mq[l].qcoef_f = (const uint32_t*)qm_fft4n[1];
+                    mq[l].q = la[l].q;
+                    mq[l].n4 = (uint32_t)n4;
+                }
+                RC(poly::quotient_mimc_lanes(lane_tab, mq.data(), L, a5.data(), alpha.data(), st));
+            }
+            RC(poly::divide_by_pseudo_vanishing_lanes(lv(G_QM, 0), n2, L, log2n, log2n + 1, st)); // :453
+            RC(poly::divide_by_pseudo_vanishing_lanes(lv(G_QL, 0), n4, L, log2n, log2n + 2, st)); // :454
+            RC(bbgpu_ntt_device_batch(lv(G_QM, 0), n2, n2, L, BBGPU_COSET_IFFT, nullptr, st));      // :457
+            RC(bbgpu_ntt_device_batch(lv(G_QL, 0), n4, n4, L, BBGPU_COSET_IFFT, nullptr, st));      // :458
+            RC(poly::add_inplace_lanes(lv(G_QL, 0), n4, lv(G_QM, 0), n2, n2, L, st));               // :461-463
+        }
+        {
+            PendingMany P;
+            for (int l = 0; l < L; l++)
+                for (int k = 0; k < 3; k++) P.scalars.push_back(lv(G_QL, l) + (size_t)k * n * 4);
+            RC(commit_many_begin(P));
+            RC(commit_many_end(P, out));
+        }
+        for (int l = 0; l < L; l++) {
+            memcpy(lanes[l].proof.T_LO, out[3 * l], 64);
+            memcpy(lanes[l].proof.T_MID, out[3 * l + 1], 64);
+            memcpy(lanes[l].proof.T_HI, out[3 * l + 2], 64);
+            lanes[l].ch.z = challenge(transcript_of(lanes[l].proof, 2)); // compute_evaluation_challenge, challenge.hpp:100-112
+        }
+
+        // ---- round 4: evaluations and the linearisation polynomial (compute_linearisation_coefficients)
+        const int nev = has_mimc ? 9 : has_seq ? 8 : 7;
+        const Fr omega = host::fr_root_of_unity(log2n);
+        std::vector<Fr> zs((size_t)2 * L);
+        {
+            std::vector<poly::EvalJob> ej((size_t)nev * L);
+            std::vector<int> zi((size_t)nev * L);
+            for (int l = 0; l < L; l++) {
+                zs[(size_t)2 * l] = lanes[l].ch.z;
+                zs[(size_t)2 * l + 1] = host::fr_mul(lanes[l].ch.z, omega);
+                const poly::EvalJob jl[9] = { { lv(G_W, l, 0), n, 0, lslot(l, 0) }, { lv(G_W, l, 1), n, 0, lslot(l, 1) }, { lv(G_W, l, 2), n, 0, lslot(l, 2) },
+                                              { lv(G_SIGMA, l, 0), n, 0, lslot(l, 3) }, { lv(G_SIGMA, l, 1), n, 0, lslot(l, 4) }, { lv(G_Z, l), n, 1, lslot(l, 5) },
+                                              { lv(G_QL, l), 3 * n, 0, lslot(l, 6) }, { lv(G_W, l, 2), n, 1, lslot(l, 7) }, { qm_coeff[1], n, 0, lslot(l, 8) } };
+                for (int j = 0; j < nev; j++) {
+                    ej[(size_t)l * nev + j] = jl[j];
+                    zi[(size_t)l * nev + j] = 2 * l + jl[j].zsel;
+                }
+            }
+            RC(poly::evaluate_lanes(ej.data(), zi.data(), nev * L, zs.data(), 2 * L, lane_tab, lane_scratch, st));
+            RC(read_lane_slots(L));
+            std::vector<poly::LinCombArgs> lc((size_t)L);
+            std::vector<Fr> cl((size_t)12 * L);
+            std::vector<poly::EvalJob> rj((size_t)L);
+            std::vector<int> rz((size_t)L);
+            for (int l = 0; l < L; l++) {
+                Fr ev[9];
+                for (int j = 0; j < nev; j++) ev[j] = host_slot(l, j);
+                lanes[l].beta_inv = host::fr_inv(lanes[l].ch.beta);
+                take_evaluations(lanes[l].proof, lanes[l].beta_inv, ev, &lanes[l].t_eval);
+                const uint64_t* pl[12];
+                const int terms = linearisation_terms(lanes[l].proof, lanes[l].ch, lanes[l].beta_inv, lv(G_Z, l), lv(G_SIGMA, l, 2), pl, &cl[(size_t)12 * l]);
+                lc[l] = poly::LinCombArgs{};
+                for (int j = 0; j < terms; j++) lc[l].p[j] = (const uint32_t*)pl[j];
+                lc[l].count = terms;
+                lc[l].out = (uint32_t*)lv(G_R, l);
+                lc[l].n = (uint32_t)n;
+                rj[l] = poly::EvalJob{ lv(G_R, l), n, 0, lslot(l, 9) };
+                rz[l] = 2 * l;
+            }
+            RC(poly::lincomb_lanes(lane_tab, lc.data(), L, cl.data(), st));
+            RC(poly::evaluate_lanes(rj.data(), rz.data(), L, zs.data(), 2 * L, lane_tab, lane_scratch, st)); // :536
+            RC(read_lane_slots(L));
+        }
+
+        // ---- round 5: the opening polynomials (compute_opening_elements)
+        {
+            std::vector<poly::LinCombArgs> oa((size_t)L), ob((size_t)L);
+            std::vector<Fr> ca((size_t)12 * L), cb((size_t)12 * L);
+            std::vector<poly::ScanJob> kj((size_t)2 * L);
+            const int oterms = has_mimc ? 10 : 9;
+            for (int l = 0; l < L; l++) {
+                Lane& X = lanes[l];
+                X.proof.linear_eval = host_slot(l, 9);
+                X.ch.nu = nu_challenge(X.proof, X.t_eval);
+                Fr nu[8];
+                nu[0] = X.ch.nu;
+                for (int i = 1; i < 8; i++) nu[i] = host::fr_mul(nu[i - 1], nu[0]);
+                const Fr& beta_inv = X.beta_inv;
+                const Fr z_pow_n = host::fr_pow(X.ch.z, (uint64_t)n), z_pow_2n = host::fr_pow(X.ch.z, (uint64_t)2 * n);
+                const Fr nu9 = host::fr_mul(nu[7], nu[0]);
+                const uint64_t* ql = lv(G_QL, l);
+                const uint64_t* ps[10] = { ql, ql + n * 4, ql + 2 * n * 4, lv(G_R, l), lv(G_W, l, 0), lv(G_W, l, 1), lv(G_W, l, 2), lv(G_SIGMA, l, 0), lv(G_SIGMA, l, 1),
+                                           qm_coeff[1] };
+                const Fr cs[10] = { host::fr_one(), z_pow_n, z_pow_2n, nu[0], nu[1], nu[2], nu[3], host::fr_mul(nu[4], beta_inv), host::fr_mul(nu[5], beta_inv), nu9 };
+                oa[l] = poly::LinCombArgs{};
+                for (int j = 0; j < oterms; j++) {
+                    oa[l].p[j] = (const uint32_t*)ps[j];
+                    ca[(size_t)12 * l + j] = cs[j];
+                }
+                oa[l].count = oterms;
+                oa[l].out = (uint32_t*)lv(G_TMP, l, 0);
+                oa[l].n = (uint32_t)n;
+                ob[l] = poly::LinCombArgs{};
+                ob[l].p[0] = (const uint32_t*)lv(G_Z, l);
+                ob[l].p[1] = (const uint32_t*)lv(G_W, l, 2);
+                ob[l].count = (has_mimc || has_seq) ? 2 : 1;
+                ob[l].out = (uint32_t*)lv(G_TMP, l, 1);
+                ob[l].n = (uint32_t)n;
+                cb[(size_t)12 * l] = nu[6];
+                cb[(size_t)12 * l + 1] = nu[7];
+                poly::ScanJob &k0 = kj[(size_t)2 * l], &k1 = kj[(size_t)2 * l + 1];
+                k0 = poly::ScanJob{};
+                k1 = poly::ScanJob{};
+                k0.in = lv(G_TMP, l, 0); k0.out = lv(G_TMP, l, 2); k0.n = n; k0.reverse = true; k0.inclusive = false; k0.z = zs[(size_t)2 * l];
+                k1.in = lv(G_TMP, l, 1); k1.out = lv(G_R, l); k1.n = n; k1.reverse = true; k1.inclusive = false; k1.z = zs[(size_t)2 * l + 1];
+            }
+            RC(poly::lincomb_lanes(lane_tab, oa.data(), L, ca.data(), st));
+            RC(poly::lincomb_lanes(lane_tab, ob.data(), L, cb.data(), st)); // nu^7 Z (+ nu^8 w_o)
+            RC(poly::scan_lanes(1, kj.data(), 2 * L, lane_tab, lane_scratch, st));
+            PendingMany P;
+            for (int l = 0; l < L; l++) {
+                P.scalars.push_back(lv(G_TMP, l, 2));
+                P.scalars.push_back(lv(G_R, l));
+            }
+            RC(commit_many_begin(P));
+            RC(commit_many_end(P, out)); // :650-658
+        }
+        for (int l = 0; l < L; l++) {
+            memcpy(lanes[l].proof.PI_Z, out[2 * l], 64);
+            memcpy(lanes[l].proof.PI_Z_OMEGA, out[2 * l + 1], 64);
+            memcpy(proofs_out + (size_t)l * BBGPU_PLONK_PROOF_WORDS, &lanes[l].proof, sizeof(Proof));
+            batch_challenges[l] = lanes[l].ch;
+        }
+        batch_count = L;
+        batch_timing[0] = now_ms() - t0;
+        batch_timing[2] = batch_timing[0] - batch_timing[1];
+        batch_timing[3] = timing[3];
+        return BBGPU_OK;
+    }
 };
+constexpr int PlonkProver::lane_group_vectors[PlonkProver::G_COUNT];
 
 std::mutex g_pmu;
 std::vector<PlonkProver*> g_provers;
+
+// argument checks of the batch entry that need no device: the caller's arrays and the size bound
+int check_batch_args(const PlonkProver* p, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o, const uint64_t* out)
+{
+    if (count < 1 || count > BBGPU_PLONK_MAX_BATCH) {
+        set_error("count %d: a batch holds 1..%d proofs", count, BBGPU_PLONK_MAX_BATCH);
+        return BBGPU_ERR_ARG;
+    }
+    if (!w_l || !w_r || !w_o || !out) {
+        set_error("null array: %s", !w_l ? "w_l" : !w_r ? "w_r" : !w_o ? "w_o" : "proofs_out");
+        return BBGPU_ERR_ARG;
+    }
+    for (int j = 0; j < count; j++)
+        if (!w_l[j] || !w_r[j] || !w_o[j]) {
+            set_error("null entry: %s[%d]", !w_l[j] ? "w_l" : !w_r[j] ? "w_r" : "w_o", j);
+            return BBGPU_ERR_ARG;
+        }
+    if (p && (size_t)count * p->n > ((size_t)1 << 22)) {
+        set_error("count %d x n %zu: a batch holds at most 2^22 gates in all (6 GiB of per-lane state)", count, p->n);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
 
 PlonkProver* get(int h)
 {
@@ -742,6 +1279,7 @@ PlonkProver* get(int h)
 } // namespace
 
 std::mutex& plonk_mutex() { return g_pmu; }
+uint64_t plonk_lane_bytes() { return g_lane_bytes.load(); }
 void plonk_release_all_locked()
 {
     for (auto*& p : g_provers) {
@@ -815,6 +1353,43 @@ int bbgpu_plonk_construct_proof(int prover, uint64_t proof_out[BBGPU_PLONK_PROOF
     int rc = p->construct_proof();
     if (rc) return rc;
     memcpy(proof_out, &p->proof, sizeof(Proof));
+    return BBGPU_OK;
+}
+
+int bbgpu_plonk_construct_proof_batch(int prover, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o,
+                                      uint64_t* proofs_out)
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    // everything that can be refused without a device is refused before one is bound
+    if (int rc = check_batch_args(nullptr, count, w_l, w_r, w_o, proofs_out)) return rc;
+    PlonkProver* p = get(prover);
+    if (!p) return BBGPU_ERR_ARG;
+    if (int rc = check_batch_args(p, count, w_l, w_r, w_o, proofs_out)) return rc;
+    if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
+    const int rc = p->construct_proof_batch(count, w_l, w_r, w_o, proofs_out);
+    if (rc) (void)hipStreamSynchronize(p->st); // nothing of a failed batch is still running when the caller sees the error
+    return rc;
+}
+
+int bbgpu_plonk_batch_challenges(int prover, int lane, uint64_t out[20])
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    PlonkProver* p = get(prover);
+    if (!p || !out) return BBGPU_ERR_ARG;
+    if (lane < 0 || lane >= p->batch_count) {
+        set_error("lane %d: the last batch of this prover had %d", lane, p->batch_count);
+        return BBGPU_ERR_ARG;
+    }
+    memcpy(out, &p->batch_challenges[lane], 160);
+    return BBGPU_OK;
+}
+
+int bbgpu_plonk_last_batch_timing(int prover, double ms_out[4])
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    PlonkProver* p = get(prover);
+    if (!p || !ms_out) return BBGPU_ERR_ARG;
+    for (int i = 0; i < 4; i++) ms_out[i] = p->batch_timing[i];
     return BBGPU_OK;
 }
 

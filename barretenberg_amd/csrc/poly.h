@@ -99,6 +99,64 @@ struct ScanJob {
     uint64_t* d_total;  // optional 32-byte device slot
 };
 
+// ---- lane-batched forms (a batch of proofs of one circuit, plonk.hip) ------------------------------------------------------------------------------
+// One launch serves every lane: blockIdx.y selects a RECORD of a device table -- the argument struct the single-lane kernel takes by value (16 lanes of
+// ZTermsArgs would not fit the kernel-argument space), holding the lane's vectors and its challenge-dependent constants.  The host writes the records
+// into pinned memory and the table crosses with one copy in front of the launch; every workgroup reads one record, uniformly.
+struct LaneTable {
+    uint8_t *d = nullptr, *h = nullptr; // device table and its pinned mirror
+    size_t cap = 0, used = 0, flushed = 0;
+    int init(size_t bytes);
+    void release();
+    void reset() { used = flushed = 0; } // start of a batch: regions are never rewritten while a copy of them may be in flight
+    int reserve(size_t bytes, void** host, void** dev);
+    template <class T> int push(int count, T** host, const T** dev) { return reserve(sizeof(T) * (size_t)count, (void**)host, (void**)dev); }
+    int flush(hipStream_t st); // everything pushed since the last flush, one copy
+};
+struct Mul2cArgs {
+    uint32_t* out;
+    const uint32_t *a, *b;
+    uint32_t n;
+    Limbs9 c_fix_m261;
+};
+struct SigmaPrepArgs {
+    uint32_t* dst;
+    const uint32_t *sigma, *w;
+    uint32_t n, n_dst;
+    Limbs9 gamma_m256;
+};
+struct CopyPadArgs { // dst[0..n_dst) = c * src[0..n_src) (or src itself), zeros behind
+    uint32_t* dst;
+    const uint32_t* src;
+    uint32_t n_src, n_dst, scaled;
+    Limbs9 c_m261;
+};
+struct EvalTabJob {
+    const uint32_t* c;
+    uint32_t *result, *partial; // 32-byte device slot; this job's 256 block partials
+    uint32_t n, blocks;
+    Limbs9 zT;
+    PowTab T;
+};
+// `lanes` records each; A[l] carries lane l's vectors (and n), the functions fill in the constants
+int z_terms_lanes(LaneTable& T, const ZTermsArgs* A, int lanes, const host::Fr& root, const host::Fr* beta, const host::Fr* gamma, hipStream_t st);
+int quotient_large_lanes(LaneTable& T, const QuotLargeArgs* A, int lanes, const host::Fr& root4n, const host::Fr* beta, const host::Fr* gamma, hipStream_t st);
+int quotient_mid_lanes(LaneTable& T, const QuotMidArgs* A, int lanes, const host::Fr* alpha, const host::Fr* alpha_base, hipStream_t st);
+int quotient_mimc_lanes(LaneTable& T, const QuotMimcArgs* A, int lanes, const host::Fr* alpha_base, const host::Fr* alpha_step, hipStream_t st);
+int quotient_bool_lanes(LaneTable& T, const QuotBoolArgs* A, int lanes, const host::Fr* c_left, const host::Fr* c_right, const host::Fr* c_out, hipStream_t st);
+int quotient_seq_lanes(LaneTable& T, const QuotSeqArgs* A, int lanes, const host::Fr* c, hipStream_t st);
+int lincomb_lanes(LaneTable& T, const LinCombArgs* A, int lanes, const host::Fr* coeffs /* lanes x 12 */, hipStream_t st);
+int mul2c_lanes(LaneTable& T, const Mul2cArgs* A, int lanes, const host::Fr* c, hipStream_t st);
+int sigma_prepare_lanes(LaneTable& T, const SigmaPrepArgs* A, int records, const host::Fr* gamma /* per record */, hipStream_t st);
+int copy_pad_lanes(LaneTable& T, const CopyPadArgs* A, int records, const host::Fr* c /* per record; null: plain copy */, hipStream_t st);
+// the same vector of every lane at base + lane * stride (elements), no per-lane constant
+int add_inplace_lanes(uint64_t* d_a, size_t stride_a, const uint64_t* d_b, size_t stride_b, size_t n, int lanes, hipStream_t st);
+int divide_by_pseudo_vanishing_lanes(uint64_t* d_coeffs, size_t stride, int lanes, int log2n, int log2N, hipStream_t st);
+// `count` scans of one mode and one length (<= 2^22) in shared launches; jobs[j].d_total, where given, receives the total directly
+int scan_lanes(int mode, const ScanJob* jobs, int count, LaneTable& T, Scratch& S, hipStream_t st);
+// `count` evaluations, job j at z[zidx[j]]
+int evaluate_lanes(const EvalJob* jobs, const int* zidx, int count, const host::Fr* z, int nz, LaneTable& T, Scratch& S, hipStream_t st);
+
 PowTab make_powtab(const host::Fr& base);
 // up to two scans of the same kind in shared launches: mode 0 = running products, mode 1 = Horner suffix sums
 int scan_pair(int mode, const ScanJob* jobs, int count, Scratch& S, hipStream_t st);

@@ -74,7 +74,17 @@ template <int L, int V> __device__ __forceinline__ void stv(uint32_t* __restrict
     q[0] = make_uint4(w[0], w[1], w[2], w[3]);
     q[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
-__device__ __forceinline__ FrC cst(const Limbs9& c) { return fe_from<Fr>(c.d); }
+// U: the constant is a field of a record in a device table (the lane-batched kernels below), written by the host before the launch and by nobody
+// during it, and every lane of the workgroup reads the same record: it is read as constant memory, i.e. through the scalar cache into scalar
+// registers, where a by-value kernel argument would have been.  Only for fields of such records: never for a local.
+template <bool U = false> __device__ __forceinline__ FrC cst(const Limbs9& c)
+{
+    if (!U) return fe_from<Fr>(c.d);
+    FrC r;
+#pragma unroll
+    for (int i = 0; i < NL; i++) r.d[i] = ((const __attribute__((address_space(4))) uint32_t*)c.d)[i];
+    return r;
+}
 __device__ __forceinline__ FrC fix2() { return fe_from<Fr>(Fr::M256_TO_M261); }
 __device__ __forceinline__ FrC fix3() { return fe_from<Fr>(Fr::FIX3); }
 __device__ __forceinline__ FrC fix4() { return fe_from<Fr>(Fr::FIX4); }
@@ -91,11 +101,11 @@ template <class F, int L, int V> __device__ __forceinline__ Fe<F, 1, 2> tight2(c
 using FrH = Fe<Fr, 2, 8>; // loop-carried Horner accumulator: (product) + (loaded value), fed straight into the next multiply
 
 // start * base^e, start in either form (the result keeps it); T.p[j] = base^(2^j) in the 2^261 form
-__device__ __forceinline__ FrM pow_tab(const PowTab& T, uint32_t e, const Limbs9& start)
+template <bool U = false> __device__ __forceinline__ FrM pow_tab(const PowTab& T, uint32_t e, const Limbs9& start)
 {
-    FrM acc = mul(cst(start), fe_from<Fr>(Fr::ONE));
+    FrM acc = mul(cst(start), fe_from<Fr>(Fr::ONE)); // (plain read: `start` may be a local of the caller, not a table field)
     for (int j = 0; e; j++, e >>= 1)
-        if (e & 1) acc = mul(acc, cst(T.p[j]));
+        if (e & 1) acc = mul(acc, cst<U>(T.p[j]));
     return acc;
 }
 
@@ -173,7 +183,7 @@ struct ScanArgs {
 
 // LDS doubling scan over the SCAN_T thread partials of a block.  v = this thread's inclusive partial on entry; returns the
 // exclusive partial (combination of all LATER threads for suffix scans / EARLIER threads for prefix scans).
-template <int MODE, int ZB = 0> __device__ __forceinline__ FrM block_scan(FrM v, uint32_t* sh, bool towards_high, const ScanArgs& A, FrM* total)
+template <int MODE, int ZB = 0, bool U = false> __device__ __forceinline__ FrM block_scan(FrM v, uint32_t* sh, bool towards_high, const ScanArgs& A, FrM* total)
 {
     // position p runs in scan order: p = 0 is the first element combined
     const uint32_t t = threadIdx.x;
@@ -195,7 +205,7 @@ template <int MODE, int ZB = 0> __device__ __forceinline__ FrM block_scan(FrM v,
                 // suffix Horner: scan order runs from the highest index down; position p holds S over `off` earlier
                 // positions: S_new = S_here + z^(RUN * off) * S_earlier ... earlier positions are HIGHER indices, so
                 // S(i..) = S_here + z^(len_here) * S_later with len_here = RUN * off thread-runs combined so far
-                v = tight2<Fr>(add(v, mul(o, cst(A.zpow[ZB + j]))));
+                v = tight2<Fr>(add(v, mul(o, cst<U>(A.zpow[ZB + j]))));
             }
         }
         __syncthreads();
@@ -237,10 +247,8 @@ template <int MODE> __device__ __forceinline__ FrV ld_or_id(const uint32_t* p, u
 
 // phase 1: per-thread run totals, block scan of them -> tpart (exclusive within the block), bpart (block total)
 // (two independent scans per launch: blockIdx.y selects the argument block; the second may be empty, n = 0)
-template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase1(ScanArgs A0, ScanArgs A1)
+template <int MODE, bool U> __device__ __forceinline__ void scan_phase1_body(const ScanArgs& A, uint32_t* sh)
 {
-    __shared__ uint32_t sh[NL * SCAN_T];
-    const ScanArgs& A = blockIdx.y ? A1 : A0;
     if (blockIdx.x * SCAN_BLOCK >= A.n) return; // whole workgroup: the two scans may differ in length
     const uint32_t t = threadIdx.x, b = blockIdx.x;
     const uint32_t base = b * SCAN_BLOCK + t * RUN;
@@ -253,24 +261,33 @@ template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase1(Scan
         for (int k = 1; k < RUN; k++) run = mulv(run, ld_or_id<0>(A.in, base + k, A.n));
     } else {
         // E = sum_k x_{base+k} z^k, Horner from the top
-        const FrC z = cst(A.zpow[8]);
+        const FrC z = cst<U>(A.zpow[8]);
         FrH h = ld_or_id<1>(A.in, base + RUN - 1, A.n);
 #pragma unroll
         for (int k = RUN - 2; k >= 0; k--) h = add(mul(h, z), ld_or_id<1>(A.in, base + k, A.n));
         run = tight2<Fr>(h);
     }
     FrM total;
-    FrM ex = block_scan<MODE>(run, sh, !suffix, A, &total);
+    FrM ex = block_scan<MODE, 0, U>(run, sh, !suffix, A, &total);
     const uint32_t tid = b * SCAN_T + t;
     if ((size_t)tid * RUN < A.n) stv(A.tpart, tid, ex);
     if (t == 0) stv(A.bpart, b, total);
 }
-
-// phase 3: out_i from the block carry, the thread partial and the in-run elements
-template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase3(ScanArgs A0, ScanArgs A1)
+template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase1(ScanArgs A0, ScanArgs A1)
 {
     __shared__ uint32_t sh[NL * SCAN_T];
-    const ScanArgs& A = blockIdx.y ? A1 : A0;
+    scan_phase1_body<MODE, false>(blockIdx.y ? A1 : A0, sh);
+}
+// the same over a device table of jobs (blockIdx.y = job): the lanes of a proof batch, two scans each
+template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase1_tab(const ScanArgs* __restrict__ tab)
+{
+    __shared__ uint32_t sh[NL * SCAN_T];
+    scan_phase1_body<MODE, true>(tab[blockIdx.y], sh);
+}
+
+// phase 3: out_i from the block carry, the thread partial and the in-run elements
+template <int MODE, bool U> __device__ __forceinline__ void scan_phase3_body(const ScanArgs& A, uint32_t* sh)
+{
     const uint32_t t = threadIdx.x, b = blockIdx.x;
     if (b * SCAN_BLOCK >= A.n) return; // whole workgroup: the two scans may differ in length
     const bool suffix = (MODE == 1) || A.reverse;
@@ -286,7 +303,7 @@ template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase3(Scan
             v = tight2<Fr>(h);
         }
         FrM total;
-        const FrM ex = block_scan<MODE, 12>(v, sh, !suffix, A, &total);
+        const FrM ex = block_scan<MODE, 12, U>(v, sh, !suffix, A, &total);
         if (t == b) {
 #pragma unroll
             for (int k = 0; k < NL; k++) sh[k] = ex.d[k];
@@ -332,11 +349,11 @@ template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase3(Scan
         const uint32_t after = SCAN_T - 1 - t;
         FrM zp = mul(fe_from<Fr>(Fr::ONE), fe_from<Fr>(Fr::ONE)); // one in the 2^261 form
         for (int j = 0; j < 8; j++)
-            if ((after >> j) & 1) zp = mul(zp, cst(A.zpow[j]));
+            if ((after >> j) & 1) zp = mul(zp, cst<U>(A.zpow[j]));
         FrH acc = ldv(A.tpart, tid);
         if (A.fused_nb) acc = add(mul(carry, zp), ldv(A.tpart, tid));
         else if (A.has_carry) acc = add(mul(ldv(A.bcarry, b), zp), ldv(A.tpart, tid));
-        const FrC z = cst(A.zpow[8]);
+        const FrC z = cst<U>(A.zpow[8]);
         for (int k = RUN - 1; k >= 0; k--) {
             if (base + k >= A.n) continue; // padded zeros do not change acc
             const FrV x = ldv(A.in, base + k);
@@ -349,6 +366,16 @@ template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase3(Scan
             }
         }
     }
+}
+template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase3(ScanArgs A0, ScanArgs A1)
+{
+    __shared__ uint32_t sh[NL * SCAN_T];
+    scan_phase3_body<MODE, false>(blockIdx.y ? A1 : A0, sh);
+}
+template <int MODE> __global__ void __launch_bounds__(SCAN_T, MODE == 0 ? 7 : 8) k_scan_phase3_tab(const ScanArgs* __restrict__ tab)
+{
+    __shared__ uint32_t sh[NL * SCAN_T];
+    scan_phase3_body<MODE, true>(tab[blockIdx.y], sh);
 }
 
 // ---- evaluate: sum_i c_i z^i ------------------------------------------------------------------------------------------
@@ -425,25 +452,22 @@ __global__ void __launch_bounds__(PT) k_sum_small(const uint32_t* __restrict__ p
 }
 
 // several evaluations in one pair of launches (blockIdx.y = job): the prover's seven openings at z / z w (prover.cpp:478-512)
-__global__ void __launch_bounds__(PT) k_eval_partial_batch(EvalBatchArgs A)
+template <bool U>
+__device__ __forceinline__ void eval_partial_body(const uint32_t* __restrict__ c, uint32_t n, uint32_t nblocks, const PowTab& T, const Limbs9& zT_m261,
+                                                  uint32_t* __restrict__ partial, uint32_t* sh)
 {
-    __shared__ uint32_t sh[NL * PT];
-    const uint32_t job = blockIdx.y;
-    const uint32_t n = A.n[job], nblocks = A.blocks[job];
     if (blockIdx.x >= nblocks) return;
-    const uint32_t* __restrict__ c = A.c[job];
-    const PowTab& T = A.T[A.zsel[job]];
     const uint32_t nt = nblocks * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     FrM acc = mul(fe_zero<Fr>(), fe_from<Fr>(Fr::ONE));
     if (t < n) {
         const uint32_t cnt = (n - t + nt - 1) / nt;
-        const FrC zT = cst(A.zT[job]);
+        const FrC zT = cst<U>(zT_m261);
         FrH h = ldv(c, t + (size_t)(cnt - 1) * nt);
         for (uint32_t k = cnt - 1; k-- > 0;) h = add(mul(h, zT), ldv(c, t + (size_t)k * nt));
         Limbs9 one261;
 #pragma unroll
         for (int k = 0; k < NL; k++) one261.d[k] = Fr::ONE[k];
-        acc = mul(h, pow_tab(T, t, one261)); // * z^t
+        acc = mul(h, pow_tab<U>(T, t, one261)); // * z^t
     }
 #pragma unroll
     for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = acc.d[k];
@@ -466,14 +490,24 @@ __global__ void __launch_bounds__(PT) k_eval_partial_batch(EvalBatchArgs A)
         FrM sm;
 #pragma unroll
         for (int k = 0; k < NL; k++) sm.d[k] = sh[k * PT];
-        stv(A.partial, (size_t)job * 256 + blockIdx.x, sm);
+        stv(partial, blockIdx.x, sm);
     }
 }
-__global__ void __launch_bounds__(PT) k_sum_small_batch(EvalBatchArgs A)
+__global__ void __launch_bounds__(PT) k_eval_partial_batch(EvalBatchArgs A)
 {
     __shared__ uint32_t sh[NL * PT];
-    const uint32_t job = blockIdx.x, count = A.blocks[job];
-    const uint32_t* partial = A.partial + (size_t)job * 256 * 8;
+    const uint32_t job = blockIdx.y;
+    eval_partial_body<false>(A.c[job], A.n[job], A.blocks[job], A.T[A.zsel[job]], A.zT[job], A.partial + (size_t)job * 256 * 8, sh);
+}
+// any number of evaluations, each at a point of its own, from a device table of jobs (blockIdx.y = job): the openings of every lane of a proof batch
+__global__ void __launch_bounds__(PT) k_eval_partial_tab(const EvalTabJob* __restrict__ tab)
+{
+    __shared__ uint32_t sh[NL * PT];
+    const EvalTabJob& J = tab[blockIdx.y];
+    eval_partial_body<true>(J.c, J.n, J.blocks, J.T, J.zT, J.partial, sh);
+}
+__device__ __forceinline__ void sum_small_body(const uint32_t* __restrict__ partial, uint32_t count, uint32_t* __restrict__ result, uint32_t* sh)
+{
     FrM acc = mul(fe_zero<Fr>(), fe_from<Fr>(Fr::ONE));
     for (uint32_t i = threadIdx.x; i < count; i += PT) acc = tight2<Fr>(add(acc, ldv(partial, i)));
 #pragma unroll
@@ -497,8 +531,20 @@ __global__ void __launch_bounds__(PT) k_sum_small_batch(EvalBatchArgs A)
         FrM sm;
 #pragma unroll
         for (int k = 0; k < NL; k++) sm.d[k] = sh[k * PT];
-        stv(A.result[job], 0, sm);
+        stv(result, 0, sm);
     }
+}
+__global__ void __launch_bounds__(PT) k_sum_small_batch(EvalBatchArgs A)
+{
+    __shared__ uint32_t sh[NL * PT];
+    const uint32_t job = blockIdx.x;
+    sum_small_body(A.partial + (size_t)job * 256 * 8, A.blocks[job], A.result[job], sh);
+}
+__global__ void __launch_bounds__(PT) k_sum_small_tab(const EvalTabJob* __restrict__ tab)
+{
+    __shared__ uint32_t sh[NL * PT];
+    const EvalTabJob& J = tab[blockIdx.x];
+    sum_small_body(J.partial, J.blocks, J.result, sh);
 }
 
 // ---- prover round kernels -------------------------------------------------------------------------------------------
@@ -521,16 +567,16 @@ __global__ void __launch_bounds__(PT) k_sigma_from_mapping(uint32_t* __restrict_
 // prover.cpp:148-187: numerator / denominator factors of the grand product, three wires multiplied together
 //   num_i = (w_l + beta w^i + gamma)(w_r + beta k1 w^i + gamma)(w_o + beta k2 w^i + gamma)
 //   den_i = (w_l + beta sigma_1 + gamma)(w_r + beta sigma_2 + gamma)(w_o + beta sigma_3 + gamma)
-__global__ void __launch_bounds__(PT) k_z_terms(ZTermsArgs A)
+template <bool U> __device__ __forceinline__ void z_terms_body(const ZTermsArgs& A)
 {
     const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= A.n) return;
     Limbs9 one261;
 #pragma unroll
     for (int k = 0; k < NL; k++) one261.d[k] = Fr::ONE[k];
-    FrM x = pow_tab(A.root, t, one261); // w^t, 2^261 form
-    const FrC step = cst(A.step_m261), beta = cst(A.beta_m256), bk1 = cst(A.beta_k1_m256), bk2 = cst(A.beta_k2_m256), gamma = cst(A.gamma_m256),
-              beta261 = cst(A.beta_m261);
+    FrM x = pow_tab<U>(A.root, t, one261); // w^t, 2^261 form
+    const FrC step = cst<U>(A.step_m261), beta = cst<U>(A.beta_m256), bk1 = cst<U>(A.beta_k1_m256), bk2 = cst<U>(A.beta_k2_m256), gamma = cst<U>(A.gamma_m256),
+              beta261 = cst<U>(A.beta_m261);
     for (uint32_t i = t; i < A.n; i += nt) {
         const FrV wl = ldv(A.w_l, i), wr = ldv(A.w_r, i), wo = ldv(A.w_o, i);
         auto a0 = add(add(mul(x, beta), gamma), wl);
@@ -544,6 +590,8 @@ __global__ void __launch_bounds__(PT) k_z_terms(ZTermsArgs A)
         x = mul(x, step);
     }
 }
+__global__ void __launch_bounds__(PT) k_z_terms(ZTermsArgs A) { z_terms_body<false>(A); }
+__global__ void __launch_bounds__(PT) k_z_terms_lanes(const ZTermsArgs* __restrict__ tab) { z_terms_body<true>(tab[blockIdx.y]); } // one table record per lane
 
 // prover.cpp:253-269: dst (4n) = beta sigma(X) + w(X) + gamma in coefficient form, zero-padded
 __global__ void __launch_bounds__(PT) k_sigma_prepare(uint32_t* __restrict__ dst, const uint32_t* __restrict__ sigma, const uint32_t* __restrict__ w,
@@ -565,12 +613,12 @@ __global__ void __launch_bounds__(PT) k_sigma_prepare(uint32_t* __restrict__ dst
 // prover.cpp:294-299 and :310-341 fused: the degree-3n part of the quotient numerator on the 4n coset
 //   q[i] = (w_l + beta x + gamma)(w_r + beta k1 x + gamma)(w_o + beta k2 x + gamma) zf[i]  -  s1 s2 s3 zf[i + 4],   x = g w_4n^i
 // (zf = alpha * Z on the coset, index i + 4 wraps: prover.cpp:286-289 appends the first four values instead)
-__global__ void __launch_bounds__(PT) k_quotient_large(QuotLargeArgs A)
+template <bool U> __device__ __forceinline__ void quotient_large_body(const QuotLargeArgs& A)
 {
     const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= A.n4) return;
-    FrM x = pow_tab(A.root, t, A.g_m261);
-    const FrC step = cst(A.step_m261), beta = cst(A.beta_m256), bk1 = cst(A.beta_k1_m256), bk2 = cst(A.beta_k2_m256), gamma = cst(A.gamma_m256);
+    FrM x = pow_tab<U>(A.root, t, A.g_m261);
+    const FrC step = cst<U>(A.step_m261), beta = cst<U>(A.beta_m256), bk1 = cst<U>(A.beta_k1_m256), bk2 = cst<U>(A.beta_k2_m256), gamma = cst<U>(A.gamma_m256);
     for (uint32_t i = t; i < A.n4; i += nt) {
         auto t0 = add(add(mul(x, beta), gamma), ldv(A.wl_f, i));
         auto t1 = add(add(mul(x, bk1), gamma), ldv(A.wr_f, i));
@@ -581,32 +629,37 @@ __global__ void __launch_bounds__(PT) k_quotient_large(QuotLargeArgs A)
         x = mul(x, step);
     }
 }
+__global__ void __launch_bounds__(PT) k_quotient_large(QuotLargeArgs A) { quotient_large_body<false>(A); }
+__global__ void __launch_bounds__(PT) k_quotient_large_lanes(const QuotLargeArgs* __restrict__ tab) { quotient_large_body<true>(tab[blockIdx.y]); } // one table record per lane
 
 // prover.cpp:360-402 and arithmetic_widget.cpp:86-101 fused: the degree-2n part on the 2n coset
 //   q[i] = (zf[2i+4] - alpha) alpha l1[i+4] + (zf[2i] - alpha) alpha^2 l1[i]
 //        + abase (qm wl wr + ql wl + qr wr + qo wo + qc),  wires at index 2i of their 4n transforms
-__global__ void __launch_bounds__(PT) k_quotient_mid(QuotMidArgs A)
+template <bool U> __device__ __forceinline__ void quotient_mid_body(const QuotMidArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n2) return;
     const uint32_t m4 = 2 * A.n2 - 1, m2 = A.n2 - 1;
-    const FrC alpha = cst(A.alpha_m256);
-    auto t6 = mul(mul(sub(ldv(A.z_f, (2 * i + 4) & m4), alpha), ldv(A.l1, (i + 4) & m2)), cst(A.alpha_fix_m261));   // * alpha * 2^5
-    auto t4 = mul(mul(sub(ldv(A.z_f, 2 * i), alpha), ldv(A.l1, i)), cst(A.alpha2_fix_m261));                          // * alpha^2 * 2^5
+    const FrC alpha = cst<U>(A.alpha_m256);
+    auto t6 = mul(mul(sub(ldv(A.z_f, (2 * i + 4) & m4), alpha), ldv(A.l1, (i + 4) & m2)), cst<U>(A.alpha_fix_m261));   // * alpha * 2^5
+    auto t4 = mul(mul(sub(ldv(A.z_f, 2 * i), alpha), ldv(A.l1, i)), cst<U>(A.alpha2_fix_m261));                          // * alpha^2 * 2^5
     const FrV wl = ldv(A.wl_f, 2 * i), wr = ldv(A.wr_f, 2 * i), wo = ldv(A.wo_f, 2 * i);
     // selector transforms are stored unscaled; abase carries the fix factors: three-operand term needs 2^10, two-operand 2^5
-    auto g3 = mul(mul(mul(ldv(A.qm_f, i), wl), wr), cst(A.abase_fix3_m261));
+    auto g3 = mul(mul(mul(ldv(A.qm_f, i), wl), wr), cst<U>(A.abase_fix3_m261));
     auto gl = mul(ldv(A.ql_f, i), wl);
     auto gr = mul(ldv(A.qr_f, i), wr);
     auto go = mul(ldv(A.qo_f, i), wo);
-    auto g2 = mul(add(add(gl, gr), go), cst(A.abase_fix2_m261));
-    auto gc = mul(ldv(A.qc_f, i), cst(A.abase_m261));
+    auto g2 = mul(add(add(gl, gr), go), cst<U>(A.abase_fix2_m261));
+    auto gc = mul(ldv(A.qc_f, i), cst<U>(A.abase_m261));
     stv(A.q, i, add(add(add(t6, t4), add(g3, g2)), gc));
 }
+__global__ void __launch_bounds__(PT) k_quotient_mid(QuotMidArgs A) { quotient_mid_body<false>(A); }
+// (second bound = waves per SIMD: the record-fed form is held to the registers of the by-value kernel)
+__global__ void __launch_bounds__(PT, 6) k_quotient_mid_lanes(const QuotMidArgs* __restrict__ tab) { quotient_mid_body<true>(tab[blockIdx.y]); } // one table record per lane
 
 // mimc_widget.cpp:58-90 on the 4n coset: with T0 = w_o + w_l + q_coef,
 //   q[i] += abase q_sel [ (T0^3 - w_r) + alpha (w_r^2 T0 - w_o[i + 4]) ]        (w_o[i + 4] = the next gate's output wire)
-__global__ void __launch_bounds__(PT) k_quotient_mimc(QuotMimcArgs A)
+template <bool U> __device__ __forceinline__ void quotient_mimc_body(const QuotMimcArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n4) return;
@@ -614,32 +667,38 @@ __global__ void __launch_bounds__(PT) k_quotient_mimc(QuotMimcArgs A)
     const auto t0 = weak(add(add(wo, wl), ldv(A.qcoef_f, i)));
     const auto t0sq = mulv(t0, t0);
     const auto t1 = weak(sub(mulv(t0sq, t0), wr));
-    const auto t2 = mul(weak(sub(mulv(mulv(wr, wr), t0), won)), cst(A.alpha_m261));
+    const auto t2 = mul(weak(sub(mulv(mulv(wr, wr), t0), won)), cst<U>(A.alpha_m261));
     const auto sum = weak(add(t1, t2));
-    stv(A.q, i, add(mul(mul(sum, ldv(A.qsel_f, i)), cst(A.abase_fix_m261)), ldv(A.q, i)));
+    stv(A.q, i, add(mul(mul(sum, ldv(A.qsel_f, i)), cst<U>(A.abase_fix_m261)), ldv(A.q, i)));
 }
+__global__ void __launch_bounds__(PT) k_quotient_mimc(QuotMimcArgs A) { quotient_mimc_body<false>(A); }
+__global__ void __launch_bounds__(PT, 8) k_quotient_mimc_lanes(const QuotMimcArgs* __restrict__ tab) { quotient_mimc_body<true>(tab[blockIdx.y]); } // one table record per lane
 
 // sequential_widget.cpp:47-62: q[i] += c q_o_next[i] w_o[2i + 4] on the 2n coset (index 2i + 4 of the 4n evaluations = the next gate's row)
-__global__ void __launch_bounds__(PT) k_quotient_seq(QuotSeqArgs A)
+template <bool U> __device__ __forceinline__ void quotient_seq_body(const QuotSeqArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n2) return;
     const uint32_t m4 = 2 * A.n2 - 1;
-    auto t = mul(mul(ldv(A.qon_f, i), ldv(A.wo_f, (2 * i + 4) & m4)), cst(A.c_fix_m261));
+    auto t = mul(mul(ldv(A.qon_f, i), ldv(A.wo_f, (2 * i + 4) & m4)), cst<U>(A.c_fix_m261));
     stv(A.q, i, add(t, ldv(A.q, i)));
 }
+__global__ void __launch_bounds__(PT) k_quotient_seq(QuotSeqArgs A) { quotient_seq_body<false>(A); }
+__global__ void __launch_bounds__(PT) k_quotient_seq_lanes(const QuotSeqArgs* __restrict__ tab) { quotient_seq_body<true>(tab[blockIdx.y]); } // one table record per lane
 
 // bool_widget.cpp:62-100: q[i] += c_l q_bl (w_l^2 - w_l) + c_r q_br (w_r^2 - w_r) + c_o q_bo (w_o^2 - w_o), wires at index 2i
-__global__ void __launch_bounds__(PT) k_quotient_bool(QuotBoolArgs A)
+template <bool U> __device__ __forceinline__ void quotient_bool_body(const QuotBoolArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n2) return;
     const FrV wl = ldv(A.wl_f, 2 * i), wr = ldv(A.wr_f, 2 * i), wo = ldv(A.wo_f, 2 * i);
-    auto tl = mul(mul(weak(sub(mulv(wl, wl), wl)), ldv(A.qbl_f, i)), cst(A.cl_fix_m261));
-    auto tr = mul(mul(weak(sub(mulv(wr, wr), wr)), ldv(A.qbr_f, i)), cst(A.cr_fix_m261));
-    auto to = mul(mul(weak(sub(mulv(wo, wo), wo)), ldv(A.qbo_f, i)), cst(A.co_fix_m261));
+    auto tl = mul(mul(weak(sub(mulv(wl, wl), wl)), ldv(A.qbl_f, i)), cst<U>(A.cl_fix_m261));
+    auto tr = mul(mul(weak(sub(mulv(wr, wr), wr)), ldv(A.qbr_f, i)), cst<U>(A.cr_fix_m261));
+    auto to = mul(mul(weak(sub(mulv(wo, wo), wo)), ldv(A.qbo_f, i)), cst<U>(A.co_fix_m261));
     stv(A.q, i, add(add(add(tl, tr), to), ldv(A.q, i)));
 }
+__global__ void __launch_bounds__(PT) k_quotient_bool(QuotBoolArgs A) { quotient_bool_body<false>(A); }
+__global__ void __launch_bounds__(PT) k_quotient_bool_lanes(const QuotBoolArgs* __restrict__ tab) { quotient_bool_body<true>(tab[blockIdx.y]); } // one table record per lane
 
 // polynomial_arithmetic.cpp:478-560: c[i] *= (x_i - w_n^-1) / ((x_i)^n - 1),  x_i = g w_N^i;  (x_i)^n - 1 takes k = N/n values
 __global__ void __launch_bounds__(PT) k_divide_vanishing(uint32_t* __restrict__ c, uint32_t N, uint32_t k, PowTab root, Limbs9 g_m261, Limbs9 step_m261,
@@ -683,14 +742,83 @@ __global__ void __launch_bounds__(PT) k_l1_scale(uint32_t* __restrict__ l1, uint
 }
 
 // prover.cpp:520-528 + arithmetic_widget.cpp:106-126: r[i] = sum_j c_j p_j[i] over the seven coefficient-form polynomials
-__global__ void __launch_bounds__(PT) k_lincomb(LinCombArgs A)
+template <bool U> __device__ __forceinline__ void lincomb_body(const LinCombArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
-    FrM acc = mul(ldv(A.p[0], i), cst(A.c[0]));
-    for (int j = 1; j < A.count; j++) acc = tight2<Fr>(add(acc, mul(ldv(A.p[j], i), cst(A.c[j]))));
+    FrM acc = mul(ldv(A.p[0], i), cst<U>(A.c[0]));
+    for (int j = 1; j < A.count; j++) acc = tight2<Fr>(add(acc, mul(ldv(A.p[j], i), cst<U>(A.c[j]))));
     if (A.out_add) acc = tight2<Fr>(add(acc, ldv(A.out_add, i)));
     stv(A.out, i, acc);
+}
+__global__ void __launch_bounds__(PT) k_lincomb(LinCombArgs A) { lincomb_body<false>(A); }
+__global__ void __launch_bounds__(PT) k_lincomb_lanes(const LinCombArgs* __restrict__ tab) { lincomb_body<true>(tab[blockIdx.y]); } // one table record per lane
+
+// ---- lane-batched forms of the small kernels (blockIdx.y = record of a device table, or lane of a strided vector) ------------------------------------
+__global__ void __launch_bounds__(PT) k_mul2c_lanes(const Mul2cArgs* __restrict__ tab)
+{
+    const Mul2cArgs& A = tab[blockIdx.y];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    stv(A.out, i, mul(mul(ldv(A.a, i), ldv(A.b, i)), cst<true>(A.c_fix_m261)));
+}
+__global__ void __launch_bounds__(PT) k_sigma_prepare_lanes(const SigmaPrepArgs* __restrict__ tab)
+{
+    const SigmaPrepArgs& A = tab[blockIdx.y];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n_dst) return;
+    if (i >= A.n) {
+        uint4* q = reinterpret_cast<uint4*>(A.dst + (size_t)i * 8);
+        q[0] = make_uint4(0, 0, 0, 0);
+        q[1] = make_uint4(0, 0, 0, 0);
+        return;
+    }
+    auto v = add(ldv(A.sigma, i), ldv(A.w, i));
+    if (i == 0) stv(A.dst, i, add(v, cst<true>(A.gamma_m256)));
+    else stv(A.dst, i, v);
+}
+// k_copy_pad with an optional per-record multiplier: alpha Z and beta sigma_i are scaled in coefficient form, in front of the lanes' shared plain
+// transform (the *_WITH_CONSTANT kinds take one constant per batched launch; scaling commutes with the transform and every value is exact)
+__global__ void __launch_bounds__(PT) k_copy_pad_lanes(const CopyPadArgs* __restrict__ tab)
+{
+    const CopyPadArgs& A = tab[blockIdx.y];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n_dst) return;
+    uint4* q = reinterpret_cast<uint4*>(A.dst + (size_t)i * 8);
+    if (i >= A.n_src) {
+        q[0] = make_uint4(0, 0, 0, 0);
+        q[1] = make_uint4(0, 0, 0, 0);
+    } else if (A.scaled) {
+        stv(A.dst, i, mul(ldv(A.src, i), cst<true>(A.c_m261)));
+    } else {
+        const uint4* sp = reinterpret_cast<const uint4*>(A.src + (size_t)i * 8);
+        q[0] = sp[0];
+        q[1] = sp[1];
+    }
+}
+__global__ void __launch_bounds__(PT) k_add_inplace_lanes(uint32_t* __restrict__ a, size_t stride_a, const uint32_t* __restrict__ b, size_t stride_b, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    a += (size_t)blockIdx.y * stride_a * 8;
+    b += (size_t)blockIdx.y * stride_b * 8;
+    stv(a, i, add(ldv(a, i), ldv(b, i)));
+}
+__global__ void __launch_bounds__(PT) k_divide_vanishing_lanes(uint32_t* __restrict__ c, size_t stride, uint32_t N, uint32_t k, PowTab root, Limbs9 g_m261,
+                                                             Limbs9 step_m261, Limbs9 wninv_m261, Limbs9 inv0, Limbs9 inv1, Limbs9 inv2, Limbs9 inv3)
+{
+    const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= N) return;
+    c += (size_t)blockIdx.y * stride * 8;
+    FrM x = pow_tab(root, t, g_m261);
+    const FrC step = cst(step_m261), wninv = cst(wninv_m261);
+    const uint32_t sel = t & (k - 1); // nt is a multiple of 4, so i mod k is fixed per thread
+    const FrC iv = cst(sel == 0 ? inv0 : sel == 1 ? inv1 : sel == 2 ? inv2 : inv3);
+    for (uint32_t i = t; i < N; i += nt) {
+        auto num = weak(sub(x, wninv)); // 2^261 form
+        stv(c, i, mul(mul(ldv(c, i), num), iv));
+        x = mul(x, step);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1055,16 +1183,20 @@ int sigma_from_mapping(uint64_t* d_out, const uint32_t* d_mapping, const uint64_
     return BBGPU_OK;
 }
 
-int z_terms(ZTermsArgs A, const host::Fr& root, const host::Fr& beta, const host::Fr& gamma, hipStream_t st)
+static void z_terms_challenges(ZTermsArgs& A, const host::Fr& beta, const host::Fr& gamma)
 {
-    const uint32_t blocks = strided_blocks(A.n);
-    A.root = make_powtab(root);
-    A.step_m261 = host::limbs_m261(host::fr_pow(root, (uint64_t)blocks * PT));
     A.beta_m256 = host::limbs_m256(beta);
     A.beta_m261 = host::limbs_m261(beta);
     A.beta_k1_m256 = host::limbs_m256(host::fr_mul(beta, host::fr_from_limbs(FrHostP::GEN5)));
     A.beta_k2_m256 = host::limbs_m256(host::fr_mul(beta, host::fr_from_limbs(FrHostP::GEN7)));
     A.gamma_m256 = host::limbs_m256(gamma);
+}
+int z_terms(ZTermsArgs A, const host::Fr& root, const host::Fr& beta, const host::Fr& gamma, hipStream_t st)
+{
+    const uint32_t blocks = strided_blocks(A.n);
+    A.root = make_powtab(root);
+    A.step_m261 = host::limbs_m261(host::fr_pow(root, (uint64_t)blocks * PT));
+    z_terms_challenges(A, beta, gamma);
     k_z_terms<<<blocks, PT, 0, st>>>(A);
     HIPCHK(launch_check());
     return BBGPU_OK;
@@ -1078,22 +1210,26 @@ int sigma_prepare(uint64_t* d_dst, const uint64_t* d_sigma, const uint64_t* d_w,
     return BBGPU_OK;
 }
 
+static void quotient_large_challenges(QuotLargeArgs& A, const host::Fr& beta, const host::Fr& gamma)
+{
+    A.beta_m256 = host::limbs_m256(beta);
+    A.beta_k1_m256 = host::limbs_m256(host::fr_mul(beta, host::fr_from_limbs(FrHostP::GEN5)));
+    A.beta_k2_m256 = host::limbs_m256(host::fr_mul(beta, host::fr_from_limbs(FrHostP::GEN7)));
+    A.gamma_m256 = host::limbs_m256(gamma);
+}
 int quotient_large(QuotLargeArgs A, const host::Fr& root4n, const host::Fr& beta, const host::Fr& gamma, hipStream_t st)
 {
     const uint32_t blocks = strided_blocks(A.n4);
     A.root = make_powtab(root4n);
     A.g_m261 = host::limbs_m261(host::fr_from_limbs(FrHostP::GEN5));
     A.step_m261 = host::limbs_m261(host::fr_pow(root4n, (uint64_t)blocks * PT));
-    A.beta_m256 = host::limbs_m256(beta);
-    A.beta_k1_m256 = host::limbs_m256(host::fr_mul(beta, host::fr_from_limbs(FrHostP::GEN5)));
-    A.beta_k2_m256 = host::limbs_m256(host::fr_mul(beta, host::fr_from_limbs(FrHostP::GEN7)));
-    A.gamma_m256 = host::limbs_m256(gamma);
+    quotient_large_challenges(A, beta, gamma);
     k_quotient_large<<<blocks, PT, 0, st>>>(A);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
 
-int quotient_mid(QuotMidArgs A, const host::Fr& alpha, const host::Fr& alpha_base, hipStream_t st)
+static void quotient_mid_challenges(QuotMidArgs& A, const host::Fr& alpha, const host::Fr& alpha_base)
 {
     const host::Fr f2 = host::fr_from_u64(32), f3 = host::fr_from_u64(1024);
     A.alpha_m256 = host::limbs_m256(alpha);
@@ -1102,6 +1238,10 @@ int quotient_mid(QuotMidArgs A, const host::Fr& alpha, const host::Fr& alpha_bas
     A.abase_m261 = host::limbs_m261(alpha_base);
     A.abase_fix2_m261 = host::limbs_m261(host::fr_mul(alpha_base, f2));
     A.abase_fix3_m261 = host::limbs_m261(host::fr_mul(alpha_base, f3));
+}
+int quotient_mid(QuotMidArgs A, const host::Fr& alpha, const host::Fr& alpha_base, hipStream_t st)
+{
+    quotient_mid_challenges(A, alpha, alpha_base);
     k_quotient_mid<<<pw_blocks(A.n2), PT, 0, st>>>(A);
     HIPCHK(launch_check());
     return BBGPU_OK;
@@ -1144,7 +1284,7 @@ static host::Fr coset_gen_pow_n(int log2n)
 }
 
 // divide_by_pseudo_vanishing_polynomial(coeffs, src = 2^log2n, target = 2^log2N), in place on the resident coset evaluations
-int divide_by_pseudo_vanishing(uint64_t* d_coeffs, int log2n, int log2N, hipStream_t st)
+int divide_by_pseudo_vanishing_lanes(uint64_t* d_coeffs, size_t stride, int lanes, int log2n, int log2N, hipStream_t st)
 {
     const int lk = log2N - log2n;
     if (lk < 0 || lk > 2) {
@@ -1167,10 +1307,20 @@ int divide_by_pseudo_vanishing(uint64_t* d_coeffs, int log2n, int log2N, hipStre
     }
     const host::Fr rootN = host::fr_root_of_unity(log2N), wninv = host::fr_inv(host::fr_root_of_unity(log2n));
     const uint32_t blocks = strided_blocks(N);
-    k_divide_vanishing<<<blocks, PT, 0, st>>>((uint32_t*)d_coeffs, (uint32_t)N, k, make_powtab(rootN), host::limbs_m261(host::fr_from_limbs(FrHostP::GEN5)),
-                                             host::limbs_m261(host::fr_pow(rootN, (uint64_t)blocks * PT)), host::limbs_m261(wninv), inv[0], inv[1], inv[2], inv[3]);
+    if (lanes > 0)
+        k_divide_vanishing_lanes<<<dim3(blocks, lanes), PT, 0, st>>>((uint32_t*)d_coeffs, stride, (uint32_t)N, k, make_powtab(rootN),
+                                                                    host::limbs_m261(host::fr_from_limbs(FrHostP::GEN5)),
+                                                                    host::limbs_m261(host::fr_pow(rootN, (uint64_t)blocks * PT)), host::limbs_m261(wninv), inv[0],
+                                                                    inv[1], inv[2], inv[3]);
+    else
+        k_divide_vanishing<<<blocks, PT, 0, st>>>((uint32_t*)d_coeffs, (uint32_t)N, k, make_powtab(rootN), host::limbs_m261(host::fr_from_limbs(FrHostP::GEN5)),
+                                                 host::limbs_m261(host::fr_pow(rootN, (uint64_t)blocks * PT)), host::limbs_m261(wninv), inv[0], inv[1], inv[2], inv[3]);
     HIPCHK(launch_check());
     return BBGPU_OK;
+}
+int divide_by_pseudo_vanishing(uint64_t* d_coeffs, int log2n, int log2N, hipStream_t st)
+{
+    return divide_by_pseudo_vanishing_lanes(d_coeffs, 0, 0, log2n, log2N, st); // lanes = 0: the single-vector kernel
 }
 
 // compute_lagrange_polynomial_fft(l_1, src = 2^log2n, target = 2^log2N): N resident values; d_tmp: N elements of workspace
@@ -1211,6 +1361,275 @@ int lincomb(LinCombArgs A, const host::Fr* coeffs, hipStream_t st)
 {
     for (int j = 0; j < A.count; j++) A.c[j] = host::limbs_m261(coeffs[j]);
     k_lincomb<<<pw_blocks(A.n), PT, 0, st>>>(A);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+
+// ---- lane-batched forms: table plumbing ------------------------------------------------------------------------------------------------------------
+int LaneTable::init(size_t bytes)
+{
+    if (d) return BBGPU_OK;
+    HIPCHK(dev_malloc((void**)&d, bytes));
+    if (hipHostMalloc((void**)&h, bytes) != hipSuccess) {
+        (void)dev_free(d);
+        d = h = nullptr;
+        set_error("pinned lane table of %zu bytes refused", bytes);
+        return BBGPU_ERR_HIP;
+    }
+    cap = bytes;
+    used = flushed = 0;
+    return BBGPU_OK;
+}
+void LaneTable::release()
+{
+    if (d) (void)dev_free(d);
+    if (h) (void)hipHostFree(h);
+    d = h = nullptr;
+    cap = used = flushed = 0;
+}
+int LaneTable::reserve(size_t bytes, void** host, void** dev)
+{
+    const size_t at = (used + 63) & ~(size_t)63;
+    if (!d || at + bytes > cap) {
+        set_error("lane table full (%zu + %zu of %zu bytes)", at, bytes, cap);
+        return BBGPU_ERR_SIZE;
+    }
+    *host = h + at;
+    *dev = d + at;
+    used = at + bytes;
+    return BBGPU_OK;
+}
+int LaneTable::flush(hipStream_t st)
+{
+    if (used == flushed) return BBGPU_OK;
+    HIPCHK(h2d_async(d + flushed, h + flushed, used - flushed, st));
+    flushed = used;
+    return BBGPU_OK;
+}
+// the records of one launch: copied into the pinned table, completed by `fill`, shipped
+template <class T, class F> static int table_records(LaneTable& Tb, const T* A, int count, const T** dev, hipStream_t st, F fill)
+{
+    T* hrec = nullptr;
+    if (int rc = Tb.push(count, &hrec, dev)) return rc;
+    for (int l = 0; l < count; l++) {
+        hrec[l] = A[l];
+        fill(hrec[l], l);
+    }
+    return Tb.flush(st);
+}
+
+int z_terms_lanes(LaneTable& T, const ZTermsArgs* A, int lanes, const host::Fr& root, const host::Fr* beta, const host::Fr* gamma, hipStream_t st)
+{
+    const uint32_t blocks = strided_blocks(A[0].n);
+    const PowTab rt = make_powtab(root);
+    const Limbs9 step = host::limbs_m261(host::fr_pow(root, (uint64_t)blocks * PT));
+    const ZTermsArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st, [&](ZTermsArgs& R, int l) {
+            R.root = rt;
+            R.step_m261 = step;
+            z_terms_challenges(R, beta[l], gamma[l]);
+        }))
+        return rc;
+    k_z_terms_lanes<<<dim3(blocks, lanes), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int quotient_large_lanes(LaneTable& T, const QuotLargeArgs* A, int lanes, const host::Fr& root4n, const host::Fr* beta, const host::Fr* gamma, hipStream_t st)
+{
+    const uint32_t blocks = strided_blocks(A[0].n4);
+    const PowTab rt = make_powtab(root4n);
+    const Limbs9 step = host::limbs_m261(host::fr_pow(root4n, (uint64_t)blocks * PT)), g = host::limbs_m261(host::fr_from_limbs(FrHostP::GEN5));
+    const QuotLargeArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st, [&](QuotLargeArgs& R, int l) {
+            R.root = rt;
+            R.g_m261 = g;
+            R.step_m261 = step;
+            quotient_large_challenges(R, beta[l], gamma[l]);
+        }))
+        return rc;
+    k_quotient_large_lanes<<<dim3(blocks, lanes), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int quotient_mid_lanes(LaneTable& T, const QuotMidArgs* A, int lanes, const host::Fr* alpha, const host::Fr* alpha_base, hipStream_t st)
+{
+    const QuotMidArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st, [&](QuotMidArgs& R, int l) { quotient_mid_challenges(R, alpha[l], alpha_base[l]); })) return rc;
+    k_quotient_mid_lanes<<<dim3(pw_blocks(A[0].n2), lanes), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int quotient_mimc_lanes(LaneTable& T, const QuotMimcArgs* A, int lanes, const host::Fr* alpha_base, const host::Fr* alpha_step, hipStream_t st)
+{
+    const QuotMimcArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st, [&](QuotMimcArgs& R, int l) {
+            R.alpha_m261 = host::limbs_m261(alpha_step[l]);
+            R.abase_fix_m261 = host::limbs_m261(host::fr_mul(alpha_base[l], host::fr_from_u64(32)));
+        }))
+        return rc;
+    k_quotient_mimc_lanes<<<dim3(pw_blocks(A[0].n4), lanes), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int quotient_bool_lanes(LaneTable& T, const QuotBoolArgs* A, int lanes, const host::Fr* c_left, const host::Fr* c_right, const host::Fr* c_out, hipStream_t st)
+{
+    const host::Fr f2 = host::fr_from_u64(32);
+    const QuotBoolArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st, [&](QuotBoolArgs& R, int l) {
+            R.cl_fix_m261 = host::limbs_m261(host::fr_mul(c_left[l], f2));
+            R.cr_fix_m261 = host::limbs_m261(host::fr_mul(c_right[l], f2));
+            R.co_fix_m261 = host::limbs_m261(host::fr_mul(c_out[l], f2));
+        }))
+        return rc;
+    k_quotient_bool_lanes<<<dim3(pw_blocks(A[0].n2), lanes), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int quotient_seq_lanes(LaneTable& T, const QuotSeqArgs* A, int lanes, const host::Fr* c, hipStream_t st)
+{
+    const QuotSeqArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st,
+                               [&](QuotSeqArgs& R, int l) { R.c_fix_m261 = host::limbs_m261(host::fr_mul(c[l], host::fr_from_u64(32))); }))
+        return rc;
+    k_quotient_seq_lanes<<<dim3(pw_blocks(A[0].n2), lanes), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int lincomb_lanes(LaneTable& T, const LinCombArgs* A, int lanes, const host::Fr* coeffs, hipStream_t st)
+{
+    const LinCombArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st, [&](LinCombArgs& R, int l) {
+            for (int j = 0; j < R.count; j++) R.c[j] = host::limbs_m261(coeffs[(size_t)l * 12 + j]);
+        }))
+        return rc;
+    k_lincomb_lanes<<<dim3(pw_blocks(A[0].n), lanes), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int mul2c_lanes(LaneTable& T, const Mul2cArgs* A, int lanes, const host::Fr* c, hipStream_t st)
+{
+    const Mul2cArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st,
+                               [&](Mul2cArgs& R, int l) { R.c_fix_m261 = host::limbs_m261(host::fr_mul(c[l], host::fr_from_u64(32))); }))
+        return rc;
+    k_mul2c_lanes<<<dim3(pw_blocks(A[0].n), lanes), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int sigma_prepare_lanes(LaneTable& T, const SigmaPrepArgs* A, int records, const host::Fr* gamma, hipStream_t st)
+{
+    const SigmaPrepArgs* dev = nullptr;
+    if (int rc = table_records(T, A, records, &dev, st, [&](SigmaPrepArgs& R, int l) { R.gamma_m256 = host::limbs_m256(gamma[l]); })) return rc;
+    k_sigma_prepare_lanes<<<dim3(pw_blocks(A[0].n_dst), records), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int copy_pad_lanes(LaneTable& T, const CopyPadArgs* A, int records, const host::Fr* c, hipStream_t st)
+{
+    const CopyPadArgs* dev = nullptr;
+    if (int rc = table_records(T, A, records, &dev, st, [&](CopyPadArgs& R, int l) {
+            R.scaled = c ? 1u : 0u;
+            R.c_m261 = c ? host::limbs_m261(c[l]) : Limbs9{};
+        }))
+        return rc;
+    k_copy_pad_lanes<<<dim3(pw_blocks(A[0].n_dst), records), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int add_inplace_lanes(uint64_t* d_a, size_t stride_a, const uint64_t* d_b, size_t stride_b, size_t n, int lanes, hipStream_t st)
+{
+    k_add_inplace_lanes<<<dim3(pw_blocks(n), lanes), PT, 0, st>>>((uint32_t*)d_a, stride_a, (const uint32_t*)d_b, stride_b, (uint32_t)n);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+
+// scan_pair over a table of jobs: the same phases, grid.y = job.  All jobs have one length, so one grid shape serves them; up to 2^22 elements the scan
+// over the block totals is the fused form (<= SCAN_T blocks) or one workgroup per job.
+int scan_lanes(int mode, const ScanJob* jobs, int count, LaneTable& T, Scratch& S, hipStream_t st)
+{
+    if (count < 1) return BBGPU_ERR_ARG;
+    const size_t n = jobs[0].n, nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    for (int j = 0; j < count; j++)
+        if (jobs[j].n != n || n == 0 || nb > (size_t)SCAN_BLOCK) {
+            set_error("lane-batched scan: one length for all jobs, 1 <= n <= 2^22");
+            return BBGPU_ERR_SIZE;
+        }
+    const size_t per = scan_scratch_bytes(n);
+    if (int rc = S.ensure(per * (size_t)count + 64)) return rc;
+    ScanArgs *A = nullptr, *B = nullptr, *A3 = nullptr;
+    const ScanArgs *dA = nullptr, *dB = nullptr, *dA3 = nullptr;
+    if (int rc = T.push(count, &A, &dA)) return rc;
+    if (int rc = T.push(count, &B, &dB)) return rc;
+    if (int rc = T.push(count, &A3, &dA3)) return rc;
+    const bool fused = nb <= (size_t)SCAN_T;
+    for (int j = 0; j < count; j++) {
+        scan_fill(mode, jobs[j], S.base + per * (size_t)j, A[j], B[j]);
+        if (jobs[j].d_total) B[j].bpart = (uint32_t*)jobs[j].d_total; // one element: the grand total, written where the caller wants it
+        A3[j] = A[j];
+        if (!jobs[j].out) A3[j].n = 0;
+        if (fused) {
+            A3[j].fused_nb = (uint32_t)nb;
+            A3[j].total_out = B[j].bpart;
+            A3[j].n = A[j].n;
+        }
+    }
+    if (int rc = T.flush(st)) return rc;
+    const dim3 g1((uint32_t)nb, count), gb(1, count);
+    if (mode == 0) {
+        k_scan_phase1_tab<0><<<g1, SCAN_T, 0, st>>>(dA);
+        if (!fused) {
+            k_scan_phase1_tab<0><<<gb, SCAN_T, 0, st>>>(dB);
+            k_scan_phase3_tab<0><<<gb, SCAN_T, 0, st>>>(dB);
+        }
+        k_scan_phase3_tab<0><<<g1, SCAN_T, 0, st>>>(dA3);
+    } else {
+        k_scan_phase1_tab<1><<<g1, SCAN_T, 0, st>>>(dA);
+        if (!fused) {
+            k_scan_phase1_tab<1><<<gb, SCAN_T, 0, st>>>(dB);
+            k_scan_phase3_tab<1><<<gb, SCAN_T, 0, st>>>(dB);
+        }
+        k_scan_phase3_tab<1><<<g1, SCAN_T, 0, st>>>(dA3);
+    }
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+
+int evaluate_lanes(const EvalJob* jobs, const int* zidx, int count, const host::Fr* z, int nz, LaneTable& T, Scratch& S, hipStream_t st)
+{
+    if (count < 1 || nz < 1) return BBGPU_ERR_ARG;
+    if (int rc = S.ensure((size_t)count * 256 * 32 + 64)) return rc;
+    EvalTabJob* J = nullptr;
+    const EvalTabJob* dJ = nullptr;
+    if (int rc = T.push(count, &J, &dJ)) return rc;
+    std::vector<PowTab> tabs((size_t)nz);
+    for (int k = 0; k < nz; k++) tabs[k] = make_powtab(z[k]);
+    // z^(blocks * PT): the jobs of a proof have two lengths (n and 3n), so two values per point
+    struct ZT { int zi; uint32_t blocks; Limbs9 v; };
+    std::vector<ZT> zts;
+    uint32_t maxb = 1;
+    for (int j = 0; j < count; j++) {
+        const size_t n = jobs[j].n;
+        if (n == 0 || zidx[j] < 0 || zidx[j] >= nz) return BBGPU_ERR_ARG;
+        const uint32_t blocks = eval_blocks(n);
+        const Limbs9* zt = nullptr;
+        for (const ZT& e : zts)
+            if (e.zi == zidx[j] && e.blocks == blocks) zt = &e.v;
+        if (!zt) {
+            zts.push_back(ZT{ zidx[j], blocks, host::limbs_m261(host::fr_pow(z[zidx[j]], (uint64_t)blocks * PT)) });
+            zt = &zts.back().v;
+        }
+        J[j].c = (const uint32_t*)jobs[j].coeffs;
+        J[j].result = (uint32_t*)jobs[j].d_result;
+        J[j].partial = (uint32_t*)S.base + (size_t)j * 256 * 8;
+        J[j].n = (uint32_t)n;
+        J[j].blocks = blocks;
+        J[j].zT = *zt;
+        J[j].T = tabs[zidx[j]];
+        maxb = std::max(maxb, blocks);
+    }
+    if (int rc = T.flush(st)) return rc;
+    k_eval_partial_tab<<<dim3(maxb, count), PT, 0, st>>>(dJ);
+    k_sum_small_tab<<<count, PT, 0, st>>>(dJ);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }

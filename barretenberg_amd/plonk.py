@@ -392,6 +392,34 @@ class Prover:
         self.gpu._chk(self.gpu.lib.bbgpu_plonk_construct_proof(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64))))
         return out
 
+    def construct_proofs(self, witnesses):
+        """one proof per witness in one resident call (bbgpu_plonk_construct_proof_batch): witnesses is a sequence of (w_l, w_r, w_o), each
+        (n, 4) uint64 as for set_witness -> (count, 120) uint64; row j is what set_witness(*witnesses[j]) + construct_proof() returns"""
+        L = self.gpu.lib
+        count = len(witnesses)
+        keep = [[np.ascontiguousarray(a, dtype=np.uint64) for a in w] for w in witnesses]
+        for w in keep:
+            assert len(w) == 3 and all(a.size == self.n * 4 for a in w), "each witness is (w_l, w_r, w_o) of n x 4 limbs"
+        cols = [(C.c_void_p * max(count, 1))(*[w[k].ctypes.data for w in keep]) for k in range(3)]
+        out = np.zeros((count, 120), dtype=np.uint64)
+        L.bbgpu_plonk_construct_proof_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.gpu._chk(L.bbgpu_plonk_construct_proof_batch(self.handle, count, cols[0], cols[1], cols[2], out.ctypes.data))
+        return out
+
+    def batch_challenges(self, lane):
+        """challenges() of lane `lane` of the last construct_proofs call"""
+        out = np.zeros(20, dtype=np.uint64)
+        self.gpu.lib.bbgpu_plonk_batch_challenges.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        self.gpu._chk(self.gpu.lib.bbgpu_plonk_batch_challenges(self.handle, int(lane), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return {k: out[4 * i:4 * i + 4] for i, k in enumerate(("beta", "gamma", "alpha", "z", "nu"))}
+
+    def batch_timing(self):
+        """timing() of the last construct_proofs call, for the whole batch"""
+        buf = (C.c_double * 4)()
+        self.gpu.lib.bbgpu_plonk_last_batch_timing.argtypes = [C.c_int, C.POINTER(C.c_double)]
+        self.gpu._chk(self.gpu.lib.bbgpu_plonk_last_batch_timing(self.handle, buf))
+        return {"total_ms": buf[0], "commitments_ms": buf[1], "rest_ms": buf[2], "first_use_preparation_ms": buf[3]}
+
     def preprocess(self):
         """waffle::preprocess(prover): -> dict of the eight verification-key commitments, each (8,) uint64 affine"""
         out = np.zeros(96, dtype=np.uint64)

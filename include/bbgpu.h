@@ -62,7 +62,8 @@ int bbgpu_device_count(void);
  * the life of the binding, and the m partial sums are added on the host -- the point-range split of batched_scalar_multiplications
  * (scalar_multiplication.cpp:703-738), over GPUs instead of threads.  The result is the one-context result, bit for bit.  With m == 1 the call runs
  * on context 0 as it does without this binding.  Everything else -- transforms, polynomial helpers, bbgpu_msm_g1_plain, the device-pointer MSMs
- * and their tickets, SRS handles, the resident prover -- runs on context 0.
+ * and their tickets, SRS handles, the resident prover -- runs on context 0 (bbgpu_plonk_construct_proof_batch too: like the single proof it holds the
+ * prover's lock from its first launch to its last byte).
  * Memory: each context caches the slices it was given of a table registered on first sight (1 / m of its points and window tables each);
  * BBGPU_SRS_CACHE_BYTES caps every context's cache on its own.  A table registered EXPLICITLY stays whole on context 0 (its handle serves the
  * device entries); a split call over it uses it there for context 0's slice and the other contexts register their slices on first sight.
@@ -89,7 +90,7 @@ typedef struct {
     uint64_t ntt_table_cap_bytes;
     uint64_t ntt_table_sets;      /* how many domain sizes are cached */
     uint64_t msm_workspace_bytes; /* the MSM slots' workspaces (allocated on first use of a slot, sized by its largest MSM) */
-    uint64_t staging_bytes;       /* scalar / coefficient staging, transform scratch, polynomial temporaries */
+    uint64_t staging_bytes;       /* scalar / coefficient staging, transform scratch, polynomial temporaries, the lanes of bbgpu_plonk_construct_proof_batch */
     uint64_t pinned_host_bytes;   /* pinned host memory: staging buffers and the slots' result arrays */
 } bbgpu_memory_info;
 int bbgpu_memory_stats(bbgpu_memory_info* out);                     /* the sum over every bound context */
@@ -364,6 +365,21 @@ int bbgpu_plonk_construct_proof(int prover, uint64_t proof_out[BBGPU_PLONK_PROOF
 int bbgpu_plonk_preprocess(int prover, uint64_t vk_out[BBGPU_PLONK_VK_WORDS]);
 int bbgpu_plonk_last_challenges(int prover, uint64_t out[20]); /* beta, gamma, alpha, z, nu (waffle_types.hpp:9-16) */
 int bbgpu_plonk_last_timing(int prover, double ms_out[4]);     /* construct_proof wall ms: total, in commitments, rest, first-use preparation */
+/* A batch of proofs of the prover's circuit, one per witness, in one call: the rounds of construct_proof advance in lockstep over `count` LANES, every
+ * round step one launch for all lanes, the commitments of a round as batch tickets side by side -- the chip is mostly idle inside one proof of up to
+ * about 2^18 gates, and only another proof's work can fill it (each round waits for its own Fiat-Shamir challenge).
+ * w_l[j], w_r[j], w_o[j]: host arrays of n x 4 limbs (the format of bbgpu_plonk_prover_set_witness).  proofs_out: count x BBGPU_PLONK_PROOF_WORDS;
+ * proof j is, byte for byte, what bbgpu_plonk_prover_set_witness(w_l[j], w_r[j], w_o[j]) + bbgpu_plonk_construct_proof would return.
+ * BBGPU_ERR_ARG: unknown handle, count < 1, count > BBGPU_PLONK_MAX_BATCH, a null array or a null entry; BBGPU_ERR_SIZE: count * n > 2^22 (the lanes
+ * hold 48 vectors of n x 32 bytes each: 96 MiB per lane at 2^16 gates, 6 GiB at the bound).  These checks come before the library binds a device.
+ * The lanes are allocated on the first batch, grown when a larger count arrives, released with the handle, and counted in
+ * bbgpu_memory_info.staging_bytes.  The call touches neither the witness the handle holds for bbgpu_plonk_construct_proof nor
+ * bbgpu_plonk_last_challenges / _last_timing.  On a failure every MSM ticket the call issued has been collected and the handle stays usable. */
+#define BBGPU_PLONK_MAX_BATCH 16
+int bbgpu_plonk_construct_proof_batch(int prover, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o,
+                                      uint64_t* proofs_out);
+int bbgpu_plonk_batch_challenges(int prover, int lane, uint64_t out[20]); /* beta, gamma, alpha, z, nu of lane `lane` of the last batch */
+int bbgpu_plonk_last_batch_timing(int prover, double ms_out[4]);          /* as bbgpu_plonk_last_timing, for the whole batch */
 int bbgpu_plonk_prover_destroy(int prover);
 /* challenge.hpp:64-112 recomputed from a finished proof: gamma, beta, alpha, z (4 limbs each).  Host only, no GPU needed. */
 int bbgpu_plonk_challenges_from_proof(const uint64_t proof[BBGPU_PLONK_PROOF_WORDS], uint64_t out[16]);
