@@ -54,7 +54,10 @@ C_ABI_SYMBOLS = [
     "bbgpu_host_msm_g1", "bbgpu_host_ntt", "bbgpu_host_fr_evaluate", "bbgpu_host_kate_opening", "bbgpu_host_lagrange_l1_fft",
     "bbgpu_host_divide_by_pseudo_vanishing", "bbgpu_memory_stats", "bbgpu_fault_inject", "bbgpu_fault_stats", "bbgpu_srs_set_validate",
     "bbgpu_init_devices", "bbgpu_num_contexts", "bbgpu_memory_stats_context",
+    "bbgpu_plonk_check_witness", "bbgpu_plonk_check_witness_batch", "bbgpu_plonk_set_witness_check", "bbgpu_plonk_last_witness_report",
+    "bbgpu_host_plonk_check_witness",
 ]
+ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
 
 class MemoryInfo(C.Structure):
@@ -67,6 +70,15 @@ class FaultInfo(C.Structure):
     """bbgpu_fault_info (include/bbgpu.h)"""
     _fields_ = [(k, C.c_uint64) for k in ("alloc_calls", "h2d_calls", "d2h_calls", "launch_checks", "armed", "fired", "absorbed", "live_allocations",
                                           "live_bytes", "slots_pending")]
+
+
+class WitnessReport(C.Structure):
+    """bbgpu_plonk_witness_report (include/bbgpu.h)"""
+    _fields_ = [("gate_failures", C.c_uint64), ("copy_failures", C.c_uint64)] + \
+        [(k, C.c_uint32) for k in ("first_gate", "first_gate_kinds", "kinds", "first_copy", "first_copy_target", "_pad")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "_pad"}
 
 
 class BbGpuError(RuntimeError):

@@ -24,6 +24,7 @@
 #include "bbgpu_internal.h"
 #include "host_fr.hpp"
 #include "host_g1.hpp"
+#include "host_plonk_check.hpp"
 #include "keccak.hpp"
 #include "poly.h"
 
@@ -124,6 +125,16 @@ class PlonkProver {
     Proof proof;
     double timing[8] = {}; // total, msm, ntt+pointwise (the rest), first-use preparation
 
+    // witness check (bbgpu_plonk_check_witness*, bbgpu_plonk_set_witness_check): the result records of BBGPU_PLONK_MAX_BATCH lanes -- counts, then the
+    // atomicMin words (poly.h) -- in one small allocation beside `slots` / `lane_slots`, made on the first check; lane 0 serves the single proof
+    bool witness_check = false;
+    poly::WitnessCheckCounts* check_counts = nullptr;
+    poly::WitnessCheckFirst* check_first = nullptr;
+    void* h_check = nullptr; // pinned mirror
+    bbgpu_plonk_witness_report reports[BBGPU_PLONK_MAX_BATCH] = {};
+    int report_count = 0;
+    static constexpr size_t check_bytes = BBGPU_PLONK_MAX_BATCH * (sizeof(poly::WitnessCheckCounts) + sizeof(poly::WitnessCheckFirst));
+
     ~PlonkProver() { release(); }
     void release()
     {
@@ -143,6 +154,10 @@ class PlonkProver {
         allocs.clear();
         if (h_slots) (void)hipHostFree(h_slots);
         h_slots = nullptr;
+        if (h_check) (void)hipHostFree(h_check);
+        h_check = nullptr;
+        check_counts = nullptr; // (in `allocs`)
+        check_first = nullptr;
         scratch.release();
         if (st) (void)hipStreamDestroy(st);
         st = nullptr;
@@ -372,6 +387,94 @@ class PlonkProver {
         return b;
     }
 
+    // ---- witness check ----------------------------------------------------------------------------------------------------
+    // Needs nothing that a proof computes: the wire values as uploaded, the selector VALUES and the mappings of init().
+    int ensure_check()
+    {
+        if (check_counts) return BBGPU_OK;
+        if (!h_check) HIPCHK(hipHostMalloc(&h_check, check_bytes));
+        uint8_t* d = nullptr;
+        RC(dalloc(&d, check_bytes));
+        check_counts = reinterpret_cast<poly::WitnessCheckCounts*>(d);
+        check_first = reinterpret_cast<poly::WitnessCheckFirst*>(d + BBGPU_PLONK_MAX_BATCH * sizeof(poly::WitnessCheckCounts));
+        return BBGPU_OK;
+    }
+    poly::WitnessCheckArgs check_args(const uint64_t* wl, const uint64_t* wr, const uint64_t* wo, int lane) const
+    {
+        poly::WitnessCheckArgs A{};
+        A.w_l = (const uint32_t*)wl; A.w_r = (const uint32_t*)wr; A.w_o = (const uint32_t*)wo;
+        A.q_m = (const uint32_t*)q_lagrange[0]; A.q_l = (const uint32_t*)q_lagrange[1]; A.q_r = (const uint32_t*)q_lagrange[2];
+        A.q_o = (const uint32_t*)q_lagrange[3]; A.q_c = (const uint32_t*)q_lagrange[4];
+        A.q_on = has_seq ? (const uint32_t*)qs_lagrange : nullptr;
+        if (has_bool) { A.q_bl = (const uint32_t*)qb_lagrange[0]; A.q_br = (const uint32_t*)qb_lagrange[1]; A.q_bo = (const uint32_t*)qb_lagrange[2]; }
+        if (has_mimc) { A.q_sel = (const uint32_t*)qm_lagrange[0]; A.q_coef = (const uint32_t*)qm_lagrange[1]; }
+        A.s1 = sigma_mapping[0]; A.s2 = sigma_mapping[1]; A.s3 = sigma_mapping[2];
+        A.counts = check_counts + lane;
+        A.first = check_first + lane;
+        A.n = (uint32_t)n;
+        return A;
+    }
+    // the two kernels over `count` lanes (0: the witness the handle holds, into record 0) and the copy of the records, all on `st`
+    int check_enqueue(int count)
+    {
+        RC(ensure_check());
+        if (count == 0) {
+            RC(poly::check_witness(check_args(w_lagrange[0], w_lagrange[1], w_lagrange[2], 0), st));
+        } else {
+            std::vector<poly::WitnessCheckArgs> ca((size_t)count);
+            for (int l = 0; l < count; l++) ca[l] = check_args(lv(G_WLAG, l, 0), lv(G_WLAG, l, 1), lv(G_WLAG, l, 2), l);
+            RC(poly::check_witness_lanes(lane_tab, ca.data(), count, st));
+        }
+        HIPCHK(d2h_async(h_check, check_counts, check_bytes, st));
+        return BBGPU_OK;
+    }
+    // waits for the records and turns them into `reports`; with `verdict`, BBGPU_ERR_WITNESS when a lane fails
+    int check_finish(int count, bool verdict)
+    {
+        report_count = 0;
+        HIPCHK(hipStreamSynchronize(st));
+        const int L = std::max(count, 1);
+        const poly::WitnessCheckCounts* hc = static_cast<const poly::WitnessCheckCounts*>(h_check);
+        const poly::WitnessCheckFirst* hf = reinterpret_cast<const poly::WitnessCheckFirst*>(hc + BBGPU_PLONK_MAX_BATCH);
+        for (int l = 0; l < L; l++) {
+            bbgpu_plonk_witness_report R = host::plonk_report_clear();
+            R.gate_failures = hc[l].gate_failures;
+            R.copy_failures = hc[l].copy_failures;
+            R.kinds = hc[l].kinds;
+            if (hf[l].gate != ~0ull) {
+                R.first_gate = (uint32_t)(hf[l].gate >> 32);
+                R.first_gate_kinds = (uint32_t)hf[l].gate;
+            }
+            if (hf[l].copy != ~0ull) {
+                const uint32_t key = (uint32_t)(hf[l].copy >> 32);
+                R.first_copy = (key >> 2) | ((key & 3u) << 30);
+                R.first_copy_target = (uint32_t)hf[l].copy;
+            }
+            reports[l] = R;
+        }
+        report_count = L;
+        if (!verdict) return BBGPU_OK;
+        for (int l = 0; l < L; l++) {
+            const bbgpu_plonk_witness_report& R = reports[l];
+            if (!R.gate_failures && !R.copy_failures) continue;
+            if (R.gate_failures)
+                set_error("witness of lane %d does not satisfy the circuit: gate identity (kinds 0x%x) fails in row %u (%llu failing rows, %llu failing copy constraints)",
+                          l, R.first_gate_kinds, R.first_gate, (unsigned long long)R.gate_failures, (unsigned long long)R.copy_failures);
+            else
+                set_error("witness of lane %d does not satisfy the circuit: copy constraint of row %u, wire %u fails (mapping entry 0x%08x; %llu failing positions)", l,
+                          R.first_copy & ((1u << 29) - 1u), R.first_copy >> 30, R.first_copy_target, (unsigned long long)R.copy_failures);
+            return BBGPU_ERR_WITNESS;
+        }
+        return BBGPU_OK;
+    }
+    int check_witness(bbgpu_plonk_witness_report* out)
+    {
+        RC(check_enqueue(0));
+        RC(check_finish(0, false));
+        *out = reports[0];
+        return BBGPU_OK;
+    }
+
     // ---- circuit-only state (first proof) -----------------------------------------------------------------------------
     int prepare_circuit()
     {
@@ -533,7 +636,7 @@ class PlonkProver {
     // prover.cpp:405-465 (after the wire / Z parts above)
     int compute_quotient_polynomial()
     {
-        RC(compute_wire_coefficients());
+        // (compute_wire_coefficients() has run: construct_proof)
         RC(compute_wire_commitments());
         RC(compute_z_coefficients());
         RC(compute_z_commitment());
@@ -749,6 +852,10 @@ class PlonkProver {
         timing[0] = timing[1] = timing[2] = 0;
         RC(prepare_circuit());
         const double t0 = now_ms();
+        // opt-in: the check kernels run beside the wires' inverse transform, and their verdict is in before the first commitment is issued
+        if (witness_check) RC(check_enqueue(0));
+        RC(compute_wire_coefficients());
+        if (witness_check) RC(check_finish(0, true));
         RC(compute_quotient_polynomial());
         RC(compute_quotient_commitment());
         RC(compute_opening_elements());
@@ -933,8 +1040,10 @@ class PlonkProver {
             const uint64_t* hw[3] = { hwl[l], hwr[l], hwo[l] };
             for (int k = 0; k < 3; k++) RC(host_to_device(lv(G_WLAG, l, k), hw[k], n * 32, st));
         }
+        if (witness_check) RC(check_enqueue(L)); // opt-in: beside the inverse transforms, the verdict before the first commitment is issued
         RC(copy(lv(G_W, 0), lv(G_WLAG, 0), (size_t)3 * L * n));
         RC(bbgpu_ntt_device_batch(lv(G_W, 0), n, n, 3 * L, BBGPU_IFFT, nullptr, st));
+        if (witness_check) RC(check_finish(L, true));
         {
             PendingMany P;
             for (int l = 0; l < L; l++)
@@ -1238,6 +1347,21 @@ class PlonkProver {
         batch_timing[3] = timing[3];
         return BBGPU_OK;
     }
+    // the check alone over `count` witnesses, uploaded into the lanes a batch proof of the same count would use
+    int check_witness_batch(int count, const uint64_t* const* hwl, const uint64_t* const* hwr, const uint64_t* const* hwo, bbgpu_plonk_witness_report* out)
+    {
+        RC(prepare_circuit()); // (ensure_lanes derives the lanes' shared sigma coefficients from it)
+        RC(ensure_lanes(count));
+        lane_tab.reset();
+        for (int l = 0; l < count; l++) {
+            const uint64_t* hw[3] = { hwl[l], hwr[l], hwo[l] };
+            for (int k = 0; k < 3; k++) RC(host_to_device(lv(G_WLAG, l, k), hw[k], n * 32, st));
+        }
+        RC(check_enqueue(count));
+        RC(check_finish(count, false));
+        memcpy(out, reports, sizeof(bbgpu_plonk_witness_report) * (size_t)count);
+        return BBGPU_OK;
+    }
 };
 constexpr int PlonkProver::lane_group_vectors[PlonkProver::G_COUNT];
 
@@ -1245,14 +1369,15 @@ std::mutex g_pmu;
 std::vector<PlonkProver*> g_provers;
 
 // argument checks of the batch entry that need no device: the caller's arrays and the size bound
-int check_batch_args(const PlonkProver* p, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o, const uint64_t* out)
+int check_batch_args(const PlonkProver* p, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o, const void* out,
+                     const char* out_name = "proofs_out")
 {
     if (count < 1 || count > BBGPU_PLONK_MAX_BATCH) {
         set_error("count %d: a batch holds 1..%d proofs", count, BBGPU_PLONK_MAX_BATCH);
         return BBGPU_ERR_ARG;
     }
     if (!w_l || !w_r || !w_o || !out) {
-        set_error("null array: %s", !w_l ? "w_l" : !w_r ? "w_r" : !w_o ? "w_o" : "proofs_out");
+        set_error("null array: %s", !w_l ? "w_l" : !w_r ? "w_r" : !w_o ? "w_o" : out_name);
         return BBGPU_ERR_ARG;
     }
     for (int j = 0; j < count; j++)
@@ -1296,7 +1421,8 @@ using namespace bbgpu;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int bbgpu_plonk_prover_create(const bbgpu_plonk_circuit* c, int srs_handle)
+// what can be said about a circuit description without a device (bbgpu_plonk_prover_create, bbgpu_host_plonk_check_witness)
+static int check_circuit_fields(const bbgpu_plonk_circuit* c)
 {
     if (!c || !c->w_l || !c->w_r || !c->w_o || !c->sigma_1_mapping || !c->sigma_2_mapping || !c->sigma_3_mapping || !c->q_m || !c->q_l || !c->q_r ||
         !c->q_o || !c->q_c) {
@@ -1318,6 +1444,12 @@ int bbgpu_plonk_prover_create(const bbgpu_plonk_circuit* c, int srs_handle)
         set_error("circuit size %zu: must be a power of two, 4 <= n <= 2^21 (the largest size a reference proof exists for: larger proofs would be parity-unpinned)", c->n);
         return BBGPU_ERR_SIZE;
     }
+    return BBGPU_OK;
+}
+
+int bbgpu_plonk_prover_create(const bbgpu_plonk_circuit* c, int srs_handle)
+{
+    if (int rc = check_circuit_fields(c)) return rc;
     const int W = bbgpu_srs_num_windows(srs_handle, c->n);
     if (W < 0) {
         set_error("unknown SRS handle %d", srs_handle);
@@ -1369,6 +1501,66 @@ int bbgpu_plonk_construct_proof_batch(int prover, int count, const uint64_t* con
     const int rc = p->construct_proof_batch(count, w_l, w_r, w_o, proofs_out);
     if (rc) (void)hipStreamSynchronize(p->st); // nothing of a failed batch is still running when the caller sees the error
     return rc;
+}
+
+int bbgpu_plonk_check_witness(int prover, bbgpu_plonk_witness_report* out)
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    PlonkProver* p = get(prover);
+    if (!p || !out) return BBGPU_ERR_ARG;
+    if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
+    const int rc = p->check_witness(out);
+    if (rc) (void)hipStreamSynchronize(p->st);
+    return rc;
+}
+
+int bbgpu_plonk_check_witness_batch(int prover, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o,
+                                    bbgpu_plonk_witness_report* out)
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    // everything that can be refused without a device is refused before one is bound
+    if (int rc = check_batch_args(nullptr, count, w_l, w_r, w_o, out, "out")) return rc;
+    PlonkProver* p = get(prover);
+    if (!p) return BBGPU_ERR_ARG;
+    if (int rc = check_batch_args(p, count, w_l, w_r, w_o, out, "out")) return rc;
+    if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
+    const int rc = p->check_witness_batch(count, w_l, w_r, w_o, out);
+    if (rc) (void)hipStreamSynchronize(p->st); // the caller's arrays are no longer read when it sees the error
+    return rc;
+}
+
+int bbgpu_plonk_set_witness_check(int prover, int enabled)
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    PlonkProver* p = get(prover);
+    if (!p) return BBGPU_ERR_ARG;
+    p->witness_check = enabled != 0;
+    return BBGPU_OK;
+}
+
+int bbgpu_plonk_last_witness_report(int prover, int lane, bbgpu_plonk_witness_report* out)
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    PlonkProver* p = get(prover);
+    if (!p || !out) return BBGPU_ERR_ARG;
+    if (lane < 0 || lane >= p->report_count) {
+        set_error("lane %d: the last witness check of this prover covered %d", lane, p->report_count);
+        return BBGPU_ERR_ARG;
+    }
+    *out = p->reports[lane];
+    return BBGPU_OK;
+}
+
+// the same definition on the host (host_plonk_check.hpp): no HIP call, no lock, no state
+int bbgpu_host_plonk_check_witness(const bbgpu_plonk_circuit* circuit, bbgpu_plonk_witness_report* out)
+{
+    if (int rc = check_circuit_fields(circuit)) return rc;
+    if (!out) {
+        set_error("null report");
+        return BBGPU_ERR_ARG;
+    }
+    *out = host::plonk_check_witness(*circuit);
+    return BBGPU_OK;
 }
 
 int bbgpu_plonk_batch_challenges(int prover, int lane, uint64_t out[20])

@@ -75,6 +75,34 @@ struct LinCombArgs {
     int count;
 };
 
+// ---- witness check (bbgpu_plonk_check_witness*, include/bbgpu.h: rows 0 .. n-2 only, the last row is not constrained) ----------------------------------------
+// What the two check kernels leave per lane: 40 bytes, kept as two arrays (one per preset value) so that two memsets in front of the launches prepare every
+// lane.  Integer atomics only, and none at all for a witness that satisfies the circuit.
+struct WitnessCheckCounts {
+    unsigned long long gate_failures, copy_failures; // preset 0
+    uint32_t kinds, _pad;                            // OR of the kind masks of all failing rows
+};
+struct WitnessCheckFirst {          // preset all ones = none; atomicMin
+    unsigned long long gate;        // (row << 32) | kind mask of that row
+    unsigned long long copy;        // ((row << 2 | wire) << 32) | the position's mapping entry
+};
+struct WitnessCheckArgs {
+    const uint32_t *w_l, *w_r, *w_o;                   // n Lagrange-form values each (any representative below 2^256)
+    const uint32_t *q_m, *q_l, *q_r, *q_o, *q_c;       // selector VALUES
+    const uint32_t* q_on;                              // sequential widget: q_o_next, else null
+    const uint32_t *q_bl, *q_br, *q_bo;                // bool widget, else null
+    const uint32_t *q_sel, *q_coef;                    // MiMC widget: q_mimc_selector, q_mimc_coefficient, else null
+    const uint32_t *s1, *s2, *s3;                      // the three sigma mappings
+    WitnessCheckCounts* counts;                        // this lane's record
+    WitnessCheckFirst* first;
+    uint32_t n;
+    Limbs9 one_m256;
+};
+struct LaneTable;
+// presets `lanes` consecutive records starting at A[0].counts / A[0].first, then k_check_gates and k_check_copies: two launches however many lanes
+int check_witness(WitnessCheckArgs A, hipStream_t st);
+int check_witness_lanes(LaneTable& T, const WitnessCheckArgs* A, int lanes, hipStream_t st);
+
 struct EvalJob {
     const uint64_t* coeffs;
     size_t n;

@@ -700,6 +700,117 @@ template <bool U> __device__ __forceinline__ void quotient_bool_body(const QuotB
 __global__ void __launch_bounds__(PT) k_quotient_bool(QuotBoolArgs A) { quotient_bool_body<false>(A); }
 __global__ void __launch_bounds__(PT) k_quotient_bool_lanes(const QuotBoolArgs* __restrict__ tab) { quotient_bool_body<true>(tab[blockIdx.y]); } // one table record per lane
 
+// ---- witness check: does the witness satisfy the circuit in rows 0 .. n-2 (include/bbgpu.h, bbgpu_plonk_check_witness) --------------------------------
+// A zero test needs no canonical value: a fresh product (or shared-reduction sum of products) has exact limbs and a value below 2p, so it is zero modulo
+// r iff it is 0 or r (is_zero_mulout); every identity below ends in such a product, and a constant factor 2^-5k of the Montgomery forms does not move a zero.
+//
+// The workgroup's findings meet on chip: shuffles inside a wave, four LDS slots across the waves, then ONE thread issues the atomics -- and only if the
+// workgroup found anything, so a witness that satisfies the circuit issues none.
+__device__ __forceinline__ void check_commit(uint32_t bad, unsigned long long first, uint32_t kinds, unsigned long long* __restrict__ d_count,
+                                             unsigned long long* __restrict__ d_first, uint32_t* __restrict__ d_kinds)
+{
+    __shared__ unsigned long long s_first[PT / 64];
+    __shared__ uint32_t s_bad[PT / 64], s_kinds[PT / 64];
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        bad += __shfl_xor(bad, o);
+        kinds |= __shfl_xor(kinds, o);
+        const uint32_t lo = __shfl_xor((uint32_t)first, o), hi = __shfl_xor((uint32_t)(first >> 32), o);
+        const unsigned long long f = ((unsigned long long)hi << 32) | lo;
+        first = f < first ? f : first;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_bad[threadIdx.x >> 6] = bad;
+        s_kinds[threadIdx.x >> 6] = kinds;
+        s_first[threadIdx.x >> 6] = first;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int w = 1; w < PT / 64; w++) {
+        bad += s_bad[w];
+        kinds |= s_kinds[w];
+        first = s_first[w] < first ? s_first[w] : first;
+    }
+    if (!bad) return;
+    atomicAdd(d_count, (unsigned long long)bad);
+    atomicMin(d_first, first);
+    if (d_kinds) atomicOr(d_kinds, kinds);
+}
+
+// One thread per row, strided.  The identities (arithmetic_widget.cpp:86-101, sequential_widget.cpp:47-62, bool_widget.cpp:62-100, mimc_widget.cpp:68-85) on
+// the VALUES: each must vanish on its own.  The widget set is the circuit's, the same for every lane: uniform branches.
+template <bool U> __device__ __forceinline__ void check_gates_body(const WitnessCheckArgs& A)
+{
+    const uint32_t nt = gridDim.x * blockDim.x, rows = A.n - 1;
+    const bool has_seq = A.q_on != nullptr, has_bool = A.q_bl != nullptr, has_mimc = A.q_sel != nullptr;
+    const FrC one256 = cst<U>(A.one_m256), one261 = fe_from<Fr>(Fr::ONE);
+    uint32_t bad = 0, kinds = 0;
+    unsigned long long first = ~0ull;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += nt) {
+        const FrV wl = ldv(A.w_l, i), wr = ldv(A.w_r, i), wo = ldv(A.w_o, i);
+        uint32_t k = 0;
+        // q_l w_l + q_r w_r and (q_m w_l) w_r + q_o w_o: two reductions for four products, all carrying 2^251; one more brings the sum to the memory
+        // form and adds q_c
+        const auto t1 = mul_add(ldv(A.q_l, i), wl, ldv(A.q_r, i), wr);
+        const auto t2 = mul_add(mulv(ldv(A.q_m, i), wl), wr, ldv(A.q_o, i), wo);
+        const FrV qc = ldv(A.q_c, i);
+        bool arith_zero;
+        if (has_seq) arith_zero = is_zero_mulout(mul_add(add(add(t1, t2), mul(ldv(A.q_on, i), ldv(A.w_o, i + 1))), fix2(), qc, one261));
+        else arith_zero = is_zero_mulout(mul_add(add(t1, t2), fix2(), qc, one261));
+        if (!arith_zero) k |= BBGPU_PLONK_FAIL_ARITH;
+        if (has_bool) { // q (w^2 - w) = q w (w - 1)
+            if (!is_zero_mulout(mul(mul(wl, sub(wl, one256)), ldv(A.q_bl, i)))) k |= BBGPU_PLONK_FAIL_BOOL_L;
+            if (!is_zero_mulout(mul(mul(wr, sub(wr, one256)), ldv(A.q_br, i)))) k |= BBGPU_PLONK_FAIL_BOOL_R;
+            if (!is_zero_mulout(mul(mul(wo, sub(wo, one256)), ldv(A.q_bo, i)))) k |= BBGPU_PLONK_FAIL_BOOL_O;
+        }
+        if (has_mimc) { // t = w_o + w_l + q_coef:  q_sel (t^3 - w_r),  q_sel (t w_r^2 - w_o[i + 1])
+            const FrV qsel = ldv(A.q_sel, i);
+            const auto t = weak(add(add(wo, wl), ldv(A.q_coef, i)));
+            if (!is_zero_mulout(mul(weak(sub(mulv(mulv(t, t), t), wr)), qsel))) k |= BBGPU_PLONK_FAIL_MIMC_CUBE;
+            if (!is_zero_mulout(mul(weak(sub(mulv(mulv(wr, wr), t), ldv(A.w_o, i + 1))), qsel))) k |= BBGPU_PLONK_FAIL_MIMC_OUT;
+        }
+        if (k) {
+            const unsigned long long f = ((unsigned long long)i << 32) | k;
+            first = f < first ? f : first;
+            kinds |= k;
+            bad++;
+        }
+    }
+    check_commit(bad, first, kinds, &A.counts->gate_failures, &A.first->gate, &A.counts->kinds);
+}
+__global__ void __launch_bounds__(PT) k_check_gates(WitnessCheckArgs A) { check_gates_body<false>(A); }
+__global__ void __launch_bounds__(PT) k_check_gates_lanes(const WitnessCheckArgs* __restrict__ tab) { check_gates_body<true>(tab[blockIdx.y]); } // one table record per lane
+
+// One thread per row: its three mapping entries, decoded as k_sigma_from_mapping decodes them; the value at the target (a 32-byte gather out of the lane's
+// three wire vectors) must equal the position's own value modulo r -- the difference is tested, the representatives may differ -- and the target must lie in
+// a constrained row.
+template <bool U> __device__ __forceinline__ void check_copies_body(const WitnessCheckArgs& A)
+{
+    const uint32_t nt = gridDim.x * blockDim.x, rows = A.n - 1;
+    const FrC one261 = fe_from<Fr>(Fr::ONE);
+    uint32_t bad = 0;
+    unsigned long long first = ~0ull;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += nt) {
+        auto position = [&](const uint32_t* __restrict__ mapping, const uint32_t* __restrict__ own, uint32_t wire) {
+            const uint32_t m = mapping[i];
+            const uint32_t row = (m & ((1u << 29) - 1u)) & (A.n - 1), type = (m >> 30) & 3u;
+            const uint32_t* __restrict__ src = type == 2 ? A.w_o : type == 1 ? A.w_r : A.w_l;
+            const bool equal = is_zero_mulout(mul(sub(ldv(own, i), ldv(src, row)), one261));
+            if (equal && row < rows) return;
+            const unsigned long long f = ((unsigned long long)((i << 2) | wire) << 32) | m;
+            first = f < first ? f : first;
+            bad++;
+        };
+        position(A.s1, A.w_l, 0);
+        position(A.s2, A.w_r, 1);
+        position(A.s3, A.w_o, 2);
+    }
+    check_commit(bad, first, 0, &A.counts->copy_failures, &A.first->copy, nullptr);
+}
+__global__ void __launch_bounds__(PT) k_check_copies(WitnessCheckArgs A) { check_copies_body<false>(A); }
+__global__ void __launch_bounds__(PT) k_check_copies_lanes(const WitnessCheckArgs* __restrict__ tab) { check_copies_body<true>(tab[blockIdx.y]); } // one table record per lane
+
 // polynomial_arithmetic.cpp:478-560: c[i] *= (x_i - w_n^-1) / ((x_i)^n - 1),  x_i = g w_N^i;  (x_i)^n - 1 takes k = N/n values
 __global__ void __launch_bounds__(PT) k_divide_vanishing(uint32_t* __restrict__ c, uint32_t N, uint32_t k, PowTab root, Limbs9 g_m261, Limbs9 step_m261,
                                                        Limbs9 wninv_m261, Limbs9 inv0, Limbs9 inv1, Limbs9 inv2, Limbs9 inv3)
@@ -1275,6 +1386,25 @@ int quotient_bool(QuotBoolArgs A, const host::Fr& c_left, const host::Fr& c_righ
     return BBGPU_OK;
 }
 
+// the records of `lanes` lanes, consecutive from counts / first: zero the counts, all ones (= none) into the atomicMin words
+static int check_witness_preset(WitnessCheckCounts* counts, WitnessCheckFirst* first, int lanes, hipStream_t st)
+{
+    HIPCHK(hipMemsetAsync(counts, 0, sizeof(WitnessCheckCounts) * (size_t)lanes, st));
+    HIPCHK(hipMemsetAsync(first, 0xff, sizeof(WitnessCheckFirst) * (size_t)lanes, st));
+    return BBGPU_OK;
+}
+int check_witness(WitnessCheckArgs A, hipStream_t st)
+{
+    A.one_m256 = host::limbs_m256(host::fr_one());
+    if (int rc = check_witness_preset(A.counts, A.first, 1, st)) return rc;
+    const uint32_t blocks = strided_blocks(A.n);
+    k_check_gates<<<blocks, PT, 0, st>>>(A);
+    HIPCHK(launch_check());
+    k_check_copies<<<blocks, PT, 0, st>>>(A);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+
 // g^n for n = 2^log2n
 static host::Fr coset_gen_pow_n(int log2n)
 {
@@ -1492,6 +1622,19 @@ int quotient_seq_lanes(LaneTable& T, const QuotSeqArgs* A, int lanes, const host
                                [&](QuotSeqArgs& R, int l) { R.c_fix_m261 = host::limbs_m261(host::fr_mul(c[l], host::fr_from_u64(32))); }))
         return rc;
     k_quotient_seq_lanes<<<dim3(pw_blocks(A[0].n2), lanes), PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int check_witness_lanes(LaneTable& T, const WitnessCheckArgs* A, int lanes, hipStream_t st)
+{
+    const Limbs9 one = host::limbs_m256(host::fr_one());
+    const WitnessCheckArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st, [&](WitnessCheckArgs& R, int) { R.one_m256 = one; })) return rc;
+    if (int rc = check_witness_preset(A[0].counts, A[0].first, lanes, st)) return rc;
+    const dim3 grid(strided_blocks(A[0].n), lanes);
+    k_check_gates_lanes<<<grid, PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    k_check_copies_lanes<<<grid, PT, 0, st>>>(dev);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }

@@ -361,6 +361,49 @@ class _Circuit(C.Structure):
                                                                "q_mimc_selector", "q_mimc_coefficient", "q_o_next")]
 
 
+FAIL_KINDS = {"ARITH": 1, "BOOL_L": 2, "BOOL_R": 4, "BOOL_O": 8, "MIMC_CUBE": 16, "MIMC_OUT": 32}  # BBGPU_PLONK_FAIL_*
+NONE = 0xFFFFFFFF  # BBGPU_PLONK_NONE
+
+
+class WitnessError(Exception):
+    """construct_proof / construct_proofs with set_witness_check(True): a witness does not satisfy the circuit and no proof was written.
+    ``reports`` holds one report dict per lane (one for the single proof); a lane is good iff gate_failures == copy_failures == 0."""
+
+    def __init__(self, message, reports):
+        super().__init__(message)
+        self.reports = reports
+
+    def bad_lanes(self):
+        return [j for j, r in enumerate(self.reports) if r["gate_failures"] or r["copy_failures"]]
+
+
+def _circuit_struct(state):
+    """-> (_Circuit, the arrays it points into)"""
+    n = int(state["n"])
+    keep = {k: np.ascontiguousarray(state[k]) for k in state if k != "n"}
+    c = _Circuit()
+    c.n = n
+    for k, a in keep.items():
+        want = np.uint32 if k.endswith("mapping") else np.uint64
+        assert a.dtype == want and a.shape[0] == n, k
+        setattr(c, k, a.ctypes.data)
+    return c, keep
+
+
+def host_check_witness(state, lib=None):
+    """bbgpu_host_plonk_check_witness: does the witness state["w_l" / "w_r" / "w_o"] satisfy the circuit `state` (rows 0 .. n-2: include/bbgpu.h)?
+    Host arithmetic, no GPU.  -> report dict"""
+    from .bbgpu import BbGpu, WitnessReport
+    if lib is None:
+        lib = BbGpu(init=False)
+    c, keep = _circuit_struct(state)
+    rep = WitnessReport()
+    lib.lib.bbgpu_host_plonk_check_witness.argtypes = [C.POINTER(_Circuit), C.POINTER(WitnessReport)]
+    lib._chk(lib.lib.bbgpu_host_plonk_check_witness(C.byref(c), C.byref(rep)))
+    del keep
+    return rep.as_dict()
+
+
 class Prover:
     """waffle::Prover over the C ABI: Prover(gpu, circuit_state, srs_handle).construct_proof()"""
 
@@ -373,13 +416,7 @@ class Prover:
         L.bbgpu_plonk_last_timing.argtypes = [C.c_int, C.POINTER(C.c_double)]
         L.bbgpu_plonk_prover_set_witness.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         self.n = int(state["n"])
-        self._keep = {k: np.ascontiguousarray(state[k]) for k in state if k != "n"}
-        c = _Circuit()
-        c.n = self.n
-        for k, a in self._keep.items():
-            want = np.uint32 if k.endswith("mapping") else np.uint64
-            assert a.dtype == want and a.shape[0] == self.n, k
-            setattr(c, k, a.ctypes.data)
+        c, self._keep = _circuit_struct(state)
         self.handle = gpu._chk(L.bbgpu_plonk_prover_create(C.byref(c), srs_handle))
 
     def set_witness(self, w_l, w_r, w_o):
@@ -389,8 +426,53 @@ class Prover:
     def construct_proof(self):
         """-> (120,) uint64: nine affine commitments, seven evaluations, five widget-dependent evaluations (waffle_types.hpp:18-45)"""
         out = np.zeros(120, dtype=np.uint64)
-        self.gpu._chk(self.gpu.lib.bbgpu_plonk_construct_proof(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self._chk_witness(self.gpu.lib.bbgpu_plonk_construct_proof(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64))), 1)
         return out
+
+    def _chk_witness(self, rc, lanes):
+        """_chk of a proof call: BBGPU_ERR_WITNESS becomes a WitnessError that carries every lane's report"""
+        from .bbgpu import ERR_WITNESS
+        if rc == ERR_WITNESS:
+            message = self.gpu.lib.bbgpu_last_error().decode()
+            raise WitnessError(message, [self.last_witness_report(j) for j in range(lanes)])
+        return self.gpu._chk(rc)
+
+    def set_witness_check(self, flag):
+        """bbgpu_plonk_set_witness_check: construct_proof / construct_proofs check their witnesses first and raise WitnessError (default off)"""
+        self.gpu.lib.bbgpu_plonk_set_witness_check.argtypes = [C.c_int, C.c_int]
+        self.gpu._chk(self.gpu.lib.bbgpu_plonk_set_witness_check(self.handle, 1 if flag else 0))
+
+    def check_witness(self):
+        """bbgpu_plonk_check_witness: the witness the prover holds -> report dict (good iff gate_failures == copy_failures == 0)"""
+        from .bbgpu import WitnessReport
+        rep = WitnessReport()
+        self.gpu.lib.bbgpu_plonk_check_witness.argtypes = [C.c_int, C.POINTER(WitnessReport)]
+        self.gpu._chk(self.gpu.lib.bbgpu_plonk_check_witness(self.handle, C.byref(rep)))
+        return rep.as_dict()
+
+    def check_witnesses(self, witnesses, raw=False):
+        """bbgpu_plonk_check_witness_batch: witnesses as construct_proofs takes them -> one report dict per lane, in one resident call
+        (raw: -> (reports, the bytes of the report array as the library wrote it))"""
+        from .bbgpu import WitnessReport
+        L = self.gpu.lib
+        count = len(witnesses)
+        keep = [[np.ascontiguousarray(a, dtype=np.uint64) for a in w] for w in witnesses]
+        for w in keep:
+            assert len(w) == 3 and all(a.size == self.n * 4 for a in w), "each witness is (w_l, w_r, w_o) of n x 4 limbs"
+        cols = [(C.c_void_p * max(count, 1))(*[w[k].ctypes.data for w in keep]) for k in range(3)]
+        reps = (WitnessReport * max(count, 1))()
+        L.bbgpu_plonk_check_witness_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(WitnessReport)]
+        self.gpu._chk(L.bbgpu_plonk_check_witness_batch(self.handle, count, cols[0], cols[1], cols[2], reps))
+        out = [reps[j].as_dict() for j in range(count)]
+        return (out, bytes(reps)[:40 * count]) if raw else out
+
+    def last_witness_report(self, lane=0):
+        """bbgpu_plonk_last_witness_report: lane `lane` of the last checked proof call or check entry"""
+        from .bbgpu import WitnessReport
+        rep = WitnessReport()
+        self.gpu.lib.bbgpu_plonk_last_witness_report.argtypes = [C.c_int, C.c_int, C.POINTER(WitnessReport)]
+        self.gpu._chk(self.gpu.lib.bbgpu_plonk_last_witness_report(self.handle, int(lane), C.byref(rep)))
+        return rep.as_dict()
 
     def construct_proofs(self, witnesses):
         """one proof per witness in one resident call (bbgpu_plonk_construct_proof_batch): witnesses is a sequence of (w_l, w_r, w_o), each
@@ -403,7 +485,7 @@ class Prover:
         cols = [(C.c_void_p * max(count, 1))(*[w[k].ctypes.data for w in keep]) for k in range(3)]
         out = np.zeros((count, 120), dtype=np.uint64)
         L.bbgpu_plonk_construct_proof_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.gpu._chk(L.bbgpu_plonk_construct_proof_batch(self.handle, count, cols[0], cols[1], cols[2], out.ctypes.data))
+        self._chk_witness(L.bbgpu_plonk_construct_proof_batch(self.handle, count, cols[0], cols[1], cols[2], out.ctypes.data), count)
         return out
 
     def batch_challenges(self, lane):

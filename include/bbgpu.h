@@ -31,8 +31,9 @@ enum {
     BBGPU_ERR_SIZE = -2,  /* size not supported (NTT: n must be 2^k, 2 <= n <= 2^28 = the two-adicity of the field) */
     BBGPU_ERR_ARG = -3,   /* null pointer / bad enum / unknown handle */
     BBGPU_ERR_STATE = -4, /* library not initialised / every MSM slot in flight / a table that lacks what the call needs */
-    BBGPU_ERR_LOST = -5   /* an IN-PLACE host-buffer call failed while its result was being copied back: the caller's buffer may hold a mixture of
+    BBGPU_ERR_LOST = -5,  /* an IN-PLACE host-buffer call failed while its result was being copied back: the caller's buffer may hold a mixture of
                              input and output (the one failure the shim cannot answer with a host computation) */
+    BBGPU_ERR_WITNESS = -6 /* bbgpu_plonk_set_witness_check is on and a witness does not satisfy the circuit: no proof was written */
 };
 
 /* polynomial_arithmetic.hpp:27-41: which member of the fft family */
@@ -380,6 +381,56 @@ int bbgpu_plonk_construct_proof_batch(int prover, int count, const uint64_t* con
                                       uint64_t* proofs_out);
 int bbgpu_plonk_batch_challenges(int prover, int lane, uint64_t out[20]); /* beta, gamma, alpha, z, nu of lane `lane` of the last batch */
 int bbgpu_plonk_last_batch_timing(int prover, double ms_out[4]);          /* as bbgpu_plonk_last_timing, for the whole batch */
+/* ---- does a witness satisfy the circuit?  (checked on the GPU before proving; the reference has no such check) ------
+ * The prover takes any witness: for one that violates the circuit it returns BBGPU_OK and 960 bytes the Verifier rejects (Prover::construct_proof
+ * divides by the vanishing polynomial blindly, and so do the entries above).  These entries answer the question exactly, and say where.
+ * What "satisfies" means is what the proof system enforces.  It divides every identity by the PSEUDO vanishing polynomial
+ * Z_H*(X) = (X^n - 1) / (X - w^(n-1)) (polynomial_arithmetic.cpp:478-560), and the grand product runs over rows 0 .. n-2 with Z(w^(n-1)) = 1 enforced by
+ * the L_{n-1} term (prover.cpp:135-222, :364-398): ROW n-1 IS NOT CONSTRAINED, neither its gate identity nor its copy constraints, and the Verifier
+ * accepts whatever stands there (all composers but one leave a padding row, new_n >= n + 1; MiMCComposer::preprocess rounds n itself, and the
+ * Verifier rejects its honest proof when the gate count is a power of two -- two wire cycles then run through row n-1, which the check reports).
+ * With R = n - 1, rows i = 0 .. R-1, all arithmetic modulo r on any representative below 2^256:
+ *   gate identities, each zero on its own (the widgets separate them by powers of alpha):
+ *     ARITH      q_m w_l w_r + q_l w_l + q_r w_r + q_o w_o + q_c  (+ q_o_next[i] w_o[i+1] with the sequential widget, sequential_widget.cpp:47-62)
+ *     BOOL_L/R/O q_bl (w_l^2 - w_l), q_br (w_r^2 - w_r), q_bo (w_o^2 - w_o)                                     (bool_widget.cpp:62-100)
+ *     MIMC_CUBE  q_mimc_selector (t^3 - w_r),  MIMC_OUT  q_mimc_selector (t w_r^2 - w_o[i+1]),  t = w_o + w_l + q_mimc_coefficient  (mimc_widget.cpp:68-85)
+ *   copy constraints: for each of the 3R wire positions p = (row i < R, wire k) with the mapping entry m decoded as the prover decodes it
+ *     (row = (m & (2^29 - 1)) & (n - 1), wire = bits 30-31, code 3 read as the left wire): the value at sigma(p) equals the value at p modulo r, AND
+ *     sigma(p) lies in a row < R (a position whose sigma points into row n-1 breaks the grand product as surely as unequal values do).
+ * Whether the three mappings form a permutation is a property of the circuit, not of a witness, and is not checked. */
+#define BBGPU_PLONK_FAIL_ARITH 1u
+#define BBGPU_PLONK_FAIL_BOOL_L 2u
+#define BBGPU_PLONK_FAIL_BOOL_R 4u
+#define BBGPU_PLONK_FAIL_BOOL_O 8u
+#define BBGPU_PLONK_FAIL_MIMC_CUBE 16u
+#define BBGPU_PLONK_FAIL_MIMC_OUT 32u
+#define BBGPU_PLONK_NONE 0xFFFFFFFFu
+typedef struct {
+    uint64_t gate_failures;     /* rows < n-1 in which at least one identity is non-zero */
+    uint64_t copy_failures;     /* wire positions in rows < n-1 that fail their copy constraint */
+    uint32_t first_gate;        /* smallest failing row, BBGPU_PLONK_NONE if none */
+    uint32_t first_gate_kinds;  /* the identities failing in that row (bit mask), 0 if none */
+    uint32_t kinds;             /* OR of the masks of all failing rows */
+    uint32_t first_copy;        /* first failing position in mapping encoding (row | wire << 30), ordered by row, then wire; BBGPU_PLONK_NONE if none */
+    uint32_t first_copy_target; /* its mapping entry, BBGPU_PLONK_NONE if none */
+    uint32_t _pad;
+} bbgpu_plonk_witness_report;
+/* A witness is good iff gate_failures == 0 && copy_failures == 0.  Both entries return BBGPU_OK when the check RAN; the verdict is in the report.  The
+ * reports do not vary from run to run and equal bbgpu_host_plonk_check_witness's, field for field.  Two launches per call however many lanes.
+ * bbgpu_plonk_check_witness: the witness the handle holds (bbgpu_plonk_prover_create / _set_witness).
+ * bbgpu_plonk_check_witness_batch: `count` witnesses as bbgpu_plonk_construct_proof_batch takes them, one report each; the same argument and size rules,
+ * refused before a device is bound.  The witnesses are uploaded into the lanes of the batch entry, so a following batch proof of the same count
+ * allocates nothing new.  Neither entry touches the witness the handle holds, its challenges or its timings. */
+int bbgpu_plonk_check_witness(int prover, bbgpu_plonk_witness_report* out);
+int bbgpu_plonk_check_witness_batch(int prover, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o,
+                                    bbgpu_plonk_witness_report* out /* count */);
+/* enabled != 0: bbgpu_plonk_construct_proof and bbgpu_plonk_construct_proof_batch check the witness(es) they are about to prove -- the same kernels on the
+ * vectors already uploaded -- before the first commitment.  If any lane fails, the call returns BBGPU_ERR_WITNESS, writes NO proof bytes for any lane, has
+ * no MSM ticket outstanding and leaves the handle usable; bbgpu_last_error() names the first bad lane, row and kind, bbgpu_plonk_last_witness_report gives
+ * every lane's report (lane 0 for the single proof).  The caller drops the bad lanes and calls again.  Default 0: nothing is checked, launched or copied
+ * that was not before. */
+int bbgpu_plonk_set_witness_check(int prover, int enabled);
+int bbgpu_plonk_last_witness_report(int prover, int lane, bbgpu_plonk_witness_report* out); /* of the last checked proof call or check entry */
 int bbgpu_plonk_prover_destroy(int prover);
 /* challenge.hpp:64-112 recomputed from a finished proof: gamma, beta, alpha, z (4 limbs each).  Host only, no GPU needed. */
 int bbgpu_plonk_challenges_from_proof(const uint64_t proof[BBGPU_PLONK_PROOF_WORDS], uint64_t out[16]);
@@ -397,6 +448,9 @@ int bbgpu_host_fr_evaluate(const uint64_t* coeffs, size_t n, const uint64_t z[4]
 int bbgpu_host_kate_opening(const uint64_t* src, uint64_t* dest, size_t n, const uint64_t z[4], uint64_t f_of_z[4]);
 int bbgpu_host_lagrange_l1_fft(uint64_t* l_1, size_t n_src, size_t n_target);
 int bbgpu_host_divide_by_pseudo_vanishing(uint64_t* coeffs, size_t n_src, size_t n_target);
+/* bbgpu_plonk_check_witness on the host, for a caller without a GPU: the same definition, the same report; circuit->w_l / w_r / w_o are the witness.
+ * Argument errors as bbgpu_plonk_prover_create (BBGPU_ERR_ARG: a null field, a widget's selectors given in part; BBGPU_ERR_SIZE: n). */
+int bbgpu_host_plonk_check_witness(const bbgpu_plonk_circuit* circuit, bbgpu_plonk_witness_report* out);
 
 /* ---- device self-test: known-answer entry points for the field and group layer ------------------------------------
  * One GPU lane per case runs the device arithmetic every kernel is built from (csrc/fe.hpp incl. the gfx950 asm products, csrc/g1.hpp);
