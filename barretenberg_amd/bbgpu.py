@@ -56,6 +56,8 @@ C_ABI_SYMBOLS = [
     "bbgpu_init_devices", "bbgpu_num_contexts", "bbgpu_memory_stats_context",
     "bbgpu_plonk_check_witness", "bbgpu_plonk_check_witness_batch", "bbgpu_plonk_set_witness_check", "bbgpu_plonk_last_witness_report",
     "bbgpu_host_plonk_check_witness",
+    "bbgpu_plonk_prover_set_wire_map", "bbgpu_plonk_prover_set_witness_from", "bbgpu_plonk_construct_proof_batch_from",
+    "bbgpu_plonk_check_witness_batch_from",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -79,6 +81,14 @@ class WitnessReport(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "_pad"}
+
+
+class PlonkWitness(C.Structure):
+    """bbgpu_plonk_witness (include/bbgpu.h)"""
+    WIRES, VARIABLES = 0, 1  # form
+    HOST, DEVICE = 0, 1      # where
+    _fields_ = [("form", C.c_int), ("where", C.c_int), ("w_l", C.c_void_p), ("w_r", C.c_void_p), ("w_o", C.c_void_p), ("variables", C.c_void_p),
+                ("hip_stream", C.c_void_p)]
 
 
 class BbGpuError(RuntimeError):

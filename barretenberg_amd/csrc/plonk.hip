@@ -135,11 +135,46 @@ class PlonkProver {
     int report_count = 0;
     static constexpr size_t check_bytes = BBGPU_PLONK_MAX_BATCH * (sizeof(poly::WitnessCheckCounts) + sizeof(poly::WitnessCheckFirst));
 
+    // witnesses as composer variables (bbgpu_plonk_prover_set_wire_map, the VARIABLES form of bbgpu_plonk_witness): the circuit's wire -> variable indices,
+    // w_l | w_r | w_o in one allocation, and where host variables land before the expansion -- one buffer for the witness the handle holds, one per lane
+    // for the batches (`lane_vars`, beside the lane groups below).  All of it is counted with the lanes (g_lane_bytes) and goes with the handle.
+    uint32_t* wire_map = nullptr;
+    size_t num_variables = 0;
+    uint64_t* var_stage = nullptr;
+    uint64_t* lane_vars = nullptr;
+    size_t lane_vars_bytes = 0;
+    hipEvent_t caller_ready = nullptr; // orders `st` behind the stream a caller produced its device buffers on
+
     ~PlonkProver() { release(); }
+    void release_wire_map()
+    {
+        if (wire_map) {
+            (void)dev_free(wire_map);
+            g_lane_bytes -= 3 * n * 4;
+        }
+        wire_map = nullptr;
+        if (var_stage) {
+            (void)dev_free(var_stage);
+            g_lane_bytes -= num_variables * 32;
+        }
+        var_stage = nullptr;
+        release_lane_vars();
+        num_variables = 0;
+    }
+    void release_lane_vars()
+    {
+        if (lane_vars) (void)dev_free(lane_vars);
+        lane_vars = nullptr;
+        g_lane_bytes -= lane_vars_bytes;
+        lane_vars_bytes = 0;
+    }
     void release()
     {
         if (st) (void)hipStreamSynchronize(st);
         release_lanes();
+        release_wire_map();
+        if (caller_ready) (void)hipEventDestroy(caller_ready);
+        caller_ready = nullptr;
         if (sigma_coeff) (void)dev_free(sigma_coeff);
         sigma_coeff = nullptr;
         lane_tab.release();
@@ -264,6 +299,71 @@ class PlonkProver {
         const uint64_t* hw[3] = { wl, wr, wo };
         for (int k = 0; k < 3; k++) RC(host_to_device(w_lagrange[k], hw[k], n * 32, st));
         HIPCHK(hipStreamSynchronize(st));
+        return BBGPU_OK;
+    }
+
+    // ---- witnesses in other forms and places (bbgpu_plonk_witness) ------------------------------------------------------------------
+    int set_wire_map(const uint32_t* const idx[3], size_t nv)
+    {
+        HIPCHK(hipStreamSynchronize(st));
+        release_wire_map(); // the staging is sized by the number of variables: a new map starts over
+        uint32_t* d = nullptr;
+        HIPCHK(dev_malloc((void**)&d, 3 * n * 4));
+        std::vector<uint32_t> all(3 * n);
+        for (int k = 0; k < 3; k++) memcpy(all.data() + (size_t)k * n, idx[k], n * 4);
+        int rc = host_to_device(d, all.data(), 3 * n * 4, st);
+        if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = BBGPU_ERR_HIP; // `all` goes away
+        if (rc) {
+            (void)hipStreamSynchronize(st);
+            (void)dev_free(d);
+            return rc;
+        }
+        wire_map = d;
+        num_variables = nv;
+        g_lane_bytes += 3 * n * 4;
+        return BBGPU_OK;
+    }
+    // `st` continues behind everything enqueued so far on the stream the caller produced a device buffer on
+    int wait_for_caller(void* hip_stream)
+    {
+        if (!caller_ready) HIPCHK(hipEventCreateWithFlags(&caller_ready, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(caller_ready, static_cast<hipStream_t>(hip_stream)));
+        HIPCHK(hipStreamWaitEvent(st, caller_ready, 0));
+        return BBGPU_OK;
+    }
+    poly::ExpandWiresArgs expand_args(const uint64_t* variables, uint64_t* const dst[3]) const
+    {
+        poly::ExpandWiresArgs A{};
+        A.variables = (const uint32_t*)variables;
+        for (int k = 0; k < 3; k++) {
+            A.index[k] = wire_map + (size_t)k * n;
+            A.dst[k] = (uint32_t*)dst[k];
+        }
+        A.n = (uint32_t)n;
+        A.num_variables = (uint32_t)num_variables;
+        return A;
+    }
+    // the witness the handle holds, from any form and place (the descriptor has passed check_witness_desc and, for DEVICE, check_device_pointers)
+    int set_witness_from(const bbgpu_plonk_witness& W)
+    {
+        const uint64_t* hw[3] = { W.w_l, W.w_r, W.w_o };
+        if (W.where == BBGPU_PLONK_WITNESS_DEVICE) RC(wait_for_caller(W.hip_stream));
+        if (W.form == BBGPU_PLONK_WITNESS_WIRES) {
+            if (W.where == BBGPU_PLONK_WITNESS_HOST) return set_witness(W.w_l, W.w_r, W.w_o);
+            for (int k = 0; k < 3; k++) RC(copy(w_lagrange[k], hw[k], n));
+        } else {
+            const uint64_t* src = W.variables;
+            if (W.where == BBGPU_PLONK_WITNESS_HOST) {
+                if (!var_stage) {
+                    HIPCHK(dev_malloc((void**)&var_stage, num_variables * 32));
+                    g_lane_bytes += num_variables * 32;
+                }
+                RC(host_to_device(var_stage, W.variables, num_variables * 32, st));
+                src = var_stage;
+            }
+            RC(poly::expand_wires(expand_args(src, w_lagrange), st));
+        }
+        HIPCHK(hipStreamSynchronize(st)); // the caller's buffers may be reused after this call
         return BBGPU_OK;
     }
 
@@ -896,6 +996,7 @@ class PlonkProver {
             if (g) (void)dev_free(g);
             g = nullptr;
         }
+        release_lane_vars();
         if (lane_slots) (void)dev_free(lane_slots);
         lane_slots = nullptr;
         g_lane_bytes -= lane_bytes();
@@ -1021,7 +1122,46 @@ class PlonkProver {
         return v;
     }
 
-    int construct_proof_batch(int count, const uint64_t* const* hwl, const uint64_t* const* hwr, const uint64_t* const* hwo, uint64_t* proofs_out)
+    // Round 0 of a batch: lane l's Lagrange-form wires (G_WLAG) from witness l in whatever form and place it comes.  Expanded host wires are three uploads
+    // per lane, as ever; expanded device wires three device copies; variables one upload per lane (none from device memory: the expansion reads the
+    // caller's buffer) and ONE expansion launch for all such lanes.  The caller's buffers are last read by work enqueued here, and every entry that
+    // calls this synchronises `st` before it returns.
+    int load_lanes(int L, const bbgpu_plonk_witness* W)
+    {
+        bool host_variables = false;
+        for (int l = 0; l < L; l++) {
+            host_variables |= W[l].form == BBGPU_PLONK_WITNESS_VARIABLES && W[l].where == BBGPU_PLONK_WITNESS_HOST;
+            if (W[l].where == BBGPU_PLONK_WITNESS_DEVICE && (l == 0 || W[l - 1].where != BBGPU_PLONK_WITNESS_DEVICE || W[l - 1].hip_stream != W[l].hip_stream))
+                RC(wait_for_caller(W[l].hip_stream));
+        }
+        if (host_variables && !lane_vars) { // grows with the lanes (ensure_lanes releases it with them), sized for every lane the handle has
+            const size_t bytes = (size_t)lanes_cap * num_variables * 32;
+            HIPCHK(dev_malloc((void**)&lane_vars, bytes));
+            lane_vars_bytes = bytes;
+            g_lane_bytes += bytes;
+        }
+        std::vector<poly::ExpandWiresArgs> ex;
+        for (int l = 0; l < L; l++) {
+            const uint64_t* hw[3] = { W[l].w_l, W[l].w_r, W[l].w_o };
+            if (W[l].form == BBGPU_PLONK_WITNESS_WIRES) {
+                for (int k = 0; k < 3; k++)
+                    RC(W[l].where == BBGPU_PLONK_WITNESS_HOST ? host_to_device(lv(G_WLAG, l, k), hw[k], n * 32, st) : copy(lv(G_WLAG, l, k), hw[k], n));
+                continue;
+            }
+            const uint64_t* src = W[l].variables;
+            if (W[l].where == BBGPU_PLONK_WITNESS_HOST) {
+                uint64_t* stage = lane_vars + (size_t)l * num_variables * 4;
+                RC(host_to_device(stage, W[l].variables, num_variables * 32, st));
+                src = stage;
+            }
+            uint64_t* const dst[3] = { lv(G_WLAG, l, 0), lv(G_WLAG, l, 1), lv(G_WLAG, l, 2) };
+            ex.push_back(expand_args(src, dst));
+        }
+        if (!ex.empty()) RC(poly::expand_wires_lanes(lane_tab, ex.data(), (int)ex.size(), st));
+        return BBGPU_OK;
+    }
+
+    int construct_proof_batch(int count, const bbgpu_plonk_witness* W, uint64_t* proofs_out)
     {
         batch_timing[0] = batch_timing[1] = batch_timing[2] = 0;
         RC(prepare_circuit());
@@ -1036,10 +1176,7 @@ class PlonkProver {
         uint64_t(*out)[8] = reinterpret_cast<uint64_t(*)[8]>(pts.data());
 
         // ---- round 1: wires (prover.cpp:124-133, :65-86)
-        for (int l = 0; l < L; l++) {
-            const uint64_t* hw[3] = { hwl[l], hwr[l], hwo[l] };
-            for (int k = 0; k < 3; k++) RC(host_to_device(lv(G_WLAG, l, k), hw[k], n * 32, st));
-        }
+        RC(load_lanes(L, W));
         if (witness_check) RC(check_enqueue(L)); // opt-in: beside the inverse transforms, the verdict before the first commitment is issued
         RC(copy(lv(G_W, 0), lv(G_WLAG, 0), (size_t)3 * L * n));
         RC(bbgpu_ntt_device_batch(lv(G_W, 0), n, n, 3 * L, BBGPU_IFFT, nullptr, st));
@@ -1348,15 +1485,12 @@ class PlonkProver {
         return BBGPU_OK;
     }
     // the check alone over `count` witnesses, uploaded into the lanes a batch proof of the same count would use
-    int check_witness_batch(int count, const uint64_t* const* hwl, const uint64_t* const* hwr, const uint64_t* const* hwo, bbgpu_plonk_witness_report* out)
+    int check_witness_batch(int count, const bbgpu_plonk_witness* W, bbgpu_plonk_witness_report* out)
     {
         RC(prepare_circuit()); // (ensure_lanes derives the lanes' shared sigma coefficients from it)
         RC(ensure_lanes(count));
         lane_tab.reset();
-        for (int l = 0; l < count; l++) {
-            const uint64_t* hw[3] = { hwl[l], hwr[l], hwo[l] };
-            for (int k = 0; k < 3; k++) RC(host_to_device(lv(G_WLAG, l, k), hw[k], n * 32, st));
-        }
+        RC(load_lanes(count, W));
         RC(check_enqueue(count));
         RC(check_finish(count, false));
         memcpy(out, reports, sizeof(bbgpu_plonk_witness_report) * (size_t)count);
@@ -1368,6 +1502,14 @@ constexpr int PlonkProver::lane_group_vectors[PlonkProver::G_COUNT];
 std::mutex g_pmu;
 std::vector<PlonkProver*> g_provers;
 
+int check_batch_size(const PlonkProver* p, int count)
+{
+    if ((size_t)count * p->n > ((size_t)1 << 22)) {
+        set_error("count %d x n %zu: a batch holds at most 2^22 gates in all (6 GiB of per-lane state)", count, p->n);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
 // argument checks of the batch entry that need no device: the caller's arrays and the size bound
 int check_batch_args(const PlonkProver* p, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o, const void* out,
                      const char* out_name = "proofs_out")
@@ -1385,11 +1527,117 @@ int check_batch_args(const PlonkProver* p, int count, const uint64_t* const* w_l
             set_error("null entry: %s[%d]", !w_l[j] ? "w_l" : !w_r[j] ? "w_r" : "w_o", j);
             return BBGPU_ERR_ARG;
         }
-    if (p && (size_t)count * p->n > ((size_t)1 << 22)) {
-        set_error("count %d x n %zu: a batch holds at most 2^22 gates in all (6 GiB of per-lane state)", count, p->n);
-        return BBGPU_ERR_SIZE;
+    return p ? check_batch_size(p, count) : BBGPU_OK;
+}
+
+// the same for witness descriptors (bbgpu_plonk_witness): `lane` < 0 names the single descriptor of bbgpu_plonk_prover_set_witness_from
+int check_witness_desc(const bbgpu_plonk_witness* w, int lane)
+{
+    char who[32] = "witness";
+    if (lane >= 0) snprintf(who, sizeof who, "witness[%d]", lane);
+    if (w->form != BBGPU_PLONK_WITNESS_WIRES && w->form != BBGPU_PLONK_WITNESS_VARIABLES) {
+        set_error("%s: unknown form %d", who, w->form);
+        return BBGPU_ERR_ARG;
+    }
+    if (w->where != BBGPU_PLONK_WITNESS_HOST && w->where != BBGPU_PLONK_WITNESS_DEVICE) {
+        set_error("%s: unknown where %d", who, w->where);
+        return BBGPU_ERR_ARG;
+    }
+    if (w->form == BBGPU_PLONK_WITNESS_WIRES && (!w->w_l || !w->w_r || !w->w_o)) {
+        set_error("%s: null pointer: %s", who, !w->w_l ? "w_l" : !w->w_r ? "w_r" : "w_o");
+        return BBGPU_ERR_ARG;
+    }
+    if (w->form == BBGPU_PLONK_WITNESS_VARIABLES && !w->variables) {
+        set_error("%s: null pointer: variables", who);
+        return BBGPU_ERR_ARG;
     }
     return BBGPU_OK;
+}
+int check_witness_descs(int count, const bbgpu_plonk_witness* w, const void* out, const char* out_name)
+{
+    if (count < 1 || count > BBGPU_PLONK_MAX_BATCH) {
+        set_error("count %d: a batch holds 1..%d proofs", count, BBGPU_PLONK_MAX_BATCH);
+        return BBGPU_ERR_ARG;
+    }
+    if (!w || !out) {
+        set_error("null array: %s", !w ? "witness descriptors" : out_name);
+        return BBGPU_ERR_ARG;
+    }
+    for (int j = 0; j < count; j++)
+        if (int rc = check_witness_desc(w + j, j)) return rc;
+    return BBGPU_OK;
+}
+// what a descriptor asks of the handle: a wire map for the VARIABLES form
+int check_witness_state(const PlonkProver* p, int count, const bbgpu_plonk_witness* w)
+{
+    for (int j = 0; j < count; j++)
+        if (w[j].form == BBGPU_PLONK_WITNESS_VARIABLES && !p->wire_map) {
+            set_error("witness in VARIABLES form, but the prover has no wire map: bbgpu_plonk_prover_set_wire_map first");
+            return BBGPU_ERR_STATE;
+        }
+    return BBGPU_OK;
+}
+// A DEVICE pointer is dereferenced by a kernel: with XNACK off a pointer the device cannot reach faults the card, so everything but device memory of
+// the calling thread's current device (context 0's, after bind_calling_thread) is refused here, before anything is enqueued.
+int check_device_range(const void* ptr, size_t bytes, const char* who, const char* name)
+{
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, ptr) != hipSuccess) {
+        (void)hipGetLastError(); // (or the next launch check would report it)
+        set_error("%s: %s = %p is not memory the HIP runtime knows: where = DEVICE takes device memory", who, name, ptr);
+        return BBGPU_ERR_ARG;
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != dev) {
+        set_error("%s: %s = %p is %s, not device memory of device %d (the prover's)", who, name, ptr,
+                  a.type == hipMemoryTypeDevice ? "memory of another device" : a.type == hipMemoryTypeHost ? "host memory" : "not plain device memory", dev);
+        return BBGPU_ERR_ARG;
+    }
+    if ((uintptr_t)ptr & 15u) {
+        set_error("%s: %s = %p is not 16-byte aligned", who, name, ptr);
+        return BBGPU_ERR_ARG;
+    }
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: %s = %p: the HIP runtime cannot tell the extent of its allocation, so the vector cannot be shown to lie inside it", who, name, ptr);
+        return BBGPU_ERR_ARG;
+    }
+    if ((const char*)ptr + bytes > (const char*)base + size) {
+        set_error("%s: %s = %p + %zu bytes runs past the end of its allocation (%p + %zu)", who, name, ptr, bytes, base, size);
+        return BBGPU_ERR_ARG;
+    }
+    return BBGPU_OK;
+}
+int check_device_pointers(const PlonkProver* p, int count, const bbgpu_plonk_witness* w, bool single = false)
+{
+    for (int j = 0; j < count; j++) {
+        if (w[j].where != BBGPU_PLONK_WITNESS_DEVICE) continue;
+        char who[32] = "witness";
+        if (!single) snprintf(who, sizeof who, "witness[%d]", j);
+        if (w[j].form == BBGPU_PLONK_WITNESS_VARIABLES) {
+            RC(check_device_range(w[j].variables, p->num_variables * 32, who, "variables"));
+        } else {
+            RC(check_device_range(w[j].w_l, p->n * 32, who, "w_l"));
+            RC(check_device_range(w[j].w_r, p->n * 32, who, "w_r"));
+            RC(check_device_range(w[j].w_o, p->n * 32, who, "w_o"));
+        }
+    }
+    return BBGPU_OK;
+}
+// the descriptors of the host-array entries
+void wires_on_host(int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o, bbgpu_plonk_witness* out)
+{
+    for (int j = 0; j < count; j++) {
+        out[j] = bbgpu_plonk_witness{};
+        out[j].form = BBGPU_PLONK_WITNESS_WIRES;
+        out[j].where = BBGPU_PLONK_WITNESS_HOST;
+        out[j].w_l = w_l[j];
+        out[j].w_r = w_r[j];
+        out[j].w_o = w_o[j];
+    }
 }
 
 PlonkProver* get(int h)
@@ -1498,8 +1746,90 @@ int bbgpu_plonk_construct_proof_batch(int prover, int count, const uint64_t* con
     if (!p) return BBGPU_ERR_ARG;
     if (int rc = check_batch_args(p, count, w_l, w_r, w_o, proofs_out)) return rc;
     if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
-    const int rc = p->construct_proof_batch(count, w_l, w_r, w_o, proofs_out);
+    bbgpu_plonk_witness W[BBGPU_PLONK_MAX_BATCH];
+    wires_on_host(count, w_l, w_r, w_o, W);
+    const int rc = p->construct_proof_batch(count, W, proofs_out);
     if (rc) (void)hipStreamSynchronize(p->st); // nothing of a failed batch is still running when the caller sees the error
+    return rc;
+}
+
+int bbgpu_plonk_prover_set_wire_map(int prover, const uint32_t* w_l_index, const uint32_t* w_r_index, const uint32_t* w_o_index, size_t num_variables)
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    // everything that can be refused without a device is refused before one is bound
+    if (!w_l_index || !w_r_index || !w_o_index) {
+        set_error("null array: %s", !w_l_index ? "w_l_index" : !w_r_index ? "w_r_index" : "w_o_index");
+        return BBGPU_ERR_ARG;
+    }
+    if (num_variables == 0) {
+        set_error("num_variables 0: a wire map references at least one variable");
+        return BBGPU_ERR_SIZE;
+    }
+    PlonkProver* p = get(prover);
+    if (!p) return BBGPU_ERR_ARG;
+    if (num_variables > 4 * p->n) {
+        set_error("num_variables %zu: at most 4 n = %zu (a map of n = %zu gates references at most 3 n variables)", num_variables, 4 * p->n, p->n);
+        return BBGPU_ERR_SIZE;
+    }
+    const uint32_t* const idx[3] = { w_l_index, w_r_index, w_o_index };
+    static const char* const names[3] = { "w_l_index", "w_r_index", "w_o_index" };
+    for (int k = 0; k < 3; k++)
+        for (size_t i = 0; i < p->n; i++)
+            if (idx[k][i] >= num_variables) {
+                set_error("%s[%zu] = %u is not below num_variables %zu", names[k], i, idx[k][i], num_variables);
+                return BBGPU_ERR_ARG;
+            }
+    if (int rcb = bind_calling_thread()) return rcb; // the copies below are enqueued from THIS thread
+    return p->set_wire_map(idx, num_variables);
+}
+
+int bbgpu_plonk_prover_set_witness_from(int prover, const bbgpu_plonk_witness* w)
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    if (!w) {
+        set_error("null witness descriptor");
+        return BBGPU_ERR_ARG;
+    }
+    if (int rc = check_witness_desc(w, -1)) return rc;
+    PlonkProver* p = get(prover);
+    if (!p) return BBGPU_ERR_ARG;
+    if (int rc = check_witness_state(p, 1, w)) return rc;
+    if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
+    if (int rc = check_device_pointers(p, 1, w, true)) return rc;
+    const int rc = p->set_witness_from(*w);
+    if (rc) (void)hipStreamSynchronize(p->st); // the caller's buffers are no longer read when it sees the error
+    return rc;
+}
+
+int bbgpu_plonk_construct_proof_batch_from(int prover, int count, const bbgpu_plonk_witness* w, uint64_t* proofs_out)
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    // everything that can be refused without a device is refused before one is bound
+    if (int rc = check_witness_descs(count, w, proofs_out, "proofs_out")) return rc;
+    PlonkProver* p = get(prover);
+    if (!p) return BBGPU_ERR_ARG;
+    if (int rc = check_batch_size(p, count)) return rc;
+    if (int rc = check_witness_state(p, count, w)) return rc;
+    if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
+    if (int rc = check_device_pointers(p, count, w)) return rc;
+    const int rc = p->construct_proof_batch(count, w, proofs_out);
+    if (rc) (void)hipStreamSynchronize(p->st); // nothing of a failed batch is still running when the caller sees the error
+    return rc;
+}
+
+int bbgpu_plonk_check_witness_batch_from(int prover, int count, const bbgpu_plonk_witness* w, bbgpu_plonk_witness_report* out)
+{
+    std::lock_guard<std::mutex> lk(g_pmu);
+    // everything that can be refused without a device is refused before one is bound
+    if (int rc = check_witness_descs(count, w, out, "out")) return rc;
+    PlonkProver* p = get(prover);
+    if (!p) return BBGPU_ERR_ARG;
+    if (int rc = check_batch_size(p, count)) return rc;
+    if (int rc = check_witness_state(p, count, w)) return rc;
+    if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
+    if (int rc = check_device_pointers(p, count, w)) return rc;
+    const int rc = p->check_witness_batch(count, w, out);
+    if (rc) (void)hipStreamSynchronize(p->st); // the caller's buffers are no longer read when it sees the error
     return rc;
 }
 
@@ -1524,7 +1854,9 @@ int bbgpu_plonk_check_witness_batch(int prover, int count, const uint64_t* const
     if (!p) return BBGPU_ERR_ARG;
     if (int rc = check_batch_args(p, count, w_l, w_r, w_o, out, "out")) return rc;
     if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
-    const int rc = p->check_witness_batch(count, w_l, w_r, w_o, out);
+    bbgpu_plonk_witness W[BBGPU_PLONK_MAX_BATCH];
+    wires_on_host(count, w_l, w_r, w_o, W);
+    const int rc = p->check_witness_batch(count, W, out);
     if (rc) (void)hipStreamSynchronize(p->st); // the caller's arrays are no longer read when it sees the error
     return rc;
 }

@@ -103,6 +103,18 @@ struct LaneTable;
 int check_witness(WitnessCheckArgs A, hipStream_t st);
 int check_witness_lanes(LaneTable& T, const WitnessCheckArgs* A, int lanes, hipStream_t st);
 
+// ---- wires from composer variables (bbgpu_plonk_prover_set_wire_map, the VARIABLES form of bbgpu_plonk_witness) ---------------------------------------------
+// dst[k][i] = variables[index[k][i]], k = w_l, w_r, w_o: the loop of Composer::preprocess() (standard_composer.cpp:205-209) on the device, bit for bit.
+// Every index is below num_variables: bbgpu_plonk_prover_set_wire_map refuses a map that is not, on the host, before it is uploaded.
+struct ExpandWiresArgs {
+    const uint32_t* variables;  // num_variables x 8 words, 16-byte aligned
+    const uint32_t* index[3];   // n entries each
+    uint32_t* dst[3];           // n x 8 words each
+    uint32_t n, num_variables;
+};
+int expand_wires(ExpandWiresArgs A, hipStream_t st);
+int expand_wires_lanes(LaneTable& T, const ExpandWiresArgs* A, int lanes, hipStream_t st); // one launch for the three wires of all lanes
+
 struct EvalJob {
     const uint64_t* coeffs;
     size_t n;

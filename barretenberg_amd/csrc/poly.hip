@@ -811,6 +811,25 @@ template <bool U> __device__ __forceinline__ void check_copies_body(const Witnes
 __global__ void __launch_bounds__(PT) k_check_copies(WitnessCheckArgs A) { check_copies_body<false>(A); }
 __global__ void __launch_bounds__(PT) k_check_copies_lanes(const WitnessCheckArgs* __restrict__ tab) { check_copies_body<true>(tab[blockIdx.y]); } // one table record per lane
 
+// Wires from composer variables: element e of the 3n wire cells (wire-major) is variables[index[e]], copied bit for bit -- no reduction, the wires path
+// uploads whatever representative the caller gave.  Two adjacent lanes per element, 16 bytes each: a wave reads 32 consecutive indices (each by both
+// lanes of its pair: one 128-byte request), gathers 32 rows of 32 bytes -- the gather k_check_copies does, out of a vector that sits in L2 / the Infinity
+// Cache (2 MiB per lane at 2^16 gates) -- and stores 1 KiB contiguously.  Plain vector loads and stores, nothing else.
+__device__ __forceinline__ void expand_wires_body(const ExpandWiresArgs& A) // (one body for both kernels: it reads no cst<U>() constant)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, e = t >> 1, half = t & 1u;
+    if (e >= 3u * A.n) return;
+    const uint32_t k = e / A.n, i = e - k * A.n;
+    const uint32_t* __restrict__ index = k == 2 ? A.index[2] : k == 1 ? A.index[1] : A.index[0];
+    uint32_t* __restrict__ dst = k == 2 ? A.dst[2] : k == 1 ? A.dst[1] : A.dst[0];
+    // a defensive clamp: bbgpu_plonk_prover_set_wire_map refused every index >= num_variables on the host, so on an intact map it changes nothing; a map
+    // corrupted afterwards gives a wrong value (the witness check or the verifier sees it), not a read outside the variables
+    const uint32_t v = min(index[i], A.num_variables - 1u);
+    reinterpret_cast<uint4*>(dst + (size_t)i * 8)[half] = reinterpret_cast<const uint4*>(A.variables + (size_t)v * 8)[half];
+}
+__global__ void __launch_bounds__(PT) k_expand_wires(ExpandWiresArgs A) { expand_wires_body(A); }
+__global__ void __launch_bounds__(PT) k_expand_wires_lanes(const ExpandWiresArgs* __restrict__ tab) { expand_wires_body(tab[blockIdx.y]); } // one table record per lane
+
 // polynomial_arithmetic.cpp:478-560: c[i] *= (x_i - w_n^-1) / ((x_i)^n - 1),  x_i = g w_N^i;  (x_i)^n - 1 takes k = N/n values
 __global__ void __launch_bounds__(PT) k_divide_vanishing(uint32_t* __restrict__ c, uint32_t N, uint32_t k, PowTab root, Limbs9 g_m261, Limbs9 step_m261,
                                                        Limbs9 wninv_m261, Limbs9 inv0, Limbs9 inv1, Limbs9 inv2, Limbs9 inv3)
@@ -1404,6 +1423,12 @@ int check_witness(WitnessCheckArgs A, hipStream_t st)
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
+int expand_wires(ExpandWiresArgs A, hipStream_t st)
+{
+    k_expand_wires<<<pw_blocks((size_t)6 * A.n), PT, 0, st>>>(A); // two lanes per element, 3n elements
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
 
 // g^n for n = 2^log2n
 static host::Fr coset_gen_pow_n(int log2n)
@@ -1635,6 +1660,14 @@ int check_witness_lanes(LaneTable& T, const WitnessCheckArgs* A, int lanes, hipS
     k_check_gates_lanes<<<grid, PT, 0, st>>>(dev);
     HIPCHK(launch_check());
     k_check_copies_lanes<<<grid, PT, 0, st>>>(dev);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+int expand_wires_lanes(LaneTable& T, const ExpandWiresArgs* A, int lanes, hipStream_t st)
+{
+    const ExpandWiresArgs* dev = nullptr;
+    if (int rc = table_records(T, A, lanes, &dev, st, [](ExpandWiresArgs&, int) {})) return rc;
+    k_expand_wires_lanes<<<dim3(pw_blocks((size_t)6 * A[0].n), lanes), PT, 0, st>>>(dev);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }

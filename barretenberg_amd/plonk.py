@@ -105,6 +105,24 @@ class StandardComposer:
             "q_o": to_montgomery_limbs(sel[3]), "q_c": to_montgomery_limbs(sel[4]),
         }
 
+    def _padded_wires(self):
+        """-> (w_l, w_r, w_o index lists, variables) exactly as this composer's preprocess() pads them: here the zero variable appended,
+        new_n the power of two >= n + 1, padding rows pointing at it"""
+        n = self.n
+        log2_n = (n + 1).bit_length() - 1
+        if (1 << log2_n) != n + 1:
+            log2_n += 1
+        pad = (1 << log2_n) - n
+        zero_idx = len(self.variables)
+        return [w + [zero_idx] * pad for w in (self.w_l, self.w_r, self.w_o)], self.variables + [0]
+
+    def wire_map(self):
+        """what Prover.set_wire_map / set_variables take: (w_l_index, w_r_index, w_o_index, variables_limbs) with
+        variables_limbs[w_x_index] == preprocess()["w_x"] -- the loop of standard_composer.cpp:205-209 left to the GPU.  The indices are a
+        property of the circuit; only variables_limbs changes from witness to witness."""
+        cols, variables = self._padded_wires()
+        return tuple(np.array(c, dtype=np.uint32) for c in cols) + (to_montgomery_limbs(variables),)
+
 
 class BoolComposer(StandardComposer):
     """waffle::BoolComposer (composer/bool_composer.hpp:8-46, bool_composer.cpp:13-143): boolean constraints are not gates of their
@@ -151,6 +169,14 @@ class BoolComposer(StandardComposer):
             "q_o": to_montgomery_limbs(sel[3]), "q_c": to_montgomery_limbs(sel[4]),
             "q_bl": to_montgomery_limbs(qb[0]), "q_br": to_montgomery_limbs(qb[1]), "q_bo": to_montgomery_limbs(qb[2]),
         }
+
+    def _padded_wires(self):  # bool_composer.cpp:100-115: the composer's own zero variable pads, none is appended
+        n = self.n
+        log2_n = (n + 1).bit_length() - 1
+        if (1 << log2_n) != n + 1:
+            log2_n += 1
+        pad = (1 << log2_n) - n
+        return [w + [self.zero_idx] * pad for w in (self.w_l, self.w_r, self.w_o)], list(self.variables)
 
 
 class MiMCComposer(StandardComposer):
@@ -206,14 +232,17 @@ class MiMCComposer(StandardComposer):
         self.wire_epicycles[self.zero_idx].append((self.n, RIGHT))
         self.n += 1
 
-    # mimc_composer.cpp:170-250
-    def preprocess(self):
-        if self.current_output_wire != NO_WITNESS:  # close the chain: only the output wire of this gate is constrained
+    def _close_chain(self):  # mimc_composer.cpp:170-185: a pending output wire gets a gate of its own, where only that wire is constrained
+        if self.current_output_wire != NO_WITNESS:
             self.w_o.append(self.current_output_wire); self.w_l.append(self.zero_idx); self.w_r.append(self.zero_idx)
             self._zero_selectors(0, 0)
             self.wire_epicycles[self.current_output_wire].append((self.n, OUTPUT))
             self.n += 1
             self.current_output_wire = NO_WITNESS
+
+    # mimc_composer.cpp:170-250
+    def preprocess(self):
+        self._close_chain()
         n = self.n
         log2_n = n.bit_length() - 1
         if (1 << log2_n) != n:
@@ -237,6 +266,15 @@ class MiMCComposer(StandardComposer):
             "q_o": to_montgomery_limbs(sel[3]), "q_c": to_montgomery_limbs(sel[4]),
             "q_mimc_selector": to_montgomery_limbs(sel[5]), "q_mimc_coefficient": to_montgomery_limbs(sel[6]),
         }
+
+    def _padded_wires(self):  # mimc_composer.cpp:170-200: closes the chain as preprocess() does (whichever is called first), n itself is rounded up
+        self._close_chain()
+        n = self.n
+        log2_n = n.bit_length() - 1
+        if (1 << log2_n) != n:
+            log2_n += 1
+        pad = (1 << log2_n) - n
+        return [c + [self.zero_idx] * pad for c in (self.w_l, self.w_r, self.w_o)], list(self.variables)
 
 
 def mimc_circuit(num_gates, x0, k):
@@ -404,6 +442,33 @@ def host_check_witness(state, lib=None):
     return rep.as_dict()
 
 
+def variables_from_wires(w_l, w_r, w_o):
+    """any expanded witness -> ((w_l_index, w_r_index, w_o_index), variables): the distinct 32-byte rows of the three wire vectors are the
+    variables, every cell the index of its row.  For states that come without a composer (tests/golden/plonk_extended_state.npz); a composer's
+    own wire_map() keeps the composer's numbering instead."""
+    cols = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4) for a in (w_l, w_r, w_o)]
+    n = cols[0].shape[0]
+    variables, inverse = np.unique(np.concatenate(cols), axis=0, return_inverse=True)
+    inverse = np.asarray(inverse).reshape(-1).astype(np.uint32)
+    return tuple(inverse[k * n:(k + 1) * n].copy() for k in range(3)), np.ascontiguousarray(variables)
+
+
+def _witness_array(a, words):
+    """one array of a witness item -> (pointer, on the device?, stream, what keeps it alive): numpy arrays and CPU tensors go as host memory,
+    CUDA tensors (uint64, or int64 viewed as such) as their data_ptr() with the current torch stream"""
+    if hasattr(a, "data_ptr") and hasattr(a, "is_cuda"):  # a torch.Tensor
+        import torch
+        assert a.dtype in (torch.int64, torch.uint64), "tensors hold 64-bit limbs (uint64, or int64 viewed as such)"
+        if a.is_cuda:
+            a = a.contiguous()
+            assert a.numel() == words, "expected %d limbs, got %d" % (words, a.numel())
+            return a.data_ptr(), True, torch.cuda.current_stream(a.device).cuda_stream, a
+        a = (a.view(torch.int64) if a.dtype != torch.int64 else a).numpy().view(np.uint64)
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    assert a.size == words, "expected %d limbs, got %d" % (words, a.size)
+    return a.ctypes.data, False, None, a
+
+
 class Prover:
     """waffle::Prover over the C ABI: Prover(gpu, circuit_state, srs_handle).construct_proof()"""
 
@@ -487,6 +552,82 @@ class Prover:
         L.bbgpu_plonk_construct_proof_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk_witness(L.bbgpu_plonk_construct_proof_batch(self.handle, count, cols[0], cols[1], cols[2], out.ctypes.data), count)
         return out
+
+    # ---- witnesses as composer variables, from host or device memory (bbgpu_plonk_prover_set_wire_map, bbgpu_plonk_witness) ----
+    def set_wire_map(self, w_l_index, w_r_index, w_o_index, num_variables):
+        """the circuit's wire -> variable indices (StandardComposer.wire_map()[:3], or variables_from_wires): once per prover; a witness is then
+        its variables, (num_variables, 4) uint64"""
+        idx = [np.ascontiguousarray(a, dtype=np.uint32) for a in (w_l_index, w_r_index, w_o_index)]
+        assert all(a.size == self.n for a in idx), "each index array has n entries"
+        f = self.gpu.lib.bbgpu_plonk_prover_set_wire_map
+        f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        self.gpu._chk(f(self.handle, idx[0].ctypes.data, idx[1].ctypes.data, idx[2].ctypes.data, int(num_variables)))
+        self.num_variables = int(num_variables)
+
+    def _describe(self, item):
+        """a witness item -> (PlonkWitness, what keeps its memory alive): (w_l, w_r, w_o) or one variables array; numpy arrays, CPU tensors
+        (host) or CUDA tensors (device, current torch stream)"""
+        from .bbgpu import PlonkWitness
+        d = PlonkWitness()
+        if isinstance(item, (tuple, list)):
+            assert len(item) == 3, "an expanded witness is (w_l, w_r, w_o)"
+            got = [_witness_array(a, self.n * 4) for a in item]
+            assert len({g[1] for g in got}) == 1, "w_l, w_r and w_o of one witness live in one place"
+            d.form, (d.w_l, d.w_r, d.w_o) = PlonkWitness.WIRES, [g[0] for g in got]
+        else:
+            nv = getattr(self, "num_variables", None)
+            if nv is None:  # the library answers (BBGPU_ERR_STATE); only the size is unknown here
+                nv = (item.numel() if hasattr(item, "numel") else np.asarray(item).size) // 4
+            got = [_witness_array(item, nv * 4)]
+            d.form, d.variables = PlonkWitness.VARIABLES, got[0][0]
+        d.where = PlonkWitness.DEVICE if got[0][1] else PlonkWitness.HOST
+        d.hip_stream = got[0][2]
+        return d, [g[3] for g in got]
+
+    def _describe_all(self, items):
+        from .bbgpu import PlonkWitness
+        pairs = [self._describe(it) for it in items]
+        descs = (PlonkWitness * max(len(pairs), 1))(*[p[0] for p in pairs])
+        return descs, [p[1] for p in pairs]
+
+    def set_witness_from(self, item):
+        """bbgpu_plonk_prover_set_witness_from: the witness the prover holds, from (w_l, w_r, w_o) or a variables array, numpy or torch"""
+        from .bbgpu import PlonkWitness
+        d, keep = self._describe(item)
+        f = self.gpu.lib.bbgpu_plonk_prover_set_witness_from
+        f.argtypes = [C.c_int, C.POINTER(PlonkWitness)]
+        self.gpu._chk(f(self.handle, C.byref(d)))
+        del keep
+
+    def set_variables(self, v):
+        """set_witness for a witness given as its composer variables (needs set_wire_map)"""
+        assert not isinstance(v, (tuple, list)), "one (num_variables, 4) array"
+        self.set_witness_from(v)
+
+    def construct_proofs_from(self, items):
+        """construct_proofs for witnesses in any form and place, mixed freely: each item is (w_l, w_r, w_o) or one variables array, each array
+        numpy / a CPU tensor (host) or a CUDA tensor (device memory, ordered behind the current torch stream) -> (count, 120) uint64"""
+        from .bbgpu import PlonkWitness
+        descs, keep = self._describe_all(items)
+        out = np.zeros((len(items), 120), dtype=np.uint64)
+        f = self.gpu.lib.bbgpu_plonk_construct_proof_batch_from
+        f.argtypes = [C.c_int, C.c_int, C.POINTER(PlonkWitness), C.c_void_p]
+        self._chk_witness(f(self.handle, len(items), descs, out.ctypes.data), len(items))
+        del keep
+        return out
+
+    def check_witnesses_from(self, items, raw=False):
+        """check_witnesses for witnesses in any form and place (see construct_proofs_from) -> one report dict per lane"""
+        from .bbgpu import PlonkWitness, WitnessReport
+        descs, keep = self._describe_all(items)
+        count = len(items)
+        reps = (WitnessReport * max(count, 1))()
+        f = self.gpu.lib.bbgpu_plonk_check_witness_batch_from
+        f.argtypes = [C.c_int, C.c_int, C.POINTER(PlonkWitness), C.POINTER(WitnessReport)]
+        self.gpu._chk(f(self.handle, count, descs, reps))
+        del keep
+        out = [reps[j].as_dict() for j in range(count)]
+        return (out, bytes(reps)[:40 * count]) if raw else out
 
     def batch_challenges(self, lane):
         """challenges() of lane `lane` of the last construct_proofs call"""

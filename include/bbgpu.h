@@ -431,6 +431,43 @@ int bbgpu_plonk_check_witness_batch(int prover, int count, const uint64_t* const
  * that was not before. */
 int bbgpu_plonk_set_witness_check(int prover, int enabled);
 int bbgpu_plonk_last_witness_report(int prover, int lane, bbgpu_plonk_witness_report* out); /* of the last checked proof call or check entry */
+/* ---- witnesses as composer variables, from host or device memory --------------------------------------------------
+ * The entries above take a witness as three expanded wire vectors in host memory.  Those exist only after Composer::preprocess() has run the loop
+ * output_state.w_l[i] = variables[w_l[i]] (standard_composer.cpp:205-209; the bool, MiMC and extended composers have the same loop), and two thirds of
+ * their bytes are repeats: the circuit -- selectors, mappings AND the wire -> variable indices -- is the same for every witness, only the composer's
+ * `variables` differ.  With a wire map on the handle a witness is its variables, and the loop runs on the GPU, one launch for all lanes.
+ * bbgpu_plonk_prover_set_wire_map: the indices the composer holds (ComposerBase::w_l / w_r / w_o after preprocess() padded them with zero_idx), n
+ * entries each, every entry < num_variables.  A property of the circuit: set once per handle (a second call replaces the map).
+ * BBGPU_ERR_ARG: a null array; an index >= num_variables (the message names the wire and the first such row: checked here, once, on the host, so that
+ * no kernel ever reads outside the variables).  BBGPU_ERR_SIZE: num_variables 0 or > 4 n (a map references at most 3 n variables; the slack is for
+ * variables no gate uses, e.g. after assert_equal; the bound sizes the per-lane staging).  All of that comes before the library binds a device. */
+int bbgpu_plonk_prover_set_wire_map(int prover, const uint32_t* w_l_index, const uint32_t* w_r_index, const uint32_t* w_o_index, size_t num_variables);
+enum { BBGPU_PLONK_WITNESS_WIRES = 0, BBGPU_PLONK_WITNESS_VARIABLES = 1 }; /* form  */
+enum { BBGPU_PLONK_WITNESS_HOST = 0, BBGPU_PLONK_WITNESS_DEVICE = 1 };     /* where */
+typedef struct {
+    int form, where;
+    const uint64_t *w_l, *w_r, *w_o; /* WIRES: n x 4 limbs each (as bbgpu_plonk_prover_set_witness) */
+    const uint64_t* variables;       /* VARIABLES: num_variables x 4 limbs, Montgomery, any representative below 2^256 (copied bit for bit) */
+    void* hip_stream;                /* DEVICE: the stream the data was produced on (NULL = the legacy default stream) */
+} bbgpu_plonk_witness;
+/* The three witness-taking entries for a witness in any form and place; lanes of one batch may mix them.  WIRES / HOST is exactly the path of the entries
+ * above (the same uploads, launches and bytes); every other kind yields, byte for byte, the proof / report of the expanded wires.  Everything else --
+ * bbgpu_plonk_set_witness_check, _last_witness_report, _batch_challenges, _last_batch_timing, count <= BBGPU_PLONK_MAX_BATCH, count * n <= 2^22 -- applies
+ * unchanged.  BBGPU_ERR_ARG: a null descriptor, a null pointer the form needs, an unknown form or where (refused before a device is bound);
+ * BBGPU_ERR_STATE: VARIABLES on a handle without a wire map.
+ * DEVICE pointers are dereferenced by kernels, and with XNACK off a pointer the device cannot reach faults the card: each is looked up in the runtime
+ * before anything is enqueued and must be 16-byte aligned device memory of the prover's device (context 0's) that holds the whole vector, else
+ * BBGPU_ERR_ARG.  "Holds the whole vector" is judged against the runtime's allocation (hipMemGetAddressRange; a pointer whose allocation the runtime
+ * cannot bound is refused): a sub-allocation of a caching allocator -- a tensor shorter than the vector inside a larger block -- passes, its length is
+ * the caller's to get right.  The library records an event on hip_stream and lets the prover's stream wait for it, so hip_stream must be a live stream
+ * of the prover's device (NULL = the legacy default stream); it is not validated, a stale handle or a stream of another device is the runtime's error
+ * (BBGPU_ERR_HIP), reported after the pointer checks.  The buffers are only read, and may be reused when the call returns.  Host variables cross once per lane (num_variables x 32 bytes against 3 n x 32 of wires), device variables not at all.
+ * The device copy of the map (3 n x 4 bytes), the variables staging of the single entry and, for the batches, one more lane group of
+ * count x num_variables x 32 bytes -- it grows with the lanes and goes with them -- are counted in bbgpu_memory_info.staging_bytes and released with
+ * the handle.  After a failure the handle stays usable and no MSM ticket is outstanding. */
+int bbgpu_plonk_prover_set_witness_from(int prover, const bbgpu_plonk_witness* w);
+int bbgpu_plonk_construct_proof_batch_from(int prover, int count, const bbgpu_plonk_witness* w /* count */, uint64_t* proofs_out);
+int bbgpu_plonk_check_witness_batch_from(int prover, int count, const bbgpu_plonk_witness* w /* count */, bbgpu_plonk_witness_report* out /* count */);
 int bbgpu_plonk_prover_destroy(int prover);
 /* challenge.hpp:64-112 recomputed from a finished proof: gamma, beta, alpha, z (4 limbs each).  Host only, no GPU needed. */
 int bbgpu_plonk_challenges_from_proof(const uint64_t proof[BBGPU_PLONK_PROOF_WORDS], uint64_t out[16]);
