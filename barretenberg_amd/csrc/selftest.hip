@@ -134,6 +134,39 @@ __device__ void st_xyzz(uint64_t* o, const Xyzz& p)
     for (int i = 0; i < 16; i++) o[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
 }
 
+// The bucket accumulation's operand as msm_accumulate_kernel has it: a table row packed by store_affine_m261 and read back -- sign applied on the
+// packed words -- by load_affine_m261_signed.  q: affine x, y in limbs 0-7, limb 8 != 0 <=> negative digit.
+__device__ __forceinline__ void ld_signed_row(Fe<Fq, 1, 1>& px, Fe<Fq, 1, 2>& py, const uint64_t* q)
+{
+    uint32_t w[16];
+    store_affine_m261(w, m256_to_m261<Fq>(ld<Fq>(q)), m256_to_m261<Fq>(ld<Fq>(q + 4)));
+    load_affine_m261_signed(px, py, w, q[8] != 0);
+}
+// One trip of msm_accumulate_kernel's loop on (acc, acc_inf), without the bucket boundary: the entry starts a sum where the flag says infinity,
+// otherwise it goes through madd_ip -- the same two one-sided branches, kept apart the same way.
+__device__ __forceinline__ void accumulate_step(Xyzz& acc, bool& acc_inf, const Fe<Fq, 1, 1>& px, const Fe<Fq, 1, 2>& py)
+{
+    const bool start = acc_inf;
+    if (start) {
+        acc.x = px;
+        acc.y = py;
+        acc.zz = fe_one<Fq>();
+        acc.zzz = fe_one<Fq>();
+        acc_inf = false;
+    }
+    asm volatile("" ::: "memory");
+    if (!start) madd_ip(acc, acc_inf, px, py);
+}
+// the flag and the accumulator must say the same, or the case cannot pass: all-ones is no field element
+__device__ void st_xyzz_flagged(uint64_t* o, const Xyzz& p, bool acc_inf)
+{
+    if (acc_inf != is_infinity(p)) {
+        for (int i = 0; i < 16; i++) o[i] = ~0ull;
+        return;
+    }
+    st_xyzz(o, p);
+}
+
 // p_in: n x 12 limbs (Jacobian), q_in: n x 12 limbs (Jacobian; the mixed addition reads only its affine x, y)
 __global__ void selftest_g1_kernel(const uint64_t* p_in, const uint64_t* q_in, uint64_t* out, int n, int op)
 {
@@ -165,9 +198,46 @@ __global__ void selftest_g1_kernel(const uint64_t* p_in, const uint64_t* q_in, u
         dbl_affine(R, a);
         break;
     }
+    case BBGPU_SELFTEST_G1_MADD_IP: { // the accumulation's own addition: signed packed row, start branch or madd_ip, infinity as a flag
+        Fe<Fq, 1, 1> px;
+        Fe<Fq, 1, 2> py;
+        ld_signed_row(px, py, q_in + 12 * i);
+        R = P;
+        bool acc_inf = is_infinity(P);
+        accumulate_step(R, acc_inf, px, py);
+        st_xyzz_flagged(out + 16 * i, R, acc_inf);
+        return;
+    }
     default: set_infinity(R);
     }
     st_xyzz(out + 16 * i, R);
+}
+
+// Lane i folds count_i signed operands of the ring q[begin_i .. end_i), from q[start_i] on and wrapping, from an infinite start, as one chunk of the
+// accumulation does; (start, count, begin, end) are limbs 0-3 of p row i.  Every lane of a wave can be given a sequence of its own, so that at
+// one trip some lanes start, some add, some double and some cancel; lanes that are handed the same ring and start move in step, and only
+// their counts differ.  A description out of range (end > n, begin >= end, start outside the ring, count > 4096) gives all-ones.
+__global__ void selftest_g1_chain_kernel(const uint64_t* p_in, const uint64_t* q_in, uint64_t* out, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t start = p_in[12 * i], count = p_in[12 * i + 1], begin = p_in[12 * i + 2], end = p_in[12 * i + 3];
+    if (end > (uint64_t)n || begin >= end || start < begin || start >= end || count > 4096) {
+        for (int k = 0; k < 16; k++) out[16 * i + k] = ~0ull;
+        return;
+    }
+    Xyzz acc;
+    set_infinity(acc);
+    bool acc_inf = true;
+    uint32_t at = (uint32_t)start;
+    for (uint32_t k = 0; k < (uint32_t)count; k++) {
+        Fe<Fq, 1, 1> px;
+        Fe<Fq, 1, 2> py;
+        ld_signed_row(px, py, q_in + 12 * (size_t)at);
+        accumulate_step(acc, acc_inf, px, py);
+        at = at + 1 == (uint32_t)end ? (uint32_t)begin : at + 1;
+    }
+    st_xyzz_flagged(out + 16 * i, acc, acc_inf);
 }
 
 // the quad addition of g1_quad.hpp: four lanes per case, lane l holding coordinate l of both operands
@@ -232,12 +302,14 @@ int bbgpu_selftest_field(int field, int op, const uint64_t* a, const uint64_t* b
 int bbgpu_selftest_g1(int op, const uint64_t* p, const uint64_t* q, size_t n, uint64_t* out)
 {
     if (!p || !q || !out || n == 0 || n > (1u << 20)) return BBGPU_ERR_ARG;
+    if (op == BBGPU_SELFTEST_G1_MADD_IP_CHAIN && n > 4096) return BBGPU_ERR_ARG; // up to 4096 additions per lane
     if (bbgpu_device_count() == 0) {
         set_error("no HIP device available: libbbgpu has no CPU fallback");
         return BBGPU_ERR_HIP;
     }
     return run(p, n * 96, q, n * 96, out, n * 128, (int)n, [&](uint64_t* dp, uint64_t* dq, uint64_t* dout) {
         if (op == BBGPU_SELFTEST_G1_QUAD_ADD) selftest_g1_quad_kernel<<<(int)((4 * n + 63) / 64), 64>>>(dp, dq, dout, (int)n);
+        else if (op == BBGPU_SELFTEST_G1_MADD_IP_CHAIN) selftest_g1_chain_kernel<<<(int)((n + 63) / 64), 64>>>(dp, dq, dout, (int)n);
         else selftest_g1_kernel<<<(int)((n + 63) / 64), 64>>>(dp, dq, dout, (int)n, op);
     });
 }

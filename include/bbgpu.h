@@ -516,7 +516,13 @@ enum {
     BBGPU_SELFTEST_G1_DBL = 2,       /* 2 p                                                        g1::dbl, :153-217 */
     BBGPU_SELFTEST_G1_DBL_AFFINE = 3,/* 2 p for an affine p (the P + P branch of the mixed addition) */
     BBGPU_SELFTEST_G1_MADD_NEG = 4,  /* p - (q.x, q.y): the conditionally negated operand the bucket accumulation feeds (group_impl_asm.tcc:71-153) */
-    BBGPU_SELFTEST_G1_QUAD_ADD = 5   /* p + q by the four-lanes-per-point addition of the bucket reduction (csrc/g1_quad.hpp) */
+    BBGPU_SELFTEST_G1_QUAD_ADD = 5,  /* p + q by the four-lanes-per-point addition of the bucket reduction (csrc/g1_quad.hpp) */
+    BBGPU_SELFTEST_G1_MADD_IP = 6,   /* p +- (q.x, q.y) as ONE TRIP of the bucket accumulation does it: q limb 8 != 0 = negative digit; the operand packed as a
+                                        table row and read back signed, the start branch for an infinite p, else madd_ip with infinity as a flag.  A flag that
+                                        disagrees with the accumulator afterwards gives all-ones in the 16 output limbs */
+    BBGPU_SELFTEST_G1_MADD_IP_CHAIN = 7 /* out[i] = sum of count_i signed operands of the ring q[begin_i .. end_i) from q[start_i] on, wrapping, folded that way from
+                                        an infinite start; p row i carries start_i, count_i, begin_i, end_i in limbs 0-3 (n <= 4096, count <= 4096, end <= n; out
+                                        of range: all-ones).  The caller gives each lane of a wave a sequence of its own, or the same one with different counts */
 };
 /* field: 0 = fq, 1 = fr; a, b, out: n x 4 limbs */
 int bbgpu_selftest_field(int field, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);

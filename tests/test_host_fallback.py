@@ -70,6 +70,46 @@ def test_host_msm_vs_oracle(lib, oracle, srs, n):
     assert int(lib.host_msm(sc, same_t, 64)[7]) >> 63 == 1
 
 
+@pytest.fixture(scope="module")
+def colliding(oracle):
+    from tests.colliding import Tables
+    return Tables(oracle, 4096)
+
+
+@pytest.mark.parametrize("n", [25, 1000, 4096])
+@pytest.mark.parametrize("xname", ["one", "minus_one", "root4", "root8", "two"])
+def test_host_msm_colliding_tables(lib, oracle, colliding, xname, n):
+    """the bucket method of the host code over tables P_i = x^i G that hold one, two, four or eight distinct points (or G, 2G, 4G, ...), six scalar
+    mixes each (tests/colliding.py): equal and opposite points meet in every bucket, whole sums cancel.  Expected: (sum s_i x^i) G, no bucket
+    method involved; the endomorphism table and the plain one"""
+    from oracle.pyoracle import FQ
+    from tests.colliding import MIXES, same_point
+    pts, table = colliding.points(xname)
+    one = oracle.const(FQ, "one")
+    for mix in MIXES:
+        sc, want = colliding.case(xname, mix, n)
+        assert same_point(lib.host_msm(sc, table, n), want, one), (xname, mix, n)
+        assert same_point(lib.host_msm(sc, pts, n, plain=True), want, one), (xname, mix, n, "plain")
+
+
+@pytest.mark.parametrize("n", [25, 1000, 4096])
+def test_host_msm_runs_of_a_point_and_its_negative(lib, oracle, n):
+    """h copies of G followed by n - h copies of -G under one scalar: runs of equal points and of their negatives in one bucket per window;
+    h = n / 2 ends at infinity.  Expected: (2 h - n) s G"""
+    from oracle.pyoracle import FQ
+    from tests.colliding import R, closed_form_point, same_point, to_limbs
+    G = oracle.g1_one_affine()
+    NG = G.copy()
+    NG[4:8] = oracle.neg(FQ, G[4:8])
+    s = to_int(oracle.random_scalars(0xC0111DE5 + n, 1)[0])
+    sc = to_limbs([s] * n)
+    for h in (n // 2, n // 2 - 5):
+        pts = aligned_copy(np.concatenate([np.tile(G, (h, 1)), np.tile(NG, (n - h, 1))]))
+        want = closed_form_point(oracle, (2 * h - n) * s % R)
+        assert same_point(lib.host_msm(sc, oracle.point_table(pts), n), want, oracle.const(FQ, "one")), (n, h)
+        assert same_point(lib.host_msm(sc, pts, n, plain=True), want, oracle.const(FQ, "one")), (n, h, "plain")
+
+
 def test_host_ntt_reference_fixtures(lib, oracle, golden):
     """outputs of the reference itself: n = 2 .. 16 in full, SHA-256 digests + samples at 2^8 .. 2^16, all seven entry points"""
     g = golden("ntt.json")

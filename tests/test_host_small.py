@@ -82,6 +82,26 @@ def test_host_msm_batched_and_skew(lib, oracle, small_srs):
     assert int(lib.pippenger(aligned_copy(sc[:2]), same_t, 2)[7]) >> 63 == 1
 
 
+@pytest.fixture(scope="module")
+def colliding(oracle):
+    from tests.colliding import Tables
+    return Tables(oracle, 32)
+
+
+@pytest.mark.parametrize("xname", ["one", "minus_one", "root4", "root8", "two"])
+def test_host_msm_colliding_tables(lib, oracle, colliding, xname):
+    """the tiny-size host path (n <= 24, the shipped threshold) over tables P_i = x^i G of one, two, four or eight distinct points (or G, 2G, 4G,
+    ...), six scalar mixes each (tests/colliding.py), against (sum s_i x^i) G: P + P, P - P and sums that cancel altogether"""
+    from tests.colliding import MIXES, same_point
+    pts, table = colliding.points(xname)
+    one = oracle.const(FQ, "one")
+    for n in (2, 3, 9, 16, 24):
+        for mix in MIXES:
+            sc, want = colliding.case(xname, mix, n)
+            assert same_point(lib.pippenger(sc, table, n), want, one), (xname, mix, n)
+            assert same_point(lib.pippenger_low_memory(sc, pts, n), want, one), (xname, mix, n, "plain")
+
+
 def test_host_ntt_reference_fixtures(lib, golden):
     """outputs of the reference itself for n = 2 .. 16, all seven entry points (tests/golden/ntt.json)"""
     g = golden("ntt.json")

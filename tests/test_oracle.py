@@ -218,6 +218,33 @@ def test_msm_vs_naive(oracle, msm_inputs):
     assert np.array_equal(oracle.g1_normalize(acc), oracle.msm_affine(scalars, table, n))
 
 
+@pytest.fixture(scope="module")
+def colliding(oracle):
+    from tests.colliding import Tables
+    return Tables(oracle, 4096)
+
+
+@pytest.mark.parametrize("xname", ["one", "minus_one", "root4", "root8", "two"])
+def test_golden_msm_colliding_tables(oracle, golden, colliding, xname):
+    """tests/golden/msm_colliding.json (tools/gen_golden.py): what the REFERENCE's pippenger() returns over tables of one, two, four or eight
+    distinct points and over G, 2G, 4G, ... under the mixes of tests/colliding.py.  Both checkers the other tests lean on are pinned to it: the
+    closed form (sum s_i x^i) G and the oracle's Pippenger (Tables.case asserts that the two agree)"""
+    from tests.colliding import MIXES, seed_of, x_plain
+    cases = [c for c in golden("msm_colliding.json")["cases"] if c["x"] == xname]
+    sizes = {c["n"] for c in cases}
+    assert {(c["n"], c["mix"]) for c in cases} == {(n, m) for n in sizes for m in MIXES} and len(sizes) >= 8 and max(sizes) == 4096
+    seen_inf = 0
+    for c in cases:
+        assert int(c["seed"], 16) == seed_of(xname, c["mix"], c["n"]) and int(c["x_plain"], 16) == x_plain(oracle, xname)
+        sc, want = colliding.case(xname, c["mix"], c["n"])
+        if c.get("infinity"):
+            assert int(want[7]) >> 63 == 1 and not want[:7].any(), c
+            seen_inf += 1
+        else:
+            assert np.array_equal(want[0:4], limbs(c["px"])) and np.array_equal(want[4:8], limbs(c["py"])), c
+    assert seen_inf >= len(sizes)  # at least the zero_sum mix of every n
+
+
 def test_golden_ntt_small(oracle, golden):
     g = golden("ntt.json")
     const = limbs(g["constant"])

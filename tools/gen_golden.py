@@ -2,9 +2,12 @@
 """Generate tests/golden/*.json from the REFERENCE itself (oracle/_ref/libbbref.so = the reference's own
 scalar_multiplication.cpp / polynomial_arithmetic.cpp / evaluation_domain.cpp compiled in place, x86-64 asm path).
 
-Run in the build container (needs /root/reference):   python tools/gen_golden.py [--big]
+Run in the build container (needs /root/reference):   python tools/gen_golden.py [--big | --colliding-only]
 Inputs are deterministic (splitmix64 streams) so the fixtures hold only seeds + expected outputs
-(or SHA-256 digests + sampled elements for large vectors).  `--big` adds the 2^20 MSM and 2^20 / 2^22 NTT cases.
+(or SHA-256 digests + sampled elements for large vectors).  `--big` adds the 2^20 MSM and 2^20 / 2^22 NTT cases; `--colliding-only`
+writes msm_colliding.json (MSMs over tables of colliding points) and leaves the rest alone.  That fixture's INPUTS are built by
+tests/colliding.py, the module the tests build theirs with, so that both sides cannot drift apart; what the fixture pins is the reference's
+OUTPUT for them, which no code of this repository computes.
 """
 import argparse
 import hashlib
@@ -58,12 +61,47 @@ def noncanonical_fast(coeffs):
     return out
 
 
+COLLIDING_SIZES = (25, 200, 1000, 1023, 1024, 1025, 2051, 4096)
+
+
+def colliding(O, R):
+    """tests/golden/msm_colliding.json: the reference's pippenger() over tables P_i = x^i G that hold few distinct points (x = 1, -1, a 4th and an
+    8th root of unity) or powers of two of one point (x = 2), under the scalar mixes of tests/colliding.py -- inputs the other fixtures only
+    have at n = 32.  Results only: x, n, mix, seed and the normalised point or the infinity flag."""
+    from tests.colliding import MIXES, XS, Tables, raw_scalars, seed_of, to_limbs, x_plain
+    T = Tables(O, max(COLLIDING_SIZES))
+    cases = []
+    for xname in XS:
+        x = x_plain(O, xname)
+        srs, table = T.points(xname)
+        assert np.array_equal(R.point_table(srs), table)
+        for n in COLLIDING_SIZES:
+            for mix in MIXES:
+                seed = seed_of(xname, mix, n)
+                sc = to_limbs(raw_scalars(O, mix, n, x, seed))
+                out = R.pippenger(sc, table, n, 0)
+                case = {"x": xname, "x_plain": "0x%x" % x, "n": n, "mix": mix, "seed": "0x%x" % seed}
+                if int(out[7]) >> 63:
+                    case["infinity"] = True
+                else:
+                    out = O.g1_normalize(out)
+                    case["px"], case["py"] = hx(out[0:4]), hx(out[4:8])
+                cases.append(case)
+    json.dump({"source": "reference scalar_multiplication.cpp pippenger() via oracle/_ref; inputs by tests/colliding.py", "cases": cases},
+              open(os.path.join(GOLD, "msm_colliding.json"), "w"), indent=0)
+    print("msm_colliding.json: %d cases, %d at infinity" % (len(cases), sum("infinity" in c for c in cases)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true")
+    ap.add_argument("--colliding-only", action="store_true", help="write tests/golden/msm_colliding.json and leave the other fixtures as they are")
     args = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     O, R = Oracle(), Ref(True)
+    if args.colliding_only:
+        colliding(O, R)
+        return
     rng_state = [0xA5A5A5A5DEADBEEF]
 
     def rnd256(bits=256):
@@ -193,6 +231,7 @@ def main():
     outs = R.batched_msm(jobs, [table[:8192]] * 3)
     msm["batched_3x4096"] = [{"offset": o, "x": hx(v[0:4]), "y": hx(v[4:8]), "z": hx(v[8:12])} for o, v in zip((0, 4096, 8192), outs)]
     json.dump(msm, open(os.path.join(GOLD, "msm.json"), "w"), indent=0)
+    colliding(O, R)
 
     # ---------------- NTT --------------------------------------------------------------------------------------------
     const = O.random_scalars(CONST_SEED, 1)[0]
