@@ -1,5 +1,5 @@
 // host_plonk_check.hpp -- does a witness satisfy the circuit?  The definition of include/bbgpu.h (bbgpu_plonk_check_witness) on the host, behind
-// bbgpu_host_plonk_check_witness: for a caller without a GPU, and the statement the GPU kernels (poly.hip k_check_gates / k_check_copies) are compared with.
+// bbgpu_host_plonk_check_witness: for a caller without a GPU, and the statement the GPU kernels (poly.hip k_check_gates_lanes / k_check_copies_lanes) are compared with.
 // Like host_fallback.hpp: the library's own host field code (host_fr.hpp), a few host threads above 2^15 rows, no HIP call, no lock, no state.
 //
 // Rows 0 .. n-2 only: the proof system divides by the pseudo vanishing polynomial (polynomial_arithmetic.cpp:478-560) and the grand product stops at

@@ -1,11 +1,18 @@
 // plonk.hip -- the PLONK prover rounds with every polynomial resident in HBM (BASELINE config 5).
 //
 // Restates waffle::Prover::construct_proof (src/barretenberg/waffle/proof_system/prover/prover.cpp:661-670) for the
-// standard arithmetic circuit (widgets/arithmetic_widget.cpp): the member functions below carry the reference's names and
-// cite the lines they follow.  The reference moves every polynomial across the boundary for each of its 26 transforms and
+// standard arithmetic circuit (widgets/arithmetic_widget.cpp) and its optional widgets: the rounds below cite the lines they
+// follow.  The reference moves every polynomial across the boundary for each of its 26 transforms and
 // 9 commitments; here the witness and circuit polynomials are uploaded once, all NTTs (ntt.hip), MSMs (msm.hip) and the
 // O(n) loops in between (poly.hip) run on the device, and only 32-byte evaluations and 96-byte commitments come back --
 // they have to, because the Fiat-Shamir challenges (challenge.hpp:64-135, Keccak-256 on the host) depend on them.
+//
+// There is ONE prover: PlonkProver::prove() advances the five rounds in lockstep over the lanes of a lane set.  A single proof
+// (bbgpu_plonk_construct_proof) is that engine over the handle's own lane, whose wires are the witness the handle holds; a
+// batch (bbgpu_plonk_construct_proof_batch*) is the same engine over the batch lanes, loaded from the caller's witnesses first.
+// Witness loading (load_lanes) and the witness check (check_enqueue / check_finish) address the current set in the same way.
+// Either kind of call flushes its kernels' table records through h2d_async and reads its result slots through d2h_async, so
+// both pass the h2d / d2h fault funnels (bbgpu_fault_inject).
 //
 // Bit-exactness: every proof element is a canonical field value or a normalised curve point, both unique, and exact
 // arithmetic makes them independent of evaluation order; the proof bytes equal the reference's (tests/golden/plonk_proofs.json).
@@ -72,25 +79,46 @@ struct Challenges {
 
 std::atomic<uint64_t> g_lane_bytes{ 0 }; // device bytes held by the lanes of every prover's batches (bbgpu_memory_stats: staging_bytes)
 
+// The streams of a destroyed prover wait here for the next one (under g_pmu, until plonk_release_all_locked).  Events of the library's shared state --
+// the staging ring's, the transforms' scratch, the MSM slots' -- were last recorded on them, and the runtime reaches through such an event to the stream
+// it was recorded on when the event is waited for (with the streams destroyed per handle: a sporadic "event last recorded in a capturing stream" from
+// hipEventSynchronize, in a process that captures nothing).
+std::vector<hipStream_t> g_idle_streams;
+int take_stream(hipStream_t* s)
+{
+    if (g_idle_streams.empty()) {
+        HIPCHK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    } else {
+        *s = g_idle_streams.back();
+        g_idle_streams.pop_back();
+    }
+    return BBGPU_OK;
+}
+void give_stream(hipStream_t& s)
+{
+    if (s) g_idle_streams.push_back(s);
+    s = nullptr;
+}
+
 class PlonkProver {
   public:
     size_t n = 0;
     int log2n = 0;
     int srs = -1;
     hipStream_t st = nullptr;
-    hipStream_t st_msm = nullptr;   // the commitments' own queue, ordered after `st` by an event instead of a host round trip
+    hipStream_t st_ticket[8] = {};  // the commitments' own queues, one per MSM slot (tickets that share a stream serialise), ordered after `st` by an event
     hipEvent_t scalars_ready = nullptr;
-    poly::Scratch scratch;
+    poly::Scratch scratch;          // scans and evaluations of the lanes, the inversion behind L_1
     std::vector<void*> allocs;
 
-    // inputs (prover.hpp:44-59, arithmetic_widget.hpp:45-49): Lagrange-base values / permutation mappings
-    uint64_t* w_lagrange[3] = {};
+    // inputs (prover.hpp:44-59, arithmetic_widget.hpp:45-49): permutation mappings / Lagrange-base selector values
     uint32_t* sigma_mapping[3] = {};
     uint64_t* q_lagrange[5] = {};
     // circuit- / domain-only state, built on first use
     bool circuit_ready = false;
     uint64_t* roots = nullptr;        // w^i, i < n
     uint64_t* sigma_lagrange[3] = {}; // permutation.hpp:15-87
+    uint64_t* sigma_coeff = nullptr;  // the three sigma polynomials in coefficient form, UNSCALED (prover.cpp:245-247 without the beta: the lanes scale them by theirs)
     uint64_t* q_coeff[5] = {};        // selector polynomials, coefficient form
     uint64_t* q_fft2n[5] = {};        // their coset evaluations on the 2n domain (unscaled)
     uint64_t* l_1 = nullptr;          // L_1 on the 2n coset
@@ -107,26 +135,54 @@ class PlonkProver {
     // optional sequential widget (sequential_widget.hpp): q_o_next
     bool has_seq = false;
     uint64_t *qs_lagrange = nullptr, *qs_coeff = nullptr, *qs_fft2n = nullptr;
-    // per proof
-    uint64_t* w[3] = {};        // wire polynomials, coefficient form          (Prover::w_l, w_r, w_o after :130-132)
-    uint64_t* sigma[3] = {};    // beta * sigma_i, coefficient form             (after :245-247)
-    uint64_t* z = nullptr;      // grand product polynomial, coefficient form   (after :221)
-    uint64_t* w_fft[3] = {};    // 4n coset evaluations                          (circuit_state.w_*_fft)
-    uint64_t* s_fft[3] = {};    // w_i + beta sigma_i + gamma on the 4n coset
-    uint64_t* z_fft = nullptr;  // alpha * Z on the 4n coset
-    uint64_t* quotient_large = nullptr; // 4n
-    uint64_t* quotient_mid = nullptr;   // 2n
-    uint64_t* r = nullptr;              // linearisation polynomial
-    uint64_t* tmp[3] = {};              // n-sized workspaces (num / den / opening polynomials)
-    uint64_t* slots = nullptr;          // 16 x 32 bytes of device results
-    void* h_slots = nullptr;            // pinned mirror
 
+    // ---- lanes ------------------------------------------------------------------------------------------------------------------------------------------
+    // Every proof runs in a LANE: the per-proof vectors, lane-major inside one allocation per group, so that the same polynomial of all lanes of a set is
+    // one strided batch for the transforms and one launch (grid.y = lane) for the kernels of poly.hip.  The handle's OWN set has one lane, made with the
+    // handle: its G_WLAG group is the witness the handle holds, and bbgpu_plonk_construct_proof proves it.  The BATCH set grows with the largest batch
+    // (ensure_lanes) and is counted in g_lane_bytes.  The rounds (prove) and the witness loading and checking address whichever set is current.
+    enum {
+        G_WLAG,  // wires, Lagrange base                                            (Prover::w_l, w_r, w_o before :130-132)
+        G_W,     // wire polynomials, coefficient form                              (after :130-132)
+        G_SIGMA, // beta * sigma_i, coefficient form                                (after :245-247)
+        G_WFFT,  // the wires on the 4n coset                                       (circuit_state.w_*_fft)
+        G_SFFT,  // w_i + beta sigma_i + gamma on the 4n coset
+        G_Z,     // grand product polynomial, coefficient form                      (after :221)
+        G_ZFFT,  // alpha * Z on the 4n coset
+        G_QL,    // quotient_large, 4n
+        G_QM,    // quotient_mid, 2n
+        G_R,     // linearisation polynomial
+        G_TMP,   // workspaces (num / den / opening polynomials)
+        G_COUNT
+    };
+    static constexpr int lane_group_vectors[G_COUNT] = { 3, 3, 3, 12, 12, 1, 4, 4, 2, 1, 3 }; // n-sized vectors per lane: 48 in all
+    struct LaneSet {
+        int count = 0;                 // lanes it has room for
+        uint64_t* group[G_COUNT] = {};
+        uint64_t* slots = nullptr;     // 16 x 32 bytes of device results per lane
+        uint64_t* vars = nullptr;      // where host variables land before the expansion, num_variables x 32 bytes per lane: made on first use, counted in g_lane_bytes
+        size_t vars_bytes = 0;
+    };
+    struct Lane {
+        Challenges ch;
+        Proof proof;
+        Fr t_eval, beta_inv;
+    };
+    LaneSet own, batch;
+    LaneSet* cur = &own;
+    poly::LaneTable lane_tab;
+    void* h_lane_slots = nullptr; // pinned mirror of a set's slots, BBGPU_PLONK_MAX_BATCH lanes
+    std::vector<Lane> lanes;      // the host side of the lanes of the run in progress
+
+    // what the last single proof / the last batch left for the bbgpu_plonk_last_* / bbgpu_plonk_batch_* getters: neither kind of run writes the other's
     Challenges challenges;
-    Proof proof;
     double timing[8] = {}; // total, msm, ntt+pointwise (the rest), first-use preparation
+    Challenges batch_challenges[BBGPU_PLONK_MAX_BATCH] = {};
+    int batch_count = 0;
+    double batch_timing[4] = {};
 
     // witness check (bbgpu_plonk_check_witness*, bbgpu_plonk_set_witness_check): the result records of BBGPU_PLONK_MAX_BATCH lanes -- counts, then the
-    // atomicMin words (poly.h) -- in one small allocation beside `slots` / `lane_slots`, made on the first check; lane 0 serves the single proof
+    // atomicMin words (poly.h) -- in one small allocation, made on the first check
     bool witness_check = false;
     poly::WitnessCheckCounts* check_counts = nullptr;
     poly::WitnessCheckFirst* check_first = nullptr;
@@ -136,16 +192,19 @@ class PlonkProver {
     static constexpr size_t check_bytes = BBGPU_PLONK_MAX_BATCH * (sizeof(poly::WitnessCheckCounts) + sizeof(poly::WitnessCheckFirst));
 
     // witnesses as composer variables (bbgpu_plonk_prover_set_wire_map, the VARIABLES form of bbgpu_plonk_witness): the circuit's wire -> variable indices,
-    // w_l | w_r | w_o in one allocation, and where host variables land before the expansion -- one buffer for the witness the handle holds, one per lane
-    // for the batches (`lane_vars`, beside the lane groups below).  All of it is counted with the lanes (g_lane_bytes) and goes with the handle.
+    // w_l | w_r | w_o in one allocation.  It and the sets' variables staging are counted with the lanes (g_lane_bytes) and go with the handle.
     uint32_t* wire_map = nullptr;
     size_t num_variables = 0;
-    uint64_t* var_stage = nullptr;
-    uint64_t* lane_vars = nullptr;
-    size_t lane_vars_bytes = 0;
     hipEvent_t caller_ready = nullptr; // orders `st` behind the stream a caller produced its device buffers on
 
     ~PlonkProver() { release(); }
+    void release_vars(LaneSet& s)
+    {
+        if (s.vars) (void)dev_free(s.vars);
+        s.vars = nullptr;
+        g_lane_bytes -= s.vars_bytes;
+        s.vars_bytes = 0;
+    }
     void release_wire_map()
     {
         if (wire_map) {
@@ -153,20 +212,9 @@ class PlonkProver {
             g_lane_bytes -= 3 * n * 4;
         }
         wire_map = nullptr;
-        if (var_stage) {
-            (void)dev_free(var_stage);
-            g_lane_bytes -= num_variables * 32;
-        }
-        var_stage = nullptr;
-        release_lane_vars();
+        release_vars(own);
+        release_vars(batch);
         num_variables = 0;
-    }
-    void release_lane_vars()
-    {
-        if (lane_vars) (void)dev_free(lane_vars);
-        lane_vars = nullptr;
-        g_lane_bytes -= lane_vars_bytes;
-        lane_vars_bytes = 0;
     }
     void release()
     {
@@ -175,29 +223,19 @@ class PlonkProver {
         release_wire_map();
         if (caller_ready) (void)hipEventDestroy(caller_ready);
         caller_ready = nullptr;
-        if (sigma_coeff) (void)dev_free(sigma_coeff);
-        sigma_coeff = nullptr;
         lane_tab.release();
-        lane_scratch.release();
         if (h_lane_slots) (void)hipHostFree(h_lane_slots);
         h_lane_slots = nullptr;
-        for (hipStream_t& q : st_ticket) {
-            if (q) (void)hipStreamDestroy(q);
-            q = nullptr;
-        }
-        for (void* p : allocs) (void)dev_free(p);
+        for (hipStream_t& q : st_ticket) give_stream(q);
+        for (void* p : allocs) (void)dev_free(p); // the circuit's state, the own lane, the check records
         allocs.clear();
-        if (h_slots) (void)hipHostFree(h_slots);
-        h_slots = nullptr;
+        own = LaneSet{};
         if (h_check) (void)hipHostFree(h_check);
         h_check = nullptr;
-        check_counts = nullptr; // (in `allocs`)
+        check_counts = nullptr;
         check_first = nullptr;
         scratch.release();
-        if (st) (void)hipStreamDestroy(st);
-        st = nullptr;
-        if (st_msm) (void)hipStreamDestroy(st_msm);
-        st_msm = nullptr;
+        give_stream(st);
         if (scalars_ready) (void)hipEventDestroy(scalars_ready);
         scalars_ready = nullptr;
     }
@@ -213,31 +251,28 @@ class PlonkProver {
         n = c->n;
         log2n = ilog2(n);
         srs = srs_handle;
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&st_msm, hipStreamNonBlocking));
+        RC(take_stream(&st));
+        for (hipStream_t& q : st_ticket) RC(take_stream(&q));
         HIPCHK(hipEventCreateWithFlags(&scalars_ready, hipEventDisableTiming));
         const size_t fb = n * 32;
         const uint64_t* hw[3] = { c->w_l, c->w_r, c->w_o };
         const uint32_t* hm[3] = { c->sigma_1_mapping, c->sigma_2_mapping, c->sigma_3_mapping };
         const uint64_t* hq[5] = { c->q_m, c->q_l, c->q_r, c->q_o, c->q_c };
-        // the three wire / sigma polynomials (and the five selectors) sit back to back so that their transforms run as one
-        // batched launch (bbgpu_ntt_device_batch): at these sizes a single transform leaves most of the chip idle
-        RC(dalloc(&w_lagrange[0], 3 * fb));
+        // the own lane, and what every run needs beside its lanes: nothing of it is made lazily, so that a witness upload allocates its staging only
+        own.count = 1;
+        for (int g = 0; g < G_COUNT; g++) RC(dalloc(&own.group[g], lane_group_vectors[g] * fb));
+        RC(dalloc(&own.slots, 16 * 32));
+        HIPCHK(hipHostMalloc(&h_lane_slots, (size_t)BBGPU_PLONK_MAX_BATCH * 16 * 32));
+        RC(lane_tab.init((size_t)2 << 20));
+        RC(scratch.ensure(std::max(2 * poly::scan_scratch_bytes(n), (size_t)9 * 256 * 32) + 64)); // one lane's two scans / nine evaluations; batches grow it
+        // the three sigma polynomials (and the five selectors) sit back to back so that their transforms run as one batched launch
+        // (bbgpu_ntt_device_batch): at these sizes a single transform leaves most of the chip idle
         RC(dalloc(&sigma_lagrange[0], 3 * fb));
-        RC(dalloc(&w[0], 3 * fb));
-        RC(dalloc(&sigma[0], 3 * fb));
-        RC(dalloc(&w_fft[0], 12 * fb));
-        RC(dalloc(&s_fft[0], 12 * fb));
+        RC(dalloc(&sigma_coeff, 3 * fb));
         for (int k = 0; k < 3; k++) {
-            w_lagrange[k] = w_lagrange[0] + (size_t)k * n * 4;
             sigma_lagrange[k] = sigma_lagrange[0] + (size_t)k * n * 4;
-            w[k] = w[0] + (size_t)k * n * 4;
-            sigma[k] = sigma[0] + (size_t)k * n * 4;
-            w_fft[k] = w_fft[0] + (size_t)k * 4 * n * 4;
-            s_fft[k] = s_fft[0] + (size_t)k * 4 * n * 4;
             RC(dalloc(&sigma_mapping[k], n * 4));
-            RC(dalloc(&tmp[k], fb));
-            RC(host_to_device(w_lagrange[k], hw[k], fb, st));
+            RC(host_to_device(lv(G_WLAG, 0, k), hw[k], fb, st));
             RC(host_to_device(sigma_mapping[k], hm[k], n * 4, st));
         }
         RC(dalloc(&q_lagrange[0], 5 * fb));
@@ -284,21 +319,7 @@ class PlonkProver {
         }
         RC(dalloc(&roots, fb));
         RC(dalloc(&l_1, 2 * fb));
-        RC(dalloc(&z, fb));
-        RC(dalloc(&z_fft, 4 * fb));
-        RC(dalloc(&quotient_large, 4 * fb));
-        RC(dalloc(&quotient_mid, 2 * fb));
-        RC(dalloc(&r, fb));
-        RC(dalloc(&slots, 16 * 32));
-        HIPCHK(hipHostMalloc(&h_slots, 16 * 32));
         HIPCHK(hipStreamSynchronize(st)); // the caller's arrays may go away after this call (uploads above 8 MiB read them asynchronously)
-        return BBGPU_OK;
-    }
-    int set_witness(const uint64_t* wl, const uint64_t* wr, const uint64_t* wo)
-    {
-        const uint64_t* hw[3] = { wl, wr, wo };
-        for (int k = 0; k < 3; k++) RC(host_to_device(w_lagrange[k], hw[k], n * 32, st));
-        HIPCHK(hipStreamSynchronize(st));
         return BBGPU_OK;
     }
 
@@ -346,114 +367,17 @@ class PlonkProver {
     // the witness the handle holds, from any form and place (the descriptor has passed check_witness_desc and, for DEVICE, check_device_pointers)
     int set_witness_from(const bbgpu_plonk_witness& W)
     {
-        const uint64_t* hw[3] = { W.w_l, W.w_r, W.w_o };
-        if (W.where == BBGPU_PLONK_WITNESS_DEVICE) RC(wait_for_caller(W.hip_stream));
-        if (W.form == BBGPU_PLONK_WITNESS_WIRES) {
-            if (W.where == BBGPU_PLONK_WITNESS_HOST) return set_witness(W.w_l, W.w_r, W.w_o);
-            for (int k = 0; k < 3; k++) RC(copy(w_lagrange[k], hw[k], n));
-        } else {
-            const uint64_t* src = W.variables;
-            if (W.where == BBGPU_PLONK_WITNESS_HOST) {
-                if (!var_stage) {
-                    HIPCHK(dev_malloc((void**)&var_stage, num_variables * 32));
-                    g_lane_bytes += num_variables * 32;
-                }
-                RC(host_to_device(var_stage, W.variables, num_variables * 32, st));
-                src = var_stage;
-            }
-            RC(poly::expand_wires(expand_args(src, w_lagrange), st));
-        }
+        use(own);
+        RC(load_lanes(1, &W));
         HIPCHK(hipStreamSynchronize(st)); // the caller's buffers may be reused after this call
         return BBGPU_OK;
     }
 
     // ---- small helpers ----------------------------------------------------------------------------------------------
-    int ntt(uint64_t* d, size_t size, int kind, const Fr* c = nullptr) { return bbgpu_ntt_device(d, size, kind, c ? c->d : nullptr, st); }
-    // `batch` transforms of consecutive polynomials (the contiguous triples / quintuples above)
-    int ntt_batch(uint64_t* d, size_t size, int batch, int kind, const Fr* c = nullptr)
-    {
-        return bbgpu_ntt_device_batch(d, size, size, batch, kind, c ? c->d : nullptr, st);
-    }
     int copy(uint64_t* dst, const uint64_t* src, size_t count)
     {
         HIPCHK(hipMemcpyAsync(dst, src, count * 32, hipMemcpyDeviceToDevice, st));
         return BBGPU_OK;
-    }
-    // commitments of `count` <= 3 resident coefficient vectors of n scalars: one batched pass (bbgpu_msm_g1_device_batch_async);
-    // without window tables on the SRS, side-by-side single MSMs.  Split in two so that work of the NEXT round which does not depend
-    // on this round's challenge can be enqueued on our stream in between: a 2^16-point batch is a ~0.4 ms chain of mostly
-    // latency-bound launches on the MSM's own queues, beside which transforms run almost for free.
-    // Tickets that were issued and never waited on would stay `pending` for the life of the process and turn every later host-pointer MSM
-    // into BBGPU_ERR_STATE: whatever happens between commit_begin and commit_end (a failing transform, a failing second ticket), the
-    // destructor drains what is still outstanding.
-    struct PendingCommit {
-        int count = 0, ticket = -1, tk[3] = { -1, -1, -1 };
-        bool batched = true;
-        double t0 = 0.0;
-        PendingCommit() = default;
-        PendingCommit(const PendingCommit&) = delete;
-        PendingCommit& operator=(const PendingCommit&) = delete;
-        ~PendingCommit() { drain(); }
-        void drain()
-        {
-            uint64_t sink[4 * 12];
-            if (ticket >= 0) (void)bbgpu_msm_g1_batch_wait(ticket, sink);
-            ticket = -1;
-            for (int& t : tk) {
-                if (t >= 0) (void)bbgpu_msm_g1_wait(t, sink);
-                t = -1;
-            }
-        }
-    };
-    int commit_begin(const uint64_t* const* scalars, int count, PendingCommit& P)
-    {
-        P.drain();
-        P.batched = true;
-        P.t0 = now_ms();
-        P.count = count;
-        // the scalars are produced on `st`; the commitments run on their own queue behind an event (no host round trip)
-        HIPCHK(hipEventRecord(scalars_ready, st));
-        HIPCHK(hipStreamWaitEvent(st_msm, scalars_ready, 0));
-        const int bt = bbgpu_msm_g1_device_batch_async(srs, 0, scalars, count, n, st_msm);
-        if (bt >= 0) {
-            P.ticket = bt;
-            return BBGPU_OK;
-        }
-        if (bt != BBGPU_ERR_ARG) return bt;
-        P.batched = false;
-        const int W = bbgpu_srs_num_windows(srs, n);
-        if (W < 0) return W;
-        for (int i = 0; i < count; i++) {
-            const int t = bbgpu_msm_g1_device_async(srs, 0, scalars[i], n, 0, W, st_msm);
-            if (t < 0) return t; // the tickets issued so far are drained by P's destructor
-            P.tk[i] = t;
-        }
-        return BBGPU_OK;
-    }
-    int commit_end(PendingCommit& P, uint64_t (*out)[8])
-    {
-        uint64_t res[4 * 12];
-        if (P.batched) {
-            const int t = P.ticket;
-            P.ticket = -1; // a wait consumes the ticket whatever it returns
-            RC(bbgpu_msm_g1_batch_wait(t, res));
-            for (int i = 0; i < P.count; i++) memcpy(out[i], res + 12 * i, 64); // normalised: x, y canonical
-        } else {
-            for (int i = 0; i < P.count; i++) {
-                const int t = P.tk[i];
-                P.tk[i] = -1;
-                RC(bbgpu_msm_g1_wait(t, res));
-                memcpy(out[i], res, 64);
-            }
-        }
-        timing[1] += now_ms() - P.t0;
-        return BBGPU_OK;
-    }
-    int commit(const uint64_t* const* scalars, int count, uint64_t (*out)[8])
-    {
-        PendingCommit P;
-        RC(commit_begin(scalars, count, P));
-        return commit_end(P, out);
     }
     // challenge.hpp:15-62: commitments / evaluations enter the transcript out of Montgomery form
     static void put_point(std::vector<uint64_t>& buf, const uint64_t p[8])
@@ -477,7 +401,6 @@ class PlonkProver {
         host::hash_field_elements(buf.data(), buf.size() / 4, h.d);
         return host::fr_to_mont(h); // challenge.hpp:70-71: the raw 256-bit digest, reduced by the Montgomery conversion
     }
-    std::vector<uint64_t> transcript_upto(int stage) const { return transcript_of(proof, stage); }
     static std::vector<uint64_t> transcript_of(const Proof& proof, int stage)
     {
         std::vector<uint64_t> b;
@@ -499,10 +422,10 @@ class PlonkProver {
         check_first = reinterpret_cast<poly::WitnessCheckFirst*>(d + BBGPU_PLONK_MAX_BATCH * sizeof(poly::WitnessCheckCounts));
         return BBGPU_OK;
     }
-    poly::WitnessCheckArgs check_args(const uint64_t* wl, const uint64_t* wr, const uint64_t* wo, int lane) const
+    poly::WitnessCheckArgs check_args(int lane) const
     {
         poly::WitnessCheckArgs A{};
-        A.w_l = (const uint32_t*)wl; A.w_r = (const uint32_t*)wr; A.w_o = (const uint32_t*)wo;
+        A.w_l = (const uint32_t*)lv(G_WLAG, lane, 0); A.w_r = (const uint32_t*)lv(G_WLAG, lane, 1); A.w_o = (const uint32_t*)lv(G_WLAG, lane, 2);
         A.q_m = (const uint32_t*)q_lagrange[0]; A.q_l = (const uint32_t*)q_lagrange[1]; A.q_r = (const uint32_t*)q_lagrange[2];
         A.q_o = (const uint32_t*)q_lagrange[3]; A.q_c = (const uint32_t*)q_lagrange[4];
         A.q_on = has_seq ? (const uint32_t*)qs_lagrange : nullptr;
@@ -514,17 +437,13 @@ class PlonkProver {
         A.n = (uint32_t)n;
         return A;
     }
-    // the two kernels over `count` lanes (0: the witness the handle holds, into record 0) and the copy of the records, all on `st`
+    // the two kernels over the first `count` lanes of the current set and the copy of their records, all on `st`
     int check_enqueue(int count)
     {
         RC(ensure_check());
-        if (count == 0) {
-            RC(poly::check_witness(check_args(w_lagrange[0], w_lagrange[1], w_lagrange[2], 0), st));
-        } else {
-            std::vector<poly::WitnessCheckArgs> ca((size_t)count);
-            for (int l = 0; l < count; l++) ca[l] = check_args(lv(G_WLAG, l, 0), lv(G_WLAG, l, 1), lv(G_WLAG, l, 2), l);
-            RC(poly::check_witness_lanes(lane_tab, ca.data(), count, st));
-        }
+        std::vector<poly::WitnessCheckArgs> ca((size_t)count);
+        for (int l = 0; l < count; l++) ca[l] = check_args(l);
+        RC(poly::check_witness_lanes(lane_tab, ca.data(), count, st));
         HIPCHK(d2h_async(h_check, check_counts, check_bytes, st));
         return BBGPU_OK;
     }
@@ -533,10 +452,9 @@ class PlonkProver {
     {
         report_count = 0;
         HIPCHK(hipStreamSynchronize(st));
-        const int L = std::max(count, 1);
         const poly::WitnessCheckCounts* hc = static_cast<const poly::WitnessCheckCounts*>(h_check);
         const poly::WitnessCheckFirst* hf = reinterpret_cast<const poly::WitnessCheckFirst*>(hc + BBGPU_PLONK_MAX_BATCH);
-        for (int l = 0; l < L; l++) {
+        for (int l = 0; l < count; l++) {
             bbgpu_plonk_witness_report R = host::plonk_report_clear();
             R.gate_failures = hc[l].gate_failures;
             R.copy_failures = hc[l].copy_failures;
@@ -552,9 +470,9 @@ class PlonkProver {
             }
             reports[l] = R;
         }
-        report_count = L;
+        report_count = count;
         if (!verdict) return BBGPU_OK;
-        for (int l = 0; l < L; l++) {
+        for (int l = 0; l < count; l++) {
             const bbgpu_plonk_witness_report& R = reports[l];
             if (!R.gate_failures && !R.copy_failures) continue;
             if (R.gate_failures)
@@ -567,11 +485,24 @@ class PlonkProver {
         }
         return BBGPU_OK;
     }
+    // the check alone: over the witness the handle holds ...
     int check_witness(bbgpu_plonk_witness_report* out)
     {
-        RC(check_enqueue(0));
-        RC(check_finish(0, false));
+        use(own);
+        RC(check_enqueue(1));
+        RC(check_finish(1, false));
         *out = reports[0];
+        return BBGPU_OK;
+    }
+    // ... and over `count` witnesses, loaded into the lanes a batch proof of the same count would use
+    int check_witness_batch(int count, const bbgpu_plonk_witness* W, bbgpu_plonk_witness_report* out)
+    {
+        RC(ensure_lanes(count));
+        use(batch);
+        RC(load_lanes(count, W));
+        RC(check_enqueue(count));
+        RC(check_finish(count, false));
+        memcpy(out, reports, sizeof(bbgpu_plonk_witness_report) * (size_t)count);
         return BBGPU_OK;
     }
 
@@ -581,185 +512,42 @@ class PlonkProver {
         if (circuit_ready) return BBGPU_OK;
         const double t0 = now_ms();
         const Fr root = host::fr_root_of_unity(log2n);
+        // `batch` transforms of consecutive polynomials of `size` coefficients (the contiguous groups of init())
+        auto ntts = [&](uint64_t* d, size_t size, int batch, int kind) { return bbgpu_ntt_device_batch(d, size, size, batch, kind, nullptr, st); };
         RC(poly::powers(roots, n, root, host::fr_one(), st));
         for (int k = 0; k < 3; k++) RC(poly::sigma_from_mapping(sigma_lagrange[k], sigma_mapping[k], roots, n, st)); // prover.cpp:663-665
+        RC(copy(sigma_coeff, sigma_lagrange[0], 3 * n)); // prover.cpp:245-247 without the beta
+        RC(ntts(sigma_coeff, n, 3, BBGPU_IFFT));
         // arithmetic_widget.cpp:68-84 without the alpha scaling (applied in quotient_mid)
         RC(copy(q_coeff[0], q_lagrange[0], 5 * n));
-        RC(ntt_batch(q_coeff[0], n, 5, BBGPU_IFFT));
+        RC(ntts(q_coeff[0], n, 5, BBGPU_IFFT));
         for (int k = 0; k < 5; k++) RC(poly::copy_pad(q_fft2n[k], q_coeff[k], n, 2 * n, st));
-        RC(ntt_batch(q_fft2n[0], 2 * n, 5, BBGPU_COSET_FFT));
+        RC(ntts(q_fft2n[0], 2 * n, 5, BBGPU_COSET_FFT));
         if (has_bool) { // bool_widget.cpp:64-74 without the alpha scalings (applied in quotient_bool)
             RC(copy(qb_coeff[0], qb_lagrange[0], 3 * n));
-            RC(ntt_batch(qb_coeff[0], n, 3, BBGPU_IFFT));
+            RC(ntts(qb_coeff[0], n, 3, BBGPU_IFFT));
             for (int k = 0; k < 3; k++) RC(poly::copy_pad(qb_fft2n[k], qb_coeff[k], n, 2 * n, st));
-            RC(ntt_batch(qb_fft2n[0], 2 * n, 3, BBGPU_COSET_FFT));
+            RC(ntts(qb_fft2n[0], 2 * n, 3, BBGPU_COSET_FFT));
         }
         if (has_seq) { // sequential_widget.cpp:49-54 without the alpha scaling (applied in quotient_seq)
             RC(copy(qs_coeff, qs_lagrange, n));
-            RC(ntt(qs_coeff, n, BBGPU_IFFT));
+            RC(ntts(qs_coeff, n, 1, BBGPU_IFFT));
             RC(poly::copy_pad(qs_fft2n, qs_coeff, n, 2 * n, st));
-            RC(ntt(qs_fft2n, 2 * n, BBGPU_COSET_FFT));
+            RC(ntts(qs_fft2n, 2 * n, 1, BBGPU_COSET_FFT));
         }
         if (has_mimc) { // mimc_widget.cpp:60-67 without the alpha scaling (applied in quotient_mimc)
             RC(copy(qm_coeff[0], qm_lagrange[0], 2 * n));
-            RC(ntt_batch(qm_coeff[0], n, 2, BBGPU_IFFT));
+            RC(ntts(qm_coeff[0], n, 2, BBGPU_IFFT));
             for (int k = 0; k < 2; k++) RC(poly::copy_pad(qm_fft4n[k], qm_coeff[k], n, 4 * n, st));
-            RC(ntt_batch(qm_fft4n[0], 4 * n, 2, BBGPU_COSET_FFT));
+            RC(ntts(qm_fft4n[0], 4 * n, 2, BBGPU_COSET_FFT));
         }
-        RC(poly::lagrange_l1_fft(l_1, quotient_mid, log2n, log2n + 1, scratch, st)); // prover.cpp:350-351 (quotient_mid as workspace)
+        RC(poly::lagrange_l1_fft(l_1, own.group[G_QM], log2n, log2n + 1, scratch, st)); // prover.cpp:350-351 (the own lane's quotient_mid as workspace)
         HIPCHK(hipStreamSynchronize(st));
         circuit_ready = true;
         timing[3] = now_ms() - t0;
         return BBGPU_OK;
     }
 
-    // prover.cpp:124-133
-    int compute_wire_coefficients()
-    {
-        RC(copy(w[0], w_lagrange[0], 3 * n));
-        RC(ntt_batch(w[0], n, 3, BBGPU_IFFT));
-        return BBGPU_OK;
-    }
-    // prover.cpp:65-86
-    int compute_wire_commitments()
-    {
-        const uint64_t* sc[3] = { w[0], w[1], w[2] };
-        uint64_t out[3][8];
-        PendingCommit P;
-        RC(commit_begin(sc, 3, P));
-        // beside the commitments: the wires on the 4n coset (prover.cpp:418-425) need no challenge
-        for (int k = 0; k < 3; k++) RC(poly::copy_pad(w_fft[k], w[k], n, 4 * n, st));
-        RC(ntt_batch(w_fft[0], 4 * n, 3, BBGPU_COSET_FFT));
-        RC(commit_end(P, out));
-        memcpy(proof.W_L, out[0], 64);
-        memcpy(proof.W_R, out[1], 64);
-        memcpy(proof.W_O, out[2], 64);
-        std::vector<uint64_t> b = transcript_upto(0);
-        challenges.gamma = challenge(b); // compute_gamma, challenge.hpp:64-73
-        put_fr(b, challenges.gamma);
-        challenges.beta = challenge(b);  // compute_beta, :75-85
-        return BBGPU_OK;
-    }
-    // prover.cpp:135-222: Z(w^m) = prod_{i<m} num_i / den_i.  The six serial accumulator chains (:194-202) and the batch
-    // inversion (:215) become one exclusive prefix-product scan of the numerators, one inclusive suffix-product scan of the
-    // denominators and a single inversion: 1 / prod_{i<m} den_i = (prod_{i>=m} den_i) / prod_i den_i.
-    int compute_z_coefficients()
-    {
-        poly::ZTermsArgs A{};
-        A.w_l = (const uint32_t*)w_lagrange[0]; A.w_r = (const uint32_t*)w_lagrange[1]; A.w_o = (const uint32_t*)w_lagrange[2];
-        A.s1 = (const uint32_t*)sigma_lagrange[0]; A.s2 = (const uint32_t*)sigma_lagrange[1]; A.s3 = (const uint32_t*)sigma_lagrange[2];
-        A.num = (uint32_t*)tmp[0]; A.den = (uint32_t*)tmp[1];
-        A.n = (uint32_t)n;
-        RC(poly::z_terms(A, host::fr_root_of_unity(log2n), challenges.beta, challenges.gamma, st));
-        // PN: exclusive prefix products of num -> tmp[2];  SD: inclusive suffix products of den -> r (free at this point), total -> slot 0
-        poly::ScanJob sj[2] = {};
-        sj[0].in = tmp[0]; sj[0].out = tmp[2]; sj[0].n = n; sj[0].reverse = false; sj[0].inclusive = false;
-        sj[1].in = tmp[1]; sj[1].out = r; sj[1].n = n; sj[1].reverse = true; sj[1].inclusive = true; sj[1].d_total = slots;
-        RC(poly::scan_pair(0, sj, 2, scratch, st));
-        HIPCHK(hipMemcpyAsync(h_slots, slots, 32, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        Fr total;
-        memcpy(total.d, h_slots, 32);
-        RC(poly::mul2c(z, tmp[2], r, n, host::fr_inv(total), st));
-        RC(ntt(z, n, BBGPU_IFFT));
-        return BBGPU_OK;
-    }
-    // prover.cpp:88-105
-    int compute_z_commitment()
-    {
-        const uint64_t* sc[1] = { z };
-        uint64_t out[1][8];
-        PendingCommit P;
-        RC(commit_begin(sc, 1, P));
-        // beside the commitment: the permutation polynomials need beta and gamma only (prover.cpp:245-247, :253-276)
-        RC(copy(sigma[0], sigma_lagrange[0], 3 * n));
-        RC(ntt_batch(sigma[0], n, 3, BBGPU_IFFT_WITH_CONSTANT, &challenges.beta));
-        for (int k = 0; k < 3; k++) RC(poly::sigma_prepare(s_fft[k], sigma[k], w[k], n, 4 * n, challenges.gamma, st));
-        RC(ntt_batch(s_fft[0], 4 * n, 3, BBGPU_COSET_FFT));
-        RC(commit_end(P, out));
-        memcpy(proof.Z_1, out[0], 64);
-        challenges.alpha = challenge(transcript_upto(1)); // compute_alpha, challenge.hpp:87-98
-        return BBGPU_OK;
-    }
-    // prover.cpp:224-300 + :302-341 (fused into one pass over the 4n coset) and :350-402 + arithmetic_widget.cpp:66-104
-    int compute_quotient_numerators()
-    {
-        const size_t n4 = 4 * n, n2 = 2 * n;
-        // w_fft (the wires on the 4n coset) and s_fft (w_i + beta sigma_i + gamma there) were enqueued beside the wire / Z commitments
-        RC(poly::copy_pad(z_fft, z, n, n4, st)); // :440
-        RC(ntt(z_fft, n4, BBGPU_COSET_FFT_WITH_CONSTANT, &challenges.alpha)); // :278
-        poly::QuotLargeArgs L{};
-        L.wl_f = (const uint32_t*)w_fft[0]; L.wr_f = (const uint32_t*)w_fft[1]; L.wo_f = (const uint32_t*)w_fft[2];
-        L.s1_f = (const uint32_t*)s_fft[0]; L.s2_f = (const uint32_t*)s_fft[1]; L.s3_f = (const uint32_t*)s_fft[2];
-        L.z_f = (const uint32_t*)z_fft;
-        L.q = (uint32_t*)quotient_large;
-        L.n4 = (uint32_t)n4;
-        RC(poly::quotient_large(L, host::fr_root_of_unity(log2n + 2), challenges.beta, challenges.gamma, st));
-        // :446-451: alpha_base = alpha^4 (the product with alpha on :447 is discarded by the reference: fr::mul returns by value)
-        const Fr alpha_base = host::fr_sqr(host::fr_sqr(challenges.alpha));
-        poly::QuotMidArgs M{};
-        M.z_f = (const uint32_t*)z_fft;
-        M.wl_f = (const uint32_t*)w_fft[0]; M.wr_f = (const uint32_t*)w_fft[1]; M.wo_f = (const uint32_t*)w_fft[2];
-        M.l1 = (const uint32_t*)l_1;
-        M.qm_f = (const uint32_t*)q_fft2n[0]; M.ql_f = (const uint32_t*)q_fft2n[1]; M.qr_f = (const uint32_t*)q_fft2n[2];
-        M.qo_f = (const uint32_t*)q_fft2n[3]; M.qc_f = (const uint32_t*)q_fft2n[4];
-        M.q = (uint32_t*)quotient_mid;
-        M.n2 = (uint32_t)n2;
-        RC(poly::quotient_mid(M, challenges.alpha, alpha_base, st));
-        if (has_seq) { // sequential_widget.cpp:47-62: old_alpha = (alpha_base * alpha) / alpha = the arithmetic widget's own power; hands alpha_base * alpha on unchanged
-            poly::QuotSeqArgs Sq{};
-            Sq.wo_f = M.wo_f;
-            Sq.qon_f = (const uint32_t*)qs_fft2n;
-            Sq.q = (uint32_t*)quotient_mid;
-            Sq.n2 = (uint32_t)n2;
-            RC(poly::quotient_seq(Sq, alpha_base, st));
-        }
-        if (has_bool) { // the widget chain: the arithmetic widget hands on alpha_base * alpha (arithmetic_widget.cpp:103), the bool widget uses it and the next two powers
-            const Fr a5 = host::fr_mul(alpha_base, challenges.alpha), a6 = host::fr_mul(a5, challenges.alpha), a7 = host::fr_mul(a6, challenges.alpha);
-            poly::QuotBoolArgs Bq{};
-            Bq.wl_f = M.wl_f; Bq.wr_f = M.wr_f; Bq.wo_f = M.wo_f;
-            Bq.qbl_f = (const uint32_t*)qb_fft2n[0]; Bq.qbr_f = (const uint32_t*)qb_fft2n[1]; Bq.qbo_f = (const uint32_t*)qb_fft2n[2];
-            Bq.q = (uint32_t*)quotient_mid;
-            Bq.n2 = (uint32_t)n2;
-            RC(poly::quotient_bool(Bq, a5, a6, a7, st));
-        }
-        if (has_mimc) { // second widget of a MiMCComposer circuit: alpha_base * alpha from the arithmetic widget, alpha_step = alpha
-            poly::QuotMimcArgs Mq{};
-            Mq.wl_f = L.wl_f; Mq.wr_f = L.wr_f; Mq.wo_f = L.wo_f;
-            Mq.qsel_f = (const uint32_t*)qm_fft4n[0]; Mq.qcoef_f = (const uint32_t*)qm_fft4n[1];
-            Mq.q = (uint32_t*)quotient_large;
-            Mq.n4 = (uint32_t)n4;
-            RC(poly::quotient_mimc(Mq, host::fr_mul(alpha_base, challenges.alpha), challenges.alpha, st));
-        }
-        return BBGPU_OK;
-    }
-    // prover.cpp:405-465 (after the wire / Z parts above)
-    int compute_quotient_polynomial()
-    {
-        // (compute_wire_coefficients() has run: construct_proof)
-        RC(compute_wire_commitments());
-        RC(compute_z_coefficients());
-        RC(compute_z_commitment());
-        RC(compute_quotient_numerators());
-        RC(poly::divide_by_pseudo_vanishing(quotient_mid, log2n, log2n + 1, st));   // :453
-        RC(poly::divide_by_pseudo_vanishing(quotient_large, log2n, log2n + 2, st)); // :454
-        RC(ntt(quotient_mid, 2 * n, BBGPU_COSET_IFFT));                             // :457
-        RC(ntt(quotient_large, 4 * n, BBGPU_COSET_IFFT));                           // :458
-        RC(poly::add_inplace(quotient_large, quotient_mid, 2 * n, st));             // :461-463
-        return BBGPU_OK;
-    }
-    // prover.cpp:107-122
-    int compute_quotient_commitment()
-    {
-        const uint64_t* sc[3] = { quotient_large, quotient_large + n * 4, quotient_large + 2 * n * 4 };
-        uint64_t out[3][8];
-        RC(commit(sc, 3, out));
-        memcpy(proof.T_LO, out[0], 64);
-        memcpy(proof.T_MID, out[1], 64);
-        memcpy(proof.T_HI, out[2], 64);
-        challenges.z = challenge(transcript_upto(2)); // compute_evaluation_challenge, challenge.hpp:100-112
-        return BBGPU_OK;
-    }
     // polynomial_arithmetic.cpp:594-626, l_1 only
     Fr lagrange_l1_at(const Fr& zc) const
     {
@@ -767,38 +555,6 @@ class PlonkProver {
         for (int i = 0; i < log2n; i++) zp = host::fr_sqr(zp);
         const Fr numerator = host::fr_mul(host::fr_sub(zp, host::fr_one()), host::fr_inv(host::fr_from_u64((uint64_t)n)));
         return host::fr_mul(numerator, host::fr_inv(host::fr_sub(zc, host::fr_one())));
-    }
-    // prover.cpp:467-538; returns t_eval
-    int compute_linearisation_coefficients(Fr* t_eval)
-    {
-        const Fr& zc = challenges.z;
-        const Fr beta_inv = host::fr_inv(challenges.beta);
-        const Fr shifted_z = host::fr_mul(zc, host::fr_root_of_unity(log2n));
-        // seven evaluations, one read-back (:478-480, :504-506, :512)
-        const Fr zs[2] = { zc, shifted_z };
-        const poly::EvalJob ej[9] = { { w[0], n, 0, slots + 0 * 4 }, { w[1], n, 0, slots + 1 * 4 }, { w[2], n, 0, slots + 2 * 4 },
-                                      { sigma[0], n, 0, slots + 3 * 4 }, { sigma[1], n, 0, slots + 4 * 4 }, { z, n, 1, slots + 5 * 4 },
-                                      { quotient_large, 3 * n, 0, slots + 6 * 4 },
-                                      // MiMC widget: REQUIRES_W_O_SHIFTED (prover.cpp:499-502) and compute_proof_elements (mimc_widget.cpp:92-95)
-                                      { w[2], n, 1, slots + 7 * 4 }, { qm_coeff[1], n, 0, slots + 8 * 4 } };
-        const int nev = has_mimc ? 9 : has_seq ? 8 : 7; // the sequential widget is REQUIRES_W_O_SHIFTED too (sequential_widget.cpp:16)
-        RC(poly::evaluate_batch_to_device(ej, nev, zs, scratch, st));
-        HIPCHK(hipMemcpyAsync(h_slots, slots, (size_t)nev * 32, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        Fr ev[9];
-        memcpy(ev, h_slots, (size_t)nev * 32);
-        take_evaluations(proof, beta_inv, ev, t_eval);
-        const uint64_t* pl[12];
-        Fr cl[12];
-        const int terms = linearisation_terms(proof, challenges, beta_inv, z, sigma[2], pl, cl);
-        poly::LinCombArgs A{};
-        for (int j = 0; j < terms; j++) A.p[j] = (const uint32_t*)pl[j];
-        A.count = terms;
-        A.out = (uint32_t*)r;
-        A.n = (uint32_t)n;
-        RC(poly::lincomb(A, cl, st));
-        RC(poly::evaluate(r, n, zc, &proof.linear_eval, scratch, st)); // :536
-        return BBGPU_OK;
     }
     // the evaluations of one proof, in the order of the jobs above (:478-515)
     void take_evaluations(Proof& proof, const Fr& beta_inv, const Fr ev[9], Fr* t_eval) const
@@ -868,177 +624,71 @@ class PlonkProver {
         put_fr(b, proof.linear_eval); put_fr(b, t_eval);
         return challenge(b);
     }
-    // prover.cpp:540-659
-    int compute_opening_elements()
-    {
-        Fr t_eval;
-        RC(compute_linearisation_coefficients(&t_eval));
-        challenges.nu = nu_challenge(proof, t_eval);
-        Fr nu[8];
-        nu[0] = challenges.nu;
-        for (int i = 1; i < 8; i++) nu[i] = host::fr_mul(nu[i - 1], nu[0]);
-        const Fr beta_inv = host::fr_inv(challenges.beta);
-        const Fr z_pow_n = host::fr_pow(challenges.z, (uint64_t)n), z_pow_2n = host::fr_pow(challenges.z, (uint64_t)2 * n);
-        // :567-595 as one linear combination of nine resident vectors
-        poly::LinCombArgs A{};
-        // with the MiMC or the sequential widget: w_o joins the shifted opening at nu^8 (prover.cpp:627-635) and q_mimc_coefficient the main one at nu^9
-        // (mimc_widget.cpp:115-123)
-        const Fr nu9 = host::fr_mul(nu[7], nu[0]);
-        const uint64_t* ps[10] = { quotient_large, quotient_large + n * 4, quotient_large + 2 * n * 4, r, w[0], w[1], w[2], sigma[0], sigma[1], qm_coeff[1] };
-        const Fr cs[10] = { host::fr_one(), z_pow_n, z_pow_2n, nu[0], nu[1], nu[2], nu[3], host::fr_mul(nu[4], beta_inv), host::fr_mul(nu[5], beta_inv), nu9 };
-        const int oterms = has_mimc ? 10 : 9;
-        for (int j = 0; j < oterms; j++) A.p[j] = (const uint32_t*)ps[j];
-        A.count = oterms;
-        A.out = (uint32_t*)tmp[0];
-        A.n = (uint32_t)n;
-        RC(poly::lincomb(A, cs, st));
-        poly::LinCombArgs B{};
-        B.p[0] = (const uint32_t*)z;
-        B.p[1] = (const uint32_t*)w[2];
-        B.count = (has_mimc || has_seq) ? 2 : 1;
-        B.out = (uint32_t*)tmp[1];
-        B.n = (uint32_t)n;
-        RC(poly::lincomb(B, &nu[6], st)); // nu^7 Z (+ nu^8 w_o)
-        // compute_kate_opening_coefficients (polynomial_arithmetic.cpp:562-591): W_i = sum_{j>i} F_j z^(j-i-1); the serial
-        // recurrence becomes a Horner suffix scan, the remainder F(z) drops out
-        const Fr shifted_z = host::fr_mul(challenges.z, host::fr_root_of_unity(log2n));
-        poly::ScanJob kj[2] = {};
-        kj[0].in = tmp[0]; kj[0].out = tmp[2]; kj[0].n = n; kj[0].reverse = true; kj[0].inclusive = false; kj[0].z = challenges.z;
-        kj[1].in = tmp[1]; kj[1].out = r; kj[1].n = n; kj[1].reverse = true; kj[1].inclusive = false; kj[1].z = shifted_z;
-        RC(poly::scan_pair(1, kj, 2, scratch, st));
-        const uint64_t* sc[2] = { tmp[2], r };
-        uint64_t out[2][8];
-        RC(commit(sc, 2, out)); // :650-658
-        memcpy(proof.PI_Z, out[0], 64);
-        memcpy(proof.PI_Z_OMEGA, out[1], 64);
-        return BBGPU_OK;
-    }
     // waffle::preprocess(prover) (preprocess.hpp:16-55) + ProverArithmeticWidget::compute_preprocessed_commitments
-    // (arithmetic_widget.cpp:128-157): the verification key -- commitments to sigma_1..3 and to q_m, q_l, q_r, q_o, q_c
+    // (arithmetic_widget.cpp:128-157): the verification key -- commitments to sigma_1..3 and to q_m, q_l, q_r, q_o, q_c, then the widgets' selectors
     int preprocess(uint64_t (*out)[8])
     {
         RC(prepare_circuit());
-        // sigma polynomials in coefficient form, unscaled (the proof rounds scale them by beta)
-        RC(copy(tmp[0], sigma_lagrange[0], n));
-        RC(copy(tmp[1], sigma_lagrange[1], n));
-        RC(copy(tmp[2], sigma_lagrange[2], n));
-        for (int k = 0; k < 3; k++) RC(ntt(tmp[k], n, BBGPU_IFFT));
-        const uint64_t* s3[3] = { tmp[0], tmp[1], tmp[2] };
-        RC(commit(s3, 3, out));
-        const uint64_t* q3[3] = { q_coeff[0], q_coeff[1], q_coeff[2] };
-        RC(commit(q3, 3, out + 3));
-        const uint64_t* q2[2] = { q_coeff[3], q_coeff[4] };
-        RC(commit(q2, 2, out + 6));
-        int at = 8;
-        if (has_seq) { // sequential_widget.cpp:79-106, second widget of the ExtendedComposer's chain
-            const uint64_t* qn[1] = { qs_coeff };
-            RC(commit(qn, 1, out + at));
-            at += 1;
-        }
-        if (has_bool) { // bool_widget.cpp:118-152
-            const uint64_t* qb[3] = { qb_coeff[0], qb_coeff[1], qb_coeff[2] };
-            RC(commit(qb, 3, out + at));
-        }
+        PendingMany P;
+        for (int k = 0; k < 3; k++) P.scalars.push_back(sigma_coeff + (size_t)k * n * 4);
+        for (int k = 0; k < 5; k++) P.scalars.push_back(q_coeff[k]);
+        if (has_seq) P.scalars.push_back(qs_coeff); // sequential_widget.cpp:79-106, second widget of the ExtendedComposer's chain
+        if (has_bool)                               // bool_widget.cpp:118-152
+            for (int k = 0; k < 3; k++) P.scalars.push_back(qb_coeff[k]);
         if (has_mimc) { // mimc_widget.cpp:125-160: q_mimc_coefficient first, then q_mimc_selector
-            const uint64_t* qmm[2] = { qm_coeff[1], qm_coeff[0] };
-            RC(commit(qmm, 2, out + 8));
+            P.scalars.push_back(qm_coeff[1]);
+            P.scalars.push_back(qm_coeff[0]);
         }
-        return BBGPU_OK;
-    }
-    // prover.cpp:661-670
-    int construct_proof()
-    {
-        memset(&proof, 0, sizeof proof);
-        timing[0] = timing[1] = timing[2] = 0;
-        RC(prepare_circuit());
-        const double t0 = now_ms();
-        // opt-in: the check kernels run beside the wires' inverse transform, and their verdict is in before the first commitment is issued
-        if (witness_check) RC(check_enqueue(0));
-        RC(compute_wire_coefficients());
-        if (witness_check) RC(check_finish(0, true));
-        RC(compute_quotient_polynomial());
-        RC(compute_quotient_commitment());
-        RC(compute_opening_elements());
-        timing[0] = now_ms() - t0;
-        timing[2] = timing[0] - timing[1];
-        return BBGPU_OK;
+        RC(commit_many_begin(P));
+        return commit_many_end(P, out, &timing[1]);
     }
 
-    // ==== a batch of proofs of this circuit, advanced in lockstep (bbgpu_plonk_construct_proof_batch) =================================================
-    // The circuit-only state above is shared; every LANE has the per-proof vectors of init() once more, lane-major inside one allocation per group, so
-    // that the same polynomial of all lanes is one strided batch for the transforms and one launch (grid.y = lane) for the kernels of poly.hip.
-    // Each host synchronisation point of construct_proof() is reached once per batch: the device work of all lanes is enqueued, then the host finishes
-    // every lane's commitments, hashes every lane's transcript and enqueues the next round.
-    struct Lane {
-        Challenges ch;
-        Proof proof;
-        Fr t_eval, beta_inv;
-    };
-    enum { G_WLAG, G_W, G_SIGMA, G_WFFT, G_SFFT, G_Z, G_ZFFT, G_QL, G_QM, G_R, G_TMP, G_COUNT };
-    static constexpr int lane_group_vectors[G_COUNT] = { 3, 3, 3, 12, 12, 1, 4, 4, 2, 1, 3 }; // n-sized vectors per lane: 48 in all
-    int lanes_cap = 0;
-    uint64_t* lane_group[G_COUNT] = {};
-    uint64_t* lane_slots = nullptr;   // 16 x 32 bytes of device results per lane
-    void* h_lane_slots = nullptr;     // pinned mirror, BBGPU_PLONK_MAX_BATCH lanes
-    uint64_t* sigma_coeff = nullptr;  // the three sigma polynomials in coefficient form, UNSCALED: once per circuit (the lanes scale them by their beta)
-    poly::LaneTable lane_tab;
-    poly::Scratch lane_scratch;
-    hipStream_t st_ticket[8] = {};    // one queue per MSM slot: tickets that share a stream serialise
-    std::vector<Lane> lanes;
-    Challenges batch_challenges[BBGPU_PLONK_MAX_BATCH] = {};
-    int batch_count = 0;
-    double batch_timing[4] = {};
-
-    size_t lane_bytes() const { return (size_t)lanes_cap * (48 * n * 32 + 16 * 32); }
+    // ==== the rounds, advanced in lockstep over the lanes of the current set ===========================================================================
+    // The circuit-only state above is shared by all lanes.  Each host synchronisation point of waffle::Prover::construct_proof is reached once per run:
+    // the device work of all lanes is enqueued, then the host finishes every lane's commitments, hashes every lane's transcript and enqueues the next round.
+    size_t lane_bytes() const { return (size_t)batch.count * (48 * n * 32 + 16 * 32); }
     void release_lanes()
     {
-        for (uint64_t*& g : lane_group) {
+        for (uint64_t*& g : batch.group) {
             if (g) (void)dev_free(g);
             g = nullptr;
         }
-        release_lane_vars();
-        if (lane_slots) (void)dev_free(lane_slots);
-        lane_slots = nullptr;
+        release_vars(batch);
+        if (batch.slots) (void)dev_free(batch.slots);
+        batch.slots = nullptr;
         g_lane_bytes -= lane_bytes();
-        lanes_cap = 0;
+        batch.count = 0;
+    }
+    // the set the calls below address; the table's regions are free again (every entry leaves `st` idle)
+    void use(LaneSet& s)
+    {
+        cur = &s;
+        lane_tab.reset();
     }
     // vector k of group g of lane l
-    uint64_t* lv(int g, int l, int k = 0) const { return lane_group[g] + ((size_t)l * lane_group_vectors[g] + k) * n * 4; }
-    uint64_t* lslot(int l, int k) const { return lane_slots + ((size_t)l * 16 + k) * 4; }
+    uint64_t* lv(int g, int l, int k = 0) const { return cur->group[g] + ((size_t)l * lane_group_vectors[g] + k) * n * 4; }
+    uint64_t* lslot(int l, int k) const { return cur->slots + ((size_t)l * 16 + k) * 4; }
     int ensure_lanes(int count)
     {
-        if (!st_ticket[0])
-            for (hipStream_t& q : st_ticket) HIPCHK(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-        if (!h_lane_slots) HIPCHK(hipHostMalloc(&h_lane_slots, (size_t)BBGPU_PLONK_MAX_BATCH * 16 * 32));
-        RC(lane_tab.init((size_t)2 << 20));
-        if (!sigma_coeff) { // prover.cpp:245-247 without the beta
-            uint64_t* sc = nullptr;
-            HIPCHK(dev_malloc((void**)&sc, 3 * n * 32));
-            int rc = copy(sc, sigma_lagrange[0], 3 * n);
-            if (!rc) rc = ntt_batch(sc, n, 3, BBGPU_IFFT);
-            if (rc) {
-                (void)hipStreamSynchronize(st);
-                (void)dev_free(sc);
-                return rc;
-            }
-            sigma_coeff = sc;
-        }
-        if (count <= lanes_cap) return BBGPU_OK;
+        if (count <= batch.count) return BBGPU_OK;
         HIPCHK(hipStreamSynchronize(st));
         release_lanes(); // nothing of a lane outlives its batch: a larger count starts over
-        lanes_cap = count;
+        batch.count = count;
         g_lane_bytes += lane_bytes();
         int rc = BBGPU_OK;
         for (int g = 0; g < G_COUNT && !rc; g++)
-            if (dev_malloc((void**)&lane_group[g], (size_t)count * lane_group_vectors[g] * n * 32) != hipSuccess) rc = BBGPU_ERR_HIP;
-        if (!rc && dev_malloc((void**)&lane_slots, (size_t)count * 16 * 32) != hipSuccess) rc = BBGPU_ERR_HIP;
+            if (dev_malloc((void**)&batch.group[g], (size_t)count * lane_group_vectors[g] * n * 32) != hipSuccess) rc = BBGPU_ERR_HIP;
+        if (!rc && dev_malloc((void**)&batch.slots, (size_t)count * 16 * 32) != hipSuccess) rc = BBGPU_ERR_HIP;
         if (rc) release_lanes(); // a refused allocation gives back the groups it had got
         return rc;
     }
 
     // `total` commitments over n scalars each, as batch tickets of up to MSM_MAX_JOBS jobs on queues of their own behind `scalars_ready`; over an SRS
     // without window tables, single tickets.  As many tickets as there are free slots go out at once; the rest follows when those are collected.
-    // Whatever happens in between, the destructor collects what is still outstanding (see PendingCommit).
+    // Tickets that were issued and never waited on would stay `pending` for the life of the process and turn every later host-pointer MSM into
+    // BBGPU_ERR_STATE: whatever happens between begin and end (a failing transform, a failing later ticket), the destructor collects what is still
+    // outstanding.  Work that does not depend on a round's challenge is enqueued on `st` between begin and end: a 2^16-point batch is a ~0.4 ms chain of
+    // mostly latency-bound launches on the MSMs' own queues, beside which transforms run almost for free.
     struct PendingMany {
         struct Tk { int ticket, first, jobs; bool batched; };
         std::vector<Tk> held;
@@ -1093,7 +743,7 @@ class PlonkProver {
         HIPCHK(hipEventRecord(scalars_ready, st)); // the scalars are produced on `st`
         return commit_many_issue(P);
     }
-    int commit_many_end(PendingMany& P, uint64_t (*out)[8])
+    int commit_many_end(PendingMany& P, uint64_t (*out)[8], double* msm_ms)
     {
         uint64_t res[4 * 12];
         for (;;) {
@@ -1106,12 +756,12 @@ class PlonkProver {
             if (P.next >= (int)P.scalars.size()) break;
             RC(commit_many_issue(P));
         }
-        batch_timing[1] += now_ms() - P.t0;
+        *msm_ms += now_ms() - P.t0;
         return BBGPU_OK;
     }
     int read_lane_slots(int count)
     {
-        HIPCHK(d2h_async(h_lane_slots, lane_slots, (size_t)count * 16 * 32, st));
+        HIPCHK(d2h_async(h_lane_slots, cur->slots, (size_t)count * 16 * 32, st));
         HIPCHK(hipStreamSynchronize(st));
         return BBGPU_OK;
     }
@@ -1122,7 +772,7 @@ class PlonkProver {
         return v;
     }
 
-    // Round 0 of a batch: lane l's Lagrange-form wires (G_WLAG) from witness l in whatever form and place it comes.  Expanded host wires are three uploads
+    // Round 0: lane l's Lagrange-form wires (G_WLAG of the current set) from witness l in whatever form and place it comes.  Expanded host wires are three uploads
     // per lane, as ever; expanded device wires three device copies; variables one upload per lane (none from device memory: the expansion reads the
     // caller's buffer) and ONE expansion launch for all such lanes.  The caller's buffers are last read by work enqueued here, and every entry that
     // calls this synchronises `st` before it returns.
@@ -1134,10 +784,10 @@ class PlonkProver {
             if (W[l].where == BBGPU_PLONK_WITNESS_DEVICE && (l == 0 || W[l - 1].where != BBGPU_PLONK_WITNESS_DEVICE || W[l - 1].hip_stream != W[l].hip_stream))
                 RC(wait_for_caller(W[l].hip_stream));
         }
-        if (host_variables && !lane_vars) { // grows with the lanes (ensure_lanes releases it with them), sized for every lane the handle has
-            const size_t bytes = (size_t)lanes_cap * num_variables * 32;
-            HIPCHK(dev_malloc((void**)&lane_vars, bytes));
-            lane_vars_bytes = bytes;
+        if (host_variables && !cur->vars) { // sized for every lane of the set: the batch set's goes with its lanes when they grow (ensure_lanes)
+            const size_t bytes = (size_t)cur->count * num_variables * 32;
+            HIPCHK(dev_malloc((void**)&cur->vars, bytes));
+            cur->vars_bytes = bytes;
             g_lane_bytes += bytes;
         }
         std::vector<poly::ExpandWiresArgs> ex;
@@ -1150,7 +800,7 @@ class PlonkProver {
             }
             const uint64_t* src = W[l].variables;
             if (W[l].where == BBGPU_PLONK_WITNESS_HOST) {
-                uint64_t* stage = lane_vars + (size_t)l * num_variables * 4;
+                uint64_t* stage = cur->vars + (size_t)l * num_variables * 4;
                 RC(host_to_device(stage, W[l].variables, num_variables * 32, st));
                 src = stage;
             }
@@ -1161,22 +811,21 @@ class PlonkProver {
         return BBGPU_OK;
     }
 
-    int construct_proof_batch(int count, const bbgpu_plonk_witness* W, uint64_t* proofs_out)
+    // waffle::Prover::construct_proof (prover.cpp:661-670) over the first L lanes of the current set; the finished proofs and challenges are left in
+    // `lanes`.  W: the L witnesses to load first, or null when the wires are in the lanes already.  tm: total, msm, the rest, first-use preparation.
+    int prove(int L, const bbgpu_plonk_witness* W, double tm[4])
     {
-        batch_timing[0] = batch_timing[1] = batch_timing[2] = 0;
+        tm[0] = tm[1] = tm[2] = 0;
         RC(prepare_circuit());
-        RC(ensure_lanes(count));
         const double t0 = now_ms();
-        lanes.assign((size_t)count, Lane{});
-        lane_tab.reset();
+        lanes.assign((size_t)L, Lane{});
         const size_t n4 = 4 * n, n2 = 2 * n;
-        const int L = count;
         std::vector<Fr> fa((size_t)3 * L), fb((size_t)3 * L), fc((size_t)L);
         std::vector<uint64_t> pts((size_t)3 * L * 8);
         uint64_t(*out)[8] = reinterpret_cast<uint64_t(*)[8]>(pts.data());
 
         // ---- round 1: wires (prover.cpp:124-133, :65-86)
-        RC(load_lanes(L, W));
+        if (W) RC(load_lanes(L, W));
         if (witness_check) RC(check_enqueue(L)); // opt-in: beside the inverse transforms, the verdict before the first commitment is issued
         RC(copy(lv(G_W, 0), lv(G_WLAG, 0), (size_t)3 * L * n));
         RC(bbgpu_ntt_device_batch(lv(G_W, 0), n, n, 3 * L, BBGPU_IFFT, nullptr, st));
@@ -1199,7 +848,7 @@ class PlonkProver {
                 }
             RC(poly::copy_pad_lanes(lane_tab, cp.data(), 3 * L, nullptr, st));
             RC(bbgpu_ntt_device_batch(lv(G_WFFT, 0), n4, n4, 3 * L, BBGPU_COSET_FFT, nullptr, st));
-            RC(commit_many_end(P, out));
+            RC(commit_many_end(P, out, &tm[1]));
         }
         for (int l = 0; l < L; l++) {
             Lane& X = lanes[l];
@@ -1214,7 +863,9 @@ class PlonkProver {
             fb[l] = X.ch.gamma;
         }
 
-        // ---- round 2: the grand product (prover.cpp:135-222, :88-105); see compute_z_coefficients for the scans
+        // ---- round 2: the grand product (prover.cpp:135-222, :88-105): Z(w^m) = prod_{i<m} num_i / den_i.  The six serial accumulator chains (:194-202)
+        // and the batch inversion (:215) become one exclusive prefix-product scan of the numerators (-> G_TMP 2), one inclusive suffix-product scan of the
+        // denominators (-> G_R, free at this point; total -> slot 0) and a single inversion: 1 / prod_{i<m} den_i = (prod_{i>=m} den_i) / prod_i den_i.
         {
             std::vector<poly::ZTermsArgs> za((size_t)L);
             std::vector<poly::ScanJob> sj((size_t)2 * L);
@@ -1232,7 +883,7 @@ class PlonkProver {
                 sd.in = lv(G_TMP, l, 1); sd.out = lv(G_R, l); sd.n = n; sd.reverse = true; sd.inclusive = true; sd.d_total = lslot(l, 0);
             }
             RC(poly::z_terms_lanes(lane_tab, za.data(), L, host::fr_root_of_unity(log2n), fa.data(), fb.data(), st));
-            RC(poly::scan_lanes(0, sj.data(), 2 * L, lane_tab, lane_scratch, st));
+            RC(poly::scan_lanes(0, sj.data(), 2 * L, lane_tab, scratch, st));
             RC(read_lane_slots(L));
             std::vector<poly::Mul2cArgs> ma((size_t)L);
             for (int l = 0; l < L; l++) {
@@ -1273,14 +924,15 @@ class PlonkProver {
             RC(poly::copy_pad_lanes(lane_tab, cp.data(), 3 * L, fa.data(), st));
             RC(poly::sigma_prepare_lanes(lane_tab, sp.data(), 3 * L, fb.data(), st));
             RC(bbgpu_ntt_device_batch(lv(G_SFFT, 0), n4, n4, 3 * L, BBGPU_COSET_FFT, nullptr, st));
-            RC(commit_many_end(P, out));
+            RC(commit_many_end(P, out, &tm[1]));
         }
         for (int l = 0; l < L; l++) {
             memcpy(lanes[l].proof.Z_1, out[l], 64);
             lanes[l].ch.alpha = challenge(transcript_of(lanes[l].proof, 1)); // compute_alpha, challenge.hpp:87-98
         }
 
-        // ---- round 3: the quotient (compute_quotient_numerators, compute_quotient_polynomial, compute_quotient_commitment)
+        // ---- round 3: the quotient.  prover.cpp:224-300 + :302-341 fused into one pass over the 4n coset, :350-402 + arithmetic_widget.cpp:66-104 into one
+        // over the 2n coset, then :405-465 and the commitments of :107-122.  G_WFFT and G_SFFT were enqueued beside the wire / Z commitments.
         {
             std::vector<poly::CopyPadArgs> cp((size_t)L);
             std::vector<poly::QuotLargeArgs> la((size_t)L);
@@ -1366,7 +1018,7 @@ class PlonkProver {
             for (int l = 0; l < L; l++)
                 for (int k = 0; k < 3; k++) P.scalars.push_back(lv(G_QL, l) + (size_t)k * n * 4);
             RC(commit_many_begin(P));
-            RC(commit_many_end(P, out));
+            RC(commit_many_end(P, out, &tm[1]));
         }
         for (int l = 0; l < L; l++) {
             memcpy(lanes[l].proof.T_LO, out[3 * l], 64);
@@ -1375,7 +1027,9 @@ class PlonkProver {
             lanes[l].ch.z = challenge(transcript_of(lanes[l].proof, 2)); // compute_evaluation_challenge, challenge.hpp:100-112
         }
 
-        // ---- round 4: evaluations and the linearisation polynomial (compute_linearisation_coefficients)
+        // ---- round 4: evaluations and the linearisation polynomial (prover.cpp:467-538): the evaluations of all lanes in one pair of launches and one
+        // read-back (:478-480, :504-506, :512; with the MiMC or the sequential widget w_o at z omega, REQUIRES_W_O_SHIFTED, prover.cpp:499-502,
+        // sequential_widget.cpp:16, and with the MiMC widget q_mimc_coefficient, mimc_widget.cpp:92-95), then r and its evaluation (:536)
         const int nev = has_mimc ? 9 : has_seq ? 8 : 7;
         const Fr omega = host::fr_root_of_unity(log2n);
         std::vector<Fr> zs((size_t)2 * L);
@@ -1393,7 +1047,7 @@ class PlonkProver {
                     zi[(size_t)l * nev + j] = 2 * l + jl[j].zsel;
                 }
             }
-            RC(poly::evaluate_lanes(ej.data(), zi.data(), nev * L, zs.data(), 2 * L, lane_tab, lane_scratch, st));
+            RC(poly::evaluate_lanes(ej.data(), zi.data(), nev * L, zs.data(), 2 * L, lane_tab, scratch, st));
             RC(read_lane_slots(L));
             std::vector<poly::LinCombArgs> lc((size_t)L);
             std::vector<Fr> cl((size_t)12 * L);
@@ -1415,11 +1069,14 @@ class PlonkProver {
                 rz[l] = 2 * l;
             }
             RC(poly::lincomb_lanes(lane_tab, lc.data(), L, cl.data(), st));
-            RC(poly::evaluate_lanes(rj.data(), rz.data(), L, zs.data(), 2 * L, lane_tab, lane_scratch, st)); // :536
+            RC(poly::evaluate_lanes(rj.data(), rz.data(), L, zs.data(), 2 * L, lane_tab, scratch, st)); // :536
             RC(read_lane_slots(L));
         }
 
-        // ---- round 5: the opening polynomials (compute_opening_elements)
+        // ---- round 5: the opening polynomials (prover.cpp:540-659).  :567-595 is one linear combination of nine resident vectors; with the MiMC or the
+        // sequential widget w_o joins the shifted opening at nu^8 (:627-635) and q_mimc_coefficient the main one at nu^9 (mimc_widget.cpp:115-123).
+        // compute_kate_opening_coefficients (polynomial_arithmetic.cpp:562-591): W_i = sum_{j>i} F_j z^(j-i-1); the serial recurrence becomes a Horner
+        // suffix scan, the remainder F(z) drops out.
         {
             std::vector<poly::LinCombArgs> oa((size_t)L), ob((size_t)L);
             std::vector<Fr> ca((size_t)12 * L), cb((size_t)12 * L);
@@ -1463,37 +1120,44 @@ class PlonkProver {
             }
             RC(poly::lincomb_lanes(lane_tab, oa.data(), L, ca.data(), st));
             RC(poly::lincomb_lanes(lane_tab, ob.data(), L, cb.data(), st)); // nu^7 Z (+ nu^8 w_o)
-            RC(poly::scan_lanes(1, kj.data(), 2 * L, lane_tab, lane_scratch, st));
+            RC(poly::scan_lanes(1, kj.data(), 2 * L, lane_tab, scratch, st));
             PendingMany P;
             for (int l = 0; l < L; l++) {
                 P.scalars.push_back(lv(G_TMP, l, 2));
                 P.scalars.push_back(lv(G_R, l));
             }
             RC(commit_many_begin(P));
-            RC(commit_many_end(P, out)); // :650-658
+            RC(commit_many_end(P, out, &tm[1])); // :650-658
         }
         for (int l = 0; l < L; l++) {
             memcpy(lanes[l].proof.PI_Z, out[2 * l], 64);
             memcpy(lanes[l].proof.PI_Z_OMEGA, out[2 * l + 1], 64);
+        }
+        tm[0] = now_ms() - t0;
+        tm[2] = tm[0] - tm[1];
+        tm[3] = timing[3];
+        return BBGPU_OK;
+    }
+    // the witness the handle holds, in the own lane
+    int construct_proof(uint64_t* proof_out)
+    {
+        use(own);
+        RC(prove(1, nullptr, timing));
+        memcpy(proof_out, &lanes[0].proof, sizeof(Proof));
+        challenges = lanes[0].ch;
+        return BBGPU_OK;
+    }
+    // bbgpu_plonk_construct_proof_batch*: `count` witnesses in the batch lanes
+    int construct_proof_batch(int count, const bbgpu_plonk_witness* W, uint64_t* proofs_out)
+    {
+        RC(ensure_lanes(count));
+        use(batch);
+        RC(prove(count, W, batch_timing));
+        for (int l = 0; l < count; l++) {
             memcpy(proofs_out + (size_t)l * BBGPU_PLONK_PROOF_WORDS, &lanes[l].proof, sizeof(Proof));
             batch_challenges[l] = lanes[l].ch;
         }
-        batch_count = L;
-        batch_timing[0] = now_ms() - t0;
-        batch_timing[2] = batch_timing[0] - batch_timing[1];
-        batch_timing[3] = timing[3];
-        return BBGPU_OK;
-    }
-    // the check alone over `count` witnesses, uploaded into the lanes a batch proof of the same count would use
-    int check_witness_batch(int count, const bbgpu_plonk_witness* W, bbgpu_plonk_witness_report* out)
-    {
-        RC(prepare_circuit()); // (ensure_lanes derives the lanes' shared sigma coefficients from it)
-        RC(ensure_lanes(count));
-        lane_tab.reset();
-        RC(load_lanes(count, W));
-        RC(check_enqueue(count));
-        RC(check_finish(count, false));
-        memcpy(out, reports, sizeof(bbgpu_plonk_witness_report) * (size_t)count);
+        batch_count = count;
         return BBGPU_OK;
     }
 };
@@ -1660,6 +1324,8 @@ void plonk_release_all_locked()
         p = nullptr;
     }
     g_provers.clear();
+    for (hipStream_t q : g_idle_streams) (void)hipStreamDestroy(q);
+    g_idle_streams.clear();
 }
 
 } // namespace bbgpu
@@ -1721,7 +1387,11 @@ int bbgpu_plonk_prover_set_witness(int prover, const uint64_t* w_l, const uint64
     if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
     PlonkProver* p = get(prover);
     if (!p || !w_l || !w_r || !w_o) return BBGPU_ERR_ARG;
-    return p->set_witness(w_l, w_r, w_o);
+    bbgpu_plonk_witness W;
+    wires_on_host(1, &w_l, &w_r, &w_o, &W);
+    const int rc = p->set_witness_from(W);
+    if (rc) (void)hipStreamSynchronize(p->st); // the caller's arrays are no longer read when it sees the error
+    return rc;
 }
 
 int bbgpu_plonk_construct_proof(int prover, uint64_t proof_out[BBGPU_PLONK_PROOF_WORDS])
@@ -1730,10 +1400,9 @@ int bbgpu_plonk_construct_proof(int prover, uint64_t proof_out[BBGPU_PLONK_PROOF
     if (int rcb = bind_calling_thread()) return rcb; // the kernels below are launched from THIS thread
     PlonkProver* p = get(prover);
     if (!p || !proof_out) return BBGPU_ERR_ARG;
-    int rc = p->construct_proof();
-    if (rc) return rc;
-    memcpy(proof_out, &p->proof, sizeof(Proof));
-    return BBGPU_OK;
+    const int rc = p->construct_proof(proof_out);
+    if (rc) (void)hipStreamSynchronize(p->st); // nothing of a failed proof is still running when the caller sees the error
+    return rc;
 }
 
 int bbgpu_plonk_construct_proof_batch(int prover, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o,
@@ -1949,14 +1618,14 @@ int bbgpu_plonk_last_timing(int prover, double ms_out[4])
 int bbgpu_plonk_challenges_from_proof(const uint64_t proof_words[BBGPU_PLONK_PROOF_WORDS], uint64_t out[16])
 {
     if (!proof_words || !out) return BBGPU_ERR_ARG;
-    PlonkProver p;
-    memcpy(&p.proof, proof_words, sizeof(Proof));
-    std::vector<uint64_t> b = p.transcript_upto(0);
+    Proof proof;
+    memcpy(&proof, proof_words, sizeof(Proof));
+    std::vector<uint64_t> b = PlonkProver::transcript_of(proof, 0);
     const Fr gamma = PlonkProver::challenge(b);
     PlonkProver::put_fr(b, gamma);
     const Fr beta = PlonkProver::challenge(b);
-    const Fr alpha = PlonkProver::challenge(p.transcript_upto(1));
-    const Fr z = PlonkProver::challenge(p.transcript_upto(2));
+    const Fr alpha = PlonkProver::challenge(PlonkProver::transcript_of(proof, 1));
+    const Fr z = PlonkProver::challenge(PlonkProver::transcript_of(proof, 2));
     memcpy(out, gamma.d, 32);
     memcpy(out + 4, beta.d, 32);
     memcpy(out + 8, alpha.d, 32);

@@ -99,8 +99,7 @@ struct WitnessCheckArgs {
     Limbs9 one_m256;
 };
 struct LaneTable;
-// presets `lanes` consecutive records starting at A[0].counts / A[0].first, then k_check_gates and k_check_copies: two launches however many lanes
-int check_witness(WitnessCheckArgs A, hipStream_t st);
+// presets `lanes` consecutive records starting at A[0].counts / A[0].first, then the gate and the copy kernel: two launches however many lanes
 int check_witness_lanes(LaneTable& T, const WitnessCheckArgs* A, int lanes, hipStream_t st);
 
 // ---- wires from composer variables (bbgpu_plonk_prover_set_wire_map, the VARIABLES form of bbgpu_plonk_witness) ---------------------------------------------
@@ -112,7 +111,6 @@ struct ExpandWiresArgs {
     uint32_t* dst[3];           // n x 8 words each
     uint32_t n, num_variables;
 };
-int expand_wires(ExpandWiresArgs A, hipStream_t st);
 int expand_wires_lanes(LaneTable& T, const ExpandWiresArgs* A, int lanes, hipStream_t st); // one launch for the three wires of all lanes
 
 struct EvalJob {
@@ -120,15 +118,6 @@ struct EvalJob {
     size_t n;
     int zsel;           // evaluate at z[zsel]
     uint64_t* d_result; // 32-byte device slot
-};
-struct EvalBatchArgs {
-    const uint32_t* c[10];
-    uint32_t* result[10];
-    uint32_t n[10], blocks[10];
-    uint8_t zsel[10];
-    Limbs9 zT[10];
-    PowTab T[2];
-    uint32_t* partial; // 10 x 256 elements
 };
 struct ScanJob {
     const uint64_t* in;
@@ -139,9 +128,9 @@ struct ScanJob {
     uint64_t* d_total;  // optional 32-byte device slot
 };
 
-// ---- lane-batched forms (a batch of proofs of one circuit, plonk.hip) ------------------------------------------------------------------------------
-// One launch serves every lane: blockIdx.y selects a RECORD of a device table -- the argument struct the single-lane kernel takes by value (16 lanes of
-// ZTermsArgs would not fit the kernel-argument space), holding the lane's vectors and its challenge-dependent constants.  The host writes the records
+// ---- the prover's round kernels (the lanes of plonk.hip: one for a single proof, up to 16 for a batch) ---------------------------------------------
+// One launch serves every lane: blockIdx.y selects a RECORD of a device table -- one of the argument structs above (16 lanes of ZTermsArgs would not
+// fit the kernel-argument space), holding the lane's vectors and its challenge-dependent constants.  The host writes the records
 // into pinned memory and the table crosses with one copy in front of the launch; every workgroup reads one record, uniformly.
 struct LaneTable {
     uint8_t *d = nullptr, *h = nullptr; // device table and its pinned mirror
@@ -192,21 +181,17 @@ int copy_pad_lanes(LaneTable& T, const CopyPadArgs* A, int records, const host::
 // the same vector of every lane at base + lane * stride (elements), no per-lane constant
 int add_inplace_lanes(uint64_t* d_a, size_t stride_a, const uint64_t* d_b, size_t stride_b, size_t n, int lanes, hipStream_t st);
 int divide_by_pseudo_vanishing_lanes(uint64_t* d_coeffs, size_t stride, int lanes, int log2n, int log2N, hipStream_t st);
-// `count` scans of one mode and one length (<= 2^22) in shared launches; jobs[j].d_total, where given, receives the total directly
+// `count` scans of one mode (0 = running products, 1 = Horner suffix sums) and one length (<= 2^22) in shared launches; jobs[j].d_total, where given,
+// receives the total directly
 int scan_lanes(int mode, const ScanJob* jobs, int count, LaneTable& T, Scratch& S, hipStream_t st);
 // `count` evaluations, job j at z[zidx[j]]
 int evaluate_lanes(const EvalJob* jobs, const int* zidx, int count, const host::Fr* z, int nz, LaneTable& T, Scratch& S, hipStream_t st);
 
 PowTab make_powtab(const host::Fr& base);
-// up to two scans of the same kind in shared launches: mode 0 = running products, mode 1 = Horner suffix sums
-int scan_pair(int mode, const ScanJob* jobs, int count, Scratch& S, hipStream_t st);
-int evaluate_batch_to_device(const EvalJob* jobs, int count, const host::Fr z[2], Scratch& S, hipStream_t st);
 
 int powers(uint64_t* d_out, size_t n, const host::Fr& base, const host::Fr& start, hipStream_t st);
 int copy_pad(uint64_t* d_dst, const uint64_t* d_src, size_t n_src, size_t n_dst, hipStream_t st);
-int add_inplace(uint64_t* d_a, const uint64_t* d_b, size_t n, hipStream_t st);
 int mul_pointwise(uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, size_t n, hipStream_t st);
-int mul2c(uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, size_t n, const host::Fr& c, hipStream_t st);
 
 size_t scan_scratch_bytes(size_t n);
 // exclusive / inclusive running products, prefix or suffix; d_out may be null when only the total is wanted
@@ -218,16 +203,8 @@ int evaluate(const uint64_t* d_coeffs, size_t n, const host::Fr& z, host::Fr* ou
 int batch_invert(uint64_t* d_v, uint64_t* d_tmp, size_t n, Scratch& S, hipStream_t st);
 
 int sigma_from_mapping(uint64_t* d_out, const uint32_t* d_mapping, const uint64_t* d_roots, size_t n, hipStream_t st);
-int z_terms(ZTermsArgs A, const host::Fr& root, const host::Fr& beta, const host::Fr& gamma, hipStream_t st);
-int sigma_prepare(uint64_t* d_dst, const uint64_t* d_sigma, const uint64_t* d_w, size_t n, size_t n_dst, const host::Fr& gamma, hipStream_t st);
-int quotient_large(QuotLargeArgs A, const host::Fr& root4n, const host::Fr& beta, const host::Fr& gamma, hipStream_t st);
-int quotient_mid(QuotMidArgs A, const host::Fr& alpha, const host::Fr& alpha_base, hipStream_t st);
-int quotient_mimc(QuotMimcArgs A, const host::Fr& alpha_base, const host::Fr& alpha_step, hipStream_t st);
-int quotient_bool(QuotBoolArgs A, const host::Fr& c_left, const host::Fr& c_right, const host::Fr& c_out, hipStream_t st);
-int quotient_seq(QuotSeqArgs A, const host::Fr& c, hipStream_t st); // sequential_widget.cpp:47-62: quotient_mid[i] += c q_o_next[i] w_o[2i + 4]
 int divide_by_pseudo_vanishing(uint64_t* d_coeffs, int log2n, int log2N, hipStream_t st);
 int lagrange_l1_fft(uint64_t* d_l1, uint64_t* d_tmp, int log2n, int log2N, Scratch& S, hipStream_t st);
-int lincomb(LinCombArgs A, const host::Fr* coeffs, hipStream_t st);
 
 } // namespace poly
 } // namespace bbgpu

@@ -137,13 +137,6 @@ __global__ void __launch_bounds__(PT) k_copy_pad(uint32_t* __restrict__ dst, con
         q[1] = make_uint4(0, 0, 0, 0);
     }
 }
-// a[i] += b[i]
-__global__ void __launch_bounds__(PT) k_add_inplace(uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    stv(a, i, add(ldv(a, i), ldv(b, i)));
-}
 // out[i] = a[i] * b[i] * c   (c in the 2^261 form, already carrying the FIX2 factor: c' = c * 2^5)
 __global__ void __launch_bounds__(PT) k_mul2c(uint32_t* __restrict__ out, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t n,
                                             Limbs9 c_fix_m261)
@@ -452,7 +445,6 @@ __global__ void __launch_bounds__(PT) k_sum_small(const uint32_t* __restrict__ p
 }
 
 // several evaluations in one pair of launches (blockIdx.y = job): the prover's seven openings at z / z w (prover.cpp:478-512)
-template <bool U>
 __device__ __forceinline__ void eval_partial_body(const uint32_t* __restrict__ c, uint32_t n, uint32_t nblocks, const PowTab& T, const Limbs9& zT_m261,
                                                   uint32_t* __restrict__ partial, uint32_t* sh)
 {
@@ -461,13 +453,13 @@ __device__ __forceinline__ void eval_partial_body(const uint32_t* __restrict__ c
     FrM acc = mul(fe_zero<Fr>(), fe_from<Fr>(Fr::ONE));
     if (t < n) {
         const uint32_t cnt = (n - t + nt - 1) / nt;
-        const FrC zT = cst<U>(zT_m261);
+        const FrC zT = cst<true>(zT_m261);
         FrH h = ldv(c, t + (size_t)(cnt - 1) * nt);
         for (uint32_t k = cnt - 1; k-- > 0;) h = add(mul(h, zT), ldv(c, t + (size_t)k * nt));
         Limbs9 one261;
 #pragma unroll
         for (int k = 0; k < NL; k++) one261.d[k] = Fr::ONE[k];
-        acc = mul(h, pow_tab<U>(T, t, one261)); // * z^t
+        acc = mul(h, pow_tab<true>(T, t, one261)); // * z^t
     }
 #pragma unroll
     for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = acc.d[k];
@@ -493,18 +485,12 @@ __device__ __forceinline__ void eval_partial_body(const uint32_t* __restrict__ c
         stv(partial, blockIdx.x, sm);
     }
 }
-__global__ void __launch_bounds__(PT) k_eval_partial_batch(EvalBatchArgs A)
-{
-    __shared__ uint32_t sh[NL * PT];
-    const uint32_t job = blockIdx.y;
-    eval_partial_body<false>(A.c[job], A.n[job], A.blocks[job], A.T[A.zsel[job]], A.zT[job], A.partial + (size_t)job * 256 * 8, sh);
-}
 // any number of evaluations, each at a point of its own, from a device table of jobs (blockIdx.y = job): the openings of every lane of a proof batch
 __global__ void __launch_bounds__(PT) k_eval_partial_tab(const EvalTabJob* __restrict__ tab)
 {
     __shared__ uint32_t sh[NL * PT];
     const EvalTabJob& J = tab[blockIdx.y];
-    eval_partial_body<true>(J.c, J.n, J.blocks, J.T, J.zT, J.partial, sh);
+    eval_partial_body(J.c, J.n, J.blocks, J.T, J.zT, J.partial, sh);
 }
 __device__ __forceinline__ void sum_small_body(const uint32_t* __restrict__ partial, uint32_t count, uint32_t* __restrict__ result, uint32_t* sh)
 {
@@ -534,12 +520,6 @@ __device__ __forceinline__ void sum_small_body(const uint32_t* __restrict__ part
         stv(result, 0, sm);
     }
 }
-__global__ void __launch_bounds__(PT) k_sum_small_batch(EvalBatchArgs A)
-{
-    __shared__ uint32_t sh[NL * PT];
-    const uint32_t job = blockIdx.x;
-    sum_small_body(A.partial + (size_t)job * 256 * 8, A.blocks[job], A.result[job], sh);
-}
 __global__ void __launch_bounds__(PT) k_sum_small_tab(const EvalTabJob* __restrict__ tab)
 {
     __shared__ uint32_t sh[NL * PT];
@@ -567,16 +547,16 @@ __global__ void __launch_bounds__(PT) k_sigma_from_mapping(uint32_t* __restrict_
 // prover.cpp:148-187: numerator / denominator factors of the grand product, three wires multiplied together
 //   num_i = (w_l + beta w^i + gamma)(w_r + beta k1 w^i + gamma)(w_o + beta k2 w^i + gamma)
 //   den_i = (w_l + beta sigma_1 + gamma)(w_r + beta sigma_2 + gamma)(w_o + beta sigma_3 + gamma)
-template <bool U> __device__ __forceinline__ void z_terms_body(const ZTermsArgs& A)
+__device__ __forceinline__ void z_terms_body(const ZTermsArgs& A)
 {
     const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= A.n) return;
     Limbs9 one261;
 #pragma unroll
     for (int k = 0; k < NL; k++) one261.d[k] = Fr::ONE[k];
-    FrM x = pow_tab<U>(A.root, t, one261); // w^t, 2^261 form
-    const FrC step = cst<U>(A.step_m261), beta = cst<U>(A.beta_m256), bk1 = cst<U>(A.beta_k1_m256), bk2 = cst<U>(A.beta_k2_m256), gamma = cst<U>(A.gamma_m256),
-              beta261 = cst<U>(A.beta_m261);
+    FrM x = pow_tab<true>(A.root, t, one261); // w^t, 2^261 form
+    const FrC step = cst<true>(A.step_m261), beta = cst<true>(A.beta_m256), bk1 = cst<true>(A.beta_k1_m256), bk2 = cst<true>(A.beta_k2_m256), gamma = cst<true>(A.gamma_m256),
+              beta261 = cst<true>(A.beta_m261);
     for (uint32_t i = t; i < A.n; i += nt) {
         const FrV wl = ldv(A.w_l, i), wr = ldv(A.w_r, i), wo = ldv(A.w_o, i);
         auto a0 = add(add(mul(x, beta), gamma), wl);
@@ -590,35 +570,17 @@ template <bool U> __device__ __forceinline__ void z_terms_body(const ZTermsArgs&
         x = mul(x, step);
     }
 }
-__global__ void __launch_bounds__(PT) k_z_terms(ZTermsArgs A) { z_terms_body<false>(A); }
-__global__ void __launch_bounds__(PT) k_z_terms_lanes(const ZTermsArgs* __restrict__ tab) { z_terms_body<true>(tab[blockIdx.y]); } // one table record per lane
-
-// prover.cpp:253-269: dst (4n) = beta sigma(X) + w(X) + gamma in coefficient form, zero-padded
-__global__ void __launch_bounds__(PT) k_sigma_prepare(uint32_t* __restrict__ dst, const uint32_t* __restrict__ sigma, const uint32_t* __restrict__ w,
-                                                    uint32_t n, uint32_t n_dst, Limbs9 gamma_m256)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_dst) return;
-    if (i >= n) {
-        uint4* q = reinterpret_cast<uint4*>(dst + (size_t)i * 8);
-        q[0] = make_uint4(0, 0, 0, 0);
-        q[1] = make_uint4(0, 0, 0, 0);
-        return;
-    }
-    auto v = add(ldv(sigma, i), ldv(w, i));
-    if (i == 0) stv(dst, i, add(v, cst(gamma_m256)));
-    else stv(dst, i, v);
-}
+__global__ void __launch_bounds__(PT) k_z_terms_lanes(const ZTermsArgs* __restrict__ tab) { z_terms_body(tab[blockIdx.y]); } // one table record per lane
 
 // prover.cpp:294-299 and :310-341 fused: the degree-3n part of the quotient numerator on the 4n coset
 //   q[i] = (w_l + beta x + gamma)(w_r + beta k1 x + gamma)(w_o + beta k2 x + gamma) zf[i]  -  s1 s2 s3 zf[i + 4],   x = g w_4n^i
 // (zf = alpha * Z on the coset, index i + 4 wraps: prover.cpp:286-289 appends the first four values instead)
-template <bool U> __device__ __forceinline__ void quotient_large_body(const QuotLargeArgs& A)
+__device__ __forceinline__ void quotient_large_body(const QuotLargeArgs& A)
 {
     const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= A.n4) return;
-    FrM x = pow_tab<U>(A.root, t, A.g_m261);
-    const FrC step = cst<U>(A.step_m261), beta = cst<U>(A.beta_m256), bk1 = cst<U>(A.beta_k1_m256), bk2 = cst<U>(A.beta_k2_m256), gamma = cst<U>(A.gamma_m256);
+    FrM x = pow_tab<true>(A.root, t, A.g_m261);
+    const FrC step = cst<true>(A.step_m261), beta = cst<true>(A.beta_m256), bk1 = cst<true>(A.beta_k1_m256), bk2 = cst<true>(A.beta_k2_m256), gamma = cst<true>(A.gamma_m256);
     for (uint32_t i = t; i < A.n4; i += nt) {
         auto t0 = add(add(mul(x, beta), gamma), ldv(A.wl_f, i));
         auto t1 = add(add(mul(x, bk1), gamma), ldv(A.wr_f, i));
@@ -629,37 +591,35 @@ template <bool U> __device__ __forceinline__ void quotient_large_body(const Quot
         x = mul(x, step);
     }
 }
-__global__ void __launch_bounds__(PT) k_quotient_large(QuotLargeArgs A) { quotient_large_body<false>(A); }
-__global__ void __launch_bounds__(PT) k_quotient_large_lanes(const QuotLargeArgs* __restrict__ tab) { quotient_large_body<true>(tab[blockIdx.y]); } // one table record per lane
+__global__ void __launch_bounds__(PT) k_quotient_large_lanes(const QuotLargeArgs* __restrict__ tab) { quotient_large_body(tab[blockIdx.y]); } // one table record per lane
 
 // prover.cpp:360-402 and arithmetic_widget.cpp:86-101 fused: the degree-2n part on the 2n coset
 //   q[i] = (zf[2i+4] - alpha) alpha l1[i+4] + (zf[2i] - alpha) alpha^2 l1[i]
 //        + abase (qm wl wr + ql wl + qr wr + qo wo + qc),  wires at index 2i of their 4n transforms
-template <bool U> __device__ __forceinline__ void quotient_mid_body(const QuotMidArgs& A)
+__device__ __forceinline__ void quotient_mid_body(const QuotMidArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n2) return;
     const uint32_t m4 = 2 * A.n2 - 1, m2 = A.n2 - 1;
-    const FrC alpha = cst<U>(A.alpha_m256);
-    auto t6 = mul(mul(sub(ldv(A.z_f, (2 * i + 4) & m4), alpha), ldv(A.l1, (i + 4) & m2)), cst<U>(A.alpha_fix_m261));   // * alpha * 2^5
-    auto t4 = mul(mul(sub(ldv(A.z_f, 2 * i), alpha), ldv(A.l1, i)), cst<U>(A.alpha2_fix_m261));                          // * alpha^2 * 2^5
+    const FrC alpha = cst<true>(A.alpha_m256);
+    auto t6 = mul(mul(sub(ldv(A.z_f, (2 * i + 4) & m4), alpha), ldv(A.l1, (i + 4) & m2)), cst<true>(A.alpha_fix_m261));   // * alpha * 2^5
+    auto t4 = mul(mul(sub(ldv(A.z_f, 2 * i), alpha), ldv(A.l1, i)), cst<true>(A.alpha2_fix_m261));                          // * alpha^2 * 2^5
     const FrV wl = ldv(A.wl_f, 2 * i), wr = ldv(A.wr_f, 2 * i), wo = ldv(A.wo_f, 2 * i);
     // selector transforms are stored unscaled; abase carries the fix factors: three-operand term needs 2^10, two-operand 2^5
-    auto g3 = mul(mul(mul(ldv(A.qm_f, i), wl), wr), cst<U>(A.abase_fix3_m261));
+    auto g3 = mul(mul(mul(ldv(A.qm_f, i), wl), wr), cst<true>(A.abase_fix3_m261));
     auto gl = mul(ldv(A.ql_f, i), wl);
     auto gr = mul(ldv(A.qr_f, i), wr);
     auto go = mul(ldv(A.qo_f, i), wo);
-    auto g2 = mul(add(add(gl, gr), go), cst<U>(A.abase_fix2_m261));
-    auto gc = mul(ldv(A.qc_f, i), cst<U>(A.abase_m261));
+    auto g2 = mul(add(add(gl, gr), go), cst<true>(A.abase_fix2_m261));
+    auto gc = mul(ldv(A.qc_f, i), cst<true>(A.abase_m261));
     stv(A.q, i, add(add(add(t6, t4), add(g3, g2)), gc));
 }
-__global__ void __launch_bounds__(PT) k_quotient_mid(QuotMidArgs A) { quotient_mid_body<false>(A); }
-// (second bound = waves per SIMD: the record-fed form is held to the registers of the by-value kernel)
-__global__ void __launch_bounds__(PT, 6) k_quotient_mid_lanes(const QuotMidArgs* __restrict__ tab) { quotient_mid_body<true>(tab[blockIdx.y]); } // one table record per lane
+// (second bound = waves per SIMD: holds the body to the registers it takes when its constants arrive as kernel arguments)
+__global__ void __launch_bounds__(PT, 6) k_quotient_mid_lanes(const QuotMidArgs* __restrict__ tab) { quotient_mid_body(tab[blockIdx.y]); } // one table record per lane
 
 // mimc_widget.cpp:58-90 on the 4n coset: with T0 = w_o + w_l + q_coef,
 //   q[i] += abase q_sel [ (T0^3 - w_r) + alpha (w_r^2 T0 - w_o[i + 4]) ]        (w_o[i + 4] = the next gate's output wire)
-template <bool U> __device__ __forceinline__ void quotient_mimc_body(const QuotMimcArgs& A)
+__device__ __forceinline__ void quotient_mimc_body(const QuotMimcArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n4) return;
@@ -667,38 +627,35 @@ template <bool U> __device__ __forceinline__ void quotient_mimc_body(const QuotM
     const auto t0 = weak(add(add(wo, wl), ldv(A.qcoef_f, i)));
     const auto t0sq = mulv(t0, t0);
     const auto t1 = weak(sub(mulv(t0sq, t0), wr));
-    const auto t2 = mul(weak(sub(mulv(mulv(wr, wr), t0), won)), cst<U>(A.alpha_m261));
+    const auto t2 = mul(weak(sub(mulv(mulv(wr, wr), t0), won)), cst<true>(A.alpha_m261));
     const auto sum = weak(add(t1, t2));
-    stv(A.q, i, add(mul(mul(sum, ldv(A.qsel_f, i)), cst<U>(A.abase_fix_m261)), ldv(A.q, i)));
+    stv(A.q, i, add(mul(mul(sum, ldv(A.qsel_f, i)), cst<true>(A.abase_fix_m261)), ldv(A.q, i)));
 }
-__global__ void __launch_bounds__(PT) k_quotient_mimc(QuotMimcArgs A) { quotient_mimc_body<false>(A); }
-__global__ void __launch_bounds__(PT, 8) k_quotient_mimc_lanes(const QuotMimcArgs* __restrict__ tab) { quotient_mimc_body<true>(tab[blockIdx.y]); } // one table record per lane
+__global__ void __launch_bounds__(PT, 8) k_quotient_mimc_lanes(const QuotMimcArgs* __restrict__ tab) { quotient_mimc_body(tab[blockIdx.y]); } // one table record per lane
 
 // sequential_widget.cpp:47-62: q[i] += c q_o_next[i] w_o[2i + 4] on the 2n coset (index 2i + 4 of the 4n evaluations = the next gate's row)
-template <bool U> __device__ __forceinline__ void quotient_seq_body(const QuotSeqArgs& A)
+__device__ __forceinline__ void quotient_seq_body(const QuotSeqArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n2) return;
     const uint32_t m4 = 2 * A.n2 - 1;
-    auto t = mul(mul(ldv(A.qon_f, i), ldv(A.wo_f, (2 * i + 4) & m4)), cst<U>(A.c_fix_m261));
+    auto t = mul(mul(ldv(A.qon_f, i), ldv(A.wo_f, (2 * i + 4) & m4)), cst<true>(A.c_fix_m261));
     stv(A.q, i, add(t, ldv(A.q, i)));
 }
-__global__ void __launch_bounds__(PT) k_quotient_seq(QuotSeqArgs A) { quotient_seq_body<false>(A); }
-__global__ void __launch_bounds__(PT) k_quotient_seq_lanes(const QuotSeqArgs* __restrict__ tab) { quotient_seq_body<true>(tab[blockIdx.y]); } // one table record per lane
+__global__ void __launch_bounds__(PT) k_quotient_seq_lanes(const QuotSeqArgs* __restrict__ tab) { quotient_seq_body(tab[blockIdx.y]); } // one table record per lane
 
 // bool_widget.cpp:62-100: q[i] += c_l q_bl (w_l^2 - w_l) + c_r q_br (w_r^2 - w_r) + c_o q_bo (w_o^2 - w_o), wires at index 2i
-template <bool U> __device__ __forceinline__ void quotient_bool_body(const QuotBoolArgs& A)
+__device__ __forceinline__ void quotient_bool_body(const QuotBoolArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n2) return;
     const FrV wl = ldv(A.wl_f, 2 * i), wr = ldv(A.wr_f, 2 * i), wo = ldv(A.wo_f, 2 * i);
-    auto tl = mul(mul(weak(sub(mulv(wl, wl), wl)), ldv(A.qbl_f, i)), cst<U>(A.cl_fix_m261));
-    auto tr = mul(mul(weak(sub(mulv(wr, wr), wr)), ldv(A.qbr_f, i)), cst<U>(A.cr_fix_m261));
-    auto to = mul(mul(weak(sub(mulv(wo, wo), wo)), ldv(A.qbo_f, i)), cst<U>(A.co_fix_m261));
+    auto tl = mul(mul(weak(sub(mulv(wl, wl), wl)), ldv(A.qbl_f, i)), cst<true>(A.cl_fix_m261));
+    auto tr = mul(mul(weak(sub(mulv(wr, wr), wr)), ldv(A.qbr_f, i)), cst<true>(A.cr_fix_m261));
+    auto to = mul(mul(weak(sub(mulv(wo, wo), wo)), ldv(A.qbo_f, i)), cst<true>(A.co_fix_m261));
     stv(A.q, i, add(add(add(tl, tr), to), ldv(A.q, i)));
 }
-__global__ void __launch_bounds__(PT) k_quotient_bool(QuotBoolArgs A) { quotient_bool_body<false>(A); }
-__global__ void __launch_bounds__(PT) k_quotient_bool_lanes(const QuotBoolArgs* __restrict__ tab) { quotient_bool_body<true>(tab[blockIdx.y]); } // one table record per lane
+__global__ void __launch_bounds__(PT) k_quotient_bool_lanes(const QuotBoolArgs* __restrict__ tab) { quotient_bool_body(tab[blockIdx.y]); } // one table record per lane
 
 // ---- witness check: does the witness satisfy the circuit in rows 0 .. n-2 (include/bbgpu.h, bbgpu_plonk_check_witness) --------------------------------
 // A zero test needs no canonical value: a fresh product (or shared-reduction sum of products) has exact limbs and a value below 2p, so it is zero modulo
@@ -740,11 +697,11 @@ __device__ __forceinline__ void check_commit(uint32_t bad, unsigned long long fi
 
 // One thread per row, strided.  The identities (arithmetic_widget.cpp:86-101, sequential_widget.cpp:47-62, bool_widget.cpp:62-100, mimc_widget.cpp:68-85) on
 // the VALUES: each must vanish on its own.  The widget set is the circuit's, the same for every lane: uniform branches.
-template <bool U> __device__ __forceinline__ void check_gates_body(const WitnessCheckArgs& A)
+__device__ __forceinline__ void check_gates_body(const WitnessCheckArgs& A)
 {
     const uint32_t nt = gridDim.x * blockDim.x, rows = A.n - 1;
     const bool has_seq = A.q_on != nullptr, has_bool = A.q_bl != nullptr, has_mimc = A.q_sel != nullptr;
-    const FrC one256 = cst<U>(A.one_m256), one261 = fe_from<Fr>(Fr::ONE);
+    const FrC one256 = cst<true>(A.one_m256), one261 = fe_from<Fr>(Fr::ONE);
     uint32_t bad = 0, kinds = 0;
     unsigned long long first = ~0ull;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += nt) {
@@ -779,13 +736,12 @@ template <bool U> __device__ __forceinline__ void check_gates_body(const Witness
     }
     check_commit(bad, first, kinds, &A.counts->gate_failures, &A.first->gate, &A.counts->kinds);
 }
-__global__ void __launch_bounds__(PT) k_check_gates(WitnessCheckArgs A) { check_gates_body<false>(A); }
-__global__ void __launch_bounds__(PT) k_check_gates_lanes(const WitnessCheckArgs* __restrict__ tab) { check_gates_body<true>(tab[blockIdx.y]); } // one table record per lane
+__global__ void __launch_bounds__(PT) k_check_gates_lanes(const WitnessCheckArgs* __restrict__ tab) { check_gates_body(tab[blockIdx.y]); } // one table record per lane
 
 // One thread per row: its three mapping entries, decoded as k_sigma_from_mapping decodes them; the value at the target (a 32-byte gather out of the lane's
 // three wire vectors) must equal the position's own value modulo r -- the difference is tested, the representatives may differ -- and the target must lie in
 // a constrained row.
-template <bool U> __device__ __forceinline__ void check_copies_body(const WitnessCheckArgs& A)
+__device__ __forceinline__ void check_copies_body(const WitnessCheckArgs& A)
 {
     const uint32_t nt = gridDim.x * blockDim.x, rows = A.n - 1;
     const FrC one261 = fe_from<Fr>(Fr::ONE);
@@ -808,14 +764,13 @@ template <bool U> __device__ __forceinline__ void check_copies_body(const Witnes
     }
     check_commit(bad, first, 0, &A.counts->copy_failures, &A.first->copy, nullptr);
 }
-__global__ void __launch_bounds__(PT) k_check_copies(WitnessCheckArgs A) { check_copies_body<false>(A); }
-__global__ void __launch_bounds__(PT) k_check_copies_lanes(const WitnessCheckArgs* __restrict__ tab) { check_copies_body<true>(tab[blockIdx.y]); } // one table record per lane
+__global__ void __launch_bounds__(PT) k_check_copies_lanes(const WitnessCheckArgs* __restrict__ tab) { check_copies_body(tab[blockIdx.y]); } // one table record per lane
 
 // Wires from composer variables: element e of the 3n wire cells (wire-major) is variables[index[e]], copied bit for bit -- no reduction, the wires path
 // uploads whatever representative the caller gave.  Two adjacent lanes per element, 16 bytes each: a wave reads 32 consecutive indices (each by both
-// lanes of its pair: one 128-byte request), gathers 32 rows of 32 bytes -- the gather k_check_copies does, out of a vector that sits in L2 / the Infinity
+// lanes of its pair: one 128-byte request), gathers 32 rows of 32 bytes -- the gather k_check_copies_lanes does, out of a vector that sits in L2 / the Infinity
 // Cache (2 MiB per lane at 2^16 gates) -- and stores 1 KiB contiguously.  Plain vector loads and stores, nothing else.
-__device__ __forceinline__ void expand_wires_body(const ExpandWiresArgs& A) // (one body for both kernels: it reads no cst<U>() constant)
+__device__ __forceinline__ void expand_wires_body(const ExpandWiresArgs& A)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, e = t >> 1, half = t & 1u;
     if (e >= 3u * A.n) return;
@@ -827,7 +782,6 @@ __device__ __forceinline__ void expand_wires_body(const ExpandWiresArgs& A) // (
     const uint32_t v = min(index[i], A.num_variables - 1u);
     reinterpret_cast<uint4*>(dst + (size_t)i * 8)[half] = reinterpret_cast<const uint4*>(A.variables + (size_t)v * 8)[half];
 }
-__global__ void __launch_bounds__(PT) k_expand_wires(ExpandWiresArgs A) { expand_wires_body(A); }
 __global__ void __launch_bounds__(PT) k_expand_wires_lanes(const ExpandWiresArgs* __restrict__ tab) { expand_wires_body(tab[blockIdx.y]); } // one table record per lane
 
 // polynomial_arithmetic.cpp:478-560: c[i] *= (x_i - w_n^-1) / ((x_i)^n - 1),  x_i = g w_N^i;  (x_i)^n - 1 takes k = N/n values
@@ -872,17 +826,16 @@ __global__ void __launch_bounds__(PT) k_l1_scale(uint32_t* __restrict__ l1, uint
 }
 
 // prover.cpp:520-528 + arithmetic_widget.cpp:106-126: r[i] = sum_j c_j p_j[i] over the seven coefficient-form polynomials
-template <bool U> __device__ __forceinline__ void lincomb_body(const LinCombArgs& A)
+__device__ __forceinline__ void lincomb_body(const LinCombArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
-    FrM acc = mul(ldv(A.p[0], i), cst<U>(A.c[0]));
-    for (int j = 1; j < A.count; j++) acc = tight2<Fr>(add(acc, mul(ldv(A.p[j], i), cst<U>(A.c[j]))));
+    FrM acc = mul(ldv(A.p[0], i), cst<true>(A.c[0]));
+    for (int j = 1; j < A.count; j++) acc = tight2<Fr>(add(acc, mul(ldv(A.p[j], i), cst<true>(A.c[j]))));
     if (A.out_add) acc = tight2<Fr>(add(acc, ldv(A.out_add, i)));
     stv(A.out, i, acc);
 }
-__global__ void __launch_bounds__(PT) k_lincomb(LinCombArgs A) { lincomb_body<false>(A); }
-__global__ void __launch_bounds__(PT) k_lincomb_lanes(const LinCombArgs* __restrict__ tab) { lincomb_body<true>(tab[blockIdx.y]); } // one table record per lane
+__global__ void __launch_bounds__(PT) k_lincomb_lanes(const LinCombArgs* __restrict__ tab) { lincomb_body(tab[blockIdx.y]); } // one table record per lane
 
 // ---- lane-batched forms of the small kernels (blockIdx.y = record of a device table, or lane of a strided vector) ------------------------------------
 __global__ void __launch_bounds__(PT) k_mul2c_lanes(const Mul2cArgs* __restrict__ tab)
@@ -892,6 +845,7 @@ __global__ void __launch_bounds__(PT) k_mul2c_lanes(const Mul2cArgs* __restrict_
     if (i >= A.n) return;
     stv(A.out, i, mul(mul(ldv(A.a, i), ldv(A.b, i)), cst<true>(A.c_fix_m261)));
 }
+// prover.cpp:253-269: dst (4n) = beta sigma(X) + w(X) + gamma in coefficient form, zero-padded
 __global__ void __launch_bounds__(PT) k_sigma_prepare_lanes(const SigmaPrepArgs* __restrict__ tab)
 {
     const SigmaPrepArgs& A = tab[blockIdx.y];
@@ -1011,19 +965,13 @@ int copy_pad(uint64_t* d_dst, const uint64_t* d_src, size_t n_src, size_t n_dst,
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
-int add_inplace(uint64_t* d_a, const uint64_t* d_b, size_t n, hipStream_t st)
-{
-    k_add_inplace<<<pw_blocks(n), PT, 0, st>>>((uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t)n);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
 int mul_pointwise(uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, size_t n, hipStream_t st)
 {
     k_mul<<<pw_blocks(n), PT, 0, st>>>((uint32_t*)d_out, (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t)n);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
-int mul2c(uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, size_t n, const host::Fr& c, hipStream_t st)
+static int mul2c(uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, size_t n, const host::Fr& c, hipStream_t st)
 {
     const host::Fr cf = host::fr_mul(c, host::fr_from_u64(32)); // c * 2^5: the FIX2 factor folded in
     k_mul2c<<<pw_blocks(n), PT, 0, st>>>((uint32_t*)d_out, (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t)n, host::limbs_m261(cf));
@@ -1094,7 +1042,7 @@ static void scan_fill(int mode, const ScanJob& J, uint8_t* base, ScanArgs& A, Sc
     }
 }
 static int scan_pair_at(int mode, const ScanJob* jobs, int count, uint8_t* base, hipStream_t st);
-int scan_pair(int mode, const ScanJob* jobs, int count, Scratch& S, hipStream_t st)
+static int scan_pair(int mode, const ScanJob* jobs, int count, Scratch& S, hipStream_t st)
 {
     if (count < 1 || count > 2) return BBGPU_ERR_ARG;
     size_t total = 0;
@@ -1252,34 +1200,6 @@ int evaluate(const uint64_t* d_coeffs, size_t n, const host::Fr& z, host::Fr* ou
     return BBGPU_OK;
 }
 
-// up to 10 evaluations (each at z[0] or z[1]) in one pair of launches; results land in the jobs' 32-byte device slots
-int evaluate_batch_to_device(const EvalJob* jobs, int count, const host::Fr z[2], Scratch& S, hipStream_t st)
-{
-    if (count < 1 || count > 10) return BBGPU_ERR_ARG;
-    int rc = S.ensure((size_t)10 * 256 * 32 + 64);
-    if (rc) return rc;
-    EvalBatchArgs A{};
-    A.T[0] = make_powtab(z[0]);
-    A.T[1] = make_powtab(z[1]);
-    A.partial = (uint32_t*)S.base;
-    uint32_t maxb = 1;
-    for (int j = 0; j < count; j++) {
-        const size_t n = jobs[j].n;
-        const uint32_t blocks = eval_blocks(n);
-        A.c[j] = (const uint32_t*)jobs[j].coeffs;
-        A.n[j] = (uint32_t)n;
-        A.blocks[j] = blocks;
-        A.zsel[j] = (uint8_t)(jobs[j].zsel ? 1 : 0);
-        A.zT[j] = host::limbs_m261(host::fr_pow(z[A.zsel[j]], (uint64_t)blocks * PT));
-        A.result[j] = (uint32_t*)jobs[j].d_result;
-        maxb = std::max(maxb, blocks);
-    }
-    k_eval_partial_batch<<<dim3(maxb, count), PT, 0, st>>>(A);
-    k_sum_small_batch<<<count, PT, 0, st>>>(A);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
 // fr::batch_invert (field.hpp:503-522) on a resident vector: inv(a_i) = (prod_{j<i} a_j)(prod_{j>i} a_j) / prod_j a_j.
 // Two product scans and ONE field inversion on the host (10 us; a Fermat chain on one GPU lane takes ~0.25 ms).
 // d_tmp: n elements of workspace.  All a_i must be non-zero (the reference's loop has the same precondition).
@@ -1321,25 +1241,6 @@ static void z_terms_challenges(ZTermsArgs& A, const host::Fr& beta, const host::
     A.beta_k2_m256 = host::limbs_m256(host::fr_mul(beta, host::fr_from_limbs(FrHostP::GEN7)));
     A.gamma_m256 = host::limbs_m256(gamma);
 }
-int z_terms(ZTermsArgs A, const host::Fr& root, const host::Fr& beta, const host::Fr& gamma, hipStream_t st)
-{
-    const uint32_t blocks = strided_blocks(A.n);
-    A.root = make_powtab(root);
-    A.step_m261 = host::limbs_m261(host::fr_pow(root, (uint64_t)blocks * PT));
-    z_terms_challenges(A, beta, gamma);
-    k_z_terms<<<blocks, PT, 0, st>>>(A);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-int sigma_prepare(uint64_t* d_dst, const uint64_t* d_sigma, const uint64_t* d_w, size_t n, size_t n_dst, const host::Fr& gamma, hipStream_t st)
-{
-    k_sigma_prepare<<<pw_blocks(n_dst), PT, 0, st>>>((uint32_t*)d_dst, (const uint32_t*)d_sigma, (const uint32_t*)d_w, (uint32_t)n, (uint32_t)n_dst,
-                                                    host::limbs_m256(gamma));
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
 static void quotient_large_challenges(QuotLargeArgs& A, const host::Fr& beta, const host::Fr& gamma)
 {
     A.beta_m256 = host::limbs_m256(beta);
@@ -1347,18 +1248,6 @@ static void quotient_large_challenges(QuotLargeArgs& A, const host::Fr& beta, co
     A.beta_k2_m256 = host::limbs_m256(host::fr_mul(beta, host::fr_from_limbs(FrHostP::GEN7)));
     A.gamma_m256 = host::limbs_m256(gamma);
 }
-int quotient_large(QuotLargeArgs A, const host::Fr& root4n, const host::Fr& beta, const host::Fr& gamma, hipStream_t st)
-{
-    const uint32_t blocks = strided_blocks(A.n4);
-    A.root = make_powtab(root4n);
-    A.g_m261 = host::limbs_m261(host::fr_from_limbs(FrHostP::GEN5));
-    A.step_m261 = host::limbs_m261(host::fr_pow(root4n, (uint64_t)blocks * PT));
-    quotient_large_challenges(A, beta, gamma);
-    k_quotient_large<<<blocks, PT, 0, st>>>(A);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
 static void quotient_mid_challenges(QuotMidArgs& A, const host::Fr& alpha, const host::Fr& alpha_base)
 {
     const host::Fr f2 = host::fr_from_u64(32), f3 = host::fr_from_u64(1024);
@@ -1369,42 +1258,6 @@ static void quotient_mid_challenges(QuotMidArgs& A, const host::Fr& alpha, const
     A.abase_fix2_m261 = host::limbs_m261(host::fr_mul(alpha_base, f2));
     A.abase_fix3_m261 = host::limbs_m261(host::fr_mul(alpha_base, f3));
 }
-int quotient_mid(QuotMidArgs A, const host::Fr& alpha, const host::Fr& alpha_base, hipStream_t st)
-{
-    quotient_mid_challenges(A, alpha, alpha_base);
-    k_quotient_mid<<<pw_blocks(A.n2), PT, 0, st>>>(A);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-int quotient_mimc(QuotMimcArgs A, const host::Fr& alpha_base, const host::Fr& alpha_step, hipStream_t st)
-{
-    A.alpha_m261 = host::limbs_m261(alpha_step);
-    A.abase_fix_m261 = host::limbs_m261(host::fr_mul(alpha_base, host::fr_from_u64(32)));
-    k_quotient_mimc<<<pw_blocks(A.n4), PT, 0, st>>>(A);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-int quotient_seq(QuotSeqArgs A, const host::Fr& c, hipStream_t st)
-{
-    A.c_fix_m261 = host::limbs_m261(host::fr_mul(c, host::fr_from_u64(32)));
-    k_quotient_seq<<<pw_blocks(A.n2), PT, 0, st>>>(A);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-int quotient_bool(QuotBoolArgs A, const host::Fr& c_left, const host::Fr& c_right, const host::Fr& c_out, hipStream_t st)
-{
-    const host::Fr f2 = host::fr_from_u64(32);
-    A.cl_fix_m261 = host::limbs_m261(host::fr_mul(c_left, f2));
-    A.cr_fix_m261 = host::limbs_m261(host::fr_mul(c_right, f2));
-    A.co_fix_m261 = host::limbs_m261(host::fr_mul(c_out, f2));
-    k_quotient_bool<<<pw_blocks(A.n2), PT, 0, st>>>(A);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
 // the records of `lanes` lanes, consecutive from counts / first: zero the counts, all ones (= none) into the atomicMin words
 static int check_witness_preset(WitnessCheckCounts* counts, WitnessCheckFirst* first, int lanes, hipStream_t st)
 {
@@ -1412,24 +1265,6 @@ static int check_witness_preset(WitnessCheckCounts* counts, WitnessCheckFirst* f
     HIPCHK(hipMemsetAsync(first, 0xff, sizeof(WitnessCheckFirst) * (size_t)lanes, st));
     return BBGPU_OK;
 }
-int check_witness(WitnessCheckArgs A, hipStream_t st)
-{
-    A.one_m256 = host::limbs_m256(host::fr_one());
-    if (int rc = check_witness_preset(A.counts, A.first, 1, st)) return rc;
-    const uint32_t blocks = strided_blocks(A.n);
-    k_check_gates<<<blocks, PT, 0, st>>>(A);
-    HIPCHK(launch_check());
-    k_check_copies<<<blocks, PT, 0, st>>>(A);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-int expand_wires(ExpandWiresArgs A, hipStream_t st)
-{
-    k_expand_wires<<<pw_blocks((size_t)6 * A.n), PT, 0, st>>>(A); // two lanes per element, 3n elements
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
 // g^n for n = 2^log2n
 static host::Fr coset_gen_pow_n(int log2n)
 {
@@ -1508,14 +1343,6 @@ int lagrange_l1_fft(uint64_t* d_l1, uint64_t* d_tmp, int log2n, int log2N, Scrat
         s[j] = host::limbs_m261(v);
     }
     k_l1_scale<<<pw_blocks(N), PT, 0, st>>>((uint32_t*)d_l1, (uint32_t)N, k, s[0], s[1], s[2], s[3]);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-int lincomb(LinCombArgs A, const host::Fr* coeffs, hipStream_t st)
-{
-    for (int j = 0; j < A.count; j++) A.c[j] = host::limbs_m261(coeffs[j]);
-    k_lincomb<<<pw_blocks(A.n), PT, 0, st>>>(A);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
@@ -1719,7 +1546,7 @@ int add_inplace_lanes(uint64_t* d_a, size_t stride_a, const uint64_t* d_b, size_
     return BBGPU_OK;
 }
 
-// scan_pair over a table of jobs: the same phases, grid.y = job.  All jobs have one length, so one grid shape serves them; up to 2^22 elements the scan
+// the scans of scan_pair_at over a table of jobs: the same phases, grid.y = job.  All jobs have one length, so one grid shape serves them; up to 2^22 elements the scan
 // over the block totals is the fused form (<= SCAN_T blocks) or one workgroup per job.
 int scan_lanes(int mode, const ScanJob* jobs, int count, LaneTable& T, Scratch& S, hipStream_t st)
 {

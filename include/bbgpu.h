@@ -357,7 +357,11 @@ typedef struct {
 #define BBGPU_PLONK_PROOF_WORDS 120
 int bbgpu_plonk_prover_create(const bbgpu_plonk_circuit* circuit, int srs_handle); /* returns a prover handle >= 0 */
 int bbgpu_plonk_prover_set_witness(int prover, const uint64_t* w_l, const uint64_t* w_r, const uint64_t* w_o);
-int bbgpu_plonk_construct_proof(int prover, uint64_t proof_out[BBGPU_PLONK_PROOF_WORDS]); /* Prover::construct_proof, prover.cpp:661-670 */
+/* Prover::construct_proof (prover.cpp:661-670) of the witness the handle holds.  It is a batch of one over a lane of the handle's own (see
+ * bbgpu_plonk_construct_proof_batch below): the same rounds, kernels and copies, so it passes the "h2d" / "d2h" funnels of bbgpu_fault_inject as a batch
+ * does -- the records its kernels read are uploaded, its evaluations read back, through them.  On a failure proof_out is not written, no MSM ticket is
+ * outstanding and the handle stays usable.  It touches neither bbgpu_plonk_batch_challenges nor bbgpu_plonk_last_batch_timing. */
+int bbgpu_plonk_construct_proof(int prover, uint64_t proof_out[BBGPU_PLONK_PROOF_WORDS]);
 /* waffle::preprocess(prover) (preprocess.hpp:16-55, arithmetic_widget.cpp:128-157, bool_widget.cpp:118-152): the verification key of
  * the circuit -- SIGMA_1, SIGMA_2, SIGMA_3, the commitments to q_m, q_l, q_r, q_o, q_c, and with the bool widget those to q_bl, q_br,
  * q_bo, with the MiMC widget q_mimc_coefficient, q_mimc_selector, with the sequential widget q_o_next (before the bool widget's three) --
@@ -373,8 +377,8 @@ int bbgpu_plonk_last_timing(int prover, double ms_out[4]);     /* construct_proo
  * proof j is, byte for byte, what bbgpu_plonk_prover_set_witness(w_l[j], w_r[j], w_o[j]) + bbgpu_plonk_construct_proof would return.
  * BBGPU_ERR_ARG: unknown handle, count < 1, count > BBGPU_PLONK_MAX_BATCH, a null array or a null entry; BBGPU_ERR_SIZE: count * n > 2^22 (the lanes
  * hold 48 vectors of n x 32 bytes each: 96 MiB per lane at 2^16 gates, 6 GiB at the bound).  These checks come before the library binds a device.
- * The lanes are allocated on the first batch, grown when a larger count arrives, released with the handle, and counted in
- * bbgpu_memory_info.staging_bytes.  The call touches neither the witness the handle holds for bbgpu_plonk_construct_proof nor
+ * The batch lanes are allocated on the first batch, grown when a larger count arrives, released with the handle, and counted in
+ * bbgpu_memory_info.staging_bytes (the handle's own lane, which the single entries use, is part of the handle from its creation).  The call touches neither the witness the handle holds for bbgpu_plonk_construct_proof nor
  * bbgpu_plonk_last_challenges / _last_timing.  On a failure every MSM ticket the call issued has been collected and the handle stays usable. */
 #define BBGPU_PLONK_MAX_BATCH 16
 int bbgpu_plonk_construct_proof_batch(int prover, int count, const uint64_t* const* w_l, const uint64_t* const* w_r, const uint64_t* const* w_o,

@@ -181,10 +181,18 @@ def test_single_proof_after_a_batch_is_unchanged(gpu, srs_for, golden, gates):
         for name in CH:
             assert np.array_equal(after_ch[name], ch_before[name]), name
         assert B.batch.timing() == t_before
+        batch_ch = [{k: v.copy() for k, v in B.batch.batch_challenges(lane).items()} for lane in range(3)]
+        batch_t = B.batch.batch_timing()
         after = B.batch.construct_proof()
         assert np.array_equal(after, before) and proof_lines(B.n, after) == gold
         for name in CH:
             assert hx(B.batch.challenges()[name])[0] == tr["challenges"][str(gates)][name], name
+        # and the other way round: the single proof runs through the same rounds, and leaves what the batch reported alone
+        for lane in range(3):
+            got = B.batch.batch_challenges(lane)
+            for name in CH:
+                assert np.array_equal(got[name], batch_ch[lane][name]), (lane, name)
+        assert B.batch.batch_timing() == batch_t
     finally:
         B.destroy()
 

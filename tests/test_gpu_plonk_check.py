@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the witness check of the resident prover: bbgpu_plonk_check_witness / _check_witness_batch (poly.hip k_check_gates / k_check_copies,
+"""GPU tests (-m gpu) of the witness check of the resident prover: bbgpu_plonk_check_witness / _check_witness_batch (poly.hip k_check_gates_lanes / k_check_copies_lanes,
 single and lane-batched), the opt-in gate bbgpu_plonk_set_witness_check in front of construct_proof / construct_proof_batch, and their funnel counts.
 Three bars: (1) every GPU report equals the host entry's for the same witness, field by field (the host entry is held to the plain-Python model in
 tests/test_plonk_check_host.py); (2) the REFERENCE'S VERIFIER judges the definition: a proof made with the check off verifies iff the report is all-clear;

@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of the witness forms of the resident prover: bbgpu_plonk_prover_set_wire_map, bbgpu_plonk_witness and the three *_from entries
-(plonk.hip load_lanes / set_witness_from, poly.hip k_expand_wires / k_expand_wires_lanes).  A witness may come as expanded wires or as the composer's
+(plonk.hip load_lanes / set_witness_from, poly.hip k_expand_wires_lanes).  A witness may come as expanded wires or as the composer's
 variables, from host memory or from device memory handed over from torch.  The bar is the wires path's: whatever the form and the place, every lane's
 proof, challenges and check report are byte for byte what set_witness + construct_proof / bbgpu_host_plonk_check_witness give for the expanded wires,
 lane 0 equals the reference's golden proof, and the reference's own Verifier accepts a lane.  Witness j of a batch is the circuit built with other
