@@ -97,8 +97,6 @@ struct MsmSlot {
 };
 int msm_choose_c(size_t n);
 int msm_num_windows(int c);
-int msm_issue(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, size_t tab_stride, int tab_c, const uint64_t* d_scalars, size_t n, int wb,
-              int we, hipStream_t st, int want_timing);
 int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, size_t tab_stride, int tab_c, const uint64_t* const* d_scalars_v, int jobs,
                     size_t n, int wb, int we, hipStream_t st, int want_timing, uint32_t row_i0 = 0, uint32_t row_i1 = 0xffffffffu, uint32_t brow0 = 0,
                     uint32_t brow1 = 0xffffffffu);
@@ -108,7 +106,6 @@ int msm_issue_rows(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, siz
                    uint64_t row_begin, uint64_t row_end, hipStream_t st, int want_timing);
 int msm_finish_batch(MsmSlot& S, host::Xyzz* results, MsmTiming* timing);
 int srs_build_table(const uint32_t* d_srs, size_t n, int c, int num_windows, int w_begin, int w_end, uint32_t** d_alloc_out, uint32_t** d_tab_out, hipStream_t st);
-int msm_finish(MsmSlot& S, host::Xyzz* result, MsmTiming* timing);
 int srs_upload(const uint64_t* host_table, size_t n, uint32_t** d_srs_out, hipStream_t st, size_t stride_bytes = 128);
 int srs_upload_into(const uint64_t* host_table, size_t n, uint32_t* d_raw, uint32_t* d_srs, hipStream_t st, size_t stride_bytes);
 int srs_generate(const uint64_t* x_mont256, size_t first, size_t n, uint32_t** d_srs_out, uint64_t* host_table_out, hipStream_t st);

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <optional>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -688,13 +689,9 @@ struct SlotReservation {
         if (b >= 0) ctx().slot[b].reserved = false;
     }
 };
-int ensure_slot_stream(MsmSlot& S)
-{
-    if (!S.stream) CHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-    return BBGPU_OK;
-}
 
 // The pieces of the point range [off, off + n) of an entry: one per table segment it touches (one in all without tables or inside one segment).
+// -1 (with the error text): more than `cap`.
 struct PointPiece {
     const SrsEntry::TabSeg* seg; // null: no tables
     size_t off_in_seg, first, len; // first: offset inside the call's range (and its scalars)
@@ -713,7 +710,10 @@ int split_pieces(const SrsEntry& e, size_t off, size_t n, PointPiece* out, int c
     for (const auto& sg : e.segs) {
         const size_t lo = std::max(off, sg.first), hi = std::min(off + n, sg.first + sg.n);
         if (lo >= hi) continue;
-        if (cnt == cap) return -1;
+        if (cnt == cap) {
+            set_error("MSM of %zu points spans more than %d table segments", n, cap);
+            return -1;
+        }
         out[cnt++] = PointPiece{ &sg, lo - sg.first, lo - off, hi - lo };
     }
     return cnt;
@@ -739,6 +739,14 @@ void drain_ticket(int t)
     }
     if (S.pending) (void)msm_finish_batch(S, dump, nullptr);
 }
+// the same for n tickets after a failure: the slots are usable again, and the error text stays the first failure's
+void drain_tickets(const int* t, int n)
+{
+    char keep[sizeof(g_err)];
+    memcpy(keep, g_err, sizeof(keep));
+    for (int k = 0; k < n; k++) drain_ticket(t[k]);
+    memcpy(g_err, keep, sizeof(keep));
+}
 // Issues `jobs` MSMs (one scalar vector each) over points [off, off + n) of entry e, windows [wb, we), on slot t; `st` = the caller's stream or the
 // slot's own.  Inside one table segment (every SRS up to 2^20 points) that is one pass through the kernels.  A range that spans several segments
 // is issued as one PIECE per segment, dealt alternately to slot t and -- when one is free -- a HELPER slot with its own stream and workspace, so
@@ -753,10 +761,7 @@ int issue_ticket(int t, const SrsEntry& e, size_t off, const uint64_t* const* d_
     if (!windows_resident(e, wb, we)) return BBGPU_ERR_STATE;
     PointPiece pc[MAX_POINT_PIECES];
     const int np = split_pieces(e, off, n, pc, MAX_POINT_PIECES);
-    if (np < 0) {
-        set_error("MSM of %zu points spans more than %d table segments", n, MAX_POINT_PIECES);
-        return BBGPU_ERR_SIZE;
-    }
+    if (np < 0) return BBGPU_ERR_SIZE;
     if (np == 1) {
         S.throughput = others_pending(&S);
         const uint32_t* tab = pc[0].seg ? pc[0].seg->d_tab + pc[0].off_in_seg * 16 : nullptr;
@@ -773,7 +778,6 @@ int issue_ticket(int t, const SrsEntry& e, size_t off, const uint64_t* const* d_
     }
     MsmSlot* H = h >= 0 ? &ctx().slot[h] : nullptr;
     if (H) {
-        if (int rc = ensure_slot_stream(*H)) return rc;
         // `st` carries the producer of the scalars -- a caller's kernel, or the asynchronous upload host_to_device() queued on the slot's OWN stream
         // (bbgpu_msm_g1 / _batch): the helper's stream starts behind what is enqueued there now, whichever stream that is
         if (!ctx().helper_dep[h]) CHK(hipEventCreateWithFlags(&ctx().helper_dep[h], hipEventDisableTiming));
@@ -807,17 +811,8 @@ int issue_ticket(int t, const SrsEntry& e, size_t off, const uint64_t* const* d_
         H->is_helper = true;
         S.helper = h;
     }
-    if (rc != BBGPU_OK) {
-        char keep[sizeof(g_err)];
-        memcpy(keep, g_err, sizeof(keep));
-        drain_ticket(t);
-        memcpy(g_err, keep, sizeof(keep));
-    }
+    if (rc != BBGPU_OK) drain_tickets(&t, 1);
     return rc;
-}
-int issue_on_entry(int t, const SrsEntry& e, size_t off, const uint64_t* d_scalars, size_t n, int wb, int we, hipStream_t st)
-{
-    return issue_ticket(t, e, off, &d_scalars, 1, n, wb, we, st);
 }
 // waits for ticket t and adds up its pieces: one point per job
 int finish_ticket(int t, host::Xyzz* results, MsmTiming* timing)
@@ -945,6 +940,128 @@ void srs_mark_stale(int idx)
     else e.stale_for_host = true;
 }
 
+double now_ms() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+
+// How the host scalars of bbgpu_msm_g1 / _plain / _batch go through the MSM slots: the one place that knows.  A call opens the pipeline on the (up to
+// two) slots that are free, PUSHES point ranges against resolved tables -- the ranges of one MSM, or of the jobs of a batch -- and FINISHES.  Ticket k rides
+// slot k mod slots with that slot's staging buffer: the scalars of range k+1 cross the link and its kernels are enqueued while the bucket-reduction
+// tail and the host finish of range k run (a prover round's 3/1/3/2 MSMs, prover.cpp:65-122,650-658).  Tickets are collected in issue order and their
+// sums handed to done(tag, sum).  Whatever fails -- here or in the caller between two pushes -- nothing of the call stays in flight: every slot is
+// drained, at once or by the destructor, and the error text stays the first failure's.
+size_t largest_piece(const PointPiece* pc, int np) { size_t m = 0; for (int k = 0; k < np; k++) m = std::max(m, pc[k].len); return m; }
+// tickets of a pipeline on `slots` slots that have been collected once room is made for push number p: all but the slots - 1 before it
+size_t collected_before(size_t p, int slots) { return p - std::min(p, (size_t)std::max(slots, 1) - 1); }
+template <class Done> struct HostMsmPipeline { // Done: void(size_t tag, const host::Xyzz& sum)
+    int sl[2] = { -1, -1 }, ns = 0; // whatever slots are free (a caller -- or another thread -- may hold asynchronous tickets on any of them): two give the pipeline, one works
+    Done done;
+    double ms_push = 0, ms_wait = 0; // BBGPU_TRACE_SRS: time spent so far in uploads + launches, in collections
+
+    explicit HostMsmPipeline(Done d) : done(std::move(d)) {}
+    HostMsmPipeline(const HostMsmPipeline&) = delete;
+    ~HostMsmPipeline()
+    {
+        if (bg.posted) (void)full_check_join(bg); // the job reads the caller's table and the entry's fingerprints
+        drain();
+    }
+    int open()
+    {
+        if (int rc = ensure_init()) return rc;
+        if ((ns = free_slots(sl, 2)) == 0) {
+            set_error("all %d MSM slots are in flight: call bbgpu_msm_g1_wait first", Context::NSLOT);
+            return BBGPU_ERR_STATE;
+        }
+        reserve.emplace(sl, ns); // the slots of the rotation are nobody's helper (every push lies inside one table segment and asks for none itself)
+        return BBGPU_OK;
+    }
+    hipStream_t first_stream() const { return ctx().slot[sl[0]].stream; } // of the slot the first push takes
+    // frees the slot and staging buffer of the next push: collects the ticket that still holds them
+    int make_room() { return collected < collected_before(issued, ns) ? collect() : BBGPU_OK; }
+    // host scalars [0, len) against points [off, off + len) of e; stage_bytes: the largest range the caller will push (the staging buffers are sized once)
+    int push(const SrsEntry& e, size_t off, const uint64_t* scalars, size_t len, size_t stage_bytes, size_t tag, MsmTiming* timing)
+    {
+        if (int rc = make_room()) return rc;
+        const size_t w = issued % (size_t)ns;
+        MsmSlot& S = ctx().slot[sl[w]];
+        const double t0 = tr ? now_ms() : 0;
+        int rc = grow(stage[w], cap[w], stage_bytes);
+        if (rc == BBGPU_OK) rc = host_to_device(*stage[w], scalars, len * 32, S.stream);
+        if (rc == BBGPU_OK) rc = issue_ticket(sl[w], e, off, stage[w], 1, len, 0, entry_windows(e, len), S.stream);
+        if (rc) { drain(); return rc; }
+        if (tr) ms_push += now_ms() - t0;
+        fl[w] = InFlight{ tag, timing };
+        issued++;
+        return BBGPU_OK;
+    }
+    // EXACT mode: rows [off, off + n) of entry idx are compared in full with the caller's table by finish(), once per distinct range, on the host beside
+    // the kernels issued by then.  background: the call's scalars bypass the staging pool (uploads above host_stage_max go to hipMemcpyAsync as they
+    // are), so the check starts NOW on the pool's helper threads -- before the upload -- and is joined in finish()
+    void check_in_full(int idx, size_t off, const uint64_t* points, size_t n, bool background)
+    {
+        for (const auto& c : checks)
+            if (c.idx == idx && c.off == off && c.n == n) return;
+        if (background && checks.empty()) full_check_post(bg, ctx().srs[idx], off, points, n);
+        checks.push_back(Check{ idx, off, points, n });
+    }
+    // the exact-mode checks, then the collection of what is in flight.  *stale: a resident table differs from the caller's memory and was dropped;
+    // nothing is in flight, and what done() has been handed came from the stale copy: the caller's rerun replaces all of it
+    int finish(bool* stale)
+    {
+        for (size_t k = 0; k < checks.size(); k++) {
+            const Check& c = checks[k];
+            const bool same = (k == 0 && bg.posted) ? full_check_join(bg) : !ctx().srs[c.idx].live || contents_match_full(ctx().srs[c.idx], c.off, c.points, c.n);
+            if (!same) {
+                srs_mark_stale(c.idx);
+                *stale = true;
+            }
+        }
+        if (*stale) {
+            drain();
+            return BBGPU_OK;
+        }
+        while (collected < issued)
+            if (int rc = collect()) return rc;
+        return BBGPU_OK;
+    }
+
+private:
+    struct InFlight { size_t tag; MsmTiming* timing; } fl[2] = {};
+    size_t issued = 0, collected = 0;
+    uint64_t** stage[2] = { &ctx().d_stage, &ctx().d_stage2 };
+    size_t* cap[2] = { &ctx().stage_cap, &ctx().stage2_cap };
+    std::optional<SlotReservation> reserve;
+    struct Check { int idx; size_t off; const uint64_t* points; size_t n; };
+    std::vector<Check> checks;
+    FullCheckJob bg; // checks[0], when it runs in the background
+    const bool tr = trace_srs();
+
+    int collect() // the oldest ticket in flight
+    {
+        const size_t w = collected++ % (size_t)ns;
+        const double t0 = tr ? now_ms() : 0;
+        host::Xyzz sum;
+        if (int rc = finish_ticket(sl[w], &sum, fl[w].timing)) { drain(); return rc; }
+        done(fl[w].tag, sum);
+        if (tr) ms_wait += now_ms() - t0;
+        return BBGPU_OK;
+    }
+    void drain() // nothing of the call stays in flight
+    {
+        drain_tickets(sl, ns);
+        collected = issued;
+    }
+};
+
+// EXACT cache mode: a call runs against the resident copy of a table while the host re-hashes every row of the caller's; if they differ the copy is
+// dropped and the call runs once more, now uploading the table as it is (the reference reads the caller's points on every call,
+// scalar_multiplication.cpp:604-617).  Exactly one rerun.
+template <class Once> int rerun_if_stale(Once once)
+{
+    bool stale = false;
+    int rc = once(&stale);
+    if (stale) rc = once(&stale);
+    return rc;
+}
+
 int log2_exact(size_t n)
 {
     if (n == 0 || (n & (n - 1))) return -1;
@@ -960,13 +1077,7 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
 // the sum before normalisation: a context's partial sum of a split call (bbgpu_msm_g1) is added to the others' first
 int msm_host_ptrs_sum(const uint64_t* scalars, const uint64_t* points, size_t n, host::Xyzz* out, bool plain = false)
 {
-    // EXACT cache mode: the call runs against the resident copy while the host re-hashes every row of the caller's table; if they differ the
-    // copy is dropped and the call runs once more, now uploading the table as it is (the reference reads the caller's points on every call,
-    // scalar_multiplication.cpp:604-617)
-    bool stale = false;
-    int rc = msm_host_ptrs_once(scalars, points, n, out, plain, &stale);
-    if (stale) rc = msm_host_ptrs_once(scalars, points, n, out, plain, &stale);
-    return rc;
+    return rerun_if_stale([&](bool* stale) { return msm_host_ptrs_once(scalars, points, n, out, plain, stale); });
 }
 int msm_host_ptrs(const uint64_t* scalars, const uint64_t* points, size_t n, uint64_t out[12], bool plain = false)
 {
@@ -994,62 +1105,41 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
         *out = host::msm_small(scalars, points, n, plain ? 8 : 16);
         return BBGPU_OK;
     }
-    {
-        int rc = ensure_init();
-        if (rc) return rc;
-    }
-    // whatever slots are free (a caller -- or another thread -- may hold asynchronous tickets on any of them): two give the pipeline, one works
-    int sl[2];
-    const int ns = free_slots(sl, 2);
-    if (ns == 0) {
-        set_error("all %d MSM slots are in flight: call bbgpu_msm_g1_wait first", Context::NSLOT);
-        return BBGPU_ERR_STATE;
-    }
-    for (int k = 0; k < ns; k++)
-        if (int rc = ensure_slot_stream(ctx().slot[sl[k]])) return rc;
-    SlotReservation reserve(sl, ns);
+    host::Xyzz res = host::g1_infinity();
+    HostMsmPipeline P([&res](size_t, const host::Xyzz& part) { res = host::g1_add(res, part); });
+    if (int rc = P.open()) return rc;
+    // exact cache mode on a table large enough that the scalars bypass the staging pool: the full check starts NOW, before the upload
+    if (full_check) P.check_in_full(idx, off, points, n, n * 32 > ctx().host_stage_max);
     // A table that was never registered and is too small to be an SRS (the verifier's ~20 freshly built points,
     // verifier.cpp:359-363) is used once and forgotten: caching it by address would both leak device memory per call and
     // serve stale points when the caller's vector is freed and its address reused.  Larger unknown tables are taken to be a
     // long-lived SRS and registered on first sight.
-    // exact cache mode on a table large enough that the scalars bypass the staging pool: the full check starts NOW, on the pool's helper threads, and is joined
-    // once the kernels are issued (every way out of this function joins it first: the job reads the caller's table and the entry's fingerprints)
-    FullCheckJob bg;
-    struct BgGuard { FullCheckJob& j; ~BgGuard() { if (j.posted) (void)full_check_join(j); } } bg_guard{ bg };
-    if (full_check && n * 32 > ctx().host_stage_max) full_check_post(bg, ctx().srs[idx], off, points, n);
     SrsEntry transient{};
     const bool is_transient = idx < 0 && (plain || n < AUTO_REGISTER_MIN_POINTS);
     const bool tr = trace_srs();
-    auto now_ms = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double q0 = tr ? now_ms() : 0;
     // a small table that is used once (the verifier's freshly built points, test tables): uploaded into a buffer the library keeps, on the stream of the
     // slot that runs the call's one range -- no allocation, no free, no wait (round 5: those were ~0.05 of the 0.39 ms such a call took)
     const bool small_once = is_transient && n < AUTO_REGISTER_MIN_POINTS;
-    if (small_once) {
-        const size_t stride = plain ? 64 : 128;
-        int rc = grow(&ctx().d_small_tab, &ctx().small_tab_cap, AUTO_REGISTER_MIN_POINTS * (128 + 64));
-        if (rc) return rc;
-        uint32_t* d_raw = (uint32_t*)ctx().d_small_tab;
-        uint32_t* d = d_raw + AUTO_REGISTER_MIN_POINTS * 32;
-        if ((rc = srs_upload_into(points, n, d_raw, d, ctx().slot[sl[0]].stream, stride)) != BBGPU_OK) return rc;
-        transient.host_ptr = points;
-        transient.n = n;
-        transient.d_srs = d;
-        transient.live = true;
-        off = 0;
-    } else
     if (idx < 0) {
         uint32_t* d = nullptr;
-        int rc = srs_upload(points, n, &d, ctx().stream, plain ? 64 : 128);
+        int rc = BBGPU_OK;
+        if (small_once) {
+            if ((rc = grow(&ctx().d_small_tab, &ctx().small_tab_cap, AUTO_REGISTER_MIN_POINTS * (128 + 64))) != BBGPU_OK) return rc;
+            uint32_t* d_raw = (uint32_t*)ctx().d_small_tab;
+            d = d_raw + AUTO_REGISTER_MIN_POINTS * 32;
+            rc = srs_upload_into(points, n, d_raw, d, P.first_stream(), plain ? 64 : 128);
+        } else {
+            rc = srs_upload(points, n, &d, ctx().stream, plain ? 64 : 128);
+        }
         if (rc) return rc;
         if (is_transient) {
             transient.host_ptr = points;
             transient.n = n;
             transient.d_srs = d;
             transient.live = true;
-        } else {
-            idx = add_srs(points, n, d, true);
-            if (idx < 0) return idx;
+        } else if ((idx = add_srs(points, n, d, true)) < 0) {
+            return idx;
         }
         off = 0;
     }
@@ -1059,76 +1149,34 @@ int msm_host_ptrs_once(const uint64_t* scalars, const uint64_t* points, size_t n
     // added on the host.  Above 2^20 points the ranges are the table segments the call touches (each at most 2^20 points with its own window
     // tables); inside one segment a call of 2^19 points and more is cut in two -- one 2^20-point call: 32 MiB of scalars = 0.6 ms on the link
     // before the first kernel, against 0.22 ms for the first of two ranges (bench.py `boundary`).  BBGPU_HOST_MSM_SPLIT=1 keeps one range per segment.
-    static const size_t split_env = [] { const char* v = getenv("BBGPU_HOST_MSM_SPLIT"); return v ? (size_t)std::max(1, atoi(v)) : (size_t)0; }();
-    struct Range { size_t o, len; };
-    std::vector<Range> ranges;
-    {
-        PointPiece pc[MAX_POINT_PIECES];
-        const int np = split_pieces(e, off, n, pc, MAX_POINT_PIECES);
-        if (np < 0) {
-            if (is_transient && !small_once) (void)dev_free(transient.d_srs);
-            set_error("MSM of %zu points spans more than %d table segments", n, MAX_POINT_PIECES);
-            return BBGPU_ERR_SIZE;
-        }
-        if (np > 1) {
-            for (int k = 0; k < np; k++) ranges.push_back(Range{ pc[k].first, pc[k].len });
-        } else {
-            // Measured on MI355X (tools/boundary_ab.py, 2^20 points): one range 2.05-2.08 ms, two 1.77 ms, four 2.17-2.20 ms -- every range pays its
-            // own sort and bucket-reduction tail (~0.3 ms of launches that only partly hide), so two it is, the first one the smaller: its
-            // upload is the part nothing hides, and the second range's upload (0.6 ms x its share) still fits under the first one's kernels.
-            const size_t parts = ns < 2 ? 1 : (split_env ? split_env : (n >= ((size_t)1 << 19) ? 2 : 1));
-            // first range 3/8 of the points; measured 25 / 30 / 34 / 37 / 42 %: 1.84 / 1.80 / 1.83 / 1.775 / 1.79 ms
-            const size_t base = parts == 2 ? ((n * 3 / 8) & ~(size_t)7) : n / parts;
-            for (size_t k = 0; k < parts; k++) {
-                const size_t o = k * base, len = (k + 1 == parts) ? n - o : base;
-                if (len) ranges.push_back(Range{ o, len });
-            }
+    static const size_t split_env = [] { const char* v = getenv("BBGPU_HOST_MSM_SPLIT"); return v ? (size_t)std::min(MAX_POINT_PIECES, std::max(1, atoi(v))) : (size_t)0; }();
+    PointPiece pc[MAX_POINT_PIECES]; // the ranges: .first and .len are what the loop below reads
+    int np = split_pieces(e, off, n, pc, MAX_POINT_PIECES);
+    if (np < 0) return BBGPU_ERR_SIZE; // (not a transient table: those have no segments)
+    if (np == 1) {
+        // Measured on MI355X (tools/boundary_ab.py, 2^20 points): one range 2.05-2.08 ms, two 1.77 ms, four 2.17-2.20 ms -- every range pays its
+        // own sort and bucket-reduction tail (~0.3 ms of launches that only partly hide), so two it is, the first one the smaller: its
+        // upload is the part nothing hides, and the second range's upload (0.6 ms x its share) still fits under the first one's kernels.
+        const size_t parts = P.ns < 2 ? 1 : (split_env ? split_env : (n >= ((size_t)1 << 19) ? 2 : 1));
+        // first range 3/8 of the points; measured 25 / 30 / 34 / 37 / 42 %: 1.84 / 1.80 / 1.83 / 1.775 / 1.79 ms
+        const size_t base = parts == 2 ? ((n * 3 / 8) & ~(size_t)7) : n / parts;
+        np = 0;
+        for (size_t k = 0; k < parts; k++) {
+            const size_t o = k * base, len = (k + 1 == parts) ? n - o : base;
+            if (len) pc[np++] = PointPiece{ nullptr, 0, o, len };
         }
     }
-    size_t max_len = 0;
-    for (const auto& r : ranges) max_len = std::max(max_len, r.len);
+    const size_t stage_bytes = largest_piece(pc, np) * 32;
     const double q1 = tr ? now_ms() : 0;
-    uint64_t** stage[2] = { &ctx().d_stage, &ctx().d_stage2 };
-    size_t* cap[2] = { &ctx().stage_cap, &ctx().stage2_cap };
-    host::Xyzz res = host::g1_infinity();
     int rc = BBGPU_OK;
-    size_t issued = 0, finished = 0;
-    auto finish = [&](size_t k) -> int {
-        host::Xyzz part;
-        int r = finish_ticket(sl[k % (size_t)ns], &part, k + 1 == ranges.size() ? &ctx().last : nullptr);
-        finished = k + 1;
-        if (r == BBGPU_OK) res = host::g1_add(res, part);
-        return r;
-    };
-    for (size_t k = 0; k < ranges.size() && rc == BBGPU_OK; k++) {
-        const size_t w = k % (size_t)ns;
-        if (k >= (size_t)ns) rc = finish(k - (size_t)ns); // frees this range's slot and staging buffer
-        MsmSlot& S = ctx().slot[sl[w]];
-        if (rc == BBGPU_OK) rc = grow(stage[w], cap[w], max_len * 32);
-        if (rc == BBGPU_OK) rc = host_to_device(*stage[w], scalars + ranges[k].o * 4, ranges[k].len * 32, S.stream);
-        if (rc == BBGPU_OK) rc = issue_on_entry(sl[w], e, off + ranges[k].o, *stage[w], ranges[k].len, 0, entry_windows(e, ranges[k].len), S.stream);
-        if (rc == BBGPU_OK) issued = k + 1;
-    }
-    const double q2 = tr ? now_ms() : 0;
-    // exact mode: every row of the caller's table against the fingerprints of the resident copy, on the host while the kernels issued above run
-    if (rc == BBGPU_OK && full_check && !(bg.posted ? full_check_join(bg) : contents_match_full(ctx().srs[idx], off, points, n))) {
-        for (int k = 0; k < ns; k++) drain_ticket(sl[k]);
-        srs_mark_stale(idx);
-        *stale = true;
-        return BBGPU_OK;
-    }
-    while (rc == BBGPU_OK && finished < issued) rc = finish(finished);
-    if (rc != BBGPU_OK) { // drain whatever is still in flight so that the slots are usable again (the error text is the first failure's)
-        char keep[sizeof(g_err)];
-        memcpy(keep, g_err, sizeof(keep));
-        for (int k = 0; k < ns; k++) drain_ticket(sl[k]);
-        memcpy(g_err, keep, sizeof(keep));
-    }
+    for (int k = 0; k < np && rc == BBGPU_OK; k++)
+        rc = P.push(e, off + pc[k].first, scalars + pc[k].first * 4, pc[k].len, stage_bytes, (size_t)k, k + 1 == np ? &ctx().last : nullptr);
+    if (rc == BBGPU_OK) rc = P.finish(stale);
     const double q3 = tr ? now_ms() : 0;
-    if (is_transient && !small_once) (void)dev_free(transient.d_srs); // the finishes have waited for the kernels
-    if (rc) return rc;
+    if (is_transient && !small_once) (void)dev_free(transient.d_srs); // the pipeline has waited for the kernels
+    if (rc || *stale) return rc;
     *out = res;
-    if (tr) fprintf(stderr, "bbgpu msm n=%zu: table %.3f, upload + issue %.3f, wait + host sums %.3f, free %.3f ms\n", n, q1 - q0, q2 - q1, q3 - q2, now_ms() - q3);
+    if (tr) fprintf(stderr, "bbgpu msm n=%zu: table %.3f, upload + issue %.3f, wait + host sums %.3f, free %.3f ms\n", n, q1 - q0, P.ms_push, P.ms_wait, now_ms() - q3);
     return BBGPU_OK;
 }
 
@@ -2122,23 +2170,40 @@ void bbgpu_set_host_thresholds(int msm_max_points, int ntt_max_elements)
     }
 }
 
+// scalar_multiplication.cpp:678-685: report and leave the outputs untouched
+static int batch_equal_sizes(const bbgpu_msm_job* jobs, size_t num_jobs)
+{
+    for (size_t i = 1; i < num_jobs; i++)
+        if (jobs[i].num_elements != jobs[0].num_elements) {
+            set_error("batched_scalar_multiplications err: each scalar mul must be same size.");
+            return BBGPU_ERR_ARG;
+        }
+    return BBGPU_OK;
+}
+// tiny jobs go one at a time through msm_host_ptrs*: the host may answer them (caller has called read_host_env())
+static bool batch_job_by_job(size_t n) { return n == 0 || n <= (size_t)ctx().host_msm_max; }
+// Job i of a batch of n-point jobs has a null pointer while `slots` MSM slots are free.  done: how many jobs have their outputs written by then -- job by
+// job every earlier one; through the pipeline those collected when room is made for job i's first range (what two slots leave in flight is one
+// range, the last of job i-1).  numbered: the text names the job, which it does only where two slots run the pipeline, as it always has
+struct NullJob { size_t done; bool numbered; };
+static NullJob batch_null_job(size_t n, size_t i, int slots)
+{
+    if (batch_job_by_job(n)) return NullJob{ i, false };
+    return NullJob{ collected_before(i, slots), slots >= 2 };
+}
+static int null_job_error(const NullJob& nj, size_t i)
+{
+    set_error(nj.numbered ? "null scalars/points in job %zu" : "null scalars/points", i);
+    return BBGPU_ERR_ARG;
+}
 static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale, host::Xyzz* sums);
 // sums: null -- each job's normalised result goes to its output; else job i's sum goes to sums[i], not normalised (a context's partial sums of a split batch)
 static int msm_g1_batch_run(bbgpu_msm_job* jobs, size_t num_jobs, host::Xyzz* sums)
 {
-    bool stale = false; // exact cache mode: a resident table turned out to differ from the caller's memory -- dropped; the batch runs once more on a fresh upload
-    int rc = msm_g1_batch_once(jobs, num_jobs, &stale, sums);
-    if (stale) rc = msm_g1_batch_once(jobs, num_jobs, &stale, sums);
-    return rc;
-}
-// one at a time: tiny jobs (answered on the host), fewer than two free slots, or jobs above one table segment (each is a pipeline of its own).
-// Else the two-slot pipeline, whose free slots go to sl[0..1].  Caller holds the current context's lock and has called read_host_env().
-static bool batch_one_by_one(size_t n, int* sl)
-{
-    return n == 0 || n <= (size_t)ctx().host_msm_max || n > ((size_t)1 << 20) || free_slots(sl, 2) < 2;
+    return rerun_if_stale([&](bool* stale) { return msm_g1_batch_once(jobs, num_jobs, stale, sums); });
 }
 // the first num_jobs jobs of a batch of equal sizes, non-null pointers, split over m contexts (slices sl): context k takes its slice of EVERY job
-// through its own two-slot pipeline (as the reference's threads each take a range of every job, :703-738); each job's output is the fold of its
+// through its own slot pipeline (as the reference's threads each take a range of every job, :703-738); each job's output is the fold of its
 // m partial sums
 static int msm_g1_batch_split(bbgpu_msm_job* jobs, size_t num_jobs, const multi::Slice* sl, int m)
 {
@@ -2176,23 +2241,15 @@ int bbgpu_msm_g1_batch(bbgpu_msm_job* jobs, size_t num_jobs)
     if (m == 1) return msm_g1_batch_run(jobs, num_jobs, nullptr);
     // split over the contexts.  The checks of msm_g1_batch_once come first, on the caller's thread, with what one context does on them: unequal sizes
     // leave every output untouched; a null job i ends the batch with the outputs of the jobs one context would have finished by then written
+    if (int rc = batch_equal_sizes(jobs, num_jobs)) return rc;
     const size_t n = jobs[0].num_elements;
-    for (size_t i = 1; i < num_jobs; i++)
-        if (jobs[i].num_elements != n) {
-            set_error("batched_scalar_multiplications err: each scalar mul must be same size."); // scalar_multiplication.cpp:678-685
-            return BBGPU_ERR_ARG;
-        }
     for (size_t i = 0; i < num_jobs; i++)
         if (!jobs[i].scalars || !jobs[i].points) {
             read_host_env();
             int fs[2];
-            const bool one_by_one = batch_one_by_one(n, fs);
-            // one by one: jobs 0 .. i-1 are done (msm_host_ptrs reports the null job); the pipeline: job i-1 is issued but not yet collected
-            const size_t done = one_by_one ? i : (i ? i - 1 : 0);
-            if (int rc = msm_g1_batch_split(jobs, done, sl, m)) return rc;
-            if (one_by_one) set_error("null scalars/points");
-            else set_error("null scalars/points in job %zu", i);
-            return BBGPU_ERR_ARG;
+            const NullJob nj = batch_null_job(n, i, free_slots(fs, 2));
+            if (int rc = msm_g1_batch_split(jobs, nj.done, sl, m)) return rc;
+            return null_job_error(nj, i);
         }
     return msm_g1_batch_split(jobs, num_jobs, sl, m);
 }
@@ -2202,18 +2259,10 @@ static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale, 
     int rc = BBGPU_OK;
     if (num_jobs == 0) return BBGPU_OK;
     if (!jobs) return BBGPU_ERR_ARG;
-    for (size_t i = 1; i < num_jobs; i++) {
-        if (jobs[i].num_elements != jobs[0].num_elements) {
-            // scalar_multiplication.cpp:678-685: report and leave the outputs untouched
-            set_error("batched_scalar_multiplications err: each scalar mul must be same size.");
-            return BBGPU_ERR_ARG;
-        }
-    }
+    if ((rc = batch_equal_sizes(jobs, num_jobs)) != BBGPU_OK) return rc;
     const size_t n = jobs[0].num_elements;
     read_host_env();
-    int sl[2];
-    const bool one_by_one = batch_one_by_one(n, sl);
-    if (one_by_one) {
+    if (batch_job_by_job(n)) {
         for (size_t i = 0; i < num_jobs; i++) {
             rc = sums ? msm_host_ptrs_sum(jobs[i].scalars, jobs[i].points, jobs[i].num_elements, &sums[i])
                       : msm_host_ptrs(jobs[i].scalars, jobs[i].points, jobs[i].num_elements, jobs[i].output);
@@ -2221,88 +2270,95 @@ static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale, 
         }
         return BBGPU_OK;
     }
-    if ((rc = ensure_init()) != BBGPU_OK) return rc;
-    for (int k = 0; k < 2; k++)
-        if ((rc = ensure_slot_stream(ctx().slot[sl[k]])) != BBGPU_OK) return rc;
-    SlotReservation reserve(sl, 2); // a job that straddles two table segments takes its helper elsewhere (or none)
-    // Two-slot pipeline over the jobs of a prover round (3/1/3/2 MSMs, prover.cpp:65-122,650-658): job i+1's scalars
-    // cross PCIe and its kernels are enqueued while job i's bucket-reduction tail and host finish run.
-    uint64_t** stage[2] = { &ctx().d_stage, &ctx().d_stage2 };
-    size_t* cap[2] = { &ctx().stage_cap, &ctx().stage2_cap };
-    auto now_ms = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
+    // The jobs go through the slot pipeline one range each -- a job above one table segment one range per segment it touches, like any other.  The tag
+    // of a range is its job, with the low bit set on the job's last range: ranges are collected in issue order, so one running sum serves
+    auto null_job = [&](size_t i) { return !jobs[i].scalars || !jobs[i].points; };
+    int fs[2]; // job 0's pointers come before the slots it would need, as a single call's do: with none free it is still the null job that is reported
+    if (null_job(0)) return null_job_error(batch_null_job(n, 0, free_slots(fs, 2)), 0);
+    host::Xyzz acc = host::g1_infinity();
+    HostMsmPipeline P([&](size_t tag, const host::Xyzz& part) {
+        acc = host::g1_add(acc, part);
+        if (!(tag & 1)) return;
+        if (sums) sums[tag >> 1] = acc;
+        else host::g1_to_normalised(acc, jobs[tag >> 1].output);
+        acc = host::g1_infinity();
+    });
+    if ((rc = P.open()) != BBGPU_OK) return rc;
     const bool tr = trace_srs();
-    struct FullCheck { int idx; size_t off; const uint64_t* points; };
-    std::vector<FullCheck> to_check;
-    auto issue = [&](size_t i) -> int {
-        const double q0 = tr ? now_ms() : 0;
-        const int t = (int)(i & 1);
-        MsmSlot& S = ctx().slot[sl[t]];
-        if (!jobs[i].scalars || !jobs[i].points) {
-            set_error("null scalars/points in job %zu", i);
-            return BBGPU_ERR_ARG;
-        }
+    for (size_t i = 0; i < num_jobs; i++) {
+        const double push0 = P.ms_push, wait0 = P.ms_wait;
+        if ((rc = P.make_room()) != BBGPU_OK) return rc; // before the job is looked at: what a null job leaves written does not depend on the job
+        if (null_job(i)) return null_job_error(batch_null_job(n, i, P.ns), i);
+        const double q1 = tr ? now_ms() : 0;
         size_t off = 0;
         bool full_check = false;
         int idx = find_srs(jobs[i].points, n, &off, &full_check);
         if (idx < 0) {
             uint32_t* d = nullptr;
-            int r = srs_upload(jobs[i].points, n, &d, ctx().stream);
-            if (r) return r;
-            idx = add_srs(jobs[i].points, n, d, true);
-            if (idx < 0) return idx;
+            if ((rc = srs_upload(jobs[i].points, n, &d, ctx().stream)) != BBGPU_OK) return rc;
+            if ((idx = add_srs(jobs[i].points, n, d, true)) < 0) return idx;
         }
-        if (full_check) { // exact mode: checked in full once per distinct range of the batch, after the last job is issued (beside the kernels)
-            bool known = false;
-            for (const auto& c : to_check) known = known || (c.idx == idx && c.off == off);
-            if (!known) to_check.push_back(FullCheck{ idx, off, jobs[i].points });
-        }
-        const double q1 = tr ? now_ms() : 0;
-        int r = grow(stage[t], cap[t], n * 32);
-        if (r) return r;
-        if ((r = host_to_device(*stage[t], jobs[i].scalars, n * 32, S.stream)) != BBGPU_OK) return r;
+        if (full_check) P.check_in_full(idx, off, jobs[i].points, n, false);
         const double q2 = tr ? now_ms() : 0;
-        r = issue_on_entry(sl[t], ctx().srs[idx], off, *stage[t], n, 0, entry_windows(ctx().srs[idx], n), S.stream);
-        if (tr) fprintf(stderr, "bbgpu batch: job %zu srs %.3f, copy call %.3f, kernel launches %.3f ms\n", i, q1 - q0, q2 - q1, now_ms() - q2);
-        return r;
-    };
-    auto finish = [&](size_t i) -> int {
-        host::Xyzz res;
-        int r = finish_ticket(sl[i & 1], &res, nullptr);
-        if (r) return r;
-        if (sums) sums[i] = res;
-        else host::g1_to_normalised(res, jobs[i].output);
-        return BBGPU_OK;
-    };
-    for (size_t i = 0; i < num_jobs && rc == BBGPU_OK; i++) {
-        const double t0 = tr ? now_ms() : 0;
-        rc = issue(i);
-        const double t1 = tr ? now_ms() : 0;
-        if (rc == BBGPU_OK && i >= 1) rc = finish(i - 1);
-        if (tr) fprintf(stderr, "bbgpu batch: job %zu issue %.3f ms, finish(prev) %.3f ms\n", i, t1 - t0, now_ms() - t1);
+        PointPiece pc[MAX_POINT_PIECES];
+        const int np = split_pieces(ctx().srs[idx], off, n, pc, MAX_POINT_PIECES);
+        if (np < 0) return BBGPU_ERR_SIZE;
+        const size_t stage_bytes = largest_piece(pc, np) * 32;
+        for (int k = 0; k < np; k++)
+            if ((rc = P.push(ctx().srs[idx], off + pc[k].first, jobs[i].scalars + pc[k].first * 4, pc[k].len, stage_bytes, i * 2 + (k + 1 == np), nullptr)) != BBGPU_OK) return rc;
+        if (tr) fprintf(stderr, "bbgpu batch: job %zu (%d ranges) srs %.3f, upload + issue %.3f, wait for earlier jobs %.3f ms\n", i, np, q2 - q1, P.ms_push - push0, P.ms_wait - wait0);
     }
-    const double t2 = tr ? now_ms() : 0;
-    if (rc == BBGPU_OK) {
-        bool bad = false;
-        for (const auto& c : to_check)
-            if (ctx().srs[c.idx].live && !contents_match_full(ctx().srs[c.idx], c.off, c.points, n)) {
-                srs_mark_stale(c.idx);
-                bad = true;
-            }
-        if (bad) { // outputs already written came from the stale copy: the rerun overwrites every one of them
-            for (int k = 0; k < 2; k++) drain_ticket(sl[k]);
-            *stale = true;
-            return BBGPU_OK;
-        }
-    }
-    if (rc == BBGPU_OK) rc = finish(num_jobs - 1);
-    if (tr) fprintf(stderr, "bbgpu batch: last finish %.3f ms\n", now_ms() - t2);
-    if (rc != BBGPU_OK) { // nothing of this call stays in flight (the error text is the first failure's)
-        char keep[sizeof(g_err)];
-        memcpy(keep, g_err, sizeof(keep));
-        for (int k = 0; k < 2; k++) drain_ticket(sl[k]);
-        memcpy(g_err, keep, sizeof(keep));
-    }
+    const double wait0 = P.ms_wait;
+    rc = P.finish(stale);
+    if (tr) fprintf(stderr, "bbgpu batch: last wait %.3f ms\n", P.ms_wait - wait0);
     return rc;
+}
+
+// What the four asynchronous entries share.  ticket_srs: the library is up and the handle names a live table.  begin_ticket: a free slot (slots 0 and 1
+// alternate -- the two-deep pipeline of consecutive large MSMs: measured 1.50 ms/step against 1.72 when four streams rotate, more streams than
+// hardware queues delay the next MSM's sort behind the previous one's tail -- and the others only take the overflow when both are busy, a prover
+// round's three side-by-side commitments), the caller's stream or the slot's own, and the slot's issue flags as a single-piece MSM wants them
+// (issue_ticket sets its own).  commit_ticket: the issue went through, the ticket is the slot.
+static int ticket_srs(int srs_handle, const SrsEntry** e)
+{
+    if (int rc = ensure_init()) return rc;
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
+        set_error("unknown SRS handle %d", srs_handle);
+        return BBGPU_ERR_ARG;
+    }
+    *e = &ctx().srs[srs_handle];
+    return BBGPU_OK;
+}
+// what the two share entries check before they take a slot (kind: "row" / "bucket")
+static int share_ticket_srs(int srs_handle, size_t offset, const uint64_t* d_scalars, size_t n, const char* kind, const SrsEntry** ep)
+{
+    if (int rc = ticket_srs(srs_handle, ep)) return rc;
+    const SrsEntry& e = **ep;
+    if (offset + n > e.n || !d_scalars || n == 0) {
+        set_error("MSM range [%zu, %zu) outside the registered table of %zu points", offset, offset + n, e.n);
+        return BBGPU_ERR_ARG;
+    }
+    if (e.segs.size() != 1) {
+        set_error(e.has_tab() ? "%s-range shares need ONE table segment: this SRS of %zu points keeps %zu (split it by point range instead)"
+                              : "%s-range shares need the pre-shifted window tables (one shared bucket set): this table has none", kind, e.n, e.segs.size());
+        return BBGPU_ERR_STATE;
+    }
+    return BBGPU_OK;
+}
+static int begin_ticket(void* hip_stream, int* t, hipStream_t* st)
+{
+    if ((*t = pick_slot()) < 0) return BBGPU_ERR_STATE;
+    MsmSlot& S = ctx().slot[*t];
+    *st = hip_stream ? (hipStream_t)hip_stream : S.stream;
+    S.helper = -1;
+    S.append = false;
+    S.throughput = others_pending(&S);
+    return BBGPU_OK;
+}
+static int commit_ticket(int t)
+{
+    if (t < 2) ctx().next_slot = t ^ 1;
+    return t;
 }
 
 int bbgpu_msm_g1_device(int srs_handle, size_t offset, const uint64_t* d_scalars, size_t n, int window_begin, int window_end,
@@ -2317,30 +2373,19 @@ int bbgpu_msm_g1_device_async(int srs_handle, size_t offset, const uint64_t* d_s
                               void* hip_stream)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = ensure_init();
-    if (rc) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
-        set_error("unknown SRS handle %d", srs_handle);
-        return BBGPU_ERR_ARG;
-    }
-    const SrsEntry& e = ctx().srs[srs_handle];
+    const SrsEntry* ep = nullptr;
+    if (int rc = ticket_srs(srs_handle, &ep)) return rc;
+    const SrsEntry& e = *ep;
     if (offset + n > e.n || (!d_scalars && n)) {
         set_error("MSM range [%zu, %zu) outside the registered table of %zu points", offset, offset + n, e.n);
         return BBGPU_ERR_ARG;
     }
-    // slots 0 and 1 alternate (the two-deep pipeline of consecutive large MSMs: measured 1.50 ms/step against 1.72 when four
-    // streams rotate -- more streams than hardware queues delay the next MSM's sort behind the previous one's tail);
-    // slots 2 and 3 only take the overflow when both are busy (a prover round's three side-by-side commitments)
-    const int t = pick_slot();
-    if (t < 0) return BBGPU_ERR_STATE;
-    MsmSlot& S = ctx().slot[t];
-    if (!S.stream) CHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : S.stream;
-    rc = issue_on_entry(t, e, offset, d_scalars, n, window_begin, window_end, st);
+    int t;
+    hipStream_t st;
+    if (int rc = begin_ticket(hip_stream, &t, &st)) return rc;
+    const int rc = issue_ticket(t, e, offset, &d_scalars, 1, n, window_begin, window_end, st);
     if (rc == BBGPU_ERR_ARG) set_error("bad window range [%d, %d)", window_begin, window_end);
-    if (rc) return rc;
-    if (t < 2) ctx().next_slot = t ^ 1;
-    return t;
+    return rc ? rc : commit_ticket(t);
 }
 
 int bbgpu_srs_has_window_tables(int srs_handle)
@@ -2354,87 +2399,43 @@ int bbgpu_msm_g1_device_rows_async(int srs_handle, size_t offset, const uint64_t
                                    void* hip_stream)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = ensure_init();
-    if (rc) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
-        set_error("unknown SRS handle %d", srs_handle);
-        return BBGPU_ERR_ARG;
-    }
-    const SrsEntry& e = ctx().srs[srs_handle];
-    if (offset + n > e.n || !d_scalars || n == 0) {
-        set_error("MSM range [%zu, %zu) outside the registered table of %zu points", offset, offset + n, e.n);
-        return BBGPU_ERR_ARG;
-    }
-    if (e.segs.size() != 1) {
-        set_error(e.has_tab() ? "row-range shares need ONE table segment: this SRS of %zu points keeps %zu (split it by point range instead)"
-                              : "row-range shares need the pre-shifted window tables (one shared bucket set): this table has none", e.n, e.segs.size());
-        return BBGPU_ERR_STATE;
-    }
-    const int t = pick_slot();
-    if (t < 0) return BBGPU_ERR_STATE;
-    MsmSlot& S = ctx().slot[t];
-    if (!S.stream) CHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : S.stream;
+    const SrsEntry* ep = nullptr;
+    if (int rc = share_ticket_srs(srs_handle, offset, d_scalars, n, "row", &ep)) return rc;
+    const SrsEntry& e = *ep;
+    int t;
+    hipStream_t st;
+    if (int rc = begin_ticket(hip_stream, &t, &st)) return rc;
     if (n && row_end > row_begin && !windows_resident(e, (int)(row_begin / n), (int)((row_end + n - 1) / n))) return BBGPU_ERR_STATE;
-    S.helper = -1;
-    S.append = false;
-    S.throughput = others_pending(&S);
-    rc = msm_issue_rows(S, e.d_srs + offset * 16, e.segs[0].d_tab + offset * 16, e.n, e.tab_c, d_scalars, n, row_begin, row_end, st, ctx().timing);
+    const int rc = msm_issue_rows(ctx().slot[t], e.d_srs + offset * 16, e.segs[0].d_tab + offset * 16, e.n, e.tab_c, d_scalars, n, row_begin, row_end, st, ctx().timing);
     if (rc == BBGPU_ERR_ARG) set_error("bad row range [%llu, %llu) of %d x %zu", (unsigned long long)row_begin, (unsigned long long)row_end, e.tab_W, n);
-    if (rc) return rc;
-    if (t < 2) ctx().next_slot = t ^ 1;
-    return t;
+    return rc ? rc : commit_ticket(t);
 }
 
 int bbgpu_msm_g1_device_buckets_async(int srs_handle, size_t offset, const uint64_t* d_scalars, size_t n, int share, int share_count, void* hip_stream)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = ensure_init();
-    if (rc) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
-        set_error("unknown SRS handle %d", srs_handle);
-        return BBGPU_ERR_ARG;
-    }
-    const SrsEntry& e = ctx().srs[srs_handle];
-    if (offset + n > e.n || !d_scalars || n == 0) {
-        set_error("MSM range [%zu, %zu) outside the registered table of %zu points", offset, offset + n, e.n);
-        return BBGPU_ERR_ARG;
-    }
-    if (e.segs.size() != 1) {
-        set_error(e.has_tab() ? "bucket-range shares need ONE table segment: this SRS of %zu points keeps %zu (split it by point range instead)"
-                              : "bucket-range shares need the pre-shifted window tables (one shared bucket set): this table has none", e.n, e.segs.size());
-        return BBGPU_ERR_STATE;
-    }
-    const int t = pick_slot();
-    if (t < 0) return BBGPU_ERR_STATE;
-    MsmSlot& S = ctx().slot[t];
-    if (!S.stream) CHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : S.stream;
+    const SrsEntry* ep = nullptr;
+    if (int rc = share_ticket_srs(srs_handle, offset, d_scalars, n, "bucket", &ep)) return rc;
+    const SrsEntry& e = *ep;
+    int t;
+    hipStream_t st;
+    if (int rc = begin_ticket(hip_stream, &t, &st)) return rc;
     if (!windows_resident(e, 0, e.tab_W)) return BBGPU_ERR_STATE; // every share reads every window's table
     if (share < 0 || share_count < 1 || share >= share_count) {
         set_error("bad bucket share %d of %d", share, share_count);
         return BBGPU_ERR_ARG;
     }
-    S.helper = -1;
-    S.append = false;
-    S.throughput = others_pending(&S);
-    rc = msm_issue_buckets(S, e.d_srs + offset * 16, e.segs[0].d_tab + offset * 16, e.n, e.tab_c, d_scalars, n, (uint32_t)share, (uint32_t)share_count, st, ctx().timing);
+    const int rc = msm_issue_buckets(ctx().slot[t], e.d_srs + offset * 16, e.segs[0].d_tab + offset * 16, e.n, e.tab_c, d_scalars, n, (uint32_t)share, (uint32_t)share_count, st, ctx().timing);
     if (rc == BBGPU_ERR_ARG) set_error("bad bucket share %d of %d (at most one share per row of the bucket matrix)", share, share_count);
-    if (rc) return rc;
-    if (t < 2) ctx().next_slot = t ^ 1;
-    return t;
+    return rc ? rc : commit_ticket(t);
 }
 
 int bbgpu_msm_g1_device_batch_async(int srs_handle, size_t offset, const uint64_t* const* d_scalars, int jobs, size_t n, void* hip_stream)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = ensure_init();
-    if (rc) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
-        set_error("unknown SRS handle %d", srs_handle);
-        return BBGPU_ERR_ARG;
-    }
-    const SrsEntry& e = ctx().srs[srs_handle];
+    const SrsEntry* ep = nullptr;
+    if (int rc = ticket_srs(srs_handle, &ep)) return rc;
+    const SrsEntry& e = *ep;
     if (!d_scalars || jobs < 1 || offset + n > e.n) {
         set_error("bad batch: jobs %d, range [%zu, %zu) of %zu points", jobs, offset, offset + n, e.n);
         return BBGPU_ERR_ARG;
@@ -2443,15 +2444,11 @@ int bbgpu_msm_g1_device_batch_async(int srs_handle, size_t offset, const uint64_
         set_error("batched MSM: 1..%d jobs over an SRS registered with window tables (bbgpu_set_precompute, n >= 1024)", MSM_MAX_JOBS);
         return BBGPU_ERR_ARG;
     }
-    const int t = pick_slot();
-    if (t < 0) return BBGPU_ERR_STATE;
-    MsmSlot& S = ctx().slot[t];
-    if (!S.stream) CHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : S.stream;
-    rc = issue_ticket(t, e, offset, d_scalars, jobs, n, 0, entry_windows(e, n), st);
-    if (rc) return rc;
-    if (t < 2) ctx().next_slot = t ^ 1;
-    return t;
+    int t;
+    hipStream_t st;
+    if (int rc = begin_ticket(hip_stream, &t, &st)) return rc;
+    const int rc = issue_ticket(t, e, offset, d_scalars, jobs, n, 0, entry_windows(e, n), st);
+    return rc ? rc : commit_ticket(t);
 }
 
 // The blocking part of a wait runs WITHOUT the library mutex: the events of the ticket's slot (and of its helper) are picked up under the lock,

@@ -1035,7 +1035,7 @@ __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_merge_kernel(const u
                                                               uint32_t ch, uint32_t MERGE_LIGHT, uint32_t logG)
 {
     // buckets [bucket_begin, total_buckets): a bucket-range share merges (and later folds) its own buckets only
-    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue_batch()
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t G = 1u << logG, b = bucket_begin + (t >> logG), j = t & (G - 1);
     if (b >= total_buckets) return; // whole groups leave together (groups are aligned inside a wave)
@@ -1076,7 +1076,7 @@ __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_merge_kernel(const u
 __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_merge_heavy_kernel(const uint32_t* __restrict__ gstart, const uint32_t* __restrict__ partials,
                                                                     uint32_t* __restrict__ buckets, uint32_t* __restrict__ heavy, uint32_t ch, uint32_t* __restrict__ hpart)
 {
-    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue_batch()
     __shared__ uint32_t sh[FOLD_LDS_WORDS];
     __shared__ uint32_t last_flag;
     const uint32_t count = heavy[0];
@@ -1221,7 +1221,7 @@ __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_merge_quad_kernel(co
                                                                    uint32_t* __restrict__ buckets, uint32_t* __restrict__ heavy, uint32_t bucket_begin, uint32_t total_buckets,
                                                                    uint32_t ch, uint32_t MERGE_LIGHT, uint32_t logQ)
 {
-    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue_batch()
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, l = t & 3, quad = t >> 2;
     const uint32_t Q = 1u << logQ, b = bucket_begin + (quad >> logQ), j = quad & (Q - 1);
     if (b >= total_buckets) return; // whole bucket groups leave together (4 Q lanes, aligned inside a wave)
@@ -1278,7 +1278,7 @@ __global__ void __launch_bounds__(QFOLD_T) TAIL_OCC msm_rowcol_quad_kernel(const
 {
     // rows [r0, r0 + rows) of the H x L bucket matrix (all of them, or a bucket-range share's): blockIdx.x < rows sums row r0 + blockIdx.x,
     // the L blocks after them sum the columns over those rows.  R of the other rows is not written: the caller zeroed it (infinity).
-    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue_batch()
     __shared__ uint32_t sh[(QFOLD_T / 64) * 4 * NL];
     const uint32_t g = blockIdx.y, t = threadIdx.x, nb = H * L, l = t & 3, quad = t >> 2;
     if (zero_out) { // small MSMs: the export slots (infinity = all zero) are cleared here instead of by a fill launch
@@ -1312,7 +1312,7 @@ constexpr uint32_t ROWCOL_SEG = 4;
 __global__ void __launch_bounds__(MSM_THREADS) TAIL_OCC msm_rowcol_seg_kernel(const uint32_t* __restrict__ buckets, uint32_t* __restrict__ segs, uint32_t H, uint32_t L,
                                                                                                                 uint32_t* __restrict__ zero_out, uint32_t zero_words)
 {
-    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue()
+    __builtin_amdgcn_s_setprio(TAIL_PRIO); // tail kernels: short dependent chains, see msm_issue_batch()
     const uint32_t g = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x, nb = H * L;
     if (zero_out) { // the export slots (infinity = all zero) are cleared here instead of by a fill launch
         const uint32_t gid = g * gridDim.x * blockDim.x + t, all = gridDim.y * gridDim.x * blockDim.x;
@@ -1575,19 +1575,6 @@ void MsmWorkspace::release()
     cap = 0;
 }
 
-// Runs windows [wb, we) of the MSM of d_scalars[0..n) against resident points srs[0..n); returns the partial sum
-// sum_{w in [wb,we)} 2^(c w) S_w as host XYZZ (Montgomery 2^256).
-// Enqueues windows [wb, we) of the MSM of d_scalars[0..n) against resident points srs[0..n) on `st` (all kernels and the
-// final 16 KiB device-to-host copy of the per-window leftover points); returns without waiting.  msm_finish() waits for
-// the slot's event and runs the host tail.  Two slots let the tail of one MSM overlap the head of the next.
-// Table mode (d_tab != nullptr): d_tab[w * tab_stride + i] = 2^(tab_c * w) * P_i for the points of this call, so every window
-// feeds ONE shared bucket set (groups = 1): the bucket reduction and the host finish shrink 16-fold and no positional
-// doublings are needed.
-int msm_issue(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, size_t tab_stride, int tab_c, const uint64_t* d_scalars, size_t n, int wb,
-              int we, hipStream_t st, int want_timing)
-{
-    return msm_issue_batch(S, d_srs, d_tab, tab_stride, tab_c, &d_scalars, 1, n, wb, we, st, want_timing, 0, (uint32_t)n);
-}
 // Share [row_begin, row_end) of the W * n (window, point) pairs, rows counted window-major: row = w * n + i.  With window tables every pair
 // is just one table row feeding the one shared bucket set, so ANY split of the rows is a valid split of the MSM; splitting rows instead
 // of whole windows keeps N ranks balanced when N does not divide W (15 windows over 8 ranks: 1.875 windows each instead of 2).
@@ -1616,10 +1603,6 @@ int msm_issue_buckets(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, 
     return msm_issue_batch(S, d_srs, d_tab, tab_stride, tab_c, &d_scalars, 1, n, 0, (int)P.W, st, want_timing, 0, 0xffffffffu, r0, r1);
 }
 
-// `jobs` MSMs of n scalars each over the SAME points as one pass through the pipeline (SURVEY 8f #1, the prover's 3 / 1 / 3 / 2
-// commitments per round, prover.cpp:65-122,650-658): each job is a bucket set ("group") of the shared sort / accumulate / merge /
-// reduction kernels, so the batch costs one chain of launches and one chain of dependent group additions instead of `jobs`.
-// Table mode and the full window range only.  msm_finish_batch returns one point per job.
 // "accumulation ended" events of the last ACC_RING timed MSMs, in issue order.  With two MSMs in flight the next accumulation is
 // enqueued while the previous one still runs (its sort is done early), so the event pair around the kernel also measures the time it sat
 // in the queue; the kernel cannot execute before the previous accumulation has drained (one resident wave of workgroups fills the chip),
@@ -1648,6 +1631,16 @@ void AccRing::release()
         }
     seq = 0;
 }
+// `jobs` MSMs of n scalars each over the SAME points as one pass through the pipeline (SURVEY 8f #1, the prover's 3 / 1 / 3 / 2
+// commitments per round, prover.cpp:65-122,650-658): each job is a bucket set ("group") of the shared sort / accumulate / merge /
+// reduction kernels, so the batch costs one chain of launches and one chain of dependent group additions instead of `jobs`.
+// Table mode and the full window range only.  msm_finish_batch returns one point per job.
+// Enqueues windows [wb, we) of `jobs` MSMs of n scalars each against resident points srs[0..n) on `st` (all kernels and the final device-to-host
+// copy of the leftover points); returns without waiting.  msm_finish_batch() waits for the slot's event and runs the host tail: per job the partial
+// sum sum_{w in [wb,we)} 2^(c w) S_w as host XYZZ (Montgomery 2^256).  Two slots let the tail of one MSM overlap the head of the next.
+// Table mode (d_tab != nullptr): d_tab[w * tab_stride + i] = 2^(tab_c * w) * P_i for the points of this call, so every window
+// feeds ONE shared bucket set (groups = 1): the bucket reduction and the host finish shrink 16-fold and no positional
+// doublings are needed.
 int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, size_t tab_stride, int tab_c, const uint64_t* const* d_scalars_v, int jobs,
                     size_t n, int wb, int we, hipStream_t st, int want_timing, uint32_t row_i0, uint32_t row_i1, uint32_t brow0, uint32_t brow1)
 {
@@ -1928,7 +1921,7 @@ static int finish_timing(MsmSlot& S, MsmTiming* timing)
     }
     return BBGPU_OK;
 }
-int msm_finish(MsmSlot& S, host::Xyzz* result, MsmTiming* timing)
+static int msm_finish(MsmSlot& S, host::Xyzz* result, MsmTiming* timing)
 {
     *result = host::g1_infinity();
     if (!S.pending) return BBGPU_ERR_STATE;

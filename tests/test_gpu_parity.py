@@ -731,8 +731,8 @@ def test_msm_pieces_against_the_oracle(gpu, oracle, msm_small):
                 got = gpu.msm_device(h, d.data_ptr(), n, offset=off)
                 assert np.array_equal(got[:8], want[:8]), (seg, off, n)
                 assert np.array_equal(gpu.pippenger(aligned_copy(scalars[:n]), tab[2 * off:], n)[:8], want[:8]), ("host", seg, off, n)
-            # the host-pointer batch (batched_scalar_multiplications) over sub-slices that straddle segment boundaries: its two-slot pipeline keeps its slots to itself,
-            # a straddling job takes its helper elsewhere
+            # the host-pointer batch (batched_scalar_multiplications) over sub-slices that straddle segment boundaries: a straddling job goes through the
+            # slot pipeline as one range per segment it touches
             nb = min(2 * seg, 1500)
             offs = [max(0, seg - 5), 3, 2 * seg - nb // 2, seg // 2]
             jobs = [(tab[2 * o:], aligned_copy(scalars[k:k + nb]), nb) for k, o in enumerate(offs)]
@@ -759,6 +759,102 @@ def test_msm_pieces_against_the_oracle(gpu, oracle, msm_small):
             gpu.srs_release(h)
     finally:
         del os.environ["BBGPU_TABLE_SEG_POINTS"]
+
+
+@pytest.fixture(scope="module")
+def few_slots_wants(oracle, msm_small):
+    """oracle points for the two tests below, computed once: the 4096-point MSM the held tickets run, the 10,000-point MSM and three 1,500-point jobs
+    whose sub-slices straddle the boundaries of 1,000-point segments"""
+    g, srs, table, scalars = msm_small
+    offs = (995, 3, 2500)
+    return {
+        "held": oracle.msm_affine(aligned_copy(scalars[:4096]), aligned_copy(table[:2 * 4096]), 4096),
+        "whole": oracle.msm_affine(aligned_copy(scalars[:10000]), aligned_copy(table[:2 * 10000]), 10000),
+        "offs": offs,
+        "jobs": [oracle.msm_affine(aligned_copy(scalars[k:k + 1500]), aligned_copy(table[2 * o:2 * (o + 1500)]), 1500) for k, o in enumerate(offs)],
+    }
+
+
+def _hold_tickets(gpu, table, scalars, count):
+    """`count` asynchronous 4096-point MSMs in flight on a registered table: they keep their slots until msm_wait()"""
+    import torch
+    h = gpu.srs_register(aligned_copy(table[:2 * 4096]))
+    d = torch.from_numpy(aligned_copy(scalars[:4096]).view(np.int64)).cuda()
+    return h, d, [gpu.msm_device_async(h, d.data_ptr(), 4096) for _ in range(count)]
+
+
+def test_msm_host_entries_with_few_free_slots(gpu, msm_small, few_slots_wants):
+    """pippenger() and batched_scalar_multiplications() while a caller holds asynchronous tickets: 7 held leave ONE free slot, 6 held leave two that
+    are not slots 0 / 1.  The 10,000-point table is cut into ten 1,000-point segments (BBGPU_TABLE_SEG_POINTS), so the single call is ten ranges and
+    every job of the batch lies above one segment.  All results equal the oracle's, the held tickets' as well."""
+    import os
+    g, srs, table, scalars = msm_small
+    W = few_slots_wants
+    for held in (7, 6):
+        h, d, tickets = _hold_tickets(gpu, table, scalars, held)
+        assert gpu.fault_stats()["slots_pending"] == held
+        try:
+            os.environ["BBGPU_TABLE_SEG_POINTS"] = "1000"
+            tab = aligned_copy(table[:2 * 10000])  # its own address: registered on first sight under this segment size
+            assert np.array_equal(gpu.pippenger(aligned_copy(scalars[:10000]), tab, 10000)[:8], W["whole"][:8]), held
+            jobs = [(tab[2 * o:], aligned_copy(scalars[k:k + 1500]), 1500) for k, o in enumerate(W["offs"])]
+            outs = gpu.batched_scalar_multiplications(jobs)
+            for k in range(3):
+                assert np.array_equal(outs[k][:8], W["jobs"][k][:8]), (held, k)
+        finally:
+            del os.environ["BBGPU_TABLE_SEG_POINTS"]
+        assert gpu.fault_stats()["slots_pending"] == held
+        for t in tickets:
+            assert np.array_equal(gpu.msm_wait(t)[:8], W["held"][:8]), (held, t)
+        assert gpu.fault_stats()["slots_pending"] == 0
+        gpu.srs_release(h)
+
+
+def test_msm_batch_null_job_with_one_context(gpu, msm_small, few_slots_wants):
+    """three jobs of 2048 points, job 2's scalars null, in ONE context: error -3, nothing left in flight, and the outputs written are those of the
+    jobs collected by the time job 2 is looked at -- job 0 with all slots free (job 1 is still in flight on the second slot), jobs 0 and 1 with one
+    free slot (7 tickets held).  The text carries the job number where two slots are free, "null scalars/points in job 2"; with one free slot it is
+    the plain "null scalars/points".  That is the parent commit's text, learnt by running this test once against the parent's library (there such a
+    batch ran job by job through the single-call entry), which passes it whole.  With no slot free and job 0 null it is still the null job that is
+    reported, nothing written, the 8 tickets held."""
+    import ctypes as C
+    from barretenberg_amd.bbgpu import MsmJob, _ptr
+    g, srs, table, scalars = msm_small
+    n = 2048
+    t = aligned_copy(table[:2 * n])
+    sc = [aligned_copy(scalars[k * n:(k + 1) * n]) for k in range(3)]
+    want = [gpu.pippenger(s, t, n) for s in sc[:2]]
+
+    def run(null=2):
+        arr = (MsmJob * 3)()
+        for j, s in zip(arr, sc):
+            j.points, j.scalars, j.num_elements = _ptr(t), _ptr(s), n
+        arr[null].scalars = C.cast(None, type(arr[null].scalars))
+        rc = gpu.lib.bbgpu_msm_g1_batch(arr, 3)
+        return rc, gpu.lib.bbgpu_last_error().decode(), [np.array(list(j.output), dtype=np.uint64) for j in arr]
+
+    rc, text, out = run()
+    print("all slots free:", rc, repr(text))
+    assert rc == -3 and text == "null scalars/points in job 2"
+    assert np.array_equal(out[0], want[0])
+    assert not out[1].any() and not out[2].any()
+    assert gpu.fault_stats()["slots_pending"] == 0
+    h, d, tickets = _hold_tickets(gpu, table, scalars, 7)
+    rc, text, out = run()
+    print("one slot free:", rc, repr(text))
+    assert rc == -3 and text == "null scalars/points"
+    assert np.array_equal(out[0], want[0]) and np.array_equal(out[1], want[1])
+    assert not out[2].any()
+    assert gpu.fault_stats()["slots_pending"] == 7
+    tickets.append(gpu.msm_device_async(h, d.data_ptr(), 4096))  # no slot free: a null job 0 is still reported as such, its pointers come before the slots
+    rc, text, out = run(null=0)
+    print("no slot free, job 0 null:", rc, repr(text))
+    assert rc == -3 and text == "null scalars/points"
+    assert not any(o.any() for o in out)
+    assert gpu.fault_stats()["slots_pending"] == 8
+    for tk in tickets:
+        assert np.array_equal(gpu.msm_wait(tk)[:8], few_slots_wants["held"][:8])
+    gpu.srs_release(h)
 
 
 def test_msm_skewed_scalars_full_size(gpu, oracle, golden):
