@@ -58,6 +58,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_host_plonk_check_witness",
     "bbgpu_plonk_prover_set_wire_map", "bbgpu_plonk_prover_set_witness_from", "bbgpu_plonk_construct_proof_batch_from",
     "bbgpu_plonk_check_witness_batch_from",
+    "bbgpu_host_pairing", "bbgpu_host_pairing_check", "bbgpu_transcript_read_g2", "bbgpu_srs_check", "bbgpu_host_srs_check",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -81,6 +82,25 @@ class WitnessReport(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "_pad"}
+
+
+class SrsReport(C.Structure):
+    """bbgpu_srs_report (include/bbgpu.h)"""
+    NONE = 0xFFFFFFFFFFFFFFFF  # first_bad_point / first_bad_power when there is none
+    _fields_ = [("n", C.c_uint64), ("bad_points", C.c_uint64), ("first_bad_point", C.c_uint64), ("first_is_generator", C.c_uint32), ("g2_ok", C.c_uint32),
+                ("powers_checked", C.c_uint32), ("powers_ok", C.c_uint32), ("first_bad_power", C.c_uint64), ("seed", C.c_uint64 * 4), ("a", C.c_uint64 * 8),
+                ("b", C.c_uint64 * 8)]
+    g2_given = True  # set by the binding: was an x * G2 passed to the check?
+
+    @property
+    def ok(self):
+        """the table is good: every row on the curve and, when x * G2 was given, a usable x * G2 and the powers test passed"""
+        return self.bad_points == 0 and (not self.g2_given or (self.g2_ok == 1 and self.powers_ok == 1))
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32)}
+        d.update(seed=[int(v) for v in self.seed], a=[int(v) for v in self.a], b=[int(v) for v in self.b], ok=bool(self.ok))
+        return d
 
 
 class PlonkWitness(C.Structure):
@@ -273,6 +293,58 @@ class BbGpu:
         """the file io::read_transcript accepts for this SRS: degree - 1 G1 points + {G2, x G2} (io.hpp:36-182)"""
         self.lib.bbgpu_transcript_write.argtypes = [C.c_char_p, u64p, C.c_size_t, u64p]
         self._chk(self.lib.bbgpu_transcript_write(path.encode(), _ptr(points_endo_table), degree, _ptr(np.ascontiguousarray(x_mont, dtype=np.uint64))))
+
+    def transcript_read_g2(self, path):
+        """the other half of io::read_transcript: the file's second G2 point, x * G2 (io.hpp:100-135,171-180) as (16,) uint64, Montgomery"""
+        self.lib.bbgpu_transcript_read_g2.argtypes = [C.c_char_p, u64p]
+        out = np.zeros(16, dtype=np.uint64)
+        self._chk(self.lib.bbgpu_transcript_read_g2(path.encode(), _ptr(out)))
+        return out
+
+    # ---- is this table an SRS?  (bbgpu_srs_check and its host twin; the pairing is host code, no GPU needed) -----------------------
+    def host_pairing(self, p, q):
+        """pairing::reduced_ate_pairing(P, Q): p (8,) affine G1, q (16,) affine G2 -> (12, 4) fq in the reference's fq12 order"""
+        p, q = np.ascontiguousarray(p, dtype=np.uint64).reshape(-1)[:8].copy(), np.ascontiguousarray(q, dtype=np.uint64).reshape(16)
+        out = np.zeros((12, 4), dtype=np.uint64)
+        self.lib.bbgpu_host_pairing.argtypes = [u64p, u64p, u64p]
+        self._chk(self.lib.bbgpu_host_pairing(_ptr(p), _ptr(q), _ptr(out)))
+        return out
+
+    def host_pairing_check(self, ps, qs):
+        """prod_k e(ps[k], qs[k]) == 1, one shared final exponentiation; ps (k, 8), qs (k, 16)"""
+        ps = np.ascontiguousarray(ps, dtype=np.uint64).reshape(-1, 8)
+        qs = np.ascontiguousarray(qs, dtype=np.uint64).reshape(-1, 16)
+        assert ps.shape[0] == qs.shape[0]
+        one = C.c_int(0)
+        self.lib.bbgpu_host_pairing_check.argtypes = [u64p, u64p, C.c_size_t, C.POINTER(C.c_int)]
+        self._chk(self.lib.bbgpu_host_pairing_check(_ptr(ps), _ptr(qs), ps.shape[0], C.byref(one)))
+        return one.value == 1
+
+    @staticmethod
+    def _srs_check_args(g2_x, seed, locate):
+        g2 = np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16) if g2_x is not None else None
+        sd = np.ascontiguousarray(seed, dtype=np.uint64).reshape(4) if seed is not None else None
+        return g2, sd, (_ptr(g2) if g2 is not None else None), (_ptr(sd) if sd is not None else None), (1 if locate else 0)
+
+    def srs_check(self, handle, n, g2_x=None, seed=None, locate=False):
+        """bbgpu_srs_check: rows [0, n) of a resident table on the curve, and -- with g2_x = x * G2 -- P_{i+1} = x P_i for every i by two MSMs and one
+        pairing check.  seed None: drawn from the operating system (the table's maker must not know it).  Returns an SrsReport (.ok, .as_dict())."""
+        g2, sd, g2p, sdp, flags = self._srs_check_args(g2_x, seed, locate)
+        rep = SrsReport()
+        self.lib.bbgpu_srs_check.argtypes = [C.c_int, C.c_size_t, u64p, u64p, C.c_int, C.POINTER(SrsReport)]
+        self._chk(self.lib.bbgpu_srs_check(int(handle), int(n), g2p, sdp, flags, C.byref(rep)))
+        rep.g2_given = g2 is not None
+        return rep
+
+    def host_srs_check(self, table, n=None, g2_x=None, seed=None, locate=False):
+        """bbgpu_host_srs_check: the same check over the even entries of a (2n, 8) endo table, on the host; no GPU needed"""
+        n = table.shape[0] // 2 if n is None else n
+        g2, sd, g2p, sdp, flags = self._srs_check_args(g2_x, seed, locate)
+        rep = SrsReport()
+        self.lib.bbgpu_host_srs_check.argtypes = [u64p, C.c_size_t, u64p, u64p, C.c_int, C.POINTER(SrsReport)]
+        self._chk(self.lib.bbgpu_host_srs_check(_ptr(table), int(n), g2p, sdp, flags, C.byref(rep)))
+        rep.g2_given = g2 is not None
+        return rep
 
     def srs_cache_stats(self):
         """(live tables, of which registered on first sight, device bytes those hold)"""

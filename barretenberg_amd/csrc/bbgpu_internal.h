@@ -110,6 +110,14 @@ int srs_upload(const uint64_t* host_table, size_t n, uint32_t** d_srs_out, hipSt
 int srs_upload_into(const uint64_t* host_table, size_t n, uint32_t* d_raw, uint32_t* d_srs, hipStream_t st, size_t stride_bytes);
 int srs_generate(const uint64_t* x_mont256, size_t first, size_t n, uint32_t** d_srs_out, uint64_t* host_table_out, hipStream_t st);
 
+// srs_check.hip: the O(n) device parts of bbgpu_srs_check that are not an MSM
+struct SrsCurveFindings {
+    unsigned long long bad_points, first_bad_point; // rows with y^2 != x^3 + 3, the smallest of them (the caller starts it at ~0)
+    uint32_t first_is_generator, _pad;
+};
+int srs_check_curve(const uint32_t* d_srs, size_t n, const uint64_t generator_m261[8], SrsCurveFindings* d_out, hipStream_t st);
+int srs_check_scalars(const uint64_t seed[4], size_t count, uint64_t* d_out, hipStream_t st);
+
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);
 int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_t st, bool* touched = nullptr); // *touched: h_dst may have been written (even on failure)

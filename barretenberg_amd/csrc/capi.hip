@@ -26,6 +26,8 @@
 #include "host_small.hpp"
 #include "host_fallback.hpp"
 #include "host_copy_pool.hpp"
+#include "host_pairing.hpp"
+#include "host_srs_check.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
 
@@ -238,6 +240,8 @@ struct Context {
     size_t scratch_cap = 0;
     uint64_t* d_small_tab = nullptr; // a small point table that is used once (raw upload + working form): kept, so that such a call allocates and frees nothing
     size_t small_tab_cap = 0;
+    uint64_t* d_srs_check = nullptr; // bbgpu_srs_check: the curve findings (first 64 bytes), then the n - 1 multipliers of 32 bytes
+    size_t srs_check_cap = 0;
     int timing = 0; // 0 off, 1 every stage, 2 the accumulation only (bbgpu_set_timing)
     bool precompute = true; // build window tables for registered SRS (bbgpu_set_precompute)
     uint64_t use_clock = 0;  // LRU clock of the SRS cache
@@ -1328,6 +1332,9 @@ void release_context(bool primary)
     if (C.d_small_tab) (void)dev_free(C.d_small_tab);
     C.d_small_tab = nullptr;
     C.small_tab_cap = 0;
+    if (C.d_srs_check) (void)dev_free(C.d_srs_check);
+    C.d_srs_check = nullptr;
+    C.srs_check_cap = 0;
     if (primary) ntt_release_tables();
     if (C.shared_done) (void)hipEventDestroy(C.shared_done);
     C.shared_done = nullptr;
@@ -1375,7 +1382,7 @@ void add_context_memory(const Context& C, bool primary, bbgpu_memory_info* out)
         out->msm_workspace_bytes += sl.ws.cap;
         if (sl.ws.h_out) out->pinned_host_bytes += (uint64_t)MSM_HOUT_GROUPS * 64 * 128;
     }
-    out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap;
+    out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap + C.srs_check_cap;
     if (primary) out->staging_bytes += plonk_lane_bytes(); // the resident prover runs on context 0
     for (int k = 0; k < Context::HOST_RING; k++)
         if (C.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
@@ -1893,6 +1900,150 @@ int bbgpu_host_divide_by_pseudo_vanishing(uint64_t* coeffs, size_t n_src, size_t
     if (ls < 1 || lt < ls || lt > 28) return BBGPU_ERR_SIZE;
     host::divide_by_pseudo_vanishing(coeffs, ls, lt);
     return BBGPU_OK;
+}
+
+/* ---- the pairing and the SRS check (host_pairing.hpp, host_srs_check.hpp, srs_check.hip) ---- */
+int bbgpu_host_pairing(const uint64_t p[8], const uint64_t q[16], uint64_t out[48])
+{
+    if (!p || !q || !out) {
+        set_error("null p / q / out");
+        return BBGPU_ERR_ARG;
+    }
+    const host::Fq12 e = host::pairing_product(p, q, 1);
+    memcpy(out, &e, 384);
+    return BBGPU_OK;
+}
+int bbgpu_host_pairing_check(const uint64_t* p, const uint64_t* q, size_t k, int* is_one)
+{
+    if (!is_one || (k && (!p || !q))) {
+        set_error("null p / q / is_one");
+        return BBGPU_ERR_ARG;
+    }
+    *is_one = host::fq12_eq(host::pairing_product(p, q, k), host::fq12_one()) ? 1 : 0;
+    return BBGPU_OK;
+}
+
+// io.hpp:100-135,171-180 restated: behind the manifest's num_g1_points G1 records come num_g2_points G2 records of 128 bytes (x.c0, x.c1, y.c0, y.c1 in the
+// format of the G1 coordinates); record 0 is the generator, record 1 is x * G2.  Host only.
+int bbgpu_transcript_read_g2(const char* path, uint64_t g2_x_out[16])
+{
+    if (!path || !g2_x_out) return BBGPU_ERR_ARG;
+    FILE* f = fopen(path, "rb");
+    if (!f) {
+        set_error("cannot open transcript %s", path);
+        return BBGPU_ERR_ARG;
+    }
+    unsigned char man[28], rec[128];
+    bool ok = fread(man, 1, 28, f) == 28;
+    auto be32 = [&](int i) { return ((uint32_t)man[4 * i] << 24) | ((uint32_t)man[4 * i + 1] << 16) | ((uint32_t)man[4 * i + 2] << 8) | man[4 * i + 3]; };
+    if (ok && be32(5) < 2) {
+        fclose(f);
+        set_error("transcript %s holds %u G2 points, x * G2 is the second", path, be32(5));
+        return BBGPU_ERR_SIZE;
+    }
+    ok = ok && fseek(f, 28 + (long)be32(4) * 64 + 128, SEEK_SET) == 0 && fread(rec, 1, 128, f) == 128;
+    fclose(f);
+    if (!ok) {
+        set_error("transcript %s: short read", path);
+        return BBGPU_ERR_SIZE;
+    }
+    const host::Fq rsq = { { 0xF32CFC5B538AFA89ULL, 0xB5E71911D44501FBULL, 0x47AB1EFF0A417FF6ULL, 0x06D89F71CAB8351FULL } }; // 2^512 mod q (fq.hpp:48-51)
+    for (int c = 0; c < 4; c++) {
+        host::Fq v;
+        for (int l = 0; l < 4; l++) {
+            uint64_t w = 0;
+            for (int b = 0; b < 8; b++) w = (w << 8) | rec[c * 32 + l * 8 + b];
+            v.d[l] = w;
+        }
+        v = host::fq_mul(v, rsq);
+        memcpy(g2_x_out + 4 * c, v.d, 32);
+    }
+    return BBGPU_OK;
+}
+
+int bbgpu_host_srs_check(const uint64_t* points_endo_table, size_t n, const uint64_t g2_x[16], const uint64_t seed[4], int flags, bbgpu_srs_report* out)
+{
+    if (!points_endo_table || !out || n == 0 || (flags & ~BBGPU_SRS_CHECK_LOCATE)) {
+        set_error("SRS check: null table / out, n == 0 or unknown flag bits 0x%x", flags);
+        return BBGPU_ERR_ARG;
+    }
+    uint64_t sd[4];
+    if (!host::srs_check_seed(seed, sd)) {
+        set_error("SRS check: the operating system gave no randomness");
+        return BBGPU_ERR_STATE;
+    }
+    return host::srs_check_host(points_endo_table, n, g2_x, sd, flags, out);
+}
+
+int bbgpu_srs_check(int srs_handle, size_t n, const uint64_t g2_x[16], const uint64_t seed[4], int flags, bbgpu_srs_report* out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound: a handle can only exist once one is
+    if (!out || n == 0 || (flags & ~BBGPU_SRS_CHECK_LOCATE)) {
+        set_error("SRS check: null out, n == 0 or unknown flag bits 0x%x", flags);
+        return BBGPU_ERR_ARG;
+    }
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
+        set_error("unknown SRS handle %d", srs_handle);
+        return BBGPU_ERR_ARG;
+    }
+    if (n > ctx().srs[srs_handle].n) {
+        set_error("SRS check of %zu rows, the table holds %zu", n, ctx().srs[srs_handle].n);
+        return BBGPU_ERR_ARG;
+    }
+    if (int rc = ensure_init()) return rc;
+    const SrsEntry& e = ctx().srs[srs_handle];
+    uint64_t sd[4];
+    if (!host::srs_check_seed(seed, sd)) {
+        set_error("SRS check: the operating system gave no randomness");
+        return BBGPU_ERR_STATE;
+    }
+    host::srs_report_init(out, n, sd);
+    out->g2_ok = host::srs_check_g2_ok(g2_x) ? 1 : 0;
+    const bool want_powers = out->g2_ok && n >= 2;
+    constexpr size_t HEAD = 64; // the findings, padded: the multipliers behind them stay 16-byte aligned
+    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, HEAD + (want_powers ? (n - 1) * 32 : 0))) return rc;
+    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
+    uint64_t* d_rho = ctx().d_srs_check + HEAD / 8;
+    const hipStream_t st = ctx().stream;
+    // the generator (1, 2) as a resident row: Montgomery-261, canonical
+    uint64_t gen[8];
+    {
+        host::Fq gx = host::FQ_ONE; // 2^256 mod q
+        for (int i = 0; i < 5; i++) gx = host::fq_dbl(gx);
+        const host::Fq gy = host::fq_dbl(gx);
+        memcpy(gen, gx.d, 32);
+        memcpy(gen + 4, gy.d, 32);
+    }
+    // one pass over the rows and, beside it, the multipliers; ONE synchronisation before the verdict on the curve test is read
+    const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
+    SrsCurveFindings got = init;
+    CHK(h2d_async(d_find, &init, sizeof init, st));
+    if (int rc = srs_check_curve(e.d_srs, n, gen, d_find, st)) return rc;
+    if (want_powers)
+        if (int rc = srs_check_scalars(sd, n - 1, d_rho, st)) return rc;
+    CHK(d2h_async(&got, d_find, sizeof got, st));
+    CHK(hipStreamSynchronize(st));
+    out->bad_points = got.bad_points;
+    out->first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
+    out->first_is_generator = got.first_is_generator;
+    if (!want_powers || out->bad_points) return BBGPU_OK;
+    // A and B: two tickets in flight over the SAME scalars, against points [0, m) and [1, m + 1) of the handle
+    return host::srs_check_powers(out, g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
+        const int W = entry_windows(e, m);
+        const int ta = bbgpu_msm_g1_device_async(srs_handle, 0, d_rho, m, 0, W, nullptr);
+        if (ta < 0) return ta;
+        const int tb = bbgpu_msm_g1_device_async(srs_handle, 1, d_rho, m, 0, W, nullptr);
+        if (tb < 0) {
+            drain_tickets(&ta, 1);
+            return tb;
+        }
+        if (int rc = bbgpu_msm_g1_wait(ta, a12)) {
+            drain_tickets(&tb, 1);
+            return rc;
+        }
+        return bbgpu_msm_g1_wait(tb, b12);
+    });
 }
 
 /* ---- SRS ---- */

@@ -493,6 +493,61 @@ int bbgpu_host_divide_by_pseudo_vanishing(uint64_t* coeffs, size_t n_src, size_t
  * Argument errors as bbgpu_plonk_prover_create (BBGPU_ERR_ARG: a null field, a widget's selectors given in part; BBGPU_ERR_SIZE: n). */
 int bbgpu_host_plonk_check_witness(const bbgpu_plonk_circuit* circuit, bbgpu_plonk_witness_report* out);
 
+/* ---- is this table an SRS?  (curve membership and the powers of x, checked on the GPU; the pairing on the host) ------
+ * The entries above read, write, generate, cache and fingerprint structured reference strings and never ask whether the points are one:
+ * bbgpu_transcript_read_g1 converts whatever 64-byte records the file holds, bbgpu_srs_register uploads them, and a row off the curve -- or a table
+ * whose rows are not x^i G for the x behind the transcript's x G2 -- still yields BBGPU_OK and a proof the Verifier rejects two pairings later.
+ * The reference pins the property for ONE pair of points (test/test_io.cpp:12-34, read_transcript_loads_well_formed_srs: e(-x G, G2) e(G, x G2) = 1,
+ * plus g1::on_curve over the points); bbgpu_srs_check covers every row.
+ * The pairing (curves/bn254/pairing.cpp over fields/field{2,6,12}.hpp, restated in csrc/host_pairing.hpp) is host code: these three entries make no
+ * HIP call, take no lock and are re-entrant, like the bbgpu_host_* family. */
+/* pairing::reduced_ate_pairing(P, Q) (pairing.cpp:333-347): out = 12 fq in the reference's fq12 order (c0.c0.c0, c0.c0.c1, c0.c1.c0 ... c1.c2.c1),
+ * Montgomery, canonical.  p: affine G1 {x, y}, infinity flag honoured (result one).  q: g2::affine_element {x.c0, x.c1, y.c0, y.c1}, not infinity. */
+int bbgpu_host_pairing(const uint64_t p[8], const uint64_t q[16], uint64_t out[48]);
+/* is_one = (prod_k e(p_k, q_k) == 1) with one shared Miller-loop squaring chain and one final exponentiation (reduced_ate_pairing_batch,
+ * pairing.cpp:364-385); p: k x 8 words, q: k x 16 words.  k == 0: one. */
+int bbgpu_host_pairing_check(const uint64_t* p, const uint64_t* q, size_t k, int* is_one);
+/* the other half of io::read_transcript: the file's second G2 point, x * G2 (io.hpp:100-135,171-180), in Montgomery form */
+int bbgpu_transcript_read_g2(const char* path, uint64_t g2_x_out[16]);
+
+/* bbgpu_srs_check: rows [0, n) of a registered / generated table, P_i.
+ *   curve test   every row satisfies y^2 = x^3 + 3 (one pass over the resident rows); row 0 is compared with the generator (1, 2)
+ *   powers of x  with multipliers rho_i the table's maker could not know, A = sum_{i < n-1} rho_i P_i and B = sum_{i < n-1} rho_i P_{i+1} (two MSMs in
+ *                flight over the same scalars, at offsets 0 and 1 of the handle) satisfy e(A, x G2) = e(B, G2) iff P_{i+1} = x P_i for every i, up to a
+ *                soundness error of about 2^-253 per check.  Together with first_is_generator that is P_i = x^i G.
+ * rho_i = Keccak-256(seed as 32 bytes, limbs little-endian || i as 8 bytes little-endian), the digest read as four little-endian 64-bit words with
+ * the top three bits cleared (253 bits, below r), handed to the MSM as they are: the effective multipliers rho_i 2^-256 are uniform over 2^253 residues.
+ * THE SEED MUST NOT BE KNOWN TO WHOEVER MADE THE TABLE -- a table can be built to pass for multipliers known in advance.  That is why seed == NULL
+ * draws 32 bytes from the operating system (getrandom) and why the seed is reported only afterwards, so that a finding can be replayed.
+ * Return codes: BBGPU_OK means the check RAN; the verdict is in the report.  A table is good iff bad_points == 0 and, when g2_x was given,
+ * g2_ok && powers_ok.  BBGPU_ERR_ARG (unknown handle, n == 0, n beyond the table, null out, unknown flag bits) is refused before a device is bound.
+ * The entry runs on context 0 under the library mutex; its scalars (n - 1 x 32 bytes) live in library staging counted in
+ * bbgpu_memory_info.staging_bytes.  On any failure no MSM ticket is outstanding and the handle stays usable.  An honest table issues no atomic, and the
+ * report does not vary from run to run; with the same seed it equals bbgpu_host_srs_check's field for field, a and b included.
+ * BBGPU_SRS_CHECK_LOCATE: after a failed powers test the prefix length is bisected (prefix m passes iff every pair below m holds): at most ceil(log2 n)
+ * more rounds of two MSMs and one pairing check, no new buffers.
+ * Cost on one MI355X (tools/srs_check_bench.py, profiles/srs_check.txt; wall, one box): 2^16 rows 1.68 ms against 0.41 ms for the two MSMs alone, 2^20 rows 4.37 ms
+ * against 2.81 ms; the excess (1.3 / 1.6 ms) is mostly the host tail (bbgpu_host_pairing_check of two pairs alone: 0.98 ms).  A negated row located: 22.8 / 48.4 ms.
+ * The odd (endomorphism) entries of a caller's table are not validated: the library never reads them. */
+typedef struct {
+    uint64_t n;                 /* rows checked: points [0, n) of the handle */
+    uint64_t bad_points;        /* rows with y^2 != x^3 + 3 */
+    uint64_t first_bad_point;   /* smallest such row, UINT64_MAX if none */
+    uint32_t first_is_generator;/* row 0 == (1, 2) */
+    uint32_t g2_ok;             /* g2_x given, on the twist curve, not infinity, r * g2_x == infinity */
+    uint32_t powers_checked;    /* the pairing test ran: g2_ok && bad_points == 0 && n >= 2 */
+    uint32_t powers_ok;         /* e(A, x G2) == e(B, G2) */
+    uint64_t first_bad_power;   /* with BBGPU_SRS_CHECK_LOCATE and !powers_ok: smallest i with P_{i+1} != x P_i, else UINT64_MAX */
+    uint64_t seed[4];           /* the seed used (the caller's, or the one drawn), so that a finding can be replayed */
+    uint64_t a[8], b[8];        /* A = sum_{i<n-1} rho_i P_i,  B = sum_{i<n-1} rho_i P_{i+1}, affine (infinity flag honoured; infinity when the test did not run) */
+} bbgpu_srs_report;
+#define BBGPU_SRS_CHECK_LOCATE 1
+int bbgpu_srs_check(int srs_handle, size_t n, const uint64_t g2_x[16] /* NULL: curve test only */, const uint64_t seed[4] /* NULL: OS randomness */,
+                    int flags, bbgpu_srs_report* out);
+/* the same definition over the even entries of a caller's 2n-entry endo table, on the host (csrc/host_srs_check.hpp: a plain loop for the curve test,
+ * the bucket method behind bbgpu_host_msm_g1 for A and B, the same pairing tail and bisection); no HIP call, no lock */
+int bbgpu_host_srs_check(const uint64_t* points_endo_table, size_t n, const uint64_t g2_x[16], const uint64_t seed[4], int flags, bbgpu_srs_report* out);
+
 /* ---- device self-test: known-answer entry points for the field and group layer ------------------------------------
  * One GPU lane per case runs the device arithmetic every kernel is built from (csrc/fe.hpp incl. the gfx950 asm products, csrc/g1.hpp);
  * operands and results in the reference's memory format, canonical.  What each op returns (a, b = the operands' residues):
