@@ -59,6 +59,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_plonk_prover_set_wire_map", "bbgpu_plonk_prover_set_witness_from", "bbgpu_plonk_construct_proof_batch_from",
     "bbgpu_plonk_check_witness_batch_from",
     "bbgpu_host_pairing", "bbgpu_host_pairing_check", "bbgpu_transcript_read_g2", "bbgpu_srs_check", "bbgpu_host_srs_check",
+    "bbgpu_plonk_verifier_create", "bbgpu_plonk_verifier_destroy", "bbgpu_plonk_verify_batch", "bbgpu_host_plonk_verify_batch", "bbgpu_plonk_verify_last_timing",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -100,6 +101,26 @@ class SrsReport(C.Structure):
     def as_dict(self):
         d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32)}
         d.update(seed=[int(v) for v in self.seed], a=[int(v) for v in self.a], b=[int(v) for v in self.b], ok=bool(self.ok))
+        return d
+
+
+class PlonkVerifyReport(C.Structure):
+    """bbgpu_plonk_verify_report (include/bbgpu.h)"""
+    NONE = 0xFFFFFFFFFFFFFFFF  # first_bad_status / first_bad_proof when there is none
+    BAD_POINT, ZERO_EVAL = 1, 2  # status bits
+    _fields_ = [("count", C.c_uint64), ("bad_status", C.c_uint64), ("first_bad_status", C.c_uint64), ("pairing_checked", C.c_uint32),
+                ("pairing_ok", C.c_uint32), ("first_bad_proof", C.c_uint64), ("seed", C.c_uint64 * 4), ("a", C.c_uint64 * 8), ("b", C.c_uint64 * 8)]
+    status = None  # set by the binding: (count,) uint32, the per-proof bit masks
+
+    @property
+    def ok(self):
+        """every proof of the batch is valid"""
+        return self.bad_status == 0 and self.pairing_checked == 1 and self.pairing_ok == 1
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32)}
+        d.update(seed=[int(v) for v in self.seed], a=[int(v) for v in self.a], b=[int(v) for v in self.b], ok=bool(self.ok),
+                 status=[int(v) for v in self.status] if self.status is not None else None)
         return d
 
 
@@ -344,6 +365,60 @@ class BbGpu:
         self.lib.bbgpu_host_srs_check.argtypes = [u64p, C.c_size_t, u64p, u64p, C.c_int, C.POINTER(SrsReport)]
         self._chk(self.lib.bbgpu_host_srs_check(_ptr(table), int(n), g2p, sdp, flags, C.byref(rep)))
         rep.g2_given = g2 is not None
+        return rep
+
+    # ---- is this proof valid?  (bbgpu_plonk_verify_batch and its host twin) ----------------------------------------------------------
+    WIDGET_BOOL, WIDGET_MIMC, WIDGET_SEQUENTIAL = 1, 2, 4
+
+    @staticmethod
+    def _verify_args(proofs, seed):
+        proofs = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 120)
+        sd = np.ascontiguousarray(seed, dtype=np.uint64).reshape(4) if seed is not None else None
+        return proofs, sd, (_ptr(sd) if sd is not None else None), np.zeros(max(1, proofs.shape[0]), dtype=np.uint32)
+
+    def plonk_verifier_create(self, n, widgets, vk, g2_x):
+        """bbgpu_plonk_verifier_create: vk as bbgpu_plonk_preprocess writes it ((8..12, 8) uint64), g2_x = x * G2 (16,); host work only"""
+        key = np.zeros(96, dtype=np.uint64)
+        v = np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1)
+        key[:v.size] = v
+        g2 = np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16)
+        self.lib.bbgpu_plonk_verifier_create.argtypes = [C.c_size_t, C.c_int, u64p, u64p]
+        h = self.lib.bbgpu_plonk_verifier_create(int(n), int(widgets), _ptr(key), _ptr(g2))
+        self._chk(min(h, 0))
+        return h
+
+    def plonk_verifier_destroy(self, verifier):
+        self._chk(self.lib.bbgpu_plonk_verifier_destroy(int(verifier)))
+
+    def plonk_verify_batch(self, verifier, proofs, seed=None, locate=False):
+        """bbgpu_plonk_verify_batch: proofs (count, 120) uint64 of the handle's circuit.  seed None: drawn from the operating system (whoever made the
+        proofs must not know it).  Returns a PlonkVerifyReport (.ok, .status, .as_dict())."""
+        proofs, sd, sdp, status = self._verify_args(proofs, seed)
+        rep = PlonkVerifyReport()
+        self.lib.bbgpu_plonk_verify_batch.argtypes = [C.c_int, u64p, C.c_size_t, u64p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(PlonkVerifyReport)]
+        self._chk(self.lib.bbgpu_plonk_verify_batch(int(verifier), _ptr(proofs), proofs.shape[0], sdp, 1 if locate else 0,
+                                                    status.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rep)))
+        rep.status = status[:proofs.shape[0]]
+        return rep
+
+    def plonk_verify_last_timing(self):
+        """bbgpu_plonk_verify_last_timing: wall ms of the last plonk_verify_batch by stage"""
+        buf = (C.c_double * 5)()
+        self.lib.bbgpu_plonk_verify_last_timing.argtypes = [C.POINTER(C.c_double)]
+        self._chk(self.lib.bbgpu_plonk_verify_last_timing(buf))
+        return dict(zip(("total_ms", "terms_ms", "fold_ms", "msm_ms", "host_tail_ms"), buf))
+
+    def host_plonk_verify_batch(self, n, widgets, vk, g2_x, proofs, seed=None, locate=False):
+        """bbgpu_host_plonk_verify_batch: the same definition on the host; no GPU needed"""
+        proofs, sd, sdp, status = self._verify_args(proofs, seed)
+        key = np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1).copy()
+        g2 = np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16)
+        rep = PlonkVerifyReport()
+        self.lib.bbgpu_host_plonk_verify_batch.argtypes = [C.c_size_t, C.c_int, u64p, u64p, u64p, C.c_size_t, u64p, C.c_int, C.POINTER(C.c_uint32),
+                                                           C.POINTER(PlonkVerifyReport)]
+        self._chk(self.lib.bbgpu_host_plonk_verify_batch(int(n), int(widgets), _ptr(key), _ptr(g2), _ptr(proofs), proofs.shape[0], sdp,
+                                                         1 if locate else 0, status.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rep)))
+        rep.status = status[:proofs.shape[0]]
         return rep
 
     def srs_cache_stats(self):

@@ -118,6 +118,21 @@ struct SrsCurveFindings {
 int srs_check_curve(const uint32_t* d_srs, size_t n, const uint64_t generator_m261[8], SrsCurveFindings* d_out, hipStream_t st);
 int srs_check_scalars(const uint64_t seed[4], size_t count, uint64_t* d_out, hipStream_t st);
 
+// plonk_verify.hip: the device parts of bbgpu_plonk_verify_batch that are not an MSM
+struct VerifyDeviceKey {
+    uint32_t log2n, widgets, num_vk;
+    uint32_t root[9], root_inv[9], n_inv[9]; // omega, omega^-1, 1 / n: Montgomery-261, 29-bit limbs (host_fr.hpp limbs_m261)
+};
+struct VerifyDeviceBuffers {
+    const uint64_t* proofs; // count x BBGPU_PLONK_PROOF_WORDS
+    uint32_t *rows_own, *rows_other; // count x 9 and count x 2 resident rows (64 bytes)
+    uint64_t *scal_own, *scal_other; // the scalars on them, 4 words each
+    uint64_t* shared;                // [shared point][proof] x 4 words: rho_j s_jk
+    uint32_t* status;                // count
+};
+int plonk_verify_terms(const VerifyDeviceKey& key, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B, hipStream_t st);
+int plonk_verify_fold(const uint64_t* d_shared, size_t count, size_t m, int num_shared, uint32_t skip_mask, uint64_t* d_out, hipStream_t st);
+
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);
 int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_t st, bool* touched = nullptr); // *touched: h_dst may have been written (even on failure)

@@ -28,6 +28,7 @@
 #include "host_copy_pool.hpp"
 #include "host_pairing.hpp"
 #include "host_srs_check.hpp"
+#include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
 
@@ -242,6 +243,8 @@ struct Context {
     size_t small_tab_cap = 0;
     uint64_t* d_srs_check = nullptr; // bbgpu_srs_check: the curve findings (first 64 bytes), then the n - 1 multipliers of 32 bytes
     size_t srs_check_cap = 0;
+    uint64_t* d_verify = nullptr; // bbgpu_plonk_verify_batch: the proofs, the rows and scalars of the two sums, the shared terms, the statuses
+    size_t verify_cap = 0;
     int timing = 0; // 0 off, 1 every stage, 2 the accumulation only (bbgpu_set_timing)
     bool precompute = true; // build window tables for registered SRS (bbgpu_set_precompute)
     uint64_t use_clock = 0;  // LRU clock of the SRS cache
@@ -1335,6 +1338,9 @@ void release_context(bool primary)
     if (C.d_srs_check) (void)dev_free(C.d_srs_check);
     C.d_srs_check = nullptr;
     C.srs_check_cap = 0;
+    if (C.d_verify) (void)dev_free(C.d_verify);
+    C.d_verify = nullptr;
+    C.verify_cap = 0;
     if (primary) ntt_release_tables();
     if (C.shared_done) (void)hipEventDestroy(C.shared_done);
     C.shared_done = nullptr;
@@ -1382,7 +1388,7 @@ void add_context_memory(const Context& C, bool primary, bbgpu_memory_info* out)
         out->msm_workspace_bytes += sl.ws.cap;
         if (sl.ws.h_out) out->pinned_host_bytes += (uint64_t)MSM_HOUT_GROUPS * 64 * 128;
     }
-    out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap + C.srs_check_cap;
+    out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap + C.srs_check_cap + C.verify_cap;
     if (primary) out->staging_bytes += plonk_lane_bytes(); // the resident prover runs on context 0
     for (int k = 0; k < Context::HOST_RING; k++)
         if (C.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
@@ -2046,6 +2052,38 @@ int bbgpu_srs_check(int srs_handle, size_t n, const uint64_t g2_x[16], const uin
     });
 }
 
+/* ---- batched PLONK verification (host_plonk_verify.hpp, plonk_verify.hip) ---- */
+static int verify_args(const uint64_t* proofs, size_t count, int flags, const uint32_t* status, const bbgpu_plonk_verify_report* out)
+{
+    if (!proofs || !status || !out || count < 1 || (flags & ~BBGPU_PLONK_VERIFY_LOCATE)) {
+        set_error("PLONK verify: null proofs / status / out, count < 1 or unknown flag bits 0x%x", flags);
+        return BBGPU_ERR_ARG;
+    }
+    if (count > BBGPU_PLONK_VERIFY_MAX_BATCH) {
+        set_error("PLONK verify: %zu proofs, at most %d per call", count, BBGPU_PLONK_VERIFY_MAX_BATCH);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
+
+int bbgpu_host_plonk_verify_batch(size_t n, int widgets, const uint64_t* vk, const uint64_t g2_x[16], const uint64_t* proofs, size_t count,
+                                  const uint64_t seed[4], int flags, uint32_t* status, bbgpu_plonk_verify_report* out)
+{
+    if (int rc = verify_args(proofs, count, flags, status, out)) return rc;
+    host::VerifyKey K;
+    const char* why = "";
+    if (int rc = host::verify_key_init(&K, n, widgets, vk, g2_x, &why)) {
+        set_error("PLONK verify: %s", why);
+        return rc;
+    }
+    uint64_t sd[4];
+    if (!host::srs_check_seed(seed, sd)) {
+        set_error("PLONK verify: the operating system gave no randomness");
+        return BBGPU_ERR_STATE;
+    }
+    return host::verify_host(K, proofs, count, sd, flags, status, out);
+}
+
 /* ---- SRS ---- */
 int bbgpu_srs_register(const uint64_t* points_endo_table, size_t n)
 {
@@ -2537,6 +2575,166 @@ int bbgpu_msm_g1_device_async(int srs_handle, size_t offset, const uint64_t* d_s
     const int rc = issue_ticket(t, e, offset, &d_scalars, 1, n, window_begin, window_end, st);
     if (rc == BBGPU_ERR_ARG) set_error("bad window range [%d, %d)", window_begin, window_end);
     return rc ? rc : commit_ticket(t);
+}
+
+/* ---- bbgpu_plonk_verify_batch: verifier handles, and the GPU entry (the host twin and the argument checks are further up) ---- */
+namespace {
+struct VerifierHandle {
+    host::VerifyKey K;
+    VerifyDeviceKey D;
+    uint64_t shared_rows[host::VERIFY_MAX_SHARED * 8]; // the key's points and the generator as resident rows: Montgomery-261, canonical
+    uint32_t skip_mask = 0;                            // key points at infinity: a stand-in row, scalar zero
+};
+std::vector<VerifierHandle*> g_verifiers; // under g_mu; never shrinks: a handle is an index
+double g_verify_ms[5] = { 0, 0, 0, 0, 0 }; // bbgpu_plonk_verify_last_timing: wall ms of the last call between the synchronisations it makes anyway
+} // namespace
+
+int bbgpu_plonk_verifier_create(size_t n, int widgets, const uint64_t vk[BBGPU_PLONK_VK_WORDS], const uint64_t g2_x[16])
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    VerifierHandle* H = new VerifierHandle();
+    const char* why = "";
+    if (int rc = host::verify_key_init(&H->K, n, widgets, vk, g2_x, &why)) {
+        set_error("PLONK verifier: %s", why);
+        delete H;
+        return rc;
+    }
+    const host::VerifyKey& K = H->K;
+    H->D.log2n = (uint32_t)K.log2n;
+    H->D.widgets = (uint32_t)K.widgets;
+    H->D.num_vk = (uint32_t)K.num_vk;
+    const Limbs9 root = host::limbs_m261(K.root), root_inv = host::limbs_m261(K.root_inv), n_inv = host::limbs_m261(K.n_inv);
+    for (int i = 0; i < NL; i++) {
+        H->D.root[i] = root.d[i];
+        H->D.root_inv[i] = root_inv.d[i];
+        H->D.n_inv[i] = n_inv.d[i];
+    }
+    uint64_t pts[host::VERIFY_MAX_SHARED * 8];
+    host::verify_shared_points(K, pts);
+    for (int k = 0; k < K.num_shared(); k++) {
+        if (k < K.num_vk && K.vk_inf[k]) H->skip_mask |= 1u << k;
+        for (int c = 0; c < 2; c++) { // x 2^256 -> x 2^261, canonical
+            host::Fq v;
+            memcpy(v.d, pts + 8 * k + 4 * c, 32);
+            v = host::fq_canonical(v);
+            for (int i = 0; i < 5; i++) v = host::fq_dbl(v);
+            memcpy(H->shared_rows + 8 * k + 4 * c, v.d, 32);
+        }
+    }
+    for (size_t h = 0; h < g_verifiers.size(); h++)
+        if (!g_verifiers[h]) {
+            g_verifiers[h] = H;
+            return (int)h;
+        }
+    g_verifiers.push_back(H);
+    return (int)g_verifiers.size() - 1;
+}
+
+int bbgpu_plonk_verifier_destroy(int verifier)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (verifier < 0 || verifier >= (int)g_verifiers.size() || !g_verifiers[verifier]) {
+        set_error("unknown verifier handle %d", verifier);
+        return BBGPU_ERR_ARG;
+    }
+    delete g_verifiers[verifier];
+    g_verifiers[verifier] = nullptr;
+    return BBGPU_OK;
+}
+
+int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count, const uint64_t seed[4], int flags, uint32_t* status,
+                             bbgpu_plonk_verify_report* out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    if (int rc = verify_args(proofs, count, flags, status, out)) return rc;
+    if (verifier < 0 || verifier >= (int)g_verifiers.size() || !g_verifiers[verifier]) {
+        set_error("unknown verifier handle %d", verifier);
+        return BBGPU_ERR_ARG;
+    }
+    if (int rc = ensure_init()) return rc;
+    const VerifierHandle& H = *g_verifiers[verifier];
+    const double t_begin = now_ms();
+    for (double& v : g_verify_ms) v = 0;
+    uint64_t sd[4];
+    if (!host::srs_check_seed(seed, sd)) {
+        set_error("PLONK verify: the operating system gave no randomness");
+        return BBGPU_ERR_STATE;
+    }
+    host::verify_report_init(out, count, sd);
+    // one staging buffer, every part a multiple of 64 bytes: the proofs | rows of A: shared, then nine per proof | rows of B: two per proof |
+    // scalars of A, of B | the shared terms [point][proof] | the statuses
+    const size_t S = (size_t)H.K.num_shared(), na = S + host::VERIFY_OWN * count, nb = 2 * count;
+    auto up64 = [](size_t b) { return (b + 63) & ~(size_t)63; };
+    const size_t o_rows_a = up64(count * BBGPU_PLONK_PROOF_WORDS * 8), o_rows_b = o_rows_a + na * 64, o_scal_a = o_rows_b + nb * 64,
+                 o_scal_b = o_scal_a + up64(na * 32), o_shared = o_scal_b + nb * 32, o_status = o_shared + up64(S * count * 32),
+                 total = o_status + up64(count * 4);
+    if (int rc = grow(&ctx().d_verify, &ctx().verify_cap, total)) return rc;
+    uint8_t* base = reinterpret_cast<uint8_t*>(ctx().d_verify);
+    uint32_t *d_rows_a = reinterpret_cast<uint32_t*>(base + o_rows_a), *d_rows_b = reinterpret_cast<uint32_t*>(base + o_rows_b);
+    uint64_t *d_scal_a = reinterpret_cast<uint64_t*>(base + o_scal_a), *d_scal_b = reinterpret_cast<uint64_t*>(base + o_scal_b);
+    uint64_t* d_shared = reinterpret_cast<uint64_t*>(base + o_shared);
+    uint32_t* d_status = reinterpret_cast<uint32_t*>(base + o_status);
+    const hipStream_t st = ctx().stream;
+    if (int rc = host_to_device(base, proofs, count * BBGPU_PLONK_PROOF_WORDS * 8, st)) return rc;
+    CHK(h2d_async(d_rows_a, H.shared_rows, S * 64, st));
+    VerifyDeviceBuffers B;
+    B.proofs = reinterpret_cast<const uint64_t*>(base);
+    B.rows_own = d_rows_a + S * 16;
+    B.rows_other = d_rows_b;
+    B.scal_own = d_scal_a + S * 4;
+    B.scal_other = d_scal_b;
+    B.shared = d_shared;
+    B.status = d_status;
+    if (int rc = plonk_verify_terms(H.D, sd, count, B, st)) return rc;
+    CHK(d2h_async(status, d_status, count * 4, st));
+    CHK(hipStreamSynchronize(st));
+    g_verify_ms[1] = now_ms() - t_begin;
+    host::verify_count_status(out, status);
+    // A and B: two tickets in flight over transient tables (the rows the kernel wrote; no window tables), the scalars where the kernels left them
+    SrsEntry ea{}, eb{};
+    ea.n = na;
+    ea.d_srs = d_rows_a;
+    eb.n = nb;
+    eb.d_srs = d_rows_b;
+    ea.live = eb.live = true;
+    const int rc_tail = host::verify_tail(out, H.K.g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
+        const double t_fold = now_ms();
+        if (int rc = plonk_verify_fold(d_shared, count, m, (int)S, H.skip_mask, d_scal_a, st)) return rc;
+        CHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
+        const double t_msm = now_ms();
+        g_verify_ms[2] += t_msm - t_fold;
+        const size_t ma = S + host::VERIFY_OWN * m, mb = 2 * m;
+        int ta, tb;
+        hipStream_t sa, sb;
+        if (int rc = begin_ticket(nullptr, &ta, &sa)) return rc;
+        if (int rc = issue_ticket(ta, ea, 0, &d_scal_a, 1, ma, 0, entry_windows(ea, ma), sa)) return rc;
+        commit_ticket(ta);
+        int rc = begin_ticket(nullptr, &tb, &sb);
+        if (rc == BBGPU_OK && (rc = issue_ticket(tb, eb, 0, &d_scal_b, 1, mb, 0, entry_windows(eb, mb), sb)) == BBGPU_OK) commit_ticket(tb);
+        if (rc != BBGPU_OK) {
+            drain_tickets(&ta, 1);
+            return rc;
+        }
+        if (int rcw = bbgpu_msm_g1_wait(ta, a12)) {
+            drain_tickets(&tb, 1);
+            return rcw;
+        }
+        const int rcb = bbgpu_msm_g1_wait(tb, b12);
+        g_verify_ms[3] += now_ms() - t_msm;
+        return rcb;
+    });
+    g_verify_ms[0] = now_ms() - t_begin;
+    g_verify_ms[4] = g_verify_ms[0] - g_verify_ms[1] - g_verify_ms[2] - g_verify_ms[3]; // the pairing checks (and the normalisations around them)
+    return rc_tail;
+}
+
+int bbgpu_plonk_verify_last_timing(double ms_out[5])
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!ms_out) return BBGPU_ERR_ARG;
+    for (int i = 0; i < 5; i++) ms_out[i] = g_verify_ms[i];
+    return BBGPU_OK;
 }
 
 int bbgpu_srs_has_window_tables(int srs_handle)

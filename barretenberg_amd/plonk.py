@@ -696,3 +696,52 @@ def proof_from_lines(lines):
         h = ln.split()[1]
         words += [int(h[16 * (3 - k):16 * (4 - k)], 16) for k in range(4)]
     return n, np.array(words + [0] * 20, dtype=np.uint64)
+
+
+def proof_words(lines):
+    """inverse of proof_lines for every widget set: the named lines, in any number -> (n, (120,) uint64)"""
+    names = [p + c for p in PROOF_POINTS for c in (".x", ".y")] + list(PROOF_EVALS) + list(PROOF_EVALS_WIDGET)
+    out = np.zeros(120, dtype=np.uint64)
+    n = None
+    for ln in lines:
+        k, v = ln.split()
+        if k == "n":
+            n = int(v)
+        elif k in names:
+            i = names.index(k)
+            out[4 * i:4 * i + 4] = [int(v[16 * (3 - j):16 * (4 - j)], 16) for j in range(4)]
+    return n, out
+
+
+def widget_bits(state):
+    """the widget set of a circuit state as bbgpu_plonk_verifier_create takes it"""
+    from .bbgpu import BbGpu
+    return (BbGpu.WIDGET_BOOL if "q_bl" in state else 0) | (BbGpu.WIDGET_MIMC if "q_mimc_selector" in state else 0) | \
+        (BbGpu.WIDGET_SEQUENTIAL if "q_o_next" in state else 0)
+
+
+class Verifier:
+    """waffle::Verifier for batches of proofs of one circuit over the C ABI (bbgpu_plonk_verifier_create / bbgpu_plonk_verify_batch):
+    Verifier(gpu, n, widgets, vk, g2_x).verify(proofs) -> PlonkVerifyReport; host=True runs bbgpu_host_plonk_verify_batch (no GPU needed)"""
+
+    def __init__(self, gpu, n, widgets, vk, g2_x):
+        self.gpu, self.n, self.widgets = gpu, int(n), int(widgets)
+        self.vk = np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1, 8).copy()
+        self.g2_x = np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16).copy()
+        self.handle = gpu.plonk_verifier_create(self.n, self.widgets, self.vk, self.g2_x)
+
+    @classmethod
+    def from_prover(cls, prover, g2_x):
+        """the verifier of a Prover's circuit: its key by preprocess() (one GPU call), x * G2 from the SRS's transcript (BbGpu.transcript_read_g2)"""
+        vk = prover.preprocess()
+        return cls(prover.gpu, prover.n, widget_bits(prover._keep), np.stack(list(vk.values())), g2_x)
+
+    def verify(self, proofs, seed=None, locate=False, host=False):
+        if host:
+            return self.gpu.host_plonk_verify_batch(self.n, self.widgets, self.vk, self.g2_x, proofs, seed, locate)
+        return self.gpu.plonk_verify_batch(self.handle, proofs, seed, locate)
+
+    def destroy(self):
+        if self.handle is not None:
+            self.gpu.plonk_verifier_destroy(self.handle)
+            self.handle = None

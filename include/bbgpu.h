@@ -548,6 +548,74 @@ int bbgpu_srs_check(int srs_handle, size_t n, const uint64_t g2_x[16] /* NULL: c
  * the bucket method behind bbgpu_host_msm_g1 for A and B, the same pairing tail and bisection); no HIP call, no lock */
 int bbgpu_host_srs_check(const uint64_t* points_endo_table, size_t n, const uint64_t g2_x[16], const uint64_t seed[4], int flags, bbgpu_srs_report* out);
 
+/* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
+ * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
+ * per-proof part is what :55-355 computes -- six Keccak transcripts (challenge.hpp), the Lagrange evaluations (polynomial_arithmetic.cpp:594-626),
+ * the linear terms (linearizer.hpp), t_eval, batch_evaluation and the widgets' scalars -- and the rest is folded with multipliers rho_j:
+ *   A = sum_j rho_j (scalars on proof j's own nine points) + sum_k (sum_j rho_j s_jk) V_k     V_k: the key's points, then the generator (-batch_evaluation)
+ *   B = sum_j rho_j (u_j PI_Z_OMEGA_j + PI_Z_j)
+ *   pairing_ok = (e(A, G2) e(-B, x G2) == 1)                                                 one bbgpu_host_pairing_check of two pairs
+ * over the proofs with status 0.  The batch is good iff every status is 0 and pairing_ok; the soundness error is about 2^-250 per check.
+ * rho_j = Keccak-256(seed || j) with the top three bits cleared, derived and handed to the sums exactly as bbgpu_srs_check's multipliers are.
+ * THE SEED MUST NOT BE KNOWN TO WHOEVER MADE THE PROOFS -- invalid proofs can be built to cancel for multipliers known in advance.  That is why
+ * seed == NULL draws 32 bytes from the operating system (getrandom) and why the seed is reported only afterwards, so that a finding can be replayed.
+ * A verifier handle holds n = 2^k, the widget set (the combinations bbgpu_plonk_circuit admits), the verification key exactly as
+ * bbgpu_plonk_preprocess writes it (8 to 12 points, its order) and the transcript's x G2 (bbgpu_transcript_read_g2).  Create is host work: g2_x must be
+ * on the twist, finite and of order r; every key point must carry the infinity flag (the commitment to a selector that is identically zero; it
+ * contributes nothing, as the reference skips it) or lie on the curve.
+ * status[j], a bit mask per proof of BBGPU_PLONK_PROOF_WORDS words (the reference's rules are verifier.cpp:59-102):
+ *   BAD_POINT  Z_1, T_LO or PI_Z is not a finite point on the curve (g1::on_curve is false for infinity, group.hpp:536-551), OR one of W_L, W_R, W_O,
+ *              T_MID, T_HI, PI_Z_OMEGA is finite and off the curve.  THE SECOND HALF IS STRICTER THAN THE REFERENCE, which silently leaves such a point
+ *              out of its sum (:266-346; an off-curve PI_Z_OMEGA is still multiplied by u at :362) and then fails the pairing except with negligible
+ *              probability: we reject outright.  One of those six WITH the infinity flag contributes nothing, exactly as the reference's skip does:
+ *              honest proofs of a circuit with an identically zero wire are accepted (tests/golden/infinity_commitments.json).
+ *   ZERO_EVAL  sigma_1_eval, sigma_2_eval or linear_eval is zero as fr::eq sees it: all four words zero (field.hpp:166-170).  The representative r is
+ *              not zero there and not here: such a proof gets status 0 and is judged by the pairing (tests/golden/plonk_verify.json pins the case).
+ * Evaluations and x coordinates may be any representative below 2^256, y coordinates any below 2^255 (bit 255 of y is the infinity flag, group.hpp:133-151:
+ * a y with it set is never read as a finite coordinate); they are reduced before use, the transcript hashes what the reference hashes.
+ * Return codes: BBGPU_OK means the check RAN; the verdict is in the report.  BBGPU_ERR_ARG: a null pointer, an unknown handle, an unknown flag or
+ * widget bit, a bad key point or g2_x, count < 1; BBGPU_ERR_SIZE: n is not 2^k, count > BBGPU_PLONK_VERIFY_MAX_BATCH -- refused before a device is bound.
+ * bbgpu_plonk_verify_batch has no host path, whatever the count (bbgpu_set_host_thresholds governs host-pointer MSMs only): kernel k_verify_terms does the
+ * per-proof work, one proof per thread, k_verify_fold the sums over j of the shared terms (exact field additions in a fixed tree, no atomics), A and B are
+ * two device MSMs in flight over transient tables the kernel wrote; the scalars never leave the device.  It runs on context 0 under the library mutex; its
+ * buffers are library staging counted in bbgpu_memory_info.staging_bytes.  On any failure no MSM ticket is outstanding and the handle stays usable.
+ * The report does not vary from run to run and, for the same seed, equals bbgpu_host_plonk_verify_batch's field for field, a and b included.
+ * BBGPU_PLONK_VERIFY_LOCATE: after a failed pairing test the prefix length is bisected (prefix m passes iff every proof below m verifies): at most
+ * ceil(log2 count) more rounds of one fold, two MSMs and one pairing check over the per-proof terms already computed, no new buffers.
+ * Cost on one MI355X (tools/plonk_verify_bench.py, profiles/plonk_verify.txt; wall, one box, proofs of 2^16 gates): one call 2.12 ms at 256 proofs (upload,
+ * k_verify_terms and status read-back 0.61, fold 0.02, the two MSMs 0.48, the host pairing check 1.02) and 3.72 ms at 2^14 (0.92 / 0.05 / 1.74 / 1.01):
+ * 0.137 / 0.0084 / 0.00070 / 0.00023 ms per proof at 16 / 256 / 4096 / 2^14 proofs, against 0.165 / 0.0166 / 0.0062 for the host twin and about 0.8 ms for
+ * the reference's verify_proof (a difference of two process walls of its driver, quartiles 0.4 .. 1.2 ms). */
+#define BBGPU_PLONK_WIDGET_BOOL 1
+#define BBGPU_PLONK_WIDGET_MIMC 2
+#define BBGPU_PLONK_WIDGET_SEQUENTIAL 4
+#define BBGPU_PLONK_VERIFY_BAD_POINT 1u
+#define BBGPU_PLONK_VERIFY_ZERO_EVAL 2u
+#define BBGPU_PLONK_VERIFY_LOCATE 1
+#define BBGPU_PLONK_VERIFY_MAX_BATCH 16384
+typedef struct {
+    uint64_t count;             /* proofs in the batch */
+    uint64_t bad_status;        /* proofs with status != 0 */
+    uint64_t first_bad_status;  /* smallest such index, UINT64_MAX if none */
+    uint32_t pairing_checked;   /* the pairing test ran */
+    uint32_t pairing_ok;        /* e(A, G2) e(-B, x G2) == 1 over the proofs with status 0 */
+    uint64_t first_bad_proof;   /* with BBGPU_PLONK_VERIFY_LOCATE and !pairing_ok: smallest j whose proof (status 0) does not verify, else UINT64_MAX */
+    uint64_t seed[4];           /* the seed used (the caller's, or the one drawn), so that a finding can be replayed */
+    uint64_t a[8], b[8];        /* A and B, affine (infinity flag honoured) */
+} bbgpu_plonk_verify_report;
+int bbgpu_plonk_verifier_create(size_t n, int widgets, const uint64_t vk[BBGPU_PLONK_VK_WORDS], const uint64_t g2_x[16]); /* handle >= 0; host work only */
+int bbgpu_plonk_verifier_destroy(int verifier);
+int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count, const uint64_t seed[4] /* NULL: OS randomness */, int flags,
+                             uint32_t* status /* count */, bbgpu_plonk_verify_report* out);
+/* DIAGNOSTIC (tools/plonk_verify_bench.py; not part of the verdict, one set of figures per process, overwritten by every call, zeros before the first):
+ * wall ms of the last bbgpu_plonk_verify_batch, taken between the synchronisations the call makes anyway: total; upload, k_verify_terms and the read-back
+ * of the statuses; k_verify_fold; the two MSMs; the host tail (pairing check, normalisations) -- with LOCATE summed over the rounds */
+int bbgpu_plonk_verify_last_timing(double ms_out[5]);
+/* the same definition on the host (csrc/host_plonk_verify.hpp), for a caller without a GPU or with one proof; no HIP call, no lock.  vk: as many points
+ * as the widget set has (8 to 12) */
+int bbgpu_host_plonk_verify_batch(size_t n, int widgets, const uint64_t* vk, const uint64_t g2_x[16], const uint64_t* proofs, size_t count,
+                                  const uint64_t seed[4], int flags, uint32_t* status, bbgpu_plonk_verify_report* out);
+
 /* ---- device self-test: known-answer entry points for the field and group layer ------------------------------------
  * One GPU lane per case runs the device arithmetic every kernel is built from (csrc/fe.hpp incl. the gfx950 asm products, csrc/g1.hpp);
  * operands and results in the reference's memory format, canonical.  What each op returns (a, b = the operands' residues):
