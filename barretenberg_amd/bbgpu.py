@@ -60,6 +60,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_plonk_check_witness_batch_from",
     "bbgpu_host_pairing", "bbgpu_host_pairing_check", "bbgpu_transcript_read_g2", "bbgpu_srs_check", "bbgpu_host_srs_check",
     "bbgpu_plonk_verifier_create", "bbgpu_plonk_verifier_destroy", "bbgpu_plonk_verify_batch", "bbgpu_host_plonk_verify_batch", "bbgpu_plonk_verify_last_timing",
+    "bbgpu_srs_update", "bbgpu_host_srs_update", "bbgpu_host_srs_update_check", "bbgpu_transcript_write_g2", "bbgpu_selftest_endo_split",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -101,6 +102,18 @@ class SrsReport(C.Structure):
     def as_dict(self):
         d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32)}
         d.update(seed=[int(v) for v in self.seed], a=[int(v) for v in self.a], b=[int(v) for v in self.b], ok=bool(self.ok))
+        return d
+
+
+class SrsUpdateReport(C.Structure):
+    """bbgpu_srs_update_report (include/bbgpu.h)"""
+    NONE = 0xFFFFFFFFFFFFFFFF  # first_bad_point when there is none
+    _fields_ = [("n", C.c_uint64), ("first_power", C.c_uint64), ("bad_points", C.c_uint64), ("first_bad_point", C.c_uint64), ("g2_ok", C.c_uint32),
+                ("_pad", C.c_uint32), ("y_g2", C.c_uint64 * 16), ("g2_x_out", C.c_uint64 * 16)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32) and k != "_pad"}
+        d.update(y_g2=[int(v) for v in self.y_g2], g2_x_out=[int(v) for v in self.g2_x_out])
         return d
 
 
@@ -366,6 +379,63 @@ class BbGpu:
         self._chk(self.lib.bbgpu_host_srs_check(_ptr(table), int(n), g2p, sdp, flags, C.byref(rep)))
         rep.g2_given = g2 is not None
         return rep
+
+    # ---- make this SRS your own  (bbgpu_srs_update, its host twin, the proof of an update, the writer for a string nobody holds the secret of) ----
+    def _srs_update_error(self, rc, rep):
+        err = BbGpuError("bbgpu error %d: %s" % (rc, self.lib.bbgpu_last_error().decode()))
+        err.report = rep  # filled when rows off the curve were the reason
+        return err
+
+    def srs_update(self, handle, n, y_mont, g2_x=None, want_host_table=False, first=0):
+        """bbgpu_srs_update: rows [0, n) of a resident table times y^(first + i) -> (new handle, its (2n, 8) host table or None, SrsUpdateReport).
+        A row off the curve raises BbGpuError with the report in .report; no table is made."""
+        table = np.zeros((2 * n, 8), dtype=np.uint64) if want_host_table else None
+        ya = np.ascontiguousarray(y_mont, dtype=np.uint64).reshape(4) if y_mont is not None else None
+        g2 = np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16) if g2_x is not None else None
+        rep = SrsUpdateReport()
+        self.lib.bbgpu_srs_update.argtypes = [C.c_int, C.c_size_t, C.c_size_t, u64p, u64p, u64p, C.POINTER(SrsUpdateReport)]
+        h = self.lib.bbgpu_srs_update(int(handle), int(n), int(first), _ptr(ya) if ya is not None else None, _ptr(g2) if g2 is not None else None,
+                                      _ptr(table) if want_host_table else None, C.byref(rep))
+        if h < 0:
+            raise self._srs_update_error(h, rep)
+        return h, table, rep
+
+    def host_srs_update(self, table, n, y_mont, g2_x=None, first=0, out=None):
+        """bbgpu_host_srs_update: the same over the even entries of a (2n, 8) endo table, on the host -> (table, SrsUpdateReport); out: the array to write
+        (may be `table` itself), default a new one"""
+        out = np.zeros((2 * n, 8), dtype=np.uint64) if out is None else out
+        ya = np.ascontiguousarray(y_mont, dtype=np.uint64).reshape(4) if y_mont is not None else None
+        g2 = np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16) if g2_x is not None else None
+        rep = SrsUpdateReport()
+        self.lib.bbgpu_host_srs_update.argtypes = [u64p, C.c_size_t, C.c_size_t, u64p, u64p, u64p, C.POINTER(SrsUpdateReport)]
+        rc = self.lib.bbgpu_host_srs_update(_ptr(table), int(n), int(first), _ptr(ya) if ya is not None else None, _ptr(g2) if g2 is not None else None,
+                                            _ptr(out), C.byref(rep))
+        if rc < 0:
+            raise self._srs_update_error(rc, rep)
+        return out, rep
+
+    def host_srs_update_check(self, old_p1, new_p1, y_g2):
+        """bbgpu_host_srs_update_check: is new_p1 = y old_p1 for the y behind y_g2 = y G2 (row 1 of the old and of the new table)?"""
+        a = np.ascontiguousarray(old_p1, dtype=np.uint64).reshape(-1)[:8].copy()
+        b = np.ascontiguousarray(new_p1, dtype=np.uint64).reshape(-1)[:8].copy()
+        q = np.ascontiguousarray(y_g2, dtype=np.uint64).reshape(16)
+        ok = C.c_int(0)
+        self.lib.bbgpu_host_srs_update_check.argtypes = [u64p, u64p, u64p, C.POINTER(C.c_int)]
+        self._chk(self.lib.bbgpu_host_srs_update_check(_ptr(a), _ptr(b), _ptr(q), C.byref(ok)))
+        return ok.value == 1
+
+    def write_transcript_g2(self, path, table, degree, g2_x):
+        """bbgpu_transcript_write_g2: write_transcript for a string whose secret nobody holds; g2_x = x G2 (16,)"""
+        self.lib.bbgpu_transcript_write_g2.argtypes = [C.c_char_p, u64p, C.c_size_t, u64p]
+        self._chk(self.lib.bbgpu_transcript_write_g2(path.encode(), _ptr(table), degree, _ptr(np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16))))
+
+    def selftest_endo_split(self, k, on_device=True):
+        """bbgpu_selftest_endo_split: k (n, 4) plain integers -> (n, 6): |k1| (2), |k2| (2), flags, 0"""
+        k = np.ascontiguousarray(k, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros((k.shape[0], 6), dtype=np.uint64)
+        self.lib.bbgpu_selftest_endo_split.argtypes = [C.c_int, u64p, C.c_size_t, u64p]
+        self._chk(self.lib.bbgpu_selftest_endo_split(1 if on_device else 0, _ptr(k), k.shape[0], _ptr(out)))
+        return out
 
     # ---- is this proof valid?  (bbgpu_plonk_verify_batch and its host twin) ----------------------------------------------------------
     WIDGET_BOOL, WIDGET_MIMC, WIDGET_SEQUENTIAL = 1, 2, 4

@@ -109,6 +109,11 @@ int srs_build_table(const uint32_t* d_srs, size_t n, int c, int num_windows, int
 int srs_upload(const uint64_t* host_table, size_t n, uint32_t** d_srs_out, hipStream_t st, size_t stride_bytes = 128);
 int srs_upload_into(const uint64_t* host_table, size_t n, uint32_t* d_raw, uint32_t* d_srs, hipStream_t st, size_t stride_bytes);
 int srs_generate(const uint64_t* x_mont256, size_t first, size_t n, uint32_t** d_srs_out, uint64_t* host_table_out, hipStream_t st);
+int srs_export(const uint32_t* d_srs, size_t n, uint32_t* d_table, hipStream_t st);
+
+// srs_update.hip: rows times powers of y into a new allocation (bbgpu_srs_update)
+int srs_update_rows(const uint32_t* d_in, size_t n, uint64_t first_power, const uint64_t* y_mont256, uint32_t** d_out_rows, uint64_t* host_table_out, hipStream_t st,
+                    float* kernel_ms = nullptr);
 
 // srs_check.hip: the O(n) device parts of bbgpu_srs_check that are not an MSM
 struct SrsCurveFindings {

@@ -28,6 +28,7 @@
 #include "host_copy_pool.hpp"
 #include "host_pairing.hpp"
 #include "host_srs_check.hpp"
+#include "host_srs_update.hpp"
 #include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
@@ -2120,6 +2121,94 @@ int bbgpu_srs_generate(const uint64_t* x_mont, size_t n, uint64_t* host_endo_tab
     return bbgpu_srs_generate_range(x_mont, 0, n, host_endo_table_out);
 }
 
+/* ---- the SRS update (host_srs_update.hpp, srs_update.hip) ---- */
+static int srs_update_args(size_t n, size_t first_power, const uint64_t* y_mont, host::Fr* y)
+{
+    if (!y_mont || n == 0 || first_power > ((size_t)1 << 32) || n > ((size_t)1 << 32) - first_power) {
+        set_error("SRS update: null y, n == 0 or first_power + n beyond 2^32");
+        return BBGPU_ERR_ARG;
+    }
+    if (!host::srs_update_secret(y_mont, y)) {
+        set_error("SRS update: y is zero modulo r");
+        return BBGPU_ERR_ARG;
+    }
+    return BBGPU_OK;
+}
+
+int bbgpu_host_srs_update(const uint64_t* points_endo_table, size_t n, size_t first_power, const uint64_t y_mont[4], const uint64_t g2_x[16],
+                          uint64_t* table_out, bbgpu_srs_update_report* out)
+{
+    if (!points_endo_table || !table_out) {
+        set_error("SRS update: null table");
+        return BBGPU_ERR_ARG;
+    }
+    host::Fr y;
+    if (int rc = srs_update_args(n, first_power, y_mont, &y)) return rc;
+    bbgpu_srs_update_report rep;
+    host::srs_update_report_init(&rep, n, first_power, y, g2_x);
+    const int rc = host::srs_update_host(points_endo_table, n, first_power, y, table_out, &rep);
+    if (out) *out = rep;
+    if (rc) set_error("SRS update: row %llu is not on the curve (%llu such rows)", (unsigned long long)rep.first_bad_point, (unsigned long long)rep.bad_points);
+    return rc;
+}
+
+int bbgpu_host_srs_update_check(const uint64_t old_p1[8], const uint64_t new_p1[8], const uint64_t y_g2[16], int* ok)
+{
+    if (!old_p1 || !new_p1 || !y_g2 || !ok) {
+        set_error("null old_p1 / new_p1 / y_g2 / ok");
+        return BBGPU_ERR_ARG;
+    }
+    *ok = host::srs_update_check(old_p1, new_p1, y_g2) ? 1 : 0;
+    return BBGPU_OK;
+}
+
+int bbgpu_srs_update(int srs_handle, size_t n, size_t first_power, const uint64_t y_mont[4], const uint64_t g2_x[16], uint64_t* host_endo_table_out,
+                     bbgpu_srs_update_report* out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound: a handle can only exist once one is
+    host::Fr y;
+    if (int rc = srs_update_args(n, first_power, y_mont, &y)) return rc;
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
+        set_error("unknown SRS handle %d", srs_handle);
+        return BBGPU_ERR_ARG;
+    }
+    if (n > ctx().srs[srs_handle].n) {
+        set_error("SRS update of %zu rows, the table holds %zu", n, ctx().srs[srs_handle].n);
+        return BBGPU_ERR_ARG;
+    }
+    if (int rc = ensure_init()) return rc;
+    bbgpu_srs_update_report rep;
+    host::srs_update_report_init(&rep, n, first_power, y, g2_x);
+    const uint32_t* d_in = ctx().srs[srs_handle].d_srs; // add_srs below may move the registry: nothing of the entry is held across it
+    const hipStream_t st = ctx().stream;
+    // the curve pass of bbgpu_srs_check over the input rows (its staging, its kernel); the generator verdict is not used
+    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, 64)) return rc;
+    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
+    const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
+    SrsCurveFindings got = init;
+    CHK(h2d_async(d_find, &init, sizeof init, st));
+    if (int rc = srs_check_curve(d_in, n, no_generator, d_find, st)) return rc;
+    CHK(d2h_async(&got, d_find, sizeof got, st));
+    CHK(hipStreamSynchronize(st));
+    rep.bad_points = got.bad_points;
+    rep.first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
+    if (out) *out = rep;
+    if (rep.bad_points) {
+        set_error("SRS update: row %llu is not on the curve (%llu such rows)", (unsigned long long)rep.first_bad_point, (unsigned long long)rep.bad_points);
+        return BBGPU_ERR_ARG;
+    }
+    uint32_t* d = nullptr;
+    float kernel_ms = 0;
+    if (int rc = srs_update_rows(d_in, n, (uint64_t)first_power, y.d, &d, host_endo_table_out, st, ctx().timing ? &kernel_ms : nullptr)) return rc;
+    if (ctx().timing) { // bbgpu_last_timing: index 0, the update kernel alone
+        ctx().last.count = 1;
+        ctx().last.ms[0] = kernel_ms;
+    }
+    return add_srs(host_endo_table_out, n, d, false);
+}
+
 // io.hpp:36-182 restated for the G1 part: 28-byte manifest of seven big-endian uint32 (fields 5 = num_g1_points), then points as
 // x, y, each four 64-bit limbs least-significant limb first, every limb big-endian, NOT in Montgomery form; file point k is
 // x^(k+1) G and monomials[0] is the generator (read_transcript :159-181).  Fills the complete 2n-entry endomorphism table of
@@ -2196,48 +2285,28 @@ int bbgpu_transcript_write(const char* path, const uint64_t* points_endo_table, 
         set_error("transcript secret is zero");
         return BBGPU_ERR_ARG;
     }
-    FILE* f = fopen(path, "wb");
-    if (!f) {
-        set_error("cannot create transcript %s", path);
+    const char* why = "";
+    if (!host::transcript_write_file(path, points_endo_table, degree, xg2, &why)) {
+        set_error("%s %s", why, path);
         return BBGPU_ERR_ARG;
     }
-    const host::Fq one_raw = { { 1, 0, 0, 0 } };
-    auto put_fq = [&](unsigned char* dst, const uint64_t* mont) {
-        host::Fq v;
-        memcpy(v.d, mont, 32);
-        v = host::fq_mul(v, one_raw); // out of Montgomery form
-        for (int l = 0; l < 4; l++)
-            for (int b = 0; b < 8; b++) dst[l * 8 + b] = (unsigned char)(v.d[l] >> (8 * (7 - b)));
-    };
-    const uint32_t man[7] = { 0, 1, (uint32_t)(degree - 1), 2, (uint32_t)(degree - 1), 2, 0 };
-    unsigned char mb[28];
-    for (int i = 0; i < 7; i++)
-        for (int b = 0; b < 4; b++) mb[4 * i + b] = (unsigned char)(man[i] >> (8 * (3 - b)));
-    bool ok = fwrite(mb, 1, 28, f) == 28;
-    std::vector<unsigned char> buf(64 * 4096);
-    for (size_t done = 1; ok && done < degree;) {
-        const size_t chunk = std::min<size_t>(4096, degree - done);
-        for (size_t k = 0; k < chunk; k++) {
-            const uint64_t* e = points_endo_table + (done + k) * 16;
-            put_fq(&buf[k * 64], e);
-            put_fq(&buf[k * 64 + 32], e + 4);
-        }
-        ok = fwrite(buf.data(), 64, chunk, f) == chunk;
-        done += chunk;
+    return BBGPU_OK;
+}
+
+// the same file for a string whose secret nobody holds (an updated one): x G2 is the caller's, checked as bbgpu_srs_check checks it.  Host only.
+int bbgpu_transcript_write_g2(const char* path, const uint64_t* points_endo_table, size_t degree, const uint64_t g2_x[16])
+{
+    if (!path || !points_endo_table || degree < 2 || !g2_x || degree - 1 > 0xffffffffu) {
+        set_error("transcript: null path / table / g2_x, degree < 2 or beyond 2^32");
+        return BBGPU_ERR_ARG;
     }
-    unsigned char g2b[2 * 128 + 64];
-    memset(g2b, 0, sizeof(g2b));
-    const host::G2Affine pts[2] = { host::G2_ONE, xg2 };
-    for (int i = 0; i < 2; i++) { // g2::affine_element = {x.c0, x.c1, y.c0, y.c1} (io.hpp:100-135)
-        put_fq(g2b + 128 * i, pts[i].x.c0.d);
-        put_fq(g2b + 128 * i + 32, pts[i].x.c1.d);
-        put_fq(g2b + 128 * i + 64, pts[i].y.c0.d);
-        put_fq(g2b + 128 * i + 96, pts[i].y.c1.d);
+    if (!host::srs_check_g2_ok(g2_x)) {
+        set_error("transcript x * G2 is not a point of G2");
+        return BBGPU_ERR_ARG;
     }
-    ok = ok && fwrite(g2b, 1, sizeof(g2b), f) == sizeof(g2b);
-    ok = (fclose(f) == 0) && ok;
-    if (!ok) {
-        set_error("short write to transcript %s", path);
+    const char* why = "";
+    if (!host::transcript_write_file(path, points_endo_table, degree, host::g2_from_words(g2_x), &why)) {
+        set_error("%s %s", why, path);
         return BBGPU_ERR_ARG;
     }
     return BBGPU_OK;

@@ -2023,6 +2023,14 @@ int srs_build_table(const uint32_t* d_srs, size_t n, int c, int num_windows, int
     return BBGPU_OK;
 }
 
+// resident rows -> the 2n-entry endo table (d_table: n x 128 bytes), enqueued on `st`
+int srs_export(const uint32_t* d_srs, size_t n, uint32_t* d_table, hipStream_t st)
+{
+    srs_export_kernel<<<(uint32_t)((n + 127) / 128), 128, 0, st>>>(d_srs, d_table, (uint32_t)n);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+
 int srs_generate(const uint64_t* x_mont256, size_t first, size_t n, uint32_t** d_srs_out, uint64_t* host_table_out, hipStream_t st)
 {
     DevBuf tab, srs;

@@ -548,6 +548,62 @@ int bbgpu_srs_check(int srs_handle, size_t n, const uint64_t g2_x[16] /* NULL: c
  * the bucket method behind bbgpu_host_msm_g1 for A and B, the same pairing tail and bisection); no HIP call, no lock */
 int bbgpu_host_srs_check(const uint64_t* points_endo_table, size_t n, const uint64_t g2_x[16], const uint64_t seed[4], int flags, bbgpu_srs_report* out);
 
+/* ---- make this SRS your own: rows times powers of a secret, with proof ------
+ * A universal, updatable string is one anybody may multiply a secret of their own into: from P_i = x^i G and x G2 to (x y)^i G and (x y) G2, after which
+ * the string is sound as long as ONE contributor's secret is forgotten.  bbgpu_srs_update is that operation on a resident table, row-wise:
+ *   row i  <-  y^(first_power + i) * P_i                     n independent variable-base multiplications by 254-bit scalars
+ * and bbgpu_host_srs_update_check is the proof a third party needs that the new string is the old one with some secret multiplied in.
+ * The reference has no counterpart (its strings come from a file, io.hpp:159-181).
+ *   y            Montgomery form, any representative below 2^256.  y == 0 (mod r) is refused (BBGPU_ERR_ARG: every row would be infinity); y == 1 copies.
+ *   first_power  exists so that a point-range share of a larger string (bbgpu_srs_generate_range) is updated with the powers it owns; first_power + n <= 2^32.
+ *   bad rows     the resident form has no infinity row and a point off the curve has no defined multiple: the curve pass of bbgpu_srs_check (k_srs_on_curve)
+ *                runs over the input rows first; if any fails, the report is written (when out is given), NO table is made and the entry returns
+ *                BBGPU_ERR_ARG, bbgpu_last_error() naming the first bad row.
+ *   new table    a NEW resident table, added the way bbgpu_srs_generate_range adds its own: window tables under the same conditions (bbgpu_set_precompute,
+ *                n >= 1024; an allocation the tables cannot get is ridden out without them, as there), host_endo_table_out -- filled by the export kernel of
+ *                bbgpu_srs_generate -- as the address key when given.  The input handle is untouched and stays valid.
+ *   G2 half      host work: y_g2 = y G2 and g2_x_out = y * g2_x by the double-and-add of bbgpu_transcript_write.  Only the FIRST power enters G2, whatever
+ *                first_power: e(P_{i+1}, G2) = e(P_i, x y G2) for every consecutive pair of rows.
+ * Return codes: the new handle (>= 0), or BBGPU_ERR_ARG (unknown handle, n == 0, n beyond the table, null y_mont, y == 0 mod r, first_power + n > 2^32 --
+ * all refused before a device is bound -- or a row off the curve), or BBGPU_ERR_HIP.  On any failure no handle has been created, nothing the call allocated
+ * is still live and no MSM ticket is outstanding.  The entry runs on context 0 under the library mutex; every allocation, copy and launch check passes the
+ * fault-injection funnels (a warm call: 1-2 allocations + those of the window tables, one upload, one read-back + the host table's, 2-3 launch checks + one per
+ * window-table segment).
+ * The kernel (csrc/srs_update.hip, k_srs_update): one lane per row; s = y^(first_power + i) in Fr, k = its plain value, k = k1 - lambda k2 with both halves
+ * below 2^128 (the split of fr::split_into_endomorphism_scalars with the sign of k2 kept, so that it holds for EVERY k), then one ladder over both halves
+ * with 3-bit windows of odd signed digits on P and on (beta x, -y) = -lambda P: 126 doublings and 88 complete additions, a Fermat inversion per row.
+ * With bbgpu_set_timing(1), bbgpu_last_timing() index 0 is the device time of k_srs_update alone (a pair of events around it).
+ * Cost on one MI355X (tools/srs_update_bench.py, profiles/srs_update.txt; wall, one box): 2^16 rows 5.33 ms, 7.18 ms with the host table, 1.91 ms when the
+ * new handle gets no window tables (bbgpu_set_precompute(0)); 2^20 rows 56.1 / 78.9 / 17.1 ms.  k_srs_update alone 1.21 ms and 16.4 ms (15.7 ns per row,
+ * ~2850 field products per row: 182 G products/s with squarings counted as products); the rest of a 2^20 call is the window tables of the new handle (39 ms)
+ * and the host table's export and read-back (15-23 ms).  The G2 half is 0.65 ms of host time whatever n.  Host twin: 22 ms per 4096 rows on 16 threads.
+ * The host twin (csrc/host_srs_update.hpp) is a plain double-and-add per row on a few threads; the results are unique affine points, so the two agree bit
+ * for bit, reports included.  bbgpu_host_srs_update, bbgpu_host_srs_update_check and bbgpu_transcript_write_g2 make no HIP call, take no lock and are
+ * re-entrant, like the bbgpu_host_* family. */
+typedef struct {
+    uint64_t n;                /* rows written */
+    uint64_t first_power;      /* row i was multiplied by y^(first_power + i) */
+    uint64_t bad_points;       /* input rows off the curve (no table is made when > 0) */
+    uint64_t first_bad_point;  /* smallest such row, UINT64_MAX if none */
+    uint32_t g2_ok;            /* g2_x given and valid as bbgpu_srs_check judges it */
+    uint32_t _pad;
+    uint64_t y_g2[16];         /* y * G2: the public half of the update, for bbgpu_host_srs_update_check */
+    uint64_t g2_x_out[16];     /* y^1 * g2_x when g2_ok, else zero: the x G2 of the updated string */
+} bbgpu_srs_update_report;
+/* rows [0, n) of a registered / generated table -> a NEW resident table, row i = y^(first_power + i) * P_i; returns its handle >= 0 */
+int bbgpu_srs_update(int srs_handle, size_t n, size_t first_power, const uint64_t y_mont[4], const uint64_t g2_x[16] /* NULL: no G2 half */,
+                     uint64_t* host_endo_table_out /* NULL: resident only */, bbgpu_srs_update_report* out /* may be NULL */);
+/* the same over the even entries of a caller's 2n-entry endo table, on the host; writes all 2n entries of table_out (may alias points_endo_table).
+ * A row off the curve: the report, BBGPU_ERR_ARG and an untouched table_out. */
+int bbgpu_host_srs_update(const uint64_t* points_endo_table, size_t n, size_t first_power, const uint64_t y_mont[4], const uint64_t g2_x[16],
+                          uint64_t* table_out, bbgpu_srs_update_report* out /* may be NULL */);
+/* is `new` the string `old` with its secret multiplied by the discrete log of y_g2?  *ok = y_g2 on the twist, finite, of order r AND
+ * e(old_p1, y_g2) e(-new_p1, G2) == 1 (one bbgpu_host_pairing_check of two pairs).  old_p1 / new_p1: row 1 of either table, affine {x, y}.  Together with
+ * bbgpu_srs_check of the new table against its g2_x_out this covers every row: the check says the rows are powers of ONE secret, this says which. */
+int bbgpu_host_srs_update_check(const uint64_t old_p1[8], const uint64_t new_p1[8], const uint64_t y_g2[16], int* ok);
+/* bbgpu_transcript_write for a string whose secret nobody holds: the caller gives x G2 itself (BBGPU_ERR_ARG unless bbgpu_srs_check would accept it) */
+int bbgpu_transcript_write_g2(const char* path, const uint64_t* points_endo_table, size_t degree, const uint64_t g2_x[16]);
+
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
  * per-proof part is what :55-355 computes -- six Keccak transcripts (challenge.hpp), the Lagrange evaluations (polynomial_arithmetic.cpp:594-626),
@@ -656,6 +712,11 @@ int bbgpu_selftest_field(int field, int op, const uint64_t* a, const uint64_t* b
 /* p, q: n x 12 limbs (Jacobian {x, y, z}, infinity flag honoured); out: n x 16 limbs {X, Y, ZZ, ZZZ} with x = X / ZZ, y = Y / ZZZ,
  * ZZ = 0 for infinity (the kernels' extended-Jacobian form; the caller normalises) */
 int bbgpu_selftest_g1(int op, const uint64_t* p, const uint64_t* q, size_t n, uint64_t* out);
+
+/* the endomorphism split of csrc/srs_update.hip, on the device (on_device != 0) or the same function on the host: k: n x 4 limbs, plain integers;
+ * out: n x 6 limbs {|k1| lo, hi, |k2| lo, hi, flags, 0} with k = +-k1 - lambda (+-k2) (mod r); flags bit 0: k1 negative, bit 1: k2 negative, bit 2: a
+ * magnitude does not fit 128 bits (never).  Where both signs are positive the magnitudes are host_wnaf.hpp's split (tests/golden/endo_wnaf.json). */
+int bbgpu_selftest_endo_split(int on_device, const uint64_t* k, size_t n, uint64_t* out);
 
 /* ---- instrumentation (bench.py) ---------------------------------------------------------------------------------
  * Device time in milliseconds of the kernels launched by the most recent bbgpu_*_device call on this thread, measured
