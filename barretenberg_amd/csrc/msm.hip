@@ -862,9 +862,59 @@ __device__ __forceinline__ void load_raw(Xyzz& p, const uint32_t* src)
         p.zzz.d[i] = src[3 * NL + i];
     }
 }
-// Register budget of the accumulation: with the asm products the allocator settles at 132 VGPRs (three waves per SIMD, which is what the
-// LDS reservation admits anyway).  Holding it to 128 like the tail kernels (4 spills, one scratch access in the hot loop) was measured
-// in one box at 1.272 vs 1.259 ms per pipelined 2^20 step: no gain, the accumulation stays uncapped.
+// The hot loop's table row: 64 bytes in four register quadruples, requested a whole trip before it is unpacked.  The request, the
+// landing and the end of the unpack are three asm statements, so that the order "unpack the old row completely, THEN request the
+// next one into the same registers" is the program's and not the scheduler's.  Left to itself (plain loads into w[16]) the compiler
+// sank the tail of the unpack below the new loads, so old and new words were live together in different registers, and it copied
+// words of the new row across the back edge -- two copies, each behind an s_waitcnt for a gather issued a few instructions before:
+// one HBM round trip per trip with nothing to issue (profiles/acc_loop_edge_isa.txt has both loop edges).
+// The compiler does not know that row_request is a load: nothing may read q between row_request and row_land, and the compiler has no
+// reason to (q's only reader is row_land's "+v"); the counted wait is an s_waitcnt of the compiler's own kind, so that its scoreboard
+// also retires what it had in flight itself (the sorted[] word, the gstart look-ahead) and asks for nothing at the loop top.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+struct RowRegs { u32x4 q0, q1, q2, q3; };
+__device__ __forceinline__ void row_request(RowRegs& r, const uint32_t* p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("global_load_dwordx4 %0, %4, off\n\t"
+                 "global_load_dwordx4 %1, %4, off offset:16\n\t"
+                 "global_load_dwordx4 %2, %4, off offset:32\n\t"
+                 "global_load_dwordx4 %3, %4, off offset:48"
+                 : "=&v"(r.q0), "=&v"(r.q1), "=&v"(r.q2), "=&v"(r.q3) : "v"(p) : "memory");
+#else
+    const u32x4* q = reinterpret_cast<const u32x4*>(p);
+    r.q0 = q[0]; r.q1 = q[1]; r.q2 = q[2]; r.q3 = q[3];
+#endif
+}
+// Everything this wave has in flight is retired here: the row (a trip old), the sorted[] word of the trip's top and whatever a flush
+// issued before the addition.  vmcnt(0) is right on every path -- a count would have to know whether the flush path ran.
+__device__ __forceinline__ void row_land(RowRegs& r, uint32_t (&w)[16])
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0); expcnt and lgkmcnt left alone
+    asm volatile("" : "+v"(r.q0), "+v"(r.q1), "+v"(r.q2), "+v"(r.q3));
+#endif
+#pragma unroll
+    for (int i = 0; i < 4; i++) { w[i] = r.q0[i]; w[4 + i] = r.q1[i]; w[8 + i] = r.q2[i]; w[12 + i] = r.q3[i]; }
+}
+// a loaded value is in its register behind this statement (the compiler waits for it here and not at its first use)
+__device__ __forceinline__ void value_landed(uint32_t& v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(v));
+#endif
+}
+// the unpacked operand exists in full before the statement behind this one (the next row_request) is issued
+__device__ __forceinline__ void operand_done(Fe<Fq, 1, 1>& x, Fe<Fq, 1, 2>& y)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(x.d[0]), "+v"(x.d[1]), "+v"(x.d[2]), "+v"(x.d[3]), "+v"(x.d[4]), "+v"(x.d[5]), "+v"(x.d[6]), "+v"(x.d[7]), "+v"(x.d[8]));
+    asm volatile("" : "+v"(y.d[0]), "+v"(y.d[1]), "+v"(y.d[2]), "+v"(y.d[3]), "+v"(y.d[4]), "+v"(y.d[5]), "+v"(y.d[6]), "+v"(y.d[7]), "+v"(y.d[8]));
+#endif
+}
+// Register budget of the accumulation: uncapped, the allocator settles at 151 VGPRs -- three waves per SIMD (up to 168), which is
+// what bounds the kernel's residency: three workgroups per CU.  Holding it to 128 for a fourth (4 spills, one scratch access in the
+// hot loop) was measured in one box at 1.272 vs 1.259 ms per pipelined 2^20 step: no gain.
 constexpr int RAW_WORDS = 4 * NL; // 36 words per partial: lazy limbs, no canonicalisation on the hot path
 // The heavy-bucket queue of the merge: heavy[0] = number of queued buckets, heavy[1 .. HEAVY_WGS] = per-bucket arrival counters of the
 // workgroups that share a bucket (K4h), heavy[HEAVY_IDS ..] = bucket ids; HEAVY_WGS raw partial sums follow the id list (MsmCarve).
@@ -912,12 +962,15 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_accumulate_kernel(const uint3
     // (round 2 copied 16 words per addition); the operand itself dies in the addition's first two products.
     uint32_t v = sorted[p0];
     uint32_t vn = sorted[p0 + 1 < p1 ? p0 + 1 : p0];
+    RowRegs row;
     uint32_t w[16];
-    ld16(srs + (size_t)(v & 0x7fffffffu) * 16, w);
+    row_request(row, srs + (size_t)(v & 0x7fffffffu) * 16);
     Fe<Fq, 1, 1> px;
     Fe<Fq, 1, 2> py;
+    row_land(row, w);
     load_affine_m261_signed(px, py, w, (v >> 31) != 0);
-    ld16(srs + (size_t)(vn & 0x7fffffffu) * 16, w);
+    operand_done(px, py);
+    row_request(row, srs + (size_t)(vn & 0x7fffffffu) * 16);
     // Every lane runs exactly `ch` trips -- a wave-uniform count: with a per-lane exit the compiler keeps the live-out values of
     // the lanes that left in a second set of registers (38 copies per trip), and a per-lane "still has entries" predicate around
     // the addition costs 40 more registers (190: two waves per SIMD).  Only the ONE lane of the grid that holds the end of the
@@ -954,6 +1007,7 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_accumulate_kernel(const uint3
                         b = l2;
                     }
                     next_end = gstart[b + 1];
+                    value_landed(next_end); // waited for HERE: left to the join below, the wait would sit on every flush, in front of the row in flight
                 }
                 after_next = gstart[min(b + 2, total_buckets + 1)];
             }
@@ -965,8 +1019,10 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_accumulate_kernel(const uint3
         }
         asm volatile("" ::: "memory");
         if (!start) madd_ip(acc, acc_inf, px, py);
+        row_land(row, w);
         load_affine_m261_signed(px, py, w, (vn >> 31) != 0);
-        ld16(srs + (size_t)(vnn & 0x7fffffffu) * 16, w);
+        operand_done(px, py);
+        row_request(row, srs + (size_t)(vnn & 0x7fffffffu) * 16);
         vn = vnn;
         e++;
     } while (--trips != 0);
@@ -993,11 +1049,14 @@ __device__ __forceinline__ Xyzz shfl_down_xyzz(const Xyzz& p, uint32_t off)
 // Workgroup tree sum over up to 256 XYZZ points held one per lane (raw lazy limbs staged through LDS, structure of arrays, only
 // the upper half of each level is stored: 128 x 144 B = 18 KiB): the dependent chain is log2(T) additions with no launch gaps.
 // Result in lane 0.  Measured alternatives: a ds_bpermute shuffle tree (576 B of LDS) is 40-60 % slower per level (36 permutes
-// per point and level); staging all 256 lanes needed 36 KiB, which beside three resident accumulation workgroups (3 x 41 KiB
-// of the CU's 160 KiB) only fits when the free LDS happens to be contiguous.
-// The tail kernels are held to 128 VGPRs (amdgpu_waves_per_eu(4, 4), ~32 registers spilled): at the 143 they would otherwise
-// take, their waves do not fit beside the three 128-VGPR accumulation waves per SIMD of the next MSM and the whole tail queued
-// behind it (rocprof timeline: merge 0.5 ms and heavy-merge 0.58 ms in the two-deep pipeline against 0.05 ms alone).
+// per point and level); staging all 256 lanes needed 36 KiB, which beside the LDS the accumulation workgroups then reserved (3 x 41 KiB
+// of the CU's 160 KiB) only fitted when the free LDS happened to be contiguous.
+// The tail kernels are held to 128 VGPRs (amdgpu_waves_per_eu(4, 4), ~32 registers spilled).  The cap dates from the 128-VGPR
+// accumulation, beside whose three waves per SIMD a fourth wave of 128 fitted and one of 143 did not (the whole tail then queued
+// behind the next MSM's accumulation: merge 0.5 ms and heavy-merge 0.58 ms in the two-deep pipeline against 0.05 ms alone).  Beside
+// today's 152-VGPR accumulation nothing of 128 registers fits either (3 x 152 + 128 > 512): a tail wave starts where an accumulation
+// workgroup has left.  The cap stays for what it was measured to buy once the accumulation had outgrown 128 registers (round 4, at
+// 141: profiles/r04_tail_cap_ab.txt) -- four tail waves per SIMD where the tail runs alone, and a pipelined step 0.5 % shorter.
 #define TAIL_OCC __attribute__((amdgpu_waves_per_eu(4, 4))) // the register cap of the tail kernels (see above)
 constexpr int FOLD_T = 256;
 constexpr int FOLD_LDS_WORDS = (FOLD_T / 2) * RAW_WORDS;
@@ -1433,11 +1492,12 @@ int msm_num_windows(int c)
 struct MsmPlan {
     uint32_t n, c, W, nb, hbits, lbits, slices, slice_len, sort_lb, sort_bins;
 };
-// K4 residency: 3 workgroups of 256 lanes per CU (3 waves per SIMD; v_mad_u64_u32 issue saturates at 2).  The 4th slot is
-// deliberately left free -- enforced by a dynamic-LDS reservation -- so that the short latency-bound kernels of the
-// previous MSM's tail (merge, folds) can run beside the accumulation of the next one (two-slot pipeline).
+// K4 residency: 3 workgroups of 256 lanes per CU = 3 waves per SIMD, set by the register file: the kernel allocates 152 VGPRs and
+// 3 x 152 <= 512 < 4 x 152 (v_mad_u64_u32 issue saturates at 2 waves anyway).  What is left of a SIMD beside three of its waves is
+// 56 registers: no wave of the tail kernels (128) or of the sort fits there, they take the place of an accumulation workgroup
+// that has finished.  (Until the kernel outgrew 128 VGPRs a 41 KiB dynamic-LDS reservation held the count at three; with the
+// register file doing that it only kept 123 KiB of every CU's LDS from its neighbours -- one-box A/B in DESIGN.md 4 -- and is gone.)
 constexpr uint32_t ACC_WG_PER_CU = 3;
-constexpr uint32_t ACC_LDS_RESERVE = 41 * 1024; // 3 x 41 KiB fit in 160 KiB, 4 do not
 static uint32_t acc_capacity_lanes()
 {
     // initialised once, thread-safely: the worker threads of a split MSM (capi.hip) may ask at the same time
@@ -1825,7 +1885,7 @@ int msm_issue_batch(MsmSlot& S, const uint32_t* d_srs, const uint32_t* d_tab, si
     // into the kernels around them, the last kernel writing the 8 KiB of results straight into the pinned host buffer.  (Round 1 measured the
     // folded tail 1..3 % SLOWER per pipelined 2^20 step and kept it for small MSMs only; with the round-2 tail it is level or ahead at every
     // size -- 1.371 vs 1.385 ms latency, 1.174 vs 1.176 ms per step, tools/msm_ab.py, two alternating runs in one box -- and is the one path.)
-    msm_accumulate_kernel<<<(max_chunks + MSM_THREADS - 1) / MSM_THREADS, MSM_THREADS, ACC_LDS_RESERVE, st>>>(points, sorted, gstart, partials, total_buckets, ch, 0, heavy);
+    msm_accumulate_kernel<<<(max_chunks + MSM_THREADS - 1) / MSM_THREADS, MSM_THREADS, 0, st>>>(points, sorted, gstart, partials, total_buckets, ch, 0, heavy);
     if (tm_acc) {
         HIPCHK(hipEventRecord(ev[3], st));
         if (int rc = acc_ring_record(S, st)) return rc;
