@@ -669,7 +669,9 @@ class BbGpu:
 
     # ---- device self-test (known-answer entry points of the field / group layer) ---------------------------------------
     SELFTEST_FIELD_OPS = {"mul": 0, "sqr": 1, "add": 2, "sub": 3, "neg": 4, "mul_add": 5, "mul_sub": 6, "lazy_limbs": 7, "lazy_weak": 8,
-                          "lazy_value": 9, "reduce": 10, "sqr_lazy": 11, "zero_tests": 12, "mul_addhi": 13, "sqr_addhi": 14}
+                          "lazy_value": 9, "reduce": 10, "sqr_lazy": 11, "zero_tests": 12, "mul_addhi": 13, "sqr_addhi": 14,
+                          "wide_mul": 15, "wide_sqr": 16, "wide_mul2": 17, "wide_mul_ip": 18, "wide_mul2_ip": 19, "wide_mul_addhi_ip": 20, "wide_sqr_addhi": 21,
+                          "wide_chain": 22}
     SELFTEST_G1_OPS = {"madd": 0, "add": 1, "dbl": 2, "dbl_affine": 3, "madd_neg": 4, "quad_add": 5, "madd_ip": 6, "madd_ip_chain": 7}
 
     def selftest_field(self, field, op, a, b):
@@ -680,6 +682,19 @@ class BbGpu:
         self.lib.bbgpu_selftest_field.argtypes = [C.c_int, C.c_int, u64p, u64p, C.c_size_t, u64p]
         self._chk(self.lib.bbgpu_selftest_field({"fq": 0, "fr": 1}[field], self.SELFTEST_FIELD_OPS[op], _ptr(a), _ptr(b), a.shape[0], _ptr(out)))
         return out
+
+    def selftest_field_raw(self, field, op, ac, bd):
+        """the raw-limb ops ('wide_*'): ac, bd: (cases, 18) uint32 -- the nine limbs of a then c, of b then d (or the addend e) -> (cases, 9) uint32
+        result limbs of the device arithmetic"""
+        ac = np.ascontiguousarray(ac, dtype=np.uint32).reshape(-1, 18)
+        bd = np.ascontiguousarray(bd, dtype=np.uint32).reshape(-1, 18)
+        rows = [np.zeros((ac.shape[0], 24), dtype=np.uint32) for _ in range(3)]
+        rows[0][:, :18] = ac
+        rows[1][:, :18] = bd
+        a, b, out = (r.view(np.uint64).reshape(-1, 4) for r in rows)
+        self.lib.bbgpu_selftest_field.argtypes = [C.c_int, C.c_int, u64p, u64p, C.c_size_t, u64p]
+        self._chk(self.lib.bbgpu_selftest_field({"fq": 0, "fr": 1}[field], self.SELFTEST_FIELD_OPS[op], _ptr(a), _ptr(b), a.shape[0], _ptr(out)))
+        return rows[2][:, :9].copy()
 
     def selftest_g1(self, op, p, q):
         """p, q: (n, 12) uint64 Jacobian -> (n, 16): X, Y, ZZ, ZZZ of the device result"""

@@ -12,7 +12,8 @@
 // Lazy bounds are tracked in the TYPE so that overflow is a compile error, not a silent GPU bug:
 //   Fe<F, L, V>:  every limb d[i] < L * U  (U = 2^29 + 8),  integer value < V * p,  value < 2^261.
 // add/sub never reduce; mul/sqr accept any operands with L1*L2 <= 6 (normalising automatically otherwise) and
-// return L = 1 with V = V1*V2/169 + 2 (since 2^261 / p > 169).  No conditional subtraction exists anywhere except in
+// return L = 1 with V = V1*V2/169 + 2 (since 2^261 / p > 169).  Products whose operands have L1*L2 <= 4 take the quotient digits of their
+// reduction 32 bits wide in Fq (eight masks fewer; quotient_digit / columns_fit / Digits below), the others 29 bits: same results modulo p, same bounds.  No conditional subtraction exists anywhere except in
 // to_canonical().
 //
 // Everything is __host__ __device__ so the same code is unit-tested on the CPU against the oracle.
@@ -192,7 +193,7 @@ template <class F, int L, int V> BB_HD FeE<F, V> carry_full(const Fe<F, L, V>& a
 // every column sum is <= 9*(L1*U)*(L2*U) + 9*2^58 + carry < 2^64 whenever L1*L2 <= 6.
 // On the device the three products below are the hand-scheduled gfx950 sequences of fe_mont_gfx950.h (generated by
 // tools/gen_mont_asm.py): hipcc schedules the C++ form with a separate 64-bit addition per column (v_lshl_add_u64) and
-// 277 instructions per multiplication, the asm form takes the carry as the addend of the column's first v_mad_u64_u32 (205).
+// 277 instructions per multiplication, the asm form takes the carry as the addend of the column's first v_mad_u64_u32 (205; 197 with wide digits).
 // The C++ form stays the definition: it is what the host build runs (tests/cpp/test_fe_host.cpp) and what
 // -DBBGPU_NO_MONT_ASM selects on the device (A/B, and the device self-test compares both against the reference's vectors).
 BB_HD uint64_t mad_carry_in(uint32_t a, uint32_t b, uint64_t c)
@@ -200,12 +201,61 @@ BB_HD uint64_t mad_carry_in(uint32_t a, uint32_t b, uint64_t c)
     return (uint64_t)a * b + c;
 }
 
+// Quotient digits.  The masked form (W = false) takes q_k = (t p') mod 2^29.  The WIDE form (W = true) takes digits 0..7 as the full 32-bit
+// product t * (-p^-1 mod 2^32): t + q_k p vanishes modulo 2^32, hence modulo 2^29, which is all a step needs, and the mask goes (eight
+// v_and_b32 per product on the device).  The top digit keeps its mask, so the quotient stays below 2^261 (1 + 2^-26) and the result below
+// t / R + p (1 + 2^-26): inside the "+ 2" of mul_v, every value bound as in the masked form.  (Nine unmasked digits would add 8 p to every
+// result: X3 of the mixed addition would no longer fit its 12 p and PP's zero test would need more multiples of p.)  What does grow is
+// the column: a digit times a limb of p is up to 2^61 instead of 2^58, so the wide form takes operands of fewer limb classes --
+// wide_columns_fit() below, from the limbs of p, decides per call site; the typed layer selects W by it and nothing else.
+template <class F, bool W> BB_HD uint32_t quotient_digit(uint32_t t, int k)
+{
+    if constexpr (W) {
+        const uint32_t q = t * F::PINV32;
+        return k < NL - 1 ? q : (q & M29);
+    } else {
+        (void)k;
+        return (t * F::PINV) & M29;
+    }
+}
+// Upper bound of the largest value the 64-bit column accumulator takes in a product whose operand pairs have limb bounds with
+// sum of L1 * L2 = ll (mul: L1 L2; sqr: L^2 -- the doubled cross terms are the same sum; a b + c d: L1 L2 + L3 L4), optionally with a
+// 32-bit addend per high column (the addhi forms): per column the carry in, ll U^2 per product slot, digit maximum times limb of p.
+template <class F> constexpr bool columns_fit(int ll, bool wide, bool addhi)
+{
+    typedef unsigned __int128 u128;
+    const u128 U = ((u128)1 << 29) + 8;
+    u128 carry = 0, worst = 0;
+    for (int k = 0; k < 2 * NL - 1; k++) {
+        u128 col = carry;
+        for (int i = 0; i < NL; i++) {
+            if (k - i < 0 || k - i >= NL) continue;
+            col += (u128)ll * U * U;
+            const u128 qmax = (wide && i < NL - 1) ? 0xffffffffu : M29;
+            col += qmax * F::P[k - i];
+        }
+        if (addhi && k >= NL) col += 0xffffffffu;
+        if (col > worst) worst = col;
+        carry = col >> 29;
+    }
+    return (worst >> 64) == 0;
+}
+template <class F> constexpr bool wide_columns_fit(int ll, bool addhi)
+{
+    return columns_fit<F>(ll, true, addhi);
+}
+static_assert(columns_fit<FqP>(6, false, true) && columns_fit<FrP>(6, false, true), "masked digits: L1 L2 <= 6 must fit");
+static_assert(!columns_fit<FqP>(7, false, false) && !columns_fit<FrP>(7, false, false), "the bound 6 is the last that fits");
+// BN254: the wide form fits up to ll = 4 for both fields (worst column 2^63.81 for Fq, 2^63.90 for Fr; ll = 5 gives 2^64.001 and 2^64.10)
+static_assert(wide_columns_fit<FqP>(4, true) && wide_columns_fit<FrP>(4, true), "");
+
 // Fused product scanning: one 64-bit accumulator walks the 18 columns; the carry out of column k is the addend of the
 // first multiply-add of column k+1, so there is no column array and no 64-bit carry addition.
-template <class F> BB_HD void mul_raw(const uint32_t (&a)[NL], const uint32_t (&b)[NL], uint32_t (&out)[NL])
+template <class F, bool W = false> BB_HD void mul_raw(const uint32_t (&a)[NL], const uint32_t (&b)[NL], uint32_t (&out)[NL])
 {
 #if BBGPU_MONT_ASM
-    mul_raw_gfx950<F>(a, b, out);
+    if constexpr (W) mul_raw_wq_gfx950<F>(a, b, out);
+    else mul_raw_gfx950<F>(a, b, out);
     return;
 #endif
     uint32_t m[NL];
@@ -217,7 +267,7 @@ template <class F> BB_HD void mul_raw(const uint32_t (&a)[NL], const uint32_t (&
         for (int i = 1; i <= k; i++) acc += (uint64_t)a[i] * b[k - i];
 #pragma unroll
         for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * F::P[k - i];
-        m[k] = ((uint32_t)acc * F::PINV) & M29;
+        m[k] = quotient_digit<F, W>((uint32_t)acc, k);
         acc += (uint64_t)m[k] * F::P[0];
         acc >>= 29;
     }
@@ -234,10 +284,11 @@ template <class F> BB_HD void mul_raw(const uint32_t (&a)[NL], const uint32_t (&
     out[NL - 1] = (uint32_t)acc;
 }
 
-template <class F> BB_HD void sqr_raw(const uint32_t (&a)[NL], uint32_t (&out)[NL])
+template <class F, bool W = false> BB_HD void sqr_raw(const uint32_t (&a)[NL], uint32_t (&out)[NL])
 {
 #if BBGPU_MONT_ASM
-    sqr_raw_gfx950<F>(a, out);
+    if constexpr (W) sqr_raw_wq_gfx950<F>(a, out);
+    else sqr_raw_gfx950<F>(a, out);
     return;
 #endif
     uint32_t a2[NL], m[NL];
@@ -262,7 +313,7 @@ template <class F> BB_HD void sqr_raw(const uint32_t (&a)[NL], uint32_t (&out)[N
         if (k < NL) {
 #pragma unroll
             for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * F::P[k - i];
-            m[k] = ((uint32_t)acc * F::PINV) & M29;
+            m[k] = quotient_digit<F, W>((uint32_t)acc, k);
             acc += (uint64_t)m[k] * F::P[0];
         } else {
 #pragma unroll
@@ -276,11 +327,12 @@ template <class F> BB_HD void sqr_raw(const uint32_t (&a)[NL], uint32_t (&out)[N
 
 // a*b + c*d with ONE Montgomery reduction (81 multiply-adds saved): columns hold 18 + 18 products, so the limb bounds
 // must satisfy L1*L2 + L3*L4 <= 6.
-template <class F>
+template <class F, bool W = false>
 BB_HD void mul2_raw(const uint32_t (&a)[NL], const uint32_t (&b)[NL], const uint32_t (&c)[NL], const uint32_t (&d)[NL], uint32_t (&out)[NL])
 {
 #if BBGPU_MONT_ASM
-    mul2_raw_gfx950<F>(a, b, c, d, out);
+    if constexpr (W) mul2_raw_wq_gfx950<F>(a, b, c, d, out);
+    else mul2_raw_gfx950<F>(a, b, c, d, out);
     return;
 #endif
     uint32_t m[NL];
@@ -296,7 +348,7 @@ BB_HD void mul2_raw(const uint32_t (&a)[NL], const uint32_t (&b)[NL], const uint
         }
 #pragma unroll
         for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * F::P[k - i];
-        m[k] = ((uint32_t)acc * F::PINV) & M29;
+        m[k] = quotient_digit<F, W>((uint32_t)acc, k);
         acc += (uint64_t)m[k] * F::P[0];
         acc >>= 29;
     }
@@ -320,26 +372,28 @@ BB_HD void mul2_raw(const uint32_t (&a)[NL], const uint32_t (&b)[NL], const uint
 // In-place forms: a <- a*b, c <- a*b + c*d.  On the device the result takes the REGISTERS of the replaced operand (fe_mont_gfx950.h:
 // operand limb j is last read in column j + 8, result limb j is written after column j + 9), so a loop-carried value that is
 // multiplied in place needs no copy on the loop's back edge; elsewhere they are the plain products.
-template <class F> BB_HD void mul_raw_inplace(uint32_t (&a)[NL], const uint32_t (&b)[NL])
+template <class F, bool W = false> BB_HD void mul_raw_inplace(uint32_t (&a)[NL], const uint32_t (&b)[NL])
 {
 #if BBGPU_MONT_ASM
-    mul_raw_inplace_gfx950<F>(a, b);
+    if constexpr (W) mul_raw_inplace_wq_gfx950<F>(a, b);
+    else mul_raw_inplace_gfx950<F>(a, b);
     return;
 #endif
     uint32_t t[NL];
-    mul_raw<F>(a, b, t);
+    mul_raw<F, W>(a, b, t);
 #pragma unroll
     for (int i = 0; i < NL; i++) a[i] = t[i];
 }
-template <class F>
+template <class F, bool W = false>
 BB_HD void mul2_raw_inplace(const uint32_t (&a)[NL], const uint32_t (&b)[NL], uint32_t (&c)[NL], const uint32_t (&d)[NL])
 {
 #if BBGPU_MONT_ASM
-    mul2_raw_inplace_gfx950<F>(a, b, c, d);
+    if constexpr (W) mul2_raw_inplace_wq_gfx950<F>(a, b, c, d);
+    else mul2_raw_inplace_gfx950<F>(a, b, c, d);
     return;
 #endif
     uint32_t t[NL];
-    mul2_raw<F>(a, b, c, d, t);
+    mul2_raw<F, W>(a, b, c, d, t);
 #pragma unroll
     for (int i = 0; i < NL; i++) c[i] = t[i];
 }
@@ -349,10 +403,11 @@ BB_HD void mul2_raw_inplace(const uint32_t (&a)[NL], const uint32_t (&b)[NL], ui
 // P = x2 ZZ1 - X1 of the mixed addition (e = K p - X1, limb-wise non-negative) costs nine additions of e's limbs instead of a separate
 // subtraction (18 instructions) and renormalisation (24), and X3 = R^2 - (PPP + 2 Q) needs no carry_full (27).  e may have any limbs below 2^32:
 // a column gains at most 2^32 against a head-room of 2^58 (9 (6 U^2) + 9 2^58 + carry < 2^64).
-template <class F> BB_HD void mul_addhi_raw_inplace(uint32_t (&a)[NL], const uint32_t (&b)[NL], const uint32_t (&e)[NL])
+template <class F, bool W = false> BB_HD void mul_addhi_raw_inplace(uint32_t (&a)[NL], const uint32_t (&b)[NL], const uint32_t (&e)[NL])
 {
 #if BBGPU_MONT_ASM
-    mul_addhi_raw_inplace_gfx950<F>(a, b, e);
+    if constexpr (W) mul_addhi_raw_inplace_wq_gfx950<F>(a, b, e);
+    else mul_addhi_raw_inplace_gfx950<F>(a, b, e);
     return;
 #endif
     uint32_t m[NL], out[NL];
@@ -364,7 +419,7 @@ template <class F> BB_HD void mul_addhi_raw_inplace(uint32_t (&a)[NL], const uin
         for (int i = 1; i <= k; i++) acc += (uint64_t)a[i] * b[k - i];
 #pragma unroll
         for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * F::P[k - i];
-        m[k] = ((uint32_t)acc * F::PINV) & M29;
+        m[k] = quotient_digit<F, W>((uint32_t)acc, k);
         acc += (uint64_t)m[k] * F::P[0];
         acc >>= 29;
     }
@@ -383,16 +438,17 @@ template <class F> BB_HD void mul_addhi_raw_inplace(uint32_t (&a)[NL], const uin
 #pragma unroll
     for (int i = 0; i < NL; i++) a[i] = out[i];
 }
-template <class F> BB_HD void sqr_addhi_raw(const uint32_t (&a)[NL], const uint32_t (&e)[NL], uint32_t (&out)[NL])
+template <class F, bool W = false> BB_HD void sqr_addhi_raw(const uint32_t (&a)[NL], const uint32_t (&e)[NL], uint32_t (&out)[NL])
 {
 #if BBGPU_MONT_ASM
-    sqr_addhi_raw_gfx950<F>(a, e, out);
+    if constexpr (W) sqr_addhi_raw_wq_gfx950<F>(a, e, out);
+    else sqr_addhi_raw_gfx950<F>(a, e, out);
     return;
 #endif
     uint32_t t[NL];
 #pragma unroll
     for (int i = 0; i < NL; i++) t[i] = a[i];
-    mul_addhi_raw_inplace<F>(t, a, e); // the host form: the plain product (the device form saves the 36 symmetric multiply-adds)
+    mul_addhi_raw_inplace<F, W>(t, a, e); // the host form: the plain product (the device form saves the 36 symmetric multiply-adds)
 #pragma unroll
     for (int i = 0; i < NL; i++) out[i] = t[i];
 }
@@ -401,6 +457,13 @@ constexpr int mul_v(int v1, int v2)
 {
     return (v1 * v2) / 169 + 2;
 }
+// The typed layer below picks the digit form per call site: wide where the field admits it (F::WIDE_DIGITS: Fq, the field of the MSM kernels, whose time
+// follows their instruction count; not Fr -- the transforms issued fewer instructions with wide digits and ran no faster, profiles/wideq_ab.txt) AND the
+// worst column for the operands' limb bounds fits 64 bits; else masked (whose own limit, ll <= 6, the static_asserts of each form keep).
+template <class F, int LL, bool ADDHI = false> struct Digits {
+    static constexpr bool wide = F::WIDE_DIGITS && wide_columns_fit<F>(LL, ADDHI);
+    static_assert(wide || columns_fit<F>(LL, false, ADDHI), "worst column of this product overflows 64 bits: weak() an operand");
+};
 
 template <class F, int L1, int V1, int L2, int V2>
 BB_HD Fe<F, 1, mul_v(V1, V2)> mul(const Fe<F, L1, V1>& a, const Fe<F, L2, V2>& b)
@@ -408,17 +471,17 @@ BB_HD Fe<F, 1, mul_v(V1, V2)> mul(const Fe<F, L1, V1>& a, const Fe<F, L2, V2>& b
     static_assert(mul_v(V1, V2) <= MAXV, "product value bound too large");
     Fe<F, 1, mul_v(V1, V2)> r;
     if constexpr (L1 * L2 <= 6) {
-        mul_raw<F>(a.d, b.d, r.d);
+        mul_raw<F, Digits<F, L1 * L2>::wide>(a.d, b.d, r.d);
     } else if constexpr (L1 >= L2 && L2 <= 6) {
         Fe<F, 1, V1> an = weak(a);
-        mul_raw<F>(an.d, b.d, r.d);
+        mul_raw<F, Digits<F, L2>::wide>(an.d, b.d, r.d);
     } else if constexpr (L2 > L1 && L1 <= 6) {
         Fe<F, 1, V2> bn = weak(b);
-        mul_raw<F>(a.d, bn.d, r.d);
+        mul_raw<F, Digits<F, L1>::wide>(a.d, bn.d, r.d);
     } else {
         Fe<F, 1, V1> an = weak(a);
         Fe<F, 1, V2> bn = weak(b);
-        mul_raw<F>(an.d, bn.d, r.d);
+        mul_raw<F, Digits<F, 1>::wide>(an.d, bn.d, r.d);
     }
     return r;
 }
@@ -434,7 +497,7 @@ BB_HD Fe<F, 1, mul2_v(V1, V2, V3, V4)> mul_add(const Fe<F, L1, V1>& a, const Fe<
     static_assert(L1 * L2 + L3 * L4 <= 6, "limb bounds too large for a shared reduction: weak() an operand");
     static_assert(mul2_v(V1, V2, V3, V4) <= MAXV, "value bound too large");
     Fe<F, 1, mul2_v(V1, V2, V3, V4)> r;
-    mul2_raw<F>(a.d, b.d, c.d, d.d, r.d);
+    mul2_raw<F, Digits<F, L1 * L2 + L3 * L4>::wide>(a.d, b.d, c.d, d.d, r.d);
     return r;
 }
 // a*b - c*d = a*b + (Kp - c)*d, one reduction
@@ -453,7 +516,7 @@ BB_HD Fe<F, 1, mul_v(V1, V2)> mul_ip(const Fe<F, L1, V1>& a, const Fe<F, L2, V2>
     Fe<F, 1, mul_v(V1, V2)> r;
 #pragma unroll
     for (int i = 0; i < NL; i++) r.d[i] = a.d[i];
-    mul_raw_inplace<F>(r.d, b.d);
+    mul_raw_inplace<F, Digits<F, L1 * L2>::wide>(r.d, b.d);
     return r;
 }
 // a*b + c*d with the result in c's registers (one reduction)
@@ -465,7 +528,7 @@ BB_HD Fe<F, 1, mul2_v(V1, V2, V3, V4)> mul_add_ip(const Fe<F, L1, V1>& a, const 
     Fe<F, 1, mul2_v(V1, V2, V3, V4)> r;
 #pragma unroll
     for (int i = 0; i < NL; i++) r.d[i] = c.d[i];
-    mul2_raw_inplace<F>(a.d, b.d, r.d, d.d);
+    mul2_raw_inplace<F, Digits<F, L1 * L2 + L3 * L4>::wide>(a.d, b.d, r.d, d.d);
     return r;
 }
 
@@ -478,7 +541,7 @@ BB_HD FeE<F, mul_v(V1, V2) + V3> mul_addhi_ip(const Fe<F, L1, V1>& a, const Fe<F
     FeE<F, mul_v(V1, V2) + V3> r;
 #pragma unroll
     for (int i = 0; i < NL; i++) r.d[i] = a.d[i];
-    mul_addhi_raw_inplace<F>(r.d, b.d, e.d);
+    mul_addhi_raw_inplace<F, Digits<F, L1 * L2, true>::wide>(r.d, b.d, e.d);
     return r;
 }
 // REDC(a^2) + e, exact limbs
@@ -487,7 +550,7 @@ template <class F, int L1, int V1, int L3, int V3> BB_HD FeE<F, mul_v(V1, V1) + 
     static_assert(L1 * L1 <= 6, "limb bound too large for the squaring: weak() the operand");
     static_assert(mul_v(V1, V1) + V3 <= MAXV, "value bound too large");
     FeE<F, mul_v(V1, V1) + V3> r;
-    sqr_addhi_raw<F>(a.d, e.d, r.d);
+    sqr_addhi_raw<F, Digits<F, L1 * L1, true>::wide>(a.d, e.d, r.d);
     return r;
 }
 
@@ -495,10 +558,10 @@ template <class F, int L1, int V1> BB_HD Fe<F, 1, mul_v(V1, V1)> sqr(const Fe<F,
 {
     Fe<F, 1, mul_v(V1, V1)> r;
     if constexpr (L1 * L1 <= 6) {
-        sqr_raw<F>(a.d, r.d);
+        sqr_raw<F, Digits<F, L1 * L1>::wide>(a.d, r.d);
     } else {
         Fe<F, 1, V1> an = weak(a);
-        sqr_raw<F>(an.d, r.d);
+        sqr_raw<F, Digits<F, 1>::wide>(an.d, r.d);
     }
     return r;
 }

@@ -129,6 +129,9 @@ template <int V> BB_HD void madd(Xyzz& acc, const AffineV<V>& a)
 //  * the full "PP == 0 (mod p)" comparison (27 compares over the limbs) runs only when limb 0 of PP is one of the three values it
 //    can have then; P == acc (rare: equal points in one bucket) doubles the accumulator itself, so the operand is dead after the
 //    first two products and they, too, run in place.
+//  * eight of the nine reductions take wide quotient digits (fe.hpp: Fq, limb bounds with L1 L2 <= 4); Y3 = R (Q - X3) + (-Y1) PPP has 1 * 3 + 3 * 1 = 6 and keeps
+//    the masked digit -- renormalising an operand for it would cost 24 instructions to save 8.  No value bound moves (the top digit stays masked), so PP is
+//    still one of 0, p, 2p when P vanishes and X3 still fits the accumulator's 12 p.
 // a.x, a.y: the operand (y already negated where the digit is negative), consumed.
 template <int VX, int VY> BB_HD void madd_ip(Xyzz& acc, bool& acc_inf, const Fe<Fq, 1, VX>& ax, const Fe<Fq, 1, VY>& ay)
 {

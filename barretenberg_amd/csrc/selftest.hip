@@ -12,6 +12,7 @@
 #include "bbgpu_internal.h"
 #include "g1.hpp"
 #include "g1_quad.hpp"
+#include "selftest_raw.hpp"
 
 namespace bbgpu {
 namespace {
@@ -110,6 +111,14 @@ template <class F> __global__ void selftest_field_kernel(const uint64_t* a_in, c
     }
     default: o[0] = o[1] = o[2] = o[3] = ~0ull;
     }
+}
+
+// ---- raw-limb ops: the wide quotient-digit forms themselves, limb for limb (selftest_raw.hpp: the same function runs in tests/cpp/fe_wideq_twin.cpp on the host)
+template <class F> __global__ void selftest_raw_kernel(const uint64_t* a_in, const uint64_t* b_in, uint64_t* out, int m, int op)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    raw_dispatch<F>(op, (const uint32_t*)a_in, (const uint32_t*)b_in, (uint32_t*)out, m, i);
 }
 
 __device__ bool ld_jacobian(Xyzz& r, const uint64_t* j)
@@ -287,12 +296,19 @@ extern "C" {
 
 int bbgpu_selftest_field(int field, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out)
 {
-    if (!a || !b || !out || n == 0 || n > (1u << 20) || (field != 0 && field != 1)) return BBGPU_ERR_ARG;
+    const bool raw = op >= BBGPU_SELFTEST_WIDE_MUL && op <= BBGPU_SELFTEST_WIDE_CHAIN;
+    if (!a || !b || !out || n == 0 || n > (1u << 20) || (field != 0 && field != 1) || (raw && n % 3 != 0)) return BBGPU_ERR_ARG;
     if (bbgpu_device_count() == 0) {
         set_error("no HIP device available: libbbgpu has no CPU fallback");
         return BBGPU_ERR_HIP;
     }
     return run(a, n * 32, b, n * 32, out, n * 32, (int)n, [&](uint64_t* da, uint64_t* db, uint64_t* dout) {
+        if (raw) {
+            const int m = (int)(n / 3), mblocks = (m + 63) / 64;
+            if (field == 0) selftest_raw_kernel<FqP><<<mblocks, 64>>>(da, db, dout, m, op);
+            else selftest_raw_kernel<FrP><<<mblocks, 64>>>(da, db, dout, m, op);
+            return;
+        }
         const int blocks = (int)((n + 63) / 64);
         if (field == 0) selftest_field_kernel<FqP><<<blocks, 64>>>(da, db, dout, (int)n, op);
         else selftest_field_kernel<FrP><<<blocks, 64>>>(da, db, dout, (int)n, op);

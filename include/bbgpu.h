@@ -691,7 +691,19 @@ enum {
     BBGPU_SELFTEST_SQR_LAZY = 11,  /* (2a - b)^2 */
     BBGPU_SELFTEST_ZERO_TESTS = 12,/* limb 0: bit 0 = (a - b == 0), bit 1 = ((a - b) a == 0) */
     BBGPU_SELFTEST_MUL_ADDHI = 13, /* a b - a                     the product with a third operand added inside its reduction (in place; the mixed addition's P and R) */
-    BBGPU_SELFTEST_SQR_ADDHI = 14  /* a^2 - (b + 2a)              the same for the squaring, addend with unnormalised limbs (the mixed addition's X3) */
+    BBGPU_SELFTEST_SQR_ADDHI = 14, /* a^2 - (b + 2a)              the same for the squaring, addend with unnormalised limbs (the mixed addition's X3) */
+    /* Raw-limb ops: the wide quotient-digit forms of csrc/fe.hpp themselves (32-bit digits 0..7, the top digit masked), result limbs as they come out.
+     * A case is THREE consecutive rows (24 words) of a, b and out: a = the nine 32-bit limbs of operand a, then of c; b = limbs of b, then of d (a b + c d)
+     * or of the addend e; out = the nine result limbs, then zeros.  n = 3 x cases. */
+    BBGPU_SELFTEST_WIDE_MUL = 15,          /* REDC(a b) */
+    BBGPU_SELFTEST_WIDE_SQR = 16,          /* REDC(a^2) */
+    BBGPU_SELFTEST_WIDE_MUL2 = 17,         /* REDC(a b + c d) */
+    BBGPU_SELFTEST_WIDE_MUL_IP = 18,       /* REDC(a b), in a's registers */
+    BBGPU_SELFTEST_WIDE_MUL2_IP = 19,      /* REDC(a b + c d), in c's registers */
+    BBGPU_SELFTEST_WIDE_MUL_ADDHI_IP = 20, /* REDC(a b) + e, in a's registers */
+    BBGPU_SELFTEST_WIDE_SQR_ADDHI = 21,    /* REDC(a^2) + e */
+    BBGPU_SELFTEST_WIDE_CHAIN = 22         /* case i: operand a of case i, then 255 in-place steps with the operands a of the cases after it (wrapping),
+                                              cycling x y, x^2 + y, y x + x y, x y + y; operands: field values below 6 p with exact limbs */
 };
 enum {
     BBGPU_SELFTEST_G1_MADD = 0,      /* p + (q.x, q.y)                                             g1::mixed_add, group.hpp:219-322 */

@@ -6,7 +6,7 @@ Why: hipcc's schedule of the same C++ (fe.hpp mul_raw/sqr_raw/mul2_raw) starts e
 previous column's carry with a separate 64-bit addition (v_lshl_add_u64: 17 per multiplication, 144 in one mixed
 addition); here the carry is the addend of the column's first v_mad_u64_u32 and one accumulator walks all 18 columns.
 Per multiplication: 162 v_mad_u64_u32 + 9 v_mul_lo_u32 + 17 v_and_b32 + 17 v_lshrrev_b64 + 1 v_alignbit_b32 = 206
-instructions (the compiler: 277).  Semantics are those of fe.hpp (field_impl_int128.tcc:72-137 in the reference, other radix).
+instructions (the compiler: 277); the *_wq_* variants (wide quotient digits, see low_column) 8 v_and_b32 fewer.  Semantics are those of fe.hpp (field_impl_int128.tcc:72-137 in the reference, other radix).
 
 The accumulator pair and one scratch register are FIXED physical VGPRs (clobbers): AMDGPU inline asm has no
 sub-register operand modifier, and the low word of the 64-bit accumulator feeds v_mul_lo_u32 / v_and_b32.
@@ -31,7 +31,12 @@ def mad(x, y, first):
 # (operand limb j is last read in column j + 8, out[j] is written at the end of column j + 9) and the quotient digits live in nine
 # scratch registers.  Same instructions, same count; what changes is where the result lands: a loop-carried value multiplied in place
 # (ZZ3 = ZZ1 * PP in the bucket accumulation) stays in its registers and the loop's back edge needs no copies.
-def low_column(ins, k, prods, q="r"):
+# Wide quotient digits (wide=True, the *_wq_* functions): digits 0..7 are the full 32-bit v_mul_lo_u32 by p' = -p^-1 mod 2^32 -- t + q p
+# vanishes modulo 2^32, hence modulo 2^29, so the mask is not needed and the digit is written where it lives: eight v_and_b32 fewer per
+# product.  The TOP digit keeps its mask: the quotient then stays below 2^261 (1 + 2^-26) and the result below t / R + p (1 + 2^-26), the value
+# bound of the masked form, where nine unmasked digits would add 8 p to every result.  What grows is the column sum (digit * p limb up to
+# 2^61): fe.hpp admits the wide forms only for operand limb bounds whose worst column stays below 2^64 (wide_columns_fit).
+def low_column(ins, k, prods, q="r", wide=False):
     """prods: list of (x, y) operand names of the a*b-type products of column k"""
     first = (k == 0)
     for (x, y) in prods:
@@ -39,8 +44,11 @@ def low_column(ins, k, prods, q="r"):
         first = False
     for i in range(k):
         ins.append(mad(f"%[{q}{i}]", f"%[p{k - i}]", False))
-    ins.append(f"v_mul_lo_u32 {TMP}, {ACC_LO}, %[pinv]")
-    ins.append(f"v_and_b32 %[{q}{k}], {MASK}, {TMP}")
+    if wide and k < NL - 1:
+        ins.append(f"v_mul_lo_u32 %[{q}{k}], {ACC_LO}, %[pinv]")
+    else:
+        ins.append(f"v_mul_lo_u32 {TMP}, {ACC_LO}, %[pinv]")
+        ins.append(f"v_and_b32 %[{q}{k}], {MASK}, {TMP}")
     ins.append(mad(f"%[{q}{k}]", "%[p0]", False))
     ins.append(f"v_lshrrev_b64 {ACC}, 29, {ACC}")
 
@@ -67,18 +75,18 @@ def high_column(ins, k, prods, q="r", o="r", e=None):
             ins.append(f"v_add_u32 %[{o}8], %[{o}8], %[{e}8]")
 
 
-def gen_mul(q="r", o="r", e=None):
+def gen_mul(q="r", o="r", e=None, wide=False):
     ins = []
     for k in range(2 * NL - 1):
         prods = [(f"%[a{i}]", f"%[b{k - i}]") for i in range(NL) if 0 <= k - i < NL]
         if k < NL:
-            low_column(ins, k, prods, q)
+            low_column(ins, k, prods, q, wide)
         else:
             high_column(ins, k, prods, q, o, e)
     return ins
 
 
-def gen_mul2(q="r", o="r"):
+def gen_mul2(q="r", o="r", wide=False):
     ins = []
     for k in range(2 * NL - 1):
         prods = []
@@ -87,13 +95,13 @@ def gen_mul2(q="r", o="r"):
                 prods.append((f"%[a{i}]", f"%[b{k - i}]"))
                 prods.append((f"%[c{i}]", f"%[d{k - i}]"))
         if k < NL:
-            low_column(ins, k, prods, q)
+            low_column(ins, k, prods, q, wide)
         else:
             high_column(ins, k, prods, q, o)
     return ins
 
 
-def gen_sqr(e=None):
+def gen_sqr(e=None, wide=False):
     ins = [f"v_lshlrev_b32 %[t{i}], 1, %[a{i}]" for i in range(NL - 1)]
     for k in range(2 * NL - 1):
         prods = []
@@ -104,7 +112,7 @@ def gen_sqr(e=None):
             if i < j < NL:
                 prods.append((f"%[t{i}]", f"%[a{j}]"))
         if k < NL:
-            low_column(ins, k, prods)
+            low_column(ins, k, prods, wide=wide)
         else:
             high_column(ins, k, prods, e=e)
     return ins
@@ -117,7 +125,7 @@ def count(ins):
     return c
 
 
-def emit_fn(name, sig, ins, outs, ins_v, temps, one=False):
+def emit_fn(name, sig, ins, outs, ins_v, temps, one=False, wide=False):
     lines = []
     lines.append(f"// {name}: " + ", ".join(f"{v} {k}" for k, v in sorted(count(ins).items())) + f" = {len(ins)} instructions")
     lines.append(f"template <class F> __device__ __forceinline__ void {name}({sig})")
@@ -129,7 +137,7 @@ def emit_fn(name, sig, ins, outs, ins_v, temps, one=False):
         lines.append(f'        "{s}\\n\\t"')
     lines.append("        : " + ", ".join(outs))
     lines.append("        : " + ", ".join(ins_v) + ",")
-    lines.append("          " + ", ".join(f'[p{i}] "s"(F::P[{i}])' for i in range(NL)) + ', [pinv] "s"(F::PINV)' + (', [one] "s"(1u)' if one else ""))
+    lines.append("          " + ", ".join(f'[p{i}] "s"(F::P[{i}])' for i in range(NL)) + ', [pinv] "s"(F::PINV' + ("32" if wide else "") + ')' + (', [one] "s"(1u)' if one else ""))
     lines.append(f"        : {CLOBBERS});")
     lines.append("}")
     return "\n".join(lines)
@@ -149,29 +157,33 @@ def main():
     b_in = [f'[b{i}] "v"(b[{i}])' for i in range(NL)]
     c_in = [f'[c{i}] "v"(c[{i}])' for i in range(NL)]
     d_in = [f'[d{i}] "v"(d[{i}])' for i in range(NL)]
-    print(emit_fn("mul_raw_gfx950", "const uint32_t (&a)[9], const uint32_t (&b)[9], uint32_t (&out)[9]", gen_mul(), outs, a_in + b_in, []))
-    print()
-    t_out = [f'[t{i}] "=&v"(t{i})' for i in range(NL - 1)]
-    print(emit_fn("sqr_raw_gfx950", "const uint32_t (&a)[9], uint32_t (&out)[9]", gen_sqr(), outs + t_out, a_in, [f"t{i}" for i in range(NL - 1)]))
-    print()
-    print(emit_fn("mul2_raw_gfx950", "const uint32_t (&a)[9], const uint32_t (&b)[9], const uint32_t (&c)[9], const uint32_t (&d)[9], uint32_t (&out)[9]",
-                  gen_mul2(), outs, a_in + b_in + c_in + d_in, []))
-    print()
-    # in-place forms: the result replaces operand a (mul) / operand c (a*b + c*d); quotient digits in scratch registers
-    m_tmp = [f"m{i}" for i in range(NL)]
-    m_out = [f'[m{i}] "=&v"(m{i})' for i in range(NL)]
-    a_io = [f'[a{i}] "+v"(a[{i}])' for i in range(NL)]
-    c_io = [f'[c{i}] "+v"(c[{i}])' for i in range(NL)]
-    print(emit_fn("mul_raw_inplace_gfx950", "uint32_t (&a)[9], const uint32_t (&b)[9]", gen_mul("m", "a"), a_io + m_out, b_in, m_tmp))
-    print()
-    print(emit_fn("mul2_raw_inplace_gfx950", "const uint32_t (&a)[9], const uint32_t (&b)[9], uint32_t (&c)[9], const uint32_t (&d)[9]",
-                  gen_mul2("m", "c"), c_io + m_out, a_in + b_in + d_in, m_tmp))
-    print()
-    # "addhi" forms: REDC(a b) + e and REDC(a^2) + e with e's limbs added inside the product's carry chain (exact limbs out)
-    e_in = [f'[e{i}] "v"(e[{i}])' for i in range(NL)]
-    print(emit_fn("mul_addhi_raw_inplace_gfx950", "uint32_t (&a)[9], const uint32_t (&b)[9], const uint32_t (&e)[9]", gen_mul("m", "a", "e"), a_io + m_out, b_in + e_in, m_tmp, one=True))
-    print()
-    print(emit_fn("sqr_addhi_raw_gfx950", "const uint32_t (&a)[9], const uint32_t (&e)[9], uint32_t (&out)[9]", gen_sqr("e"), outs + t_out, a_in + e_in, [f"t{i}" for i in range(NL - 1)], one=True))
+    for wide, sfx in ((False, ""), (True, "_wq")):
+        if wide:
+            print()
+            print("// ---- wide quotient digits: digits 0..7 unmasked 32-bit (p' mod 2^32), the top digit masked; see tools/gen_mont_asm.py ----")
+        print(emit_fn(f"mul_raw{sfx}_gfx950", "const uint32_t (&a)[9], const uint32_t (&b)[9], uint32_t (&out)[9]", gen_mul(wide=wide), outs, a_in + b_in, [], wide=wide))
+        print()
+        t_out = [f'[t{i}] "=&v"(t{i})' for i in range(NL - 1)]
+        print(emit_fn(f"sqr_raw{sfx}_gfx950", "const uint32_t (&a)[9], uint32_t (&out)[9]", gen_sqr(wide=wide), outs + t_out, a_in, [f"t{i}" for i in range(NL - 1)], wide=wide))
+        print()
+        print(emit_fn(f"mul2_raw{sfx}_gfx950", "const uint32_t (&a)[9], const uint32_t (&b)[9], const uint32_t (&c)[9], const uint32_t (&d)[9], uint32_t (&out)[9]",
+                      gen_mul2(wide=wide), outs, a_in + b_in + c_in + d_in, [], wide=wide))
+        print()
+        # in-place forms: the result replaces operand a (mul) / operand c (a*b + c*d); quotient digits in scratch registers
+        m_tmp = [f"m{i}" for i in range(NL)]
+        m_out = [f'[m{i}] "=&v"(m{i})' for i in range(NL)]
+        a_io = [f'[a{i}] "+v"(a[{i}])' for i in range(NL)]
+        c_io = [f'[c{i}] "+v"(c[{i}])' for i in range(NL)]
+        print(emit_fn(f"mul_raw_inplace{sfx}_gfx950", "uint32_t (&a)[9], const uint32_t (&b)[9]", gen_mul("m", "a", wide=wide), a_io + m_out, b_in, m_tmp, wide=wide))
+        print()
+        print(emit_fn(f"mul2_raw_inplace{sfx}_gfx950", "const uint32_t (&a)[9], const uint32_t (&b)[9], uint32_t (&c)[9], const uint32_t (&d)[9]",
+                      gen_mul2("m", "c", wide=wide), c_io + m_out, a_in + b_in + d_in, m_tmp, wide=wide))
+        print()
+        # "addhi" forms: REDC(a b) + e and REDC(a^2) + e with e's limbs added inside the product's carry chain (exact limbs out)
+        e_in = [f'[e{i}] "v"(e[{i}])' for i in range(NL)]
+        print(emit_fn(f"mul_addhi_raw_inplace{sfx}_gfx950", "uint32_t (&a)[9], const uint32_t (&b)[9], const uint32_t (&e)[9]", gen_mul("m", "a", "e", wide=wide), a_io + m_out, b_in + e_in, m_tmp, one=True, wide=wide))
+        print()
+        print(emit_fn(f"sqr_addhi_raw{sfx}_gfx950", "const uint32_t (&a)[9], const uint32_t (&e)[9], uint32_t (&out)[9]", gen_sqr("e", wide=wide), outs + t_out, a_in + e_in, [f"t{i}" for i in range(NL - 1)], one=True, wide=wide))
     print("} // namespace bbgpu")
 
 
