@@ -61,6 +61,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_host_pairing", "bbgpu_host_pairing_check", "bbgpu_transcript_read_g2", "bbgpu_srs_check", "bbgpu_host_srs_check",
     "bbgpu_plonk_verifier_create", "bbgpu_plonk_verifier_destroy", "bbgpu_plonk_verify_batch", "bbgpu_host_plonk_verify_batch", "bbgpu_plonk_verify_last_timing",
     "bbgpu_srs_update", "bbgpu_host_srs_update", "bbgpu_host_srs_update_check", "bbgpu_transcript_write_g2", "bbgpu_selftest_endo_split",
+    "bbgpu_srs_lagrange", "bbgpu_host_srs_lagrange",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -115,6 +116,15 @@ class SrsUpdateReport(C.Structure):
         d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32) and k != "_pad"}
         d.update(y_g2=[int(v) for v in self.y_g2], g2_x_out=[int(v) for v in self.g2_x_out])
         return d
+
+
+class SrsLagrangeReport(C.Structure):
+    """bbgpu_srs_lagrange_report (include/bbgpu.h)"""
+    NONE = 0xFFFFFFFFFFFFFFFF  # first_bad_point / first_infinity_row when there is none
+    _fields_ = [(k, C.c_uint64) for k in ("n", "bad_points", "first_bad_point", "infinity_rows", "first_infinity_row")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class PlonkVerifyReport(C.Structure):
@@ -428,6 +438,29 @@ class BbGpu:
         """bbgpu_transcript_write_g2: write_transcript for a string whose secret nobody holds; g2_x = x G2 (16,)"""
         self.lib.bbgpu_transcript_write_g2.argtypes = [C.c_char_p, u64p, C.c_size_t, u64p]
         self._chk(self.lib.bbgpu_transcript_write_g2(path.encode(), _ptr(table), degree, _ptr(np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16))))
+
+    # ---- the same string in the Lagrange basis  (bbgpu_srs_lagrange and its host twin) ----
+    def srs_lagrange(self, handle, n, want_host_table=False):
+        """bbgpu_srs_lagrange: rows [0, n) of a resident table -> (new handle of L_i = n^-1 sum_j omega^(-ij) P_j, its (2n, 8) host table or None,
+        SrsLagrangeReport).  A row off the curve or an output row at infinity raises BbGpuError with the report in .report; no table is made."""
+        table = np.zeros((2 * n, 8), dtype=np.uint64) if want_host_table else None
+        rep = SrsLagrangeReport()
+        self.lib.bbgpu_srs_lagrange.argtypes = [C.c_int, C.c_size_t, u64p, C.POINTER(SrsLagrangeReport)]
+        h = self.lib.bbgpu_srs_lagrange(int(handle), int(n), _ptr(table) if want_host_table else None, C.byref(rep))
+        if h < 0:
+            raise self._srs_update_error(h, rep)
+        return h, table, rep
+
+    def host_srs_lagrange(self, table, n, out=None):
+        """bbgpu_host_srs_lagrange: the same over the even entries of a (2n, 8) endo table, on the host -> (table, SrsLagrangeReport); out: the array to
+        write (may be `table` itself), default a new one"""
+        out = np.zeros((2 * n, 8), dtype=np.uint64) if out is None else out
+        rep = SrsLagrangeReport()
+        self.lib.bbgpu_host_srs_lagrange.argtypes = [u64p, C.c_size_t, u64p, C.POINTER(SrsLagrangeReport)]
+        rc = self.lib.bbgpu_host_srs_lagrange(_ptr(table), int(n), _ptr(out), C.byref(rep))
+        if rc < 0:
+            raise self._srs_update_error(rc, rep)
+        return out, rep
 
     def selftest_endo_split(self, k, on_device=True):
         """bbgpu_selftest_endo_split: k (n, 4) plain integers -> (n, 6): |k1| (2), |k2| (2), flags, 0"""

@@ -123,6 +123,10 @@ struct SrsCurveFindings {
 int srs_check_curve(const uint32_t* d_srs, size_t n, const uint64_t generator_m261[8], SrsCurveFindings* d_out, hipStream_t st);
 int srs_check_scalars(const uint64_t seed[4], size_t count, uint64_t* d_out, hipStream_t st);
 
+// srs_lagrange.hip: rows [0, n) of a resident table in the Lagrange basis of the size-n domain, into a new allocation (bbgpu_srs_lagrange)
+int srs_lagrange_rows(const uint32_t* d_in, size_t n, int log2n, const uint32_t winv_m261[9], const uint64_t ninv_plain[4], SrsCurveFindings* d_find,
+                      SrsCurveFindings* found, uint32_t** d_out_rows, uint64_t* host_table_out, hipStream_t st, float* ms3 = nullptr);
+
 // plonk_verify.hip: the device parts of bbgpu_plonk_verify_batch that are not an MSM
 struct VerifyDeviceKey {
     uint32_t log2n, widgets, num_vk;

@@ -29,6 +29,7 @@
 #include "host_pairing.hpp"
 #include "host_srs_check.hpp"
 #include "host_srs_update.hpp"
+#include "host_srs_lagrange.hpp"
 #include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
@@ -2206,6 +2207,98 @@ int bbgpu_srs_update(int srs_handle, size_t n, size_t first_power, const uint64_
         ctx().last.count = 1;
         ctx().last.ms[0] = kernel_ms;
     }
+    return add_srs(host_endo_table_out, n, d, false);
+}
+
+/* ---- the SRS in the Lagrange basis (host_srs_lagrange.hpp, srs_lagrange.hip) ---- */
+static int srs_lagrange_args(size_t n, int* log2n)
+{
+    if (n == 0) {
+        set_error("SRS Lagrange basis: n == 0");
+        return BBGPU_ERR_ARG;
+    }
+    if ((*log2n = host::srs_lagrange_log2(n)) < 0) {
+        set_error("SRS Lagrange basis: n = %zu is not a power of two between 2 and 2^%d", n, host::SRS_LAGRANGE_MAX_LOG2);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
+static int srs_lagrange_refusal(const bbgpu_srs_lagrange_report& rep)
+{
+    if (rep.bad_points)
+        set_error("SRS Lagrange basis: row %llu is not on the curve (%llu such rows)", (unsigned long long)rep.first_bad_point, (unsigned long long)rep.bad_points);
+    else
+        set_error("SRS Lagrange basis: output row %llu is the point at infinity (%llu such rows)", (unsigned long long)rep.first_infinity_row,
+                  (unsigned long long)rep.infinity_rows);
+    return BBGPU_ERR_ARG;
+}
+
+int bbgpu_host_srs_lagrange(const uint64_t* points_endo_table, size_t n, uint64_t* table_out, bbgpu_srs_lagrange_report* out)
+{
+    if (!points_endo_table || !table_out) {
+        set_error("SRS Lagrange basis: null table");
+        return BBGPU_ERR_ARG;
+    }
+    int log2n;
+    if (int rc = srs_lagrange_args(n, &log2n)) return rc;
+    bbgpu_srs_lagrange_report rep;
+    host::srs_lagrange_report_init(&rep, n);
+    const int rc = host::srs_lagrange_host(points_endo_table, n, log2n, table_out, &rep);
+    if (out) *out = rep;
+    return rc ? srs_lagrange_refusal(rep) : rc;
+}
+
+int bbgpu_srs_lagrange(int srs_handle, size_t n, uint64_t* host_endo_table_out, bbgpu_srs_lagrange_report* out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound: a handle can only exist once one is
+    int log2n;
+    if (int rc = srs_lagrange_args(n, &log2n)) return rc;
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
+        set_error("unknown SRS handle %d", srs_handle);
+        return BBGPU_ERR_ARG;
+    }
+    if (n > ctx().srs[srs_handle].n) {
+        set_error("SRS Lagrange basis of %zu rows, the table holds %zu", n, ctx().srs[srs_handle].n);
+        return BBGPU_ERR_SIZE;
+    }
+    if (int rc = ensure_init()) return rc;
+    bbgpu_srs_lagrange_report rep;
+    host::srs_lagrange_report_init(&rep, n);
+    const uint32_t* d_in = ctx().srs[srs_handle].d_srs; // add_srs below may move the registry: nothing of the entry is held across it
+    const hipStream_t st = ctx().stream;
+    // two findings in the staging of bbgpu_srs_check, started by one upload: [0] the curve pass over the input rows (the generator verdict is not used),
+    // [1] the output rows at infinity
+    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, 64)) return rc;
+    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
+    static_assert(2 * sizeof(SrsCurveFindings) <= 64, "two findings fit the staging");
+    const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    const SrsCurveFindings init[2] = { { 0, ~0ull, 0, 0 }, { 0, ~0ull, 0, 0 } };
+    SrsCurveFindings got = init[0], infinite = init[1];
+    CHK(h2d_async(d_find, init, sizeof init, st));
+    if (int rc = srs_check_curve(d_in, n, no_generator, d_find, st)) return rc;
+    CHK(d2h_async(&got, d_find, sizeof got, st));
+    CHK(hipStreamSynchronize(st));
+    rep.bad_points = got.bad_points;
+    rep.first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
+    if (rep.bad_points) {
+        if (out) *out = rep;
+        return srs_lagrange_refusal(rep);
+    }
+    host::Fr winv, ninv;
+    host::srs_lagrange_constants(log2n, &winv, &ninv);
+    const Limbs9 wl = host::limbs_m261(winv);
+    uint32_t* d = nullptr;
+    float ms3[3] = { 0, 0, 0 };
+    if (int rc = srs_lagrange_rows(d_in, n, log2n, wl.d, ninv.d, d_find + 1, &infinite, &d, host_endo_table_out, st, ctx().timing ? ms3 : nullptr)) return rc;
+    rep.infinity_rows = infinite.bad_points;
+    rep.first_infinity_row = infinite.bad_points ? infinite.first_bad_point : UINT64_MAX;
+    if (out) *out = rep;
+    if (ctx().timing) { // bbgpu_last_timing: index 0 the stage kernels alone, 1 the load (scaling) kernel, 2 the finish kernel
+        ctx().last.count = 3;
+        for (int i = 0; i < 3; i++) ctx().last.ms[i] = ms3[i];
+    }
+    if (rep.infinity_rows) return srs_lagrange_refusal(rep);
     return add_srs(host_endo_table_out, n, d, false);
 }
 

@@ -604,6 +604,54 @@ int bbgpu_host_srs_update_check(const uint64_t old_p1[8], const uint64_t new_p1[
 /* bbgpu_transcript_write for a string whose secret nobody holds: the caller gives x G2 itself (BBGPU_ERR_ARG unless bbgpu_srs_check would accept it) */
 int bbgpu_transcript_write_g2(const char* path, const uint64_t* points_endo_table, size_t degree, const uint64_t g2_x[16]);
 
+/* ---- the same string in the Lagrange basis: a group inverse NTT of a resident table ------
+ * Every table above is in the monomial basis, P_j = x^j G.  A caller who holds a polynomial as its VALUES v_i on the size-n domain commits to it over
+ *   L_i = n^-1 * sum_{j<n} omega^(-i j) * P_j          (for an honest string this is L_i(x) G; omega the root the transforms use, fr_root_of_unity(log2 n))
+ * without an inverse transform first: with c = ifft(v), sum_i v_i L_i = sum_j c_j P_j.  bbgpu_srs_lagrange makes that table from rows [0, n) of a resident
+ * one: an inverse NTT whose elements are curve points, n/2 log2 n variable-base multiplications by 254-bit twiddles.  The reference has no counterpart.
+ *   n            a power of two, 2 <= n <= 2^22, no larger than the table: otherwise BBGPU_ERR_SIZE.  n == 0 or an unknown handle: BBGPU_ERR_ARG.  All of
+ *                these are refused before a device is bound.
+ *   bad rows     as in bbgpu_srs_update: the curve pass (k_srs_on_curve) runs over the input rows first; if any fails, the report is written (when out is
+ *                given), NO table is made and the entry returns BBGPU_ERR_ARG, bbgpu_last_error() naming the first bad row.
+ *   infinity     the resident form has no infinity row, so an OUTPUT row at infinity is refused the same way: infinity_rows and first_infinity_row in the
+ *                report, BBGPU_ERR_ARG, the message naming the first such row, no table.  (The table of x = omega^k has L_i = delta_ik G.)  Infinities and
+ *                doublings INSIDE the transform are no errors: every addition is complete.
+ *   new table    a NEW resident table, added the way bbgpu_srs_update adds its own: window tables under the same conditions (bbgpu_set_precompute,
+ *                n >= 1024; an allocation the tables cannot get is ridden out without them), host_endo_table_out -- filled by the export kernel of
+ *                bbgpu_srs_generate -- as the address key when given.  The input handle is untouched and stays valid; every MSM entry serves the new one.
+ * Return codes: the new handle (>= 0), BBGPU_ERR_SIZE, BBGPU_ERR_ARG or BBGPU_ERR_HIP.  On any failure no handle has been created, nothing the call
+ * allocated is still live and no MSM ticket is outstanding.  The entry runs on context 0 under the library mutex; every allocation, copy and launch check
+ * passes the fault-injection funnels (a warm call: the scratch and the new rows + the export buffer + those of the window tables; one upload; two
+ * read-backs + the host table's; two launch checks -- the curve pass, and the chain of load, stage and finish kernels -- + the export kernel's + one per
+ * window-table segment).
+ * The kernels (csrc/srs_lagrange.hip): radix-2, decimation in time, on a scratch of n projective points (XYZZ, 128 bytes each, ZZ == 0 for infinity).
+ * k_lagrange_load puts n^-1 * P_bitrev(i) into slot i (one ladder per row); log2 n launches of k_lagrange_stage run (a, b) -> (a + w b, a - w b) in place,
+ * one lane per butterfly, w = omega^-e made in the lane by square-and-multiply and w b by the ladder of k_srs_update (csrc/g1_ladder.hpp: signed
+ * endomorphism split, 3-bit odd signed windows, 126 doublings) over a projective base and without its inversion -- butterflies with w = 1 skip it;
+ * k_lagrange_finish normalises with one Fermat inversion per row and counts the rows at infinity.
+ * With bbgpu_set_timing(1), bbgpu_last_timing() index 0 is the device time of the stage kernels alone, index 1 that of k_lagrange_load, index 2 that of
+ * k_lagrange_finish.
+ * Cost on one MI355X (tools/srs_lagrange_bench.py, profiles/srs_lagrange.txt; one box, k_srs_update measured in the same run): 2^20 rows 183.8 ms wall,
+ * 204.5 ms with the host table, 145.8 ms when the new handle gets no window tables; the stage kernels alone 129.6 ms = 13.7 ns per butterfly that runs a
+ * ladder (~2520 field products; k_srs_update in that run: 15.4 ns per row), the load kernel 14.2 ms, the finish kernel 1.9 ms.  2^16 rows 19.6 ms wall
+ * (stages 14.7 ms), 2^12 rows 17.4 ms (stages 10.7 ms): below 2^18 rows a stage launch no longer fills the chip and every stage costs the ~0.9 ms one wave
+ * needs for its ladder, so small conversions cost log2 n x 0.9 ms.  Host twin: 107 ms per 4096 rows on 16 threads.
+ * The host twin (csrc/host_srs_lagrange.hpp) is a plain radix-2 over host_g1.hpp with a plain double-and-add per twiddle on a few threads; the results are
+ * unique affine points, so the two agree bit for bit, reports included.  It makes no HIP call, takes no lock and is re-entrant. */
+typedef struct {
+    uint64_t n;                  /* rows converted: rows [0, n) of the handle */
+    uint64_t bad_points;         /* input rows off the curve (no table is made when > 0) */
+    uint64_t first_bad_point;    /* UINT64_MAX if none */
+    uint64_t infinity_rows;      /* OUTPUT rows that are the point at infinity (no table is made when > 0) */
+    uint64_t first_infinity_row; /* UINT64_MAX if none */
+} bbgpu_srs_lagrange_report;
+/* rows [0, n) of a registered / generated table -> a NEW resident table, row i = L_i; returns its handle >= 0 */
+int bbgpu_srs_lagrange(int srs_handle, size_t n, uint64_t* host_endo_table_out /* NULL: resident only */, bbgpu_srs_lagrange_report* out /* may be NULL */);
+/* the same over the even entries of a caller's 2n-entry endo table, on the host; writes all 2n entries of table_out (may alias points_endo_table).
+ * A row off the curve or an output row at infinity: the report, BBGPU_ERR_ARG and an untouched table_out. */
+int bbgpu_host_srs_lagrange(const uint64_t* points_endo_table, size_t n, uint64_t* table_out /* 2n entries, may alias */,
+                            bbgpu_srs_lagrange_report* out /* may be NULL */);
+
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
  * per-proof part is what :55-355 computes -- six Keccak transcripts (challenge.hpp), the Lagrange evaluations (polynomial_arithmetic.cpp:594-626),
