@@ -60,6 +60,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_plonk_check_witness_batch_from",
     "bbgpu_host_pairing", "bbgpu_host_pairing_check", "bbgpu_transcript_read_g2", "bbgpu_srs_check", "bbgpu_host_srs_check",
     "bbgpu_plonk_verifier_create", "bbgpu_plonk_verifier_destroy", "bbgpu_plonk_verify_batch", "bbgpu_host_plonk_verify_batch", "bbgpu_plonk_verify_last_timing",
+    "bbgpu_plonk_verify_multi", "bbgpu_host_plonk_verify_multi",
     "bbgpu_srs_update", "bbgpu_host_srs_update", "bbgpu_host_srs_update_check", "bbgpu_transcript_write_g2", "bbgpu_selftest_endo_split",
     "bbgpu_srs_lagrange", "bbgpu_host_srs_lagrange",
 ]
@@ -145,6 +146,11 @@ class PlonkVerifyReport(C.Structure):
         d.update(seed=[int(v) for v in self.seed], a=[int(v) for v in self.a], b=[int(v) for v in self.b], ok=bool(self.ok),
                  status=[int(v) for v in self.status] if self.status is not None else None)
         return d
+
+
+class PlonkVerifyKey(C.Structure):
+    """bbgpu_plonk_verify_key (include/bbgpu.h)"""
+    _fields_ = [("n", C.c_size_t), ("widgets", C.c_int), ("vk", C.c_void_p)]
 
 
 class PlonkWitness(C.Structure):
@@ -505,7 +511,7 @@ class BbGpu:
         return rep
 
     def plonk_verify_last_timing(self):
-        """bbgpu_plonk_verify_last_timing: wall ms of the last plonk_verify_batch by stage"""
+        """bbgpu_plonk_verify_last_timing: wall ms of the last plonk_verify_batch or plonk_verify_multi by stage"""
         buf = (C.c_double * 5)()
         self.lib.bbgpu_plonk_verify_last_timing.argtypes = [C.POINTER(C.c_double)]
         self._chk(self.lib.bbgpu_plonk_verify_last_timing(buf))
@@ -521,6 +527,44 @@ class BbGpu:
                                                            C.POINTER(PlonkVerifyReport)]
         self._chk(self.lib.bbgpu_host_plonk_verify_batch(int(n), int(widgets), _ptr(key), _ptr(g2), _ptr(proofs), proofs.shape[0], sdp,
                                                          1 if locate else 0, status.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rep)))
+        rep.status = status[:proofs.shape[0]]
+        return rep
+
+    @staticmethod
+    def _verify_labels(circuit):
+        labels = np.ascontiguousarray(circuit, dtype=np.uint32).reshape(-1)
+        return labels, labels.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def plonk_verify_multi(self, verifiers, circuit, proofs, seed=None, locate=False):
+        """bbgpu_plonk_verify_multi: proofs (count, 120) uint64 of SEVERAL circuits under one x * G2 in one batch; verifiers: the handles, circuit (count,):
+        proof j claims the circuit of verifiers[circuit[j]].  One pairing check for all.  Returns a PlonkVerifyReport."""
+        proofs, sd, sdp, status = self._verify_args(proofs, seed)
+        labels, lp = self._verify_labels(circuit)
+        if labels.shape[0] != proofs.shape[0]:
+            raise ValueError("plonk_verify_multi: %d labels for %d proofs" % (labels.shape[0], proofs.shape[0]))
+        hs = (C.c_int * max(1, len(verifiers)))(*[int(h) for h in verifiers])
+        rep = PlonkVerifyReport()
+        self.lib.bbgpu_plonk_verify_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_uint32), u64p, C.c_size_t, u64p, C.c_int,
+                                                      C.POINTER(C.c_uint32), C.POINTER(PlonkVerifyReport)]
+        self._chk(self.lib.bbgpu_plonk_verify_multi(hs, len(verifiers), lp, _ptr(proofs), proofs.shape[0], sdp, 1 if locate else 0,
+                                                    status.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rep)))
+        rep.status = status[:proofs.shape[0]]
+        return rep
+
+    def host_plonk_verify_multi(self, keys, g2_x, circuit, proofs, seed=None, locate=False):
+        """bbgpu_host_plonk_verify_multi: the same definition on the host; keys: one (n, widgets, vk) per circuit; no GPU needed"""
+        proofs, sd, sdp, status = self._verify_args(proofs, seed)
+        labels, lp = self._verify_labels(circuit)
+        if labels.shape[0] != proofs.shape[0]:
+            raise ValueError("host_plonk_verify_multi: %d labels for %d proofs" % (labels.shape[0], proofs.shape[0]))
+        vks = [np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1).copy() for _, _, vk in keys]
+        ks = (PlonkVerifyKey * max(1, len(keys)))(*[PlonkVerifyKey(int(n), int(w), v.ctypes.data) for (n, w, _), v in zip(keys, vks)])
+        g2 = np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16)
+        rep = PlonkVerifyReport()
+        self.lib.bbgpu_host_plonk_verify_multi.argtypes = [C.POINTER(PlonkVerifyKey), C.c_int, u64p, C.POINTER(C.c_uint32), u64p, C.c_size_t, u64p,
+                                                           C.c_int, C.POINTER(C.c_uint32), C.POINTER(PlonkVerifyReport)]
+        self._chk(self.lib.bbgpu_host_plonk_verify_multi(ks, len(keys), _ptr(g2), lp, _ptr(proofs), proofs.shape[0], sdp, 1 if locate else 0,
+                                                         status.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rep)))
         rep.status = status[:proofs.shape[0]]
         return rep
 

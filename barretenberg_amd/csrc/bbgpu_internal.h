@@ -141,6 +141,20 @@ struct VerifyDeviceBuffers {
 };
 int plonk_verify_terms(const VerifyDeviceKey& key, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B, hipStream_t st);
 int plonk_verify_fold(const uint64_t* d_shared, size_t count, size_t m, int num_shared, uint32_t skip_mask, uint64_t* d_out, hipStream_t st);
+// bbgpu_plonk_verify_multi: what a thread of k_verify_terms<true> and a workgroup of k_verify_fold_mixed read about one circuit of the call.  192 bytes
+// (a multiple of 64: the table sits in the staging buffer before the shared rows); the three constants 12 words apart, each read by three 16-byte loads
+struct VerifyRecord {
+    uint32_t log2n, widgets, num_vk;
+    uint32_t base;      // the circuit's first shared row among the rows (and scalars) of A
+    uint32_t skip_mask; // key points at infinity: their scalars are written as zero
+    uint32_t pad[7];
+    uint32_t root[12], root_inv[12], n_inv[12]; // Montgomery-261, 29-bit limbs in the first nine words
+};
+static_assert(sizeof(VerifyRecord) == 192, "VerifyRecord: 192 bytes");
+int plonk_verify_terms_mixed(const VerifyRecord* d_records, const uint32_t* d_circuit, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B,
+                             hipStream_t st);
+int plonk_verify_fold_mixed(const uint64_t* d_shared, const uint32_t* d_circuit, const VerifyRecord* d_records, int num_circuits, int max_shared, size_t count,
+                            size_t m, uint64_t* d_out, hipStream_t st);
 
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);

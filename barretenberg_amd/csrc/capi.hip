@@ -2086,6 +2086,51 @@ int bbgpu_host_plonk_verify_batch(size_t n, int widgets, const uint64_t* vk, con
     return host::verify_host(K, proofs, count, sd, flags, status, out);
 }
 
+// what bbgpu_plonk_verify_multi and its host twin refuse alike: `what` names the first argument ("verifiers" / "keys")
+static int verify_multi_args(const void* circuits, int num, const char* what, const uint32_t* circuit, const uint64_t* proofs, size_t count, int flags,
+                             const uint32_t* status, const bbgpu_plonk_verify_report* out)
+{
+    if (!circuits || !circuit) {
+        set_error("PLONK verify: null %s or circuit", what);
+        return BBGPU_ERR_ARG;
+    }
+    if (num < 1) {
+        set_error("PLONK verify: %d %s, at least one", num, what);
+        return BBGPU_ERR_ARG;
+    }
+    if (int rc = verify_args(proofs, count, flags, status, out)) return rc;
+    if (num > BBGPU_PLONK_VERIFY_MAX_CIRCUITS) {
+        set_error("PLONK verify: %d %s, at most %d per call", num, what, BBGPU_PLONK_VERIFY_MAX_CIRCUITS);
+        return BBGPU_ERR_SIZE;
+    }
+    for (size_t j = 0; j < count; j++)
+        if (circuit[j] >= (uint32_t)num) {
+            set_error("PLONK verify: circuit[%zu] = %u, but there are %d %s", j, circuit[j], num, what);
+            return BBGPU_ERR_ARG;
+        }
+    return BBGPU_OK;
+}
+
+int bbgpu_host_plonk_verify_multi(const bbgpu_plonk_verify_key* keys, int num_keys, const uint64_t g2_x[16], const uint32_t* circuit, const uint64_t* proofs,
+                                  size_t count, const uint64_t seed[4], int flags, uint32_t* status, bbgpu_plonk_verify_report* out)
+{
+    if (int rc = verify_multi_args(keys, num_keys, "keys", circuit, proofs, count, flags, status, out)) return rc;
+    std::vector<host::VerifyKey> K((size_t)num_keys);
+    for (int c = 0; c < num_keys; c++) {
+        const char* why = "";
+        if (int rc = host::verify_key_init(&K[c], keys[c].n, keys[c].widgets, keys[c].vk, g2_x, &why)) {
+            set_error("PLONK verify: key %d: %s", c, why);
+            return rc;
+        }
+    }
+    uint64_t sd[4];
+    if (!host::srs_check_seed(seed, sd)) {
+        set_error("PLONK verify: the operating system gave no randomness");
+        return BBGPU_ERR_STATE;
+    }
+    return host::verify_host_multi(K, g2_x, circuit, proofs, count, sd, flags, status, out);
+}
+
 /* ---- SRS ---- */
 int bbgpu_srs_register(const uint64_t* points_endo_table, size_t n)
 {
@@ -2804,6 +2849,27 @@ int bbgpu_plonk_verifier_destroy(int verifier)
     return BBGPU_OK;
 }
 
+// A and B: two tickets in flight over transient tables, the first ma and mb rows and scalars of each; on a failure none is outstanding
+static int verify_two_msms(const SrsEntry& ea, const SrsEntry& eb, uint64_t* d_scal_a, uint64_t* d_scal_b, size_t ma, size_t mb, uint64_t* a12, uint64_t* b12)
+{
+    int ta, tb;
+    hipStream_t sa, sb;
+    if (int rc = begin_ticket(nullptr, &ta, &sa)) return rc;
+    if (int rc = issue_ticket(ta, ea, 0, &d_scal_a, 1, ma, 0, entry_windows(ea, ma), sa)) return rc;
+    commit_ticket(ta);
+    int rc = begin_ticket(nullptr, &tb, &sb);
+    if (rc == BBGPU_OK && (rc = issue_ticket(tb, eb, 0, &d_scal_b, 1, mb, 0, entry_windows(eb, mb), sb)) == BBGPU_OK) commit_ticket(tb);
+    if (rc != BBGPU_OK) {
+        drain_tickets(&ta, 1);
+        return rc;
+    }
+    if (int rcw = bbgpu_msm_g1_wait(ta, a12)) {
+        drain_tickets(&tb, 1);
+        return rcw;
+    }
+    return bbgpu_msm_g1_wait(tb, b12);
+}
+
 int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count, const uint64_t seed[4], int flags, uint32_t* status,
                              bbgpu_plonk_verify_report* out)
 {
@@ -2866,28 +2932,131 @@ int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count,
         CHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
         const double t_msm = now_ms();
         g_verify_ms[2] += t_msm - t_fold;
-        const size_t ma = S + host::VERIFY_OWN * m, mb = 2 * m;
-        int ta, tb;
-        hipStream_t sa, sb;
-        if (int rc = begin_ticket(nullptr, &ta, &sa)) return rc;
-        if (int rc = issue_ticket(ta, ea, 0, &d_scal_a, 1, ma, 0, entry_windows(ea, ma), sa)) return rc;
-        commit_ticket(ta);
-        int rc = begin_ticket(nullptr, &tb, &sb);
-        if (rc == BBGPU_OK && (rc = issue_ticket(tb, eb, 0, &d_scal_b, 1, mb, 0, entry_windows(eb, mb), sb)) == BBGPU_OK) commit_ticket(tb);
-        if (rc != BBGPU_OK) {
-            drain_tickets(&ta, 1);
-            return rc;
-        }
-        if (int rcw = bbgpu_msm_g1_wait(ta, a12)) {
-            drain_tickets(&tb, 1);
-            return rcw;
-        }
-        const int rcb = bbgpu_msm_g1_wait(tb, b12);
+        if (int rc = verify_two_msms(ea, eb, d_scal_a, d_scal_b, S + host::VERIFY_OWN * m, 2 * m, a12, b12)) return rc;
         g_verify_ms[3] += now_ms() - t_msm;
-        return rcb;
+        return BBGPU_OK;
     });
     g_verify_ms[0] = now_ms() - t_begin;
     g_verify_ms[4] = g_verify_ms[0] - g_verify_ms[1] - g_verify_ms[2] - g_verify_ms[3]; // the pairing checks (and the normalisations around them)
+    return rc_tail;
+}
+
+int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint32_t* circuit, const uint64_t* proofs, size_t count, const uint64_t seed[4],
+                             int flags, uint32_t* status, bbgpu_plonk_verify_report* out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    if (int rc = verify_multi_args(verifiers, num_verifiers, "verifiers", circuit, proofs, count, flags, status, out)) return rc;
+    const size_t G = (size_t)num_verifiers;
+    const VerifierHandle* H[BBGPU_PLONK_VERIFY_MAX_CIRCUITS];
+    for (size_t c = 0; c < G; c++) {
+        const int v = verifiers[c];
+        if (v < 0 || v >= (int)g_verifiers.size() || !g_verifiers[v]) {
+            set_error("unknown verifier handle %d (verifiers[%zu])", v, c);
+            return BBGPU_ERR_ARG;
+        }
+        H[c] = g_verifiers[v];
+        if (memcmp(H[c]->K.g2_x, H[0]->K.g2_x, sizeof H[0]->K.g2_x) != 0) {
+            set_error("PLONK verify: verifiers[%zu] (handle %d) and verifiers[0] (handle %d) hold different g2_x: one call, one reference string", c, v,
+                      verifiers[0]);
+            return BBGPU_ERR_ARG;
+        }
+    }
+    if (int rc = ensure_init()) return rc;
+    const double t_begin = now_ms();
+    for (double& v : g_verify_ms) v = 0;
+    uint64_t sd[4];
+    if (!host::srs_check_seed(seed, sd)) {
+        set_error("PLONK verify: the operating system gave no randomness");
+        return BBGPU_ERR_STATE;
+    }
+    host::verify_report_init(out, count, sd);
+    // one staging buffer, every part a multiple of 64 bytes: the proofs | circuit[] | the records | rows of A: every circuit's shared rows, then nine
+    // per proof | rows of B: two per proof | scalars of A, of B | the shared terms [slot][proof] | the statuses.  circuit[], the records and the shared
+    // rows are neighbours there because they arrive in one copy.
+    size_t T = 0, S_max = 0; // shared rows in all, the most of one circuit
+    for (size_t c = 0; c < G; c++) {
+        T += (size_t)H[c]->K.num_shared();
+        S_max = std::max(S_max, (size_t)H[c]->K.num_shared());
+    }
+    const size_t na = T + host::VERIFY_OWN * count, nb = 2 * count;
+    auto up64 = [](size_t b) { return (b + 63) & ~(size_t)63; };
+    const size_t o_circuit = up64(count * BBGPU_PLONK_PROOF_WORDS * 8), o_records = o_circuit + up64(count * 4), o_rows_a = o_records + G * sizeof(VerifyRecord),
+                 o_rows_b = o_rows_a + na * 64, o_scal_a = o_rows_b + nb * 64, o_scal_b = o_scal_a + up64(na * 32), o_shared = o_scal_b + nb * 32,
+                 o_status = o_shared + up64(S_max * count * 32), total = o_status + up64(count * 4);
+    const size_t head_bytes = o_rows_a + T * 64 - o_circuit;
+    static_assert(BBGPU_PLONK_VERIFY_MAX_BATCH * 4 + BBGPU_PLONK_VERIFY_MAX_CIRCUITS * (sizeof(VerifyRecord) + host::VERIFY_MAX_SHARED * 64) <= Context::HOST_CHUNK,
+                  "circuit[], the records and the shared rows fit one pinned staging buffer");
+    if (int rc = grow(&ctx().d_verify, &ctx().verify_cap, total)) return rc;
+    uint8_t* base = reinterpret_cast<uint8_t*>(ctx().d_verify);
+    const uint32_t* d_circuit = reinterpret_cast<const uint32_t*>(base + o_circuit);
+    const VerifyRecord* d_records = reinterpret_cast<const VerifyRecord*>(base + o_records);
+    uint32_t *d_rows_a = reinterpret_cast<uint32_t*>(base + o_rows_a), *d_rows_b = reinterpret_cast<uint32_t*>(base + o_rows_b);
+    uint64_t *d_scal_a = reinterpret_cast<uint64_t*>(base + o_scal_a), *d_scal_b = reinterpret_cast<uint64_t*>(base + o_scal_b);
+    uint64_t* d_shared = reinterpret_cast<uint64_t*>(base + o_shared);
+    uint32_t* d_status = reinterpret_cast<uint32_t*>(base + o_status);
+    const hipStream_t st = ctx().stream;
+    if (int rc = host_to_device(base, proofs, count * BBGPU_PLONK_PROOF_WORDS * 8, st)) return rc;
+    {
+        // built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy
+        if (int rc = host_stage_ensure()) return rc;
+        const int kb = (int)(ctx().h_stage_next++ % Context::HOST_RING);
+        CHK(hipEventSynchronize(ctx().h_stage_free[kb]));
+        uint8_t* h = static_cast<uint8_t*>(ctx().h_stage[kb]);
+        memset(h, 0, o_rows_a - o_circuit);
+        memcpy(h, circuit, count * 4);
+        VerifyRecord* rec = reinterpret_cast<VerifyRecord*>(h + (o_records - o_circuit));
+        uint8_t* rows = h + (o_rows_a - o_circuit);
+        size_t at = 0;
+        for (size_t c = 0; c < G; c++) {
+            const VerifyDeviceKey& D = H[c]->D;
+            rec[c].log2n = D.log2n;
+            rec[c].widgets = D.widgets;
+            rec[c].num_vk = D.num_vk;
+            rec[c].base = (uint32_t)at;
+            rec[c].skip_mask = H[c]->skip_mask;
+            for (int i = 0; i < NL; i++) {
+                rec[c].root[i] = D.root[i];
+                rec[c].root_inv[i] = D.root_inv[i];
+                rec[c].n_inv[i] = D.n_inv[i];
+            }
+            memcpy(rows + at * 64, H[c]->shared_rows, (size_t)H[c]->K.num_shared() * 64);
+            at += (size_t)H[c]->K.num_shared();
+        }
+        CHK(h2d_async(base + o_circuit, h, head_bytes, st));
+        CHK(hipEventRecord(ctx().h_stage_free[kb], st));
+    }
+    VerifyDeviceBuffers B;
+    B.proofs = reinterpret_cast<const uint64_t*>(base);
+    B.rows_own = d_rows_a + T * 16;
+    B.rows_other = d_rows_b;
+    B.scal_own = d_scal_a + T * 4;
+    B.scal_other = d_scal_b;
+    B.shared = d_shared;
+    B.status = d_status;
+    if (int rc = plonk_verify_terms_mixed(d_records, d_circuit, sd, count, B, st)) return rc;
+    CHK(d2h_async(status, d_status, count * 4, st));
+    CHK(hipStreamSynchronize(st));
+    g_verify_ms[1] = now_ms() - t_begin;
+    host::verify_count_status(out, status);
+    SrsEntry ea{}, eb{};
+    ea.n = na;
+    ea.d_srs = d_rows_a;
+    eb.n = nb;
+    eb.d_srs = d_rows_b;
+    ea.live = eb.live = true;
+    const int rc_tail = host::verify_tail(out, H[0]->K.g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
+        const double t_fold = now_ms();
+        if (int rc = plonk_verify_fold_mixed(d_shared, d_circuit, d_records, (int)G, (int)S_max, count, m, d_scal_a, st)) return rc;
+        CHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
+        const double t_msm = now_ms();
+        g_verify_ms[2] += t_msm - t_fold;
+        if (int rc = verify_two_msms(ea, eb, d_scal_a, d_scal_b, T + host::VERIFY_OWN * m, 2 * m, a12, b12)) return rc;
+        g_verify_ms[3] += now_ms() - t_msm;
+        return BBGPU_OK;
+    });
+    g_verify_ms[0] = now_ms() - t_begin;
+    g_verify_ms[4] = g_verify_ms[0] - g_verify_ms[1] - g_verify_ms[2] - g_verify_ms[3];
     return rc_tail;
 }
 

@@ -1,8 +1,10 @@
-// plonk_verify.hip -- the two device parts of bbgpu_plonk_verify_batch (include/bbgpu.h) that are not an MSM: the per-proof work of
+// plonk_verify.hip -- the two device parts of bbgpu_plonk_verify_batch and bbgpu_plonk_verify_multi (include/bbgpu.h) that are not an MSM: the per-proof work of
 // waffle::Verifier::verify_proof (verifier.cpp:55-355) and the sums over the batch of the scalars on the shared points.  The definition both follow is
 // host_plonk_verify.hpp's verify_terms (the host twin; the comments there name the reference's lines); the sums A and B are the existing device MSM
 // over the rows and scalars written here (capi.hip), the pairing is host code (host_pairing.hpp).
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "bbgpu_internal.h"
 #include "g1.hpp"
@@ -139,8 +141,23 @@ struct VerifyKernelArgs {
     Limbs9 root, root_inv, n_inv; // Montgomery-261
     Seed seed;
 };
+// bbgpu_plonk_verify_multi: proof j is of circuit[j], whose constants a thread reads from records[circuit[j]] (bbgpu_internal.h); shared is
+// [slot < max over the circuits of num_vk + 1][proof], a proof fills the slots of its own circuit
+struct VerifyMixedArgs {
+    const uint64_t* proofs;
+    uint32_t *rows_own, *rows_other;
+    uint64_t *scal_own, *scal_other, *shared;
+    uint32_t* status;
+    const VerifyRecord* records; // one per circuit of the call
+    const uint32_t* circuit;     // count
+    uint32_t count;
+    Seed seed;
+};
 
-__global__ void __launch_bounds__(VT) k_verify_terms(VerifyKernelArgs P)
+// MIXED false: n, the widget set and the key's size are the launch's (kernel arguments: every branch on them is uniform).  MIXED true: they are the
+// thread's own, read from its circuit's record where they are needed, so that the z^n loop and the widget branches diverge inside a wave that holds
+// proofs of several circuits; the arithmetic is the same text.
+template <bool MIXED> __global__ void __launch_bounds__(VT) k_verify_terms(typename std::conditional<MIXED, VerifyMixedArgs, VerifyKernelArgs>::type P)
 {
     __shared__ uint64_t s_msg[MSG_LANES * VT];
     const uint32_t j = blockIdx.x * VT + threadIdx.x;
@@ -218,7 +235,29 @@ __global__ void __launch_bounds__(VT) k_verify_terms(VerifyKernelArgs P)
         qmc = load(11, -1);
     }
     P.status[j] = status;
-    const uint32_t S = P.num_vk + 1;
+    const VerifyRecord* rec = nullptr;
+    if constexpr (MIXED) rec = P.records + P.circuit[j];
+    uint32_t S, log2n, widgets;
+    if constexpr (MIXED) {
+        S = rec->num_vk + 1;
+        log2n = rec->log2n;
+        widgets = rec->widgets;
+    } else {
+        S = P.num_vk + 1;
+        log2n = P.log2n;
+        widgets = P.widgets;
+    }
+    // omega, omega^-1, 1 / n: which = 0, 1, 2
+    auto domain = [&](int which) -> F2 {
+        if constexpr (MIXED) {
+            const uint4* q = reinterpret_cast<const uint4*>(rec->root) + 3 * which; // 12 words per constant, 16-byte aligned (VerifyRecord)
+            const uint4 a = q[0], b = q[1], c = q[2];
+            const uint32_t d[NL] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x };
+            return fe_from<FrP>(d);
+        } else {
+            return fe_from<FrP>(which == 0 ? P.root.d : which == 1 ? P.root_inv.d : P.n_inv.d);
+        }
+    };
     if (status) { // zeros on finite stand-in rows: nothing of this proof enters a sum
         const uint32_t zero8[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
 #pragma unroll 1
@@ -238,7 +277,6 @@ __global__ void __launch_bounds__(VT) k_verify_terms(VerifyKernelArgs P)
 
     // ---- challenges, field values (host_plonk_verify.hpp verify_terms, line for line) ----------------------------------------------------------------
     const F2 one = fe_one<FrP>();
-    const F2 root = fe_from<FrP>(P.root.d), root_inv = fe_from<FrP>(P.root_inv.d), n_inv = fe_from<FrP>(P.n_inv.d);
     const F2 gamma = challenge<24>(msg);
     put_fr(msg, 6, gamma);
     const F2 beta = challenge<28>(msg);
@@ -253,15 +291,16 @@ __global__ void __launch_bounds__(VT) k_verify_terms(VerifyKernelArgs P)
     const F2 z = challenge<56>(msg);
 
     F2 z_n = z;
-    for (uint32_t i = 0; i < P.log2n; i++) z_n = sqr(z_n);
+    for (uint32_t i = 0; i < log2n; i++) z_n = sqr(z_n);
+    const F2 root = domain(0);
     const auto num = wsub(z_n, one), d1 = wsub(z, one), d2 = wsub(mul(mul(z, root), root), one);
     const F2 d12 = mul(d1, d2);
     const uint64_t r_minus_2[4] = { FrP::P64[0] - 2, FrP::P64[1], FrP::P64[2], FrP::P64[3] };
     const F2 inv = pow_u256<FrP>(F2(mul(d12, num)), r_minus_2);
     const F2 inv_d1 = mul(inv, mul(d2, num)), inv_d2 = mul(inv, mul(d1, num)), inv_num = mul(inv, d12);
-    const F2 num_n = mul(num, n_inv);
+    const F2 num_n = mul(num, domain(2));
     const F2 l_1 = mul(num_n, inv_d1), l_nm1 = mul(num_n, inv_d2);
-    const F2 inv_vanishing = mul(wsub(z, root_inv), inv_num);
+    const F2 inv_vanishing = mul(wsub(z, domain(1)), inv_num);
 
     const F2 a2 = sqr(alpha), a3 = mul(a2, alpha), a4 = sqr(a2), a5 = mul(a4, alpha);
     const F2 zb = mul(z, beta);
@@ -280,10 +319,10 @@ __global__ void __launch_bounds__(VT) k_verify_terms(VerifyKernelArgs P)
 
     const F2 nu2 = sqr(nu), nu3 = mul(nu2, nu), nu4 = sqr(nu2), nu5 = mul(nu4, nu), nu6 = mul(nu5, nu), nu7 = mul(nu6, nu), nu8 = sqr(nu4), nu9 = mul(nu8, nu);
     const F2 nu7u = mul(nu7, u);
-    const bool seq = (P.widgets & BBGPU_PLONK_WIDGET_SEQUENTIAL) != 0, has_bool = (P.widgets & BBGPU_PLONK_WIDGET_BOOL) != 0,
-               mimc = (P.widgets & BBGPU_PLONK_WIDGET_MIMC) != 0, wo_shifted = seq || mimc;
+    const bool seq = (widgets & BBGPU_PLONK_WIDGET_SEQUENTIAL) != 0, has_bool = (widgets & BBGPU_PLONK_WIDGET_BOOL) != 0,
+               mimc = (widgets & BBGPU_PLONK_WIDGET_MIMC) != 0, wo_shifted = seq || mimc;
     const F2 zero = fe_zero<FrP>();
-    // batch_evaluation: a widget's term is computed whatever the widget set (the set is uniform over the launch) and zeroed when it is absent
+    // batch_evaluation: a widget's term is computed whatever the widget set (uniform over the launch, or the thread's own) and zeroed when it is absent
     const F2 b_shift = sel(wo_shifted, mul(mul(wo_sh, nu8), u), zero);
     const F2 b_mimc = sel(mimc, mul(qmc, sel(wo_shifted, nu9, nu8)), zero);
     const auto batch = wadd(wadd(wadd(wadd(wadd(wadd(wadd(wadd(wadd(t_eval, mul(nu, lin)), mul(nu2, wl)), mul(nu3, wr)), mul(nu4, wo)), mul(nu5, s1)),
@@ -310,7 +349,7 @@ __global__ void __launch_bounds__(VT) k_verify_terms(VerifyKernelArgs P)
     put_scalar(so + 4 * 5, z_n, rho, inf(5));
     put_scalar(so + 4 * 6, sqr(z_n), rho, inf(6));
     put_scalar(so + 4 * 7, z, rho, false);
-    put_scalar(so + 4 * 8, mul(mul(z, root), u), rho, inf(8));
+    put_scalar(so + 4 * 8, mul(mul(z, domain(0)), u), rho, inf(8));
     put_scalar(P.scal_other + ((size_t)j * 2 + 0) * 4, u, rho, inf(8));
     put_scalar(P.scal_other + ((size_t)j * 2 + 1) * 4, one, rho, false);
     auto shared_at = [&](uint32_t k) { return P.shared + ((size_t)k * P.count + j) * 4; };
@@ -364,17 +403,9 @@ __device__ __forceinline__ void fr_add_canonical(uint64_t (&a)[4], const uint64_
 #pragma unroll
     for (int i = 0; i < 4; i++) a[i] = borrow ? s[i] : d[i];
 }
-__global__ void __launch_bounds__(FT) k_verify_fold(const uint64_t* __restrict__ shared, uint32_t count, uint32_t m, uint32_t skip_mask, uint64_t* __restrict__ out)
+// the 256 partial sums of a workgroup into one, by a fixed tree; thread 0 writes it (zero for a key point at infinity: its row is a stand-in)
+__device__ __forceinline__ void fold_finish(uint64_t (&s_acc)[FT][4], const uint64_t (&acc)[4], bool skip, uint64_t* __restrict__ dst)
 {
-    __shared__ uint64_t s_acc[FT][4];
-    const uint32_t k = blockIdx.x;
-    uint64_t acc[4] = { 0, 0, 0, 0 };
-    for (uint32_t j = threadIdx.x; j < m; j += FT) {
-        const ulonglong2* q = reinterpret_cast<const ulonglong2*>(shared + ((size_t)k * count + j) * 4);
-        const ulonglong2 lo = q[0], hi = q[1];
-        const uint64_t v[4] = { lo.x, lo.y, hi.x, hi.y };
-        fr_add_canonical(acc, v);
-    }
 #pragma unroll
     for (int i = 0; i < 4; i++) s_acc[threadIdx.x][i] = acc[i];
     __syncthreads();
@@ -390,10 +421,41 @@ __global__ void __launch_bounds__(FT) k_verify_fold(const uint64_t* __restrict__
         __syncthreads();
     }
     if (threadIdx.x != 0) return;
-    const bool skip = ((skip_mask >> k) & 1u) != 0; // a key point at infinity: its row is a stand-in
-    ulonglong2* o2 = reinterpret_cast<ulonglong2*>(out + 4 * (size_t)k);
+    ulonglong2* o2 = reinterpret_cast<ulonglong2*>(dst);
     o2[0] = make_ulonglong2(skip ? 0 : s_acc[0][0], skip ? 0 : s_acc[0][1]);
     o2[1] = make_ulonglong2(skip ? 0 : s_acc[0][2], skip ? 0 : s_acc[0][3]);
+}
+__global__ void __launch_bounds__(FT) k_verify_fold(const uint64_t* __restrict__ shared, uint32_t count, uint32_t m, uint32_t skip_mask, uint64_t* __restrict__ out)
+{
+    __shared__ uint64_t s_acc[FT][4];
+    const uint32_t k = blockIdx.x;
+    uint64_t acc[4] = { 0, 0, 0, 0 };
+    for (uint32_t j = threadIdx.x; j < m; j += FT) {
+        const ulonglong2* q = reinterpret_cast<const ulonglong2*>(shared + ((size_t)k * count + j) * 4);
+        const ulonglong2 lo = q[0], hi = q[1];
+        const uint64_t v[4] = { lo.x, lo.y, hi.x, hi.y };
+        fr_add_canonical(acc, v);
+    }
+    fold_finish(s_acc, acc, ((skip_mask >> k) & 1u) != 0, out + 4 * (size_t)k);
+}
+// bbgpu_plonk_verify_multi: workgroup (k, c) sums slot k over the proofs j < m labelled c into the scalar of circuit c's k-th shared row; a proof of
+// another circuit costs its 4-byte label, not the 32-byte term.  The additions are exact: which threads met a circuit's proofs shows in no result.
+__global__ void __launch_bounds__(FT) k_verify_fold_mixed(const uint64_t* __restrict__ shared, const uint32_t* __restrict__ circuit,
+                                                          const VerifyRecord* __restrict__ records, uint32_t count, uint32_t m, uint64_t* __restrict__ out)
+{
+    __shared__ uint64_t s_acc[FT][4];
+    const uint32_t k = blockIdx.x, c = blockIdx.y;
+    const uint32_t num_vk = records[c].num_vk, base = records[c].base, skip_mask = records[c].skip_mask;
+    if (k > num_vk) return; // the whole workgroup: circuit c has no such slot
+    uint64_t acc[4] = { 0, 0, 0, 0 };
+    for (uint32_t j = threadIdx.x; j < m; j += FT) {
+        if (circuit[j] != c) continue;
+        const ulonglong2* q = reinterpret_cast<const ulonglong2*>(shared + ((size_t)k * count + j) * 4);
+        const ulonglong2 lo = q[0], hi = q[1];
+        const uint64_t v[4] = { lo.x, lo.y, hi.x, hi.y };
+        fr_add_canonical(acc, v);
+    }
+    fold_finish(s_acc, acc, ((skip_mask >> k) & 1u) != 0, out + 4 * (size_t)(base + k));
 }
 
 } // namespace
@@ -418,7 +480,28 @@ int plonk_verify_terms(const VerifyDeviceKey& key, const uint64_t seed[4], size_
         P.n_inv.d[i] = key.n_inv[i];
     }
     for (int k = 0; k < 4; k++) P.seed.d[k] = seed[k];
-    k_verify_terms<<<(uint32_t)((count + VT - 1) / VT), VT, 0, st>>>(P);
+    k_verify_terms<false><<<(uint32_t)((count + VT - 1) / VT), VT, 0, st>>>(P);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+
+// the same for proofs of several circuits: d_records[d_circuit[j]] is proof j's circuit
+int plonk_verify_terms_mixed(const VerifyRecord* d_records, const uint32_t* d_circuit, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B,
+                             hipStream_t st)
+{
+    VerifyMixedArgs P;
+    P.proofs = B.proofs;
+    P.rows_own = B.rows_own;
+    P.rows_other = B.rows_other;
+    P.scal_own = B.scal_own;
+    P.scal_other = B.scal_other;
+    P.shared = B.shared;
+    P.status = B.status;
+    P.records = d_records;
+    P.circuit = d_circuit;
+    P.count = (uint32_t)count;
+    for (int k = 0; k < 4; k++) P.seed.d[k] = seed[k];
+    k_verify_terms<true><<<(uint32_t)((count + VT - 1) / VT), VT, 0, st>>>(P);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
@@ -427,6 +510,15 @@ int plonk_verify_terms(const VerifyDeviceKey& key, const uint64_t seed[4], size_
 int plonk_verify_fold(const uint64_t* d_shared, size_t count, size_t m, int num_shared, uint32_t skip_mask, uint64_t* d_out, hipStream_t st)
 {
     k_verify_fold<<<(uint32_t)num_shared, FT, 0, st>>>(d_shared, (uint32_t)count, (uint32_t)m, skip_mask, d_out);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+
+// d_out[records[c].base + k] for every circuit c < num_circuits and every slot k of it (max_shared: the largest num_vk + 1 among them)
+int plonk_verify_fold_mixed(const uint64_t* d_shared, const uint32_t* d_circuit, const VerifyRecord* d_records, int num_circuits, int max_shared, size_t count,
+                            size_t m, uint64_t* d_out, hipStream_t st)
+{
+    k_verify_fold_mixed<<<dim3((uint32_t)max_shared, (uint32_t)num_circuits), FT, 0, st>>>(d_shared, d_circuit, d_records, (uint32_t)count, (uint32_t)m, d_out);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }

@@ -741,6 +741,15 @@ class Verifier:
             return self.gpu.host_plonk_verify_batch(self.n, self.widgets, self.vk, self.g2_x, proofs, seed, locate)
         return self.gpu.plonk_verify_batch(self.handle, proofs, seed, locate)
 
+    @staticmethod
+    def verify_mixed(verifiers, circuit, proofs, seed=None, locate=False, host=False):
+        """a queue of proofs of several circuits in one call (bbgpu_plonk_verify_multi): proof j claims the circuit of verifiers[circuit[j]]; the
+        Verifiers share one g2_x.  One pairing check for all; host=True runs bbgpu_host_plonk_verify_multi (no GPU needed)"""
+        gpu = verifiers[0].gpu
+        if host:
+            return gpu.host_plonk_verify_multi([(v.n, v.widgets, v.vk) for v in verifiers], verifiers[0].g2_x, circuit, proofs, seed, locate)
+        return gpu.plonk_verify_multi([v.handle for v in verifiers], circuit, proofs, seed, locate)
+
     def destroy(self):
         if self.handle is not None:
             self.gpu.plonk_verifier_destroy(self.handle)

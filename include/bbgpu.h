@@ -712,13 +712,47 @@ int bbgpu_plonk_verifier_destroy(int verifier);
 int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count, const uint64_t seed[4] /* NULL: OS randomness */, int flags,
                              uint32_t* status /* count */, bbgpu_plonk_verify_report* out);
 /* DIAGNOSTIC (tools/plonk_verify_bench.py; not part of the verdict, one set of figures per process, overwritten by every call, zeros before the first):
- * wall ms of the last bbgpu_plonk_verify_batch, taken between the synchronisations the call makes anyway: total; upload, k_verify_terms and the read-back
+ * wall ms of the last bbgpu_plonk_verify_batch or bbgpu_plonk_verify_multi, taken between the synchronisations the call makes anyway: total; upload, k_verify_terms and the read-back
  * of the statuses; k_verify_fold; the two MSMs; the host tail (pairing check, normalisations) -- with LOCATE summed over the rounds */
 int bbgpu_plonk_verify_last_timing(double ms_out[5]);
 /* the same definition on the host (csrc/host_plonk_verify.hpp), for a caller without a GPU or with one proof; no HIP call, no lock.  vk: as many points
  * as the widget set has (8 to 12) */
 int bbgpu_host_plonk_verify_batch(size_t n, int widgets, const uint64_t* vk, const uint64_t g2_x[16], const uint64_t* proofs, size_t count,
                                   const uint64_t seed[4], int flags, uint32_t* status, bbgpu_plonk_verify_report* out);
+/* PROOFS OF SEVERAL CIRCUITS IN ONE BATCH.  The fold is linear in the points and every circuit of one reference string meets the same x G2, so the
+ * proofs of all circuits go into the same two sums and one product of two pairings.  Given verifier handles v_0 .. v_{G-1},
+ * 1 <= G <= BBGPU_PLONK_VERIFY_MAX_CIRCUITS, `count` proofs in the caller's order and circuit[j] < G naming the handle whose circuit proof j claims:
+ *   status[j]   as above: it depends on the proof alone
+ *   rho_j     = Keccak-256(seed || j), top three bits cleared             j: the position in the caller's array
+ *   A = sum_j rho_j (own scalars . own nine points of proof j, computed with n, root and widgets of circuit[j])
+ *     + sum_c sum_k (sum over the j with circuit[j] = c of rho_j s_jk) V_{c,k}                  V_{c,.}: key c's points, then the generator
+ *   B = sum_j rho_j (u_j PI_Z_OMEGA_j + PI_Z_j)
+ *   pairing_ok = (e(A, G2) e(-B, x G2) == 1)
+ * over the proofs with status 0; a key point at infinity has its scalar zeroed, per circuit.  A proof under the wrong label is a bad proof: it has
+ * status 0 and fails the pairing.  BBGPU_PLONK_VERIFY_LOCATE bisects the prefix length over the caller's order exactly as above (prefix m passes iff every
+ * proof below m verifies under its own label); the report is the same struct.  With G = 1 the definition IS bbgpu_plonk_verify_batch's and the report
+ * equals that entry's field for field, a and b included.  The same handle may appear more than once in `verifiers`: legal, the same verdict (the sums
+ * over a circuit's proofs are exact, how they are split shows in no result).
+ * Refused before a device is bound -- BBGPU_ERR_ARG: a null pointer, num_verifiers < 1, an unknown handle, a circuit[j] >= num_verifiers (the error text
+ * names j), handles whose g2_x differ (compared on the words the handle stores), an unknown flag, count < 1; BBGPU_ERR_SIZE: num_verifiers >
+ * BBGPU_PLONK_VERIFY_MAX_CIRCUITS, count > BBGPU_PLONK_VERIFY_MAX_BATCH.
+ * On the device each thread of k_verify_terms reads n, the widget set and the domain's constants from its circuit's record (a table of G records the call
+ * uploads together with circuit[] and the shared rows, in one copy), k_verify_fold_mixed sums slot k of circuit c in workgroup (k, c); a warm call passes
+ * as many allocation / upload / read-back / launch checks and synchronises as often as bbgpu_plonk_verify_batch at the same count, whatever G.
+ * bbgpu_plonk_verify_last_timing reports the last call of either GPU entry.  Cost: tools/plonk_verify_multi_bench.py, profiles/plonk_verify_multi.txt. */
+#define BBGPU_PLONK_VERIFY_MAX_CIRCUITS 64
+int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint32_t* circuit /* count */, const uint64_t* proofs, size_t count,
+                             const uint64_t seed[4] /* NULL: OS randomness */, int flags, uint32_t* status /* count */, bbgpu_plonk_verify_report* out);
+/* the same on the host (csrc/host_plonk_verify.hpp): one key per circuit (n, widget set, vk of as many points as the set has), all under one g2_x;
+ * for one seed the report equals bbgpu_plonk_verify_multi's field for field */
+typedef struct {
+    size_t n;
+    int widgets;
+    const uint64_t* vk;
+} bbgpu_plonk_verify_key;
+int bbgpu_host_plonk_verify_multi(const bbgpu_plonk_verify_key* keys, int num_keys, const uint64_t g2_x[16], const uint32_t* circuit /* count */,
+                                  const uint64_t* proofs, size_t count, const uint64_t seed[4], int flags, uint32_t* status,
+                                  bbgpu_plonk_verify_report* out);
 
 /* ---- device self-test: known-answer entry points for the field and group layer ------------------------------------
  * One GPU lane per case runs the device arithmetic every kernel is built from (csrc/fe.hpp incl. the gfx950 asm products, csrc/g1.hpp);
