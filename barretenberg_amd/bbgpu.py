@@ -63,6 +63,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_plonk_verify_multi", "bbgpu_host_plonk_verify_multi",
     "bbgpu_srs_update", "bbgpu_host_srs_update", "bbgpu_host_srs_update_check", "bbgpu_transcript_write_g2", "bbgpu_selftest_endo_split",
     "bbgpu_srs_lagrange", "bbgpu_host_srs_lagrange",
+    "bbgpu_selftest_plonk_round",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -781,6 +782,43 @@ class BbGpu:
         self.lib.bbgpu_selftest_g1.argtypes = [C.c_int, u64p, u64p, C.c_size_t, u64p]
         self._chk(self.lib.bbgpu_selftest_g1(self.SELFTEST_G1_OPS[op], _ptr(p), _ptr(q), p.shape[0], _ptr(out)))
         return out
+
+    # ---- one round kernel of the PLONK prover on its own (bbgpu_selftest_plonk_round) --------------------------------------------------
+    SELFTEST_PLONK_KERNELS = {"z_terms": 0, "quot_large": 1, "quot_mid": 2, "quot_seq": 3, "quot_bool": 4, "quot_mimc": 5, "lincomb": 6, "mul2c": 7,
+                              "sigma_prepare": 8, "copy_pad": 9, "add_inplace": 10, "divide_vanishing": 11, "scan": 12, "evaluate": 13}
+
+    @staticmethod
+    def _plonk_round_out_lens(kernel, length, params):
+        """per-lane length of every output of bbgpu_selftest_plonk_round (the `out` column of its table in include/bbgpu.h)"""
+        if kernel == "z_terms":
+            return [length, length]
+        if kernel in ("sigma_prepare", "copy_pad", "add_inplace"):
+            return [int(params[0])]
+        if kernel == "divide_vanishing":
+            return [int(params[1])]
+        if kernel == "scan":
+            return [length] * bool(int(params[1]) & 4) + [1] * bool(int(params[1]) & 8)
+        return [1] if kernel == "evaluate" else [length]
+
+    def selftest_plonk_round(self, kernel, lanes, length, inputs, consts=None, params=()):
+        """kernel: a name of SELFTEST_PLONK_KERNELS; inputs: lane-major (lanes * per-lane length, 4) uint64 arrays in the order of the table in
+        include/bbgpu.h; consts: (k, 4) canonical Montgomery values, lane-major; params: the kernel's integers -> list of (lanes * per-lane length, 4)
+        arrays, canonical.  What the kernel does not support raises BbGpuError (-3)."""
+        try:
+            out_lens = self._plonk_round_out_lens(kernel, int(length), params)
+        except (IndexError, TypeError):
+            out_lens = [int(length)]  # too few parameters: the entry refuses the call
+        ins = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4) for a in inputs]
+        cs = np.ascontiguousarray(consts if consts is not None else np.zeros((0, 4)), dtype=np.uint64).reshape(-1, 4)
+        outs = [np.zeros((max(0, int(lanes) * int(n)), 4), dtype=np.uint64) for n in out_lens]
+        pr = (C.c_uint32 * max(1, len(params)))(*[int(v) for v in params])
+        inp = (u64p * max(1, len(ins)))(*[_ptr(a) for a in ins])
+        outp = (u64p * max(1, len(outs)))(*[_ptr(a) for a in outs])
+        self.lib.bbgpu_selftest_plonk_round.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_uint32), C.c_int, C.POINTER(u64p), C.c_int, u64p,
+                                                        C.c_size_t, C.POINTER(u64p), C.c_int]
+        self._chk(self.lib.bbgpu_selftest_plonk_round(self.SELFTEST_PLONK_KERNELS.get(kernel, -1), int(lanes), int(length), pr, len(params), inp, len(ins),
+                                                      _ptr(cs) if cs.shape[0] else None, cs.shape[0], outp, len(outs)))
+        return outs
 
     # ---- instrumentation ---------------------------------------------------------------------------------------------
     def set_timing(self, on=True):

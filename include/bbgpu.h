@@ -812,6 +812,52 @@ int bbgpu_selftest_g1(int op, const uint64_t* p, const uint64_t* q, size_t n, ui
  * magnitude does not fit 128 bits (never).  Where both signs are positive the magnitudes are host_wnaf.hpp's split (tests/golden/endo_wnaf.json). */
 int bbgpu_selftest_endo_split(int on_device, const uint64_t* k, size_t n, uint64_t* out);
 
+/* One round kernel of the PLONK prover (csrc/poly.hip) on its own, through the host function the prover itself calls (poly.h: *_lanes, scan_lanes,
+ * evaluate_lanes) with a lane table of the entry's own: records, challenge-dependent constants and grids are made by the product's code.  Host pointers
+ * in and out; the entry allocates, uploads, synchronises, downloads and frees.  Every vector is LANE-MAJOR: lane l's elements follow lane l - 1's, 4 limbs
+ * each, in the reference's memory format (any value below 2^256 is a legal input; outputs are canonical).  `len` is the kernel's own length; the per-lane
+ * length of each vector is given below in units of len.  consts: Fr values in memory form, CANONICAL (the prover's challenges are), `lanes` x k of them
+ * (lane-major) unless stated.  Fresh outputs are preset to all-ones, so an element a kernel leaves out cannot pass for a field value.
+ *   kernel             len   params                          in (per-lane length)                                   consts per lane        out
+ *   Z_TERMS            n     -                               w_l w_r w_o s1 s2 s3 (n)                               beta gamma             num den (n)
+ *   QUOT_LARGE         4n    -                               wl wr wo s1 s2 s3 zf (len)                             beta gamma             q (len)
+ *   QUOT_MID           2n    -                               zf wl wr wo (2 len), l1 qm ql qr qo qc (len)           alpha alpha_base       q (len)
+ *   QUOT_SEQ           2n    -                               wo (2 len), q_o_next (len), q (len)                    c                      q (len)
+ *   QUOT_BOOL          2n    -                               wl wr wo (2 len), q_bl q_br q_bo (len), q (len)        c_l c_r c_o            q (len)
+ *   QUOT_MIMC          4n    -                               wl wr wo q_sel q_coef q (len)                          alpha_base alpha_step  q (len)
+ *   LINCOMB            n     count (1..12), has_addend       p_0 .. p_(count-1) [addend] (len)                      c_0 .. c_(count-1)     out (len)
+ *   MUL2C              n     -                               a b (len)                                              c                      out (len)
+ *   SIGMA_PREPARE      n     n_dst (>= len)                  sigma w (len)                                          gamma                  dst (n_dst)
+ *   COPY_PAD           n_src n_dst (>= len), scaled          src (len)                                              c if scaled, else none dst (n_dst)
+ *   ADD_INPLACE        n     stride_a, stride_b (>= len)     a (stride_a), b (stride_b)                             -                      a (stride_a)
+ *   DIVIDE_VANISHING   N     log2(N / n) (0..2), stride >= N c (stride)                                             -                      c (stride)
+ *   SCAN               n     mode (0 products, 1 Horner),    in (len); `lanes` is the number of jobs                z (mode 1 only)        [out (len)] [total (1)]
+ *                            flags: 1 reverse, 2 inclusive,
+ *                            4 an output vector, 8 a total
+ *   EVALUATE           n     nz (1..16), zidx[0..lanes)      coefficients (len); `lanes` is the number of jobs      nz points IN ALL       result (1)
+ * BBGPU_ERR_ARG, before a device is touched: an unknown kernel, lanes outside 1..16, len 0 or lanes x (the longest vector) above 2^22, a length that is
+ * no power of two where the kernel masks indices or takes a root of unity (Z_TERMS, the QUOT_* kernels, DIVIDE_VANISHING), a wrong number of vectors,
+ * parameters or constants, a null pointer, a constant that is not below r, a parameter outside the range above (a destination or stride shorter than len,
+ * a zidx outside nz, a SCAN that asks for neither output).  All lanes of a call have one length: the kernels take their grid from lane 0. */
+enum {
+    BBGPU_SELFTEST_PLONK_Z_TERMS = 0,
+    BBGPU_SELFTEST_PLONK_QUOT_LARGE = 1,
+    BBGPU_SELFTEST_PLONK_QUOT_MID = 2,
+    BBGPU_SELFTEST_PLONK_QUOT_SEQ = 3,
+    BBGPU_SELFTEST_PLONK_QUOT_BOOL = 4,
+    BBGPU_SELFTEST_PLONK_QUOT_MIMC = 5,
+    BBGPU_SELFTEST_PLONK_LINCOMB = 6,
+    BBGPU_SELFTEST_PLONK_MUL2C = 7,
+    BBGPU_SELFTEST_PLONK_SIGMA_PREPARE = 8,
+    BBGPU_SELFTEST_PLONK_COPY_PAD = 9,
+    BBGPU_SELFTEST_PLONK_ADD_INPLACE = 10,
+    BBGPU_SELFTEST_PLONK_DIVIDE_VANISHING = 11,
+    BBGPU_SELFTEST_PLONK_SCAN = 12,
+    BBGPU_SELFTEST_PLONK_EVALUATE = 13
+};
+int bbgpu_selftest_plonk_round(int kernel, int lanes, size_t len, const uint32_t* params, int num_params, const uint64_t* const* in, int num_in,
+                               const uint64_t* consts, size_t num_consts, uint64_t* const* out, int num_out);
+
 /* ---- instrumentation (bench.py) ---------------------------------------------------------------------------------
  * Device time in milliseconds of the kernels launched by the most recent bbgpu_*_device call on this thread, measured
  * with hipEvents on the stream the kernels ran on.  index: 0 = total, then per stage: 1 digits, 2 sort, 3 accumulation,

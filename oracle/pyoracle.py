@@ -412,15 +412,13 @@ class PolyOracle:
 
     @classmethod
     def plain(cls, a):
-        a = np.asarray(a, dtype=np.uint64).reshape(-1, 4)
-        return [to_int(row) * cls.MONT_INV % cls.R for row in a]
+        buf = np.ascontiguousarray(a, dtype="<u8").reshape(-1, 4).tobytes()  # four little-endian limbs = one 32-byte little-endian integer
+        return [int.from_bytes(buf[k:k + 32], "little") * cls.MONT_INV % cls.R for k in range(0, len(buf), 32)]
 
     @classmethod
     def mont(cls, values):
-        out = np.zeros((len(values), 4), dtype=np.uint64)
-        for i, v in enumerate(values):
-            out[i] = from_int(v % cls.R * cls.MONT % cls.R)
-        return out
+        buf = b"".join((v % cls.R * cls.MONT % cls.R).to_bytes(32, "little") for v in values)
+        return np.frombuffer(buf, dtype="<u8").astype(np.uint64).reshape(-1, 4)
 
     @classmethod
     def root(cls, log2n):  # field.hpp:487-494
