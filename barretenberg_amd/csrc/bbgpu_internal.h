@@ -11,6 +11,15 @@
 namespace bbgpu {
 
 void set_error(const char* fmt, ...);
+// a failed HIP call: recorded with its place, and the calling function returns BBGPU_ERR_HIP
+#define HIPCHK(x)                                                                                                      \
+    do {                                                                                                               \
+        hipError_t e_ = (x);                                                                                           \
+        if (e_ != hipSuccess) {                                                                                        \
+            set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));                                \
+            return BBGPU_ERR_HIP;                                                                                      \
+        }                                                                                                              \
+    } while (0)
 
 // capi.hip: EVERY device allocation, host<->device copy of a caller's buffer and launch check of the library goes through these four, so that
 // (i) a test can make the k-th one fail on a machine that HAS a GPU (BBGPU_FAIL_AT / bbgpu_fault_inject: "alloc:k", "h2d:k", "d2h:k", "launch:k" -- the

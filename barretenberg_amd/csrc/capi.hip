@@ -301,15 +301,6 @@ thread_local int t_ctx = 0;
 inline Context& ctx() { return g_ctxs[t_ctx]; }
 inline std::recursive_mutex& ctx_lock() { return t_ctx == 0 ? g_mu : ctx().own_mu; }
 
-#define CHK(x)                                                                                                         \
-    do {                                                                                                               \
-        hipError_t e_ = (x);                                                                                           \
-        if (e_ != hipSuccess) {                                                                                        \
-            set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));                                \
-            return BBGPU_ERR_HIP;                                                                                      \
-        }                                                                                                              \
-    } while (0)
-
 void read_host_env()
 {
     // the staging knobs are read once per context whatever else happened; the two thresholds only while bbgpu_set_host_thresholds() has not set them
@@ -341,7 +332,7 @@ int ensure_init()
         // bench.py's issuing thread on rank r > 0 -- must allocate and launch on the device this process is bound to, not on device 0
         static thread_local int bound_device = -1;
         if (bound_device != ctx().device) {
-            CHK(hipSetDevice(ctx().device));
+            HIPCHK(hipSetDevice(ctx().device));
             bound_device = ctx().device;
         }
         return BBGPU_OK;
@@ -356,15 +347,15 @@ int ensure_init()
         set_error("no HIP device available: the GPU entry points of libbbgpu have no CPU fallback");
         return BBGPU_ERR_HIP;
     }
-    CHK(hipSetDevice(ctx().device));
-    CHK(hipStreamCreateWithFlags(&ctx().stream, hipStreamNonBlocking));
+    HIPCHK(hipSetDevice(ctx().device));
+    HIPCHK(hipStreamCreateWithFlags(&ctx().stream, hipStreamNonBlocking));
     // the slot streams are made HERE, one after the other: the runtime deals streams to hardware queues in creation order, and a slot
     // stream created later (first use of a third slot, in a process that has made other streams meanwhile) can land on the queue of another slot
     for (auto& sl : ctx().slot) {
-        if (!sl.stream) CHK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
+        if (!sl.stream) HIPCHK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
         sl.acc_ring = &ctx().acc_ring;
     }
-    CHK(hipEventCreateWithFlags(&ctx().shared_done, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ctx().shared_done, hipEventDisableTiming));
     ctx().shared_used = false;
     // the cap holds for each device context on its own (bbgpu_init_devices)
     if (const char* e = getenv("BBGPU_SRS_CACHE_BYTES")) ctx().srs_cache_cap = (size_t)strtoull(e, nullptr, 0);
@@ -378,12 +369,12 @@ int ensure_init()
 // back on two streams then run one after the other instead of overwriting each other's intermediate data.
 int shared_begin(hipStream_t st)
 {
-    if (ctx().shared_used && ctx().shared_last != st) CHK(hipStreamWaitEvent(st, ctx().shared_done, 0));
+    if (ctx().shared_used && ctx().shared_last != st) HIPCHK(hipStreamWaitEvent(st, ctx().shared_done, 0));
     return BBGPU_OK;
 }
 int shared_end(hipStream_t st)
 {
-    CHK(hipEventRecord(ctx().shared_done, st));
+    HIPCHK(hipEventRecord(ctx().shared_done, st));
     ctx().shared_last = st;
     ctx().shared_used = true;
     return BBGPU_OK;
@@ -395,7 +386,7 @@ int grow(uint64_t** buf, size_t* cap, size_t bytes)
     if (*buf) (void)dev_free(*buf);
     *buf = nullptr;
     *cap = 0;
-    CHK(dev_malloc((void**)buf, bytes));
+    HIPCHK(dev_malloc((void**)buf, bytes));
     *cap = bytes;
     return BBGPU_OK;
 }
@@ -421,8 +412,8 @@ static int host_stage_ensure()
 {
     for (int k = 0; k < Context::HOST_RING; k++)
         if (!ctx().h_stage[k]) {
-            CHK(hipHostMalloc(&ctx().h_stage[k], Context::HOST_CHUNK, hipHostMallocDefault));
-            CHK(hipEventCreateWithFlags(&ctx().h_stage_free[k], hipEventDisableTiming));
+            HIPCHK(hipHostMalloc(&ctx().h_stage[k], Context::HOST_CHUNK, hipHostMallocDefault));
+            HIPCHK(hipEventCreateWithFlags(&ctx().h_stage_free[k], hipEventDisableTiming));
         }
     return BBGPU_OK;
 }
@@ -436,7 +427,7 @@ int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st)
     read_host_env();
     if (bytes == 0) return BBGPU_OK;
     if (bytes > ctx().host_stage_max) {
-        CHK(h2d_async(d_dst, h_src, bytes, st));
+        HIPCHK(h2d_async(d_dst, h_src, bytes, st));
         return BBGPU_OK;
     }
     if (int rc = host_stage_ensure()) return rc;
@@ -444,10 +435,10 @@ int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st)
     for (size_t off = 0; off < bytes; off += CH) {
         const size_t len = std::min(CH, bytes - off);
         const int k = (int)(ctx().h_stage_next++ % Context::HOST_RING);
-        CHK(hipEventSynchronize(ctx().h_stage_free[k])); // the DMA that last read this buffer has finished (no-op before its first use)
+        HIPCHK(hipEventSynchronize(ctx().h_stage_free[k])); // the DMA that last read this buffer has finished (no-op before its first use)
         ctx().copy_pool.copy(ctx().h_stage[k], (const char*)h_src + off, len);
-        CHK(h2d_async((char*)d_dst + off, ctx().h_stage[k], len, st));
-        CHK(hipEventRecord(ctx().h_stage_free[k], st));
+        HIPCHK(h2d_async((char*)d_dst + off, ctx().h_stage[k], len, st));
+        HIPCHK(hipEventRecord(ctx().h_stage_free[k], st));
     }
     return BBGPU_OK;
 }
@@ -460,9 +451,9 @@ int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_
     read_host_env();
     if (touched) *touched = false;
     if (bytes > ctx().host_stage_max) {
-        CHK(d2h_async(h_dst, d_src, bytes, st));
+        HIPCHK(d2h_async(h_dst, d_src, bytes, st));
         if (touched) *touched = true; // the DMA engine owns the destination from here on
-        CHK(hipStreamSynchronize(st));
+        HIPCHK(hipStreamSynchronize(st));
         return BBGPU_OK;
     }
     if (int rc = host_stage_ensure()) return rc;
@@ -474,13 +465,13 @@ int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_
     auto enqueue = [&](size_t c) -> int {
         const int k = (int)(ctx().h_stage_next++ % Context::HOST_RING);
         kbuf[c % Context::HOST_RING] = k;
-        CHK(hipEventSynchronize(ctx().h_stage_free[k]));
-        CHK(d2h_async(ctx().h_stage[k], (const char*)d_src + c * CH, std::min(CH, bytes - c * CH), st));
-        CHK(hipEventRecord(ctx().h_stage_free[k], st));
+        HIPCHK(hipEventSynchronize(ctx().h_stage_free[k]));
+        HIPCHK(d2h_async(ctx().h_stage[k], (const char*)d_src + c * CH, std::min(CH, bytes - c * CH), st));
+        HIPCHK(hipEventRecord(ctx().h_stage_free[k], st));
         return BBGPU_OK;
     };
     if (chunks == 0) {
-        CHK(hipStreamSynchronize(st));
+        HIPCHK(hipStreamSynchronize(st));
         return BBGPU_OK;
     }
     size_t queued = 0;
@@ -492,7 +483,7 @@ int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_
             queued++;
         }
         const int k = kbuf[c % Context::HOST_RING];
-        CHK(hipEventSynchronize(ctx().h_stage_free[k]));
+        HIPCHK(hipEventSynchronize(ctx().h_stage_free[k]));
         if (touched) *touched = true;
         ctx().copy_pool.copy((char*)h_dst + c * CH, ctx().h_stage[k], std::min(CH, bytes - c * CH));
     }
@@ -789,9 +780,9 @@ int issue_ticket(int t, const SrsEntry& e, size_t off, const uint64_t* const* d_
     if (H) {
         // `st` carries the producer of the scalars -- a caller's kernel, or the asynchronous upload host_to_device() queued on the slot's OWN stream
         // (bbgpu_msm_g1 / _batch): the helper's stream starts behind what is enqueued there now, whichever stream that is
-        if (!ctx().helper_dep[h]) CHK(hipEventCreateWithFlags(&ctx().helper_dep[h], hipEventDisableTiming));
-        CHK(hipEventRecord(ctx().helper_dep[h], st));
-        CHK(hipStreamWaitEvent(H->stream, ctx().helper_dep[h], 0));
+        if (!ctx().helper_dep[h]) HIPCHK(hipEventCreateWithFlags(&ctx().helper_dep[h], hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ctx().helper_dep[h], st));
+        HIPCHK(hipStreamWaitEvent(H->stream, ctx().helper_dep[h], 0));
         H->helper = -1;
     }
     int issued[2] = { 0, 0 };
@@ -1711,7 +1702,7 @@ int bbgpu_kate_opening_device(const uint64_t* d_src, uint64_t* d_dest, size_t n,
     if (d_dest == d_src) { // the scan's last phase reads its input while writing: work from a copy
         int rc = grow(&ctx().d_poly_tmp, &ctx().poly_tmp_cap, n * 32);
         if (rc) return rc;
-        CHK(hipMemcpyAsync(ctx().d_poly_tmp, d_src, n * 32, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx().d_poly_tmp, d_src, n * 32, hipMemcpyDeviceToDevice, st));
         src = ctx().d_poly_tmp;
     }
     return poly::horner_suffix(src, d_dest, n, zz, false, ctx().poly_scratch, st, nullptr);
@@ -2026,12 +2017,12 @@ int bbgpu_srs_check(int srs_handle, size_t n, const uint64_t g2_x[16], const uin
     // one pass over the rows and, beside it, the multipliers; ONE synchronisation before the verdict on the curve test is read
     const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
     SrsCurveFindings got = init;
-    CHK(h2d_async(d_find, &init, sizeof init, st));
+    HIPCHK(h2d_async(d_find, &init, sizeof init, st));
     if (int rc = srs_check_curve(e.d_srs, n, gen, d_find, st)) return rc;
     if (want_powers)
         if (int rc = srs_check_scalars(sd, n - 1, d_rho, st)) return rc;
-    CHK(d2h_async(&got, d_find, sizeof got, st));
-    CHK(hipStreamSynchronize(st));
+    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
+    HIPCHK(hipStreamSynchronize(st));
     out->bad_points = got.bad_points;
     out->first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
     out->first_is_generator = got.first_is_generator;
@@ -2234,10 +2225,10 @@ int bbgpu_srs_update(int srs_handle, size_t n, size_t first_power, const uint64_
     const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
     SrsCurveFindings got = init;
-    CHK(h2d_async(d_find, &init, sizeof init, st));
+    HIPCHK(h2d_async(d_find, &init, sizeof init, st));
     if (int rc = srs_check_curve(d_in, n, no_generator, d_find, st)) return rc;
-    CHK(d2h_async(&got, d_find, sizeof got, st));
-    CHK(hipStreamSynchronize(st));
+    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
+    HIPCHK(hipStreamSynchronize(st));
     rep.bad_points = got.bad_points;
     rep.first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
     if (out) *out = rep;
@@ -2320,10 +2311,10 @@ int bbgpu_srs_lagrange(int srs_handle, size_t n, uint64_t* host_endo_table_out, 
     const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     const SrsCurveFindings init[2] = { { 0, ~0ull, 0, 0 }, { 0, ~0ull, 0, 0 } };
     SrsCurveFindings got = init[0], infinite = init[1];
-    CHK(h2d_async(d_find, init, sizeof init, st));
+    HIPCHK(h2d_async(d_find, init, sizeof init, st));
     if (int rc = srs_check_curve(d_in, n, no_generator, d_find, st)) return rc;
-    CHK(d2h_async(&got, d_find, sizeof got, st));
-    CHK(hipStreamSynchronize(st));
+    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
+    HIPCHK(hipStreamSynchronize(st));
     rep.bad_points = got.bad_points;
     rep.first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
     if (rep.bad_points) {
@@ -2905,7 +2896,7 @@ int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count,
     uint32_t* d_status = reinterpret_cast<uint32_t*>(base + o_status);
     const hipStream_t st = ctx().stream;
     if (int rc = host_to_device(base, proofs, count * BBGPU_PLONK_PROOF_WORDS * 8, st)) return rc;
-    CHK(h2d_async(d_rows_a, H.shared_rows, S * 64, st));
+    HIPCHK(h2d_async(d_rows_a, H.shared_rows, S * 64, st));
     VerifyDeviceBuffers B;
     B.proofs = reinterpret_cast<const uint64_t*>(base);
     B.rows_own = d_rows_a + S * 16;
@@ -2915,8 +2906,8 @@ int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count,
     B.shared = d_shared;
     B.status = d_status;
     if (int rc = plonk_verify_terms(H.D, sd, count, B, st)) return rc;
-    CHK(d2h_async(status, d_status, count * 4, st));
-    CHK(hipStreamSynchronize(st));
+    HIPCHK(d2h_async(status, d_status, count * 4, st));
+    HIPCHK(hipStreamSynchronize(st));
     g_verify_ms[1] = now_ms() - t_begin;
     host::verify_count_status(out, status);
     // A and B: two tickets in flight over transient tables (the rows the kernel wrote; no window tables), the scalars where the kernels left them
@@ -2929,7 +2920,7 @@ int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count,
     const int rc_tail = host::verify_tail(out, H.K.g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
         const double t_fold = now_ms();
         if (int rc = plonk_verify_fold(d_shared, count, m, (int)S, H.skip_mask, d_scal_a, st)) return rc;
-        CHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
+        HIPCHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
         const double t_msm = now_ms();
         g_verify_ms[2] += t_msm - t_fold;
         if (int rc = verify_two_msms(ea, eb, d_scal_a, d_scal_b, S + host::VERIFY_OWN * m, 2 * m, a12, b12)) return rc;
@@ -3001,7 +2992,7 @@ int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint
         // built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy
         if (int rc = host_stage_ensure()) return rc;
         const int kb = (int)(ctx().h_stage_next++ % Context::HOST_RING);
-        CHK(hipEventSynchronize(ctx().h_stage_free[kb]));
+        HIPCHK(hipEventSynchronize(ctx().h_stage_free[kb]));
         uint8_t* h = static_cast<uint8_t*>(ctx().h_stage[kb]);
         memset(h, 0, o_rows_a - o_circuit);
         memcpy(h, circuit, count * 4);
@@ -3023,8 +3014,8 @@ int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint
             memcpy(rows + at * 64, H[c]->shared_rows, (size_t)H[c]->K.num_shared() * 64);
             at += (size_t)H[c]->K.num_shared();
         }
-        CHK(h2d_async(base + o_circuit, h, head_bytes, st));
-        CHK(hipEventRecord(ctx().h_stage_free[kb], st));
+        HIPCHK(h2d_async(base + o_circuit, h, head_bytes, st));
+        HIPCHK(hipEventRecord(ctx().h_stage_free[kb], st));
     }
     VerifyDeviceBuffers B;
     B.proofs = reinterpret_cast<const uint64_t*>(base);
@@ -3035,8 +3026,8 @@ int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint
     B.shared = d_shared;
     B.status = d_status;
     if (int rc = plonk_verify_terms_mixed(d_records, d_circuit, sd, count, B, st)) return rc;
-    CHK(d2h_async(status, d_status, count * 4, st));
-    CHK(hipStreamSynchronize(st));
+    HIPCHK(d2h_async(status, d_status, count * 4, st));
+    HIPCHK(hipStreamSynchronize(st));
     g_verify_ms[1] = now_ms() - t_begin;
     host::verify_count_status(out, status);
     SrsEntry ea{}, eb{};
@@ -3048,7 +3039,7 @@ int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint
     const int rc_tail = host::verify_tail(out, H[0]->K.g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
         const double t_fold = now_ms();
         if (int rc = plonk_verify_fold_mixed(d_shared, d_circuit, d_records, (int)G, (int)S_max, count, m, d_scal_a, st)) return rc;
-        CHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
+        HIPCHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
         const double t_msm = now_ms();
         g_verify_ms[2] += t_msm - t_fold;
         if (int rc = verify_two_msms(ea, eb, d_scal_a, d_scal_b, T + host::VERIFY_OWN * m, 2 * m, a12, b12)) return rc;

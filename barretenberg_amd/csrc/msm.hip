@@ -1465,15 +1465,6 @@ __global__ void __launch_bounds__(QFOLD_T) TAIL_OCC msm_final_quad_kernel(const 
 // ---------------------------------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------------------------------
-#define HIPCHK(x)                                                                                                      \
-    do {                                                                                                               \
-        hipError_t e_ = (x);                                                                                           \
-        if (e_ != hipSuccess) {                                                                                        \
-            set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));                                \
-            return BBGPU_ERR_HIP;                                                                                      \
-        }                                                                                                              \
-    } while (0)
-
 int msm_choose_c(size_t n)
 {
     // (round 5 swept fixed window sizes 5 .. 10 for the table-less small MSMs, 32 .. 1000 points, against this rule: nothing better, profiles/r05_small_sizes.txt)

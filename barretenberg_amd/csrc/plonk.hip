@@ -40,14 +40,6 @@ namespace {
 
 using host::Fr;
 
-#define HIPCHK(x)                                                                                                      \
-    do {                                                                                                               \
-        hipError_t e_ = (x);                                                                                           \
-        if (e_ != hipSuccess) {                                                                                        \
-            set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));                                \
-            return BBGPU_ERR_HIP;                                                                                      \
-        }                                                                                                              \
-    } while (0)
 #define RC(x)                                                                                                          \
     do {                                                                                                               \
         int rc_ = (x);                                                                                                 \

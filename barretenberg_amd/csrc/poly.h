@@ -125,7 +125,7 @@ struct ScanJob {
     size_t n;
     bool reverse, inclusive;
     host::Fr z;         // Horner scans only
-    uint64_t* d_total;  // optional 32-byte device slot
+    uint64_t* d_total;  // optional 32-byte device slot, 16-byte aligned: the total is stored there by a kernel, not copied
 };
 
 // ---- the prover's round kernels (the lanes of plonk.hip: one for a single proof, up to 16 for a batch) ---------------------------------------------
@@ -154,7 +154,7 @@ struct SigmaPrepArgs {
     uint32_t n, n_dst;
     Limbs9 gamma_m256;
 };
-struct CopyPadArgs { // dst[0..n_dst) = c * src[0..n_src) (or src itself), zeros behind
+struct CopyPadArgs { // dst[0..n_dst) = c * src[0..n_src) (or src itself, bit for bit: scaled = 0, the record of copy_pad), zeros behind
     uint32_t* dst;
     const uint32_t* src;
     uint32_t n_src, n_dst, scaled;
@@ -181,8 +181,9 @@ int copy_pad_lanes(LaneTable& T, const CopyPadArgs* A, int records, const host::
 // the same vector of every lane at base + lane * stride (elements), no per-lane constant
 int add_inplace_lanes(uint64_t* d_a, size_t stride_a, const uint64_t* d_b, size_t stride_b, size_t n, int lanes, hipStream_t st);
 int divide_by_pseudo_vanishing_lanes(uint64_t* d_coeffs, size_t stride, int lanes, int log2n, int log2N, hipStream_t st);
-// `count` scans of one mode (0 = running products, 1 = Horner suffix sums) and one length (<= 2^22) in shared launches; jobs[j].d_total, where given,
-// receives the total directly
+// `count` scans of one mode (0 = running products, 1 = Horner suffix sums) and one length (<= 2^22) in shared launches: the plan and the driver of
+// product_scan / horner_suffix below, the phases launched from table records instead of by value.  jobs[j].d_total, where given, receives the total
+// directly, in every form
 int scan_lanes(int mode, const ScanJob* jobs, int count, LaneTable& T, Scratch& S, hipStream_t st);
 // `count` evaluations, job j at z[zidx[j]]
 int evaluate_lanes(const EvalJob* jobs, const int* zidx, int count, const host::Fr* z, int nz, LaneTable& T, Scratch& S, hipStream_t st);

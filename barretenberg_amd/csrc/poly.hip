@@ -24,6 +24,11 @@
 // per-thread runs of 8 elements, a Hillis-Steele doubling over the 256 thread partials in LDS, a single-workgroup scan
 // of the block partials, and a final pass that applies the carries.  Exact field arithmetic makes the result independent
 // of the association order, so outputs are bit-identical to the serial loops.
+//
+// One text per kernel: a scan phase, an evaluation or a pointwise operation that serves both the single-vector helpers of
+// the C ABI and the lanes of the prover is ONE device body, wrapped twice -- k_x(Args by value) and k_x_tab / k_x_lanes
+// (const Args* table, blockIdx.y = record) -- and one host driver issues either (scan_issue, below).  The bodies take
+// U = true only where their constants are fields of a table record (see cst).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,15 +53,6 @@ constexpr int PT = 256;  // threads per workgroup of the pointwise kernels
 constexpr int RUN = 8;   // elements per thread in the scan kernels
 constexpr int SCAN_T = 256;
 constexpr int SCAN_BLOCK = SCAN_T * RUN; // 2048 elements per workgroup
-
-#define HIPCHK(x)                                                                                                      \
-    do {                                                                                                               \
-        hipError_t e_ = (x);                                                                                           \
-        if (e_ != hipSuccess) {                                                                                        \
-            set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));                                \
-            return BBGPU_ERR_HIP;                                                                                      \
-        }                                                                                                              \
-    } while (0)
 
 // ---- device helpers -------------------------------------------------------------------------------------------------
 __device__ __forceinline__ FrV ldv(const uint32_t* __restrict__ p, size_t i)
@@ -122,29 +118,36 @@ __global__ void __launch_bounds__(PT) k_powers(uint32_t* __restrict__ out, uint3
         x = mul(x, step);
     }
 }
-// dst[0..n_dst) = src[0..n_src) followed by zeros (polynomial(other, size): polynomial.cpp:48-66), canonicalising
-__global__ void __launch_bounds__(PT) k_copy_pad(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint32_t n_src, uint32_t n_dst)
+// dst[0..n_dst) = src[0..n_src) followed by zeros (polynomial(other, size): polynomial.cpp:48-66), bit for bit; with an optional per-record multiplier:
+// alpha Z and beta sigma_i are scaled in coefficient form, in front of the lanes' shared plain transform (the *_WITH_CONSTANT kinds take one constant
+// per batched launch; scaling commutes with the transform and every value is exact)
+template <bool U> __device__ __forceinline__ void copy_pad_body(const CopyPadArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_dst) return;
-    uint4* q = reinterpret_cast<uint4*>(dst + (size_t)i * 8);
-    if (i < n_src) {
-        const uint4* s = reinterpret_cast<const uint4*>(src + (size_t)i * 8);
-        q[0] = s[0];
-        q[1] = s[1];
-    } else {
+    if (i >= A.n_dst) return;
+    uint4* q = reinterpret_cast<uint4*>(A.dst + (size_t)i * 8);
+    if (i >= A.n_src) {
         q[0] = make_uint4(0, 0, 0, 0);
         q[1] = make_uint4(0, 0, 0, 0);
+    } else if (A.scaled) {
+        stv(A.dst, i, mul(ldv(A.src, i), cst<U>(A.c_m261)));
+    } else {
+        const uint4* sp = reinterpret_cast<const uint4*>(A.src + (size_t)i * 8);
+        q[0] = sp[0];
+        q[1] = sp[1];
     }
 }
+__global__ void __launch_bounds__(PT) k_copy_pad(CopyPadArgs A) { copy_pad_body<false>(A); }
+__global__ void __launch_bounds__(PT) k_copy_pad_lanes(const CopyPadArgs* __restrict__ tab) { copy_pad_body<true>(tab[blockIdx.y]); }
 // out[i] = a[i] * b[i] * c   (c in the 2^261 form, already carrying the FIX2 factor: c' = c * 2^5)
-__global__ void __launch_bounds__(PT) k_mul2c(uint32_t* __restrict__ out, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t n,
-                                            Limbs9 c_fix_m261)
+template <bool U> __device__ __forceinline__ void mul2c_body(const Mul2cArgs& A)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    stv(out, i, mul(mul(ldv(a, i), ldv(b, i)), cst(c_fix_m261)));
+    if (i >= A.n) return;
+    stv(A.out, i, mul(mul(ldv(A.a, i), ldv(A.b, i)), cst<U>(A.c_fix_m261)));
 }
+__global__ void __launch_bounds__(PT) k_mul2c(Mul2cArgs A) { mul2c_body<false>(A); }
+__global__ void __launch_bounds__(PT) k_mul2c_lanes(const Mul2cArgs* __restrict__ tab) { mul2c_body<true>(tab[blockIdx.y]); }
 // out[i] = a[i] * b[i]     (polynomial_arithmetic::mul, :328-335)
 __global__ void __launch_bounds__(PT) k_mul(uint32_t* __restrict__ out, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t n)
 {
@@ -239,10 +242,9 @@ template <int MODE> __device__ __forceinline__ FrV ld_or_id(const uint32_t* p, u
 }
 
 // phase 1: per-thread run totals, block scan of them -> tpart (exclusive within the block), bpart (block total)
-// (two independent scans per launch: blockIdx.y selects the argument block; the second may be empty, n = 0)
 template <int MODE, bool U> __device__ __forceinline__ void scan_phase1_body(const ScanArgs& A, uint32_t* sh)
 {
-    if (blockIdx.x * SCAN_BLOCK >= A.n) return; // whole workgroup: the two scans may differ in length
+    if (blockIdx.x * SCAN_BLOCK >= A.n) return; // whole workgroup
     const uint32_t t = threadIdx.x, b = blockIdx.x;
     const uint32_t base = b * SCAN_BLOCK + t * RUN;
     const bool suffix = (MODE == 1) || A.reverse;
@@ -266,10 +268,11 @@ template <int MODE, bool U> __device__ __forceinline__ void scan_phase1_body(con
     if ((size_t)tid * RUN < A.n) stv(A.tpart, tid, ex);
     if (t == 0) stv(A.bpart, b, total);
 }
-template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase1(ScanArgs A0, ScanArgs A1)
+// one scan, its arguments by value
+template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase1(ScanArgs A)
 {
     __shared__ uint32_t sh[NL * SCAN_T];
-    scan_phase1_body<MODE, false>(blockIdx.y ? A1 : A0, sh);
+    scan_phase1_body<MODE, false>(A, sh);
 }
 // the same over a device table of jobs (blockIdx.y = job): the lanes of a proof batch, two scans each
 template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase1_tab(const ScanArgs* __restrict__ tab)
@@ -282,7 +285,7 @@ template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase1_tab(
 template <int MODE, bool U> __device__ __forceinline__ void scan_phase3_body(const ScanArgs& A, uint32_t* sh)
 {
     const uint32_t t = threadIdx.x, b = blockIdx.x;
-    if (b * SCAN_BLOCK >= A.n) return; // whole workgroup: the two scans may differ in length
+    if (b * SCAN_BLOCK >= A.n) return; // whole workgroup (n = 0: a job without an output vector, where the total does not come from this phase)
     const bool suffix = (MODE == 1) || A.reverse;
     // <= SCAN_T blocks: the exclusive scan of the block totals (phase 1 + phase 3 of the nested level: two launches of one workgroup
     // each, ~40 us of a 2^16-element scan's ~95) is done here by every workgroup for itself, lane t standing for block t
@@ -360,10 +363,10 @@ template <int MODE, bool U> __device__ __forceinline__ void scan_phase3_body(con
         }
     }
 }
-template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase3(ScanArgs A0, ScanArgs A1)
+template <int MODE> __global__ void __launch_bounds__(SCAN_T) k_scan_phase3(ScanArgs A)
 {
     __shared__ uint32_t sh[NL * SCAN_T];
-    scan_phase3_body<MODE, false>(blockIdx.y ? A1 : A0, sh);
+    scan_phase3_body<MODE, false>(A, sh);
 }
 template <int MODE> __global__ void __launch_bounds__(SCAN_T, MODE == 0 ? 7 : 8) k_scan_phase3_tab(const ScanArgs* __restrict__ tab)
 {
@@ -372,23 +375,10 @@ template <int MODE> __global__ void __launch_bounds__(SCAN_T, MODE == 0 ? 7 : 8)
 }
 
 // ---- evaluate: sum_i c_i z^i ------------------------------------------------------------------------------------------
-// thread t owns indices t, t + T, t + 2T, ...: Horner in z^T from the top, then * z^t; block tree in LDS; one partial / block
-__global__ void __launch_bounds__(PT) k_eval_partial(const uint32_t* __restrict__ c, uint32_t n, PowTab T, Limbs9 zT_m261, uint32_t* __restrict__ partial)
+// dst[i] = the workgroup's sum of one value per thread, by a tree in LDS (lazy adds: 8 levels of doubling the bound stay far below the limits after a
+// tighten per level)
+__device__ __forceinline__ void block_sum(uint32_t* __restrict__ dst, size_t i, const FrM& acc, uint32_t* sh)
 {
-    __shared__ uint32_t sh[NL * PT];
-    const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
-    FrM acc = mul(fe_zero<Fr>(), fe_from<Fr>(Fr::ONE));
-    if (t < n) {
-        const uint32_t cnt = (n - t + nt - 1) / nt;
-        const FrC zT = cst(zT_m261);
-        FrH h = ldv(c, t + (size_t)(cnt - 1) * nt);
-        for (uint32_t k = cnt - 1; k-- > 0;) h = add(mul(h, zT), ldv(c, t + (size_t)k * nt));
-        Limbs9 one261;
-#pragma unroll
-        for (int k = 0; k < NL; k++) one261.d[k] = Fr::ONE[k];
-        acc = mul(h, pow_tab(T, t, one261)); // * z^t
-    }
-    // block sum (lazy adds: 8 levels of doubling the bound stay far below the limits after a tighten per level)
 #pragma unroll
     for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = acc.d[k];
     __syncthreads();
@@ -400,125 +390,63 @@ __global__ void __launch_bounds__(PT) k_eval_partial(const uint32_t* __restrict_
                 a.d[k] = sh[k * PT + threadIdx.x];
                 b.d[k] = sh[k * PT + threadIdx.x + half];
             }
-            FrM s = tight2<Fr>(add(a, b));
+            FrM sm = tight2<Fr>(add(a, b));
 #pragma unroll
-            for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = s.d[k];
+            for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = sm.d[k];
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        FrM s;
+        FrM sm;
 #pragma unroll
-        for (int k = 0; k < NL; k++) s.d[k] = sh[k * PT];
-        stv(partial, blockIdx.x, s);
+        for (int k = 0; k < NL; k++) sm.d[k] = sh[k * PT];
+        stv(dst, i, sm);
     }
 }
-// out[0] = sum of `count` partials (count <= a few hundred): one workgroup
-__global__ void __launch_bounds__(PT) k_sum_small(const uint32_t* __restrict__ partial, uint32_t count, uint32_t* __restrict__ out)
-{
-    __shared__ uint32_t sh[NL * PT];
-    FrM acc = mul(fe_zero<Fr>(), fe_from<Fr>(Fr::ONE));
-    for (uint32_t i = threadIdx.x; i < count; i += PT) acc = tight2<Fr>(add(acc, ldv(partial, i)));
-#pragma unroll
-    for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = acc.d[k];
-    __syncthreads();
-    for (uint32_t half = PT / 2; half >= 1; half >>= 1) {
-        if (threadIdx.x < half) {
-            FrM a, b;
-#pragma unroll
-            for (int k = 0; k < NL; k++) {
-                a.d[k] = sh[k * PT + threadIdx.x];
-                b.d[k] = sh[k * PT + threadIdx.x + half];
-            }
-            FrM s = tight2<Fr>(add(a, b));
-#pragma unroll
-            for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = s.d[k];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        FrM s;
-#pragma unroll
-        for (int k = 0; k < NL; k++) s.d[k] = sh[k * PT];
-        stv(out, 0, s);
-    }
-}
-
-// several evaluations in one pair of launches (blockIdx.y = job): the prover's seven openings at z / z w (prover.cpp:478-512)
+// thread t owns indices t, t + T, t + 2T, ... (T = nblocks * PT threads): Horner in z^T from the top, then * z^t; one partial / block
+template <bool U>
 __device__ __forceinline__ void eval_partial_body(const uint32_t* __restrict__ c, uint32_t n, uint32_t nblocks, const PowTab& T, const Limbs9& zT_m261,
                                                   uint32_t* __restrict__ partial, uint32_t* sh)
 {
-    if (blockIdx.x >= nblocks) return;
+    if (blockIdx.x >= nblocks) return; // (the jobs of a table share one grid: the widest job's)
     const uint32_t nt = nblocks * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     FrM acc = mul(fe_zero<Fr>(), fe_from<Fr>(Fr::ONE));
     if (t < n) {
         const uint32_t cnt = (n - t + nt - 1) / nt;
-        const FrC zT = cst<true>(zT_m261);
+        const FrC zT = cst<U>(zT_m261);
         FrH h = ldv(c, t + (size_t)(cnt - 1) * nt);
         for (uint32_t k = cnt - 1; k-- > 0;) h = add(mul(h, zT), ldv(c, t + (size_t)k * nt));
         Limbs9 one261;
 #pragma unroll
         for (int k = 0; k < NL; k++) one261.d[k] = Fr::ONE[k];
-        acc = mul(h, pow_tab<true>(T, t, one261)); // * z^t
+        acc = mul(h, pow_tab<U>(T, t, one261)); // * z^t
     }
-#pragma unroll
-    for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = acc.d[k];
-    __syncthreads();
-    for (uint32_t half = PT / 2; half >= 1; half >>= 1) {
-        if (threadIdx.x < half) {
-            FrM a, b;
-#pragma unroll
-            for (int k = 0; k < NL; k++) {
-                a.d[k] = sh[k * PT + threadIdx.x];
-                b.d[k] = sh[k * PT + threadIdx.x + half];
-            }
-            FrM sm = tight2<Fr>(add(a, b));
-#pragma unroll
-            for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = sm.d[k];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        FrM sm;
-#pragma unroll
-        for (int k = 0; k < NL; k++) sm.d[k] = sh[k * PT];
-        stv(partial, blockIdx.x, sm);
-    }
+    block_sum(partial, blockIdx.x, acc, sh);
+}
+__global__ void __launch_bounds__(PT) k_eval_partial(const uint32_t* __restrict__ c, uint32_t n, PowTab T, Limbs9 zT_m261, uint32_t* __restrict__ partial)
+{
+    __shared__ uint32_t sh[NL * PT];
+    eval_partial_body<false>(c, n, gridDim.x, T, zT_m261, partial, sh);
 }
 // any number of evaluations, each at a point of its own, from a device table of jobs (blockIdx.y = job): the openings of every lane of a proof batch
+// (the prover's seven openings at z / z w, prover.cpp:478-512)
 __global__ void __launch_bounds__(PT) k_eval_partial_tab(const EvalTabJob* __restrict__ tab)
 {
     __shared__ uint32_t sh[NL * PT];
     const EvalTabJob& J = tab[blockIdx.y];
-    eval_partial_body(J.c, J.n, J.blocks, J.T, J.zT, J.partial, sh);
+    eval_partial_body<true>(J.c, J.n, J.blocks, J.T, J.zT, J.partial, sh);
 }
+// result[0] = sum of `count` partials (count <= a few hundred): one workgroup
 __device__ __forceinline__ void sum_small_body(const uint32_t* __restrict__ partial, uint32_t count, uint32_t* __restrict__ result, uint32_t* sh)
 {
     FrM acc = mul(fe_zero<Fr>(), fe_from<Fr>(Fr::ONE));
     for (uint32_t i = threadIdx.x; i < count; i += PT) acc = tight2<Fr>(add(acc, ldv(partial, i)));
-#pragma unroll
-    for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = acc.d[k];
-    __syncthreads();
-    for (uint32_t half = PT / 2; half >= 1; half >>= 1) {
-        if (threadIdx.x < half) {
-            FrM a, b;
-#pragma unroll
-            for (int k = 0; k < NL; k++) {
-                a.d[k] = sh[k * PT + threadIdx.x];
-                b.d[k] = sh[k * PT + threadIdx.x + half];
-            }
-            FrM sm = tight2<Fr>(add(a, b));
-#pragma unroll
-            for (int k = 0; k < NL; k++) sh[k * PT + threadIdx.x] = sm.d[k];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        FrM sm;
-#pragma unroll
-        for (int k = 0; k < NL; k++) sm.d[k] = sh[k * PT];
-        stv(result, 0, sm);
-    }
+    block_sum(result, 0, acc, sh);
+}
+__global__ void __launch_bounds__(PT) k_sum_small(const uint32_t* __restrict__ partial, uint32_t count, uint32_t* __restrict__ out)
+{
+    __shared__ uint32_t sh[NL * PT];
+    sum_small_body(partial, count, out, sh);
 }
 __global__ void __launch_bounds__(PT) k_sum_small_tab(const EvalTabJob* __restrict__ tab)
 {
@@ -784,23 +712,6 @@ __device__ __forceinline__ void expand_wires_body(const ExpandWiresArgs& A)
 }
 __global__ void __launch_bounds__(PT) k_expand_wires_lanes(const ExpandWiresArgs* __restrict__ tab) { expand_wires_body(tab[blockIdx.y]); } // one table record per lane
 
-// polynomial_arithmetic.cpp:478-560: c[i] *= (x_i - w_n^-1) / ((x_i)^n - 1),  x_i = g w_N^i;  (x_i)^n - 1 takes k = N/n values
-__global__ void __launch_bounds__(PT) k_divide_vanishing(uint32_t* __restrict__ c, uint32_t N, uint32_t k, PowTab root, Limbs9 g_m261, Limbs9 step_m261,
-                                                       Limbs9 wninv_m261, Limbs9 inv0, Limbs9 inv1, Limbs9 inv2, Limbs9 inv3)
-{
-    const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= N) return;
-    FrM x = pow_tab(root, t, g_m261);
-    const FrC step = cst(step_m261), wninv = cst(wninv_m261);
-    const uint32_t sel = t & (k - 1); // nt is a multiple of 4, so i mod k is fixed per thread
-    const FrC iv = cst(sel == 0 ? inv0 : sel == 1 ? inv1 : sel == 2 ? inv2 : inv3);
-    for (uint32_t i = t; i < N; i += nt) {
-        auto num = weak(sub(x, wninv));                 // 2^261 form
-        stv(c, i, mul(mul(ldv(c, i), num), iv));
-        x = mul(x, step);
-    }
-}
-
 // polynomial_arithmetic.cpp:381-476, first half: d[i] = g w_N^i - 1 (to be inverted)
 __global__ void __launch_bounds__(PT) k_l1_denominators(uint32_t* __restrict__ d, uint32_t N, PowTab root, Limbs9 g_m256, Limbs9 step_m261)
 {
@@ -838,13 +749,6 @@ __device__ __forceinline__ void lincomb_body(const LinCombArgs& A)
 __global__ void __launch_bounds__(PT) k_lincomb_lanes(const LinCombArgs* __restrict__ tab) { lincomb_body(tab[blockIdx.y]); } // one table record per lane
 
 // ---- lane-batched forms of the small kernels (blockIdx.y = record of a device table, or lane of a strided vector) ------------------------------------
-__global__ void __launch_bounds__(PT) k_mul2c_lanes(const Mul2cArgs* __restrict__ tab)
-{
-    const Mul2cArgs& A = tab[blockIdx.y];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= A.n) return;
-    stv(A.out, i, mul(mul(ldv(A.a, i), ldv(A.b, i)), cst<true>(A.c_fix_m261)));
-}
 // prover.cpp:253-269: dst (4n) = beta sigma(X) + w(X) + gamma in coefficient form, zero-padded
 __global__ void __launch_bounds__(PT) k_sigma_prepare_lanes(const SigmaPrepArgs* __restrict__ tab)
 {
@@ -861,25 +765,6 @@ __global__ void __launch_bounds__(PT) k_sigma_prepare_lanes(const SigmaPrepArgs*
     if (i == 0) stv(A.dst, i, add(v, cst<true>(A.gamma_m256)));
     else stv(A.dst, i, v);
 }
-// k_copy_pad with an optional per-record multiplier: alpha Z and beta sigma_i are scaled in coefficient form, in front of the lanes' shared plain
-// transform (the *_WITH_CONSTANT kinds take one constant per batched launch; scaling commutes with the transform and every value is exact)
-__global__ void __launch_bounds__(PT) k_copy_pad_lanes(const CopyPadArgs* __restrict__ tab)
-{
-    const CopyPadArgs& A = tab[blockIdx.y];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= A.n_dst) return;
-    uint4* q = reinterpret_cast<uint4*>(A.dst + (size_t)i * 8);
-    if (i >= A.n_src) {
-        q[0] = make_uint4(0, 0, 0, 0);
-        q[1] = make_uint4(0, 0, 0, 0);
-    } else if (A.scaled) {
-        stv(A.dst, i, mul(ldv(A.src, i), cst<true>(A.c_m261)));
-    } else {
-        const uint4* sp = reinterpret_cast<const uint4*>(A.src + (size_t)i * 8);
-        q[0] = sp[0];
-        q[1] = sp[1];
-    }
-}
 __global__ void __launch_bounds__(PT) k_add_inplace_lanes(uint32_t* __restrict__ a, size_t stride_a, const uint32_t* __restrict__ b, size_t stride_b, uint32_t n)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -888,6 +773,7 @@ __global__ void __launch_bounds__(PT) k_add_inplace_lanes(uint32_t* __restrict__
     b += (size_t)blockIdx.y * stride_b * 8;
     stv(a, i, add(ldv(a, i), ldv(b, i)));
 }
+// polynomial_arithmetic.cpp:478-560: c[i] *= (x_i - w_n^-1) / ((x_i)^n - 1),  x_i = g w_N^i;  (x_i)^n - 1 takes k = N/n values
 __global__ void __launch_bounds__(PT) k_divide_vanishing_lanes(uint32_t* __restrict__ c, size_t stride, uint32_t N, uint32_t k, PowTab root, Limbs9 g_m261,
                                                              Limbs9 step_m261, Limbs9 wninv_m261, Limbs9 inv0, Limbs9 inv1, Limbs9 inv2, Limbs9 inv3)
 {
@@ -961,7 +847,12 @@ int powers(uint64_t* d_out, size_t n, const host::Fr& base, const host::Fr& star
 }
 int copy_pad(uint64_t* d_dst, const uint64_t* d_src, size_t n_src, size_t n_dst, hipStream_t st)
 {
-    k_copy_pad<<<pw_blocks(n_dst), PT, 0, st>>>((uint32_t*)d_dst, (const uint32_t*)d_src, (uint32_t)n_src, (uint32_t)n_dst);
+    CopyPadArgs A{}; // the unscaled record
+    A.dst = (uint32_t*)d_dst;
+    A.src = (const uint32_t*)d_src;
+    A.n_src = (uint32_t)n_src;
+    A.n_dst = (uint32_t)n_dst;
+    k_copy_pad<<<pw_blocks(n_dst), PT, 0, st>>>(A);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
@@ -974,7 +865,7 @@ int mul_pointwise(uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, siz
 static int mul2c(uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, size_t n, const host::Fr& c, hipStream_t st)
 {
     const host::Fr cf = host::fr_mul(c, host::fr_from_u64(32)); // c * 2^5: the FIX2 factor folded in
-    k_mul2c<<<pw_blocks(n), PT, 0, st>>>((uint32_t*)d_out, (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t)n, host::limbs_m261(cf));
+    k_mul2c<<<pw_blocks(n), PT, 0, st>>>(Mul2cArgs{ (uint32_t*)d_out, (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t)n, host::limbs_m261(cf) });
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
@@ -993,10 +884,13 @@ size_t scan_scratch_bytes(size_t n)
 }
 
 // MODE 0 product scan (z ignored) / MODE 1 Horner suffix sums with multiplier z.  Three phases: runs of RUN per thread and a scan of the thread partials
-// in LDS (phase 1), a scan over the block totals, the carry pass (phase 3).  The scan over the block totals is one workgroup up to 2^22 elements
-// and the same three phases again above (round 4: n up to 2^28, the transforms' limit; the prover's L_1 scan is 2n).
-// Up to two independent scans of the same mode share the launches (ScanJob[2]; the second may have n = 0).
-static void scan_fill(int mode, const ScanJob& J, uint8_t* base, ScanArgs& A, ScanArgs& B)
+// in LDS (phase 1), a scan over the block totals, the carry pass (phase 3).  The scan over the block totals takes one of three forms:
+//   fused   (<= SCAN_T block totals, n <= 2^19): every workgroup of phase 3 scans them for itself; two launches;
+//   one workgroup (<= SCAN_BLOCK block totals, n <= 2^22): phase 1 and phase 3 of a second level B, one workgroup per job; four launches;
+//   nested  (above, n up to 2^28, the transforms' limit; the prover's L_1 scan is 2n): the same three phases again, on the scratch behind this level's.
+// The plan of one job: A (phase 1), B (the one-workgroup level over the block totals) and A3 (phase 3) in the job's scratch at `base`.  The total of
+// everything is the one element B.bpart points at -- the caller's slot where it gave one -- whichever form writes it.
+static void scan_plan(int mode, const ScanJob& J, uint8_t* base, ScanArgs& A, ScanArgs& B, ScanArgs& A3)
 {
     const size_t n = J.n;
     const size_t nt = (n + RUN - 1) / RUN, nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK, nt2 = (nb + RUN - 1) / RUN;
@@ -1015,11 +909,11 @@ static void scan_fill(int mode, const ScanJob& J, uint8_t* base, ScanArgs& A, Sc
     A.reverse = J.reverse ? 1u : 0u;
     A.inclusive = J.inclusive ? 1u : 0u;
     A.has_carry = 1;
-    B = A; // the nested scan over the block totals: exclusive, same direction
+    B = A; // the scan over the block totals: exclusive, same direction
     B.in = bpart;
     B.out = bcarry;
     B.tpart = tpart2;
-    B.bpart = bpart2;
+    B.bpart = J.d_total ? (uint32_t*)J.d_total : bpart2;
     B.bcarry = nullptr;
     B.has_carry = 0;
     B.n = (uint32_t)nb;
@@ -1030,7 +924,7 @@ static void scan_fill(int mode, const ScanJob& J, uint8_t* base, ScanArgs& A, Sc
         for (int j = 0; j < 8; j++) { A.zpow[j] = host::limbs_m261(p); p = host::fr_sqr(p); }
         A.zpow[8] = host::limbs_m261(J.z);
         A.zpow[9] = host::limbs_m261(zr);
-        // nested level: its "elements" are whole blocks, so its z is z^SCAN_BLOCK
+        // the level over the block totals: its "elements" are whole blocks, so its z is z^SCAN_BLOCK
         host::Fr zb = host::fr_pow(J.z, SCAN_BLOCK);
         p = zb;
         for (int j = 0; j < 8; j++) { A.zpow[12 + j] = host::limbs_m261(p); p = host::fr_sqr(p); }
@@ -1040,115 +934,93 @@ static void scan_fill(int mode, const ScanJob& J, uint8_t* base, ScanArgs& A, Sc
         B.zpow[8] = host::limbs_m261(zb);
         B.zpow[9] = host::limbs_m261(zbr);
     }
-}
-static int scan_pair_at(int mode, const ScanJob* jobs, int count, uint8_t* base, hipStream_t st);
-static int scan_pair(int mode, const ScanJob* jobs, int count, Scratch& S, hipStream_t st)
-{
-    if (count < 1 || count > 2) return BBGPU_ERR_ARG;
-    size_t total = 0;
-    for (int j = 0; j < count; j++) {
-        if (jobs[j].n > ((size_t)1 << 28)) {
-            set_error("scan of %zu elements: at most 2^28", jobs[j].n);
-            return BBGPU_ERR_SIZE;
-        }
-        total += scan_scratch_bytes(jobs[j].n);
+    A3 = A;
+    if (nb <= (size_t)SCAN_T) { // fused: phase 3 also runs for a scan without an output vector, for the total
+        A3.fused_nb = (uint32_t)nb;
+        A3.total_out = B.bpart;
+    } else if (!J.out) {
+        A3.n = 0;
     }
-    int rc = S.ensure(total + 64); // the whole nest at once: the workspace must not move under the launches of an outer level
-    if (rc) return rc;
-    return scan_pair_at(mode, jobs, count, S.base, st);
 }
-static int scan_pair_at(int mode, const ScanJob* jobs, int count, uint8_t* base, hipStream_t st)
+// How a phase is launched is all that tells a single scan from the scans of a lane table: its record by value, or every job's record from the table
+// (dev, grid.y = job).
+template <int MODE> static void scan_phase1(const ScanArgs* rec, const ScanArgs* dev, dim3 grid, hipStream_t st)
 {
-    size_t off[3] = { 0, 0, 0 }, nbmax = 0;
-    for (int j = 0; j < count; j++) {
-        off[j + 1] = off[j] + scan_scratch_bytes(jobs[j].n);
-        nbmax = std::max(nbmax, (jobs[j].n + SCAN_BLOCK - 1) / SCAN_BLOCK);
+    if (dev) k_scan_phase1_tab<MODE><<<grid, SCAN_T, 0, st>>>(dev);
+    else k_scan_phase1<MODE><<<grid, SCAN_T, 0, st>>>(*rec);
+}
+template <int MODE> static void scan_phase3(const ScanArgs* rec, const ScanArgs* dev, dim3 grid, hipStream_t st)
+{
+    if (dev) k_scan_phase3_tab<MODE><<<grid, SCAN_T, 0, st>>>(dev);
+    else k_scan_phase3<MODE><<<grid, SCAN_T, 0, st>>>(*rec);
+}
+// `count` scans of one length n >= 1, job j on the scratch at base + j * scan_scratch_bytes(n) (the caller has made it large enough: the whole nest at
+// once, the workspace must not move under the launches of an outer level).  T: the lane table that carries the records; null: one job, by value.
+template <int MODE> static int scan_issue(const ScanJob* jobs, int count, uint8_t* base, LaneTable* T, hipStream_t st)
+{
+    const size_t n = jobs[0].n, nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK, per = scan_scratch_bytes(n);
+    ScanArgs one[3];
+    ScanArgs *A = &one[0], *B = &one[1], *A3 = &one[2];
+    const ScanArgs *dA = nullptr, *dB = nullptr, *dA3 = nullptr;
+    if (T) {
+        if (int rc = T->push(count, &A, &dA)) return rc;
+        if (int rc = T->push(count, &B, &dB)) return rc;
+        if (int rc = T->push(count, &A3, &dA3)) return rc;
     }
-    if (nbmax == 0) return BBGPU_OK;
-    struct { uint8_t* base; } S{ base };
-    ScanArgs A[2], B[2];
-    A[1] = ScanArgs{};
-    B[1] = ScanArgs{};
     bool any_out = false;
     for (int j = 0; j < count; j++) {
-        scan_fill(mode, jobs[j], S.base + off[j], A[j], B[j]);
+        scan_plan(MODE, jobs[j], base + per * (size_t)j, A[j], B[j], A3[j]);
         any_out = any_out || jobs[j].out;
     }
-    ScanArgs A3[2] = { A[0], A[1] };
-    for (int j = 0; j < count; j++)
-        if (!jobs[j].out) A3[j].n = 0;
-    const dim3 g1((uint32_t)nbmax, count), gb(1, count);
-    if (nbmax <= (size_t)SCAN_T) {
-        for (int j = 0; j < count; j++) {
-            A3[j].fused_nb = (uint32_t)((jobs[j].n + SCAN_BLOCK - 1) / SCAN_BLOCK);
-            A3[j].total_out = B[j].bpart;
-            A3[j].n = A[j].n; // also the scans without an output vector run phase 3 (for the total)
-        }
-        if (mode == 0) {
-            k_scan_phase1<0><<<g1, SCAN_T, 0, st>>>(A[0], A[1]);
-            k_scan_phase3<0><<<g1, SCAN_T, 0, st>>>(A3[0], A3[1]);
-        } else {
-            k_scan_phase1<1><<<g1, SCAN_T, 0, st>>>(A[0], A[1]);
-            k_scan_phase3<1><<<g1, SCAN_T, 0, st>>>(A3[0], A3[1]);
-        }
-    } else if (nbmax > (size_t)SCAN_BLOCK) {
+    if (T)
+        if (int rc = T->flush(st)) return rc;
+    const dim3 g1((uint32_t)nb, count), gb(1, count);
+    scan_phase1<MODE>(A, dA, g1, st);
+    if (nb > (size_t)SCAN_BLOCK) {
         // more block totals than one workgroup scans: the scan over them (exclusive, same direction; Horner: multiplier z^SCAN_BLOCK) is a scan of this
-        // kind itself, run on the scratch behind this level's; its grand total lands where the one-workgroup form leaves it (B.bpart)
-        if (mode == 0) k_scan_phase1<0><<<g1, SCAN_T, 0, st>>>(A[0], A[1]);
-        else k_scan_phase1<1><<<g1, SCAN_T, 0, st>>>(A[0], A[1]);
-        for (int j = 0; j < count; j++) {
-            const size_t nb = (jobs[j].n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-            if (nb == 0) continue;
-            if (nb <= (size_t)SCAN_BLOCK) { // the shorter of two jobs may still fit a workgroup: the one-block form, alone in its launch
-                ScanArgs none{};
-                if (mode == 0) {
-                    k_scan_phase1<0><<<dim3(1, 1), SCAN_T, 0, st>>>(B[j], none);
-                    k_scan_phase3<0><<<dim3(1, 1), SCAN_T, 0, st>>>(B[j], none);
-                } else {
-                    k_scan_phase1<1><<<dim3(1, 1), SCAN_T, 0, st>>>(B[j], none);
-                    k_scan_phase3<1><<<dim3(1, 1), SCAN_T, 0, st>>>(B[j], none);
-                }
-                continue;
-            }
-            ScanJob I{};
-            I.in = (const uint64_t*)A[j].bpart;
-            I.out = (uint64_t*)A[j].bcarry;
-            I.n = nb;
-            I.reverse = jobs[j].reverse;
-            I.inclusive = false;
-            I.d_total = (uint64_t*)B[j].bpart;
-            if (mode == 1) I.z = host::fr_pow(jobs[j].z, SCAN_BLOCK);
-            if (int rc = scan_pair_at(mode, &I, 1, S.base + off[j] + scan_scratch_own(jobs[j].n), st)) return rc;
-        }
-        if (any_out) {
-            if (mode == 0) k_scan_phase3<0><<<g1, SCAN_T, 0, st>>>(A3[0], A3[1]);
-            else k_scan_phase3<1><<<g1, SCAN_T, 0, st>>>(A3[0], A3[1]);
-        }
-    } else
-    if (mode == 0) {
-        k_scan_phase1<0><<<g1, SCAN_T, 0, st>>>(A[0], A[1]);
-        k_scan_phase1<0><<<gb, SCAN_T, 0, st>>>(B[0], B[1]);
-        k_scan_phase3<0><<<gb, SCAN_T, 0, st>>>(B[0], B[1]);
-        if (any_out) k_scan_phase3<0><<<g1, SCAN_T, 0, st>>>(A3[0], A3[1]);
-    } else {
-        k_scan_phase1<1><<<g1, SCAN_T, 0, st>>>(A[0], A[1]);
-        k_scan_phase1<1><<<gb, SCAN_T, 0, st>>>(B[0], B[1]);
-        k_scan_phase3<1><<<gb, SCAN_T, 0, st>>>(B[0], B[1]);
-        if (any_out) k_scan_phase3<1><<<g1, SCAN_T, 0, st>>>(A3[0], A3[1]);
+        // kind itself, run on the scratch behind this level's; its grand total lands where the one-workgroup form leaves it (B.bpart).  One job only.
+        ScanJob I{};
+        I.in = (const uint64_t*)A[0].bpart;
+        I.out = (uint64_t*)A[0].bcarry;
+        I.n = nb;
+        I.reverse = jobs[0].reverse;
+        I.inclusive = false;
+        I.d_total = (uint64_t*)B[0].bpart;
+        if (MODE == 1) I.z = host::fr_pow(jobs[0].z, SCAN_BLOCK);
+        if (int rc = scan_issue<MODE>(&I, 1, base + scan_scratch_own(n), nullptr, st)) return rc;
+    } else if (nb > (size_t)SCAN_T) {
+        scan_phase1<MODE>(B, dB, gb, st);
+        scan_phase3<MODE>(B, dB, gb, st);
     }
+    if (nb <= (size_t)SCAN_T || any_out) scan_phase3<MODE>(A3, dA3, g1, st);
     HIPCHK(launch_check());
-    for (int j = 0; j < count; j++)
-        if (jobs[j].d_total && jobs[j].n) HIPCHK(hipMemcpyAsync(jobs[j].d_total, B[j].bpart, 32, hipMemcpyDeviceToDevice, st));
     return BBGPU_OK;
 }
 static int scan_run(int mode, const uint64_t* d_in, uint64_t* d_out, size_t n, bool reverse, bool inclusive, const host::Fr* z, Scratch& S,
                     hipStream_t st, uint64_t* d_total /* optional: 32-byte device slot receiving the full combination */)
 {
     if (n == 0) return BBGPU_OK;
+    if (n > ((size_t)1 << 28)) {
+        set_error("scan of %zu elements: at most 2^28", n);
+        return BBGPU_ERR_SIZE;
+    }
     ScanJob J{};
     J.in = d_in; J.out = d_out; J.n = n; J.reverse = reverse; J.inclusive = inclusive; J.d_total = d_total;
     if (z) J.z = *z;
-    return scan_pair(mode, &J, 1, S, st);
+    if (int rc = S.ensure(scan_scratch_bytes(n) + 64)) return rc;
+    return mode == 0 ? scan_issue<0>(&J, 1, S.base, nullptr, st) : scan_issue<1>(&J, 1, S.base, nullptr, st);
+}
+int scan_lanes(int mode, const ScanJob* jobs, int count, LaneTable& T, Scratch& S, hipStream_t st)
+{
+    if (count < 1) return BBGPU_ERR_ARG;
+    const size_t n = jobs[0].n;
+    for (int j = 0; j < count; j++)
+        if (jobs[j].n != n || n == 0 || n > (size_t)SCAN_BLOCK * SCAN_BLOCK) { // the nested form is not batched
+            set_error("lane-batched scan: one length for all jobs, 1 <= n <= 2^22");
+            return BBGPU_ERR_SIZE;
+        }
+    if (int rc = S.ensure(scan_scratch_bytes(n) * (size_t)count + 64)) return rc;
+    return mode == 0 ? scan_issue<0>(jobs, count, S.base, &T, st) : scan_issue<1>(jobs, count, S.base, &T, st);
 }
 
 int product_scan(const uint64_t* d_in, uint64_t* d_out, size_t n, bool reverse, bool inclusive, Scratch& S, hipStream_t st, uint64_t* d_total)
@@ -1297,20 +1169,16 @@ int divide_by_pseudo_vanishing_lanes(uint64_t* d_coeffs, size_t stride, int lane
     }
     const host::Fr rootN = host::fr_root_of_unity(log2N), wninv = host::fr_inv(host::fr_root_of_unity(log2n));
     const uint32_t blocks = strided_blocks(N);
-    if (lanes > 0)
-        k_divide_vanishing_lanes<<<dim3(blocks, lanes), PT, 0, st>>>((uint32_t*)d_coeffs, stride, (uint32_t)N, k, make_powtab(rootN),
-                                                                    host::limbs_m261(host::fr_from_limbs(FrHostP::GEN5)),
-                                                                    host::limbs_m261(host::fr_pow(rootN, (uint64_t)blocks * PT)), host::limbs_m261(wninv), inv[0],
-                                                                    inv[1], inv[2], inv[3]);
-    else
-        k_divide_vanishing<<<blocks, PT, 0, st>>>((uint32_t*)d_coeffs, (uint32_t)N, k, make_powtab(rootN), host::limbs_m261(host::fr_from_limbs(FrHostP::GEN5)),
-                                                 host::limbs_m261(host::fr_pow(rootN, (uint64_t)blocks * PT)), host::limbs_m261(wninv), inv[0], inv[1], inv[2], inv[3]);
+    k_divide_vanishing_lanes<<<dim3(blocks, lanes), PT, 0, st>>>((uint32_t*)d_coeffs, stride, (uint32_t)N, k, make_powtab(rootN),
+                                                                host::limbs_m261(host::fr_from_limbs(FrHostP::GEN5)),
+                                                                host::limbs_m261(host::fr_pow(rootN, (uint64_t)blocks * PT)), host::limbs_m261(wninv), inv[0],
+                                                                inv[1], inv[2], inv[3]);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
 int divide_by_pseudo_vanishing(uint64_t* d_coeffs, int log2n, int log2N, hipStream_t st)
 {
-    return divide_by_pseudo_vanishing_lanes(d_coeffs, 0, 0, log2n, log2N, st); // lanes = 0: the single-vector kernel
+    return divide_by_pseudo_vanishing_lanes(d_coeffs, 0, 1, log2n, log2N, st); // a single vector is one lane
 }
 
 // compute_lagrange_polynomial_fft(l_1, src = 2^log2n, target = 2^log2N): N resident values; d_tmp: N elements of workspace
@@ -1542,57 +1410,6 @@ int copy_pad_lanes(LaneTable& T, const CopyPadArgs* A, int records, const host::
 int add_inplace_lanes(uint64_t* d_a, size_t stride_a, const uint64_t* d_b, size_t stride_b, size_t n, int lanes, hipStream_t st)
 {
     k_add_inplace_lanes<<<dim3(pw_blocks(n), lanes), PT, 0, st>>>((uint32_t*)d_a, stride_a, (const uint32_t*)d_b, stride_b, (uint32_t)n);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-// the scans of scan_pair_at over a table of jobs: the same phases, grid.y = job.  All jobs have one length, so one grid shape serves them; up to 2^22 elements the scan
-// over the block totals is the fused form (<= SCAN_T blocks) or one workgroup per job.
-int scan_lanes(int mode, const ScanJob* jobs, int count, LaneTable& T, Scratch& S, hipStream_t st)
-{
-    if (count < 1) return BBGPU_ERR_ARG;
-    const size_t n = jobs[0].n, nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    for (int j = 0; j < count; j++)
-        if (jobs[j].n != n || n == 0 || nb > (size_t)SCAN_BLOCK) {
-            set_error("lane-batched scan: one length for all jobs, 1 <= n <= 2^22");
-            return BBGPU_ERR_SIZE;
-        }
-    const size_t per = scan_scratch_bytes(n);
-    if (int rc = S.ensure(per * (size_t)count + 64)) return rc;
-    ScanArgs *A = nullptr, *B = nullptr, *A3 = nullptr;
-    const ScanArgs *dA = nullptr, *dB = nullptr, *dA3 = nullptr;
-    if (int rc = T.push(count, &A, &dA)) return rc;
-    if (int rc = T.push(count, &B, &dB)) return rc;
-    if (int rc = T.push(count, &A3, &dA3)) return rc;
-    const bool fused = nb <= (size_t)SCAN_T;
-    for (int j = 0; j < count; j++) {
-        scan_fill(mode, jobs[j], S.base + per * (size_t)j, A[j], B[j]);
-        if (jobs[j].d_total) B[j].bpart = (uint32_t*)jobs[j].d_total; // one element: the grand total, written where the caller wants it
-        A3[j] = A[j];
-        if (!jobs[j].out) A3[j].n = 0;
-        if (fused) {
-            A3[j].fused_nb = (uint32_t)nb;
-            A3[j].total_out = B[j].bpart;
-            A3[j].n = A[j].n;
-        }
-    }
-    if (int rc = T.flush(st)) return rc;
-    const dim3 g1((uint32_t)nb, count), gb(1, count);
-    if (mode == 0) {
-        k_scan_phase1_tab<0><<<g1, SCAN_T, 0, st>>>(dA);
-        if (!fused) {
-            k_scan_phase1_tab<0><<<gb, SCAN_T, 0, st>>>(dB);
-            k_scan_phase3_tab<0><<<gb, SCAN_T, 0, st>>>(dB);
-        }
-        k_scan_phase3_tab<0><<<g1, SCAN_T, 0, st>>>(dA3);
-    } else {
-        k_scan_phase1_tab<1><<<g1, SCAN_T, 0, st>>>(dA);
-        if (!fused) {
-            k_scan_phase1_tab<1><<<gb, SCAN_T, 0, st>>>(dB);
-            k_scan_phase3_tab<1><<<gb, SCAN_T, 0, st>>>(dB);
-        }
-        k_scan_phase3_tab<1><<<g1, SCAN_T, 0, st>>>(dA3);
-    }
     HIPCHK(launch_check());
     return BBGPU_OK;
 }

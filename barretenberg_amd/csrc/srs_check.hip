@@ -11,15 +11,6 @@
 
 namespace bbgpu {
 
-#define HIPCHK(x)                                                                                                      \
-    do {                                                                                                               \
-        hipError_t e_ = (x);                                                                                           \
-        if (e_ != hipSuccess) {                                                                                        \
-            set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));                                \
-            return BBGPU_ERR_HIP;                                                                                      \
-        }                                                                                                              \
-    } while (0)
-
 namespace {
 
 constexpr int CT = 256; // threads per workgroup, both kernels

@@ -15,15 +15,6 @@
 
 namespace bbgpu {
 
-#define HIPCHK(x)                                                                                                      \
-    do {                                                                                                               \
-        hipError_t e_ = (x);                                                                                           \
-        if (e_ != hipSuccess) {                                                                                        \
-            set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));                                \
-            return BBGPU_ERR_HIP;                                                                                      \
-        }                                                                                                              \
-    } while (0)
-
 namespace {
 
 constexpr int LT = 64;  // threads per workgroup of the ladder kernels: one wave, as k_srs_update

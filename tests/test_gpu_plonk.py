@@ -96,6 +96,30 @@ def test_scans_and_evaluate_vs_oracle(gpu, torch, oracle, n):
     assert np.array_equal(host(d3), P.batch_invert(v))
 
 
+@pytest.mark.parametrize("n", [1 << 19, (1 << 19) + 1])
+def test_scans_where_the_fused_form_ends_vs_oracle(gpu, torch, oracle, n):
+    """2^19 elements leave 256 block totals, the most that every workgroup of the carry pass scans for itself (two launches); one element more leaves
+    257, the first length whose block totals get a level of their own (four launches), and a last block of one element.  Every output against the
+    big-integer oracle, inputs partly non-canonical.  The oracle takes about a second per scan of this length, so 2^19 + 1 is checked in full and 2^19
+    in the suffix product and the opening."""
+    full = n > 1 << 19
+    v = noncanonical(oracle.random_scalars(0xF5ED + n, n), FR_MODULUS)
+    z = oracle.random_scalars(0xF5EE + n, 1)[0]
+    dv = dev(torch, v)
+    out = torch.zeros_like(dv)
+    for reverse, inclusive in ((True, False), (False, True)) if full else ((True, False),):
+        gpu.product_scan_device(dv.data_ptr(), out.data_ptr(), n, reverse, inclusive)
+        assert np.array_equal(host(out), P.product_scan(v, reverse, inclusive)), (n, reverse, inclusive)
+    f = gpu.compute_kate_opening_coefficients_device(dv.data_ptr(), out.data_ptr(), n, z)
+    want, wf = P.kate_opening(v, z)
+    assert np.array_equal(host(out), want) and np.array_equal(f, wf)
+    d2 = dv.clone()  # in place
+    f2 = gpu.compute_kate_opening_coefficients_device(d2.data_ptr(), d2.data_ptr(), n, z)
+    assert np.array_equal(host(d2), want) and np.array_equal(f2, wf)
+    if full:
+        assert np.array_equal(gpu.evaluate_device(dv.data_ptr(), n, z), P.evaluate(v, z))
+
+
 @pytest.mark.parametrize("log2n", [2, 5, 10])
 def test_domain_helpers_vs_oracle(gpu, torch, oracle, log2n):
     n = 1 << log2n

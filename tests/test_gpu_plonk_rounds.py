@@ -298,6 +298,30 @@ def test_scan_jobs(gpu, oracle, mode, n, count):
                     same(got[-1], PolyOracle.mont(totals), "totals, flags %d" % flags)
 
 
+@pytest.mark.parametrize("mode", (0, 1))
+def test_scan_jobs_past_the_fused_form(gpu, oracle, mode):
+    """2^19 + 1 elements leave 257 block totals per job, one more than the carry pass scans for itself: the totals get a level of their own, one
+    workgroup per job, and the last block holds one element.  Two jobs (the entry takes 2^22 elements), vector and total: suffix products without the
+    element itself, and inclusive Horner sums."""
+    n, count = (1 << 19) + 1, 2
+    v = _scan_inputs(oracle, mode, n, count)
+    ch, chm = cases.challenges(oracle, seed_of(19, mode), count, 1)
+    p = plain_lanes(v, count)
+    if mode == 0:
+        flags = 1 | 12
+        want = np.concatenate([PolyOracle.product_scan(v.reshape(count, n, 4)[j], True, False) for j in range(count)])
+        totals = [cases.product_of(p[j]) for j in range(count)]
+    else:
+        flags = 2 | 12
+        sums = [cases.horner_suffix(p[j], ch[j][0], True) for j in range(count)]
+        want = PolyOracle.mont([x for s in sums for x in s])
+        totals = [cases.evaluate(p[j], ch[j][0]) for j in range(count)]
+    got = gpu.selftest_plonk_round("scan", count, n, [v], consts=chm if mode else None, params=(mode, flags))
+    assert len(got) == 2
+    same(got[0], want, "scan, mode %d" % mode)
+    same(got[1], PolyOracle.mont(totals), "totals, mode %d" % mode)
+
+
 @pytest.mark.parametrize("count", COUNTS)
 @pytest.mark.parametrize("n", SCAN_LENGTHS)
 def test_evaluate_jobs(gpu, oracle, n, count):
