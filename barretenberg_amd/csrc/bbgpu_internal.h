@@ -136,11 +136,7 @@ int srs_check_scalars(const uint64_t seed[4], size_t count, uint64_t* d_out, hip
 int srs_lagrange_rows(const uint32_t* d_in, size_t n, int log2n, const uint32_t winv_m261[9], const uint64_t ninv_plain[4], SrsCurveFindings* d_find,
                       SrsCurveFindings* found, uint32_t** d_out_rows, uint64_t* host_table_out, hipStream_t st, float* ms3 = nullptr);
 
-// plonk_verify.hip: the device parts of bbgpu_plonk_verify_batch that are not an MSM
-struct VerifyDeviceKey {
-    uint32_t log2n, widgets, num_vk;
-    uint32_t root[9], root_inv[9], n_inv[9]; // omega, omega^-1, 1 / n: Montgomery-261, 29-bit limbs (host_fr.hpp limbs_m261)
-};
+// plonk_verify.hip: the device parts of a verify call (bbgpu_plonk_verify_batch, bbgpu_plonk_verify_multi) that are not an MSM
 struct VerifyDeviceBuffers {
     const uint64_t* proofs; // count x BBGPU_PLONK_PROOF_WORDS
     uint32_t *rows_own, *rows_other; // count x 9 and count x 2 resident rows (64 bytes)
@@ -148,22 +144,27 @@ struct VerifyDeviceBuffers {
     uint64_t* shared;                // [shared point][proof] x 4 words: rho_j s_jk
     uint32_t* status;                // count
 };
-int plonk_verify_terms(const VerifyDeviceKey& key, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B, hipStream_t st);
-int plonk_verify_fold(const uint64_t* d_shared, size_t count, size_t m, int num_shared, uint32_t skip_mask, uint64_t* d_out, hipStream_t st);
-// bbgpu_plonk_verify_multi: what a thread of k_verify_terms<true> and a workgroup of k_verify_fold_mixed read about one circuit of the call.  192 bytes
-// (a multiple of 64: the table sits in the staging buffer before the shared rows); the three constants 12 words apart, each read by three 16-byte loads
+// What the kernels read about one circuit: a verifier handle keeps it, a call of one circuit passes it as a kernel argument, a call of several lays
+// them out as a table on the device.  192 bytes (a multiple of 64: the table sits in the staging buffer before the shared rows); the three constants 12
+// words apart, each read from the table by three 16-byte loads
 struct VerifyRecord {
     uint32_t log2n, widgets, num_vk;
-    uint32_t base;      // the circuit's first shared row among the rows (and scalars) of A
+    uint32_t base;      // the circuit's first shared row among the rows (and scalars) of A: set per call
     uint32_t skip_mask; // key points at infinity: their scalars are written as zero
     uint32_t pad[7];
-    uint32_t root[12], root_inv[12], n_inv[12]; // Montgomery-261, 29-bit limbs in the first nine words
+    uint32_t root[12], root_inv[12], n_inv[12]; // omega, omega^-1, 1 / n: Montgomery-261, 29-bit limbs (host_fr.hpp limbs_m261) in the first nine words
 };
 static_assert(sizeof(VerifyRecord) == 192, "VerifyRecord: 192 bytes");
-int plonk_verify_terms_mixed(const VerifyRecord* d_records, const uint32_t* d_circuit, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B,
-                             hipStream_t st);
-int plonk_verify_fold_mixed(const uint64_t* d_shared, const uint32_t* d_circuit, const VerifyRecord* d_records, int num_circuits, int max_shared, size_t count,
-                            size_t m, uint64_t* d_out, hipStream_t st);
+// the circuits of one call: the one record (host memory), or, with `one` null, the device table, proof j's index into it at d_circuit[j], and the
+// largest num_vk + 1 among the records
+struct VerifyCircuits {
+    const VerifyRecord* one = nullptr;
+    const VerifyRecord* d_records = nullptr;
+    const uint32_t* d_circuit = nullptr;
+    int num_circuits = 1, max_shared = 0;
+};
+int plonk_verify_terms(const VerifyCircuits& C, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B, hipStream_t st);
+int plonk_verify_fold(const VerifyCircuits& C, const uint64_t* d_shared, size_t count, size_t m, uint64_t* d_out, hipStream_t st); // the first m proofs
 
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);

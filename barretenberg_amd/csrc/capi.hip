@@ -2059,6 +2059,14 @@ static int verify_args(const uint64_t* proofs, size_t count, int flags, const ui
     return BBGPU_OK;
 }
 
+// the call's seed: the caller's, or drawn from the operating system
+static int verify_seed(const uint64_t* seed, uint64_t sd[4])
+{
+    if (host::srs_check_seed(seed, sd)) return BBGPU_OK;
+    set_error("PLONK verify: the operating system gave no randomness");
+    return BBGPU_ERR_STATE;
+}
+
 int bbgpu_host_plonk_verify_batch(size_t n, int widgets, const uint64_t* vk, const uint64_t g2_x[16], const uint64_t* proofs, size_t count,
                                   const uint64_t seed[4], int flags, uint32_t* status, bbgpu_plonk_verify_report* out)
 {
@@ -2070,10 +2078,7 @@ int bbgpu_host_plonk_verify_batch(size_t n, int widgets, const uint64_t* vk, con
         return rc;
     }
     uint64_t sd[4];
-    if (!host::srs_check_seed(seed, sd)) {
-        set_error("PLONK verify: the operating system gave no randomness");
-        return BBGPU_ERR_STATE;
-    }
+    if (int rc = verify_seed(seed, sd)) return rc;
     return host::verify_host(K, proofs, count, sd, flags, status, out);
 }
 
@@ -2115,11 +2120,8 @@ int bbgpu_host_plonk_verify_multi(const bbgpu_plonk_verify_key* keys, int num_ke
         }
     }
     uint64_t sd[4];
-    if (!host::srs_check_seed(seed, sd)) {
-        set_error("PLONK verify: the operating system gave no randomness");
-        return BBGPU_ERR_STATE;
-    }
-    return host::verify_host_multi(K, g2_x, circuit, proofs, count, sd, flags, status, out);
+    if (int rc = verify_seed(seed, sd)) return rc;
+    return host::verify_host_multi(K.data(), K.size(), g2_x, circuit, proofs, count, sd, flags, status, out);
 }
 
 /* ---- SRS ---- */
@@ -2775,16 +2777,17 @@ int bbgpu_msm_g1_device_async(int srs_handle, size_t offset, const uint64_t* d_s
     return rc ? rc : commit_ticket(t);
 }
 
-/* ---- bbgpu_plonk_verify_batch: verifier handles, and the GPU entry (the host twin and the argument checks are further up) ---- */
+/* ---- bbgpu_plonk_verify_batch, bbgpu_plonk_verify_multi: verifier handles, and the GPU entries over one driver (the host twins and the argument checks
+   are further up) ---- */
 namespace {
 struct VerifierHandle {
     host::VerifyKey K;
-    VerifyDeviceKey D;
+    VerifyRecord rec = {};                             // what the kernels read; base 0 (a call of several circuits sets it in its own copy)
     uint64_t shared_rows[host::VERIFY_MAX_SHARED * 8]; // the key's points and the generator as resident rows: Montgomery-261, canonical
-    uint32_t skip_mask = 0;                            // key points at infinity: a stand-in row, scalar zero
 };
 std::vector<VerifierHandle*> g_verifiers; // under g_mu; never shrinks: a handle is an index
 double g_verify_ms[5] = { 0, 0, 0, 0, 0 }; // bbgpu_plonk_verify_last_timing: wall ms of the last call between the synchronisations it makes anyway
+VerifierHandle* verifier_at(int v) { return v >= 0 && v < (int)g_verifiers.size() ? g_verifiers[v] : nullptr; } // null: no such handle
 } // namespace
 
 int bbgpu_plonk_verifier_create(size_t n, int widgets, const uint64_t vk[BBGPU_PLONK_VK_WORDS], const uint64_t g2_x[16])
@@ -2798,19 +2801,17 @@ int bbgpu_plonk_verifier_create(size_t n, int widgets, const uint64_t vk[BBGPU_P
         return rc;
     }
     const host::VerifyKey& K = H->K;
-    H->D.log2n = (uint32_t)K.log2n;
-    H->D.widgets = (uint32_t)K.widgets;
-    H->D.num_vk = (uint32_t)K.num_vk;
+    H->rec.log2n = (uint32_t)K.log2n;
+    H->rec.widgets = (uint32_t)K.widgets;
+    H->rec.num_vk = (uint32_t)K.num_vk;
     const Limbs9 root = host::limbs_m261(K.root), root_inv = host::limbs_m261(K.root_inv), n_inv = host::limbs_m261(K.n_inv);
-    for (int i = 0; i < NL; i++) {
-        H->D.root[i] = root.d[i];
-        H->D.root_inv[i] = root_inv.d[i];
-        H->D.n_inv[i] = n_inv.d[i];
-    }
+    memcpy(H->rec.root, root.d, sizeof root.d);
+    memcpy(H->rec.root_inv, root_inv.d, sizeof root_inv.d);
+    memcpy(H->rec.n_inv, n_inv.d, sizeof n_inv.d);
     uint64_t pts[host::VERIFY_MAX_SHARED * 8];
     host::verify_shared_points(K, pts);
     for (int k = 0; k < K.num_shared(); k++) {
-        if (k < K.num_vk && K.vk_inf[k]) H->skip_mask |= 1u << k;
+        if (k < K.num_vk && K.vk_inf[k]) H->rec.skip_mask |= 1u << k; // a stand-in row, scalar zero
         for (int c = 0; c < 2; c++) { // x 2^256 -> x 2^261, canonical
             host::Fq v;
             memcpy(v.d, pts + 8 * k + 4 * c, 32);
@@ -2831,7 +2832,7 @@ int bbgpu_plonk_verifier_create(size_t n, int widgets, const uint64_t vk[BBGPU_P
 int bbgpu_plonk_verifier_destroy(int verifier)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (verifier < 0 || verifier >= (int)g_verifiers.size() || !g_verifiers[verifier]) {
+    if (!verifier_at(verifier)) {
         set_error("unknown verifier handle %d", verifier);
         return BBGPU_ERR_ARG;
     }
@@ -2861,110 +2862,21 @@ static int verify_two_msms(const SrsEntry& ea, const SrsEntry& eb, uint64_t* d_s
     return bbgpu_msm_g1_wait(tb, b12);
 }
 
-int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count, const uint64_t seed[4], int flags, uint32_t* status,
-                             bbgpu_plonk_verify_report* out)
+// Both entries behind their argument checks: proof j is of H[circuit[j]], every handle under H[0]'s g2_x.  A call of one circuit (G == 1: circuit[] is
+// not read) passes that circuit's record to the kernels as an argument; a call of several lays circuit[] and the records out on the device.
+static int verify_run(const VerifierHandle* const* H, size_t G, const uint32_t* circuit, const uint64_t* proofs, size_t count, const uint64_t seed[4], int flags,
+                      uint32_t* status, bbgpu_plonk_verify_report* out)
 {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    // argument errors before a device is bound
-    if (int rc = verify_args(proofs, count, flags, status, out)) return rc;
-    if (verifier < 0 || verifier >= (int)g_verifiers.size() || !g_verifiers[verifier]) {
-        set_error("unknown verifier handle %d", verifier);
-        return BBGPU_ERR_ARG;
-    }
-    if (int rc = ensure_init()) return rc;
-    const VerifierHandle& H = *g_verifiers[verifier];
-    const double t_begin = now_ms();
-    for (double& v : g_verify_ms) v = 0;
-    uint64_t sd[4];
-    if (!host::srs_check_seed(seed, sd)) {
-        set_error("PLONK verify: the operating system gave no randomness");
-        return BBGPU_ERR_STATE;
-    }
-    host::verify_report_init(out, count, sd);
-    // one staging buffer, every part a multiple of 64 bytes: the proofs | rows of A: shared, then nine per proof | rows of B: two per proof |
-    // scalars of A, of B | the shared terms [point][proof] | the statuses
-    const size_t S = (size_t)H.K.num_shared(), na = S + host::VERIFY_OWN * count, nb = 2 * count;
-    auto up64 = [](size_t b) { return (b + 63) & ~(size_t)63; };
-    const size_t o_rows_a = up64(count * BBGPU_PLONK_PROOF_WORDS * 8), o_rows_b = o_rows_a + na * 64, o_scal_a = o_rows_b + nb * 64,
-                 o_scal_b = o_scal_a + up64(na * 32), o_shared = o_scal_b + nb * 32, o_status = o_shared + up64(S * count * 32),
-                 total = o_status + up64(count * 4);
-    if (int rc = grow(&ctx().d_verify, &ctx().verify_cap, total)) return rc;
-    uint8_t* base = reinterpret_cast<uint8_t*>(ctx().d_verify);
-    uint32_t *d_rows_a = reinterpret_cast<uint32_t*>(base + o_rows_a), *d_rows_b = reinterpret_cast<uint32_t*>(base + o_rows_b);
-    uint64_t *d_scal_a = reinterpret_cast<uint64_t*>(base + o_scal_a), *d_scal_b = reinterpret_cast<uint64_t*>(base + o_scal_b);
-    uint64_t* d_shared = reinterpret_cast<uint64_t*>(base + o_shared);
-    uint32_t* d_status = reinterpret_cast<uint32_t*>(base + o_status);
-    const hipStream_t st = ctx().stream;
-    if (int rc = host_to_device(base, proofs, count * BBGPU_PLONK_PROOF_WORDS * 8, st)) return rc;
-    HIPCHK(h2d_async(d_rows_a, H.shared_rows, S * 64, st));
-    VerifyDeviceBuffers B;
-    B.proofs = reinterpret_cast<const uint64_t*>(base);
-    B.rows_own = d_rows_a + S * 16;
-    B.rows_other = d_rows_b;
-    B.scal_own = d_scal_a + S * 4;
-    B.scal_other = d_scal_b;
-    B.shared = d_shared;
-    B.status = d_status;
-    if (int rc = plonk_verify_terms(H.D, sd, count, B, st)) return rc;
-    HIPCHK(d2h_async(status, d_status, count * 4, st));
-    HIPCHK(hipStreamSynchronize(st));
-    g_verify_ms[1] = now_ms() - t_begin;
-    host::verify_count_status(out, status);
-    // A and B: two tickets in flight over transient tables (the rows the kernel wrote; no window tables), the scalars where the kernels left them
-    SrsEntry ea{}, eb{};
-    ea.n = na;
-    ea.d_srs = d_rows_a;
-    eb.n = nb;
-    eb.d_srs = d_rows_b;
-    ea.live = eb.live = true;
-    const int rc_tail = host::verify_tail(out, H.K.g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
-        const double t_fold = now_ms();
-        if (int rc = plonk_verify_fold(d_shared, count, m, (int)S, H.skip_mask, d_scal_a, st)) return rc;
-        HIPCHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
-        const double t_msm = now_ms();
-        g_verify_ms[2] += t_msm - t_fold;
-        if (int rc = verify_two_msms(ea, eb, d_scal_a, d_scal_b, S + host::VERIFY_OWN * m, 2 * m, a12, b12)) return rc;
-        g_verify_ms[3] += now_ms() - t_msm;
-        return BBGPU_OK;
-    });
-    g_verify_ms[0] = now_ms() - t_begin;
-    g_verify_ms[4] = g_verify_ms[0] - g_verify_ms[1] - g_verify_ms[2] - g_verify_ms[3]; // the pairing checks (and the normalisations around them)
-    return rc_tail;
-}
-
-int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint32_t* circuit, const uint64_t* proofs, size_t count, const uint64_t seed[4],
-                             int flags, uint32_t* status, bbgpu_plonk_verify_report* out)
-{
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    // argument errors before a device is bound
-    if (int rc = verify_multi_args(verifiers, num_verifiers, "verifiers", circuit, proofs, count, flags, status, out)) return rc;
-    const size_t G = (size_t)num_verifiers;
-    const VerifierHandle* H[BBGPU_PLONK_VERIFY_MAX_CIRCUITS];
-    for (size_t c = 0; c < G; c++) {
-        const int v = verifiers[c];
-        if (v < 0 || v >= (int)g_verifiers.size() || !g_verifiers[v]) {
-            set_error("unknown verifier handle %d (verifiers[%zu])", v, c);
-            return BBGPU_ERR_ARG;
-        }
-        H[c] = g_verifiers[v];
-        if (memcmp(H[c]->K.g2_x, H[0]->K.g2_x, sizeof H[0]->K.g2_x) != 0) {
-            set_error("PLONK verify: verifiers[%zu] (handle %d) and verifiers[0] (handle %d) hold different g2_x: one call, one reference string", c, v,
-                      verifiers[0]);
-            return BBGPU_ERR_ARG;
-        }
-    }
     if (int rc = ensure_init()) return rc;
     const double t_begin = now_ms();
     for (double& v : g_verify_ms) v = 0;
     uint64_t sd[4];
-    if (!host::srs_check_seed(seed, sd)) {
-        set_error("PLONK verify: the operating system gave no randomness");
-        return BBGPU_ERR_STATE;
-    }
+    if (int rc = verify_seed(seed, sd)) return rc;
     host::verify_report_init(out, count, sd);
+    const bool uniform = G == 1;
     // one staging buffer, every part a multiple of 64 bytes: the proofs | circuit[] | the records | rows of A: every circuit's shared rows, then nine
-    // per proof | rows of B: two per proof | scalars of A, of B | the shared terms [slot][proof] | the statuses.  circuit[], the records and the shared
-    // rows are neighbours there because they arrive in one copy.
+    // per proof | rows of B: two per proof | scalars of A, of B | the shared terms [slot][proof] | the statuses.  circuit[], the records (both empty when
+    // the call is uniform) and the shared rows are neighbours there because they arrive in one copy.
     size_t T = 0, S_max = 0; // shared rows in all, the most of one circuit
     for (size_t c = 0; c < G; c++) {
         T += (size_t)H[c]->K.num_shared();
@@ -2972,44 +2884,45 @@ int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint
     }
     const size_t na = T + host::VERIFY_OWN * count, nb = 2 * count;
     auto up64 = [](size_t b) { return (b + 63) & ~(size_t)63; };
-    const size_t o_circuit = up64(count * BBGPU_PLONK_PROOF_WORDS * 8), o_records = o_circuit + up64(count * 4), o_rows_a = o_records + G * sizeof(VerifyRecord),
-                 o_rows_b = o_rows_a + na * 64, o_scal_a = o_rows_b + nb * 64, o_scal_b = o_scal_a + up64(na * 32), o_shared = o_scal_b + nb * 32,
-                 o_status = o_shared + up64(S_max * count * 32), total = o_status + up64(count * 4);
+    const size_t o_circuit = up64(count * BBGPU_PLONK_PROOF_WORDS * 8), o_records = o_circuit + (uniform ? 0 : up64(count * 4)),
+                 o_rows_a = o_records + (uniform ? 0 : G * sizeof(VerifyRecord)), o_rows_b = o_rows_a + na * 64, o_scal_a = o_rows_b + nb * 64,
+                 o_scal_b = o_scal_a + up64(na * 32), o_shared = o_scal_b + nb * 32, o_status = o_shared + up64(S_max * count * 32),
+                 total = o_status + up64(count * 4);
     const size_t head_bytes = o_rows_a + T * 64 - o_circuit;
     static_assert(BBGPU_PLONK_VERIFY_MAX_BATCH * 4 + BBGPU_PLONK_VERIFY_MAX_CIRCUITS * (sizeof(VerifyRecord) + host::VERIFY_MAX_SHARED * 64) <= Context::HOST_CHUNK,
                   "circuit[], the records and the shared rows fit one pinned staging buffer");
     if (int rc = grow(&ctx().d_verify, &ctx().verify_cap, total)) return rc;
     uint8_t* base = reinterpret_cast<uint8_t*>(ctx().d_verify);
-    const uint32_t* d_circuit = reinterpret_cast<const uint32_t*>(base + o_circuit);
-    const VerifyRecord* d_records = reinterpret_cast<const VerifyRecord*>(base + o_records);
     uint32_t *d_rows_a = reinterpret_cast<uint32_t*>(base + o_rows_a), *d_rows_b = reinterpret_cast<uint32_t*>(base + o_rows_b);
     uint64_t *d_scal_a = reinterpret_cast<uint64_t*>(base + o_scal_a), *d_scal_b = reinterpret_cast<uint64_t*>(base + o_scal_b);
     uint64_t* d_shared = reinterpret_cast<uint64_t*>(base + o_shared);
     uint32_t* d_status = reinterpret_cast<uint32_t*>(base + o_status);
+    VerifyCircuits C;
+    if (uniform) {
+        C.one = &H[0]->rec;
+    } else {
+        C.d_circuit = reinterpret_cast<const uint32_t*>(base + o_circuit);
+        C.d_records = reinterpret_cast<const VerifyRecord*>(base + o_records);
+        C.num_circuits = (int)G;
+        C.max_shared = (int)S_max;
+    }
     const hipStream_t st = ctx().stream;
     if (int rc = host_to_device(base, proofs, count * BBGPU_PLONK_PROOF_WORDS * 8, st)) return rc;
     {
-        // built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy
+        // the head, built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy
         if (int rc = host_stage_ensure()) return rc;
         const int kb = (int)(ctx().h_stage_next++ % Context::HOST_RING);
         HIPCHK(hipEventSynchronize(ctx().h_stage_free[kb]));
         uint8_t* h = static_cast<uint8_t*>(ctx().h_stage[kb]);
-        memset(h, 0, o_rows_a - o_circuit);
-        memcpy(h, circuit, count * 4);
+        memset(h, 0, o_records - o_circuit);
+        if (!uniform) memcpy(h, circuit, count * 4);
         VerifyRecord* rec = reinterpret_cast<VerifyRecord*>(h + (o_records - o_circuit));
         uint8_t* rows = h + (o_rows_a - o_circuit);
         size_t at = 0;
         for (size_t c = 0; c < G; c++) {
-            const VerifyDeviceKey& D = H[c]->D;
-            rec[c].log2n = D.log2n;
-            rec[c].widgets = D.widgets;
-            rec[c].num_vk = D.num_vk;
-            rec[c].base = (uint32_t)at;
-            rec[c].skip_mask = H[c]->skip_mask;
-            for (int i = 0; i < NL; i++) {
-                rec[c].root[i] = D.root[i];
-                rec[c].root_inv[i] = D.root_inv[i];
-                rec[c].n_inv[i] = D.n_inv[i];
+            if (!uniform) {
+                rec[c] = H[c]->rec;
+                rec[c].base = (uint32_t)at;
             }
             memcpy(rows + at * 64, H[c]->shared_rows, (size_t)H[c]->K.num_shared() * 64);
             at += (size_t)H[c]->K.num_shared();
@@ -3025,11 +2938,12 @@ int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint
     B.scal_other = d_scal_b;
     B.shared = d_shared;
     B.status = d_status;
-    if (int rc = plonk_verify_terms_mixed(d_records, d_circuit, sd, count, B, st)) return rc;
+    if (int rc = plonk_verify_terms(C, sd, count, B, st)) return rc;
     HIPCHK(d2h_async(status, d_status, count * 4, st));
     HIPCHK(hipStreamSynchronize(st));
     g_verify_ms[1] = now_ms() - t_begin;
     host::verify_count_status(out, status);
+    // A and B: two tickets in flight over transient tables (the rows the kernel wrote; no window tables), the scalars where the kernels left them
     SrsEntry ea{}, eb{};
     ea.n = na;
     ea.d_srs = d_rows_a;
@@ -3038,7 +2952,7 @@ int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint
     ea.live = eb.live = true;
     const int rc_tail = host::verify_tail(out, H[0]->K.g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
         const double t_fold = now_ms();
-        if (int rc = plonk_verify_fold_mixed(d_shared, d_circuit, d_records, (int)G, (int)S_max, count, m, d_scal_a, st)) return rc;
+        if (int rc = plonk_verify_fold(C, d_shared, count, m, d_scal_a, st)) return rc;
         HIPCHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
         const double t_msm = now_ms();
         g_verify_ms[2] += t_msm - t_fold;
@@ -3047,8 +2961,43 @@ int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint
         return BBGPU_OK;
     });
     g_verify_ms[0] = now_ms() - t_begin;
-    g_verify_ms[4] = g_verify_ms[0] - g_verify_ms[1] - g_verify_ms[2] - g_verify_ms[3];
+    g_verify_ms[4] = g_verify_ms[0] - g_verify_ms[1] - g_verify_ms[2] - g_verify_ms[3]; // the pairing checks (and the normalisations around them)
     return rc_tail;
+}
+
+int bbgpu_plonk_verify_batch(int verifier, const uint64_t* proofs, size_t count, const uint64_t seed[4], int flags, uint32_t* status,
+                             bbgpu_plonk_verify_report* out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    if (int rc = verify_args(proofs, count, flags, status, out)) return rc;
+    const VerifierHandle* H = verifier_at(verifier);
+    if (!H) {
+        set_error("unknown verifier handle %d", verifier);
+        return BBGPU_ERR_ARG;
+    }
+    return verify_run(&H, 1, nullptr, proofs, count, seed, flags, status, out);
+}
+
+int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint32_t* circuit, const uint64_t* proofs, size_t count, const uint64_t seed[4],
+                             int flags, uint32_t* status, bbgpu_plonk_verify_report* out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    if (int rc = verify_multi_args(verifiers, num_verifiers, "verifiers", circuit, proofs, count, flags, status, out)) return rc;
+    const VerifierHandle* H[BBGPU_PLONK_VERIFY_MAX_CIRCUITS];
+    for (int c = 0; c < num_verifiers; c++) {
+        if (!(H[c] = verifier_at(verifiers[c]))) {
+            set_error("unknown verifier handle %d (verifiers[%d])", verifiers[c], c);
+            return BBGPU_ERR_ARG;
+        }
+        if (memcmp(H[c]->K.g2_x, H[0]->K.g2_x, sizeof H[0]->K.g2_x) != 0) {
+            set_error("PLONK verify: verifiers[%d] (handle %d) and verifiers[0] (handle %d) hold different g2_x: one call, one reference string", c, verifiers[c],
+                      verifiers[0]);
+            return BBGPU_ERR_ARG;
+        }
+    }
+    return verify_run(H, (size_t)num_verifiers, circuit, proofs, count, seed, flags, status, out);
 }
 
 int bbgpu_plonk_verify_last_timing(double ms_out[5])

@@ -2,8 +2,8 @@
 // (plonk_verify.hip, capi.hip) shares with it: the handle's key, the verdict on its points, the multipliers, the pairing tail with its bisection.
 // The per-proof work restates waffle::Verifier::verify_proof (verifier.cpp:55-355) over challenge.hpp, linearizer.hpp,
 // polynomial_arithmetic.cpp:594-626 and the four widgets' append_scalar_multiplication_inputs / compute_batch_evaluation_contribution; where the
-// reference ends in two pairings per proof (:357-379) a batch of proofs of ONE circuit (verify_host; of several under one x G2: verify_host_multi) is folded with multipliers rho_j into two sums and one
-// product of two pairings, as bbgpu_srs_check folds its row pairs (host_srs_check.hpp).  Product code, no oracle/; no HIP call, no lock.
+// reference ends in two pairings per proof (:357-379) a batch of proofs of the circuits under one x G2 (verify_host_multi; of ONE circuit: verify_host, the
+// same with one key) is folded with multipliers rho_j into two sums and one product of two pairings, as bbgpu_srs_check folds its row pairs (host_srs_check.hpp).  Product code, no oracle/; no HIP call, no lock.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -347,77 +347,30 @@ static inline void verify_own_point(const uint64_t* p, uint64_t out[8])
     memcpy(out + 4, y.d, 32);
 }
 
-// bbgpu_host_plonk_verify_batch behind its argument checks
-static inline int verify_host(const VerifyKey& K, const uint64_t* proofs, size_t count, const uint64_t seed[4], int flags, uint32_t* status,
-                              bbgpu_plonk_verify_report* R)
-{
-    verify_report_init(R, count, seed);
-    const int S = K.num_shared();
-    std::vector<VerifyTerms> terms(count);
-    // the sums' tables: [shared][own of proof 0][own of proof 1] ... and [PI_Z_OMEGA, PI_Z] per proof
-    std::vector<uint64_t> pts_a((size_t)(S + VERIFY_OWN * count) * 8), pts_b(2 * count * 8);
-    verify_shared_points(K, pts_a.data());
-    fallback_parallel(count, 4, [&](size_t lo, size_t hi) {
-        for (size_t j = lo; j < hi; j++) {
-            uint64_t rho[4];
-            srs_check_rho(seed, j, rho);
-            const uint64_t* pw = proofs + BBGPU_PLONK_PROOF_WORDS * j;
-            verify_terms(K, pw, rho, &terms[j]);
-            status[j] = terms[j].status;
-            for (int i = 0; i < VERIFY_OWN; i++) {
-                uint64_t* o = &pts_a[(size_t)(S + VERIFY_OWN * j + i) * 8];
-                if (terms[j].status) verify_own_point(pts_a.data() + 8 * (S - 1), o); // never read by a sum (scalar zero); any finite point
-                else verify_own_point(pw + 8 * i, o);
-            }
-            for (int i = 0; i < 2; i++) {
-                uint64_t* o = &pts_b[(2 * j + i) * 8];
-                if (terms[j].status) verify_own_point(pts_a.data() + 8 * (S - 1), o);
-                else verify_own_point(pw + 8 * (i == 0 ? VP_PI_Z_OMEGA : VP_PI_Z), o);
-            }
-        }
-    });
-    verify_count_status(R, status);
-    std::vector<uint64_t> sc_a((size_t)(S + VERIFY_OWN * count) * 4), sc_b(2 * count * 4);
-    for (size_t j = 0; j < count; j++) {
-        memcpy(&sc_a[(size_t)(S + VERIFY_OWN * j) * 4], terms[j].own, VERIFY_OWN * 32);
-        memcpy(&sc_b[2 * j * 4], terms[j].other, 64);
-    }
-    return verify_tail(R, K.g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) {
-        for (int k = 0; k < S; k++) {
-            Fr acc = fr_zero();
-            if (k == K.num_vk || !K.vk_inf[k])
-                for (size_t j = 0; j < m; j++) acc = fr_add(acc, terms[j].shared[k]);
-            memcpy(&sc_a[4 * (size_t)k], acc.d, 32);
-        }
-        g1_to_normalised(msm_pippenger(sc_a.data(), pts_a.data(), S + VERIFY_OWN * m, 8), a12);
-        g1_to_normalised(msm_pippenger(sc_b.data(), pts_b.data(), 2 * m, 8), b12);
-        return (int)BBGPU_OK;
-    });
-}
-
 // bbgpu_host_plonk_verify_multi behind its argument checks: proof j is of keys[circuit[j]]; every key under g2_x.  The rows of A are all circuits' shared
 // rows (circuit c's from base_c = sum of the num_shared() before it), then nine per proof in the caller's order; the scalar on V_{c,k} collects the
-// terms of the proofs labelled c.  With one key this is verify_host's table and verify_host's sums.
-static inline int verify_host_multi(const std::vector<VerifyKey>& keys, const uint64_t g2_x[16], const uint32_t* circuit, const uint64_t* proofs, size_t count,
+// terms of the proofs labelled c.  A null `circuit` labels every proof 0.
+static inline int verify_host_multi(const VerifyKey* keys, size_t num, const uint64_t g2_x[16], const uint32_t* circuit, const uint64_t* proofs, size_t count,
                                     const uint64_t seed[4], int flags, uint32_t* status, bbgpu_plonk_verify_report* R)
 {
     verify_report_init(R, count, seed);
-    std::vector<size_t> base(keys.size());
+    auto label = [&](size_t j) -> size_t { return circuit ? circuit[j] : 0; };
+    std::vector<size_t> base(num);
     size_t T = 0;
-    for (size_t c = 0; c < keys.size(); c++) {
+    for (size_t c = 0; c < num; c++) {
         base[c] = T;
         T += (size_t)keys[c].num_shared();
     }
     std::vector<VerifyTerms> terms(count);
     std::vector<uint64_t> pts_a((T + VERIFY_OWN * count) * 8), pts_b(2 * count * 8);
-    for (size_t c = 0; c < keys.size(); c++) verify_shared_points(keys[c], pts_a.data() + 8 * base[c]);
+    for (size_t c = 0; c < num; c++) verify_shared_points(keys[c], pts_a.data() + 8 * base[c]);
     const uint64_t* gen = pts_a.data() + 8 * (base[0] + keys[0].num_shared() - 1); // the generator: the last shared row of every circuit
     fallback_parallel(count, 4, [&](size_t lo, size_t hi) {
         for (size_t j = lo; j < hi; j++) {
             uint64_t rho[4];
             srs_check_rho(seed, j, rho);
             const uint64_t* pw = proofs + BBGPU_PLONK_PROOF_WORDS * j;
-            verify_terms(keys[circuit[j]], pw, rho, &terms[j]);
+            verify_terms(keys[label(j)], pw, rho, &terms[j]);
             status[j] = terms[j].status;
             for (int i = 0; i < VERIFY_OWN; i++) verify_own_point(terms[j].status ? gen : pw + 8 * i, &pts_a[(T + VERIFY_OWN * j + i) * 8]);
             for (int i = 0; i < 2; i++) verify_own_point(terms[j].status ? gen : pw + 8 * (i == 0 ? VP_PI_Z_OMEGA : VP_PI_Z), &pts_b[(2 * j + i) * 8]);
@@ -432,15 +385,23 @@ static inline int verify_host_multi(const std::vector<VerifyKey>& keys, const ui
     return verify_tail(R, g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) {
         std::vector<Fr> acc(T, fr_zero());
         for (size_t j = 0; j < m; j++) {
-            const VerifyKey& K = keys[circuit[j]];
+            const VerifyKey& K = keys[label(j)];
+            Fr* a = &acc[base[label(j)]];
             for (int k = 0; k < K.num_shared(); k++)
-                if (k == K.num_vk || !K.vk_inf[k]) acc[base[circuit[j]] + k] = fr_add(acc[base[circuit[j]] + k], terms[j].shared[k]);
+                if (k == K.num_vk || !K.vk_inf[k]) a[k] = fr_add(a[k], terms[j].shared[k]);
         }
         memcpy(sc_a.data(), acc.data(), T * 32);
         g1_to_normalised(msm_pippenger(sc_a.data(), pts_a.data(), T + VERIFY_OWN * m, 8), a12);
         g1_to_normalised(msm_pippenger(sc_b.data(), pts_b.data(), 2 * m, 8), b12);
         return (int)BBGPU_OK;
     });
+}
+
+// bbgpu_host_plonk_verify_batch behind its argument checks: one key, every proof of it
+static inline int verify_host(const VerifyKey& K, const uint64_t* proofs, size_t count, const uint64_t seed[4], int flags, uint32_t* status,
+                              bbgpu_plonk_verify_report* R)
+{
+    return verify_host_multi(&K, 1, K.g2_x, nullptr, proofs, count, seed, flags, status, R);
 }
 
 } // namespace host

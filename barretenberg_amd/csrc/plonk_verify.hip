@@ -1,5 +1,6 @@
-// plonk_verify.hip -- the two device parts of bbgpu_plonk_verify_batch and bbgpu_plonk_verify_multi (include/bbgpu.h) that are not an MSM: the per-proof work of
-// waffle::Verifier::verify_proof (verifier.cpp:55-355) and the sums over the batch of the scalars on the shared points.  The definition both follow is
+// plonk_verify.hip -- the two device parts of a verify call (include/bbgpu.h: bbgpu_plonk_verify_batch, bbgpu_plonk_verify_multi; one driver in capi.hip)
+// that are not an MSM: the per-proof work of waffle::Verifier::verify_proof (verifier.cpp:55-355) and the sums over the batch of the scalars on the shared
+// points.  Each is one text in two instantiations: proofs of one circuit (its record a kernel argument), or of several.  The definition both follow is
 // host_plonk_verify.hpp's verify_terms (the host twin; the comments there name the reference's lines); the sums A and B are the existing device MSM
 // over the rows and scalars written here (capi.hip), the pairing is host code (host_pairing.hpp).
 #include <hip/hip_runtime.h>
@@ -120,7 +121,8 @@ template <int L, int V> __device__ __forceinline__ void put_scalar(uint64_t* dst
     st8(dst, w);
 }
 
-struct VerifyKernelArgs {
+// what both instantiations take, then the call's circuits: the one record by value, or the table and a label per proof
+struct VerifyArgs {
     const uint64_t* proofs; // count x 120 words
     uint32_t* rows_own;     // count x 9 rows of 64 bytes (Montgomery-261, canonical: what the MSM kernels read), the proof's order
     uint32_t* rows_other;   // count x 2 rows: PI_Z_OMEGA, PI_Z
@@ -128,27 +130,29 @@ struct VerifyKernelArgs {
     uint64_t* scal_other;   // count x 2 x 4 words
     uint64_t* shared;       // [shared point][proof] x 4 words
     uint32_t* status;       // count
-    uint32_t count, log2n, widgets, num_vk;
-    Limbs9 root, root_inv, n_inv; // Montgomery-261
-    Seed seed;
-};
-// bbgpu_plonk_verify_multi: proof j is of circuit[j], whose constants a thread reads from records[circuit[j]] (bbgpu_internal.h); shared is
-// [slot < max over the circuits of num_vk + 1][proof], a proof fills the slots of its own circuit
-struct VerifyMixedArgs {
-    const uint64_t* proofs;
-    uint32_t *rows_own, *rows_other;
-    uint64_t *scal_own, *scal_other, *shared;
-    uint32_t* status;
-    const VerifyRecord* records; // one per circuit of the call
-    const uint32_t* circuit;     // count
     uint32_t count;
     Seed seed;
+    VerifyArgs(const VerifyDeviceBuffers& B, size_t n, const uint64_t sd[4])
+        : proofs(B.proofs), rows_own(B.rows_own), rows_other(B.rows_other), scal_own(B.scal_own), scal_other(B.scal_other), shared(B.shared), status(B.status),
+          count((uint32_t)n)
+    {
+        for (int k = 0; k < 4; k++) seed.d[k] = sd[k];
+    }
+};
+struct VerifyUniformArgs : VerifyArgs {
+    VerifyRecord rec; // base unused
+};
+// proof j is of circuit[j], whose constants a thread reads from records[circuit[j]] (bbgpu_internal.h); shared is [slot < max over the circuits of
+// num_vk + 1][proof], a proof fills the slots of its own circuit
+struct VerifyMixedArgs : VerifyArgs {
+    const VerifyRecord* records; // one per circuit of the call
+    const uint32_t* circuit;     // count
 };
 
 // MIXED false: n, the widget set and the key's size are the launch's (kernel arguments: every branch on them is uniform).  MIXED true: they are the
 // thread's own, read from its circuit's record where they are needed, so that the z^n loop and the widget branches diverge inside a wave that holds
 // proofs of several circuits; the arithmetic is the same text.
-template <bool MIXED> __global__ void __launch_bounds__(VT) k_verify_terms(typename std::conditional<MIXED, VerifyMixedArgs, VerifyKernelArgs>::type P)
+template <bool MIXED> __global__ void __launch_bounds__(VT) k_verify_terms(typename std::conditional<MIXED, VerifyMixedArgs, VerifyUniformArgs>::type P)
 {
     __shared__ uint64_t s_msg[MSG_LANES * VT];
     const uint32_t j = blockIdx.x * VT + threadIdx.x;
@@ -234,9 +238,9 @@ template <bool MIXED> __global__ void __launch_bounds__(VT) k_verify_terms(typen
         log2n = rec->log2n;
         widgets = rec->widgets;
     } else {
-        S = P.num_vk + 1;
-        log2n = P.log2n;
-        widgets = P.widgets;
+        S = P.rec.num_vk + 1;
+        log2n = P.rec.log2n;
+        widgets = P.rec.widgets;
     }
     // omega, omega^-1, 1 / n: which = 0, 1, 2
     auto domain = [&](int which) -> F2 {
@@ -246,7 +250,9 @@ template <bool MIXED> __global__ void __launch_bounds__(VT) k_verify_terms(typen
             const uint32_t d[NL] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x };
             return fe_from<FrP>(d);
         } else {
-            return fe_from<FrP>(which == 0 ? P.root.d : which == 1 ? P.root_inv.d : P.n_inv.d);
+            const uint32_t(&w)[12] = which == 0 ? P.rec.root : which == 1 ? P.rec.root_inv : P.rec.n_inv;
+            const uint32_t d[NL] = { w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8] };
+            return fe_from<FrP>(d);
         }
     };
     if (status) { // zeros on finite stand-in rows: nothing of this proof enters a sum
@@ -416,31 +422,25 @@ __device__ __forceinline__ void fold_finish(uint64_t (&s_acc)[FT][4], const uint
     o2[0] = make_ulonglong2(skip ? 0 : s_acc[0][0], skip ? 0 : s_acc[0][1]);
     o2[1] = make_ulonglong2(skip ? 0 : s_acc[0][2], skip ? 0 : s_acc[0][3]);
 }
-__global__ void __launch_bounds__(FT) k_verify_fold(const uint64_t* __restrict__ shared, uint32_t count, uint32_t m, uint32_t skip_mask, uint64_t* __restrict__ out)
-{
-    __shared__ uint64_t s_acc[FT][4];
-    const uint32_t k = blockIdx.x;
-    uint64_t acc[4] = { 0, 0, 0, 0 };
-    for (uint32_t j = threadIdx.x; j < m; j += FT) {
-        const ulonglong2* q = reinterpret_cast<const ulonglong2*>(shared + ((size_t)k * count + j) * 4);
-        const ulonglong2 lo = q[0], hi = q[1];
-        const uint64_t v[4] = { lo.x, lo.y, hi.x, hi.y };
-        fr_add_canonical(acc, v);
-    }
-    fold_finish(s_acc, acc, ((skip_mask >> k) & 1u) != 0, out + 4 * (size_t)k);
-}
-// bbgpu_plonk_verify_multi: workgroup (k, c) sums slot k over the proofs j < m labelled c into the scalar of circuit c's k-th shared row; a proof of
-// another circuit costs its 4-byte label, not the 32-byte term.  The additions are exact: which threads met a circuit's proofs shows in no result.
-__global__ void __launch_bounds__(FT) k_verify_fold_mixed(const uint64_t* __restrict__ shared, const uint32_t* __restrict__ circuit,
-                                                          const VerifyRecord* __restrict__ records, uint32_t count, uint32_t m, uint64_t* __restrict__ out)
+// MIXED false: workgroup k sums slot k over the proofs j < m into out[k].  MIXED true: workgroup (k, c) sums slot k over the proofs j < m labelled c
+// into the scalar of circuit c's k-th shared row; a proof of another circuit costs its 4-byte label, not the 32-byte term.
+template <bool MIXED> __global__ void __launch_bounds__(FT) k_verify_fold(const uint64_t* __restrict__ shared, const uint32_t* __restrict__ circuit,
+                                                                          const VerifyRecord* __restrict__ records, uint32_t count, uint32_t m,
+                                                                          uint32_t skip_mask, uint64_t* __restrict__ out)
 {
     __shared__ uint64_t s_acc[FT][4];
     const uint32_t k = blockIdx.x, c = blockIdx.y;
-    const uint32_t num_vk = records[c].num_vk, base = records[c].base, skip_mask = records[c].skip_mask;
-    if (k > num_vk) return; // the whole workgroup: circuit c has no such slot
+    uint32_t base = 0;
+    if constexpr (MIXED) {
+        const uint32_t num_vk = records[c].num_vk;
+        base = records[c].base;
+        skip_mask = records[c].skip_mask;
+        if (k > num_vk) return; // the whole workgroup: circuit c has no such slot
+    }
     uint64_t acc[4] = { 0, 0, 0, 0 };
     for (uint32_t j = threadIdx.x; j < m; j += FT) {
-        if (circuit[j] != c) continue;
+        if constexpr (MIXED)
+            if (circuit[j] != c) continue;
         const ulonglong2* q = reinterpret_cast<const ulonglong2*>(shared + ((size_t)k * count + j) * 4);
         const ulonglong2 lo = q[0], hi = q[1];
         const uint64_t v[4] = { lo.x, lo.y, hi.x, hi.y };
@@ -451,65 +451,22 @@ __global__ void __launch_bounds__(FT) k_verify_fold_mixed(const uint64_t* __rest
 
 } // namespace
 
-int plonk_verify_terms(const VerifyDeviceKey& key, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B, hipStream_t st)
+int plonk_verify_terms(const VerifyCircuits& C, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B, hipStream_t st)
 {
-    VerifyKernelArgs P;
-    P.proofs = B.proofs;
-    P.rows_own = B.rows_own;
-    P.rows_other = B.rows_other;
-    P.scal_own = B.scal_own;
-    P.scal_other = B.scal_other;
-    P.shared = B.shared;
-    P.status = B.status;
-    P.count = (uint32_t)count;
-    P.log2n = key.log2n;
-    P.widgets = key.widgets;
-    P.num_vk = key.num_vk;
-    for (int i = 0; i < NL; i++) {
-        P.root.d[i] = key.root[i];
-        P.root_inv.d[i] = key.root_inv[i];
-        P.n_inv.d[i] = key.n_inv[i];
-    }
-    for (int k = 0; k < 4; k++) P.seed.d[k] = seed[k];
-    k_verify_terms<false><<<(uint32_t)((count + VT - 1) / VT), VT, 0, st>>>(P);
+    const uint32_t grid = (uint32_t)((count + VT - 1) / VT);
+    if (C.one) k_verify_terms<false><<<grid, VT, 0, st>>>(VerifyUniformArgs{ { B, count, seed }, *C.one });
+    else k_verify_terms<true><<<grid, VT, 0, st>>>(VerifyMixedArgs{ { B, count, seed }, C.d_records, C.d_circuit });
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
 
-// the same for proofs of several circuits: d_records[d_circuit[j]] is proof j's circuit
-int plonk_verify_terms_mixed(const VerifyRecord* d_records, const uint32_t* d_circuit, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B,
-                             hipStream_t st)
+// the sums over the first m proofs: d_out[k] for the shared points of the one circuit, or d_out[records[c].base + k] for every circuit c and slot k of it
+int plonk_verify_fold(const VerifyCircuits& C, const uint64_t* d_shared, size_t count, size_t m, uint64_t* d_out, hipStream_t st)
 {
-    VerifyMixedArgs P;
-    P.proofs = B.proofs;
-    P.rows_own = B.rows_own;
-    P.rows_other = B.rows_other;
-    P.scal_own = B.scal_own;
-    P.scal_other = B.scal_other;
-    P.shared = B.shared;
-    P.status = B.status;
-    P.records = d_records;
-    P.circuit = d_circuit;
-    P.count = (uint32_t)count;
-    for (int k = 0; k < 4; k++) P.seed.d[k] = seed[k];
-    k_verify_terms<true><<<(uint32_t)((count + VT - 1) / VT), VT, 0, st>>>(P);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-// d_out[k] for the num_shared shared points: the sum over the first m proofs
-int plonk_verify_fold(const uint64_t* d_shared, size_t count, size_t m, int num_shared, uint32_t skip_mask, uint64_t* d_out, hipStream_t st)
-{
-    k_verify_fold<<<(uint32_t)num_shared, FT, 0, st>>>(d_shared, (uint32_t)count, (uint32_t)m, skip_mask, d_out);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-// d_out[records[c].base + k] for every circuit c < num_circuits and every slot k of it (max_shared: the largest num_vk + 1 among them)
-int plonk_verify_fold_mixed(const uint64_t* d_shared, const uint32_t* d_circuit, const VerifyRecord* d_records, int num_circuits, int max_shared, size_t count,
-                            size_t m, uint64_t* d_out, hipStream_t st)
-{
-    k_verify_fold_mixed<<<dim3((uint32_t)max_shared, (uint32_t)num_circuits), FT, 0, st>>>(d_shared, d_circuit, d_records, (uint32_t)count, (uint32_t)m, d_out);
+    if (C.one) k_verify_fold<false><<<C.one->num_vk + 1, FT, 0, st>>>(d_shared, nullptr, nullptr, (uint32_t)count, (uint32_t)m, C.one->skip_mask, d_out);
+    else
+        k_verify_fold<true><<<dim3((uint32_t)C.max_shared, (uint32_t)C.num_circuits), FT, 0, st>>>(d_shared, C.d_circuit, C.d_records, (uint32_t)count, (uint32_t)m, 0,
+                                                                                                   d_out);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }

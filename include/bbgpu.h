@@ -736,8 +736,9 @@ int bbgpu_host_plonk_verify_batch(size_t n, int widgets, const uint64_t* vk, con
  * Refused before a device is bound -- BBGPU_ERR_ARG: a null pointer, num_verifiers < 1, an unknown handle, a circuit[j] >= num_verifiers (the error text
  * names j), handles whose g2_x differ (compared on the words the handle stores), an unknown flag, count < 1; BBGPU_ERR_SIZE: num_verifiers >
  * BBGPU_PLONK_VERIFY_MAX_CIRCUITS, count > BBGPU_PLONK_VERIFY_MAX_BATCH.
- * On the device each thread of k_verify_terms reads n, the widget set and the domain's constants from its circuit's record (a table of G records the call
- * uploads together with circuit[] and the shared rows, in one copy), k_verify_fold_mixed sums slot k of circuit c in workgroup (k, c); a warm call passes
+ * On the device (G > 1; with G = 1 the call IS bbgpu_plonk_verify_batch's, the same driver and kernels) each thread of k_verify_terms reads n, the widget
+ * set and the domain's constants from its circuit's record (a table of G records the call uploads together with circuit[] and the shared rows, in one
+ * copy), k_verify_fold sums slot k of circuit c in workgroup (k, c); a warm call passes
  * as many allocation / upload / read-back / launch checks and synchronises as often as bbgpu_plonk_verify_batch at the same count, whatever G.
  * bbgpu_plonk_verify_last_timing reports the last call of either GPU entry.  Cost: tools/plonk_verify_multi_bench.py, profiles/plonk_verify_multi.txt. */
 #define BBGPU_PLONK_VERIFY_MAX_CIRCUITS 64

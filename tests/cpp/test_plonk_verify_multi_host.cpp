@@ -109,13 +109,13 @@ int main(int argc, char** argv)
             if (!row.status && !row.verdict && first_failing == UINT64_MAX) first_failing = j;
         }
         bbgpu_plonk_verify_report R, R2;
-        CHECK(verify_host_multi(keys, g2_x, circuit.data(), batch.data(), rows.size(), seed, BBGPU_PLONK_VERIFY_LOCATE, status.data(), &R) == BBGPU_OK, "batch");
+        CHECK(verify_host_multi(keys.data(), keys.size(), g2_x, circuit.data(), batch.data(), rows.size(), seed, BBGPU_PLONK_VERIFY_LOCATE, status.data(), &R) == BBGPU_OK, "batch");
         for (size_t j = 0; j < rows.size(); j++) CHECK((int)status[j] == rows[order[j]].status, "batch: status[%zu] = %u", j, status[j]);
         CHECK(R.count == rows.size() && R.bad_status == flagged && R.first_bad_status == first_flagged, "batch: %llu flagged, first %llu",
               (unsigned long long)R.bad_status, (unsigned long long)R.first_bad_status);
         CHECK(R.pairing_checked == 1 && R.pairing_ok == 0 && R.first_bad_proof == first_failing, "batch: first bad proof %llu, want %llu",
               (unsigned long long)R.first_bad_proof, (unsigned long long)first_failing);
-        CHECK(verify_host_multi(keys, g2_x, circuit.data(), batch.data(), rows.size(), seed, BBGPU_PLONK_VERIFY_LOCATE, status.data(), &R2) == BBGPU_OK, "again");
+        CHECK(verify_host_multi(keys.data(), keys.size(), g2_x, circuit.data(), batch.data(), rows.size(), seed, BBGPU_PLONK_VERIFY_LOCATE, status.data(), &R2) == BBGPU_OK, "again");
         CHECK(!memcmp(&R, &R2, sizeof R), "one seed, two reports");
         // the rows the reference accepted, alone: one good batch of several circuits
         std::vector<uint64_t> good;
@@ -125,7 +125,7 @@ int main(int argc, char** argv)
                 good.insert(good.end(), &batch[j * BBGPU_PLONK_PROOF_WORDS], &batch[(j + 1) * BBGPU_PLONK_PROOF_WORDS]);
                 good_circuit.push_back(circuit[j]);
             }
-        CHECK(verify_host_multi(keys, g2_x, good_circuit.data(), good.data(), good_circuit.size(), seed, 0, status.data(), &R) == BBGPU_OK, "good");
+        CHECK(verify_host_multi(keys.data(), keys.size(), g2_x, good_circuit.data(), good.data(), good_circuit.size(), seed, 0, status.data(), &R) == BBGPU_OK, "good");
         CHECK(R.bad_status == 0 && R.pairing_ok == 1 && good_circuit.size() >= 15, "the accepted rows: %zu, pairing_ok %u", good_circuit.size(), R.pairing_ok);
     }
     // one circuit: verify_host's report; the same key twice, labels alternating: its a, b and verdict
@@ -137,10 +137,11 @@ int main(int argc, char** argv)
         std::vector<uint32_t> zeros(count, 0), alternating(count), s1(count), s2(count);
         for (size_t j = 0; j < count; j++) alternating[j] = (uint32_t)(j & 1);
         bbgpu_plonk_verify_report one, multi, twice;
+        const std::vector<VerifyKey> same = { keys[0], keys[0] };
         CHECK(verify_host(keys[0], batch.data(), count, seed, BBGPU_PLONK_VERIFY_LOCATE, s1.data(), &one) == BBGPU_OK, "verify_host");
-        CHECK(verify_host_multi({ keys[0] }, g2_x, zeros.data(), batch.data(), count, seed, BBGPU_PLONK_VERIFY_LOCATE, s2.data(), &multi) == BBGPU_OK, "G = 1");
+        CHECK(verify_host_multi(keys.data(), 1, g2_x, zeros.data(), batch.data(), count, seed, BBGPU_PLONK_VERIFY_LOCATE, s2.data(), &multi) == BBGPU_OK, "G = 1");
         CHECK(!memcmp(&one, &multi, sizeof one) && s1 == s2, "G = 1 is not verify_host's report");
-        CHECK(verify_host_multi({ keys[0], keys[0] }, g2_x, alternating.data(), batch.data(), count, seed, BBGPU_PLONK_VERIFY_LOCATE, s2.data(), &twice) == BBGPU_OK,
+        CHECK(verify_host_multi(same.data(), same.size(), g2_x, alternating.data(), batch.data(), count, seed, BBGPU_PLONK_VERIFY_LOCATE, s2.data(), &twice) == BBGPU_OK,
               "the same key twice");
         CHECK(!memcmp(&one, &twice, sizeof one) && s1 == s2, "the same key twice is not verify_host's report");
         CHECK(one.pairing_ok == 0 && one.first_bad_proof == 1, "first bad proof %llu", (unsigned long long)one.first_bad_proof);

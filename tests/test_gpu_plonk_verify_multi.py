@@ -1,5 +1,5 @@
 """bbgpu_plonk_verify_multi on the GPU (-m gpu): proofs of several circuits in one batch -- k_verify_terms<true> reads each thread's circuit from a
-record, k_verify_fold_mixed sums a circuit's shared terms in workgroup (slot, circuit), A and B are two device MSMs, one pairing tail for all.  Every
+record, k_verify_fold<true> sums a circuit's shared terms in workgroup (slot, circuit), A and B are two device MSMs, one pairing tail for all.  Every
 report is compared, field for field and with status, a and b, with bbgpu_host_plonk_verify_multi on the same batch; expected verdicts come from the
 reference's verdicts on the rows (tests/golden/plonk_verify.json) or from what a tamper changes (tests/plonk_verify_multi_cases.tampered), never from
 this code's own answer.  Shapes are small on purpose: less than a wave, three waves with the last partial, and the fold's strided loop past 2 x 256."""
@@ -133,6 +133,17 @@ def test_one_circuit_and_duplicate_handles_equal_the_single_circuit_entry(lib, h
         assert whole(lib.plonk_verify_multi([h, h, h], (np.arange(70) % 3).astype(np.uint32), proofs, SEED, False)) == \
             whole(lib.plonk_verify_batch(h, proofs, SEED, False))
     assert lib.fault_stats()["slots_pending"] == 0
+
+
+def test_a_second_verifier_without_proofs_changes_nothing(lib, handles):
+    """seven proofs of standard/32, all labelled 0, beside a verifier of more shared rows that gets none: the mixed fold over an empty circuit writes
+    zeros on that circuit's rows, so the report is the one-verifier call's bit for bit, and the host twin's"""
+    labels = np.zeros(7, dtype=np.uint32)
+    proofs = honest_batch(np.full(7, index("standard/32")))
+    proofs[5] = row("standard/32", "neg_Z_1")["proof"]
+    one = lib.plonk_verify_multi([handles[index("standard/32")]], labels, proofs, SEED, True)
+    assert not one.ok and int(one.first_bad_proof) == 5
+    assert whole(both(lib, handles, labels, proofs, names=["standard/32", "extended/32"])) == whole(one)
 
 
 def test_one_seed_one_report(lib, handles, batch130):

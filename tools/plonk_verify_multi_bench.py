@@ -8,7 +8,11 @@ repeated to the count; fixed seed, no LOCATE; every report is checked to be good
      of the cell's pairs lies below its pair's sum of separate calls.
   2. bbgpu_plonk_verify_batch, parent against child, at 256 and 2^14 proofs of one circuit.  "no regression" is printed only where the child's median
      lies within the parent's median plus the spread (the parent's interquartile range in this run).
-  3. G = 1 through bbgpu_plonk_verify_multi against bbgpu_plonk_verify_batch (both child), at 256 and 2^14 proofs: the per-thread record and branches.
+  3. G = 1 through bbgpu_plonk_verify_multi against bbgpu_plonk_verify_batch (both child), at 256 and 2^14 proofs: one call since both entries run
+     one driver, which takes the single-circuit kernels whenever the call names one verifier.
+  4. bbgpu_plonk_verify_multi, parent against child (a parent that has the entry), G = 1, 2, 4, 6 at 256 proofs per circuit and G = 1 at 2^14: section
+     2's rule.
+--sections picks some of the four, e.g. to repeat a cell with more pairs.
 Usage: make the parent's library once (barretenberg_amd/csrc: `make variant NAME=parent` in a checkout of the parent, copied to
 barretenberg_amd/_variants/libbbgpu_parent.so), then  python tools/plonk_verify_multi_bench.py [--pairs 31] [--parent-lib PATH]"""
 import argparse
@@ -61,6 +65,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=31)
     ap.add_argument("--parent-lib", default=PARENT_LIB)
+    ap.add_argument("--sections", default="1,2,3,4")
     args = ap.parse_args()
     from barretenberg_amd import BbGpu
     from tests.plonk_verify_cases import fixture
@@ -71,7 +76,7 @@ def main():
     os.environ["BBGPU_LIB"] = args.parent_lib
     parent = BbGpu(device=0)
     del os.environ["BBGPU_LIB"]
-    assert not hasattr(parent.lib, "bbgpu_plonk_verify_multi"), "--parent-lib is not the parent: it has the new entry"
+    sections = {int(x) for x in args.sections.split(",")}
     g2_x, circuits, _ = fixture()
     hc = [child.plonk_verifier_create(circuits[c]["n"], circuits[c]["widgets"], circuits[c]["vk"], g2_x) for c in CIRCUITS]
     hp = [parent.plonk_verifier_create(circuits[c]["n"], circuits[c]["widgets"], circuits[c]["vk"], g2_x) for c in CIRCUITS]
@@ -79,7 +84,7 @@ def main():
           % (child.version(), parent.version(), args.pairs))
 
     print("\n1. one mixed call (child) against G calls of bbgpu_plonk_verify_batch (parent); circuits: the first G of %s" % ", ".join(CIRCUITS))
-    for per in (256, 16):
+    for per in (256, 16) if 1 in sections else ():
         for G in (1, 2, 4, 6):
             labels = (np.arange(G * per) % G).astype(np.uint32)
             proofs = honest_batch(labels)
@@ -96,18 +101,22 @@ def main():
 
     one = np.zeros(1 << 14, dtype=np.uint32) + index("standard/32")
     big = honest_batch(one)
-    print("\n2. bbgpu_plonk_verify_batch, parent against child (standard/32)")
-    for count in (256, 1 << 14):
-        pr = np.ascontiguousarray(big[:count])
-        tp, tc = pairs(args.pairs, lambda: parent.plonk_verify_batch(hp[0], pr, SEED), lambda: child.plonk_verify_batch(hc[0], pr, SEED))
+
+    def regression_line(what, tp, tc):
         sp, sc = stats(tp), stats(tc)
         holds = sc["med"] <= sp["med"] + sp["iqr"]
-        print("count %5d  %s  %s  %s" % (count, show("parent", tp), show("child", tc),
-                                        "no regression: the child's median within the parent's plus its spread" if holds else
-                                        "REGRESSION by this run's rule: the child's median is above the parent's plus its spread"), flush=True)
+        print("%s  %s  %s  %s" % (what, show("parent", tp), show("child", tc),
+                                  "no regression: the child's median within the parent's plus its spread" if holds else
+                                  "REGRESSION by this run's rule: the child's median is above the parent's plus its spread"), flush=True)
+
+    print("\n2. bbgpu_plonk_verify_batch, parent against child (standard/32)")
+    for count in (256, 1 << 14) if 2 in sections else ():
+        pr = np.ascontiguousarray(big[:count])
+        tp, tc = pairs(args.pairs, lambda: parent.plonk_verify_batch(hp[0], pr, SEED), lambda: child.plonk_verify_batch(hc[0], pr, SEED))
+        regression_line("count %5d" % count, tp, tc)
 
     print("\n3. G = 1 through bbgpu_plonk_verify_multi against bbgpu_plonk_verify_batch, both child (standard/32)")
-    for count in (256, 1 << 14):
+    for count in (256, 1 << 14) if 3 in sections else ():
         pr, lb = np.ascontiguousarray(big[:count]), np.zeros(count, dtype=np.uint32)
         split_m, split_b = [], []
 
@@ -126,6 +135,16 @@ def main():
         note = "slower by more than the spread" if sm["med"] > sb["med"] + sb["iqr"] else "within the spread" if sm["med"] >= sb["med"] - sb["iqr"] else "faster by more than the spread"
         print("count %5d  %s  %s  upload + k_verify_terms + read-back: multi %6.3f batch %6.3f  multi is %s"
               % (count, show("multi", tm), show("batch", tb), terms[0], terms[1], note), flush=True)
+
+    print("\n4. bbgpu_plonk_verify_multi, parent against child; circuits as in 1, the labels round-robin")
+    if 4 in sections and not hasattr(parent.lib, "bbgpu_plonk_verify_multi"):
+        print("skipped: the parent has no such entry")
+    elif 4 in sections:
+        for G, per in ((1, 256), (2, 256), (4, 256), (6, 256), (1, 1 << 14)):
+            labels = (np.arange(G * per) % G).astype(np.uint32)
+            proofs = honest_batch(labels)
+            tp, tc = pairs(args.pairs, lambda: parent.plonk_verify_multi(hp[:G], labels, proofs, SEED), lambda: child.plonk_verify_multi(hc[:G], labels, proofs, SEED))
+            regression_line("G %d x %5d proofs" % (G, per), tp, tc)
     for g, hs in ((child, hc), (parent, hp)):
         for h in hs:
             g.plonk_verifier_destroy(h)
