@@ -63,6 +63,8 @@ C_ABI_SYMBOLS = [
     "bbgpu_plonk_verify_multi", "bbgpu_host_plonk_verify_multi",
     "bbgpu_srs_update", "bbgpu_host_srs_update", "bbgpu_host_srs_update_check", "bbgpu_transcript_write_g2", "bbgpu_selftest_endo_split",
     "bbgpu_srs_lagrange", "bbgpu_host_srs_lagrange",
+    "bbgpu_fr_evaluate_lagrange_device", "bbgpu_kate_opening_lagrange_device", "bbgpu_host_fr_evaluate_lagrange", "bbgpu_host_kate_opening_lagrange",
+    "bbgpu_srs_lagrange_check", "bbgpu_host_srs_lagrange_check",
     "bbgpu_selftest_plonk_round",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
@@ -127,6 +129,23 @@ class SrsLagrangeReport(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class SrsLagrangeCheckReport(C.Structure):
+    """bbgpu_srs_lagrange_check_report (include/bbgpu.h)"""
+    NONE = 0xFFFFFFFFFFFFFFFF  # first_bad_point / first_bad_row when there is none
+    _fields_ = [("n", C.c_uint64), ("bad_points", C.c_uint64), ("first_bad_point", C.c_uint64), ("basis_checked", C.c_uint32), ("basis_ok", C.c_uint32),
+                ("first_bad_row", C.c_uint64), ("seed", C.c_uint64 * 4), ("a", C.c_uint64 * 8), ("b", C.c_uint64 * 8)]
+
+    @property
+    def ok(self):
+        """the table is the Lagrange form of the string: every row on the curve and the basis test passed"""
+        return self.bad_points == 0 and self.basis_ok == 1
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32)}
+        d.update(seed=[int(v) for v in self.seed], a=[int(v) for v in self.a], b=[int(v) for v in self.b], ok=bool(self.ok))
+        return d
 
 
 class PlonkVerifyReport(C.Structure):
@@ -309,6 +328,23 @@ class BbGpu:
         self._chk(self.lib.bbgpu_kate_opening_device(d_src, d_dest, n, _ptr(np.ascontiguousarray(z, dtype=np.uint64)), _ptr(f), stream or 0))
         return f
 
+    def evaluate_lagrange_device(self, d_values, n, z, batch=1, stride=None, stream=None):
+        """bbgpu_fr_evaluate_lagrange_device: `batch` polynomials given by their values on the size-n domain (stride elements apart), at z -> (batch, 4)"""
+        out = np.zeros((max(int(batch), 1), 4), dtype=np.uint64)
+        self.lib.bbgpu_fr_evaluate_lagrange_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, u64p, u64p, C.c_void_p]
+        self._chk(self.lib.bbgpu_fr_evaluate_lagrange_device(d_values, n, n if stride is None else stride, batch,
+                                                             _ptr(np.ascontiguousarray(z, dtype=np.uint64)), _ptr(out), stream or 0))
+        return out
+
+    def kate_opening_lagrange_device(self, d_values, d_quotient, n, z, batch=1, stride=None, want_f=True, stream=None):
+        """bbgpu_kate_opening_lagrange_device: the values of (f_b(X) - f_b(z)) / (X - z) on the domain into d_quotient (may be d_values itself); returns
+        f_b(z) as (batch, 4), or None with want_f=False (then only the batch inversion synchronises)"""
+        f = np.zeros((max(int(batch), 1), 4), dtype=np.uint64) if want_f else None
+        self.lib.bbgpu_kate_opening_lagrange_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, u64p, u64p, C.c_void_p]
+        self._chk(self.lib.bbgpu_kate_opening_lagrange_device(d_values, d_quotient, n, n if stride is None else stride, batch,
+                                                              _ptr(np.ascontiguousarray(z, dtype=np.uint64)), _ptr(f) if want_f else None, stream or 0))
+        return f
+
     def compute_lagrange_polynomial_fft_device(self, d_l_1, n_src, n_target, stream=None):
         """polynomial_arithmetic::compute_lagrange_polynomial_fft (:381-476)"""
         self._chk(self.lib.bbgpu_lagrange_l1_fft_device(d_l_1, n_src, n_target, stream or 0))
@@ -468,6 +504,27 @@ class BbGpu:
         if rc < 0:
             raise self._srs_update_error(rc, rep)
         return out, rep
+
+    # ---- is this table the Lagrange form of that string?  (bbgpu_srs_lagrange_check and its host twin) ----
+    def srs_lagrange_check(self, lagrange_handle, monomial_handle, n, seed=None, locate=False):
+        """bbgpu_srs_lagrange_check: rows [0, n) of the Lagrange handle on the curve, and equal to L_i of the monomial handle's rows by two MSMs and one
+        transform.  seed None: drawn from the operating system.  Returns an SrsLagrangeCheckReport (.ok, .as_dict())."""
+        sd = np.ascontiguousarray(seed, dtype=np.uint64).reshape(4) if seed is not None else None
+        rep = SrsLagrangeCheckReport()
+        self.lib.bbgpu_srs_lagrange_check.argtypes = [C.c_int, C.c_int, C.c_size_t, u64p, C.c_int, C.POINTER(SrsLagrangeCheckReport)]
+        self._chk(self.lib.bbgpu_srs_lagrange_check(int(lagrange_handle), int(monomial_handle), int(n), _ptr(sd) if sd is not None else None,
+                                                    1 if locate else 0, C.byref(rep)))
+        return rep
+
+    def host_srs_lagrange_check(self, lagrange_table, monomial_table, n=None, seed=None, locate=False):
+        """bbgpu_host_srs_lagrange_check: the same check over the even entries of two (2n, 8) endo tables, on the host; no GPU needed"""
+        n = lagrange_table.shape[0] // 2 if n is None else n
+        sd = np.ascontiguousarray(seed, dtype=np.uint64).reshape(4) if seed is not None else None
+        rep = SrsLagrangeCheckReport()
+        self.lib.bbgpu_host_srs_lagrange_check.argtypes = [u64p, u64p, C.c_size_t, u64p, C.c_int, C.POINTER(SrsLagrangeCheckReport)]
+        self._chk(self.lib.bbgpu_host_srs_lagrange_check(_ptr(lagrange_table), _ptr(monomial_table), int(n), _ptr(sd) if sd is not None else None,
+                                                         1 if locate else 0, C.byref(rep)))
+        return rep
 
     def selftest_endo_split(self, k, on_device=True):
         """bbgpu_selftest_endo_split: k (n, 4) plain integers -> (n, 6): |k1| (2), |k2| (2), flags, 0"""
@@ -733,6 +790,28 @@ class BbGpu:
         self.lib.bbgpu_host_kate_opening.argtypes = [u64p, u64p, C.c_size_t, u64p, u64p]
         self._chk(self.lib.bbgpu_host_kate_opening(_ptr(src), _ptr(dest), src.shape[0], _ptr(np.ascontiguousarray(z, dtype=np.uint64)), _ptr(f)))
         return dest, f
+
+    def host_evaluate_lagrange(self, values, z, n=None, batch=1, stride=None):
+        """bbgpu_host_fr_evaluate_lagrange: values (batch * stride, 4) -> (batch, 4); n defaults to the stride, the stride to rows / batch"""
+        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        stride = values.shape[0] // max(int(batch), 1) if stride is None else stride
+        n = stride if n is None else n
+        out = np.zeros((max(int(batch), 1), 4), dtype=np.uint64)
+        self.lib.bbgpu_host_fr_evaluate_lagrange.argtypes = [u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, u64p]
+        self._chk(self.lib.bbgpu_host_fr_evaluate_lagrange(_ptr(values), n, stride, batch, _ptr(np.ascontiguousarray(z, dtype=np.uint64)), _ptr(out)))
+        return out
+
+    def host_kate_opening_lagrange(self, values, z, n=None, batch=1, stride=None, out=None):
+        """bbgpu_host_kate_opening_lagrange -> (quotient values in the layout of `values`, f(z) as (batch, 4)); out: the array to write (may be `values`
+        itself), default a copy of `values` (so that the elements between the polynomials show they were left alone)"""
+        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        stride = values.shape[0] // max(int(batch), 1) if stride is None else stride
+        n = stride if n is None else n
+        out = values.copy() if out is None else out
+        f = np.zeros((max(int(batch), 1), 4), dtype=np.uint64)
+        self.lib.bbgpu_host_kate_opening_lagrange.argtypes = [u64p, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, u64p]
+        self._chk(self.lib.bbgpu_host_kate_opening_lagrange(_ptr(values), _ptr(out), n, stride, batch, _ptr(np.ascontiguousarray(z, dtype=np.uint64)), _ptr(f)))
+        return out, f
 
     def host_lagrange_l1_fft(self, n_src, n_target):
         out = np.zeros((n_target, 4), dtype=np.uint64)

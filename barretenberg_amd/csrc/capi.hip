@@ -30,6 +30,8 @@
 #include "host_srs_check.hpp"
 #include "host_srs_update.hpp"
 #include "host_srs_lagrange.hpp"
+#include "host_lagrange_open.hpp"
+#include "host_srs_lagrange_check.hpp"
 #include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
@@ -1708,6 +1710,53 @@ int bbgpu_kate_opening_device(const uint64_t* d_src, uint64_t* d_dest, size_t n,
     return poly::horner_suffix(src, d_dest, n, zz, false, ctx().poly_scratch, st, nullptr);
 }
 
+/* ---- evaluation and opening in evaluation form (host_lagrange_open.hpp, poly.hip bary_open) ---- */
+// the verdict both the device entries and the host twins give on their arguments; ptr_ok: the entry's own pointers
+static int lagrange_open_args(const char* what, bool ptr_ok, size_t n, size_t stride_elems, int batch)
+{
+    if (!host::lagrange_open_sizes_ok(n, stride_elems, batch)) {
+        set_error("%s: n = %zu must be a power of two in [2, 2^%d], batch = %d in 1..%d and the stride (%zu) no smaller than n", what, n,
+                  host::LAGRANGE_OPEN_MAX_LOG2, batch, host::LAGRANGE_OPEN_MAX_BATCH, stride_elems);
+        return BBGPU_ERR_SIZE;
+    }
+    if (!ptr_ok) {
+        set_error("%s: null values / quotient / z / out", what);
+        return BBGPU_ERR_ARG;
+    }
+    return BBGPU_OK;
+}
+// argument errors are refused before a device is bound; the case decision (z on the domain, and where) is the host's, before anything is launched
+static int lagrange_open_device(const char* what, bool ptr_ok, const uint64_t* d_values, uint64_t* d_quotient, size_t n, size_t stride_elems, int batch,
+                                const uint64_t* z, uint64_t* out, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rc = lagrange_open_args(what, ptr_ok, n, stride_elems, batch)) return rc;
+    if (int rc = ensure_init()) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = shared_begin(st)) return rc;
+    SharedGuard shared_guard_{ st };
+    const int log2n = host::lagrange_open_log2(n);
+    const host::Fr zz = host::fr_mul(load_fr(z), host::fr_one());
+    size_t m = 0;
+    const bool on = host::lagrange_open_on_domain(zz, log2n, &m);
+    if (!on || d_quotient)
+        if (int rc = grow(&ctx().d_poly_tmp, &ctx().poly_tmp_cap, n * 32)) return rc;
+    std::vector<host::Fr> y(out ? (size_t)batch : 0);
+    if (int rc = poly::bary_open(d_values, d_quotient, log2n, stride_elems, batch, zz, on, m, ctx().d_poly_tmp, out ? y.data() : nullptr, ctx().poly_scratch, st))
+        return rc;
+    if (out) memcpy(out, y.data(), (size_t)batch * 32);
+    return BBGPU_OK;
+}
+int bbgpu_fr_evaluate_lagrange_device(const uint64_t* d_values, size_t n, size_t stride_elems, int batch, const uint64_t z[4], uint64_t* out, void* hip_stream)
+{
+    return lagrange_open_device("evaluate_lagrange", d_values && z && out, d_values, nullptr, n, stride_elems, batch, z, out, hip_stream);
+}
+int bbgpu_kate_opening_lagrange_device(const uint64_t* d_values, uint64_t* d_quotient, size_t n, size_t stride_elems, int batch, const uint64_t z[4],
+                                       uint64_t* f_of_z, void* hip_stream)
+{
+    return lagrange_open_device("kate_opening_lagrange", d_values && d_quotient && z, d_values, d_quotient, n, stride_elems, batch, z, f_of_z, hip_stream);
+}
+
 int bbgpu_lagrange_l1_fft_device(uint64_t* d_l_1, size_t n_src, size_t n_target, void* hip_stream)
 {
     POLY_ENTER(d_l_1);
@@ -1882,6 +1931,19 @@ int bbgpu_host_kate_opening(const uint64_t* src, uint64_t* dest, size_t n, const
     if (((!src || !dest) && n) || !z) return BBGPU_ERR_ARG;
     const host::Fr f = host::kate_opening(src, dest, n, load_fr(z));
     if (f_of_z) memcpy(f_of_z, f.d, 32);
+    return BBGPU_OK;
+}
+int bbgpu_host_fr_evaluate_lagrange(const uint64_t* values, size_t n, size_t stride_elems, int batch, const uint64_t z[4], uint64_t* out)
+{
+    if (int rc = lagrange_open_args("host evaluate_lagrange", values && z && out, n, stride_elems, batch)) return rc;
+    host::lagrange_open_host(values, nullptr, n, stride_elems, batch, load_fr(z), out);
+    return BBGPU_OK;
+}
+int bbgpu_host_kate_opening_lagrange(const uint64_t* values, uint64_t* quotient, size_t n, size_t stride_elems, int batch, const uint64_t z[4],
+                                     uint64_t* f_of_z)
+{
+    if (int rc = lagrange_open_args("host kate_opening_lagrange", values && quotient && z, n, stride_elems, batch)) return rc;
+    host::lagrange_open_host(values, quotient, n, stride_elems, batch, load_fr(z), f_of_z);
     return BBGPU_OK;
 }
 int bbgpu_host_lagrange_l1_fft(uint64_t* l_1, size_t n_src, size_t n_target)
@@ -2338,6 +2400,98 @@ int bbgpu_srs_lagrange(int srs_handle, size_t n, uint64_t* host_endo_table_out, 
     }
     if (rep.infinity_rows) return srs_lagrange_refusal(rep);
     return add_srs(host_endo_table_out, n, d, false);
+}
+
+/* ---- is this table the Lagrange form of that string?  (host_srs_lagrange_check.hpp; the parts of bbgpu_srs_check, no kernel of its own) ---- */
+static int srs_lagrange_check_args(size_t n, int flags, const void* out, int* log2n)
+{
+    if (!out || (flags & ~BBGPU_SRS_LAGRANGE_CHECK_LOCATE)) {
+        set_error("SRS Lagrange check: null out or unknown flag bits 0x%x", flags);
+        return BBGPU_ERR_ARG;
+    }
+    if ((*log2n = host::srs_lagrange_log2(n)) < 0) {
+        set_error("SRS Lagrange check: n = %zu is not a power of two between 2 and 2^%d", n, host::SRS_LAGRANGE_MAX_LOG2);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
+
+int bbgpu_host_srs_lagrange_check(const uint64_t* lagrange_endo_table, const uint64_t* monomial_endo_table, size_t n, const uint64_t seed[4], int flags,
+                                  bbgpu_srs_lagrange_check_report* out)
+{
+    if (!lagrange_endo_table || !monomial_endo_table) {
+        set_error("SRS Lagrange check: null table");
+        return BBGPU_ERR_ARG;
+    }
+    int log2n;
+    if (int rc = srs_lagrange_check_args(n, flags, out, &log2n)) return rc;
+    uint64_t sd[4];
+    if (!host::srs_check_seed(seed, sd)) {
+        set_error("SRS Lagrange check: the operating system gave no randomness");
+        return BBGPU_ERR_STATE;
+    }
+    return host::srs_lagrange_check_host(lagrange_endo_table, monomial_endo_table, n, log2n, sd, flags, out);
+}
+
+int bbgpu_srs_lagrange_check(int lagrange_handle, int monomial_handle, size_t n, const uint64_t seed[4], int flags, bbgpu_srs_lagrange_check_report* out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound: a handle can only exist once one is
+    int log2n;
+    if (int rc = srs_lagrange_check_args(n, flags, out, &log2n)) return rc;
+    for (const int h : { lagrange_handle, monomial_handle }) {
+        if (h < 0 || h >= (int)ctx().srs.size() || !ctx().srs[h].live) {
+            set_error("unknown SRS handle %d", h);
+            return BBGPU_ERR_ARG;
+        }
+        if (n > ctx().srs[h].n) {
+            set_error("SRS Lagrange check of %zu rows, the table of handle %d holds %zu", n, h, ctx().srs[h].n);
+            return BBGPU_ERR_SIZE;
+        }
+    }
+    if (int rc = ensure_init()) return rc;
+    uint64_t sd[4];
+    if (!host::srs_check_seed(seed, sd)) {
+        set_error("SRS Lagrange check: the operating system gave no randomness");
+        return BBGPU_ERR_STATE;
+    }
+    host::srs_lagrange_check_report_init(out, n, sd);
+    // the staging of bbgpu_srs_check: the findings, the n multipliers, and the copy of them that is transformed
+    constexpr size_t HEAD = 64;
+    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, HEAD + 2 * n * 32)) return rc;
+    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
+    uint64_t *d_rho = ctx().d_srs_check + HEAD / 8, *d_coef = d_rho + 4 * n;
+    const hipStream_t st = ctx().stream;
+    const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
+    SrsCurveFindings got = init;
+    HIPCHK(h2d_async(d_find, &init, sizeof init, st));
+    if (int rc = srs_check_curve(ctx().srs[lagrange_handle].d_srs, n, no_generator, d_find, st)) return rc;
+    if (int rc = srs_check_scalars(sd, n, d_rho, st)) return rc;
+    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
+    HIPCHK(hipStreamSynchronize(st));
+    out->bad_points = got.bad_points;
+    out->first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
+    if (out->bad_points) return BBGPU_OK;
+    // A and B: the copy is cut and transformed on the library's stream, then two tickets in flight
+    return host::srs_lagrange_check_basis(out, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
+        HIPCHK(hipMemcpyAsync(d_coef, d_rho, m * 32, hipMemcpyDeviceToDevice, st));
+        if (m < n) HIPCHK(hipMemsetAsync(d_coef + 4 * m, 0, (n - m) * 32, st));
+        if (int rc = bbgpu_ntt_device(d_coef, n, BBGPU_IFFT, nullptr, st)) return rc;
+        HIPCHK(hipStreamSynchronize(st)); // the tickets run on slot streams
+        const int ta = bbgpu_msm_g1_device_async(lagrange_handle, 0, d_rho, m, 0, entry_windows(ctx().srs[lagrange_handle], m), nullptr);
+        if (ta < 0) return ta;
+        const int tb = bbgpu_msm_g1_device_async(monomial_handle, 0, d_coef, n, 0, entry_windows(ctx().srs[monomial_handle], n), nullptr);
+        if (tb < 0) {
+            drain_tickets(&ta, 1);
+            return tb;
+        }
+        if (int rc = bbgpu_msm_g1_wait(ta, a12)) {
+            drain_tickets(&tb, 1);
+            return rc;
+        }
+        return bbgpu_msm_g1_wait(tb, b12);
+    });
 }
 
 // io.hpp:36-182 restated for the G1 part: 28-byte manifest of seven big-endian uint32 (fields 5 = num_g1_points), then points as

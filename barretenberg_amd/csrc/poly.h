@@ -206,6 +206,11 @@ int batch_invert(uint64_t* d_v, uint64_t* d_tmp, size_t n, Scratch& S, hipStream
 int sigma_from_mapping(uint64_t* d_out, const uint32_t* d_mapping, const uint64_t* d_roots, size_t n, hipStream_t st);
 int divide_by_pseudo_vanishing(uint64_t* d_coeffs, int log2n, int log2N, hipStream_t st);
 int lagrange_l1_fft(uint64_t* d_l1, uint64_t* d_tmp, int log2n, int log2N, Scratch& S, hipStream_t st);
+// `batch` polynomials given by their values on the size-2^log2n domain (polynomial b at d_values + b * stride elements), evaluated at z (canonical) into
+// h_out (may be null) and, with d_quotient (null, d_values itself or disjoint; same stride), opened there: the values of (f(X) - f(z)) / (X - z).
+// on_domain / m: z == w^m, decided by the caller (host_lagrange_open.hpp).  d_tmp: n elements of workspace
+int bary_open(const uint64_t* d_values, uint64_t* d_quotient, int log2n, size_t stride, int batch, const host::Fr& z, bool on_domain, size_t m,
+              uint64_t* d_tmp, host::Fr* h_out, Scratch& S, hipStream_t st);
 
 } // namespace poly
 } // namespace bbgpu

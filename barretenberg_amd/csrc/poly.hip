@@ -9,6 +9,8 @@
 //   fr::batch_invert                                             fields/field.hpp:503-522
 //   the grand-product prefix products                            waffle/proof_system/prover/prover.cpp:194-202
 //   compute_permutation_lagrange_base_single                     waffle/proof_system/permutation.hpp:15-87
+// adds what the reference has no counterpart of: evaluation and opening of polynomials given by their VALUES on the domain (the k_bary_* kernels and
+// bary_open: barycentric sums over one shared batch inversion, no transform),
 // and provides the fused pointwise kernels of the prover rounds (prover.cpp:135-222,224-300,302-403,461-463,520-528,567-595,
 // arithmetic_widget.cpp:66-104,106-126).
 //
@@ -39,6 +41,7 @@
 #include "bbgpu_internal.h"
 #include "fe.hpp"
 #include "host_fr.hpp"
+#include "host_lagrange_open.hpp"
 #include "poly.h"
 
 namespace bbgpu {
@@ -736,6 +739,75 @@ __global__ void __launch_bounds__(PT) k_l1_scale(uint32_t* __restrict__ l1, uint
     stv(l1, i, mul(ldv(l1, i), s));
 }
 
+// ---- evaluation and opening in evaluation form (bary_open below; the reference has no counterpart) ----------------------------------------------------
+// d[i] = z - w^i (to be inverted), and one at i == m: the index of z on the domain, or none (m >= n)
+__global__ void __launch_bounds__(PT) k_bary_denominators(uint32_t* __restrict__ d, uint32_t n, uint32_t m, PowTab root, Limbs9 z_m256, Limbs9 step_m261)
+{
+    const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    Limbs9 one256;
+#pragma unroll
+    for (int k = 0; k < NL; k++) one256.d[k] = Fr::ONE_M256[k];
+    FrM x = pow_tab(root, t, one256); // memory form
+    const FrC step = cst(step_m261), z = cst(z_m256), one = fe_from<Fr>(Fr::ONE_M256);
+    for (uint32_t i = t; i < n; i += nt) {
+        if (i == m) stv(d, i, one);
+        else stv(d, i, sub(z, x));
+        x = mul(x, step);
+    }
+}
+// partial[y][block] = the workgroup's share of sum_i a_i x_i over polynomial y (blockIdx.y), thread t owning i = t, t + T, ...:
+//   off the domain (m >= n)  a = v,  x_i = w^i inv_i      (start_m261 = 2^5: the factor a product of three memory-form values lacks)
+//   on it                    a = q,  x_i = w^(i - m), the term i == m left out      (start_m261 = w^-m)
+// One shared reduction per term: acc <- t x + acc * 1 keeps the (1, 2) bound of a fresh product.
+__global__ void __launch_bounds__(PT) k_bary_dot(const uint32_t* __restrict__ a, size_t stride, const uint32_t* __restrict__ inv, uint32_t n, uint32_t m,
+                                                 PowTab root, Limbs9 start_m261, Limbs9 step_m261, uint32_t* __restrict__ partial)
+{
+    __shared__ uint32_t sh[NL * PT];
+    const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
+    a += (size_t)blockIdx.y * stride * 8;
+    const FrC one = fe_from<Fr>(Fr::ONE);
+    FrM acc = mul(fe_zero<Fr>(), one);
+    if (t < n) {
+        FrM x = pow_tab(root, t, start_m261);
+        const FrC step = cst(step_m261);
+        if (m >= n) {
+            for (uint32_t i = t; i < n; i += nt) {
+                acc = mul_add(mul(ldv(a, i), ldv(inv, i)), x, acc, one);
+                x = mul(x, step);
+            }
+        } else {
+            for (uint32_t i = t; i < n; i += nt) {
+                if (i != m) acc = mul_add(ldv(a, i), x, acc, one);
+                x = mul(x, step);
+            }
+        }
+    }
+    block_sum(partial, (size_t)blockIdx.y * gridDim.x + blockIdx.x, acc, sh);
+}
+// one workgroup per polynomial: the sum of its partials times c, to slot[y] (off the domain: c = (z^n - 1) / n, the value f(z)) or to element m of the
+// quotient (on it: c = -1); sums: batch x 32 bytes of workspace
+__global__ void __launch_bounds__(PT) k_bary_finish(const uint32_t* __restrict__ partial, uint32_t blocks, uint32_t* __restrict__ sums, Limbs9 c_m261,
+                                                    uint32_t* __restrict__ dst, size_t dst_stride, uint32_t dst_index)
+{
+    __shared__ uint32_t sh[NL * PT];
+    const uint32_t y = blockIdx.x;
+    sum_small_body(partial + (size_t)y * blocks * 8, blocks, sums + (size_t)y * 8, sh);
+    if (threadIdx.x == 0) stv(dst + (size_t)y * dst_stride * 8, dst_index, mul(ldv(sums, y), cst(c_m261))); // its own store, read back
+}
+// q[i] = (slot[y] - v[i]) inv[i]; on the domain element m is k_bary_finish's.  q may be v: every element is read by the thread that writes it
+__global__ void __launch_bounds__(PT) k_bary_quotient(const uint32_t* v, uint32_t* q, size_t stride, const uint32_t* __restrict__ inv,
+                                                      const uint32_t* __restrict__ slot, uint32_t n, uint32_t m)
+{
+    const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    v += (size_t)blockIdx.y * stride * 8;
+    q += (size_t)blockIdx.y * stride * 8;
+    const FrV y = ldv(slot, blockIdx.y);
+    for (uint32_t i = t; i < n; i += nt)
+        if (i != m) stv(q, i, mulv(sub(y, ldv(v, i)), ldv(inv, i)));
+}
+
 // prover.cpp:520-528 + arithmetic_widget.cpp:106-126: r[i] = sum_j c_j p_j[i] over the seven coefficient-form polynomials
 __device__ __forceinline__ void lincomb_body(const LinCombArgs& A)
 {
@@ -1212,6 +1284,71 @@ int lagrange_l1_fft(uint64_t* d_l1, uint64_t* d_tmp, int log2n, int log2N, Scrat
     }
     k_l1_scale<<<pw_blocks(N), PT, 0, st>>>((uint32_t*)d_l1, (uint32_t)N, k, s[0], s[1], s[2], s[3]);
     HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+
+// Evaluation and opening of `batch` polynomials given by their values on the size-2^log2n domain (polynomial b at d_values + b * stride elements), at one
+// z (canonical; on_domain / m: the host's verdict, host_lagrange_open.hpp).  ONE inversion for the whole batch: the denominators z - w^i are shared.
+//   off the domain   denominators, batch_invert, dot (v_i w^i inv_i), finish (* (z^n - 1) / n -> slot b), quotient (slot b - v_i) inv_i
+//   on it            denominators (one at m), batch_invert, v_m -> slot b by a copy, quotient (all but m), dot (q_i w^(i - m)), finish (* -1 -> q_m);
+//                    without a quotient only the copy
+// d_quotient: null (evaluation only), d_values itself, or a buffer that does not overlap it.  h_out: null, or batch values read back (the only
+// synchronisation besides batch_invert's).  d_tmp: n elements.  The scratch holds batch_invert's share first, then the inverses, the partials and the slots.
+// slot b = element m of polynomial b, as it stands
+static hipError_t bary_stash(uint32_t* d_slot, const uint64_t* d_vm, size_t stride, int batch, hipStream_t st)
+{
+    if (batch > 1 && stride * 32 <= 0x7fffffffu) // one strided copy while the pitch is one the runtime takes
+        return hipMemcpy2DAsync(d_slot, 32, d_vm, stride * 32, 32, (size_t)batch, hipMemcpyDeviceToDevice, st);
+    for (int b = 0; b < batch; b++)
+        if (hipError_t e = hipMemcpyAsync(d_slot + 8 * (size_t)b, d_vm + 4 * (size_t)b * stride, 32, hipMemcpyDeviceToDevice, st)) return e;
+    return hipSuccess;
+}
+int bary_open(const uint64_t* d_values, uint64_t* d_quotient, int log2n, size_t stride, int batch, const host::Fr& z, bool on_domain, size_t m,
+              uint64_t* d_tmp, host::Fr* h_out, Scratch& S, hipStream_t st)
+{
+    const size_t n = (size_t)1 << log2n;
+    const uint32_t dblocks = eval_blocks(n), blocks = strided_blocks(n), mm = on_domain ? (uint32_t)m : 0xffffffffu;
+    int rc = ensure_pinned(S);
+    if (rc) return rc;
+    const size_t off_inv = (scan_scratch_bytes(n) + 64 + n * 32 + 64 + 63) & ~(size_t)63; // behind everything batch_invert asks for: its ensure() keeps the buffer
+    const size_t off_partial = off_inv + n * 32, off_slot = off_partial + (size_t)batch * dblocks * 32, off_sums = off_slot + (size_t)batch * 32;
+    rc = S.ensure(off_sums + (size_t)batch * 32);
+    if (rc) return rc;
+    uint32_t *d_inv = (uint32_t*)(S.base + off_inv), *d_partial = (uint32_t*)(S.base + off_partial), *d_slot = (uint32_t*)(S.base + off_slot),
+             *d_sums = (uint32_t*)(S.base + off_sums);
+    const uint32_t *v = (const uint32_t*)d_values;
+    uint32_t* q = (uint32_t*)d_quotient;
+    if (!on_domain || q) {
+        const host::Fr root = host::fr_root_of_unity(log2n);
+        const PowTab T = make_powtab(root);
+        const Limbs9 dstep = host::limbs_m261(host::fr_pow(root, (uint64_t)dblocks * PT));
+        const dim3 dgrid(dblocks, (uint32_t)batch), qgrid(blocks, (uint32_t)batch);
+        k_bary_denominators<<<blocks, PT, 0, st>>>(d_inv, (uint32_t)n, mm, T, host::limbs_m256(z), host::limbs_m261(host::fr_pow(root, (uint64_t)blocks * PT)));
+        HIPCHK(launch_check());
+        rc = batch_invert((uint64_t*)d_inv, d_tmp, n, S, st);
+        if (rc) return rc;
+        if (!on_domain) {
+            k_bary_dot<<<dgrid, PT, 0, st>>>(v, stride, d_inv, (uint32_t)n, mm, T, host::limbs_m261(host::fr_from_u64(32)), dstep, d_partial);
+            k_bary_finish<<<batch, PT, 0, st>>>(d_partial, dblocks, d_sums, host::limbs_m261(host::lagrange_open_scale(z, log2n)), d_slot, 1, 0);
+            if (q) k_bary_quotient<<<qgrid, PT, 0, st>>>(v, q, stride, d_inv, d_slot, (uint32_t)n, mm);
+        } else {
+            HIPCHK(bary_stash(d_slot, d_values + 4 * m, stride, batch, st)); // before element m can be overwritten (q may be v)
+            k_bary_quotient<<<qgrid, PT, 0, st>>>(v, q, stride, d_inv, d_slot, (uint32_t)n, mm);
+            k_bary_dot<<<dgrid, PT, 0, st>>>(q, stride, d_inv, (uint32_t)n, mm, T, host::limbs_m261(host::fr_inv(host::fr_pow(root, (uint64_t)m))), dstep, d_partial);
+            k_bary_finish<<<batch, PT, 0, st>>>(d_partial, dblocks, d_sums, host::limbs_m261(host::fr_neg(host::fr_one())), q, stride, mm);
+        }
+        HIPCHK(launch_check());
+    } else {
+        HIPCHK(bary_stash(d_slot, d_values + 4 * m, stride, batch, st));
+    }
+    if (!h_out) return BBGPU_OK;
+    HIPCHK(d2h_async(S.h_pinned, d_slot, (size_t)batch * 32, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int b = 0; b < batch; b++) {
+        host::Fr y;
+        memcpy(y.d, (const uint8_t*)S.h_pinned + 32 * (size_t)b, 32);
+        h_out[b] = host::fr_mul(y, host::fr_one()); // v_m is the caller's representative: canonical out
+    }
     return BBGPU_OK;
 }
 

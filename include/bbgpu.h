@@ -314,6 +314,47 @@ int bbgpu_divide_by_pseudo_vanishing_device(uint64_t* d_coeffs, size_t n_src, si
 /* waffle::compute_permutation_lagrange_base_single(output, permutation, small_domain) (permutation.hpp:15-87) */
 int bbgpu_permutation_lagrange_base_device(uint64_t* d_out, const uint32_t* d_mapping, size_t n, void* hip_stream);
 
+/* Evaluation and opening in evaluation form: `batch` polynomials of degree < n given by their VALUES v_i = f(w^i) on the size-n domain (w =
+ * fr_root_of_unity(log2 n), the root the transforms and bbgpu_srs_lagrange use), value i of polynomial b at d_values[(b * stride_elems + i) * 4], at one
+ * point z -- without the inverse transform the coefficient-form entries above need first.  The reference has no counterpart.  For z outside the domain
+ *   f(z) = (z^n - 1) / n * sum_i v_i w^i / (z - w^i)          q_i = (f(z) - v_i) / (z - w^i)
+ * and for z = w^m:  f(z) = v_m,  q_i = (v_m - v_i) / (z - w^i) for i != m,  q_m = -sum_{i != m} q_i w^(i - m).  The host decides which case holds before
+ * anything is launched (z reduced, z^n == 1 by log2 n squarings, then m bit by bit), so z on the domain -- given as any representative, w^m + r
+ * included -- is legal and exact.
+ *   out / f_of_z  batch x 4 words of HOST memory: bit for bit what bbgpu_fr_evaluate_device returns for ifft(values_b).  f_of_z may be NULL.
+ *   d_quotient    the values of (f_b(X) - f_b(z)) / (X - z) on the domain, in the layout (and with the stride) of d_values: bit for bit the fft of what
+ *                 bbgpu_kate_opening_device writes for ifft(values_b), so its commitment over a bbgpu_srs_lagrange handle is the opening proof.  It may
+ *                 alias d_values only if it IS d_values; elements between the polynomials (stride_elems > n) are neither read nor written.
+ *   errors        BBGPU_ERR_SIZE: n not a power of two in [2, 2^24], batch outside 1..64, stride_elems < n; BBGPU_ERR_ARG: null d_values, d_quotient, z
+ *                 or out -- all refused before a device is bound.  The device pointers themselves are the caller's responsibility, as for every helper
+ *                 of this section: they are not validated.
+ * One inversion per call, shared by the polynomials of the batch (csrc/poly.hip bary_open: k_bary_denominators, the batch inversion of
+ * bbgpu_fr_batch_invert_device, k_bary_dot + k_bary_finish, k_bary_quotient; the powers of w are made in the lanes, no table of roots is kept or read).
+ * The batch inversion synchronises the stream ONCE for its host inversion, so these entries are not fully asynchronous; when f_of_z == NULL nothing else
+ * synchronises, otherwise one read-back does.  bbgpu_fr_evaluate_lagrange_device at z on the domain is a copy of v_m alone.  They run on context 0 and use
+ * the library's polynomial scratch (bbgpu_memory_info.staging_bytes: about 3 n x 32 bytes + 8 KiB per polynomial of the batch); they keep no per-domain table.
+ * Every allocation, read-back and launch check passes the fault-injection funnels (a warm call: no allocation, no upload, one read-back when values are
+ * returned, five launch checks -- the denominators, the two scans and the scaling of the inversion, the chain of dot, finish and quotient).
+ * Cost on one MI355X (tools/lagrange_open_bench.py, profiles/lagrange_open.txt; wall ms per call sequence, these entries against the PARENT library's
+ * bbgpu_ntt_device_batch(IFFT) + one coefficient-form entry per polynomial, alternating in one process; the transform path is not charged the copy that
+ * keeping the values would cost):
+ *                                 2^16 values                      2^20 values
+ *                            batch 1         batch 8          batch 1         batch 8
+ *   evaluate              0.182 / 0.083   0.187 / 0.418    0.351 / 0.163   0.554 / 1.120
+ *   open                  0.189 / 0.130   0.202 / 0.773    0.374 / 0.266   0.723 / 1.932
+ *   open + commitments    0.472 / 0.420   2.251 / 2.826    1.645 / 1.551   10.76 / 12.03
+ * Evaluate, batch 1: the transform path wins at both sizes (by 0.10 and 0.19 ms) -- a call here is the batch inversion, two product scans and a
+ * synchronisation, against a transform of 0.03 .. 0.1 ms; a caller with ONE polynomial should take IFFT + bbgpu_fr_evaluate_device.  Evaluate, batch 8:
+ * this entry wins (2.2x and 2.0x): the inversion is shared, its time hardly grows with the batch, the other path pays per polynomial.  Open, batch 1: the
+ * transform path wins again (by 0.06 and 0.11 ms), and still does with the commitment behind it (by 0.05 and 0.09 ms, beyond the spreads of 0.02 and
+ * 0.06): take IFFT + bbgpu_kate_opening_device for one polynomial when the monomial table is resident anyway.  Open, batch 8: this entry wins (3.8x and
+ * 2.7x; by 0.58 and 1.27 ms of a call sequence that the eight MSMs dominate once the commitments are counted).  What the entries buy at
+ * batch 1 is not time: the monomial table and the transform's tables need not be resident. */
+int bbgpu_fr_evaluate_lagrange_device(const uint64_t* d_values, size_t n, size_t stride_elems, int batch, const uint64_t z[4],
+                                      uint64_t* out /* batch x 4, host */, void* hip_stream);
+int bbgpu_kate_opening_lagrange_device(const uint64_t* d_values, uint64_t* d_quotient, size_t n, size_t stride_elems, int batch, const uint64_t z[4],
+                                       uint64_t* f_of_z /* batch x 4, host; may be NULL */, void* hip_stream);
+
 /* The same on host buffers (copied to the device and back): what the C++ shim forwards the co-resident functions of the replaced
  * translation unit to, so that polynomial_arithmetic.o / scalar_multiplication.o can be left out of the link altogether. */
 int bbgpu_fr_evaluate(const uint64_t* coeffs, size_t n, const uint64_t z[4], uint64_t out[4]);
@@ -488,6 +529,11 @@ int bbgpu_host_ntt(uint64_t* coeffs, size_t n, int kind, const uint64_t* constan
 int bbgpu_host_fr_evaluate(const uint64_t* coeffs, size_t n, const uint64_t z[4], uint64_t out[4]);
 int bbgpu_host_kate_opening(const uint64_t* src, uint64_t* dest, size_t n, const uint64_t z[4], uint64_t f_of_z[4]);
 int bbgpu_host_lagrange_l1_fft(uint64_t* l_1, size_t n_src, size_t n_target);
+/* the host twins of the two entries on values (csrc/host_lagrange_open.hpp): plain loops with Montgomery's trick, the same argument verdict, host buffers
+ * throughout; results are canonical field elements, so they equal the device entries' bit for bit.  No HIP call, no lock, re-entrant */
+int bbgpu_host_fr_evaluate_lagrange(const uint64_t* values, size_t n, size_t stride_elems, int batch, const uint64_t z[4], uint64_t* out);
+int bbgpu_host_kate_opening_lagrange(const uint64_t* values, uint64_t* quotient, size_t n, size_t stride_elems, int batch, const uint64_t z[4],
+                                     uint64_t* f_of_z /* may be NULL */);
 int bbgpu_host_divide_by_pseudo_vanishing(uint64_t* coeffs, size_t n_src, size_t n_target);
 /* bbgpu_plonk_check_witness on the host, for a caller without a GPU: the same definition, the same report; circuit->w_l / w_r / w_o are the witness.
  * Argument errors as bbgpu_plonk_prover_create (BBGPU_ERR_ARG: a null field, a widget's selectors given in part; BBGPU_ERR_SIZE: n). */
@@ -651,6 +697,48 @@ int bbgpu_srs_lagrange(int srs_handle, size_t n, uint64_t* host_endo_table_out /
  * A row off the curve or an output row at infinity: the report, BBGPU_ERR_ARG and an untouched table_out. */
 int bbgpu_host_srs_lagrange(const uint64_t* points_endo_table, size_t n, uint64_t* table_out /* 2n entries, may alias */,
                             bbgpu_srs_lagrange_report* out /* may be NULL */);
+
+/* ---- is this table the Lagrange form of that string?  (two MSMs and one transform; no pairing) ------
+ * bbgpu_srs_lagrange is expensive, so its table is made once, exported (host_endo_table_out) and registered again in later runs -- after which nothing
+ * above can say whether the registered rows R_i still are the L_i of the string: bbgpu_srs_check fails such a table by construction (its rows are not powers
+ * of x), and a wrong row yields BBGPU_OK and a commitment the verifier rejects.  bbgpu_srs_lagrange_check answers it for rows [0, n) of both handles:
+ *   curve test   every row of the Lagrange table satisfies y^2 = x^3 + 3 (the pass of bbgpu_srs_check; row 0 is not compared with the generator)
+ *   basis test   with the multipliers rho_i of bbgpu_srs_check (same derivation from the seed, same seed rules, i < n), A = sum_i rho_i R_i over the
+ *                Lagrange handle and B = sum_j ifft(rho)_j P_j over the monomial handle (a copy of rho transformed in place by BBGPU_IFFT; two MSM
+ *                tickets in flight) are the same point iff R_i = L_i for every i, up to a soundness error of about 2^-253: B = sum_i rho_i L_i, and a
+ *                non-zero combination of the differences R_i - L_i vanishes at random multipliers with that chance.  The two normalised points are
+ *                compared on the host.
+ * Whether the monomial string itself is honest is bbgpu_srs_check's question, not this entry's.
+ * BBGPU_SRS_LAGRANGE_CHECK_LOCATE: after a failed basis test the prefix length m is bisected -- A over the first m multipliers and rows, B over the
+ * transform of rho with the entries from m on zeroed; prefix m passes iff every row below m is right -- at most ceil(log2 n) more rounds of one transform
+ * and two MSMs, no buffer beyond the copy.
+ * Return codes: BBGPU_OK means the check RAN; the verdict is in the report (good iff bad_points == 0 && basis_ok).  BBGPU_ERR_SIZE: n not a power of two
+ * in [2, 2^22] or larger than either table.  BBGPU_ERR_ARG: an unknown handle, null out, unknown flag bits.  All are refused before a device is bound.
+ * The entry runs on context 0 under the library mutex; the multipliers and their copy (2 n x 32 bytes) live in the staging of bbgpu_srs_check, counted in
+ * bbgpu_memory_info.staging_bytes.  After any failure no MSM ticket is outstanding and both handles stay usable; neither table is written.  With the same
+ * seed the report equals bbgpu_host_srs_lagrange_check's field for field, a and b included.  A warm honest check of 4096 rows without LOCATE passes no
+ * allocation, one upload, one read-back and six launch checks (the curve pass, the multipliers, the transform's two passes, one per MSM) and
+ * synchronises twice before the tickets are issued (the curve verdict, the transformed copy).
+ * Cost on one MI355X (tools/lagrange_open_bench.py, profiles/lagrange_open.txt; wall, one box): 2^16 rows 0.479 ms against 0.381 ms for two device MSMs in
+ * flight over the same handles alone, 2^20 rows 2.965 against 2.580 ms: the check costs its two MSMs plus 0.10 / 0.39 ms for the curve pass, the
+ * multipliers, the copy, the transform and the two synchronisations; no pairing, so no host tail. */
+#define BBGPU_SRS_LAGRANGE_CHECK_LOCATE 1
+typedef struct {
+    uint64_t n;                 /* rows checked: rows [0, n) of both handles */
+    uint64_t bad_points;        /* rows of the Lagrange table off the curve */
+    uint64_t first_bad_point;   /* smallest such row, UINT64_MAX if none */
+    uint32_t basis_checked;     /* the basis test ran: bad_points == 0 */
+    uint32_t basis_ok;          /* sum_i rho_i R_i == sum_j ifft(rho)_j P_j */
+    uint64_t first_bad_row;     /* with BBGPU_SRS_LAGRANGE_CHECK_LOCATE and !basis_ok: smallest i whose row is not L_i, else UINT64_MAX */
+    uint64_t seed[4];           /* the seed used (the caller's, or the one drawn), so that a finding can be replayed */
+    uint64_t a[8], b[8];        /* the two sums, affine (infinity flag honoured; infinity when the test did not run) */
+} bbgpu_srs_lagrange_check_report;
+int bbgpu_srs_lagrange_check(int lagrange_handle, int monomial_handle, size_t n, const uint64_t seed[4] /* NULL: OS randomness */, int flags,
+                             bbgpu_srs_lagrange_check_report* out);
+/* the same definition over the even entries of two 2n-entry endo tables, on the host (csrc/host_srs_lagrange_check.hpp: the curve loop, the transform and
+ * the bucket method of the bbgpu_host_* family, the same verdict and bisection); no HIP call, no lock */
+int bbgpu_host_srs_lagrange_check(const uint64_t* lagrange_endo_table, const uint64_t* monomial_endo_table, size_t n, const uint64_t seed[4], int flags,
+                                  bbgpu_srs_lagrange_check_report* out);
 
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
