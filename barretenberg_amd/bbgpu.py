@@ -65,6 +65,8 @@ C_ABI_SYMBOLS = [
     "bbgpu_srs_lagrange", "bbgpu_host_srs_lagrange",
     "bbgpu_fr_evaluate_lagrange_device", "bbgpu_kate_opening_lagrange_device", "bbgpu_host_fr_evaluate_lagrange", "bbgpu_host_kate_opening_lagrange",
     "bbgpu_srs_lagrange_check", "bbgpu_host_srs_lagrange_check",
+    "bbgpu_lagrange_opening_begin", "bbgpu_lagrange_opening_evaluate", "bbgpu_lagrange_opening_open", "bbgpu_lagrange_opening_open_folded",
+    "bbgpu_lagrange_opening_end", "bbgpu_fr_fold_device", "bbgpu_host_fr_fold", "bbgpu_host_kate_opening_lagrange_folded", "bbgpu_host_kzg_check_openings",
     "bbgpu_selftest_plonk_round",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
@@ -344,6 +346,52 @@ class BbGpu:
         self._chk(self.lib.bbgpu_kate_opening_lagrange_device(d_values, d_quotient, n, n if stride is None else stride, batch,
                                                               _ptr(np.ascontiguousarray(z, dtype=np.uint64)), _ptr(f) if want_f else None, stream or 0))
         return f
+
+    # ---- opening sessions: several points over one shared inversion, folded openings (bbgpu_lagrange_opening_*) ----
+    def lagrange_opening_begin(self, n, z, points=None, stream=None):
+        """bbgpu_lagrange_opening_begin: z (points, 4) -> session handle; the inverses of all points by one launch and one batch inversion"""
+        z = None if z is None else np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+        points = (z.shape[0] if z is not None else 1) if points is None else points
+        self.lib.bbgpu_lagrange_opening_begin.argtypes = [C.c_size_t, u64p, C.c_int, C.c_void_p]
+        return self._chk(self.lib.bbgpu_lagrange_opening_begin(n, _ptr(z) if z is not None else None, points, stream or 0))
+
+    def lagrange_opening_evaluate(self, session, point, d_values, n, batch=1, stride=None, stream=None):
+        """bbgpu_lagrange_opening_evaluate -> (batch, 4): what evaluate_lagrange_device returns at the session's z_point (n: the session's, for the default stride)"""
+        out = np.zeros((max(int(batch), 1), 4), dtype=np.uint64)
+        self.lib.bbgpu_lagrange_opening_evaluate.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, u64p, C.c_void_p]
+        self._chk(self.lib.bbgpu_lagrange_opening_evaluate(session, point, d_values, n if stride is None else stride, batch, _ptr(out), stream or 0))
+        return out
+
+    def lagrange_opening_open(self, session, point, d_values, d_quotient, n, batch=1, stride=None, want_f=True, stream=None):
+        """bbgpu_lagrange_opening_open: what kate_opening_lagrange_device writes and returns at the session's z_point; None with want_f=False"""
+        f = np.zeros((max(int(batch), 1), 4), dtype=np.uint64) if want_f else None
+        self.lib.bbgpu_lagrange_opening_open.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, u64p, C.c_void_p]
+        self._chk(self.lib.bbgpu_lagrange_opening_open(session, point, d_values, d_quotient, n if stride is None else stride, batch,
+                                                       _ptr(f) if want_f else None, stream or 0))
+        return f
+
+    def lagrange_opening_open_folded(self, session, point, d_values, n, gamma, d_quotient, batch=None, stride=None, accumulate=False, want_f=True, stream=None):
+        """bbgpu_lagrange_opening_open_folded: d_quotient (n elements) = or += the opening of sum_b gamma_b f_b at the session's z_point; returns F(z) as
+        (4,), or None with want_f=False.  gamma (batch, 4); batch defaults to its rows"""
+        g = None if gamma is None else np.ascontiguousarray(gamma, dtype=np.uint64).reshape(-1, 4)
+        batch = g.shape[0] if batch is None else batch
+        f = np.zeros(4, dtype=np.uint64) if want_f else None
+        self.lib.bbgpu_lagrange_opening_open_folded.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, u64p, C.c_void_p, C.c_int, u64p, C.c_void_p]
+        self._chk(self.lib.bbgpu_lagrange_opening_open_folded(session, point, d_values, n if stride is None else stride, batch, _ptr(g) if g is not None else None,
+                                                              d_quotient, int(bool(accumulate)), _ptr(f) if want_f else None, stream or 0))
+        return f
+
+    def lagrange_opening_end(self, session):
+        self.lib.bbgpu_lagrange_opening_end.argtypes = [C.c_int]
+        self._chk(self.lib.bbgpu_lagrange_opening_end(session))
+
+    def fold_device(self, d_out, d_values, n, gamma, batch=None, stride=None, accumulate=False, stream=None):
+        """bbgpu_fr_fold_device: d_out[i] = or += sum_b gamma_b v_{b,i}; any n in [1, 2^24]"""
+        g = None if gamma is None else np.ascontiguousarray(gamma, dtype=np.uint64).reshape(-1, 4)
+        batch = g.shape[0] if batch is None else batch
+        self.lib.bbgpu_fr_fold_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, u64p, C.c_int, C.c_void_p]
+        self._chk(self.lib.bbgpu_fr_fold_device(d_out, d_values, n, n if stride is None else stride, batch, _ptr(g) if g is not None else None,
+                                                int(bool(accumulate)), stream or 0))
 
     def compute_lagrange_polynomial_fft_device(self, d_l_1, n_src, n_target, stream=None):
         """polynomial_arithmetic::compute_lagrange_polynomial_fft (:381-476)"""
@@ -812,6 +860,46 @@ class BbGpu:
         self.lib.bbgpu_host_kate_opening_lagrange.argtypes = [u64p, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, u64p]
         self._chk(self.lib.bbgpu_host_kate_opening_lagrange(_ptr(values), _ptr(out), n, stride, batch, _ptr(np.ascontiguousarray(z, dtype=np.uint64)), _ptr(f)))
         return out, f
+
+    def host_fold(self, values, gamma, n=None, batch=None, stride=None, out=None):
+        """bbgpu_host_fr_fold -> (n, 4): sum_b gamma_b v_b, or `out` with that added to it"""
+        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        g = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(-1, 4)
+        batch = g.shape[0] if batch is None else batch
+        stride = values.shape[0] // max(int(batch), 1) if stride is None else stride
+        n = stride if n is None else n
+        acc = out is not None
+        out = np.zeros((max(int(n), 1), 4), dtype=np.uint64) if out is None else out
+        self.lib.bbgpu_host_fr_fold.argtypes = [u64p, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, C.c_int]
+        self._chk(self.lib.bbgpu_host_fr_fold(_ptr(out), _ptr(values), n, stride, batch, _ptr(g), int(acc)))
+        return out
+
+    def host_kate_opening_lagrange_folded(self, values, gamma, z, n=None, batch=None, stride=None, out=None):
+        """bbgpu_host_kate_opening_lagrange_folded -> (quotient (n, 4), F(z) as (4,)); with `out` the quotient is added to it"""
+        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        g = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(-1, 4)
+        batch = g.shape[0] if batch is None else batch
+        stride = values.shape[0] // max(int(batch), 1) if stride is None else stride
+        n = stride if n is None else n
+        acc = out is not None
+        out = np.zeros((max(int(n), 1), 4), dtype=np.uint64) if out is None else out
+        f = np.zeros(4, dtype=np.uint64)
+        self.lib.bbgpu_host_kate_opening_lagrange_folded.argtypes = [u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, u64p, u64p, C.c_int, u64p]
+        self._chk(self.lib.bbgpu_host_kate_opening_lagrange_folded(_ptr(values), n, stride, batch, _ptr(g), _ptr(np.ascontiguousarray(z, dtype=np.uint64)),
+                                                                   _ptr(out), int(acc), _ptr(f)))
+        return out, f
+
+    def host_kzg_check_openings(self, commitments, z, y, proofs, g2_x, seed=None):
+        """bbgpu_host_kzg_check_openings: k claims (C_t, z_t, y_t, pi_t) -> bool, by one pairing product of two pairs; commitments / proofs (k, 8) affine"""
+        cs = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
+        ps = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8)
+        zs, ys = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4), np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 4)
+        assert cs.shape[0] == ps.shape[0] == zs.shape[0] == ys.shape[0]
+        g2, sd, g2p, sdp, _ = self._srs_check_args(g2_x, seed, False)
+        ok = C.c_int(0)
+        self.lib.bbgpu_host_kzg_check_openings.argtypes = [u64p, u64p, u64p, u64p, C.c_size_t, u64p, u64p, C.POINTER(C.c_int)]
+        self._chk(self.lib.bbgpu_host_kzg_check_openings(_ptr(cs), _ptr(zs), _ptr(ys), _ptr(ps), cs.shape[0], g2p, sdp, C.byref(ok)))
+        return ok.value == 1
 
     def host_lagrange_l1_fft(self, n_src, n_target):
         out = np.zeros((n_target, 4), dtype=np.uint64)

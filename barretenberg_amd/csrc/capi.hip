@@ -30,6 +30,7 @@
 #include "host_srs_check.hpp"
 #include "host_srs_update.hpp"
 #include "host_srs_lagrange.hpp"
+#include "host_kzg_check.hpp"
 #include "host_lagrange_open.hpp"
 #include "host_srs_lagrange_check.hpp"
 #include "host_plonk_verify.hpp"
@@ -1287,6 +1288,31 @@ int run_on_contexts(int m, const std::function<int(int)>& fn)
     return rc;
 }
 
+// ---- opening sessions (bbgpu_lagrange_opening_*, below): the inverses 1 / (z_t - w^i) of up to BBGPU_OPENING_MAX_POINTS points on one domain, made once by
+// begin and kept in an allocation of the session's own until end or bbgpu_shutdown.  Context 0, under g_mu.
+struct OpeningSession {
+    bool live = false;
+    int log2n = 0, points = 0;
+    host::Fr z[BBGPU_OPENING_MAX_POINTS]; // canonical
+    bool on[BBGPU_OPENING_MAX_POINTS];    // z_t = w^(m_t): the host's verdict, taken once
+    size_t m[BBGPU_OPENING_MAX_POINTS];
+    uint64_t* d_inv = nullptr;            // points x n elements, point-major
+    size_t bytes = 0;
+};
+OpeningSession g_opening[BBGPU_OPENING_MAX_SESSIONS];
+size_t opening_session_bytes()
+{
+    size_t b = 0;
+    for (const auto& o : g_opening)
+        if (o.live) b += o.bytes;
+    return b;
+}
+void opening_release(OpeningSession& o)
+{
+    if (o.live && o.d_inv) (void)dev_free(o.d_inv);
+    o = OpeningSession();
+}
+
 // Everything the current context holds, on the thread that drives it (its device is that thread's current one).  Context 0 (primary) also owns the
 // resident prover and the transforms' tables.
 void release_context(bool primary)
@@ -1294,6 +1320,8 @@ void release_context(bool primary)
     Context& C = ctx();
     if (!C.ready) return;
     if (primary) plonk_release_all_locked();
+    if (primary)
+        for (auto& o : g_opening) opening_release(o);
     // nothing may still be reading the pinned staging buffers or a slot's workspace when they are freed: collect what is in flight
     // (an MSM a caller never waited for, a copy queued before an error return) and drain every stream first
     for (int k = 0; k < Context::NSLOT; k++)
@@ -1384,7 +1412,7 @@ void add_context_memory(const Context& C, bool primary, bbgpu_memory_info* out)
         if (sl.ws.h_out) out->pinned_host_bytes += (uint64_t)MSM_HOUT_GROUPS * 64 * 128;
     }
     out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap + C.srs_check_cap + C.verify_cap;
-    if (primary) out->staging_bytes += plonk_lane_bytes(); // the resident prover runs on context 0
+    if (primary) out->staging_bytes += plonk_lane_bytes() + opening_session_bytes(); // the resident prover and the opening sessions live on context 0
     for (int k = 0; k < Context::HOST_RING; k++)
         if (C.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
 }
@@ -1757,6 +1785,162 @@ int bbgpu_kate_opening_lagrange_device(const uint64_t* d_values, uint64_t* d_quo
     return lagrange_open_device("kate_opening_lagrange", d_values && d_quotient && z, d_values, d_quotient, n, stride_elems, batch, z, f_of_z, hip_stream);
 }
 
+/* ---- opening sessions: several points over ONE shared inversion, folded openings (poly.hip bary_inverses / bary_open_with / bary_open_folded) ---- */
+int bbgpu_lagrange_opening_begin(size_t n, const uint64_t* z, int points, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    const int log2n = host::lagrange_open_log2(n);
+    if (log2n < 1 || points < 1 || points > BBGPU_OPENING_MAX_POINTS || (size_t)points * n > ((size_t)1 << host::LAGRANGE_OPEN_MAX_LOG2)) {
+        set_error("lagrange_opening_begin: n = %zu must be a power of two in [2, 2^%d], points = %d in 1..%d and points x n at most 2^%d", n,
+                  host::LAGRANGE_OPEN_MAX_LOG2, points, BBGPU_OPENING_MAX_POINTS, host::LAGRANGE_OPEN_MAX_LOG2);
+        return BBGPU_ERR_SIZE;
+    }
+    if (!z) {
+        set_error("lagrange_opening_begin: null z");
+        return BBGPU_ERR_ARG;
+    }
+    int slot = -1;
+    for (int k = 0; k < BBGPU_OPENING_MAX_SESSIONS && slot < 0; k++)
+        if (!g_opening[k].live) slot = k;
+    if (slot < 0) {
+        set_error("lagrange_opening_begin: %d sessions are live", BBGPU_OPENING_MAX_SESSIONS);
+        return BBGPU_ERR_STATE;
+    }
+    if (int rc = ensure_init()) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = shared_begin(st)) return rc;
+    SharedGuard shared_guard_{ st };
+    OpeningSession o;
+    o.log2n = log2n;
+    o.points = points;
+    for (int t = 0; t < points; t++) {
+        o.z[t] = host::fr_mul(load_fr(z + 4 * t), host::fr_one());
+        o.m[t] = 0;
+        o.on[t] = host::lagrange_open_on_domain(o.z[t], log2n, &o.m[t]);
+    }
+    o.bytes = (size_t)points * n * 32;
+    if (int rc = grow(&ctx().d_poly_tmp, &ctx().poly_tmp_cap, o.bytes)) return rc;
+    HIPCHK(dev_malloc((void**)&o.d_inv, o.bytes));
+    if (int rc = poly::bary_inverses(o.d_inv, log2n, points, o.z, o.on, o.m, ctx().d_poly_tmp, ctx().poly_scratch, st)) {
+        (void)dev_free(o.d_inv); // (waits for the device: nothing queued still writes it)
+        return rc;
+    }
+    o.live = true;
+    g_opening[slot] = o;
+    return slot;
+}
+// the verdict the session calls share, in this order: batch, the call's own pointers, the session and its point, the stride (against the session's n)
+static int opening_call_args(const char* what, int session, int point, bool ptr_ok, size_t stride_elems, int batch, OpeningSession** out)
+{
+    if (batch < 1 || batch > host::LAGRANGE_OPEN_MAX_BATCH) {
+        set_error("%s: batch = %d must be in 1..%d", what, batch, host::LAGRANGE_OPEN_MAX_BATCH);
+        return BBGPU_ERR_SIZE;
+    }
+    if (!ptr_ok) {
+        set_error("%s: null values / quotient / gamma / out", what);
+        return BBGPU_ERR_ARG;
+    }
+    if (session < 0 || session >= BBGPU_OPENING_MAX_SESSIONS || !g_opening[session].live) {
+        set_error("%s: unknown opening session %d", what, session);
+        return BBGPU_ERR_ARG;
+    }
+    OpeningSession& o = g_opening[session];
+    if (point < 0 || point >= o.points) {
+        set_error("%s: point %d, the session has %d", what, point, o.points);
+        return BBGPU_ERR_ARG;
+    }
+    if (stride_elems < ((size_t)1 << o.log2n)) {
+        set_error("%s: the stride (%zu) is smaller than n = %zu", what, stride_elems, (size_t)1 << o.log2n);
+        return BBGPU_ERR_SIZE;
+    }
+    *out = &o;
+    return BBGPU_OK;
+}
+static int opening_session_open(const char* what, bool ptr_ok, int session, int point, const uint64_t* d_values, uint64_t* d_quotient, size_t stride_elems,
+                                int batch, uint64_t* out, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    OpeningSession* o = nullptr;
+    if (int rc = opening_call_args(what, session, point, ptr_ok, stride_elems, batch, &o)) return rc;
+    if (int rc = ensure_init()) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = shared_begin(st)) return rc;
+    SharedGuard shared_guard_{ st };
+    std::vector<host::Fr> y(out ? (size_t)batch : 0);
+    if (int rc = poly::bary_open_with(d_values, d_quotient, o->log2n, stride_elems, batch, o->z[point], o->on[point], o->m[point],
+                                      o->d_inv + ((size_t)point << o->log2n) * 4, out ? y.data() : nullptr, ctx().poly_scratch, st))
+        return rc;
+    if (out) memcpy(out, y.data(), (size_t)batch * 32);
+    return BBGPU_OK;
+}
+int bbgpu_lagrange_opening_evaluate(int session, int point, const uint64_t* d_values, size_t stride_elems, int batch, uint64_t* out, void* hip_stream)
+{
+    return opening_session_open("lagrange_opening_evaluate", d_values && out, session, point, d_values, nullptr, stride_elems, batch, out, hip_stream);
+}
+int bbgpu_lagrange_opening_open(int session, int point, const uint64_t* d_values, uint64_t* d_quotient, size_t stride_elems, int batch, uint64_t* f_of_z,
+                                void* hip_stream)
+{
+    return opening_session_open("lagrange_opening_open", d_values && d_quotient, session, point, d_values, d_quotient, stride_elems, batch, f_of_z, hip_stream);
+}
+int bbgpu_lagrange_opening_open_folded(int session, int point, const uint64_t* d_values, size_t stride_elems, int batch, const uint64_t* gamma,
+                                       uint64_t* d_quotient, int accumulate, uint64_t folded_f_of_z[4], void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    OpeningSession* o = nullptr;
+    if (int rc = opening_call_args("lagrange_opening_open_folded", session, point, d_values && d_quotient && gamma, stride_elems, batch, &o)) return rc;
+    if (int rc = ensure_init()) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = shared_begin(st)) return rc;
+    SharedGuard shared_guard_{ st };
+    std::vector<host::Fr> g((size_t)batch);
+    for (int b = 0; b < batch; b++) g[b] = load_fr(gamma + 4 * b);
+    host::Fr f;
+    if (int rc = poly::bary_open_folded(d_values, o->log2n, stride_elems, batch, g.data(), o->z[point], o->on[point], o->m[point],
+                                        o->d_inv + ((size_t)point << o->log2n) * 4, d_quotient, accumulate != 0, folded_f_of_z ? &f : nullptr,
+                                        ctx().poly_scratch, st))
+        return rc;
+    if (folded_f_of_z) memcpy(folded_f_of_z, f.d, 32);
+    return BBGPU_OK;
+}
+int bbgpu_lagrange_opening_end(int session)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (session < 0 || session >= BBGPU_OPENING_MAX_SESSIONS || !g_opening[session].live) {
+        set_error("lagrange_opening_end: unknown opening session %d", session);
+        return BBGPU_ERR_ARG;
+    }
+    opening_release(g_opening[session]); // (dev_free waits for the device: no queued call still reads the inverses)
+    return BBGPU_OK;
+}
+
+// the verdict of the fold and its twin
+static int fold_args(const char* what, bool ptr_ok, size_t n, size_t stride_elems, int batch)
+{
+    if (!host::fold_sizes_ok(n, stride_elems, batch)) {
+        set_error("%s: n = %zu must be in [1, 2^24], batch = %d in 1..%d and the stride (%zu) no smaller than n", what, n, batch, host::LAGRANGE_OPEN_MAX_BATCH,
+                  stride_elems);
+        return BBGPU_ERR_SIZE;
+    }
+    if (!ptr_ok) {
+        set_error("%s: null out / values / gamma", what);
+        return BBGPU_ERR_ARG;
+    }
+    return BBGPU_OK;
+}
+int bbgpu_fr_fold_device(uint64_t* d_out, const uint64_t* d_values, size_t n, size_t stride_elems, int batch, const uint64_t* gamma, int accumulate,
+                         void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rc = fold_args("fr_fold", d_out && d_values && gamma, n, stride_elems, batch)) return rc;
+    if (int rc = ensure_init()) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = shared_begin(st)) return rc;
+    SharedGuard shared_guard_{ st };
+    std::vector<host::Fr> g((size_t)batch);
+    for (int b = 0; b < batch; b++) g[b] = load_fr(gamma + 4 * b);
+    return poly::fold(d_out, d_values, n, stride_elems, batch, g.data(), accumulate != 0, st);
+}
+
 int bbgpu_lagrange_l1_fft_device(uint64_t* d_l_1, size_t n_src, size_t n_target, void* hip_stream)
 {
     POLY_ENTER(d_l_1);
@@ -1946,6 +2130,19 @@ int bbgpu_host_kate_opening_lagrange(const uint64_t* values, uint64_t* quotient,
     host::lagrange_open_host(values, quotient, n, stride_elems, batch, load_fr(z), f_of_z);
     return BBGPU_OK;
 }
+int bbgpu_host_fr_fold(uint64_t* out, const uint64_t* values, size_t n, size_t stride_elems, int batch, const uint64_t* gamma, int accumulate)
+{
+    if (int rc = fold_args("host fr_fold", out && values && gamma, n, stride_elems, batch)) return rc;
+    host::fold_host(out, values, n, stride_elems, batch, gamma, accumulate != 0);
+    return BBGPU_OK;
+}
+int bbgpu_host_kate_opening_lagrange_folded(const uint64_t* values, size_t n, size_t stride_elems, int batch, const uint64_t* gamma, const uint64_t z[4],
+                                            uint64_t* quotient, int accumulate, uint64_t folded_f_of_z[4])
+{
+    if (int rc = lagrange_open_args("host kate_opening_lagrange_folded", values && gamma && z && quotient, n, stride_elems, batch)) return rc;
+    host::lagrange_open_folded_host(values, n, stride_elems, batch, gamma, load_fr(z), quotient, accumulate != 0, folded_f_of_z);
+    return BBGPU_OK;
+}
 int bbgpu_host_lagrange_l1_fft(uint64_t* l_1, size_t n_src, size_t n_target)
 {
     const int ls = log2_exact(n_src), lt = log2_exact(n_target);
@@ -1981,6 +2178,35 @@ int bbgpu_host_pairing_check(const uint64_t* p, const uint64_t* q, size_t k, int
         return BBGPU_ERR_ARG;
     }
     *is_one = host::fq12_eq(host::pairing_product(p, q, k), host::fq12_one()) ? 1 : 0;
+    return BBGPU_OK;
+}
+
+int bbgpu_host_kzg_check_openings(const uint64_t* commitments, const uint64_t* z, const uint64_t* y, const uint64_t* proofs, size_t k, const uint64_t g2_x[16],
+                                  const uint64_t seed[4], int* ok)
+{
+    if (k < 1 || k > host::KZG_CHECK_MAX_OPENINGS) {
+        set_error("KZG check: %zu openings, 1..%zu are taken", k, host::KZG_CHECK_MAX_OPENINGS);
+        return BBGPU_ERR_SIZE;
+    }
+    if (!commitments || !z || !y || !proofs || !g2_x || !ok) {
+        set_error("KZG check: null commitments / z / y / proofs / g2_x / ok");
+        return BBGPU_ERR_ARG;
+    }
+    for (size_t t = 0; t < k; t++)
+        if (!host::g1_words_acceptable(commitments + 8 * t) || !host::g1_words_acceptable(proofs + 8 * t)) {
+            set_error("KZG check: commitment or proof %zu is not on the curve", t);
+            return BBGPU_ERR_ARG;
+        }
+    if (!host::srs_check_g2_ok(g2_x)) {
+        set_error("KZG check: g2_x is at infinity, off the twist curve or not of order r");
+        return BBGPU_ERR_ARG;
+    }
+    uint64_t sd[4];
+    if (!host::srs_check_seed(seed, sd)) {
+        set_error("KZG check: the operating system gave no randomness");
+        return BBGPU_ERR_STATE;
+    }
+    *ok = host::kzg_check_openings(commitments, z, y, proofs, k, g2_x, sd) ? 1 : 0;
     return BBGPU_OK;
 }
 

@@ -5,6 +5,8 @@
 // and for z = w^m:  f(z) = v_m,  q_i = (v_m - v_i) / (z - w^i) for i != m,  q_m = -sum_{i != m} q_i w^(i - m)  (the X^(n-1) coefficient of a quotient
 // of degree n - 2 is zero).  No transform.  The twin is plain loops with Montgomery's trick for the n inversions -- deliberately NOT the launch
 // structure of poly.hip; both sides write canonical field elements, so they agree bit for bit.  Product code, no oracle/; no HIP call, no lock.
+// Behind them the fold sum_b gamma_b v_b and the opening of a fold (bbgpu_fr_fold_device, bbgpu_lagrange_opening_open_folded): the fold as a plain loop, then
+// the definition above on the folded vector.  The sessions of the device side have no counterpart here: they are an economy, not part of the definition.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -110,6 +112,44 @@ static inline void lagrange_open_host(const uint64_t* values, uint64_t* quotient
         }
         if (on) q[m] = fr_neg(acc);
     }
+}
+
+// ---- folds (bbgpu_fr_fold_device, bbgpu_lagrange_opening_open_folded and their twins) ------------------------------------------------------------------
+constexpr size_t FOLD_MAX_N = (size_t)1 << 24;
+// the fold alone takes any length, not only a domain's
+static inline bool fold_sizes_ok(size_t n, size_t stride_elems, int batch)
+{
+    return n >= 1 && n <= FOLD_MAX_N && batch >= 1 && batch <= LAGRANGE_OPEN_MAX_BATCH && stride_elems >= n;
+}
+// out[i] = sum_b gamma_b v_{b,i}, or that added to out[i]; canonical.  out must not overlap values
+static inline void fold_host(uint64_t* out, const uint64_t* values, size_t n, size_t stride, int batch, const uint64_t* gamma, bool accumulate)
+{
+    const Fr* v = reinterpret_cast<const Fr*>(values);
+    const Fr* g = reinterpret_cast<const Fr*>(gamma);
+    Fr* o = reinterpret_cast<Fr*>(out);
+    const Fr one = fr_one();
+    std::vector<Fr> gc((size_t)batch); // canonical: fr_mul takes one operand of any representative, not two
+    for (int b = 0; b < batch; b++) gc[b] = fr_mul(g[b], one);
+    for (size_t i = 0; i < n; i++) {
+        Fr acc = accumulate ? fr_mul(o[i], one) : fr_zero();
+        for (int b = 0; b < batch; b++) acc = fr_add(acc, fr_mul(v[(size_t)b * stride + i], gc[b]));
+        o[i] = acc;
+    }
+}
+// the opening of F = sum_b gamma_b f_b at z: quotient[i] = (or +=) the values of (F(X) - F(z)) / (X - z); f_out (may be null) = F(z).  Stateless: the fold,
+// then the definition above on the folded vector
+static inline void lagrange_open_folded_host(const uint64_t* values, size_t n, size_t stride, int batch, const uint64_t* gamma, const Fr& z, uint64_t* quotient,
+                                             bool accumulate, uint64_t* f_out)
+{
+    std::vector<Fr> folded(n);
+    fold_host(folded[0].d, values, n, stride, batch, gamma, false);
+    if (!accumulate) {
+        lagrange_open_host(folded[0].d, quotient, n, n, 1, z, f_out);
+        return;
+    }
+    lagrange_open_host(folded[0].d, folded[0].d, n, n, 1, z, f_out);
+    Fr* q = reinterpret_cast<Fr*>(quotient);
+    for (size_t i = 0; i < n; i++) q[i] = fr_add(fr_mul(q[i], fr_one()), folded[i]);
 }
 
 } // namespace host

@@ -14,6 +14,18 @@ struct PowTab {
     Limbs9 p[24]; // base^(2^j), 2^261 form
 };
 
+// the points of one launch of k_bary_denominators (an opening session has up to BARY_MAX_POINTS; bary_open has one), by value
+constexpr int BARY_MAX_POINTS = 4;
+struct BaryPoints {
+    Limbs9 z_m256[BARY_MAX_POINTS];
+    uint32_t m[BARY_MAX_POINTS]; // the index of z on the domain, or >= n
+};
+// the multipliers of a fold (k_fold, k_bary_fold_dot), 2^261 form, by value
+constexpr int FOLD_MAX_BATCH = 64;
+struct FoldCoeffs {
+    Limbs9 c[FOLD_MAX_BATCH];
+};
+
 // growable device workspace private to one stream of work (+ 4 KiB of pinned host memory for 32-byte read-backs)
 struct Scratch {
     uint8_t* base = nullptr;
@@ -211,6 +223,17 @@ int lagrange_l1_fft(uint64_t* d_l1, uint64_t* d_tmp, int log2n, int log2N, Scrat
 // on_domain / m: z == w^m, decided by the caller (host_lagrange_open.hpp).  d_tmp: n elements of workspace
 int bary_open(const uint64_t* d_values, uint64_t* d_quotient, int log2n, size_t stride, int batch, const host::Fr& z, bool on_domain, size_t m,
               uint64_t* d_tmp, host::Fr* h_out, Scratch& S, hipStream_t st);
+// Its two halves, for an opening session (capi.hip): the inverses 1 / (z_t - w^i) of up to BARY_MAX_POINTS points, point-major into d_inv (points x n
+// elements; d_tmp: as many of workspace), by one launch and one batch_invert; then evaluation / opening at one point over ITS n inverses, as often as wanted
+int bary_inverses(uint64_t* d_inv, int log2n, int points, const host::Fr* z, const bool* on_domain, const size_t* m, uint64_t* d_tmp, Scratch& S,
+                  hipStream_t st);
+int bary_open_with(const uint64_t* d_values, uint64_t* d_quotient, int log2n, size_t stride, int batch, const host::Fr& z, bool on_domain, size_t m,
+                   const uint64_t* d_inverses, host::Fr* h_out, Scratch& S, hipStream_t st);
+// the opening of F = sum_b gamma_b f_b over the same inverses: d_quotient (n elements, not overlapping d_values) is set or added to; h_out: null or F(z)
+int bary_open_folded(const uint64_t* d_values, int log2n, size_t stride, int batch, const host::Fr* gamma, const host::Fr& z, bool on_domain, size_t m,
+                     const uint64_t* d_inverses, uint64_t* d_quotient, bool accumulate, host::Fr* h_out, Scratch& S, hipStream_t st);
+// d_out[i] = (d_out[i] +) sum_b gamma_b v_{b,i}: any n, batch <= FOLD_MAX_BATCH
+int fold(uint64_t* d_out, const uint64_t* d_values, size_t n, size_t stride, int batch, const host::Fr* gamma, bool accumulate, hipStream_t st);
 
 } // namespace poly
 } // namespace bbgpu

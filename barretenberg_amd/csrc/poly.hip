@@ -10,7 +10,8 @@
 //   the grand-product prefix products                            waffle/proof_system/prover/prover.cpp:194-202
 //   compute_permutation_lagrange_base_single                     waffle/proof_system/permutation.hpp:15-87
 // adds what the reference has no counterpart of: evaluation and opening of polynomials given by their VALUES on the domain (the k_bary_* kernels and
-// bary_open: barycentric sums over one shared batch inversion, no transform),
+// bary_open: barycentric sums over one shared batch inversion, no transform; bary_inverses / bary_open_with / bary_open_folded: the same at several
+// points of an opening session over ONE inversion, and the opening of a fold of polynomials -- k_bary_fold_dot, k_fold),
 // and provides the fused pointwise kernels of the prover rounds (prover.cpp:135-222,224-300,302-403,461-463,520-528,567-595,
 // arithmetic_widget.cpp:66-104,106-126).
 //
@@ -740,16 +741,18 @@ __global__ void __launch_bounds__(PT) k_l1_scale(uint32_t* __restrict__ l1, uint
 }
 
 // ---- evaluation and opening in evaluation form (bary_open below; the reference has no counterpart) ----------------------------------------------------
-// d[i] = z - w^i (to be inverted), and one at i == m: the index of z on the domain, or none (m >= n)
-__global__ void __launch_bounds__(PT) k_bary_denominators(uint32_t* __restrict__ d, uint32_t n, uint32_t m, PowTab root, Limbs9 z_m256, Limbs9 step_m261)
+// d[y][i] = z_y - w^i (to be inverted), and one at i == m_y: the index of z_y on the domain, or none (m_y >= n); point y = blockIdx.y, point-major
+__global__ void __launch_bounds__(PT) k_bary_denominators(uint32_t* __restrict__ d, uint32_t n, BaryPoints P, PowTab root, Limbs9 step_m261)
 {
     const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
+    d += (size_t)blockIdx.y * n * 8;
+    const uint32_t m = P.m[blockIdx.y];
     Limbs9 one256;
 #pragma unroll
     for (int k = 0; k < NL; k++) one256.d[k] = Fr::ONE_M256[k];
     FrM x = pow_tab(root, t, one256); // memory form
-    const FrC step = cst(step_m261), z = cst(z_m256), one = fe_from<Fr>(Fr::ONE_M256);
+    const FrC step = cst(step_m261), z = cst(P.z_m256[blockIdx.y]), one = fe_from<Fr>(Fr::ONE_M256);
     for (uint32_t i = t; i < n; i += nt) {
         if (i == m) stv(d, i, one);
         else stv(d, i, sub(z, x));
@@ -806,6 +809,46 @@ __global__ void __launch_bounds__(PT) k_bary_quotient(const uint32_t* v, uint32_
     const FrV y = ldv(slot, blockIdx.y);
     for (uint32_t i = t; i < n; i += nt)
         if (i != m) stv(q, i, mulv(sub(y, ldv(v, i)), ldv(inv, i)));
+}
+// F_i = sum_b gamma_b v_{b,i} over `batch` polynomials `stride` elements apart (gamma by value, 2^261 form): one shared reduction per term, memory form
+__device__ __forceinline__ FrM fold_at(const uint32_t* __restrict__ v, size_t stride, int batch, const FoldCoeffs& G, uint32_t i)
+{
+    const FrC one = fe_from<Fr>(Fr::ONE);
+    FrM f = mul(ldv(v, i), cst(G.c[0]));
+    for (int b = 1; b < batch; b++) f = mul_add(ldv(v + (size_t)b * stride * 8, i), cst(G.c[b]), f, one);
+    return f;
+}
+// out[i] = F_i, or out[i] + F_i (bbgpu_fr_fold_device; the fold of an opening at z on the domain)
+__global__ void __launch_bounds__(PT) k_fold(uint32_t* __restrict__ out, const uint32_t* __restrict__ v, size_t stride, int batch, FoldCoeffs G, uint32_t n,
+                                             uint32_t accumulate)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const FrM f = fold_at(v, stride, batch, G, i);
+    if (accumulate) stv(out, i, add(f, ldv(out, i)));
+    else stv(out, i, f);
+}
+// the fold and k_bary_dot's sum off the domain in one trip over the values: folded[i] = F_i and partial[block] = the workgroup's share of
+// sum_i F_i w^i inv_i, thread t owning i = t, t + T, ... (start_m261 = 2^5, as in k_bary_dot)
+__global__ void __launch_bounds__(PT) k_bary_fold_dot(const uint32_t* __restrict__ v, size_t stride, int batch, FoldCoeffs G, const uint32_t* __restrict__ inv,
+                                                      uint32_t n, PowTab root, Limbs9 start_m261, Limbs9 step_m261, uint32_t* __restrict__ folded,
+                                                      uint32_t* __restrict__ partial)
+{
+    __shared__ uint32_t sh[NL * PT];
+    const uint32_t nt = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
+    const FrC one = fe_from<Fr>(Fr::ONE);
+    FrM acc = mul(fe_zero<Fr>(), one);
+    if (t < n) {
+        FrM x = pow_tab(root, t, start_m261);
+        const FrC step = cst(step_m261);
+        for (uint32_t i = t; i < n; i += nt) {
+            const FrM f = fold_at(v, stride, batch, G, i);
+            stv(folded, i, f);
+            acc = mul_add(mul(f, ldv(inv, i)), x, acc, one);
+            x = mul(x, step);
+        }
+    }
+    block_sum(partial, blockIdx.x, acc, sh);
 }
 
 // prover.cpp:520-528 + arithmetic_widget.cpp:106-126: r[i] = sum_j c_j p_j[i] over the seven coefficient-form polynomials
@@ -1292,6 +1335,8 @@ int lagrange_l1_fft(uint64_t* d_l1, uint64_t* d_tmp, int log2n, int log2N, Scrat
 //   off the domain   denominators, batch_invert, dot (v_i w^i inv_i), finish (* (z^n - 1) / n -> slot b), quotient (slot b - v_i) inv_i
 //   on it            denominators (one at m), batch_invert, v_m -> slot b by a copy, quotient (all but m), dot (q_i w^(i - m)), finish (* -1 -> q_m);
 //                    without a quotient only the copy
+// bary_open is "make inverses" (bary_inverses) followed by "use inverses" (bary_apply); an opening session makes the inverses of several points once
+// and uses them call by call (bary_open_with, bary_open_folded).
 // d_quotient: null (evaluation only), d_values itself, or a buffer that does not overlap it.  h_out: null, or batch values read back (the only
 // synchronisation besides batch_invert's).  d_tmp: n elements.  The scratch holds batch_invert's share first, then the inverses, the partials and the slots.
 // slot b = element m of polynomial b, as it stands
@@ -1303,45 +1348,9 @@ static hipError_t bary_stash(uint32_t* d_slot, const uint64_t* d_vm, size_t stri
         if (hipError_t e = hipMemcpyAsync(d_slot + 8 * (size_t)b, d_vm + 4 * (size_t)b * stride, 32, hipMemcpyDeviceToDevice, st)) return e;
     return hipSuccess;
 }
-int bary_open(const uint64_t* d_values, uint64_t* d_quotient, int log2n, size_t stride, int batch, const host::Fr& z, bool on_domain, size_t m,
-              uint64_t* d_tmp, host::Fr* h_out, Scratch& S, hipStream_t st)
+// batch x 4 words from the slots to the host: the read-back and the synchronisation of a call that returns values
+static int bary_read_slots(const uint32_t* d_slot, int batch, host::Fr* h_out, Scratch& S, hipStream_t st)
 {
-    const size_t n = (size_t)1 << log2n;
-    const uint32_t dblocks = eval_blocks(n), blocks = strided_blocks(n), mm = on_domain ? (uint32_t)m : 0xffffffffu;
-    int rc = ensure_pinned(S);
-    if (rc) return rc;
-    const size_t off_inv = (scan_scratch_bytes(n) + 64 + n * 32 + 64 + 63) & ~(size_t)63; // behind everything batch_invert asks for: its ensure() keeps the buffer
-    const size_t off_partial = off_inv + n * 32, off_slot = off_partial + (size_t)batch * dblocks * 32, off_sums = off_slot + (size_t)batch * 32;
-    rc = S.ensure(off_sums + (size_t)batch * 32);
-    if (rc) return rc;
-    uint32_t *d_inv = (uint32_t*)(S.base + off_inv), *d_partial = (uint32_t*)(S.base + off_partial), *d_slot = (uint32_t*)(S.base + off_slot),
-             *d_sums = (uint32_t*)(S.base + off_sums);
-    const uint32_t *v = (const uint32_t*)d_values;
-    uint32_t* q = (uint32_t*)d_quotient;
-    if (!on_domain || q) {
-        const host::Fr root = host::fr_root_of_unity(log2n);
-        const PowTab T = make_powtab(root);
-        const Limbs9 dstep = host::limbs_m261(host::fr_pow(root, (uint64_t)dblocks * PT));
-        const dim3 dgrid(dblocks, (uint32_t)batch), qgrid(blocks, (uint32_t)batch);
-        k_bary_denominators<<<blocks, PT, 0, st>>>(d_inv, (uint32_t)n, mm, T, host::limbs_m256(z), host::limbs_m261(host::fr_pow(root, (uint64_t)blocks * PT)));
-        HIPCHK(launch_check());
-        rc = batch_invert((uint64_t*)d_inv, d_tmp, n, S, st);
-        if (rc) return rc;
-        if (!on_domain) {
-            k_bary_dot<<<dgrid, PT, 0, st>>>(v, stride, d_inv, (uint32_t)n, mm, T, host::limbs_m261(host::fr_from_u64(32)), dstep, d_partial);
-            k_bary_finish<<<batch, PT, 0, st>>>(d_partial, dblocks, d_sums, host::limbs_m261(host::lagrange_open_scale(z, log2n)), d_slot, 1, 0);
-            if (q) k_bary_quotient<<<qgrid, PT, 0, st>>>(v, q, stride, d_inv, d_slot, (uint32_t)n, mm);
-        } else {
-            HIPCHK(bary_stash(d_slot, d_values + 4 * m, stride, batch, st)); // before element m can be overwritten (q may be v)
-            k_bary_quotient<<<qgrid, PT, 0, st>>>(v, q, stride, d_inv, d_slot, (uint32_t)n, mm);
-            k_bary_dot<<<dgrid, PT, 0, st>>>(q, stride, d_inv, (uint32_t)n, mm, T, host::limbs_m261(host::fr_inv(host::fr_pow(root, (uint64_t)m))), dstep, d_partial);
-            k_bary_finish<<<batch, PT, 0, st>>>(d_partial, dblocks, d_sums, host::limbs_m261(host::fr_neg(host::fr_one())), q, stride, mm);
-        }
-        HIPCHK(launch_check());
-    } else {
-        HIPCHK(bary_stash(d_slot, d_values + 4 * m, stride, batch, st));
-    }
-    if (!h_out) return BBGPU_OK;
     HIPCHK(d2h_async(S.h_pinned, d_slot, (size_t)batch * 32, st));
     HIPCHK(hipStreamSynchronize(st));
     for (int b = 0; b < batch; b++) {
@@ -1350,6 +1359,148 @@ int bary_open(const uint64_t* d_values, uint64_t* d_quotient, int log2n, size_t 
         h_out[b] = host::fr_mul(y, host::fr_one()); // v_m is the caller's representative: canonical out
     }
     return BBGPU_OK;
+}
+// what the kernels behind the inversion work in: the dot kernel's partials, the slots and the sums of `batch` polynomials
+struct BaryWork {
+    uint32_t *partial, *slot, *sums;
+};
+static size_t bary_work_bytes(size_t n, int batch) { return ((size_t)batch * eval_blocks(n) + 2 * (size_t)batch) * 32; }
+static BaryWork bary_work_at(uint8_t* base, size_t n, int batch)
+{
+    BaryWork W;
+    W.partial = (uint32_t*)base;
+    W.slot = W.partial + (size_t)batch * eval_blocks(n) * 8;
+    W.sums = W.slot + (size_t)batch * 8;
+    return W;
+}
+// "make inverses": d_inv[t * n + i] = 1 / (z_t - w^i) (one at i == m_t when z_t = w^(m_t)) for `points` points, point-major, by ONE launch and ONE
+// batch_invert -- one host inversion and one synchronisation however many points.  d_tmp: points x n elements of workspace
+int bary_inverses(uint64_t* d_inv, int log2n, int points, const host::Fr* z, const bool* on_domain, const size_t* m, uint64_t* d_tmp, Scratch& S,
+                  hipStream_t st)
+{
+    const size_t n = (size_t)1 << log2n;
+    const uint32_t blocks = strided_blocks(n);
+    const host::Fr root = host::fr_root_of_unity(log2n);
+    BaryPoints P;
+    for (int t = 0; t < BARY_MAX_POINTS; t++) {
+        P.z_m256[t] = host::limbs_m256(z[t < points ? t : 0]);
+        P.m[t] = (t < points && on_domain[t]) ? (uint32_t)m[t] : 0xffffffffu;
+    }
+    k_bary_denominators<<<dim3(blocks, (uint32_t)points), PT, 0, st>>>((uint32_t*)d_inv, (uint32_t)n, P, make_powtab(root),
+                                                                       host::limbs_m261(host::fr_pow(root, (uint64_t)blocks * PT)));
+    HIPCHK(launch_check());
+    return batch_invert(d_inv, d_tmp, (size_t)points * n, S, st);
+}
+// "use inverses": evaluation and opening at one point over its n inverses; W: bary_work_bytes(n, batch) of workspace
+static int bary_apply(const uint64_t* d_values, uint64_t* d_quotient, int log2n, size_t stride, int batch, const host::Fr& z, bool on_domain, size_t m,
+                      const uint64_t* d_inverses, const BaryWork& W, host::Fr* h_out, Scratch& S, hipStream_t st)
+{
+    const size_t n = (size_t)1 << log2n;
+    const uint32_t dblocks = eval_blocks(n), blocks = strided_blocks(n), mm = on_domain ? (uint32_t)m : 0xffffffffu;
+    const uint32_t *v = (const uint32_t*)d_values, *d_inv = (const uint32_t*)d_inverses;
+    uint32_t* q = (uint32_t*)d_quotient;
+    if (!on_domain || q) {
+        const host::Fr root = host::fr_root_of_unity(log2n);
+        const PowTab T = make_powtab(root);
+        const Limbs9 dstep = host::limbs_m261(host::fr_pow(root, (uint64_t)dblocks * PT));
+        const dim3 dgrid(dblocks, (uint32_t)batch), qgrid(blocks, (uint32_t)batch);
+        if (!on_domain) {
+            k_bary_dot<<<dgrid, PT, 0, st>>>(v, stride, d_inv, (uint32_t)n, mm, T, host::limbs_m261(host::fr_from_u64(32)), dstep, W.partial);
+            k_bary_finish<<<batch, PT, 0, st>>>(W.partial, dblocks, W.sums, host::limbs_m261(host::lagrange_open_scale(z, log2n)), W.slot, 1, 0);
+            if (q) k_bary_quotient<<<qgrid, PT, 0, st>>>(v, q, stride, d_inv, W.slot, (uint32_t)n, mm);
+        } else {
+            HIPCHK(bary_stash(W.slot, d_values + 4 * m, stride, batch, st)); // before element m can be overwritten (q may be v)
+            k_bary_quotient<<<qgrid, PT, 0, st>>>(v, q, stride, d_inv, W.slot, (uint32_t)n, mm);
+            k_bary_dot<<<dgrid, PT, 0, st>>>(q, stride, d_inv, (uint32_t)n, mm, T, host::limbs_m261(host::fr_inv(host::fr_pow(root, (uint64_t)m))), dstep, W.partial);
+            k_bary_finish<<<batch, PT, 0, st>>>(W.partial, dblocks, W.sums, host::limbs_m261(host::fr_neg(host::fr_one())), q, stride, mm);
+        }
+        HIPCHK(launch_check());
+    } else {
+        HIPCHK(bary_stash(W.slot, d_values + 4 * m, stride, batch, st));
+    }
+    return h_out ? bary_read_slots(W.slot, batch, h_out, S, st) : (int)BBGPU_OK;
+}
+int bary_open(const uint64_t* d_values, uint64_t* d_quotient, int log2n, size_t stride, int batch, const host::Fr& z, bool on_domain, size_t m,
+              uint64_t* d_tmp, host::Fr* h_out, Scratch& S, hipStream_t st)
+{
+    const size_t n = (size_t)1 << log2n;
+    int rc = ensure_pinned(S);
+    if (rc) return rc;
+    const size_t off_inv = (scan_scratch_bytes(n) + 64 + n * 32 + 64 + 63) & ~(size_t)63; // behind everything batch_invert asks for: its ensure() keeps the buffer
+    const size_t off_work = off_inv + n * 32;
+    rc = S.ensure(off_work + bary_work_bytes(n, batch));
+    if (rc) return rc;
+    uint64_t* d_inv = (uint64_t*)(S.base + off_inv);
+    if (!on_domain || d_quotient) {
+        rc = bary_inverses(d_inv, log2n, 1, &z, &on_domain, &m, d_tmp, S, st);
+        if (rc) return rc;
+    }
+    return bary_apply(d_values, d_quotient, log2n, stride, batch, z, on_domain, m, d_inv, bary_work_at(S.base + off_work, n, batch), h_out, S, st);
+}
+// the same over inverses made earlier (an opening session, capi.hip): no denominators, no inversion; the workspace is the front of the scratch
+int bary_open_with(const uint64_t* d_values, uint64_t* d_quotient, int log2n, size_t stride, int batch, const host::Fr& z, bool on_domain, size_t m,
+                   const uint64_t* d_inverses, host::Fr* h_out, Scratch& S, hipStream_t st)
+{
+    const size_t n = (size_t)1 << log2n;
+    int rc = ensure_pinned(S);
+    if (rc) return rc;
+    rc = S.ensure(bary_work_bytes(n, batch));
+    if (rc) return rc;
+    return bary_apply(d_values, d_quotient, log2n, stride, batch, z, on_domain, m, d_inverses, bary_work_at(S.base, n, batch), h_out, S, st);
+}
+
+static FoldCoeffs fold_coeffs(const host::Fr* gamma, int batch)
+{
+    FoldCoeffs G;
+    for (int b = 0; b < FOLD_MAX_BATCH; b++) G.c[b] = host::limbs_m261(b < batch ? gamma[b] : host::fr_zero());
+    return G;
+}
+// d_out[i] = (d_out[i] +) sum_b gamma_b v_{b,i}, canonical; any n
+int fold(uint64_t* d_out, const uint64_t* d_values, size_t n, size_t stride, int batch, const host::Fr* gamma, bool accumulate, hipStream_t st)
+{
+    k_fold<<<pw_blocks(n), PT, 0, st>>>((uint32_t*)d_out, (const uint32_t*)d_values, stride, batch, fold_coeffs(gamma, batch), (uint32_t)n, accumulate ? 1u : 0u);
+    HIPCHK(launch_check());
+    return BBGPU_OK;
+}
+// The opening of the fold F = sum_b gamma_b f_b at one point of a session: the values of (F(X) - F(z)) / (X - z) stored into d_quotient (n elements, not
+// overlapping d_values) or added to it; h_out: null, or F(z).  The batch x n values are read ONCE:
+//   off the domain   fold + dot in one trip (k_bary_fold_dot: F_i stored, F_i w^i inv_i summed), finish, quotient in place on F
+//   on it            fold (k_fold), F_m -> slot by a copy, quotient in place (all but m), dot (q_i w^(i - m)), finish (* -1 -> q_m)
+// When accumulating, F and its quotient live in the scratch and one more pass adds the n elements to d_quotient.
+int bary_open_folded(const uint64_t* d_values, int log2n, size_t stride, int batch, const host::Fr* gamma, const host::Fr& z, bool on_domain, size_t m,
+                     const uint64_t* d_inverses, uint64_t* d_quotient, bool accumulate, host::Fr* h_out, Scratch& S, hipStream_t st)
+{
+    const size_t n = (size_t)1 << log2n;
+    const uint32_t dblocks = eval_blocks(n), blocks = strided_blocks(n), mm = on_domain ? (uint32_t)m : 0xffffffffu;
+    int rc = ensure_pinned(S);
+    if (rc) return rc;
+    const size_t off_work = accumulate ? n * 32 : 0;
+    rc = S.ensure(off_work + bary_work_bytes(n, 1));
+    if (rc) return rc;
+    const BaryWork W = bary_work_at(S.base + off_work, n, 1);
+    uint32_t* F = accumulate ? (uint32_t*)S.base : (uint32_t*)d_quotient;
+    const uint32_t *v = (const uint32_t*)d_values, *d_inv = (const uint32_t*)d_inverses;
+    const host::Fr root = host::fr_root_of_unity(log2n);
+    const PowTab T = make_powtab(root);
+    const Limbs9 dstep = host::limbs_m261(host::fr_pow(root, (uint64_t)dblocks * PT));
+    const FoldCoeffs G = fold_coeffs(gamma, batch);
+    if (!on_domain) {
+        k_bary_fold_dot<<<dblocks, PT, 0, st>>>(v, stride, batch, G, d_inv, (uint32_t)n, T, host::limbs_m261(host::fr_from_u64(32)), dstep, F, W.partial);
+        k_bary_finish<<<1, PT, 0, st>>>(W.partial, dblocks, W.sums, host::limbs_m261(host::lagrange_open_scale(z, log2n)), W.slot, 1, 0);
+        k_bary_quotient<<<blocks, PT, 0, st>>>(F, F, n, d_inv, W.slot, (uint32_t)n, mm);
+    } else {
+        k_fold<<<pw_blocks(n), PT, 0, st>>>(F, v, stride, batch, G, (uint32_t)n, 0u);
+        HIPCHK(bary_stash(W.slot, (const uint64_t*)F + 4 * m, n, 1, st));
+        k_bary_quotient<<<blocks, PT, 0, st>>>(F, F, n, d_inv, W.slot, (uint32_t)n, mm);
+        k_bary_dot<<<dblocks, PT, 0, st>>>(F, n, d_inv, (uint32_t)n, mm, T, host::limbs_m261(host::fr_inv(host::fr_pow(root, (uint64_t)m))), dstep, W.partial);
+        k_bary_finish<<<1, PT, 0, st>>>(W.partial, dblocks, W.sums, host::limbs_m261(host::fr_neg(host::fr_one())), F, n, mm);
+    }
+    HIPCHK(launch_check());
+    if (accumulate) {
+        rc = add_inplace_lanes(d_quotient, n, (const uint64_t*)F, n, n, 1, st);
+        if (rc) return rc;
+    }
+    return h_out ? bary_read_slots(W.slot, 1, h_out, S, st) : (int)BBGPU_OK;
 }
 
 // ---- lane-batched forms: table plumbing ------------------------------------------------------------------------------------------------------------

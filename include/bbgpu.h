@@ -355,6 +355,74 @@ int bbgpu_fr_evaluate_lagrange_device(const uint64_t* d_values, size_t n, size_t
 int bbgpu_kate_opening_lagrange_device(const uint64_t* d_values, uint64_t* d_quotient, size_t n, size_t stride_elems, int batch, const uint64_t z[4],
                                        uint64_t* f_of_z /* batch x 4, host; may be NULL */, void* hip_stream);
 
+/* Opening sessions: the same two operations at SEVERAL points over one shared inversion, and the opening of a FOLD of polynomials.  The two entries above
+ * spend most of a call on the batch inversion and throw the inverses 1 / (z - w^i) away; a prover that opens at z and z w (as PLONK does), or evaluates
+ * first to derive its folding challenge and opens afterwards, pays it two or four times, and commits to one quotient per polynomial.  A session makes the
+ * inverses of up to BBGPU_OPENING_MAX_POINTS points ONCE and keeps them; every pairing-based protocol then folds the polynomials opened at one point with
+ * challenge multipliers and commits to ONE quotient per point -- the quotient is linear in the polynomial.  Domain, root, value layout and the on-domain
+ * rules are those of the two entries above; all field elements are in the reference's memory format, any representative in, canonical out.
+ *   begin        z: points x 4 words of HOST memory.  Every z_t is reduced and judged on the host (on the domain, and where) as above; ONE launch writes the
+ *                denominators of all points, point-major (k_bary_denominators, one grid row per point, z_t and m_t by value), ONE batch inversion
+ *                inverts them -- one host inversion and one synchronisation for the whole session.  Equal points are legal.  Returns a handle >= 0.  The
+ *                inverses (points x n x 32 bytes) live in an allocation of the session's own, counted in bbgpu_memory_info.staging_bytes, released by end
+ *                and by bbgpu_shutdown.  BBGPU_ERR_SIZE: n not a power of two in [2, 2^24], points outside 1..4, points x n > 2^24; BBGPU_ERR_ARG: null z;
+ *                BBGPU_ERR_STATE: BBGPU_OPENING_MAX_SESSIONS sessions are live -- all refused before a device is bound.  After a failed begin no session
+ *                exists and nothing it allocated is live.
+ *   evaluate     bit for bit what bbgpu_fr_evaluate_lagrange_device returns for the same values at the session's z_point, without denominators or an
+ *                inversion: off the domain k_bary_dot and k_bary_finish, on it the copy of v_m alone; one read-back synchronises.
+ *   open         bit for bit bbgpu_kate_opening_lagrange_device, the in-place rule and the untouched padding included: off the domain dot, finish,
+ *                quotient; on it stash, quotient, dot, finish.  With f_of_z == NULL it synchronises nothing.
+ *   open_folded  with F = sum_b gamma_b f_b (gamma: batch x 4 words of HOST memory), d_quotient[i], n elements, is set -- or, with accumulate != 0, added
+ *                to, canonically -- to the values of (F(X) - F(z)) / (X - z) on the domain, element m for z = w^m included (the rule above applied to F);
+ *                folded_f_of_z (may be NULL) = F(z), the F of this call alone.  accumulate == 0 writes every one of the n elements.  d_quotient must not
+ *                overlap d_values (not validated, like every device pointer of this section).  The quotient is linear: several calls with accumulate fold
+ *                polynomials that live in different buffers or strides into one proof.  The batch x n values are read ONCE: off the domain k_bary_fold_dot
+ *                forms F_i (one shared reduction per term), stores it and sums F_i w^i inv_i in the same trip, then k_bary_finish and k_bary_quotient
+ *                run in place on the n elements; on the domain k_fold, the copy of F_m, quotient, dot, finish.  When accumulating, F and its quotient are
+ *                made in the scratch and one more pass over n elements adds them to d_quotient.
+ *   end          releases the session; BBGPU_ERR_ARG for a handle that is not live.
+ * The four session calls refuse without touching a device: BBGPU_ERR_SIZE for batch outside 1..64 or stride_elems < n, BBGPU_ERR_ARG for an unknown
+ * session, a point outside the session or a null pointer the call needs.  They run on context 0 under the library mutex; every allocation, read-back and
+ * launch check passes the fault-injection funnels (warm calls at n = 4096, DESIGN.md 7 -- begin: one allocation, four launch checks, the denominators and
+ * the inversion's three; evaluate: one launch check off the domain, none on it, one read-back; open: one launch check, one read-back when f_of_z is
+ * wanted; open_folded: one launch check, two when accumulating, one read-back when folded_f_of_z is wanted; no upload anywhere).  After a failed call the
+ * session stays usable.
+ * Cost on one MI355X (tools/opening_session_bench.py, profiles/opening_session.txt; wall ms per call sequence, this library against the PARENT library in
+ * one process, alternating pairs, medians of 21, spreads as interquartile ranges).  The PLONK shape: eight polynomials, six opened at z and two at z w, all
+ * evaluations wanted, one proof point per point -- parent: two bbgpu_kate_opening_lagrange_device calls and eight MSMs; session: begin(2 points), two
+ * evaluate, two open_folded, two MSMs, end.  One polynomial: begin + evaluate + end against the parent's entry and against IFFT + bbgpu_fr_evaluate_device.
+ *                                          2^16 values                  2^20 values
+ *                                      session / parent              session / parent
+ *   PLONK shape + commitments          1.210 / 2.444                 3.786 / 10.93          session lower, by 1.23 and 7.14 ms (spreads 0.04, 0.12)
+ *   PLONK shape, no commitments        0.611 / 0.392                 1.255 / 1.011          PARENT lower, by 0.22 and 0.24 ms (spreads 0.006, 0.011)
+ *   evaluate one polynomial            0.198 / 0.181  (IFFT: 0.086)  0.534 / 0.345  (IFFT: 0.167)   parent lower by 0.02 and 0.19 ms, the transform path lowest
+ * With the commitments the sequence falls by the six MSMs saved, as expected (2.0x and 2.9x).  WITHOUT them it goes the other way: the expectation that
+ * it falls by about one inversion is refuted.  The calls alone (the same file): begin(2 points) + end 0.338 / 0.622 ms around a batch inversion of 2 n elements
+ * that takes 0.118 / 0.355 -- the session's own allocation, a hipMalloc and a hipFree that waits for the device, costs 0.2 .. 0.3 ms, more than the inversion
+ * it saves (0.1 .. 0.2 ms) -- and the four session calls cost 0.064 + 0.062 + 0.096 + 0.073 ms at 2^16 and 0.212 + 0.102 + 0.175 + 0.119 at 2^20, two of
+ * them (the evaluations) a synchronisation each that the parent's two calls do not make.  (At 2^16 the allocation's cost is bimodal between runs: the same
+ * begin + evaluate + end measured 0.198 in one pairing and 0.382 in the next.)  A caller who needs the values before the folding challenge has no
+ * alternative to evaluating first; one who opens a single point without folding and commits per polynomial should stay with the entries above.  Nothing
+ * was tuned after these measurements.  The two existing entries, parent against child in the same run, agree within 0.007 ms in every cell (batch 1 and 8,
+ * both sizes), inside the spreads.
+ */
+#define BBGPU_OPENING_MAX_POINTS 4
+#define BBGPU_OPENING_MAX_SESSIONS 16
+int bbgpu_lagrange_opening_begin(size_t n, const uint64_t* z /* points x 4, host */, int points, void* hip_stream); /* session handle >= 0 */
+int bbgpu_lagrange_opening_evaluate(int session, int point, const uint64_t* d_values, size_t stride_elems, int batch,
+                                    uint64_t* out /* batch x 4, host */, void* hip_stream);
+int bbgpu_lagrange_opening_open(int session, int point, const uint64_t* d_values, uint64_t* d_quotient, size_t stride_elems, int batch,
+                                uint64_t* f_of_z /* batch x 4, host; may be NULL */, void* hip_stream);
+int bbgpu_lagrange_opening_open_folded(int session, int point, const uint64_t* d_values, size_t stride_elems, int batch,
+                                       const uint64_t* gamma /* batch x 4, host */, uint64_t* d_quotient /* n elements */, int accumulate,
+                                       uint64_t folded_f_of_z[4] /* host; may be NULL */, void* hip_stream);
+int bbgpu_lagrange_opening_end(int session);
+/* The fold alone: d_out[i] is set (accumulate == 0) or added to sum_b gamma_b v_{b,i}, canonical, asynchronous (k_fold, one launch): what a prover folds
+ * beside the quotient.  1 <= n <= 2^24, not necessarily a power of two; batch 1..64; stride_elems >= n (else BBGPU_ERR_SIZE); BBGPU_ERR_ARG for a null
+ * pointer; both before a device is bound.  d_out must not overlap d_values. */
+int bbgpu_fr_fold_device(uint64_t* d_out /* n */, const uint64_t* d_values, size_t n, size_t stride_elems, int batch,
+                         const uint64_t* gamma /* batch x 4, host */, int accumulate, void* hip_stream);
+
 /* The same on host buffers (copied to the device and back): what the C++ shim forwards the co-resident functions of the replaced
  * translation unit to, so that polynomial_arithmetic.o / scalar_multiplication.o can be left out of the link altogether. */
 int bbgpu_fr_evaluate(const uint64_t* coeffs, size_t n, const uint64_t z[4], uint64_t out[4]);
@@ -534,6 +602,11 @@ int bbgpu_host_lagrange_l1_fft(uint64_t* l_1, size_t n_src, size_t n_target);
 int bbgpu_host_fr_evaluate_lagrange(const uint64_t* values, size_t n, size_t stride_elems, int batch, const uint64_t z[4], uint64_t* out);
 int bbgpu_host_kate_opening_lagrange(const uint64_t* values, uint64_t* quotient, size_t n, size_t stride_elems, int batch, const uint64_t z[4],
                                      uint64_t* f_of_z /* may be NULL */);
+/* the twins of bbgpu_fr_fold_device and of a folded opening: plain loops (the fold, then the definition on the folded vector), the same argument verdicts;
+ * stateless -- a session is a device-side economy, not part of the definition */
+int bbgpu_host_fr_fold(uint64_t* out, const uint64_t* values, size_t n, size_t stride_elems, int batch, const uint64_t* gamma, int accumulate);
+int bbgpu_host_kate_opening_lagrange_folded(const uint64_t* values, size_t n, size_t stride_elems, int batch, const uint64_t* gamma, const uint64_t z[4],
+                                            uint64_t* quotient /* n */, int accumulate, uint64_t folded_f_of_z[4] /* may be NULL */);
 int bbgpu_host_divide_by_pseudo_vanishing(uint64_t* coeffs, size_t n_src, size_t n_target);
 /* bbgpu_plonk_check_witness on the host, for a caller without a GPU: the same definition, the same report; circuit->w_l / w_r / w_o are the witness.
  * Argument errors as bbgpu_plonk_prover_create (BBGPU_ERR_ARG: a null field, a widget's selectors given in part; BBGPU_ERR_SIZE: n). */
@@ -553,6 +626,15 @@ int bbgpu_host_pairing(const uint64_t p[8], const uint64_t q[16], uint64_t out[4
 /* is_one = (prod_k e(p_k, q_k) == 1) with one shared Miller-loop squaring chain and one final exponentiation (reduced_ate_pairing_batch,
  * pairing.cpp:364-385); p: k x 8 words, q: k x 16 words.  k == 0: one. */
 int bbgpu_host_pairing_check(const uint64_t* p, const uint64_t* q, size_t k, int* is_one);
+/* The check of k KZG openings (csrc/host_kzg_check.hpp), 1 <= k <= 64: claim t says that the polynomial committed to by C_t takes the value y_t at z_t, with
+ * proof point pi_t (the commitment of the quotient, e.g. an MSM of what bbgpu_lagrange_opening_open_folded writes over a bbgpu_srs_lagrange handle).
+ *   *ok = ( e(sum_t rho_t (C_t - y_t G + z_t pi_t), G2) e(-sum_t rho_t pi_t, x G2) == 1 ),  one pairing product of two pairs,
+ * rho_t = bbgpu_srs_check's multipliers Keccak-256(seed, t) with the top three bits cleared, the seed rules the same (NULL: drawn from the operating
+ * system).  commitments / proofs: k x 8 words, affine {x, y}, the infinity flag honoured; z / y: k x 4 words.  For a folded opening C_t is the caller's folded
+ * commitment sum_b gamma_b C_b -- bbgpu_host_msm_g1 over a plain table of the commitments with gamma as it stands -- and y_t the folded value.
+ * BBGPU_ERR_SIZE: k outside 1..64; BBGPU_ERR_ARG: a null pointer, a finite point off the curve, a g2_x that bbgpu_srs_check would not take.  Host only. */
+int bbgpu_host_kzg_check_openings(const uint64_t* commitments /* k x 8 */, const uint64_t* z /* k x 4 */, const uint64_t* y /* k x 4 */,
+                                  const uint64_t* proofs /* k x 8 */, size_t k, const uint64_t g2_x[16], const uint64_t seed[4] /* NULL: OS randomness */, int* ok);
 /* the other half of io::read_transcript: the file's second G2 point, x * G2 (io.hpp:100-135,171-180), in Montgomery form */
 int bbgpu_transcript_read_g2(const char* path, uint64_t g2_x_out[16]);
 
