@@ -68,6 +68,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_lagrange_opening_begin", "bbgpu_lagrange_opening_evaluate", "bbgpu_lagrange_opening_open", "bbgpu_lagrange_opening_open_folded",
     "bbgpu_lagrange_opening_end", "bbgpu_fr_fold_device", "bbgpu_host_fr_fold", "bbgpu_host_kate_opening_lagrange_folded", "bbgpu_host_kzg_check_openings",
     "bbgpu_selftest_plonk_round",
+    "bbgpu_kzg_open_all_setup", "bbgpu_kzg_open_all_release", "bbgpu_kzg_open_all_device", "bbgpu_host_kzg_open_all",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -552,6 +553,33 @@ class BbGpu:
         if rc < 0:
             raise self._srs_update_error(rc, rep)
         return out, rep
+
+    # ---- a polynomial opened at every point of its domain  (bbgpu_kzg_open_all_* and the host twin) ----
+    def kzg_open_all_setup(self, handle, n):
+        """bbgpu_kzg_open_all_setup: DFT_2n of the reversed rows [0, n - 1) of a resident monomial table, kept on the device -> setup handle"""
+        self.lib.bbgpu_kzg_open_all_setup.argtypes = [C.c_int, C.c_size_t]
+        return self._chk(self.lib.bbgpu_kzg_open_all_setup(int(handle), int(n)))
+
+    def kzg_open_all_release(self, setup):
+        self.lib.bbgpu_kzg_open_all_release.argtypes = [C.c_int]
+        self._chk(self.lib.bbgpu_kzg_open_all_release(int(setup)))
+
+    def kzg_open_all_device(self, setup, d_coeffs, n, batch=1, stride=None, stream=None, out=None):
+        """bbgpu_kzg_open_all_device: `batch` polynomials in coefficient form on the device (stride elements apart) -> (batch, n, 8): the affine KZG proof
+        of polynomial b at omega^i, infinity flagged in bit 63 of y[3]"""
+        out = np.zeros((max(int(batch), 1), int(n), 8), dtype=np.uint64) if out is None else out
+        self.lib.bbgpu_kzg_open_all_device.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, u64p, C.c_void_p]
+        self._chk(self.lib.bbgpu_kzg_open_all_device(int(setup), d_coeffs, n if stride is None else stride, batch, _ptr(out), stream or 0))
+        return out
+
+    def host_kzg_open_all(self, table, n, coeffs, batch=1, stride=None):
+        """bbgpu_host_kzg_open_all: the same on the host, over the even entries of a (>= 2 (n - 1), 8) endo table; coeffs (batch * stride, 4) -> (batch, n, 8)"""
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+        stride = coeffs.shape[0] // max(int(batch), 1) if stride is None else stride
+        out = np.zeros((max(int(batch), 1), int(n), 8), dtype=np.uint64)
+        self.lib.bbgpu_host_kzg_open_all.argtypes = [u64p, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p]
+        self._chk(self.lib.bbgpu_host_kzg_open_all(_ptr(table), int(n), _ptr(coeffs), stride, batch, _ptr(out)))
+        return out
 
     # ---- is this table the Lagrange form of that string?  (bbgpu_srs_lagrange_check and its host twin) ----
     def srs_lagrange_check(self, lagrange_handle, monomial_handle, n, seed=None, locate=False):

@@ -33,6 +33,7 @@
 #include "host_kzg_check.hpp"
 #include "host_lagrange_open.hpp"
 #include "host_srs_lagrange_check.hpp"
+#include "host_kzg_open_all.hpp"
 #include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
@@ -1313,6 +1314,28 @@ void opening_release(OpeningSession& o)
     o = OpeningSession();
 }
 
+// ---- setups of bbgpu_kzg_open_all_* (below): S^ = DFT_2n(s) of one (string, n), 2 n scratch points made once by the setup entry and kept in an allocation of
+// the setup's own until its release or bbgpu_shutdown.  Context 0, under g_mu.
+struct OpenAllSetup {
+    bool live = false;
+    int log2n = 0;
+    uint32_t* d_S = nullptr;
+    size_t bytes = 0;
+};
+OpenAllSetup g_open_all[BBGPU_KZG_OPEN_ALL_MAX_SETUPS];
+size_t open_all_setup_bytes()
+{
+    size_t b = 0;
+    for (const auto& o : g_open_all)
+        if (o.live) b += o.bytes;
+    return b;
+}
+void open_all_release(OpenAllSetup& o)
+{
+    if (o.live && o.d_S) (void)dev_free(o.d_S);
+    o = OpenAllSetup();
+}
+
 // Everything the current context holds, on the thread that drives it (its device is that thread's current one).  Context 0 (primary) also owns the
 // resident prover and the transforms' tables.
 void release_context(bool primary)
@@ -1322,6 +1345,8 @@ void release_context(bool primary)
     if (primary) plonk_release_all_locked();
     if (primary)
         for (auto& o : g_opening) opening_release(o);
+    if (primary)
+        for (auto& o : g_open_all) open_all_release(o);
     // nothing may still be reading the pinned staging buffers or a slot's workspace when they are freed: collect what is in flight
     // (an MSM a caller never waited for, a copy queued before an error return) and drain every stream first
     for (int k = 0; k < Context::NSLOT; k++)
@@ -1412,7 +1437,7 @@ void add_context_memory(const Context& C, bool primary, bbgpu_memory_info* out)
         if (sl.ws.h_out) out->pinned_host_bytes += (uint64_t)MSM_HOUT_GROUPS * 64 * 128;
     }
     out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap + C.srs_check_cap + C.verify_cap;
-    if (primary) out->staging_bytes += plonk_lane_bytes() + opening_session_bytes(); // the resident prover and the opening sessions live on context 0
+    if (primary) out->staging_bytes += plonk_lane_bytes() + opening_session_bytes() + open_all_setup_bytes(); // the resident prover, the opening sessions and the open-all setups live on context 0
     for (int k = 0; k < Context::HOST_RING; k++)
         if (C.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
 }
@@ -2724,6 +2749,149 @@ int bbgpu_srs_lagrange_check(int lagrange_handle, int monomial_handle, size_t n,
 // x, y, each four 64-bit limbs least-significant limb first, every limb big-endian, NOT in Montgomery form; file point k is
 // x^(k+1) G and monomials[0] is the generator (read_transcript :159-181).  Fills the complete 2n-entry endomorphism table of
 // generate_pippenger_point_table (scalar_multiplication.cpp:131-140): entry 2i = P_i, entry 2i+1 = (beta x_i, -y_i).  Host only.
+/* ---- a polynomial opened at every point of its domain: all n KZG proofs at once (host_kzg_open_all.hpp, kzg_open_all.hip) ---- */
+static int open_all_n(const char* what, size_t n, int* log2n)
+{
+    if ((*log2n = host::kzg_open_all_log2(n)) < 0) {
+        set_error("%s: n = %zu is not a power of two between 2 and 2^%d", what, n, host::KZG_OPEN_ALL_MAX_LOG2);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
+static int open_all_batch(const char* what, int batch)
+{
+    if (batch < 1 || batch > host::KZG_OPEN_ALL_MAX_BATCH) {
+        set_error("%s: batch = %d must be in 1..%d", what, batch, host::KZG_OPEN_ALL_MAX_BATCH);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
+static int open_all_sizes(const char* what, size_t n, size_t stride_elems, int batch)
+{
+    if (!host::kzg_open_all_sizes_ok(n, stride_elems, batch)) {
+        set_error("%s: the stride (%zu) must be no smaller than n = %zu and batch x 2 n (%d x %zu) at most 2^%d", what, stride_elems, n, batch, 2 * n,
+                  host::KZG_OPEN_ALL_MAX_SLOTS_LOG2);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
+
+int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const uint64_t* coeffs, size_t stride_elems, int batch, uint64_t* proofs_out)
+{
+    int log2n;
+    if (int rc = open_all_n("host kzg_open_all", n, &log2n)) return rc;
+    if (int rc = open_all_batch("host kzg_open_all", batch)) return rc;
+    if (!points_endo_table || !coeffs || !proofs_out) {
+        set_error("host kzg_open_all: null table / coeffs / proofs");
+        return BBGPU_ERR_ARG;
+    }
+    if (int rc = open_all_sizes("host kzg_open_all", n, stride_elems, batch)) return rc;
+    std::vector<host::Xyzz> S;
+    uint64_t bad = 0;
+    if (host::kzg_open_all_setup_host(points_endo_table, n, log2n, S, &bad)) {
+        set_error("host kzg_open_all: row %llu is not on the curve", (unsigned long long)bad);
+        return BBGPU_ERR_ARG;
+    }
+    host::kzg_open_all_proofs_host(S, n, log2n, coeffs, stride_elems, batch, proofs_out);
+    return BBGPU_OK;
+}
+
+int bbgpu_kzg_open_all_setup(int srs_handle, size_t n)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound: a handle can only exist once one is
+    int log2n;
+    if (int rc = open_all_n("kzg_open_all_setup", n, &log2n)) return rc;
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
+        set_error("unknown SRS handle %d", srs_handle);
+        return BBGPU_ERR_ARG;
+    }
+    if (n > ctx().srs[srs_handle].n) {
+        set_error("kzg_open_all_setup of %zu rows, the table holds %zu", n, ctx().srs[srs_handle].n);
+        return BBGPU_ERR_SIZE;
+    }
+    int slot = -1;
+    for (int k = 0; k < BBGPU_KZG_OPEN_ALL_MAX_SETUPS && slot < 0; k++)
+        if (!g_open_all[k].live) slot = k;
+    if (slot < 0) {
+        set_error("kzg_open_all_setup: %d setups are live", BBGPU_KZG_OPEN_ALL_MAX_SETUPS);
+        return BBGPU_ERR_STATE;
+    }
+    if (int rc = ensure_init()) return rc;
+    const uint32_t* d_in = ctx().srs[srs_handle].d_srs;
+    const hipStream_t st = ctx().stream;
+    // the curve pass over the rows the string reads, [0, n - 1), in the staging of bbgpu_srs_check (the generator verdict is not used)
+    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, 64)) return rc;
+    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
+    const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
+    SrsCurveFindings got = init;
+    HIPCHK(h2d_async(d_find, &init, sizeof init, st));
+    if (int rc = srs_check_curve(d_in, n - 1, no_generator, d_find, st)) return rc;
+    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (got.bad_points) {
+        set_error("kzg_open_all_setup: row %llu is not on the curve (%llu such rows)", (unsigned long long)got.first_bad_point, (unsigned long long)got.bad_points);
+        return BBGPU_ERR_ARG;
+    }
+    const Limbs9 W = host::limbs_m261(host::fr_root_of_unity(log2n + 1));
+    OpenAllSetup o;
+    if (int rc = kzg_open_all_string(d_in, n, log2n, W.d, &o.d_S, st)) return rc;
+    o.log2n = log2n;
+    o.bytes = 2 * n * 128;
+    o.live = true;
+    g_open_all[slot] = o;
+    return slot;
+}
+
+int bbgpu_kzg_open_all_release(int setup)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (setup < 0 || setup >= BBGPU_KZG_OPEN_ALL_MAX_SETUPS || !g_open_all[setup].live) {
+        set_error("kzg_open_all_release: unknown setup %d", setup);
+        return BBGPU_ERR_ARG;
+    }
+    open_all_release(g_open_all[setup]); // (dev_free waits for the device: no queued call still reads S^)
+    return BBGPU_OK;
+}
+
+int bbgpu_kzg_open_all_device(int setup, const uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* proofs_out, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rc = open_all_batch("kzg_open_all", batch)) return rc;
+    if (!d_coeffs || !proofs_out) {
+        set_error("kzg_open_all: null coeffs / proofs");
+        return BBGPU_ERR_ARG;
+    }
+    if (setup < 0 || setup >= BBGPU_KZG_OPEN_ALL_MAX_SETUPS || !g_open_all[setup].live) {
+        set_error("kzg_open_all: unknown setup %d", setup);
+        return BBGPU_ERR_ARG;
+    }
+    const OpenAllSetup& o = g_open_all[setup];
+    const size_t n = (size_t)1 << o.log2n, N = 2 * n;
+    if (int rc = open_all_sizes("kzg_open_all", n, stride_elems, batch)) return rc;
+    if (int rc = ensure_init()) return rc;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    // t, then t^, then the proofs (batch x N x 32 = batch x n x 64 bytes), and the scratch points
+    DevBuf t, scratch;
+    HIPCHK(dev_malloc(&t.p, (size_t)batch * N * 32));
+    HIPCHK(dev_malloc(&scratch.p, (size_t)batch * N * 128));
+    if (int rc = kzg_open_all_t(d_coeffs, stride_elems, batch, n, t.as<uint64_t>(), st)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(t.as<uint64_t>(), N, N, batch, BBGPU_FFT, nullptr, hip_stream)) return rc;
+    const host::Fr W = host::fr_root_of_unity(o.log2n + 1);
+    const host::Fr c32 = host::fr_from_mont(host::fr_mul(host::fr_inv(host::fr_from_u64((uint64_t)N)), host::fr_from_u64(32))); // the plain integer 32 / N
+    float ms4[4] = { 0, 0, 0, 0 };
+    if (int rc = kzg_open_all_chain(o.d_S, t.as<uint64_t>(), scratch.as<uint32_t>(), n, o.log2n, batch, host::limbs_m256(c32).d, host::limbs_m261(host::fr_inv(W)).d,
+                                    host::limbs_m261(host::fr_root_of_unity(o.log2n)).d, st, ctx().timing ? ms4 : nullptr))
+        return rc;
+    if (int rc = device_to_host_sync(proofs_out, t.p, (size_t)batch * n * 64, st)) return rc;
+    if (ctx().timing) { // bbgpu_last_timing: index 0 the load kernel, 1 the inverse stages, 2 the gather kernel and the forward stages, 3 the finish kernel
+        ctx().last.count = 4;
+        for (int i = 0; i < 4; i++) ctx().last.ms[i] = ms4[i];
+    }
+    return BBGPU_OK;
+}
+
 int bbgpu_transcript_read_g1(const char* path, size_t degree, uint64_t* points_endo_table_out)
 {
     if (!path || !points_endo_table_out || degree == 0) return BBGPU_ERR_ARG;

@@ -48,6 +48,28 @@ static inline Xyzz g1_times_plain(const Xyzz& p, const Fr& k)
     return acc;
 }
 
+// the radix-2 transform on points, in place: v holds the input in bit-reversed order, root (Montgomery) is a primitive 2^log2n-th root of unity or its
+// inverse; out comes sum_j root^(i j) in_j in natural order.  A plain double-and-add per twiddle.  (host_kzg_open_all.hpp runs it both ways.)
+static inline void g1_transform_host(std::vector<Xyzz>& v, int log2n, const Fr& root)
+{
+    const size_t n = (size_t)1 << log2n;
+    for (int s = 0; s < log2n; s++) {
+        const size_t m = (size_t)1 << s, step = n >> (s + 1); // butterflies (k + j, k + j + m), twiddle root^(j step)
+        fallback_parallel(n / 2, 8, [&](size_t lo, size_t hi) {
+            for (size_t u = lo; u < hi; u++) {
+                const size_t j = u & (m - 1), k = (u >> s) << (s + 1);
+                const Xyzz a = v[k + j];
+                Xyzz t = v[k + j + m];
+                if (j) t = g1_times_plain(t, fr_from_mont(fr_pow(root, (uint64_t)(j * step))));
+                Xyzz nt = t;
+                nt.y = fq_neg(t.y);
+                v[k + j] = g1_add(a, t);
+                v[k + j + m] = g1_add(a, nt);
+            }
+        });
+    }
+}
+
 // bbgpu_host_srs_lagrange: rows are the even entries of a 2n-entry endo table; table_out may alias table.  n = 2^log2n.
 static inline int srs_lagrange_host(const uint64_t* table, size_t n, int log2n, uint64_t* table_out, bbgpu_srs_lagrange_report* R)
 {
@@ -73,21 +95,7 @@ static inline int srs_lagrange_host(const uint64_t* table, size_t n, int log2n, 
     fallback_parallel(n, 16, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; i++) v[i] = g1_times_plain(v[i], ninv);
     });
-    for (int s = 0; s < log2n; s++) {
-        const size_t m = (size_t)1 << s, step = n >> (s + 1); // butterflies (k + j, k + j + m), twiddle omega_n^-(j step)
-        fallback_parallel(n / 2, 8, [&](size_t lo, size_t hi) {
-            for (size_t u = lo; u < hi; u++) {
-                const size_t j = u & (m - 1), k = (u >> s) << (s + 1);
-                const Xyzz a = v[k + j];
-                Xyzz t = v[k + j + m];
-                if (j) t = g1_times_plain(t, fr_from_mont(fr_pow(winv, (uint64_t)(j * step))));
-                Xyzz nt = t;
-                nt.y = fq_neg(t.y);
-                v[k + j] = g1_add(a, t);
-                v[k + j + m] = g1_add(a, nt);
-            }
-        });
-    }
+    g1_transform_host(v, log2n, winv);
     std::vector<uint64_t> out(16 * n);
     std::vector<uint8_t> inf(n, 0);
     fallback_parallel(n, 64, [&](size_t lo, size_t hi) {

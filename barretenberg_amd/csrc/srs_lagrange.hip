@@ -2,7 +2,7 @@
 // basis of the size-n domain, L_i = n^-1 sum_j omega^(-i j) P_j: an inverse NTT whose elements are curve points.  Radix-2, decimation in time, one lane per
 // butterfly, on a scratch of n projective points (XYZZ, 128 bytes each; g1_ladder.hpp):
 //   k_lagrange_load    slot i <- n^-1 * P_bitrev(i): the scaling goes in here, one ladder per row over an affine base, no inversion;
-//   k_lagrange_stage   log2 n launches, in place: (a, b) -> (a + w b, a - w b) with w = omega^(-e) made in the lane by square-and-multiply on e (as
+//   k_lagrange_stage   (g1_stage.hpp) log2 n launches, in place: (a, b) -> (a + w b, a - w b) with w = omega^(-e) made in the lane by square-and-multiply on e (as
 //                      k_srs_update makes y^e; no twiddle table) and w b by the ladder of k_srs_update over a projective base.  e == 0 skips the ladder;
 //   k_lagrange_finish  one Fermat inversion per row to the resident form; rows at infinity are counted as k_srs_on_curve counts its findings.
 // The reference has no counterpart: its strings are monomial (io.hpp:159-181) and its Lagrange-basis polynomials are transformed, never committed as values.
@@ -11,15 +11,13 @@
 #include <algorithm>
 
 #include "bbgpu_internal.h"
-#include "g1_ladder.hpp"
+#include "g1_stage.hpp"
 
 namespace bbgpu {
 
 namespace {
 
-constexpr int LT = 64;  // threads per workgroup of the ladder kernels: one wave, as k_srs_update
-constexpr int FT = 256; // of the finish kernel, as k_srs_on_curve
-constexpr int LAGRANGE_WB = 3; // the windows of k_srs_update (srs_update.hip)
+constexpr int FT = 256; // threads per workgroup of the finish kernel, as k_srs_on_curve (LT, of the ladder kernels, and the windows: g1_stage.hpp)
 
 struct Scalar256 {
     uint64_t d[4];
@@ -44,41 +42,6 @@ __global__ void __launch_bounds__(LT) k_lagrange_load(const uint32_t* __restrict
     uint32_t o[32];
     store_pt(o, acc, inf);
     store_words32(scratch + (size_t)i * 32, o);
-}
-
-// stage s (half = 2^s): butterfly u of n / 2 owns slots g 2 half + pos and that + half, with the twiddle omega_n^-(pos n / (2 half)).  While a stage has at
-// least a wave of groups, consecutive lanes take consecutive GROUPS at one position: the twiddle, and with it the skip of the ladder at pos == 0, is
-// wave-uniform (every slot is 128 bytes, so neither order coalesces).  Later stages take consecutive positions of one group.
-__global__ void __launch_bounds__(LT) k_lagrange_stage(uint32_t* __restrict__ scratch, uint32_t n, uint32_t log2n, uint32_t s, Limbs9 winv261)
-{
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n / 2) return;
-    const uint32_t half = 1u << s, groups = n >> (s + 1);
-    uint32_t pos, g;
-    if (groups >= (uint32_t)LT) {
-        pos = u >> (log2n - 1 - s); // < half
-        g = u & (groups - 1);
-    } else {
-        pos = u & (half - 1);
-        g = u >> s; // < groups
-    }
-    const size_t ia = (size_t)g * 2 * half + pos, ib = ia + half; // ib <= (groups - 1) 2 half + 2 half - 1 = n - 1
-    const uint32_t e = pos * groups;                              // < n / 2
-    uint64_t k[4] = { 1, 0, 0, 0 };
-    if (e) {
-        Fe<FrP, 1, 2> w = fe_one<FrP>(), b = fe_from<FrP>(winv261.d);
-        for (uint32_t x = e; x; x >>= 1) {
-            if (x & 1) w = mul(w, b);
-            b = sqr(b);
-        }
-        FeT<FrP> one_raw = fe_zero<FrP>();
-        one_raw.d[0] = 1;
-        uint32_t kw[8];
-        to_canonical(mul(w, one_raw), kw);
-#pragma unroll
-        for (int t = 0; t < 4; t++) k[t] = (uint64_t)kw[2 * t] | ((uint64_t)kw[2 * t + 1] << 32);
-    }
-    butterfly_slots<LAGRANGE_WB>(scratch + ia * 32, scratch + ib * 32, k, e == 0);
 }
 
 // row i <- the affine form of slot i (Montgomery-261, canonical); a slot at infinity gives a zero row and a finding.  Findings meet on chip as in
@@ -166,7 +129,7 @@ int srs_lagrange_rows(const uint32_t* d_in, size_t n, int log2n, const uint32_t 
     if (ms3) HIPCHK(hipEventRecord(ev.e[0], st));
     k_lagrange_load<<<(n32 + LT - 1) / LT, LT, 0, st>>>(d_in, scratch.as<uint32_t>(), n32, lg, k);
     if (ms3) HIPCHK(hipEventRecord(ev.e[1], st));
-    for (uint32_t s = 0; s < lg; s++) k_lagrange_stage<<<(n32 / 2 + LT - 1) / LT, LT, 0, st>>>(scratch.as<uint32_t>(), n32, lg, s, wl);
+    for (uint32_t s = 0; s < lg; s++) k_lagrange_stage<<<(n32 / 2 + LT - 1) / LT, LT, 0, st>>>(scratch.as<uint32_t>(), n32, lg, s, wl, 0);
     if (ms3) HIPCHK(hipEventRecord(ev.e[2], st));
     k_lagrange_finish<<<(uint32_t)std::min<size_t>((n + FT - 1) / FT, 2048), FT, 0, st>>>(scratch.as<uint32_t>(), rows.as<uint32_t>(), (uint64_t)n, d_find);
     HIPCHK(launch_check()); // the chain: load, stages, finish

@@ -753,7 +753,7 @@ int bbgpu_transcript_write_g2(const char* path, const uint64_t* points_endo_tabl
  * read-backs + the host table's; two launch checks -- the curve pass, and the chain of load, stage and finish kernels -- + the export kernel's + one per
  * window-table segment).
  * The kernels (csrc/srs_lagrange.hip): radix-2, decimation in time, on a scratch of n projective points (XYZZ, 128 bytes each, ZZ == 0 for infinity).
- * k_lagrange_load puts n^-1 * P_bitrev(i) into slot i (one ladder per row); log2 n launches of k_lagrange_stage run (a, b) -> (a + w b, a - w b) in place,
+ * k_lagrange_load puts n^-1 * P_bitrev(i) into slot i (one ladder per row); log2 n launches of k_lagrange_stage (csrc/g1_stage.hpp) run (a, b) -> (a + w b, a - w b) in place,
  * one lane per butterfly, w = omega^-e made in the lane by square-and-multiply and w b by the ladder of k_srs_update (csrc/g1_ladder.hpp: signed
  * endomorphism split, 3-bit odd signed windows, 126 doublings) over a projective base and without its inversion -- butterflies with w = 1 skip it;
  * k_lagrange_finish normalises with one Fermat inversion per row and counts the rows at infinity.
@@ -821,6 +821,66 @@ int bbgpu_srs_lagrange_check(int lagrange_handle, int monomial_handle, size_t n,
  * the bucket method of the bbgpu_host_* family, the same verdict and bisection); no HIP call, no lock */
 int bbgpu_host_srs_lagrange_check(const uint64_t* lagrange_endo_table, const uint64_t* monomial_endo_table, size_t n, const uint64_t seed[4], int flags,
                                   bbgpu_srs_lagrange_check_report* out);
+
+/* ---- open a polynomial at every point of its domain: all n KZG proofs at once ------
+ * The opening proof of f = sum_j c_j X^j at z is pi(z) = [(f(X) - f(z)) / (X - z)](x) G = sum_{m <= n-2} z^m h_m with h_m = sum_{j > m} c_j P_(j-m-1).  Every
+ * entry above prices one proof at an O(n) quotient pass and an n-point MSM; a caller who needs the proof at EVERY point of the size-n domain (data
+ * availability sampling, vector commitments, lookup tables, one evaluation with its proof per party) would pay that n times.  The n proofs are one
+ * structured linear map of the string (Feist and Khovratovich): (pi(omega^0) .. pi(omega^(n-1))) is the forward size-n group transform of
+ * (h_0 .. h_(n-2), infinity), and h is a Toeplitz product that one cyclic convolution of length N = 2 n delivers.  With omega = fr_root_of_unity(log2 n) and
+ * W = fr_root_of_unity(log2 n + 1), the roots the transforms and bbgpu_srs_lagrange use:
+ *   s = (P_(n-2), P_(n-3), .., P_0, infinity x (n + 1))        the string only
+ *   t = (c_(n-1), 0 x (n + 1), c_1, c_2, .., c_(n-2))          (n = 2: (c_1, 0, 0, 0))
+ *   h = the first n entries of IDFT_N(DFT_N(s) o DFT_N(t)), root W, the product pointwise
+ * O(n log n) group operations in place of n MSMs.  The reference has no counterpart.
+ * bbgpu_kzg_open_all_setup computes S^ = DFT_N(s) ONCE from rows [0, n - 1) of a resident monomial table and keeps its N rows on the device (scratch form,
+ * 128 bytes each, ZZ == 0 for infinity; counted in bbgpu_memory_info.staging_bytes, released by bbgpu_kzg_open_all_release or bbgpu_shutdown).
+ *   n            a power of two, 2 <= n <= 2^21, no larger than the table: otherwise BBGPU_ERR_SIZE.  An unknown SRS handle: BBGPU_ERR_ARG.
+ *                BBGPU_ERR_STATE: BBGPU_KZG_OPEN_ALL_MAX_SETUPS setups are live.  All are refused before a device is bound.
+ *   bad rows     the curve pass (k_srs_on_curve) runs over the input rows first, as in bbgpu_srs_lagrange: a bad row is BBGPU_ERR_ARG, bbgpu_last_error()
+ *                naming the first one, and no setup is made.
+ *   infinity     a row of S^ at infinity is legal and kept exactly -- it is an intermediate, not a table anyone commits over.  It happens when
+ *                (W^k / x)^(n-1) = 1 and W^k != x; at n = 4 that is x = W^k zeta, zeta a primitive cube root of unity in Fr.
+ * Returns the setup handle (>= 0).  A warm setup passes one allocation (S^), one upload and one read-back (the curve findings) and two launch checks (the
+ * curve pass; the chain of k_open_all_string and the log2 N stage kernels).  The SRS handle is not read after the setup returns and may be released.
+ * bbgpu_kzg_open_all_device opens `batch` polynomials in coefficient form over one setup: coefficient j of polynomial b at
+ * d_coeffs[(b * stride_elems + j) * 4] (device memory, read only; the reference's memory format, any representative), and writes batch x n affine points to
+ * HOST memory: proofs_out[(b * n + i) * 8] is pi_b(omega^i) in the reference's format (Montgomery-256, canonical; infinity: bit 63 of y[3], every other word
+ * zero).  Infinity is an ordinary result: a constant polynomial has every proof at infinity.  The evaluations y_i = f(omega^i) are one bbgpu_ntt_device
+ * away for the caller; this entry does not return them.
+ *   BBGPU_ERR_SIZE   batch outside 1..64, stride_elems < n, batch x 2 n > 2^22
+ *   BBGPU_ERR_ARG    an unknown setup, a null pointer                                    -- all refused before a device is bound
+ * The kernels (csrc/kzg_open_all.hip; every one takes the polynomial from blockIdx.y, so that a batch of small domains fills the chip): k_open_all_t writes
+ * the batch x N scalars of t and bbgpu_ntt_device_batch transforms them; k_open_all_load puts (N^-1 t^_bitrev(i)) * S^_bitrev(i) into slot i -- each lane reads
+ * its own scalar, brings it to a plain canonical integer by one product and runs one ladder (csrc/g1_ladder.hpp) over a projective base; a zero scalar or
+ * an infinite base gives infinity; log2 N launches of k_lagrange_stage (csrc/g1_stage.hpp, the one text bbgpu_srs_lagrange launches too) with root W^-1;
+ * k_open_all_gather copies slots 0 .. n-2 bit-reversed into the upper half of the polynomial's own slots, with infinity last; log2 n launches of
+ * k_lagrange_stage with root omega there; k_open_all_finish normalises with one Fermat inversion per row and refuses nothing.  One wave per workgroup,
+ * 3-bit windows, no twiddle table, as bbgpu_srs_lagrange.
+ * The entry runs on context 0 under the library mutex; every allocation, copy and launch check passes the fault-injection funnels.  A warm call at n = 64:
+ * two allocations (t, which later holds the proofs, and the scratch points), no upload, one read-back (the proofs: one staging chunk), and three launch
+ * checks (k_open_all_t; the transform's single pass at this size; the chain from the load kernel to the finish kernel).  After a failure nothing the call allocated is live and
+ * the setup stays usable.  With bbgpu_set_timing(1), bbgpu_last_timing() index 0 is the device time of k_open_all_load, 1 that of the inverse stages, 2 that
+ * of the gather kernel and the forward stages, 3 that of k_open_all_finish.
+ * Cost on one MI355X (tools/kzg_open_all_bench.py, profiles/kzg_open_all.txt): wall ms per call, proofs read back to the host, one box.  n = 2^12:
+ * 24.5 ms at batch 1 and 28.0 ms at batch 16 -- a single 4096-row call is bound by the latency of its 25 stage launches (the inverse stages 12.1 ms, the
+ * gather and the forward stages 11.1 ms, the load kernel 1.0 ms, the finish kernel 0.15 ms of device time), and fifteen more polynomials ride along for
+ * 3.6 ms; n = 2^16: 34.8 ms at batch 1, 348 ms at batch 16 (the chip is full: inverse stages 214 ms, forward 102 ms, load 28 ms); n = 2^20: 433 ms (inverse
+ * stages 271 ms = 12.9 ns per butterfly that runs a ladder, forward 130 ms, load 28 ms, finish 1.9 ms).  The setup, with its release: 12.2 ms, 16.8 ms and
+ * 271 ms.  Against the path a caller had before -- bbgpu_kate_opening_device, then bbgpu_msm_g1_device, per point over the same handle, timed in the same
+ * process on a SAMPLE of 256 points and SCALED to all n (an extrapolation): 1.54 s at 2^12, 24.2 s at 2^16 and 1487 s at 2^20 per polynomial; the new
+ * entry is lower at every size measured, by far more than either spread.
+ * The host twin (csrc/host_kzg_open_all.hpp) runs the same construction over host_g1.hpp: the scalar transform of the bbgpu_host_* family, the radix-2
+ * group transform of bbgpu_host_srs_lagrange and a plain double-and-add per product.  The results are unique affine points, so device and twin agree bit
+ * for bit.  It takes the even entries of a caller's endo table (at least n - 1 rows are read), makes no HIP call, takes no lock and is re-entrant; its
+ * errors are those of the two device entries (a row off the curve: BBGPU_ERR_ARG naming it). */
+#define BBGPU_KZG_OPEN_ALL_MAX_SETUPS 16
+int bbgpu_kzg_open_all_setup(int srs_handle, size_t n); /* setup handle >= 0 */
+int bbgpu_kzg_open_all_release(int setup);
+int bbgpu_kzg_open_all_device(int setup, const uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* proofs_out /* host, batch x n x 8 */,
+                              void* hip_stream);
+int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const uint64_t* coeffs, size_t stride_elems, int batch,
+                            uint64_t* proofs_out /* batch x n x 8 */);
 
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
