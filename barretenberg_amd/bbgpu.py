@@ -69,6 +69,8 @@ C_ABI_SYMBOLS = [
     "bbgpu_lagrange_opening_end", "bbgpu_fr_fold_device", "bbgpu_host_fr_fold", "bbgpu_host_kate_opening_lagrange_folded", "bbgpu_host_kzg_check_openings",
     "bbgpu_selftest_plonk_round",
     "bbgpu_kzg_open_all_setup", "bbgpu_kzg_open_all_release", "bbgpu_kzg_open_all_device", "bbgpu_host_kzg_open_all",
+    "bbgpu_kzg_check_openings", "bbgpu_kzg_check_open_all", "bbgpu_host_kzg_check_openings_batch", "bbgpu_host_kzg_check_open_all",
+    "bbgpu_kzg_check_last_timing",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -168,6 +170,18 @@ class PlonkVerifyReport(C.Structure):
         d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32)}
         d.update(seed=[int(v) for v in self.seed], a=[int(v) for v in self.a], b=[int(v) for v in self.b], ok=bool(self.ok),
                  status=[int(v) for v in self.status] if self.status is not None else None)
+        return d
+
+
+class KzgCheckReport(C.Structure):
+    """bbgpu_kzg_check_report (include/bbgpu.h)"""
+    NONE = 0xFFFFFFFFFFFFFFFF  # first_bad when there is none
+    _fields_ = [("count", C.c_uint64), ("bad_points", C.c_uint64), ("first_bad", C.c_uint64), ("first_bad_is_proof", C.c_uint32), ("g2_ok", C.c_uint32),
+                ("ok", C.c_uint32), ("rounds", C.c_uint32), ("first_failing", C.c_int64), ("seed", C.c_uint64 * 4), ("a", C.c_uint64 * 8), ("b", C.c_uint64 * 8)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32, C.c_int64)}
+        d.update(seed=[int(v) for v in self.seed], a=[int(v) for v in self.a], b=[int(v) for v in self.b])
         return d
 
 
@@ -580,6 +594,64 @@ class BbGpu:
         self.lib.bbgpu_host_kzg_open_all.argtypes = [u64p, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p]
         self._chk(self.lib.bbgpu_host_kzg_open_all(_ptr(table), int(n), _ptr(coeffs), stride, batch, _ptr(out)))
         return out
+
+    # ---- do these openings hold?  (bbgpu_kzg_check_openings, bbgpu_kzg_check_open_all and the host twins) ----
+    def _kzg_check_openings(self, fn, commitments, z, y, proofs, g2_x, which, seed, locate):
+        cs = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
+        ps = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8)
+        zs, ys = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4), np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 4)
+        labels = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1) if which is not None else None
+        count = ps.shape[0]
+        if zs.shape[0] != count or ys.shape[0] != count or (labels is None and cs.shape[0] != count) or (labels is not None and labels.shape[0] != count):
+            raise ValueError("kzg_check_openings: %d proofs, %d z, %d y, %d commitments, %s labels" %
+                             (count, zs.shape[0], ys.shape[0], cs.shape[0], "no" if labels is None else labels.shape[0]))
+        g2, sd, g2p, sdp, flags = self._srs_check_args(g2_x, seed, locate)
+        rep = KzgCheckReport()
+        fn.argtypes = [u64p, C.POINTER(C.c_uint32), C.c_size_t, u64p, u64p, u64p, C.c_size_t, u64p, u64p, C.c_int, C.POINTER(KzgCheckReport)]
+        lp = labels.ctypes.data_as(C.POINTER(C.c_uint32)) if labels is not None else None
+        self._chk(fn(_ptr(cs), lp, cs.shape[0], _ptr(zs), _ptr(ys), _ptr(ps), count, g2p, sdp, flags, C.byref(rep)))
+        return rep.as_dict()
+
+    def _kzg_check_open_all(self, fn, commitments, values, proofs, n, g2_x, batch, stride, seed, locate):
+        cs = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
+        ps = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8)
+        vs = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        batch = cs.shape[0] if batch is None else int(batch)
+        stride = int(n) if stride is None else int(stride)
+        if 1 <= batch <= 64 and int(n) >= 1 and (cs.shape[0] < batch or ps.shape[0] < batch * int(n) or vs.shape[0] < (batch - 1) * stride + int(n)):
+            raise ValueError("kzg_check_open_all: batch %d of n = %d at stride %d over %d commitments, %d values, %d proofs" %
+                             (batch, n, stride, cs.shape[0], vs.shape[0], ps.shape[0]))
+        g2, sd, g2p, sdp, flags = self._srs_check_args(g2_x, seed, locate)
+        rep = KzgCheckReport()
+        fn.argtypes = [u64p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p, u64p, C.c_int, C.POINTER(KzgCheckReport)]
+        self._chk(fn(_ptr(cs), _ptr(vs), stride, _ptr(ps), int(n), batch, g2p, sdp, flags, C.byref(rep)))
+        return rep.as_dict()
+
+    def kzg_check_openings(self, commitments, z, y, proofs, g2_x, which=None, seed=None, locate=False):
+        """bbgpu_kzg_check_openings: up to 2^20 claims (C, z_t, y_t, pi_t) checked on the GPU by two MSMs and ONE pairing product.  which None: one
+        commitment per claim, (count, 8); else (count,) labels into at most 64 shared commitments.  seed None: drawn from the operating system (whoever
+        made the proofs must not know it).  Returns the report as a dict (ok, bad_points, first_bad, first_failing, rounds, seed, a, b ...)."""
+        return self._kzg_check_openings(self.lib.bbgpu_kzg_check_openings, commitments, z, y, proofs, g2_x, which, seed, locate)
+
+    def host_kzg_check_openings_batch(self, commitments, z, y, proofs, g2_x, which=None, seed=None, locate=False):
+        """bbgpu_host_kzg_check_openings_batch: the same definition on the host; no GPU needed"""
+        return self._kzg_check_openings(self.lib.bbgpu_host_kzg_check_openings_batch, commitments, z, y, proofs, g2_x, which, seed, locate)
+
+    def kzg_check_open_all(self, commitments, values, proofs, n, g2_x, batch=None, stride=None, seed=None, locate=False):
+        """bbgpu_kzg_check_open_all: what kzg_open_all_device writes, checked in one call: commitments (batch, 8), values (batch * stride, 4) with
+        values[b * stride + i] = f_b(omega^i), proofs (batch, n, 8).  Returns the report as a dict."""
+        return self._kzg_check_open_all(self.lib.bbgpu_kzg_check_open_all, commitments, values, proofs, n, g2_x, batch, stride, seed, locate)
+
+    def host_kzg_check_open_all(self, commitments, values, proofs, n, g2_x, batch=None, stride=None, seed=None, locate=False):
+        """bbgpu_host_kzg_check_open_all: the same definition on the host; no GPU needed"""
+        return self._kzg_check_open_all(self.lib.bbgpu_host_kzg_check_open_all, commitments, values, proofs, n, g2_x, batch, stride, seed, locate)
+
+    def kzg_check_last_timing(self):
+        """bbgpu_kzg_check_last_timing: wall ms of the last kzg_check_openings or kzg_check_open_all by stage"""
+        buf = (C.c_double * 5)()
+        self.lib.bbgpu_kzg_check_last_timing.argtypes = [C.POINTER(C.c_double)]
+        self._chk(self.lib.bbgpu_kzg_check_last_timing(buf))
+        return dict(zip(("total_ms", "claims_ms", "fold_ms", "msm_ms", "host_tail_ms"), buf))
 
     # ---- is this table the Lagrange form of that string?  (bbgpu_srs_lagrange_check and its host twin) ----
     def srs_lagrange_check(self, lagrange_handle, monomial_handle, n, seed=None, locate=False):

@@ -172,6 +172,27 @@ struct VerifyCircuits {
 int plonk_verify_terms(const VerifyCircuits& C, const uint64_t seed[4], size_t count, const VerifyDeviceBuffers& B, hipStream_t st);
 int plonk_verify_fold(const VerifyCircuits& C, const uint64_t* d_shared, size_t count, size_t m, uint64_t* d_out, hipStream_t st); // the first m proofs
 
+// kzg_check.hip: the device parts of a check of KZG openings (bbgpu_kzg_check_openings, bbgpu_kzg_check_open_all) that are not an MSM
+struct KzgFindings {
+    unsigned long long bad_points, first_key; // finite points off the curve; the smallest 2 t + (1 for the proof) among them (the caller starts it at ~0)
+};
+struct KzgCheckBuffers {
+    const uint64_t *proofs, *commitments, *z, *y; // the caller's arrays on the device: count x 8, count x 8 (per-claim layout), count x 4 (not open-all), count x 4
+    const uint32_t* which;                        // count labels (shared layout with explicit labels)
+    uint32_t* rows;                               // the claims' resident rows: (C_t, pi_t) in the per-claim layout, else pi_t
+    uint64_t *scal_a, *scal_b;                    // the scalars of A and of B on those rows
+    uint64_t *term_y, *term_rho;                  // count x 4 words each: rho_t y_t; rho_t (shared layouts)
+    uint64_t* partial;                            // (S + 1) x KZG_FOLD_MAX_RANGES x 4 words
+    KzgFindings* find;
+};
+constexpr size_t KZG_FOLD_RANGE = 4096;      // claims per workgroup of the fold until KZG_FOLD_MAX_RANGES ranges are in use
+constexpr size_t KZG_FOLD_MAX_RANGES = 256;  // one thread of the finish kernel per range
+uint32_t kzg_check_claim_threads(size_t count); // threads of the k_kzg_claims grid: the stride of the open-all form's powers
+uint32_t kzg_check_fold_ranges(size_t m);
+int kzg_check_claims(const KzgCheckBuffers& B, const uint64_t seed[4], size_t count, bool per_claim, bool open_all, int log2n, const uint32_t omega_m261[9],
+                     const uint32_t step_m261[9], hipStream_t st);
+int kzg_check_fold(const KzgCheckBuffers& B, size_t m, size_t S, int log2n, uint64_t skip_mask, uint64_t* d_out, hipStream_t st); // the first m claims
+
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);
 int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_t st, bool* touched = nullptr); // *touched: h_dst may have been written (even on failure)

@@ -31,6 +31,7 @@
 #include "host_srs_update.hpp"
 #include "host_srs_lagrange.hpp"
 #include "host_kzg_check.hpp"
+#include "host_kzg_check_batch.hpp"
 #include "host_lagrange_open.hpp"
 #include "host_srs_lagrange_check.hpp"
 #include "host_kzg_open_all.hpp"
@@ -251,6 +252,8 @@ struct Context {
     size_t srs_check_cap = 0;
     uint64_t* d_verify = nullptr; // bbgpu_plonk_verify_batch: the proofs, the rows and scalars of the two sums, the shared terms, the statuses
     size_t verify_cap = 0;
+    uint64_t* d_kzg_check = nullptr; // bbgpu_kzg_check_*: the caller's arrays, the rows and scalars of the two sums, the terms, the partial sums, the findings
+    size_t kzg_check_cap = 0;
     int timing = 0; // 0 off, 1 every stage, 2 the accumulation only (bbgpu_set_timing)
     bool precompute = true; // build window tables for registered SRS (bbgpu_set_precompute)
     uint64_t use_clock = 0;  // LRU clock of the SRS cache
@@ -1389,6 +1392,9 @@ void release_context(bool primary)
     if (C.d_verify) (void)dev_free(C.d_verify);
     C.d_verify = nullptr;
     C.verify_cap = 0;
+    if (C.d_kzg_check) (void)dev_free(C.d_kzg_check);
+    C.d_kzg_check = nullptr;
+    C.kzg_check_cap = 0;
     if (primary) ntt_release_tables();
     if (C.shared_done) (void)hipEventDestroy(C.shared_done);
     C.shared_done = nullptr;
@@ -1436,7 +1442,7 @@ void add_context_memory(const Context& C, bool primary, bbgpu_memory_info* out)
         out->msm_workspace_bytes += sl.ws.cap;
         if (sl.ws.h_out) out->pinned_host_bytes += (uint64_t)MSM_HOUT_GROUPS * 64 * 128;
     }
-    out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap + C.srs_check_cap + C.verify_cap;
+    out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap + C.srs_check_cap + C.verify_cap + C.kzg_check_cap;
     if (primary) out->staging_bytes += plonk_lane_bytes() + opening_session_bytes() + open_all_setup_bytes(); // the resident prover, the opening sessions and the open-all setups live on context 0
     for (int k = 0; k < Context::HOST_RING; k++)
         if (C.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
@@ -3553,6 +3559,224 @@ int bbgpu_plonk_verify_last_timing(double ms_out[5])
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (!ms_out) return BBGPU_ERR_ARG;
     for (int i = 0; i < 5; i++) ms_out[i] = g_verify_ms[i];
+    return BBGPU_OK;
+}
+
+/* ---- batched check of KZG openings (host_kzg_check_batch.hpp, kzg_check.hip) ---- */
+namespace {
+double g_kzg_check_ms[5] = { 0, 0, 0, 0, 0 }; // bbgpu_kzg_check_last_timing: wall ms of the last call between the synchronisations it makes anyway
+}
+
+static int kzg_check_refused(int rc, const char* why)
+{
+    set_error("KZG check: %s", why);
+    return rc;
+}
+// the call of bbgpu_(host_)kzg_check_openings and its argument verdict
+static int kzg_check_openings_call(host::KzgCheckCall* K, const uint64_t* commitments, const uint32_t* which, size_t num_commitments, const uint64_t* z,
+                                   const uint64_t* y, const uint64_t* proofs, size_t count, const uint64_t* g2_x, int flags, const bbgpu_kzg_check_report* out)
+{
+    K->commitments = commitments;
+    K->which = which;
+    K->S = which ? num_commitments : 0;
+    K->z = z;
+    K->y = y;
+    K->proofs = proofs;
+    K->count = count;
+    const char* why = "";
+    if (int rc = host::kzg_check_args(*K, which == nullptr, num_commitments, g2_x, flags, out, &why)) return kzg_check_refused(rc, why);
+    return BBGPU_OK;
+}
+// the same for bbgpu_(host_)kzg_check_open_all
+static int kzg_check_open_all_call(host::KzgCheckCall* K, const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n,
+                                   int batch, const uint64_t* g2_x, int flags, const bbgpu_kzg_check_report* out)
+{
+    if (!host::kzg_check_open_all_sizes_ok(n, stride, batch, &K->log2n))
+        return kzg_check_refused(BBGPU_ERR_SIZE, "n a power of two, 1 <= batch <= 64, stride >= n and batch x n <= 2^20 are taken");
+    K->commitments = commitments;
+    K->S = (size_t)batch;
+    K->y = values;
+    K->y_stride = stride;
+    K->proofs = proofs;
+    K->count = (size_t)batch * n;
+    K->open_all = true;
+    const char* why = "";
+    if (int rc = host::kzg_check_args(*K, false, (size_t)batch, g2_x, flags, out, &why)) return kzg_check_refused(rc, why);
+    return BBGPU_OK;
+}
+static int kzg_check_seed(const uint64_t* seed, uint64_t sd[4])
+{
+    if (host::srs_check_seed(seed, sd)) return BBGPU_OK;
+    set_error("KZG check: the operating system gave no randomness");
+    return BBGPU_ERR_STATE;
+}
+
+int bbgpu_host_kzg_check_openings_batch(const uint64_t* commitments, const uint32_t* which, size_t num_commitments, const uint64_t* z, const uint64_t* y,
+                                        const uint64_t* proofs, size_t count, const uint64_t g2_x[16], const uint64_t seed[4], int flags,
+                                        bbgpu_kzg_check_report* report)
+{
+    host::KzgCheckCall K;
+    if (int rc = kzg_check_openings_call(&K, commitments, which, num_commitments, z, y, proofs, count, g2_x, flags, report)) return rc;
+    uint64_t sd[4];
+    if (int rc = kzg_check_seed(seed, sd)) return rc;
+    return host::kzg_check_host(K, g2_x, sd, flags, report);
+}
+int bbgpu_host_kzg_check_open_all(const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n, int batch,
+                                  const uint64_t g2_x[16], const uint64_t seed[4], int flags, bbgpu_kzg_check_report* report)
+{
+    host::KzgCheckCall K;
+    if (int rc = kzg_check_open_all_call(&K, commitments, values, stride, proofs, n, batch, g2_x, flags, report)) return rc;
+    uint64_t sd[4];
+    if (int rc = kzg_check_seed(seed, sd)) return rc;
+    return host::kzg_check_host(K, g2_x, sd, flags, report);
+}
+
+// a point in the reference's format as a resident row (Montgomery-261, canonical); the generator for the point at infinity.  Returns the infinity flag.
+static bool kzg_check_resident_row(const uint64_t* p, uint64_t out[8])
+{
+    uint64_t pt[8];
+    const bool inf = host::kzg_row(p, pt);
+    for (int c = 0; c < 2; c++) { // x 2^256 -> x 2^261
+        host::Fq v;
+        memcpy(v.d, pt + 4 * c, 32);
+        for (int i = 0; i < 5; i++) v = host::fq_dbl(v);
+        memcpy(out + 4 * c, v.d, 32);
+    }
+    return inf;
+}
+
+// The three forms behind their argument checks, modelled on verify_run: upload, k_kzg_claims, ONE synchronisation before the findings are read, then per
+// round the fold and two tickets over the rows as transient tables, and the shared host tail.
+static int kzg_check_run(const host::KzgCheckCall& K, const uint64_t g2_x[16], const uint64_t* seed, int flags, bbgpu_kzg_check_report* out)
+{
+    if (int rc = ensure_init()) return rc;
+    const double t_begin = now_ms();
+    for (double& v : g_kzg_check_ms) v = 0;
+    uint64_t sd[4];
+    if (int rc = kzg_check_seed(seed, sd)) return rc;
+    host::kzg_report_init(out, K.count, sd);
+    const size_t count = K.count, S = K.S, H = K.head(), per = K.per(), na = H + per * count, nb = per * count;
+    const bool per_claim = !K.shared();
+    // one staging buffer, every part at a multiple of 32 bytes (the kernels read and write 16 bytes at a time): the proofs | y | z | the per-claim commitments | the labels | the findings | the rows: the
+    // shared commitments, G, then the claims' | the scalars of A, of B | the terms rho y, rho | the partial sums of the fold.  The findings and the head
+    // of the rows are neighbours because they arrive in one copy.
+    auto up64 = [](size_t b) { return (b + 63) & ~(size_t)63; };
+    const size_t o_y = count * 64, o_z = o_y + count * 32, o_commit = o_z + (K.open_all ? 0 : count * 32), o_which = o_commit + (per_claim ? count * 64 : 0),
+                 o_find = o_which + (K.which ? up64(count * 4) : 0), o_rows = o_find + 64, o_scal_a = o_rows + na * 64, o_scal_b = o_scal_a + up64(na * 32),
+                 o_term_y = o_scal_b + up64(nb * 32), o_term_rho = o_term_y + count * 32, o_partial = o_term_rho + (per_claim ? 0 : count * 32),
+                 total = o_partial + H * KZG_FOLD_MAX_RANGES * 32;
+    static_assert(64 + (BBGPU_KZG_CHECK_MAX_COMMITMENTS + 1) * 64 <= Context::HOST_CHUNK, "the findings and the shared rows fit one pinned staging buffer");
+    if (int rc = grow(&ctx().d_kzg_check, &ctx().kzg_check_cap, total)) return rc;
+    uint8_t* base = reinterpret_cast<uint8_t*>(ctx().d_kzg_check);
+    uint32_t* d_rows = reinterpret_cast<uint32_t*>(base + o_rows);
+    uint64_t *d_scal_a = reinterpret_cast<uint64_t*>(base + o_scal_a), *d_scal_b = reinterpret_cast<uint64_t*>(base + o_scal_b);
+    KzgCheckBuffers B{};
+    B.proofs = reinterpret_cast<const uint64_t*>(base);
+    B.y = reinterpret_cast<const uint64_t*>(base + o_y);
+    B.z = K.open_all ? nullptr : reinterpret_cast<const uint64_t*>(base + o_z);
+    B.commitments = per_claim ? reinterpret_cast<const uint64_t*>(base + o_commit) : nullptr;
+    B.which = K.which ? reinterpret_cast<const uint32_t*>(base + o_which) : nullptr;
+    B.rows = d_rows + H * 16;
+    B.scal_a = d_scal_a + H * 4;
+    B.scal_b = d_scal_b;
+    B.term_y = reinterpret_cast<uint64_t*>(base + o_term_y);
+    B.term_rho = per_claim ? nullptr : reinterpret_cast<uint64_t*>(base + o_term_rho);
+    B.partial = reinterpret_cast<uint64_t*>(base + o_partial);
+    B.find = reinterpret_cast<KzgFindings*>(base + o_find);
+    const hipStream_t st = ctx().stream;
+    if (int rc = host_to_device(base, K.proofs, count * 64, st)) return rc;
+    if (K.open_all && K.y_stride != ((size_t)1 << K.log2n)) { // the values of each polynomial, without the caller's padding
+        const size_t n = (size_t)1 << K.log2n;
+        for (size_t b = 0; b < S; b++)
+            if (int rc = host_to_device(base + o_y + b * n * 32, K.y + b * K.y_stride * 4, n * 32, st)) return rc;
+    } else if (int rc = host_to_device(base + o_y, K.y, count * 32, st)) {
+        return rc;
+    }
+    if (!K.open_all)
+        if (int rc = host_to_device(base + o_z, K.z, count * 32, st)) return rc;
+    if (per_claim)
+        if (int rc = host_to_device(base + o_commit, K.commitments, count * 64, st)) return rc;
+    if (K.which)
+        if (int rc = host_to_device(base + o_which, K.which, count * 4, st)) return rc;
+    uint64_t shared_bad, shared_first, skip_mask = 0;
+    host::kzg_shared_findings(K, &shared_bad, &shared_first);
+    {
+        // the head, built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy: the findings' start, the shared rows, G
+        if (int rc = host_stage_ensure()) return rc;
+        const int kb = (int)(ctx().h_stage_next++ % Context::HOST_RING);
+        HIPCHK(hipEventSynchronize(ctx().h_stage_free[kb]));
+        uint8_t* h = static_cast<uint8_t*>(ctx().h_stage[kb]);
+        memset(h, 0, 64);
+        const KzgFindings init = { 0, ~0ull };
+        memcpy(h, &init, sizeof init);
+        uint64_t* rows = reinterpret_cast<uint64_t*>(h + 64);
+        for (size_t c = 0; c < S; c++)
+            if (kzg_check_resident_row(K.commitments + 8 * c, rows + 8 * c)) skip_mask |= 1ull << c;
+        const uint64_t inf[8] = { 0, 0, 0, 0, 0, 0, 0, 1ull << 63 };
+        (void)kzg_check_resident_row(inf, rows + 8 * S); // the generator
+        HIPCHK(h2d_async(base + o_find, h, 64 + H * 64, st));
+        HIPCHK(hipEventRecord(ctx().h_stage_free[kb], st));
+    }
+    Limbs9 omega{}, step{};
+    if (K.open_all) {
+        const host::Fr w = host::fr_root_of_unity(K.log2n);
+        omega = host::limbs_m261(w);
+        step = host::limbs_m261(host::fr_pow(w, (uint64_t)kzg_check_claim_threads(count) & (((uint64_t)1 << K.log2n) - 1)));
+    }
+    if (int rc = kzg_check_claims(B, sd, count, per_claim, K.open_all, K.log2n, omega.d, step.d, st)) return rc;
+    KzgFindings got = { 0, ~0ull };
+    HIPCHK(d2h_async(&got, B.find, sizeof got, st));
+    HIPCHK(hipStreamSynchronize(st));
+    g_kzg_check_ms[1] = now_ms() - t_begin;
+    host::kzg_report_findings(out, shared_bad, shared_first, got.bad_points, got.first_key);
+    int rc_tail = BBGPU_OK;
+    if (!out->bad_points) {
+        // A and B: two tickets in flight over ONE transient table (the rows written above; no window tables), A from its head, B from the first claim on
+        SrsEntry ea{}, eb{};
+        ea.n = na;
+        ea.d_srs = d_rows;
+        eb.n = nb;
+        eb.d_srs = d_rows + H * 16;
+        ea.live = eb.live = true;
+        rc_tail = host::kzg_check_tail(out, g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
+            const double t_fold = now_ms();
+            if (int rc = kzg_check_fold(B, m, S, K.log2n, skip_mask, d_scal_a, st)) return rc;
+            HIPCHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
+            const double t_msm = now_ms();
+            g_kzg_check_ms[2] += t_msm - t_fold;
+            if (int rc = verify_two_msms(ea, eb, d_scal_a, d_scal_b, H + per * m, per * m, a12, b12)) return rc;
+            g_kzg_check_ms[3] += now_ms() - t_msm;
+            return BBGPU_OK;
+        });
+    }
+    g_kzg_check_ms[0] = now_ms() - t_begin;
+    g_kzg_check_ms[4] = g_kzg_check_ms[0] - g_kzg_check_ms[1] - g_kzg_check_ms[2] - g_kzg_check_ms[3]; // the pairing checks (and the normalisations around them)
+    return rc_tail;
+}
+
+int bbgpu_kzg_check_openings(const uint64_t* commitments, const uint32_t* which, size_t num_commitments, const uint64_t* z, const uint64_t* y,
+                             const uint64_t* proofs, size_t count, const uint64_t g2_x[16], const uint64_t seed[4], int flags, bbgpu_kzg_check_report* report)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    host::KzgCheckCall K;
+    if (int rc = kzg_check_openings_call(&K, commitments, which, num_commitments, z, y, proofs, count, g2_x, flags, report)) return rc;
+    return kzg_check_run(K, g2_x, seed, flags, report);
+}
+int bbgpu_kzg_check_open_all(const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n, int batch,
+                             const uint64_t g2_x[16], const uint64_t seed[4], int flags, bbgpu_kzg_check_report* report)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    host::KzgCheckCall K;
+    if (int rc = kzg_check_open_all_call(&K, commitments, values, stride, proofs, n, batch, g2_x, flags, report)) return rc;
+    return kzg_check_run(K, g2_x, seed, flags, report);
+}
+int bbgpu_kzg_check_last_timing(double ms_out[5])
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!ms_out) return BBGPU_ERR_ARG;
+    for (int i = 0; i < 5; i++) ms_out[i] = g_kzg_check_ms[i];
     return BBGPU_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "bbgpu_internal.h"
+#include "fr_sum_device.hpp"
 #include "g1.hpp"
 #include "keccak_device.hpp"
 
@@ -379,27 +380,6 @@ template <bool MIXED> __global__ void __launch_bounds__(VT) k_verify_terms(typen
 // ---- k_verify_fold: out[k] = sum over the proofs j < m of shared[k][j], one workgroup per shared point ----------------------------------------------
 // Canonical 256-bit additions modulo r: exact, so the fixed tree below gives the value any other order would.  No floating point, no atomics.
 constexpr int FT = 256;
-__device__ __forceinline__ void fr_add_canonical(uint64_t (&a)[4], const uint64_t (&b)[4])
-{
-    uint64_t s[4], carry = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint64_t t = a[i] + b[i];
-        const uint64_t c1 = t < a[i];
-        s[i] = t + carry;
-        carry = c1 | (uint64_t)(s[i] < t);
-    }
-    uint64_t d[4], borrow = 0; // a + b < 2 r < 2^255: no carry out; subtract r once if it fits
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint64_t t = s[i] - FrP::P64[i];
-        const uint64_t b1 = s[i] < FrP::P64[i];
-        d[i] = t - borrow;
-        borrow = b1 | (uint64_t)(t < borrow);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) a[i] = borrow ? s[i] : d[i];
-}
 // the 256 partial sums of a workgroup into one, by a fixed tree; thread 0 writes it (zero for a key point at infinity: its row is a stand-in)
 __device__ __forceinline__ void fold_finish(uint64_t (&s_acc)[FT][4], const uint64_t (&acc)[4], bool skip, uint64_t* __restrict__ dst)
 {

@@ -882,6 +882,80 @@ int bbgpu_kzg_open_all_device(int setup, const uint64_t* d_coeffs, size_t stride
 int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const uint64_t* coeffs, size_t stride_elems, int batch,
                             uint64_t* proofs_out /* batch x n x 8 */);
 
+/* ---- do these openings hold?  (up to 2^20 KZG claims: the per-claim rows and scalars on the GPU, one pairing check) ------
+ * bbgpu_host_kzg_check_openings above is host only and takes 64 claims; one call of bbgpu_kzg_open_all_device writes up to 2^20 proofs, and a
+ * data-availability verifier receives thousands of (commitment, point, value, proof) claims per request.  These entries check `count` claims -- "the
+ * polynomial behind the claim's commitment takes the value y_t at z_t, with proof point pi_t" -- in one call, by the same definition:
+ *   A = sum_t rho_t C_t + sum_t (rho_t z_t) pi_t - (sum_t rho_t y_t) G,   B = sum_t rho_t pi_t,   ok = ( e(A, G2) e(-B, x G2) == 1 )
+ * rho_t = bbgpu_srs_check's multipliers Keccak-256(seed || t) with the top three bits cleared, t the claim's position in the caller's arrays, handed to
+ * the sums as they are; the seed rules are the same (NULL: 32 bytes from the operating system; THE SEED MUST NOT BE KNOWN TO WHOEVER MADE THE PROOFS; it
+ * is reported afterwards so that a finding can be replayed).  The soundness error is about 2^-253 per check.  All pointers are HOST memory; points are
+ * affine {x, y} in the reference's format, the infinity flag honoured; z / y: 4 words each, any representative below 2^256.
+ * bbgpu_kzg_check_openings has two layouts:
+ *   which == NULL   commitments holds count x 8 words, one per claim: exactly bbgpu_host_kzg_check_openings; num_commitments is not read.
+ *   which != NULL   1 <= num_commitments <= BBGPU_KZG_CHECK_MAX_COMMITMENTS shared commitments, claim t is of commitments[which[t]] (the labelling of
+ *                   bbgpu_plonk_verify_multi); the sum over the commitments becomes sum_c (sum_{t: which[t] = c} rho_t) C_c.
+ * bbgpu_kzg_check_open_all is the shared layout for what bbgpu_kzg_open_all_device writes: claim t = b n + i has commitment b, z_t = omega^i (made on
+ * the device, omega the root of the size-n domain), y_t = values[(b * stride + i) * 4] and pi_t = proofs[(b * n + i) * 8].
+ * Return codes: BBGPU_OK means the check RAN; the verdict is report.ok.  Refused before a device is bound -- BBGPU_ERR_SIZE: count outside 1 ..
+ * BBGPU_KZG_CHECK_MAX_CLAIMS, n not a power of two, batch outside 1..64, stride < n, batch x n > 2^20; BBGPU_ERR_ARG: a null pointer, num_commitments outside
+ * 1..64, a which[t] >= num_commitments, unknown flag bits, a g2_x that bbgpu_srs_check would not take.  Unlike bbgpu_host_kzg_check_openings, a finite point
+ * off the curve is a FINDING, not an argument error: bad_points counts them among commitments and proofs, first_bad names the first (a shared commitment
+ * by its own index before any claim; in the per-claim layout C_t before pi_t), ok = 0, rounds = 0 and no MSM is issued.  Points at infinity are legal and add
+ * nothing (the proof of a constant polynomial is infinity).
+ * The kernels (csrc/kzg_check.hip): k_kzg_claims takes one claim per thread, strided -- rho_t by csrc/keccak_device.hpp, pi_t (and C_t in the per-claim
+ * layout) by 16-byte loads, the curve test of k_srs_on_curve, the point as a resident row (the generator under scalar zero for infinity), the scalars rho_t
+ * for B and rho_t z_t for A by one product with rho_t read as an integer (the twin's fr_mul), the term rho_t y_t; in the open-all form z_t starts from
+ * square-and-multiply on i and advances by one product per stride.  Findings meet in the wave and in one LDS slot per wave; one thread per workgroup issues
+ * the atomics, an honest call none.  k_kzg_fold (at most 256 ranges of claims, then k_kzg_fold_finish when there is more than one range) writes -sum rho_t y_t
+ * on G and sum_{which[t] = c} rho_t on C_c for the first m claims: canonical additions modulo r in a fixed tree, no atomics, no floating point.  A and B are
+ * the existing device MSM over the rows as transient tables -- ONE table, read by A from its head and by B from the first claim on -- and the pairing
+ * is one bbgpu_host_pairing_check of two pairs.  BBGPU_KZG_CHECK_LOCATE: after a failed check the prefix length is bisected (at most ceil(log2 count) more
+ * rounds of fold, two MSMs and pairing, no new buffer): first_failing is the smallest t such that claims [0, t] fail.
+ * The entries run on context 0 under the library mutex.  One staging buffer (the caller's arrays, the rows, both scalar arrays, the terms, the partial
+ * sums, the findings: 288 bytes per claim in the open-all form, 324 in the shared layout with labels, 480 in the per-claim layout, i.e. 503 MB at 2^20
+ * claims) is kept between calls, counted in bbgpu_memory_info.staging_bytes and released by bbgpu_shutdown.  Uploads go through the library's
+ * host_to_device (pinned staging in 1 MiB chunks up to 8 MiB, the direct copy above); the shared rows are converted on the host and sent with the
+ * findings' start value in one copy.  A warm call of 256 claims passes no allocation, one read-back (the findings), four launch checks (k_kzg_claims,
+ * k_kzg_fold, one per MSM ticket) and five uploads in the per-claim layout (proofs, y, z, commitments, the head) and with labels (labels in place of the
+ * commitments), three in the open-all form (proofs, values, the head; one more per polynomial when stride > n); with a finding one launch check.
+ * After any failure no MSM ticket is outstanding.  With the same seed the report equals the host twin's field for field, a and b included.
+ * The host twins (csrc/host_kzg_check_batch.hpp) are plain loops over the host bucket method and the host pairing: no HIP call, no lock.
+ * Cost on one MI355X (tools/kzg_check_bench.py, profiles/kzg_check.txt; wall ms per call, one box, the claims of ONE polynomial): open-all form 1.69 ms at
+ * 256 claims, 1.90 at 4096, 2.66 at 2^16, 7.08 at 2^20; per-claim layout 1.82 / 2.00 / 3.51 / 10.95.  Up to 2^16 claims a call is the two MSMs plus the
+ * 1.0 ms host tail (the pairing check); at 2^20 the open-all form spends 2.3 ms on the uploads (96 MB) and k_kzg_claims, 3.5 ms in the MSMs, 1.0 ms in
+ * the tail -- the upload does not dominate.  The path there was before, bbgpu_host_kzg_check_openings over 64 claims at a time: 2.4-2.6 ms per call,
+ * timed on 8 chunks and SCALED (an extrapolation) 9.9 ms, 156 ms, 2.6 s and 41 s.  NOT measured: the kernels alone from events, the labelled layout at
+ * the large sizes, the rounds of LOCATE, several polynomials per call.  Nothing was tuned. */
+#define BBGPU_KZG_CHECK_MAX_CLAIMS      (1u << 20)
+#define BBGPU_KZG_CHECK_MAX_COMMITMENTS 64
+#define BBGPU_KZG_CHECK_LOCATE          1
+typedef struct {
+    uint64_t count;              /* claims in the call */
+    uint64_t bad_points;         /* finite points off the curve among commitments and proofs */
+    uint64_t first_bad;          /* claim index (commitment index if it is a shared commitment), UINT64_MAX if none */
+    uint32_t first_bad_is_proof; /* the first finding is claim first_bad's proof, not a commitment */
+    uint32_t g2_ok;              /* 1: a g2_x that is not usable is refused with the arguments */
+    uint32_t ok;                 /* bad_points == 0 and e(A, G2) e(-B, x G2) == 1 */
+    uint32_t rounds;             /* rounds of fold, two MSMs and pairing: 0 with findings, 1, or 1 + the bisection's */
+    int64_t first_failing;       /* with BBGPU_KZG_CHECK_LOCATE after a failed check: smallest t such that claims [0, t] fail; -1 otherwise */
+    uint64_t seed[4];            /* the seed in use */
+    uint64_t a[8], b[8];         /* A and B, affine (infinity flag honoured; infinity when no sums were taken) */
+} bbgpu_kzg_check_report;
+int bbgpu_kzg_check_openings(const uint64_t* commitments, const uint32_t* which /* NULL: one commitment per claim */, size_t num_commitments,
+                             const uint64_t* z /* count x 4 */, const uint64_t* y /* count x 4 */, const uint64_t* proofs /* count x 8 */, size_t count,
+                             const uint64_t g2_x[16], const uint64_t seed[4] /* NULL: OS randomness */, int flags, bbgpu_kzg_check_report* report);
+int bbgpu_kzg_check_open_all(const uint64_t* commitments /* batch x 8 */, const uint64_t* values /* batch x stride x 4 */, size_t stride,
+                             const uint64_t* proofs /* batch x n x 8 */, size_t n, int batch, const uint64_t g2_x[16], const uint64_t seed[4], int flags,
+                             bbgpu_kzg_check_report* report);
+int bbgpu_host_kzg_check_openings_batch(const uint64_t* commitments, const uint32_t* which, size_t num_commitments, const uint64_t* z, const uint64_t* y,
+                                        const uint64_t* proofs, size_t count, const uint64_t g2_x[16], const uint64_t seed[4], int flags,
+                                        bbgpu_kzg_check_report* report);
+int bbgpu_host_kzg_check_open_all(const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n, int batch,
+                                  const uint64_t g2_x[16], const uint64_t seed[4], int flags, bbgpu_kzg_check_report* report);
+/* wall ms of the last bbgpu_kzg_check_* call between the synchronisations it makes anyway: total, uploads and k_kzg_claims, folds, MSMs, host tail */
+int bbgpu_kzg_check_last_timing(double ms_out[5]);
+
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
  * per-proof part is what :55-355 computes -- six Keccak transcripts (challenge.hpp), the Lagrange evaluations (polynomial_arithmetic.cpp:594-626),
