@@ -424,6 +424,17 @@ static int host_stage_ensure()
         }
     return BBGPU_OK;
 }
+// `bytes` (at most HOST_CHUNK) built by fill(h) in the next pinned buffer of the ring and sent to d_dst in ONE copy; the caller holds the context's lock
+template <class Fill> static int stage_head(void* d_dst, size_t bytes, hipStream_t st, Fill fill)
+{
+    if (int rc = host_stage_ensure()) return rc;
+    const int k = (int)(ctx().h_stage_next++ % Context::HOST_RING);
+    HIPCHK(hipEventSynchronize(ctx().h_stage_free[k])); // the DMA that last read this buffer has finished (no-op before its first use)
+    fill(static_cast<uint8_t*>(ctx().h_stage[k]));
+    HIPCHK(h2d_async(d_dst, ctx().h_stage[k], bytes, st));
+    HIPCHK(hipEventRecord(ctx().h_stage_free[k], st));
+    return BBGPU_OK;
+}
 // Both directions take the current context's lock themselves -- context 0's is the library mutex (recursive: the capi entry points already hold it):
 // the resident prover's uploads (plonk.hip, which holds only its own mutex) would otherwise race with a transform or an MSM of another thread on the
 // staging buffers, their events and the single-producer copy pool.  A worker of a split MSM takes its own context's lock (the caller holds g_mu).
@@ -437,15 +448,10 @@ int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st)
         HIPCHK(h2d_async(d_dst, h_src, bytes, st));
         return BBGPU_OK;
     }
-    if (int rc = host_stage_ensure()) return rc;
     const size_t CH = ctx().host_chunk;
     for (size_t off = 0; off < bytes; off += CH) {
         const size_t len = std::min(CH, bytes - off);
-        const int k = (int)(ctx().h_stage_next++ % Context::HOST_RING);
-        HIPCHK(hipEventSynchronize(ctx().h_stage_free[k])); // the DMA that last read this buffer has finished (no-op before its first use)
-        ctx().copy_pool.copy(ctx().h_stage[k], (const char*)h_src + off, len);
-        HIPCHK(h2d_async((char*)d_dst + off, ctx().h_stage[k], len, st));
-        HIPCHK(hipEventRecord(ctx().h_stage_free[k], st));
+        if (int rc = stage_head((char*)d_dst + off, len, st, [&](uint8_t* h) { ctx().copy_pool.copy(h, (const char*)h_src + off, len); })) return rc;
     }
     return BBGPU_OK;
 }
@@ -1448,6 +1454,157 @@ void add_context_memory(const Context& C, bool primary, bbgpu_memory_info* out)
         if (C.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
 }
 
+// ---- what the asynchronous MSM entries and the pairing checks' drivers share ------------------------------------------------------------------------
+// srs_live: the handle names a live table.  ticket_srs: the library is up, and that.  begin_ticket: a free slot (slots 0 and 1
+// alternate -- the two-deep pipeline of consecutive large MSMs: measured 1.50 ms/step against 1.72 when four streams rotate, more streams than
+// hardware queues delay the next MSM's sort behind the previous one's tail -- and the others only take the overflow when both are busy, a prover
+// round's three side-by-side commitments), the caller's stream or the slot's own, and the slot's issue flags as a single-piece MSM wants them
+// (issue_ticket sets its own).  commit_ticket: the issue went through, the ticket is the slot.
+int srs_live(int srs_handle, const SrsEntry** e)
+{
+    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
+        set_error("unknown SRS handle %d", srs_handle);
+        return BBGPU_ERR_ARG;
+    }
+    *e = &ctx().srs[srs_handle];
+    return BBGPU_OK;
+}
+int ticket_srs(int srs_handle, const SrsEntry** e)
+{
+    if (int rc = ensure_init()) return rc;
+    return srs_live(srs_handle, e);
+}
+// a live table of at least n rows, for the entries that read rows [0, n) of a handle: an argument error, before a device is bound (a handle can only exist
+// once one is).  what: the operation, for the text; too_many_code: what n above the table's size is to this entry
+int srs_rows(const char* what, int srs_handle, size_t n, int too_many_code, const SrsEntry** e, bool name_handle = false)
+{
+    if (int rc = srs_live(srs_handle, e)) return rc;
+    if (n <= (*e)->n) return BBGPU_OK;
+    if (name_handle) set_error("%s of %zu rows, the table of handle %d holds %zu", what, n, srs_handle, (*e)->n);
+    else set_error("%s of %zu rows, the table holds %zu", what, n, (*e)->n);
+    return too_many_code;
+}
+int begin_ticket(void* hip_stream, int* t, hipStream_t* st)
+{
+    if ((*t = pick_slot()) < 0) return BBGPU_ERR_STATE;
+    MsmSlot& S = ctx().slot[*t];
+    *st = hip_stream ? (hipStream_t)hip_stream : S.stream;
+    S.helper = -1;
+    S.append = false;
+    S.throughput = others_pending(&S);
+    return BBGPU_OK;
+}
+int commit_ticket(int t)
+{
+    if (t < 2) ctx().next_slot = t ^ 1;
+    return t;
+}
+
+// A and B of a random-combination check: two tickets in flight, ma scalars at d_a against rows [off_a, off_a + ma) of ea and the same for B, every window of
+// each table.  On a failure none is outstanding.
+int two_msms(const SrsEntry& ea, size_t off_a, const uint64_t* d_a, size_t ma, const SrsEntry& eb, size_t off_b, const uint64_t* d_b, size_t mb, uint64_t* a12,
+             uint64_t* b12)
+{
+    int ta, tb;
+    hipStream_t sa, sb;
+    if (int rc = begin_ticket(nullptr, &ta, &sa)) return rc;
+    if (int rc = issue_ticket(ta, ea, off_a, &d_a, 1, ma, 0, entry_windows(ea, ma), sa)) return rc;
+    commit_ticket(ta);
+    int rc = begin_ticket(nullptr, &tb, &sb);
+    if (rc == BBGPU_OK && (rc = issue_ticket(tb, eb, off_b, &d_b, 1, mb, 0, entry_windows(eb, mb), sb)) == BBGPU_OK) commit_ticket(tb);
+    if (rc != BBGPU_OK) {
+        drain_tickets(&ta, 1);
+        return rc;
+    }
+    if (int rcw = bbgpu_msm_g1_wait(ta, a12)) {
+        drain_tickets(&tb, 1);
+        return rcw;
+    }
+    return bbgpu_msm_g1_wait(tb, b12);
+}
+// rows a kernel of the call wrote, as a transient table for two_msms: no window tables
+SrsEntry transient_table(uint32_t* d_rows, size_t n)
+{
+    SrsEntry e{};
+    e.n = n;
+    e.d_srs = d_rows;
+    e.live = true;
+    return e;
+}
+
+// the call's seed: the caller's, or drawn from the operating system
+int call_seed(const char* what, const uint64_t* seed, uint64_t sd[4])
+{
+    if (host::srs_check_seed(seed, sd)) return BBGPU_OK;
+    set_error("%s: the operating system gave no randomness", what);
+    return BBGPU_ERR_STATE;
+}
+
+// an affine point in memory form (Montgomery-256, any representative) as a resident row: Montgomery-261 (x 2^5), canonical
+void resident_row(const uint64_t p[8], uint64_t out[8])
+{
+    host::Fq v[2];
+    host::g1_words_canonical(p, &v[0], &v[1]);
+    for (host::Fq& c : v)
+        for (int i = 0; i < 5; i++) c = host::fq_dbl(c);
+    memcpy(out, v, 64);
+}
+
+// The curve pass of bbgpu_srs_check over rows [0, n) of a resident table, for every entry that reads one: the shared staging grown to its 64-byte head (the
+// findings, padded: what lies behind them stays 16-byte aligned) and `extra` bytes, `records` (1 or 2) findings started by ONE upload -- the second is for a
+// later kernel of the caller's, at findings + 1 --, the kernel, beside(d_extra, st) -- whatever else the caller wants on the stream before the read-back --
+// and ONE synchronisation.  generator_m261: the row first_is_generator compares row 0 with (null: the verdict is not used).
+const SrsCurveFindings NO_FINDINGS = { 0, ~0ull, 0, 0 };
+template <class Beside>
+int curve_pass(const uint32_t* d_rows, size_t n, const uint64_t* generator_m261, size_t extra, int records, Beside beside, uint64_t* bad_points,
+               uint64_t* first_bad_point, uint32_t* first_is_generator = nullptr)
+{
+    static_assert(2 * sizeof(SrsCurveFindings) <= 64, "two findings fit the head of the staging");
+    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, 64 + extra)) return rc;
+    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
+    const hipStream_t st = ctx().stream;
+    const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    const SrsCurveFindings init[2] = { NO_FINDINGS, NO_FINDINGS };
+    SrsCurveFindings got = NO_FINDINGS;
+    HIPCHK(h2d_async(d_find, init, (size_t)records * sizeof init[0], st));
+    if (int rc = srs_check_curve(d_rows, n, generator_m261 ? generator_m261 : no_generator, d_find, st)) return rc;
+    if (int rc = beside(ctx().d_srs_check + 8, st)) return rc;
+    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *bad_points = got.bad_points;
+    *first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
+    if (first_is_generator) *first_is_generator = got.first_is_generator;
+    return BBGPU_OK;
+}
+int curve_pass(const uint32_t* d_rows, size_t n, int records, uint64_t* bad_points, uint64_t* first_bad_point)
+{
+    return curve_pass(d_rows, n, nullptr, 0, records, [](uint64_t*, hipStream_t) { return (int)BBGPU_OK; }, bad_points, first_bad_point);
+}
+
+// bbgpu_plonk_verify_last_timing, bbgpu_kzg_check_last_timing: wall ms of the last call between the synchronisations it makes anyway -- [0] the call, [1] up to
+// the first synchronisation, [2] the folds, [3] the MSMs, [4] the rest: the pairing checks (and the normalisations around them)
+struct StageClock {
+    double ms[5] = { 0, 0, 0, 0, 0 }, t_begin = 0;
+    void begin()
+    {
+        for (double& v : ms) v = 0;
+        t_begin = now_ms();
+    }
+    void first_sync() { ms[1] = now_ms() - t_begin; }
+    void end()
+    {
+        ms[0] = now_ms() - t_begin;
+        ms[4] = ms[0] - ms[1] - ms[2] - ms[3];
+    }
+    int read(double ms_out[5]) const
+    {
+        if (!ms_out) return BBGPU_ERR_ARG;
+        for (int i = 0; i < 5; i++) ms_out[i] = ms[i];
+        return BBGPU_OK;
+    }
+};
+StageClock g_verify_clock, g_kzg_check_clock;
+
 } // namespace
 } // namespace bbgpu
 
@@ -2233,12 +2390,18 @@ int bbgpu_host_kzg_check_openings(const uint64_t* commitments, const uint64_t* z
         return BBGPU_ERR_ARG;
     }
     uint64_t sd[4];
-    if (!host::srs_check_seed(seed, sd)) {
-        set_error("KZG check: the operating system gave no randomness");
-        return BBGPU_ERR_STATE;
-    }
-    *ok = host::kzg_check_openings(commitments, z, y, proofs, k, g2_x, sd) ? 1 : 0;
-    return BBGPU_OK;
+    if (int rc = call_seed("KZG check", seed, sd)) return rc;
+    // the batch check's twin over a call with one commitment per claim
+    host::KzgCheckCall K;
+    K.commitments = commitments;
+    K.z = z;
+    K.y = y;
+    K.proofs = proofs;
+    K.count = k;
+    bbgpu_kzg_check_report rep;
+    const int rc = host::kzg_check_host(K, g2_x, sd, 0, &rep);
+    *ok = rep.ok ? 1 : 0;
+    return rc;
 }
 
 // io.hpp:100-135,171-180 restated: behind the manifest's num_g1_points G1 records come num_g2_points G2 records of 128 bytes (x.c0, x.c1, y.c0, y.c1 in the
@@ -2286,10 +2449,7 @@ int bbgpu_host_srs_check(const uint64_t* points_endo_table, size_t n, const uint
         return BBGPU_ERR_ARG;
     }
     uint64_t sd[4];
-    if (!host::srs_check_seed(seed, sd)) {
-        set_error("SRS check: the operating system gave no randomness");
-        return BBGPU_ERR_STATE;
-    }
+    if (int rc = call_seed("SRS check", seed, sd)) return rc;
     return host::srs_check_host(points_endo_table, n, g2_x, sd, flags, out);
 }
 
@@ -2301,67 +2461,27 @@ int bbgpu_srs_check(int srs_handle, size_t n, const uint64_t g2_x[16], const uin
         set_error("SRS check: null out, n == 0 or unknown flag bits 0x%x", flags);
         return BBGPU_ERR_ARG;
     }
-    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
-        set_error("unknown SRS handle %d", srs_handle);
-        return BBGPU_ERR_ARG;
-    }
-    if (n > ctx().srs[srs_handle].n) {
-        set_error("SRS check of %zu rows, the table holds %zu", n, ctx().srs[srs_handle].n);
-        return BBGPU_ERR_ARG;
-    }
+    const SrsEntry* ep = nullptr;
+    if (int rc = srs_rows("SRS check", srs_handle, n, BBGPU_ERR_ARG, &ep)) return rc;
     if (int rc = ensure_init()) return rc;
-    const SrsEntry& e = ctx().srs[srs_handle];
+    const SrsEntry& e = *ep;
     uint64_t sd[4];
-    if (!host::srs_check_seed(seed, sd)) {
-        set_error("SRS check: the operating system gave no randomness");
-        return BBGPU_ERR_STATE;
-    }
+    if (int rc = call_seed("SRS check", seed, sd)) return rc;
     host::srs_report_init(out, n, sd);
     out->g2_ok = host::srs_check_g2_ok(g2_x) ? 1 : 0;
     const bool want_powers = out->g2_ok && n >= 2;
-    constexpr size_t HEAD = 64; // the findings, padded: the multipliers behind them stay 16-byte aligned
-    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, HEAD + (want_powers ? (n - 1) * 32 : 0))) return rc;
-    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
-    uint64_t* d_rho = ctx().d_srs_check + HEAD / 8;
-    const hipStream_t st = ctx().stream;
-    // the generator (1, 2) as a resident row: Montgomery-261, canonical
-    uint64_t gen[8];
-    {
-        host::Fq gx = host::FQ_ONE; // 2^256 mod q
-        for (int i = 0; i < 5; i++) gx = host::fq_dbl(gx);
-        const host::Fq gy = host::fq_dbl(gx);
-        memcpy(gen, gx.d, 32);
-        memcpy(gen + 4, gy.d, 32);
-    }
-    // one pass over the rows and, beside it, the multipliers; ONE synchronisation before the verdict on the curve test is read
-    const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
-    SrsCurveFindings got = init;
-    HIPCHK(h2d_async(d_find, &init, sizeof init, st));
-    if (int rc = srs_check_curve(e.d_srs, n, gen, d_find, st)) return rc;
-    if (want_powers)
-        if (int rc = srs_check_scalars(sd, n - 1, d_rho, st)) return rc;
-    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
-    HIPCHK(hipStreamSynchronize(st));
-    out->bad_points = got.bad_points;
-    out->first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
-    out->first_is_generator = got.first_is_generator;
+    // one pass over the rows (row 0 against the generator (1, 2)) and, beside it, the multipliers; ONE synchronisation before the verdict on the curve test is read
+    uint64_t gen256[8], gen[8], *d_rho = nullptr;
+    host::g1_generator_words(gen256);
+    resident_row(gen256, gen);
+    if (int rc = curve_pass(e.d_srs, n, gen, want_powers ? (n - 1) * 32 : 0, 1, [&](uint64_t* d_extra, hipStream_t st) {
+            d_rho = d_extra;
+            return want_powers ? srs_check_scalars(sd, n - 1, d_rho, st) : (int)BBGPU_OK;
+        }, &out->bad_points, &out->first_bad_point, &out->first_is_generator))
+        return rc;
     if (!want_powers || out->bad_points) return BBGPU_OK;
-    // A and B: two tickets in flight over the SAME scalars, against points [0, m) and [1, m + 1) of the handle
-    return host::srs_check_powers(out, g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
-        const int W = entry_windows(e, m);
-        const int ta = bbgpu_msm_g1_device_async(srs_handle, 0, d_rho, m, 0, W, nullptr);
-        if (ta < 0) return ta;
-        const int tb = bbgpu_msm_g1_device_async(srs_handle, 1, d_rho, m, 0, W, nullptr);
-        if (tb < 0) {
-            drain_tickets(&ta, 1);
-            return tb;
-        }
-        if (int rc = bbgpu_msm_g1_wait(ta, a12)) {
-            drain_tickets(&tb, 1);
-            return rc;
-        }
-        return bbgpu_msm_g1_wait(tb, b12);
-    });
+    // A and B over the SAME scalars, against points [0, m) and [1, m + 1) of the handle
+    return host::srs_check_powers(out, g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) { return two_msms(e, 0, d_rho, m, e, 1, d_rho, m, a12, b12); });
 }
 
 /* ---- batched PLONK verification (host_plonk_verify.hpp, plonk_verify.hip) ---- */
@@ -2378,14 +2498,6 @@ static int verify_args(const uint64_t* proofs, size_t count, int flags, const ui
     return BBGPU_OK;
 }
 
-// the call's seed: the caller's, or drawn from the operating system
-static int verify_seed(const uint64_t* seed, uint64_t sd[4])
-{
-    if (host::srs_check_seed(seed, sd)) return BBGPU_OK;
-    set_error("PLONK verify: the operating system gave no randomness");
-    return BBGPU_ERR_STATE;
-}
-
 int bbgpu_host_plonk_verify_batch(size_t n, int widgets, const uint64_t* vk, const uint64_t g2_x[16], const uint64_t* proofs, size_t count,
                                   const uint64_t seed[4], int flags, uint32_t* status, bbgpu_plonk_verify_report* out)
 {
@@ -2397,7 +2509,7 @@ int bbgpu_host_plonk_verify_batch(size_t n, int widgets, const uint64_t* vk, con
         return rc;
     }
     uint64_t sd[4];
-    if (int rc = verify_seed(seed, sd)) return rc;
+    if (int rc = call_seed("PLONK verify", seed, sd)) return rc;
     return host::verify_host(K, proofs, count, sd, flags, status, out);
 }
 
@@ -2439,7 +2551,7 @@ int bbgpu_host_plonk_verify_multi(const bbgpu_plonk_verify_key* keys, int num_ke
         }
     }
     uint64_t sd[4];
-    if (int rc = verify_seed(seed, sd)) return rc;
+    if (int rc = call_seed("PLONK verify", seed, sd)) return rc;
     return host::verify_host_multi(K.data(), K.size(), g2_x, circuit, proofs, count, sd, flags, status, out);
 }
 
@@ -2527,31 +2639,14 @@ int bbgpu_srs_update(int srs_handle, size_t n, size_t first_power, const uint64_
     // argument errors before a device is bound: a handle can only exist once one is
     host::Fr y;
     if (int rc = srs_update_args(n, first_power, y_mont, &y)) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
-        set_error("unknown SRS handle %d", srs_handle);
-        return BBGPU_ERR_ARG;
-    }
-    if (n > ctx().srs[srs_handle].n) {
-        set_error("SRS update of %zu rows, the table holds %zu", n, ctx().srs[srs_handle].n);
-        return BBGPU_ERR_ARG;
-    }
+    const SrsEntry* ep = nullptr;
+    if (int rc = srs_rows("SRS update", srs_handle, n, BBGPU_ERR_ARG, &ep)) return rc;
     if (int rc = ensure_init()) return rc;
     bbgpu_srs_update_report rep;
     host::srs_update_report_init(&rep, n, first_power, y, g2_x);
-    const uint32_t* d_in = ctx().srs[srs_handle].d_srs; // add_srs below may move the registry: nothing of the entry is held across it
+    const uint32_t* d_in = ep->d_srs; // add_srs below may move the registry: nothing of the entry is held across it
     const hipStream_t st = ctx().stream;
-    // the curve pass of bbgpu_srs_check over the input rows (its staging, its kernel); the generator verdict is not used
-    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, 64)) return rc;
-    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
-    const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
-    SrsCurveFindings got = init;
-    HIPCHK(h2d_async(d_find, &init, sizeof init, st));
-    if (int rc = srs_check_curve(d_in, n, no_generator, d_find, st)) return rc;
-    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
-    HIPCHK(hipStreamSynchronize(st));
-    rep.bad_points = got.bad_points;
-    rep.first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
+    if (int rc = curve_pass(d_in, n, 1, &rep.bad_points, &rep.first_bad_point)) return rc;
     if (out) *out = rep;
     if (rep.bad_points) {
         set_error("SRS update: row %llu is not on the curve (%llu such rows)", (unsigned long long)rep.first_bad_point, (unsigned long long)rep.bad_points);
@@ -2611,33 +2706,17 @@ int bbgpu_srs_lagrange(int srs_handle, size_t n, uint64_t* host_endo_table_out, 
     // argument errors before a device is bound: a handle can only exist once one is
     int log2n;
     if (int rc = srs_lagrange_args(n, &log2n)) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
-        set_error("unknown SRS handle %d", srs_handle);
-        return BBGPU_ERR_ARG;
-    }
-    if (n > ctx().srs[srs_handle].n) {
-        set_error("SRS Lagrange basis of %zu rows, the table holds %zu", n, ctx().srs[srs_handle].n);
-        return BBGPU_ERR_SIZE;
-    }
+    const SrsEntry* ep = nullptr;
+    if (int rc = srs_rows("SRS Lagrange basis", srs_handle, n, BBGPU_ERR_SIZE, &ep)) return rc;
     if (int rc = ensure_init()) return rc;
     bbgpu_srs_lagrange_report rep;
     host::srs_lagrange_report_init(&rep, n);
-    const uint32_t* d_in = ctx().srs[srs_handle].d_srs; // add_srs below may move the registry: nothing of the entry is held across it
+    const uint32_t* d_in = ep->d_srs; // add_srs below may move the registry: nothing of the entry is held across it
     const hipStream_t st = ctx().stream;
-    // two findings in the staging of bbgpu_srs_check, started by one upload: [0] the curve pass over the input rows (the generator verdict is not used),
-    // [1] the output rows at infinity
-    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, 64)) return rc;
+    // two findings, started by the one upload: [0] the curve pass over the input rows, [1] the output rows at infinity
+    if (int rc = curve_pass(d_in, n, 2, &rep.bad_points, &rep.first_bad_point)) return rc;
     SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
-    static_assert(2 * sizeof(SrsCurveFindings) <= 64, "two findings fit the staging");
-    const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const SrsCurveFindings init[2] = { { 0, ~0ull, 0, 0 }, { 0, ~0ull, 0, 0 } };
-    SrsCurveFindings got = init[0], infinite = init[1];
-    HIPCHK(h2d_async(d_find, init, sizeof init, st));
-    if (int rc = srs_check_curve(d_in, n, no_generator, d_find, st)) return rc;
-    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
-    HIPCHK(hipStreamSynchronize(st));
-    rep.bad_points = got.bad_points;
-    rep.first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
+    SrsCurveFindings infinite = NO_FINDINGS;
     if (rep.bad_points) {
         if (out) *out = rep;
         return srs_lagrange_refusal(rep);
@@ -2683,10 +2762,7 @@ int bbgpu_host_srs_lagrange_check(const uint64_t* lagrange_endo_table, const uin
     int log2n;
     if (int rc = srs_lagrange_check_args(n, flags, out, &log2n)) return rc;
     uint64_t sd[4];
-    if (!host::srs_check_seed(seed, sd)) {
-        set_error("SRS Lagrange check: the operating system gave no randomness");
-        return BBGPU_ERR_STATE;
-    }
+    if (int rc = call_seed("SRS Lagrange check", seed, sd)) return rc;
     return host::srs_lagrange_check_host(lagrange_endo_table, monomial_endo_table, n, log2n, sd, flags, out);
 }
 
@@ -2696,58 +2772,28 @@ int bbgpu_srs_lagrange_check(int lagrange_handle, int monomial_handle, size_t n,
     // argument errors before a device is bound: a handle can only exist once one is
     int log2n;
     if (int rc = srs_lagrange_check_args(n, flags, out, &log2n)) return rc;
-    for (const int h : { lagrange_handle, monomial_handle }) {
-        if (h < 0 || h >= (int)ctx().srs.size() || !ctx().srs[h].live) {
-            set_error("unknown SRS handle %d", h);
-            return BBGPU_ERR_ARG;
-        }
-        if (n > ctx().srs[h].n) {
-            set_error("SRS Lagrange check of %zu rows, the table of handle %d holds %zu", n, h, ctx().srs[h].n);
-            return BBGPU_ERR_SIZE;
-        }
-    }
+    const SrsEntry *el = nullptr, *em = nullptr;
+    if (int rc = srs_rows("SRS Lagrange check", lagrange_handle, n, BBGPU_ERR_SIZE, &el, true)) return rc;
+    if (int rc = srs_rows("SRS Lagrange check", monomial_handle, n, BBGPU_ERR_SIZE, &em, true)) return rc;
     if (int rc = ensure_init()) return rc;
     uint64_t sd[4];
-    if (!host::srs_check_seed(seed, sd)) {
-        set_error("SRS Lagrange check: the operating system gave no randomness");
-        return BBGPU_ERR_STATE;
-    }
+    if (int rc = call_seed("SRS Lagrange check", seed, sd)) return rc;
     host::srs_lagrange_check_report_init(out, n, sd);
-    // the staging of bbgpu_srs_check: the findings, the n multipliers, and the copy of them that is transformed
-    constexpr size_t HEAD = 64;
-    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, HEAD + 2 * n * 32)) return rc;
-    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
-    uint64_t *d_rho = ctx().d_srs_check + HEAD / 8, *d_coef = d_rho + 4 * n;
-    const hipStream_t st = ctx().stream;
-    const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
-    SrsCurveFindings got = init;
-    HIPCHK(h2d_async(d_find, &init, sizeof init, st));
-    if (int rc = srs_check_curve(ctx().srs[lagrange_handle].d_srs, n, no_generator, d_find, st)) return rc;
-    if (int rc = srs_check_scalars(sd, n, d_rho, st)) return rc;
-    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
-    HIPCHK(hipStreamSynchronize(st));
-    out->bad_points = got.bad_points;
-    out->first_bad_point = got.bad_points ? got.first_bad_point : UINT64_MAX;
+    // behind the findings: the n multipliers, made beside the curve pass, and the copy of them that is transformed
+    uint64_t* d_rho = nullptr;
+    if (int rc = curve_pass(el->d_srs, n, nullptr, 2 * n * 32, 1, [&](uint64_t* d_extra, hipStream_t st) { return srs_check_scalars(sd, n, d_rho = d_extra, st); },
+                            &out->bad_points, &out->first_bad_point))
+        return rc;
     if (out->bad_points) return BBGPU_OK;
+    uint64_t* d_coef = d_rho + 4 * n;
+    const hipStream_t st = ctx().stream;
     // A and B: the copy is cut and transformed on the library's stream, then two tickets in flight
     return host::srs_lagrange_check_basis(out, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
         HIPCHK(hipMemcpyAsync(d_coef, d_rho, m * 32, hipMemcpyDeviceToDevice, st));
         if (m < n) HIPCHK(hipMemsetAsync(d_coef + 4 * m, 0, (n - m) * 32, st));
         if (int rc = bbgpu_ntt_device(d_coef, n, BBGPU_IFFT, nullptr, st)) return rc;
         HIPCHK(hipStreamSynchronize(st)); // the tickets run on slot streams
-        const int ta = bbgpu_msm_g1_device_async(lagrange_handle, 0, d_rho, m, 0, entry_windows(ctx().srs[lagrange_handle], m), nullptr);
-        if (ta < 0) return ta;
-        const int tb = bbgpu_msm_g1_device_async(monomial_handle, 0, d_coef, n, 0, entry_windows(ctx().srs[monomial_handle], n), nullptr);
-        if (tb < 0) {
-            drain_tickets(&ta, 1);
-            return tb;
-        }
-        if (int rc = bbgpu_msm_g1_wait(ta, a12)) {
-            drain_tickets(&tb, 1);
-            return rc;
-        }
-        return bbgpu_msm_g1_wait(tb, b12);
+        return two_msms(*el, 0, d_rho, m, *em, 0, d_coef, n, a12, b12);
     });
 }
 
@@ -2808,14 +2854,8 @@ int bbgpu_kzg_open_all_setup(int srs_handle, size_t n)
     // argument errors before a device is bound: a handle can only exist once one is
     int log2n;
     if (int rc = open_all_n("kzg_open_all_setup", n, &log2n)) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
-        set_error("unknown SRS handle %d", srs_handle);
-        return BBGPU_ERR_ARG;
-    }
-    if (n > ctx().srs[srs_handle].n) {
-        set_error("kzg_open_all_setup of %zu rows, the table holds %zu", n, ctx().srs[srs_handle].n);
-        return BBGPU_ERR_SIZE;
-    }
+    const SrsEntry* ep = nullptr;
+    if (int rc = srs_rows("kzg_open_all_setup", srs_handle, n, BBGPU_ERR_SIZE, &ep)) return rc;
     int slot = -1;
     for (int k = 0; k < BBGPU_KZG_OPEN_ALL_MAX_SETUPS && slot < 0; k++)
         if (!g_open_all[k].live) slot = k;
@@ -2824,20 +2864,13 @@ int bbgpu_kzg_open_all_setup(int srs_handle, size_t n)
         return BBGPU_ERR_STATE;
     }
     if (int rc = ensure_init()) return rc;
-    const uint32_t* d_in = ctx().srs[srs_handle].d_srs;
+    const uint32_t* d_in = ep->d_srs;
     const hipStream_t st = ctx().stream;
-    // the curve pass over the rows the string reads, [0, n - 1), in the staging of bbgpu_srs_check (the generator verdict is not used)
-    if (int rc = grow(&ctx().d_srs_check, &ctx().srs_check_cap, 64)) return rc;
-    SrsCurveFindings* d_find = reinterpret_cast<SrsCurveFindings*>(ctx().d_srs_check);
-    const uint64_t no_generator[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const SrsCurveFindings init = { 0, ~0ull, 0, 0 };
-    SrsCurveFindings got = init;
-    HIPCHK(h2d_async(d_find, &init, sizeof init, st));
-    if (int rc = srs_check_curve(d_in, n - 1, no_generator, d_find, st)) return rc;
-    HIPCHK(d2h_async(&got, d_find, sizeof got, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (got.bad_points) {
-        set_error("kzg_open_all_setup: row %llu is not on the curve (%llu such rows)", (unsigned long long)got.first_bad_point, (unsigned long long)got.bad_points);
+    // the curve pass over the rows the string reads, [0, n - 1)
+    uint64_t bad_points, first_bad_point;
+    if (int rc = curve_pass(d_in, n - 1, 1, &bad_points, &first_bad_point)) return rc;
+    if (bad_points) {
+        set_error("kzg_open_all_setup: row %llu is not on the curve (%llu such rows)", (unsigned long long)first_bad_point, (unsigned long long)bad_points);
         return BBGPU_ERR_ARG;
     }
     const Limbs9 W = host::limbs_m261(host::fr_root_of_unity(log2n + 1));
@@ -3257,21 +3290,6 @@ static int msm_g1_batch_once(bbgpu_msm_job* jobs, size_t num_jobs, bool* stale, 
     return rc;
 }
 
-// What the four asynchronous entries share.  ticket_srs: the library is up and the handle names a live table.  begin_ticket: a free slot (slots 0 and 1
-// alternate -- the two-deep pipeline of consecutive large MSMs: measured 1.50 ms/step against 1.72 when four streams rotate, more streams than
-// hardware queues delay the next MSM's sort behind the previous one's tail -- and the others only take the overflow when both are busy, a prover
-// round's three side-by-side commitments), the caller's stream or the slot's own, and the slot's issue flags as a single-piece MSM wants them
-// (issue_ticket sets its own).  commit_ticket: the issue went through, the ticket is the slot.
-static int ticket_srs(int srs_handle, const SrsEntry** e)
-{
-    if (int rc = ensure_init()) return rc;
-    if (srs_handle < 0 || srs_handle >= (int)ctx().srs.size() || !ctx().srs[srs_handle].live) {
-        set_error("unknown SRS handle %d", srs_handle);
-        return BBGPU_ERR_ARG;
-    }
-    *e = &ctx().srs[srs_handle];
-    return BBGPU_OK;
-}
 // what the two share entries check before they take a slot (kind: "row" / "bucket")
 static int share_ticket_srs(int srs_handle, size_t offset, const uint64_t* d_scalars, size_t n, const char* kind, const SrsEntry** ep)
 {
@@ -3288,22 +3306,6 @@ static int share_ticket_srs(int srs_handle, size_t offset, const uint64_t* d_sca
     }
     return BBGPU_OK;
 }
-static int begin_ticket(void* hip_stream, int* t, hipStream_t* st)
-{
-    if ((*t = pick_slot()) < 0) return BBGPU_ERR_STATE;
-    MsmSlot& S = ctx().slot[*t];
-    *st = hip_stream ? (hipStream_t)hip_stream : S.stream;
-    S.helper = -1;
-    S.append = false;
-    S.throughput = others_pending(&S);
-    return BBGPU_OK;
-}
-static int commit_ticket(int t)
-{
-    if (t < 2) ctx().next_slot = t ^ 1;
-    return t;
-}
-
 int bbgpu_msm_g1_device(int srs_handle, size_t offset, const uint64_t* d_scalars, size_t n, int window_begin, int window_end,
                         uint64_t out[12], void* hip_stream)
 {
@@ -3340,7 +3342,6 @@ struct VerifierHandle {
     uint64_t shared_rows[host::VERIFY_MAX_SHARED * 8]; // the key's points and the generator as resident rows: Montgomery-261, canonical
 };
 std::vector<VerifierHandle*> g_verifiers; // under g_mu; never shrinks: a handle is an index
-double g_verify_ms[5] = { 0, 0, 0, 0, 0 }; // bbgpu_plonk_verify_last_timing: wall ms of the last call between the synchronisations it makes anyway
 VerifierHandle* verifier_at(int v) { return v >= 0 && v < (int)g_verifiers.size() ? g_verifiers[v] : nullptr; } // null: no such handle
 } // namespace
 
@@ -3366,13 +3367,7 @@ int bbgpu_plonk_verifier_create(size_t n, int widgets, const uint64_t vk[BBGPU_P
     host::verify_shared_points(K, pts);
     for (int k = 0; k < K.num_shared(); k++) {
         if (k < K.num_vk && K.vk_inf[k]) H->rec.skip_mask |= 1u << k; // a stand-in row, scalar zero
-        for (int c = 0; c < 2; c++) { // x 2^256 -> x 2^261, canonical
-            host::Fq v;
-            memcpy(v.d, pts + 8 * k + 4 * c, 32);
-            v = host::fq_canonical(v);
-            for (int i = 0; i < 5; i++) v = host::fq_dbl(v);
-            memcpy(H->shared_rows + 8 * k + 4 * c, v.d, 32);
-        }
+        resident_row(pts + 8 * k, H->shared_rows + 8 * k);
     }
     for (size_t h = 0; h < g_verifiers.size(); h++)
         if (!g_verifiers[h]) {
@@ -3395,37 +3390,16 @@ int bbgpu_plonk_verifier_destroy(int verifier)
     return BBGPU_OK;
 }
 
-// A and B: two tickets in flight over transient tables, the first ma and mb rows and scalars of each; on a failure none is outstanding
-static int verify_two_msms(const SrsEntry& ea, const SrsEntry& eb, uint64_t* d_scal_a, uint64_t* d_scal_b, size_t ma, size_t mb, uint64_t* a12, uint64_t* b12)
-{
-    int ta, tb;
-    hipStream_t sa, sb;
-    if (int rc = begin_ticket(nullptr, &ta, &sa)) return rc;
-    if (int rc = issue_ticket(ta, ea, 0, &d_scal_a, 1, ma, 0, entry_windows(ea, ma), sa)) return rc;
-    commit_ticket(ta);
-    int rc = begin_ticket(nullptr, &tb, &sb);
-    if (rc == BBGPU_OK && (rc = issue_ticket(tb, eb, 0, &d_scal_b, 1, mb, 0, entry_windows(eb, mb), sb)) == BBGPU_OK) commit_ticket(tb);
-    if (rc != BBGPU_OK) {
-        drain_tickets(&ta, 1);
-        return rc;
-    }
-    if (int rcw = bbgpu_msm_g1_wait(ta, a12)) {
-        drain_tickets(&tb, 1);
-        return rcw;
-    }
-    return bbgpu_msm_g1_wait(tb, b12);
-}
-
 // Both entries behind their argument checks: proof j is of H[circuit[j]], every handle under H[0]'s g2_x.  A call of one circuit (G == 1: circuit[] is
 // not read) passes that circuit's record to the kernels as an argument; a call of several lays circuit[] and the records out on the device.
 static int verify_run(const VerifierHandle* const* H, size_t G, const uint32_t* circuit, const uint64_t* proofs, size_t count, const uint64_t seed[4], int flags,
                       uint32_t* status, bbgpu_plonk_verify_report* out)
 {
     if (int rc = ensure_init()) return rc;
-    const double t_begin = now_ms();
-    for (double& v : g_verify_ms) v = 0;
+    StageClock& clock = g_verify_clock;
+    clock.begin();
     uint64_t sd[4];
-    if (int rc = verify_seed(seed, sd)) return rc;
+    if (int rc = call_seed("PLONK verify", seed, sd)) return rc;
     host::verify_report_init(out, count, sd);
     const bool uniform = G == 1;
     // one staging buffer, every part a multiple of 64 bytes: the proofs | circuit[] | the records | rows of A: every circuit's shared rows, then nine
@@ -3462,12 +3436,8 @@ static int verify_run(const VerifierHandle* const* H, size_t G, const uint32_t* 
     }
     const hipStream_t st = ctx().stream;
     if (int rc = host_to_device(base, proofs, count * BBGPU_PLONK_PROOF_WORDS * 8, st)) return rc;
-    {
-        // the head, built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy
-        if (int rc = host_stage_ensure()) return rc;
-        const int kb = (int)(ctx().h_stage_next++ % Context::HOST_RING);
-        HIPCHK(hipEventSynchronize(ctx().h_stage_free[kb]));
-        uint8_t* h = static_cast<uint8_t*>(ctx().h_stage[kb]);
+    // the head, built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy
+    const int rc_head = stage_head(base + o_circuit, head_bytes, st, [&](uint8_t* h) {
         memset(h, 0, o_records - o_circuit);
         if (!uniform) memcpy(h, circuit, count * 4);
         VerifyRecord* rec = reinterpret_cast<VerifyRecord*>(h + (o_records - o_circuit));
@@ -3481,9 +3451,8 @@ static int verify_run(const VerifierHandle* const* H, size_t G, const uint32_t* 
             memcpy(rows + at * 64, H[c]->shared_rows, (size_t)H[c]->K.num_shared() * 64);
             at += (size_t)H[c]->K.num_shared();
         }
-        HIPCHK(h2d_async(base + o_circuit, h, head_bytes, st));
-        HIPCHK(hipEventRecord(ctx().h_stage_free[kb], st));
-    }
+    });
+    if (rc_head) return rc_head;
     VerifyDeviceBuffers B;
     B.proofs = reinterpret_cast<const uint64_t*>(base);
     B.rows_own = d_rows_a + T * 16;
@@ -3495,27 +3464,21 @@ static int verify_run(const VerifierHandle* const* H, size_t G, const uint32_t* 
     if (int rc = plonk_verify_terms(C, sd, count, B, st)) return rc;
     HIPCHK(d2h_async(status, d_status, count * 4, st));
     HIPCHK(hipStreamSynchronize(st));
-    g_verify_ms[1] = now_ms() - t_begin;
+    clock.first_sync();
     host::verify_count_status(out, status);
-    // A and B: two tickets in flight over transient tables (the rows the kernel wrote; no window tables), the scalars where the kernels left them
-    SrsEntry ea{}, eb{};
-    ea.n = na;
-    ea.d_srs = d_rows_a;
-    eb.n = nb;
-    eb.d_srs = d_rows_b;
-    ea.live = eb.live = true;
+    // A and B: two tickets in flight over the rows the kernel wrote, the scalars where the kernels left them
+    const SrsEntry ea = transient_table(d_rows_a, na), eb = transient_table(d_rows_b, nb);
     const int rc_tail = host::verify_tail(out, H[0]->K.g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
         const double t_fold = now_ms();
         if (int rc = plonk_verify_fold(C, d_shared, count, m, d_scal_a, st)) return rc;
         HIPCHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
         const double t_msm = now_ms();
-        g_verify_ms[2] += t_msm - t_fold;
-        if (int rc = verify_two_msms(ea, eb, d_scal_a, d_scal_b, T + host::VERIFY_OWN * m, 2 * m, a12, b12)) return rc;
-        g_verify_ms[3] += now_ms() - t_msm;
+        clock.ms[2] += t_msm - t_fold;
+        if (int rc = two_msms(ea, 0, d_scal_a, T + host::VERIFY_OWN * m, eb, 0, d_scal_b, 2 * m, a12, b12)) return rc;
+        clock.ms[3] += now_ms() - t_msm;
         return BBGPU_OK;
     });
-    g_verify_ms[0] = now_ms() - t_begin;
-    g_verify_ms[4] = g_verify_ms[0] - g_verify_ms[1] - g_verify_ms[2] - g_verify_ms[3]; // the pairing checks (and the normalisations around them)
+    clock.end();
     return rc_tail;
 }
 
@@ -3557,16 +3520,10 @@ int bbgpu_plonk_verify_multi(const int* verifiers, int num_verifiers, const uint
 int bbgpu_plonk_verify_last_timing(double ms_out[5])
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!ms_out) return BBGPU_ERR_ARG;
-    for (int i = 0; i < 5; i++) ms_out[i] = g_verify_ms[i];
-    return BBGPU_OK;
+    return g_verify_clock.read(ms_out);
 }
 
 /* ---- batched check of KZG openings (host_kzg_check_batch.hpp, kzg_check.hip) ---- */
-namespace {
-double g_kzg_check_ms[5] = { 0, 0, 0, 0, 0 }; // bbgpu_kzg_check_last_timing: wall ms of the last call between the synchronisations it makes anyway
-}
-
 static int kzg_check_refused(int rc, const char* why)
 {
     set_error("KZG check: %s", why);
@@ -3604,12 +3561,6 @@ static int kzg_check_open_all_call(host::KzgCheckCall* K, const uint64_t* commit
     if (int rc = host::kzg_check_args(*K, false, (size_t)batch, g2_x, flags, out, &why)) return kzg_check_refused(rc, why);
     return BBGPU_OK;
 }
-static int kzg_check_seed(const uint64_t* seed, uint64_t sd[4])
-{
-    if (host::srs_check_seed(seed, sd)) return BBGPU_OK;
-    set_error("KZG check: the operating system gave no randomness");
-    return BBGPU_ERR_STATE;
-}
 
 int bbgpu_host_kzg_check_openings_batch(const uint64_t* commitments, const uint32_t* which, size_t num_commitments, const uint64_t* z, const uint64_t* y,
                                         const uint64_t* proofs, size_t count, const uint64_t g2_x[16], const uint64_t seed[4], int flags,
@@ -3618,7 +3569,7 @@ int bbgpu_host_kzg_check_openings_batch(const uint64_t* commitments, const uint3
     host::KzgCheckCall K;
     if (int rc = kzg_check_openings_call(&K, commitments, which, num_commitments, z, y, proofs, count, g2_x, flags, report)) return rc;
     uint64_t sd[4];
-    if (int rc = kzg_check_seed(seed, sd)) return rc;
+    if (int rc = call_seed("KZG check", seed, sd)) return rc;
     return host::kzg_check_host(K, g2_x, sd, flags, report);
 }
 int bbgpu_host_kzg_check_open_all(const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n, int batch,
@@ -3627,7 +3578,7 @@ int bbgpu_host_kzg_check_open_all(const uint64_t* commitments, const uint64_t* v
     host::KzgCheckCall K;
     if (int rc = kzg_check_open_all_call(&K, commitments, values, stride, proofs, n, batch, g2_x, flags, report)) return rc;
     uint64_t sd[4];
-    if (int rc = kzg_check_seed(seed, sd)) return rc;
+    if (int rc = call_seed("KZG check", seed, sd)) return rc;
     return host::kzg_check_host(K, g2_x, sd, flags, report);
 }
 
@@ -3636,12 +3587,7 @@ static bool kzg_check_resident_row(const uint64_t* p, uint64_t out[8])
 {
     uint64_t pt[8];
     const bool inf = host::kzg_row(p, pt);
-    for (int c = 0; c < 2; c++) { // x 2^256 -> x 2^261
-        host::Fq v;
-        memcpy(v.d, pt + 4 * c, 32);
-        for (int i = 0; i < 5; i++) v = host::fq_dbl(v);
-        memcpy(out + 4 * c, v.d, 32);
-    }
+    resident_row(pt, out);
     return inf;
 }
 
@@ -3650,10 +3596,10 @@ static bool kzg_check_resident_row(const uint64_t* p, uint64_t out[8])
 static int kzg_check_run(const host::KzgCheckCall& K, const uint64_t g2_x[16], const uint64_t* seed, int flags, bbgpu_kzg_check_report* out)
 {
     if (int rc = ensure_init()) return rc;
-    const double t_begin = now_ms();
-    for (double& v : g_kzg_check_ms) v = 0;
+    StageClock& clock = g_kzg_check_clock;
+    clock.begin();
     uint64_t sd[4];
-    if (int rc = kzg_check_seed(seed, sd)) return rc;
+    if (int rc = call_seed("KZG check", seed, sd)) return rc;
     host::kzg_report_init(out, K.count, sd);
     const size_t count = K.count, S = K.S, H = K.head(), per = K.per(), na = H + per * count, nb = per * count;
     const bool per_claim = !K.shared();
@@ -3700,12 +3646,8 @@ static int kzg_check_run(const host::KzgCheckCall& K, const uint64_t g2_x[16], c
         if (int rc = host_to_device(base + o_which, K.which, count * 4, st)) return rc;
     uint64_t shared_bad, shared_first, skip_mask = 0;
     host::kzg_shared_findings(K, &shared_bad, &shared_first);
-    {
-        // the head, built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy: the findings' start, the shared rows, G
-        if (int rc = host_stage_ensure()) return rc;
-        const int kb = (int)(ctx().h_stage_next++ % Context::HOST_RING);
-        HIPCHK(hipEventSynchronize(ctx().h_stage_free[kb]));
-        uint8_t* h = static_cast<uint8_t*>(ctx().h_stage[kb]);
+    // the head, built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy: the findings' start, the shared rows, G
+    const int rc_head = stage_head(base + o_find, 64 + H * 64, st, [&](uint8_t* h) {
         memset(h, 0, 64);
         const KzgFindings init = { 0, ~0ull };
         memcpy(h, &init, sizeof init);
@@ -3714,9 +3656,8 @@ static int kzg_check_run(const host::KzgCheckCall& K, const uint64_t g2_x[16], c
             if (kzg_check_resident_row(K.commitments + 8 * c, rows + 8 * c)) skip_mask |= 1ull << c;
         const uint64_t inf[8] = { 0, 0, 0, 0, 0, 0, 0, 1ull << 63 };
         (void)kzg_check_resident_row(inf, rows + 8 * S); // the generator
-        HIPCHK(h2d_async(base + o_find, h, 64 + H * 64, st));
-        HIPCHK(hipEventRecord(ctx().h_stage_free[kb], st));
-    }
+    });
+    if (rc_head) return rc_head;
     Limbs9 omega{}, step{};
     if (K.open_all) {
         const host::Fr w = host::fr_root_of_unity(K.log2n);
@@ -3727,30 +3668,24 @@ static int kzg_check_run(const host::KzgCheckCall& K, const uint64_t g2_x[16], c
     KzgFindings got = { 0, ~0ull };
     HIPCHK(d2h_async(&got, B.find, sizeof got, st));
     HIPCHK(hipStreamSynchronize(st));
-    g_kzg_check_ms[1] = now_ms() - t_begin;
+    clock.first_sync();
     host::kzg_report_findings(out, shared_bad, shared_first, got.bad_points, got.first_key);
     int rc_tail = BBGPU_OK;
     if (!out->bad_points) {
         // A and B: two tickets in flight over ONE transient table (the rows written above; no window tables), A from its head, B from the first claim on
-        SrsEntry ea{}, eb{};
-        ea.n = na;
-        ea.d_srs = d_rows;
-        eb.n = nb;
-        eb.d_srs = d_rows + H * 16;
-        ea.live = eb.live = true;
+        const SrsEntry ea = transient_table(d_rows, na), eb = transient_table(d_rows + H * 16, nb);
         rc_tail = host::kzg_check_tail(out, g2_x, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
             const double t_fold = now_ms();
             if (int rc = kzg_check_fold(B, m, S, K.log2n, skip_mask, d_scal_a, st)) return rc;
             HIPCHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
             const double t_msm = now_ms();
-            g_kzg_check_ms[2] += t_msm - t_fold;
-            if (int rc = verify_two_msms(ea, eb, d_scal_a, d_scal_b, H + per * m, per * m, a12, b12)) return rc;
-            g_kzg_check_ms[3] += now_ms() - t_msm;
+            clock.ms[2] += t_msm - t_fold;
+            if (int rc = two_msms(ea, 0, d_scal_a, H + per * m, eb, 0, d_scal_b, per * m, a12, b12)) return rc;
+            clock.ms[3] += now_ms() - t_msm;
             return BBGPU_OK;
         });
     }
-    g_kzg_check_ms[0] = now_ms() - t_begin;
-    g_kzg_check_ms[4] = g_kzg_check_ms[0] - g_kzg_check_ms[1] - g_kzg_check_ms[2] - g_kzg_check_ms[3]; // the pairing checks (and the normalisations around them)
+    clock.end();
     return rc_tail;
 }
 
@@ -3775,9 +3710,7 @@ int bbgpu_kzg_check_open_all(const uint64_t* commitments, const uint64_t* values
 int bbgpu_kzg_check_last_timing(double ms_out[5])
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!ms_out) return BBGPU_ERR_ARG;
-    for (int i = 0; i < 5; i++) ms_out[i] = g_kzg_check_ms[i];
-    return BBGPU_OK;
+    return g_kzg_check_clock.read(ms_out);
 }
 
 int bbgpu_srs_has_window_tables(int srs_handle)

@@ -52,8 +52,7 @@ static inline void kzg_report_init(bbgpu_kzg_check_report* R, size_t count, cons
     R->first_bad = UINT64_MAX;
     R->first_failing = -1;
     R->g2_ok = 1; // a g2_x that is not is refused with the arguments
-    memcpy(R->seed, seed, 32);
-    R->a[7] = R->b[7] = 1ULL << 63; // no sums taken: the point at infinity
+    report_no_sums(seed, R->seed, R->a, R->b);
 }
 
 // The findings among the points.  Shared commitments come first: if one of them is off the curve it is the first finding, by its own index.  Among the
@@ -78,29 +77,20 @@ static inline void kzg_shared_findings(const KzgCheckCall& K, uint64_t* bad, uin
         if (!g1_words_acceptable(K.commitments + 8 * c) && (*bad)++ == 0) *first = c;
 }
 
-// The tail once the points are known to be good.  sums(m, a12, b12): A and B over the claims [0, m), normalised; BBGPU_OK or the entry's error.  With
-// BBGPU_KZG_CHECK_LOCATE and a failed test the prefix length is bisected as verify_tail does: prefix m passes iff every claim below m holds (up to the
-// soundness error), so the smallest failing prefix ends in the first false claim; at most ceil(log2 count) more rounds.
+// The tail once the points are known to be good, through prefix_check with the verifier's pairing.  sums(m, a12, b12): A and B over the claims [0, m).
+// With BBGPU_KZG_CHECK_LOCATE the first failing prefix ends in the first false claim.
 template <class Sums> static inline int kzg_check_tail(bbgpu_kzg_check_report* R, const uint64_t g2_x[16], int flags, Sums sums)
 {
-    uint64_t a12[12], b12[12];
-    const size_t count = (size_t)R->count;
-    if (int rc = sums(count, a12, b12)) return rc;
-    R->rounds = 1;
-    memcpy(R->a, a12, 64);
-    memcpy(R->b, b12, 64);
-    R->ok = verify_pair(a12, b12, g2_x) ? 1 : 0;
-    if (R->ok || !(flags & BBGPU_KZG_CHECK_LOCATE)) return BBGPU_OK;
-    size_t lo = 0, hi = count; // prefix lo passes (the empty one trivially), prefix hi fails
-    while (hi - lo > 1) {
-        const size_t mid = lo + (hi - lo) / 2;
-        if (int rc = sums(mid, a12, b12)) return rc;
-        R->rounds++;
-        if (verify_pair(a12, b12, g2_x)) lo = mid;
-        else hi = mid;
-    }
-    R->first_failing = (int64_t)(hi - 1);
-    return BBGPU_OK;
+    PrefixVerdict v;
+    const int rc = prefix_check((size_t)R->count, (flags & BBGPU_KZG_CHECK_LOCATE) != 0, sums,
+                                [&](const uint64_t* a12, const uint64_t* b12) { return verify_pair(a12, b12, g2_x); }, &v);
+    if (!v.rounds) return rc;
+    memcpy(R->a, v.a, 64);
+    memcpy(R->b, v.b, 64);
+    R->rounds = v.rounds;
+    R->ok = v.ok ? 1 : 0;
+    if (v.first_failing != SIZE_MAX) R->first_failing = (int64_t)v.first_failing;
+    return rc;
 }
 
 // the argument verdicts every entry gives before anything else: 0, or the code with *why set
@@ -175,11 +165,7 @@ static inline int kzg_check_host(const KzgCheckCall& K, const uint64_t g2_x[16],
     std::vector<Fr> rho(count), term(count);
     std::vector<bool> shared_inf(K.S);
     for (size_t c = 0; c < K.S; c++) shared_inf[c] = kzg_row(K.commitments + 8 * c, &pts[8 * c]);
-    {
-        const Fq gy = fq_dbl(FQ_ONE);
-        memcpy(&pts[8 * (H - 1)], FQ_ONE.d, 32);
-        memcpy(&pts[8 * (H - 1) + 4], gy.d, 32);
-    }
+    g1_generator_words(&pts[8 * (H - 1)]);
     const Fr omega = K.open_all ? fr_root_of_unity(K.log2n) : fr_one();
     fallback_parallel(count, 1024, [&](size_t lo, size_t hi) {
         Fr zt = K.open_all ? fr_pow(omega, lo & (((size_t)1 << K.log2n) - 1)) : fr_zero();

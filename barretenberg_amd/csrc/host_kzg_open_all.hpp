@@ -53,14 +53,10 @@ static inline int kzg_open_all_setup_host(const uint64_t* table, size_t n, int l
 {
     const size_t N = 2 * n;
     S.assign(N, g1_infinity());
-    const Fq three = fq_add(fq_dbl(FQ_ONE), FQ_ONE);
     for (size_t j = 0; j + 1 < n; j++) {
         Fq px, py;
-        memcpy(px.d, table + 16 * j, 32);
-        memcpy(py.d, table + 16 * j + 4, 32);
-        px = fq_canonical(px);
-        py = fq_canonical(py);
-        if (!fq_eq(fq_sqr(py), fq_add(fq_mul(fq_sqr(px), px), three))) {
+        g1_words_canonical(table + 16 * j, &px, &py);
+        if (!g1_on_curve(px, py)) {
             *bad_row = j;
             return BBGPU_ERR_ARG;
         }

@@ -47,17 +47,6 @@ static inline bool verify_widgets_ok(int w)
     return w == 0 || w == BBGPU_PLONK_WIDGET_BOOL || w == BBGPU_PLONK_WIDGET_MIMC || w == BBGPU_PLONK_WIDGET_SEQUENTIAL ||
            w == (BBGPU_PLONK_WIDGET_SEQUENTIAL | BBGPU_PLONK_WIDGET_BOOL);
 }
-// an affine point as the proof and the key hold it: the flag, or y^2 = x^3 + 3 on the residues (any representative below 2^256)
-static inline bool g1_words_on_curve(const uint64_t p[8])
-{
-    Fq x, y;
-    memcpy(x.d, p, 32);
-    memcpy(y.d, p + 4, 32);
-    x = fq_canonical(x);
-    y = fq_canonical(y);
-    const Fq three = fq_add(fq_dbl(FQ_ONE), FQ_ONE);
-    return fq_eq(fq_sqr(y), fq_add(fq_mul(fq_sqr(x), x), three));
-}
 static inline Fr fr_canonical(Fr a) // any 256-bit value: 2^256 < 6 r
 {
     for (int i = 0; i < 5; i++) fr_cond_sub_p(a);
@@ -265,49 +254,26 @@ static inline void verify_report_init(bbgpu_plonk_verify_report* R, size_t count
     R->count = count;
     R->first_bad_status = UINT64_MAX;
     R->first_bad_proof = UINT64_MAX;
-    memcpy(R->seed, seed, 32);
-    R->a[7] = R->b[7] = 1ULL << 63; // no sums taken: the point at infinity
+    report_no_sums(seed, R->seed, R->a, R->b);
 }
 
 // e(A, G2) e(-B, x G2) == 1 (verifier.cpp:360-379 with reference_string.cpp:27-28: the sum with T_LO meets G2, the negated openings meet x G2)
-static inline bool verify_pair(const uint64_t a12[12], const uint64_t b12[12], const uint64_t g2_x[16])
-{
-    uint64_t p[16], q[32];
-    memcpy(p, a12, 64);
-    memcpy(p + 8, b12, 64);
-    if (!g1_words_is_inf(b12)) {
-        Fq y;
-        memcpy(y.d, b12 + 4, 32);
-        y = fq_neg(y);
-        memcpy(p + 12, y.d, 32);
-    }
-    memcpy(q, &G2_ONE, 128);
-    memcpy(q + 16, g2_x, 128);
-    return fq12_eq(pairing_product(p, q, 2), fq12_one());
-}
+static inline bool verify_pair(const uint64_t a12[12], const uint64_t b12[12], const uint64_t g2_x[16]) { return pair_is_one(a12, b12, &G2_ONE, g2_x); }
 
-// The tail once every status is known.  sums(m, a12, b12): A and B over the proofs [0, m), normalised; BBGPU_OK or the entry's error.  The sums run over
-// the proofs with status 0 (the others contribute zeros), the verdict on the batch needs both.  With BBGPU_PLONK_VERIFY_LOCATE and a failed test the prefix
-// length is bisected: prefix m passes iff every proof below m verifies, so the smallest failing prefix ends in the first bad proof.
+// The tail once every status is known, through prefix_check.  sums(m, a12, b12): A and B over the proofs [0, m).  The sums run over the proofs with status 0
+// (the others contribute zeros), the verdict on the batch needs both.  With BBGPU_PLONK_VERIFY_LOCATE the first failing prefix ends in the first bad proof.
 template <class Sums> static inline int verify_tail(bbgpu_plonk_verify_report* R, const uint64_t g2_x[16], int flags, Sums sums)
 {
-    uint64_t a12[12], b12[12];
-    const size_t count = (size_t)R->count;
-    if (int rc = sums(count, a12, b12)) return rc;
-    memcpy(R->a, a12, 64);
-    memcpy(R->b, b12, 64);
+    PrefixVerdict v;
+    const int rc = prefix_check((size_t)R->count, (flags & BBGPU_PLONK_VERIFY_LOCATE) != 0, sums,
+                                [&](const uint64_t* a12, const uint64_t* b12) { return verify_pair(a12, b12, g2_x); }, &v);
+    if (!v.rounds) return rc;
+    memcpy(R->a, v.a, 64);
+    memcpy(R->b, v.b, 64);
     R->pairing_checked = 1;
-    R->pairing_ok = verify_pair(a12, b12, g2_x) ? 1 : 0;
-    if (R->pairing_ok || !(flags & BBGPU_PLONK_VERIFY_LOCATE)) return BBGPU_OK;
-    size_t lo = 0, hi = count; // prefix lo passes (the empty one trivially), prefix hi fails
-    while (hi - lo > 1) {
-        const size_t mid = lo + (hi - lo) / 2;
-        if (int rc = sums(mid, a12, b12)) return rc;
-        if (verify_pair(a12, b12, g2_x)) lo = mid;
-        else hi = mid;
-    }
-    R->first_bad_proof = hi - 1;
-    return BBGPU_OK;
+    R->pairing_ok = v.ok ? 1 : 0;
+    if (v.first_failing != SIZE_MAX) R->first_bad_proof = v.first_failing;
+    return rc;
 }
 
 static inline void verify_count_status(bbgpu_plonk_verify_report* R, const uint32_t* status)
@@ -319,30 +285,17 @@ static inline void verify_count_status(bbgpu_plonk_verify_report* R, const uint3
 // the key's points and the generator as the sums take them: 64 bytes each, an infinite key point replaced by the generator (its scalar is zero)
 static inline void verify_shared_points(const VerifyKey& K, uint64_t* out /* num_shared x 8 */)
 {
-    const Fq gy = fq_dbl(FQ_ONE);
     for (int k = 0; k < K.num_shared(); k++) {
-        if (k < K.num_vk && !K.vk_inf[k]) {
-            memcpy(out + 8 * k, K.vk + 8 * k, 64);
-        } else {
-            memcpy(out + 8 * k, FQ_ONE.d, 32);
-            memcpy(out + 8 * k + 4, gy.d, 32);
-        }
+        if (k < K.num_vk && !K.vk_inf[k]) memcpy(out + 8 * k, K.vk + 8 * k, 64);
+        else g1_generator_words(out + 8 * k);
     }
 }
 // a proof's point as a sum takes it: canonical coordinates; the generator where the flag is set (its scalar is zero)
 static inline void verify_own_point(const uint64_t* p, uint64_t out[8])
 {
-    if (g1_words_is_inf(p)) {
-        const Fq gy = fq_dbl(FQ_ONE);
-        memcpy(out, FQ_ONE.d, 32);
-        memcpy(out + 4, gy.d, 32);
-        return;
-    }
+    if (g1_words_is_inf(p)) return g1_generator_words(out);
     Fq x, y;
-    memcpy(x.d, p, 32);
-    memcpy(y.d, p + 4, 32);
-    x = fq_canonical(x);
-    y = fq_canonical(y);
+    g1_words_canonical(p, &x, &y);
     memcpy(out, x.d, 32);
     memcpy(out + 4, y.d, 32);
 }

@@ -73,18 +73,12 @@ static inline void g1_transform_host(std::vector<Xyzz>& v, int log2n, const Fr& 
 // bbgpu_host_srs_lagrange: rows are the even entries of a 2n-entry endo table; table_out may alias table.  n = 2^log2n.
 static inline int srs_lagrange_host(const uint64_t* table, size_t n, int log2n, uint64_t* table_out, bbgpu_srs_lagrange_report* R)
 {
-    // the curve loop of srs_check_host, into bit-reversed slots
+    // the curve test of canonical_rows (host_random_check.hpp), into bit-reversed slots
     std::vector<Xyzz> v(n);
-    const Fq three = fq_add(fq_dbl(FQ_ONE), FQ_ONE);
     for (size_t j = 0; j < n; j++) {
         Fq px, py;
-        memcpy(px.d, table + 16 * j, 32);
-        memcpy(py.d, table + 16 * j + 4, 32);
-        px = fq_canonical(px);
-        py = fq_canonical(py);
-        if (!fq_eq(fq_sqr(py), fq_add(fq_mul(fq_sqr(px), px), three))) {
-            if (R->bad_points++ == 0) R->first_bad_point = j;
-        }
+        g1_words_canonical(table + 16 * j, &px, &py);
+        if (!g1_on_curve(px, py) && R->bad_points++ == 0) R->first_bad_point = j;
         size_t i = 0;
         for (int b = 0; b < log2n; b++) i |= ((j >> b) & 1) << (log2n - 1 - b);
         v[i] = Xyzz{ px, py, FQ_ONE, FQ_ONE };

@@ -54,18 +54,11 @@ static inline void srs_update_report_init(bbgpu_srs_update_report* R, size_t n, 
 // bbgpu_host_srs_update: rows are the even entries of a 2n-entry endo table; table_out may alias table
 static inline int srs_update_host(const uint64_t* table, size_t n, size_t first_power, const Fr& y, uint64_t* table_out, bbgpu_srs_update_report* R)
 {
-    // the curve loop of srs_check_host: canonical coordinates, y^2 = x^3 + 3
+    // the curve test of canonical_rows (host_random_check.hpp): canonical coordinates, y^2 = x^3 + 3
     std::vector<Fq> rows(2 * n);
-    const Fq three = fq_add(fq_dbl(FQ_ONE), FQ_ONE);
     for (size_t i = 0; i < n; i++) {
-        Fq px, py;
-        memcpy(px.d, table + 16 * i, 32);
-        memcpy(py.d, table + 16 * i + 4, 32);
-        rows[2 * i] = px = fq_canonical(px);
-        rows[2 * i + 1] = py = fq_canonical(py);
-        if (!fq_eq(fq_sqr(py), fq_add(fq_mul(fq_sqr(px), px), three))) {
-            if (R->bad_points++ == 0) R->first_bad_point = i;
-        }
+        g1_words_canonical(table + 16 * i, &rows[2 * i], &rows[2 * i + 1]);
+        if (!g1_on_curve(rows[2 * i], rows[2 * i + 1]) && R->bad_points++ == 0) R->first_bad_point = i;
     }
     if (R->bad_points) return BBGPU_ERR_ARG;
     fallback_parallel(n, 16, [&](size_t lo, size_t hi) {
@@ -98,16 +91,7 @@ static inline int srs_update_host(const uint64_t* table, size_t n, size_t first_
 static inline bool srs_update_check(const uint64_t old_p1[8], const uint64_t new_p1[8], const uint64_t y_g2[16])
 {
     if (!srs_check_g2_ok(y_g2) || g1_words_is_inf(old_p1) || g1_words_is_inf(new_p1)) return false;
-    uint64_t p[16], q[32];
-    memcpy(p, old_p1, 64);
-    memcpy(p + 8, new_p1, 64);
-    Fq ny;
-    memcpy(ny.d, new_p1 + 4, 32);
-    ny = fq_neg(fq_canonical(ny));
-    memcpy(p + 12, ny.d, 32);
-    memcpy(q, y_g2, 128);
-    memcpy(q + 16, &G2_ONE, 128);
-    return fq12_eq(pairing_product(p, q, 2), fq12_one());
+    return pair_is_one(old_p1, new_p1, y_g2, &G2_ONE); // (new_p1's y is made canonical before it is negated)
 }
 
 // io.hpp:36-135,159-181 restated for WRITING (see bbgpu_transcript_write): the G1 records of entries 2 .. 2 (degree - 1) of the endo table, then G2 and the

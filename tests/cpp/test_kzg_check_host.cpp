@@ -1,7 +1,7 @@
 // Host twins of the batched check of KZG openings (csrc/host_kzg_check_batch.hpp: kzg_check_host behind its argument checks) under AddressSanitizer and
 // UndefinedBehaviorSanitizer.  The program makes its own string P_j = x^j G and x G2 from a secret, commits to polynomials with the host bucket
 // method, opens them with kate_opening at points on and off the domain, and holds the twins to: the verdict of the 64-claim check the library had
-// before (kzg_check_openings), the shared layout against the per-claim layout, the open-all form against explicit z = omega^i, infinities, findings,
+// before (kzg_check_openings below), the shared layout against the per-claim layout, the open-all form against explicit z = omega^i, infinities, findings,
 // and the bisection.
 // A stand-alone program with its own main; built and run by tests/test_kzg_check_host.py::test_host_twins_under_sanitizers.
 #include <cstdio>
@@ -107,6 +107,38 @@ static bbgpu_kzg_check_report run(const World& W, const Claims& C, bool shared, 
     CHECK(kzg_check_args(K, !shared, W.commitments.size(), W.g2_x, flags, &R, &why) == BBGPU_OK, "arguments: %s", why);
     CHECK(kzg_check_host(K, W.g2_x, seed, flags, &R) == BBGPU_OK, "the check ran");
     return R;
+}
+// The definition claim by claim, as the 64-claim entry computed it before it became a call of the twin: plain tables, points at infinity left out (the
+// twin gives them a zero scalar).  Kept here as the twin's independent check.
+static bool kzg_check_openings(const uint64_t* commitments, const uint64_t* z, const uint64_t* y, const uint64_t* proofs, size_t k, const uint64_t g2_x[16],
+                               const uint64_t seed[4])
+{
+    std::vector<uint64_t> pa, sa, pb, sb;
+    auto push = [](std::vector<uint64_t>& pts, std::vector<uint64_t>& sc, const uint64_t* p, const Fr& s) {
+        if (g1_words_is_inf(p)) return;
+        Fq c[2];
+        g1_words_canonical(p, &c[0], &c[1]);
+        pts.insert(pts.end(), c[0].d, c[0].d + 4);
+        pts.insert(pts.end(), c[1].d, c[1].d + 4);
+        sc.insert(sc.end(), s.d, s.d + 4);
+    };
+    Fr ysum = fr_zero();
+    for (size_t t = 0; t < k; t++) {
+        Fr rho, zt, yt;
+        srs_check_rho(seed, t, rho.d);
+        memcpy(zt.d, z + 4 * t, 32);
+        memcpy(yt.d, y + 4 * t, 32);
+        push(pa, sa, commitments + 8 * t, rho);
+        push(pa, sa, proofs + 8 * t, fr_mul(rho, zt));
+        push(pb, sb, proofs + 8 * t, rho);
+        ysum = fr_add(ysum, fr_mul(rho, yt));
+    }
+    uint64_t g[8], a12[12], b12[12];
+    g1_generator_words(g);
+    push(pa, sa, g, fr_neg(ysum));
+    g1_to_normalised(msm_pippenger(sa.data(), pa.data(), sa.size() / 4, 8), a12);
+    g1_to_normalised(msm_pippenger(sb.data(), pb.data(), sb.size() / 4, 8), b12);
+    return pair_is_one(a12, b12, &G2_ONE, g2_x);
 }
 static bool same(const bbgpu_kzg_check_report& a, const bbgpu_kzg_check_report& b)
 {
