@@ -69,6 +69,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_lagrange_opening_end", "bbgpu_fr_fold_device", "bbgpu_host_fr_fold", "bbgpu_host_kate_opening_lagrange_folded", "bbgpu_host_kzg_check_openings",
     "bbgpu_selftest_plonk_round",
     "bbgpu_kzg_open_all_setup", "bbgpu_kzg_open_all_release", "bbgpu_kzg_open_all_device", "bbgpu_host_kzg_open_all",
+    "bbgpu_kzg_open_cosets_setup", "bbgpu_kzg_open_cosets_release", "bbgpu_kzg_open_cosets_device", "bbgpu_host_kzg_open_cosets",
     "bbgpu_kzg_check_openings", "bbgpu_kzg_check_open_all", "bbgpu_host_kzg_check_openings_batch", "bbgpu_host_kzg_check_open_all",
     "bbgpu_kzg_check_last_timing",
 ]
@@ -593,6 +594,35 @@ class BbGpu:
         out = np.zeros((max(int(batch), 1), int(n), 8), dtype=np.uint64)
         self.lib.bbgpu_host_kzg_open_all.argtypes = [u64p, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p]
         self._chk(self.lib.bbgpu_host_kzg_open_all(_ptr(table), int(n), _ptr(coeffs), stride, batch, _ptr(out)))
+        return out
+
+    # ---- a polynomial opened on every coset of its domain  (bbgpu_kzg_open_cosets_* and the host twin) ----
+    def kzg_open_cosets_setup(self, handle, n, coset):
+        """bbgpu_kzg_open_cosets_setup: per residue e < coset, DFT_(2n/coset) of the reversed rows e, e + coset, .. of a resident monomial table (rows
+        [0, n - coset) are read), kept on the device -> setup handle"""
+        self.lib.bbgpu_kzg_open_cosets_setup.argtypes = [C.c_int, C.c_size_t, C.c_size_t]
+        return self._chk(self.lib.bbgpu_kzg_open_cosets_setup(int(handle), int(n), int(coset)))
+
+    def kzg_open_cosets_release(self, setup):
+        self.lib.bbgpu_kzg_open_cosets_release.argtypes = [C.c_int]
+        self._chk(self.lib.bbgpu_kzg_open_cosets_release(int(setup)))
+
+    def kzg_open_cosets_device(self, setup, d_coeffs, n, coset, batch=1, stride=None, stream=None, out=None):
+        """bbgpu_kzg_open_cosets_device: `batch` polynomials in coefficient form on the device (stride elements apart) -> (batch, n / coset, 8): the affine
+        KZG proof of polynomial b on coset k = { omega^(k + (n / coset) j) }, infinity flagged in bit 63 of y[3]"""
+        out = np.zeros((max(int(batch), 1), max(int(n) // max(int(coset), 1), 1), 8), dtype=np.uint64) if out is None else out
+        self.lib.bbgpu_kzg_open_cosets_device.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, u64p, C.c_void_p]
+        self._chk(self.lib.bbgpu_kzg_open_cosets_device(int(setup), d_coeffs, n if stride is None else stride, batch, _ptr(out), stream or 0))
+        return out
+
+    def host_kzg_open_cosets(self, table, n, coset, coeffs, batch=1, stride=None):
+        """bbgpu_host_kzg_open_cosets: the same on the host, over the even entries of a (>= 2 (n - coset), 8) endo table; coeffs (batch * stride, 4) ->
+        (batch, n / coset, 8)"""
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+        stride = coeffs.shape[0] // max(int(batch), 1) if stride is None else stride
+        out = np.zeros((max(int(batch), 1), max(int(n) // max(int(coset), 1), 1), 8), dtype=np.uint64)
+        self.lib.bbgpu_host_kzg_open_cosets.argtypes = [u64p, C.c_size_t, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p]
+        self._chk(self.lib.bbgpu_host_kzg_open_cosets(_ptr(table), int(n), int(coset), _ptr(coeffs), stride, batch, _ptr(out)))
         return out
 
     # ---- do these openings hold?  (bbgpu_kzg_check_openings, bbgpu_kzg_check_open_all and the host twins) ----

@@ -35,6 +35,7 @@
 #include "host_lagrange_open.hpp"
 #include "host_srs_lagrange_check.hpp"
 #include "host_kzg_open_all.hpp"
+#include "host_kzg_open_cosets.hpp"
 #include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
@@ -1345,6 +1346,28 @@ void open_all_release(OpenAllSetup& o)
     o = OpenAllSetup();
 }
 
+// ---- setups of bbgpu_kzg_open_cosets_* (below): S^(e) = DFT_M(s^(e)), e < l, of one (string, n, l): l x M = 2 n scratch points, kept as the open-all setups
+// are, in a pool of their own.  Context 0, under g_mu.
+struct OpenCosetsSetup {
+    bool live = false;
+    int log2n = 0, log2l = 0;
+    uint32_t* d_S = nullptr;
+    size_t bytes = 0;
+};
+OpenCosetsSetup g_open_cosets[BBGPU_KZG_OPEN_COSETS_MAX_SETUPS];
+size_t open_cosets_setup_bytes()
+{
+    size_t b = 0;
+    for (const auto& o : g_open_cosets)
+        if (o.live) b += o.bytes;
+    return b;
+}
+void open_cosets_release(OpenCosetsSetup& o)
+{
+    if (o.live && o.d_S) (void)dev_free(o.d_S);
+    o = OpenCosetsSetup();
+}
+
 // Everything the current context holds, on the thread that drives it (its device is that thread's current one).  Context 0 (primary) also owns the
 // resident prover and the transforms' tables.
 void release_context(bool primary)
@@ -1356,6 +1379,8 @@ void release_context(bool primary)
         for (auto& o : g_opening) opening_release(o);
     if (primary)
         for (auto& o : g_open_all) open_all_release(o);
+    if (primary)
+        for (auto& o : g_open_cosets) open_cosets_release(o);
     // nothing may still be reading the pinned staging buffers or a slot's workspace when they are freed: collect what is in flight
     // (an MSM a caller never waited for, a copy queued before an error return) and drain every stream first
     for (int k = 0; k < Context::NSLOT; k++)
@@ -1449,7 +1474,7 @@ void add_context_memory(const Context& C, bool primary, bbgpu_memory_info* out)
         if (sl.ws.h_out) out->pinned_host_bytes += (uint64_t)MSM_HOUT_GROUPS * 64 * 128;
     }
     out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap + C.srs_check_cap + C.verify_cap + C.kzg_check_cap;
-    if (primary) out->staging_bytes += plonk_lane_bytes() + opening_session_bytes() + open_all_setup_bytes(); // the resident prover, the opening sessions and the open-all setups live on context 0
+    if (primary) out->staging_bytes += plonk_lane_bytes() + opening_session_bytes() + open_all_setup_bytes() + open_cosets_setup_bytes(); // the resident prover, the opening sessions and the open-all and open-cosets setups live on context 0
     for (int k = 0; k < Context::HOST_RING; k++)
         if (C.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
 }
@@ -2925,6 +2950,127 @@ int bbgpu_kzg_open_all_device(int setup, const uint64_t* d_coeffs, size_t stride
         return rc;
     if (int rc = device_to_host_sync(proofs_out, t.p, (size_t)batch * n * 64, st)) return rc;
     if (ctx().timing) { // bbgpu_last_timing: index 0 the load kernel, 1 the inverse stages, 2 the gather kernel and the forward stages, 3 the finish kernel
+        ctx().last.count = 4;
+        for (int i = 0; i < 4; i++) ctx().last.ms[i] = ms4[i];
+    }
+    return BBGPU_OK;
+}
+
+/* ---- a polynomial opened on every coset of its domain: all n / l KZG cell proofs at once (host_kzg_open_cosets.hpp, kzg_open_cosets.hip) ---- */
+static int open_cosets_n(const char* what, size_t n, size_t coset, int* log2n, int* log2l)
+{
+    if (!host::kzg_open_cosets_log2(n, coset, log2n, log2l)) {
+        set_error("%s: n = %zu must be a power of two between 2 and 2^%d and the coset size (%zu) a power of two between 1 and %d, at most n / 2", what, n,
+                  host::KZG_OPEN_ALL_MAX_LOG2, coset, BBGPU_KZG_OPEN_COSETS_MAX_COSET);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
+
+int bbgpu_host_kzg_open_cosets(const uint64_t* points_endo_table, size_t n, size_t coset, const uint64_t* coeffs, size_t stride_elems, int batch,
+                               uint64_t* proofs_out)
+{
+    int log2n, log2l;
+    if (int rc = open_cosets_n("host kzg_open_cosets", n, coset, &log2n, &log2l)) return rc;
+    if (int rc = open_all_batch("host kzg_open_cosets", batch)) return rc;
+    if (!points_endo_table || !coeffs || !proofs_out) {
+        set_error("host kzg_open_cosets: null table / coeffs / proofs");
+        return BBGPU_ERR_ARG;
+    }
+    if (int rc = open_all_sizes("host kzg_open_cosets", n, stride_elems, batch)) return rc;
+    std::vector<host::Xyzz> S;
+    uint64_t bad = 0;
+    if (host::kzg_open_cosets_setup_host(points_endo_table, log2n, log2l, S, &bad)) {
+        set_error("host kzg_open_cosets: row %llu is not on the curve", (unsigned long long)bad);
+        return BBGPU_ERR_ARG;
+    }
+    host::kzg_open_cosets_proofs_host(S, log2n, log2l, coeffs, stride_elems, batch, proofs_out);
+    return BBGPU_OK;
+}
+
+int bbgpu_kzg_open_cosets_setup(int srs_handle, size_t n, size_t coset)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound: a handle can only exist once one is
+    int log2n, log2l;
+    if (int rc = open_cosets_n("kzg_open_cosets_setup", n, coset, &log2n, &log2l)) return rc;
+    const SrsEntry* ep = nullptr;
+    if (int rc = srs_rows("kzg_open_cosets_setup", srs_handle, n, BBGPU_ERR_SIZE, &ep)) return rc;
+    int slot = -1;
+    for (int k = 0; k < BBGPU_KZG_OPEN_COSETS_MAX_SETUPS && slot < 0; k++)
+        if (!g_open_cosets[k].live) slot = k;
+    if (slot < 0) {
+        set_error("kzg_open_cosets_setup: %d setups are live", BBGPU_KZG_OPEN_COSETS_MAX_SETUPS);
+        return BBGPU_ERR_STATE;
+    }
+    if (int rc = ensure_init()) return rc;
+    const uint32_t* d_in = ep->d_srs;
+    const hipStream_t st = ctx().stream;
+    // the curve pass over the rows the strings read, [0, n - l)
+    uint64_t bad_points, first_bad_point;
+    if (int rc = curve_pass(d_in, n - coset, 1, &bad_points, &first_bad_point)) return rc;
+    if (bad_points) {
+        set_error("kzg_open_cosets_setup: row %llu is not on the curve (%llu such rows)", (unsigned long long)first_bad_point, (unsigned long long)bad_points);
+        return BBGPU_ERR_ARG;
+    }
+    const Limbs9 W = host::limbs_m261(host::fr_root_of_unity(log2n - log2l + 1));
+    OpenCosetsSetup o;
+    if (int rc = kzg_open_cosets_string(d_in, log2n, log2l, W.d, &o.d_S, st)) return rc;
+    o.log2n = log2n;
+    o.log2l = log2l;
+    o.bytes = 2 * n * 128;
+    o.live = true;
+    g_open_cosets[slot] = o;
+    return slot;
+}
+
+int bbgpu_kzg_open_cosets_release(int setup)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (setup < 0 || setup >= BBGPU_KZG_OPEN_COSETS_MAX_SETUPS || !g_open_cosets[setup].live) {
+        set_error("kzg_open_cosets_release: unknown setup %d", setup);
+        return BBGPU_ERR_ARG;
+    }
+    open_cosets_release(g_open_cosets[setup]); // (dev_free waits for the device: no queued call still reads S^)
+    return BBGPU_OK;
+}
+
+int bbgpu_kzg_open_cosets_device(int setup, const uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* proofs_out, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rc = open_all_batch("kzg_open_cosets", batch)) return rc;
+    if (!d_coeffs || !proofs_out) {
+        set_error("kzg_open_cosets: null coeffs / proofs");
+        return BBGPU_ERR_ARG;
+    }
+    if (setup < 0 || setup >= BBGPU_KZG_OPEN_COSETS_MAX_SETUPS || !g_open_cosets[setup].live) {
+        set_error("kzg_open_cosets: unknown setup %d", setup);
+        return BBGPU_ERR_ARG;
+    }
+    const OpenCosetsSetup& o = g_open_cosets[setup];
+    const int log2M = o.log2n - o.log2l + 1;
+    const size_t n = (size_t)1 << o.log2n, l = (size_t)1 << o.log2l, M = (size_t)1 << log2M;
+    if (int rc = open_all_sizes("kzg_open_cosets", n, stride_elems, batch)) return rc;
+    if (int rc = ensure_init()) return rc;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    // t, then t^, then the proofs (batch x 2 n x 32 bytes hold batch x m x 64), and the M scratch points of every polynomial
+    DevBuf t, scratch;
+    HIPCHK(dev_malloc(&t.p, (size_t)batch * 2 * n * 32));
+    HIPCHK(dev_malloc(&scratch.p, (size_t)batch * M * 128));
+    if (int rc = kzg_open_cosets_t(d_coeffs, stride_elems, batch, o.log2n, o.log2l, t.as<uint64_t>(), st)) return rc;
+    // batch x l transforms of length M, side by side; the batched transform takes KZG_OPEN_ALL_MAX_BATCH of them per call
+    for (size_t done = 0, all = (size_t)batch * l; done < all; done += host::KZG_OPEN_ALL_MAX_BATCH) {
+        const int group = (int)std::min<size_t>(all - done, host::KZG_OPEN_ALL_MAX_BATCH);
+        if (int rc = bbgpu_ntt_device_batch(t.as<uint64_t>() + done * M * 4, M, M, group, BBGPU_FFT, nullptr, hip_stream)) return rc;
+    }
+    const host::Fr W = host::fr_root_of_unity(log2M);
+    const host::Fr c32 = host::fr_from_mont(host::fr_mul(host::fr_inv(host::fr_from_u64((uint64_t)M)), host::fr_from_u64(32))); // the plain integer 32 / M
+    float ms4[4] = { 0, 0, 0, 0 };
+    if (int rc = kzg_open_cosets_chain(o.d_S, t.as<uint64_t>(), scratch.as<uint32_t>(), o.log2n, o.log2l, batch, host::limbs_m256(c32).d,
+                                       host::limbs_m261(host::fr_inv(W)).d, host::limbs_m261(host::fr_root_of_unity(log2M - 1)).d, st, ctx().timing ? ms4 : nullptr))
+        return rc;
+    if (int rc = device_to_host_sync(proofs_out, t.p, (size_t)batch * (M / 2) * 64, st)) return rc;
+    if (ctx().timing) { // bbgpu_last_timing: index 0 the sum kernel, 1 the inverse stages, 2 the gather kernel and the forward stages, 3 the finish kernel
         ctx().last.count = 4;
         for (int i = 0; i < 4; i++) ctx().last.ms[i] = ms4[i];
     }

@@ -882,6 +882,76 @@ int bbgpu_kzg_open_all_device(int setup, const uint64_t* d_coeffs, size_t stride
 int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const uint64_t* coeffs, size_t stride_elems, int batch,
                             uint64_t* proofs_out /* batch x n x 8 */);
 
+/* ---- open a polynomial on every coset of its domain: all n / l KZG cell proofs at once ------
+ * A data-availability sampler does not ship one proof per point but CELLS: the l evaluations on one coset of the domain with ONE proof for all l of them
+ * (the multi-proofs of the same paper of Feist and Khovratovich).  With l = `coset` a power of two, m = n / l >= 2, omega = fr_root_of_unity(log2 n) and
+ * psi = omega^l = fr_root_of_unity(log2 m): coset k < m is { omega^(k + m j) : j < l }, its vanishing polynomial is X^l - psi^k, and
+ *   pi_k = [q_k(x)] G,  f = q_k (X^l - psi^k) + r_k,  deg r_k < l.
+ * (pi_0 .. pi_(m-1)) is the forward size-m group transform, root psi, of (h_0 .. h_(m-2), infinity) with h_u = sum_{j >= (u+1) l} c_j P_(j - (u+1) l).
+ * Split by residue e = j mod l, c^(e)_a = c_(e + l a) and P^(e)_b = P_(e + l b): h = sum_e Toeplitz(c^(e), P^(e)), each term in the layout of the block
+ * above at size m.  With M = 2 m and W = fr_root_of_unity(log2 M):
+ *   s^(e) = (P^(e)_(m-2), .., P^(e)_0, infinity x (m + 1))
+ *   t^(e) = (c^(e)_(m-1), 0 x (m + 1), c^(e)_1, .., c^(e)_(m-2))          (m = 2: (c^(e)_1, 0, 0, 0))
+ *   h = the first m entries of IDFT_M( sum_e DFT_M(s^(e)) o DFT_M(t^(e)) )
+ * The l products are summed in the Fourier domain, so ONE inverse transform of length M and ONE forward transform of length m serve all l residues: the
+ * 2 n ladder products of bbgpu_kzg_open_all_device, and l times fewer group butterflies.  A caller of that entry gets the same proofs by folding l single
+ * proofs per cell on the host: pi_k = sum_j [omega^(k + m j) / (l psi^k)] pi(omega^(k + m j)); the tests tie the two entries by that identity.  The
+ * reference has no counterpart.
+ * bbgpu_kzg_open_cosets_setup computes S^(e) = DFT_M(s^(e)) for every e < l ONCE from rows [0, n - l) of a resident monomial table and keeps the l x M =
+ * 2 n rows on the device (the footprint of an open-all setup; counted in bbgpu_memory_info.staging_bytes, released by bbgpu_kzg_open_cosets_release or
+ * bbgpu_shutdown).
+ *   n, coset     powers of two, 1 <= coset <= BBGPU_KZG_OPEN_COSETS_MAX_COSET, n / coset >= 2, n <= 2^21 and no larger than the table: otherwise
+ *                BBGPU_ERR_SIZE.  An unknown SRS handle: BBGPU_ERR_ARG.  BBGPU_ERR_STATE: BBGPU_KZG_OPEN_COSETS_MAX_SETUPS setups are live -- a pool of its
+ *                own: the setups of bbgpu_kzg_open_all_setup neither count against it nor are refused by it.  All are refused before a device is bound.
+ *   coset == 1   is accepted on purpose: the construction is then that of the block above, and the proofs are those of bbgpu_kzg_open_all_device bit for bit.
+ *   bad rows     the curve pass runs over the rows the setup reads, [0, n - l), as in bbgpu_kzg_open_all_setup: a bad row is BBGPU_ERR_ARG,
+ *                bbgpu_last_error() naming the first one, and no setup is made.  Rows from n - l on are not read.
+ *   infinity     a row of S^(e) at infinity is legal and kept exactly.
+ * Returns the setup handle (>= 0).  A warm setup passes one allocation (S^), one upload and one read-back (the curve findings) and two launch checks (the
+ * curve pass; the chain of k_open_cosets_string and the log2 M stage kernels).  The SRS handle is not read after the setup returns and may be released.
+ * bbgpu_kzg_open_cosets_device opens `batch` polynomials in coefficient form over one setup: coefficient j of polynomial b at
+ * d_coeffs[(b * stride_elems + j) * 4] (device memory, read only; the reference's memory format, any representative), and writes batch x m affine points to
+ * HOST memory: proofs_out[(b * m + k) * 8] is pi_k of polynomial b in the reference's format (Montgomery-256, canonical; infinity: bit 63 of y[3], every
+ * other word zero).  Infinity is an ordinary result: a polynomial of degree below l has every proof at infinity.  The order is natural in k: the values of
+ * cell k are entries k, k + m, k + 2 m, .. of the caller's own size-n bbgpu_ntt_device of the coefficients; this entry does not return them.
+ *   BBGPU_ERR_SIZE   batch outside 1..64, stride_elems < n, batch x 2 n > 2^22
+ *   BBGPU_ERR_ARG    an unknown setup, a null pointer                                    -- all refused before a device is bound
+ * The kernels (csrc/kzg_open_cosets.hip; every one takes the polynomial from blockIdx.y): k_open_cosets_t writes the batch x l x M scalars of t^(e) and
+ * bbgpu_ntt_device_batch transforms them, 64 transforms per call; k_open_cosets_sum puts sum_e (M^-1 t^^(e)_j) * S^(e)_j, j = bitrev(i), into slot i --
+ * one wave takes 64 / l frequencies, lane (f, e) brings its own scalar to a plain integer and runs one ladder (csrc/g1_ladder.hpp) over its own projective
+ * base, and the l results of a frequency are added in a log2 l-level tree across lanes, the points crossing in 8 KiB of LDS; the additions are complete
+ * (either side at infinity, equal points, opposite points); log2 M launches of k_lagrange_stage (csrc/g1_stage.hpp) with root W^-1; k_open_cosets_gather,
+ * log2 m launches of k_lagrange_stage with root psi and k_open_cosets_finish are the open-all kernels at sizes m and M.
+ * The entry runs on context 0 under the library mutex; every allocation, copy and launch check passes the fault-injection funnels.  A warm call at
+ * (n, l) = (256, 4): two allocations (t, which later holds the proofs, and the scratch points), no upload, one read-back (the proofs: one staging chunk),
+ * and three launch checks (k_open_cosets_t; the transform's single pass at this size -- one more for every further group of 64 transforms; the chain from
+ * the sum kernel to the finish kernel).  After a failure nothing the call allocated is live and the setup stays usable.  With bbgpu_set_timing(1),
+ * bbgpu_last_timing() index 0 is the device time of k_open_cosets_sum, 1 that of the inverse stages, 2 that of the gather kernel and the forward stages,
+ * 3 that of k_open_cosets_finish.
+ * Cost on one MI355X (tools/kzg_open_cosets_bench.py, profiles/kzg_open_cosets.txt): wall ms per call, proofs read back to the host, one box, against
+ * bbgpu_kzg_open_all_device at the same n and batch TIMED IN THE SAME PROCESS in alternating pairs -- the n single proofs only: the l-point host fold per
+ * cell that the old path needs on top was not timed and is not charged.  l = 64: n = 2^12 13.2 ms against 24.5 (batch 16: 15.9 against 26.9); n = 2^16
+ * 21.7 against 35.0 (batch 16: 50.1 against 351); n = 2^20 57.4 against 436 (medians of 3 pairs; the others of 9).  l = 4 at n = 2^16: 30.1 against 34.9
+ * (batch 16: 104 against 349).  The new entry is lower in every cell, by more than the full range (max - min) of either leg's timings.  Device times at
+ * (2^20, 64): the sum kernel 31.4 ms, the inverse stages 14.0 ms, the gather and the forward stages 13.1 ms, the finish kernel 0.16 ms -- the 2 n ladders
+ * are now more than half the call, and a call of few polynomials stays bound from below by the latency of its log2 M + log2 m stage launches (about 0.9
+ * ms each: 12.0 of 13.2 ms at (2^12, 64)).  k_open_cosets_sum against k_open_all_load over the same 2 n ladders, both from bbgpu_set_timing in that process:
+ * +0.96 ms on 30.4 at 2^20 and +0.15 on 2.2 at 2^16 -- the tree and the LDS crossing cost 3 to 7 percent of the kernel.  231 VGPRs against 229, no scratch
+ * memory in either (the compiler's resource remarks, at the head of the profile).  The setup, with its release: 6.5 ms, 10.8 ms and 187 ms at l = 64, 14.7
+ * ms at (2^16, 4).  Nothing was tuned after these measurements.
+ * The host twin (csrc/host_kzg_open_cosets.hpp) runs the same construction over host_g1.hpp with a plain double-and-add per product and a plain
+ * left-to-right sum over e.  The results are unique affine points, so device and twin agree bit for bit.  It takes the even entries of a caller's endo
+ * table (n - l rows are read), makes no HIP call, takes no lock and is re-entrant; its errors are those of the two device entries (a row off the curve:
+ * BBGPU_ERR_ARG naming it). */
+#define BBGPU_KZG_OPEN_COSETS_MAX_SETUPS 16
+#define BBGPU_KZG_OPEN_COSETS_MAX_COSET 64
+int bbgpu_kzg_open_cosets_setup(int srs_handle, size_t n, size_t coset); /* setup handle >= 0 */
+int bbgpu_kzg_open_cosets_release(int setup);
+int bbgpu_kzg_open_cosets_device(int setup, const uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* proofs_out /* host, batch x (n / coset) x 8 */,
+                                 void* hip_stream);
+int bbgpu_host_kzg_open_cosets(const uint64_t* points_endo_table, size_t n, size_t coset, const uint64_t* coeffs, size_t stride_elems, int batch,
+                               uint64_t* proofs_out /* batch x (n / coset) x 8 */);
+
 /* ---- do these openings hold?  (up to 2^20 KZG claims: the per-claim rows and scalars on the GPU, one pairing check) ------
  * bbgpu_host_kzg_check_openings above is host only and takes 64 claims; one call of bbgpu_kzg_open_all_device writes up to 2^20 proofs, and a
  * data-availability verifier receives thousands of (commitment, point, value, proof) claims per request.  These entries check `count` claims -- "the
