@@ -71,7 +71,8 @@ C_ABI_SYMBOLS = [
     "bbgpu_kzg_open_all_setup", "bbgpu_kzg_open_all_release", "bbgpu_kzg_open_all_device", "bbgpu_host_kzg_open_all",
     "bbgpu_kzg_open_cosets_setup", "bbgpu_kzg_open_cosets_release", "bbgpu_kzg_open_cosets_device", "bbgpu_host_kzg_open_cosets",
     "bbgpu_kzg_check_openings", "bbgpu_kzg_check_open_all", "bbgpu_host_kzg_check_openings_batch", "bbgpu_host_kzg_check_open_all",
-    "bbgpu_kzg_check_last_timing",
+    "bbgpu_kzg_check_last_timing", "bbgpu_kzg_check_cells", "bbgpu_kzg_check_open_cosets", "bbgpu_host_kzg_check_cells",
+    "bbgpu_host_kzg_check_open_cosets", "bbgpu_host_kzg_cells_key_check",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -677,11 +678,82 @@ class BbGpu:
         return self._kzg_check_open_all(self.lib.bbgpu_host_kzg_check_open_all, commitments, values, proofs, n, g2_x, batch, stride, seed, locate)
 
     def kzg_check_last_timing(self):
-        """bbgpu_kzg_check_last_timing: wall ms of the last kzg_check_openings or kzg_check_open_all by stage"""
+        """bbgpu_kzg_check_last_timing: wall ms of the last kzg_check_openings, kzg_check_open_all, kzg_check_cells or kzg_check_open_cosets by stage
+        (claims_ms: the uploads and the per-claim kernel, for cells the per-cell and the coefficient kernel)"""
         buf = (C.c_double * 5)()
         self.lib.bbgpu_kzg_check_last_timing.argtypes = [C.POINTER(C.c_double)]
         self._chk(self.lib.bbgpu_kzg_check_last_timing(buf))
         return dict(zip(("total_ms", "claims_ms", "fold_ms", "msm_ms", "host_tail_ms"), buf))
+
+    # ---- do these cell proofs hold?  (bbgpu_kzg_check_cells, bbgpu_kzg_check_open_cosets, the host twins and the key check) ----
+    def _kzg_check_cells(self, fn, commitments, which, cell, values, proofs, n, coset, g1_head, g2_xl, seed, locate, flags):
+        cs = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
+        ps = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8)
+        vs = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        head = np.ascontiguousarray(g1_head, dtype=np.uint64).reshape(-1, 8)
+        labels, cells = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1), np.ascontiguousarray(cell, dtype=np.uint32).reshape(-1)
+        count = ps.shape[0]
+        if labels.shape[0] != count or cells.shape[0] != count or (1 <= int(coset) <= 64 and (vs.shape[0] != count * int(coset) or head.shape[0] < int(coset))):
+            raise ValueError("kzg_check_cells: %d proofs, %d labels, %d cell indices, %d values, %d head rows at coset %d" %
+                             (count, labels.shape[0], cells.shape[0], vs.shape[0], head.shape[0], coset))
+        g2, sd, g2p, sdp, fl = self._srs_check_args(g2_xl, seed, locate)
+        rep = KzgCheckReport()
+        u32p = C.POINTER(C.c_uint32)
+        fn.argtypes = [u64p, C.c_size_t, u32p, u32p, u64p, u64p, C.c_size_t, C.c_size_t, C.c_size_t, u64p, u64p, u64p, C.c_int, C.POINTER(KzgCheckReport)]
+        self._chk(fn(_ptr(cs), cs.shape[0], labels.ctypes.data_as(u32p), cells.ctypes.data_as(u32p), _ptr(vs), _ptr(ps), count, int(n), int(coset), _ptr(head),
+                     g2p, sdp, fl if flags is None else int(flags), C.byref(rep)))
+        return rep.as_dict()
+
+    def _kzg_check_open_cosets(self, fn, commitments, values, proofs, n, coset, g1_head, g2_xl, batch, stride, seed, locate, flags):
+        cs = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
+        ps = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8)
+        vs = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        head = np.ascontiguousarray(g1_head, dtype=np.uint64).reshape(-1, 8)
+        batch = cs.shape[0] if batch is None else int(batch)
+        stride = int(n) if stride is None else int(stride)
+        if 1 <= batch <= 64 and 1 <= int(coset) <= 64 and int(n) >= 1 and (cs.shape[0] < batch or ps.shape[0] < batch * (int(n) // int(coset)) or
+                                                                            vs.shape[0] < (batch - 1) * stride + int(n) or head.shape[0] < int(coset)):
+            raise ValueError("kzg_check_open_cosets: batch %d of n = %d, coset %d at stride %d over %d commitments, %d values, %d proofs, %d head rows" %
+                             (batch, n, coset, stride, cs.shape[0], vs.shape[0], ps.shape[0], head.shape[0]))
+        g2, sd, g2p, sdp, fl = self._srs_check_args(g2_xl, seed, locate)
+        rep = KzgCheckReport()
+        fn.argtypes = [u64p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, u64p, u64p, C.c_int, C.POINTER(KzgCheckReport)]
+        self._chk(fn(_ptr(cs), _ptr(vs), stride, _ptr(ps), int(n), int(coset), batch, _ptr(head), g2p, sdp, fl if flags is None else int(flags), C.byref(rep)))
+        return rep.as_dict()
+
+    def kzg_check_cells(self, commitments, which, cell, values, proofs, n, coset, g1_head, g2_xl, seed=None, locate=False, flags=None):
+        """bbgpu_kzg_check_cells: `count` cell proofs checked on the GPU by two MSMs and ONE pairing product.  Cell t is cell cell[t] (< n / coset) of
+        commitments[which[t]] (at most 64 of them); values (count * coset, 4): f(omega^(k + (n / coset) j)), j < coset, per cell; proofs (count, 8);
+        g1_head (coset, 8): the first rows of the monomial string; g2_xl: [x^coset] G2.  seed None: drawn from the operating system (whoever made the
+        proofs must not know it).  Returns the report as a dict (ok, bad_points, first_bad, first_failing, rounds, seed, a, b ...)."""
+        return self._kzg_check_cells(self.lib.bbgpu_kzg_check_cells, commitments, which, cell, values, proofs, n, coset, g1_head, g2_xl, seed, locate, flags)
+
+    def host_kzg_check_cells(self, commitments, which, cell, values, proofs, n, coset, g1_head, g2_xl, seed=None, locate=False, flags=None):
+        """bbgpu_host_kzg_check_cells: the same definition on the host; no GPU needed"""
+        return self._kzg_check_cells(self.lib.bbgpu_host_kzg_check_cells, commitments, which, cell, values, proofs, n, coset, g1_head, g2_xl, seed, locate,
+                                     flags)
+
+    def kzg_check_open_cosets(self, commitments, values, proofs, n, coset, g1_head, g2_xl, batch=None, stride=None, seed=None, locate=False, flags=None):
+        """bbgpu_kzg_check_open_cosets: what kzg_open_cosets_device writes, checked in one call: commitments (batch, 8), values (batch * stride, 4) the
+        size-n transforms (ntt_device), proofs (batch, n / coset, 8).  Returns the report as a dict; its count is in cells."""
+        return self._kzg_check_open_cosets(self.lib.bbgpu_kzg_check_open_cosets, commitments, values, proofs, n, coset, g1_head, g2_xl, batch, stride, seed,
+                                           locate, flags)
+
+    def host_kzg_check_open_cosets(self, commitments, values, proofs, n, coset, g1_head, g2_xl, batch=None, stride=None, seed=None, locate=False, flags=None):
+        """bbgpu_host_kzg_check_open_cosets: the same definition on the host; no GPU needed"""
+        return self._kzg_check_open_cosets(self.lib.bbgpu_host_kzg_check_open_cosets, commitments, values, proofs, n, coset, g1_head, g2_xl, batch, stride,
+                                           seed, locate, flags)
+
+    def host_kzg_cells_key_check(self, g1_head, coset, g2_x, g2_xl):
+        """bbgpu_host_kzg_cells_key_check: is g2_xl = [x^coset] G2 for the x of g1_head (coset, 8) and g2_x?  One pairing product; host only -> bool"""
+        head = np.ascontiguousarray(g1_head, dtype=np.uint64).reshape(-1, 8)
+        if 1 <= int(coset) <= 64 and head.shape[0] < int(coset):
+            raise ValueError("host_kzg_cells_key_check: %d head rows at coset %d" % (head.shape[0], coset))
+        a, b = np.ascontiguousarray(g2_x, dtype=np.uint64).reshape(16), np.ascontiguousarray(g2_xl, dtype=np.uint64).reshape(16)
+        ok = C.c_int(0)
+        self.lib.bbgpu_host_kzg_cells_key_check.argtypes = [u64p, C.c_size_t, u64p, u64p, C.POINTER(C.c_int)]
+        self._chk(self.lib.bbgpu_host_kzg_cells_key_check(_ptr(head), int(coset), _ptr(a), _ptr(b), C.byref(ok)))
+        return bool(ok.value)
 
     # ---- is this table the Lagrange form of that string?  (bbgpu_srs_lagrange_check and its host twin) ----
     def srs_lagrange_check(self, lagrange_handle, monomial_handle, n, seed=None, locate=False):

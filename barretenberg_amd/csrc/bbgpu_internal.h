@@ -199,6 +199,28 @@ int kzg_check_claims(const KzgCheckBuffers& B, const uint64_t seed[4], size_t co
                      const uint32_t step_m261[9], hipStream_t st);
 int kzg_check_fold(const KzgCheckBuffers& B, size_t m, size_t S, int log2n, uint64_t skip_mask, uint64_t* d_out, hipStream_t st); // the first m claims
 
+// kzg_check_cells.hip: the device parts of a check of KZG cell proofs (bbgpu_kzg_check_cells, bbgpu_kzg_check_open_cosets) that are not an MSM.
+// l = 2^log2l values per cell, m = 2^(log2n - log2l) cells per polynomial.  Labelled form: which / cell given, the values of cell t at values[t l ..].
+// Open-cosets form (which == cell == null): cell t = b m + k, its values at values[b n + k + m j], j < l.
+struct KzgCellsBuffers {
+    const uint64_t *proofs, *values; // the caller's arrays on the device: count x 8 words; count x l x 4 words, or batch x n x 4
+    const uint32_t *which, *cell;    // count labels and cell indices (labelled form)
+    uint32_t* rows;                  // the cells' rows pi_t: 64 bytes each, Montgomery-261, canonical
+    uint64_t *scal_a, *scal_b;       // the scalars of A and of B on those rows: rho_t psi^(k_t), rho_t
+    uint64_t *term_rho, *term;       // count x 4 words: rho_t; count x l x 4 words: T_{t,i} = rho_t a_{t,i}
+    uint64_t* partial;               // (S + l) x KZG_FOLD_MAX_RANGES x 4 words
+    const uint32_t* roots;           // KZG_CELLS_MAX_COSET x 9 limbs: zeta^(-e), Montgomery-261 (the first l are read)
+    KzgFindings* find;
+};
+constexpr int KZG_CELLS_MAX_COSET = 64;
+constexpr uint32_t KZG_CELLS_COEF_MAX_BLOCKS = 1024; // workgroups of the coefficient kernel; the rest by its stride
+int kzg_cells_claims(const KzgCellsBuffers& B, const uint64_t seed[4], size_t count, int log2n, int log2l, const uint32_t psi_m261[9], hipStream_t st);
+// omega_inv: omega^-1; into: 2^5 / l -- what takes a value from memory form to Montgomery-261 and divides by l in one product
+int kzg_cells_coefficients(const KzgCellsBuffers& B, size_t count, int log2n, int log2l, const uint32_t omega_inv_m261[9], const uint32_t into_m261[9],
+                           hipStream_t st, float* ms = nullptr);
+// the scalars of the head of A over the cells [0, cells): d_out[c] for the S shared commitments, d_out[S + i] = -s_i on P_i
+int kzg_cells_fold(const KzgCellsBuffers& B, size_t cells, size_t S, int log2n, int log2l, uint64_t skip_mask, uint64_t* d_out, hipStream_t st);
+
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);
 int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_t st, bool* touched = nullptr); // *touched: h_dst may have been written (even on failure)

@@ -1026,6 +1026,80 @@ int bbgpu_host_kzg_check_open_all(const uint64_t* commitments, const uint64_t* v
 /* wall ms of the last bbgpu_kzg_check_* call between the synchronisations it makes anyway: total, uploads and k_kzg_claims, folds, MSMs, host tail */
 int bbgpu_kzg_check_last_timing(double ms_out[5]);
 
+/* ---- do these CELL proofs hold?  (a batch of cells of bbgpu_kzg_open_cosets_device: the interpolation polynomials on the GPU, one pairing check) ------
+ * bbgpu_kzg_open_cosets_device writes the n / l cell proofs a data-availability sampler ships; the entries above take single-point claims only.  These
+ * check `count` cells.  Notation: l = coset, m = n / l, omega = fr_root_of_unity(log2 n), psi = omega^l, zeta = omega^m.  Cell k < m of the polynomial f
+ * holds v_j = f(omega^(k + m j)), j < l in natural order -- the entries k, k + m, k + 2 m, .. of the caller's size-n bbgpu_ntt_device, as the open-cosets
+ * block says -- and its proof pi_k has f = q_k (X^l - psi^k) + r_k, where r_k = sum_i a_{k,i} X^i is the interpolation polynomial of the cell:
+ *   a_{k,i} = omega^(-k i) l^-1 sum_j v_j zeta^(-i j)                    (a size-l inverse transform, then a twist)
+ * For cells t < count, each (commitment label c_t, cell index k_t, l values, pi_t), rho_t the multipliers of bbgpu_srs_check by the cell's position:
+ *   s_i = sum_t rho_t a_{t,i}                                                                   (i < l)
+ *   A   = sum_c (sum_{t: c_t = c} rho_t) C_c - sum_{i < l} s_i P_i + sum_t (rho_t psi^(k_t)) pi_t,     B = sum_t rho_t pi_t
+ *   ok  = ( e(A, G2) e(-B, [x^l] G2) == 1 )
+ * g1_head holds P_0 .. P_(l-1), the first l rows of the monomial string (affine, the reference's format).  g2_xl = [x^l] G2 IS A VERIFIER-KEY ITEM THE
+ * CALLER SUPPLIES: a transcript that carries only x G2 CANNOT verify cells for l > 1 (x^l G2 does not follow from x G2 without the secret).
+ * bbgpu_host_kzg_cells_key_check says whether a g2_xl belongs to a head and an x G2: g2_xl on the twist, finite, of order r, and
+ * e(P_(l-1), g2_x) e(-G, g2_xl) == 1 -- one bbgpu_host_pairing_check of two pairs; host only, no lock, re-entrant; at l = 1 it says whether g2_xl == g2_x as
+ * points.  A head row, g2_x or g2_xl it cannot use gives *ok = 0; BBGPU_ERR_SIZE: coset not a power of two in 1..64, BBGPU_ERR_ARG: a null pointer.
+ * At l = 1 with P_0 = G and g2_xl = g2_x, A and B are exactly those of bbgpu_kzg_check_open_all, and so is the report.
+ * bbgpu_kzg_check_cells is the labelled form: cell t is cell cell[t] of commitments[which[t]], its l values at values[(t l + j) * 4]; the same (label,
+ * cell) twice is legal.  bbgpu_kzg_check_open_cosets is exactly what bbgpu_kzg_open_cosets_device writes: cell t = b m + k has label b and cell k, pi_t =
+ * proofs[(b m + k) * 8], and its values are gathered ON THE DEVICE from the transform at values[b * stride * 4], m elements apart (no host transpose).
+ * The report is bbgpu_kzg_check_report with `count` in cells; flags, seed rules, the soundness error and the meaning of BBGPU_OK are those of
+ * bbgpu_kzg_check_openings.  Values: any representative below 2^256.  Points at infinity are legal: a polynomial of degree below l has every proof at
+ * infinity, A and B are then both infinity and ok = 1; a commitment at infinity is the zero polynomial.
+ * Refused before a device is bound -- BBGPU_ERR_SIZE: coset not a power of two in 1 .. BBGPU_KZG_OPEN_COSETS_MAX_COSET, n not a power of two, n / coset < 2,
+ * n > 2^21, count outside 1 .. 2^20, count x coset > 2^20, batch outside 1..64, stride < n (batch x n > 2^20 is count x coset > 2^20); BBGPU_ERR_ARG: a null
+ * pointer, num_commitments outside 1..64, a which[t] >= num_commitments or a cell[t] >= n / coset, unknown flag bits, a g2_xl that bbgpu_srs_check would not
+ * take, a g1_head row at infinity or off the curve (it is a key, not a claim; bbgpu_last_error() names the first such row).  A commitment or a proof that
+ * is finite and off the curve is a FINDING as in the entries above: bad_points, first_bad (a commitment by its own index before any cell),
+ * first_bad_is_proof, ok = 0, rounds = 0, no MSM.  BBGPU_KZG_CHECK_LOCATE: first_failing is the smallest t such that cells [0, t] fail.
+ * The kernels (csrc/kzg_check_cells.hip).  k_kzg_cells takes one cell per thread, strided, as k_kzg_claims takes a claim: rho_t (kept in memory for the
+ * two kernels below), the curve test of pi_t and its resident row, rho_t psi^(k_t) for A (psi^k by square-and-multiply over log2 m bits) and rho_t for B;
+ * findings meet on chip, an honest call issues no atomic.  k_kzg_cell_coefficients gives a cell to l NEIGHBOURING LANES -- a wave takes 64 / l cells, a
+ * workgroup 256 / l, strided over at most 1024 workgroups; lanes of a cell past the end compute on zeros, so every lane reaches every barrier and
+ * exchange.  Each lane loads one value by two 16-byte loads (open-cosets form: the workgroup loads transposed, neighbouring threads neighbouring cells,
+ * 256 / l x 32 bytes in a row, and hands the words over through 8 KiB of LDS), brings it into the field and divides by l in one product, runs the log2 l
+ * decimation-in-frequency stages across lanes -- the partner's nine limbs by __shfl_xor, ONE product per lane and stage, roots from a table of l <= 64
+ * entries that arrives with the head --, applies the twist omega^(-k i) (square-and-multiply over the log2 n bits of k i mod n) and rho_t read as an
+ * integer, and writes the canonical term T_{t,i} = rho_t a_{t,i}, which the fold and LOCATE read again: 2 log2 n + log2 l + 3 field products per value, 60
+ * (labelled) / 65 (open-cosets) VGPRs, no scratch.  k_kzg_cells_fold (at most 256 ranges of cells x (S + l) slots, then k_kzg_cells_fold_finish when there is
+ * more than one range) writes sum_{c_t = c} rho_t on C_c and r - s_i on P_i (zero stays zero) for the first m cells: canonical additions in a fixed tree, no
+ * atomics, no floating point.  The rows are ONE transient table -- the S commitments, P_0 .. P_(l-1), then pi_t -- read by A from its head and by B from
+ * the first cell on, so a prefix of the cells is a prefix of both sums.  All values are exact residues written canonically: with the same seed the
+ * report equals the host twin's field for field, a and b included.
+ * The entries run on context 0 under the library mutex and use the staging buffer of the entries above (224 + 64 l bytes per cell, 8 more with labels:
+ * 71 MB at 2^20 values in cells of 64), kept between calls and counted in staging_bytes.  The head -- the roots, the findings' start value, the shared rows,
+ * P_0 .. P_(l-1) -- is converted on the host and sent in one copy.  A warm call of 256 cells at l = 4 passes no allocation, one read-back (the findings),
+ * five launch checks (k_kzg_cells, k_kzg_cell_coefficients, k_kzg_cells_fold, one per MSM ticket) and five uploads in the labelled form (proofs, values,
+ * labels, cell indices, the head), three in the open-cosets form (proofs, values, the head; one more per polynomial when stride > n); with a finding two
+ * launch checks (no fold, no ticket).  After any failure no MSM ticket is outstanding.  bbgpu_kzg_check_last_timing reports these entries too: index 1 is
+ * the uploads and the two cell kernels.  With bbgpu_set_timing, bbgpu_last_timing gives the coefficient kernel alone (index 0, device events).
+ * The host twins (csrc/host_kzg_check_cells.hpp) are plain loops -- a size-l transform per cell over host_fr.hpp, the host bucket method, the host
+ * pairing: no HIP call, no lock.
+ * Cost on one MI355X (tools/kzg_check_cells_bench.py, profiles/kzg_check_cells.txt; wall ms per call, one box, open-cosets form, medians of 9):
+ * (n, l, batch) = (2^12, 64, 1) 1.74, (2^16, 64, 1) 1.95, (2^16, 64, 16) 3.02, (2^16, 4, 1) 2.20, (2^20, 64, 1) 3.09.  At 2^20 values the uploads (32 MB) and
+ * the two cell kernels are 1.05-1.10 ms, the fold 0.03, the two MSMs over 16384 rows 0.69, the host tail (the pairing) 1.01.  k_kzg_cell_coefficients alone
+ * from events: 0.297 ms at (2^16, 64, 16) and 0.352 ms at (2^20, 64, 1), beside 0.287 and 0.343 ms for the product count at the 150 Gmul/s of
+ * fe_mont_gfx950.h.  Against bbgpu_kzg_check_open_all over the SAME 2^20 values at (n, batch) = (2^16, 16), alternating pairs in one process: 3.07 ms
+ * against 7.15, beyond the full range of either leg (0.14).  NOT measured: the rounds of LOCATE, the labelled form at large sizes.  Nothing was tuned. */
+int bbgpu_kzg_check_cells(const uint64_t* commitments /* num_commitments x 8 */, size_t num_commitments, const uint32_t* which /* count */,
+                          const uint32_t* cell /* count, each < n / coset */, const uint64_t* values /* count x coset x 4 */,
+                          const uint64_t* proofs /* count x 8 */, size_t count, size_t n, size_t coset, const uint64_t* g1_head /* coset x 8 */,
+                          const uint64_t g2_xl[16], const uint64_t seed[4] /* NULL: OS randomness */, int flags, bbgpu_kzg_check_report* report);
+int bbgpu_kzg_check_open_cosets(const uint64_t* commitments /* batch x 8 */, const uint64_t* values /* batch x stride x 4: the size-n transforms */,
+                                size_t stride, const uint64_t* proofs /* batch x (n / coset) x 8 */, size_t n, size_t coset, int batch,
+                                const uint64_t* g1_head /* coset x 8 */, const uint64_t g2_xl[16], const uint64_t seed[4], int flags,
+                                bbgpu_kzg_check_report* report);
+int bbgpu_host_kzg_check_cells(const uint64_t* commitments, size_t num_commitments, const uint32_t* which, const uint32_t* cell, const uint64_t* values,
+                               const uint64_t* proofs, size_t count, size_t n, size_t coset, const uint64_t* g1_head, const uint64_t g2_xl[16],
+                               const uint64_t seed[4], int flags, bbgpu_kzg_check_report* report);
+int bbgpu_host_kzg_check_open_cosets(const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n, size_t coset,
+                                     int batch, const uint64_t* g1_head, const uint64_t g2_xl[16], const uint64_t seed[4], int flags,
+                                     bbgpu_kzg_check_report* report);
+/* *ok = 1 when g2_xl is [x^coset] G2 for the x of g1_head and g2_x; host only, no lock, re-entrant */
+int bbgpu_host_kzg_cells_key_check(const uint64_t* g1_head /* coset x 8 */, size_t coset, const uint64_t g2_x[16], const uint64_t g2_xl[16], int* ok);
+
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
  * per-proof part is what :55-355 computes -- six Keccak transcripts (challenge.hpp), the Lagrange evaluations (polynomial_arithmetic.cpp:594-626),
