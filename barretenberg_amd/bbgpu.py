@@ -72,7 +72,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_kzg_open_cosets_setup", "bbgpu_kzg_open_cosets_release", "bbgpu_kzg_open_cosets_device", "bbgpu_host_kzg_open_cosets",
     "bbgpu_kzg_check_openings", "bbgpu_kzg_check_open_all", "bbgpu_host_kzg_check_openings_batch", "bbgpu_host_kzg_check_open_all",
     "bbgpu_kzg_check_last_timing", "bbgpu_kzg_check_cells", "bbgpu_kzg_check_open_cosets", "bbgpu_host_kzg_check_cells",
-    "bbgpu_host_kzg_check_open_cosets", "bbgpu_host_kzg_cells_key_check",
+    "bbgpu_host_kzg_check_open_cosets", "bbgpu_host_kzg_cells_key_check", "bbgpu_kzg_recover_cells", "bbgpu_host_kzg_recover_cells",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -185,6 +185,14 @@ class KzgCheckReport(C.Structure):
         d = {k: int(getattr(self, k)) for k, t in self._fields_ if t in (C.c_uint64, C.c_uint32, C.c_int64)}
         d.update(seed=[int(v) for v in self.seed], a=[int(v) for v in self.a], b=[int(v) for v in self.b])
         return d
+
+
+class KzgRecoverReport(C.Structure):
+    """bbgpu_kzg_recover_report (include/bbgpu.h)"""
+    _fields_ = [("consistent", C.c_uint32), ("first_bad_poly", C.c_uint32), ("first_bad_coeff", C.c_uint64), ("missing", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class PlonkVerifyKey(C.Structure):
@@ -625,6 +633,47 @@ class BbGpu:
         self.lib.bbgpu_host_kzg_open_cosets.argtypes = [u64p, C.c_size_t, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p]
         self._chk(self.lib.bbgpu_host_kzg_open_cosets(_ptr(table), int(n), int(coset), _ptr(coeffs), stride, batch, _ptr(out)))
         return out
+
+    # ---- polynomials recovered from a subset of their cells  (bbgpu_kzg_recover_cells and the host twin) ----
+    RECOVER_TILE = 256  # KZG_RECOVER_TILE (csrc/bbgpu_internal.h): roots of missing cells per LDS tile of k_recover_vanish
+
+    @staticmethod
+    def _kzg_recover_args(cell, values, coset, batch):
+        cell = np.ascontiguousarray(cell, dtype=np.uint32).reshape(-1)
+        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        if values.shape[0] < max(int(batch), 1) * cell.shape[0] * max(int(coset), 1):  # the library would read past the end
+            raise ValueError("kzg_recover_cells: %d values for batch %d of %d cells of %d" % (values.shape[0], batch, cell.shape[0], coset))
+        return cell, values, cell.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def kzg_recover_cells(self, cell, values, n, coset, degree_bound, d_coeffs_out, batch=1, stride=None, want_values=True, stream=None, out=None):
+        """bbgpu_kzg_recover_cells: `batch` polynomials of degree < degree_bound from the same listed cells (cell: distinct indices below n / coset, any
+        order; values (batch, count, coset, 4): polynomial b, listed cell t, point j, on the host) -> coefficients [0, n) of polynomial b at element b *
+        stride of the device buffer d_coeffs_out, what kzg_open_cosets_device takes.  Returns ((batch, n, 4) the size-n transforms -- `out` when given --,
+        or None without want_values; the report as a dict)."""
+        cell, values, cp = self._kzg_recover_args(cell, values, coset, batch)
+        if want_values and out is None:
+            out = np.zeros((max(int(batch), 1), max(int(n), 1), 4), dtype=np.uint64)
+        out = out if want_values else None
+        rep = KzgRecoverReport()
+        self.lib.bbgpu_kzg_recover_cells.argtypes = [C.POINTER(C.c_uint32), C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
+                                                     C.c_size_t, u64p, C.POINTER(KzgRecoverReport), C.c_void_p]
+        self._chk(self.lib.bbgpu_kzg_recover_cells(cp, cell.shape[0], _ptr(values), int(n), int(coset), int(degree_bound), int(batch), d_coeffs_out,
+                                                   int(n) if stride is None else int(stride), _ptr(out) if want_values else None, C.byref(rep), stream or 0))
+        return out, rep.as_dict()
+
+    def host_kzg_recover_cells(self, cell, values, n, coset, degree_bound, batch=1, stride=None, want_values=True, out=None):
+        """bbgpu_host_kzg_recover_cells: the same on the host -> ((batch * stride, 4) coefficients -- `out` when given, whose elements [n, stride) of every
+        polynomial stay as they are --, the transforms or None, the report as a dict)"""
+        cell, values, cp = self._kzg_recover_args(cell, values, coset, batch)
+        stride = int(n) if stride is None else int(stride)
+        coeffs = np.zeros((max(int(batch), 1) * max(stride, 1), 4), dtype=np.uint64) if out is None else out
+        vals = np.zeros((max(int(batch), 1), max(int(n), 1), 4), dtype=np.uint64) if want_values else None
+        rep = KzgRecoverReport()
+        self.lib.bbgpu_host_kzg_recover_cells.argtypes = [C.POINTER(C.c_uint32), C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, u64p,
+                                                          C.c_size_t, u64p, C.POINTER(KzgRecoverReport)]
+        self._chk(self.lib.bbgpu_host_kzg_recover_cells(cp, cell.shape[0], _ptr(values), int(n), int(coset), int(degree_bound), int(batch), _ptr(coeffs), stride,
+                                                        _ptr(vals) if want_values else None, C.byref(rep)))
+        return coeffs, vals, rep.as_dict()
 
     # ---- do these openings hold?  (bbgpu_kzg_check_openings, bbgpu_kzg_check_open_all and the host twins) ----
     def _kzg_check_openings(self, fn, commitments, z, y, proofs, g2_x, which, seed, locate):

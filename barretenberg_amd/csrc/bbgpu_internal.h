@@ -221,6 +221,23 @@ int kzg_cells_coefficients(const KzgCellsBuffers& B, size_t count, int log2n, in
 // the scalars of the head of A over the cells [0, cells): d_out[c] for the S shared commitments, d_out[S + i] = -s_i on P_i
 int kzg_cells_fold(const KzgCellsBuffers& B, size_t cells, size_t S, int log2n, int log2l, uint64_t skip_mask, uint64_t* d_out, hipStream_t st);
 
+// kzg_recover_cells.hip: the device parts of bbgpu_kzg_recover_cells that are neither a transform nor the batch inversion.  l = 2^log2l values per cell,
+// m = 2^(log2n - log2l) cells per polynomial, mu of them missing (d_missing: ascending; may be null when mu == 0).
+struct RecoverFindings {
+    unsigned long long first_bad, first_bug; // the smallest nonzero coefficient in [d, count l) and in [count l, n) (the caller starts both at ~0)
+};
+constexpr int KZG_RECOVER_TILE = 256;                  // roots of missing cells per LDS tile of k_recover_vanish
+constexpr uint32_t KZG_RECOVER_TAIL_MAX_BLOCKS = 1024; // workgroups per polynomial of the tail kernel; the rest by its stride
+int kzg_recover_group_log2(int log2m); // log2 of the lanes that share one a in k_recover_vanish
+// d_z[a] = z_a as a Montgomery-261 multiplier, d_zc[a] = z'_a x 2^-5 in the memory format (its inverse there is the multiplier 1 / z'_a): m x 4 words each
+// d_roots: 9 x mu words of workspace for psi^k, k missing
+int kzg_recover_vanish(const uint32_t* d_missing, size_t mu, int log2n, int log2l, uint32_t* d_roots, uint64_t* d_z, uint64_t* d_zc, hipStream_t st);
+int kzg_recover_scatter(const uint64_t* d_values, const uint32_t* d_cell, size_t count, const uint32_t* d_missing, const uint64_t* d_z, int log2n, int log2l,
+                        int batch, uint64_t* d_out, size_t stride_elems, hipStream_t st);
+int kzg_recover_divide(uint64_t* d_q, size_t stride_elems, int batch, const uint64_t* d_inv, int log2n, int log2l, hipStream_t st);
+int kzg_recover_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* d_copy, int log2n, size_t degree_bound, size_t present, RecoverFindings* d_find,
+                     hipStream_t st);
+
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);
 int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_t st, bool* touched = nullptr); // *touched: h_dst may have been written (even on failure)

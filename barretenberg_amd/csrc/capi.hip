@@ -37,6 +37,7 @@
 #include "host_srs_lagrange_check.hpp"
 #include "host_kzg_open_all.hpp"
 #include "host_kzg_open_cosets.hpp"
+#include "host_kzg_recover_cells.hpp"
 #include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
@@ -4044,6 +4045,105 @@ int bbgpu_kzg_check_last_timing(double ms_out[5])
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     return g_kzg_check_clock.read(ms_out);
+}
+
+/* ---- polynomials recovered from a subset of their cells (host_kzg_recover_cells.hpp, kzg_recover_cells.hip) ---- */
+int bbgpu_host_kzg_recover_cells(const uint32_t* cell, size_t count, const uint64_t* values, size_t n, size_t coset, size_t degree_bound, int batch,
+                                 uint64_t* coeffs_out, size_t stride_elems, uint64_t* values_out, bbgpu_kzg_recover_report* report)
+{
+    host::KzgRecoverShape S;
+    char why[320];
+    int rc = host::kzg_recover_verdict("host kzg_recover_cells", cell, count, values, n, coset, degree_bound, batch, coeffs_out, stride_elems, report, &S, why,
+                                       sizeof why);
+    if (rc == BBGPU_OK) rc = host::kzg_recover_cells_host(S, cell, count, values, degree_bound, batch, coeffs_out, stride_elems, values_out, report, why, sizeof why);
+    if (rc) set_error("%s", why);
+    return rc;
+}
+
+int bbgpu_kzg_recover_cells(const uint32_t* cell, size_t count, const uint64_t* values, size_t n, size_t coset, size_t degree_bound, int batch,
+                            uint64_t* d_coeffs_out, size_t stride_elems, uint64_t* values_out, bbgpu_kzg_recover_report* report, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    host::KzgRecoverShape S;
+    char why[320];
+    if (int rc = host::kzg_recover_verdict("kzg_recover_cells", cell, count, values, n, coset, degree_bound, batch, d_coeffs_out, stride_elems, report, &S, why,
+                                           sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (int rc = ensure_init()) return rc;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const size_t m = S.m, mu = S.mu, present = count * coset;
+    struct Events { // the stage boundaries of bbgpu_last_timing, only made when timing is on
+        hipEvent_t e[8] = {};
+        ~Events()
+        {
+            for (hipEvent_t v : e)
+                if (v) (void)hipEventDestroy(v);
+        }
+    } ev;
+    const bool timed = ctx().timing != 0;
+    if (timed)
+        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
+    auto mark = [&](int k) -> int {
+        if (timed) HIPCHK(hipEventRecord(ev.e[k], st));
+        return BBGPU_OK;
+    };
+    // the cell list and the missing cells in one array | z, z' and the roots of the missing cells | the values | the findings | the copy the forward
+    // transform works in
+    DevBuf lists, z, vals, find, copy;
+    HIPCHK(dev_malloc(&lists.p, m * 4));
+    HIPCHK(dev_malloc(&z.p, 2 * m * 32 + mu * sizeof(Limbs9)));
+    HIPCHK(dev_malloc(&vals.p, (size_t)batch * present * 32));
+    HIPCHK(dev_malloc(&find.p, (size_t)batch * sizeof(RecoverFindings)));
+    if (values_out) HIPCHK(dev_malloc(&copy.p, (size_t)batch * n * 32));
+    uint32_t *d_cell = lists.as<uint32_t>(), *d_missing = d_cell + count;
+    uint64_t *d_z = z.as<uint64_t>(), *d_zc = d_z + 4 * m;
+    uint32_t* d_roots = reinterpret_cast<uint32_t*>(d_zc + 4 * m);
+    std::vector<uint32_t> both(cell, cell + count);
+    both.insert(both.end(), S.missing.begin(), S.missing.end());
+    std::vector<RecoverFindings> found((size_t)batch, RecoverFindings{ ~0ull, ~0ull });
+    if (int rc = host_to_device(d_cell, both.data(), m * 4, st)) return rc;
+    if (int rc = host_to_device(find.p, found.data(), found.size() * sizeof(RecoverFindings), st)) return rc;
+    if (int rc = host_to_device(vals.p, values, (size_t)batch * present * 32, st)) return rc;
+    if (int rc = mark(0)) return rc;
+    if (int rc = kzg_recover_vanish(d_missing, mu, S.log2n, S.log2l, d_roots, d_z, d_zc, st)) return rc;
+    if (int rc = mark(1)) return rc;
+    if (int rc = bbgpu_fr_batch_invert_device(d_zc, m, hip_stream)) return rc; // z' is never zero: g^n != 1
+    if (int rc = mark(2)) return rc;
+    if (int rc = kzg_recover_scatter(vals.as<uint64_t>(), d_cell, count, d_missing, d_z, S.log2n, S.log2l, batch, d_coeffs_out, stride_elems, st)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_IFFT, nullptr, hip_stream)) return rc;
+    if (int rc = mark(3)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_FFT, nullptr, hip_stream)) return rc;
+    if (int rc = kzg_recover_divide(d_coeffs_out, stride_elems, batch, d_zc, S.log2n, S.log2l, st)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_IFFT, nullptr, hip_stream)) return rc;
+    if (int rc = kzg_recover_tail(d_coeffs_out, stride_elems, batch, copy.as<uint64_t>(), S.log2n, degree_bound, present, find.as<RecoverFindings>(), st)) return rc;
+    if (int rc = mark(4)) return rc;
+    if (values_out) {
+        if (int rc = bbgpu_ntt_device_batch(copy.as<uint64_t>(), n, n, batch, BBGPU_FFT, nullptr, hip_stream)) return rc;
+        if (int rc = mark(5)) return rc;
+    }
+    if (int rc = device_to_host_sync(found.data(), find.p, found.size() * sizeof(RecoverFindings), st)) return rc;
+    std::vector<uint64_t> first_bad((size_t)batch), first_bug((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        first_bad[(size_t)b] = found[(size_t)b].first_bad;
+        first_bug[(size_t)b] = found[(size_t)b].first_bug;
+    }
+    if (int rc = host::kzg_recover_report("kzg_recover_cells", first_bad.data(), first_bug.data(), batch, mu, report, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (values_out)
+        if (int rc = device_to_host_sync(values_out, copy.p, (size_t)batch * n * 32, st)) return rc;
+    if (timed) { // bbgpu_last_timing: index 0 k_recover_vanish, 1 scatter and IFFT, 2 coset FFT, divide, coset IFFT and tail, 3 the forward transform (if asked for)
+        ctx().last.count = values_out ? 4 : 3;
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[0], ev.e[0], ev.e[1]));
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[1], ev.e[2], ev.e[3]));
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[2], ev.e[3], ev.e[4]));
+        if (values_out) HIPCHK(hipEventElapsedTime(&ctx().last.ms[3], ev.e[4], ev.e[5]));
+    }
+    return BBGPU_OK;
 }
 
 int bbgpu_srs_has_window_tables(int srs_handle)

@@ -1100,6 +1100,78 @@ int bbgpu_host_kzg_check_open_cosets(const uint64_t* commitments, const uint64_t
 /* *ok = 1 when g2_xl is [x^coset] G2 for the x of g1_head and g2_x; host only, no lock, re-entrant */
 int bbgpu_host_kzg_cells_key_check(const uint64_t* g1_head /* coset x 8 */, size_t coset, const uint64_t g2_x[16], const uint64_t g2_xl[16], int* ok);
 
+/* ---- recover polynomials from a subset of their cells  (the vanishing polynomial of the missing cells on the GPU, three transforms, a verdict) ------
+ * bbgpu_kzg_open_cosets_device makes the n / l cell proofs of a polynomial and bbgpu_kzg_check_cells / bbgpu_kzg_check_open_cosets check them.  A node that
+ * samples cells holds SOME cells of each polynomial, usually the same columns of many rows, and must rebuild the polynomials: the missing cells, and then
+ * their proofs through the producer.  bbgpu_kzg_recover_cells does the first on the device and leaves the coefficients where the producer reads them.  The
+ * reference has no counterpart.  Notation as in the two blocks above: l = coset, m = n / l, omega = the n-th root of the transforms, psi = omega^l, g the
+ * coset generator of BBGPU_COSET_FFT; cell k < m holds f(omega^(k + m j)), j < l, and vanishes under X^l - psi^k.
+ * Given the degree bound d (deg f < d <= n) and `count` distinct cells with count * l >= d, the same for all `batch` polynomials -- the column-custody case,
+ * which makes the vanishing polynomial a once-per-call cost; different sets are one call each -- let K be the mu = m - count missing cells and
+ *   Z(X) = prod_{k in K} (X^l - psi^k),   z_a = prod_{k in K} (psi^a - psi^k) = Z(omega^i),   z'_a = prod_{k in K} (g^l psi^a - psi^k) = Z(g omega^i),   a = i mod m.
+ * z_a is zero exactly on the missing cells, z'_a never (g^n != 1), and Z never exists in coefficient form.  Per polynomial:
+ *   E_i = v_i z_(i mod m) on the present cells, 0 on the missing ones      the values of f Z on the whole domain, deg f Z < n
+ *   P = IFFT(E);   Q = COSET_FFT(P);   Q_i *= 1 / z'_(i mod m);   D = COSET_IFFT(Q) = f                one batch inversion of m values per call
+ * D always has degree < count * l.  The cells are values of ONE polynomial of degree < d if and only if coefficients [d, count * l) of D are all zero: an
+ * exact statement, not a probabilistic one -- one altered value among redundant cells always shows.  With count * l == d there is no redundancy: ANY values
+ * are the values of a polynomial of degree < d, the report says consistent = 1 and cannot say otherwise.  An inconsistent polynomial is still written (D as
+ * computed) with consistent = 0 and the return value stays BBGPU_OK: a finding, not an error, as in the check entries.
+ *   values        HOST, batch x count x coset x 4 words: polynomial b, listed cell t, point j; any representative below 2^256 in the reference's memory format
+ *   d_coeffs_out  DEVICE, polynomial b at element b * stride_elems: coefficients [0, n) canonical Montgomery, elements [n, stride_elems) untouched -- exactly
+ *                 what bbgpu_kzg_open_cosets_device and bbgpu_ntt_device take
+ *   values_out    HOST or NULL: batch x n x 4, V = FFT(D), all n values, cell k at entries k, k + m, .. as everywhere else -- what bbgpu_kzg_check_open_cosets takes
+ *   hip_stream    NULL = the legacy default stream; the call returns after its last copy has finished
+ * Refused before a device is bound, outputs untouched -- BBGPU_ERR_SIZE: n or coset not a power of two, coset outside 1..64, n / coset < 2, n > 2^21,
+ * n / coset > BBGPU_KZG_RECOVER_MAX_CELLS = 2^16, degree_bound outside 1..n, count * coset < degree_bound (too few cells), count > n / coset, batch outside
+ * 1..64, stride_elems < n, batch * n > 2^22; BBGPU_ERR_ARG: a null pointer (values_out may be NULL), a cell index >= n / coset, the same cell listed twice --
+ * bbgpu_last_error() names the first offender.  BBGPU_ERR_HIP with a text of its own: a nonzero coefficient in [count * l, n), which no input can cause.
+ * Scope: m <= 2^16 because the vanishing values cost mu x m pairs (at most 2^15 x 2^16); a subproduct tree for larger m -- small l at large n -- is a later
+ * change.  Proofs are the caller's next call: bbgpu_kzg_open_cosets_device on d_coeffs_out.
+ * The kernels (csrc/kzg_recover_cells.hip; the last three take the polynomial from blockIdx.y): k_recover_roots writes psi^k for the missing cells once;
+ * k_recover_vanish, the compute-bound part, gives G = min(64, 2^18 / m) neighbouring lanes to every a, walks K in LDS tiles of 256 roots with two
+ * accumulators per lane (one subtraction and one product each per pair, sharing the staged root) and multiplies the G partial products in a tree across
+ * lanes by __shfl_xor; bbgpu_fr_batch_invert_device's path inverts the m values z'; k_recover_scatter writes every slot of E once (values read in a row,
+ * written m elements apart; no transpose through LDS: one pass of 64 bytes per element beside three transforms); k_recover_divide; k_recover_tail
+ * canonicalises and finds the smallest nonzero index in [d, count * l) and in [count * l, n) per polynomial by a min-reduction on chip -- an honest call
+ * issues no atomic.  The transforms are bbgpu_ntt_device_batch's, in place in d_coeffs_out at stride_elems; values_out costs a fourth on a copy.
+ * Resources (hipcc -Rpass-analysis=kernel-resource-usage): k_recover_vanish 76 VGPRs, 9216 bytes of LDS, 6 waves per SIMD; k_recover_roots 41, k_recover_scatter
+ * 32, k_recover_divide 32, k_recover_tail 41 VGPRs; no scratch and no spill in any.
+ * It runs on context 0 under the library mutex.  A warm call at (256, 4) with values_out passes five allocations (the cell lists; z, z' and the roots; the
+ * values; the findings; the copy for the forward transform -- four without values_out), three uploads (the lists, the findings' start, the values), two
+ * read-backs (the findings, the transforms -- one without) and eleven launch checks (roots + vanish; the inversion's two scans and its product; scatter; four
+ * transforms; divide; tail); every site failed once through bbgpu_fault_inject returns BBGPU_ERR_HIP, leaves nothing the call allocated live, and the next
+ * call is bit-exact (tests/test_gpu_kzg_recover_cells.py).  With bbgpu_set_timing(1), bbgpu_last_timing() index 0 is the device time of k_recover_roots and
+ * k_recover_vanish, 1 that of scatter and IFFT, 2 that of coset FFT, divide, coset IFFT and tail, 3 that of the forward transform (only with values_out).
+ * Cost on one MI355X (tools/kzg_recover_cells_bench.py, profiles/kzg_recover_cells.txt): wall ms per call with values_out read back into a buffer the caller
+ * keeps, one box, medians of 9 alternating pairs beside the same four bbgpu_ntt_device_batch calls alone (no copy), every other cell missing / one cell
+ * missing, degree bound n / 2: (n, l, batch) = (8192, 64, 1) 0.42 / 0.42 against 0.14; (8192, 64, 64) 1.53 / 1.50 against 0.27; (2^16, 64, 16) 1.98 / 2.28
+ * against 0.40; (2^20, 64, 1) 3.99 / 2.41 against 0.47; (2^20, 64, 4) 8.18 / 7.45 against 1.67.  The difference is the copies across the link (count x l x
+ * 32 bytes up, n x 32 down per polynomial), the vanishing values, the inversion with its synchronisation, scatter, divide and tail.  Device times from
+ * events at (2^20, 64, 1), every other cell missing: roots + vanish 1.88 ms, scatter + IFFT 0.14, coset FFT + divide + coset IFFT + tail 0.26, FFT 0.11.
+ * k_recover_vanish against its own product count, 2 mu m = 2^28 at that shape, at the 150 Gmul/s of fe_mont_gfx950.h (1.79 ms): 1.05 times at batch 1 and
+ * 1.18 at batch 4 in that run, 1.20 and 1.22 in the run before it -- the kernel runs near the multiplier's rate.  With the roots of each tile computed
+ * inside the kernel it took 1.88 times (3.36 ms): that is why k_recover_roots exists; nothing else was tuned.  At the small shapes the kernel takes 0.03
+ * to 0.05 ms whatever mu: the powers psi^a and the launch, not the pairs.  A values_out buffer allocated afresh for every call (32 MiB or more) cost 20 to
+ * 30 ms per call in the host's page handling during an earlier run: keep the buffer.  NOT measured: l < 64, m near 2^16 with many cells missing (the
+ * worst case, 2^32 products), the host twin.
+ * The host twin (csrc/host_kzg_recover_cells.hpp; plain loops over host_fr.hpp and the radix-2 transform of host_fallback.hpp, one inversion per z'; no HIP
+ * call, no lock, re-entrant) has the same refusals and the same canonical outputs: device and twin agree bit for bit, report included.  It is held to the
+ * polynomial the cells came from and, at n <= 64, to Lagrange interpolation over Python integers (tests/test_kzg_recover_cells_host.py). */
+#define BBGPU_KZG_RECOVER_MAX_CELLS (1u << 16)
+typedef struct {
+    uint32_t consistent;      /* 1: every polynomial has coefficients [d, count * coset) all zero (vacuous when count * coset == d) */
+    uint32_t first_bad_poly;  /* smallest b with a nonzero coefficient there, else 0 */
+    uint64_t first_bad_coeff; /* its smallest such index, else 0 */
+    uint64_t missing;         /* mu = n / coset - count */
+} bbgpu_kzg_recover_report;
+int bbgpu_kzg_recover_cells(const uint32_t* cell /* count, distinct, each < n / coset, any order */, size_t count,
+                            const uint64_t* values /* HOST, batch x count x coset x 4: polynomial b, listed cell t, point j */, size_t n, size_t coset,
+                            size_t degree_bound, int batch, uint64_t* d_coeffs_out /* DEVICE, batch x stride_elems x 4 */, size_t stride_elems,
+                            uint64_t* values_out /* HOST or NULL: batch x n x 4, the size-n transforms */, bbgpu_kzg_recover_report* report, void* hip_stream);
+int bbgpu_host_kzg_recover_cells(const uint32_t* cell, size_t count, const uint64_t* values, size_t n, size_t coset, size_t degree_bound, int batch,
+                                 uint64_t* coeffs_out /* HOST, batch x stride_elems x 4 */, size_t stride_elems, uint64_t* values_out,
+                                 bbgpu_kzg_recover_report* report);
+
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
  * per-proof part is what :55-355 computes -- six Keccak transcripts (challenge.hpp), the Lagrange evaluations (polynomial_arithmetic.cpp:594-626),
