@@ -73,6 +73,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_kzg_check_openings", "bbgpu_kzg_check_open_all", "bbgpu_host_kzg_check_openings_batch", "bbgpu_host_kzg_check_open_all",
     "bbgpu_kzg_check_last_timing", "bbgpu_kzg_check_cells", "bbgpu_kzg_check_open_cosets", "bbgpu_host_kzg_check_cells",
     "bbgpu_host_kzg_check_open_cosets", "bbgpu_host_kzg_cells_key_check", "bbgpu_kzg_recover_cells", "bbgpu_host_kzg_recover_cells",
+    "bbgpu_kzg_recover_cells_each", "bbgpu_host_kzg_recover_cells_each",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -190,6 +191,15 @@ class KzgCheckReport(C.Structure):
 class KzgRecoverReport(C.Structure):
     """bbgpu_kzg_recover_report (include/bbgpu.h)"""
     _fields_ = [("consistent", C.c_uint32), ("first_bad_poly", C.c_uint32), ("first_bad_coeff", C.c_uint64), ("missing", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class KzgRecoverEachReport(C.Structure):
+    """bbgpu_kzg_recover_each_report (include/bbgpu.h)"""
+    NONE = 0xFFFFFFFFFFFFFFFF  # an entry of first_bad when the polynomial has none
+    _fields_ = [("consistent", C.c_uint32), ("first_bad_poly", C.c_uint32), ("first_bad_coeff", C.c_uint64), ("max_missing", C.c_uint64)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -674,6 +684,63 @@ class BbGpu:
         self._chk(self.lib.bbgpu_host_kzg_recover_cells(cp, cell.shape[0], _ptr(values), int(n), int(coset), int(degree_bound), int(batch), _ptr(coeffs), stride,
                                                         _ptr(vals) if want_values else None, C.byref(rep)))
         return coeffs, vals, rep.as_dict()
+
+    # ---- the same for polynomials whose cell sets differ  (bbgpu_kzg_recover_cells_each and the host twin) ----
+    RECOVER_EACH_LEAF = 64  # KZG_RECOVER_EACH_LEAF (csrc/bbgpu_internal.h): roots per leaf of the product tree
+
+    @staticmethod
+    def _kzg_recover_each_args(cells, values, coset):
+        lists = [np.ascontiguousarray(c, dtype=np.uint32).reshape(-1) for c in cells]
+        offsets = np.zeros(len(lists) + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum([c.shape[0] for c in lists])
+        cell = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.uint32)]))  # never empty
+        if isinstance(values, np.ndarray):  # one array for the whole call, already in the order of the lists: handed over as it is
+            flat = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+            if flat.shape[0] < int(offsets[-1]) * max(int(coset), 1):
+                raise ValueError("kzg_recover_cells_each: %d values for %d cells of %d" % (flat.shape[0], int(offsets[-1]), coset))
+            return offsets, cell, flat, len(lists)
+        vals = [np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4) for v in values]
+        if len(lists) != len(vals):
+            raise ValueError("kzg_recover_cells_each: %d cell lists, %d value arrays" % (len(lists), len(vals)))
+        for b, (c, v) in enumerate(zip(lists, vals)):
+            if v.shape[0] < c.shape[0] * max(int(coset), 1):  # the library would read past the end
+                raise ValueError("kzg_recover_cells_each: polynomial %d: %d values for %d cells of %d" % (b, v.shape[0], c.shape[0], coset))
+        flat = np.ascontiguousarray(np.concatenate([v[:c.shape[0] * max(int(coset), 1)] for c, v in zip(lists, vals)] + [np.zeros((1, 4), dtype=np.uint64)]))
+        return offsets, cell, flat, len(lists)
+
+    def kzg_recover_cells_each(self, cells, values, n, coset, degree_bound, d_coeffs_out, stride=None, want_values=True, stream=None, out=None):
+        """bbgpu_kzg_recover_cells_each: len(cells) polynomials of degree < degree_bound, polynomial b from ITS OWN listed cells (cells[b]: distinct indices
+        below n / coset, any order; values[b] (count_b, coset, 4): listed cell t, point j, on the host -- or ONE array that holds them all in that order, which is not copied) -> coefficients [0, n) of polynomial b at element b
+        * stride of the device buffer d_coeffs_out.  Returns ((batch, n, 4) the size-n transforms -- `out` when given --, or None without want_values; the
+        report as a dict; (batch,) uint64 first_bad, KzgRecoverEachReport.NONE where a polynomial has none)."""
+        offsets, cell, flat, batch = self._kzg_recover_each_args(cells, values, coset)
+        if want_values and out is None:
+            out = np.zeros((max(batch, 1), max(int(n), 1), 4), dtype=np.uint64)
+        out = out if want_values else None
+        rep, first_bad = KzgRecoverEachReport(), np.zeros(max(batch, 1), dtype=np.uint64)
+        u32p = C.POINTER(C.c_uint32)
+        self.lib.bbgpu_kzg_recover_cells_each.argtypes = [u32p, u32p, u64p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, u64p, u64p,
+                                                          C.POINTER(KzgRecoverEachReport), C.c_void_p]
+        self._chk(self.lib.bbgpu_kzg_recover_cells_each(offsets.ctypes.data_as(u32p), cell.ctypes.data_as(u32p), _ptr(flat), int(n), int(coset), int(degree_bound),
+                                                        batch, d_coeffs_out, int(n) if stride is None else int(stride), _ptr(out) if want_values else None,
+                                                        _ptr(first_bad), C.byref(rep), stream or 0))
+        return out, rep.as_dict(), first_bad
+
+    def host_kzg_recover_cells_each(self, cells, values, n, coset, degree_bound, stride=None, want_values=True, out=None):
+        """bbgpu_host_kzg_recover_cells_each: the same on the host -> ((batch * stride, 4) coefficients -- `out` when given, whose elements [n, stride) of
+        every polynomial stay as they are --, the transforms or None, the report as a dict, first_bad)"""
+        offsets, cell, flat, batch = self._kzg_recover_each_args(cells, values, coset)
+        stride = int(n) if stride is None else int(stride)
+        coeffs = np.zeros((max(batch, 1) * max(stride, 1), 4), dtype=np.uint64) if out is None else out
+        vals = np.zeros((max(batch, 1), max(int(n), 1), 4), dtype=np.uint64) if want_values else None
+        rep, first_bad = KzgRecoverEachReport(), np.zeros(max(batch, 1), dtype=np.uint64)
+        u32p = C.POINTER(C.c_uint32)
+        self.lib.bbgpu_host_kzg_recover_cells_each.argtypes = [u32p, u32p, u64p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, u64p, C.c_size_t, u64p, u64p,
+                                                               C.POINTER(KzgRecoverEachReport)]
+        self._chk(self.lib.bbgpu_host_kzg_recover_cells_each(offsets.ctypes.data_as(u32p), cell.ctypes.data_as(u32p), _ptr(flat), int(n), int(coset),
+                                                             int(degree_bound), batch, _ptr(coeffs), stride, _ptr(vals) if want_values else None, _ptr(first_bad),
+                                                             C.byref(rep)))
+        return coeffs, vals, rep.as_dict(), first_bad
 
     # ---- do these openings hold?  (bbgpu_kzg_check_openings, bbgpu_kzg_check_open_all and the host twins) ----
     def _kzg_check_openings(self, fn, commitments, z, y, proofs, g2_x, which, seed, locate):

@@ -238,6 +238,28 @@ int kzg_recover_divide(uint64_t* d_q, size_t stride_elems, int batch, const uint
 int kzg_recover_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* d_copy, int log2n, size_t degree_bound, size_t present, RecoverFindings* d_find,
                      hipStream_t st);
 
+// kzg_recover_each.hip: the device parts of bbgpu_kzg_recover_cells_each that are neither a transform nor the batch inversion.  Polynomial b lists the
+// cells d_cell[d_off[b] .. d_off[b + 1]) and misses d_mu[b]; row b of d_missing (M entries, M the common power of two >= every mu_b, >= 1) holds its
+// missing cells and then ~0.  The product tree lives in batch x 2 M elements: at the level of nodes of degree D every node has a slot of 2 D elements,
+// its D low coefficients (the leading 1 is implied) and D zeros.
+// T: roots per leaf of the product tree, T / 64 waves of k_each_leaves.  128 and 256 compile too (a leaf then spans waves that exchange through LDS): the
+// comparison of profiles/kzg_recover_each.txt is a build with 256 here; BbGpu.RECOVER_EACH_LEAF (bbgpu.py) mirrors the value
+constexpr int KZG_RECOVER_EACH_LEAF = 64;
+struct KzgRecoverEachLists {
+    const uint32_t *d_off, *d_mu, *d_cell, *d_missing;
+    size_t M;
+};
+constexpr size_t kzg_recover_each_table_words(int log2m) { return (((size_t)1 << ((log2m + 1) / 2)) + ((size_t)1 << (log2m / 2))) * 9; } // k_each_powers
+int kzg_recover_each_leaves(const uint32_t* d_missing, int batch, size_t M, int log2m, uint64_t* d_tree, hipStream_t st);
+int kzg_recover_each_pair(uint64_t* d_tree, size_t pairs, int log2s, hipStream_t st);
+int kzg_recover_each_gather(const uint64_t* d_tree, const uint32_t* d_mu, int batch, size_t M, int log2n, int log2l, uint32_t* d_tab, uint64_t* d_zin,
+                            uint64_t* d_zcin, hipStream_t st);
+int kzg_recover_each_scatter(const uint64_t* d_values, const KzgRecoverEachLists& L, const uint64_t* d_z, int log2n, int log2l, int batch, uint64_t* d_out,
+                             size_t stride_elems, hipStream_t st);
+int kzg_recover_each_divide(uint64_t* d_q, size_t stride_elems, int batch, const uint64_t* d_inv, int log2n, int log2l, hipStream_t st);
+int kzg_recover_each_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* d_copy, int log2n, int log2l, size_t degree_bound, const uint32_t* d_off,
+                          RecoverFindings* d_find, hipStream_t st);
+
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);
 int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_t st, bool* touched = nullptr); // *touched: h_dst may have been written (even on failure)

@@ -38,6 +38,7 @@
 #include "host_kzg_open_all.hpp"
 #include "host_kzg_open_cosets.hpp"
 #include "host_kzg_recover_cells.hpp"
+#include "host_kzg_recover_each.hpp"
 #include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
@@ -4137,6 +4138,160 @@ int bbgpu_kzg_recover_cells(const uint32_t* cell, size_t count, const uint64_t* 
     if (values_out)
         if (int rc = device_to_host_sync(values_out, copy.p, (size_t)batch * n * 32, st)) return rc;
     if (timed) { // bbgpu_last_timing: index 0 k_recover_vanish, 1 scatter and IFFT, 2 coset FFT, divide, coset IFFT and tail, 3 the forward transform (if asked for)
+        ctx().last.count = values_out ? 4 : 3;
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[0], ev.e[0], ev.e[1]));
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[1], ev.e[2], ev.e[3]));
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[2], ev.e[3], ev.e[4]));
+        if (values_out) HIPCHK(hipEventElapsedTime(&ctx().last.ms[3], ev.e[4], ev.e[5]));
+    }
+    return BBGPU_OK;
+}
+
+/* ---- the same for polynomials whose cell sets differ, at any n / l (host_kzg_recover_each.hpp, kzg_recover_each.hip) ---- */
+int bbgpu_host_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32_t* cell, const uint64_t* values, size_t n, size_t coset, size_t degree_bound,
+                                      int batch, uint64_t* coeffs_out, size_t stride_elems, uint64_t* values_out, uint64_t* first_bad_out,
+                                      bbgpu_kzg_recover_each_report* report)
+{
+    host::KzgRecoverEachShape S;
+    char why[320];
+    int rc = host::kzg_recover_each_verdict("host kzg_recover_cells_each", cell_offsets, cell, values, n, coset, degree_bound, batch, coeffs_out, stride_elems, report,
+                                            &S, why, sizeof why);
+    if (rc == BBGPU_OK)
+        rc = host::kzg_recover_cells_each_host(S, cell_offsets, cell, values, degree_bound, batch, coeffs_out, stride_elems, values_out, first_bad_out, report, why,
+                                               sizeof why);
+    if (rc) set_error("%s", why);
+    return rc;
+}
+
+// `count` transforms of 2^lg elements, `stride` elements apart, through the internal entry: no cap of 64, the grid's limit in y respected, the shared
+// scratch sized for a whole chunk (transforms above 2^11 points go through it)
+static int recover_each_ntt(uint64_t* d, size_t stride, size_t count, int lg, int kind, hipStream_t st)
+{
+    constexpr size_t CHUNK = 32768;
+    if (lg > 11)
+        if (int rc = grow(&ctx().d_scratch, &ctx().scratch_cap, (std::min(count, CHUNK) << lg) * 32)) return rc;
+    if (int rc = shared_begin(st)) return rc;
+    for (size_t c0 = 0; c0 < count; c0 += CHUNK) {
+        const int rc = ntt_device_batch(d + 4 * c0 * stride, stride, (int)std::min(CHUNK, count - c0), ctx().d_scratch, lg, kind, nullptr, st);
+        if (rc == BBGPU_ERR_HIP) {
+            const hipError_t he = hipGetLastError(); // hipSuccess: the failing call has already described itself (launch_check / dev_malloc)
+            if (he != hipSuccess) set_error("NTT launch failed: %s", hipGetErrorString(he));
+        }
+        if (rc) return rc;
+    }
+    return shared_end(st);
+}
+
+int bbgpu_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32_t* cell, const uint64_t* values, size_t n, size_t coset, size_t degree_bound, int batch,
+                                 uint64_t* d_coeffs_out, size_t stride_elems, uint64_t* values_out, uint64_t* first_bad_out,
+                                 bbgpu_kzg_recover_each_report* report, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    host::KzgRecoverEachShape S;
+    char why[320];
+    if (int rc = host::kzg_recover_each_verdict("kzg_recover_cells_each", cell_offsets, cell, values, n, coset, degree_bound, batch, d_coeffs_out, stride_elems,
+                                                report, &S, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (int rc = ensure_init()) return rc;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const size_t m = S.m, total = S.total, B = (size_t)batch;
+    const int log2m = S.log2n - S.log2l;
+    size_t M = 1; // the common padded number of roots: a power of two, >= every mu_b, <= m (every polynomial lists a cell)
+    while (M < S.max_missing) M <<= 1;
+    const size_t T = std::min<size_t>(KZG_RECOVER_EACH_LEAF, M);
+    struct Events { // the stage boundaries of bbgpu_last_timing, only made when timing is on
+        hipEvent_t e[8] = {};
+        ~Events()
+        {
+            for (hipEvent_t v : e)
+                if (v) (void)hipEventDestroy(v);
+        }
+    } ev;
+    const bool timed = ctx().timing != 0;
+    if (timed)
+        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
+    auto mark = [&](int k) -> int {
+        if (timed) HIPCHK(hipEventRecord(ev.e[k], st));
+        return BBGPU_OK;
+    };
+    // offsets, counts of missing cells, cell lists and padded missing lists in one array | the tree | the inputs of the two Z transforms, then z and z',
+    // and the power table | the values | the findings | the copy the forward transform works in
+    DevBuf lists, tree, z, vals, find, copy;
+    const size_t list_words = (B + 1) + B + total + B * M;
+    HIPCHK(dev_malloc(&lists.p, list_words * 4));
+    HIPCHK(dev_malloc(&tree.p, B * 2 * M * 32));
+    HIPCHK(dev_malloc(&z.p, 2 * B * m * 32 + kzg_recover_each_table_words(log2m) * 4));
+    HIPCHK(dev_malloc(&vals.p, total * coset * 32));
+    HIPCHK(dev_malloc(&find.p, B * sizeof(RecoverFindings)));
+    if (values_out) HIPCHK(dev_malloc(&copy.p, B * n * 32));
+    std::vector<uint32_t> all(list_words, ~0u);
+    for (size_t b = 0; b <= B; b++) all[b] = cell_offsets[b];
+    for (size_t b = 0; b < B; b++) {
+        all[B + 1 + b] = (uint32_t)S.missing[b].size();
+        std::copy(S.missing[b].begin(), S.missing[b].end(), all.begin() + (2 * B + 1 + total + b * M));
+    }
+    std::copy(cell, cell + total, all.begin() + (2 * B + 1));
+    KzgRecoverEachLists L{};
+    L.d_off = lists.as<uint32_t>();
+    L.d_mu = L.d_off + B + 1;
+    L.d_cell = L.d_mu + B;
+    L.d_missing = L.d_cell + total;
+    L.M = M;
+    uint64_t *d_tree = tree.as<uint64_t>(), *d_z = z.as<uint64_t>(), *d_zc = d_z + 4 * B * m;
+    uint32_t* d_tab = reinterpret_cast<uint32_t*>(d_zc + 4 * B * m);
+    std::vector<RecoverFindings> found(B, RecoverFindings{ ~0ull, ~0ull });
+    if (int rc = host_to_device(lists.p, all.data(), list_words * 4, st)) return rc;
+    if (int rc = host_to_device(find.p, found.data(), found.size() * sizeof(RecoverFindings), st)) return rc;
+    if (int rc = host_to_device(vals.p, values, total * coset * 32, st)) return rc;
+    if (int rc = mark(0)) return rc;
+    // the tree: leaves of T roots, then one level per doubling -- forward transform of every slot, sibling products, inverse transform of every other slot
+    if (int rc = kzg_recover_each_leaves(L.d_missing, batch, M, log2m, d_tree, st)) return rc;
+    for (size_t D = T; D < M; D <<= 1) {
+        const int lg = log2_exact(2 * D);
+        const size_t slots = B * M / D;
+        if (int rc = recover_each_ntt(d_tree, 2 * D, slots, lg, BBGPU_FFT, st)) return rc;
+        if (int rc = kzg_recover_each_pair(d_tree, slots / 2, lg, st)) return rc;
+        if (int rc = recover_each_ntt(d_tree, 4 * D, slots / 2, lg, BBGPU_IFFT, st)) return rc;
+    }
+    // Z_b's coefficients, scaled for the domain and for the coset, and the 2 x batch transforms of size m that make z and z' x 2^-5 of them
+    if (int rc = kzg_recover_each_gather(d_tree, L.d_mu, batch, M, S.log2n, S.log2l, d_tab, d_z, d_zc, st)) return rc;
+    if (int rc = recover_each_ntt(d_z, m, 2 * B, log2m, BBGPU_FFT, st)) return rc;
+    if (int rc = mark(1)) return rc;
+    if (int rc = bbgpu_fr_batch_invert_device(d_zc, B * m, hip_stream)) return rc; // z' is never zero: g^n != 1
+    if (int rc = mark(2)) return rc;
+    if (int rc = kzg_recover_each_scatter(vals.as<uint64_t>(), L, d_z, S.log2n, S.log2l, batch, d_coeffs_out, stride_elems, st)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_IFFT, nullptr, hip_stream)) return rc;
+    if (int rc = mark(3)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_FFT, nullptr, hip_stream)) return rc;
+    if (int rc = kzg_recover_each_divide(d_coeffs_out, stride_elems, batch, d_zc, S.log2n, S.log2l, st)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_IFFT, nullptr, hip_stream)) return rc;
+    if (int rc = kzg_recover_each_tail(d_coeffs_out, stride_elems, batch, copy.as<uint64_t>(), S.log2n, S.log2l, degree_bound, L.d_off, find.as<RecoverFindings>(), st))
+        return rc;
+    if (int rc = mark(4)) return rc;
+    if (values_out) {
+        if (int rc = bbgpu_ntt_device_batch(copy.as<uint64_t>(), n, n, batch, BBGPU_FFT, nullptr, hip_stream)) return rc;
+        if (int rc = mark(5)) return rc;
+    }
+    if (int rc = device_to_host_sync(found.data(), find.p, found.size() * sizeof(RecoverFindings), st)) return rc;
+    std::vector<uint64_t> first_bad(B), first_bug(B);
+    for (size_t b = 0; b < B; b++) {
+        first_bad[b] = found[b].first_bad;
+        first_bug[b] = found[b].first_bug;
+    }
+    // the verdict into locals first: nothing of the caller's host memory is written before the last copy has succeeded
+    bbgpu_kzg_recover_each_report rep;
+    if (int rc = host::kzg_recover_each_report("kzg_recover_cells_each", first_bad.data(), first_bug.data(), batch, S.max_missing, nullptr, &rep, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (values_out)
+        if (int rc = device_to_host_sync(values_out, copy.p, B * n * 32, st)) return rc;
+    *report = rep;
+    if (first_bad_out) std::copy(first_bad.begin(), first_bad.end(), first_bad_out);
+    if (timed) { // bbgpu_last_timing: index 0 leaves, levels, gather and the two Z transforms, 1 scatter and IFFT, 2 coset FFT, divide, coset IFFT and tail, 3 the forward transform (if asked for)
         ctx().last.count = values_out ? 4 : 3;
         HIPCHK(hipEventElapsedTime(&ctx().last.ms[0], ev.e[0], ev.e[1]));
         HIPCHK(hipEventElapsedTime(&ctx().last.ms[1], ev.e[2], ev.e[3]));

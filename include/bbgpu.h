@@ -1107,7 +1107,7 @@ int bbgpu_host_kzg_cells_key_check(const uint64_t* g1_head /* coset x 8 */, size
  * reference has no counterpart.  Notation as in the two blocks above: l = coset, m = n / l, omega = the n-th root of the transforms, psi = omega^l, g the
  * coset generator of BBGPU_COSET_FFT; cell k < m holds f(omega^(k + m j)), j < l, and vanishes under X^l - psi^k.
  * Given the degree bound d (deg f < d <= n) and `count` distinct cells with count * l >= d, the same for all `batch` polynomials -- the column-custody case,
- * which makes the vanishing polynomial a once-per-call cost; different sets are one call each -- let K be the mu = m - count missing cells and
+ * which makes the vanishing polynomial a once-per-call cost; different sets are one call each, or ONE call of bbgpu_kzg_recover_cells_each below -- let K be the mu = m - count missing cells and
  *   Z(X) = prod_{k in K} (X^l - psi^k),   z_a = prod_{k in K} (psi^a - psi^k) = Z(omega^i),   z'_a = prod_{k in K} (g^l psi^a - psi^k) = Z(g omega^i),   a = i mod m.
  * z_a is zero exactly on the missing cells, z'_a never (g^n != 1), and Z never exists in coefficient form.  Per polynomial:
  *   E_i = v_i z_(i mod m) on the present cells, 0 on the missing ones      the values of f Z on the whole domain, deg f Z < n
@@ -1125,8 +1125,8 @@ int bbgpu_host_kzg_cells_key_check(const uint64_t* g1_head /* coset x 8 */, size
  * n / coset > BBGPU_KZG_RECOVER_MAX_CELLS = 2^16, degree_bound outside 1..n, count * coset < degree_bound (too few cells), count > n / coset, batch outside
  * 1..64, stride_elems < n, batch * n > 2^22; BBGPU_ERR_ARG: a null pointer (values_out may be NULL), a cell index >= n / coset, the same cell listed twice --
  * bbgpu_last_error() names the first offender.  BBGPU_ERR_HIP with a text of its own: a nonzero coefficient in [count * l, n), which no input can cause.
- * Scope: m <= 2^16 because the vanishing values cost mu x m pairs (at most 2^15 x 2^16); a subproduct tree for larger m -- small l at large n -- is a later
- * change.  Proofs are the caller's next call: bbgpu_kzg_open_cosets_device on d_coeffs_out.
+ * Scope: m <= 2^16 because the vanishing values cost mu x m pairs (at most 2^15 x 2^16); larger m -- small l at large n -- is what
+ * bbgpu_kzg_recover_cells_each below takes, by a product tree.  Proofs are the caller's next call: bbgpu_kzg_open_cosets_device on d_coeffs_out.
  * The kernels (csrc/kzg_recover_cells.hip; the last three take the polynomial from blockIdx.y): k_recover_roots writes psi^k for the missing cells once;
  * k_recover_vanish, the compute-bound part, gives G = min(64, 2^18 / m) neighbouring lanes to every a, walks K in LDS tiles of 256 roots with two
  * accumulators per lane (one subtraction and one product each per pair, sharing the staged root) and multiplies the G partial products in a tree across
@@ -1171,6 +1171,88 @@ int bbgpu_kzg_recover_cells(const uint32_t* cell /* count, distinct, each < n / 
 int bbgpu_host_kzg_recover_cells(const uint32_t* cell, size_t count, const uint64_t* values, size_t n, size_t coset, size_t degree_bound, int batch,
                                  uint64_t* coeffs_out /* HOST, batch x stride_elems x 4 */, size_t stride_elems, uint64_t* values_out,
                                  bbgpu_kzg_recover_report* report);
+
+/* ---- recover polynomials whose cell sets differ, at any n / l  (the vanishing polynomials in coefficient form from a product tree) ------
+ * bbgpu_kzg_recover_cells above wants the same cells of every polynomial and at most 2^16 cells, because it computes the values of Z by mu x m pair
+ * products once per call.  A node that samples at random, or repairs the rows of a 2-D layout, holds a DIFFERENT set of each polynomial, and plain
+ * Reed-Solomon erasure decoding (l = 1) has m = n cells.  bbgpu_kzg_recover_cells_each takes per-polynomial cell lists and any m = n / l up to n = 2^21:
+ * polynomial b lists count_b = cell_offsets[b + 1] - cell_offsets[b] distinct cells with count_b * l >= d and misses the mu_b = m - count_b cells K_b.
+ * Everything the block above fixes holds here too: notation, the layout of cells, the memory format of `values` (now cell_offsets[batch] x coset x 4 words
+ * in the order of `cell`), what d_coeffs_out and values_out contain, canonical Montgomery outputs, "a finding, not an error" for inconsistent cells, the
+ * vacuous verdict where count_b * l == d, context 0 under the library mutex, the return after the last copy.  first_bad_out, if given, receives per
+ * polynomial the smallest nonzero index in [d, count_b * l), UINT64_MAX for none; the report names the first such polynomial.  The device entry
+ * writes report and first_bad_out only after its last copy has succeeded.
+ * Z_b(Y) = prod_{k in K_b} (Y - psi^k), Y = X^l, in COEFFICIENT form, O(m log^2 m) products, batched over the polynomials:
+ *   roots    every polynomial's list is padded with ZERO roots to a common power of two M >= max mu_b (>= 1, <= m since count_b >= 1): the padded product
+ *            is Y^(M - mu_b) Z_b, so Z_b's coefficients are the padded product's read from offset M - mu_b -- exact, no division, mu_b = 0 gives Z_b = 1
+ *   leaves   k_each_leaves: T = min(64, M) roots -> the T low coefficients of their monic product (the leading 1 is implied everywhere in the tree), one
+ *            coefficient per lane, one wave per leaf: per root c_i <- c_i - r c_(i+1) with the neighbour's nine limbs by __shfl_down and one two-product
+ *            reduction (mul_add) per lane; the roots -psi^k are computed by the same lanes into LDS first (no roots kernel)
+ *   levels   (X^D + a)(X^D + b) = X^(2D) + X^D (a + b) + a b with deg a b <= 2 D - 2: the low part fits a cyclic transform of size 2 D without wrap-around.
+ *            Every node keeps its D low coefficients in a slot of 2 D elements, upper half zero; per level ONE batched FFT of size 2 D over all slots of
+ *            all polynomials, k_each_pair -- s (A_j + B_j) + A_j B_j with s = (-1)^j = the value of X^D, written over A_j, zero over B_j -- and ONE batched
+ *            IFFT of every other slot, which leaves the parent's 2 D coefficients in the low half of its slot of 4 D: three launch groups per level and no
+ *            separate add or repack kernel.  The transforms are the internal ntt_device_batch (blockIdx.y = transform; calls split at 32768 transforms;
+ *            the shared scratch sized per call for sizes above 2^11).  The walk visits the domain sizes 2 T .. M and then m and n once each, in
+ *            ascending order, every size used at once after it is fetched: under the table cache's least-recently-used rule (BBGPU_NTT_TABLE_BYTES) a
+ *            set that is dropped is one the call no longer needs, and all sets to 2^21 together hold 0.5 GiB of the default 8 GiB
+ *   values   k_each_powers + k_each_gather write Z_b's mu_b + 1 coefficients x 2^5 and x (g^l)^j 2^-5 (two small power tables) zero-padded to m; ONE batched
+ *            FFT of 2 batch transforms of size m gives z_b as Montgomery-261 multipliers and z'_b x 2^-5; one batch inversion over all batch x m z'
+ *   the rest as above with per-polynomial lists: k_each_scatter, IFFT, COSET_FFT, k_each_divide, COSET_IFFT, k_each_tail (windows [d, count_b l) and
+ *            [count_b l, n) per polynomial), the optional FFT.  csrc/kzg_recover_cells.hip is unchanged and bbgpu_kzg_recover_cells bit-identical.
+ * Refused before a device is bound, outputs untouched -- BBGPU_ERR_SIZE: n or coset not a power of two, coset outside 1..64, n / coset < 2, n > 2^21,
+ * degree_bound outside 1..n, batch outside 1..64, stride_elems < n, batch * n > 2^22, for some b count_b = 0, count_b > n / coset or count_b * coset <
+ * degree_bound; BBGPU_ERR_ARG: a null pointer (values_out and first_bad_out may be NULL), cell_offsets[0] != 0 or offsets that decrease, a cell index >=
+ * n / coset, a cell listed twice within one polynomial -- bbgpu_last_error() names the first offender by polynomial and position.  There is NO cap on
+ * n / coset.  BBGPU_ERR_HIP with a text of its own: a nonzero coefficient in [count_b * l, n), which no input can cause.  Not here: a per-polynomial
+ * degree bound, cells of different sizes in one call, n > 2^21.
+ * Resources (hipcc -Rpass-analysis=kernel-resource-usage, VGPRs / LDS bytes / waves per SIMD): k_each_leaves 52 / 9216 / 8, k_each_pair 45 / 0 / 8,
+ * k_each_powers 42 / 0 / 8, k_each_gather 41 / 0 / 8, k_each_scatter 32 / 0 / 8, k_each_divide 32 / 0 / 8, k_each_tail 41 / 32 / 8; no scratch and no
+ * spill in any.
+ * A warm call with values_out passes six allocations (the lists; the tree; z, z' and the power tables; the values; the findings; the copy for the forward
+ * transform -- five without values_out), three uploads (the lists, the findings' start, the values), two read-backs (the findings, the transforms -- one
+ * without) and, at (256, 4) where 64 cells make one leaf and no level, thirteen launch checks (leaves; powers + gather; the Z transforms; the inversion's
+ * two scans and its product; scatter; four transforms; divide; tail); every tree level adds three (at (1024, 1) with 200 cells missing: nineteen).
+ * Every site failed once through bbgpu_fault_inject returns BBGPU_ERR_HIP, leaves nothing the call allocated live, and the next call is bit-exact
+ * (tests/test_gpu_kzg_recover_each.py).  With bbgpu_set_timing(1), bbgpu_last_timing() index 0 is the device time of leaves, levels, gather and the Z
+ * transforms, 1 that of scatter and IFFT, 2 that of coset FFT, divide, coset IFFT and tail, 3 that of the forward transform (only with values_out); the
+ * batch inversion lies between 0 and 1 and is in none.
+ * Cost on one MI355X (tools/kzg_recover_each_bench.py, profiles/kzg_recover_each.txt; wall ms per call with values_out read back into a buffer the caller
+ * keeps, one box, medians of 9 alternating pairs).  SAME set for all polynomials, this entry / bbgpu_kzg_recover_cells, every other cell missing and
+ * one cell missing: (n, l, batch) = (8192, 64, 1) 0.49 / 0.43 and 0.45 / 0.43; (2^16, 64, 16) 2.30 / 2.10 and 2.40 / 2.33; (2^20, 64, 1) 2.57 / 4.19
+ * and 2.48 / 2.49; (2^20, 64, 4) 6.97 / 8.32 and 7.70 / 7.44 -- the tree wins where the pair kernel has work (0.45 ms of device time against 1.88 at
+ * (2^20, 64) with half the cells missing) and loses 0.02 to 0.25 ms elsewhere to its extra launches and lists; that is the figure for moving the old
+ * entry onto the tree, which this change does not do.  DIFFERENT sets, a random half missing, one call here against `batch` calls there: (2^16, 64, 16)
+ * 2.36 against 11.84; (2^20, 64, 4) 7.37 against 16.96.  The shapes only this entry takes, half the cells missing: (2^20, 1, 1) 10.0 ms, device times
+ * tree + Z transforms 2.72, scatter + IFFT 0.16, coset FFT + divide + coset IFFT + tail 0.29, FFT 0.12; (2^20, 4, 4) 13.5 ms, device 2.27 / 0.52 / 0.99 /
+ * 0.41; the rest of the wall time is the host's lists of missing cells, the copies across the link and the inversion of batch x m values.
+ * T was chosen by measurement (a build with KZG_RECOVER_EACH_LEAF = 256 in csrc/bbgpu_internal.h runs a leaf on four waves that exchange through LDS behind one barrier per
+ * root; kernel trace, same box): k_each_leaves 0.448 ms at T = 64, 2.00 times its product count M T per polynomial at the 150 Gmul/s of
+ * fe_mont_gfx950.h (0.224 ms for 2^25; every lane and root is a two-product reduction), 1.445 ms at T = 256, 1.61 times its count (0.895 ms for 2^27);
+ * the tree with the Z transforms 2.72 ms against 3.41 at (2^20, 1, 1), 2.27 against 2.99 at (2^20, 4, 4), 0.48 against 0.62 at (2^20, 64, 4): the two
+ * levels T = 256 saves cost less than its leaves add, so T = 64 ships.  NOT timed: the host twin, l = 1 at batch x n = 2^22, batches in which one
+ * polynomial misses far more cells than the others (all are padded to the largest M), the inversion and the host's part of a call on their own.
+ * The host twin (csrc/host_kzg_recover_each.hpp) is plain loops and deliberately NOT a tree: z_b and z'_b by direct products over K_b, once per
+ * polynomial, exactly as host_kzg_recover_cells.hpp does, so that it states independently what the tree must produce.  That costs sum_b mu_b x m x 2
+ * products: a checker for test sizes, not a fallback for m = 2^20.  Same refusals, same canonical outputs, report and first_bad_out included; no HIP
+ * call, no lock, re-entrant.  It is held to Lagrange interpolation over Python integers at n <= 64 and to bbgpu_host_kzg_recover_cells bit for bit
+ * where the sets agree (tests/test_kzg_recover_each_host.py). */
+typedef struct {
+    uint32_t consistent;      /* 1: every polynomial b has coefficients [d, count_b * coset) all zero (vacuous where count_b * coset == d) */
+    uint32_t first_bad_poly;  /* smallest b that has not, else 0 */
+    uint64_t first_bad_coeff; /* its smallest such index, else 0 */
+    uint64_t max_missing;     /* max over b of n / coset - count_b */
+} bbgpu_kzg_recover_each_report;
+int bbgpu_kzg_recover_cells_each(const uint32_t* cell_offsets /* batch + 1, cell_offsets[0] = 0, non-decreasing */,
+                                 const uint32_t* cell /* cell_offsets[batch]: polynomial b owns cell[cell_offsets[b] .. cell_offsets[b + 1]), distinct, any order */,
+                                 const uint64_t* values /* HOST, cell_offsets[batch] x coset x 4, in the order of `cell` */, size_t n, size_t coset,
+                                 size_t degree_bound, int batch, uint64_t* d_coeffs_out /* DEVICE, batch x stride_elems x 4 */, size_t stride_elems,
+                                 uint64_t* values_out /* HOST or NULL, batch x n x 4 */,
+                                 uint64_t* first_bad_out /* HOST or NULL, batch: smallest nonzero index in [d, count_b * coset) of polynomial b, UINT64_MAX if none */,
+                                 bbgpu_kzg_recover_each_report* report, void* hip_stream);
+int bbgpu_host_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32_t* cell, const uint64_t* values, size_t n, size_t coset, size_t degree_bound,
+                                      int batch, uint64_t* coeffs_out /* HOST, batch x stride_elems x 4 */, size_t stride_elems, uint64_t* values_out,
+                                      uint64_t* first_bad_out, bbgpu_kzg_recover_each_report* report);
 
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
