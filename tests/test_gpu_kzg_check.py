@@ -4,7 +4,11 @@ field for field, a and b included, under a fixed seed -- the twins themselves ar
 tests/test_kzg_check_host.py.  Counts: 1 (the smallest call), 63 / 64 / 65 (the wave edge), 255 / 256 / 257 (the workgroup edge), 1023 / 1025 (the
 small-table threshold of the transient MSM), 20480 (proofs across two 1 MiB upload chunks, a fold of more than one range).  The open-all form takes
 count = batch x 2^k with batch <= 64 only: of the counts above that is 1, 63, 64 and 256; 65, 255, 257, 1023 and 1025 have no such factorisation (they
-are covered there by (2, 1), (64, 3), (256, 16) and (4096, 5))."""
+are covered there by (2, 1), (64, 3), (256, 16) and (4096, 5)).  Past the grid of k_kzg_claims (2048 workgroups of 256, so claim 2^19 is the first that
+a thread takes in its second trip): 2^19 + 257 claims in the shared and the per-claim form, 33 x 2^14 (a partial second trip) and 64 x 2^14 (two full
+trips, all 256 fold ranges) in the open-all form, over one world of 2^20 claims that the device producers make once."""
+import time
+
 import numpy as np
 import pytest
 
@@ -16,6 +20,7 @@ pytestmark = pytest.mark.gpu
 KINDS = ("alloc", "h2d", "d2h", "launch")
 KEYS = {"alloc": "alloc_calls", "h2d": "h2d_calls", "d2h": "d2h_calls", "launch": "launch_checks"}
 FAR = 1 << 62
+HALF = 1 << 19  # the threads of the k_kzg_claims grid at its cap: claim HALF + i is thread i's second
 COUNTS = [1, 63, 64, 65, 255, 256, 257, 1023, 1025]
 POSITIONS = [0, 63, 64, 256, 299]  # of 300 claims: the first, both sides of the wave edge, the first of the second workgroup, the last
 # the funnels one warm call of 256 claims passes (include/bbgpu.h).  Uploads: the proofs, y, z, then the commitments (per-claim layout) or the labels
@@ -146,6 +151,111 @@ def test_the_proofs_of_open_all_device_are_accepted(lib, oracle, W):
     proofs[4, n - 1] = negated(oracle, proofs[4, n - 1])
     got, want = both_open_all(lib, V, proofs=proofs, locate=True)
     assert got == want and got["ok"] == 0 and got["first_failing"] == n * batch - 1 and got["rounds"] <= 1 + 15
+
+
+@pytest.fixture(scope="module")
+def big(lib, oracle, W):
+    """(n, batch) = (2^14, 64) by the device producers: 2^20 true claims, every proof finite; z: the domain.  Made once, never written to."""
+    from tests.kzg_open_all_cases import domain
+    t0 = time.perf_counter()
+    V = device_world(lib, oracle, W, 1 << 14, 64)
+    print("producers of the world of 2^20 claims: %.2f s" % (time.perf_counter() - t0))
+    return dict(V, z=domain(oracle, 1 << 14))
+
+
+def first_polynomials(V, batch):
+    return dict(V, batch=batch, commitments=V["commitments"][:batch], values=V["values"][:batch], proofs=V["proofs"][:batch])
+
+
+def first_claims(V, count):
+    """claims t < count of the world in the shared layout with explicit z: claim t is point t % n of polynomial t // n -> (which, z, y, proofs)"""
+    t, n = np.arange(count), V["n"]
+    return ((t // n).astype(np.uint32), aligned_copy(V["z"][t % n]), aligned_copy(V["values"].reshape(-1, 4)[:count]),
+            aligned_copy(V["proofs"].reshape(-1, 8)[:count]))
+
+
+def open_all_report(lib, V, values=None, proofs=None, **kw):
+    return lib.kzg_check_open_all(V["commitments"], V["values"] if values is None else values, V["proofs"] if proofs is None else proofs, V["n"], V["g2_x"],
+                                  seed=SEED, **kw)
+
+
+@pytest.mark.parametrize("batch", [33, 64])
+def test_open_all_form_past_the_claim_grid(lib, oracle, big, batch):
+    """540,672 claims: threads 0 .. 16383 take two claims, the others one; 2^20 claims: two full trips and 256 fold ranges.  The call says ok; a false
+    value at the last claim of the first trip, at the first of the second and at the last claim, and a negated proof inside the second trip's first
+    workgroup, are each located exactly.  No twin at this size: the located claim is the reference."""
+    V = first_polynomials(big, batch)
+    n, count = V["n"], batch * V["n"]
+    got = open_all_report(lib, V)
+    assert got["ok"] == 1 and scalars(got) == honest(count)
+    for t in (HALF - 1, HALF, count - 1):
+        values = V["values"].copy()
+        values[t // n, t % n] = plus_one(oracle, values[t // n, t % n])
+        got = open_all_report(lib, V, values=values, locate=True)
+        assert got["ok"] == 0 and got["first_failing"] == t and got["count"] == count, (t, got)
+    t = HALF + 129
+    proofs = V["proofs"].copy()
+    proofs[t // n, t % n] = negated(oracle, proofs[t // n, t % n])
+    got = open_all_report(lib, V, proofs=proofs, locate=True)
+    assert got["ok"] == 0 and got["first_failing"] == t, got
+    assert lib.fault_stats()["slots_pending"] == 0
+
+
+def test_shared_and_per_claim_forms_past_the_claim_grid(lib, oracle, big):
+    """2^19 + 257 claims over 33 commitments: 257 threads take a second claim.  Honest, and a false value at claim 2^19 + 100 located, in both forms; and
+    at 33 x 2^14 claims the shared form with explicit z gives the open-all form's report, a and b included."""
+    count, g2_x = HALF + 257, big["g2_x"]
+    which, z, y, p = first_claims(big, count)
+    cs = aligned_copy(big["commitments"][:33])
+    Cs = aligned_copy(cs[which])
+    assert int(which[-1]) == 32
+    assert scalars(lib.kzg_check_openings(cs, z, y, p, g2_x, which=which, seed=SEED)) == honest(count)
+    assert scalars(lib.kzg_check_openings(Cs, z, y, p, g2_x, seed=SEED)) == honest(count)
+    y2 = y.copy()
+    y2[HALF + 100] = plus_one(oracle, y[HALF + 100])
+    for commitments, kw in ((cs, dict(which=which)), (Cs, {})):
+        got = lib.kzg_check_openings(commitments, z, y2, p, g2_x, seed=SEED, locate=True, **kw)
+        assert got["ok"] == 0 and got["first_failing"] == HALF + 100 and got["count"] == count, got
+    V = first_polynomials(big, 33)
+    which, z, y, p = first_claims(big, 33 * V["n"])
+    assert lib.kzg_check_openings(cs, z, y, p, g2_x, which=which, seed=SEED) == open_all_report(lib, V)
+
+
+def test_findings_of_the_second_trip(lib, oracle, big):
+    """off-curve points at claims a thread meets in its second trip: the count and the first finding are exact (the key of a per-claim commitment is 2 t,
+    of a proof 2 t + 1); with a finding in each trip of ONE thread (claims 5 and 2^19 + 5) the count is the sum and the first is the first trip's"""
+    count, g2_x, t = HALF + 257, big["g2_x"], HALF + 5
+    which, z, y, p = first_claims(big, count)
+    cs = aligned_copy(big["commitments"][:33])
+    Cs = aligned_copy(cs[which])
+    V = first_polynomials(big, 33)
+    n = V["n"]
+    for spots in ((t,), (5, t)):
+        p2, proofs = p.copy(), V["proofs"].copy()
+        for s in spots:
+            p2[s] = off_curve(oracle, p[s])
+            proofs[s // n, s % n] = off_curve(oracle, proofs[s // n, s % n])
+        found = dict(ok=0, rounds=0, bad_points=len(spots), first_bad=spots[0], first_bad_is_proof=1)
+        assert scalars(lib.kzg_check_openings(cs, z, y, p2, g2_x, which=which, seed=SEED)) == honest(count, **found), spots
+        assert scalars(lib.kzg_check_openings(Cs, z, y, p2, g2_x, seed=SEED)) == honest(count, **found), spots
+        assert scalars(open_all_report(lib, V, proofs=proofs)) == honest(33 * n, **found), spots
+    c2, p2 = Cs.copy(), p.copy()
+    c2[t], p2[t - 1] = off_curve(oracle, Cs[t]), off_curve(oracle, p[t - 1])  # keys 2 t and 2 (t - 1) + 1: the proof comes first
+    got = lib.kzg_check_openings(c2, z, y, p2, g2_x, seed=SEED)
+    assert scalars(got) == honest(count, ok=0, rounds=0, bad_points=2, first_bad=t - 1, first_bad_is_proof=1)
+    assert scalars(lib.kzg_check_openings(cs, z, y, p, g2_x, which=which, seed=SEED)) == honest(count)  # the next call is the honest one
+
+
+def test_the_twin_past_the_claim_grid(lib, big):
+    """the shared form at 2^19 + 257 claims, report against report; the twin's wall time is printed"""
+    count = HALF + 257
+    which, z, y, p = first_claims(big, count)
+    cs = aligned_copy(big["commitments"][:33])
+    got = lib.kzg_check_openings(cs, z, y, p, big["g2_x"], which=which, seed=SEED)
+    t0 = time.perf_counter()
+    want = lib.host_kzg_check_openings_batch(cs, z, y, p, big["g2_x"], which=which, seed=SEED)
+    print("host twin at %d claims: %.2f s" % (count, time.perf_counter() - t0))
+    assert got == want and got["ok"] == 1
 
 
 @pytest.mark.parametrize("t", POSITIONS)

@@ -2,7 +2,8 @@
 k_kzg_cell_coefficients in both instantiations, k_kzg_cells_fold, k_kzg_cells_fold_finish) and the driver in capi.hip against the host twins
 (csrc/host_kzg_check_cells.hpp), report against report, field for field, a and b included, under a fixed seed -- the twins themselves are held to an
 independent reference by tests/test_kzg_check_cells_host.py.  l lanes take a cell, so the counts are chosen in cells around the edges of a wave (64 / l
-cells) and of a workgroup (256 / l cells) for every l."""
+cells) and of a workgroup (256 / l cells) for every l.  Past the grids: 33 x 2^14 and 64 x 2^14 cells of one point (k_kzg_cells' 2^19 threads), 5120 cells
+of 64 points in the open-cosets form (the coefficient kernel's 1024 workgroups of 4 cells)."""
 import numpy as np
 import pytest
 
@@ -155,6 +156,45 @@ def test_second_trip_of_the_stride_loop(lib, oracle, worlds):
     assert got == want and scalars(got) == honest(count)
     got, want = both(lib, W, which, cell, false_value(oracle, values, 64, 4098, 63), proofs, locate=True)
     assert got == want and got["first_failing"] == 4098
+
+
+@pytest.fixture(scope="module")
+def one_point_world(lib, oracle, tmp_path_factory):
+    """(n, l, batch) = (2^14, 1, 64) by the device producers: 2^20 cells of one point.  Made once, never written to."""
+    return device_world(lib, oracle, tmp_path_factory.mktemp("cells_of_one_point"), 1 << 14, 1, 64)
+
+
+@pytest.mark.parametrize("batch", [33, 64])
+def test_cosets_of_one_point_past_the_cell_grid(lib, oracle, one_point_world, batch):
+    """l = 1 at 33 x 2^14 and 64 x 2^14 cells: k_kzg_cells' 2^19 threads take a partial and a full second trip, the 1024 workgroups of 256 cells of the
+    coefficient kernel more than two, the fold all its ranges.  The report is bbgpu_kzg_check_open_all's on the same data ([x^1] G2 is x G2), honest and
+    with a false value at cell 2^19 + 100 located."""
+    V, n, t = one_point_world, 1 << 14, (1 << 19) + 100
+    cs, proofs, values = V["commitments"][:batch], V["proofs"][:batch], aligned_copy(V["values"][:batch].reshape(-1, 4))
+    got = lib.kzg_check_open_cosets(cs, values, proofs, n, 1, V["head"], V["g2_xl"], seed=SEED)
+    assert got == lib.kzg_check_open_all(cs, values, proofs, n, V["g2_xl"], seed=SEED) and scalars(got) == honest(batch * n)
+    values[t] = plus_one(oracle, values[t])
+    got = lib.kzg_check_open_cosets(cs, values, proofs, n, 1, V["head"], V["g2_xl"], seed=SEED, locate=True)
+    assert got == lib.kzg_check_open_all(cs, values, proofs, n, V["g2_xl"], seed=SEED, locate=True)
+    assert got["ok"] == 0 and got["first_failing"] == t and got["count"] == batch * n, got
+
+
+def test_second_trip_of_the_transposed_load(lib, oracle, tmp_path):
+    """(n, l, batch) = (2^16, 64, 5) by the device producers: 5120 cells, 327,680 values, so the 1024 workgroups of 4 cells of the open-cosets form of the
+    coefficient kernel take a second trip through their transposed load.  Device against twin, field for field, with padding between the polynomials;
+    then a false value in cell 4097 (its last point) and in the last cell, each located exactly."""
+    n, l, batch = 1 << 16, 64, 5
+    V = device_world(lib, oracle, tmp_path, n, l, batch)
+    m = n // l
+    buf, stride = padded(oracle, V, 5)
+    got, want = both_cosets(lib, V, values=buf, stride=stride)
+    assert got["ok"] == 1 and got == want and scalars(got) == honest(batch * m), (got, want)
+    for t, j in ((4097, l - 1), (batch * m - 1, 0)):
+        b, k = t // m, t % m
+        false = buf.copy()
+        false[b * stride + k + m * j] = plus_one(oracle, false[b * stride + k + m * j])
+        got, want = both_cosets(lib, V, values=false, stride=stride, locate=True)
+        assert got == want and got["ok"] == 0 and got["first_failing"] == t, (t, got, want)
 
 
 def counted(lib, run, keys):

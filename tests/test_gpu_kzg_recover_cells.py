@@ -5,7 +5,8 @@ tests/test_kzg_recover_cells_host.py.  Shapes, with m = n / l cells and mu of th
   k_recover_vanish runs G = min(64, 2^18 / m) lanes per cell index and 256 threads per workgroup: m = 2 (half a workgroup), 4 (one), 8 (two) at G = 64;
   G = 64, 32, 16, 8, 4 at m = 2^12 .. 2^16 -- every width the bound m <= 2^16 leaves (G = 1 and 2 would need m >= 2^17);
   its LDS tile holds T = 256 roots (BbGpu.RECOVER_TILE): mu = T - 1, T, T + 1, 2 T + 1 at m = 1024, and mu = 0 and 1;
-  l = 1 .. 64 at n = 64 l for the scatter's and the divide's index arithmetic; batch 1, 3 and 64 at n = 256; one larger shape, (2^16, 64), half missing.
+  l = 1 .. 64 at n = 64 l for the scatter's and the divide's index arithmetic; batch 1, 3 and 64 at n = 256; one larger shape, (2^16, 64), half missing;
+  k_recover_tail runs at most 1024 workgroups of 256: (2^19, 64) takes it through a second trip, with extra coefficients whose index the report must name.
 Then altered cells, a round trip through bbgpu_kzg_open_cosets_device and bbgpu_kzg_check_open_cosets, and the error contract under injected failures of
 the four host-side funnels (no failure is provoked on the device)."""
 import numpy as np
@@ -18,6 +19,7 @@ KINDS = ("alloc", "h2d", "d2h", "launch")
 KEYS = {"alloc": "alloc_calls", "h2d": "h2d_calls", "d2h": "d2h_calls", "launch": "launch_checks"}
 FAR = 1 << 62
 T = 256
+TAIL = 1 << 18  # KZG_RECOVER_TAIL_MAX_BLOCKS = 1024 workgroups of 256: coefficient TAIL + i is thread i's second
 # the funnels one warm call at (n, l) = (256, 4) with the transforms read back passes (include/bbgpu.h): allocations -- the cell lists, z and z', the values,
 # the findings, the copy the forward transform works in; uploads -- the lists, the findings' start, the values; read-backs -- the findings, the transforms;
 # launch checks -- k_recover_roots with k_recover_vanish, the batch inversion's two scans and its product, k_recover_scatter, four transforms, k_recover_divide, k_recover_tail
@@ -111,6 +113,59 @@ def test_a_larger_shape(lib):
     """(2^16, 64): 1024 cells, every even one missing, degree bound n / 2"""
     n, l = 1 << 16, 64
     agree(lib, n, l, n // 2, list(range(0, n // l, 2)))
+
+
+@pytest.fixture(scope="module")
+def big(lib, oracle):
+    """(n, l) = (2^19, 64), batch 2, degree bound n / 4, 100 of the 8192 cells missing: polynomials and transforms by the device (bbgpu_ntt_device, which
+    tests/test_gpu_ntt_sizes.py ties to the oracle), the cells, the listed values per polynomial.  Made once, never written to."""
+    from tests.test_gpu_kzg_recover_each import cell_values, polynomials, split
+    n, l, mu = 1 << 19, 64, 100
+    coeffs, values = polynomials(lib, oracle, n, n // 4, 2, seed=7)
+    cells = split(n // l, mu, 70)[1]
+    return dict(n=n, l=l, d=n // 4, mu=mu, coeffs=coeffs, values=values, cells=cells, listed=[cell_values(values[b], l, cells) for b in range(2)])
+
+
+def transforms_of(lib, coeffs):
+    import torch
+    t = dev(coeffs)
+    lib.ntt_device(t.data_ptr(), coeffs.shape[0], "fft")
+    torch.cuda.synchronize()
+    return t.cpu().numpy().view(np.uint64).reshape(-1, 4)
+
+
+def test_the_tail_past_its_grid(lib, big):
+    """n = 2^19: the 1024 workgroups of 256 of k_recover_tail take a second trip.  Device against twin bit for bit (with mu = 100 the twin's products are
+    few), the coefficients against the polynomials the cells were made from, the transforms against bbgpu_ntt_device's"""
+    n, l, d = big["n"], big["l"], big["d"]
+    (got, got_v, got_rep), (want, want_v, want_rep) = both(lib, n, l, d, big["cells"], np.concatenate(big["listed"]), batch=2, pad=PAD)
+    assert np.array_equal(got, want) and np.array_equal(got_v, want_v)
+    assert got_rep == want_rep == dict(consistent=1, first_bad_poly=0, first_bad_coeff=0, missing=big["mu"])
+    assert np.array_equal(got.reshape(2, n + PAD, 4)[:, :n], big["coeffs"]) and np.array_equal(got_v, big["values"])
+
+
+# coefficients of polynomial 1 beyond the degree bound 2^17 and below the (8192 - 100) x 64 values supplied: the cells then belong to a polynomial of
+# degree below the number of values, which is recovered exactly, and the report names its first coefficient at or beyond the bound
+EXTRA = {"last_of_trip_one": [TAIL - 1], "first_of_trip_two": [TAIL], "last_admissible": [(8192 - 100) * 64 - 1], "one_in_each_trip": [TAIL + 3, TAIL - 7]}
+
+
+@pytest.mark.parametrize("where", sorted(EXTRA))
+def test_the_tail_names_the_first_extra_coefficient(lib, big, where):
+    import torch
+    from tests.test_gpu_kzg_recover_each import cell_values
+    n, l, d, cells = big["n"], big["l"], big["d"], big["cells"]
+    assert all(d <= j < len(cells) * l for j in EXTRA[where])
+    c1 = big["coeffs"][1].copy()
+    for j in EXTRA[where]:
+        c1[j] = memory([0xE17A + j])[0]
+    v1 = transforms_of(lib, c1)
+    d_out = dev(coefficient_buffer(2, n + PAD))
+    got_v, rep = lib.kzg_recover_cells(cells, np.concatenate([big["listed"][0], cell_values(v1, l, cells)]), n, l, d, d_out.data_ptr(), batch=2, stride=n + PAD)
+    torch.cuda.synchronize()
+    rows = d_out.cpu().numpy().view(np.uint64).reshape(2, n + PAD, 4)
+    assert rep == dict(consistent=0, first_bad_poly=1, first_bad_coeff=min(EXTRA[where]), missing=big["mu"])
+    assert np.array_equal(rows[0, :n], big["coeffs"][0]) and np.array_equal(rows[1, :n], c1)
+    assert np.array_equal(got_v[0], big["values"][0]) and np.array_equal(got_v[1], v1)
 
 
 def test_one_altered_value_among_redundant_cells(lib):

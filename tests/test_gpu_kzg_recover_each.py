@@ -6,6 +6,8 @@ level, k_each_powers, k_each_gather, k_each_scatter, k_each_divide, k_each_tail)
   against bbgpu_kzg_recover_cells bit for bit where every polynomial holds the same set;
   beyond that entry's 2^16 cells, where no twin is affordable, against the polynomials the cells were made from (values by bbgpu_ntt_device, which
     tests/test_gpu_ntt_sizes.py ties to the oracle), and once against the twin with few cells missing;
+  past the grid of k_each_tail (1024 workgroups of 256) at n = 2^19 and 2^20, with extra coefficients whose index the report must name exactly, and at
+    batch x M = 2^22 roots, where the transforms of the first tree level are handed over in two chunks;
   a round trip through bbgpu_kzg_open_cosets_device and bbgpu_kzg_check_open_cosets; and the error contract under injected failures of the four host-side
   funnels (no failure is provoked on the device).  The twin itself is held to plain-integer interpolation by tests/test_kzg_recover_each_host.py."""
 import numpy as np
@@ -18,6 +20,7 @@ pytestmark = pytest.mark.gpu
 KINDS = ("alloc", "h2d", "d2h", "launch")
 KEYS = {"alloc": "alloc_calls", "h2d": "h2d_calls", "d2h": "d2h_calls", "launch": "launch_checks"}
 FAR = 1 << 62
+TAIL = 1 << 18  # KZG_RECOVER_TAIL_MAX_BLOCKS = 1024 workgroups of 256: coefficient TAIL + i is thread i's second
 # the funnels one warm call passes with the transforms read back (include/bbgpu.h).  Allocations: the lists, the tree, z with z' and the power table, the
 # values, the findings, the copy the forward transform works in; uploads: the lists, the findings' start, the values; read-backs: the findings, the
 # transforms.  Launch checks at (256, 4), where 64 cells make one leaf per polynomial and no level: k_each_leaves, k_each_powers with k_each_gather, the
@@ -160,6 +163,97 @@ def test_device_equals_twin_beyond_the_cell_limit(lib, oracle):
     cells = [split(n, mu, 30 + b)[1] for b, mu in enumerate(mus)]
     got, want = both(lib, n, l, d, cells, [cell_values(values[b], l, c) for b, c in enumerate(cells)])
     assert same(got, want) and np.array_equal(got[0].reshape(2, n, 4), coeffs) and got[2]["consistent"] == 1 and got[2]["max_missing"] == mus[0]
+
+
+def transforms_of(lib, coeffs):
+    import torch
+    t = dev(coeffs)
+    lib.ntt_device(t.data_ptr(), coeffs.shape[0], "fft")
+    torch.cuda.synchronize()
+    return host(t)
+
+
+@pytest.fixture(scope="module")
+def big(lib, oracle):
+    """(n, l) = (2^19, 64), batch 2, degree bound n / 4, 100 and 37 of the 8192 cells missing.  Made once, never written to."""
+    n, l, mus = 1 << 19, 64, (100, 37)
+    coeffs, values = polynomials(lib, oracle, n, n // 4, 2, seed=5)
+    cells = [split(n // l, mu, 60 + b)[1] for b, mu in enumerate(mus)]
+    return dict(n=n, l=l, d=n // 4, mus=mus, coeffs=coeffs, values=values, cells=cells, vals=[cell_values(values[b], l, c) for b, c in enumerate(cells)])
+
+
+def test_the_tail_past_its_grid(lib, big):
+    """n = 2^19: the 1024 workgroups of 256 of k_each_tail take a second trip.  Device against twin bit for bit (few cells are missing, so the twin's
+    direct products are few), the coefficients against the original polynomials, the transforms against bbgpu_ntt_device's"""
+    n = big["n"]
+    got, want = both(lib, n, big["l"], big["d"], big["cells"], big["vals"], PAD)
+    assert same(got, want)
+    assert np.array_equal(got[0].reshape(2, n + PAD, 4)[:, :n], big["coeffs"]) and np.array_equal(got[1], big["values"])
+    assert got[2] == dict(consistent=1, first_bad_poly=0, first_bad_coeff=0, max_missing=100) and got[3].tolist() == [NONE, NONE]
+
+
+# coefficients of polynomial 1 beyond the degree bound 2^17 and below the (8192 - 37) x 64 values it supplies: its cells then belong to a polynomial of
+# degree below the number of values, which is recovered exactly, and the report names its first coefficient at or beyond the bound
+EXTRA = {"last_of_trip_one": [TAIL - 1], "first_of_trip_two": [TAIL], "last_admissible": [(8192 - 37) * 64 - 1], "one_in_each_trip": [TAIL + 3, TAIL - 7]}
+
+
+@pytest.mark.parametrize("where", sorted(EXTRA))
+def test_the_tail_names_the_first_extra_coefficient(lib, big, where):
+    import torch
+    n, l, d, cells = big["n"], big["l"], big["d"], big["cells"]
+    assert all(d <= j < len(cells[1]) * l for j in EXTRA[where])
+    c1 = big["coeffs"][1].copy()
+    for j in EXTRA[where]:
+        c1[j] = memory([0xE17A + j])[0]
+    v1 = transforms_of(lib, c1)
+    d_out = dev(coefficient_buffer(2, n + PAD))
+    got_v, rep, first = lib.kzg_recover_cells_each(cells, [big["vals"][0], cell_values(v1, l, cells[1])], n, l, d, d_out.data_ptr(), stride=n + PAD)
+    torch.cuda.synchronize()
+    rows = host(d_out).reshape(2, n + PAD, 4)
+    assert rep == dict(consistent=0, first_bad_poly=1, first_bad_coeff=min(EXTRA[where]), max_missing=100) and first.tolist() == [NONE, min(EXTRA[where])]
+    assert np.array_equal(rows[0, :n], big["coeffs"][0]) and np.array_equal(rows[1, :n], c1)
+    assert np.array_equal(got_v[0], big["values"][0]) and np.array_equal(got_v[1], v1)
+
+
+@pytest.fixture(scope="module")
+def huge(lib, oracle):
+    """(n, l, batch) = (2^20, 1, 4), degree bound n / 4, 2^19 + 1, 0, 65 and 1000 points missing: the common padded count is M = 2^20, so the first tree
+    level transforms batch x M / 64 = 65,536 slots of 128 points -- two chunks of the 32768 that recover_each_ntt (capi.hip) hands over at a time.  Made
+    once, never written to."""
+    n, mus = 1 << 20, ((1 << 19) + 1, 0, 65, 1000)
+    coeffs, values = polynomials(lib, oracle, n, n // 4, 4, seed=6)
+    cells = [split(n, mu, 80 + b)[1] for b, mu in enumerate(mus)]
+    return dict(n=n, d=n // 4, mus=mus, coeffs=coeffs, values=values, cells=cells, vals=[cell_values(values[b], 1, c) for b, c in enumerate(cells)])
+
+
+def test_the_chunk_loop_of_the_tree_transforms(lib, huge):
+    """batch x M = 2^22: no twin at this size (its direct products would be 2^39).  The recovered coefficients are the original polynomials, all four in
+    full, the transforms bbgpu_ntt_device's, the report consistent with max_missing = 2^19 + 1"""
+    import torch
+    n = huge["n"]
+    d_out = dev(np.zeros((4 * n, 4), dtype=np.uint64))
+    got_v, rep, first = lib.kzg_recover_cells_each(huge["cells"], huge["vals"], n, 1, huge["d"], d_out.data_ptr())
+    torch.cuda.synchronize()
+    assert rep == dict(consistent=1, first_bad_poly=0, first_bad_coeff=0, max_missing=(1 << 19) + 1) and first.tolist() == [NONE] * 4
+    assert np.array_equal(host(d_out).reshape(4, n, 4), huge["coeffs"]) and np.array_equal(got_v, huge["values"])
+
+
+def test_the_fourth_trip_of_the_tail(lib, huge):
+    """the same call with an extra coefficient of polynomial 2 at 3 x 2^18 + 5 (k_each_tail's fourth trip at n = 2^20) and one of polynomial 3 at 2^18,
+    the degree bound itself: the first findings per polynomial, and the report names polynomial 2"""
+    import torch
+    n, extra = huge["n"], {2: 3 * TAIL + 5, 3: TAIL}
+    coeffs, vals = huge["coeffs"].copy(), list(huge["vals"])
+    for b, j in extra.items():
+        assert huge["d"] <= j < len(huge["cells"][b])
+        coeffs[b, j] = memory([0xE17A + j])[0]
+        vals[b] = cell_values(transforms_of(lib, coeffs[b]), 1, huge["cells"][b])
+    d_out = dev(np.zeros((4 * n, 4), dtype=np.uint64))
+    _, rep, first = lib.kzg_recover_cells_each(huge["cells"], vals, n, 1, huge["d"], d_out.data_ptr(), want_values=False)
+    torch.cuda.synchronize()
+    assert rep == dict(consistent=0, first_bad_poly=2, first_bad_coeff=extra[2], max_missing=(1 << 19) + 1)
+    assert first.tolist() == [NONE, NONE, extra[2], extra[3]]
+    assert np.array_equal(host(d_out).reshape(4, n, 4), coeffs)  # polynomials 0 and 1 the originals, 2 and 3 with their extra terms
 
 
 def test_round_trip_through_the_producer_and_the_checker(lib, oracle, tmp_path):

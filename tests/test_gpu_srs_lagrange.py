@@ -2,7 +2,7 @@
 butterfly per lane and stage on projective points, the normalisation that counts infinities), the export kernel, the registration of the new table.  Every
 exported table is compared bit for bit with bbgpu_host_srs_lagrange's -- itself held to the definition by tests/test_srs_lagrange_host.py -- and the two
 reports field for field.  Sizes: n = 2 (one butterfly), 4, 8 (a partial wave), 64, 128 (exactly one wave of butterflies), 256 (two workgroups), 1024 (the
-first size with window tables), 4096 (twelve stages); 2^14 through the MSM identity only."""
+first size with window tables), 4096 (twelve stages); 2^14 and 2^20 (past the grid of the finish kernel) through the MSM identity only."""
 import numpy as np
 import pytest
 
@@ -20,6 +20,7 @@ FAR = 1 << 62
 WARM = {(256, True): dict(alloc_calls=3, h2d_calls=1, d2h_calls=3, launch_checks=3), (256, False): dict(alloc_calls=2, h2d_calls=1, d2h_calls=2, launch_checks=2),
         (1024, True): dict(alloc_calls=4, h2d_calls=1, d2h_calls=3, launch_checks=4), (1024, False): dict(alloc_calls=3, h2d_calls=1, d2h_calls=2, launch_checks=3)}
 BIG = 1 << 14
+HUGE = 1 << 20  # k_lagrange_finish runs 2048 workgroups of 256: rows from 2^19 on are a thread's second
 
 
 @pytest.fixture(scope="module")
@@ -65,24 +66,47 @@ def test_host_parity(lib, world, n):
     assert lib.fault_stats()["slots_pending"] == 0
 
 
-@pytest.mark.parametrize("n", [4096, BIG])
+@pytest.mark.parametrize("n", [4096, BIG, HUGE])
 def test_the_handle_commits_to_values(lib, oracle, world, n):
-    """sum_i v_i L_i over the new handle == sum_j ifft(v)_j P_j over the input handle, both by the device MSM; the input handle is untouched"""
+    """sum_i v_i L_i over the new handle == sum_j ifft(v)_j P_j over the input handle, both by the device MSM; the input handle is untouched.  Random v
+    make every output row count: at 2^20 rows (an input handle of its own) that includes the rows the finish kernel writes in its second trip."""
     import torch
-    v = oracle.random_scalars(0x7A61 + n, n)
-    c = lib.ntt(aligned_copy(v), "ifft")
-    dv, dc = torch.from_numpy(v.view(np.int64)).cuda(), torch.from_numpy(c.view(np.int64)).cuda()
-    h, table, _ = lib.srs_lagrange(world["h"], n, want_host_table=(n == 4096))
+    source = world["h"] if n <= BIG else lib.srs_generate(secret_x(oracle), n)
     try:
-        assert lib.srs_has_window_tables(h)
-        got = lib.msm_device(h, dv.data_ptr(), n)[:8]
-        assert np.array_equal(got, lib.msm_device(world["h"], dc.data_ptr(), n)[:8])
-        if n == 4096:
-            assert np.array_equal(got, oracle.msm_affine(v, aligned_copy(table), n)[:8])
-            assert np.array_equal(lib.pippenger(v, table, n)[:8], got)  # the host table is the address key of the new handle
+        v = oracle.random_scalars(0x7A61 + n, n)
+        c = lib.ntt(aligned_copy(v), "ifft")
+        dv, dc = torch.from_numpy(v.view(np.int64)).cuda(), torch.from_numpy(c.view(np.int64)).cuda()
+        h, table, rep = lib.srs_lagrange(source, n, want_host_table=(n == 4096))
+        try:
+            assert whole(rep) == dict(n=n, bad_points=0, first_bad_point=NONE, infinity_rows=0, first_infinity_row=NONE)
+            assert lib.srs_has_window_tables(h)
+            got = lib.msm_device(h, dv.data_ptr(), n)[:8]
+            assert np.array_equal(got, lib.msm_device(source, dc.data_ptr(), n)[:8])
+            if n == 4096:
+                assert np.array_equal(got, oracle.msm_affine(v, aligned_copy(table), n)[:8])
+                assert np.array_equal(lib.pippenger(v, table, n)[:8], got)  # the host table is the address key of the new handle
+        finally:
+            lib.srs_release(h)
     finally:
-        lib.srs_release(h)
+        if n > BIG:
+            lib.srs_release(source)
     assert lib.fault_stats()["slots_pending"] == 0
+
+
+def test_the_string_of_the_secret_one_at_two_to_the_twenty(lib, oracle):
+    """P_0 .. P_(n-1) all G (generated under the secret 1): every output row but row 0 is at infinity.  The refusal's report is the sum of the counts of
+    both trips of the finish kernel's 2^19 threads, and a minimum that lives in the first"""
+    from barretenberg_amd import BbGpuError
+    from oracle.pyoracle import FR
+    h0 = lib.srs_generate(oracle.const(FR, "one"), HUGE)
+    try:
+        live, allocations = lib.srs_cache_stats()[0], lib.fault_stats()["live_allocations"]
+        with pytest.raises(BbGpuError, match=" -3:.*row 1 ") as err:
+            lib.srs_lagrange(h0, HUGE)
+        assert whole(err.value.report) == dict(n=HUGE, bad_points=0, first_bad_point=NONE, infinity_rows=HUGE - 1, first_infinity_row=1)
+        assert lib.srs_cache_stats()[0] == live and lib.fault_stats()["live_allocations"] == allocations
+    finally:
+        lib.srs_release(h0)
 
 
 def special_tables(oracle, honest):
