@@ -74,6 +74,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_kzg_check_last_timing", "bbgpu_kzg_check_cells", "bbgpu_kzg_check_open_cosets", "bbgpu_host_kzg_check_cells",
     "bbgpu_host_kzg_check_open_cosets", "bbgpu_host_kzg_cells_key_check", "bbgpu_kzg_recover_cells", "bbgpu_host_kzg_recover_cells",
     "bbgpu_kzg_recover_cells_each", "bbgpu_host_kzg_recover_cells_each",
+    "bbgpu_g1_ntt", "bbgpu_host_g1_ntt", "bbgpu_g1_recover", "bbgpu_host_g1_recover", "bbgpu_g1_set_stage_mapping",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -191,6 +192,14 @@ class KzgCheckReport(C.Structure):
 class KzgRecoverReport(C.Structure):
     """bbgpu_kzg_recover_report (include/bbgpu.h)"""
     _fields_ = [("consistent", C.c_uint32), ("first_bad_poly", C.c_uint32), ("first_bad_coeff", C.c_uint64), ("missing", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class G1RecoverReport(C.Structure):
+    """bbgpu_g1_recover_report (include/bbgpu.h)"""
+    _fields_ = [("consistent", C.c_uint32), ("first_bad_column", C.c_uint32), ("first_bad_coeff", C.c_uint64), ("missing", C.c_uint64)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -741,6 +750,65 @@ class BbGpu:
                                                              int(degree_bound), batch, _ptr(coeffs), stride, _ptr(vals) if want_values else None, _ptr(first_bad),
                                                              C.byref(rep)))
         return coeffs, vals, rep.as_dict(), first_bad
+
+    # ---- columns of curve points: transforms and erasure decoding  (bbgpu_g1_ntt, bbgpu_g1_recover and the host twins) ----
+    @staticmethod
+    def _g1_ntt_args(points, n, batch, out):
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        if points.shape[0] < max(int(batch), 1) * max(int(n), 1):  # the library would read past the end
+            raise ValueError("g1_ntt: %d points for batch %d of %d" % (points.shape[0], batch, n))
+        if out is None:
+            out = np.zeros((max(int(batch), 1), max(int(n), 1), 8), dtype=np.uint64)
+        return points, out
+
+    def g1_ntt(self, points, n, kind="fft", batch=1, stream=None, out=None):
+        """bbgpu_g1_ntt: `batch` columns of n affine points (points (batch, n, 8) on the host, the reference's memory format, infinity as its flag) ->
+        (batch, n, 8) their transforms, "fft" or "ifft" -- `out` when given, which may be `points` itself"""
+        points, out = self._g1_ntt_args(points, n, batch, out)
+        self.lib.bbgpu_g1_ntt.argtypes = [u64p, u64p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        self._chk(self.lib.bbgpu_g1_ntt(_ptr(points), _ptr(out), int(n), int(batch), NTT_KINDS[kind] if isinstance(kind, str) else int(kind), stream or 0))
+        return out
+
+    def host_g1_ntt(self, points, n, kind="fft", batch=1, out=None):
+        """bbgpu_host_g1_ntt: the same on the host"""
+        points, out = self._g1_ntt_args(points, n, batch, out)
+        self.lib.bbgpu_host_g1_ntt.argtypes = [u64p, u64p, C.c_size_t, C.c_int, C.c_int]
+        self._chk(self.lib.bbgpu_host_g1_ntt(_ptr(points), _ptr(out), int(n), int(batch), NTT_KINDS[kind] if isinstance(kind, str) else int(kind)))
+        return out
+
+    @staticmethod
+    def _g1_recover_args(row, points, n, batch, out):
+        row = np.ascontiguousarray(row, dtype=np.uint32).reshape(-1)
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        if points.shape[0] < max(int(batch), 1) * row.shape[0]:  # the library would read past the end
+            raise ValueError("g1_recover: %d points for batch %d of %d rows" % (points.shape[0], batch, row.shape[0]))
+        if out is None:
+            out = np.zeros((max(int(batch), 1), max(int(n), 1), 8), dtype=np.uint64)
+        return row, points, out, row.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def g1_recover(self, row, points, n, degree_bound, batch=1, stream=None, out=None):
+        """bbgpu_g1_recover: `batch` columns of n points, each a codeword of degree < degree_bound, from the same listed rows (row: distinct indices below n,
+        any order; points (batch, count, 8): column b, listed row t, on the host) -> ((batch, n, 8) all n points of every column -- `out` when given --,
+        the report as a dict)"""
+        row, points, out, rp = self._g1_recover_args(row, points, n, batch, out)
+        rep = G1RecoverReport()
+        self.lib.bbgpu_g1_recover.argtypes = [C.POINTER(C.c_uint32), C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, C.POINTER(G1RecoverReport),
+                                              C.c_void_p]
+        self._chk(self.lib.bbgpu_g1_recover(rp, row.shape[0], _ptr(points), int(n), int(degree_bound), int(batch), _ptr(out), C.byref(rep), stream or 0))
+        return out, rep.as_dict()
+
+    def host_g1_recover(self, row, points, n, degree_bound, batch=1, out=None):
+        """bbgpu_host_g1_recover: the same on the host"""
+        row, points, out, rp = self._g1_recover_args(row, points, n, batch, out)
+        rep = G1RecoverReport()
+        self.lib.bbgpu_host_g1_recover.argtypes = [C.POINTER(C.c_uint32), C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, C.POINTER(G1RecoverReport)]
+        self._chk(self.lib.bbgpu_host_g1_recover(rp, row.shape[0], _ptr(points), int(n), int(degree_bound), int(batch), _ptr(out), C.byref(rep)))
+        return out, rep.as_dict()
+
+    def g1_set_stage_mapping(self, mapping):
+        """bbgpu_g1_set_stage_mapping: 0 the library's choice of stage kernel for g1_ntt and g1_recover, 1 k_lagrange_stage and 2 k_g1_stage_cols for every
+        shape (tools/g1_recover_bench.py)"""
+        self._chk(self.lib.bbgpu_g1_set_stage_mapping(int(mapping)))
 
     # ---- do these openings hold?  (bbgpu_kzg_check_openings, bbgpu_kzg_check_open_all and the host twins) ----
     def _kzg_check_openings(self, fn, commitments, z, y, proofs, g2_x, which, seed, locate):

@@ -39,6 +39,7 @@
 #include "host_kzg_open_cosets.hpp"
 #include "host_kzg_recover_cells.hpp"
 #include "host_kzg_recover_each.hpp"
+#include "host_g1_recover.hpp"
 #include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
@@ -4297,6 +4298,174 @@ int bbgpu_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32_t* c
         HIPCHK(hipEventElapsedTime(&ctx().last.ms[1], ev.e[2], ev.e[3]));
         HIPCHK(hipEventElapsedTime(&ctx().last.ms[2], ev.e[3], ev.e[4]));
         if (values_out) HIPCHK(hipEventElapsedTime(&ctx().last.ms[3], ev.e[4], ev.e[5]));
+    }
+    return BBGPU_OK;
+}
+
+/* ---- transforms and erasure decoding on columns of curve points (host_g1_recover.hpp, g1_recover.hip) ---- */
+static int g_g1_stage_mapping = 0; // bbgpu_g1_set_stage_mapping: 0 the dispatch below, 1 and 2 one kernel for every shape (the bench's comparison)
+// Which stage kernel runs the transforms of a call: k_g1_stage_cols where a column has fewer butterflies than a wave has lanes (n <= 64) -- the shapes at
+// which k_lagrange_stage, one column per blockIdx.y, leaves lanes idle and launches a workgroup per column --, k_lagrange_stage from n = 128 on, where every
+// wave of either mapping is full and profiles/g1_recover.txt shows no median lower by more than the legs' full range.
+static int g1_transform_dispatch(uint32_t* d_scratch, int log2n, int batch, const host::Fr& root, hipStream_t st)
+{
+    const Limbs9 r = host::limbs_m261(root);
+    const bool cols = g_g1_stage_mapping == 2 || (g_g1_stage_mapping == 0 && log2n <= 6);
+    return cols ? g1_cols_transform(d_scratch, log2n, batch, r.d, st) : g1_cols_transform_rows(d_scratch, log2n, batch, r.d, st);
+}
+int bbgpu_g1_set_stage_mapping(int mapping)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (mapping < 0 || mapping > 2) return BBGPU_ERR_ARG;
+    g_g1_stage_mapping = mapping;
+    return BBGPU_OK;
+}
+
+int bbgpu_host_g1_ntt(const uint64_t* points, uint64_t* points_out, size_t n, int batch, int kind)
+{
+    char why[320];
+    int log2n = 0;
+    if (int rc = host::g1_ntt_verdict("host g1_ntt", points, points_out, n, batch, kind, &log2n, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    host::g1_ntt_host(points, points_out, log2n, batch, kind);
+    return BBGPU_OK;
+}
+
+int bbgpu_g1_ntt(const uint64_t* points, uint64_t* points_out, size_t n, int batch, int kind, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    char why[320];
+    int log2n = 0;
+    if (int rc = host::g1_ntt_verdict("g1_ntt", points, points_out, n, batch, kind, &log2n, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (int rc = ensure_init()) return rc;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const size_t total = (size_t)batch * n;
+    // the points, then the affine results | the scratch
+    DevBuf io, scratch;
+    HIPCHK(dev_malloc(&io.p, total * 64));
+    HIPCHK(dev_malloc(&scratch.p, total * 128));
+    if (int rc = host_to_device(io.p, points, total * 64, st)) return rc;
+    host::Fr winv, ninv;
+    host::srs_lagrange_constants(log2n, &winv, &ninv);
+    const bool inverse = kind == BBGPU_IFFT;
+    if (int rc = g1_cols_load(io.as<uint32_t>(), n, nullptr, nullptr, inverse ? ninv.d : nullptr, scratch.as<uint32_t>(), log2n, batch, st)) return rc;
+    if (int rc = g1_transform_dispatch(scratch.as<uint32_t>(), log2n, batch, inverse ? winv : host::fr_root_of_unity(log2n), st)) return rc;
+    if (int rc = g1_cols_finish(scratch.as<uint32_t>(), io.as<uint32_t>(), log2n, batch, st)) return rc;
+    return device_to_host_sync(points_out, io.p, total * 64, st);
+}
+
+int bbgpu_host_g1_recover(const uint32_t* row, size_t count, const uint64_t* points, size_t n, size_t degree_bound, int batch, uint64_t* points_out,
+                          bbgpu_g1_recover_report* report)
+{
+    host::KzgRecoverShape S;
+    char why[320];
+    int rc = host::g1_recover_verdict("host g1_recover", row, count, points, n, degree_bound, batch, points_out, report, &S, why, sizeof why);
+    if (rc == BBGPU_OK) rc = host::g1_recover_host(S, row, count, points, degree_bound, batch, points_out, report, why, sizeof why);
+    if (rc) set_error("%s", why);
+    return rc;
+}
+
+int bbgpu_g1_recover(const uint32_t* row, size_t count, const uint64_t* points, size_t n, size_t degree_bound, int batch, uint64_t* points_out,
+                     bbgpu_g1_recover_report* report, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    host::KzgRecoverShape S;
+    char why[320];
+    if (int rc = host::g1_recover_verdict("g1_recover", row, count, points, n, degree_bound, batch, points_out, report, &S, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (int rc = ensure_init()) return rc;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const size_t mu = S.mu, total = (size_t)batch * n;
+    const int lg = S.log2n;
+    struct Events { // the stage boundaries of bbgpu_last_timing, only made when timing is on
+        hipEvent_t e[7] = {};
+        ~Events()
+        {
+            for (hipEvent_t v : e)
+                if (v) (void)hipEventDestroy(v);
+        }
+    } ev;
+    const bool timed = ctx().timing != 0;
+    if (timed)
+        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
+    auto mark = [&](int k) -> int {
+        if (timed) HIPCHK(hipEventRecord(ev.e[k], st));
+        return BBGPU_OK;
+    };
+    // the place of every row in the list and the missing rows | z, z', the four scalar tables and the roots of the missing rows | the points | the
+    // findings | the two scratches (the first one takes the affine results at the end)
+    DevBuf lists, zt, in, find, scratch;
+    HIPCHK(dev_malloc(&lists.p, 2 * n * 4));
+    HIPCHK(dev_malloc(&zt.p, 6 * n * 32 + mu * sizeof(Limbs9)));
+    HIPCHK(dev_malloc(&in.p, (size_t)batch * count * 64));
+    HIPCHK(dev_malloc(&find.p, (size_t)batch * sizeof(RecoverFindings)));
+    HIPCHK(dev_malloc(&scratch.p, 2 * total * 128));
+    uint32_t *d_slot_of = lists.as<uint32_t>(), *d_missing = d_slot_of + n;
+    uint64_t *d_z = zt.as<uint64_t>(), *d_zc = d_z + 4 * n, *d_tabs = d_zc + 4 * n;
+    const uint64_t *d_kz = d_tabs, *d_kg = d_tabs + 4 * n, *d_kq = d_tabs + 8 * n, *d_kgi = d_tabs + 12 * n;
+    uint32_t* d_roots = reinterpret_cast<uint32_t*>(d_tabs + 16 * n);
+    uint32_t *A = scratch.as<uint32_t>(), *B = A + total * 32;
+    std::vector<uint32_t> both(2 * n, ~0u);
+    for (size_t t = 0; t < count; t++) both[row[t]] = (uint32_t)t;
+    std::copy(S.missing.begin(), S.missing.end(), both.begin() + (ptrdiff_t)n);
+    std::vector<RecoverFindings> found((size_t)batch, RecoverFindings{ ~0ull, ~0ull });
+    if (int rc = host_to_device(lists.p, both.data(), 2 * n * 4, st)) return rc;
+    if (int rc = host_to_device(find.p, found.data(), found.size() * sizeof(RecoverFindings), st)) return rc;
+    if (int rc = host_to_device(in.p, points, (size_t)batch * count * 64, st)) return rc;
+    host::Fr winv, ninv;
+    host::srs_lagrange_constants(lg, &winv, &ninv);
+    const host::Fr w = host::fr_root_of_unity(lg), g = host::fr_from_limbs(FrHostP::GEN5);
+    if (int rc = mark(0)) return rc;
+    if (int rc = kzg_recover_vanish(d_missing, mu, lg, 0, d_roots, d_z, d_zc, st)) return rc;
+    if (int rc = mark(1)) return rc;
+    if (int rc = bbgpu_fr_batch_invert_device(d_zc, n, hip_stream)) return rc; // z' is never zero: g^n != 1
+    if (int rc = g1_cols_scalars(d_z, d_zc, d_tabs, lg, host::limbs_m256(ninv).d, host::limbs_m261(g).d, host::limbs_m261(host::fr_inv(g)).d, st)) return rc;
+    if (int rc = mark(2)) return rc;
+    if (int rc = g1_cols_load(in.as<uint32_t>(), count, d_slot_of, d_kz, nullptr, A, lg, batch, st)) return rc;
+    if (int rc = g1_transform_dispatch(A, lg, batch, winv, st)) return rc;
+    if (int rc = mark(3)) return rc;
+    if (int rc = g1_cols_scale(A, B, d_kg, lg, batch, st)) return rc;
+    if (int rc = g1_transform_dispatch(B, lg, batch, w, st)) return rc;
+    if (int rc = g1_cols_scale(B, A, d_kq, lg, batch, st)) return rc;
+    if (int rc = g1_transform_dispatch(A, lg, batch, winv, st)) return rc;
+    if (int rc = g1_cols_scale(A, B, d_kgi, lg, batch, st)) return rc;
+    if (int rc = g1_cols_verdict(B, lg, batch, degree_bound, count, find.as<RecoverFindings>(), st)) return rc;
+    if (int rc = mark(4)) return rc;
+    if (int rc = g1_transform_dispatch(B, lg, batch, w, st)) return rc;
+    if (int rc = mark(6)) return rc;
+    if (int rc = g1_cols_finish(B, A, lg, batch, st)) return rc;
+    if (int rc = mark(5)) return rc;
+    if (int rc = device_to_host_sync(found.data(), find.p, found.size() * sizeof(RecoverFindings), st)) return rc;
+    std::vector<uint64_t> first_bad((size_t)batch), first_bug((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        first_bad[(size_t)b] = found[(size_t)b].first_bad;
+        first_bug[(size_t)b] = found[(size_t)b].first_bug;
+    }
+    // the verdict into a local first: nothing of the caller's host memory is written before the last copy has succeeded
+    bbgpu_g1_recover_report rep;
+    if (int rc = host::g1_recover_report_of("g1_recover", first_bad.data(), first_bug.data(), batch, mu, &rep, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (int rc = device_to_host_sync(points_out, A, total * 64, st)) return rc;
+    *report = rep;
+    if (timed) { // bbgpu_last_timing: 0 the vanishing values, 1 load and IFFT, 2 shift, FFT, divide, IFFT, unshift and verdict, 3 the last FFT and the finish,
+                 // 4 the finish alone (a part of 3)
+        ctx().last.count = 5;
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[4], ev.e[6], ev.e[5]));
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[0], ev.e[0], ev.e[1]));
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[1], ev.e[2], ev.e[3]));
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[2], ev.e[3], ev.e[4]));
+        HIPCHK(hipEventElapsedTime(&ctx().last.ms[3], ev.e[4], ev.e[5]));
     }
     return BBGPU_OK;
 }

@@ -1254,6 +1254,103 @@ int bbgpu_host_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32
                                       int batch, uint64_t* coeffs_out /* HOST, batch x stride_elems x 4 */, size_t stride_elems, uint64_t* values_out,
                                       uint64_t* first_bad_out, bbgpu_kzg_recover_each_report* report);
 
+/* ---- recover missing G1 points of a codeword  (transforms whose elements are curve points, batched over short columns; erasure decoding in the group) ------
+ * The three blocks above rebuild the FIELD side of a sampled 2-D layout.  Its GROUP side: k rows (polynomials) are Reed-Solomon-extended column-wise to
+ * R = 2 k rows over the size-R domain; commitment and every cell proof are linear in the polynomial, so for each column c the row commitments C_r and the
+ * cell proofs pi_(r, c), r < R, are a codeword whose symbols are curve points -- the values on the size-R domain of a "polynomial" of degree < k with G1
+ * coefficients.  bbgpu_g1_ntt transforms such columns and bbgpu_g1_recover decodes them from a subset of their rows, without the data: a producer gets the
+ * proofs of the R - k extension rows from those of the k it made, and a sampler that holds the commitments and proofs of some rows gets the rest.  The
+ * reference has no counterpart.
+ * Points are affine in the reference's memory format, 8 words, exactly as bbgpu_kzg_open_cosets_device writes them: coordinates Montgomery-256 and
+ * CANONICAL, infinity as bit 63 of y[3] with every other word zero.  Infinity is an ordinary input and an ordinary output, and every addition is complete:
+ * equal points, opposite points and infinity on either side are not errors.
+ * bbgpu_g1_ntt, `batch` columns of n points: forward out_i = sum_j rho^(i j) P_j with rho = fr_root_of_unity(log2 n), the root bbgpu_ntt uses; inverse the
+ * same with rho^-1, times n^-1.  points_out may alias points.  Refused with outputs untouched -- BBGPU_ERR_SIZE: n not a power of two, n < 2, n > 2^16,
+ * batch < 1, batch * n > 2^20; BBGPU_ERR_ARG: a null pointer, any kind but BBGPU_FFT and BBGPU_IFFT (there is no coset transform on points), a point off the
+ * curve or with a coordinate that is not canonical -- bbgpu_last_error() names the first such column and position.  The curve test runs on the HOST, in the
+ * verdict the device entry and the twin share (a few products per point on up to 16 threads), so every refusal comes before a device is bound.
+ * bbgpu_g1_recover, the decoder: the same `count` rows of every column are present -- a row that is missing lacks its commitment and all its proofs.  In
+ * the notation of the bbgpu_kzg_recover_cells block with l = 1 and m = n = R: K the mu = n - count missing rows, g the coset generator of BBGPU_COSET_FFT,
+ *   z_i = prod_{k in K} (rho^i - rho^k),   z'_i = prod_{k in K} (g rho^i - rho^k)       what k_recover_roots, k_recover_vanish and the batch inversion compute
+ * at coset 1, once per call for all columns (hence n <= BBGPU_KZG_RECOVER_MAX_CELLS).  Per column:
+ *   E_i = z_i * P_i on the present rows, infinity on the missing ones;   P = IFFT(E);   Q = FFT(g^j * P_j);   Q_i <- z'_i^-1 * Q_i;   D' = IFFT(Q);
+ *   D_j = g^-j * D'_j;   points_out = FFT(D): ALL n points of the column in natural order
+ * The verdict is exact, as in the field entry: the points are a codeword of degree < d iff coefficients [d, count) of every D are the point at infinity
+ * (the group has prime order: a coefficient is at infinity iff the scalar decoder's is zero).  With count == d it is vacuous and says 1.  An inconsistent
+ * column is still written and is a finding, not an error: the return value stays BBGPU_OK and the report names the first such column and its smallest
+ * coefficient index not at infinity.  A coefficient in [count, n) that is not at infinity is BBGPU_ERR_HIP with a text of its own: no input can cause it.
+ * Refused before a device is bound, outputs untouched -- BBGPU_ERR_SIZE: n not a power of two, n < 2, n > 2^16, degree_bound outside 1..n, count <
+ * degree_bound, count > n, batch < 1, batch * n > 2^20; BBGPU_ERR_ARG: a null pointer, a row index >= n, a row listed twice, a point off the curve or not
+ * canonical -- the message names the first offender.  Not here: per-column row sets, n > 2^16 (the product tree of kzg_recover_each.hip for the vanishing
+ * values), device-resident inputs and outputs, G2.
+ * The kernels (csrc/g1_recover.hip).  A stage launch that does not fill the chip costs about the 0.9 ms one wave needs for its ladder, so a small decode
+ * costs its count of ladder-bearing launches, not its count of points: 4 + 4 log2 n.
+ *   k_g1_stage_cols  (n <= 64; from n = 128 on the drivers launch k_lagrange_stage, see the cost below) the butterfly of csrc/g1_stage.hpp (butterfly_slots<3>, unchanged) with (position, column, group) flattened into one lane index,
+ *                    position-major: k_lagrange_stage takes the column from blockIdx.y and one lane per butterfly -- at R = 8 four live lanes in a wave of
+ *                    64 and one wave per column.  Here consecutive lanes take consecutive (column, group) pairs at ONE position whenever batch x groups >=
+ *                    64, so the twiddle and the skip of the ladder at position 0 stay wave-uniform; below that, consecutive positions as the existing
+ *                    kernel.  Both entries use it; the existing group entries keep theirs and are not moved here
+ *   four fused ladder passes, each "slot <- scalar * point" with the bit reversal of the NEXT transform folded in, so that no transform has a load or a
+ *                    scale launch of its own: k_g1_load (n^-1 z_i) * P_i -> slot bitrev(i), infinity for missing rows; k_g1_scale three times: the coset
+ *                    shift g^j, the division n^-1 / z'_i, the unshift g^-j.  A permuting pass in place is a race between a slot and its bit-reversed
+ *                    partner: a call owns a SECOND SCRATCH and every pass reads one and writes the other (2 x 128 bytes per point).  The per-index
+ *                    scalars come from four device tables k_g1_scalars makes once per call, plain canonical integers for the ladder
+ *   k_g1_verdict     one workgroup per column between the unshift and the last transform (which consumes D in place): a min-reduction on chip over ZZ
+ *                    != 0 in [d, count) and in [count, n), written without any atomic
+ *   k_g1_finish      the affine form of every slot, one Fermat inversion per point as k_lagrange_finish and k_open_cosets_finish; a batch inversion over
+ *                    the batch x n Z-coordinates was NOT built -- see the cost of the finish below
+ * Resources (hipcc -Rpass-analysis=kernel-resource-usage, VGPRs / AGPRs / LDS bytes / waves per SIMD): k_g1_stage_cols
+ * 231 / 0 / 0 / 2, k_g1_load 250 / 0 / 0 / 2, k_g1_scale 229 / 0 / 0 / 2 (the ladder's table fills the register file, as in k_lagrange_stage: 231), k_g1_scalars
+ * 50 / 0 / 0 / 8, k_g1_verdict 16 / 0 / 32 / 8, k_g1_finish 75 / 0 / 0 / 6; no scratch and no spill in any.
+ * Both entries run on context 0 under the library mutex.  A warm bbgpu_g1_recover at (n, d, missing, batch) = (8, 4, 4, 3) passes five allocations (the
+ * lists; z, z', the tables and the roots; the points; the findings; the two scratches), three uploads (the lists, the findings' start, the points), two
+ * read-backs (the findings, the points) and fifteen launch checks (roots + vanish; the inversion's two scans and its product; the tables; the load; four
+ * transforms; three scale passes; the verdict; the finish); a warm bbgpu_g1_ntt two allocations, one upload, one read-back and three launch checks.  Every
+ * site failed once through bbgpu_fault_inject returns BBGPU_ERR_HIP, leaves nothing the call allocated live, and the next call is bit-exact
+ * (tests/test_gpu_g1_recover.py).  With bbgpu_set_timing(1), bbgpu_last_timing() of bbgpu_g1_recover: index 0 the vanishing values, 1 the load and the
+ * first inverse transform, 2 shift, forward, divide, inverse, unshift and verdict, 3 the final transform and the finish, 4 the finish alone (a part of 3).
+ * Cost on one MI355X (tools/g1_recover_bench.py, profiles/g1_recover.txt; wall ms per call, copies of the points across the link included, one process,
+ * medians of 9 alternating pairs).  (a) k_g1_stage_cols against the parent's mapping (k_lagrange_stage, the column in blockIdx.y), the same forward
+ * bbgpu_g1_ntt, new / old: (n, batch) = (8, 4096) 3.27 / 14.77; (64, 512) 6.34 / 7.53; (64, 8192) 22.07 / 40.04; (128, 256) 7.29 / 7.60; (128, 4096) 25.05 /
+ * 26.90; (512, 65) 9.56 / 9.36; (2^16, 1) 17.32 / 17.04.  By the rule of the open-cosets block -- a median lower by more than the full range (max - min)
+ * of either leg -- the new mapping wins (8, 4096) and (64, 8192), where the old one leaves lanes idle and launches a workgroup per column; at (64, 512) its
+ * median is lower but one outlier of 11.6 ms widens the range past the gap; from n = 128 on every wave of either mapping is full, the medians lie within
+ * 7 % of one another and inside the range, and at (2^16, 1) the two coincide as expected (1.6 %, the pool's +- 5 %).  So the drivers DISPATCH: k_g1_stage_cols
+ * for n <= 64, k_lagrange_stage from n = 128 on (bbgpu_g1_set_stage_mapping forces either, for the bench).  (b) bbgpu_g1_recover against 4 + 4 log2 n times
+ * the latency of one ladder-bearing launch, 1.28 ms in that run (the device time of k_g1_load with one ladder plus the one stage of n = 2, which is position 0
+ * and runs none, at (2, 1): an upper estimate, two launches): (n, batch, missing) = (8, 65, 4) 13.2 ms wall, 12.9 device, 0.63 times 16 x 1.28; (512, 65, 256)
+ * 37.0 wall, 36.0 device, 0.70 times; (4096, 16, 2048) 50.1 wall, 48.2 device, 0.72 times -- below one because stage 0 of every transform is position 0
+ * throughout and runs no ladder (4 log2 n launches carry one, not 4 + 4 log2 n), and because slots at infinity skip theirs (half the load's at these shapes).
+ * Nothing was tuned to that ratio.  Device times at (512, 65, 256): vanishing values 0.04, load + IFFT 8.4, shift .. verdict 19.3, FFT + finish 8.3.  The
+ * finish kernel alone (bbgpu_last_timing index 4, a part of 3) takes 0.16 to 0.19 ms at 520 to 65536 points, under 2 % of any call: that is why one Fermat
+ * inversion per point stayed and no batch inversion over the Z-coordinates was built.  (c) The alternative the decode replaces for a producer, at
+ * (512, 65, 256) with d = 256: 37.3 ms for the 256 extension rows' commitments and proofs beside 261.7 ms for 16 calls of bbgpu_kzg_open_cosets_device at
+ * (2^12, 64), batch 16, in the same process (which makes the proofs only, and needs the rows' data).  NOT timed: batch x n = 2^20, n = 2^16 in the decoder
+ * (2^16 x 2^15 pair products for the vanishing values), columns with few rows missing, the host's curve test on its own, the host twins.
+ * The host twins (csrc/host_g1_recover.hpp; plain loops over host_g1.hpp and g1_transform_host, a double-and-add per scalar, z and z' by direct
+ * products; no HIP call, no lock, re-entrant) have the same refusals, the same canonical outputs and the same report: affine results are unique, so device
+ * and twin agree bit for bit.  They are held to the scalar transform and the scalar decoder on multiples of the generator
+ * (tests/test_g1_recover_host.py). */
+typedef struct {
+    uint32_t consistent;       /* 1: every column has coefficients [d, count) all at infinity (vacuous when count == d) */
+    uint32_t first_bad_column; /* smallest b with a coefficient there that is not, else 0 */
+    uint64_t first_bad_coeff;  /* its smallest such index, else 0 */
+    uint64_t missing;          /* mu = n - count */
+} bbgpu_g1_recover_report;
+int bbgpu_g1_ntt(const uint64_t* points /* HOST, batch x n x 8 */, uint64_t* points_out /* HOST, batch x n x 8, may alias */, size_t n, int batch,
+                 int kind /* BBGPU_FFT or BBGPU_IFFT */, void* hip_stream);
+int bbgpu_host_g1_ntt(const uint64_t* points, uint64_t* points_out, size_t n, int batch, int kind);
+int bbgpu_g1_recover(const uint32_t* row /* count, distinct, each < n, any order */, size_t count,
+                     const uint64_t* points /* HOST, batch x count x 8: column b, listed row t */, size_t n, size_t degree_bound, int batch,
+                     uint64_t* points_out /* HOST, batch x n x 8: ALL n points of every column, natural order */, bbgpu_g1_recover_report* report,
+                     void* hip_stream);
+int bbgpu_host_g1_recover(const uint32_t* row, size_t count, const uint64_t* points, size_t n, size_t degree_bound, int batch, uint64_t* points_out,
+                          bbgpu_g1_recover_report* report);
+/* the stage kernel both entries launch: 0 the dispatch described above (the default), 1 k_lagrange_stage with the column in blockIdx.y for every shape
+ * (batch <= 65535, else BBGPU_ERR_SIZE from the entries), 2 k_g1_stage_cols for every shape -- for the comparison of tools/g1_recover_bench.py and the
+ * tests; results are bit-identical.  BBGPU_ERR_ARG for any other value */
+int bbgpu_g1_set_stage_mapping(int mapping);
+
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
  * per-proof part is what :55-355 computes -- six Keccak transcripts (challenge.hpp), the Lagrange evaluations (polynomial_arithmetic.cpp:594-626),
