@@ -70,6 +70,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_selftest_plonk_round",
     "bbgpu_kzg_open_all_setup", "bbgpu_kzg_open_all_release", "bbgpu_kzg_open_all_device", "bbgpu_host_kzg_open_all",
     "bbgpu_kzg_open_cosets_setup", "bbgpu_kzg_open_cosets_release", "bbgpu_kzg_open_cosets_device", "bbgpu_host_kzg_open_cosets",
+    "bbgpu_kzg_open_cosets_setup_bounded", "bbgpu_host_kzg_open_cosets_bounded",
     "bbgpu_kzg_check_openings", "bbgpu_kzg_check_open_all", "bbgpu_host_kzg_check_openings_batch", "bbgpu_host_kzg_check_open_all",
     "bbgpu_kzg_check_last_timing", "bbgpu_kzg_check_cells", "bbgpu_kzg_check_open_cosets", "bbgpu_host_kzg_check_cells",
     "bbgpu_host_kzg_check_open_cosets", "bbgpu_host_kzg_cells_key_check", "bbgpu_kzg_recover_cells", "bbgpu_host_kzg_recover_cells",
@@ -625,11 +626,15 @@ class BbGpu:
         return out
 
     # ---- a polynomial opened on every coset of its domain  (bbgpu_kzg_open_cosets_* and the host twin) ----
-    def kzg_open_cosets_setup(self, handle, n, coset):
+    def kzg_open_cosets_setup(self, handle, n, coset, degree_bound=None):
         """bbgpu_kzg_open_cosets_setup: per residue e < coset, DFT_(2n/coset) of the reversed rows e, e + coset, .. of a resident monomial table (rows
-        [0, n - coset) are read), kept on the device -> setup handle"""
-        self.lib.bbgpu_kzg_open_cosets_setup.argtypes = [C.c_int, C.c_size_t, C.c_size_t]
-        return self._chk(self.lib.bbgpu_kzg_open_cosets_setup(int(handle), int(n), int(coset)))
+        [0, n - coset) are read), kept on the device -> setup handle.  With degree_bound = d (bbgpu_kzg_open_cosets_setup_bounded): for polynomials of
+        degree < d, transforms of length 2d/coset over rows [0, d - coset) -- a table of d rows is enough"""
+        if degree_bound is None:
+            self.lib.bbgpu_kzg_open_cosets_setup.argtypes = [C.c_int, C.c_size_t, C.c_size_t]
+            return self._chk(self.lib.bbgpu_kzg_open_cosets_setup(int(handle), int(n), int(coset)))
+        self.lib.bbgpu_kzg_open_cosets_setup_bounded.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t]
+        return self._chk(self.lib.bbgpu_kzg_open_cosets_setup_bounded(int(handle), int(n), int(coset), int(degree_bound)))
 
     def kzg_open_cosets_release(self, setup):
         self.lib.bbgpu_kzg_open_cosets_release.argtypes = [C.c_int]
@@ -637,18 +642,23 @@ class BbGpu:
 
     def kzg_open_cosets_device(self, setup, d_coeffs, n, coset, batch=1, stride=None, stream=None, out=None):
         """bbgpu_kzg_open_cosets_device: `batch` polynomials in coefficient form on the device (stride elements apart) -> (batch, n / coset, 8): the affine
-        KZG proof of polynomial b on coset k = { omega^(k + (n / coset) j) }, infinity flagged in bit 63 of y[3]"""
+        KZG proof of polynomial b on coset k = { omega^(k + (n / coset) j) }, infinity flagged in bit 63 of y[3].  The stride is judged by the library alone:
+        over a setup with a degree bound d it may be as small as d (coefficients from d on are not read), so pass it -- the default is n"""
         out = np.zeros((max(int(batch), 1), max(int(n) // max(int(coset), 1), 1), 8), dtype=np.uint64) if out is None else out
         self.lib.bbgpu_kzg_open_cosets_device.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, u64p, C.c_void_p]
         self._chk(self.lib.bbgpu_kzg_open_cosets_device(int(setup), d_coeffs, n if stride is None else stride, batch, _ptr(out), stream or 0))
         return out
 
-    def host_kzg_open_cosets(self, table, n, coset, coeffs, batch=1, stride=None):
+    def host_kzg_open_cosets(self, table, n, coset, coeffs, batch=1, stride=None, degree_bound=None):
         """bbgpu_host_kzg_open_cosets: the same on the host, over the even entries of a (>= 2 (n - coset), 8) endo table; coeffs (batch * stride, 4) ->
-        (batch, n / coset, 8)"""
+        (batch, n / coset, 8).  With degree_bound = d (bbgpu_host_kzg_open_cosets_bounded): rows [0, d - coset) and coefficients [0, d) are read"""
         coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
         stride = coeffs.shape[0] // max(int(batch), 1) if stride is None else stride
         out = np.zeros((max(int(batch), 1), max(int(n) // max(int(coset), 1), 1), 8), dtype=np.uint64)
+        if degree_bound is not None:
+            self.lib.bbgpu_host_kzg_open_cosets_bounded.argtypes = [u64p, C.c_size_t, C.c_size_t, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p]
+            self._chk(self.lib.bbgpu_host_kzg_open_cosets_bounded(_ptr(table), int(n), int(coset), int(degree_bound), _ptr(coeffs), stride, batch, _ptr(out)))
+            return out
         self.lib.bbgpu_host_kzg_open_cosets.argtypes = [u64p, C.c_size_t, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p]
         self._chk(self.lib.bbgpu_host_kzg_open_cosets(_ptr(table), int(n), int(coset), _ptr(coeffs), stride, batch, _ptr(out)))
         return out

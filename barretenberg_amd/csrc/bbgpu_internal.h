@@ -142,11 +142,12 @@ int kzg_open_all_t(const uint64_t* d_coeffs, size_t stride_elems, int batch, siz
 int kzg_open_all_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scratch, size_t n, int log2n, int batch, const uint32_t c32[9], const uint32_t Winv[9],
                        const uint32_t omega[9], hipStream_t st, float* ms4 = nullptr);
 
-// kzg_open_cosets.hip: the proofs of a polynomial on every coset of its domain (bbgpu_kzg_open_cosets_setup, bbgpu_kzg_open_cosets_device)
-int kzg_open_cosets_string(const uint32_t* d_in, int log2n, int log2l, const uint32_t W_m261[9], uint32_t** d_S, hipStream_t st);
-int kzg_open_cosets_t(const uint64_t* d_coeffs, size_t stride_elems, int batch, int log2n, int log2l, uint64_t* d_t, hipStream_t st);
-int kzg_open_cosets_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scratch, int log2n, int log2l, int batch, const uint32_t c32[9], const uint32_t Winv[9],
-                          const uint32_t psi[9], hipStream_t st, float* ms4 = nullptr);
+// kzg_open_cosets.hip: the proofs of a polynomial on every coset of its domain (bbgpu_kzg_open_cosets_setup(_bounded), bbgpu_kzg_open_cosets_device); d =
+// 2^log2d is the degree bound of the setup, n without one
+int kzg_open_cosets_string(const uint32_t* d_in, int log2d, int log2l, const uint32_t W_m261[9], uint32_t** d_S, hipStream_t st);
+int kzg_open_cosets_t(const uint64_t* d_coeffs, size_t stride_elems, int batch, int log2d, int log2l, uint64_t* d_t, hipStream_t st);
+int kzg_open_cosets_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scratch, int log2n, int log2l, int log2d, int batch, const uint32_t c32[9],
+                          const uint32_t Winv[9], const uint32_t psi[9], hipStream_t st, float* ms4 = nullptr);
 
 // plonk_verify.hip: the device parts of a verify call (bbgpu_plonk_verify_batch, bbgpu_plonk_verify_multi) that are not an MSM
 struct VerifyDeviceBuffers {

@@ -1350,11 +1350,11 @@ void open_all_release(OpenAllSetup& o)
     o = OpenAllSetup();
 }
 
-// ---- setups of bbgpu_kzg_open_cosets_* (below): S^(e) = DFT_M(s^(e)), e < l, of one (string, n, l): l x M = 2 n scratch points, kept as the open-all setups
-// are, in a pool of their own.  Context 0, under g_mu.
+// ---- setups of bbgpu_kzg_open_cosets_* (below): S^(e) = DFT_M(s^(e)), e < l, of one (string, n, l, d), d the degree bound (n without one): l x M = 2 d
+// scratch points, kept as the open-all setups are, in a pool of their own.  Context 0, under g_mu.
 struct OpenCosetsSetup {
     bool live = false;
-    int log2n = 0, log2l = 0;
+    int log2n = 0, log2l = 0, log2d = 0;
     uint32_t* d_S = nullptr;
     size_t bytes = 0;
 };
@@ -2971,35 +2971,66 @@ static int open_cosets_n(const char* what, size_t n, size_t coset, int* log2n, i
     return BBGPU_OK;
 }
 
-int bbgpu_host_kzg_open_cosets(const uint64_t* points_endo_table, size_t n, size_t coset, const uint64_t* coeffs, size_t stride_elems, int batch,
-                               uint64_t* proofs_out)
+// the degree bound of a setup of (n, l)
+static int open_cosets_bound(const char* what, int log2n, int log2l, size_t degree_bound, int* log2d)
 {
-    int log2n, log2l;
+    if ((*log2d = host::kzg_open_cosets_bound_log2(log2n, log2l, degree_bound)) < 0) {
+        set_error("%s: the degree bound (%zu) must be a power of two between twice the coset size (%zu) and n = %zu", what, degree_bound, (size_t)2 << log2l,
+                  (size_t)1 << log2n);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
+// the sizes of one call over a setup of (n, d)
+static int open_cosets_sizes(const char* what, size_t n, size_t d, size_t stride_elems, int batch)
+{
+    if (!host::kzg_open_cosets_sizes_ok(n, d, stride_elems, batch)) {
+        set_error("%s: the stride (%zu) must be no smaller than %s = %zu and batch x 2 n (%d x %zu) at most 2^%d", what, stride_elems,
+                  d == n ? "n" : "the degree bound", d, batch, 2 * n, host::KZG_OPEN_ALL_MAX_SLOTS_LOG2);
+        return BBGPU_ERR_SIZE;
+    }
+    return BBGPU_OK;
+}
+
+int bbgpu_host_kzg_open_cosets_bounded(const uint64_t* points_endo_table, size_t n, size_t coset, size_t degree_bound, const uint64_t* coeffs, size_t stride_elems,
+                                       int batch, uint64_t* proofs_out)
+{
+    int log2n, log2l, log2d;
     if (int rc = open_cosets_n("host kzg_open_cosets", n, coset, &log2n, &log2l)) return rc;
+    if (int rc = open_cosets_bound("host kzg_open_cosets", log2n, log2l, degree_bound, &log2d)) return rc;
     if (int rc = open_all_batch("host kzg_open_cosets", batch)) return rc;
     if (!points_endo_table || !coeffs || !proofs_out) {
         set_error("host kzg_open_cosets: null table / coeffs / proofs");
         return BBGPU_ERR_ARG;
     }
-    if (int rc = open_all_sizes("host kzg_open_cosets", n, stride_elems, batch)) return rc;
+    if (int rc = open_cosets_sizes("host kzg_open_cosets", n, degree_bound, stride_elems, batch)) return rc;
     std::vector<host::Xyzz> S;
     uint64_t bad = 0;
-    if (host::kzg_open_cosets_setup_host(points_endo_table, log2n, log2l, S, &bad)) {
+    if (host::kzg_open_cosets_setup_bounded_host(points_endo_table, log2d, log2l, S, &bad)) {
         set_error("host kzg_open_cosets: row %llu is not on the curve", (unsigned long long)bad);
         return BBGPU_ERR_ARG;
     }
-    host::kzg_open_cosets_proofs_host(S, log2n, log2l, coeffs, stride_elems, batch, proofs_out);
+    host::kzg_open_cosets_proofs_bounded_host(S, log2n, log2l, log2d, coeffs, stride_elems, batch, proofs_out);
     return BBGPU_OK;
 }
 
-int bbgpu_kzg_open_cosets_setup(int srs_handle, size_t n, size_t coset)
+int bbgpu_host_kzg_open_cosets(const uint64_t* points_endo_table, size_t n, size_t coset, const uint64_t* coeffs, size_t stride_elems, int batch,
+                               uint64_t* proofs_out)
+{
+    int log2n, log2l;
+    if (int rc = open_cosets_n("host kzg_open_cosets", n, coset, &log2n, &log2l)) return rc; // (the bound of the call below is n: never refused)
+    return bbgpu_host_kzg_open_cosets_bounded(points_endo_table, n, coset, n, coeffs, stride_elems, batch, proofs_out);
+}
+
+int bbgpu_kzg_open_cosets_setup_bounded(int srs_handle, size_t n, size_t coset, size_t degree_bound)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     // argument errors before a device is bound: a handle can only exist once one is
-    int log2n, log2l;
+    int log2n, log2l, log2d;
     if (int rc = open_cosets_n("kzg_open_cosets_setup", n, coset, &log2n, &log2l)) return rc;
+    if (int rc = open_cosets_bound("kzg_open_cosets_setup", log2n, log2l, degree_bound, &log2d)) return rc;
     const SrsEntry* ep = nullptr;
-    if (int rc = srs_rows("kzg_open_cosets_setup", srs_handle, n, BBGPU_ERR_SIZE, &ep)) return rc;
+    if (int rc = srs_rows("kzg_open_cosets_setup", srs_handle, degree_bound, BBGPU_ERR_SIZE, &ep)) return rc; // d rows serve every n
     int slot = -1;
     for (int k = 0; k < BBGPU_KZG_OPEN_COSETS_MAX_SETUPS && slot < 0; k++)
         if (!g_open_cosets[k].live) slot = k;
@@ -3010,23 +3041,26 @@ int bbgpu_kzg_open_cosets_setup(int srs_handle, size_t n, size_t coset)
     if (int rc = ensure_init()) return rc;
     const uint32_t* d_in = ep->d_srs;
     const hipStream_t st = ctx().stream;
-    // the curve pass over the rows the strings read, [0, n - l)
+    // the curve pass over the rows the strings read, [0, d - l)
     uint64_t bad_points, first_bad_point;
-    if (int rc = curve_pass(d_in, n - coset, 1, &bad_points, &first_bad_point)) return rc;
+    if (int rc = curve_pass(d_in, degree_bound - coset, 1, &bad_points, &first_bad_point)) return rc;
     if (bad_points) {
         set_error("kzg_open_cosets_setup: row %llu is not on the curve (%llu such rows)", (unsigned long long)first_bad_point, (unsigned long long)bad_points);
         return BBGPU_ERR_ARG;
     }
-    const Limbs9 W = host::limbs_m261(host::fr_root_of_unity(log2n - log2l + 1));
+    const Limbs9 W = host::limbs_m261(host::fr_root_of_unity(log2d - log2l + 1));
     OpenCosetsSetup o;
-    if (int rc = kzg_open_cosets_string(d_in, log2n, log2l, W.d, &o.d_S, st)) return rc;
+    if (int rc = kzg_open_cosets_string(d_in, log2d, log2l, W.d, &o.d_S, st)) return rc;
     o.log2n = log2n;
     o.log2l = log2l;
-    o.bytes = 2 * n * 128;
+    o.log2d = log2d;
+    o.bytes = 2 * degree_bound * 128;
     o.live = true;
     g_open_cosets[slot] = o;
     return slot;
 }
+
+int bbgpu_kzg_open_cosets_setup(int srs_handle, size_t n, size_t coset) { return bbgpu_kzg_open_cosets_setup_bounded(srs_handle, n, coset, n); }
 
 int bbgpu_kzg_open_cosets_release(int setup)
 {
@@ -3052,16 +3086,17 @@ int bbgpu_kzg_open_cosets_device(int setup, const uint64_t* d_coeffs, size_t str
         return BBGPU_ERR_ARG;
     }
     const OpenCosetsSetup& o = g_open_cosets[setup];
-    const int log2M = o.log2n - o.log2l + 1;
-    const size_t n = (size_t)1 << o.log2n, l = (size_t)1 << o.log2l, M = (size_t)1 << log2M;
-    if (int rc = open_all_sizes("kzg_open_cosets", n, stride_elems, batch)) return rc;
+    const int log2M = o.log2d - o.log2l + 1; // M = 2 mu = 2 d / l
+    const size_t n = (size_t)1 << o.log2n, d = (size_t)1 << o.log2d, l = (size_t)1 << o.log2l, m = n >> o.log2l, M = (size_t)1 << log2M;
+    if (int rc = open_cosets_sizes("kzg_open_cosets", n, d, stride_elems, batch)) return rc;
     if (int rc = ensure_init()) return rc;
     const hipStream_t st = (hipStream_t)hip_stream;
-    // t, then t^, then the proofs (batch x 2 n x 32 bytes hold batch x m x 64), and the M scratch points of every polynomial
+    // t, then t^, then the proofs: batch x 2 d x 32 bytes of scalars, batch x m x 64 of proofs -- the larger of the two (the scalars unless d < m; at d = n
+    // they hold the proofs l times over); and the 2 m scratch points of every polynomial: the convolution in [0, M), the forward transform in [m, 2 m)
     DevBuf t, scratch;
-    HIPCHK(dev_malloc(&t.p, (size_t)batch * 2 * n * 32));
-    HIPCHK(dev_malloc(&scratch.p, (size_t)batch * M * 128));
-    if (int rc = kzg_open_cosets_t(d_coeffs, stride_elems, batch, o.log2n, o.log2l, t.as<uint64_t>(), st)) return rc;
+    HIPCHK(dev_malloc(&t.p, (size_t)batch * std::max(2 * d * 32, m * 64)));
+    HIPCHK(dev_malloc(&scratch.p, (size_t)batch * 2 * m * 128));
+    if (int rc = kzg_open_cosets_t(d_coeffs, stride_elems, batch, o.log2d, o.log2l, t.as<uint64_t>(), st)) return rc;
     // batch x l transforms of length M, side by side; the batched transform takes KZG_OPEN_ALL_MAX_BATCH of them per call
     for (size_t done = 0, all = (size_t)batch * l; done < all; done += host::KZG_OPEN_ALL_MAX_BATCH) {
         const int group = (int)std::min<size_t>(all - done, host::KZG_OPEN_ALL_MAX_BATCH);
@@ -3070,10 +3105,11 @@ int bbgpu_kzg_open_cosets_device(int setup, const uint64_t* d_coeffs, size_t str
     const host::Fr W = host::fr_root_of_unity(log2M);
     const host::Fr c32 = host::fr_from_mont(host::fr_mul(host::fr_inv(host::fr_from_u64((uint64_t)M)), host::fr_from_u64(32))); // the plain integer 32 / M
     float ms4[4] = { 0, 0, 0, 0 };
-    if (int rc = kzg_open_cosets_chain(o.d_S, t.as<uint64_t>(), scratch.as<uint32_t>(), o.log2n, o.log2l, batch, host::limbs_m256(c32).d,
-                                       host::limbs_m261(host::fr_inv(W)).d, host::limbs_m261(host::fr_root_of_unity(log2M - 1)).d, st, ctx().timing ? ms4 : nullptr))
+    if (int rc = kzg_open_cosets_chain(o.d_S, t.as<uint64_t>(), scratch.as<uint32_t>(), o.log2n, o.log2l, o.log2d, batch, host::limbs_m256(c32).d,
+                                       host::limbs_m261(host::fr_inv(W)).d, host::limbs_m261(host::fr_root_of_unity(o.log2n - o.log2l)).d, st,
+                                       ctx().timing ? ms4 : nullptr))
         return rc;
-    if (int rc = device_to_host_sync(proofs_out, t.p, (size_t)batch * (M / 2) * 64, st)) return rc;
+    if (int rc = device_to_host_sync(proofs_out, t.p, (size_t)batch * m * 64, st)) return rc;
     if (ctx().timing) { // bbgpu_last_timing: index 0 the sum kernel, 1 the inverse stages, 2 the gather kernel and the forward stages, 3 the finish kernel
         ctx().last.count = 4;
         for (int i = 0; i < 4; i++) ctx().last.ms[i] = ms4[i];

@@ -6,7 +6,15 @@
 //   h = the first m entries of IDFT_M( sum_e DFT_M(s^(e)) o DFT_M(t^(e)) ),
 // and the proofs are the size-m forward transform, root omega^l, of (h_0 .. h_(m-2), infinity).  At l = 1 this is host_kzg_open_all.hpp.  Scalars by
 // ntt_radix2, points by g1_transform_host with a plain double-and-add per product and a plain left-to-right sum over e -- NOT the ladder and the lane tree
-// of kzg_open_cosets.hip, so that device and twin check each other.  Product code, no oracle/; no HIP call, no lock.
+// of kzg_open_cosets.hip, so that device and twin check each other.
+// A polynomial of degree < d, d a power of two with 2 l <= d <= n (bbgpu_kzg_open_cosets_setup_bounded), needs Toeplitz products of size mu = d / l only: with
+// M = 2 mu and W the M-th root,
+//   s^(e) = (P^(e)_(mu-2) .. P^(e)_0, infinity x (mu + 1)),   t^(e) = (c^(e)_(mu-1), 0 x (mu + 1), c^(e)_1 .. c^(e)_(mu-2)),
+//   h = the first mu entries of IDFT_M( sum_e DFT_M(s^(e)) o DFT_M(t^(e)) ),
+// and the proofs are the size-m forward transform, root omega^l, of (h_0 .. h_(mu-2), infinity x (m - mu + 1)): rows [0, d - l) and coefficients [0, d) are
+// read.  The twin runs ALL log2 m stages of that last transform over the zero-padded input -- NOT the replicating gather of kzg_open_cosets.hip, which
+// skips the first log2 (m / mu) of them.  d = n is the construction above, and the entries without a bound are that case.
+// Product code, no oracle/; no HIP call, no lock.
 #pragma once
 #include <algorithm>
 
@@ -26,6 +34,18 @@ static inline bool kzg_open_cosets_log2(size_t n, size_t coset, int* log2n, int*
         if (coset == (size_t)1 << c) *log2l = c;
     return *log2n >= 1 && *log2l >= 0 && *log2n - *log2l >= 1;
 }
+// the degree bound d of a setup of (n, l): a power of two with 2 l <= d <= n -> log2 d, else -1
+static inline int kzg_open_cosets_bound_log2(int log2n, int log2l, size_t degree_bound)
+{
+    for (int k = log2l + 1; k <= log2n; k++)
+        if (degree_bound == (size_t)1 << k) return k;
+    return -1;
+}
+// the sizes of one call over a setup of (n, d): kzg_open_all_sizes_ok with the stride held to d, the coefficients that are read
+static inline bool kzg_open_cosets_sizes_ok(size_t n, size_t d, size_t stride_elems, int batch)
+{
+    return kzg_open_all_sizes_ok(n, n, batch) && stride_elems >= d;
+}
 // element i of t^(e), i < M = 2 m: (c^(e)_(m-1), 0 x (m + 1), c^(e)_1 .. c^(e)_(m-2)) -> the index of the coefficient, or -1 for a zero
 static inline long kzg_open_cosets_t_source(size_t i, size_t m, size_t l, size_t e)
 {
@@ -33,21 +53,21 @@ static inline long kzg_open_cosets_t_source(size_t i, size_t m, size_t l, size_t
     return a < 0 ? -1 : (long)(e + l * (size_t)a);
 }
 
-// S^(e) = DFT_M(s^(e)) for every e < l, transform e at S[e M ..], natural order.  Rows [0, n - l) of the table are read (the even entries of an endo
-// table); one off the curve: BBGPU_ERR_ARG and the first such index in *bad_row.
-static inline int kzg_open_cosets_setup_host(const uint64_t* table, int log2n, int log2l, std::vector<Xyzz>& S, uint64_t* bad_row)
+// S^(e) = DFT_M(s^(e)) for every e < l, M = 2 mu = 2 d / l, transform e at S[e M ..], natural order.  Rows [0, d - l) of the table are read (the even
+// entries of an endo table); one off the curve: BBGPU_ERR_ARG and the first such index in *bad_row.
+static inline int kzg_open_cosets_setup_bounded_host(const uint64_t* table, int log2d, int log2l, std::vector<Xyzz>& S, uint64_t* bad_row)
 {
-    const int log2M = log2n - log2l + 1;
-    const size_t n = (size_t)1 << log2n, l = (size_t)1 << log2l, m = n >> log2l, M = 2 * m;
+    const int log2M = log2d - log2l + 1;
+    const size_t d = (size_t)1 << log2d, l = (size_t)1 << log2l, mu = d >> log2l, M = 2 * mu;
     S.assign(l * M, g1_infinity());
-    for (size_t j = 0; j < n - l; j++) { // row j = e + l b, b <= m - 2
+    for (size_t j = 0; j < d - l; j++) { // row j = e + l b, b <= mu - 2
         Fq px, py;
         g1_words_canonical(table + 16 * j, &px, &py);
         if (!g1_on_curve(px, py)) {
             *bad_row = j;
             return BBGPU_ERR_ARG;
         }
-        S[(j % l) * M + bit_reverse(m - 2 - j / l, log2M)] = Xyzz{ px, py, FQ_ONE, FQ_ONE };
+        S[(j % l) * M + bit_reverse(mu - 2 - j / l, log2M)] = Xyzz{ px, py, FQ_ONE, FQ_ONE };
     }
     std::vector<Xyzz> v(M);
     for (size_t e = 0; e < l; e++) {
@@ -57,14 +77,19 @@ static inline int kzg_open_cosets_setup_host(const uint64_t* table, int log2n, i
     }
     return BBGPU_OK;
 }
-
-// the proofs of `batch` polynomials over S^: proofs_out[(b m + k) * 8] = the affine pi_k of polynomial b, reference format (infinity: bit 63 of y[3], rest
-// zero)
-static inline void kzg_open_cosets_proofs_host(const std::vector<Xyzz>& S, int log2n, int log2l, const uint64_t* coeffs, size_t stride_elems, int batch,
-                                               uint64_t* proofs_out)
+// the same without a bound: d = n
+static inline int kzg_open_cosets_setup_host(const uint64_t* table, int log2n, int log2l, std::vector<Xyzz>& S, uint64_t* bad_row)
 {
-    const int log2m = log2n - log2l, log2M = log2m + 1;
-    const size_t l = (size_t)1 << log2l, m = (size_t)1 << log2m, M = 2 * m;
+    return kzg_open_cosets_setup_bounded_host(table, log2n, log2l, S, bad_row);
+}
+
+// the proofs of `batch` polynomials of degree < d over S^ of (d, l): proofs_out[(b m + k) * 8] = the affine pi_k of polynomial b, reference format (infinity:
+// bit 63 of y[3], rest zero).  Coefficients [0, d) of every polynomial are read and nothing from d on.
+static inline void kzg_open_cosets_proofs_bounded_host(const std::vector<Xyzz>& S, int log2n, int log2l, int log2d, const uint64_t* coeffs, size_t stride_elems,
+                                                       int batch, uint64_t* proofs_out)
+{
+    const int log2m = log2n - log2l, log2mu = log2d - log2l, log2M = log2mu + 1;
+    const size_t l = (size_t)1 << log2l, m = (size_t)1 << log2m, mu = (size_t)1 << log2mu, M = 2 * mu;
     const Fr W = fr_root_of_unity(log2M), Minv = fr_inv(fr_from_u64((uint64_t)M));
     std::vector<uint64_t> t(4 * l * M);
     std::vector<Xyzz> v(M), u(m);
@@ -73,7 +98,7 @@ static inline void kzg_open_cosets_proofs_host(const std::vector<Xyzz>& S, int l
         for (size_t e = 0; e < l; e++) {
             uint64_t* te = &t[4 * e * M];
             for (size_t i = 0; i < M; i++) {
-                const long src = kzg_open_cosets_t_source(i, m, l, e);
+                const long src = kzg_open_cosets_t_source(i, mu, l, e); // < d
                 if (src < 0) memset(te + 4 * i, 0, 32);
                 else memcpy(te + 4 * i, c + 4 * (size_t)src, 32);
             }
@@ -92,9 +117,9 @@ static inline void kzg_open_cosets_proofs_host(const std::vector<Xyzz>& S, int l
             }
         });
         g1_transform_host(v, log2M, fr_inv(W));
-        for (size_t a = 0; a + 1 < m; a++) u[bit_reverse(a, log2m)] = v[a];
-        u[m - 1] = g1_infinity(); // bit_reverse(m - 1) == m - 1
-        g1_transform_host(u, log2m, fr_root_of_unity(log2m));
+        std::fill(u.begin(), u.end(), g1_infinity()); // h_(mu-1) and everything from mu on: infinity
+        for (size_t a = 0; a + 1 < mu; a++) u[bit_reverse(a, log2m)] = v[a];
+        g1_transform_host(u, log2m, fr_root_of_unity(log2m)); // all log2 m stages
         uint64_t* out = proofs_out + (size_t)b * m * 8;
         fallback_parallel(m, 64, [&](size_t lo, size_t hi) {
             for (size_t i = lo; i < hi; i++) {
@@ -104,6 +129,12 @@ static inline void kzg_open_cosets_proofs_host(const std::vector<Xyzz>& S, int l
             }
         });
     }
+}
+// the same without a bound: d = n
+static inline void kzg_open_cosets_proofs_host(const std::vector<Xyzz>& S, int log2n, int log2l, const uint64_t* coeffs, size_t stride_elems, int batch,
+                                               uint64_t* proofs_out)
+{
+    kzg_open_cosets_proofs_bounded_host(S, log2n, log2l, log2n, coeffs, stride_elems, batch, proofs_out);
 }
 
 } // namespace host

@@ -3,17 +3,22 @@
 // (host_kzg_open_cosets.hpp states it).  String and coefficients are split by residue e = j mod l into l problems of the kzg_open_all.hip layout at size m,
 // whose products are SUMMED in the Fourier domain: with M = 2 m and W the M-th root, one inverse transform of length M and one forward transform of length m
 // serve all l residues.  Points live on a scratch of projective points (XYZZ, 128 bytes each, ZZ == 0 for infinity; g1_ladder.hpp) and every per-call kernel
-// takes the polynomial of a batch from blockIdx.y:
+// takes the polynomial of a batch from blockIdx.y.  A setup carries a degree bound d, 2 l <= d <= n (bbgpu_kzg_open_cosets_setup_bounded; d = n without one):
+// the Toeplitz products then have size mu = d / l, M = 2 mu, and only the last forward transform lives on the size-m domain, rho = m / mu:
 //   k_open_cosets_string (setup) slot i of transform e <- s^(e)_bitrev(i); log2 M launches of k_lagrange_stage (g1_stage.hpp), gridDim.y = l, with root W
-//                        leave S^(e) = DFT_M(s^(e)), l x M = 2 n points kept by the handle;
+//                        leave S^(e) = DFT_M(s^(e)), l x M = 2 d points kept by the handle;
 //   k_open_cosets_t      the batch x l x M scalars of t^(e) from the coefficients; bbgpu_ntt_device_batch transforms them (capi.hip);
 //   k_open_cosets_sum    slot i <- sum_e (M^-1 t^^(e)_j) * S^(e)_j, j = bitrev(i): lane (f, e) of a wave runs the ladder of residue e at the wave's f-th
 //                        frequency, then the l results of a frequency are added in a log2 l-level tree across lanes, through LDS;
-//   k_lagrange_stage     log2 M launches with root W^-1: slots [0, m - 1) now hold h;
-//   k_open_cosets_gather slot m + bitrev_m(u) <- slot u for u < m - 1, slot 2 m - 1 <- infinity;
-//   k_lagrange_stage     log2 m launches with root omega^l on those upper halves;
+//   k_lagrange_stage     log2 M launches with root W^-1: slots [0, mu - 1) now hold h;
+//   k_open_cosets_gather slot m + rho bitrev_mu(u) + c <- slot u for u < mu - 1 and every c < rho, the rho slots of u = mu - 1 <- infinity: the size-m
+//                        input (h_0 .. h_(mu-2), infinity x (m - mu + 1)) in bit-reversed order is nonzero at multiples of rho only, and stages 0 ..
+//                        log2 rho - 1 of the decimation in time would turn every (a, infinity) into (a, a) -- the gather writes those copies itself;
+//   k_lagrange_stage     stages log2 rho .. log2 m - 1 of the size-m transform with root omega^l on those upper halves (all log2 m at d = n);
 //   k_open_cosets_finish one Fermat inversion per row to the reference's affine format.
-// The gather and the finish kernel are those of kzg_open_all.hip at sizes m and M (each file has its own copy, as of the stage kernel).  One wave per
+// Every polynomial owns 2 m scratch slots whatever d is: the convolution in [0, M), M <= 2 m, the forward transform in [m, 2 m) (M <= m when d < n, and at
+// d = n the gather reads below m and writes from m on).  At d = n every launch, index and result is that of the construction without a bound.  The finish
+// kernel is that of kzg_open_all.hip at size m (each file has its own copy, as of the stage kernel).  One wave per
 // workgroup, 3-bit windows and no twiddle table, as srs_lagrange.hip.  The reference has no counterpart.
 #include <hip/hip_runtime.h>
 
@@ -26,7 +31,8 @@ namespace {
 
 constexpr int FT = 256; // threads per workgroup of the kernels that run no ladder
 
-// slot i of transform e, g = e M + i < l M = 2 n <- s^(e)_j, j = bitrev_M(i): row e + l (m - 2 - j) of the table for j <= m - 2 (ZZ = ZZZ = 1), infinity above
+// slot i of transform e, g = e M + i < l M = 2 d <- s^(e)_j, j = bitrev_M(i): row e + l (mu - 2 - j) of the table for j <= mu - 2 (ZZ = ZZZ = 1), infinity
+// above.  m here is mu = d / l.
 __global__ void __launch_bounds__(FT) k_open_cosets_string(const uint32_t* __restrict__ in, uint32_t* __restrict__ scratch, uint32_t m, uint32_t log2M, uint32_t log2l)
 {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -36,7 +42,7 @@ __global__ void __launch_bounds__(FT) k_open_cosets_string(const uint32_t* __res
     uint32_t o[32];
     if (j <= m - 2) {
         uint32_t w[16];
-        const uint4* src = reinterpret_cast<const uint4*>(in + (size_t)(e + ((m - 2 - j) << log2l)) * 16); // row <= l - 1 + l (m - 2) < n - l
+        const uint4* src = reinterpret_cast<const uint4*>(in + (size_t)(e + ((m - 2 - j) << log2l)) * 16); // row <= l - 1 + l (mu - 2) < d - l
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             const uint4 v = src[t];
@@ -52,8 +58,9 @@ __global__ void __launch_bounds__(FT) k_open_cosets_string(const uint32_t* __res
     store_words32(scratch + (size_t)g * 32, o);
 }
 
-// t^(e)_i of polynomial blockIdx.y, g = e M + i < 2 n: c_(e + l (m - 1)) at i == 0, zero for 1 <= i <= m + 1, c_(e + l (i - m - 1)) above
-// (host_kzg_open_cosets.hpp kzg_open_cosets_t_source).  The words are copied as they are: the transform takes any representative.
+// t^(e)_i of polynomial blockIdx.y, g = e M + i < 2 d, m here mu = d / l: c_(e + l (mu - 1)) at i == 0, zero for 1 <= i <= mu + 1, c_(e + l (i - mu - 1))
+// above (host_kzg_open_cosets.hpp kzg_open_cosets_t_source).  The words are copied as they are: the transform takes any representative.  Coefficients from
+// d on are not read.
 __global__ void __launch_bounds__(FT) k_open_cosets_t(const uint32_t* __restrict__ coeffs, size_t stride_elems, uint32_t* __restrict__ t, uint32_t m, uint32_t log2M,
                                                       uint32_t log2l)
 {
@@ -63,7 +70,7 @@ __global__ void __launch_bounds__(FT) k_open_cosets_t(const uint32_t* __restrict
     const uint32_t e = g >> log2M, i = g & (2 * m - 1);
     uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
     if (i == 0 || i > m + 1) {
-        const uint32_t src = e + ((i == 0 ? m - 1 : i - m - 1) << log2l); // <= l - 1 + l (m - 1) < n <= stride_elems
+        const uint32_t src = e + ((i == 0 ? m - 1 : i - m - 1) << log2l); // <= l - 1 + l (mu - 1) < d <= stride_elems
         const uint4* c = reinterpret_cast<const uint4*>(coeffs + (b * stride_elems + src) * 8);
         lo = c[0];
         hi = c[1];
@@ -78,9 +85,10 @@ __global__ void __launch_bounds__(FT) k_open_cosets_t(const uint32_t* __restrict
 // frequencies.  Each lane runs its own ladder (a zero scalar or an infinite base gives infinity; so does a lane past the end, which arises for l M < 64
 // only), then level d of the tree adds the point of lane e + 2^d to that of every lane e with e mod 2^(d+1) == 0.  The points cross in LDS as 32 canonical
 // words, word w of lane L at w * 64 + L (consecutive lanes on consecutive banks).  The addition is complete: either side may be infinity, equal points
-// double and opposite ones give infinity (add_pt), as two residues of an honest string meet whenever their scalars are in the string's own ratio.
+// double and opposite ones give infinity (add_pt), as two residues of an honest string meet whenever their scalars are in the string's own ratio.  The
+// slots of polynomial b start at b * slots (2 m of the domain, >= M).
 __global__ void __launch_bounds__(LT) k_open_cosets_sum(const uint32_t* __restrict__ that, const uint32_t* __restrict__ S, uint32_t* __restrict__ scratch, uint32_t M,
-                                                        uint32_t log2M, uint32_t log2l, Limbs9 c32)
+                                                        uint32_t log2M, uint32_t log2l, Limbs9 c32, size_t slots)
 {
     __shared__ uint32_t cross[32 * LT];
     const uint32_t lane = threadIdx.x, g = blockIdx.x * LT + lane; // < 2^22 + 64
@@ -140,26 +148,28 @@ __global__ void __launch_bounds__(LT) k_open_cosets_sum(const uint32_t* __restri
     if (e == 0 && i < M) {
         uint32_t o[32];
         store_pt(o, acc, inf);
-        store_words32(scratch + ((b << log2M) + i) * 32, o);
+        store_words32(scratch + (b * slots + i) * 32, o);
     }
 }
 
-// the size-m scratch of the forward transform, slots [m, 2 m) of polynomial blockIdx.y: m + bitrev(u) <- slot u for u < m - 1, 2 m - 1 <- infinity
-// (bitrev(m - 1) == m - 1).  Reads touch slots below m only and writes slots from m on.
-__global__ void __launch_bounds__(FT) k_open_cosets_gather(uint32_t* __restrict__ scratch, uint32_t m, uint32_t log2m)
+// the size-m scratch of the forward transform, slots [m, 2 m) of polynomial blockIdx.y, after its first log2 rho stages, rho = m / mu: thread q = u rho + c
+// copies slot u < mu - 1 (h_u) to slot m + rho bitrev_mu(u) + c, and the rho threads of u = mu - 1 write infinity (bitrev(mu - 1) == mu - 1).  Reads touch
+// slots below mu <= m only and writes slots from m on.  At rho = 1 thread u writes slot m + bitrev_m(u).
+__global__ void __launch_bounds__(FT) k_open_cosets_gather(uint32_t* __restrict__ scratch, uint32_t m, uint32_t log2mu, uint32_t log2rho)
 {
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= m) return;
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= m) return;
     uint32_t* base = scratch + (size_t)blockIdx.y * 2 * m * 32;
-    const uint32_t j = __brev(u) >> (32 - log2m); // log2m >= 1; j < m
+    const uint32_t u = q >> log2rho, c = q & ((1u << log2rho) - 1u); // u < mu
+    const uint32_t j = __brev(u) >> (32 - log2mu);                    // log2mu >= 1; j < mu
     uint32_t w[32];
-    if (u == m - 1) {
+    if (u == (1u << log2mu) - 1u) {
 #pragma unroll
         for (int t = 0; t < 32; t++) w[t] = 0;
     } else {
         load_words32(base + (size_t)u * 32, w);
     }
-    store_words32(base + (size_t)(m + j) * 32, w);
+    store_words32(base + (size_t)(m + (j << log2rho) + c) * 32, w); // < 2 m
 }
 
 // proof k of polynomial blockIdx.y <- the affine form of slot m + k in the reference's format.  Infinity is an ordinary result: nothing is counted.
@@ -203,13 +213,13 @@ uint32_t blocks_of(uint32_t count, int threads) { return (count + threads - 1) /
 
 } // namespace
 
-// d_in: at least n - l resident rows on the curve, n = 2^log2n, l = 2^log2l, 0 <= log2l <= 6, 1 <= log2n - log2l, log2n <= 21; W_m261:
-// fr_root_of_unity(log2n - log2l + 1), Montgomery-261, canonical 29-bit limbs (host_fr.hpp limbs_m261).  *d_S: a new allocation of 2 n scratch points,
+// d_in: at least d - l resident rows on the curve, d = 2^log2d, l = 2^log2l, 0 <= log2l <= 6, 1 <= log2d - log2l, log2d <= 21; W_m261:
+// fr_root_of_unity(log2d - log2l + 1), Montgomery-261, canonical 29-bit limbs (host_fr.hpp limbs_m261).  *d_S: a new allocation of 2 d scratch points,
 // S^(e) in natural order at e M, the caller's on success.
-int kzg_open_cosets_string(const uint32_t* d_in, int log2n, int log2l, const uint32_t W_m261[9], uint32_t** d_S, hipStream_t st)
+int kzg_open_cosets_string(const uint32_t* d_in, int log2d, int log2l, const uint32_t W_m261[9], uint32_t** d_S, hipStream_t st)
 {
     *d_S = nullptr;
-    const uint32_t lgl = (uint32_t)log2l, lgM = (uint32_t)(log2n - log2l) + 1, M = 1u << lgM, l = 1u << lgl;
+    const uint32_t lgl = (uint32_t)log2l, lgM = (uint32_t)(log2d - log2l) + 1, M = 1u << lgM, l = 1u << lgl;
     DevBuf S;
     HIPCHK(dev_malloc(&S.p, ((size_t)M << lgl) * 128));
     k_open_cosets_string<<<blocks_of(M << lgl, FT), FT, 0, st>>>(d_in, S.as<uint32_t>(), M / 2, lgM, lgl);
@@ -221,22 +231,22 @@ int kzg_open_cosets_string(const uint32_t* d_in, int log2n, int log2l, const uin
     return BBGPU_OK;
 }
 
-// d_t <- the batch x l x M scalars of t^(e), transform e of polynomial b at (b l + e) M (d_t: batch x 2 n elements)
-int kzg_open_cosets_t(const uint64_t* d_coeffs, size_t stride_elems, int batch, int log2n, int log2l, uint64_t* d_t, hipStream_t st)
+// d_t <- the batch x l x M scalars of t^(e), M = 2 d / l, transform e of polynomial b at (b l + e) M (d_t: batch x 2 d elements)
+int kzg_open_cosets_t(const uint64_t* d_coeffs, size_t stride_elems, int batch, int log2d, int log2l, uint64_t* d_t, hipStream_t st)
 {
-    const uint32_t lgM = (uint32_t)(log2n - log2l) + 1;
-    k_open_cosets_t<<<dim3(blocks_of(2u << log2n, FT), (uint32_t)batch), FT, 0, st>>>((const uint32_t*)d_coeffs, stride_elems, (uint32_t*)d_t, 1u << (lgM - 1), lgM,
+    const uint32_t lgM = (uint32_t)(log2d - log2l) + 1;
+    k_open_cosets_t<<<dim3(blocks_of(2u << log2d, FT), (uint32_t)batch), FT, 0, st>>>((const uint32_t*)d_coeffs, stride_elems, (uint32_t*)d_t, 1u << (lgM - 1), lgM,
                                                                                       (uint32_t)log2l);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
 
-// d_that: DFT_M(t^(e)) of every polynomial and residue, batch x 2 n elements in the memory format; on return the same buffer holds the batch x m proofs (64
-// bytes each).  d_scratch: batch x M scratch points.  c32: the plain integer 32 M^-1 mod r; Winv, psi: fr_root_of_unity(log2 M)^-1 and
+// d_that: DFT_M(t^(e)) of every polynomial and residue, batch x 2 d elements in the memory format, in a buffer that also takes the batch x m proofs (64 bytes
+// each), which it holds on return.  d_scratch: batch x 2 m scratch points.  c32: the plain integer 32 M^-1 mod r; Winv, psi: fr_root_of_unity(log2 M)^-1 and
 // fr_root_of_unity(log2 m), Montgomery-261 -- all canonical 29-bit limbs.  Nothing is synchronised unless ms4 is given: then the device times of the sum
 // kernel, the inverse stages, the gather kernel with the forward stages, and the finish kernel (bbgpu_set_timing).
-int kzg_open_cosets_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scratch, int log2n, int log2l, int batch, const uint32_t c32[9], const uint32_t Winv[9],
-                          const uint32_t psi[9], hipStream_t st, float* ms4)
+int kzg_open_cosets_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scratch, int log2n, int log2l, int log2d, int batch, const uint32_t c32[9],
+                          const uint32_t Winv[9], const uint32_t psi[9], hipStream_t st, float* ms4)
 {
     struct Events {
         hipEvent_t e[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
@@ -248,15 +258,17 @@ int kzg_open_cosets_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scr
     } ev;
     if (ms4)
         for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
-    const uint32_t lgl = (uint32_t)log2l, lgm = (uint32_t)(log2n - log2l), lgM = lgm + 1, m = 1u << lgm, M = 2 * m, nb = (uint32_t)batch;
+    const uint32_t lgl = (uint32_t)log2l, lgm = (uint32_t)(log2n - log2l), lgmu = (uint32_t)(log2d - log2l), lgM = lgmu + 1, lgrho = lgm - lgmu;
+    const uint32_t m = 1u << lgm, M = 2u << lgmu, nb = (uint32_t)batch;
+    const size_t slots = 2 * (size_t)m; // per polynomial
     if (ms4) HIPCHK(hipEventRecord(ev.e[0], st));
-    k_open_cosets_sum<<<dim3(blocks_of(M << lgl, LT), nb), LT, 0, st>>>((const uint32_t*)d_that, d_S, d_scratch, M, lgM, lgl, to_limbs9(c32));
+    k_open_cosets_sum<<<dim3(blocks_of(M << lgl, LT), nb), LT, 0, st>>>((const uint32_t*)d_that, d_S, d_scratch, M, lgM, lgl, to_limbs9(c32), slots);
     if (ms4) HIPCHK(hipEventRecord(ev.e[1], st));
     const Limbs9 wi = to_limbs9(Winv), ps = to_limbs9(psi);
-    for (uint32_t s = 0; s < lgM; s++) k_lagrange_stage<<<dim3(blocks_of(m, LT), nb), LT, 0, st>>>(d_scratch, M, lgM, s, wi, (size_t)M);
+    for (uint32_t s = 0; s < lgM; s++) k_lagrange_stage<<<dim3(blocks_of(M / 2, LT), nb), LT, 0, st>>>(d_scratch, M, lgM, s, wi, slots);
     if (ms4) HIPCHK(hipEventRecord(ev.e[2], st));
-    k_open_cosets_gather<<<dim3(blocks_of(m, FT), nb), FT, 0, st>>>(d_scratch, m, lgm);
-    for (uint32_t s = 0; s < lgm; s++) k_lagrange_stage<<<dim3(blocks_of(m / 2, LT), nb), LT, 0, st>>>(d_scratch + (size_t)m * 32, m, lgm, s, ps, (size_t)M);
+    k_open_cosets_gather<<<dim3(blocks_of(m, FT), nb), FT, 0, st>>>(d_scratch, m, lgmu, lgrho);
+    for (uint32_t s = lgrho; s < lgm; s++) k_lagrange_stage<<<dim3(blocks_of(m / 2, LT), nb), LT, 0, st>>>(d_scratch + (size_t)m * 32, m, lgm, s, ps, slots);
     if (ms4) HIPCHK(hipEventRecord(ev.e[3], st));
     k_open_cosets_finish<<<dim3(blocks_of(m, FT), nb), FT, 0, st>>>(d_scratch, (uint32_t*)d_that, m);
     HIPCHK(launch_check()); // the chain: sum, stages, gather, stages, finish

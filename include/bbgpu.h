@@ -902,7 +902,8 @@ int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const u
  * bbgpu_shutdown).
  *   n, coset     powers of two, 1 <= coset <= BBGPU_KZG_OPEN_COSETS_MAX_COSET, n / coset >= 2, n <= 2^21 and no larger than the table: otherwise
  *                BBGPU_ERR_SIZE.  An unknown SRS handle: BBGPU_ERR_ARG.  BBGPU_ERR_STATE: BBGPU_KZG_OPEN_COSETS_MAX_SETUPS setups are live -- a pool of its
- *                own: the setups of bbgpu_kzg_open_all_setup neither count against it nor are refused by it.  All are refused before a device is bound.
+ *                own: the setups of bbgpu_kzg_open_all_setup neither count against it nor are refused by it (those of bbgpu_kzg_open_cosets_setup_bounded,
+ *                the next block, are setups of this pool).  All are refused before a device is bound.
  *   coset == 1   is accepted on purpose: the construction is then that of the block above, and the proofs are those of bbgpu_kzg_open_all_device bit for bit.
  *   bad rows     the curve pass runs over the rows the setup reads, [0, n - l), as in bbgpu_kzg_open_all_setup: a bad row is BBGPU_ERR_ARG,
  *                bbgpu_last_error() naming the first one, and no setup is made.  Rows from n - l on are not read.
@@ -914,7 +915,7 @@ int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const u
  * HOST memory: proofs_out[(b * m + k) * 8] is pi_k of polynomial b in the reference's format (Montgomery-256, canonical; infinity: bit 63 of y[3], every
  * other word zero).  Infinity is an ordinary result: a polynomial of degree below l has every proof at infinity.  The order is natural in k: the values of
  * cell k are entries k, k + m, k + 2 m, .. of the caller's own size-n bbgpu_ntt_device of the coefficients; this entry does not return them.
- *   BBGPU_ERR_SIZE   batch outside 1..64, stride_elems < n, batch x 2 n > 2^22
+ *   BBGPU_ERR_SIZE   batch outside 1..64, stride_elems < n (< d over a setup with a degree bound d: the next block), batch x 2 n > 2^22
  *   BBGPU_ERR_ARG    an unknown setup, a null pointer                                    -- all refused before a device is bound
  * The kernels (csrc/kzg_open_cosets.hip; every one takes the polynomial from blockIdx.y): k_open_cosets_t writes the batch x l x M scalars of t^(e) and
  * bbgpu_ntt_device_batch transforms them, 64 transforms per call; k_open_cosets_sum puts sum_e (M^-1 t^^(e)_j) * S^(e)_j, j = bitrev(i), into slot i --
@@ -951,6 +952,61 @@ int bbgpu_kzg_open_cosets_device(int setup, const uint64_t* d_coeffs, size_t str
                                  void* hip_stream);
 int bbgpu_host_kzg_open_cosets(const uint64_t* points_endo_table, size_t n, size_t coset, const uint64_t* coeffs, size_t stride_elems, int batch,
                                uint64_t* proofs_out /* batch x (n / coset) x 8 */);
+
+/* ---- open cosets of a polynomial of BOUNDED DEGREE: half the ladders at d = n / 2, and a string of d rows is enough ------
+ * Everything downstream of the block above is built around a polynomial of degree < d on a domain of size n > d (bbgpu_kzg_recover_cells wants
+ * count x l >= d, bbgpu_g1_recover extends k rows to 2 k), but a setup of the block above treats every polynomial as degree < n: n - l rows of the string,
+ * 2 n rows of S^, 2 n ladders and an inverse transform of length 2 n / l per call.  For degree < d = `degree_bound` the Toeplitz products of the same
+ * construction have size mu = d / l, not m = n / l; only the last forward transform lives on the size-m domain.  With M = 2 mu, rho = m / mu,
+ * W = fr_root_of_unity(log2 M) and psi = omega^l:
+ *   s^(e) = (P^(e)_(mu-2), .., P^(e)_0, infinity x (mu + 1))
+ *   t^(e) = (c^(e)_(mu-1), 0 x (mu + 1), c^(e)_1, .., c^(e)_(mu-2))          (mu = 2: (c^(e)_1, 0, 0, 0))
+ *   h = the first mu entries of IDFT_M( sum_e DFT_M(s^(e)) o DFT_M(t^(e)) )
+ *   (pi_0 .. pi_(m-1)) = DFT_m, root psi, of (h_0 .. h_(mu-2), infinity x (m - mu + 1))
+ * bbgpu_kzg_open_cosets_setup_bounded makes a setup of this kind in the pool of the block above (BBGPU_KZG_OPEN_COSETS_MAX_SETUPS setups in all, bounded or
+ * not); the handle is used with bbgpu_kzg_open_cosets_device and bbgpu_kzg_open_cosets_release -- there is no second device entry.
+ *   degree_bound a power of two with 2 x coset <= degree_bound <= n, otherwise BBGPU_ERR_SIZE, refused before a device is bound as the sizes of the block
+ *                above are.  degree_bound == n IS bbgpu_kzg_open_cosets_setup(srs_handle, n, coset): the same rows read, the same footprint, the same
+ *                launches and proofs (that entry is this call).
+ *   the table    rows [0, d - l) are read and curve-checked (a bad row: BBGPU_ERR_ARG naming the first one, no setup is made); rows from d - l on are not
+ *                read, and the table need hold no more than d rows: a string of d rows opens on the domain of size n = d, 2 d, 4 d, .. up to 2^21.  A table of
+ *                fewer than d rows: BBGPU_ERR_SIZE.
+ *   footprint    l x M = 2 d rows of S^ (2 d x 128 bytes, counted in bbgpu_memory_info.staging_bytes while the setup lives).
+ * Over a bounded setup bbgpu_kzg_open_cosets_device reads coefficients [0, d) of each polynomial and NOTHING FROM d ON: WHAT LIES AT [d, stride_elems) IS
+ * NOT READ AND NOT CHECKED -- a polynomial whose coefficients there are not zero gets the proofs of its truncation to degree < d, which hold for no
+ * commitment of the whole polynomial.  stride_elems >= d is accepted (BBGPU_ERR_SIZE below d), so the d_coeffs_out of bbgpu_kzg_recover_cells goes in with
+ * that call's stride.  The batch rule stays that of the domain: batch in 1..64, batch x 2 n <= 2^22.  The result is the same batch x m proofs in the same
+ * format and natural order; for a polynomial whose coefficients from d on are zero they are the proofs of an unbounded setup bit for bit (unique affine
+ * points).  coset == 1 through this entry is the bounded form of bbgpu_kzg_open_all_device, which has no bound of its own.
+ * The kernels (csrc/kzg_open_cosets.hip) tell mu from m: k_open_cosets_string, k_open_cosets_t and k_open_cosets_sum run at size M = 2 mu -- l x M = 2 d
+ * threads and ladders, source rows and coefficients below d; the inverse transform is log2 M launches of k_lagrange_stage over M slots;
+ * k_open_cosets_gather REPLICATES: slot m + rho bitrev_mu(u) + c <- h_u for u < mu - 1 and every c < rho, the rho slots of u = mu - 1 <- infinity.  The
+ * stage kernel is a decimation in time over bit-reversed input, whose nonzero entries sit at multiples of rho here, so its first log2 rho stages would
+ * only turn (a, infinity) into (a, a); the gather writes those copies and only stages log2 rho .. log2 m - 1 are launched.  k_open_cosets_finish is
+ * unchanged.  Every polynomial keeps 2 m scratch slots whatever d is (the convolution in [0, M), the forward transform in [m, 2 m)), and the buffer of
+ * the scalars, which later holds the proofs, has the larger of batch x 2 d x 32 and batch x m x 64 bytes (the proofs outgrow the scalars when d < m, as
+ * at (1024, 1, 4)).  The gather: 38 VGPRs (16 SGPRs), no LDS, no scratch memory, 8 waves per SIMD -- the figures of the gather it replaces; the other kernels
+ * as in the block above; no scratch memory in any kernel (the compiler's resource remarks, at the head of profiles/kzg_open_bounded.txt).
+ * A warm setup and a warm call at (n, l, d) = (512, 4, 256) pass the funnels of the block above at (256, 4): setup -- one allocation, one upload, one
+ * read-back, two launch checks; call -- two allocations, no upload, one read-back, three launch checks.  After a failure nothing the call allocated is
+ * live and the setup stays usable.  bbgpu_set_timing(1) reports the same four device times with the same meaning.
+ * Cost on one MI355X (tools/kzg_open_bounded_bench.py, profiles/kzg_open_bounded.txt): wall ms per call at d = n / 2, l = 64, proofs read back to the host, one
+ * box, against THE SAME ENTRY over a setup without a bound fed the same coefficients zero-padded, timed in the same process in alternating pairs (medians
+ * of 9 pairs, 3 at 2^20).  n = 2^12: 12.8 ms against 13.0 (batch 16: 15.3 against 16.2); n = 2^16: 19.9 against 22.0 (batch 16: 35.9 against 51.6);
+ * n = 2^20: 43.6 against 59.4.  By the rule of the block above -- a leg wins a shape when its median is lower by more than the full range (max - min) of
+ * either leg -- the bounded setup wins four of the five shapes, (2^16, 64) and (2^20, 64) among them, and loses none: at (2^12, 64), batch 1, its median is
+ * lower by 0.25 ms, WITHIN the spread of 0.48 -- a call of one small polynomial is bound by the latency of its stage launches, of which the bound saves two
+ * of 13, one of them the forward stage 0, which runs no ladder.  Device times at (2^20, 64), bounded against unbounded: the sum kernel 16.7 ms against 31.2, the inverse stages 13.1 against 14.0, the gather and
+ * the forward stages 13.1 against 13.1, the finish kernel 0.16 against 0.16 -- the ladders halve, one inverse stage fewer at half the length saves 1 ms, and
+ * the forward transform does not move: the stage it loses was a launch over copies.  The setup, with its release: 88.3 ms against 186.6 at 2^20, 9.6
+ * against 10.8 at 2^16, 7.0 against 6.5 at 2^12 (not paired; at that size the setup is bound by its launches).  NOT timed: other ratios d / n, l < 64, the
+ * host twin.  Nothing was tuned after these measurements.
+ * The host twin (csrc/host_kzg_open_cosets.hpp) restates the construction with the twin's own transforms and runs ALL log2 m stages of the last transform
+ * over the zero-padded input -- not the replicating gather -- so that device and twin check each other; bbgpu_host_kzg_open_cosets is its d = n case.  It
+ * reads rows [0, d - l) of the table and coefficients [0, d); its errors are those of the device entries. */
+int bbgpu_kzg_open_cosets_setup_bounded(int srs_handle, size_t n, size_t coset, size_t degree_bound); /* setup handle >= 0, of the pool above */
+int bbgpu_host_kzg_open_cosets_bounded(const uint64_t* points_endo_table, size_t n, size_t coset, size_t degree_bound, const uint64_t* coeffs,
+                                       size_t stride_elems, int batch, uint64_t* proofs_out /* batch x (n / coset) x 8 */);
 
 /* ---- do these openings hold?  (up to 2^20 KZG claims: the per-claim rows and scalars on the GPU, one pairing check) ------
  * bbgpu_host_kzg_check_openings above is host only and takes 64 claims; one call of bbgpu_kzg_open_all_device writes up to 2^20 proofs, and a
@@ -1126,7 +1182,8 @@ int bbgpu_host_kzg_cells_key_check(const uint64_t* g1_head /* coset x 8 */, size
  * 1..64, stride_elems < n, batch * n > 2^22; BBGPU_ERR_ARG: a null pointer (values_out may be NULL), a cell index >= n / coset, the same cell listed twice --
  * bbgpu_last_error() names the first offender.  BBGPU_ERR_HIP with a text of its own: a nonzero coefficient in [count * l, n), which no input can cause.
  * Scope: m <= 2^16 because the vanishing values cost mu x m pairs (at most 2^15 x 2^16); larger m -- small l at large n -- is what
- * bbgpu_kzg_recover_cells_each below takes, by a product tree.  Proofs are the caller's next call: bbgpu_kzg_open_cosets_device on d_coeffs_out.
+ * bbgpu_kzg_recover_cells_each below takes, by a product tree.  Proofs are the caller's next call: bbgpu_kzg_open_cosets_device on d_coeffs_out
+ * (over a setup of bbgpu_kzg_open_cosets_setup_bounded with the same degree_bound, where that is a power of two: half the ladders at d = n / 2).
  * The kernels (csrc/kzg_recover_cells.hip; the last three take the polynomial from blockIdx.y): k_recover_roots writes psi^k for the missing cells once;
  * k_recover_vanish, the compute-bound part, gives G = min(64, 2^18 / m) neighbouring lanes to every a, walks K in LDS tiles of 256 roots with two
  * accumulators per lane (one subtraction and one product each per pair, sharing the staged root) and multiplies the G partial products in a tree across
