@@ -40,6 +40,36 @@ struct DevBuf {
     template <class T> T* as() const { return static_cast<T*>(p); }
     template <class T> T* release() { T* r = static_cast<T*>(p); p = nullptr; return r; }
 };
+// the N events between the timed stages of a call (bbgpu_set_timing): made only when timing is on, destroyed on every way out of the function
+template <int N> struct StageEvents {
+    hipEvent_t e[N] = {};
+    bool on = false;
+    StageEvents() = default;
+    StageEvents(const StageEvents&) = delete;
+    StageEvents& operator=(const StageEvents&) = delete;
+    ~StageEvents()
+    {
+        for (hipEvent_t v : e)
+            if (v) (void)hipEventDestroy(v);
+    }
+    int create(bool timed)
+    {
+        on = timed;
+        if (on)
+            for (hipEvent_t& v : e) HIPCHK(hipEventCreate(&v));
+        return BBGPU_OK;
+    }
+    int mark(int k, hipStream_t st) // nothing when timing is off
+    {
+        if (on) HIPCHK(hipEventRecord(e[k], st));
+        return BBGPU_OK;
+    }
+    int ms(int a, int b, float* out) // from mark a to mark b, both complete; timing is on
+    {
+        HIPCHK(hipEventElapsedTime(out, e[a], e[b]));
+        return BBGPU_OK;
+    }
+};
 void fault_absorbed();     // a failure the library rode out by itself (an SRS kept without its window tables): counted, so a test can tell it from a lost injection
 
 // ntt.hip
@@ -233,11 +263,19 @@ int kzg_recover_group_log2(int log2m); // log2 of the lanes that share one a in 
 // d_z[a] = z_a as a Montgomery-261 multiplier, d_zc[a] = z'_a x 2^-5 in the memory format (its inverse there is the multiplier 1 / z'_a): m x 4 words each
 // d_roots: 9 x mu words of workspace for psi^k, k missing
 int kzg_recover_vanish(const uint32_t* d_missing, size_t mu, int log2n, int log2l, uint32_t* d_roots, uint64_t* d_z, uint64_t* d_zc, hipStream_t st);
-int kzg_recover_scatter(const uint64_t* d_values, const uint32_t* d_cell, size_t count, const uint32_t* d_missing, const uint64_t* d_z, int log2n, int log2l,
-                        int batch, uint64_t* d_out, size_t stride_elems, hipStream_t st);
-int kzg_recover_divide(uint64_t* d_q, size_t stride_elems, int batch, const uint64_t* d_inv, int log2n, int log2l, hipStream_t st);
-int kzg_recover_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* d_copy, int log2n, size_t degree_bound, size_t present, RecoverFindings* d_find,
-                     hipStream_t st);
+// The back end of bbgpu_kzg_recover_cells AND bbgpu_kzg_recover_cells_each.  Polynomial b has d_off[b + 1] - d_off[b] cells, their values from element
+// d_off[b] l of d_values on, their indices from d_cell[d_off[b] & cell_mask] on; it misses the d_mu[b] cells at d_missing[b missing_stride ..]; its z and
+// z' lie b z_stride elements into theirs.  Each entry: cell_mask = ~0, missing_stride = M (below), z_stride = m.  Same-set entry: d_off[b] = b count,
+// d_mu[b] = mu, and mask and strides 0 -- one row of each for all.
+struct RecoverLists {
+    const uint32_t *d_off, *d_mu, *d_cell, *d_missing;
+    uint32_t cell_mask, missing_stride, z_stride;
+};
+int kzg_recover_scatter(const uint64_t* d_values, const RecoverLists& L, const uint64_t* d_z, int log2n, int log2l, int batch, uint64_t* d_out, size_t stride_elems,
+                        hipStream_t st);
+int kzg_recover_divide(uint64_t* d_q, size_t stride_elems, int batch, const uint64_t* d_inv, const RecoverLists& L, int log2n, int log2l, hipStream_t st);
+int kzg_recover_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* d_copy, int log2n, int log2l, size_t degree_bound, const RecoverLists& L,
+                     RecoverFindings* d_find, hipStream_t st);
 
 // kzg_recover_each.hip: the device parts of bbgpu_kzg_recover_cells_each that are neither a transform nor the batch inversion.  Polynomial b lists the
 // cells d_cell[d_off[b] .. d_off[b + 1]) and misses d_mu[b]; row b of d_missing (M entries, M the common power of two >= every mu_b, >= 1) holds its
@@ -246,20 +284,11 @@ int kzg_recover_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_
 // T: roots per leaf of the product tree, T / 64 waves of k_each_leaves.  128 and 256 compile too (a leaf then spans waves that exchange through LDS): the
 // comparison of profiles/kzg_recover_each.txt is a build with 256 here; BbGpu.RECOVER_EACH_LEAF (bbgpu.py) mirrors the value
 constexpr int KZG_RECOVER_EACH_LEAF = 64;
-struct KzgRecoverEachLists {
-    const uint32_t *d_off, *d_mu, *d_cell, *d_missing;
-    size_t M;
-};
 constexpr size_t kzg_recover_each_table_words(int log2m) { return (((size_t)1 << ((log2m + 1) / 2)) + ((size_t)1 << (log2m / 2))) * 9; } // k_each_powers
 int kzg_recover_each_leaves(const uint32_t* d_missing, int batch, size_t M, int log2m, uint64_t* d_tree, hipStream_t st);
 int kzg_recover_each_pair(uint64_t* d_tree, size_t pairs, int log2s, hipStream_t st);
 int kzg_recover_each_gather(const uint64_t* d_tree, const uint32_t* d_mu, int batch, size_t M, int log2n, int log2l, uint32_t* d_tab, uint64_t* d_zin,
                             uint64_t* d_zcin, hipStream_t st);
-int kzg_recover_each_scatter(const uint64_t* d_values, const KzgRecoverEachLists& L, const uint64_t* d_z, int log2n, int log2l, int batch, uint64_t* d_out,
-                             size_t stride_elems, hipStream_t st);
-int kzg_recover_each_divide(uint64_t* d_q, size_t stride_elems, int batch, const uint64_t* d_inv, int log2n, int log2l, hipStream_t st);
-int kzg_recover_each_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* d_copy, int log2n, int log2l, size_t degree_bound, const uint32_t* d_off,
-                          RecoverFindings* d_find, hipStream_t st);
 
 // g1_recover.hip: the device parts of bbgpu_g1_ntt and bbgpu_g1_recover.  Columns of n = 2^log2n scratch points (128 bytes each), column b at slot b n;
 // batch x n <= 2^20.  Nothing here synchronises.

@@ -4098,6 +4098,60 @@ int bbgpu_host_kzg_recover_cells(const uint32_t* cell, size_t count, const uint6
     return rc;
 }
 
+// The findings of the three recoveries on the host: ~0 goes up before the kernels, their minima come down after them, split for the report functions.
+struct RecoverFound {
+    std::vector<RecoverFindings> both;
+    std::vector<uint64_t> first_bad, first_bug;
+    explicit RecoverFound(int batch) : both((size_t)batch, RecoverFindings{ ~0ull, ~0ull }), first_bad((size_t)batch), first_bug((size_t)batch) {}
+    int begin(void* d_find, hipStream_t st) { return host_to_device(d_find, both.data(), both.size() * sizeof(RecoverFindings), st); }
+    int end(const void* d_find, hipStream_t st)
+    {
+        if (int rc = device_to_host_sync(both.data(), d_find, both.size() * sizeof(RecoverFindings), st)) return rc;
+        for (size_t b = 0; b < both.size(); b++) {
+            first_bad[b] = both[b].first_bad;
+            first_bug[b] = both[b].first_bug;
+        }
+        return BBGPU_OK;
+    }
+};
+
+// What bbgpu_kzg_recover_cells and bbgpu_kzg_recover_cells_each do once z (d_z) and z' x 2^-5 (d_zc) stand, z_elems elements each, and event 1 can be
+// marked: the batch inversion, scatter and IFFT, coset FFT, divide, coset IFFT and tail, the forward transform of the copy if there is one, and the
+// findings on the host.  Events 1 .. 5 are marked here; recover_cells_timing reads them once the caller has nothing left that can fail.
+static int recover_back_end(const RecoverLists& L, const uint64_t* d_vals, uint64_t* d_z, uint64_t* d_zc, size_t z_elems, size_t n, int log2n, int log2l,
+                            size_t degree_bound, int batch, uint64_t* d_coeffs_out, size_t stride_elems, uint64_t* d_copy, RecoverFindings* d_find,
+                            RecoverFound& F, StageEvents<6>& ev, void* hip_stream)
+{
+    const hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = ev.mark(1, st)) return rc;
+    if (int rc = bbgpu_fr_batch_invert_device(d_zc, z_elems, hip_stream)) return rc; // z' is never zero: g^n != 1
+    if (int rc = ev.mark(2, st)) return rc;
+    if (int rc = kzg_recover_scatter(d_vals, L, d_z, log2n, log2l, batch, d_coeffs_out, stride_elems, st)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_IFFT, nullptr, hip_stream)) return rc;
+    if (int rc = ev.mark(3, st)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_FFT, nullptr, hip_stream)) return rc;
+    if (int rc = kzg_recover_divide(d_coeffs_out, stride_elems, batch, d_zc, L, log2n, log2l, st)) return rc;
+    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_IFFT, nullptr, hip_stream)) return rc;
+    if (int rc = kzg_recover_tail(d_coeffs_out, stride_elems, batch, d_copy, log2n, log2l, degree_bound, L, d_find, st)) return rc;
+    if (int rc = ev.mark(4, st)) return rc;
+    if (d_copy) {
+        if (int rc = bbgpu_ntt_device_batch(d_copy, n, n, batch, BBGPU_FFT, nullptr, hip_stream)) return rc;
+        if (int rc = ev.mark(5, st)) return rc;
+    }
+    return F.end(d_find, st);
+}
+// bbgpu_last_timing of both: index 0 what made z and z' (the caller's, between events 0 and 1), 1 scatter and IFFT, 2 coset FFT, divide, coset IFFT and
+// tail, 3 the forward transform (if asked for)
+static int recover_cells_timing(StageEvents<6>& ev, bool forward)
+{
+    if (!ev.on) return BBGPU_OK;
+    ctx().last.count = forward ? 4 : 3;
+    if (int rc = ev.ms(0, 1, &ctx().last.ms[0])) return rc;
+    if (int rc = ev.ms(2, 3, &ctx().last.ms[1])) return rc;
+    if (int rc = ev.ms(3, 4, &ctx().last.ms[2])) return rc;
+    return forward ? ev.ms(4, 5, &ctx().last.ms[3]) : BBGPU_OK;
+}
+
 int bbgpu_kzg_recover_cells(const uint32_t* cell, size_t count, const uint64_t* values, size_t n, size_t coset, size_t degree_bound, int batch,
                             uint64_t* d_coeffs_out, size_t stride_elems, uint64_t* values_out, bbgpu_kzg_recover_report* report, void* hip_stream)
 {
@@ -4112,76 +4166,46 @@ int bbgpu_kzg_recover_cells(const uint32_t* cell, size_t count, const uint64_t* 
     }
     if (int rc = ensure_init()) return rc;
     const hipStream_t st = (hipStream_t)hip_stream;
-    const size_t m = S.m, mu = S.mu, present = count * coset;
-    struct Events { // the stage boundaries of bbgpu_last_timing, only made when timing is on
-        hipEvent_t e[8] = {};
-        ~Events()
-        {
-            for (hipEvent_t v : e)
-                if (v) (void)hipEventDestroy(v);
-        }
-    } ev;
-    const bool timed = ctx().timing != 0;
-    if (timed)
-        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
-    auto mark = [&](int k) -> int {
-        if (timed) HIPCHK(hipEventRecord(ev.e[k], st));
-        return BBGPU_OK;
-    };
-    // the cell list and the missing cells in one array | z, z' and the roots of the missing cells | the values | the findings | the copy the forward
-    // transform works in
+    const size_t m = S.m, mu = S.mu, present = count * coset, B = (size_t)batch;
+    StageEvents<6> ev; // the stage boundaries of bbgpu_last_timing
+    if (int rc = ev.create(ctx().timing != 0)) return rc;
+    // the offsets b count, batch times mu, the cell list and the missing cells (ascending) in one array | z, z' and the roots of the missing cells | the
+    // values | the findings | the copy the forward transform works in
     DevBuf lists, z, vals, find, copy;
-    HIPCHK(dev_malloc(&lists.p, m * 4));
+    const size_t list_words = (B + 1) + B + m;
+    HIPCHK(dev_malloc(&lists.p, list_words * 4));
     HIPCHK(dev_malloc(&z.p, 2 * m * 32 + mu * sizeof(Limbs9)));
-    HIPCHK(dev_malloc(&vals.p, (size_t)batch * present * 32));
-    HIPCHK(dev_malloc(&find.p, (size_t)batch * sizeof(RecoverFindings)));
-    if (values_out) HIPCHK(dev_malloc(&copy.p, (size_t)batch * n * 32));
-    uint32_t *d_cell = lists.as<uint32_t>(), *d_missing = d_cell + count;
+    HIPCHK(dev_malloc(&vals.p, B * present * 32));
+    HIPCHK(dev_malloc(&find.p, B * sizeof(RecoverFindings)));
+    if (values_out) HIPCHK(dev_malloc(&copy.p, B * n * 32));
+    std::vector<uint32_t> all(list_words);
+    for (size_t b = 0; b <= B; b++) all[b] = (uint32_t)(b * count);
+    std::fill_n(all.begin() + (B + 1), B, (uint32_t)mu);
+    std::copy(cell, cell + count, all.begin() + (2 * B + 1));
+    std::copy(S.missing.begin(), S.missing.end(), all.begin() + (2 * B + 1 + count));
+    RecoverLists L{}; // mask and strides zero: one list of cells, one row of missing cells, one z and one z' for every polynomial
+    L.d_off = lists.as<uint32_t>();
+    L.d_mu = L.d_off + B + 1;
+    L.d_cell = L.d_mu + B;
+    L.d_missing = L.d_cell + count;
     uint64_t *d_z = z.as<uint64_t>(), *d_zc = d_z + 4 * m;
     uint32_t* d_roots = reinterpret_cast<uint32_t*>(d_zc + 4 * m);
-    std::vector<uint32_t> both(cell, cell + count);
-    both.insert(both.end(), S.missing.begin(), S.missing.end());
-    std::vector<RecoverFindings> found((size_t)batch, RecoverFindings{ ~0ull, ~0ull });
-    if (int rc = host_to_device(d_cell, both.data(), m * 4, st)) return rc;
-    if (int rc = host_to_device(find.p, found.data(), found.size() * sizeof(RecoverFindings), st)) return rc;
-    if (int rc = host_to_device(vals.p, values, (size_t)batch * present * 32, st)) return rc;
-    if (int rc = mark(0)) return rc;
-    if (int rc = kzg_recover_vanish(d_missing, mu, S.log2n, S.log2l, d_roots, d_z, d_zc, st)) return rc;
-    if (int rc = mark(1)) return rc;
-    if (int rc = bbgpu_fr_batch_invert_device(d_zc, m, hip_stream)) return rc; // z' is never zero: g^n != 1
-    if (int rc = mark(2)) return rc;
-    if (int rc = kzg_recover_scatter(vals.as<uint64_t>(), d_cell, count, d_missing, d_z, S.log2n, S.log2l, batch, d_coeffs_out, stride_elems, st)) return rc;
-    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_IFFT, nullptr, hip_stream)) return rc;
-    if (int rc = mark(3)) return rc;
-    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_FFT, nullptr, hip_stream)) return rc;
-    if (int rc = kzg_recover_divide(d_coeffs_out, stride_elems, batch, d_zc, S.log2n, S.log2l, st)) return rc;
-    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_IFFT, nullptr, hip_stream)) return rc;
-    if (int rc = kzg_recover_tail(d_coeffs_out, stride_elems, batch, copy.as<uint64_t>(), S.log2n, degree_bound, present, find.as<RecoverFindings>(), st)) return rc;
-    if (int rc = mark(4)) return rc;
-    if (values_out) {
-        if (int rc = bbgpu_ntt_device_batch(copy.as<uint64_t>(), n, n, batch, BBGPU_FFT, nullptr, hip_stream)) return rc;
-        if (int rc = mark(5)) return rc;
-    }
-    if (int rc = device_to_host_sync(found.data(), find.p, found.size() * sizeof(RecoverFindings), st)) return rc;
-    std::vector<uint64_t> first_bad((size_t)batch), first_bug((size_t)batch);
-    for (int b = 0; b < batch; b++) {
-        first_bad[(size_t)b] = found[(size_t)b].first_bad;
-        first_bug[(size_t)b] = found[(size_t)b].first_bug;
-    }
-    if (int rc = host::kzg_recover_report("kzg_recover_cells", first_bad.data(), first_bug.data(), batch, mu, report, why, sizeof why)) {
+    RecoverFound F(batch);
+    if (int rc = host_to_device(lists.p, all.data(), list_words * 4, st)) return rc;
+    if (int rc = F.begin(find.p, st)) return rc;
+    if (int rc = host_to_device(vals.p, values, B * present * 32, st)) return rc;
+    if (int rc = ev.mark(0, st)) return rc;
+    if (int rc = kzg_recover_vanish(L.d_missing, mu, S.log2n, S.log2l, d_roots, d_z, d_zc, st)) return rc;
+    if (int rc = recover_back_end(L, vals.as<uint64_t>(), d_z, d_zc, m, n, S.log2n, S.log2l, degree_bound, batch, d_coeffs_out, stride_elems, copy.as<uint64_t>(),
+                                  find.as<RecoverFindings>(), F, ev, hip_stream))
+        return rc;
+    if (int rc = host::kzg_recover_report("kzg_recover_cells", F.first_bad.data(), F.first_bug.data(), batch, mu, report, why, sizeof why)) {
         set_error("%s", why);
         return rc;
     }
     if (values_out)
-        if (int rc = device_to_host_sync(values_out, copy.p, (size_t)batch * n * 32, st)) return rc;
-    if (timed) { // bbgpu_last_timing: index 0 k_recover_vanish, 1 scatter and IFFT, 2 coset FFT, divide, coset IFFT and tail, 3 the forward transform (if asked for)
-        ctx().last.count = values_out ? 4 : 3;
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[0], ev.e[0], ev.e[1]));
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[1], ev.e[2], ev.e[3]));
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[2], ev.e[3], ev.e[4]));
-        if (values_out) HIPCHK(hipEventElapsedTime(&ctx().last.ms[3], ev.e[4], ev.e[5]));
-    }
-    return BBGPU_OK;
+        if (int rc = device_to_host_sync(values_out, copy.p, B * n * 32, st)) return rc;
+    return recover_cells_timing(ev, values_out != nullptr);
 }
 
 /* ---- the same for polynomials whose cell sets differ, at any n / l (host_kzg_recover_each.hpp, kzg_recover_each.hip) ---- */
@@ -4239,21 +4263,8 @@ int bbgpu_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32_t* c
     size_t M = 1; // the common padded number of roots: a power of two, >= every mu_b, <= m (every polynomial lists a cell)
     while (M < S.max_missing) M <<= 1;
     const size_t T = std::min<size_t>(KZG_RECOVER_EACH_LEAF, M);
-    struct Events { // the stage boundaries of bbgpu_last_timing, only made when timing is on
-        hipEvent_t e[8] = {};
-        ~Events()
-        {
-            for (hipEvent_t v : e)
-                if (v) (void)hipEventDestroy(v);
-        }
-    } ev;
-    const bool timed = ctx().timing != 0;
-    if (timed)
-        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
-    auto mark = [&](int k) -> int {
-        if (timed) HIPCHK(hipEventRecord(ev.e[k], st));
-        return BBGPU_OK;
-    };
+    StageEvents<6> ev; // the stage boundaries of bbgpu_last_timing
+    if (int rc = ev.create(ctx().timing != 0)) return rc;
     // offsets, counts of missing cells, cell lists and padded missing lists in one array | the tree | the inputs of the two Z transforms, then z and z',
     // and the power table | the values | the findings | the copy the forward transform works in
     DevBuf lists, tree, z, vals, find, copy;
@@ -4271,19 +4282,21 @@ int bbgpu_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32_t* c
         std::copy(S.missing[b].begin(), S.missing[b].end(), all.begin() + (2 * B + 1 + total + b * M));
     }
     std::copy(cell, cell + total, all.begin() + (2 * B + 1));
-    KzgRecoverEachLists L{};
+    RecoverLists L{};
     L.d_off = lists.as<uint32_t>();
     L.d_mu = L.d_off + B + 1;
     L.d_cell = L.d_mu + B;
     L.d_missing = L.d_cell + total;
-    L.M = M;
+    L.cell_mask = ~0u;
+    L.missing_stride = (uint32_t)M;
+    L.z_stride = (uint32_t)m;
     uint64_t *d_tree = tree.as<uint64_t>(), *d_z = z.as<uint64_t>(), *d_zc = d_z + 4 * B * m;
     uint32_t* d_tab = reinterpret_cast<uint32_t*>(d_zc + 4 * B * m);
-    std::vector<RecoverFindings> found(B, RecoverFindings{ ~0ull, ~0ull });
+    RecoverFound F(batch);
     if (int rc = host_to_device(lists.p, all.data(), list_words * 4, st)) return rc;
-    if (int rc = host_to_device(find.p, found.data(), found.size() * sizeof(RecoverFindings), st)) return rc;
+    if (int rc = F.begin(find.p, st)) return rc;
     if (int rc = host_to_device(vals.p, values, total * coset * 32, st)) return rc;
-    if (int rc = mark(0)) return rc;
+    if (int rc = ev.mark(0, st)) return rc;
     // the tree: leaves of T roots, then one level per doubling -- forward transform of every slot, sibling products, inverse transform of every other slot
     if (int rc = kzg_recover_each_leaves(L.d_missing, batch, M, log2m, d_tree, st)) return rc;
     for (size_t D = T; D < M; D <<= 1) {
@@ -4296,46 +4309,20 @@ int bbgpu_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32_t* c
     // Z_b's coefficients, scaled for the domain and for the coset, and the 2 x batch transforms of size m that make z and z' x 2^-5 of them
     if (int rc = kzg_recover_each_gather(d_tree, L.d_mu, batch, M, S.log2n, S.log2l, d_tab, d_z, d_zc, st)) return rc;
     if (int rc = recover_each_ntt(d_z, m, 2 * B, log2m, BBGPU_FFT, st)) return rc;
-    if (int rc = mark(1)) return rc;
-    if (int rc = bbgpu_fr_batch_invert_device(d_zc, B * m, hip_stream)) return rc; // z' is never zero: g^n != 1
-    if (int rc = mark(2)) return rc;
-    if (int rc = kzg_recover_each_scatter(vals.as<uint64_t>(), L, d_z, S.log2n, S.log2l, batch, d_coeffs_out, stride_elems, st)) return rc;
-    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_IFFT, nullptr, hip_stream)) return rc;
-    if (int rc = mark(3)) return rc;
-    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_FFT, nullptr, hip_stream)) return rc;
-    if (int rc = kzg_recover_each_divide(d_coeffs_out, stride_elems, batch, d_zc, S.log2n, S.log2l, st)) return rc;
-    if (int rc = bbgpu_ntt_device_batch(d_coeffs_out, n, stride_elems, batch, BBGPU_COSET_IFFT, nullptr, hip_stream)) return rc;
-    if (int rc = kzg_recover_each_tail(d_coeffs_out, stride_elems, batch, copy.as<uint64_t>(), S.log2n, S.log2l, degree_bound, L.d_off, find.as<RecoverFindings>(), st))
+    if (int rc = recover_back_end(L, vals.as<uint64_t>(), d_z, d_zc, B * m, n, S.log2n, S.log2l, degree_bound, batch, d_coeffs_out, stride_elems,
+                                  copy.as<uint64_t>(), find.as<RecoverFindings>(), F, ev, hip_stream))
         return rc;
-    if (int rc = mark(4)) return rc;
-    if (values_out) {
-        if (int rc = bbgpu_ntt_device_batch(copy.as<uint64_t>(), n, n, batch, BBGPU_FFT, nullptr, hip_stream)) return rc;
-        if (int rc = mark(5)) return rc;
-    }
-    if (int rc = device_to_host_sync(found.data(), find.p, found.size() * sizeof(RecoverFindings), st)) return rc;
-    std::vector<uint64_t> first_bad(B), first_bug(B);
-    for (size_t b = 0; b < B; b++) {
-        first_bad[b] = found[b].first_bad;
-        first_bug[b] = found[b].first_bug;
-    }
     // the verdict into locals first: nothing of the caller's host memory is written before the last copy has succeeded
     bbgpu_kzg_recover_each_report rep;
-    if (int rc = host::kzg_recover_each_report("kzg_recover_cells_each", first_bad.data(), first_bug.data(), batch, S.max_missing, nullptr, &rep, why, sizeof why)) {
+    if (int rc = host::kzg_recover_each_report("kzg_recover_cells_each", F.first_bad.data(), F.first_bug.data(), batch, S.max_missing, nullptr, &rep, why, sizeof why)) {
         set_error("%s", why);
         return rc;
     }
     if (values_out)
         if (int rc = device_to_host_sync(values_out, copy.p, B * n * 32, st)) return rc;
     *report = rep;
-    if (first_bad_out) std::copy(first_bad.begin(), first_bad.end(), first_bad_out);
-    if (timed) { // bbgpu_last_timing: index 0 leaves, levels, gather and the two Z transforms, 1 scatter and IFFT, 2 coset FFT, divide, coset IFFT and tail, 3 the forward transform (if asked for)
-        ctx().last.count = values_out ? 4 : 3;
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[0], ev.e[0], ev.e[1]));
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[1], ev.e[2], ev.e[3]));
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[2], ev.e[3], ev.e[4]));
-        if (values_out) HIPCHK(hipEventElapsedTime(&ctx().last.ms[3], ev.e[4], ev.e[5]));
-    }
-    return BBGPU_OK;
+    if (first_bad_out) std::copy(F.first_bad.begin(), F.first_bad.end(), first_bad_out);
+    return recover_cells_timing(ev, values_out != nullptr);
 }
 
 /* ---- transforms and erasure decoding on columns of curve points (host_g1_recover.hpp, g1_recover.hip) ---- */
@@ -4422,21 +4409,8 @@ int bbgpu_g1_recover(const uint32_t* row, size_t count, const uint64_t* points, 
     const hipStream_t st = (hipStream_t)hip_stream;
     const size_t mu = S.mu, total = (size_t)batch * n;
     const int lg = S.log2n;
-    struct Events { // the stage boundaries of bbgpu_last_timing, only made when timing is on
-        hipEvent_t e[7] = {};
-        ~Events()
-        {
-            for (hipEvent_t v : e)
-                if (v) (void)hipEventDestroy(v);
-        }
-    } ev;
-    const bool timed = ctx().timing != 0;
-    if (timed)
-        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
-    auto mark = [&](int k) -> int {
-        if (timed) HIPCHK(hipEventRecord(ev.e[k], st));
-        return BBGPU_OK;
-    };
+    StageEvents<7> ev; // the stage boundaries of bbgpu_last_timing
+    if (int rc = ev.create(ctx().timing != 0)) return rc;
     // the place of every row in the list and the missing rows | z, z', the four scalar tables and the roots of the missing rows | the points | the
     // findings | the two scratches (the first one takes the affine results at the end)
     DevBuf lists, zt, in, find, scratch;
@@ -4453,55 +4427,50 @@ int bbgpu_g1_recover(const uint32_t* row, size_t count, const uint64_t* points, 
     std::vector<uint32_t> both(2 * n, ~0u);
     for (size_t t = 0; t < count; t++) both[row[t]] = (uint32_t)t;
     std::copy(S.missing.begin(), S.missing.end(), both.begin() + (ptrdiff_t)n);
-    std::vector<RecoverFindings> found((size_t)batch, RecoverFindings{ ~0ull, ~0ull });
+    RecoverFound F(batch);
     if (int rc = host_to_device(lists.p, both.data(), 2 * n * 4, st)) return rc;
-    if (int rc = host_to_device(find.p, found.data(), found.size() * sizeof(RecoverFindings), st)) return rc;
+    if (int rc = F.begin(find.p, st)) return rc;
     if (int rc = host_to_device(in.p, points, (size_t)batch * count * 64, st)) return rc;
     host::Fr winv, ninv;
     host::srs_lagrange_constants(lg, &winv, &ninv);
     const host::Fr w = host::fr_root_of_unity(lg), g = host::fr_from_limbs(FrHostP::GEN5);
-    if (int rc = mark(0)) return rc;
+    if (int rc = ev.mark(0, st)) return rc;
     if (int rc = kzg_recover_vanish(d_missing, mu, lg, 0, d_roots, d_z, d_zc, st)) return rc;
-    if (int rc = mark(1)) return rc;
+    if (int rc = ev.mark(1, st)) return rc;
     if (int rc = bbgpu_fr_batch_invert_device(d_zc, n, hip_stream)) return rc; // z' is never zero: g^n != 1
     if (int rc = g1_cols_scalars(d_z, d_zc, d_tabs, lg, host::limbs_m256(ninv).d, host::limbs_m261(g).d, host::limbs_m261(host::fr_inv(g)).d, st)) return rc;
-    if (int rc = mark(2)) return rc;
+    if (int rc = ev.mark(2, st)) return rc;
     if (int rc = g1_cols_load(in.as<uint32_t>(), count, d_slot_of, d_kz, nullptr, A, lg, batch, st)) return rc;
     if (int rc = g1_transform_dispatch(A, lg, batch, winv, st)) return rc;
-    if (int rc = mark(3)) return rc;
+    if (int rc = ev.mark(3, st)) return rc;
     if (int rc = g1_cols_scale(A, B, d_kg, lg, batch, st)) return rc;
     if (int rc = g1_transform_dispatch(B, lg, batch, w, st)) return rc;
     if (int rc = g1_cols_scale(B, A, d_kq, lg, batch, st)) return rc;
     if (int rc = g1_transform_dispatch(A, lg, batch, winv, st)) return rc;
     if (int rc = g1_cols_scale(A, B, d_kgi, lg, batch, st)) return rc;
     if (int rc = g1_cols_verdict(B, lg, batch, degree_bound, count, find.as<RecoverFindings>(), st)) return rc;
-    if (int rc = mark(4)) return rc;
+    if (int rc = ev.mark(4, st)) return rc;
     if (int rc = g1_transform_dispatch(B, lg, batch, w, st)) return rc;
-    if (int rc = mark(6)) return rc;
+    if (int rc = ev.mark(6, st)) return rc;
     if (int rc = g1_cols_finish(B, A, lg, batch, st)) return rc;
-    if (int rc = mark(5)) return rc;
-    if (int rc = device_to_host_sync(found.data(), find.p, found.size() * sizeof(RecoverFindings), st)) return rc;
-    std::vector<uint64_t> first_bad((size_t)batch), first_bug((size_t)batch);
-    for (int b = 0; b < batch; b++) {
-        first_bad[(size_t)b] = found[(size_t)b].first_bad;
-        first_bug[(size_t)b] = found[(size_t)b].first_bug;
-    }
+    if (int rc = ev.mark(5, st)) return rc;
+    if (int rc = F.end(find.p, st)) return rc;
     // the verdict into a local first: nothing of the caller's host memory is written before the last copy has succeeded
     bbgpu_g1_recover_report rep;
-    if (int rc = host::g1_recover_report_of("g1_recover", first_bad.data(), first_bug.data(), batch, mu, &rep, why, sizeof why)) {
+    if (int rc = host::g1_recover_report_of("g1_recover", F.first_bad.data(), F.first_bug.data(), batch, mu, &rep, why, sizeof why)) {
         set_error("%s", why);
         return rc;
     }
     if (int rc = device_to_host_sync(points_out, A, total * 64, st)) return rc;
     *report = rep;
-    if (timed) { // bbgpu_last_timing: 0 the vanishing values, 1 load and IFFT, 2 shift, FFT, divide, IFFT, unshift and verdict, 3 the last FFT and the finish,
+    if (ev.on) { // bbgpu_last_timing: 0 the vanishing values, 1 load and IFFT, 2 shift, FFT, divide, IFFT, unshift and verdict, 3 the last FFT and the finish,
                  // 4 the finish alone (a part of 3)
         ctx().last.count = 5;
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[4], ev.e[6], ev.e[5]));
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[0], ev.e[0], ev.e[1]));
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[1], ev.e[2], ev.e[3]));
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[2], ev.e[3], ev.e[4]));
-        HIPCHK(hipEventElapsedTime(&ctx().last.ms[3], ev.e[4], ev.e[5]));
+        if (int rc = ev.ms(6, 5, &ctx().last.ms[4])) return rc;
+        if (int rc = ev.ms(0, 1, &ctx().last.ms[0])) return rc;
+        if (int rc = ev.ms(2, 3, &ctx().last.ms[1])) return rc;
+        if (int rc = ev.ms(3, 4, &ctx().last.ms[2])) return rc;
+        if (int rc = ev.ms(4, 5, &ctx().last.ms[3])) return rc;
     }
     return BBGPU_OK;
 }

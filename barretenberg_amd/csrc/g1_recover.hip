@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "bbgpu_internal.h"
+#include "fr_mem_device.hpp"
 #include "g1_stage.hpp"
 
 namespace bbgpu {
@@ -245,22 +246,7 @@ __global__ void __launch_bounds__(FT) k_g1_verdict(const uint32_t* __restrict__ 
             else bug = min(bug, j);
         }
     }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        bad = min(bad, (uint32_t)__shfl_xor((int)bad, o));
-        bug = min(bug, (uint32_t)__shfl_xor((int)bug, o));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_bad[threadIdx.x >> 6] = bad;
-        s_bug[threadIdx.x >> 6] = bug;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-#pragma unroll
-    for (int k = 1; k < FT / 64; k++) {
-        bad = min(bad, s_bad[k]);
-        bug = min(bug, s_bug[k]);
-    }
+    if (!min_pair_to_thread0<FT>(bad, bug, s_bad, s_bug)) return;
     if (bad != ~0u) find[b].first_bad = bad;
     if (bug != ~0u) find[b].first_bug = bug;
 }

@@ -30,16 +30,23 @@ struct KzgRecoverShape {
     std::vector<uint32_t> missing; // the mu cells that are not listed, ascending
 };
 
+// log2 n and log2 of the coset size where they are powers of two within the limits above, else -1 (both verdicts, each with its own text)
+static inline void kzg_recover_log2s(size_t n, size_t coset, int* log2n, int* log2l)
+{
+    *log2n = *log2l = -1;
+    for (int k = 1; k <= KZG_RECOVER_MAX_LOG2; k++)
+        if (n == (size_t)1 << k) *log2n = k;
+    for (int c = 0; c <= KZG_RECOVER_MAX_COSET_LOG2; c++)
+        if (coset == (size_t)1 << c) *log2l = c;
+}
+
 // The verdict on a call's arguments, in the order of include/bbgpu.h: sizes (BBGPU_ERR_SIZE), then pointers and the cell list (BBGPU_ERR_ARG); `why`
 // gets the text.  Nothing is read before it is known to be there; on BBGPU_OK *S holds the shape and the missing cells.
 static inline int kzg_recover_verdict(const char* what, const uint32_t* cell, size_t count, const void* values, size_t n, size_t coset, size_t degree_bound,
                                       int batch, const void* coeffs_out, size_t stride_elems, const void* report, KzgRecoverShape* S, char* why, size_t why_len)
 {
-    int log2n = -1, log2l = -1;
-    for (int k = 1; k <= KZG_RECOVER_MAX_LOG2; k++)
-        if (n == (size_t)1 << k) log2n = k;
-    for (int c = 0; c <= KZG_RECOVER_MAX_COSET_LOG2; c++)
-        if (coset == (size_t)1 << c) log2l = c;
+    int log2n, log2l;
+    kzg_recover_log2s(n, coset, &log2n, &log2l);
     if (log2n < 0 || log2l < 0 || log2n - log2l < 1 || log2n - log2l > KZG_RECOVER_MAX_CELLS_LOG2) {
         snprintf(why, why_len, "%s: n = %zu must be a power of two between 2 and 2^%d, the coset size (%zu) a power of two between 1 and %d, and n / coset between 2 and 2^%d",
                  what, n, KZG_RECOVER_MAX_LOG2, coset, 1 << KZG_RECOVER_MAX_COSET_LOG2, KZG_RECOVER_MAX_CELLS_LOG2);
@@ -139,6 +146,40 @@ static inline void kzg_recover_vanishing_host(const KzgRecoverShape& S, std::vec
     });
 }
 
+// ONE polynomial of either twin (host_kzg_recover_each.hpp loops over this too): its `count` listed cells and their count x l values, z and 1 / z' of
+// ITS missing cells (kzg_recover_vanishing_host) -> the n coefficients at coeffs_out, the n values at values_out unless that is null, and the smallest
+// index in [d, count l) and in [count l, n) with a nonzero coefficient (~0 for none).  work: 4 n words of the caller's, overwritten.
+static inline void kzg_recover_one_host(const KzgRecoverShape& S, const uint32_t* cell, size_t count, const uint64_t* values, const std::vector<Fr>& z,
+                                        const std::vector<Fr>& zc_inv, size_t degree_bound, std::vector<uint64_t>& work, uint64_t* first_bad, uint64_t* first_bug,
+                                        uint64_t* coeffs_out, uint64_t* values_out)
+{
+    const size_t n = S.n, l = S.l, m = S.m, present = count * l;
+    const Fr one = fr_one();
+    Fr* E = reinterpret_cast<Fr*>(work.data());
+    for (size_t i = 0; i < n; i++) E[i] = fr_zero();
+    for (size_t t = 0; t < count; t++)
+        for (size_t j = 0; j < l; j++) {
+            Fr x;
+            memcpy(x.d, values + 4 * (t * l + j), 32);
+            E[cell[t] + m * j] = fr_mul(fr_mul(x, one), z[cell[t]]); // any representative below 2^256 -> the field
+        }
+    ntt_radix2(work.data(), S.log2n, BBGPU_IFFT, nullptr);
+    ntt_radix2(work.data(), S.log2n, BBGPU_COSET_FFT, nullptr);
+    for (size_t i = 0; i < n; i++) E[i] = fr_mul(E[i], zc_inv[i & (m - 1)]);
+    ntt_radix2(work.data(), S.log2n, BBGPU_COSET_IFFT, nullptr);
+    *first_bad = *first_bug = ~0ull;
+    for (size_t i = degree_bound; i < n; i++) {
+        if (fr_is_zero(E[i])) continue;
+        uint64_t& first = i < present ? *first_bad : *first_bug;
+        if (first == ~0ull) first = i;
+    }
+    memcpy(coeffs_out, work.data(), n * 32);
+    if (values_out) {
+        ntt_radix2(work.data(), S.log2n, BBGPU_FFT, nullptr);
+        memcpy(values_out, work.data(), n * 32);
+    }
+}
+
 // The twin behind its verdict.  coeffs_out: batch x stride_elems x 4 in host memory, [0, n) of every polynomial written; values_out: null or batch x n x 4
 static inline int kzg_recover_cells_host(const KzgRecoverShape& S, const uint32_t* cell, size_t count, const uint64_t* values, size_t degree_bound, int batch,
                                          uint64_t* coeffs_out, size_t stride_elems, uint64_t* values_out, bbgpu_kzg_recover_report* report, char* why,
@@ -146,35 +187,10 @@ static inline int kzg_recover_cells_host(const KzgRecoverShape& S, const uint32_
 {
     std::vector<Fr> z, zc_inv;
     kzg_recover_vanishing_host(S, z, zc_inv);
-    const size_t n = S.n, l = S.l, m = S.m, present = count * l;
-    const Fr one = fr_one();
-    std::vector<uint64_t> first_bad((size_t)batch, ~0ull), first_bug((size_t)batch, ~0ull);
-    std::vector<uint64_t> work(4 * n);
-    Fr* E = reinterpret_cast<Fr*>(work.data());
-    for (int b = 0; b < batch; b++) {
-        for (size_t i = 0; i < n; i++) E[i] = fr_zero();
-        const uint64_t* v = values + (size_t)b * present * 4;
-        for (size_t t = 0; t < count; t++)
-            for (size_t j = 0; j < l; j++) {
-                Fr x;
-                memcpy(x.d, v + 4 * (t * l + j), 32);
-                E[cell[t] + m * j] = fr_mul(fr_mul(x, one), z[cell[t]]); // any representative below 2^256 -> the field
-            }
-        ntt_radix2(work.data(), S.log2n, BBGPU_IFFT, nullptr);
-        ntt_radix2(work.data(), S.log2n, BBGPU_COSET_FFT, nullptr);
-        for (size_t i = 0; i < n; i++) E[i] = fr_mul(E[i], zc_inv[i & (m - 1)]);
-        ntt_radix2(work.data(), S.log2n, BBGPU_COSET_IFFT, nullptr);
-        for (size_t i = degree_bound; i < n; i++) {
-            if (fr_is_zero(E[i])) continue;
-            uint64_t& first = i < present ? first_bad[(size_t)b] : first_bug[(size_t)b];
-            if (first == ~0ull) first = i;
-        }
-        memcpy(coeffs_out + (size_t)b * stride_elems * 4, work.data(), n * 32);
-        if (values_out) {
-            ntt_radix2(work.data(), S.log2n, BBGPU_FFT, nullptr);
-            memcpy(values_out + (size_t)b * n * 4, work.data(), n * 32);
-        }
-    }
+    std::vector<uint64_t> first_bad((size_t)batch), first_bug((size_t)batch), work(4 * S.n);
+    for (size_t b = 0; b < (size_t)batch; b++)
+        kzg_recover_one_host(S, cell, count, values + b * count * S.l * 4, z, zc_inv, degree_bound, work, &first_bad[b], &first_bug[b],
+                             coeffs_out + b * stride_elems * 4, values_out ? values_out + b * S.n * 4 : nullptr);
     return kzg_recover_report("host kzg_recover_cells", first_bad.data(), first_bug.data(), batch, S.mu, report, why, why_len);
 }
 

@@ -29,11 +29,8 @@ static inline int kzg_recover_each_verdict(const char* what, const uint32_t* cel
                                            size_t degree_bound, int batch, const void* coeffs_out, size_t stride_elems, const void* report,
                                            KzgRecoverEachShape* S, char* why, size_t why_len)
 {
-    int log2n = -1, log2l = -1;
-    for (int k = 1; k <= KZG_RECOVER_MAX_LOG2; k++)
-        if (n == (size_t)1 << k) log2n = k;
-    for (int c = 0; c <= KZG_RECOVER_MAX_COSET_LOG2; c++)
-        if (coset == (size_t)1 << c) log2l = c;
+    int log2n, log2l;
+    kzg_recover_log2s(n, coset, &log2n, &log2l);
     if (log2n < 0 || log2l < 0 || log2n - log2l < 1) {
         snprintf(why, why_len, "%s: n = %zu must be a power of two between 2 and 2^%d, the coset size (%zu) a power of two between 1 and %d, and n / coset at least 2", what,
                  n, KZG_RECOVER_MAX_LOG2, coset, 1 << KZG_RECOVER_MAX_COSET_LOG2);
@@ -138,46 +135,20 @@ static inline int kzg_recover_cells_each_host(const KzgRecoverEachShape& S, cons
                                               size_t degree_bound, int batch, uint64_t* coeffs_out, size_t stride_elems, uint64_t* values_out,
                                               uint64_t* first_bad_out, bbgpu_kzg_recover_each_report* report, char* why, size_t why_len)
 {
-    const size_t n = S.n, l = S.l, m = S.m;
-    const Fr one = fr_one();
-    std::vector<uint64_t> first_bad((size_t)batch, ~0ull), first_bug((size_t)batch, ~0ull);
-    std::vector<uint64_t> work(4 * n);
-    Fr* E = reinterpret_cast<Fr*>(work.data());
+    std::vector<uint64_t> first_bad((size_t)batch), first_bug((size_t)batch), work(4 * S.n);
     KzgRecoverShape P; // the shape of one polynomial, as the same-set twin sees it
     P.log2n = S.log2n;
     P.log2l = S.log2l;
-    P.n = n;
-    P.l = l;
-    P.m = m;
+    P.n = S.n;
+    P.l = S.l;
+    P.m = S.m;
     std::vector<Fr> z, zc_inv;
-    for (int b = 0; b < batch; b++) {
-        P.missing = S.missing[(size_t)b];
+    for (size_t b = 0; b < (size_t)batch; b++) {
+        P.missing = S.missing[b];
         P.mu = P.missing.size();
         kzg_recover_vanishing_host(P, z, zc_inv);
-        const uint32_t* c = cell + cell_offsets[b];
-        const size_t count = cell_offsets[b + 1] - cell_offsets[b], present = count * l;
-        const uint64_t* v = values + (size_t)cell_offsets[b] * l * 4;
-        for (size_t i = 0; i < n; i++) E[i] = fr_zero();
-        for (size_t t = 0; t < count; t++)
-            for (size_t j = 0; j < l; j++) {
-                Fr x;
-                memcpy(x.d, v + 4 * (t * l + j), 32);
-                E[c[t] + m * j] = fr_mul(fr_mul(x, one), z[c[t]]); // any representative below 2^256 -> the field
-            }
-        ntt_radix2(work.data(), S.log2n, BBGPU_IFFT, nullptr);
-        ntt_radix2(work.data(), S.log2n, BBGPU_COSET_FFT, nullptr);
-        for (size_t i = 0; i < n; i++) E[i] = fr_mul(E[i], zc_inv[i & (m - 1)]);
-        ntt_radix2(work.data(), S.log2n, BBGPU_COSET_IFFT, nullptr);
-        for (size_t i = degree_bound; i < n; i++) {
-            if (fr_is_zero(E[i])) continue;
-            uint64_t& first = i < present ? first_bad[(size_t)b] : first_bug[(size_t)b];
-            if (first == ~0ull) first = i;
-        }
-        memcpy(coeffs_out + (size_t)b * stride_elems * 4, work.data(), n * 32);
-        if (values_out) {
-            ntt_radix2(work.data(), S.log2n, BBGPU_FFT, nullptr);
-            memcpy(values_out + (size_t)b * n * 4, work.data(), n * 32);
-        }
+        kzg_recover_one_host(P, cell + cell_offsets[b], cell_offsets[b + 1] - cell_offsets[b], values + (size_t)cell_offsets[b] * S.l * 4, z, zc_inv, degree_bound,
+                             work, &first_bad[b], &first_bug[b], coeffs_out + b * stride_elems * 4, values_out ? values_out + b * S.n * 4 : nullptr);
     }
     return kzg_recover_each_report("host kzg_recover_cells_each", first_bad.data(), first_bug.data(), batch, S.max_missing, first_bad_out, report, why, why_len);
 }

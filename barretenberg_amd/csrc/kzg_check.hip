@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "bbgpu_internal.h"
+#include "fr_mem_device.hpp"
 #include "fr_sum_device.hpp"
 #include "g1.hpp"
 #include "keccak_device.hpp"
@@ -17,21 +18,6 @@ namespace {
 
 constexpr int CT = 256; // threads per workgroup, every kernel here
 using F2 = Fe<FrP, 1, 2>; // a product
-
-__device__ __forceinline__ void ld8(const uint64_t* p, uint32_t (&w)[8])
-{
-    const ulonglong2* q = reinterpret_cast<const ulonglong2*>(p);
-    const ulonglong2 a = q[0], b = q[1];
-    w[0] = (uint32_t)a.x; w[1] = (uint32_t)(a.x >> 32); w[2] = (uint32_t)a.y; w[3] = (uint32_t)(a.y >> 32);
-    w[4] = (uint32_t)b.x; w[5] = (uint32_t)(b.x >> 32); w[6] = (uint32_t)b.y; w[7] = (uint32_t)(b.y >> 32);
-}
-__device__ __forceinline__ void st8(uint64_t* p, const uint32_t (&w)[8], bool zero)
-{
-    ulonglong2* q = reinterpret_cast<ulonglong2*>(p);
-    const uint64_t v0 = w[0] | ((uint64_t)w[1] << 32), v1 = w[2] | ((uint64_t)w[3] << 32), v2 = w[4] | ((uint64_t)w[5] << 32), v3 = w[6] | ((uint64_t)w[7] << 32);
-    q[0] = make_ulonglong2(zero ? 0 : v0, zero ? 0 : v1);
-    q[1] = make_ulonglong2(zero ? 0 : v2, zero ? 0 : v3);
-}
 
 // ---- k_kzg_claims: ONE CLAIM PER THREAD, strided ---------------------------------------------------------------------------------------------------------
 // A claim is independent of every other: one Keccak permutation (rho_t), one or two curve tests (k_srs_on_curve's: y y + (K p - x^2) x in one shared
@@ -203,12 +189,6 @@ __device__ __forceinline__ void put_slot(const uint64_t (&s)[4], uint32_t k, uin
     ulonglong2* o2 = reinterpret_cast<ulonglong2*>(out + 4 * (size_t)k);
     o2[0] = make_ulonglong2(skip ? 0 : v[0], skip ? 0 : v[1]);
     o2[1] = make_ulonglong2(skip ? 0 : v[2], skip ? 0 : v[3]);
-}
-__device__ __forceinline__ void ld4(const uint64_t* p, uint64_t (&v)[4])
-{
-    const ulonglong2* q = reinterpret_cast<const ulonglong2*>(p);
-    const ulonglong2 lo = q[0], hi = q[1];
-    v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
 }
 struct KzgFoldArgs {
     const uint64_t *term_y, *term_rho;

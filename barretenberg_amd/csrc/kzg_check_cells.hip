@@ -2,13 +2,15 @@
 // capi.hip) that are not an MSM: the per-cell rows and scalars, the coefficients of every cell's interpolation polynomial under the random multipliers,
 // and the sums over the cells of the scalars on the shared commitments and on P_0 .. P_(l-1).  The definition all follow is host_kzg_check_cells.hpp's
 // kzg_cells_host (the host twin); the sums A and B are the existing device MSM over the rows and scalars written here, the pairing is host code
-// (host_pairing.hpp).  The reference has no check of cell proofs.  The helpers shared with kzg_check.hip (16-byte loads and stores, the curve test of a
-// claim's point, the tree of canonical additions) are restated here: that file's kernels keep their own.
+// (host_pairing.hpp).  The reference has no check of cell proofs.  The 16-byte loads and stores and the square-and-multiply are
+// fr_mem_device.hpp's; the curve test of a claim's point and the tree of canonical additions are restated from kzg_check.hip: that file's kernels keep
+// their own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "bbgpu_internal.h"
+#include "fr_mem_device.hpp"
 #include "fr_sum_device.hpp"
 #include "g1.hpp"
 #include "keccak_device.hpp"
@@ -19,40 +21,6 @@ namespace {
 
 constexpr int CT = 256; // threads per workgroup, every kernel here
 using F2 = Fe<FrP, 1, 2>; // a product
-
-__device__ __forceinline__ void ld8(const uint64_t* p, uint32_t (&w)[8])
-{
-    const ulonglong2* q = reinterpret_cast<const ulonglong2*>(p);
-    const ulonglong2 a = q[0], b = q[1];
-    w[0] = (uint32_t)a.x; w[1] = (uint32_t)(a.x >> 32); w[2] = (uint32_t)a.y; w[3] = (uint32_t)(a.y >> 32);
-    w[4] = (uint32_t)b.x; w[5] = (uint32_t)(b.x >> 32); w[6] = (uint32_t)b.y; w[7] = (uint32_t)(b.y >> 32);
-}
-__device__ __forceinline__ void st8(uint64_t* p, const uint32_t (&w)[8], bool zero)
-{
-    ulonglong2* q = reinterpret_cast<ulonglong2*>(p);
-    const uint64_t v0 = w[0] | ((uint64_t)w[1] << 32), v1 = w[2] | ((uint64_t)w[3] << 32), v2 = w[4] | ((uint64_t)w[5] << 32), v3 = w[6] | ((uint64_t)w[7] << 32);
-    q[0] = make_ulonglong2(zero ? 0 : v0, zero ? 0 : v1);
-    q[1] = make_ulonglong2(zero ? 0 : v2, zero ? 0 : v3);
-}
-__device__ __forceinline__ void ld4(const uint64_t* p, uint64_t (&v)[4])
-{
-    const ulonglong2* q = reinterpret_cast<const ulonglong2*>(p);
-    const ulonglong2 lo = q[0], hi = q[1];
-    v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
-}
-// base^e over the low `bits` bits of e, most significant first: the same trip count on every lane
-__device__ __forceinline__ F2 pow_bits(const FeT<FrP>& base, uint32_t e, int bits)
-{
-    F2 acc = fe_one<FrP>();
-    for (int b = bits - 1; b >= 0; --b) {
-        acc = sqr(acc);
-        const F2 m = mul(acc, base);
-        const bool take = ((e >> b) & 1u) != 0;
-#pragma unroll
-        for (int i = 0; i < NL; i++) acc.d[i] = take ? m.d[i] : acc.d[i];
-    }
-    return acc;
-}
 
 // ---- k_kzg_cells: ONE CELL PER THREAD, strided -------------------------------------------------------------------------------------------------------------
 // What k_kzg_claims<false, false> does per claim, for a cell: one Keccak permutation (rho_t, kept for the coefficient kernel and the fold), the curve
@@ -347,16 +315,8 @@ int kzg_cells_claims(const KzgCellsBuffers& B, const uint64_t seed[4], size_t co
 int kzg_cells_coefficients(const KzgCellsBuffers& B, size_t count, int log2n, int log2l, const uint32_t omega_inv_m261[9], const uint32_t into_m261[9],
                            hipStream_t st, float* ms)
 {
-    struct Events {
-        hipEvent_t e[2] = { nullptr, nullptr };
-        ~Events()
-        {
-            for (hipEvent_t v : e)
-                if (v) (void)hipEventDestroy(v);
-        }
-    } ev;
-    if (ms)
-        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
+    StageEvents<2> ev;
+    if (int rc = ev.create(ms != nullptr)) return rc;
     KzgCoefArgs P{};
     P.values = B.values;
     P.cell = B.cell;
@@ -370,14 +330,14 @@ int kzg_cells_coefficients(const KzgCellsBuffers& B, size_t count, int log2n, in
     P.into = to_limbs9(into_m261);
     const size_t per = (size_t)CT >> log2l; // cells per workgroup
     const uint32_t blocks = (uint32_t)std::min<size_t>((count + per - 1) / per, KZG_CELLS_COEF_MAX_BLOCKS);
-    if (ms) HIPCHK(hipEventRecord(ev.e[0], st));
+    if (int rc = ev.mark(0, st)) return rc;
     if (B.cell) k_kzg_cell_coefficients<false><<<blocks, CT, 0, st>>>(P);
     else k_kzg_cell_coefficients<true><<<blocks, CT, 0, st>>>(P);
     HIPCHK(launch_check());
     if (ms) {
-        HIPCHK(hipEventRecord(ev.e[1], st));
+        if (int rc = ev.mark(1, st)) return rc;
         HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipEventElapsedTime(ms, ev.e[0], ev.e[1]));
+        if (int rc = ev.ms(0, 1, ms)) return rc;
     }
     return BBGPU_OK;
 }

@@ -193,32 +193,25 @@ int kzg_open_all_t(const uint64_t* d_coeffs, size_t stride_elems, int batch, siz
 int kzg_open_all_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scratch, size_t n, int log2n, int batch, const uint32_t c32[9], const uint32_t Winv[9],
                        const uint32_t omega[9], hipStream_t st, float* ms4)
 {
-    struct Events {
-        hipEvent_t e[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-        ~Events()
-        {
-            for (hipEvent_t v : e)
-                if (v) (void)hipEventDestroy(v);
-        }
-    } ev;
-    if (ms4)
-        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
+    StageEvents<5> ev;
+    if (int rc = ev.create(ms4 != nullptr)) return rc;
     const uint32_t n32 = (uint32_t)n, N = 2 * n32, lg = (uint32_t)log2n, lgN = lg + 1, nb = (uint32_t)batch;
-    if (ms4) HIPCHK(hipEventRecord(ev.e[0], st));
+    if (int rc = ev.mark(0, st)) return rc;
     k_open_all_load<<<dim3(blocks_of(N, LT), nb), LT, 0, st>>>((const uint32_t*)d_that, d_S, d_scratch, N, lgN, to_limbs9(c32));
-    if (ms4) HIPCHK(hipEventRecord(ev.e[1], st));
+    if (int rc = ev.mark(1, st)) return rc;
     const Limbs9 wi = to_limbs9(Winv), om = to_limbs9(omega);
     for (uint32_t s = 0; s < lgN; s++) k_lagrange_stage<<<dim3(blocks_of(N / 2, LT), nb), LT, 0, st>>>(d_scratch, N, lgN, s, wi, (size_t)N);
-    if (ms4) HIPCHK(hipEventRecord(ev.e[2], st));
+    if (int rc = ev.mark(2, st)) return rc;
     k_open_all_gather<<<dim3(blocks_of(n32, FT), nb), FT, 0, st>>>(d_scratch, n32, lg);
     for (uint32_t s = 0; s < lg; s++) k_lagrange_stage<<<dim3(blocks_of(n32 / 2, LT), nb), LT, 0, st>>>(d_scratch + (size_t)n32 * 32, n32, lg, s, om, (size_t)N);
-    if (ms4) HIPCHK(hipEventRecord(ev.e[3], st));
+    if (int rc = ev.mark(3, st)) return rc;
     k_open_all_finish<<<dim3(blocks_of(n32, FT), nb), FT, 0, st>>>(d_scratch, (uint32_t*)d_that, n32);
     HIPCHK(launch_check()); // the chain: load, stages, gather, stages, finish
     if (ms4) {
-        HIPCHK(hipEventRecord(ev.e[4], st));
+        if (int rc = ev.mark(4, st)) return rc;
         HIPCHK(hipStreamSynchronize(st));
-        for (int i = 0; i < 4; i++) HIPCHK(hipEventElapsedTime(&ms4[i], ev.e[i], ev.e[i + 1]));
+        for (int i = 0; i < 4; i++)
+            if (int rc = ev.ms(i, i + 1, &ms4[i])) return rc;
     }
     return BBGPU_OK;
 }

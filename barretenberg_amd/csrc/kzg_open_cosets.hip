@@ -248,34 +248,27 @@ int kzg_open_cosets_t(const uint64_t* d_coeffs, size_t stride_elems, int batch, 
 int kzg_open_cosets_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scratch, int log2n, int log2l, int log2d, int batch, const uint32_t c32[9],
                           const uint32_t Winv[9], const uint32_t psi[9], hipStream_t st, float* ms4)
 {
-    struct Events {
-        hipEvent_t e[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-        ~Events()
-        {
-            for (hipEvent_t v : e)
-                if (v) (void)hipEventDestroy(v);
-        }
-    } ev;
-    if (ms4)
-        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
+    StageEvents<5> ev;
+    if (int rc = ev.create(ms4 != nullptr)) return rc;
     const uint32_t lgl = (uint32_t)log2l, lgm = (uint32_t)(log2n - log2l), lgmu = (uint32_t)(log2d - log2l), lgM = lgmu + 1, lgrho = lgm - lgmu;
     const uint32_t m = 1u << lgm, M = 2u << lgmu, nb = (uint32_t)batch;
     const size_t slots = 2 * (size_t)m; // per polynomial
-    if (ms4) HIPCHK(hipEventRecord(ev.e[0], st));
+    if (int rc = ev.mark(0, st)) return rc;
     k_open_cosets_sum<<<dim3(blocks_of(M << lgl, LT), nb), LT, 0, st>>>((const uint32_t*)d_that, d_S, d_scratch, M, lgM, lgl, to_limbs9(c32), slots);
-    if (ms4) HIPCHK(hipEventRecord(ev.e[1], st));
+    if (int rc = ev.mark(1, st)) return rc;
     const Limbs9 wi = to_limbs9(Winv), ps = to_limbs9(psi);
     for (uint32_t s = 0; s < lgM; s++) k_lagrange_stage<<<dim3(blocks_of(M / 2, LT), nb), LT, 0, st>>>(d_scratch, M, lgM, s, wi, slots);
-    if (ms4) HIPCHK(hipEventRecord(ev.e[2], st));
+    if (int rc = ev.mark(2, st)) return rc;
     k_open_cosets_gather<<<dim3(blocks_of(m, FT), nb), FT, 0, st>>>(d_scratch, m, lgmu, lgrho);
     for (uint32_t s = lgrho; s < lgm; s++) k_lagrange_stage<<<dim3(blocks_of(m / 2, LT), nb), LT, 0, st>>>(d_scratch + (size_t)m * 32, m, lgm, s, ps, slots);
-    if (ms4) HIPCHK(hipEventRecord(ev.e[3], st));
+    if (int rc = ev.mark(3, st)) return rc;
     k_open_cosets_finish<<<dim3(blocks_of(m, FT), nb), FT, 0, st>>>(d_scratch, (uint32_t*)d_that, m);
     HIPCHK(launch_check()); // the chain: sum, stages, gather, stages, finish
     if (ms4) {
-        HIPCHK(hipEventRecord(ev.e[4], st));
+        if (int rc = ev.mark(4, st)) return rc;
         HIPCHK(hipStreamSynchronize(st));
-        for (int i = 0; i < 4; i++) HIPCHK(hipEventElapsedTime(&ms4[i], ev.e[i], ev.e[i + 1]));
+        for (int i = 0; i < 4; i++)
+            if (int rc = ev.ms(i, i + 1, &ms4[i])) return rc;
     }
     return BBGPU_OK;
 }

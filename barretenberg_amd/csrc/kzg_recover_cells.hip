@@ -3,13 +3,16 @@
 // and the tail that canonicalises the coefficients and looks for the ones that must be zero.  The definition all follow is
 // host_kzg_recover_cells.hpp's kzg_recover_cells_host (the host twin).  The reference has no recovery.  Notation: l = 2^log2l values per cell, m =
 // 2^log2m cells per polynomial, n = l m, psi = omega^l the m-th root, K the mu missing cells (ascending), g the coset generator of BBGPU_COSET_FFT.
-// The 16-byte loads and stores and the square-and-multiply are restated from kzg_check_cells.hip: that file's kernels keep their own.
+// Scatter, divide and tail are also the back end of bbgpu_kzg_recover_cells_each (kzg_recover_each.hip has what only that entry needs): they read every
+// polynomial's lists through RecoverLists (bbgpu_internal.h).  The 16-byte loads and stores, the square-and-multiply and the workgroup minimum of the
+// findings are fr_mem_device.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "bbgpu_internal.h"
 #include "fe.hpp"
+#include "fr_mem_device.hpp"
 #include "host_fr.hpp"
 
 namespace bbgpu {
@@ -20,34 +23,6 @@ constexpr int CT = 256; // threads per workgroup, every kernel here
 constexpr int RT = KZG_RECOVER_TILE; // roots per LDS tile of k_recover_vanish
 static_assert(RT == CT, "k_recover_vanish: thread tid stages root tid of a tile");
 using F2 = Fe<FrP, 1, 2>; // a product
-
-__device__ __forceinline__ void ld8(const uint64_t* p, uint32_t (&w)[8])
-{
-    const ulonglong2* q = reinterpret_cast<const ulonglong2*>(p);
-    const ulonglong2 a = q[0], b = q[1];
-    w[0] = (uint32_t)a.x; w[1] = (uint32_t)(a.x >> 32); w[2] = (uint32_t)a.y; w[3] = (uint32_t)(a.y >> 32);
-    w[4] = (uint32_t)b.x; w[5] = (uint32_t)(b.x >> 32); w[6] = (uint32_t)b.y; w[7] = (uint32_t)(b.y >> 32);
-}
-__device__ __forceinline__ void st8(uint64_t* p, const uint32_t (&w)[8], bool zero)
-{
-    ulonglong2* q = reinterpret_cast<ulonglong2*>(p);
-    const uint64_t v0 = w[0] | ((uint64_t)w[1] << 32), v1 = w[2] | ((uint64_t)w[3] << 32), v2 = w[4] | ((uint64_t)w[5] << 32), v3 = w[6] | ((uint64_t)w[7] << 32);
-    q[0] = make_ulonglong2(zero ? 0 : v0, zero ? 0 : v1);
-    q[1] = make_ulonglong2(zero ? 0 : v2, zero ? 0 : v3);
-}
-// base^e over the low `bits` bits of e, most significant first: the same trip count on every lane
-__device__ __forceinline__ F2 pow_bits(const FeT<FrP>& base, uint32_t e, int bits)
-{
-    F2 acc = fe_one<FrP>();
-    for (int b = bits - 1; b >= 0; --b) {
-        acc = sqr(acc);
-        const F2 m = mul(acc, base);
-        const bool take = ((e >> b) & 1u) != 0;
-#pragma unroll
-        for (int i = 0; i < NL; i++) acc.d[i] = take ? m.d[i] : acc.d[i];
-    }
-    return acc;
-}
 
 // ---- k_recover_roots: psi^k for every missing cell k, once per call -------------------------------------------------------------------------------------
 // Thread i takes K[i]: square-and-multiply over the log2 m bits of the index, the nine limbs of the product written limb-major (limb q of root i at
@@ -134,66 +109,74 @@ __global__ void __launch_bounds__(CT) k_recover_vanish(RecoverVanishArgs P)
     st8(P.zc + 4 * (size_t)a, o, false);
 }
 
-// ---- k_recover_scatter: E of polynomial blockIdx.y, every slot of [0, n) written once ----------------------------------------------------------------------
-// Thread u < count l takes value j = u mod l of listed cell t = u / l -- the lanes of a wave read 2 KiB in a row -- and writes v z_(cell[t]), canonical,
-// to slot cell[t] + m j; thread count l + u' writes the zero of point j = u' / mu of missing cell K[u' mod mu] (neighbouring lanes neighbouring missing
-// cells).  The writes of a cell lie m elements apart, 32 bytes each.  Not transposed through LDS: the pass moves 2 x 32 bytes per element once per call
-// beside three transforms that move each element log2 n / 4 or more times.
+// ---- k_recover_scatter, k_recover_divide, k_recover_tail: the back end of BOTH entries, polynomial b = blockIdx.y by the lists of RecoverLists --------------
+// b is uniform over a workgroup, so what a thread reads per polynomial -- off[b], off[b + 1], mu[b] -- is a scalar load.  The same-set entry is the case
+// in which every polynomial shares one row: off[b] = b count, which places its values; a mask of zero on the offset into `cell`, and a stride of zero
+// between the rows of `missing` and between the z (and z') of two polynomials.
+
+// ---- k_recover_scatter: E of polynomial b, every slot of [0, n) written once ---------------------------------------------------------------------------
+// With count_b = off[b + 1] - off[b] listed cells: thread u < count_b l takes value j = u mod l of listed cell t = u / l -- the lanes of a wave read 2 KiB
+// in a row -- and writes v z_(cell[t]), canonical, to slot cell[t] + m j; thread count_b l + u' writes the zero of point j = u' / mu_b of missing cell
+// K_b[u' mod mu_b] (neighbouring lanes neighbouring missing cells).  The writes of a cell lie m elements apart, 32 bytes each.  Not transposed through
+// LDS: the pass moves 2 x 32 bytes per element once per call beside three transforms that move each element log2 n / 4 or more times.
 struct RecoverScatterArgs {
-    const uint64_t* values; // batch x count x l x 4
-    const uint32_t *cell, *missing;
-    const uint64_t* z;
+    const uint64_t* values; // off[batch] x l x 4
+    RecoverLists L;
+    const uint64_t* z; // m x 4 per polynomial, L.z_stride elements apart
     uint64_t* out;
     size_t stride;
-    uint32_t count, mu, log2l, log2m;
+    uint32_t log2l, log2m;
 };
 __global__ void __launch_bounds__(CT) k_recover_scatter(RecoverScatterArgs P)
 {
-    const uint32_t u = blockIdx.x * (uint32_t)CT + threadIdx.x, b = blockIdx.y, present = P.count << P.log2l;
+    const uint32_t u = blockIdx.x * (uint32_t)CT + threadIdx.x, b = blockIdx.y;
     if (u >= (1u << (P.log2l + P.log2m))) return;
+    const uint32_t off = P.L.d_off[b], present = (P.L.d_off[b + 1] - off) << P.log2l;
     uint64_t* out = P.out + 4 * (size_t)b * P.stride;
     uint32_t o[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     if (u < present) {
-        const uint32_t k = P.cell[u >> P.log2l], j = u & ((1u << P.log2l) - 1u);
+        const uint32_t k = P.L.d_cell[(off & P.L.cell_mask) + (u >> P.log2l)], j = u & ((1u << P.log2l) - 1u);
         uint32_t w[8], zw[8];
-        ld8(P.values + 4 * ((size_t)b * present + u), w);
-        ld8(P.z + 4 * (size_t)k, zw);
+        ld8(P.values + 4 * (((size_t)off << P.log2l) + u), w);
+        ld8(P.z + 4 * ((size_t)b * P.L.z_stride + k), zw);
         to_canonical(mul(unpack<FrP>(w), unpack<FrP>(zw)), o);
         st8(out + 4 * ((size_t)k + ((size_t)j << P.log2m)), o, false);
     } else {
-        const uint32_t v = u - present, j = v / P.mu, k = P.missing[v - j * P.mu]; // mu > 0 here: present < n
+        const uint32_t mu = P.L.d_mu[b], v = u - present, j = v / mu, k = P.L.d_missing[(size_t)b * P.L.missing_stride + (v - j * mu)]; // mu > 0 here: present < n
         st8(out + 4 * ((size_t)k + ((size_t)j << P.log2m)), o, true);
     }
 }
 
-// ---- k_recover_divide: Q_i *= 1 / z'_(i mod m), polynomial blockIdx.y; inv holds the Montgomery-261 multipliers --------------------------------------------
-__global__ void __launch_bounds__(CT) k_recover_divide(uint64_t* __restrict__ q, size_t stride, const uint64_t* __restrict__ inv, uint32_t log2n, uint32_t log2m)
+// ---- k_recover_divide: Q_i *= 1 / z'_(i mod m) of polynomial b; inv holds the Montgomery-261 multipliers, z_stride elements between polynomials --------------
+__global__ void __launch_bounds__(CT) k_recover_divide(uint64_t* __restrict__ q, size_t stride, const uint64_t* __restrict__ inv, uint32_t z_stride, uint32_t log2n,
+                                                       uint32_t log2m)
 {
-    const uint32_t i = blockIdx.x * (uint32_t)CT + threadIdx.x;
+    const uint32_t i = blockIdx.x * (uint32_t)CT + threadIdx.x, b = blockIdx.y;
     if (i >= (1u << log2n)) return;
-    uint64_t* p = q + 4 * ((size_t)blockIdx.y * stride + i);
+    uint64_t* p = q + 4 * ((size_t)b * stride + i);
     uint32_t w[8], zw[8], o[8];
     ld8(p, w);
-    ld8(inv + 4 * (size_t)(i & ((1u << log2m) - 1u)), zw);
+    ld8(inv + 4 * ((size_t)b * z_stride + (i & ((1u << log2m) - 1u))), zw);
     to_canonical(mul(unpack<FrP>(w), unpack<FrP>(zw)), o);
     st8(p, o, false);
 }
 
-// ---- k_recover_tail: coefficients [0, n) of polynomial blockIdx.y canonical, and the two findings -----------------------------------------------------------
-// Strided over the coefficients.  A nonzero coefficient at an index in [d, present) is a finding about the DATA (first_bad), one in [present, n) a finding
-// about this library (first_bug); the smallest index of each meets on chip -- __shfl_xor, then LDS -- and ONE thread per workgroup issues an atomicMin per
-// kind, only if the workgroup found one: an honest call issues none.  copy: null, or batch x n x 4 words that get the same coefficients (the input of the
-// forward transform behind values_out).
+// ---- k_recover_tail: coefficients [0, n) of polynomial b canonical, and the two findings ------------------------------------------------------------------
+// Strided over the coefficients.  A nonzero coefficient at an index in [d, count_b l) is a finding about the DATA (first_bad), one in [count_b l, n) a
+// finding about this library (first_bug); the smallest index of each meets on chip (min_pair_to_thread0) and ONE thread per workgroup issues an atomicMin
+// per kind, only if the workgroup found one: an honest call issues none.  copy: null, or batch x n x 4 words that get the same coefficients (the input of
+// the forward transform behind values_out).
 struct RecoverTailArgs {
     uint64_t *coeffs, *copy;
     size_t stride;
+    const uint32_t* off;   // batch + 1
     RecoverFindings* find; // batch, the caller has set every word to ~0
-    uint32_t log2n, d, present;
+    uint32_t log2n, log2l, d;
 };
 __global__ void __launch_bounds__(CT) k_recover_tail(RecoverTailArgs P)
 {
     __shared__ uint32_t s_bad[CT / 64], s_bug[CT / 64];
-    const uint32_t n = 1u << P.log2n, b = blockIdx.y;
+    const uint32_t n = 1u << P.log2n, b = blockIdx.y, present = (P.off[b + 1] - P.off[b]) << P.log2l;
     const FeT<FrP> one = fe_one<FrP>();
     uint32_t bad = ~0u, bug = ~0u;
     for (uint32_t i = blockIdx.x * (uint32_t)CT + threadIdx.x; i < n; i += gridDim.x * (uint32_t)CT) {
@@ -205,26 +188,11 @@ __global__ void __launch_bounds__(CT) k_recover_tail(RecoverTailArgs P)
         if (P.copy) st8(P.copy + 4 * (((size_t)b << P.log2n) + i), o, false);
         const bool nz = (o[0] | o[1] | o[2] | o[3] | o[4] | o[5] | o[6] | o[7]) != 0;
         if (nz && i >= P.d) {
-            if (i < P.present) bad = min(bad, i);
+            if (i < present) bad = min(bad, i);
             else bug = min(bug, i);
         }
     }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        bad = min(bad, (uint32_t)__shfl_xor((int)bad, o));
-        bug = min(bug, (uint32_t)__shfl_xor((int)bug, o));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_bad[threadIdx.x >> 6] = bad;
-        s_bug[threadIdx.x >> 6] = bug;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-#pragma unroll
-    for (int k = 1; k < CT / 64; k++) {
-        bad = min(bad, s_bad[k]);
-        bug = min(bug, s_bug[k]);
-    }
+    if (!min_pair_to_thread0<CT>(bad, bug, s_bad, s_bug)) return;
     if (bad != ~0u) atomicMin(&P.find[b].first_bad, (unsigned long long)bad);
     if (bug != ~0u) atomicMin(&P.find[b].first_bug, (unsigned long long)bug);
 }
@@ -261,19 +229,16 @@ int kzg_recover_vanish(const uint32_t* d_missing, size_t mu, int log2n, int log2
     return BBGPU_OK;
 }
 
-// d_values: batch x count x l x 4 words; d_out: batch polynomials, stride_elems apart
-int kzg_recover_scatter(const uint64_t* d_values, const uint32_t* d_cell, size_t count, const uint32_t* d_missing, const uint64_t* d_z, int log2n, int log2l,
-                        int batch, uint64_t* d_out, size_t stride_elems, hipStream_t st)
+// d_values: off[batch] x l x 4 words; d_z: m x 4 words per polynomial; d_out: batch polynomials, stride_elems apart
+int kzg_recover_scatter(const uint64_t* d_values, const RecoverLists& L, const uint64_t* d_z, int log2n, int log2l, int batch, uint64_t* d_out, size_t stride_elems,
+                        hipStream_t st)
 {
     RecoverScatterArgs P{};
     P.values = d_values;
-    P.cell = d_cell;
-    P.missing = d_missing;
+    P.L = L;
     P.z = d_z;
     P.out = d_out;
     P.stride = stride_elems;
-    P.count = (uint32_t)count;
-    P.mu = (uint32_t)(((size_t)1 << (log2n - log2l)) - count);
     P.log2l = (uint32_t)log2l;
     P.log2m = (uint32_t)(log2n - log2l);
     const size_t n = (size_t)1 << log2n;
@@ -282,26 +247,28 @@ int kzg_recover_scatter(const uint64_t* d_values, const uint32_t* d_cell, size_t
     return BBGPU_OK;
 }
 
-int kzg_recover_divide(uint64_t* d_q, size_t stride_elems, int batch, const uint64_t* d_inv, int log2n, int log2l, hipStream_t st)
+int kzg_recover_divide(uint64_t* d_q, size_t stride_elems, int batch, const uint64_t* d_inv, const RecoverLists& L, int log2n, int log2l, hipStream_t st)
 {
     const size_t n = (size_t)1 << log2n;
-    k_recover_divide<<<dim3((uint32_t)((n + CT - 1) / CT), (uint32_t)batch), CT, 0, st>>>(d_q, stride_elems, d_inv, (uint32_t)log2n, (uint32_t)(log2n - log2l));
+    k_recover_divide<<<dim3((uint32_t)((n + CT - 1) / CT), (uint32_t)batch), CT, 0, st>>>(d_q, stride_elems, d_inv, L.z_stride, (uint32_t)log2n,
+                                                                                         (uint32_t)(log2n - log2l));
     HIPCHK(launch_check());
     return BBGPU_OK;
 }
 
 // d_find: batch findings, every word ~0; d_copy: null or batch x n x 4 words
-int kzg_recover_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* d_copy, int log2n, size_t degree_bound, size_t present, RecoverFindings* d_find,
-                     hipStream_t st)
+int kzg_recover_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* d_copy, int log2n, int log2l, size_t degree_bound, const RecoverLists& L,
+                     RecoverFindings* d_find, hipStream_t st)
 {
     RecoverTailArgs P{};
     P.coeffs = d_coeffs;
     P.copy = d_copy;
     P.stride = stride_elems;
+    P.off = L.d_off;
     P.find = d_find;
     P.log2n = (uint32_t)log2n;
+    P.log2l = (uint32_t)log2l;
     P.d = (uint32_t)degree_bound;
-    P.present = (uint32_t)present;
     const size_t n = (size_t)1 << log2n;
     const uint32_t blocks = (uint32_t)std::min<size_t>((n + CT - 1) / CT, KZG_RECOVER_TAIL_MAX_BLOCKS);
     k_recover_tail<<<dim3(blocks, (uint32_t)batch), CT, 0, st>>>(P);

@@ -1,19 +1,20 @@
 // kzg_recover_each.hip -- the device parts of bbgpu_kzg_recover_cells_each (include/bbgpu.h; the driver is in capi.hip) that are not a transform or the
 // batch inversion: the vanishing polynomial of every polynomial's OWN missing cells in COEFFICIENT form from a product tree -- leaves of T roots, then
 // levels of sibling products between two batched transforms -- its gather into the inputs of the two transforms that give its values on the domain and
-// on the coset, and scatter, divide and tail with per-polynomial lists.  The definition all follow is host_kzg_recover_each.hpp's
+// on the coset.  The definition all follow is host_kzg_recover_each.hpp's
 // kzg_recover_cells_each_host (the host twin, which forms no tree).  Notation as in kzg_recover_cells.hip: l = 2^log2l values per cell, m = 2^log2m cells
 // per polynomial, n = l m, psi = omega^l, g the coset generator of BBGPU_COSET_FFT, Y = X^l; polynomial b misses the mu_b cells K_b.  M is the common
 // power of two >= max mu_b (at least 1, at most m) to which every polynomial's root list is padded with ZERO roots: the padded product is
 // Y^(M - mu_b) Z_b, so Z_b's coefficients are read from offset M - mu_b -- exact, no division, no case for a mu_b that is no power of two.
-// The 16-byte loads and stores and the square-and-multiply are restated from kzg_recover_cells.hip, and scatter, divide and tail are that file's with a
-// per-polynomial base: that file's kernels keep their own, so that bbgpu_kzg_recover_cells stays what it was.
+// Scatter, divide and tail are kzg_recover_cells.hip's, which take per-polynomial lists (RecoverLists, bbgpu_internal.h); the 16-byte loads and stores
+// and the square-and-multiply are fr_mem_device.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "bbgpu_internal.h"
 #include "fe.hpp"
+#include "fr_mem_device.hpp"
 #include "host_fr.hpp"
 
 namespace bbgpu {
@@ -24,34 +25,6 @@ constexpr int CT = 256;                  // threads per workgroup, every kernel 
 constexpr int LT = KZG_RECOVER_EACH_LEAF; // roots per leaf: one wave, one coefficient per lane
 static_assert(LT == 64 || LT == 128 || LT == 256, "k_each_leaves: a leaf is one, two or four waves of one workgroup");
 using F2 = Fe<FrP, 1, 2>; // a product
-
-__device__ __forceinline__ void ld8(const uint64_t* p, uint32_t (&w)[8])
-{
-    const ulonglong2* q = reinterpret_cast<const ulonglong2*>(p);
-    const ulonglong2 a = q[0], b = q[1];
-    w[0] = (uint32_t)a.x; w[1] = (uint32_t)(a.x >> 32); w[2] = (uint32_t)a.y; w[3] = (uint32_t)(a.y >> 32);
-    w[4] = (uint32_t)b.x; w[5] = (uint32_t)(b.x >> 32); w[6] = (uint32_t)b.y; w[7] = (uint32_t)(b.y >> 32);
-}
-__device__ __forceinline__ void st8(uint64_t* p, const uint32_t (&w)[8], bool zero)
-{
-    ulonglong2* q = reinterpret_cast<ulonglong2*>(p);
-    const uint64_t v0 = w[0] | ((uint64_t)w[1] << 32), v1 = w[2] | ((uint64_t)w[3] << 32), v2 = w[4] | ((uint64_t)w[5] << 32), v3 = w[6] | ((uint64_t)w[7] << 32);
-    q[0] = make_ulonglong2(zero ? 0 : v0, zero ? 0 : v1);
-    q[1] = make_ulonglong2(zero ? 0 : v2, zero ? 0 : v3);
-}
-// base^e over the low `bits` bits of e, most significant first: the same trip count on every lane
-__device__ __forceinline__ F2 pow_bits(const FeT<FrP>& base, uint32_t e, int bits)
-{
-    F2 acc = fe_one<FrP>();
-    for (int b = bits - 1; b >= 0; --b) {
-        acc = sqr(acc);
-        const F2 m = mul(acc, base);
-        const bool take = ((e >> b) & 1u) != 0;
-#pragma unroll
-        for (int i = 0; i < NL; i++) acc.d[i] = take ? m.d[i] : acc.d[i];
-    }
-    return acc;
-}
 
 // ---- k_each_leaves: T = min(LT, M) roots -> the T low coefficients of prod (Y - r), the leading 1 implied ---------------------------------------------
 // One coefficient per lane: a leaf is max(1, T / 64) neighbouring WAVES of a workgroup of CT / 64, one wave in the build that ships (LT = 64; LT = 256,
@@ -203,98 +176,6 @@ __global__ void __launch_bounds__(CT) k_each_gather(EachGatherArgs P)
     st8(pzc, o, false);
 }
 
-// ---- k_each_scatter, k_each_divide, k_each_tail: kzg_recover_cells.hip's, every polynomial with its own lists and its own z, z' ---------------------------
-struct EachLists {
-    const uint32_t *off, *mu; // batch + 1 cell offsets; batch counts of missing cells
-    const uint32_t *cell, *missing; // off[batch] listed cells; batch x M missing cells (the first mu_b of a row)
-    uint32_t M;
-};
-struct EachScatterArgs {
-    const uint64_t* values; // off[batch] x l x 4
-    EachLists L;
-    const uint64_t* z; // batch x m x 4
-    uint64_t* out;
-    size_t stride;
-    uint32_t log2l, log2m;
-};
-__global__ void __launch_bounds__(CT) k_each_scatter(EachScatterArgs P)
-{
-    const uint32_t u = blockIdx.x * (uint32_t)CT + threadIdx.x, b = blockIdx.y;
-    if (u >= (1u << (P.log2l + P.log2m))) return;
-    const uint32_t off = P.L.off[b], present = (P.L.off[b + 1] - off) << P.log2l;
-    uint64_t* out = P.out + 4 * (size_t)b * P.stride;
-    uint32_t o[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    if (u < present) {
-        const uint32_t k = P.L.cell[off + (u >> P.log2l)], j = u & ((1u << P.log2l) - 1u);
-        uint32_t w[8], zw[8];
-        ld8(P.values + 4 * (((size_t)off << P.log2l) + u), w);
-        ld8(P.z + 4 * (((size_t)b << P.log2m) + k), zw);
-        to_canonical(mul(unpack<FrP>(w), unpack<FrP>(zw)), o);
-        st8(out + 4 * ((size_t)k + ((size_t)j << P.log2m)), o, false);
-    } else {
-        const uint32_t mu = P.L.mu[b], v = u - present, j = v / mu, k = P.L.missing[(size_t)b * P.L.M + (v - j * mu)]; // mu > 0 here: present < n
-        st8(out + 4 * ((size_t)k + ((size_t)j << P.log2m)), o, true);
-    }
-}
-
-__global__ void __launch_bounds__(CT) k_each_divide(uint64_t* __restrict__ q, size_t stride, const uint64_t* __restrict__ inv, uint32_t log2n, uint32_t log2m)
-{
-    const uint32_t i = blockIdx.x * (uint32_t)CT + threadIdx.x, b = blockIdx.y;
-    if (i >= (1u << log2n)) return;
-    uint64_t* p = q + 4 * ((size_t)b * stride + i);
-    uint32_t w[8], zw[8], o[8];
-    ld8(p, w);
-    ld8(inv + 4 * (((size_t)b << log2m) + (i & ((1u << log2m) - 1u))), zw);
-    to_canonical(mul(unpack<FrP>(w), unpack<FrP>(zw)), o);
-    st8(p, o, false);
-}
-
-struct EachTailArgs {
-    uint64_t *coeffs, *copy;
-    size_t stride;
-    const uint32_t* off;   // batch + 1
-    RecoverFindings* find; // batch, the caller has set every word to ~0
-    uint32_t log2n, log2l, d;
-};
-__global__ void __launch_bounds__(CT) k_each_tail(EachTailArgs P)
-{
-    __shared__ uint32_t s_bad[CT / 64], s_bug[CT / 64];
-    const uint32_t n = 1u << P.log2n, b = blockIdx.y, present = (P.off[b + 1] - P.off[b]) << P.log2l;
-    const FeT<FrP> one = fe_one<FrP>();
-    uint32_t bad = ~0u, bug = ~0u;
-    for (uint32_t i = blockIdx.x * (uint32_t)CT + threadIdx.x; i < n; i += gridDim.x * (uint32_t)CT) {
-        uint64_t* p = P.coeffs + 4 * ((size_t)b * P.stride + i);
-        uint32_t w[8], o[8];
-        ld8(p, w);
-        to_canonical(mul(unpack<FrP>(w), one), o);
-        st8(p, o, false);
-        if (P.copy) st8(P.copy + 4 * (((size_t)b << P.log2n) + i), o, false);
-        const bool nz = (o[0] | o[1] | o[2] | o[3] | o[4] | o[5] | o[6] | o[7]) != 0;
-        if (nz && i >= P.d) {
-            if (i < present) bad = min(bad, i);
-            else bug = min(bug, i);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        bad = min(bad, (uint32_t)__shfl_xor((int)bad, o));
-        bug = min(bug, (uint32_t)__shfl_xor((int)bug, o));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_bad[threadIdx.x >> 6] = bad;
-        s_bug[threadIdx.x >> 6] = bug;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-#pragma unroll
-    for (int k = 1; k < CT / 64; k++) {
-        bad = min(bad, s_bad[k]);
-        bug = min(bug, s_bug[k]);
-    }
-    if (bad != ~0u) atomicMin(&P.find[b].first_bad, (unsigned long long)bad);
-    if (bug != ~0u) atomicMin(&P.find[b].first_bug, (unsigned long long)bug);
-}
-
 } // namespace
 
 // d_missing: batch x M cells, polynomial b's mu_b missing cells first, then ~0 -> d_tree: batch M / T leaves, T = min(LT, M), in slots of 2 T elements
@@ -347,63 +228,6 @@ int kzg_recover_each_gather(const uint64_t* d_tree, const uint32_t* d_mu, int ba
     P.c32 = host::limbs_m261(host::fr_from_u64(32));
     P.one256 = host::limbs_m256(host::fr_one());
     k_each_gather<<<dim3((P.m + CT - 1) / CT, (uint32_t)batch), CT, 0, st>>>(P);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-static EachLists each_lists(const KzgRecoverEachLists& L)
-{
-    EachLists R{};
-    R.off = L.d_off;
-    R.mu = L.d_mu;
-    R.cell = L.d_cell;
-    R.missing = L.d_missing;
-    R.M = (uint32_t)L.M;
-    return R;
-}
-
-// d_values: off[batch] x l x 4 words; d_z: batch x m x 4; d_out: batch polynomials, stride_elems apart
-int kzg_recover_each_scatter(const uint64_t* d_values, const KzgRecoverEachLists& L, const uint64_t* d_z, int log2n, int log2l, int batch, uint64_t* d_out,
-                             size_t stride_elems, hipStream_t st)
-{
-    EachScatterArgs P{};
-    P.values = d_values;
-    P.L = each_lists(L);
-    P.z = d_z;
-    P.out = d_out;
-    P.stride = stride_elems;
-    P.log2l = (uint32_t)log2l;
-    P.log2m = (uint32_t)(log2n - log2l);
-    const size_t n = (size_t)1 << log2n;
-    k_each_scatter<<<dim3((uint32_t)((n + CT - 1) / CT), (uint32_t)batch), CT, 0, st>>>(P);
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-int kzg_recover_each_divide(uint64_t* d_q, size_t stride_elems, int batch, const uint64_t* d_inv, int log2n, int log2l, hipStream_t st)
-{
-    const size_t n = (size_t)1 << log2n;
-    k_each_divide<<<dim3((uint32_t)((n + CT - 1) / CT), (uint32_t)batch), CT, 0, st>>>(d_q, stride_elems, d_inv, (uint32_t)log2n, (uint32_t)(log2n - log2l));
-    HIPCHK(launch_check());
-    return BBGPU_OK;
-}
-
-// d_find: batch findings, every word ~0; d_copy: null or batch x n x 4 words
-int kzg_recover_each_tail(uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* d_copy, int log2n, int log2l, size_t degree_bound, const uint32_t* d_off,
-                          RecoverFindings* d_find, hipStream_t st)
-{
-    EachTailArgs P{};
-    P.coeffs = d_coeffs;
-    P.copy = d_copy;
-    P.stride = stride_elems;
-    P.off = d_off;
-    P.find = d_find;
-    P.log2n = (uint32_t)log2n;
-    P.log2l = (uint32_t)log2l;
-    P.d = (uint32_t)degree_bound;
-    const size_t n = (size_t)1 << log2n;
-    const uint32_t blocks = (uint32_t)std::min<size_t>((n + CT - 1) / CT, KZG_RECOVER_TAIL_MAX_BLOCKS);
-    k_each_tail<<<dim3(blocks, (uint32_t)batch), CT, 0, st>>>(P);
     HIPCHK(launch_check());
     return BBGPU_OK;
 }

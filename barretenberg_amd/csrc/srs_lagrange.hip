@@ -107,17 +107,9 @@ __global__ void __launch_bounds__(FT) k_lagrange_finish(const uint32_t* __restri
 int srs_lagrange_rows(const uint32_t* d_in, size_t n, int log2n, const uint32_t winv_m261[9], const uint64_t ninv_plain[4], SrsCurveFindings* d_find,
                       SrsCurveFindings* found, uint32_t** d_out_rows, uint64_t* host_table_out, hipStream_t st, float* ms3)
 {
-    struct Events {
-        hipEvent_t e[4] = { nullptr, nullptr, nullptr, nullptr };
-        ~Events()
-        {
-            for (hipEvent_t v : e)
-                if (v) (void)hipEventDestroy(v);
-        }
-    } ev;
+    StageEvents<4> ev;
     *d_out_rows = nullptr;
-    if (ms3)
-        for (hipEvent_t& v : ev.e) HIPCHK(hipEventCreate(&v));
+    if (int rc = ev.create(ms3 != nullptr)) return rc;
     DevBuf scratch, rows;
     HIPCHK(dev_malloc(&scratch.p, n * 128));
     HIPCHK(dev_malloc(&rows.p, n * 64));
@@ -126,20 +118,20 @@ int srs_lagrange_rows(const uint32_t* d_in, size_t n, int log2n, const uint32_t 
     Scalar256 k;
     for (int i = 0; i < 4; i++) k.d[i] = ninv_plain[i];
     const uint32_t n32 = (uint32_t)n, lg = (uint32_t)log2n;
-    if (ms3) HIPCHK(hipEventRecord(ev.e[0], st));
+    if (int rc = ev.mark(0, st)) return rc;
     k_lagrange_load<<<(n32 + LT - 1) / LT, LT, 0, st>>>(d_in, scratch.as<uint32_t>(), n32, lg, k);
-    if (ms3) HIPCHK(hipEventRecord(ev.e[1], st));
+    if (int rc = ev.mark(1, st)) return rc;
     for (uint32_t s = 0; s < lg; s++) k_lagrange_stage<<<(n32 / 2 + LT - 1) / LT, LT, 0, st>>>(scratch.as<uint32_t>(), n32, lg, s, wl, 0);
-    if (ms3) HIPCHK(hipEventRecord(ev.e[2], st));
+    if (int rc = ev.mark(2, st)) return rc;
     k_lagrange_finish<<<(uint32_t)std::min<size_t>((n + FT - 1) / FT, 2048), FT, 0, st>>>(scratch.as<uint32_t>(), rows.as<uint32_t>(), (uint64_t)n, d_find);
     HIPCHK(launch_check()); // the chain: load, stages, finish
-    if (ms3) HIPCHK(hipEventRecord(ev.e[3], st));
+    if (int rc = ev.mark(3, st)) return rc;
     HIPCHK(d2h_async(found, d_find, sizeof *found, st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms3) {
-        HIPCHK(hipEventElapsedTime(&ms3[0], ev.e[1], ev.e[2]));
-        HIPCHK(hipEventElapsedTime(&ms3[1], ev.e[0], ev.e[1]));
-        HIPCHK(hipEventElapsedTime(&ms3[2], ev.e[2], ev.e[3]));
+        if (int rc = ev.ms(1, 2, &ms3[0])) return rc;
+        if (int rc = ev.ms(0, 1, &ms3[1])) return rc;
+        if (int rc = ev.ms(2, 3, &ms3[2])) return rc;
     }
     if (found->bad_points) return BBGPU_OK; // no table: the buffers go with this frame
     (void)dev_free(scratch.release<void>());

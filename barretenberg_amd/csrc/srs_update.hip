@@ -83,18 +83,8 @@ constexpr int SRS_UPDATE_WB = 3;
 int srs_update_rows(const uint32_t* d_in, size_t n, uint64_t first_power, const uint64_t* y_mont256, uint32_t** d_out_rows, uint64_t* host_table_out, hipStream_t st,
                     float* kernel_ms)
 {
-    struct Events {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events()
-        {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev;
-    if (kernel_ms) {
-        HIPCHK(hipEventCreate(&ev.a));
-        HIPCHK(hipEventCreate(&ev.b));
-    }
+    StageEvents<2> ev;
+    if (int rc = ev.create(kernel_ms != nullptr)) return rc;
     DevBuf rows;
     HIPCHK(dev_malloc(&rows.p, n * 64));
     // y: Montgomery 2^256 -> 2^261, canonical limbs
@@ -107,10 +97,10 @@ int srs_update_rows(const uint32_t* d_in, size_t n, uint64_t first_power, const 
     Limbs9 yl;
     for (int i = 0; i < NL; i++) yl.d[i] = yc.d[i];
     const uint32_t blocks = (uint32_t)((n + UT - 1) / UT); // n <= 2^32: at most 2^26 workgroups
-    if (kernel_ms) HIPCHK(hipEventRecord(ev.a, st));
+    if (int rc = ev.mark(0, st)) return rc;
     k_srs_update<SRS_UPDATE_WB><<<blocks, UT, 0, st>>>(d_in, rows.as<uint32_t>(), (uint64_t)n, first_power, yl);
     HIPCHK(launch_check());
-    if (kernel_ms) HIPCHK(hipEventRecord(ev.b, st));
+    if (int rc = ev.mark(1, st)) return rc;
     if (host_table_out) {
         DevBuf exp;
         HIPCHK(dev_malloc(&exp.p, n * 128));
@@ -118,7 +108,8 @@ int srs_update_rows(const uint32_t* d_in, size_t n, uint64_t first_power, const 
         if (int rc = device_to_host_sync(host_table_out, exp.p, n * 128, st)) return rc;
     }
     HIPCHK(hipStreamSynchronize(st));
-    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    if (kernel_ms)
+        if (int rc = ev.ms(0, 1, kernel_ms)) return rc;
     *d_out_rows = rows.release<uint32_t>();
     return BBGPU_OK;
 }

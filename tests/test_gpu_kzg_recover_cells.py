@@ -177,6 +177,17 @@ def test_one_altered_value_among_redundant_cells(lib):
             assert rep["consistent"] == 0 and rep["first_bad_poly"] == 1 and d <= rep["first_bad_coeff"] < count * l
 
 
+def test_three_polynomials_share_one_row_of_lists(lib):
+    """(64, 4), m = 16: 9 cells listed out of order, 7 missing, batch 3 in a padded stride, degree bound 20, one value of polynomial 1 altered.  Scatter,
+    divide and tail read every polynomial's lists, z and z' at a stride, which is zero for this entry: the smallest shape at which a stride that is not
+    would take polynomial 1 or 2 to another row and show it.  Coefficients, transforms and report are the twin's (agree), which names polynomial 1."""
+    n, l, d, missing = 64, 4, 20, spread(16, 7)
+    cells = present_cells(n, l, missing)
+    assert len(cells) == 9 and cells.tolist() != sorted(cells.tolist())
+    rep = agree(lib, n, l, d, missing, batch=3, pad=PAD, alter=9 * l + 5)
+    assert rep["consistent"] == 0 and rep["first_bad_poly"] == 1 and d <= rep["first_bad_coeff"] < 9 * l
+
+
 def test_an_altered_value_without_redundancy_is_not_seen(lib):
     rep = agree(lib, 16, 4, 8, [0, 2], alter=3)
     assert rep == dict(consistent=1, first_bad_poly=0, first_bad_coeff=0, missing=2)

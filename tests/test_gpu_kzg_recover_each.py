@@ -1,12 +1,13 @@
 """bbgpu_kzg_recover_cells_each on the GPU (-m gpu): the kernels of csrc/kzg_recover_each.hip (k_each_leaves, k_each_pair between the transforms of a tree
-level, k_each_powers, k_each_gather, k_each_scatter, k_each_divide, k_each_tail) and the driver in capi.hip
+level, k_each_powers, k_each_gather), the back end it shares with bbgpu_kzg_recover_cells (k_recover_scatter, k_recover_divide, k_recover_tail of
+csrc/kzg_recover_cells.hip, here with per-polynomial lists) and the driver in capi.hip
   against the host twin bit for bit -- coefficients with the elements between the polynomials, transforms, report, first_bad -- with one batch that holds
     mu_b = 0, 1, T - 1, T, T + 1, 2 T + 1 and m - 1 missing cells (T = BbGpu.RECOVER_EACH_LEAF roots per leaf: the edges of the leaf, of the padding with
     zero roots and of the first tree level), unsorted lists, the last polynomial without redundancy;
   against bbgpu_kzg_recover_cells bit for bit where every polynomial holds the same set;
   beyond that entry's 2^16 cells, where no twin is affordable, against the polynomials the cells were made from (values by bbgpu_ntt_device, which
     tests/test_gpu_ntt_sizes.py ties to the oracle), and once against the twin with few cells missing;
-  past the grid of k_each_tail (1024 workgroups of 256) at n = 2^19 and 2^20, with extra coefficients whose index the report must name exactly, and at
+  past the grid of k_recover_tail (1024 workgroups of 256) at n = 2^19 and 2^20, with extra coefficients whose index the report must name exactly, and at
     batch x M = 2^22 roots, where the transforms of the first tree level are handed over in two chunks;
   a round trip through bbgpu_kzg_open_cosets_device and bbgpu_kzg_check_open_cosets; and the error contract under injected failures of the four host-side
   funnels (no failure is provoked on the device).  The twin itself is held to plain-integer interpolation by tests/test_kzg_recover_each_host.py."""
@@ -24,7 +25,7 @@ TAIL = 1 << 18  # KZG_RECOVER_TAIL_MAX_BLOCKS = 1024 workgroups of 256: coeffici
 # the funnels one warm call passes with the transforms read back (include/bbgpu.h).  Allocations: the lists, the tree, z with z' and the power table, the
 # values, the findings, the copy the forward transform works in; uploads: the lists, the findings' start, the values; read-backs: the findings, the
 # transforms.  Launch checks at (256, 4), where 64 cells make one leaf per polynomial and no level: k_each_leaves, k_each_powers with k_each_gather, the
-# Z transforms, the batch inversion's two scans and its product, k_each_scatter, four transforms, k_each_divide, k_each_tail.  At (1024, 1) with up to
+# Z transforms, the batch inversion's two scans and its product, k_recover_scatter, four transforms, k_recover_divide, k_recover_tail.  At (1024, 1) with up to
 # 200 cells missing (M = 256, two levels; transforms of 128 .. 1024 points are one launch each) every level adds three.
 WARM = {(256, 4): dict(alloc_calls=6, h2d_calls=3, d2h_calls=2, launch_checks=13), (1024, 1): dict(alloc_calls=6, h2d_calls=3, d2h_calls=2, launch_checks=19)}
 
@@ -110,6 +111,20 @@ def test_device_equals_twin_around_the_leaf_and_the_first_level(lib, oracle, n, 
     assert got[3].tolist() == [NONE] * 4 + [got[2]["first_bad_coeff"], NONE, NONE]
 
 
+def test_neighbouring_polynomials_each_with_its_own_row(lib, oracle):
+    """(64, 4), m = 16: batch 3 with 16, 9 and 5 cells listed (mu = 0, 7, 11, so M = 16 is below the leaf), degree bound 20.  One call in which the count
+    of present values, mu and the row of missing cells all differ between neighbouring values of blockIdx.y of the shared scatter, divide and tail
+    (csrc/kzg_recover_cells.hip), and one polynomial has no missing cell at all.  Device against twin bit for bit, first_bad included."""
+    n, l, d, mus = 64, 4, 20, (0, 7, 11)
+    coeffs, values = polynomials(lib, oracle, n, d, len(mus), seed=8)
+    cells = [split(n // l, mu, 90 + b)[1] for b, mu in enumerate(mus)]
+    assert [len(c) for c in cells] == [16, 9, 5]
+    got, want = both(lib, n, l, d, cells, [cell_values(values[b], l, c) for b, c in enumerate(cells)], PAD)
+    assert same(got, want)
+    assert np.array_equal(got[0].reshape(len(mus), n + PAD, 4)[:, :n], coeffs) and np.array_equal(got[1], values)
+    assert got[2] == dict(consistent=1, first_bad_poly=0, first_bad_coeff=0, max_missing=11) and got[3].tolist() == [NONE] * len(mus)
+
+
 @pytest.mark.parametrize("n,l,batch,mu", [(1 << 12, 64, 4, None), (1 << 16, 1, 1, 300)])
 def test_device_equals_the_same_set_entry(lib, oracle, n, l, batch, mu):
     """every polynomial holds the same cells: coefficients, transforms and verdict are bbgpu_kzg_recover_cells's, bit for bit"""
@@ -183,7 +198,7 @@ def big(lib, oracle):
 
 
 def test_the_tail_past_its_grid(lib, big):
-    """n = 2^19: the 1024 workgroups of 256 of k_each_tail take a second trip.  Device against twin bit for bit (few cells are missing, so the twin's
+    """n = 2^19: the 1024 workgroups of 256 of k_recover_tail take a second trip.  Device against twin bit for bit (few cells are missing, so the twin's
     direct products are few), the coefficients against the original polynomials, the transforms against bbgpu_ntt_device's"""
     n = big["n"]
     got, want = both(lib, n, big["l"], big["d"], big["cells"], big["vals"], PAD)
@@ -239,7 +254,7 @@ def test_the_chunk_loop_of_the_tree_transforms(lib, huge):
 
 
 def test_the_fourth_trip_of_the_tail(lib, huge):
-    """the same call with an extra coefficient of polynomial 2 at 3 x 2^18 + 5 (k_each_tail's fourth trip at n = 2^20) and one of polynomial 3 at 2^18,
+    """the same call with an extra coefficient of polynomial 2 at 3 x 2^18 + 5 (k_recover_tail's fourth trip at n = 2^20) and one of polynomial 3 at 2^18,
     the degree bound itself: the first findings per polynomial, and the report names polynomial 2"""
     import torch
     n, extra = huge["n"], {2: 3 * TAIL + 5, 3: TAIL}
