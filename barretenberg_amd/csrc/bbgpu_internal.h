@@ -166,14 +166,8 @@ int srs_check_scalars(const uint64_t seed[4], size_t count, uint64_t* d_out, hip
 int srs_lagrange_rows(const uint32_t* d_in, size_t n, int log2n, const uint32_t winv_m261[9], const uint64_t ninv_plain[4], SrsCurveFindings* d_find,
                       SrsCurveFindings* found, uint32_t** d_out_rows, uint64_t* host_table_out, hipStream_t st, float* ms3 = nullptr);
 
-// kzg_open_all.hip: the proofs of a polynomial at every point of its domain (bbgpu_kzg_open_all_setup, bbgpu_kzg_open_all_device)
-int kzg_open_all_string(const uint32_t* d_in, size_t n, int log2n, const uint32_t W_m261[9], uint32_t** d_S, hipStream_t st);
-int kzg_open_all_t(const uint64_t* d_coeffs, size_t stride_elems, int batch, size_t n, uint64_t* d_t, hipStream_t st);
-int kzg_open_all_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scratch, size_t n, int log2n, int batch, const uint32_t c32[9], const uint32_t Winv[9],
-                       const uint32_t omega[9], hipStream_t st, float* ms4 = nullptr);
-
 // kzg_open_cosets.hip: the proofs of a polynomial on every coset of its domain (bbgpu_kzg_open_cosets_setup(_bounded), bbgpu_kzg_open_cosets_device); d =
-// 2^log2d is the degree bound of the setup, n without one
+// 2^log2d is the degree bound of the setup, n without one.  bbgpu_kzg_open_all_setup and bbgpu_kzg_open_all_device are log2l = 0, log2d = log2n
 int kzg_open_cosets_string(const uint32_t* d_in, int log2d, int log2l, const uint32_t W_m261[9], uint32_t** d_S, hipStream_t st);
 int kzg_open_cosets_t(const uint64_t* d_coeffs, size_t stride_elems, int batch, int log2d, int log2l, uint64_t* d_t, hipStream_t st);
 int kzg_open_cosets_chain(const uint32_t* d_S, uint64_t* d_that, uint32_t* d_scratch, int log2n, int log2l, int log2d, int batch, const uint32_t c32[9],

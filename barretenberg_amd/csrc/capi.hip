@@ -1328,48 +1328,30 @@ void opening_release(OpeningSession& o)
     o = OpeningSession();
 }
 
-// ---- setups of bbgpu_kzg_open_all_* (below): S^ = DFT_2n(s) of one (string, n), 2 n scratch points made once by the setup entry and kept in an allocation of
-// the setup's own until its release or bbgpu_shutdown.  Context 0, under g_mu.
-struct OpenAllSetup {
-    bool live = false;
-    int log2n = 0;
-    uint32_t* d_S = nullptr;
-    size_t bytes = 0;
-};
-OpenAllSetup g_open_all[BBGPU_KZG_OPEN_ALL_MAX_SETUPS];
-size_t open_all_setup_bytes()
-{
-    size_t b = 0;
-    for (const auto& o : g_open_all)
-        if (o.live) b += o.bytes;
-    return b;
-}
-void open_all_release(OpenAllSetup& o)
-{
-    if (o.live && o.d_S) (void)dev_free(o.d_S);
-    o = OpenAllSetup();
-}
-
-// ---- setups of bbgpu_kzg_open_cosets_* (below): S^(e) = DFT_M(s^(e)), e < l, of one (string, n, l, d), d the degree bound (n without one): l x M = 2 d
-// scratch points, kept as the open-all setups are, in a pool of their own.  Context 0, under g_mu.
-struct OpenCosetsSetup {
+// ---- setups of bbgpu_kzg_open_all_* and bbgpu_kzg_open_cosets_* (below): S^(e) = DFT_M(s^(e)), e < l, of one (string, n, l, d), d the degree bound (n
+// without one): l x M = 2 d scratch points made once by the setup entry and kept in an allocation of the setup's own until its release or bbgpu_shutdown.
+// An open-all setup is l = 1, d = n.  Each family has a pool of its own: a handle of one is nothing to the other.  Context 0, under g_mu.
+struct OpenSetup {
     bool live = false;
     int log2n = 0, log2l = 0, log2d = 0;
     uint32_t* d_S = nullptr;
     size_t bytes = 0;
 };
-OpenCosetsSetup g_open_cosets[BBGPU_KZG_OPEN_COSETS_MAX_SETUPS];
-size_t open_cosets_setup_bytes()
+constexpr int OPEN_MAX_SETUPS = 16;
+static_assert(BBGPU_KZG_OPEN_ALL_MAX_SETUPS == OPEN_MAX_SETUPS && BBGPU_KZG_OPEN_COSETS_MAX_SETUPS == OPEN_MAX_SETUPS, "the two pools of open setups: 16 each");
+using OpenPool = OpenSetup[OPEN_MAX_SETUPS];
+OpenPool g_open_all, g_open_cosets;
+size_t open_setup_bytes(const OpenPool& pool)
 {
     size_t b = 0;
-    for (const auto& o : g_open_cosets)
+    for (const auto& o : pool)
         if (o.live) b += o.bytes;
     return b;
 }
-void open_cosets_release(OpenCosetsSetup& o)
+void open_release(OpenSetup& o)
 {
     if (o.live && o.d_S) (void)dev_free(o.d_S);
-    o = OpenCosetsSetup();
+    o = OpenSetup();
 }
 
 // Everything the current context holds, on the thread that drives it (its device is that thread's current one).  Context 0 (primary) also owns the
@@ -1382,9 +1364,9 @@ void release_context(bool primary)
     if (primary)
         for (auto& o : g_opening) opening_release(o);
     if (primary)
-        for (auto& o : g_open_all) open_all_release(o);
+        for (auto& o : g_open_all) open_release(o);
     if (primary)
-        for (auto& o : g_open_cosets) open_cosets_release(o);
+        for (auto& o : g_open_cosets) open_release(o);
     // nothing may still be reading the pinned staging buffers or a slot's workspace when they are freed: collect what is in flight
     // (an MSM a caller never waited for, a copy queued before an error return) and drain every stream first
     for (int k = 0; k < Context::NSLOT; k++)
@@ -1478,7 +1460,7 @@ void add_context_memory(const Context& C, bool primary, bbgpu_memory_info* out)
         if (sl.ws.h_out) out->pinned_host_bytes += (uint64_t)MSM_HOUT_GROUPS * 64 * 128;
     }
     out->staging_bytes += C.stage_cap + C.stage2_cap + C.scratch_cap + C.poly_tmp_cap + C.poly_scratch.cap + C.small_tab_cap + C.srs_check_cap + C.verify_cap + C.kzg_check_cap;
-    if (primary) out->staging_bytes += plonk_lane_bytes() + opening_session_bytes() + open_all_setup_bytes() + open_cosets_setup_bytes(); // the resident prover, the opening sessions and the open-all and open-cosets setups live on context 0
+    if (primary) out->staging_bytes += plonk_lane_bytes() + opening_session_bytes() + open_setup_bytes(g_open_all) + open_setup_bytes(g_open_cosets); // the resident prover, the opening sessions and the open-all and open-cosets setups live on context 0
     for (int k = 0; k < Context::HOST_RING; k++)
         if (C.h_stage[k]) out->pinned_host_bytes += Context::HOST_CHUNK;
 }
@@ -2830,7 +2812,9 @@ int bbgpu_srs_lagrange_check(int lagrange_handle, int monomial_handle, size_t n,
 // x, y, each four 64-bit limbs least-significant limb first, every limb big-endian, NOT in Montgomery form; file point k is
 // x^(k+1) G and monomials[0] is the generator (read_transcript :159-181).  Fills the complete 2n-entry endomorphism table of
 // generate_pippenger_point_table (scalar_multiplication.cpp:131-140): entry 2i = P_i, entry 2i+1 = (beta x_i, -y_i).  Host only.
-/* ---- a polynomial opened at every point of its domain: all n KZG proofs at once (host_kzg_open_all.hpp, kzg_open_all.hip) ---- */
+/* ---- a polynomial opened at every point of its domain (all n KZG proofs at once) or on every coset of it (all n / l cell proofs): one host twin and one
+ * device path, kzg_open_cosets.hip, for both families of entries -- open-all is the coset size 1 without a bound (host_kzg_open_all.hpp,
+ * host_kzg_open_cosets.hpp).  What differs between the families is the pool of setups and the wording of the verdicts on n ---- */
 static int open_all_n(const char* what, size_t n, int* log2n)
 {
     if ((*log2n = host::kzg_open_all_log2(n)) < 0) {
@@ -2847,120 +2831,6 @@ static int open_all_batch(const char* what, int batch)
     }
     return BBGPU_OK;
 }
-static int open_all_sizes(const char* what, size_t n, size_t stride_elems, int batch)
-{
-    if (!host::kzg_open_all_sizes_ok(n, stride_elems, batch)) {
-        set_error("%s: the stride (%zu) must be no smaller than n = %zu and batch x 2 n (%d x %zu) at most 2^%d", what, stride_elems, n, batch, 2 * n,
-                  host::KZG_OPEN_ALL_MAX_SLOTS_LOG2);
-        return BBGPU_ERR_SIZE;
-    }
-    return BBGPU_OK;
-}
-
-int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const uint64_t* coeffs, size_t stride_elems, int batch, uint64_t* proofs_out)
-{
-    int log2n;
-    if (int rc = open_all_n("host kzg_open_all", n, &log2n)) return rc;
-    if (int rc = open_all_batch("host kzg_open_all", batch)) return rc;
-    if (!points_endo_table || !coeffs || !proofs_out) {
-        set_error("host kzg_open_all: null table / coeffs / proofs");
-        return BBGPU_ERR_ARG;
-    }
-    if (int rc = open_all_sizes("host kzg_open_all", n, stride_elems, batch)) return rc;
-    std::vector<host::Xyzz> S;
-    uint64_t bad = 0;
-    if (host::kzg_open_all_setup_host(points_endo_table, n, log2n, S, &bad)) {
-        set_error("host kzg_open_all: row %llu is not on the curve", (unsigned long long)bad);
-        return BBGPU_ERR_ARG;
-    }
-    host::kzg_open_all_proofs_host(S, n, log2n, coeffs, stride_elems, batch, proofs_out);
-    return BBGPU_OK;
-}
-
-int bbgpu_kzg_open_all_setup(int srs_handle, size_t n)
-{
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    // argument errors before a device is bound: a handle can only exist once one is
-    int log2n;
-    if (int rc = open_all_n("kzg_open_all_setup", n, &log2n)) return rc;
-    const SrsEntry* ep = nullptr;
-    if (int rc = srs_rows("kzg_open_all_setup", srs_handle, n, BBGPU_ERR_SIZE, &ep)) return rc;
-    int slot = -1;
-    for (int k = 0; k < BBGPU_KZG_OPEN_ALL_MAX_SETUPS && slot < 0; k++)
-        if (!g_open_all[k].live) slot = k;
-    if (slot < 0) {
-        set_error("kzg_open_all_setup: %d setups are live", BBGPU_KZG_OPEN_ALL_MAX_SETUPS);
-        return BBGPU_ERR_STATE;
-    }
-    if (int rc = ensure_init()) return rc;
-    const uint32_t* d_in = ep->d_srs;
-    const hipStream_t st = ctx().stream;
-    // the curve pass over the rows the string reads, [0, n - 1)
-    uint64_t bad_points, first_bad_point;
-    if (int rc = curve_pass(d_in, n - 1, 1, &bad_points, &first_bad_point)) return rc;
-    if (bad_points) {
-        set_error("kzg_open_all_setup: row %llu is not on the curve (%llu such rows)", (unsigned long long)first_bad_point, (unsigned long long)bad_points);
-        return BBGPU_ERR_ARG;
-    }
-    const Limbs9 W = host::limbs_m261(host::fr_root_of_unity(log2n + 1));
-    OpenAllSetup o;
-    if (int rc = kzg_open_all_string(d_in, n, log2n, W.d, &o.d_S, st)) return rc;
-    o.log2n = log2n;
-    o.bytes = 2 * n * 128;
-    o.live = true;
-    g_open_all[slot] = o;
-    return slot;
-}
-
-int bbgpu_kzg_open_all_release(int setup)
-{
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (setup < 0 || setup >= BBGPU_KZG_OPEN_ALL_MAX_SETUPS || !g_open_all[setup].live) {
-        set_error("kzg_open_all_release: unknown setup %d", setup);
-        return BBGPU_ERR_ARG;
-    }
-    open_all_release(g_open_all[setup]); // (dev_free waits for the device: no queued call still reads S^)
-    return BBGPU_OK;
-}
-
-int bbgpu_kzg_open_all_device(int setup, const uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* proofs_out, void* hip_stream)
-{
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (int rc = open_all_batch("kzg_open_all", batch)) return rc;
-    if (!d_coeffs || !proofs_out) {
-        set_error("kzg_open_all: null coeffs / proofs");
-        return BBGPU_ERR_ARG;
-    }
-    if (setup < 0 || setup >= BBGPU_KZG_OPEN_ALL_MAX_SETUPS || !g_open_all[setup].live) {
-        set_error("kzg_open_all: unknown setup %d", setup);
-        return BBGPU_ERR_ARG;
-    }
-    const OpenAllSetup& o = g_open_all[setup];
-    const size_t n = (size_t)1 << o.log2n, N = 2 * n;
-    if (int rc = open_all_sizes("kzg_open_all", n, stride_elems, batch)) return rc;
-    if (int rc = ensure_init()) return rc;
-    const hipStream_t st = (hipStream_t)hip_stream;
-    // t, then t^, then the proofs (batch x N x 32 = batch x n x 64 bytes), and the scratch points
-    DevBuf t, scratch;
-    HIPCHK(dev_malloc(&t.p, (size_t)batch * N * 32));
-    HIPCHK(dev_malloc(&scratch.p, (size_t)batch * N * 128));
-    if (int rc = kzg_open_all_t(d_coeffs, stride_elems, batch, n, t.as<uint64_t>(), st)) return rc;
-    if (int rc = bbgpu_ntt_device_batch(t.as<uint64_t>(), N, N, batch, BBGPU_FFT, nullptr, hip_stream)) return rc;
-    const host::Fr W = host::fr_root_of_unity(o.log2n + 1);
-    const host::Fr c32 = host::fr_from_mont(host::fr_mul(host::fr_inv(host::fr_from_u64((uint64_t)N)), host::fr_from_u64(32))); // the plain integer 32 / N
-    float ms4[4] = { 0, 0, 0, 0 };
-    if (int rc = kzg_open_all_chain(o.d_S, t.as<uint64_t>(), scratch.as<uint32_t>(), n, o.log2n, batch, host::limbs_m256(c32).d, host::limbs_m261(host::fr_inv(W)).d,
-                                    host::limbs_m261(host::fr_root_of_unity(o.log2n)).d, st, ctx().timing ? ms4 : nullptr))
-        return rc;
-    if (int rc = device_to_host_sync(proofs_out, t.p, (size_t)batch * n * 64, st)) return rc;
-    if (ctx().timing) { // bbgpu_last_timing: index 0 the load kernel, 1 the inverse stages, 2 the gather kernel and the forward stages, 3 the finish kernel
-        ctx().last.count = 4;
-        for (int i = 0; i < 4; i++) ctx().last.ms[i] = ms4[i];
-    }
-    return BBGPU_OK;
-}
-
-/* ---- a polynomial opened on every coset of its domain: all n / l KZG cell proofs at once (host_kzg_open_cosets.hpp, kzg_open_cosets.hip) ---- */
 static int open_cosets_n(const char* what, size_t n, size_t coset, int* log2n, int* log2l)
 {
     if (!host::kzg_open_cosets_log2(n, coset, log2n, log2l)) {
@@ -2970,7 +2840,6 @@ static int open_cosets_n(const char* what, size_t n, size_t coset, int* log2n, i
     }
     return BBGPU_OK;
 }
-
 // the degree bound of a setup of (n, l)
 static int open_cosets_bound(const char* what, int log2n, int log2l, size_t degree_bound, int* log2d)
 {
@@ -2981,7 +2850,7 @@ static int open_cosets_bound(const char* what, int log2n, int log2l, size_t degr
     }
     return BBGPU_OK;
 }
-// the sizes of one call over a setup of (n, d)
+// the sizes of one call over a setup of (n, d); d == n, as of every open-all setup, speaks of n alone
 static int open_cosets_sizes(const char* what, size_t n, size_t d, size_t stride_elems, int batch)
 {
     if (!host::kzg_open_cosets_sizes_ok(n, d, stride_elems, batch)) {
@@ -2991,51 +2860,56 @@ static int open_cosets_sizes(const char* what, size_t n, size_t d, size_t stride
     }
     return BBGPU_OK;
 }
+// (n, l, d) of an entry of either family.  cosets == false: an open-all entry, which knows of no coset size and no bound -- n alone is judged, in
+// open_all_n's words, and l = 1, d = n
+static int open_shape(const char* what, bool cosets, size_t n, size_t coset, size_t degree_bound, int* log2n, int* log2l, int* log2d)
+{
+    if (!cosets) {
+        *log2l = 0;
+        const int rc = open_all_n(what, n, log2n);
+        *log2d = *log2n;
+        return rc;
+    }
+    if (int rc = open_cosets_n(what, n, coset, log2n, log2l)) return rc;
+    return open_cosets_bound(what, *log2n, *log2l, degree_bound, log2d);
+}
 
-int bbgpu_host_kzg_open_cosets_bounded(const uint64_t* points_endo_table, size_t n, size_t coset, size_t degree_bound, const uint64_t* coeffs, size_t stride_elems,
-                                       int batch, uint64_t* proofs_out)
+// the host twin of either family (open-all: coset = 1, degree_bound = n)
+static int open_host(const char* what, bool cosets, const uint64_t* points_endo_table, size_t n, size_t coset, size_t degree_bound, const uint64_t* coeffs,
+                     size_t stride_elems, int batch, uint64_t* proofs_out)
 {
     int log2n, log2l, log2d;
-    if (int rc = open_cosets_n("host kzg_open_cosets", n, coset, &log2n, &log2l)) return rc;
-    if (int rc = open_cosets_bound("host kzg_open_cosets", log2n, log2l, degree_bound, &log2d)) return rc;
-    if (int rc = open_all_batch("host kzg_open_cosets", batch)) return rc;
+    if (int rc = open_shape(what, cosets, n, coset, degree_bound, &log2n, &log2l, &log2d)) return rc;
+    if (int rc = open_all_batch(what, batch)) return rc;
     if (!points_endo_table || !coeffs || !proofs_out) {
-        set_error("host kzg_open_cosets: null table / coeffs / proofs");
+        set_error("%s: null table / coeffs / proofs", what);
         return BBGPU_ERR_ARG;
     }
-    if (int rc = open_cosets_sizes("host kzg_open_cosets", n, degree_bound, stride_elems, batch)) return rc;
+    if (int rc = open_cosets_sizes(what, n, degree_bound, stride_elems, batch)) return rc;
     std::vector<host::Xyzz> S;
     uint64_t bad = 0;
     if (host::kzg_open_cosets_setup_bounded_host(points_endo_table, log2d, log2l, S, &bad)) {
-        set_error("host kzg_open_cosets: row %llu is not on the curve", (unsigned long long)bad);
+        set_error("%s: row %llu is not on the curve", what, (unsigned long long)bad);
         return BBGPU_ERR_ARG;
     }
     host::kzg_open_cosets_proofs_bounded_host(S, log2n, log2l, log2d, coeffs, stride_elems, batch, proofs_out);
     return BBGPU_OK;
 }
 
-int bbgpu_host_kzg_open_cosets(const uint64_t* points_endo_table, size_t n, size_t coset, const uint64_t* coeffs, size_t stride_elems, int batch,
-                               uint64_t* proofs_out)
-{
-    int log2n, log2l;
-    if (int rc = open_cosets_n("host kzg_open_cosets", n, coset, &log2n, &log2l)) return rc; // (the bound of the call below is n: never refused)
-    return bbgpu_host_kzg_open_cosets_bounded(points_endo_table, n, coset, n, coeffs, stride_elems, batch, proofs_out);
-}
-
-int bbgpu_kzg_open_cosets_setup_bounded(int srs_handle, size_t n, size_t coset, size_t degree_bound)
+// a setup in `pool` (open-all: coset = 1, degree_bound = n) -> its handle, the lowest free slot of that pool
+static int open_setup_make(OpenPool& pool, const char* what, bool cosets, int srs_handle, size_t n, size_t coset, size_t degree_bound)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     // argument errors before a device is bound: a handle can only exist once one is
     int log2n, log2l, log2d;
-    if (int rc = open_cosets_n("kzg_open_cosets_setup", n, coset, &log2n, &log2l)) return rc;
-    if (int rc = open_cosets_bound("kzg_open_cosets_setup", log2n, log2l, degree_bound, &log2d)) return rc;
+    if (int rc = open_shape(what, cosets, n, coset, degree_bound, &log2n, &log2l, &log2d)) return rc;
     const SrsEntry* ep = nullptr;
-    if (int rc = srs_rows("kzg_open_cosets_setup", srs_handle, degree_bound, BBGPU_ERR_SIZE, &ep)) return rc; // d rows serve every n
+    if (int rc = srs_rows(what, srs_handle, degree_bound, BBGPU_ERR_SIZE, &ep)) return rc; // d rows serve every n
     int slot = -1;
-    for (int k = 0; k < BBGPU_KZG_OPEN_COSETS_MAX_SETUPS && slot < 0; k++)
-        if (!g_open_cosets[k].live) slot = k;
+    for (int k = 0; k < OPEN_MAX_SETUPS && slot < 0; k++)
+        if (!pool[k].live) slot = k;
     if (slot < 0) {
-        set_error("kzg_open_cosets_setup: %d setups are live", BBGPU_KZG_OPEN_COSETS_MAX_SETUPS);
+        set_error("%s: %d setups are live", what, OPEN_MAX_SETUPS);
         return BBGPU_ERR_STATE;
     }
     if (int rc = ensure_init()) return rc;
@@ -3045,50 +2919,50 @@ int bbgpu_kzg_open_cosets_setup_bounded(int srs_handle, size_t n, size_t coset, 
     uint64_t bad_points, first_bad_point;
     if (int rc = curve_pass(d_in, degree_bound - coset, 1, &bad_points, &first_bad_point)) return rc;
     if (bad_points) {
-        set_error("kzg_open_cosets_setup: row %llu is not on the curve (%llu such rows)", (unsigned long long)first_bad_point, (unsigned long long)bad_points);
+        set_error("%s: row %llu is not on the curve (%llu such rows)", what, (unsigned long long)first_bad_point, (unsigned long long)bad_points);
         return BBGPU_ERR_ARG;
     }
     const Limbs9 W = host::limbs_m261(host::fr_root_of_unity(log2d - log2l + 1));
-    OpenCosetsSetup o;
+    OpenSetup o;
     if (int rc = kzg_open_cosets_string(d_in, log2d, log2l, W.d, &o.d_S, st)) return rc;
     o.log2n = log2n;
     o.log2l = log2l;
     o.log2d = log2d;
     o.bytes = 2 * degree_bound * 128;
     o.live = true;
-    g_open_cosets[slot] = o;
+    pool[slot] = o;
     return slot;
 }
 
-int bbgpu_kzg_open_cosets_setup(int srs_handle, size_t n, size_t coset) { return bbgpu_kzg_open_cosets_setup_bounded(srs_handle, n, coset, n); }
-
-int bbgpu_kzg_open_cosets_release(int setup)
+static int open_setup_release(OpenPool& pool, const char* what, int setup)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (setup < 0 || setup >= BBGPU_KZG_OPEN_COSETS_MAX_SETUPS || !g_open_cosets[setup].live) {
-        set_error("kzg_open_cosets_release: unknown setup %d", setup);
+    if (setup < 0 || setup >= OPEN_MAX_SETUPS || !pool[setup].live) {
+        set_error("%s: unknown setup %d", what, setup);
         return BBGPU_ERR_ARG;
     }
-    open_cosets_release(g_open_cosets[setup]); // (dev_free waits for the device: no queued call still reads S^)
+    open_release(pool[setup]); // (dev_free waits for the device: no queued call still reads S^)
     return BBGPU_OK;
 }
 
-int bbgpu_kzg_open_cosets_device(int setup, const uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* proofs_out, void* hip_stream)
+// one call over a setup of `pool`
+static int open_call(const OpenPool& pool, const char* what, int setup, const uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* proofs_out,
+                     void* hip_stream)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (int rc = open_all_batch("kzg_open_cosets", batch)) return rc;
+    if (int rc = open_all_batch(what, batch)) return rc;
     if (!d_coeffs || !proofs_out) {
-        set_error("kzg_open_cosets: null coeffs / proofs");
+        set_error("%s: null coeffs / proofs", what);
         return BBGPU_ERR_ARG;
     }
-    if (setup < 0 || setup >= BBGPU_KZG_OPEN_COSETS_MAX_SETUPS || !g_open_cosets[setup].live) {
-        set_error("kzg_open_cosets: unknown setup %d", setup);
+    if (setup < 0 || setup >= OPEN_MAX_SETUPS || !pool[setup].live) {
+        set_error("%s: unknown setup %d", what, setup);
         return BBGPU_ERR_ARG;
     }
-    const OpenCosetsSetup& o = g_open_cosets[setup];
+    const OpenSetup& o = pool[setup];
     const int log2M = o.log2d - o.log2l + 1; // M = 2 mu = 2 d / l
     const size_t n = (size_t)1 << o.log2n, d = (size_t)1 << o.log2d, l = (size_t)1 << o.log2l, m = n >> o.log2l, M = (size_t)1 << log2M;
-    if (int rc = open_cosets_sizes("kzg_open_cosets", n, d, stride_elems, batch)) return rc;
+    if (int rc = open_cosets_sizes(what, n, d, stride_elems, batch)) return rc;
     if (int rc = ensure_init()) return rc;
     const hipStream_t st = (hipStream_t)hip_stream;
     // t, then t^, then the proofs: batch x 2 d x 32 bytes of scalars, batch x m x 64 of proofs -- the larger of the two (the scalars unless d < m; at d = n
@@ -3097,7 +2971,7 @@ int bbgpu_kzg_open_cosets_device(int setup, const uint64_t* d_coeffs, size_t str
     HIPCHK(dev_malloc(&t.p, (size_t)batch * std::max(2 * d * 32, m * 64)));
     HIPCHK(dev_malloc(&scratch.p, (size_t)batch * 2 * m * 128));
     if (int rc = kzg_open_cosets_t(d_coeffs, stride_elems, batch, o.log2d, o.log2l, t.as<uint64_t>(), st)) return rc;
-    // batch x l transforms of length M, side by side; the batched transform takes KZG_OPEN_ALL_MAX_BATCH of them per call
+    // batch x l transforms of length M, side by side; the batched transform takes KZG_OPEN_ALL_MAX_BATCH of them per call (one call at l = 1)
     for (size_t done = 0, all = (size_t)batch * l; done < all; done += host::KZG_OPEN_ALL_MAX_BATCH) {
         const int group = (int)std::min<size_t>(all - done, host::KZG_OPEN_ALL_MAX_BATCH);
         if (int rc = bbgpu_ntt_device_batch(t.as<uint64_t>() + done * M * 4, M, M, group, BBGPU_FFT, nullptr, hip_stream)) return rc;
@@ -3115,6 +2989,40 @@ int bbgpu_kzg_open_cosets_device(int setup, const uint64_t* d_coeffs, size_t str
         for (int i = 0; i < 4; i++) ctx().last.ms[i] = ms4[i];
     }
     return BBGPU_OK;
+}
+
+int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const uint64_t* coeffs, size_t stride_elems, int batch, uint64_t* proofs_out)
+{
+    return open_host("host kzg_open_all", false, points_endo_table, n, 1, n, coeffs, stride_elems, batch, proofs_out);
+}
+int bbgpu_kzg_open_all_setup(int srs_handle, size_t n) { return open_setup_make(g_open_all, "kzg_open_all_setup", false, srs_handle, n, 1, n); }
+int bbgpu_kzg_open_all_release(int setup) { return open_setup_release(g_open_all, "kzg_open_all_release", setup); }
+int bbgpu_kzg_open_all_device(int setup, const uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* proofs_out, void* hip_stream)
+{
+    return open_call(g_open_all, "kzg_open_all", setup, d_coeffs, stride_elems, batch, proofs_out, hip_stream);
+}
+
+int bbgpu_host_kzg_open_cosets_bounded(const uint64_t* points_endo_table, size_t n, size_t coset, size_t degree_bound, const uint64_t* coeffs, size_t stride_elems,
+                                       int batch, uint64_t* proofs_out)
+{
+    return open_host("host kzg_open_cosets", true, points_endo_table, n, coset, degree_bound, coeffs, stride_elems, batch, proofs_out);
+}
+int bbgpu_host_kzg_open_cosets(const uint64_t* points_endo_table, size_t n, size_t coset, const uint64_t* coeffs, size_t stride_elems, int batch,
+                               uint64_t* proofs_out)
+{
+    int log2n, log2l;
+    if (int rc = open_cosets_n("host kzg_open_cosets", n, coset, &log2n, &log2l)) return rc; // (the bound of the call below is n: never refused)
+    return bbgpu_host_kzg_open_cosets_bounded(points_endo_table, n, coset, n, coeffs, stride_elems, batch, proofs_out);
+}
+int bbgpu_kzg_open_cosets_setup_bounded(int srs_handle, size_t n, size_t coset, size_t degree_bound)
+{
+    return open_setup_make(g_open_cosets, "kzg_open_cosets_setup", true, srs_handle, n, coset, degree_bound);
+}
+int bbgpu_kzg_open_cosets_setup(int srs_handle, size_t n, size_t coset) { return bbgpu_kzg_open_cosets_setup_bounded(srs_handle, n, coset, n); }
+int bbgpu_kzg_open_cosets_release(int setup) { return open_setup_release(g_open_cosets, "kzg_open_cosets_release", setup); }
+int bbgpu_kzg_open_cosets_device(int setup, const uint64_t* d_coeffs, size_t stride_elems, int batch, uint64_t* proofs_out, void* hip_stream)
+{
+    return open_call(g_open_cosets, "kzg_open_cosets", setup, d_coeffs, stride_elems, batch, proofs_out, hip_stream);
 }
 
 int bbgpu_transcript_read_g1(const char* path, size_t degree, uint64_t* points_endo_table_out)

@@ -71,4 +71,13 @@ __device__ __forceinline__ bool min_pair_to_thread0(uint32_t& bad, uint32_t& bug
     return true;
 }
 
+// ---- for the launchers of those files and of kzg_open_cosets.hip: a kernel argument of nine 29-bit limbs from the host's array, and the grid of a count
+static inline Limbs9 to_limbs9(const uint32_t v[9])
+{
+    Limbs9 r;
+    for (int i = 0; i < NL; i++) r.d[i] = v[i];
+    return r;
+}
+static inline uint32_t blocks_of(uint32_t count, int threads) { return (count + threads - 1) / threads; }
+
 } // namespace bbgpu

@@ -463,6 +463,29 @@ BB_HD void store_words32(uint32_t* p, const uint32_t (&w)[32])
 #pragma unroll
     for (int t = 0; t < 8; t++) q[t] = make_uint4(w[4 * t], w[4 * t + 1], w[4 * t + 2], w[4 * t + 3]);
 }
+// o <- the affine form of the scratch point w in the reference's format (x, y: Montgomery-256, canonical; infinity: bit 63 of y[3], the rest zero), by one
+// Fermat inversion.  The finish kernels of kzg_open_cosets.hip and g1_recover.hip, each with its own indexing, are this.
+BB_HD void affine_from_scratch(const uint32_t (&w)[32], uint32_t (&o)[16])
+{
+    Pt p;
+    bool inf;
+    load_pt(p, inf, w);
+    if (inf) {
+#pragma unroll
+        for (int t = 0; t < 16; t++) o[t] = 0;
+        o[15] = 0x80000000u;
+    } else {
+        const auto inv = fq_inverse_fermat(mul(p.zz, p.zzz));
+        const auto izz = mul(inv, p.zzz), izzz = mul(inv, p.zz);
+        uint32_t c[8];
+        to_canonical(m261_to_m256<Fq>(mul(p.x, izz)), c);
+#pragma unroll
+        for (int t = 0; t < 8; t++) o[t] = c[t];
+        to_canonical(m261_to_m256<Fq>(mul(p.y, izzz)), c);
+#pragma unroll
+        for (int t = 0; t < 8; t++) o[8 + t] = c[t];
+    }
+}
 // the butterfly of one lane on its two scratch slots: (a, b) -> (a + k b, a - k b).  unit: k == 1, no ladder (k is not read then).  b is read first and a only
 // after the ladder, whose table fills the register file.
 template <int WB> BB_HD void butterfly_slots(uint32_t* pa, uint32_t* pb, const uint64_t (&k)[4], bool unit)

@@ -258,36 +258,11 @@ __global__ void __launch_bounds__(FT) k_g1_finish(const uint32_t* __restrict__ s
     if (u >= total) return;
     uint32_t w[32], o[16];
     load_words32(scratch + (size_t)u * 32, w);
-    Pt p;
-    bool inf;
-    load_pt(p, inf, w);
-    if (inf) {
-#pragma unroll
-        for (int t = 0; t < 16; t++) o[t] = 0;
-        o[15] = 0x80000000u;
-    } else {
-        const auto inv = fq_inverse_fermat(mul(p.zz, p.zzz));
-        const auto izz = mul(inv, p.zzz), izzz = mul(inv, p.zz);
-        uint32_t c[8];
-        to_canonical(m261_to_m256<Fq>(mul(p.x, izz)), c);
-#pragma unroll
-        for (int t = 0; t < 8; t++) o[t] = c[t];
-        to_canonical(m261_to_m256<Fq>(mul(p.y, izzz)), c);
-#pragma unroll
-        for (int t = 0; t < 8; t++) o[8 + t] = c[t];
-    }
+    affine_from_scratch(w, o);
     uint4* dst = reinterpret_cast<uint4*>(out + (size_t)u * 16);
 #pragma unroll
     for (int t = 0; t < 4; t++) dst[t] = make_uint4(o[4 * t], o[4 * t + 1], o[4 * t + 2], o[4 * t + 3]);
 }
-
-Limbs9 to_limbs9(const uint32_t v[9])
-{
-    Limbs9 r;
-    for (int i = 0; i < NL; i++) r.d[i] = v[i];
-    return r;
-}
-uint32_t blocks_of(uint32_t count, int threads) { return (count + threads - 1) / threads; }
 
 } // namespace
 

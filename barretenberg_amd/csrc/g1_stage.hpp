@@ -1,6 +1,7 @@
 // g1_stage.hpp -- the radix-2 butterfly stage on curve points, the one text srs_lagrange.hip (the inverse transform of bbgpu_srs_lagrange) and
-// kzg_open_all.hip (both transforms of bbgpu_kzg_open_all_device) launch: decimation in time on scratch points (XYZZ, 128 bytes each, ZZ == 0 for infinity;
-// g1_ladder.hpp), one lane per butterfly, the twiddle made in the lane from the root the caller passes.  Each including file gets its own copy of the kernel.
+// kzg_open_cosets.hip (both transforms of bbgpu_kzg_open_cosets_device and, at coset size 1, of bbgpu_kzg_open_all_device) launch: decimation in time on
+// scratch points (XYZZ, 128 bytes each, ZZ == 0 for infinity; g1_ladder.hpp), one lane per butterfly, the twiddle made in the lane from the root the
+// caller passes.  Each including file gets its own copy of the kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 

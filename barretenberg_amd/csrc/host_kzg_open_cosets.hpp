@@ -4,7 +4,8 @@
 // c^(e)_a = c_(e + l a).  With M = 2 m and W the M-th root,
 //   s^(e) = (P^(e)_(m-2) .. P^(e)_0, infinity x (m + 1)),   t^(e) = (c^(e)_(m-1), 0 x (m + 1), c^(e)_1 .. c^(e)_(m-2)),
 //   h = the first m entries of IDFT_M( sum_e DFT_M(s^(e)) o DFT_M(t^(e)) ),
-// and the proofs are the size-m forward transform, root omega^l, of (h_0 .. h_(m-2), infinity).  At l = 1 this is host_kzg_open_all.hpp.  Scalars by
+// and the proofs are the size-m forward transform, root omega^l, of (h_0 .. h_(m-2), infinity).  At l = 1 these are the n single proofs, and this twin is the one of
+// bbgpu_host_kzg_open_all too (host_kzg_open_all.hpp keeps the verdicts and constants of those entries).  Scalars by
 // ntt_radix2, points by g1_transform_host with a plain double-and-add per product and a plain left-to-right sum over e -- NOT the ladder and the lane tree
 // of kzg_open_cosets.hip, so that device and twin check each other.
 // A polynomial of degree < d, d a power of two with 2 l <= d <= n (bbgpu_kzg_open_cosets_setup_bounded), needs Toeplitz products of size mu = d / l only: with

@@ -282,13 +282,6 @@ __global__ void __launch_bounds__(CT) k_kzg_cells_fold_finish(const uint64_t* __
     put_slot(s, k, S, skip_mask, out);
 }
 
-Limbs9 to_limbs9(const uint32_t v[9])
-{
-    Limbs9 r;
-    for (int i = 0; i < NL; i++) r.d[i] = v[i];
-    return r;
-}
-
 } // namespace
 
 // B.find: one KzgFindings the caller has initialised ({0, ~0})

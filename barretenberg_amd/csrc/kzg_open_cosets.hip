@@ -1,7 +1,10 @@
-// kzg_open_cosets.hip -- the device part of bbgpu_kzg_open_cosets_setup and bbgpu_kzg_open_cosets_device (include/bbgpu.h): the KZG proof pi_k of a
-// polynomial on every coset { omega^(k + m j) : j < l } of its domain, m = n / l cosets of l points, by the multi-proof construction of Feist and Khovratovich
-// (host_kzg_open_cosets.hpp states it).  String and coefficients are split by residue e = j mod l into l problems of the kzg_open_all.hip layout at size m,
-// whose products are SUMMED in the Fourier domain: with M = 2 m and W the M-th root, one inverse transform of length M and one forward transform of length m
+// kzg_open_cosets.hip -- the device part of bbgpu_kzg_open_cosets_setup and bbgpu_kzg_open_cosets_device, and of bbgpu_kzg_open_all_setup and
+// bbgpu_kzg_open_all_device, which are the coset size l = 1 without a bound (include/bbgpu.h): the KZG proof pi_k of a polynomial on every coset
+// { omega^(k + m j) : j < l } of its domain, m = n / l cosets of l points, by the multi-proof construction of Feist and Khovratovich
+// (host_kzg_open_cosets.hpp states it).  At l = 1 that is one structured linear map of the string: with N = 2 n, W the N-th root and
+//   s = (P_(n-2) .. P_0, infinity x (n + 1)),   t = (c_(n-1), 0 x (n + 1), c_1 .. c_(n-2)),   h = the first n entries of IDFT_N(DFT_N(s) o DFT_N(t)),
+// the proofs are the size-n forward transform of (h_0 .. h_(n-2), infinity).  For l > 1 string and coefficients are split by residue e = j mod l into l
+// problems of that layout at size m, whose products are SUMMED in the Fourier domain: with M = 2 m and W the M-th root, one inverse transform of length M and one forward transform of length m
 // serve all l residues.  Points live on a scratch of projective points (XYZZ, 128 bytes each, ZZ == 0 for infinity; g1_ladder.hpp) and every per-call kernel
 // takes the polynomial of a batch from blockIdx.y.  A setup carries a degree bound d, 2 l <= d <= n (bbgpu_kzg_open_cosets_setup_bounded; d = n without one):
 // the Toeplitz products then have size mu = d / l, M = 2 mu, and only the last forward transform lives on the size-m domain, rho = m / mu:
@@ -9,20 +12,21 @@
 //                        leave S^(e) = DFT_M(s^(e)), l x M = 2 d points kept by the handle;
 //   k_open_cosets_t      the batch x l x M scalars of t^(e) from the coefficients; bbgpu_ntt_device_batch transforms them (capi.hip);
 //   k_open_cosets_sum    slot i <- sum_e (M^-1 t^^(e)_j) * S^(e)_j, j = bitrev(i): lane (f, e) of a wave runs the ladder of residue e at the wave's f-th
-//                        frequency, then the l results of a frequency are added in a log2 l-level tree across lanes, through LDS;
+//                        frequency, then the l results of a frequency are added in a log2 l-level tree across lanes, through LDS (no level at l = 1: every
+//                        lane stores its own product);
 //   k_lagrange_stage     log2 M launches with root W^-1: slots [0, mu - 1) now hold h;
 //   k_open_cosets_gather slot m + rho bitrev_mu(u) + c <- slot u for u < mu - 1 and every c < rho, the rho slots of u = mu - 1 <- infinity: the size-m
 //                        input (h_0 .. h_(mu-2), infinity x (m - mu + 1)) in bit-reversed order is nonzero at multiples of rho only, and stages 0 ..
 //                        log2 rho - 1 of the decimation in time would turn every (a, infinity) into (a, a) -- the gather writes those copies itself;
 //   k_lagrange_stage     stages log2 rho .. log2 m - 1 of the size-m transform with root omega^l on those upper halves (all log2 m at d = n);
-//   k_open_cosets_finish one Fermat inversion per row to the reference's affine format.
+//   k_open_cosets_finish one Fermat inversion per row to the reference's affine format (affine_from_scratch, g1_ladder.hpp).
 // Every polynomial owns 2 m scratch slots whatever d is: the convolution in [0, M), M <= 2 m, the forward transform in [m, 2 m) (M <= m when d < n, and at
-// d = n the gather reads below m and writes from m on).  At d = n every launch, index and result is that of the construction without a bound.  The finish
-// kernel is that of kzg_open_all.hip at size m (each file has its own copy, as of the stage kernel).  One wave per
+// d = n the gather reads below m and writes from m on).  At d = n every launch, index and result is that of the construction without a bound.  One wave per
 // workgroup, 3-bit windows and no twiddle table, as srs_lagrange.hip.  The reference has no counterpart.
 #include <hip/hip_runtime.h>
 
 #include "bbgpu_internal.h"
+#include "fr_mem_device.hpp"
 #include "g1_stage.hpp"
 
 namespace bbgpu {
@@ -80,8 +84,9 @@ __global__ void __launch_bounds__(FT) k_open_cosets_t(const uint32_t* __restrict
     dst[1] = hi;
 }
 
-// slot i of polynomial blockIdx.y <- sum_{e < l} k_e * S^(e)_j, j = bitrev_M(i), k_e = M^-1 t^^(e)_j as a plain canonical integer (the product trick of
-// k_open_all_load: c32 holds the plain integer 32 M^-1 mod r).  Thread g = i l + e: the l lanes of a frequency are neighbours, a wave takes 64 / l
+// slot i of polynomial blockIdx.y <- sum_{e < l} k_e * S^(e)_j, j = bitrev_M(i), k_e = M^-1 t^^(e)_j as a plain canonical integer (t^^ is in the memory
+// format, x 2^256, any representative, c32 holds the plain integer 32 M^-1 mod r, and the Montgomery-261 product of the two is M^-1 t^^ itself, as
+// k_srs_update brings y^e to an integer by a product with the plain one).  Thread g = i l + e: the l lanes of a frequency are neighbours, a wave takes 64 / l
 // frequencies.  Each lane runs its own ladder (a zero scalar or an infinite base gives infinity; so does a lane past the end, which arises for l M < 64
 // only), then level d of the tree adds the point of lane e + 2^d to that of every lane e with e mod 2^(d+1) == 0.  The points cross in LDS as 32 canonical
 // words, word w of lane L at w * 64 + L (consecutive lanes on consecutive banks).  The addition is complete: either side may be infinity, equal points
@@ -180,36 +185,11 @@ __global__ void __launch_bounds__(FT) k_open_cosets_finish(const uint32_t* __res
     const size_t b = blockIdx.y;
     uint32_t w[32], o[16];
     load_words32(scratch + (b * 2 * m + m + i) * 32, w);
-    Pt p;
-    bool inf;
-    load_pt(p, inf, w);
-    if (inf) {
-#pragma unroll
-        for (int t = 0; t < 16; t++) o[t] = 0;
-        o[15] = 0x80000000u;
-    } else {
-        const auto inv = fq_inverse_fermat(mul(p.zz, p.zzz));
-        const auto izz = mul(inv, p.zzz), izzz = mul(inv, p.zz);
-        uint32_t c[8];
-        to_canonical(m261_to_m256<Fq>(mul(p.x, izz)), c);
-#pragma unroll
-        for (int t = 0; t < 8; t++) o[t] = c[t];
-        to_canonical(m261_to_m256<Fq>(mul(p.y, izzz)), c);
-#pragma unroll
-        for (int t = 0; t < 8; t++) o[8 + t] = c[t];
-    }
+    affine_from_scratch(w, o);
     uint4* dst = reinterpret_cast<uint4*>(out + (b * m + i) * 16);
 #pragma unroll
     for (int t = 0; t < 4; t++) dst[t] = make_uint4(o[4 * t], o[4 * t + 1], o[4 * t + 2], o[4 * t + 3]);
 }
-
-Limbs9 to_limbs9(const uint32_t v[9])
-{
-    Limbs9 r;
-    for (int i = 0; i < NL; i++) r.d[i] = v[i];
-    return r;
-}
-uint32_t blocks_of(uint32_t count, int threads) { return (count + threads - 1) / threads; }
 
 } // namespace
 

@@ -842,7 +842,7 @@ int bbgpu_host_srs_lagrange_check(const uint64_t* lagrange_endo_table, const uin
  *   infinity     a row of S^ at infinity is legal and kept exactly -- it is an intermediate, not a table anyone commits over.  It happens when
  *                (W^k / x)^(n-1) = 1 and W^k != x; at n = 4 that is x = W^k zeta, zeta a primitive cube root of unity in Fr.
  * Returns the setup handle (>= 0).  A warm setup passes one allocation (S^), one upload and one read-back (the curve findings) and two launch checks (the
- * curve pass; the chain of k_open_all_string and the log2 N stage kernels).  The SRS handle is not read after the setup returns and may be released.
+ * curve pass; the chain of k_open_cosets_string and the log2 N stage kernels).  The SRS handle is not read after the setup returns and may be released.
  * bbgpu_kzg_open_all_device opens `batch` polynomials in coefficient form over one setup: coefficient j of polynomial b at
  * d_coeffs[(b * stride_elems + j) * 4] (device memory, read only; the reference's memory format, any representative), and writes batch x n affine points to
  * HOST memory: proofs_out[(b * n + i) * 8] is pi_b(omega^i) in the reference's format (Montgomery-256, canonical; infinity: bit 63 of y[3], every other word
@@ -850,27 +850,28 @@ int bbgpu_host_srs_lagrange_check(const uint64_t* lagrange_endo_table, const uin
  * away for the caller; this entry does not return them.
  *   BBGPU_ERR_SIZE   batch outside 1..64, stride_elems < n, batch x 2 n > 2^22
  *   BBGPU_ERR_ARG    an unknown setup, a null pointer                                    -- all refused before a device is bound
- * The kernels (csrc/kzg_open_all.hip; every one takes the polynomial from blockIdx.y, so that a batch of small domains fills the chip): k_open_all_t writes
- * the batch x N scalars of t and bbgpu_ntt_device_batch transforms them; k_open_all_load puts (N^-1 t^_bitrev(i)) * S^_bitrev(i) into slot i -- each lane reads
- * its own scalar, brings it to a plain canonical integer by one product and runs one ladder (csrc/g1_ladder.hpp) over a projective base; a zero scalar or
+ * The kernels are those of bbgpu_kzg_open_cosets_device (the next block) at coset size 1 without a degree bound: a setup of this block is such a setup, kept
+ * in a pool of its own (csrc/kzg_open_cosets.hip; every one takes the polynomial from blockIdx.y, so that a batch of small domains fills the chip):
+ * k_open_cosets_t writes the batch x N scalars of t and bbgpu_ntt_device_batch transforms them; k_open_cosets_sum, which at this size adds nothing, puts
+ * (N^-1 t^_bitrev(i)) * S^_bitrev(i) into slot i -- each lane reads its own scalar, brings it to a plain canonical integer by one product and runs one ladder (csrc/g1_ladder.hpp) over a projective base; a zero scalar or
  * an infinite base gives infinity; log2 N launches of k_lagrange_stage (csrc/g1_stage.hpp, the one text bbgpu_srs_lagrange launches too) with root W^-1;
- * k_open_all_gather copies slots 0 .. n-2 bit-reversed into the upper half of the polynomial's own slots, with infinity last; log2 n launches of
- * k_lagrange_stage with root omega there; k_open_all_finish normalises with one Fermat inversion per row and refuses nothing.  One wave per workgroup,
+ * k_open_cosets_gather copies slots 0 .. n-2 bit-reversed into the upper half of the polynomial's own slots, with infinity last; log2 n launches of
+ * k_lagrange_stage with root omega there; k_open_cosets_finish normalises with one Fermat inversion per row and refuses nothing.  One wave per workgroup,
  * 3-bit windows, no twiddle table, as bbgpu_srs_lagrange.
  * The entry runs on context 0 under the library mutex; every allocation, copy and launch check passes the fault-injection funnels.  A warm call at n = 64:
  * two allocations (t, which later holds the proofs, and the scratch points), no upload, one read-back (the proofs: one staging chunk), and three launch
- * checks (k_open_all_t; the transform's single pass at this size; the chain from the load kernel to the finish kernel).  After a failure nothing the call allocated is live and
- * the setup stays usable.  With bbgpu_set_timing(1), bbgpu_last_timing() index 0 is the device time of k_open_all_load, 1 that of the inverse stages, 2 that
- * of the gather kernel and the forward stages, 3 that of k_open_all_finish.
+ * checks (k_open_cosets_t; the transform's single pass at this size; the chain from the sum kernel to the finish kernel).  After a failure nothing the call allocated is live and
+ * the setup stays usable.  With bbgpu_set_timing(1), bbgpu_last_timing() index 0 is the device time of k_open_cosets_sum, 1 that of the inverse stages, 2 that
+ * of the gather kernel and the forward stages, 3 that of k_open_cosets_finish.
  * Cost on one MI355X (tools/kzg_open_all_bench.py, profiles/kzg_open_all.txt): wall ms per call, proofs read back to the host, one box.  n = 2^12:
  * 24.5 ms at batch 1 and 28.0 ms at batch 16 -- a single 4096-row call is bound by the latency of its 25 stage launches (the inverse stages 12.1 ms, the
- * gather and the forward stages 11.1 ms, the load kernel 1.0 ms, the finish kernel 0.15 ms of device time), and fifteen more polynomials ride along for
+ * gather and the forward stages 11.1 ms, the kernel of the ladders (then k_open_all_load, a kernel of this entry's own) 1.0 ms, the finish kernel 0.15 ms of device time), and fifteen more polynomials ride along for
  * 3.6 ms; n = 2^16: 34.8 ms at batch 1, 348 ms at batch 16 (the chip is full: inverse stages 214 ms, forward 102 ms, load 28 ms); n = 2^20: 433 ms (inverse
  * stages 271 ms = 12.9 ns per butterfly that runs a ladder, forward 130 ms, load 28 ms, finish 1.9 ms).  The setup, with its release: 12.2 ms, 16.8 ms and
  * 271 ms.  Against the path a caller had before -- bbgpu_kate_opening_device, then bbgpu_msm_g1_device, per point over the same handle, timed in the same
  * process on a SAMPLE of 256 points and SCALED to all n (an extrapolation): 1.54 s at 2^12, 24.2 s at 2^16 and 1487 s at 2^20 per polynomial; the new
  * entry is lower at every size measured, by far more than either spread.
- * The host twin (csrc/host_kzg_open_all.hpp) runs the same construction over host_g1.hpp: the scalar transform of the bbgpu_host_* family, the radix-2
+ * The host twin (that of the next block at coset size 1, csrc/host_kzg_open_cosets.hpp) runs the same construction over host_g1.hpp: the scalar transform of the bbgpu_host_* family, the radix-2
  * group transform of bbgpu_host_srs_lagrange and a plain double-and-add per product.  The results are unique affine points, so device and twin agree bit
  * for bit.  It takes the even entries of a caller's endo table (at least n - 1 rows are read), makes no HIP call, takes no lock and is re-entrant; its
  * errors are those of the two device entries (a row off the curve: BBGPU_ERR_ARG naming it). */
@@ -922,7 +923,7 @@ int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const u
  * one wave takes 64 / l frequencies, lane (f, e) brings its own scalar to a plain integer and runs one ladder (csrc/g1_ladder.hpp) over its own projective
  * base, and the l results of a frequency are added in a log2 l-level tree across lanes, the points crossing in 8 KiB of LDS; the additions are complete
  * (either side at infinity, equal points, opposite points); log2 M launches of k_lagrange_stage (csrc/g1_stage.hpp) with root W^-1; k_open_cosets_gather,
- * log2 m launches of k_lagrange_stage with root psi and k_open_cosets_finish are the open-all kernels at sizes m and M.
+ * log2 m launches of k_lagrange_stage with root psi and k_open_cosets_finish work as the block above says, at sizes m and M.
  * The entry runs on context 0 under the library mutex; every allocation, copy and launch check passes the fault-injection funnels.  A warm call at
  * (n, l) = (256, 4): two allocations (t, which later holds the proofs, and the scratch points), no upload, one read-back (the proofs: one staging chunk),
  * and three launch checks (k_open_cosets_t; the transform's single pass at this size -- one more for every further group of 64 transforms; the chain from
@@ -936,7 +937,8 @@ int bbgpu_host_kzg_open_all(const uint64_t* points_endo_table, size_t n, const u
  * (batch 16: 104 against 349).  The new entry is lower in every cell, by more than the full range (max - min) of either leg's timings.  Device times at
  * (2^20, 64): the sum kernel 31.4 ms, the inverse stages 14.0 ms, the gather and the forward stages 13.1 ms, the finish kernel 0.16 ms -- the 2 n ladders
  * are now more than half the call, and a call of few polynomials stays bound from below by the latency of its log2 M + log2 m stage launches (about 0.9
- * ms each: 12.0 of 13.2 ms at (2^12, 64)).  k_open_cosets_sum against k_open_all_load over the same 2 n ladders, both from bbgpu_set_timing in that process:
+ * ms each: 12.0 of 13.2 ms at (2^12, 64)).  k_open_cosets_sum against k_open_all_load, the treeless kernel the open-all entries then had, over the same 2 n ladders, both from bbgpu_set_timing in that
+ * process:
  * +0.96 ms on 30.4 at 2^20 and +0.15 on 2.2 at 2^16 -- the tree and the LDS crossing cost 3 to 7 percent of the kernel.  231 VGPRs against 229, no scratch
  * memory in either (the compiler's resource remarks, at the head of the profile).  The setup, with its release: 6.5 ms, 10.8 ms and 187 ms at l = 64, 14.7
  * ms at (2^16, 4).  Nothing was tuned after these measurements.

@@ -1,4 +1,5 @@
-// The host twin of bbgpu_kzg_open_all_device (csrc/host_kzg_open_all.hpp: kzg_open_all_setup_host, kzg_open_all_proofs_host) under AddressSanitizer and
+// The host twin of bbgpu_kzg_open_all_device -- the twin of the coset entries at coset size 1 without a bound (csrc/host_kzg_open_cosets.hpp:
+// kzg_open_cosets_setup_bounded_host, kzg_open_cosets_proofs_bounded_host at log2l = 0, log2d = log2n) -- under AddressSanitizer and
 // UndefinedBehaviorSanitizer, at n = 8 and n = 64.  The expected proofs come from the quotient definition, point by point: the coefficients of
 // (f(X) - f(w^i)) / (X - w^i) by kate_opening (host_fallback.hpp), committed by the bucket method over the same rows.  Batch 1 and 3, with padding between
 // the polynomials; a constant polynomial (every proof at infinity), f = X (every proof the generator) and a polynomial with a zero among t^.
@@ -7,7 +8,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../barretenberg_amd/csrc/host_kzg_open_all.hpp"
+#include "../../barretenberg_amd/csrc/host_kzg_open_cosets.hpp"
 
 using namespace bbgpu::host;
 
@@ -60,9 +61,9 @@ static void run(const std::vector<uint64_t>& table, size_t n, int batch, size_t 
     const std::vector<Fr> kept = c;
     std::vector<Xyzz> S;
     uint64_t bad = ~0ull;
-    CHECK(kzg_open_all_setup_host(table.data(), n, log2n, S, &bad) == BBGPU_OK, "%s n=%zu: setup", name, n);
+    CHECK(kzg_open_cosets_setup_bounded_host(table.data(), log2n, 0, S, &bad) == BBGPU_OK, "%s n=%zu: setup", name, n);
     std::vector<uint64_t> got((size_t)batch * n * 8 + 8, 0xA5A5A5A5A5A5A5A5ULL); // one point of guard behind
-    kzg_open_all_proofs_host(S, n, log2n, c[0].d, stride, batch, got.data());
+    kzg_open_cosets_proofs_bounded_host(S, log2n, 0, log2n, c[0].d, stride, batch, got.data());
     const Fr w = fr_root_of_unity(log2n);
     std::vector<Fr> q(n);
     for (int b = 0; b < batch; b++) {
@@ -97,7 +98,7 @@ int main()
         table[16 * 3 + 4] ^= 1;
         std::vector<Xyzz> S;
         uint64_t bad = ~0ull;
-        CHECK(kzg_open_all_setup_host(table.data(), 8, 3, S, &bad) == BBGPU_ERR_ARG && bad == 3, "bad row %llu", (unsigned long long)bad);
+        CHECK(kzg_open_cosets_setup_bounded_host(table.data(), 3, 0, S, &bad) == BBGPU_ERR_ARG && bad == 3, "bad row %llu", (unsigned long long)bad);
     }
     CHECK(kzg_open_all_log2(2) == 1 && kzg_open_all_log2((size_t)1 << 21) == 21 && kzg_open_all_log2((size_t)1 << 22) < 0 && kzg_open_all_log2(1) < 0 &&
               kzg_open_all_log2(0) < 0 && kzg_open_all_log2(6) < 0, "log2");

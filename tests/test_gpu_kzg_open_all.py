@@ -1,6 +1,6 @@
-"""bbgpu_kzg_open_all_setup / bbgpu_kzg_open_all_device on the GPU (-m gpu): the kernels of csrc/kzg_open_all.hip (the string and its transform, the scalars
-of t, the load that multiplies each row by its own scalar, both group transforms over a batch, the gather, the normalisation with infinities) against the
-host twin bit for bit -- itself held to the quotient definition by tests/test_kzg_open_all_host.py -- against the device's own per-point path, and against
+"""bbgpu_kzg_open_all_setup / bbgpu_kzg_open_all_device on the GPU (-m gpu): the kernels of csrc/kzg_open_cosets.hip at coset size 1 (the string and
+its transform, the scalars of t, the sum kernel that at this size multiplies each row by its own scalar and adds nothing, both group transforms over a
+batch, the gather, the normalisation with infinities) against the host twin bit for bit -- itself held to the quotient definition by tests/test_kzg_open_all_host.py -- against the device's own per-point path, and against
 the pairing check.  Sizes: n = 2, 4 (the shortest transforms), 32 (N = 64: one workgroup), 64 (N = 128: the first size at which k_lagrange_stage takes its
 groups-per-wave addressing), 256 with batch 1, 3 and 16 (both addressings in several stages, and the batch dimension), 4096 through the pairing check."""
 import numpy as np
@@ -15,7 +15,7 @@ KEYS = {"alloc": "alloc_calls", "h2d": "h2d_calls", "d2h": "d2h_calls", "launch"
 FAR = 1 << 62
 ROWS = 4096
 # the funnels one warm call at n = 64 passes (include/bbgpu.h): allocations -- t (later the proofs) and the scratch points; no upload; read-backs -- the
-# proofs (one staging chunk); launch checks -- k_open_all_t, the transform of t, the chain from the load kernel to the finish kernel
+# proofs (one staging chunk); launch checks -- k_open_cosets_t, the transform of t, the chain from the sum kernel to the finish kernel
 WARM = dict(alloc_calls=2, h2d_calls=0, d2h_calls=1, launch_checks=3)
 WARM_SETUP = dict(alloc_calls=1, h2d_calls=1, d2h_calls=1, launch_checks=2)
 
@@ -289,4 +289,4 @@ def test_kernel_times_are_reported(lib, oracle, world):
         ms = lib.last_timing()
     finally:
         lib.set_timing(0)
-    assert len(ms) == 4 and all(0 < v < 1000 for v in ms), ms  # the load kernel, the inverse stages, the gather and the forward stages, the finish kernel
+    assert len(ms) == 4 and all(0 < v < 1000 for v in ms), ms  # the sum kernel (no tree at l = 1), the inverse stages, the gather and the forward stages, the finish kernel

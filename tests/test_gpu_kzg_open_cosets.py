@@ -2,7 +2,7 @@
 transforms, the scalars of t^(e), the sum kernel with its ladders and its tree of additions across lanes, both group transforms over a batch, the gather, the
 normalisation with infinities) against the host twin bit for bit -- itself held to the quotient definition by tests/test_kzg_open_cosets_host.py -- against
 the definition directly at a larger size, and against the fold of bbgpu_kzg_open_all_device's own proofs.  Sizes (n, l): (4, 2) a partly filled wave and
-M = 4; (2, 1) and (64, 1) no tree, also bbgpu_kzg_open_all_device bit for bit; (8, 4); (128, 64) a full-wave tree over the shortest transform; (256, 4)
+M = 4; (2, 1) and (64, 1) no tree, also bbgpu_kzg_open_all_device bit for bit (two entries with a pool each over one device path); (8, 4); (128, 64) a full-wave tree over the shortest transform; (256, 4)
 sixteen frequencies per wave, M = 128 the first size with the groups-per-wave addressing of k_lagrange_stage; (256, 64), at batch 3 with 192 scalar
 transforms: more than one group of 64; (4096, 64) against the definition."""
 import numpy as np
@@ -80,7 +80,8 @@ def open_cosets(lib, setup, polys, n, l, stride, oracle):
 @pytest.mark.parametrize("n,l,batch,pad", [(4, 2, 1, 0), (4, 2, 3, PAD), (2, 1, 1, 0), (2, 1, 3, PAD), (64, 1, 1, 0), (64, 1, 3, PAD), (8, 4, 1, 0), (8, 4, 3, PAD),
                                            (128, 64, 1, 0), (128, 64, 3, PAD), (256, 4, 1, 0), (256, 4, 3, PAD), (256, 64, 1, 0), (256, 64, 3, PAD)])
 def test_device_against_twin(lib, oracle, world, n, l, batch, pad):
-    """every case polynomial, `batch` of them per call (the list wraps), bit for bit; at l = 1 also bbgpu_kzg_open_all_device's proofs"""
+    """every case polynomial, `batch` of them per call (the list wraps), bit for bit; at l = 1 also bbgpu_kzg_open_all_device's proofs: the same kernels
+    reached through the other entry and the other pool"""
     cases, want = coset_polynomials(oracle, n, l), world["twin"](n, l)
     for k in range(0, len(cases), batch):
         group = [cases[(k + b) % len(cases)] for b in range(batch)]
@@ -251,7 +252,8 @@ def test_injected_failures_leave_nothing_behind(lib, oracle, world, kind):
 
 
 def test_argument_errors_on_a_bound_device(lib, oracle, world):
-    """the verdicts that need a table or a setup; the pool runs out at BBGPU_KZG_OPEN_COSETS_MAX_SETUPS and is not the pool of bbgpu_kzg_open_all_setup"""
+    """the verdicts that need a table or a setup; the pool runs out at BBGPU_KZG_OPEN_COSETS_MAX_SETUPS and is not the pool of bbgpu_kzg_open_all_setup:
+    both hold the same kind of setup, and this is the guard on their staying two"""
     from barretenberg_amd import BbGpuError
     fake = 0x1000  # never dereferenced
     for n in (2 * ROWS, 1 << 21):  # larger than the table
@@ -295,6 +297,49 @@ def test_argument_errors_on_a_bound_device(lib, oracle, world):
         lib.kzg_open_cosets_release(big)
     with pytest.raises(BbGpuError, match=ERR_ARG):
         lib.kzg_open_cosets_device(big, fake, 1 << 16, 64)
+
+
+def test_a_handle_of_one_pool_is_unknown_to_the_other(lib, oracle, world):
+    """both families keep one kind of setup: a number that is live in the pool of bbgpu_kzg_open_all_setup and free in this one is refused by
+    bbgpu_kzg_open_cosets_device and bbgpu_kzg_open_cosets_release, and the open-all setup answers as before; then the mirror image with a setup of (4, 2)"""
+    from barretenberg_amd import BbGpuError
+    n = 4
+    cases = polynomials(oracle, n)
+    buf = buffer_of(oracle, [c for _, c in cases], n)
+    d = dev(buf)
+    live = lib.fault_stats()["live_allocations"]
+    if len(world["setups"]) == 16:  # no number is free in this pool: give one up
+        lib.kzg_open_cosets_release(world["setups"].pop(next(iter(world["setups"]))))
+        live -= 1
+    singles = [lib.kzg_open_all_setup(world["h"], n)]
+    while singles[-1] in world["setups"].values():
+        singles.append(lib.kzg_open_all_setup(world["h"], n))
+    s = singles[-1]
+    try:
+        with pytest.raises(BbGpuError, match=ERR_ARG):
+            lib.kzg_open_cosets_device(s, d.data_ptr(), n, 1, batch=len(cases))
+        with pytest.raises(BbGpuError, match=ERR_ARG):
+            lib.kzg_open_cosets_release(s)
+        want = lib.host_kzg_open_all(aligned_copy(world["table"][:2 * n]), n, buf, batch=len(cases))
+        assert np.array_equal(lib.kzg_open_all_device(s, d.data_ptr(), n, batch=len(cases)), want)
+    finally:
+        for t in singles:
+            lib.kzg_open_all_release(t)
+    pairs = coset_polynomials(oracle, n, 2)
+    d = dev(buffer_of(oracle, [c for _, c in pairs], n))
+    want = world["twin"](n, 2)
+    s = lib.kzg_open_cosets_setup(world["h"], n, 2)  # the pool of bbgpu_kzg_open_all_setup is empty again: every number is free there
+    try:
+        with pytest.raises(BbGpuError, match=ERR_ARG):
+            lib.kzg_open_all_device(s, d.data_ptr(), n, batch=len(pairs))
+        with pytest.raises(BbGpuError, match=ERR_ARG):
+            lib.kzg_open_all_release(s)
+        got = lib.kzg_open_cosets_device(s, d.data_ptr(), n, 2, batch=len(pairs))
+        for b, (name, _) in enumerate(pairs):
+            assert np.array_equal(got[b], want[name]), name
+    finally:
+        lib.kzg_open_cosets_release(s)
+    assert lib.fault_stats()["live_allocations"] == live
 
 
 def test_kernel_times_are_reported(lib, oracle, world):

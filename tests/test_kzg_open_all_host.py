@@ -1,4 +1,4 @@
-"""bbgpu_host_kzg_open_all (csrc/host_kzg_open_all.hpp): the n KZG proofs of a polynomial at every point of its domain by one Toeplitz product and one group
+"""bbgpu_host_kzg_open_all (csrc/host_kzg_open_all.hpp; the twin of csrc/host_kzg_open_cosets.hpp at coset size 1): the n KZG proofs of a polynomial at every point of its domain by one Toeplitz product and one group
 transform, held to the quotient definition point by point (tests/kzg_open_all_cases.py: bbgpu_host_kate_opening, then bbgpu_host_msm_g1) -- the twin the GPU
 entry is compared with bit for bit (tests/test_gpu_kzg_open_all.py) -- and the argument verdicts of the twin and of the device entries on a machine
 without a GPU.  CPU tests."""

@@ -7,8 +7,9 @@ legacy default stream; random coefficients; a generated string nobody uses.
               handle, for ONE polynomial at a SAMPLE of 256 points (fixed indices).  The leg's time is that of the 256 points; the report scales it by
               n / 256 to all n points of one polynomial, and by the batch to the batch -- an extrapolation, marked as such on every line.
 n = 2^12 and 2^16 with batch 1 and 16, n = 2^20 with batch 1.  bbgpu_kzg_open_all_setup is timed alone (setup + release, not paired).  The per-kernel
-device times of one call per cell come from bbgpu_set_timing.  No ratio is asserted: the lines say which leg's median is lower and whether the gap exceeds
-the spread (the slower leg's interquartile range).
+device times of one call per cell come from bbgpu_set_timing; the first is k_open_cosets_sum of csrc/kzg_open_cosets.hip, which at coset size 1 multiplies
+each row by its own scalar and adds nothing.  No ratio is asserted: the lines say which leg's median is lower and whether the gap exceeds the spread (the
+slower leg's interquartile range).
 Usage: python tools/kzg_open_all_bench.py [--pairs 9] [--out PATH]"""
 import argparse
 import os
@@ -72,7 +73,7 @@ def main():
             lib.kzg_open_all_device(setup, c.data_ptr(), n, batch=batch, out=out[:batch])
             ms = lib.last_timing()
             lib.set_timing(0)
-            say("n 2^%d batch %2d  device ms: load %.3f, inverse stages %.3f, gather + forward stages %.3f, finish %.3f" % ((lg, batch) + tuple(ms)))
+            say("n 2^%d batch %2d  device ms: sum (l = 1) %.3f, inverse stages %.3f, gather + forward stages %.3f, finish %.3f" % ((lg, batch) + tuple(ms)))
         lib.kzg_open_all_release(setup)
         lib.srs_release(h)
         del c, q

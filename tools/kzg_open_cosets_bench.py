@@ -6,9 +6,10 @@ device synchronise; the legacy default stream; random coefficients; a generated 
   open-all     one bbgpu_kzg_open_all_device call at the same n and batch: all n single proofs, read back to the host -- the first half of the old path.
                Its second half, an l-point MSM per cell on the host, is NOT timed and not charged: the comparison favours the old path.
 (n, l) = (2^12, 64), (2^16, 64), (2^16, 4) with batch 1 and 16, (2^20, 64) with batch 1.  bbgpu_kzg_open_cosets_setup is timed alone (setup + release, not
-paired).  The per-kernel device times of one call per leg and cell come from bbgpu_set_timing; k_open_cosets_sum and k_open_all_load run the same 2 n
-ladders per polynomial, so the difference of the two is the tree of additions across lanes.  No ratio is asserted: the lines say which leg's median is
-lower and whether the gap exceeds the spread, taken as the larger of the two legs' full ranges (max - min).
+paired).  The per-kernel device times of one call per leg and cell come from bbgpu_set_timing; both entries run k_open_cosets_sum over the same 2 n
+ladders per polynomial, the open-all one at coset size 1 where its tree has no level, so the difference of the two is the tree of additions across lanes.
+No ratio is asserted: the lines say which leg's median is lower and whether the gap exceeds the spread, taken as the larger of the two legs' full ranges
+(max - min).
 --head FILE puts the lines of FILE in front of the output (the compiler's resource remarks for csrc/kzg_open_cosets.hip, which no run on the GPU can make).
 Usage: python tools/kzg_open_cosets_bench.py [--pairs 9] [--head FILE] [--out PATH]"""
 import argparse
@@ -67,8 +68,8 @@ def main():
                 ms_all = lib.last_timing()
                 lib.set_timing(0)
                 say("n 2^%d l %2d batch %2d  open-cosets device ms: sum %.3f, inverse stages %.3f, gather + forward stages %.3f, finish %.3f" % ((lg, l, batch) + tuple(ms)))
-                say("n 2^%d l %2d batch %2d  open-all    device ms: load %.3f, inverse stages %.3f, gather + forward stages %.3f, finish %.3f; "
-                    "k_open_cosets_sum - k_open_all_load, the same %d ladders: %+.3f ms" % ((lg, l, batch) + tuple(ms_all) + (2 * n * batch, ms[0] - ms_all[0])))
+                say("n 2^%d l %2d batch %2d  open-all    device ms: sum (l = 1) %.3f, inverse stages %.3f, gather + forward stages %.3f, finish %.3f; "
+                    "k_open_cosets_sum at this l - at l = 1, the same %d ladders: %+.3f ms" % ((lg, l, batch) + tuple(ms_all) + (2 * n * batch, ms[0] - ms_all[0])))
             lib.kzg_open_cosets_release(setup)
         lib.kzg_open_all_release(single)
         lib.srs_release(h)
