@@ -76,6 +76,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_host_kzg_check_open_cosets", "bbgpu_host_kzg_cells_key_check", "bbgpu_kzg_recover_cells", "bbgpu_host_kzg_recover_cells",
     "bbgpu_kzg_recover_cells_each", "bbgpu_host_kzg_recover_cells_each",
     "bbgpu_g1_ntt", "bbgpu_host_g1_ntt", "bbgpu_g1_recover", "bbgpu_host_g1_recover", "bbgpu_g1_set_stage_mapping",
+    "bbgpu_g1_recover_each", "bbgpu_host_g1_recover_each",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -210,6 +211,15 @@ class KzgRecoverEachReport(C.Structure):
     """bbgpu_kzg_recover_each_report (include/bbgpu.h)"""
     NONE = 0xFFFFFFFFFFFFFFFF  # an entry of first_bad when the polynomial has none
     _fields_ = [("consistent", C.c_uint32), ("first_bad_poly", C.c_uint32), ("first_bad_coeff", C.c_uint64), ("max_missing", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class G1RecoverEachReport(C.Structure):
+    """bbgpu_g1_recover_each_report (include/bbgpu.h)"""
+    NONE = 0xFFFFFFFFFFFFFFFF  # an entry of first_bad when the column has none
+    _fields_ = [("consistent", C.c_uint32), ("first_bad_column", C.c_uint32), ("first_bad_coeff", C.c_uint64), ("max_missing", C.c_uint64)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -814,6 +824,53 @@ class BbGpu:
         self.lib.bbgpu_host_g1_recover.argtypes = [C.POINTER(C.c_uint32), C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, C.POINTER(G1RecoverReport)]
         self._chk(self.lib.bbgpu_host_g1_recover(rp, row.shape[0], _ptr(points), int(n), int(degree_bound), int(batch), _ptr(out), C.byref(rep)))
         return out, rep.as_dict()
+
+    # ---- the same for columns whose row sets differ  (bbgpu_g1_recover_each and the host twin) ----
+    @staticmethod
+    def _g1_recover_each_args(rows, points, n, out):
+        lists = [np.ascontiguousarray(r, dtype=np.uint32).reshape(-1) for r in rows]
+        offsets = np.zeros(len(lists) + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum([r.shape[0] for r in lists])
+        row = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.uint32)]))  # never empty
+        if isinstance(points, np.ndarray):  # one array for the whole call, already in the order of the lists: handed over as it is
+            flat = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+            if flat.shape[0] < int(offsets[-1]):
+                raise ValueError("g1_recover_each: %d points for %d rows" % (flat.shape[0], int(offsets[-1])))
+        else:
+            pts = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 8) for p in points]
+            if len(lists) != len(pts):
+                raise ValueError("g1_recover_each: %d row lists, %d point arrays" % (len(lists), len(pts)))
+            for b, (r, p) in enumerate(zip(lists, pts)):
+                if p.shape[0] < r.shape[0]:  # the library would read past the end
+                    raise ValueError("g1_recover_each: column %d: %d points for %d rows" % (b, p.shape[0], r.shape[0]))
+            flat = np.ascontiguousarray(np.concatenate([p[:r.shape[0]] for r, p in zip(lists, pts)] + [np.zeros((1, 8), dtype=np.uint64)]))
+        batch = len(lists)
+        if out is None:
+            out = np.zeros((max(batch, 1), max(int(n), 1), 8), dtype=np.uint64)
+        return offsets, row, flat, batch, out
+
+    def g1_recover_each(self, rows, points, n, degree_bound, stream=None, out=None):
+        """bbgpu_g1_recover_each: len(rows) columns of n points, each a codeword of degree < degree_bound, column b from ITS OWN listed rows (rows[b]:
+        distinct indices below n, any order; points[b] (count_b, 8): listed row t, on the host -- or ONE array that holds them all in that order, which is
+        not copied) -> ((batch, n, 8) all n points of every column -- `out` when given --, the report as a dict, (batch,) uint64 first_bad,
+        G1RecoverEachReport.NONE where a column has none)."""
+        offsets, row, flat, batch, out = self._g1_recover_each_args(rows, points, n, out)
+        rep, first_bad = G1RecoverEachReport(), np.zeros(max(batch, 1), dtype=np.uint64)
+        u32p = C.POINTER(C.c_uint32)
+        self.lib.bbgpu_g1_recover_each.argtypes = [u32p, u32p, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, u64p, C.POINTER(G1RecoverEachReport), C.c_void_p]
+        self._chk(self.lib.bbgpu_g1_recover_each(offsets.ctypes.data_as(u32p), row.ctypes.data_as(u32p), _ptr(flat), int(n), int(degree_bound), batch, _ptr(out),
+                                                 _ptr(first_bad), C.byref(rep), stream or 0))
+        return out, rep.as_dict(), first_bad
+
+    def host_g1_recover_each(self, rows, points, n, degree_bound, out=None):
+        """bbgpu_host_g1_recover_each: the same on the host"""
+        offsets, row, flat, batch, out = self._g1_recover_each_args(rows, points, n, out)
+        rep, first_bad = G1RecoverEachReport(), np.zeros(max(batch, 1), dtype=np.uint64)
+        u32p = C.POINTER(C.c_uint32)
+        self.lib.bbgpu_host_g1_recover_each.argtypes = [u32p, u32p, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p, u64p, C.POINTER(G1RecoverEachReport)]
+        self._chk(self.lib.bbgpu_host_g1_recover_each(offsets.ctypes.data_as(u32p), row.ctypes.data_as(u32p), _ptr(flat), int(n), int(degree_bound), batch,
+                                                      _ptr(out), _ptr(first_bad), C.byref(rep)))
+        return out, rep.as_dict(), first_bad
 
     def g1_set_stage_mapping(self, mapping):
         """bbgpu_g1_set_stage_mapping: 0 the library's choice of stage kernel for g1_ntt and g1_recover, 1 k_lagrange_stage and 2 k_g1_stage_cols for every

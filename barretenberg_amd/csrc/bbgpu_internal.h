@@ -285,16 +285,23 @@ int kzg_recover_each_gather(const uint64_t* d_tree, const uint32_t* d_mu, int ba
                             uint64_t* d_zcin, hipStream_t st);
 
 // g1_recover.hip: the device parts of bbgpu_g1_ntt and bbgpu_g1_recover.  Columns of n = 2^log2n scratch points (128 bytes each), column b at slot b n;
-// batch x n <= 2^20.  Nothing here synchronises.
+// batch x n <= 2^20.  Nothing here synchronises.  The last argument of load, scale, scalars and verdict is what bbgpu_g1_recover_each adds -- every column
+// with its own rows --; its default is the same-set form.  d_off: the batch + 1 row offsets: column b's points start at point d_off[b] of d_in, d_slot_of and
+// d_tab hold batch x n entries, and the verdict takes count_b = d_off[b + 1] - d_off[b].  per_column: d_tab holds batch x n entries.  cols: z, z' and the
+// tables kz, kq hold cols x n entries (0: n).
 int g1_cols_load(const uint32_t* d_in, size_t count, const uint32_t* d_slot_of, const uint64_t* d_tab, const uint64_t* k_plain, uint32_t* d_scratch, int log2n,
-                 int batch, hipStream_t st);
+                 int batch, hipStream_t st, const uint32_t* d_off = nullptr);
 int g1_cols_transform(uint32_t* d_scratch, int log2n, int batch, const uint32_t root_m261[9], hipStream_t st);
 int g1_cols_transform_rows(uint32_t* d_scratch, int log2n, int batch, const uint32_t root_m261[9], hipStream_t st); // the bench's comparison only
-int g1_cols_scale(const uint32_t* d_src, uint32_t* d_dst, const uint64_t* d_tab, int log2n, int batch, hipStream_t st);
+int g1_cols_scale(const uint32_t* d_src, uint32_t* d_dst, const uint64_t* d_tab, int log2n, int batch, hipStream_t st, bool per_column = false);
 int g1_cols_scalars(const uint64_t* d_z, const uint64_t* d_zci, uint64_t* d_tabs, int log2n, const uint32_t ninv_plain[9], const uint32_t g_m261[9],
-                    const uint32_t ginv_m261[9], hipStream_t st);
-int g1_cols_verdict(const uint32_t* d_scratch, int log2n, int batch, size_t degree_bound, size_t present, RecoverFindings* d_find, hipStream_t st);
+                    const uint32_t ginv_m261[9], hipStream_t st, int cols = 0);
+int g1_cols_verdict(const uint32_t* d_scratch, int log2n, int batch, size_t degree_bound, size_t present, RecoverFindings* d_find, hipStream_t st,
+                    const uint32_t* d_off = nullptr);
 int g1_cols_finish(const uint32_t* d_scratch, uint32_t* d_out, int log2n, int batch, hipStream_t st);
+// z and z' x 2^-5 of EVERY column, batch x n x 4 words each, in the forms of kzg_recover_vanish.  d_moff: batch + 1 offsets into d_missing, column b's
+// missing rows ascending at d_missing[d_moff[b] .. d_moff[b + 1]), fewer than n of them; d_roots: n x 9 words of workspace
+int g1_cols_vanish(const uint32_t* d_moff, const uint32_t* d_missing, int log2n, int batch, uint32_t* d_roots, uint64_t* d_z, uint64_t* d_zc, hipStream_t st);
 
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);

@@ -4383,6 +4383,111 @@ int bbgpu_g1_recover(const uint32_t* row, size_t count, const uint64_t* points, 
     return BBGPU_OK;
 }
 
+/* ---- the same for columns whose row sets differ (host_g1_recover.hpp, g1_recover.hip) ---- */
+int bbgpu_host_g1_recover_each(const uint32_t* row_offsets, const uint32_t* row, const uint64_t* points, size_t n, size_t degree_bound, int batch,
+                               uint64_t* points_out, uint64_t* first_bad_out, bbgpu_g1_recover_each_report* report)
+{
+    host::KzgRecoverEachShape S;
+    char why[320];
+    int rc = host::g1_recover_each_verdict("host g1_recover_each", row_offsets, row, points, n, degree_bound, batch, points_out, report, &S, why, sizeof why);
+    if (rc == BBGPU_OK) rc = host::g1_recover_each_host(S, row_offsets, row, points, degree_bound, batch, points_out, first_bad_out, report, why, sizeof why);
+    if (rc) set_error("%s", why);
+    return rc;
+}
+
+int bbgpu_g1_recover_each(const uint32_t* row_offsets, const uint32_t* row, const uint64_t* points, size_t n, size_t degree_bound, int batch,
+                          uint64_t* points_out, uint64_t* first_bad_out, bbgpu_g1_recover_each_report* report, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    host::KzgRecoverEachShape S;
+    char why[320];
+    if (int rc = host::g1_recover_each_verdict("g1_recover_each", row_offsets, row, points, n, degree_bound, batch, points_out, report, &S, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (int rc = ensure_init()) return rc;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const size_t B = (size_t)batch, total = B * n, listed = S.total, gone = total - listed;
+    const int lg = S.log2n;
+    StageEvents<7> ev; // the stage boundaries of bbgpu_last_timing
+    if (int rc = ev.create(ctx().timing != 0)) return rc;
+    // per column the place of every row in its list, the row offsets, the offsets of the missing rows and the missing rows of all columns, in one array |
+    // z, z' and the tables kz and kq per column, kg and kgi, and the roots | the points | the findings | the two scratches (the first one takes the
+    // affine results at the end)
+    DevBuf lists, zt, in, find, scratch;
+    const size_t list_words = total + 2 * (B + 1) + gone;
+    HIPCHK(dev_malloc(&lists.p, list_words * 4));
+    HIPCHK(dev_malloc(&zt.p, (4 * B + 2) * n * 32 + n * sizeof(Limbs9)));
+    HIPCHK(dev_malloc(&in.p, listed * 64));
+    HIPCHK(dev_malloc(&find.p, B * sizeof(RecoverFindings)));
+    HIPCHK(dev_malloc(&scratch.p, 2 * total * 128));
+    uint32_t *d_slot_of = lists.as<uint32_t>(), *d_off = d_slot_of + total, *d_moff = d_off + (B + 1), *d_missing = d_moff + (B + 1);
+    uint64_t *d_z = zt.as<uint64_t>(), *d_zc = d_z + 4 * total, *d_tabs = d_zc + 4 * total;
+    const uint64_t *d_kz = d_tabs, *d_kg = d_kz + 4 * total, *d_kq = d_kg + 4 * n, *d_kgi = d_kq + 4 * total;
+    uint32_t* d_roots = reinterpret_cast<uint32_t*>(d_tabs + 4 * (2 * total + 2 * n));
+    uint32_t *A = scratch.as<uint32_t>(), *Bs = A + total * 32;
+    std::vector<uint32_t> all(list_words, ~0u);
+    size_t at = 0; // missing rows so far
+    for (size_t b = 0; b < B; b++) {
+        const uint32_t first = row_offsets[b], count = row_offsets[b + 1] - first;
+        for (uint32_t t = 0; t < count; t++) all[b * n + row[first + t]] = t;
+        all[total + b] = first;
+        all[total + (B + 1) + b] = (uint32_t)at;
+        std::copy(S.missing[b].begin(), S.missing[b].end(), all.begin() + (ptrdiff_t)(total + 2 * (B + 1) + at));
+        at += S.missing[b].size();
+    }
+    all[total + B] = row_offsets[B];
+    all[total + (B + 1) + B] = (uint32_t)at; // == gone
+    RecoverFound F(batch);
+    if (int rc = host_to_device(lists.p, all.data(), list_words * 4, st)) return rc;
+    if (int rc = F.begin(find.p, st)) return rc;
+    if (int rc = host_to_device(in.p, points, listed * 64, st)) return rc;
+    host::Fr winv, ninv;
+    host::srs_lagrange_constants(lg, &winv, &ninv);
+    const host::Fr w = host::fr_root_of_unity(lg), g = host::fr_from_limbs(FrHostP::GEN5);
+    if (int rc = ev.mark(0, st)) return rc;
+    if (int rc = g1_cols_vanish(d_moff, d_missing, lg, batch, d_roots, d_z, d_zc, st)) return rc;
+    if (int rc = ev.mark(1, st)) return rc;
+    if (int rc = bbgpu_fr_batch_invert_device(d_zc, total, hip_stream)) return rc; // z' is never zero: g^n != 1
+    if (int rc = g1_cols_scalars(d_z, d_zc, d_tabs, lg, host::limbs_m256(ninv).d, host::limbs_m261(g).d, host::limbs_m261(host::fr_inv(g)).d, st, batch)) return rc;
+    if (int rc = ev.mark(2, st)) return rc;
+    if (int rc = g1_cols_load(in.as<uint32_t>(), 0, d_slot_of, d_kz, nullptr, A, lg, batch, st, d_off)) return rc;
+    if (int rc = g1_transform_dispatch(A, lg, batch, winv, st)) return rc;
+    if (int rc = ev.mark(3, st)) return rc;
+    if (int rc = g1_cols_scale(A, Bs, d_kg, lg, batch, st)) return rc;
+    if (int rc = g1_transform_dispatch(Bs, lg, batch, w, st)) return rc;
+    if (int rc = g1_cols_scale(Bs, A, d_kq, lg, batch, st, true)) return rc;
+    if (int rc = g1_transform_dispatch(A, lg, batch, winv, st)) return rc;
+    if (int rc = g1_cols_scale(A, Bs, d_kgi, lg, batch, st)) return rc;
+    if (int rc = g1_cols_verdict(Bs, lg, batch, degree_bound, 0, find.as<RecoverFindings>(), st, d_off)) return rc;
+    if (int rc = ev.mark(4, st)) return rc;
+    if (int rc = g1_transform_dispatch(Bs, lg, batch, w, st)) return rc;
+    if (int rc = ev.mark(6, st)) return rc;
+    if (int rc = g1_cols_finish(Bs, A, lg, batch, st)) return rc;
+    if (int rc = ev.mark(5, st)) return rc;
+    if (int rc = F.end(find.p, st)) return rc;
+    // the verdict into locals first: nothing of the caller's host memory is written before the last copy has succeeded
+    bbgpu_g1_recover_each_report rep;
+    if (int rc = host::g1_recover_each_report_of("g1_recover_each", F.first_bad.data(), F.first_bug.data(), batch, S.max_missing, nullptr, &rep, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (int rc = device_to_host_sync(points_out, A, total * 64, st)) return rc;
+    *report = rep;
+    if (first_bad_out) std::copy(F.first_bad.begin(), F.first_bad.end(), first_bad_out);
+    if (ev.on) { // bbgpu_last_timing: 0 the roots and the vanishing values, 1 load and IFFT, 2 shift, FFT, divide, IFFT, unshift and verdict, 3 the last FFT and
+                 // the finish, 4 the finish alone (a part of 3)
+        ctx().last.count = 5;
+        if (int rc = ev.ms(6, 5, &ctx().last.ms[4])) return rc;
+        if (int rc = ev.ms(0, 1, &ctx().last.ms[0])) return rc;
+        if (int rc = ev.ms(2, 3, &ctx().last.ms[1])) return rc;
+        if (int rc = ev.ms(3, 4, &ctx().last.ms[2])) return rc;
+        if (int rc = ev.ms(4, 5, &ctx().last.ms[3])) return rc;
+    }
+    return BBGPU_OK;
+}
+
 int bbgpu_srs_has_window_tables(int srs_handle)
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);

@@ -5,7 +5,8 @@
 //   E_i = z_i P_i on the present rows, infinity on the missing ones;  P = IFFT(E);  Q = FFT(g^j P_j);  Q_i <- Q_i / z'_i;  D' = IFFT(Q);  D_j = g^-j D'_j
 // and the points are a codeword of degree < d iff coefficients [d, count) of D are at infinity.  z and z' by the direct products of
 // kzg_recover_vanishing_host, one inversion per z'.  Deliberately NOT the split ladder of g1_ladder.hpp and no batch inversion, so that device and twin
-// check each other; affine results are unique and canonical, so they agree bit for bit.  Product code, no oracle/; no HIP call, no lock.
+// check each other; affine results are unique and canonical, so they agree bit for bit.  bbgpu_g1_recover_each is the same decoder with a row list, and so a
+// z and a z', per column: its verdict and twin are at the end, on the one-column routine of the same-set twin.  Product code, no oracle/; no HIP call, no lock.
 #pragma once
 #include <stdio.h>
 
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "host_kzg_recover_cells.hpp"
+#include "host_kzg_recover_each.hpp"
 #include "host_random_check.hpp"
 #include "host_srs_lagrange.hpp"
 
@@ -245,15 +247,12 @@ static inline void g1_recover_column(const KzgRecoverShape& S, const std::vector
         for (size_t i = lo; i < hi; i++) g1_to_words(b[i], out + 8 * i);
     });
 }
-// The twin behind its verdict.  Short columns are dealt to threads whole (their transforms are too small to split), long ones run one after another.
-static inline int g1_recover_host(const KzgRecoverShape& S, const uint32_t* row, size_t count, const uint64_t* points, size_t degree_bound, int batch,
-                                  uint64_t* points_out, bbgpu_g1_recover_report* report, char* why, size_t why_len)
+// g^j and g^-j for j < n: the coset shift and the unshift of both twins
+static inline void g1_recover_shift_powers(size_t n, std::vector<Fr>& gp, std::vector<Fr>& gpi)
 {
-    std::vector<Fr> z, zc_inv;
-    kzg_recover_vanishing_host(S, z, zc_inv);
-    const size_t n = S.n;
     const Fr g = fr_from_limbs(FrHostP::GEN5), ginv = fr_inv(g);
-    std::vector<Fr> gp(n), gpi(n);
+    gp.resize(n);
+    gpi.resize(n);
     Fr p = fr_one(), q = fr_one();
     for (size_t j = 0; j < n; j++) {
         gp[j] = p;
@@ -261,6 +260,16 @@ static inline int g1_recover_host(const KzgRecoverShape& S, const uint32_t* row,
         p = fr_mul(p, g);
         q = fr_mul(q, ginv);
     }
+}
+// The twin behind its verdict.  Short columns are dealt to threads whole (their transforms are too small to split), long ones run one after another.
+static inline int g1_recover_host(const KzgRecoverShape& S, const uint32_t* row, size_t count, const uint64_t* points, size_t degree_bound, int batch,
+                                  uint64_t* points_out, bbgpu_g1_recover_report* report, char* why, size_t why_len)
+{
+    std::vector<Fr> z, zc_inv;
+    kzg_recover_vanishing_host(S, z, zc_inv);
+    const size_t n = S.n;
+    std::vector<Fr> gp, gpi;
+    g1_recover_shift_powers(n, gp, gpi);
     std::vector<uint64_t> first_bad((size_t)batch, ~0ull), first_bug((size_t)batch, ~0ull);
     auto columns = [&](size_t lo, size_t hi) {
         for (size_t b = lo; b < hi; b++)
@@ -269,6 +278,147 @@ static inline int g1_recover_host(const KzgRecoverShape& S, const uint32_t* row,
     if (n < 32) fallback_parallel((size_t)batch, 1, columns);
     else columns(0, (size_t)batch);
     return g1_recover_report_of("host g1_recover", first_bad.data(), first_bug.data(), batch, S.mu, report, why, why_len);
+}
+
+// ---- bbgpu_g1_recover_each: every column with ITS OWN rows ------------------------------------------------------------------------------------------------
+constexpr int G1_RECOVER_EACH_MAX_LOG2 = 12; // BBGPU_G1_RECOVER_EACH_MAX_ROWS: the vanishing values cost sum_b 2 mu_b n products (include/bbgpu.h)
+static_assert(BBGPU_G1_RECOVER_EACH_MAX_ROWS == 1u << G1_RECOVER_EACH_MAX_LOG2, "the cap of include/bbgpu.h");
+
+// The verdict, as kzg_recover_each_verdict's at coset 1: sizes (BBGPU_ERR_SIZE; the counts need the offsets, so a null or malformed offset array is found
+// on the way and reported as BBGPU_ERR_ARG), then pointers, the row lists and the points (BBGPU_ERR_ARG); `why` names the first offender by column and
+// position.  On BBGPU_OK *S holds the shape (l = 1, m = n) and every column's missing rows, ascending.
+static inline int g1_recover_each_verdict(const char* what, const uint32_t* row_offsets, const uint32_t* row, const uint64_t* points, size_t n,
+                                          size_t degree_bound, int batch, const void* points_out, const void* report, KzgRecoverEachShape* S, char* why,
+                                          size_t why_len)
+{
+    const int lg = g1_recover_log2(n);
+    if (lg < 0 || lg > G1_RECOVER_EACH_MAX_LOG2) {
+        snprintf(why, why_len, "%s: n = %zu must be a power of two between 2 and 2^%d", what, n, G1_RECOVER_EACH_MAX_LOG2);
+        return BBGPU_ERR_SIZE;
+    }
+    if (degree_bound < 1 || degree_bound > n) {
+        snprintf(why, why_len, "%s: degree bound %zu outside 1 .. n = %zu", what, degree_bound, n);
+        return BBGPU_ERR_SIZE;
+    }
+    if (batch < 1 || (size_t)batch > G1_RECOVER_MAX_POINTS / n) {
+        snprintf(why, why_len, "%s: batch %d below 1, or batch x n above 2^20", what, batch);
+        return BBGPU_ERR_SIZE;
+    }
+    if (!row_offsets) {
+        snprintf(why, why_len, "%s: null row offsets", what);
+        return BBGPU_ERR_ARG;
+    }
+    if (row_offsets[0] != 0) {
+        snprintf(why, why_len, "%s: row_offsets[0] = %u is not 0", what, row_offsets[0]);
+        return BBGPU_ERR_ARG;
+    }
+    for (int b = 0; b < batch; b++)
+        if (row_offsets[b + 1] < row_offsets[b]) {
+            snprintf(why, why_len, "%s: column %d: row_offsets[%d] = %u is below row_offsets[%d] = %u", what, b, b + 1, row_offsets[b + 1], b, row_offsets[b]);
+            return BBGPU_ERR_ARG;
+        }
+    for (int b = 0; b < batch; b++) {
+        const size_t count = row_offsets[b + 1] - row_offsets[b];
+        if (count > n || count < degree_bound) {
+            snprintf(why, why_len, "%s: column %d lists %zu rows: at most n = %zu, and no fewer than the degree bound %zu", what, b, count, n, degree_bound);
+            return BBGPU_ERR_SIZE;
+        }
+    }
+    if (!row || !points || !points_out || !report) {
+        snprintf(why, why_len, "%s: null row / points / output / report", what);
+        return BBGPU_ERR_ARG;
+    }
+    S->missing.assign((size_t)batch, std::vector<uint32_t>());
+    S->max_missing = 0;
+    std::vector<uint8_t> listed(n);
+    for (int b = 0; b < batch; b++) {
+        const uint32_t* r = row + row_offsets[b];
+        const size_t count = row_offsets[b + 1] - row_offsets[b];
+        std::fill(listed.begin(), listed.end(), (uint8_t)0);
+        for (size_t t = 0; t < count; t++) {
+            if (r[t] >= n) {
+                snprintf(why, why_len, "%s: column %d: row[%zu] = %u (position %zu of its list) is not below n = %zu", what, b, row_offsets[b] + t, r[t], t, n);
+                return BBGPU_ERR_ARG;
+            }
+            if (listed[r[t]]) {
+                snprintf(why, why_len, "%s: column %d: row[%zu] = %u (position %zu of its list) is listed twice", what, b, row_offsets[b] + t, r[t], t);
+                return BBGPU_ERR_ARG;
+            }
+            listed[r[t]] = 1;
+        }
+        std::vector<uint32_t>& K = S->missing[(size_t)b];
+        K.reserve(n - count);
+        for (size_t k = 0; k < n; k++)
+            if (!listed[k]) K.push_back((uint32_t)k);
+        S->max_missing = std::max(S->max_missing, K.size());
+    }
+    const size_t total = row_offsets[batch], bad = g1_recover_first_bad_point(points, total);
+    if (bad != total) {
+        int b = 0;
+        while (row_offsets[b + 1] <= bad) b++; // the column that owns point `bad`: empty columns cannot (count_b >= degree_bound >= 1 anyway)
+        snprintf(why, why_len, "%s: the point at position %zu of column %d (row %u) is not on the curve or not canonical", what, bad - row_offsets[b], b, row[bad]);
+        return BBGPU_ERR_ARG;
+    }
+    S->log2n = lg;
+    S->log2l = 0;
+    S->n = n;
+    S->l = 1;
+    S->m = n;
+    S->total = total;
+    return BBGPU_OK;
+}
+// per column: the smallest index in [d, count_b) and the smallest in [count_b, n) whose coefficient is not at infinity, ~0 for none -> the report and
+// first_bad_out (null or batch); the second kind is BBGPU_ERR_HIP with its text, nothing written
+static inline int g1_recover_each_report_of(const char* what, const uint64_t* first_bad, const uint64_t* first_bug, int batch, size_t max_missing,
+                                            uint64_t* first_bad_out, bbgpu_g1_recover_each_report* out, char* why, size_t why_len)
+{
+    for (int b = 0; b < batch; b++)
+        if (first_bug[b] != ~0ull) {
+            snprintf(why, why_len, "%s: coefficient %llu of column %d is not at infinity although the construction makes it so: a bug of this library", what,
+                     (unsigned long long)first_bug[b], b);
+            return BBGPU_ERR_HIP;
+        }
+    out->consistent = 1;
+    out->first_bad_column = 0;
+    out->first_bad_coeff = 0;
+    out->max_missing = max_missing;
+    for (int b = batch - 1; b >= 0; b--) {
+        if (first_bad_out) first_bad_out[b] = first_bad[b];
+        if (first_bad[b] != ~0ull) {
+            out->consistent = 0;
+            out->first_bad_column = (uint32_t)b;
+            out->first_bad_coeff = first_bad[b];
+        }
+    }
+    return BBGPU_OK;
+}
+// The twin behind its verdict: g1_recover_column once per column with that column's rows, z and z' by direct products over ITS missing rows.  Short
+// columns are dealt to threads whole, as in g1_recover_host.
+static inline int g1_recover_each_host(const KzgRecoverEachShape& S, const uint32_t* row_offsets, const uint32_t* row, const uint64_t* points, size_t degree_bound,
+                                       int batch, uint64_t* points_out, uint64_t* first_bad_out, bbgpu_g1_recover_each_report* report, char* why, size_t why_len)
+{
+    const size_t n = S.n;
+    std::vector<Fr> gp, gpi;
+    g1_recover_shift_powers(n, gp, gpi);
+    std::vector<uint64_t> first_bad((size_t)batch, ~0ull), first_bug((size_t)batch, ~0ull);
+    auto columns = [&](size_t lo, size_t hi) {
+        KzgRecoverShape P; // the shape of one column, as the same-set twin sees it
+        P.log2n = S.log2n;
+        P.log2l = 0;
+        P.n = P.m = n;
+        P.l = 1;
+        std::vector<Fr> z, zc_inv;
+        for (size_t b = lo; b < hi; b++) {
+            P.missing = S.missing[b];
+            P.mu = P.missing.size();
+            kzg_recover_vanishing_host(P, z, zc_inv);
+            g1_recover_column(P, z, zc_inv, gp, gpi, row + row_offsets[b], row_offsets[b + 1] - row_offsets[b], points + (size_t)row_offsets[b] * 8, degree_bound,
+                              points_out + b * n * 8, &first_bad[b], &first_bug[b]);
+        }
+    };
+    if (n < 32) fallback_parallel((size_t)batch, 1, columns);
+    else columns(0, (size_t)batch);
+    return g1_recover_each_report_of("host g1_recover_each", first_bad.data(), first_bug.data(), batch, S.max_missing, first_bad_out, report, why, why_len);
 }
 
 } // namespace host

@@ -1340,8 +1340,8 @@ int bbgpu_host_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32
  * coefficient index not at infinity.  A coefficient in [count, n) that is not at infinity is BBGPU_ERR_HIP with a text of its own: no input can cause it.
  * Refused before a device is bound, outputs untouched -- BBGPU_ERR_SIZE: n not a power of two, n < 2, n > 2^16, degree_bound outside 1..n, count <
  * degree_bound, count > n, batch < 1, batch * n > 2^20; BBGPU_ERR_ARG: a null pointer, a row index >= n, a row listed twice, a point off the curve or not
- * canonical -- the message names the first offender.  Not here: per-column row sets, n > 2^16 (the product tree of kzg_recover_each.hip for the vanishing
- * values), device-resident inputs and outputs, G2.
+ * canonical -- the message names the first offender.  Per-column row sets are bbgpu_g1_recover_each below (n <= 2^12).  Not here: n > 2^16 (the product
+ * tree of kzg_recover_each.hip for the vanishing values), device-resident inputs and outputs, G2.
  * The kernels (csrc/g1_recover.hip).  A stage launch that does not fill the chip costs about the 0.9 ms one wave needs for its ladder, so a small decode
  * costs its count of ladder-bearing launches, not its count of points: 4 + 4 log2 n.
  *   k_g1_stage_cols  (n <= 64; from n = 128 on the drivers launch k_lagrange_stage, see the cost below) the butterfly of csrc/g1_stage.hpp (butterfly_slots<3>, unchanged) with (position, column, group) flattened into one lane index,
@@ -1360,7 +1360,8 @@ int bbgpu_host_kzg_recover_cells_each(const uint32_t* cell_offsets, const uint32
  *                    the batch x n Z-coordinates was NOT built -- see the cost of the finish below
  * Resources (hipcc -Rpass-analysis=kernel-resource-usage, VGPRs / AGPRs / LDS bytes / waves per SIMD): k_g1_stage_cols
  * 231 / 0 / 0 / 2, k_g1_load 250 / 0 / 0 / 2, k_g1_scale 229 / 0 / 0 / 2 (the ladder's table fills the register file, as in k_lagrange_stage: 231), k_g1_scalars
- * 50 / 0 / 0 / 8, k_g1_verdict 16 / 0 / 32 / 8, k_g1_finish 75 / 0 / 0 / 6; no scratch and no spill in any.
+ * 60 / 0 / 0 / 8 (50 before it took the per-column rows of bbgpu_g1_recover_each), k_g1_verdict 16 / 0 / 32 / 8, k_g1_finish 75 / 0 / 0 / 6; no scratch and
+ * no spill in any.
  * Both entries run on context 0 under the library mutex.  A warm bbgpu_g1_recover at (n, d, missing, batch) = (8, 4, 4, 3) passes five allocations (the
  * lists; z, z', the tables and the roots; the points; the findings; the two scratches), three uploads (the lists, the findings' start, the points), two
  * read-backs (the findings, the points) and fifteen launch checks (roots + vanish; the inversion's two scans and its product; the tables; the load; four
@@ -1409,6 +1410,89 @@ int bbgpu_host_g1_recover(const uint32_t* row, size_t count, const uint64_t* poi
  * (batch <= 65535, else BBGPU_ERR_SIZE from the entries), 2 k_g1_stage_cols for every shape -- for the comparison of tools/g1_recover_bench.py and the
  * tests; results are bit-identical.  BBGPU_ERR_ARG for any other value */
 int bbgpu_g1_set_stage_mapping(int mapping);
+
+/* ---- recover G1 codewords whose row sets differ  (one call for all columns: per-column vanishing values by direct pair products) ------
+ * bbgpu_g1_recover above wants the same rows of every column.  A sampler that draws cells at random holds the proof pi_(r, c) for a DIFFERENT set of rows
+ * r in every column c, and had to make one bbgpu_g1_recover call per distinct set -- each at the 4 + 4 log2 n ladder-bearing launches a call costs
+ * whatever its batch.  bbgpu_g1_recover_each takes per-column row lists, as bbgpu_kzg_recover_cells_each does on the field side: column b lists count_b =
+ * row_offsets[b + 1] - row_offsets[b] distinct rows with count_b >= d and misses the mu_b = n - count_b rows K_b; `points` holds row_offsets[batch] points
+ * in the order of `row`.  Everything the block above fixes holds here: the point format, infinity as an ordinary input and output, complete additions,
+ * the curve and canonicity test on the host before a device is bound, "a finding, not an error" for an inconsistent column, BBGPU_ERR_HIP with a text of
+ * its own for a coefficient in [count_b, n) that is not at infinity, context 0 under the library mutex, the return after the last copy.  Column b has
+ *   z_(b,i) = prod_{k in K_b} (rho^i - rho^k),   z'_(b,i) = prod_{k in K_b} (g rho^i - rho^k)
+ * and the per-column decode is the one stated above with these; mu_b = 0 is legal and gives z = z' = 1.  first_bad_out, if given, receives per column the
+ * smallest index in [d, count_b) whose coefficient is not at infinity, UINT64_MAX for none; the report names the first such column.  The device entry
+ * writes report and first_bad_out only after its last copy has succeeded.
+ * Refused before a device is bound, outputs untouched -- BBGPU_ERR_SIZE: n not a power of two, n < 2, n > BBGPU_G1_RECOVER_EACH_MAX_ROWS = 2^12,
+ * degree_bound outside 1..n, batch < 1, batch * n > 2^20, for some b count_b < degree_bound or count_b > n; BBGPU_ERR_ARG: a null pointer (first_bad_out
+ * may be NULL), row_offsets[0] != 0 or offsets that decrease, a row index >= n, a row listed twice within one column, a point off the curve or not
+ * canonical -- bbgpu_last_error() names the first offender by column and position.
+ * Why the cap is 2^12: the vanishing values are computed by DIRECT pair products, sum_b 2 mu_b n field products.  At n <= 2^12 and batch * n <= 2^20 that
+ * is at most 2^32 products, about 29 ms at the 150 Gmul/s of csrc/fe_mont_gfx950.h, beside the same call's ladders -- expected to cost over a second when
+ * the cap was chosen, 363 ms when measured (the cost below): the products are a small part either way.  At n = 2^16 they would be 2^36 at the same batch x n
+ * (0.46 s), comparable with the ladders; that size needs the product tree of csrc/kzg_recover_each.hip.  Not here: n > 2^12 (the product tree), device-resident inputs
+ * and outputs, G2.
+ * The kernels (csrc/g1_recover.hip).  The transforms, the ladder passes, the verdict and the finish of bbgpu_g1_recover already run over a flattened
+ * (position, column) index; what was per call and is per column here are the vanishing values and the per-index scalars:
+ *   k_g1_roots       rho^k for every k < n, once per call: a table of n x 9 words (limb-major, Montgomery-261), square-and-multiply as k_recover_roots
+ *   k_g1_vanish_cols the one compute-bound kernel of this entry: one lane per flattened (column, index) pair, index fastest; z_(b,i) as a Montgomery-261
+ *                    multiplier and z'_(b,i) x 2^-5 in the memory format, exactly the forms kzg_recover_vanish writes, so that the batch inversion (over
+ *                    batch x n elements) and the scalar tables follow unchanged.  A workgroup of 256 lanes stages the roots of missing rows in LDS tiles of
+ *                    256 (9216 bytes, as k_recover_vanish); the missing lists go up in CSR form (offsets plus ascending rows).  For n >= 256 the workgroup
+ *                    lies inside one column and walks that column's list tile by tile; for n < 256 it spans 256 / n whole columns, whose lists lie side by
+ *                    side in the CSR array and together hold at most 256 roots (mu_b <= n - 1): one tile, of which every lane walks its own column's
+ *                    sub-range.  Both products of a pair share the staged root, two accumulators per lane.  Columns in one wave may have different mu_b:
+ *                    the tile loop and its two barriers depend on the workgroup alone, a lane's own range is a predicated inner loop, lanes past the end
+ *                    of the grid have an empty range and write nothing -- no lane returns early
+ *   per-column forms of the kernels above through added arguments whose zero or null value is bbgpu_g1_recover's behaviour: k_g1_scalars writes n^-1
+ *                    z_(b,i) and n^-1 / z'_(b,i) as batch x n tables (g^j and g^-j stay n); k_g1_load takes slot_of per column (batch x n), the start of
+ *                    the column's points (row_offsets[b] in place of b count) and the per-column table; k_g1_scale takes a table stride (the division
+ *                    reads its column's row, shift and unshift stay shared); k_g1_verdict takes count_b from the offsets.  Stage kernels, dispatch and
+ *                    k_g1_finish are unchanged, and bbgpu_g1_recover and bbgpu_g1_ntt are bit-identical with the same funnel counts
+ * Resources (hipcc -Rpass-analysis=kernel-resource-usage, VGPRs / AGPRs / LDS bytes / waves per SIMD): k_g1_roots 39 / 0 / 0 / 8, k_g1_vanish_cols 82 / 0 /
+ * 9216 / 5; the kernels that took arguments: k_g1_load 250 / 0 / 0 / 2, k_g1_scale 229 / 0 / 0 / 2 (both as before: the added index arithmetic is dead before
+ * the ladder's table is live), k_g1_scalars 60 / 0 / 0 / 8 (50 before), k_g1_verdict 16 / 0 / 32 / 8; k_g1_stage_cols 231 and k_g1_finish 75 are untouched; no
+ * scratch and no spill in any.
+ * A warm call at (n, d, batch) = (8, 4, 3) with mu = 4, 3, 1 passes five allocations (the lists; z, z', the tables and the roots; the points; the
+ * findings; the two scratches), three uploads (the lists -- slot_of, the row offsets and the CSR of the missing rows in one array --, the findings' start,
+ * the points), two read-backs (the findings, the points) and fifteen launch checks (k_g1_roots with k_g1_vanish_cols; the inversion's two scans and its
+ * product; the tables; the load; four transforms; three scale passes; the verdict; the finish).  Every site failed once through bbgpu_fault_inject returns
+ * BBGPU_ERR_HIP, leaves nothing the call allocated live, and the next call is bit-exact (tests/test_gpu_g1_recover_each.py).  With bbgpu_set_timing(1),
+ * bbgpu_last_timing(): index 0 the roots and k_g1_vanish_cols, 1 the load and the first inverse transform, 2 shift through verdict, 3 the last transform
+ * and the finish, 4 the finish alone (a part of 3).
+ * Cost on one MI355X (tools/g1_recover_each_bench.py, profiles/g1_recover_each.txt; wall ms per call, copies across the link included, one process,
+ * medians of 9 alternating pairs; a median counts as lower only if it is lower by more than the full range of either leg; half the rows missing, d = n / 2).
+ * (a) ONE call over `batch` columns with a different random half missing in each, against one bbgpu_g1_recover call per distinct set in the same process,
+ * (n, batch): (8, 65), 45 distinct sets, 14.1 against 609.3 ms, 43 times; (64, 65), 65 sets, 27.8 against 1794.9, 65 times; (512, 65), 65 sets, 38.5 against
+ * 2389.5, 62 times; (4096, 16), 16 sets, 54.0 against 791.4, 14.7 times -- every gap far beyond the range, and the ratio near the number of distinct sets as
+ * launch counting predicts.  (b) The SAME set for all columns (every other row), this entry / bbgpu_g1_recover: (8, 65) 13.22 / 13.07 and (64, 65) 26.98 /
+ * 26.95, both within the range; (512, 65) 37.64 / 37.08 and (4096, 16) 52.14 / 49.88, the same-set entry lower by more than the range: the price of the
+ * per-column lists and tables, most of it the vanishing values -- 2.19 ms of device time at (4096, 16), where 65536 lanes each walk 2048 roots one after the
+ * other and the same-set kernel spreads ONE column's n values over a wave per value.  (c) bbgpu_last_timing index 0 at (4096, 256) with a different random
+ * half missing per column: 27.2 ms for sum_b 2 mu_b n = 2^32 products, 0.95 times their 28.6 ms at 150 Gmul/s; nothing was tuned to that ratio.  The same
+ * call's ladder passes and transforms took 363 ms of device time (load + IFFT 92.3, shift .. verdict 190.9, FFT + finish 80.0): the direct products are 7 %
+ * of the call at the largest shape the entry takes.  NOT timed: the host twin, the host's part of a call on its own (the curve test, the lists of missing
+ * rows), the batch inversion over batch x n values on its own, columns that miss few rows beside columns that miss many in one call, n < 4096 at batch x n
+ * = 2^20, a non-default stream.
+ * The host twin (csrc/host_g1_recover.hpp g1_recover_each_host; plain loops, the one-column routine of g1_recover_host called once per column with that
+ * column's set, z and z' by direct products; no HIP call, no lock, re-entrant) has the same refusals, the same canonical outputs, the same report and the
+ * same first_bad_out.  It is held to the scalar decoder on multiples of the generator and to bbgpu_host_g1_recover where the sets agree
+ * (tests/test_g1_recover_each_host.py). */
+#define BBGPU_G1_RECOVER_EACH_MAX_ROWS (1u << 12)
+typedef struct {
+    uint32_t consistent;       /* 1: every column b has coefficients [d, count_b) all at infinity (vacuous where count_b == d) */
+    uint32_t first_bad_column; /* smallest b that has not, else 0 */
+    uint64_t first_bad_coeff;  /* its smallest such index, else 0 */
+    uint64_t max_missing;      /* max over b of n - count_b */
+} bbgpu_g1_recover_each_report;
+int bbgpu_g1_recover_each(const uint32_t* row_offsets /* batch + 1, row_offsets[0] = 0, non-decreasing */,
+                          const uint32_t* row /* row_offsets[batch]: column b owns row[row_offsets[b] .. row_offsets[b + 1]), distinct, each < n, any order */,
+                          const uint64_t* points /* HOST, row_offsets[batch] x 8, in the order of `row` */, size_t n, size_t degree_bound, int batch,
+                          uint64_t* points_out /* HOST, batch x n x 8: ALL n points of every column, natural order */,
+                          uint64_t* first_bad_out /* HOST or NULL, batch: smallest index in [d, count_b) not at infinity, UINT64_MAX if none */,
+                          bbgpu_g1_recover_each_report* report, void* hip_stream);
+int bbgpu_host_g1_recover_each(const uint32_t* row_offsets, const uint32_t* row, const uint64_t* points, size_t n, size_t degree_bound, int batch,
+                               uint64_t* points_out, uint64_t* first_bad_out, bbgpu_g1_recover_each_report* report);
 
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
