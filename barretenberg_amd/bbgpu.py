@@ -73,7 +73,8 @@ C_ABI_SYMBOLS = [
     "bbgpu_kzg_open_cosets_setup_bounded", "bbgpu_host_kzg_open_cosets_bounded",
     "bbgpu_kzg_check_openings", "bbgpu_kzg_check_open_all", "bbgpu_host_kzg_check_openings_batch", "bbgpu_host_kzg_check_open_all",
     "bbgpu_kzg_check_last_timing", "bbgpu_kzg_check_cells", "bbgpu_kzg_check_open_cosets", "bbgpu_host_kzg_check_cells",
-    "bbgpu_host_kzg_check_open_cosets", "bbgpu_host_kzg_cells_key_check", "bbgpu_kzg_recover_cells", "bbgpu_host_kzg_recover_cells",
+    "bbgpu_host_kzg_check_open_cosets", "bbgpu_host_kzg_cells_key_check", "bbgpu_kzg_check_cells_layout", "bbgpu_kzg_check_open_cosets_layout",
+    "bbgpu_host_kzg_check_cells_layout", "bbgpu_host_kzg_check_open_cosets_layout", "bbgpu_kzg_recover_cells", "bbgpu_host_kzg_recover_cells",
     "bbgpu_kzg_recover_cells_each", "bbgpu_host_kzg_recover_cells_each",
     "bbgpu_g1_ntt", "bbgpu_host_g1_ntt", "bbgpu_g1_recover", "bbgpu_host_g1_recover", "bbgpu_g1_set_stage_mapping",
     "bbgpu_g1_recover_each", "bbgpu_host_g1_recover_each",
@@ -955,14 +956,14 @@ class BbGpu:
                      g2p, sdp, fl if flags is None else int(flags), C.byref(rep)))
         return rep.as_dict()
 
-    def _kzg_check_open_cosets(self, fn, commitments, values, proofs, n, coset, g1_head, g2_xl, batch, stride, seed, locate, flags):
+    def _kzg_check_open_cosets(self, fn, commitments, values, proofs, n, coset, g1_head, g2_xl, batch, stride, seed, locate, flags, max_batch=64):
         cs = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
         ps = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8)
         vs = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
         head = np.ascontiguousarray(g1_head, dtype=np.uint64).reshape(-1, 8)
         batch = cs.shape[0] if batch is None else int(batch)
         stride = int(n) if stride is None else int(stride)
-        if 1 <= batch <= 64 and 1 <= int(coset) <= 64 and int(n) >= 1 and (cs.shape[0] < batch or ps.shape[0] < batch * (int(n) // int(coset)) or
+        if 1 <= batch <= max_batch and 1 <= int(coset) <= 64 and int(n) >= 1 and (cs.shape[0] < batch or ps.shape[0] < batch * (int(n) // int(coset)) or
                                                                             vs.shape[0] < (batch - 1) * stride + int(n) or head.shape[0] < int(coset)):
             raise ValueError("kzg_check_open_cosets: batch %d of n = %d, coset %d at stride %d over %d commitments, %d values, %d proofs, %d head rows" %
                              (batch, n, coset, stride, cs.shape[0], vs.shape[0], ps.shape[0], head.shape[0]))
@@ -994,6 +995,31 @@ class BbGpu:
         """bbgpu_host_kzg_check_open_cosets: the same definition on the host; no GPU needed"""
         return self._kzg_check_open_cosets(self.lib.bbgpu_host_kzg_check_open_cosets, commitments, values, proofs, n, coset, g1_head, g2_xl, batch, stride,
                                            seed, locate, flags)
+
+    # ---- the same for a 2-D layout: up to 2^16 commitments per call (bbgpu_kzg_check_cells_layout, bbgpu_kzg_check_open_cosets_layout, the host twins) ----
+    MAX_LAYOUT_COMMITMENTS = 1 << 16
+
+    def kzg_check_cells_layout(self, commitments, which, cell, values, proofs, n, coset, g1_head, g2_xl, seed=None, locate=False, flags=None):
+        """bbgpu_kzg_check_cells_layout: kzg_check_cells over up to 2^16 commitments -- they are tested and converted on the GPU, the cells grouped by label
+        there once per call.  Same arguments, same report; up to 64 commitments the report is kzg_check_cells' field for field."""
+        return self._kzg_check_cells(self.lib.bbgpu_kzg_check_cells_layout, commitments, which, cell, values, proofs, n, coset, g1_head, g2_xl, seed, locate,
+                                     flags)
+
+    def host_kzg_check_cells_layout(self, commitments, which, cell, values, proofs, n, coset, g1_head, g2_xl, seed=None, locate=False, flags=None):
+        """bbgpu_host_kzg_check_cells_layout: the same definition on the host; no GPU needed"""
+        return self._kzg_check_cells(self.lib.bbgpu_host_kzg_check_cells_layout, commitments, which, cell, values, proofs, n, coset, g1_head, g2_xl, seed,
+                                     locate, flags)
+
+    def kzg_check_open_cosets_layout(self, commitments, values, proofs, n, coset, g1_head, g2_xl, batch=None, stride=None, seed=None, locate=False, flags=None):
+        """bbgpu_kzg_check_open_cosets_layout: kzg_check_open_cosets over a batch of up to 2^16 polynomials (batch x n <= 2^20)"""
+        return self._kzg_check_open_cosets(self.lib.bbgpu_kzg_check_open_cosets_layout, commitments, values, proofs, n, coset, g1_head, g2_xl, batch, stride,
+                                           seed, locate, flags, max_batch=self.MAX_LAYOUT_COMMITMENTS)
+
+    def host_kzg_check_open_cosets_layout(self, commitments, values, proofs, n, coset, g1_head, g2_xl, batch=None, stride=None, seed=None, locate=False,
+                                          flags=None):
+        """bbgpu_host_kzg_check_open_cosets_layout: the same definition on the host; no GPU needed"""
+        return self._kzg_check_open_cosets(self.lib.bbgpu_host_kzg_check_open_cosets_layout, commitments, values, proofs, n, coset, g1_head, g2_xl, batch,
+                                           stride, seed, locate, flags, max_batch=self.MAX_LAYOUT_COMMITMENTS)
 
     def host_kzg_cells_key_check(self, g1_head, coset, g2_x, g2_xl):
         """bbgpu_host_kzg_cells_key_check: is g2_xl = [x^coset] G2 for the x of g1_head (coset, 8) and g2_x?  One pairing product; host only -> bool"""

@@ -245,6 +245,25 @@ int kzg_cells_coefficients(const KzgCellsBuffers& B, size_t count, int log2n, in
                            hipStream_t st, float* ms = nullptr);
 // the scalars of the head of A over the cells [0, cells): d_out[c] for the S shared commitments, d_out[S + i] = -s_i on P_i
 int kzg_cells_fold(const KzgCellsBuffers& B, size_t cells, size_t S, int log2n, int log2l, uint64_t skip_mask, uint64_t* d_out, hipStream_t st);
+// The layout entries (bbgpu_kzg_check_cells_layout, bbgpu_kzg_check_open_cosets_layout): S <= 2^16 commitments tested and converted on the device, the
+// cells grouped by label once per call, the S commitment scalars by a fold over the lists.  which == null: the open-cosets form, label c is the cells
+// [c m, (c + 1) m) and nothing is grouped (cnt / off / poff / perm are not read).
+struct KzgLayoutBuffers {
+    const uint64_t* commitments; // S x 8 words as the caller gave them
+    const uint32_t* which;       // the count labels on the device (labelled form)
+    uint32_t* rows;              // the S rows of the commitments in the table of A
+    uint64_t* skip;              // ceil(S / 64) words: bit c set for a commitment at infinity
+    KzgFindings* find;           // bad_points: finite commitments off the curve; first_key: the smallest index among them
+    uint32_t *cnt, *off, *poff;  // S counters; S + 1 starts of the lists in perm; S + 1 first pieces
+    uint32_t* perm;              // the count cells, label by label
+    uint64_t* partial;           // kzg_layout_max_pieces x 4 words
+};
+constexpr size_t KZG_LAYOUT_PIECE = 1024; // cells per wave of the list fold: 16 per lane, the chain k_kzg_cells_fold runs over a range of KZG_FOLD_RANGE
+static_assert(KZG_LAYOUT_PIECE <= KZG_FOLD_RANGE && KZG_LAYOUT_PIECE % 64 == 0, "a piece is at most a range and whole waves");
+size_t kzg_layout_max_pieces(size_t count, size_t S, int log2m, bool cosets);
+int kzg_layout_group(const KzgLayoutBuffers& L, size_t count, size_t S, hipStream_t st, float* ms = nullptr);
+int kzg_layout_fold(const KzgLayoutBuffers& L, const uint64_t* d_term_rho, size_t cells, size_t count, size_t S, int log2m, uint64_t* d_out, hipStream_t st,
+                    float* ms = nullptr);
 
 // kzg_recover_cells.hip: the device parts of bbgpu_kzg_recover_cells that are neither a transform nor the batch inversion.  l = 2^log2l values per cell,
 // m = 2^(log2n - log2l) cells per polynomial, mu of them missing (d_missing: ascending; may be null when mu == 0).

@@ -3805,7 +3805,8 @@ int bbgpu_kzg_check_open_all(const uint64_t* commitments, const uint64_t* values
 // the call of bbgpu_(host_)kzg_check_cells and its argument verdict
 static int kzg_cells_labelled_call(host::KzgCellsCall* K, const uint64_t* commitments, size_t num_commitments, const uint32_t* which, const uint32_t* cell,
                                    const uint64_t* values, const uint64_t* proofs, size_t count, size_t n, size_t coset, const uint64_t* g1_head,
-                                   const uint64_t* g2_xl, int flags, const bbgpu_kzg_check_report* out)
+                                   const uint64_t* g2_xl, int flags, const bbgpu_kzg_check_report* out,
+                                   size_t max_commitments = BBGPU_KZG_CHECK_MAX_COMMITMENTS)
 {
     K->commitments = commitments;
     K->S = num_commitments;
@@ -3816,12 +3817,13 @@ static int kzg_cells_labelled_call(host::KzgCellsCall* K, const uint64_t* commit
     K->head = g1_head;
     K->count = count;
     char why[160];
-    if (int rc = host::kzg_cells_args(K, n, coset, 0, g2_xl, flags, out, why, sizeof why)) return kzg_check_refused(rc, why);
+    if (int rc = host::kzg_cells_args(K, n, coset, 0, g2_xl, flags, out, why, sizeof why, max_commitments)) return kzg_check_refused(rc, why);
     return BBGPU_OK;
 }
 // the same for bbgpu_(host_)kzg_check_open_cosets
 static int kzg_cells_open_cosets_call(host::KzgCellsCall* K, const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n,
-                                      size_t coset, int batch, const uint64_t* g1_head, const uint64_t* g2_xl, int flags, const bbgpu_kzg_check_report* out)
+                                      size_t coset, int batch, const uint64_t* g1_head, const uint64_t* g2_xl, int flags, const bbgpu_kzg_check_report* out,
+                                      size_t max_commitments = BBGPU_KZG_CHECK_MAX_COMMITMENTS)
 {
     K->commitments = commitments;
     K->values = values;
@@ -3830,7 +3832,7 @@ static int kzg_cells_open_cosets_call(host::KzgCellsCall* K, const uint64_t* com
     K->cosets = true;
     K->stride = stride;
     char why[160];
-    if (int rc = host::kzg_cells_args(K, n, coset, batch, g2_xl, flags, out, why, sizeof why)) return kzg_check_refused(rc, why);
+    if (int rc = host::kzg_cells_args(K, n, coset, batch, g2_xl, flags, out, why, sizeof why, max_commitments)) return kzg_check_refused(rc, why);
     return BBGPU_OK;
 }
 
@@ -3854,6 +3856,31 @@ int bbgpu_host_kzg_check_open_cosets(const uint64_t* commitments, const uint64_t
     if (int rc = call_seed("KZG check", seed, sd)) return rc;
     return host::kzg_cells_host(K, g2_xl, sd, flags, report);
 }
+// the layout twins: the same plain loops behind the cap of BBGPU_KZG_CHECK_MAX_LAYOUT_COMMITMENTS
+int bbgpu_host_kzg_check_cells_layout(const uint64_t* commitments, size_t num_commitments, const uint32_t* which, const uint32_t* cell, const uint64_t* values,
+                                      const uint64_t* proofs, size_t count, size_t n, size_t coset, const uint64_t* g1_head, const uint64_t g2_xl[16],
+                                      const uint64_t seed[4], int flags, bbgpu_kzg_check_report* report)
+{
+    host::KzgCellsCall K;
+    if (int rc = kzg_cells_labelled_call(&K, commitments, num_commitments, which, cell, values, proofs, count, n, coset, g1_head, g2_xl, flags, report,
+                                         BBGPU_KZG_CHECK_MAX_LAYOUT_COMMITMENTS))
+        return rc;
+    uint64_t sd[4];
+    if (int rc = call_seed("KZG check", seed, sd)) return rc;
+    return host::kzg_cells_host(K, g2_xl, sd, flags, report);
+}
+int bbgpu_host_kzg_check_open_cosets_layout(const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n, size_t coset,
+                                            int batch, const uint64_t* g1_head, const uint64_t g2_xl[16], const uint64_t seed[4], int flags,
+                                            bbgpu_kzg_check_report* report)
+{
+    host::KzgCellsCall K;
+    if (int rc = kzg_cells_open_cosets_call(&K, commitments, values, stride, proofs, n, coset, batch, g1_head, g2_xl, flags, report,
+                                            BBGPU_KZG_CHECK_MAX_LAYOUT_COMMITMENTS))
+        return rc;
+    uint64_t sd[4];
+    if (int rc = call_seed("KZG check", seed, sd)) return rc;
+    return host::kzg_cells_host(K, g2_xl, sd, flags, report);
+}
 int bbgpu_host_kzg_cells_key_check(const uint64_t* g1_head, size_t coset, const uint64_t g2_x[16], const uint64_t g2_xl[16], int* ok)
 {
     if (coset < 1 || coset > BBGPU_KZG_OPEN_COSETS_MAX_COSET || (coset & (coset - 1)))
@@ -3865,7 +3892,10 @@ int bbgpu_host_kzg_cells_key_check(const uint64_t* g1_head, size_t coset, const 
 
 // Both forms behind their argument checks, modelled on kzg_check_run: upload, k_kzg_cells and k_kzg_cell_coefficients, ONE synchronisation before the
 // findings are read, then per round the fold and two tickets over the rows as transient tables, and the shared host tail with [x^l] G2.
-static int kzg_cells_run(const host::KzgCellsCall& K, const uint64_t g2_xl[16], const uint64_t* seed, int flags, bbgpu_kzg_check_report* out)
+// layout: the entries of up to 2^16 commitments.  Their commitments go up as they are and k_kzg_layout_commitments makes the rows, the skip bits and the
+// findings; the table starts with P_0 .. P_(l-1), which still arrive with the head, and the commitments follow -- a sum does not depend on the order of
+// its rows --; k_kzg_cells_fold keeps the l slots of P_i and the grouped fold writes the S scalars behind them.
+static int kzg_cells_run(const host::KzgCellsCall& K, const uint64_t g2_xl[16], const uint64_t* seed, int flags, bbgpu_kzg_check_report* out, bool layout = false)
 {
     if (int rc = ensure_init()) return rc;
     StageClock& clock = g_kzg_check_clock;
@@ -3875,15 +3905,22 @@ static int kzg_cells_run(const host::KzgCellsCall& K, const uint64_t g2_xl[16], 
     host::kzg_report_init(out, K.count, sd);
     const size_t count = K.count, S = K.S, l = K.l(), n = (size_t)1 << K.log2n, H = K.rows_head(), na = H + count;
     const size_t nvals = K.cosets ? S * n : count * l;
+    const size_t HC = layout ? l : H, row_c = layout ? l : 0, row_p = layout ? 0 : S; // the rows the head brings; the first commitment's and P_0's row
     // one staging buffer, every part at a multiple of 64 bytes: the proofs | the values | the labels | the cell indices | the roots | the findings | the
     // rows: the shared commitments, P_0 .. P_(l-1), then the cells' | the scalars of A, of B | rho | the terms | the partial sums of the fold.  The roots,
-    // the findings and the head of the rows are neighbours because they arrive in one copy.
+    // the findings and the head of the rows are neighbours because they arrive in one copy.  The layout entries add: the commitments' raw words | the skip
+    // bits | and in the labelled form the S counters | the S + 1 starts of the lists | the S + 1 first pieces | the permutation | then the sums of the
+    // pieces: 76 bytes per commitment and 4 + 1/32 per cell (labelled), 64 + 1/8 + 32 ceil(m / 1024) per commitment (open-cosets).
     auto up64 = [](size_t b) { return (b + 63) & ~(size_t)63; };
     constexpr size_t ROOTS = (KZG_CELLS_MAX_COSET * sizeof(Limbs9) + 63) / 64 * 64;
     const size_t o_values = count * 64, o_which = o_values + nvals * 32, o_cell = o_which + (K.cosets ? 0 : up64(count * 4)),
                  o_roots = o_cell + (K.cosets ? 0 : up64(count * 4)), o_find = o_roots + ROOTS, o_rows = o_find + 64, o_scal_a = o_rows + na * 64,
                  o_scal_b = o_scal_a + up64(na * 32), o_rho = o_scal_b + up64(count * 32), o_term = o_rho + count * 32, o_partial = o_term + count * l * 32,
-                 total = o_partial + H * KZG_FOLD_MAX_RANGES * 32;
+                 o_commit = o_partial + HC * KZG_FOLD_MAX_RANGES * 32, o_skip = o_commit + (layout ? S * 64 : 0),
+                 o_cnt = o_skip + (layout ? up64((S + 63) / 64 * 8) : 0), o_off = o_cnt + (layout && !K.cosets ? up64(S * 4) : 0),
+                 o_poff = o_off + (layout && !K.cosets ? up64((S + 1) * 4) : 0), o_perm = o_poff + (layout && !K.cosets ? up64((S + 1) * 4) : 0),
+                 o_pieces = o_perm + (layout && !K.cosets ? up64(count * 4) : 0),
+                 total = o_pieces + (layout ? kzg_layout_max_pieces(count, S, K.log2n - K.log2l, K.cosets) * 32 : 0);
     static_assert(ROOTS + 64 + (BBGPU_KZG_CHECK_MAX_COMMITMENTS + KZG_CELLS_MAX_COSET) * 64 <= Context::HOST_CHUNK, "the head fits one pinned staging buffer");
     static_assert(KZG_CELLS_MAX_COSET == BBGPU_KZG_OPEN_COSETS_MAX_COSET, "one bound on the coset size");
     if (int rc = grow(&ctx().d_kzg_check, &ctx().kzg_check_cap, total)) return rc;
@@ -3903,6 +3940,17 @@ static int kzg_cells_run(const host::KzgCellsCall& K, const uint64_t g2_xl[16], 
     B.partial = reinterpret_cast<uint64_t*>(base + o_partial);
     B.roots = reinterpret_cast<const uint32_t*>(base + o_roots);
     B.find = reinterpret_cast<KzgFindings*>(base + o_find);
+    KzgLayoutBuffers L{};
+    L.commitments = reinterpret_cast<const uint64_t*>(base + o_commit);
+    L.which = B.which;
+    L.rows = d_rows + row_c * 16;
+    L.skip = reinterpret_cast<uint64_t*>(base + o_skip);
+    L.find = B.find + 1; // the second 16 bytes of the findings' 64
+    L.cnt = reinterpret_cast<uint32_t*>(base + o_cnt);
+    L.off = reinterpret_cast<uint32_t*>(base + o_off);
+    L.poff = reinterpret_cast<uint32_t*>(base + o_poff);
+    L.perm = reinterpret_cast<uint32_t*>(base + o_perm);
+    L.partial = reinterpret_cast<uint64_t*>(base + o_pieces);
     const hipStream_t st = ctx().stream;
     if (int rc = host_to_device(base, K.proofs, count * 64, st)) return rc;
     if (K.cosets && K.stride != n) { // the transform of each polynomial, without the caller's padding
@@ -3916,42 +3964,59 @@ static int kzg_cells_run(const host::KzgCellsCall& K, const uint64_t g2_xl[16], 
         if (int rc = host_to_device(base + o_cell, K.cell, count * 4, st)) return rc;
     }
     uint64_t shared_bad = 0, shared_first = UINT64_MAX, skip_mask = 0;
-    for (size_t c = 0; c < S; c++)
-        if (!host::g1_words_acceptable(K.commitments + 8 * c) && shared_bad++ == 0) shared_first = c;
+    if (layout) {
+        if (int rc = host_to_device(base + o_commit, K.commitments, S * 64, st)) return rc;
+    } else {
+        for (size_t c = 0; c < S; c++)
+            if (!host::g1_words_acceptable(K.commitments + 8 * c) && shared_bad++ == 0) shared_first = c;
+    }
     const host::KzgCellsDomain D = host::kzg_cells_domain(K.log2n, K.log2l);
     // the head, built in one of the library's pinned staging buffers (host_to_device's ring), sent in one copy: the roots zeta^-e, the findings' start, the
     // shared rows, P_0 .. P_(l-1)
-    const int rc_head = stage_head(base + o_roots, ROOTS + 64 + H * 64, st, [&](uint8_t* h) {
+    const int rc_head = stage_head(base + o_roots, ROOTS + 64 + HC * 64, st, [&](uint8_t* h) {
         memset(h, 0, ROOTS + 64);
         for (size_t e = 0; e < l; e++) {
             const Limbs9 z = host::limbs_m261(D.zeta_inv[e]);
             memcpy(h + e * sizeof(Limbs9), z.d, sizeof(Limbs9));
         }
-        const KzgFindings init = { 0, ~0ull };
-        memcpy(h + ROOTS, &init, sizeof init);
+        const KzgFindings init[2] = { { 0, ~0ull }, { 0, ~0ull } }; // the cells', the layout entries' commitments'
+        memcpy(h + ROOTS, init, sizeof init);
         uint64_t* rows = reinterpret_cast<uint64_t*>(h + ROOTS + 64);
-        for (size_t c = 0; c < S; c++)
+        for (size_t c = 0; c < S && !layout; c++)
             if (kzg_check_resident_row(K.commitments + 8 * c, rows + 8 * c)) skip_mask |= 1ull << c;
-        for (size_t i = 0; i < l; i++) (void)kzg_check_resident_row(K.head + 8 * i, rows + 8 * (S + i)); // finite: the arguments were checked
+        for (size_t i = 0; i < l; i++) (void)kzg_check_resident_row(K.head + 8 * i, rows + 8 * (row_p + i)); // finite: the arguments were checked
     });
     if (rc_head) return rc_head;
+    float group_ms = 0, fold_ms = 0;
+    bool fold_timed = false;
+    if (layout)
+        if (int rc = kzg_layout_group(L, count, S, st, ctx().timing ? &group_ms : nullptr)) return rc;
     if (int rc = kzg_cells_claims(B, sd, count, K.log2n, K.log2l, host::limbs_m261(D.psi).d, st)) return rc;
     float coef_ms = 0;
     if (int rc = kzg_cells_coefficients(B, count, K.log2n, K.log2l, host::limbs_m261(D.omega_inv).d,
                                         host::limbs_m261(host::fr_mul(D.l_inv, host::fr_from_u64(32))).d, st, ctx().timing ? &coef_ms : nullptr))
         return rc;
-    KzgFindings got = { 0, ~0ull };
-    HIPCHK(d2h_async(&got, B.find, sizeof got, st));
+    KzgFindings got[2] = { { 0, ~0ull }, { 0, ~0ull } };
+    HIPCHK(d2h_async(got, B.find, layout ? sizeof got : sizeof got[0], st));
     HIPCHK(hipStreamSynchronize(st));
     clock.first_sync();
-    host::kzg_report_findings(out, shared_bad, shared_first, got.bad_points, got.first_key);
+    if (layout) {
+        shared_bad = got[1].bad_points;
+        shared_first = got[1].first_key;
+    }
+    host::kzg_report_findings(out, shared_bad, shared_first, got[0].bad_points, got[0].first_key);
     int rc_tail = BBGPU_OK;
     if (!out->bad_points) {
         // A and B: two tickets in flight over ONE transient table, A from its head, B from the first cell on
         const SrsEntry ea = transient_table(d_rows, na), eb = transient_table(d_rows + H * 16, count);
         rc_tail = host::kzg_check_tail(out, g2_xl, flags, [&](size_t m, uint64_t* a12, uint64_t* b12) -> int {
             const double t_fold = now_ms();
-            if (int rc = kzg_cells_fold(B, m, S, K.log2n, K.log2l, skip_mask, d_scal_a, st)) return rc;
+            if (int rc = kzg_cells_fold(B, m, layout ? 0 : S, K.log2n, K.log2l, skip_mask, d_scal_a, st)) return rc;
+            if (layout) {
+                float* ms = ctx().timing && !fold_timed ? &fold_ms : nullptr; // the first round's
+                fold_timed = true;
+                if (int rc = kzg_layout_fold(L, B.term_rho, m, count, S, K.log2n - K.log2l, d_scal_a + row_c * 4, st, ms)) return rc;
+            }
             HIPCHK(hipStreamSynchronize(st)); // the tickets run on their slots' own streams
             const double t_msm = now_ms();
             clock.ms[2] += t_msm - t_fold;
@@ -3962,8 +4027,12 @@ static int kzg_cells_run(const host::KzgCellsCall& K, const uint64_t g2_xl[16], 
     }
     clock.end();
     if (ctx().timing) { // bbgpu_last_timing: index 0 the coefficient kernel alone (set last: the tickets' waits write their own)
-        ctx().last.count = 1;
+        ctx().last.count = layout ? 3 : 1;
         ctx().last.ms[0] = coef_ms;
+        if (layout) { // 1: k_kzg_layout_commitments and the grouping; 2: the grouped fold of the first round
+            ctx().last.ms[1] = group_ms;
+            ctx().last.ms[2] = fold_ms;
+        }
     }
     return rc_tail;
 }
@@ -3986,6 +4055,30 @@ int bbgpu_kzg_check_open_cosets(const uint64_t* commitments, const uint64_t* val
     host::KzgCellsCall K;
     if (int rc = kzg_cells_open_cosets_call(&K, commitments, values, stride, proofs, n, coset, batch, g1_head, g2_xl, flags, report)) return rc;
     return kzg_cells_run(K, g2_xl, seed, flags, report);
+}
+int bbgpu_kzg_check_cells_layout(const uint64_t* commitments, size_t num_commitments, const uint32_t* which, const uint32_t* cell, const uint64_t* values,
+                                 const uint64_t* proofs, size_t count, size_t n, size_t coset, const uint64_t* g1_head, const uint64_t g2_xl[16],
+                                 const uint64_t seed[4], int flags, bbgpu_kzg_check_report* report)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    host::KzgCellsCall K;
+    if (int rc = kzg_cells_labelled_call(&K, commitments, num_commitments, which, cell, values, proofs, count, n, coset, g1_head, g2_xl, flags, report,
+                                         BBGPU_KZG_CHECK_MAX_LAYOUT_COMMITMENTS))
+        return rc;
+    return kzg_cells_run(K, g2_xl, seed, flags, report, true);
+}
+int bbgpu_kzg_check_open_cosets_layout(const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n, size_t coset,
+                                       int batch, const uint64_t* g1_head, const uint64_t g2_xl[16], const uint64_t seed[4], int flags,
+                                       bbgpu_kzg_check_report* report)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    host::KzgCellsCall K;
+    if (int rc = kzg_cells_open_cosets_call(&K, commitments, values, stride, proofs, n, coset, batch, g1_head, g2_xl, flags, report,
+                                            BBGPU_KZG_CHECK_MAX_LAYOUT_COMMITMENTS))
+        return rc;
+    return kzg_cells_run(K, g2_xl, seed, flags, report, true);
 }
 int bbgpu_kzg_check_last_timing(double ms_out[5])
 {

@@ -1,5 +1,5 @@
-// host_kzg_check_cells.hpp -- the check of KZG CELL proofs by ONE pairing product (include/bbgpu.h: bbgpu_kzg_check_cells, bbgpu_kzg_check_open_cosets, their
-// host twins and bbgpu_host_kzg_cells_key_check): the forms a call takes, the argument verdicts, the twins' own loops.  The findings, the report and the
+// host_kzg_check_cells.hpp -- the check of KZG CELL proofs by ONE pairing product (include/bbgpu.h: bbgpu_kzg_check_cells, bbgpu_kzg_check_open_cosets, the
+// _layout entries of up to 2^16 commitments, the host twins of all four and bbgpu_host_kzg_cells_key_check): the forms a call takes, the argument verdicts, the twins' own loops.  The findings, the report and the
 // pairing tail with its bisection are host_kzg_check_batch.hpp's, with [x^l] G2 in the pairing.  Notation: l = coset, m = n / l, omega the root of the
 // size-n domain, psi = omega^l, zeta = omega^m.  Cell k of f holds v_j = f(omega^(k + m j)), j < l; its proof pi_k has f = q_k (X^l - psi^k) + r_k with
 //   r_k = sum_i a_i X^i,   a_i = omega^(-k i) l^-1 sum_j v_j zeta^(-i j)          (a size-l inverse transform, then a twist)
@@ -64,17 +64,17 @@ static inline bool kzg_cells_domain_ok(size_t n, size_t coset, int* log2n, int* 
 }
 
 // The argument verdicts every entry gives before anything else, sizes first: 0, or the code with `why` written.  K is filled in by the caller except
-// log2n / log2l; batch is read in the open-cosets form only.
+// log2n / log2l; batch is read in the open-cosets form only.  max_commitments: 64, or 2^16 for the layout entries -- the one thing they change here.
 static inline int kzg_cells_args(KzgCellsCall* K, size_t n, size_t coset, int batch, const uint64_t* g2_xl, int flags, const bbgpu_kzg_check_report* out,
-                                 char* why, size_t cap)
+                                 char* why, size_t cap, size_t max_commitments = BBGPU_KZG_CHECK_MAX_COMMITMENTS)
 {
     if (!kzg_cells_domain_ok(n, coset, &K->log2n, &K->log2l)) {
         snprintf(why, cap, "coset a power of two in 1 .. 64, n a power of two with 2 coset <= n <= 2^21 are taken");
         return BBGPU_ERR_SIZE;
     }
     if (K->cosets) {
-        if (batch < 1 || batch > BBGPU_KZG_CHECK_MAX_COMMITMENTS || K->stride < n || (size_t)batch * n > BBGPU_KZG_CHECK_MAX_CLAIMS) {
-            snprintf(why, cap, "1 <= batch <= 64, stride >= n and batch x n <= 2^20 are taken");
+        if (batch < 1 || (size_t)batch > max_commitments || K->stride < n || (size_t)batch * n > BBGPU_KZG_CHECK_MAX_CLAIMS) {
+            snprintf(why, cap, "1 <= batch <= %zu, stride >= n and batch x n <= 2^20 are taken", max_commitments);
             return BBGPU_ERR_SIZE;
         }
         K->S = (size_t)batch;
@@ -93,8 +93,8 @@ static inline int kzg_cells_args(KzgCellsCall* K, size_t n, size_t coset, int ba
         return BBGPU_ERR_ARG;
     }
     if (!K->cosets) {
-        if (K->S < 1 || K->S > BBGPU_KZG_CHECK_MAX_COMMITMENTS) {
-            snprintf(why, cap, "1 .. 64 shared commitments are taken");
+        if (K->S < 1 || K->S > max_commitments) {
+            snprintf(why, cap, "1 .. %zu shared commitments are taken", max_commitments);
             return BBGPU_ERR_ARG;
         }
         for (size_t t = 0; t < K->count; t++)

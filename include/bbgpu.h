@@ -1158,6 +1158,71 @@ int bbgpu_host_kzg_check_open_cosets(const uint64_t* commitments, const uint64_t
 /* *ok = 1 when g2_xl is [x^coset] G2 for the x of g1_head and g2_x; host only, no lock, re-entrant */
 int bbgpu_host_kzg_cells_key_check(const uint64_t* g1_head /* coset x 8 */, size_t coset, const uint64_t g2_x[16], const uint64_t g2_xl[16], int* ok);
 
+/* ---- do the cell proofs of a 2-D LAYOUT hold?  (up to 2^16 commitments in one call, still one pairing check) ------
+ * bbgpu_g1_ntt, bbgpu_g1_recover and bbgpu_g1_recover_each give the commitments of the extension rows in columns of up to 2^16 points; the two entries
+ * above take 64 commitments, so a layout of 256 data rows and 256 extension rows was at least eight calls, the cells partitioned by label on the host,
+ * each call with its own two MSMs and its own pairing.  These entries are the SAME definition -- rho_t, A, B, the pairing product, the findings,
+ * BBGPU_KZG_CHECK_LOCATE, the seed rules, the report: everything the block above says -- with two differences:
+ *   num_commitments, and batch in the open-cosets form, may be 1 .. BBGPU_KZG_CHECK_MAX_LAYOUT_COMMITMENTS = 2^16 (the tallest column the group entries
+ *   write); every other bound stays: count <= 2^20, count x coset <= 2^20, n <= 2^21, n / coset >= 2, coset a power of two <= 64, stride >= n,
+ *   batch x n <= 2^20.
+ * Refusals come before a device is bound with the codes of the block above (BBGPU_ERR_SIZE for batch, BBGPU_ERR_ARG for num_commitments or a label >=
+ * num_commitments).  The entries above, their limit of 64 and their refusals are unchanged.  For num_commitments <= 64 and the same seed the report
+ * equals that of the entry above field for field, a and b included: every sum is an exact canonical residue, whatever order it is added in.
+ * The device path (csrc/kzg_check_cells.hip; the driver is kzg_cells_run in capi.hip with its `layout` argument, which shares k_kzg_cells,
+ * k_kzg_cell_coefficients, the tail, the two tickets over one transient table and the staging buffer with the entries above):
+ *   k_kzg_layout_commitments  the commitments go up AS THEY ARE, one more upload, and are tested and converted on the device: one thread per commitment,
+ *                             the device function k_kzg_cells applies to a proof (the curve test, the resident row).  A finite point off the curve is a
+ *                             finding keyed by its own index; a wave writes the infinity flags of its 64 commitments as one word of a skip array.  The
+ *                             findings come down with the cells' in the one read-back; the host runs no loop over the commitments (the O(count) label
+ *                             validation stays).
+ *   the grouping              labelled form, once per call: k_kzg_layout_hist (integer atomics on S counters, one per wave and label), k_kzg_layout_scan (one workgroup: the starts
+ *                             of the S lists and of their pieces), k_kzg_layout_scatter (a permutation of the cells, label by label).  O(count + S).
+ *   the grouped fold          per round: k_kzg_layout_pieces gives ONE WAVE a piece of at most 1024 cells of one list -- 16 canonical additions per lane
+ *                             and six shuffle steps whatever the labels are, the chain k_kzg_cells_fold runs over a range of 4096 cells; a prefix m for
+ *                             LOCATE is the test t < m while summing --, k_kzg_layout_finish gives one wave a label and sums its pieces, writing zero for
+ *                             a commitment at infinity.  In the open-cosets form label c is the cells [c m, (c + 1) m): no grouping, the same two kernels.
+ *                             O(count + S) loads and memory; no per-commitment-per-range partial buffer.
+ *   the l slots of P_i        k_kzg_cells_fold as above, called with no commitment slot.  The table of A is P_0 .. P_(l-1), the S commitments, then pi_t:
+ *                             the head -- roots, the findings' start, P_0 .. P_(l-1) -- still arrives in one copy.
+ * No scratch in any of them; VGPR counts in the file's header block.  Staging beyond the entries above: 76 bytes per commitment and 4 per cell in the
+ * labelled form, 64 per commitment and 32 per 1024 cells in the open-cosets form, and 32 bytes per piece; counted in staging_bytes.  A warm call of 256
+ * cells at l = 4 passes no allocation, ONE read-back, seven launch checks (k_kzg_cells, k_kzg_cell_coefficients, the commitments with the grouping,
+ * k_kzg_cells_fold, the grouped fold, one per MSM ticket) and six uploads in the labelled form (proofs, values, labels, cell indices, commitments, the
+ * head), four in the open-cosets form; with a finding three launch checks.  After any failure no MSM ticket is outstanding.  With bbgpu_set_timing,
+ * bbgpu_last_timing gives device times from events: index 0 the coefficient kernel, 1 the commitments and the grouping, 2 the grouped fold of the
+ * first round.
+ * The host twins are the plain loops of csrc/host_kzg_check_cells.hpp with the cap as a parameter: one text for both families.
+ * Cost on one MI355X (tools/kzg_check_layout_bench.py, profiles/kzg_check_layout.txt; wall ms per call, medians of 9 in alternating pairs in one process,
+ * with the spread -- the full range -- of each leg; the box is shared and two legs of the run hold one outlier each, which the spread shows):
+ *   (rows, n, l) = (512, 2^11, 64), 2^20 values, open-cosets form: ONE layout call 3.01 ms (spread 0.07) against 16.26 ms for the eight calls of 64 rows
+ *   (fastest 16.15): 0.19 of the time.
+ *   (64, 2^14, 64) against the one bbgpu_kzg_check_open_cosets call it replaces: 3.008 ms (spread 0.135) against 2.994 (fastest 2.976, one call of 6.7 ms):
+ *   +0.014 ms, no slower beyond the spread of either leg (the run before, without outliers: +0.013 ms with spreads 0.063 and 0.031).
+ *   the labelled form, 2^14 cells of 64 values under 512 labels: uniform labels 3.073 ms, every cell on ONE label 3.088 (spread 0.066; the uniform leg
+ *   holds one call of 4.5 ms, its other calls lie within 0.05): +0.015 ms, within the spread.  From device events: the commitments kernel with the grouping
+ *   0.027 ms uniform and 0.021 ms on one label, the grouped fold 0.013 and 0.024 ms.
+ * The grouping was changed ONCE after a measurement: with one atomic per cell the one-label call took 3.451 ms against 3.072 (+0.379 ms, NOT within the
+ * spreads of 0.05-0.07), the grouping 0.387 ms against 0.017 -- 2^14 atomics on one counter in the histogram and again in the scatter.  The lanes of a wave
+ * that hold the same label now meet first (ballots, at most 64 trips, no memory access) and their leader issues one atomic: a counter takes one atomic per
+ * wave that holds its label.  That costs the uniform call 0.010 ms.  At l = 1 a call of 2^20 cells on one label still puts 2^14 atomics on one counter.
+ * NOT timed: the rounds of LOCATE, num_commitments above 512, the labelled form above 2^14 cells, l < 64, the host twins. */
+#define BBGPU_KZG_CHECK_MAX_LAYOUT_COMMITMENTS (1u << 16)
+int bbgpu_kzg_check_cells_layout(const uint64_t* commitments /* num_commitments x 8 */, size_t num_commitments, const uint32_t* which /* count */,
+                                 const uint32_t* cell /* count, each < n / coset */, const uint64_t* values /* count x coset x 4 */,
+                                 const uint64_t* proofs /* count x 8 */, size_t count, size_t n, size_t coset, const uint64_t* g1_head /* coset x 8 */,
+                                 const uint64_t g2_xl[16], const uint64_t seed[4] /* NULL: OS randomness */, int flags, bbgpu_kzg_check_report* report);
+int bbgpu_kzg_check_open_cosets_layout(const uint64_t* commitments /* batch x 8 */, const uint64_t* values /* batch x stride x 4: the size-n transforms */,
+                                       size_t stride, const uint64_t* proofs /* batch x (n / coset) x 8 */, size_t n, size_t coset, int batch,
+                                       const uint64_t* g1_head /* coset x 8 */, const uint64_t g2_xl[16], const uint64_t seed[4], int flags,
+                                       bbgpu_kzg_check_report* report);
+int bbgpu_host_kzg_check_cells_layout(const uint64_t* commitments, size_t num_commitments, const uint32_t* which, const uint32_t* cell,
+                                      const uint64_t* values, const uint64_t* proofs, size_t count, size_t n, size_t coset, const uint64_t* g1_head,
+                                      const uint64_t g2_xl[16], const uint64_t seed[4], int flags, bbgpu_kzg_check_report* report);
+int bbgpu_host_kzg_check_open_cosets_layout(const uint64_t* commitments, const uint64_t* values, size_t stride, const uint64_t* proofs, size_t n,
+                                            size_t coset, int batch, const uint64_t* g1_head, const uint64_t g2_xl[16], const uint64_t seed[4], int flags,
+                                            bbgpu_kzg_check_report* report);
+
 /* ---- recover polynomials from a subset of their cells  (the vanishing polynomial of the missing cells on the GPU, three transforms, a verdict) ------
  * bbgpu_kzg_open_cosets_device makes the n / l cell proofs of a polynomial and bbgpu_kzg_check_cells / bbgpu_kzg_check_open_cosets check them.  A node that
  * samples cells holds SOME cells of each polynomial, usually the same columns of many rows, and must rebuild the polynomials: the missing cells, and then
