@@ -78,6 +78,7 @@ C_ABI_SYMBOLS = [
     "bbgpu_kzg_recover_cells_each", "bbgpu_host_kzg_recover_cells_each",
     "bbgpu_g1_ntt", "bbgpu_host_g1_ntt", "bbgpu_g1_recover", "bbgpu_host_g1_recover", "bbgpu_g1_set_stage_mapping",
     "bbgpu_g1_recover_each", "bbgpu_host_g1_recover_each",
+    "bbgpu_fr_ntt_columns_device", "bbgpu_host_fr_ntt_columns", "bbgpu_fr_recover_columns_device", "bbgpu_host_fr_recover_columns",
 ]
 ERR_WITNESS = -6  # BBGPU_ERR_WITNESS: the opt-in witness check of the resident prover refused a witness
 
@@ -220,6 +221,15 @@ class KzgRecoverEachReport(C.Structure):
 class G1RecoverEachReport(C.Structure):
     """bbgpu_g1_recover_each_report (include/bbgpu.h)"""
     NONE = 0xFFFFFFFFFFFFFFFF  # an entry of first_bad when the column has none
+    _fields_ = [("consistent", C.c_uint32), ("first_bad_column", C.c_uint32), ("first_bad_coeff", C.c_uint64), ("max_missing", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class FrRecoverColumnsReport(C.Structure):
+    """bbgpu_fr_recover_columns_report (include/bbgpu.h)"""
+    NONE = 0xFFFFFFFF  # an entry of first_bad when the column has none
     _fields_ = [("consistent", C.c_uint32), ("first_bad_column", C.c_uint32), ("first_bad_coeff", C.c_uint64), ("max_missing", C.c_uint64)]
 
     def as_dict(self):
@@ -872,6 +882,62 @@ class BbGpu:
         self._chk(self.lib.bbgpu_host_g1_recover_each(offsets.ctypes.data_as(u32p), row.ctypes.data_as(u32p), _ptr(flat), int(n), int(degree_bound), batch,
                                                       _ptr(out), _ptr(first_bad), C.byref(rep)))
         return out, rep.as_dict(), first_bad
+
+    # ---- transforms and the erasure decoder down the columns of a row-major matrix  (bbgpu_fr_ntt_columns_device, bbgpu_fr_recover_columns_device, twins) ----
+    def fr_ntt_columns_device(self, d_ptr, rows, width, kind="fft", stride=None, stream=None):
+        """bbgpu_fr_ntt_columns_device: every column of the resident rows x stride matrix at d_ptr (row r at element r * stride, columns [0, width))
+        transformed in place, "fft" or "ifft" """
+        self.lib.bbgpu_fr_ntt_columns_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]
+        self._chk(self.lib.bbgpu_fr_ntt_columns_device(d_ptr, int(rows), int(width), int(width) if stride is None else int(stride),
+                                                       NTT_KINDS[kind] if isinstance(kind, str) else int(kind), stream or 0))
+
+    def host_fr_ntt_columns(self, mem, rows, width, kind="fft", stride=None):
+        """bbgpu_host_fr_ntt_columns: the same on a host matrix `mem` ((rows * stride, 4) uint64, or None for the refusal of a null pointer), in place"""
+        self.lib.bbgpu_host_fr_ntt_columns.argtypes = [u64p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+        self._chk(self.lib.bbgpu_host_fr_ntt_columns(_ptr(mem) if mem is not None else None, int(rows), int(width), int(width) if stride is None else int(stride),
+                                                     NTT_KINDS[kind] if isinstance(kind, str) else int(kind)))
+        return mem
+
+    @staticmethod
+    def _fr_columns_sets(row_sets, offsets, sets):
+        lists = [np.ascontiguousarray(r, dtype=np.uint32).reshape(-1) for r in row_sets]
+        if offsets is None:
+            offsets = np.zeros(len(lists) + 1, dtype=np.uint32)
+            offsets[1:] = np.cumsum([r.shape[0] for r in lists])
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        row = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.uint32)]))  # never empty
+        return offsets, row, len(lists) if sets is None else int(sets)
+
+    def fr_recover_columns_device(self, row_sets, d_ptr, rows, width, degree_bound, stride=None, want_first_bad=True, stream=None, offsets=None, sets=None):
+        """bbgpu_fr_recover_columns_device: the rows that column j's set (row_sets[j mod len(row_sets)]: the PRESENT rows, distinct, any order) misses are
+        written into the resident matrix at d_ptr, every column a codeword of degree < degree_bound -> (the report as a dict, (width,) uint32 first_bad
+        -- FrRecoverColumnsReport.NONE where a column has none -- or None without want_first_bad).  offsets / sets: the raw arguments in place of the ones
+        derived from the lists (the refusals)."""
+        offsets, row, sets = self._fr_columns_sets(row_sets, offsets, sets)
+        rep, first_bad = FrRecoverColumnsReport(), np.zeros(max(int(width), 1), dtype=np.uint32) if want_first_bad else None
+        u32p = C.POINTER(C.c_uint32)
+        self.lib.bbgpu_fr_recover_columns_device.argtypes = [u32p, u32p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, u32p,
+                                                             C.POINTER(FrRecoverColumnsReport), C.c_void_p]
+        self._chk(self.lib.bbgpu_fr_recover_columns_device(offsets.ctypes.data_as(u32p), row.ctypes.data_as(u32p), sets, d_ptr, int(rows), int(width),
+                                                           int(width) if stride is None else int(stride), int(degree_bound),
+                                                           first_bad.ctypes.data_as(u32p) if want_first_bad else None, C.byref(rep), stream or 0))
+        return rep.as_dict(), first_bad
+
+    def host_fr_recover_columns(self, row_sets, mem, rows, width, degree_bound, stride=None, want_first_bad=True, offsets=None, sets=None, first_bad=None,
+                                report=None):
+        """bbgpu_host_fr_recover_columns: the same on a host matrix `mem` ((rows * stride, 4) uint64), in place.  first_bad / report: the caller's own
+        buffers (so that a refusal can be seen to leave them alone)."""
+        offsets, row, sets = self._fr_columns_sets(row_sets, offsets, sets)
+        rep = FrRecoverColumnsReport() if report is None else report
+        if first_bad is None and want_first_bad:
+            first_bad = np.zeros(max(int(width), 1), dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self.lib.bbgpu_host_fr_recover_columns.argtypes = [u32p, u32p, C.c_int, u64p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, u32p,
+                                                           C.POINTER(FrRecoverColumnsReport)]
+        self._chk(self.lib.bbgpu_host_fr_recover_columns(offsets.ctypes.data_as(u32p), row.ctypes.data_as(u32p), sets, _ptr(mem) if mem is not None else None,
+                                                         int(rows), int(width), int(width) if stride is None else int(stride), int(degree_bound),
+                                                         first_bad.ctypes.data_as(u32p) if first_bad is not None else None, C.byref(rep)))
+        return rep.as_dict(), first_bad
 
     def g1_set_stage_mapping(self, mapping):
         """bbgpu_g1_set_stage_mapping: 0 the library's choice of stage kernel for g1_ntt and g1_recover, 1 k_lagrange_stage and 2 k_g1_stage_cols for every

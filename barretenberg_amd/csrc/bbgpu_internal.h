@@ -322,6 +322,18 @@ int g1_cols_finish(const uint32_t* d_scratch, uint32_t* d_out, int log2n, int ba
 // missing rows ascending at d_missing[d_moff[b] .. d_moff[b + 1]), fewer than n of them; d_roots: n x 9 words of workspace
 int g1_cols_vanish(const uint32_t* d_moff, const uint32_t* d_missing, int log2n, int batch, uint32_t* d_roots, uint64_t* d_z, uint64_t* d_zc, hipStream_t st);
 
+// fr_columns.hip: the device parts of bbgpu_fr_ntt_columns_device and bbgpu_fr_recover_columns_device.  A resident row-major matrix of rows = 2^log2rows
+// rows (<= 2^11), row r at element r stride_elems; a codeword is a column.  Nothing here synchronises.  d_tabs: fr_cols_table_words(log2rows, entries)
+// words, entries = sets x rows for the decoder (d_z, d_zci: z as a Montgomery-261 multiplier and the batch inversion of z' x 2^-5, the forms of
+// g1_cols_vanish, `entries` elements each) and 0 for the transform (d_z, d_zci not read).  d_moff: the sets + 1 offsets of g1_cols_vanish; d_present: bit
+// s rows + i set where set s lists row i; d_bad: null, or width words that receive every column's smallest index in [d, count_s), ~0 for none; d_find: two
+// words the caller starts at ~0: the smallest (column << 32 | index) in [d, count_s) and in [count_s, rows).
+size_t fr_cols_table_words(int log2rows, size_t entries);
+int fr_cols_tables(const uint64_t* d_z, const uint64_t* d_zci, size_t entries, int log2rows, uint32_t* d_tabs, hipStream_t st);
+int fr_cols_transform(uint64_t* d_rows, size_t width, size_t stride_elems, int log2rows, bool inverse, const uint32_t* d_tabs, hipStream_t st);
+int fr_cols_decode(uint64_t* d_rows, size_t width, size_t stride_elems, int log2rows, int sets, size_t degree_bound, const uint32_t* d_tabs,
+                   const uint32_t* d_moff, const uint32_t* d_present, uint32_t* d_bad, unsigned long long* d_find, hipStream_t st);
+
 // capi.hip: the caller's host buffers cross the link through the library's OWN pinned buffers (see host_to_device)
 int host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st);
 int device_to_host_sync(void* h_dst, const void* d_src, size_t bytes, hipStream_t st, bool* touched = nullptr); // *touched: h_dst may have been written (even on failure)

@@ -40,6 +40,7 @@
 #include "host_kzg_recover_cells.hpp"
 #include "host_kzg_recover_each.hpp"
 #include "host_g1_recover.hpp"
+#include "host_fr_columns.hpp"
 #include "host_plonk_verify.hpp"
 #include "multi_plan.hpp"
 #include "poly.h"
@@ -4578,6 +4579,126 @@ int bbgpu_g1_recover_each(const uint32_t* row_offsets, const uint32_t* row, cons
         if (int rc = ev.ms(3, 4, &ctx().last.ms[2])) return rc;
         if (int rc = ev.ms(4, 5, &ctx().last.ms[3])) return rc;
     }
+    return BBGPU_OK;
+}
+
+/* ---- transforms and the erasure decoder down the columns of a resident matrix (host_fr_columns.hpp, fr_columns.hip) ---- */
+int bbgpu_host_fr_ntt_columns(uint64_t* rows_mem, size_t rows, size_t width, size_t stride_elems, int kind)
+{
+    int lg;
+    char why[320];
+    if (int rc = host::fr_ntt_columns_verdict("host fr_ntt_columns", rows_mem, rows, width, stride_elems, kind, &lg, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    host::fr_ntt_columns_host(rows_mem, lg, width, stride_elems, kind);
+    return BBGPU_OK;
+}
+
+int bbgpu_fr_ntt_columns_device(uint64_t* d_rows, size_t rows, size_t width, size_t stride_elems, int kind, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    int lg;
+    char why[320];
+    if (int rc = host::fr_ntt_columns_verdict("fr_ntt_columns", d_rows, rows, width, stride_elems, kind, &lg, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (int rc = ensure_init()) return rc;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    DevBuf tabs; // the twiddles (the shift tables beside them are not read)
+    HIPCHK(dev_malloc(&tabs.p, fr_cols_table_words(lg, 0) * 4));
+    if (int rc = fr_cols_tables(nullptr, nullptr, 0, lg, tabs.as<uint32_t>(), st)) return rc;
+    if (int rc = fr_cols_transform(d_rows, width, stride_elems, lg, kind == BBGPU_IFFT, tabs.as<uint32_t>(), st)) return rc;
+    HIPCHK(hipStreamSynchronize(st)); // the tables go when this returns
+    return BBGPU_OK;
+}
+
+int bbgpu_host_fr_recover_columns(const uint32_t* set_offsets, const uint32_t* row, int sets, uint64_t* rows_mem, size_t rows, size_t width, size_t stride_elems,
+                                  size_t degree_bound, uint32_t* first_bad_out, bbgpu_fr_recover_columns_report* report)
+{
+    host::FrColumnsShape S;
+    char why[320];
+    int rc = host::fr_recover_columns_verdict("host fr_recover_columns", set_offsets, row, sets, rows_mem, rows, width, stride_elems, degree_bound, report, &S, why,
+                                              sizeof why);
+    if (rc == BBGPU_OK) rc = host::fr_recover_columns_host(S, set_offsets, row, rows_mem, degree_bound, first_bad_out, report, why, sizeof why);
+    if (rc) set_error("%s", why);
+    return rc;
+}
+
+int bbgpu_fr_recover_columns_device(const uint32_t* set_offsets, const uint32_t* row, int sets, uint64_t* d_rows, size_t rows, size_t width, size_t stride_elems,
+                                    size_t degree_bound, uint32_t* first_bad_out, bbgpu_fr_recover_columns_report* report, void* hip_stream)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    // argument errors before a device is bound
+    host::FrColumnsShape S;
+    char why[320];
+    if (int rc = host::fr_recover_columns_verdict("fr_recover_columns", set_offsets, row, sets, d_rows, rows, width, stride_elems, degree_bound, report, &S, why,
+                                                  sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    if (int rc = ensure_init()) return rc;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const int lg = S.log2rows;
+    const size_t entries = (size_t)sets * rows, gone = S.missing.size(), mask_words = (entries + 31) / 32;
+    StageEvents<3> ev; // the stage boundaries of bbgpu_last_timing
+    if (int rc = ev.create(ctx().timing != 0)) return rc;
+    // the offsets of the missing rows, the missing rows of all sets and the bits of the present ones, in one array | z, z', the tables and the roots | the
+    // call's two findings | every column's finding, if the caller wants them
+    DevBuf lists, zt, find, bad;
+    const size_t list_words = (size_t)sets + 1 + gone + mask_words, tab_words = fr_cols_table_words(lg, entries);
+    HIPCHK(dev_malloc(&lists.p, list_words * 4));
+    HIPCHK(dev_malloc(&zt.p, 2 * entries * 32 + tab_words * 4 + rows * sizeof(Limbs9)));
+    HIPCHK(dev_malloc(&find.p, 2 * sizeof(unsigned long long)));
+    if (first_bad_out) HIPCHK(dev_malloc(&bad.p, width * 4));
+    uint32_t *d_moff = lists.as<uint32_t>(), *d_missing = d_moff + sets + 1, *d_present = d_missing + gone;
+    uint64_t *d_z = zt.as<uint64_t>(), *d_zc = d_z + 4 * entries;
+    uint32_t *d_tabs = reinterpret_cast<uint32_t*>(d_zc + 4 * entries), *d_roots = d_tabs + tab_words;
+    std::vector<uint32_t> all(list_words, 0);
+    std::copy(S.moff.begin(), S.moff.end(), all.begin());
+    std::copy(S.missing.begin(), S.missing.end(), all.begin() + sets + 1);
+    for (int s = 0; s < sets; s++)
+        for (uint32_t t = set_offsets[s]; t < set_offsets[s + 1]; t++) {
+            const size_t bit = (size_t)s * rows + row[t];
+            all[(size_t)sets + 1 + gone + bit / 32] |= 1u << (bit % 32);
+        }
+    unsigned long long keys[2] = { ~0ull, ~0ull };
+    if (int rc = host_to_device(lists.p, all.data(), list_words * 4, st)) return rc;
+    if (int rc = host_to_device(find.p, keys, sizeof keys, st)) return rc;
+    if (int rc = ev.mark(0, st)) return rc;
+    if (int rc = g1_cols_vanish(d_moff, d_missing, lg, sets, d_roots, d_z, d_zc, st)) return rc;
+    if (int rc = bbgpu_fr_batch_invert_device(d_zc, entries, hip_stream)) return rc; // z' is never zero: g^rows != 1
+    if (int rc = fr_cols_tables(d_z, d_zc, entries, lg, d_tabs, st)) return rc;
+    if (int rc = ev.mark(1, st)) return rc;
+    if (int rc = fr_cols_decode(d_rows, width, stride_elems, lg, sets, degree_bound, d_tabs, d_moff, d_present, bad.as<uint32_t>(), find.as<unsigned long long>(), st))
+        return rc;
+    if (int rc = ev.mark(2, st)) return rc;
+    if (int rc = device_to_host_sync(keys, find.p, sizeof keys, st)) return rc;
+    // the verdict into locals first: nothing of the caller's host memory is written before the last copy has succeeded
+    bbgpu_fr_recover_columns_report rep;
+    const size_t bad_column = keys[0] == ~0ull ? width : (size_t)(keys[0] >> 32), bug_column = keys[1] == ~0ull ? width : (size_t)(keys[1] >> 32);
+    if (int rc = host::fr_recover_columns_report_of("fr_recover_columns", width, bad_column, keys[0] & 0xffffffffull, bug_column, keys[1] & 0xffffffffull,
+                                                    S.max_missing, &rep, why, sizeof why)) {
+        set_error("%s", why);
+        return rc;
+    }
+    std::vector<uint32_t> per_column;
+    if (first_bad_out) {
+        per_column.resize(width);
+        if (int rc = device_to_host_sync(per_column.data(), bad.p, width * 4, st)) return rc;
+    }
+    if (ev.on) { // bbgpu_last_timing: 0 the roots, the vanishing values, their inversion and the tables, 1 the decode kernel
+        float ms[2];
+        if (int rc = ev.ms(0, 1, &ms[0])) return rc;
+        if (int rc = ev.ms(1, 2, &ms[1])) return rc;
+        ctx().last.count = 2;
+        ctx().last.ms[0] = ms[0];
+        ctx().last.ms[1] = ms[1];
+    }
+    *report = rep;
+    if (first_bad_out) std::copy(per_column.begin(), per_column.end(), first_bad_out);
     return BBGPU_OK;
 }
 

@@ -1559,6 +1559,107 @@ int bbgpu_g1_recover_each(const uint32_t* row_offsets /* batch + 1, row_offsets[
 int bbgpu_host_g1_recover_each(const uint32_t* row_offsets, const uint32_t* row, const uint64_t* points, size_t n, size_t degree_bound, int batch,
                                uint64_t* points_out, uint64_t* first_bad_out, bbgpu_g1_recover_each_report* report);
 
+/* ---- transform and recover the DATA of a 2-D layout down its columns  (a tile of whole columns decoded in LDS: one read, one write) ------
+ * The blocks above work along a row on field elements (bbgpu_kzg_recover_cells, _each) and down a column on points (bbgpu_g1_ntt, bbgpu_g1_recover,
+ * _each).  These entries are the fourth quadrant: down a column, on field elements.  A layout has k rows (polynomials), Reed-Solomon-extended column-wise
+ * to rows = 2 k over the size-`rows` domain; a producer needs the extension rows' values, a sampler that holds enough rows of a column rebuilds the rest.
+ * The matrix is DEVICE-resident and row-major: row r starts at element r * stride_elems, column j < width of row r is the 4-word element at (r *
+ * stride_elems + j) * 4, in the reference's memory format (Montgomery-256); any representative below 2^256 is accepted, everything written is canonical.
+ * Elements at [width, stride_elems) of every row are neither read nor written.  A codeword is a COLUMN: `rows` values, strided by the row length.
+ * bbgpu_fr_ntt_columns_device transforms every column in place, natural order in and out, with rho = fr_root_of_unity(log2 rows) -- the root of bbgpu_ntt
+ * and bbgpu_g1_ntt --, the inverse scaled by rows^-1.
+ * bbgpu_fr_recover_columns_device: column j uses row set j mod sets.  Set s lists count_s = set_offsets[s + 1] - set_offsets[s] distinct PRESENT rows,
+ * count_s >= d, and misses the mu_s = rows - count_s rows K_s.  sets = 1 is the whole-row case (a producer extending k rows, a node that holds complete
+ * rows); sets = n / l is a sampler's: in a row, cell c holds entries c, c + m, c + 2 m, ... (m = n / l), so column j belongs to cell column j mod m.  Any
+ * sets in 1..width is taken, a power of two or not.  Per column it is the decode the bbgpu_g1_recover block states, on scalars, with the z_(s,i) and
+ * z'_(s,i) of bbgpu_g1_recover_each (set s in the place of column b):
+ *   E_i = z_(s,i) v_i on the present rows, 0 on the missing ones;  P = IFFT(E);  Q = FFT(g^j P_j);  Q_i /= z'_(s,i);  D' = IFFT(Q);  D_j = g^-j D'_j;  V = FFT(D)
+ * ONLY THE MISSING ROWS of each column are written, with V_i.  Present rows stay bit for bit as they were, also in an inconsistent column and also where
+ * they held a non-canonical representative: the matrix is the caller's data and a finding must not destroy it.  A set that misses nothing is legal (z =
+ * z' = 1): its columns get a verdict and no store.  The verdict is exact and is "a finding, not an error": a column is consistent iff coefficients [d,
+ * count_s) of its D are zero (vacuous where count_s == d); the return value is BBGPU_OK, the report names the smallest inconsistent column and its smallest
+ * such index, first_bad_out (if given) receives that index for every column, UINT32_MAX for none.  A nonzero coefficient in [count_s, rows) cannot come
+ * from any input: BBGPU_ERR_HIP with a text of its own.  Report and first_bad_out are written only after the last copy has succeeded.
+ * THE MAP IS LINEAR ACROSS ROWS: every output row is a fixed combination of the present rows, the same in every column of a set.  So the rows may equally
+ * hold COEFFICIENTS: with sets = 1, recovering and then transforming each row equals transforming each row and then recovering, and the recovered rows of
+ * coefficients are what bbgpu_kzg_open_cosets_device and an MSM read (tests/test_fr_columns_host.py, tests/test_gpu_fr_columns.py: commitments of the
+ * recovered rows equal bbgpu_g1_recover's).
+ * Refused before a device is bound, outputs untouched -- BBGPU_ERR_SIZE: rows not a power of two, rows < 2, rows > BBGPU_FR_COLUMNS_MAX_ROWS = 2^11 (the
+ * NTT's sub-transform size: a whole column fits the 2048 LDS elements of a tile), width < 1, stride_elems < width, rows * width > 2^28, sets outside
+ * 1..width, sets * rows > 2^20 (the size of the z tables, the cap bbgpu_g1_recover_each has), degree_bound outside 1..rows, for some s count_s <
+ * degree_bound or count_s > rows; BBGPU_ERR_ARG: a null pointer (first_bad_out may be NULL), set_offsets[0] != 0 or offsets that decrease, a row index >=
+ * rows, a row listed twice in one set -- bbgpu_last_error() names the first offender by set and position --, any kind but BBGPU_FFT and BBGPU_IFFT.  Not
+ * here: rows > 2^11 (two passes), per-column degree bounds, G2.  Both device entries run on context 0 under the library mutex and return after the stream
+ * has drained.
+ * WHAT A FAILED CALL MAY HAVE WRITTEN: the decode is one launch, so a call that fails after it (a read-back, the BBGPU_ERR_HIP verdict above) may have
+ * written MISSING rows, all or part; a call that fails before it has written nothing.  Present rows and the elements at [width, stride_elems) are never
+ * written, by a failed call or any other (tests/test_gpu_fr_columns.py tests exactly that).  Report and first_bad_out stay as they were.
+ * The kernels (csrc/fr_columns.hip; new HIP, the reference has no counterpart).  z and z' come from k_g1_roots and k_g1_vanish_cols (csrc/g1_recover.hip,
+ * unchanged, "column" read as "set") and the batch inversion of csrc/poly.hip.
+ *   k_fr_cols_tables  once per call: twiddles rho^k and rho^-k (rows / 2 each), g^j and g^-j (rows each), rows^-1 z_(s,i) and rows^-1 / z'_(s,i) (sets x
+ *                     rows each) as Montgomery-261 MULTIPLIERS in 12-word entries -- field factors for the products below, not the plain integers a
+ *                     ladder takes (k_g1_scalars); rows^-1 is folded into the two tables that meet an inverse transform, as there
+ *   k_fr_cols_decode  the hot kernel.  A workgroup of 512 lanes owns a tile of C = 2048 / rows consecutive columns x all rows -- 2048 elements, nine limb
+ *                     planes of 2048 words, 72 KiB of LDS, limb-major with the column fastest -- clipped at the end of the matrix (width need be no
+ *                     multiple of C and no power of two).  Row segments of C x 32 bytes are read contiguously; missing rows are not read, their slots
+ *                     start at zero.  Then everything happens in LDS: the scaling by rows^-1 z at the load, four radix-2 transforms with the three
+ *                     pointwise passes between them, and the per-column verdict -- a zero test on the exact-limb product D_j for j >= d, the smallest
+ *                     index per column by an LDS minimum that only a nonzero coefficient issues: an honest call issues no atomic, in LDS or in memory.
+ *                     Then the store of the missing rows, canonical.  ONE read of the present elements and ONE write of the missing ones per call, no
+ *                     scratch matrix.  No pass permutes: the inverse transforms run decimation in frequency (natural in, bit-reversed out), the forward
+ *                     ones decimation in time (bit-reversed in, natural out), and the pointwise passes index their tables by bitrev.  Bank behaviour
+ *                     (stated per access in the file): load, store and pointwise passes conflict-free; a stage of half h conflict-free where h C >= 64 and
+ *                     2-way in the log2(64 / C) stages below that.  From rows = 1024 on a row segment (64 or 32 bytes) is narrower than a 128-byte line;
+ *                     that is accepted, and its cost against a wider tile was not measured.  Lazy value bounds as csrc/ntt.hip keeps them, proved in the
+ *                     file's header; decimation in frequency doubles the sums, so every fifth stage runs a reduce_value on half its outputs.
+ *                     bbgpu_fr_ntt_columns_device is the same kernel text with the scaling, the verdict and the row skipping compiled out: one transform
+ *                     (decimation in time behind a bit-reversed placement at the load), every row stored
+ * Work: 4 (log2 rows) / 2 + 4 field products per element, 22 at rows = 512; a 512 x 2^16 matrix is 7.4e8 products, 4.9 ms at the 150 Gmul/s of
+ * csrc/fe_mont_gfx950.h, against about 1 GiB of traffic.
+ * Resources (hipcc -Rpass-analysis=kernel-resource-usage, VGPRs / AGPRs / LDS bytes / waves per SIMD): k_fr_cols_tables 41 / 0 / 0 / 8,
+ * k_fr_cols_decode<true> 48 / 0 / 73,728 + 8 C dynamic (81,920 at C = 1024: two workgroups fill a CU's 163,840) / 8 by registers, 4 by LDS,
+ * k_fr_cols_decode<false> (the transform) 45 / 0 / 73,728 dynamic / 8 by registers, 4 by LDS; no scratch and no spill in any.
+ * A warm call with first_bad_out passes four allocations (the lists; z, z', the tables and the roots; the call's two findings; the per-column findings),
+ * two uploads (the lists -- the CSR of the missing rows and the bits of the present ones in one array --, the findings' start), two read-backs (the two
+ * findings, the per-column findings) and six launch checks (k_g1_roots with k_g1_vanish_cols; the inversion's two scans and its product; the tables; the
+ * decode); without first_bad_out three allocations and one read-back.  bbgpu_fr_ntt_columns_device passes one allocation (the twiddles), no copy and two
+ * launch checks.  Every site failed once through bbgpu_fault_inject returns BBGPU_ERR_HIP, leaves nothing the call allocated live, and the next call is
+ * bit-exact (tests/test_gpu_fr_columns.py).  With bbgpu_set_timing(1), bbgpu_last_timing(): index 0 the roots, the vanishing values, their inversion and
+ * the tables, index 1 the decode kernel.
+ * Cost on one MI355X (tools/fr_recover_columns_bench.py, profiles/fr_recover_columns.txt; medians of 9 alternating pairs in one process; half the rows
+ * missing, d = rows / 2): wall ms per call without first_bad_out; device ms of the decode kernel (bbgpu_last_timing index 1), beside (a) its own product count at 150 Gmul/s and (b)
+ * the device time of four bbgpu_ntt_device_batch calls over the same elements as 64 transforms of rows x width / 64 -- existing code with more stages per
+ * element, an upper reference and not a target.  (rows, width, sets): (512, 2^16, 1) 7.22 ms wall, decode 6.60 ms = 1.34 x (a) 4.92, 0.51 x (b) 13.00, the
+ * vanishing values and tables 0.41; (512, 2^16, 1024) 12.03 wall -- 2^19 z values: 2.08 ms on the device and the host's lists --, decode 6.67 = 1.35 x (a), 0.52 x
+ * (b) 12.89; (64, 2^16, 64) 0.94 wall, decode 0.600 = 1.34 x (a) 0.447, 0.50 x (b) 1.201; (8, 2^18, 1) 0.42 wall, decode 0.173 = 1.24 x (a) 0.140, 0.29 x (b)
+ * 0.589; (2048, 2^12, 1) 3.33 wall, decode 2.07 = 1.43 x (a) 1.45, 0.74 x (b) 2.79 -- the one shape whose WALL time is above the four transforms' (2.83): its
+ * vanishing values, 1024 roots walked by 2048 lanes, take 1.11 ms.  The decode runs at 0.70 to 0.81 of the multiplier's rate, the rest being the LDS round
+ * trip of every stage, the 2-way conflicts stated above (rows = 2048: six of eleven stages) and the narrow row segments from rows = 1024 on, none of which
+ * was measured on its own; nothing was tuned to these ratios.  NOT timed: the host twins, bbgpu_fr_ntt_columns_device on its own, rows >= 1024 against a
+ * wider tile (two passes), widths that are no multiple of C, sets that miss different numbers of rows in one call, a call with first_bad_out, a non-default
+ * stream.
+ * The host twins (csrc/host_fr_columns.hpp; plain loops: gather a column, z and z' by direct products once per set, the one-polynomial decoder of
+ * csrc/host_kzg_recover_cells.hpp over the radix-2 transform of csrc/host_fallback.hpp, scatter the missing rows; no HIP call, no lock, re-entrant) have
+ * the same refusals, the same canonical outputs, the same report and the same first_bad_out.  They are held to Lagrange interpolation over Python integers,
+ * to bbgpu_host_ntt column by column and to bbgpu_host_kzg_recover_cells_each at coset 1 (tests/test_fr_columns_host.py). */
+#define BBGPU_FR_COLUMNS_MAX_ROWS (1u << 11)
+int bbgpu_fr_ntt_columns_device(uint64_t* d_rows /* DEVICE, rows x stride_elems x 4 */, size_t rows, size_t width, size_t stride_elems,
+                                int kind /* BBGPU_FFT or BBGPU_IFFT */, void* hip_stream);
+int bbgpu_host_fr_ntt_columns(uint64_t* rows_mem /* HOST */, size_t rows, size_t width, size_t stride_elems, int kind);
+typedef struct {
+    uint32_t consistent;       /* 1: every column has coefficients [d, count_s) all zero (vacuous where count_s == d) */
+    uint32_t first_bad_column; /* smallest such column, else 0 */
+    uint64_t first_bad_coeff;  /* its smallest such index, else 0 */
+    uint64_t max_missing;      /* max over sets of rows - count_s */
+} bbgpu_fr_recover_columns_report;
+int bbgpu_fr_recover_columns_device(const uint32_t* set_offsets /* HOST, sets + 1, set_offsets[0] = 0, non-decreasing */,
+                                    const uint32_t* row /* HOST: set s owns row[set_offsets[s] .. set_offsets[s + 1]): its PRESENT rows, distinct, < rows, any order */,
+                                    int sets, uint64_t* d_rows /* DEVICE */, size_t rows, size_t width, size_t stride_elems, size_t degree_bound,
+                                    uint32_t* first_bad_out /* HOST or NULL, width entries: smallest nonzero index in [d, count_s), UINT32_MAX if none */,
+                                    bbgpu_fr_recover_columns_report* report, void* hip_stream);
+int bbgpu_host_fr_recover_columns(const uint32_t* set_offsets, const uint32_t* row, int sets, uint64_t* rows_mem /* HOST */, size_t rows, size_t width,
+                                  size_t stride_elems, size_t degree_bound, uint32_t* first_bad_out, bbgpu_fr_recover_columns_report* report);
+
 /* ---- is this proof valid?  (batches of proofs of one circuit: the per-proof scalars on the GPU, one pairing check) ------
  * waffle::Verifier::verify_proof (verifier.cpp:55-380) costs two pairings and a 20-point MSM per proof.  For a batch of proofs of ONE circuit the
  * per-proof part is what :55-355 computes -- six Keccak transcripts (challenge.hpp), the Lagrange evaluations (polynomial_arithmetic.cpp:594-626),
